@@ -39,6 +39,14 @@ One JSON line on stdout (rank 0).  Extra objects:
   newton_krylov one inner solve of that path: 30 Arnoldi steps of the device GMRES around the JVP
   roofline_iter whole-iteration algorithmic bytes (sum over every launch of the instrumented repeat) / un-instrumented wall time
   cpu_baseline  the CPU oracle (port of the reference path) timed on this box's host cores on a bounded sample
+
+--dump-outputs DIR writes what the last timed repeat returned to its caller (rank 0's meshes), so that two builds can be compared
+output for output on the same seeded inputs:
+  result        float32 (meshes x nodes, 10): the node states the solver returned, the rank's meshes concatenated in seed order
+                (f1m: the state after the K evaluations, mapped back to node order)
+  rel_trace     float64 (meshes, K + 1): the relative residual per iteration, padded as the solver pads it
+  abs_trace     float64 (meshes, K + 1): the same, absolute
+Above 64 MB in all, `result` keeps a fixed sample of its rows (seed 0) and `result_rows` holds their indices.
 """
 from __future__ import annotations
 
@@ -89,7 +97,35 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--dump-launch-log", default=None, help="write the instrumented repeat's launches (name, ms, algorithmic bytes) as JSON")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 64_000_000
+NPY_HEADER_BYTES = 256   # upper bound of one .npy header at these ranks
+
+
+def dump_outputs(dirname, arrays, cap=DUMP_CAP_BYTES):
+    """Write ``arrays`` (name -> float32 / float64 ndarray) as ``dirname/<name>.npy``; return name -> stored shape.  When they
+    would take more than ``cap`` bytes, the largest keeps a fixed sample of its rows (seed 0, in row order) and the sampled row
+    indices are written beside it as ``<name>_rows`` (float64, exact for any row count that fits in memory)."""
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes + NPY_HEADER_BYTES for a in arrays.values())
+    if total > cap:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        a = arrays[big]
+        keep = (cap - (total - a.nbytes) - NPY_HEADER_BYTES) // (a[0].nbytes + 8)   # a kept row and its index
+        if keep < 1:
+            raise ValueError(f"--dump-outputs: the outputs besides {big} already exceed {cap} bytes")
+        rows = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+        arrays = dict(arrays, **{big: a[rows], big + "_rows": rows.astype(np.float64)})
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def launch_ranks(args) -> int:
@@ -230,6 +266,10 @@ def main():
         barrier()
         assert bool(torch.isfinite(xp).all())
         gbs = K * b_f / elapsed / 1e9
+        dumped = {}
+        if args.dump_outputs and rank == 0:
+            dumped = {"dump_outputs": {"dir": args.dump_outputs, "arrays": dump_outputs(
+                args.dump_outputs, {"result": fmap.from_plan(xp).cpu().numpy()})}}
         print(json.dumps({
             "metric": "GNN-block edges/sec (E' x f evaluations/sec) on 1M-node Poisson mesh", "value": world * Ep * K / elapsed,
             "unit": "edges/s", "iters_per_sec": world * K / elapsed, "n_gpus": world, "steps": K, "warmup": W,
@@ -239,7 +279,7 @@ def main():
                        "nodes": N, "edges_nonself": Ep},
             "roofline": {"kernel": "k_f_tile", "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": gbs / HBM_PEAK_GBS, "traffic": None, "alg_bytes_per_launch": b_f,
-                         "avg_launch_us": 1e6 * elapsed / K}}))
+                         "avg_launch_us": 1e6 * elapsed / K}, **dumped}))
         return
 
     # ---- warmup: W untimed iterations (own solver object so its memory is released)
@@ -319,6 +359,11 @@ def main():
         "rel_residual_after_K": out["rel_trace"][K - 1], "setup_s": round(t_setup, 2),
         "broyden_state_bytes": solver.nbytes,
     }
+    if args.dump_outputs and rank == 0:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {
+            "result": torch.cat([o["result"] for o in outs]).cpu().numpy(),
+            "rel_trace": np.array([o["rel_trace"] for o in outs], dtype=np.float64),
+            "abs_trace": np.array([o["abs_trace"] for o in outs], dtype=np.float64)})}
 
     # ---- per-kernel durations and algorithmic bytes: the library's launch records of an instrumented repeat of the same K steps
     # (HIP events on the launch stream around every launch; bytes stated at the launch sites, csrc/common.h PROF_BYTES)

@@ -9,11 +9,14 @@ over 2000 graphs) on the reference's own 487-node gmsh mesh -- printed below, as
 import os
 import sys
 
-import numpy as np
-import torch
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from oracle import PINNED_CPU_ENV  # noqa: E402
+
+os.environ.update(PINNED_CPU_ENV)   # before torch starts: fp32 values that every host reproduces
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import psignn_oracle as orc  # noqa: E402
 from conftest import load_case  # noqa: E402

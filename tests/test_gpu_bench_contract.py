@@ -75,3 +75,21 @@ def test_bench_two_ranks_self_launched_on_one_card():
     assert d["n_gpus"] == 2 and d["ranks"]["world_size"] == 2 and d["ranks"]["backend"] == "gloo"
     assert d["config"]["meshes_per_gpu"] == 8 and "x16" in d["config"]["parallelism"]
     assert abs(d["value"] - 2 * 8 * d["config"]["edges_nonself"] * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs writes what the last timed repeat returned (node states of every mesh of the rank, residual traces), and two
+    runs with the same arguments start from the same seeded inputs and write the same arrays."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        line = _run("--workload", "batch50k", "--nodes", "2000", "--no-cpu-baseline", "--no-kernel-timing",
+                    "--dump-outputs", str(tmp_path / d))
+        runs.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("result", "rel_trace", "abs_trace")})
+        assert sorted(os.listdir(tmp_path / d)) == ["abs_trace.npy", "rel_trace.npy", "result.npy"]
+        assert line["dump_outputs"]["arrays"]["result"] == [8 * line["config"]["nodes"], 10]
+    a, b = runs
+    assert a["result"].dtype == np.float32 and a["rel_trace"].dtype == np.float64 and a["rel_trace"].shape == (8, 7)
+    assert np.all(np.isfinite(a["result"])) and a["rel_trace"][0, 5] == line["rel_residual_after_K"]
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n

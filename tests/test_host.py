@@ -292,3 +292,30 @@ def test_checkpoints_written_here_load_with_weights_only(tmp_path):
     ck = top.load_reference_checkpoint(str(tmp_path / "m.pt"))
     assert ck["hyperparameters"]["solver"] is solver.broyden
     assert set(ck["state_dict"]) == set(net.state_dict())
+
+
+def test_bench_dump_outputs_cap_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files, at most the cap in all; above it the largest array keeps a fixed
+    sample of its rows (the same rows on every run) and their indices are stored beside it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    res = np.arange(200_000 * 10, dtype=np.float32).reshape(200_000, 10)
+    tr = np.linspace(1.0, 1e-3, 2 * 51).reshape(2, 51)
+    shapes = bench.dump_outputs(str(tmp_path / "small"), {"result": res, "rel_trace": tr})
+    assert shapes == {"result": [200_000, 10], "rel_trace": [2, 51]}
+    assert np.array_equal(np.load(tmp_path / "small" / "result.npy"), res)
+    cap = 3_000_000
+    runs = [bench.dump_outputs(str(tmp_path / d), {"result": res, "rel_trace": tr}, cap=cap) for d in ("a", "b")]
+    assert runs[0] == runs[1] and runs[0]["result"][1] == 10 and 0 < runs[0]["result"][0] < 200_000
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["rel_trace.npy", "result.npy", "result_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= cap
+    rows = np.load(tmp_path / "a" / "result_rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "result_rows.npy"))
+    assert np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "result.npy"), res[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "rel_trace.npy"), tr)
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "c"), {"n": np.arange(3)})
