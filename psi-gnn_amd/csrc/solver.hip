@@ -45,7 +45,9 @@ struct Status {
 // in LDS, and after every 64 pairs (and after the last one) the block's first 64 threads add the four waves' values in a fixed
 // order and store ONE contiguous row segment: part[plane][block * ldp + j].  Same bench: 0.76.  The reduce kernels read a
 // column of that (blocks x pairs) matrix per pair -- 64-byte sectors from L2, a quarter as many elements as before.
-#define PARTA_LD 32            // row pitch of the folded sweep's partials: at most U2R_KB_MAX + 1 = 25 kept pairs
+#define PARTA_LD 32            // row pitch of the folded sweep's partials: one entry per kept pair, so at most 32 kept pairs --
+                               // U2R_KB_MAX + 1 = 25 in the register form, U2D_LDS_KMAX + 1 = 32 in the LDS form (k_sweep_u2d drops
+                               // entries past the pitch, and k_reduce_a_check would read the next block's row in their place)
 // (block_sum_col, vec_helpers.h: RB = 1 024 threads per reduce block was tried for the column reads:
 // k_reduce_cb 9.7 vs 8.3 us, k_reduce_a_check unchanged -- a block's time is the 64-byte sectors it pulls through ONE CU, not
 // its load rounds; what helps is more blocks per column, RA below.)
@@ -1160,15 +1162,17 @@ int psignn_f_tile_fused(const psignn_plan* p, const float* W, int nl, float* xbu
                         const float* h0, const float* prb, const float* nrm, float* part, hipStream_t st);
 
 #define U2R_KB_MAX 24
+#define U2D_LDS_KMAX (PARTA_LD - 1)   // LDS form: k - j_keep0 + 1 <= PARTA_LD partials per row
+static_assert(U2R_KB_MAX + 1 <= PARTA_LD, "the register fold's kept pairs must fit a partials row");
 __global__ __launch_bounds__(TB) void kb_sweep_u2d(const BatchDesc* __restrict__ descs, int k, int j_keep0, int par);
-// LDS form of the folded sweep: up to 38 pairs x 16 B x 256 threads of dynamic LDS; asked for once per device
+// LDS form of the folded sweep: up to U2D_LDS_KMAX = 31 pairs x 16 B x 256 threads of dynamic LDS; asked for once per device
 static bool u2d_lds_attr(int dev) {
   static int state[64] = {0};   // 0 unknown, 1 granted, -1 refused
   if (dev < 0 || dev >= 64) return false;
   if (state[dev] == 0) {
-    // (38 pairs x 16 B x 256 threads = 152 KB of dynamic LDS at most, next to the kernel's 512 B of static LDS: asking for the whole
+    // (31 pairs x 16 B x 256 threads = 124 KB of dynamic LDS at most, next to the kernel's 512 B of static LDS: asking for the whole
     // 160 KB as dynamic is refused -- and the solver then silently ran with the 64 KB limits; tests/test_gpu_solver_forms.py caught it)
-    const int want = 38 * TB * 16;
+    const int want = U2D_LDS_KMAX * TB * 16;
     const bool ok = hipFuncSetAttribute((const void*)k_sweep_u2d, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess &&
                     hipFuncSetAttribute((const void*)kb_sweep_u2d, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
     if (!ok) (void)hipGetLastError();
@@ -1234,7 +1238,8 @@ static int broyden_alloc(psignn_broyden* s) {
   // offsets do not reach.
   s->u2d_reg = cdiv(eff, (int64_t)4 * TB) >= 2048 && s->M < ((int64_t)1 << 30);
   if (const char* e = getenv("PSIGNN_U2D_FORM")) s->u2d_reg = ((e[0] == 'l' || e[0] == 'L') ? 0 : 1) && s->M < ((int64_t)1 << 30);
-  const int kmax_cap = s->u2d_reg ? U2R_KB_MAX : 38;
+  // (LDS form: at most U2D_LDS_KMAX, so that k - keep0 + 1 kept pairs -- all k + 1 up to u2d_kmax, u2d_keep + 1 beyond -- fit PARTA_LD)
+  const int kmax_cap = s->u2d_reg ? U2R_KB_MAX : U2D_LDS_KMAX;
   s->u2d_kmax = fold_ok ? 24 : 0;   // LDS form: 96 KB per block at most; 20 ... 32 measure alike at K = 50, K = 20 needs >= 19
   if (const char* e = getenv("PSIGNN_U2D_KMAX")) s->u2d_kmax = fold_ok ? std::max(0, std::min(kmax_cap, atoi(e))) : 0;
   s->u2d_keep = s->u2d_kmax > 0 ? 16 : 0;

@@ -28,10 +28,10 @@ import torch
 
 from conftest import load_weights, pkg, rel_l2
 from oracle import psignn_oracle as orc
+from recurrences import _check_iteration
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = float(np.finfo(np.float32).eps)
 K = 48          # iterations per solve: the window regime starts at k = 25 with the default limits
 ENVS = {
     "default": {},                                                  # fold in registers on long vectors / big shards, in LDS below; all pairs kept to k = 24, then a window of 16
@@ -41,6 +41,7 @@ ENVS = {
     "window_from_5": {"PSIGNN_U2D_FORM": "reg", "PSIGNN_U2D_KMAX": "4", "PSIGNN_U2D_KEEP": "2"},
     "no_fold": {"PSIGNN_U2D_KMAX": "0"},                            # plain three-sweep form
     "two_pass": {"PSIGNN_UVU": "0"},                                # dots + axpy + final
+    "lds_max": {"PSIGNN_U2D_FORM": "lds", "PSIGNN_U2D_KMAX": "31", "PSIGNN_U2D_KEEP": "31"},   # LDS fold at its limit: 32 partials = PARTA_LD
 }
 _KNOBS = ("PSIGNN_U2D_FORM", "PSIGNN_U2D_KEEP", "PSIGNN_U2D_KMAX", "PSIGNN_UVU", "PSIGNN_JGROUPS")
 
@@ -65,44 +66,6 @@ class _Recorder:
             self.DX.append(self.solver.pair(0, self.back(x), "update"))
         self.X.append(self.back(x).clone())
         return self.f(x)
-
-
-def _scale(ref64, plain32):
-    """Rounding scale of a formula: distance of its plain float32 evaluation from the float64 one (plus a floor of 4 ulp)."""
-    return float((plain32.double() - ref64).norm()) + 4 * EPS32 * float(ref64.norm())
-
-
-def _check_iteration(k, U32, V32, U, V, dx, dg, g, Vk, Uk, upd_next, where):
-    """Iteration with k stored pairs (all CPU tensors; U32, V32: (k, M) float32, U, V the same in float64): the device's V_k, U_k
-    and next update against the float64 recurrences on the device's own previous state."""
-    dxd, dgd, gd = dx.double(), dg.double(), g.double()
-    # vT = -dx + (U dx) V
-    vT = -dxd + (U @ dxd) @ V
-    vT32 = -dx + (U32 @ dx) @ V32
-    e = float((Vk.double() - vT).norm())
-    assert e <= 16 * _scale(vT, vT32), (where, "vT", e, _scale(vT, vT32))
-    # u = D1 / s,  D1 = dx + dg - (V dg) U,  s = vT . dg  (the device's own vT: the stages are checked one by one)
-    D1 = dxd + dgd - (V @ dgd) @ U
-    D1_32 = dx + dg - (V32 @ dg) @ U32
-    Ukd = Uk.double()
-    proj = float(D1 @ Ukd) / float(D1 @ D1)                   # U_k = proj * D1 + remainder, proj = 1 / s
-    rem = float((Ukd - proj * D1).norm())
-    tol_dir = 16 * _scale(D1, D1_32) / float(D1.norm())
-    assert rem <= tol_dir * float(Ukd.norm()), (where, "U_k direction", rem / float(Ukd.norm()), tol_dir)
-    s64 = float(Vk.double() @ dgd)
-    s_abs = float((Vk.double() * dgd).abs().sum())
-    assert abs(1.0 / proj - s64) <= 16 * EPS32 * s_abs + 4 * tol_dir * abs(s64), (where, "s = vT.dg", 1.0 / proj, s64, s_abs)
-    # update = D2 - u beta,  D2 = g - (V g) U,  beta = vT . g
-    D2 = gd - (V @ gd) @ U
-    D2_32 = g - (V32 @ g) @ U32
-    r = D2 - upd_next.double()
-    beta = float(r @ Ukd) / float(Ukd @ Ukd)
-    rem2 = float((r - beta * Ukd).norm())
-    tol2 = 16 * _scale(D2, D2_32) + 8 * EPS32 * (float(D2.norm()) + abs(beta) * float(Ukd.norm()))
-    assert rem2 <= tol2, (where, "update", rem2, tol2)
-    b64 = float(Vk.double() @ gd)
-    b_abs = float((Vk.double() * gd).abs().sum())
-    assert abs(beta - b64) <= 16 * EPS32 * b_abs + 4 * (tol2 / float(Ukd.norm())), (where, "beta = vT.g", beta, b64, b_abs)
 
 
 def _run_recorded(eng, f, x0, n_elems=None, plan=None, shard_elems=0, back=lambda t: t):
@@ -155,20 +118,26 @@ ITS = (0, 1, 4, 5, 7, 9, 16, 17, 23, 24, 25, 26, 33, 40, 46)      # default form
 ITS_SHORT = (1, 5, 6, 24, 25, 26, 46)                             # the other forms: window entry (k = 5 / 25), both sides of it
 
 
-@pytest.mark.parametrize("size", ["mid", "long"])
+SIZES = {"mid": (100000, False), "long": (100000, True), "ragged": (100001, False), "ragged_long": (100001, True)}
+
+
+@pytest.mark.parametrize("size", list(SIZES))
 def test_update_forms_satisfy_the_broyden_recurrences(size, dev, monkeypatch):
     """f(x) = c * x + b on (100 000, 10) through the generic-callable path (``psignn_broyden_ext_*``; M = 1 M elements).
     "mid": the natural shapes at this length (4 floats per lane, unsplit sweeps: the form of 100k-node meshes and of batched
     shards); "long": PSIGNN_JGROUPS=1 selects the long-vector shapes (16 floats per lane: the form of the 1M-node headline).
+    "ragged" / "ragged_long": the same on (100 001, 10), M = 1 000 010 = 10 (mod 16): a ragged quad in the register fold
+    ``k_sweep_u2r`` and a ragged lane in the 16-float three-sweep form (every check also runs on the last 4 096 elements).
     Each variant of the update: recurrences at iterations spanning the all-kept regime, the transition k = 24 -> 25 and the
     window regime; first iterations vs the CPU oracle; register and LDS forms of the fold bit-identical."""
     eng = pkg("engine")
-    c, b, x0 = _linear(100000, 0.995, dev)
+    N, jg = SIZES[size]
+    c, b, x0 = _linear(N, 0.995, dev)
     cd, bd, x0d = c.to(dev), b.to(dev), x0.to(dev)
     f = lambda x: cd * x + bd
     with torch.no_grad():
         ref = orc.broyden(lambda x: c * x + b, x0, threshold=10, eps=0.0)
-    base = {"PSIGNN_JGROUPS": "1"} if size == "long" else {}
+    base = {"PSIGNN_JGROUPS": "1"} if jg else {}
     outs = {}
     for name, env in ENVS.items():
         _setenv(monkeypatch, {**base, **env})
@@ -215,6 +184,88 @@ def test_long_vector_natural_size_and_closed_form(dev, monkeypatch):
     _setenv(monkeypatch, {})
 
 
+@pytest.mark.parametrize("N", [1, 25, 409])
+def test_update_on_vectors_shorter_than_a_block(N, dev, monkeypatch):
+    """M = 10 (one node: less than a quad of lanes), 250 (less than one wave), 4 090 (a partial last block, M % 4 = 2) through
+    the generic-callable path: the first iterations against the CPU oracle, the recurrences while k is well below M; and a
+    well-conditioned problem converges to the closed form b / (1 - c) and stays finite through 48 iterations -- more than M
+    for the first two, so the iteration spends its last ones at the rounding floor with vT.dg ~ 0 (the NaN / inf scrubbing of
+    solver.py:188-189)."""
+    eng, solver = pkg("engine"), pkg("utilities.solver")
+    _setenv(monkeypatch, {})
+    M = N * 10
+    c, b, x0 = _linear(N, 0.995, dev, seed=3)
+    cd, bd, x0d = c.to(dev), b.to(dev), x0.to(dev)
+    with torch.no_grad():
+        ref = orc.broyden(lambda x: c * x + b, x0, threshold=6, eps=0.0)
+    rec, sv, out = _run_recorded(eng, lambda x: cd * x + bd, x0d, n_elems=M)
+    np.testing.assert_allclose(out["rel_trace"][:4], ref["rel_trace"][:4], rtol=1e-3)
+    assert rel_l2(rec.X[3], ref["xest_trace"][3]) < 1e-5
+    _check_run(rec, sv, [i for i in (0, 1, 2, 3, 5, 9, 16, 24, 25, 26) if i <= M // 3], f"M={M}")
+    sv.close()
+    c, b, x0 = _linear(N, 0.5, dev, seed=4)
+    cd, bd, x0d = c.to(dev), b.to(dev), x0.to(dev)
+    o = solver.broyden(lambda x: cd * x + bd, x0d, threshold=K, eps=0.0, keep_trace=False)
+    # once g is exactly 0, vT.dg = 0 and u = D1 / 0 is inf, which the reference's scrubbing (x != x) leaves in place: its trace
+    # turns NaN from there on too (oracle.broyden on this problem at M = 4 090) -- but only after the iteration has converged,
+    # and the result (the lowest iterate) stays finite
+    tr = o["rel_trace"]
+    bad = next((i for i, v in enumerate(tr) if not np.isfinite(v)), len(tr))
+    assert bool(torch.isfinite(o["result"]).all()) and bad > 0 and min(tr[:bad]) < 2e-7, (M, bad, tr[:bad])
+    assert rel_l2(o["result"], b / (1 - c)) < 1e-6 and o["lowest"] < 2e-7, (M, rel_l2(o["result"], b / (1 - c)), o["lowest"])
+
+
+def _first_launch_iteration(log, name):
+    """Iteration (0-based) of the first launch of `name` in a launch log of one solve: one k_reduce_check per iteration,
+    launched before sweeps 2 and 3 of that iteration and after its sweep 1."""
+    it = 0
+    for n, _, _ in log:
+        if n == name:
+            return it
+        it += n == "k_reduce_check"
+    return None
+
+
+def test_lds_fold_keeps_at_most_a_row_of_partials(dev, monkeypatch):
+    """The LDS form of the folded sweep keeps at most PARTA_LD = 32 partials per row (pairs keep0 .. k): PSIGNN_U2D_KMAX /
+    _KEEP are capped at 31 there.  Asked for 38 / 36, the library used to keep up to 39 pairs and drop the partials past the
+    row pitch, and the next iteration read the neighbouring block's row in their place (wrong a_32 ... a_38, no fault).
+
+    At the limit (31 / 31) the fold supplies every a_j through iteration 32 (at 32 it keeps pairs 1 .. 32: exactly one row),
+    so the first sweep 1 runs in iteration 33 -- not earlier (a cap of 15, the fallback when the LDS attribute is refused,
+    would show here); the recurrences hold on both sides; a request of 38 / 36 is the same solve, bit for bit."""
+    eng, nat = pkg("engine"), pkg("_native")
+    c, b, x0 = _linear(100000, 0.995, dev, seed=5)
+    cd, bd, x0d = c.to(dev), b.to(dev), x0.to(dev)
+    f = lambda x: cd * x + bd
+    M = x0d.numel()
+    runs = {}
+    for name, env in (("lds_max", ENVS["lds_max"]), ("ask_38", {"PSIGNN_U2D_FORM": "lds", "PSIGNN_U2D_KMAX": "38", "PSIGNN_U2D_KEEP": "36"})):
+        _setenv(monkeypatch, env)
+        nat.prof_enable(True)
+        nat.prof_collect()
+        try:
+            rec, sv, out = _run_recorded(eng, f, x0d, n_elems=M)
+            nat.prof_collect(with_bytes=True)
+            log = nat.prof_launch_log()
+        finally:
+            nat.prof_enable(False)
+        assert _first_launch_iteration(log, "k_sweep_u1") == 33, (name, _first_launch_iteration(log, "k_sweep_u1"))
+        it = -1
+        for n, _, byts in log:       # the fold's stated bytes: k columns of U + update, dg, g, U_k, update (per iteration k)
+            it += n == "k_reduce_check"
+            if n == "k_sweep_u2d":
+                assert byts == (it + 5) * M * 4, (name, it, byts)
+        if name == "lds_max":
+            _check_run(rec, sv, (30, 31, 32, 33, 40, 46), "lds_max")
+        runs[name] = (out["rel_trace"], [rec.X[i] for i in (10, 32, 33, 34, 40, K)])
+        sv.close()
+        del rec
+    _setenv(monkeypatch, {})
+    (ra, xa), (rb, xb) = runs["lds_max"], runs["ask_38"]
+    assert ra == rb and all(torch.equal(p, q) for p, q in zip(xa, xb))
+
+
 def _mesh_map(n, seed, dev, sd, phase=0.0):
     data, eng = pkg("data"), pkg("engine")
     mesh = data.make_hex_problem(n, seed=seed, compute_sol=False, phase=phase)
@@ -245,7 +296,7 @@ def test_fused_device_solve_is_the_host_driven_solve(dev, monkeypatch):
     sv.close()
 
 
-@pytest.mark.parametrize("envname", ["reg", "lds", "window_from_5"])
+@pytest.mark.parametrize("envname", ["reg", "lds", "window_from_5", "lds_max"])
 def test_batched_shard_in_the_window_regime(envname, dev, monkeypatch):
     """``psignn_broyden_solve_batch`` through 48 iterations (window regime from k = 25; from k = 5 with the small limits) on a
     shard of 8 x 10 267-node meshes -- the shapes of BASELINE configs[3] (shard-sized reductions, 4 floats per lane): every mesh
