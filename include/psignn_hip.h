@@ -154,6 +154,18 @@ int psignn_lin_build(psignn_lin_t* lin, const float* d_weights, int n_layers, co
                      const float* d_normals_plan, void* stream);
 int psignn_lin_jvp(const psignn_lin_t* lin, const float* d_weights, int n_layers, const float* d_v_plan, float* d_out_plan,
                    void* stream);
+/* Transposed product out = J_f(h)^T w of the same stored linearisation (the exact transpose of psignn_lin_jvp's operator: same masks,
+ * same per-node records), w and out in PLAN order.  Dirichlet plans: one kernel per product; the first call after a build also fills
+ * a transposed copy of the slot masks, the first call of the handle also allocates it and a reverse slot map (psignn_lin_bytes then
+ * counts them; the build and psignn_lin_jvp do not use them).  A handle is single-stream: its build and its products (which may write
+ * the handle's transposed masks on the first call after a build) must be issued on one stream, or ordered by the caller.  A plan whose
+ * slots the reverse map cannot pair is refused (PSIGNN_EINVAL) rather than answered without some edges.  Mixed plans: the tiled VJP
+ * at the state kept by the build (no cheaper than psignn_f_vjp_p there; no stored form of the Neumann rows yet), d_work =
+ * psignn_f_workspace_floats(plan) floats of scratch; dirichlet plans ignore d_work.  Errors: not built, in-place, wrong depth.
+ * replaces: torch.autograd.grad(new_H, H, v) at one fixed state H*: the backward hook (dirichlet/psignn/model.py:210-223), the power
+ *           method (:437-452) and the Hutchinson estimate (:416-435); same product as psignn_f_vjp_p up to fp32 summation order. */
+int psignn_lin_vjp(const psignn_lin_t* lin, const float* d_weights, int n_layers, const float* d_w_plan, float* d_out_plan,
+                   float* d_work, void* stream);
 
 /* Vector-Jacobian product out = w^T (df/dh) at h (both families), as two gather passes over the plan's
  * CSR/CSC lists (no atomics).  d_normals: (N,2) for mixed plans, else NULL.
@@ -334,6 +346,13 @@ int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* d_weights, in
                                  const float* d_prb, const float* d_normals, const float* d_grad, double eps,
                                  int poll_every, float* d_result, psignn_solve_info_t* h_info,
                                  double* h_rel_trace, double* h_abs_trace, void* stream);
+/* The same adjoint solve with psignn_lin_vjp as the map: h* is the state `lin` was last built at (on the solver's plan; a
+ * linearisation of another plan is refused).  d_grad and d_result in the caller's numbering.
+ * replaces: the backward hook of DeepEquilibrium.forward (dirichlet/psignn/model.py:210-223), with the Jacobian at H* linearised once
+ *           instead of re-derived by autograd in every solver step. */
+int psignn_broyden_solve_adjoint_lin(psignn_broyden_t* s, const psignn_lin_t* lin, const float* d_weights, int n_layers,
+                                     const float* d_grad, double eps, int poll_every, float* d_result,
+                                     psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
 /* Copy iterate i (0..n_iter) of the last solve to d_dst (needs keep_trace). */
 int psignn_broyden_get_iterate(const psignn_broyden_t* s, int i, float* d_dst, void* stream);
 /* Copy stored rank-one pair j (0 .. pairs stored - 1) of the last solve to d_dst: which = 0 -> U_j, 1 -> V_j; which = 2 -> the current

@@ -58,6 +58,7 @@ SIGNATURES = {
     "psignn_lin_bytes": (C.c_size_t, [_P]),
     "psignn_lin_build": (_INT, [_P, _P, _INT, _P, _P, _P, _P]),
     "psignn_lin_jvp": (_INT, [_P, _P, _INT, _P, _P, _P]),
+    "psignn_lin_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P]),
     "psignn_f_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P]),
     "psignn_f_vjp_p": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P]),
     "psignn_param_grad_size": (_I64, [_INT, _INT]),
@@ -93,6 +94,8 @@ SIGNATURES = {
                                     C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_broyden_solve_adjoint": (_INT, [_P, _P, _INT, _P, _P, _P, _P, C.c_double, _INT, _P, C.POINTER(SolveInfo),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_broyden_solve_adjoint_lin": (_INT, [_P, _P, _P, _INT, _P, C.c_double, _INT, _P, C.POINTER(SolveInfo),
+                                                C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_broyden_solve_batch": (_INT, [_INT, C.POINTER(_P), _P, _INT, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.c_double, _INT,
                                           C.POINTER(_P), C.POINTER(SolveInfo), C.POINTER(C.POINTER(C.c_double)),
                                           C.POINTER(C.POINTER(C.c_double)), _P]),

@@ -19,6 +19,23 @@
 // shrink to 4 bytes).  Dirichlet plans with a single-layer block; mixed plans: the tiles WITHOUT Neumann nodes (all but the boundary
 // tiles) go through the stored linearisation, the few tiles holding Neumann nodes through k_jvp_tile at the state kept from the build
 // (a Neumann row needs a third mask set per slot; not worth a second record format for ~2 % of the tiles).
+//
+// Transposed product (psignn_lin_vjp, k_vjp_lin): out = J_f(h)^T w from the SAME masks and node records, so that it is the exact
+// transpose of psignn_lin_jvp (masks recomputed from projections could flip where a pre-activation is ~0).  Per node n, the node-local
+// backward through LN', the update MLP (stored hidden mask) and the gate gives the direct term and c[n] = [c_to | c_fr], the
+// cotangents of dS_to / dS_fr (0 on Dirichlet rows, which are copies of H_init); then
+//   out[u] = direct[u] + W1i_to^T (cnt_to[u] . c_to[u]) + W1i_fr^T (cnt_fr[u] . c_fr[u])
+//          + W1j_to^T sum_{slots of u -> n} m_to(n's slot of the pair) . c_to[n] + W1j_fr^T sum m_fr(n's slot of the pair) . c_fr[n]
+// cnt_dir[u][o] = number of u's slots with mask bit o set (c[u] is the same on all of them: a popcount, as pass A of the tiled VJP).
+// The neighbour masks live with the receiving node n, so the handle keeps a transposed slot-dword array aligned with `slot`:
+//   tslot[s][l] = u's LDS row field of the slot | n's Phi_to masks of edge u -> n (bits 10..19) | n's Phi_from masks of n -> u (20..29)
+// filled per build by k_lin_tfill through a reverse slot map (k_lin_rev, once per handle, on the device from the plan's ELL rows),
+// matched per edge direction: the Phi_to and Phi_from masks of one pair may come from two different slots of n's row.
+// Both arrays are allocated on the first psignn_lin_vjp: the build and psignn_lin_jvp do not change.  One launch per product:
+// stage 1 computes c for the tile and halo rows into 80-byte LDS rows (halo rows recomputed per tile), stage 2 walks the slots from
+// u's side (a gather: fixed order, no atomics, bitwise reproducible).  Mixed plans: the tiled VJP at the state kept by the build (a
+// stored form of the Neumann rows, a third mask set per slot, is not written yet).
+//
 // weight loads of mv2 pinned chunk by chunk (tile_helpers.h; A/B in profiles/r3_ab_mv2.txt: k_jvp_lin 53 -> 48.5 us)
 #ifndef MV2_LAUNDER
 #define MV2_LAUNDER 2
@@ -38,6 +55,11 @@ struct psignn_lin {
   float *h = nullptr, *prb = nullptr, *nrm = nullptr;   // mixed plans: the state of the last build (k_jvp_tile on the Neumann tiles)
   size_t bytes = 0;
   int built = 0;
+  // transposed product (dirichlet plans), allocated on the first psignn_lin_vjp: the build and psignn_lin_jvp never touch them
+  mutable int2* rev = nullptr;        // (ell_rows, 64) reverse slot map per edge direction, filled once
+  mutable uint32_t* tslot = nullptr;  // (ell_rows, 64) transposed slot dwords, masks re-filled once per build
+  mutable int tfilled = 0;            // tslot holds the masks of the last build
+  mutable size_t tbytes = 0;
 };
 
 // Stage 1 of both kernels: rows [Pj_to | Pj_from] = W1j_{to,from} src[node] of the tile's own and halo nodes -> 80-byte LDS rows
@@ -448,6 +470,278 @@ __global__ __launch_bounds__(TILE_THREADS) LIN_OCC void k_jvp_lin(int n_tiles, i
   store10(out + n * D, dy);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Transposed product: out = J_f(h)^T w from the same stored linearisation (dirichlet plans)
+// ------------------------------------------------------------------------------------------------------------------
+// r[k] += sum_o WT[k][o] g[o], k < K: the transposed product on the [in k][out o] section, o pairs packed, one horizontal add per k
+template <int K>
+__device__ __forceinline__ void mvT(const float* __restrict__ WT, const float* g, float* r) {
+  const v2f* w = reinterpret_cast<const v2f*>(WT);
+  const v2f gp[5] = {(v2f){g[0], g[1]}, (v2f){g[2], g[3]}, (v2f){g[4], g[5]}, (v2f){g[6], g[7]}, (v2f){g[8], g[9]}};
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (k > 0 && k % MV2_CH == 0) PHASE();
+    v2f a = w[k * 5] * gp[0];
+#pragma unroll
+    for (int p = 1; p < 5; ++p) a = __builtin_elementwise_fma(w[k * 5 + p], gp[p], a);
+    r[k] += a.x + a.y;
+  }
+}
+
+// Node-local backward of one non-Dirichlet row: the transpose of k_jvp_lin's tail (LayerNorm', update MLP, gate) for the cotangent
+// wv of the row's output.  c = [c_to | c_fr] = cotangents of dS_to, dS_fr; dx = the direct term (cotangent of the row's own v).
+template <int P>
+__device__ __forceinline__ void lin_node_back(const float* __restrict__ W, const float* __restrict__ T, int lofs, const float* wv,
+                                              const float* __restrict__ recp, float* c, float* dx) {
+  using L = WLayout<P>;
+  const float4* rp = reinterpret_cast<const float4*>(recp);
+  const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];
+  const float u[D] = {r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, r3.x, r3.y};
+  const float yh[D] = {r3.z, r3.w, r4.x, r4.y, r4.z, r4.w, r5.x, r5.y, r5.z, r5.w};
+  const float al = r0.x, rs = r0.z;
+  const unsigned hm = __float_as_uint(r0.w);
+  // LN' = diag(g) rs (I - 1 1^T / D - yh yh^T / D): its transpose applied to w
+  float a[D], ma = 0.f, my = 0.f;
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    a[o] = W[L::LN_G + o] * rs * wv[o];
+    ma += a[o];
+    my = fmaf(yh[o], a[o], my);
+  }
+  ma *= (1.f / D);
+  my *= (1.f / D);
+  float dalb = 0.f, dyb[D], dub[D];
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    dyb[o] = a[o] - ma - yh[o] * my;   // dy = dx + dal u + al du
+    dalb = fmaf(u[o], dyb[o], dalb);
+    dub[o] = al * dyb[o];
+  }
+  // du = U2 (hm . dq),  dq = U1h dx + G_to dS_to + G_fr dS_fr
+  float dqb[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) dqb[k] = 0.f;
+  PHASE();
+  mvT<D>(T + L::T_U2, dub, dqb);
+#pragma unroll
+  for (int k = 0; k < D; ++k) dqb[k] = (hm >> k) & 1u ? dqb[k] : 0.f;
+  // dal = alpha (1 - alpha) (w_a . dx + a_to . dS_to + a_fr . dS_fr)
+  const float g = r0.y * dalb;
+  const float* Wf = W + lofs + L::L_FOLD;
+  const float* Wa = W + L::AL_W;
+  PHASE();
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    c[k] = g * Wf[L::F_ATO + k];
+    c[D + k] = g * Wf[L::F_AFR + k];
+  }
+  PHASE();
+  mvT<D>(T + L::T_GTO, dqb, c);
+  PHASE();
+  mvT<D>(T + L::T_GFR, dqb, c + D);
+  if (dx) {
+    PHASE();
+#pragma unroll
+    for (int k = 0; k < D; ++k) dx[k] = fmaf(g, Wa[k], dyb[k]);
+    PHASE();
+    mvT<D>(T + L::T_U1H, dqb, dx);
+  }
+}
+
+// One launch per product.  Stage 1: [c_to | c_fr] of every tile and halo row -> 80-byte LDS rows (the own row by its lane, which
+// keeps its direct term; halo rows over all threads).  Stage 2, node u: own edges through the counts of its own mask bits (a node's
+// cotangent of dS is the same on all its slots), neighbour edges through the transposed slot dwords (tslot: the LDS row of the
+// neighbour n | n's masks of the pair's slot in n's ELL row): gathered from u's side, fixed order, no atomics.
+//   out[u] = dx[u] + W1i_to^T (cnt_to[u] . c_to[u]) + W1i_fr^T (cnt_fr[u] . c_fr[u])
+//          + W1j_to^T sum_n m_to(n; u -> n) . c_to[n] + W1j_fr^T sum_n m_fr(n; n -> u) . c_fr[n]
+template <int P>
+__global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk, const TileCtx C, const float* __restrict__ W,
+                                                          int lofs, int tofs, const uint32_t* __restrict__ slot,
+                                                          const uint32_t* __restrict__ tslot, const float* __restrict__ rec,
+                                                          const float* __restrict__ tw, float* __restrict__ out) {
+  using L = WLayout<P>;
+  constexpr int RS = 20;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (tile >= n_tiles) return;
+  const int tid = threadIdx.x;
+  const int tn = C.tile_nodes;
+  const int32_t t0 = tn ? tile * tn : C.tile_ptr[tile];
+  const int n_t = tn ? min(tn, C.n_nodes - t0) : C.tile_ptr[tile + 1] - t0;
+  const int n_h = C.halo_cnt[tile];
+  const int32_t* hl = C.halo + (int64_t)tile * HALO_CAP;
+  const float* T = W + tofs;
+  // ---- stage 1
+  float dx[D];
+#pragma unroll
+  for (int o = 0; o < D; ++o) dx[o] = 0.f;
+  for (int row = tid; row < n_t + n_h; row += TILE_THREADS) {
+    const int64_t node = row < n_t ? (int64_t)(t0 + row) : (int64_t)hl[row - n_t];
+    float c[2 * D];
+#pragma unroll
+    for (int o = 0; o < 2 * D; ++o) c[o] = 0.f;
+    if (!(C.flags_p[node] & FLAG_DIRICHLET)) {   // a Dirichlet row is a copy of H_init: no cotangent flows through it
+      float wv[D];
+      load10(tw + node * D, wv);
+      if (row < n_t) lin_node_back<P>(W, T, lofs, wv, rec + node * LIN_REC, c, dx);
+      else lin_node_back<P>(W, T, lofs, wv, rec + node * LIN_REC, c, nullptr);
+    }
+    float4* q = reinterpret_cast<float4*>(lds + row * RS);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) q[i] = make_float4(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+  }
+  __syncthreads();
+  if (tid >= n_t) return;
+  const int64_t n = (int64_t)t0 + tid;
+  const int lane = tid & 63;
+  const int slice = __builtin_amdgcn_readfirstlane((tn ? tile * (tn >> 6) : C.tile_slice[tile]) + (tid >> 6));
+  const int srow0 = C.slice_off[slice];
+  const int nslots = C.slice_deg[slice];
+  const uint32_t* si = slot + (int64_t)srow0 * 64 + lane;
+  const uint32_t* ti = tslot + (int64_t)srow0 * 64 + lane;
+  // own mask bits counted in 4-bit fields, one chunk at a time: nib[j] sums bits 10 + j + 4 i (i < 5) of the node's slot dwords
+  const bool own = !(C.flags_p[n] & FLAG_DIRICHLET);   // (a Dirichlet row's own slot dwords are not written by the build)
+  unsigned cnt_lo[5] = {0u, 0u, 0u, 0u, 0u}, cnt_hi[5] = {0u, 0u, 0u, 0u, 0u};   // two 16-bit counts per word: bits 10 .. 19 | 20 .. 29
+  v2f at[5], af[5];
+#pragma unroll
+  for (int p = 0; p < 5; ++p) at[p] = af[p] = splat(0.f);
+  for (int r0 = 0; r0 < nslots; r0 += LIN_CHUNK) {
+    uint32_t sw[LIN_CHUNK], xw[LIN_CHUNK];
+#pragma unroll
+    for (int i = 0; i < LIN_CHUNK; ++i) {   // clamped index: unconditional loads
+      const int64_t r = min(r0 + i, nslots - 1);
+      xw[i] = ti[r * 64];
+      sw[i] = own ? si[r * 64] : 0u;
+    }
+    unsigned nib[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < LIN_CHUNK; ++i) {
+      if (r0 + i < nslots) {   // wave-uniform
+        const uint32_t w = xw[i];
+        const float4* q = reinterpret_cast<const float4*>(lds + (int)(w & 1023u) * RS);
+        const float4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3], v4 = q[4];
+        const float d[20] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y,
+                             v2.z, v2.w, v3.x, v3.y, v3.z, v3.w, v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int p = 0; p < 5; ++p) {
+          const int m0 = __builtin_amdgcn_sbfe(w, 10 + 2 * p, 1), m1 = __builtin_amdgcn_sbfe(w, 11 + 2 * p, 1);
+          const int m2 = __builtin_amdgcn_sbfe(w, 20 + 2 * p, 1), m3 = __builtin_amdgcn_sbfe(w, 21 + 2 * p, 1);
+          at[p] += (v2f){__int_as_float(__float_as_int(d[2 * p]) & m0), __int_as_float(__float_as_int(d[2 * p + 1]) & m1)};
+          af[p] += (v2f){__int_as_float(__float_as_int(d[10 + 2 * p]) & m2), __int_as_float(__float_as_int(d[11 + 2 * p]) & m3)};
+        }
+        const uint32_t s = sw[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nib[j] += (s >> (10 + j)) & 0x11111u;
+      }
+    }
+    // flush (at most LIN_CHUNK < 16 per nibble): bit 10 + b sits in nib[b & 3], nibble b >> 2
+#pragma unroll
+    for (int b = 0; b < 2 * D; ++b) {
+      const unsigned v = (nib[b & 3] >> (4 * (b >> 2))) & 15u;
+      if (b < D) cnt_lo[b >> 1] += v << (16 * (b & 1));
+      else cnt_hi[(b - D) >> 1] += v << (16 * (b & 1));
+    }
+  }
+  // ---- out = dx + W1i^T (cnt . c_own) + W1j^T (gathered sums)
+  const float4* q = reinterpret_cast<const float4*>(lds + tid * RS);
+  const float4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3], v4 = q[4];
+  const float co[20] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y,
+                        v2.z, v2.w, v3.x, v3.y, v3.z, v3.w, v4.x, v4.y, v4.z, v4.w};
+  float gt[D], gf[D];
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    gt[o] = (float)((cnt_lo[o >> 1] >> (16 * (o & 1))) & 0xFFFFu) * co[o];
+    gf[o] = (float)((cnt_hi[o >> 1] >> (16 * (o & 1))) & 0xFFFFu) * co[D + o];
+  }
+  PHASE();
+  mvT<D>(T + L::T_W1I_TO, gt, dx);
+  PHASE();
+  mvT<D>(T + L::T_W1I_FR, gf, dx);
+  PHASE();
+  mvT<D>(T + L::T_W1J_TO, reinterpret_cast<const float*>(at), dx);
+  PHASE();
+  mvT<D>(T + L::T_W1J_FR, reinterpret_cast<const float*>(af), dx);
+  store10(out + n * D, dx);
+}
+
+// Reverse slot map, once per handle, matched per edge DIRECTION (merge_slots in tiles.hip may pair a node's slots differently on the
+// two sides: with u -> n twice and n -> u once, mirrored, u's row is [OUT-only, MERGED] and n's [IN-only, IN-only, OUT-only]):
+//   u's slot s carries OUT (edge u -> n), the k-th such slot of u towards n  <->  the k-th IN-carrying slot of n towards u:
+//     rev[s].x = its index, whose bits 10..19 are n's Phi_to masks of that edge
+//   u's slot s carries IN  (edge n -> u), the k-th such slot of u towards n  <->  the k-th OUT-carrying slot of n towards u:
+//     rev[s].y = its index, whose bits 20..29 are n's Phi_from masks of that edge
+// (both lists are in canonical edge order on both sides, so the k-th of one side is the same edge as the k-th of the other).  -1: no
+// such direction.  A direction without a partner (a plan this matching does not understand) sets *bad: the product is refused.
+// The low 10 bits of tslot[s] get u's LDS row field of the slot (the masks are filled in per build by k_lin_tfill).
+__device__ __forceinline__ int32_t lin_tile_of(const int32_t* __restrict__ a, int n, int32_t x) {   // last i with a[i] <= x
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(256) void k_lin_rev(int64_t n_slices, int n_tiles, const TileCtx C, int2* __restrict__ rev,
+                                                 uint32_t* __restrict__ tslot, int32_t* __restrict__ bad) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t s = gid >> 6;
+  if (s >= n_slices) return;
+  const int lane = (int)(gid & 63);
+  const int tile = lin_tile_of(C.tile_slice, n_tiles, (int32_t)s);
+  const int32_t t0 = C.tile_ptr[tile], n_t = C.tile_ptr[tile + 1] - t0;
+  const int32_t u = t0 + 64 * (int32_t)(s - C.tile_slice[tile]) + lane;
+  const int64_t row0 = C.slice_off[s];
+  const int deg = C.slice_deg[s];
+  const int32_t* hl = C.halo + (int64_t)tile * HALO_CAP;
+  for (int r = 0; r < deg; ++r) {
+    const int64_t idx = (row0 + r) * 64 + lane;
+    int2 found = make_int2(-1, -1);
+    uint32_t li = 0;
+    const uint32_t e = u < t0 + n_t ? C.ell[idx].x : ELL_EMPTY;
+    if ((e & 0xFFFFu) != ELL_EMPTY) {
+      li = e & 0xFFFFu;
+      const uint32_t kind = (e >> 16) & 3u;
+      int k_out = 0, k_in = 0;   // earlier OUT- / IN-carrying slots of u towards the same neighbour
+      for (int r2 = 0; r2 < r; ++r2) {
+        const uint32_t e2 = C.ell[(row0 + r2) * 64 + lane].x;
+        if ((e2 & 0xFFFFu) != li) continue;
+        k_out += (e2 & SLOT_OUT) ? 1 : 0;
+        k_in += (e2 & SLOT_IN) ? 1 : 0;
+      }
+      const int32_t nb = (int32_t)li < n_t ? t0 + (int32_t)li : hl[li - n_t];
+      const int tile2 = lin_tile_of(C.tile_ptr, n_tiles, nb);
+      const int32_t t02 = C.tile_ptr[tile2], n_t2 = C.tile_ptr[tile2 + 1] - t02;
+      const int64_t s2 = C.tile_slice[tile2] + (nb - t02) / 64;
+      const int lane2 = (nb - t02) & 63;
+      const int32_t* hl2 = C.halo + (int64_t)tile2 * HALO_CAP;
+      const int64_t row02 = C.slice_off[s2];
+      const bool want_to = kind & 2u, want_fr = kind & 1u;
+      for (int r2 = 0; r2 < C.slice_deg[s2]; ++r2) {
+        const int64_t idx2 = (row02 + r2) * 64 + lane2;
+        const uint32_t e2 = C.ell[idx2].x;
+        if ((e2 & 0xFFFFu) == ELL_EMPTY) continue;
+        const uint32_t li2 = e2 & 0xFFFFu;
+        const int32_t back = (int32_t)li2 < n_t2 ? t02 + (int32_t)li2 : hl2[li2 - n_t2];
+        if (back != u) continue;
+        if (want_to && found.x < 0 && (e2 & SLOT_IN) && k_out-- == 0) found.x = (int32_t)idx2;
+        if (want_fr && found.y < 0 && (e2 & SLOT_OUT) && k_in-- == 0) found.y = (int32_t)idx2;
+      }
+      if ((want_to && found.x < 0) || (want_fr && found.y < 0)) atomicOr(bad, 1);
+    }
+    rev[idx] = found;
+    tslot[idx] = li;
+  }
+}
+
+// Per build: the neighbour's masks of each edge direction next to the LDS row field (bits 10 .. 29, as in the slot dwords)
+__global__ __launch_bounds__(256) void k_lin_tfill(int64_t n, const int2* __restrict__ rev, const uint32_t* __restrict__ slot,
+                                                   uint32_t* __restrict__ tslot) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int2 r = rev[i];
+  tslot[i] = (tslot[i] & 1023u) | (r.x >= 0 ? slot[r.x] & 0x000FFC00u : 0u) | (r.y >= 0 ? slot[r.y] & 0x3FF00000u : 0u);
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host
 int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
                              const float* v, float* out, int groups, hipStream_t st);
@@ -477,12 +771,12 @@ extern "C" int psignn_lin_create(psignn_lin_t** out, const psignn_plan_t* p) {
 
 extern "C" void psignn_lin_destroy(psignn_lin_t* s) {
   if (!s) return;
-  for (void* q : {(void*)s->slot, (void*)s->rec, (void*)s->h, (void*)s->prb, (void*)s->nrm})
+  for (void* q : {(void*)s->slot, (void*)s->rec, (void*)s->h, (void*)s->prb, (void*)s->nrm, (void*)s->rev, (void*)s->tslot})
     if (q) (void)hipFree(q);
   delete s;
 }
 
-extern "C" size_t psignn_lin_bytes(const psignn_lin_t* s) { return s ? s->bytes : 0; }
+extern "C" size_t psignn_lin_bytes(const psignn_lin_t* s) { return s ? s->bytes + s->tbytes : 0; }
 
 // h, prb (and, mixed plans, the unit normals) in PLAN order; dirichlet: single-layer block; mixed: any depth (the iterated layer is
 // the last one, as in psignn_f_jvp)
@@ -516,6 +810,7 @@ extern "C" int psignn_lin_build(psignn_lin_t* s, const float* W, int nl, const f
   }
   HIP_TRY(hipGetLastError());
   s->built = 1;
+  s->tfilled = 0;
   return PSIGNN_OK;
 }
 
@@ -550,3 +845,72 @@ extern "C" int psignn_lin_jvp(const psignn_lin_t* s, const float* W, int nl, con
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
+
+// w, out in PLAN order: out = J_f(h)^T w for the h of the last psignn_lin_build.  Dirichlet plans: k_vjp_lin (one launch; on the first
+// call after a build also k_lin_tfill, on the first call of the handle k_lin_rev and the two transposed arrays).  Mixed plans: the
+// tiled VJP (psignn_f_tile_vjp, work = the plan workspace) at the state kept by the build -- no stored form of the Neumann rows yet.
+int psignn_f_tile_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* w,
+                      float* out, float* work, hipStream_t st);
+
+extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, const float* w, float* out, float* work, void* stream) {
+  ARG_CHECK(s && W && w && out, "NULL argument");
+  ARG_CHECK(s->built, "psignn_lin_build has not run");
+  ARG_CHECK(w != out, "in-place product is not supported");
+  const psignn_plan* p = s->plan;
+  ARG_CHECK(p->mixed ? nl >= 1 : nl == 1, "linearised VJP: single-layer blocks (mixed plans: the last layer)");
+  hipStream_t st = (hipStream_t)stream;
+  if (p->mixed) {
+    ARG_CHECK(work, "mixed plan: the transposed product needs the plan workspace");
+    return psignn_f_tile_vjp(p, W, nl, s->h, s->prb, s->nrm, w, out, work, st);
+  }
+  const int64_t n_sl = p->ell_rows * 64;
+  if (!s->tslot) {
+    const size_t nb = (size_t)(p->ell_rows + 1) * 64, b = nb * 4 + nb * 8 + 4;
+    int32_t* bad = nullptr;
+    if (hipMalloc((void**)&s->rev, nb * 8 + 4) != hipSuccess || hipMalloc((void**)&s->tslot, nb * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      if (s->rev) (void)hipFree(s->rev);
+      s->rev = nullptr;
+      s->tslot = nullptr;
+      psignn_set_error("psignn_lin_vjp: out of device memory (%zu bytes)", b);
+      return PSIGNN_ENOMEM;
+    }
+    s->tbytes = b;
+    bad = reinterpret_cast<int32_t*>(s->rev + nb);   // one flag word behind the map
+    HIP_TRY(hipMemsetAsync(s->rev, 0xFF, nb * 8, st));
+    HIP_TRY(hipMemsetAsync(bad, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(s->tslot, 0, nb * 4, st));
+    if (p->n_slices > 0)
+      LAUNCH("k_lin_rev", st, (k_lin_rev<<<(unsigned)cdiv(p->n_slices * 64, 256), 256, 0, st>>>(
+          p->n_slices, (int)p->n_tiles, p->h_ctx, s->rev, s->tslot, bad)));
+    int32_t h_bad = 0;   // (once per handle)
+    HIP_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_bad) {
+      (void)hipFree(s->rev);
+      (void)hipFree(s->tslot);
+      s->rev = nullptr;
+      s->tslot = nullptr;
+      s->tbytes = 0;
+      psignn_set_error("psignn_lin_vjp: an edge direction of the plan's slots has no partner slot at its neighbour");
+      return PSIGNN_EINVAL;
+    }
+    s->tfilled = 0;
+  }
+  if (!s->tfilled) {
+    if (n_sl > 0)
+      LAUNCH("k_lin_tfill", st, (k_lin_tfill<<<(unsigned)cdiv(n_sl, 256), 256, 0, st>>>(n_sl, s->rev, s->slot, s->tslot)));
+    s->tfilled = 1;
+  }
+  using L = WLayout<2>;
+  const int chunk = (int)cdiv(p->n_tiles, 8);
+  const size_t lds = std::max((size_t)p->max_rows * 20 * 4, tile_lds_min());
+  // w (tile + halo rows), out (40 N each), flags, node records (tile + halo rows), slot and transposed slot dwords
+  PROF_BYTES((int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 8);
+  LAUNCH("k_vjp_lin", st, (k_vjp_lin<2><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
+      (int)p->n_tiles, chunk, p->h_ctx, W, L::layer(0), L::tp_layer(nl, false, 0), s->slot, s->tslot, s->rec, w, out)));
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
+const psignn_plan* psignn_lin_plan(const psignn_lin_t* s) { return s ? s->plan : nullptr; }

@@ -1885,6 +1885,32 @@ extern "C" int psignn_f_vjp(const psignn_plan_t* p, const float* W, int nl, cons
 extern "C" int psignn_f_vjp_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
                               const float* nrm, const float* w, float* out, float* work, void* stream);
 
+// The Broyden loop of the adjoint solve; vjp(y, out): out = J_f(h*)^T y in the solve's numbering
+template <class F>
+static int adjoint_loop(psignn_broyden* s, const float* grad, double eps, int poll_every, F&& vjp, float* d_result,
+                        psignn_solve_info_t* info, double* h_rel, double* h_abs, hipStream_t st) {
+  if (poll_every <= 0) poll_every = 8;
+  unsigned g = (unsigned)s->nblk;
+  int rc;
+  k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
+  // y0 = 0, map(y0) = grad  ->  g0 = grad, update = grad  (solver.py:131-136 with f(0) = grad)
+  HIP_TRY(hipMemsetAsync(s->h0p, 0, (size_t)s->M * 4, st));
+  VPLAIN(s->vec, k_begin, (g, TB, 0, st), s->M, s->h0p, grad, s->xbuf, s->gbuf[0], s->upd);
+  for (int it = 0; it < s->thr; ++it) {
+    // x_next = x + update, kept also in h0p (fixed address for the VJP kernels)
+    VLAUNCH("k_xnext", st, s->vec, k_xnext, (g, TB, 0, st), s->M, s->st, s->xbuf, s->upd, s->h0p);
+    if ((rc = vjp(s->h0p, s->fx))) return rc;
+    VLAUNCH("k_addv", st, s->vec, k_addv, (g, TB, 0, st), s->M, s->st, s->fx, grad);
+    launch_update(s, it, eps, st);
+    if ((it + 1) % poll_every == 0 || it + 1 == s->thr) {
+      rc = read_status(s, st);
+      if (rc) return rc;
+      if (s->h_st->done) break;
+    }
+  }
+  return finish(s, d_result, info, h_rel, h_abs, st);
+}
+
 extern "C" int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* W, int nl, const float* h_star,
                                             const float* prb, const float* nrm, const float* grad, double eps,
                                             int poll_every, float* d_result, psignn_solve_info_t* info, double* h_rel,
@@ -1897,8 +1923,6 @@ extern "C" int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* W,
   const bool tiled = p->tiled && (p->mixed || nl == 1);
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
   s->plan_order = tiled ? 1 : 0;
-  if (poll_every <= 0) poll_every = 8;
-  unsigned g = (unsigned)s->nblk;
   int rc;
   if (tiled) {  // plan-order copies: h* -> fwork tail, prb -> prbp, grad -> dg (free until the first update)
     float* hs_p = s->fwork + p->N * 4 * D;        // fwork = [B (40N) | h*_p (10N) | grad_p (10N) | ...]
@@ -1914,25 +1938,29 @@ extern "C" int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* W,
     grad = gr_p;
     prb = s->prbp;
   }
-  k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
-  // y0 = 0, map(y0) = grad  ->  g0 = grad, update = grad  (solver.py:131-136 with f(0) = grad)
-  HIP_TRY(hipMemsetAsync(s->h0p, 0, (size_t)s->M * 4, st));
-  VPLAIN(s->vec, k_begin, (g, TB, 0, st), s->M, s->h0p, grad, s->xbuf, s->gbuf[0], s->upd);
-  for (int it = 0; it < s->thr; ++it) {
-    // x_next = x + update, kept also in h0p (fixed address for the VJP kernels)
-    VLAUNCH("k_xnext", st, s->vec, k_xnext, (g, TB, 0, st), s->M, s->st, s->xbuf, s->upd, s->h0p);
-    rc = tiled ? psignn_f_vjp_p(p, W, nl, h_star, prb, nrm, s->h0p, s->fx, s->fwork, st)
-               : psignn_f_vjp(p, W, nl, h_star, prb, nrm, s->h0p, s->fx, s->fwork, st);
-    if (rc) return rc;
-    VLAUNCH("k_addv", st, s->vec, k_addv, (g, TB, 0, st), s->M, s->st, s->fx, grad);
-    launch_update(s, it, eps, st);
-    if ((it + 1) % poll_every == 0 || it + 1 == s->thr) {
-      rc = read_status(s, st);
-      if (rc) return rc;
-      if (s->h_st->done) break;
-    }
-  }
-  return finish(s, d_result, info, h_rel, h_abs, st);
+  auto vjp = [&](const float* y, float* out) {
+    return tiled ? psignn_f_vjp_p(p, W, nl, h_star, prb, nrm, y, out, s->fwork, st)
+                 : psignn_f_vjp(p, W, nl, h_star, prb, nrm, y, out, s->fwork, st);
+  };
+  return adjoint_loop(s, grad, eps, poll_every, vjp, d_result, info, h_rel, h_abs, st);
+}
+
+// Same solve with the transposed product of a stored linearisation (psignn_lin_vjp) as the map; h* = the state lin was built at
+const psignn_plan* psignn_lin_plan(const psignn_lin_t* lin);
+extern "C" int psignn_broyden_solve_adjoint_lin(psignn_broyden_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad,
+                                                double eps, int poll_every, float* d_result, psignn_solve_info_t* info,
+                                                double* h_rel, double* h_abs, void* stream) {
+  ARG_CHECK(s && s->plan, "solver was not created from a mesh plan");
+  ARG_CHECK(lin && W && grad, "NULL argument");
+  ARG_CHECK(psignn_lin_plan(lin) == s->plan, "the linearisation was made for a different plan than the solver");
+  hipStream_t st = (hipStream_t)stream;
+  const psignn_plan* p = s->plan;
+  s->plan_order = 1;
+  float* gr_p = s->fwork + p->N * 5 * D;   // fwork = [B (40N) | (10N) | grad_p (10N) | ...], as above
+  int rc;
+  if ((rc = psignn_plan_permute(p, grad, D, gr_p, 1, st))) return rc;
+  auto vjp = [&](const float* y, float* out) { return psignn_lin_vjp(lin, W, nl, y, out, s->fwork, st); };
+  return adjoint_loop(s, gr_p, eps, poll_every, vjp, d_result, info, h_rel, h_abs, st);
 }
 
 extern "C" int psignn_broyden_get_iterate(const psignn_broyden_t* s, int i, float* d_dst, void* stream) {

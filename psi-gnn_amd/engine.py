@@ -877,6 +877,23 @@ class Linearization:
                                                nat.ptr(out), nat.stream_ptr(Vc.device)), "psignn_lin_jvp")
         return out
 
+    def vjp_p(self, Wp, out=None):
+        """Wp^T J_f(H) for the H of the last ``build`` (plan order): the exact transpose of ``jvp_p`` (same stored masks and
+        per-node records); the same product as ``FixedPointMap.vjp_p`` at that H up to fp32 summation order.  ``out`` as in
+        ``jvp_p``."""
+        fm = self.fmap
+        Wc = _f32c(Wp)
+        if out is None:
+            out = torch.empty_like(Wc)
+        elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != Wc.numel():
+            raise nat.NativeError("vjp_p: out must be a contiguous float32 tensor of the state's size")
+        with torch.cuda.device(Wc.device):
+            nat.check(nat.lib().psignn_lin_vjp(self.handle, nat.ptr(fm.weights.flat), fm.weights.n_layers, nat.ptr(Wc),
+                                               nat.ptr(out), nat.ptr(fm.plan.workspace() if fm.plan.mixed else None),
+                                               nat.stream_ptr(Wc.device)),
+                      "psignn_lin_vjp")
+        return out
+
     def close(self):
         if self.handle is not None:
             nat.lib().psignn_lin_destroy(self.handle)
@@ -949,14 +966,23 @@ class DeviceBroyden:
         out["result"] = result
         return out
 
-    def solve_adjoint(self, fmap: FixedPointMap, h_star, grad, eps, poll_every=8):
-        """y = J_f(h*)^T y + grad, y_0 = 0, entirely on the device (VJP kernel inside the Broyden loop)."""
+    def solve_adjoint(self, fmap: FixedPointMap, h_star, grad, eps, poll_every=8, lin=None):
+        """y = J_f(h*)^T y + grad, y_0 = 0, entirely on the device (VJP kernel inside the Broyden loop).  ``lin``: a Linearization
+        of ``fmap`` built at h* (plan order, on this solver's plan); the loop then applies ``lin.vjp_p`` and ``h_star`` is not read."""
         hs, gr = _f32c(h_star), _f32c(grad)
         result = torch.empty_like(gr)
         info = nat.SolveInfo()
         rel = (C.c_double * self.threshold)()
         abs_ = (C.c_double * self.threshold)()
         with torch.cuda.device(self.device):
+            if lin is not None:
+                nat.check(nat.lib().psignn_broyden_solve_adjoint_lin(
+                    self.handle, lin.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(gr), float(eps),
+                    int(poll_every), nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device)),
+                    "psignn_broyden_solve_adjoint_lin")
+                out = self._collect(info, rel, abs_, result.shape, result.device)
+                out["result"] = result
+                return out
             nat.check(nat.lib().psignn_broyden_solve_adjoint(
                 self.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(hs), nat.ptr(fmap.prb),
                 nat.ptr(fmap.nrm), nat.ptr(gr), float(eps), int(poll_every), nat.ptr(result), C.byref(info), rel, abs_,

@@ -7,7 +7,11 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
 
 * ``Model(config)`` takes the reference's config dict (``latent_dim, n_layers, solver, fw_tol, fw_thres,
   bw_tol, bw_thres, path_logs``; ``hidden_dim`` ignored as in the reference).  An optional key
-  ``"bc"`` = ``"dirichlet"`` | ``"mixed"`` selects the family (the reference uses two copies of the file).
+  ``"bc"`` = ``"dirichlet"`` | ``"mixed"`` selects the family (the reference uses two copies of the file).  An optional
+  key ``"bw_linearize"`` (default False): the implicit backward, the power method and the Jacobian estimate linearise f
+  once at H* and apply the transposed stored linearisation (``engine.Linearization.vjp_p``) where the plan allows it.  On the
+  mixed family it gains nothing yet: its transposed product is the tiled VJP at the state the build kept, so the key only adds one
+  build per call there.
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
   and shapes are identical.
 * ``batch`` is any object with the PyG ``Data`` attributes (see ``data/meshdata.py``), already on the GPU.
@@ -246,18 +250,43 @@ class DeepEquilibrium(nn.Module):
                                         *[p for _, p in named])
             return new_H, jac_loss
         with torch.no_grad():
-            jac_loss = self.jac_loss_estimate(H_star, H_init.detach(), batch, vecs=1, generator=generator)
+            # both diagnostics at the same H*: one linearisation for the two of them
+            shared = (self._linearization(self.f.bind(H_init.detach(), batch), H_star)
+                      if self.path_logs and self._linearize_default(None) else None)
+            jac_loss = self.jac_loss_estimate(H_star, H_init.detach(), batch, vecs=1, generator=generator, linearize=shared)
             if not torch.is_grad_enabled() and self.path_logs:
-                _, sradius = self.power_method(H_star, H_init.detach(), batch, n_iters=150, generator=generator)
+                _, sradius = self.power_method(H_star, H_init.detach(), batch, n_iters=150, generator=generator,
+                                               linearize=shared)
                 _log(self.path_logs, "spectral_radius.csv", "\n{}".format(sradius.item()))
         return new_H, jac_loss
 
     # ---- adjoint side of the reference's training variant (dirichlet/psignn/model.py:204-241), on the VJP kernel
+    def _linearization(self, fmap, H_star):
+        """Linearisation of ``fmap`` at H* (plan order), or None where the plan has no stored form (``can_linearize``).  Its
+        device buffers are kept between calls on the same plan, like the adjoint solver's."""
+        if not fmap.can_linearize():
+            return None
+        lin = getattr(self, "_bw_lin", None)
+        if lin is None or lin.fmap.plan is not fmap.plan:
+            if lin is not None:
+                lin.close()
+            lin = self._bw_lin = engine.Linearization(fmap)
+        lin.fmap = fmap   # this call's weights and boundary data
+        return fmap.linearize_p(fmap.to_plan(H_star), lin)
+
+    def _linearize_default(self, linearize):
+        """None -> the ``bw_linearize`` config value; a bool as given; an ``engine.Linearization`` (already built at H*) as is."""
+        if isinstance(linearize, engine.Linearization):
+            return linearize
+        return bool(self.config_deq.get("bw_linearize", False)) if linearize is None else bool(linearize)
+
     def implicit_backward(self, H_star, H_init, batch, grad):
         """Solve y = J_f(H*)^T y + grad with the configured solver (the reference's backward hook, model.py:210-223):
-        returns the solver dict; ``out["result"]`` is the gradient w.r.t. the fixed point's input."""
+        returns the solver dict; ``out["result"]`` is the gradient w.r.t. the fixed point's input.  With ``bw_linearize``
+        the map is the transposed product of one linearisation of f at H* (where ``fmap.can_linearize()``)."""
         fmap = self.f.bind(H_init, batch)
         g = grad.contiguous()
+        lin = self._linearization(fmap, H_star) if self._linearize_default(None) else None
         if self.config_deq["solver"] is _solver.broyden:  # whole adjoint solve on the device
             # the solver state (2 * bw_thres * N * d floats) is kept between calls on the same plan: a training loop
             # would otherwise allocate and free it once per step
@@ -269,27 +298,38 @@ class DeepEquilibrium(nn.Module):
                 self._bw_solver = engine.DeviceBroyden(plan=fmap.plan, threshold=self.config_deq["bw_thres"], keep_trace=False)
                 self._bw_key = key
             sv = self._bw_solver
-            out = sv.solve_adjoint(fmap, H_star, g, self.config_deq["bw_tol"])
+            out = sv.solve_adjoint(fmap, H_star, g, self.config_deq["bw_tol"], lin=lin)
             out.update(eps=self.config_deq["bw_tol"], threshold=self.config_deq["bw_thres"])
             return out
+        if lin is not None:
+            return self.config_deq["solver"](lambda y: fmap.from_plan(lin.vjp_p(fmap.to_plan(y))) + g, torch.zeros_like(g),
+                                             threshold=self.config_deq["bw_thres"], eps=self.config_deq["bw_tol"])
         return self.config_deq["solver"](lambda y: fmap.vjp(H_star, y) + g, torch.zeros_like(g),
                                          threshold=self.config_deq["bw_thres"], eps=self.config_deq["bw_tol"])
 
-    @staticmethod
-    def _vjp_in_plan_order(fmap, H_star):
+    def _vjp_in_plan_order(self, fmap, H_star, linearize=False):
         """(vjp, to_plan, from_plan) working in plan order where the tiled VJP applies (saves the four permutation
-        passes of the caller-order entry point per product; norms and inner products do not depend on the numbering)."""
+        passes of the caller-order entry point per product; norms and inner products do not depend on the numbering).
+        ``linearize``: the transposed product of one linearisation at H* where the plan has one (True), or of the given
+        Linearization, built at H* by the caller."""
+        if isinstance(linearize, engine.Linearization):
+            lin = linearize
+        else:
+            lin = self._linearization(fmap, H_star) if linearize else None
+        if lin is not None:
+            return lin.vjp_p, fmap.to_plan, fmap.from_plan
         if fmap.plan.tiled and (fmap.weights.mixed or fmap.weights.n_layers == 1):
             Hp = fmap.to_plan(H_star)
             return (lambda w: fmap.vjp_p(Hp, w)), fmap.to_plan, fmap.from_plan
         ident = lambda t: t
         return (lambda w: fmap.vjp(H_star, w)), ident, ident
 
-    def jac_loss_estimate(self, H_star, H_init, batch, vecs=1, generator=None, probes=None):
+    def jac_loss_estimate(self, H_star, H_init, batch, vecs=1, generator=None, probes=None, linearize=None):
         """Hutchinson estimate of tr(J^T J) / (N d) (model.py:416-435) with the VJP kernel.  ``probes``: the Gaussian
-        vectors to use instead of drawing ``vecs`` of them (so that a test can fix them)."""
+        vectors to use instead of drawing ``vecs`` of them (so that a test can fix them).  ``linearize``: None -> the
+        ``bw_linearize`` config value; True / False; or a Linearization built at H*."""
         fmap = self.f.bind(H_init, batch)
-        vjp, to_p, _ = self._vjp_in_plan_order(fmap, H_star)
+        vjp, to_p, _ = self._vjp_in_plan_order(fmap, H_star, self._linearize_default(linearize))
         acc = 0.0
         n = vecs if probes is None else len(probes)
         for i in range(n):
@@ -297,11 +337,12 @@ class DeepEquilibrium(nn.Module):
             acc = acc + vjp(to_p(v)).norm() ** 2
         return acc / n / H_star.numel()
 
-    def power_method(self, H_star, H_init, batch, n_iters=150, generator=None, v0=None):
+    def power_method(self, H_star, H_init, batch, n_iters=150, generator=None, v0=None, linearize=None):
         """Spectral-radius estimate of J by power iteration on v^T J (model.py:437-452).  ``v0``: start vector instead
-        of a Gaussian draw."""
+        of a Gaussian draw.  ``linearize``: None -> the ``bw_linearize`` config value; True / False; or a Linearization
+        built at H*."""
         fmap = self.f.bind(H_init, batch)
-        vjp, to_p, from_p = self._vjp_in_plan_order(fmap, H_star)
+        vjp, to_p, from_p = self._vjp_in_plan_order(fmap, H_star, self._linearize_default(linearize))
         ev = to_p(torch.randn(H_star.shape, device=H_star.device, generator=generator) if v0 is None else v0)
         val = torch.zeros((), device=H_star.device)
         for _ in range(n_iters):
@@ -328,6 +369,8 @@ class _Base(nn.Module):
         d = self.config["latent_dim"]
         self.autoencoder = Autoencoder(hidden_channels=[1, d, d], activation=nn.ReLU())
         self.config_deq = {k: self.config[k] for k in ("solver", "fw_tol", "fw_thres", "bw_tol", "bw_thres", "path_logs")}
+        if "bw_linearize" in self.config:   # optional, like "bc": the transposed stored linearisation in the backward routes
+            self.config_deq["bw_linearize"] = bool(self.config["bw_linearize"])
         self.deqdss = DeepEquilibrium(
             function=Function(n_layers=self.config["n_layers"], latent_dim=d, edge_features_dim=3,
                               second_member_dim=3 if self.mixed else 2, activation=nn.ReLU(), mixed=self.mixed),
