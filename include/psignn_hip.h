@@ -109,6 +109,17 @@ int64_t psignn_weights_size(int mixed, int n_layers);
  * d_work: scratch of psignn_f_workspace_floats(plan) floats.  d_out must not alias d_h.
  * ------------------------------------------------------------------------------------------ */
 int64_t psignn_f_workspace_floats(const psignn_plan_t* plan);
+
+/* Extra scratch the derivatives of a multi-layer block need: dirichlet, the layer states h_1..h_{L-1}, the tangents and
+ * cotangents carried between layers and a single-layer weight view, (4 n_layers + 1) * N * 10 + 4096 floats; mixed (whose
+ * iterated layer is the last one), the weight view alone; 0 for single-layer blocks.  A derivative entry point that takes
+ * d_work is then given its own workspace (psignn_f_workspace_floats for psignn_f_jvp / _jvp_pw / _vjp / _vjp_p,
+ * psignn_f_param_vjp_workspace_floats for the parameter VJPs, psignn_f_vjp_backward_workspace_floats for the backward of the
+ * VJP) + psignn_f_layers_workspace_floats(plan, n_layers) floats.
+ * Multi-layer dirichlet blocks: those entry points do not take h_initial; the Dirichlet rows of the intermediate layer
+ * states are taken from d_h's own Dirichlet rows, which is exact wherever they equal h_initial's (every state f returns,
+ * h_initial itself, a fixed point). */
+int64_t psignn_f_layers_workspace_floats(const psignn_plan_t* plan, int n_layers);
 int psignn_f_forward(const psignn_plan_t* plan, const float* d_weights, int n_layers,
                      const float* d_h, const float* d_h_initial, const float* d_prb,
                      const float* d_normals, float* d_out, float* d_work, void* stream);
@@ -180,12 +191,19 @@ int psignn_f_vjp(const psignn_plan_t* plan, const float* d_weights, int n_layers
 int psignn_f_jvp_p(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h, const float* d_prb,
                    const float* d_normals, const float* d_v, float* d_out, void* stream);
 
+/* Same with a workspace: any depth.  A multi-layer dirichlet block evaluates its layer states into d_work
+ * (psignn_f_workspace_floats + psignn_f_layers_workspace_floats floats) and chains the single-layer JVPs; other blocks
+ * on tiled plans run psignn_f_jvp_p and may pass d_work = NULL.  Plans without tiles: plan order is the caller's order, and
+ * d_work is psignn_f_jvp's (never NULL). */
+int psignn_f_jvp_pw(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h, const float* d_prb,
+                    const float* d_normals, const float* d_v, float* d_out, float* d_work, void* stream);
+
 /* Same with h, prb, w and out in plan order (tiled kernels where the plan has tiles; the form the adjoint solve uses). */
 int psignn_f_vjp_p(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h,
                    const float* d_prb, const float* d_normals, const float* d_w, float* d_out, float* d_work,
                    void* stream);
 
-/* Parameter gradient  w^T (d f / d theta)  at h (plan order; tiled single-layer dirichlet plans), together with
+/* Parameter gradient  w^T (d f / d theta)  at h (plan order; tiled dirichlet plans, any depth), together with
  * w^T (d f / d h) -> d_out_h.  Replaces loss.backward() through new_H = f(H*, H_init, batch) with the hooked
  * cotangent (dirichlet/psignn/model.py:203-225, training_class.py:150-163).  d_grad receives
  * psignn_param_grad_size(mixed, n_layers) floats laid out like the leading (un-derived) section of the packed
@@ -193,12 +211,20 @@ int psignn_f_vjp_p(const psignn_plan_t* plan, const float* d_weights, int n_laye
  * derived (fold) slots stay zero.  d_work: psignn_f_param_vjp_workspace_floats(plan) floats. */
 int64_t psignn_param_grad_size(int mixed, int n_layers);
 int64_t psignn_f_param_vjp_workspace_floats(const psignn_plan_t* plan);
-/* the same in the caller's numbering and for every single-layer plan: tiled plans of both families run the tile kernels in
+/* the same in the caller's numbering and for every plan and depth: tiled plans of both families run the tile kernels in
  * record mode (mixed family: d_normals required; d_grad then also covers phi_neumann{W1,b1,W2,b2} |
  * update_neumann{N1,nb1,N2,nb2}; mixed/psignn/model.py:216-245 under loss.backward()), untiled plans the global-gather kernels. */
 int psignn_f_param_vjp(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h,
                        const float* d_prb, const float* d_normals, const float* d_w, float* d_grad, float* d_out_h,
                        float* d_work, void* stream);
+/* Same, and d_out_init (N, 10), may be NULL: the gradient w.r.t. h_initial -- the Dirichlet rows of the cotangent on the output
+ * of every layer (a multi-layer dirichlet block copies those rows from h_initial after every layer, model.py:298; otherwise the
+ * Dirichlet rows of d_w).  Any depth: n_layers > 1 needs psignn_f_param_vjp_workspace_floats + psignn_f_layers_workspace_floats
+ * floats of d_work (also for psignn_f_param_vjp / _p and psignn_f_vjp_backward at that depth).  A multi-layer mixed block
+ * receives gradients for its last layer only; the earlier layers' slots are zero (mixed/psignn/model.py:221-245). */
+int psignn_f_param_vjp_ex(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h, const float* d_prb,
+                          const float* d_normals, const float* d_w, float* d_grad, float* d_out_h, float* d_out_init,
+                          float* d_work, void* stream);
 int psignn_f_param_vjp_p(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h,
                          const float* d_prb, const float* d_w, float* d_grad, float* d_out_h, float* d_work,
                          void* stream);
@@ -207,8 +233,8 @@ int psignn_f_param_vjp_p(const psignn_plan_t* plan, const float* d_weights, int 
  * parameters (d_grad, layout above) and w.r.t. h (d_grad_h, (N,10)).  Replaces autograd's double backward through
  * jac_loss_estimate -- autograd.grad(f0, z0, v, create_graph=True), dirichlet/psignn/model.py:416-435 -- when the
  * Jacobian regulariser is part of the loss (jac_weight, training_class.py:156-159): with g = J^T v and
- * jac_loss = |g|^2 / (N d), pass gbar = (d loss / d jac_loss) * 2 g / (N d).  Caller's numbering; single-layer
- * blocks of both families (mixed: d_normals required, d_grad also covers phi_neumann | update_neumann).  d_work: psignn_f_vjp_backward_workspace_floats(plan) floats. */
+ * jac_loss = |g|^2 / (N d), pass gbar = (d loss / d jac_loss) * 2 g / (N d).  Caller's numbering; blocks of both
+ * families and any depth (multi-layer: d_work grows by psignn_f_layers_workspace_floats) (mixed: d_normals required, d_grad also covers phi_neumann | update_neumann).  d_work: psignn_f_vjp_backward_workspace_floats(plan) floats. */
 int64_t psignn_f_vjp_backward_workspace_floats(const psignn_plan_t* plan);
 int psignn_f_vjp_backward(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h,
                           const float* d_prb, const float* d_normals, const float* d_v, const float* d_gbar, float* d_grad,
@@ -341,7 +367,9 @@ int psignn_broyden_batchable(int n, psignn_broyden_t* const* solvers);
 /* Adjoint fixed point y = J_f(h*)^T y + grad with the same Broyden machinery, the VJP kernel as the map, y_0 = 0.
  * replaces: the backward hook of DeepEquilibrium.forward (dirichlet/psignn/model.py:210-223), i.e.
  *           solver(lambda y: autograd.grad(new_H, H, y) + grad, zeros, bw_thres, bw_tol).
- * All tensors in the caller's numbering. */
+ * All tensors in the caller's numbering.  Multi-layer dirichlet blocks: the layer states h_1..h_{L-1} at h* are evaluated once
+ * per solve into memory the solver owns (allocated on the first such solve, freed with the solver); every iteration then runs
+ * the L backward layers only. */
 int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* d_weights, int n_layers, const float* d_h_star,
                                  const float* d_prb, const float* d_normals, const float* d_grad, double eps,
                                  int poll_every, float* d_result, psignn_solve_info_t* h_info,

@@ -53,6 +53,9 @@ SIGNATURES = {
     "psignn_phi": (_INT, [_P, _P, _INT, _INT, _INT, _P, _P, _P, _P]),
     "psignn_f_jvp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P]),
     "psignn_f_jvp_p": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P]),
+    "psignn_f_jvp_pw": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P]),
+    "psignn_f_param_vjp_ex": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "psignn_f_layers_workspace_floats": (_I64, [_P, _INT]),
     "psignn_lin_create": (_INT, [_P, _P]),
     "psignn_lin_destroy": (None, [_P]),
     "psignn_lin_bytes": (C.c_size_t, [_P]),

@@ -434,6 +434,21 @@ extern "C" int psignn_phi(const psignn_plan_t* p, const float* W, int nl, int la
 
 int psignn_f_tile_jvp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* v,
                       float* out, hipStream_t st);
+int psignn_f_layers_jvp_stateless(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* v,
+                                  float* out, float* work, float* lw, hipStream_t st);
+
+// Layer l of a dirichlet block on the gather kernels (caller numbering): its value at h (v == NULL; h0 = h_initial's
+// Dirichlet rows) or its tangent along v.  LayerNorm on the last layer only.
+int psignn_f_gather_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* h0,
+                          const float* prb, const float* v, float* out, float* work, hipStream_t st) {
+  ARG_CHECK(p && !p->mixed && l >= 0 && l < nl, "gather layer: dirichlet plans, 0 <= layer < n_layers");
+  if (v)
+    launch_layer<2, false, true>(p, W, nl, l, l == nl - 1, h, h0, prb, nullptr, v, out, work, nullptr, 0, st);
+  else
+    launch_layer<2, false, false>(p, W, nl, l, l == nl - 1, h, h0, prb, nullptr, nullptr, out, work, nullptr, 0, st);
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
 
 // plan-order JVP (tiled single-layer dirichlet plans): the form a Krylov solver that keeps its vectors in plan order uses
 extern "C" int psignn_f_jvp_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
@@ -443,15 +458,28 @@ extern "C" int psignn_f_jvp_p(const psignn_plan_t* p, const float* W, int nl, co
   return psignn_f_tile_jvp(p, W, nl, h, prb, nrm, v, out, (hipStream_t)stream);
 }
 
+// plan-order JVP with a workspace: any depth (multi-layer dirichlet blocks evaluate their layer states into d_work)
+extern "C" int psignn_f_jvp_pw(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
+                               const float* nrm, const float* v, float* out, float* work, void* stream) {
+  ARG_CHECK(p && W && h && prb && v && out, "NULL argument");
+  ARG_CHECK(out != v && out != h, "out must not alias its inputs");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  if (!p->tiled) return psignn_f_jvp(p, W, nl, h, prb, nrm, v, out, work, stream);   // plan order == caller order
+  if (p->mixed || nl == 1) return psignn_f_tile_jvp(p, W, nl, h, prb, nrm, v, out, (hipStream_t)stream);
+  ARG_CHECK(work, "a multi-layer JVP needs a workspace");
+  return psignn_f_layers_jvp_stateless(p, W, nl, h, prb, v, out, work, work + psignn_f_workspace_floats(p), (hipStream_t)stream);
+}
+
 extern "C" int psignn_f_jvp(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
                             const float* nrm, const float* v, float* out, float* work, void* stream) {
   int rc = f_args_ok(p, W, nl, h, prb, nrm, out, work);
   if (rc) return rc;
   ARG_CHECK(v != nullptr && out != v, "v is NULL or aliases out");
-  ARG_CHECK(p->mixed || nl == 1, "JVP of a multi-layer dirichlet block is not implemented");
   hipStream_t st = (hipStream_t)stream;
+  const bool layers = !p->mixed && nl > 1;   // chain of single-layer JVPs (fgnn_layers.hip); d_work has the layer part too
+  float* lw = layers ? work + psignn_f_workspace_floats(p) : nullptr;
   KNOB_INT(mixed_tiled, [] { const char* e = getenv("PSIGNN_MIXED_JVP"); return (int)!(e && strcmp(e, "gather") == 0); }());
-  if (p->tiled && (p->mixed ? mixed_tiled : nl == 1)) {  // caller numbering -> plan order -> tiled kernel -> caller numbering
+  if (p->tiled && (p->mixed ? mixed_tiled : 1)) {  // caller numbering -> plan order -> tiled kernel -> caller numbering
     const int64_t N = p->N;
     const int P = p->mixed ? 3 : 2;
     float* hp = work;
@@ -463,9 +491,12 @@ extern "C" int psignn_f_jvp(const psignn_plan_t* p, const float* W, int nl, cons
     if ((rc = psignn_plan_permute(p, v, D, vp, 1, stream))) return rc;
     if ((rc = psignn_plan_permute(p, prb, P, pp, 1, stream))) return rc;
     if (p->mixed && (rc = psignn_plan_permute(p, nrm, 2, np, 1, stream))) return rc;
-    if ((rc = psignn_f_tile_jvp(p, W, nl, hp, pp, p->mixed ? np : nullptr, vp, op, st))) return rc;
+    if (layers) rc = psignn_f_layers_jvp_stateless(p, W, nl, hp, pp, vp, op, nullptr, lw, st);   // tile kernels: no scratch
+    else rc = psignn_f_tile_jvp(p, W, nl, hp, pp, p->mixed ? np : nullptr, vp, op, st);
+    if (rc) return rc;
     return psignn_plan_permute(p, op, D, out, 0, stream);
   }
+  if (layers) return psignn_f_layers_jvp_stateless(p, W, nl, h, prb, v, out, work, lw, st);
   if (p->mixed)
     launch_layer<3, true, true>(p, W, nl, nl - 1, 1, h, h, prb, nrm, v, out, work, nullptr, 0, st);
   else

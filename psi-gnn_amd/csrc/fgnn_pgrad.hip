@@ -212,6 +212,53 @@ __global__ __launch_bounds__(256) void k_pgrad_reduce(int nblk, int nt, const fl
   if (sub == 0 && off >= 0) grad[off] = (float)s;
 }
 
+// the single-layer maps moved to another layer's section of the flat gradient: every entry past the shared block + shift
+// (shift = l * LAYER_SZ: layer l; mixed family, l = n_layers - 1: also moves phi_neumann / update_neumann to phi_neu(n_layers))
+template <int P>
+struct MapShift {
+  int shift;
+  __device__ int operator()(int t, int i, int j) const {
+    const int off = pg_offset<P>(t, i, j);
+    return off >= WLayout<P>::SHARED_SZ ? off + shift : off;
+  }
+};
+// k_pgrad_reduce that ADDS into the gradient: the layers of a multi-layer block are reduced one after the other into one
+// flat gradient (zeroed first), so the shared entries (alpha) accumulate over the layers in a fixed order
+template <class Map>
+__global__ __launch_bounds__(256) void k_pgrad_reduce_acc(int nblk, int nt, const float* __restrict__ part,
+                                                          float* __restrict__ grad, Map map) {
+  const int e = blockIdx.x * 32 + (threadIdx.x >> 3);
+  const int sub = threadIdx.x & 7;
+  const int t = e >> 8, i = (e >> 4) & 15, j = e & 15;
+  const int off = map(t, i, j);
+  double s = 0.0;
+  if (off >= 0)
+    for (int b = sub; b < nblk; b += 8) s += (double)part[(int64_t)b * nt * 256 + e];
+  s += __shfl_xor(s, 4);
+  s += __shfl_xor(s, 2);
+  s += __shfl_xor(s, 1);
+  if (sub == 0 && off >= 0) grad[off] += (float)s;
+}
+
+static inline int pgrad_blocks(int64_t N, int* nodes_per_wave);
+
+// records of n_rec nodes -> layer l's section of the flat gradient (shift = l * LAYER_SZ): dirichlet, added to it (the layers
+// of a multi-layer block in turn); mixed, written (only the last layer acts)
+static void pg_reduce_layer(const psignn_plan* p, int64_t n_rec, const float* rec, float* part, float* grad, int shift,
+                            hipStream_t st) {
+  int npw;
+  const int nblk = pgrad_blocks(n_rec, &npw);
+  if (p->mixed) {
+    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabX><<<nblk, 256, 0, st>>>(n_rec, npw, rec, part)));
+    PROF_BYTES((int64_t)nblk * 4 * TabX::NT * 256 * 4);
+    LAUNCH("k_pgrad_reduce_layer", st, (k_pgrad_reduce<<<TabX::NT * 8, 256, 0, st>>>(nblk * 4, TabX::NT, part, grad, MapShift<3>{shift})));
+  } else {
+    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabF><<<nblk, 256, 0, st>>>(n_rec, npw, rec, part)));
+    PROF_BYTES((int64_t)nblk * TabF::NT * 256 * 4);
+    LAUNCH("k_pgrad_reduce_layer", st, (k_pgrad_reduce_acc<<<TabF::NT * 8, 256, 0, st>>>(nblk, TabF::NT, part, grad, MapShift<2>{shift})));
+  }
+}
+
 static inline int pgrad_blocks(int64_t N, int* nodes_per_wave) {
   // a wave owns >= 64 nodes (multiple of 4); at most 1024 blocks of 4 waves
   int64_t npw = std::max<int64_t>(64, cdiv(cdiv(N, (int64_t)4096), (int64_t)4) * 4);
@@ -221,6 +268,53 @@ static inline int pgrad_blocks(int64_t N, int* nodes_per_wave) {
 
 int psignn_f_gather_vjp_rec(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
                             const float* w, float* out, float* work, float* rec, hipStream_t st);
+int psignn_f_gather_vjp_rec_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
+                                  const float* nrm, const float* w, float* out, float* work, float* rec, hipStream_t st);
+int psignn_f_tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb, const float* w,
+                            float* out, float* work, float* rec, hipStream_t st);
+int psignn_f_gather_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
+                              const float* w, float* out, float* work, hipStream_t st);
+int psignn_f_gather_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* h0,
+                          const float* prb, const float* v, float* out, float* work, hipStream_t st);
+int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
+                          hipStream_t st, bool gather);
+int psignn_f_layer_view(const psignn_plan* p, const float* W, int nl, int l, float* dst, hipStream_t st);
+float* psignn_f_layer_view_slot(const psignn_plan* p, int nl, float* lw);
+int psignn_f_dir_acc(const psignn_plan* p, const uint8_t* flags, const float* src, float* dst, int first, hipStream_t st);
+int psignn_f_add_rows(const psignn_plan* p, const float* a, const float* b, float* out, hipStream_t st);
+
+// Parameter VJP of a multi-layer dirichlet block (n_layers = L > 1): w_L = w, and for k = L-1 .. 0 the single-layer record pass
+// of layer k at (h_k, w_{k+1}) gives w_k = J_k^T w_{k+1} and layer k's records, reduced into layer k's section (alpha, shared,
+// accumulates over the layers in this fixed order; laynorm's records are zero except on the last layer).  d_init (optional):
+// the h_initial cotangent, the Dirichlet rows of w_L, ..., w_1 (the rows every layer copies from h_initial).  tiles: every
+// tensor in plan order, tile kernels; otherwise the caller's order and the gather kernels.  work: >= N * (90 + 320) floats +
+// the partial tiles; lw: psignn_f_layers_workspace_floats(p, L) floats.
+static int param_vjp_layers(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w,
+                            float* d_grad, float* d_out_h, float* d_init, float* work, float* lw, bool tiles, hipStream_t st) {
+  using L = WLayout<2>;
+  const int64_t N = p->N, ND = N * D;
+  float* scratch = work;                 // tiles: B (N, 40); gather: Pj + B (N, 60)
+  float* rec = work + N * 9 * D;
+  float* part = rec + N * PGREC;
+  const uint8_t* flags = tiles ? p->flags_p : p->flags;
+  int rc = psignn_f_layer_states(p, W, nl, h, prb, lw, scratch, st, !tiles);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)L::base_total(nl, false) * 4, st));
+  float* tb[2] = {lw + (nl - 1) * ND, lw + nl * ND};
+  const float* cur = w;
+  for (int k = nl - 1; k >= 0; --k) {
+    if (d_init && (rc = psignn_f_dir_acc(p, flags, cur, d_init, k == nl - 1, st))) return rc;
+    const float* hk = k == 0 ? h : lw + (k - 1) * ND;
+    float* dst = k == 0 ? d_out_h : tb[(nl - 1 - k) & 1];
+    rc = tiles ? psignn_f_tile_vjp_layer(p, W, nl, k, hk, prb, cur, dst, scratch, rec, st)
+               : psignn_f_gather_vjp_rec_layer(p, W, nl, k, hk, prb, nullptr, cur, dst, scratch, rec, st);
+    if (rc) return rc;
+    pg_reduce_layer(p, N, rec, part, d_grad, k * L::LAYER_SZ, st);
+    cur = dst;
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
 
 extern "C" int64_t psignn_f_param_vjp_workspace_floats(const psignn_plan_t* p) {
   if (!p) return 0;
@@ -248,6 +342,11 @@ static int param_vjp_tiled(const psignn_plan* p, const float* W, int nl, const f
   if (p->mixed) {
     float* part = rec + N * TabX::NG * 16;
     HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<3>::base_total(nl, true) * 4, st));
+    if (nl > 1) {   // the last layer acts alone (mixed/psignn/model.py:221-245): its section, the earlier layers stay zero
+      pg_reduce_layer(p, N, rec, part, d_grad, (nl - 1) * WLayout<3>::LAYER_SZ, st);
+      HIP_TRY(hipGetLastError());
+      return PSIGNN_OK;
+    }
     LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabX><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
     LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabX::NT * 8, 256, 0, st>>>(nblk * 4, TabX::NT, part, d_grad, MapX())));
   } else {
@@ -264,14 +363,71 @@ static int param_vjp_tiled(const psignn_plan* p, const float* W, int nl, const f
 extern "C" int psignn_f_param_vjp_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
                                     const float* w, float* d_grad, float* d_out_h, float* work, void* stream) {
   ARG_CHECK(p && W && h && prb && w && d_grad && d_out_h && work, "NULL argument");
-  ARG_CHECK(p->tiled && !p->mixed && nl == 1,
-            "plan-order parameter gradients: tiled single-layer dirichlet plans (mixed plans: psignn_f_param_vjp, which takes the normals)");
+  ARG_CHECK(p->tiled && !p->mixed && nl >= 1 && nl <= 64,
+            "plan-order parameter gradients: tiled dirichlet plans (mixed plans: psignn_f_param_vjp, which takes the normals)");
+  if (nl > 1)   // work: psignn_f_param_vjp_workspace_floats + psignn_f_layers_workspace_floats
+    return param_vjp_layers(p, W, nl, h, prb, w, d_grad, d_out_h, nullptr, work, work + psignn_f_param_vjp_workspace_floats(p),
+                            true, (hipStream_t)stream);
   return param_vjp_tiled(p, W, nl, h, prb, nullptr, w, d_grad, d_out_h, work, (hipStream_t)stream);
 }
 
 // ---- backward of the VJP (the Jacobian regulariser's gradient; kernels and derivation in gather_backward.hip)
 int psignn_jacreg_records(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* nrm,
-                          const float* v, const float* gbar, float* out_h, float* work, float* rec, hipStream_t st);
+                          const float* v, const float* gbar, float* out_h, float* work, float* rec, hipStream_t st, int ln);
+
+// Backward of the VJP of a multi-layer dirichlet block (caller's numbering, gather kernels).  phi = gbar . (J^T v) with
+// J = J_{L-1} ... J_0:  w_L = v, w_k = J_k^T w_{k+1};  gbar_0 = gbar, gbar_{k+1} = J_k gbar_k.
+//   1. for every layer k: the single-layer double backward at (h_k, w_{k+1}, gbar_k) (LayerNorm off below the last layer) on a
+//      single-layer weight view of layer k -> layer k's parameter terms and c_k = d/dh_k with h_k held;
+//   2. back through the forward chain: a_{L-1} = c_{L-1}, a_k = c_k + J_k^T a_{k+1} with layer k's parameter-VJP terms at
+//      (h_k, a_{k+1});  d phi / d h = a_0.
+// Layer workspace slots: states (L-1) | w_1..w_{L-1} | gbar_1..gbar_{L-1} | c_0..c_{L-1} | two carried a | one product.
+static int vjp_backward_layers(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* v,
+                               const float* gbar, float* d_grad, float* d_grad_h, float* work, float* lw, hipStream_t st) {
+  using L = WLayout<2>;
+  const int64_t N = p->N, ND = N * D;
+  float* S = lw;
+  float* Wc = S + (nl - 1) * ND;
+  float* G = Wc + (nl - 1) * ND;
+  float* C = G + (nl - 1) * ND;
+  float* A = C + nl * ND;
+  float* T = A + 2 * ND;
+  float* view = psignn_f_layer_view_slot(p, nl, lw);
+  float* rec = work + N * 17 * D;
+  float* part2 = rec + 2 * N * PGREC;   // after the two record sets of the double backward
+  float* part1 = rec + N * PGREC;       // after the one record set of a parameter-VJP pass
+  auto s_ = [&](int k) -> const float* { return k == 0 ? h : S + (k - 1) * ND; };
+  int rc = psignn_f_layer_states(p, W, nl, h, prb, S, work, st, true);
+  if (rc) return rc;
+  const float* cur = v;
+  for (int k = nl - 1; k >= 1; --k) {
+    if ((rc = psignn_f_gather_vjp_layer(p, W, nl, k, s_(k), prb, cur, Wc + (k - 1) * ND, work, st))) return rc;
+    cur = Wc + (k - 1) * ND;
+  }
+  cur = gbar;
+  for (int k = 0; k + 1 < nl; ++k) {
+    if ((rc = psignn_f_gather_layer(p, W, nl, k, s_(k), s_(k), prb, cur, G + k * ND, work, st))) return rc;
+    cur = G + k * ND;
+  }
+  HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)L::base_total(nl, false) * 4, st));
+  for (int k = 0; k < nl; ++k) {
+    if ((rc = psignn_f_layer_view(p, W, nl, k, view, st))) return rc;
+    const float* wk1 = k == nl - 1 ? v : Wc + k * ND;
+    const float* gk = k == 0 ? gbar : G + (k - 1) * ND;
+    if ((rc = psignn_jacreg_records(p, view, s_(k), prb, nullptr, wk1, gk, C + k * ND, work, rec, st, k == nl - 1))) return rc;
+    pg_reduce_layer(p, 2 * N, rec, part2, d_grad, k * L::LAYER_SZ, st);
+  }
+  const float* a = C + (nl - 1) * ND;
+  for (int k = nl - 2; k >= 0; --k) {
+    if ((rc = psignn_f_gather_vjp_rec_layer(p, W, nl, k, s_(k), prb, nullptr, a, T, work, rec, st))) return rc;
+    pg_reduce_layer(p, N, rec, part1, d_grad, k * L::LAYER_SZ, st);
+    float* dst = k == 0 ? d_grad_h : A + (k & 1) * ND;
+    if ((rc = psignn_f_add_rows(p, C + k * ND, T, dst, st))) return rc;
+    a = dst;
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
 
 extern "C" int64_t psignn_f_vjp_backward_workspace_floats(const psignn_plan_t* p) {
   if (!p) return 0;
@@ -288,14 +444,27 @@ extern "C" int psignn_f_vjp_backward(const psignn_plan_t* p, const float* W, int
                                      const float* nrm, const float* v, const float* gbar, float* d_grad, float* d_grad_h,
                                      float* work, void* stream) {
   ARG_CHECK(p && W && h && prb && v && gbar && d_grad && d_grad_h && work, "NULL argument");
-  ARG_CHECK(nl == 1, "the backward of the VJP is implemented for single-layer blocks");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = p->N;
   float* rec = work + N * 17 * D;
   int npw;
   const int nblk = pgrad_blocks(2 * N, &npw);
-  int rc = psignn_jacreg_records(p, W, h, prb, nrm, v, gbar, d_grad_h, work, rec, st);
+  // n_layers > 1: work holds psignn_f_vjp_backward_workspace_floats + psignn_f_layers_workspace_floats floats
+  float* lw = work + psignn_f_vjp_backward_workspace_floats(p);
+  if (nl > 1 && !p->mixed) return vjp_backward_layers(p, W, nl, h, prb, v, gbar, d_grad, d_grad_h, work, lw, st);
+  int rc;
+  if (nl > 1) {   // mixed: the last layer acts alone -> the single-layer form on a view of it, into its section
+    float* view = psignn_f_layer_view_slot(p, nl, lw);
+    if ((rc = psignn_f_layer_view(p, W, nl, nl - 1, view, st))) return rc;
+    if ((rc = psignn_jacreg_records(p, view, h, prb, nrm, v, gbar, d_grad_h, work, rec, st, 1))) return rc;
+    HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<3>::base_total(nl, true) * 4, st));
+    pg_reduce_layer(p, 2 * N, rec, rec + 2 * N * TabX::NG * 16, d_grad, (nl - 1) * WLayout<3>::LAYER_SZ, st);
+    HIP_TRY(hipGetLastError());
+    return PSIGNN_OK;
+  }
+  rc = psignn_jacreg_records(p, W, h, prb, nrm, v, gbar, d_grad_h, work, rec, st, 1);
   if (rc) return rc;
   if (p->mixed) {
     float* part = rec + 2 * N * TabX::NG * 16;
@@ -550,17 +719,47 @@ extern "C" int psignn_residual_t(const psignn_plan_t* p, const float* d_a_ij, co
   return PSIGNN_OK;
 }
 
+extern "C" int psignn_f_param_vjp_ex(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
+                                     const float* nrm, const float* w, float* d_grad, float* d_out_h, float* d_out_init,
+                                     float* work, void* stream);
 // Caller-order parameter-VJP for every plan: tiled plans of both families run the tiled kernels (permutation passes around
 // them; mixed family since round 3); untiled plans run the global-gather kernels in PG mode.  d_normals: mixed only.
 extern "C" int psignn_f_param_vjp(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
                                   const float* nrm, const float* w, float* d_grad, float* d_out_h, float* work,
                                   void* stream) {
+  return psignn_f_param_vjp_ex(p, W, nl, h, prb, nrm, w, d_grad, d_out_h, nullptr, work, stream);
+}
+
+// Same, and the h_initial cotangent d_out_init (may be NULL): the Dirichlet rows of the cotangent on every layer's output
+// (a multi-layer dirichlet block copies them from h_initial after every layer; otherwise w's Dirichlet rows).  n_layers > 1:
+// work holds psignn_f_param_vjp_workspace_floats + psignn_f_layers_workspace_floats floats.
+extern "C" int psignn_f_param_vjp_ex(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
+                                     const float* nrm, const float* w, float* d_grad, float* d_out_h, float* d_out_init,
+                                     float* work, void* stream) {
   ARG_CHECK(p && W && h && prb && w && d_grad && d_out_h && work, "NULL argument");
-  ARG_CHECK(nl == 1, "parameter gradients are implemented for single-layer blocks");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
+  ARG_CHECK(d_out_init != w && d_out_init != h, "d_out_init must not alias its inputs");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = p->N;
   int rc;
+  if (d_out_init && (p->mixed || nl == 1) && (rc = psignn_f_dir_acc(p, p->flags, w, d_out_init, 1, st))) return rc;
+  if (nl > 1 && !p->mixed) {
+    float* lw = work + psignn_f_param_vjp_workspace_floats(p);
+    if (!p->tiled) return param_vjp_layers(p, W, nl, h, prb, w, d_grad, d_out_h, d_out_init, work, lw, false, st);
+    float* hp = work;
+    float* wp = hp + N * D;
+    float* op = wp + N * D;
+    float* pp = op + N * D;   // (N, 2)
+    float* rest = pp + N * 2;
+    float* ip = lw + (nl + 1) * N * D;   // the h_initial cotangent in plan order
+    if ((rc = psignn_plan_permute(p, h, D, hp, 1, stream))) return rc;
+    if ((rc = psignn_plan_permute(p, w, D, wp, 1, stream))) return rc;
+    if ((rc = psignn_plan_permute(p, prb, 2, pp, 1, stream))) return rc;
+    if ((rc = param_vjp_layers(p, W, nl, hp, pp, wp, d_grad, op, d_out_init ? ip : nullptr, rest, lw, true, st))) return rc;
+    if (d_out_init && (rc = psignn_plan_permute(p, ip, D, d_out_init, 0, stream))) return rc;
+    return psignn_plan_permute(p, op, D, d_out_h, 0, stream);
+  }
   KNOB_INT(mixed_tiled, [] { const char* e = getenv("PSIGNN_MIXED_PGRAD"); return (int)!(e && strcmp(e, "gather") == 0); }());
   if (p->tiled && (!p->mixed || mixed_tiled)) {
     const int P = p->mixed ? 3 : 2;
@@ -586,6 +785,11 @@ extern "C" int psignn_f_param_vjp(const psignn_plan_t* p, const float* W, int nl
   if (p->mixed) {
     float* part = rec + N * TabX::NG * 16;
     HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<3>::base_total(nl, true) * 4, st));
+    if (nl > 1) {   // the last layer's section (mixed/psignn/model.py:221-245)
+      pg_reduce_layer(p, N, rec, part, d_grad, (nl - 1) * WLayout<3>::LAYER_SZ, st);
+      HIP_TRY(hipGetLastError());
+      return PSIGNN_OK;
+    }
     LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabX><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
     LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabX::NT * 8, 256, 0, st>>>(nblk * 4, TabX::NT, part, d_grad, MapX())));
   } else {

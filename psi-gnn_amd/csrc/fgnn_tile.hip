@@ -881,6 +881,31 @@ int psignn_f_tile_forward(const psignn_plan* p, const float* W, int nl, const fl
   return PSIGNN_OK;
 }
 
+// Layer l of a dirichlet block at its own input state h (plan order; h0: the Dirichlet rows written after the layer):
+// the layer states a multi-layer derivative differentiates at (fgnn_layers.hip).  LayerNorm on the last layer only;
+// the same launches as the layer loop of psignn_f_tile_forward, so the states are bit-identical to the forward's.
+int psignn_f_tile_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* h0, const float* prb,
+                        float* out, hipStream_t st) {
+  ARG_CHECK(p && p->tiled && !p->mixed && l >= 0 && l < nl, "tiled layer: dirichlet plans, 0 <= layer < n_layers");
+  ARG_CHECK(W && h && h0 && prb && out && out != h, "bad arguments");
+  using L = WLayout<2>;
+  const int chunk = (int)cdiv(p->n_tiles, 8);
+  const unsigned grid = tile_grid(chunk);
+  size_t lds = std::max((size_t)p->max_rows * TileRow<false>::RS * 4, tile_lds_min());
+  const int32_t* tlist = tile_cost_order(p, chunk, st);
+  PROF_BYTES(89 * p->N + 20 * p->Ep);   // B_f of one layer (psignn_f_tile_forward)
+  if (stage1_mfma(false, false))
+    LAUNCH("k_f_tile_layer", st, (k_f_tile<2, false, false, true><<<grid, TILE_THREADS, lds, st>>>(
+        plain_args(), (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, h,
+        nullptr, 0, h0, prb, nullptr, out)));
+  else
+    LAUNCH("k_f_tile_layer", st, (k_f_tile<2, false, false, false><<<grid, TILE_THREADS, lds, st>>>(
+        plain_args(), (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, h,
+        nullptr, 0, h0, prb, nullptr, out)));
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
 // Fused Broyden step (single-layer models): x_next = x_cur + upd, f(x_next), g_new / x_next / norm partials.
 // Returns the number of partial entries per norm (n_tiles), or a negative error.
 int psignn_f_tile_fused(const psignn_plan* p, const float* W, int nl, float* xbuf, int64_t M, const int32_t* st_words,

@@ -1,5 +1,6 @@
 // Tiled Jacobian-vector product of f_theta (both families; the layer a solver iterates: single layer, or the last layer of
-// the mixed family's loop, which reads the original h -- mixed/psignn/model.py:221-245), plan order (gfx950).
+// the mixed family's loop, which reads the original h -- mixed/psignn/model.py:221-245; a multi-layer dirichlet block chains one
+// launch per layer, fgnn_layers.hip), plan order (gfx950).
 //
 // out = J_f(h) v: what the Newton-Krylov solver of BASELINE configs[4] needs once per inner iteration (the reference only
 // imports scipy's newton_krylov, utilities/solver.py:6; its finite-difference JVPs do not converge in fp32).
@@ -177,7 +178,8 @@ __device__ __forceinline__ void edge_pass_jvp_both(const uint4* __restrict__ slo
   }
 }
 
-template <int P, bool MIXED, bool MFMA1>
+// LN = false: the LayerNorm-off form of an intermediate layer of a multi-layer dirichlet block (launched as "k_jvp_tile_noln")
+template <int P, bool MIXED, bool MFMA1, bool LN = true>
 __global__ __launch_bounds__(TILE_THREADS) JVP_OCC void k_jvp_tile(int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
                                                            const int32_t* __restrict__ tile_ptr,
                                                            const int32_t* __restrict__ tile_slice,
@@ -464,6 +466,10 @@ __global__ __launch_bounds__(TILE_THREADS) JVP_OCC void k_jvp_tile(int n_tiles, 
   }
   }
   // ---- LayerNorm tangent (eps 1e-5, biased variance)
+  if constexpr (!LN) {
+    store10(out + n * D, dy);
+    return;
+  }
   mu *= (1.f / D);
   float var = 0.f;
 #pragma unroll
@@ -487,11 +493,14 @@ __global__ __launch_bounds__(TILE_THREADS) JVP_OCC void k_jvp_tile(int n_tiles, 
   store10(out + n * D, dy);
 }
 
+
 // h, prb, nrm (mixed plans), v, out in PLAN order.
 // groups (mixed plans): bit 0 = tiles without Neumann nodes, bit 1 = tiles holding Neumann nodes (fgnn_tile_lin.hip applies the
 // stored linearisation on the first group and this kernel on the second)
 int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
                              const float* v, float* out, int groups, hipStream_t st);
+int psignn_f_tile_jvp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
+                            const float* v, float* out, hipStream_t st);
 int psignn_f_tile_jvp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
                       const float* v, float* out, hipStream_t st) {
   return psignn_f_tile_jvp_groups(p, W, nl, h, prb, nrm, v, out, 3, st);
@@ -519,6 +528,14 @@ int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const
     HIP_TRY(hipGetLastError());
     return PSIGNN_OK;
   }
+  return psignn_f_tile_jvp_layer(p, W, nl, 0, h, prb, v, out, st);
+}
+
+// Layer l of a dirichlet block at its own input state h (plan order): LayerNorm on the last layer only.  A multi-layer JVP
+// chains these (fgnn_layers.hip).
+int psignn_f_tile_jvp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
+                            const float* v, float* out, hipStream_t st) {
+  ARG_CHECK(p && p->tiled && !p->mixed && l >= 0 && l < nl, "tiled JVP layer: dirichlet plans, 0 <= layer < n_layers");
   using L = WLayout<2>;
   const int chunk = (int)cdiv(p->n_tiles, 8);
   const size_t lds = std::max((size_t)p->max_rows * 40 * 4, tile_lds_min());
@@ -528,12 +545,22 @@ int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const
     const char* e = getenv("PSIGNN_JVP_STAGE1");
     return e ? (int)(strcmp(e, "mfma") == 0) : (int)JVP_STAGE1_DEFAULT_MFMA;
   }());
-  if (use_mfma)
-    LAUNCH("k_jvp_tile", st, (k_jvp_tile<2, false, true><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
-        (int)p->n_tiles, chunk, nullptr, JVP_TILE_ARGS, W, L::layer(0), L::tp_layer(nl, false, 0), 0, h, prb, nrm, v, out)));
-  else
-    LAUNCH("k_jvp_tile", st, (k_jvp_tile<2, false, false><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
-        (int)p->n_tiles, chunk, nullptr, JVP_TILE_ARGS, W, L::layer(0), L::tp_layer(nl, false, 0), 0, h, prb, nrm, v, out)));
+  const int lofs = L::layer(l), tofs = L::tp_layer(nl, false, l);
+#define JVP_LAYER_ARGS (int)p->n_tiles, chunk, nullptr, JVP_TILE_ARGS, W, lofs, tofs, 0, h, prb, nullptr, v, out
+  if (l == nl - 1) {
+    if (use_mfma)
+      LAUNCH("k_jvp_tile", st, (k_jvp_tile<2, false, true><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(JVP_LAYER_ARGS)));
+    else
+      LAUNCH("k_jvp_tile", st, (k_jvp_tile<2, false, false><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(JVP_LAYER_ARGS)));
+  } else {
+    // h, v, prb (8 N), flags read, the tangent written (40 N each); 20 bytes per directed edge (slot + attr)
+    PROF_BYTES(129 * p->N + 20 * p->Ep);
+    if (use_mfma)
+      LAUNCH("k_jvp_tile_noln", st, (k_jvp_tile<2, false, true, false><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(JVP_LAYER_ARGS)));
+    else
+      LAUNCH("k_jvp_tile_noln", st, (k_jvp_tile<2, false, false, false><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(JVP_LAYER_ARGS)));
+  }
+#undef JVP_LAYER_ARGS
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }

@@ -166,7 +166,9 @@ __device__ __forceinline__ void ln_fwd_bwd(const float* __restrict__ W, float mu
 #else
 #define VJPA_OCC
 #endif
-template <int P, bool MIXED, bool PG>
+// LN = false: the LayerNorm-off form of an intermediate layer of a multi-layer dirichlet block (launched as "k_vjp_tile_a_noln"):
+// dy = w, and the record groups that feed laynorm (14, 15) stay zero
+template <int P, bool MIXED, bool PG, bool LN = true>
 __global__ __launch_bounds__(VT) VJPA_OCC void k_vjp_tile_a(int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
                                                    const int32_t* __restrict__ tile_ptr,
                                                    const int32_t* __restrict__ tile_slice, const int32_t* __restrict__ halo,
@@ -436,7 +438,12 @@ __global__ __launch_bounds__(VT) VJPA_OCC void k_vjp_tile_a(int n_tiles, int chu
   // ---- backward: LayerNorm
   float w[D], dy[D];
   load10(wv + n * D, w);
-  ln_fwd_bwd<L>(W, mu, y, w, dy);
+  if constexpr (LN) {
+    ln_fwd_bwd<L>(W, mu, y, w, dy);
+  } else {
+#pragma unroll
+    for (int o = 0; o < D; ++o) dy[o] = w[o];
+  }
   float dal = 0.f, dupd[D];
   v2f g[5];
 #pragma unroll
@@ -531,10 +538,15 @@ __global__ __launch_bounds__(VT) VJPA_OCC void k_vjp_tile_a(int n_tiles, int chu
     mvb<D>(Wu + L::UPD_W1, L::CAT, 2 * D, dq, dm);
     rec_group(r + 160, reinterpret_cast<const float*>(dm), D);                 // 10: d mp_from
     rec_group(r + 176, dupd, D);                                               // 11: d upd0   (12, 13: pass B)
+    if constexpr (LN) {
 #pragma unroll
-    for (int o = 0; o < D; ++o) t[o] = w[o] * y[o];
-    rec_group(r + 224, t, D);                                                  // 14: w * yhat
-    rec_group(r + 240, w, D);                                                  // 15: w
+      for (int o = 0; o < D; ++o) t[o] = w[o] * y[o];
+      rec_group(r + 224, t, D);                                                // 14: w * yhat
+      rec_group(r + 240, w, D);                                                // 15: w
+    } else {
+      rec_group(r + 224, t, 0);
+      rec_group(r + 240, t, 0);
+    }
     // 16..19: dS[o] * (attr moments), index o*3 + c as in the W1 attr block; in-edges carry the mirrored attr
     float da[64];
     const float* dst = reinterpret_cast<const float*>(dS_to);
@@ -758,11 +770,12 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_b(int n_tiles, int chunk, const
 }
 
 // ---------------------------------------------------------------------------------------------- host
+static int tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb, const float* w,
+                          float* out, float* work, float* rec, hipStream_t st);
 static int tile_vjp_launch(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
                            const float* w, float* out, float* work, float* rec, hipStream_t st) {
   ARG_CHECK(p && p->tiled && (p->mixed || nl == 1), "tiled VJP: single-layer dirichlet plans, mixed plans");
   ARG_CHECK(!p->mixed || nrm, "mixed plan: needs unit normals");
-  ARG_CHECK(!(p->mixed && rec) || nl == 1, "parameter-gradient records: single-layer blocks");
   const int chunk = (int)cdiv(p->n_tiles, 8);
   const unsigned grid = (unsigned)(chunk * 8);
   const size_t lds_b = (size_t)p->max_rows * (20 + (p->mixed ? 1 : 0)) * 4;
@@ -799,17 +812,48 @@ static int tile_vjp_launch(const psignn_plan* p, const float* W, int nl, const f
     HIP_TRY(hipGetLastError());
     return PSIGNN_OK;
   }
+  return tile_vjp_layer(p, W, nl, 0, h, prb, w, out, work, rec, st);
+}
+
+// Layer l of a dirichlet block at its own input state h (plan order): LayerNorm on the last layer only.  A multi-layer VJP
+// chains these from the last layer down (fgnn_layers.hip).
+static int tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb, const float* w,
+                          float* out, float* work, float* rec, hipStream_t st) {
+  ARG_CHECK(p && p->tiled && !p->mixed && l >= 0 && l < nl, "tiled VJP layer: dirichlet plans, 0 <= layer < n_layers");
   using L = WLayout<2>;
+  const int chunk = (int)cdiv(p->n_tiles, 8);
+  const unsigned grid = (unsigned)(chunk * 8);
   const size_t lds_a = (size_t)p->max_rows * 20 * 4;
-#define VJP_ARGS_A (int)p->n_tiles, chunk, nullptr, VJP_PLAN, W, nl, L::layer(0), L::tp_layer(nl, false, 0), 0, h, prb, nrm, w, work, out, rec
-#define VJP_ARGS_B (int)p->n_tiles, chunk, VJP_PLAN, W, nl, L::layer(0), L::tp_layer(nl, false, 0), 0, h, work, out, rec
-  if (rec) {
-    LAUNCH("k_pgrad_tile_a", st, (k_vjp_tile_a<2, false, true><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));
-    LAUNCH("k_pgrad_tile_b", st, (k_vjp_tile_b<2, false, true><<<grid, VT, lds_b, st>>>(VJP_ARGS_B)));
+  const size_t lds_b = (size_t)p->max_rows * 20 * 4;
+  ARG_CHECK(lds_b <= 160 * 1024, "tile + halo rows exceed the LDS budget of the tiled VJP");
+  const int lofs = L::layer(l), tofs = L::tp_layer(nl, false, l);
+#define VJP_ARGS_A (int)p->n_tiles, chunk, nullptr, VJP_PLAN, W, nl, lofs, tofs, 0, h, prb, nullptr, w, work, out, rec
+#define VJP_ARGS_B (int)p->n_tiles, chunk, VJP_PLAN, W, nl, lofs, tofs, 0, h, work, out, rec
+  if (l == nl - 1) {
+    if (rec) {
+      LAUNCH("k_pgrad_tile_a", st, (k_vjp_tile_a<2, false, true><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));
+      LAUNCH("k_pgrad_tile_b", st, (k_vjp_tile_b<2, false, true><<<grid, VT, lds_b, st>>>(VJP_ARGS_B)));
+    } else {
+      LAUNCH("k_vjp_tile_a", st, (k_vjp_tile_a<2, false, false><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));
+      LAUNCH("k_vjp_tile_b", st, (k_vjp_tile_b<2, false, false><<<grid, VT, lds_b, st>>>(VJP_ARGS_B)));
+    }
   } else {
-    LAUNCH("k_vjp_tile_a", st, (k_vjp_tile_a<2, false, false><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));
-    LAUNCH("k_vjp_tile_b", st, (k_vjp_tile_b<2, false, false><<<grid, VT, lds_b, st>>>(VJP_ARGS_B)));
+    // pass A reads h, w (40 N each), prb (8 N), flags, writes B (160 N) and the node-local part (40 N) [+ the records];
+    // 20 bytes per directed edge
+    PROF_BYTES(289 * p->N + 20 * p->Ep + (rec ? (int64_t)p->N * PGREC * 4 : 0));
+    if (rec)
+      LAUNCH("k_pgrad_tile_a_noln", st, (k_vjp_tile_a<2, false, true, false><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));
+    else
+      LAUNCH("k_vjp_tile_a_noln", st, (k_vjp_tile_a<2, false, false, false><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));
+    // pass B reads h (40 N), B (160 N), the partial result (40 N), writes it (40 N) [+ two record groups]; 20 bytes per edge
+    PROF_BYTES(280 * p->N + 20 * p->Ep + (rec ? (int64_t)p->N * 128 : 0));
+    if (rec)
+      LAUNCH("k_pgrad_tile_b", st, (k_vjp_tile_b<2, false, true><<<grid, VT, lds_b, st>>>(VJP_ARGS_B)));
+    else
+      LAUNCH("k_vjp_tile_b", st, (k_vjp_tile_b<2, false, false><<<grid, VT, lds_b, st>>>(VJP_ARGS_B)));
   }
+#undef VJP_ARGS_A
+#undef VJP_ARGS_B
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
@@ -824,4 +868,9 @@ int psignn_f_tile_vjp_rec(const psignn_plan* p, const float* W, int nl, const fl
                           const float* w, float* out, float* work, float* rec, hipStream_t st) {
   ARG_CHECK(rec, "NULL record buffer");
   return tile_vjp_launch(p, W, nl, h, prb, nrm, w, out, work, rec, st);
+}
+// layer l of a dirichlet block (plan order), with records when rec != NULL
+int psignn_f_tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb, const float* w,
+                            float* out, float* work, float* rec, hipStream_t st) {
+  return tile_vjp_layer(p, W, nl, l, h, prb, w, out, work, rec, st);
 }

@@ -1,5 +1,6 @@
 // Vector-Jacobian product of f_theta:  out = w^T (d f / d h)  (gfx950), both families (a multi-layer mixed block only
-// applies its last layer, mixed/psignn/model.py:221-245; multi-layer dirichlet blocks are not supported).
+// applies its last layer, mixed/psignn/model.py:221-245; a multi-layer dirichlet block chains this kernel's layers,
+// fgnn_layers.hip).
 //
 // This is what the reference obtains from autograd -- torch.autograd.grad(new_H, H, v) -- inside the implicit
 // backward hook (dirichlet/psignn/model.py:210-223: Broyden on y = J^T y + grad), the Hutchinson Jacobian
@@ -97,7 +98,9 @@ __device__ __forceinline__ void pg_zero(float* __restrict__ g, int first, int la
   for (int i = first * 4; i < last * 4; ++i) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-template <int P, bool MIXED, bool PG>
+// LN = false: the LayerNorm-off form of an intermediate layer of a multi-layer dirichlet block (launched as "k_vjp_local_noln"):
+// dy = w, and the record groups that feed laynorm (14, 15) stay zero
+template <int P, bool MIXED, bool PG, bool LN = true>
 __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __restrict__ W, int lofs, int nofs, int unofs,
                                                    const int32_t* __restrict__ csr_ptr, const int32_t* __restrict__ csr_nbr,
                                                    const float* __restrict__ csr_attr, const int32_t* __restrict__ csc_ptr,
@@ -363,7 +366,7 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
   }
   var *= (1.f / D);
   const float rs = 1.f / sqrtf(var + 1e-5f);
-  // ---- backward: LayerNorm
+  // ---- backward: LayerNorm (LN = false: dy = w; the statistics above are then dead code)
   float dyh[D], dy[D];
   float m1 = 0.f, m2 = 0.f;
 #pragma unroll
@@ -378,7 +381,7 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
   float dal = 0.f, dupd[D];
 #pragma unroll
   for (int o = 0; o < D; ++o) {
-    dy[o] = rs * (dyh[o] - m1 - y[o] * m2);
+    dy[o] = LN ? rs * (dyh[o] - m1 - y[o] * m2) : w[o];
     dal = fmaf(dy[o], upd[o], dal);
     dupd[o] = al * dy[o];
     g[o] = dy[o];  // accumulates the node-local result; starts with the residual path y = x + ...
@@ -471,10 +474,14 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
     pg_group(r + 9 * 16, dmp_to, D);
     pg_group(r + 10 * 16, dmp_fr, D);
     pg_group(r + 11 * 16, dupd, D);
+    if constexpr (LN) {
 #pragma unroll
-    for (int o = 0; o < D; ++o) t[o] = w[o] * y[o];
-    pg_group(r + 14 * 16, t, D);
-    pg_group(r + 15 * 16, w, D);
+      for (int o = 0; o < D; ++o) t[o] = w[o] * y[o];
+      pg_group(r + 14 * 16, t, D);
+      pg_group(r + 15 * 16, w, D);
+    } else {
+      pg_zero(r, 14, 16);
+    }
     dsa[PG ? 60 : 0] = dsa[PG ? 61 : 0] = dsa[PG ? 62 : 0] = dsa[PG ? 63 : 0] = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
@@ -553,19 +560,31 @@ __global__ __launch_bounds__(256) void k_vjp_remote(int64_t N, const float* __re
   store10(out + u * D, g);
 }
 
+// layer < 0: the layer a single-layer VJP differentiates (the last one of a mixed block, layer 0 of a dirichlet block);
+// layer >= 0 (dirichlet): that layer at its own input state h, LayerNorm on the last layer only (fgnn_layers.hip)
 template <int P, bool MIXED, bool PG = false>
 static void launch_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
-                       const float* w, float* out, float* work, hipStream_t st, float* rec = nullptr) {
+                       const float* w, float* out, float* work, hipStream_t st, float* rec = nullptr, int layer_ = -1) {
   using L = WLayout<P>;
-  const int layer = MIXED ? nl - 1 : 0;
+  const int layer = layer_ >= 0 ? layer_ : (MIXED ? nl - 1 : 0);
+  const bool ln = MIXED || layer == nl - 1;
   const int lofs = L::layer(layer), nofs = L::phi_neu(nl), unofs = L::upd_neu(nl);
   const unsigned grid = (unsigned)cdiv(p->N, 256);
   float* Pj = work;                            // (N, 20 | 30)
   float* B = work + p->N * (MIXED ? 3 : 2) * D;  // (N, 40 | 60)
   LAUNCH("k_vjp_project", st, (k_vjp_project<P, MIXED><<<grid, 256, 0, st>>>(p->N, W, lofs, nofs, h, Pj)));
-  LAUNCH(PG ? "k_pgrad_local" : "k_vjp_local", st, (k_vjp_local<P, MIXED, PG><<<grid, 256, 0, st>>>(
-      p->N, W, lofs, nofs, unofs, p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr, p->flags, h, prb,
-      nrm, w, Pj, B, out, rec)));
+  if (ln) {
+    LAUNCH(PG ? "k_pgrad_local" : "k_vjp_local", st, (k_vjp_local<P, MIXED, PG><<<grid, 256, 0, st>>>(
+        p->N, W, lofs, nofs, unofs, p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr, p->flags, h, prb,
+        nrm, w, Pj, B, out, rec)));
+  } else if constexpr (!MIXED) {
+    // reads h, w (40 N each), prb (8 N), flags, CSR + CSC (4 + 4 + 12 bytes per edge each way), Pj per edge (80 bytes);
+    // writes B (160 N) and the node-local part (40 N) [+ the records]
+    PROF_BYTES(289 * p->N + 120 * (int64_t)p->E + (PG ? (int64_t)p->N * PgRec<false>::SZ * 4 : 0));
+    LAUNCH(PG ? "k_pgrad_local_noln" : "k_vjp_local_noln", st, (k_vjp_local<2, false, PG, false><<<grid, 256, 0, st>>>(
+        p->N, W, lofs, nofs, unofs, p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr, p->flags, h, prb,
+        nrm, w, Pj, B, out, rec)));
+  }
   LAUNCH(PG ? "k_pgrad_remote" : "k_vjp_remote", st, (k_vjp_remote<P, MIXED, PG><<<grid, 256, 0, st>>>(
       p->N, W, lofs, nofs, p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr, Pj, B, out, rec)));
 }
@@ -581,28 +600,57 @@ int psignn_f_gather_vjp_rec(const psignn_plan* p, const float* W, int nl, const 
   return PSIGNN_OK;
 }
 
+// layer l of a dirichlet block on the gather kernels (caller numbering), LayerNorm on the last layer only; work: N * 60 floats
+int psignn_f_gather_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
+                              const float* w, float* out, float* work, hipStream_t st) {
+  ARG_CHECK(p && !p->mixed && l >= 0 && l < nl, "gather VJP layer: dirichlet plans, 0 <= layer < n_layers");
+  launch_vjp<2, false>(p, W, nl, h, prb, nullptr, w, out, work, st, nullptr, l);
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
+// record mode of layer l (dirichlet: any layer, LayerNorm on the last only; mixed: l = nl - 1); work: N * 90 floats
+int psignn_f_gather_vjp_rec_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
+                                  const float* nrm, const float* w, float* out, float* work, float* rec, hipStream_t st) {
+  ARG_CHECK(l >= 0 && l < nl && (!p->mixed || l == nl - 1), "gather VJP records: bad layer");
+  if (p->mixed)
+    launch_vjp<3, true, true>(p, W, nl, h, prb, nrm, w, out, work, st, rec, l);
+  else
+    launch_vjp<2, false, true>(p, W, nl, h, prb, nrm, w, out, work, st, rec, l);
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
 int psignn_f_tile_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* w,
                       float* out, float* work, hipStream_t st);
+int psignn_f_layers_vjp_stateless(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w,
+                                  float* out, float* work, float* lw, hipStream_t st);
 
-// plan-order VJP: tiled kernels where the plan has tiles (dirichlet, single layer), gather kernels otherwise
+// plan-order VJP: tiled kernels where the plan has tiles, gather kernels otherwise.  Multi-layer dirichlet blocks chain the
+// single-layer VJPs (fgnn_layers.hip); their work holds psignn_f_workspace_floats + psignn_f_layers_workspace_floats floats.
 extern "C" int psignn_f_vjp_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
                               const float* nrm, const float* w, float* out, float* work, void* stream) {
   ARG_CHECK(p && W && h && prb && w && out && work, "NULL argument");
   ARG_CHECK(out != w && out != h, "out must not alias its inputs");
   if (p->tiled && (p->mixed || nl == 1)) return psignn_f_tile_vjp(p, W, nl, h, prb, nrm, w, out, work, (hipStream_t)stream);
-  ARG_CHECK(!p->tiled, "plan-order VJP of a tiled multi-layer dirichlet plan is not available");
+  if (p->tiled) {
+    ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+    return psignn_f_layers_vjp_stateless(p, W, nl, h, prb, w, out, work, work + psignn_f_workspace_floats(p), (hipStream_t)stream);
+  }
   return psignn_f_vjp(p, W, nl, h, prb, nrm, w, out, work, stream);
 }
 
 extern "C" int psignn_f_vjp(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
                             const float* nrm, const float* w, float* out, float* work, void* stream) {
   ARG_CHECK(p && W && h && prb && w && out && work, "NULL argument");
-  ARG_CHECK(p->mixed || nl == 1, "VJP of a multi-layer dirichlet block is not implemented");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
   ARG_CHECK(out != w && out != h, "out must not alias its inputs");
   hipStream_t st = (hipStream_t)stream;
+  const bool layers = !p->mixed && nl > 1;   // chain of single-layer VJPs (fgnn_layers.hip); d_work has the layer part too
+  float* lw = layers ? work + psignn_f_workspace_floats(p) : nullptr;
   KNOB_INT(mixed_tiled, [] { const char* e = getenv("PSIGNN_MIXED_VJP"); return (int)!(e && strcmp(e, "gather") == 0); }());
-  if (p->tiled && (p->mixed ? mixed_tiled : nl == 1)) {
+  if (p->tiled && (p->mixed ? mixed_tiled : 1)) {
     // caller numbering -> plan order -> tiled kernels -> caller numbering
     const int64_t N = p->N;
     const int P = p->mixed ? 3 : 2;
@@ -617,9 +665,12 @@ extern "C" int psignn_f_vjp(const psignn_plan_t* p, const float* W, int nl, cons
     if ((rc = psignn_plan_permute(p, w, D, wp, 1, stream))) return rc;
     if ((rc = psignn_plan_permute(p, prb, P, pp, 1, stream))) return rc;
     if (p->mixed && (rc = psignn_plan_permute(p, nrm, 2, np, 1, stream))) return rc;
-    if ((rc = psignn_f_tile_vjp(p, W, nl, hp, pp, p->mixed ? np : nullptr, wp, op, Bw, st))) return rc;
+    if (layers) rc = psignn_f_layers_vjp_stateless(p, W, nl, hp, pp, wp, op, Bw, lw, st);
+    else rc = psignn_f_tile_vjp(p, W, nl, hp, pp, p->mixed ? np : nullptr, wp, op, Bw, st);
+    if (rc) return rc;
     return psignn_plan_permute(p, op, D, out, 0, stream);
   }
+  if (layers) return psignn_f_layers_vjp_stateless(p, W, nl, h, prb, w, out, work, lw, st);
   if (p->mixed)
     launch_vjp<3, true>(p, W, nl, h, prb, nrm, w, out, work, st);
   else

@@ -238,7 +238,9 @@ __global__ __launch_bounds__(256) void k_jr_tangent(int64_t N, const float* __re
 }
 
 // step 2: node-level second order.  dir1[n] = d psi / d c_h (the direct part of d phi / d h).
-template <int P, bool MIXED>
+// LN = false: an intermediate layer of a multi-layer dirichlet block (no LayerNorm: psi = w . dy, so ybar = 0, dybar = w and
+// no laynorm factors); launched as "k_jr_node_noln"
+template <int P, bool MIXED, bool LN = true>
 __global__ __launch_bounds__(256) void k_jr_node(int64_t N, const float* __restrict__ W, const uint8_t* __restrict__ flags,
                                                  const float* __restrict__ h, const float* __restrict__ prb,
                                                  const float* __restrict__ nrm, const float* __restrict__ v,
@@ -346,7 +348,16 @@ __global__ __launch_bounds__(256) void k_jr_node(int64_t N, const float* __restr
     dy[o] = gx[o] + dal * upd[o] + al * dupd[o];
   }
   PHASE();
-  jr_layernorm(W + L::LN_G, w, y, dy, ybar, dybar, gln);
+  if constexpr (LN) {
+    jr_layernorm(W + L::LN_G, w, y, dy, ybar, dybar, gln);
+  } else {
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+      ybar[o] = 0.f;
+      dybar[o] = w[o];
+      gln[o] = 0.f;
+    }
+  }
   jr_group(r1 + 14 * 16, gln, D);
   float albar = 0.f, dalbar = 0.f, ub[D], dub[D];
 #pragma unroll
@@ -716,7 +727,7 @@ __global__ __launch_bounds__(256) void k_jr_edge_remote(int64_t N, const float* 
 
 template <int P, bool MIXED>
 static void jr_launch(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* nrm, const float* v,
-                      const float* gbar, float* out_h, float* work, float* rec, hipStream_t st) {
+                      const float* gbar, float* out_h, float* work, float* rec, hipStream_t st, bool ln = true) {
   using J = JrDims<MIXED>;
   const int64_t N = p->N;
   const unsigned grid = (unsigned)cdiv(N, 256);
@@ -729,7 +740,13 @@ static void jr_launch(const psignn_plan* p, const float* W, const float* h, cons
 #define JR_CSR p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr
   LAUNCH("k_jr_project", st, (k_jr_project<P, MIXED><<<grid, 256, 0, st>>>(N, W, h, gbar, Pb)));
   LAUNCH("k_jr_tangent", st, (k_jr_tangent<P, MIXED><<<grid, 256, 0, st>>>(N, W, JR_CSR, p->flags, h, gbar, Pb, cb, rec1, rec2)));
-  LAUNCH("k_jr_node", st, (k_jr_node<P, MIXED><<<grid, 256, 0, st>>>(N, W, p->flags, h, prb, nrm, v, gbar, cb, dir, rec1, rec2)));
+  if (ln) {
+    LAUNCH("k_jr_node", st, (k_jr_node<P, MIXED><<<grid, 256, 0, st>>>(N, W, p->flags, h, prb, nrm, v, gbar, cb, dir, rec1, rec2)));
+  } else if constexpr (!MIXED) {
+    // reads h, prb, v, gbar, cb (40 + 8 + 40 + 40 + 160 bytes per node), writes dir and the two node-level record sets
+    PROF_BYTES((int64_t)N * (288 + 40 + 2 * J::REC * 4));
+    LAUNCH("k_jr_node_noln", st, (k_jr_node<P, false, false><<<grid, 256, 0, st>>>(N, W, p->flags, h, prb, nrm, v, gbar, cb, dir, rec1, rec2)));
+  }
   if constexpr (MIXED)
     LAUNCH("k_jr_node_neumann", st, (k_jr_node_neumann<P><<<grid, 256, 0, st>>>(N, W, p->flags, h, prb, nrm, v, gbar, cb, dir, rec1, rec2)));
   LAUNCH("k_jr_edge_local", st, (k_jr_edge_local<P, MIXED, false><<<grid, 256, 0, st>>>(N, W, JR_CSR, p->flags, h, Pb, dir, B, out_h, rec1)));
@@ -741,12 +758,14 @@ static void jr_launch(const psignn_plan* p, const float* W, const float* h, cons
 
 // work: P (N, 40 | 60) | cb (N, 40) | B (N, 40 | 60) | dir (N, 10)  (<= N * 170 floats);  rec: (2 N, 320 | 480) = R1 then R2;
 // out_h: (N, 10) = d phi / d h
+// ln = 0: the LayerNorm-off form (an intermediate layer of a multi-layer dirichlet block).  W: a single-layer weight view.
 int psignn_jacreg_records(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* nrm,
-                          const float* v, const float* gbar, float* out_h, float* work, float* rec, hipStream_t st) {
+                          const float* v, const float* gbar, float* out_h, float* work, float* rec, hipStream_t st, int ln) {
+  ARG_CHECK(ln || !p->mixed, "the LayerNorm-off backward of the VJP is a dirichlet-family form");
   if (p->mixed)
     jr_launch<3, true>(p, W, h, prb, nrm, v, gbar, out_h, work, rec, st);
   else
-    jr_launch<2, false>(p, W, h, prb, nrm, v, gbar, out_h, work, rec, st);
+    jr_launch<2, false>(p, W, h, prb, nrm, v, gbar, out_h, work, rec, st, ln != 0);
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }

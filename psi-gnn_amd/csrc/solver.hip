@@ -74,6 +74,8 @@ struct psignn_broyden {
   // itself from the two g buffers (the same fp32 subtraction): f neither reads g_old nor writes dg -- 80 MB less per 1M-node step
   float* gbuf[2] = {nullptr, nullptr};
   float *upd = nullptr, *fx = nullptr, *fwork = nullptr;
+  float* lwork = nullptr;     // layer states of a multi-layer dirichlet block in the adjoint solve (allocated on first use)
+  int64_t lwork_floats = 0;
   float* nrm_part = nullptr;  // norm partials of the f / residual kernel: 2 * nn floats
   float* part2 = nullptr;     // three-sweep update: block partials of vT.dg, vT.g (2 * nblk floats)
   int uvu = 0;                // the update runs as three single-array sweeps U, V, U (broyden_alloc)
@@ -1306,7 +1308,7 @@ static int broyden_alloc(psignn_broyden* s) {
 extern "C" void psignn_broyden_destroy(psignn_broyden_t* s) {
   if (!s) return;
   void* ptrs[] = {s->U, s->V, s->xbuf, s->gbuf[0], s->gbuf[1], s->upd, s->fx, s->fwork, s->part, s->coef, s->st, s->nrm_part, s->part2, s->parta,
-                  s->rel_trace, s->abs_trace, s->h0p, s->prbp, s->nrmp, s->jpart};
+                  s->rel_trace, s->abs_trace, s->h0p, s->prbp, s->nrmp, s->jpart, s->lwork};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (s->h_st) (void)hipHostFree(s->h_st);
@@ -1884,6 +1886,10 @@ extern "C" int psignn_f_vjp(const psignn_plan_t* p, const float* W, int nl, cons
                             const float* nrm, const float* w, float* out, float* work, void* stream);
 extern "C" int psignn_f_vjp_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
                               const float* nrm, const float* w, float* out, float* work, void* stream);
+int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
+                          hipStream_t st, bool gather);
+int psignn_f_layers_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w, float* out,
+                        float* work, float* lw, hipStream_t st);
 
 // The Broyden loop of the adjoint solve; vjp(y, out): out = J_f(h*)^T y in the solve's numbering
 template <class F>
@@ -1919,9 +1925,29 @@ extern "C" int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* W,
   ARG_CHECK(W && h_star && prb && grad, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const psignn_plan* p = s->plan;
-  // tiled plans the tiled VJP covers (single-layer dirichlet, mixed): the whole solve in plan order; otherwise the caller's numbering
-  const bool tiled = p->tiled && (p->mixed || nl == 1);
+  // tiled plans: the whole solve in plan order; otherwise the caller's numbering
+  const bool tiled = p->tiled;
+  // multi-layer dirichlet block: the layer states h_1..h_{L-1} at h* are evaluated once per solve into solver-owned memory,
+  // each product then runs the L backward layers only (fgnn_layers.hip)
+  const bool layers = !p->mixed && nl > 1;
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
+  if (layers) {
+    const int64_t need = psignn_f_layers_workspace_floats(p, nl);
+    if (s->lwork_floats < need) {
+      if (s->lwork) HIP_TRY(hipFree(s->lwork));
+      s->bytes -= (size_t)s->lwork_floats * 4;
+      s->lwork = nullptr;
+      s->lwork_floats = 0;
+      if (hipMalloc((void**)&s->lwork, (size_t)need * 4) != hipSuccess) {
+        s->lwork = nullptr;
+        psignn_set_error("broyden: hipMalloc of the layer states (%lld floats) failed", (long long)need);
+        return PSIGNN_ENOMEM;
+      }
+      s->lwork_floats = need;
+      s->bytes += (size_t)need * 4;
+    }
+  }
   s->plan_order = tiled ? 1 : 0;
   int rc;
   if (tiled) {  // plan-order copies: h* -> fwork tail, prb -> prbp, grad -> dg (free until the first update)
@@ -1938,7 +1964,9 @@ extern "C" int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* W,
     grad = gr_p;
     prb = s->prbp;
   }
+  if (layers && (rc = psignn_f_layer_states(p, W, nl, h_star, prb, s->lwork, s->fwork, st, false))) return rc;
   auto vjp = [&](const float* y, float* out) {
+    if (layers) return psignn_f_layers_vjp(p, W, nl, h_star, prb, y, out, s->fwork, s->lwork, st);
     return tiled ? psignn_f_vjp_p(p, W, nl, h_star, prb, nrm, y, out, s->fwork, st)
                  : psignn_f_vjp(p, W, nl, h_star, prb, nrm, y, out, s->fwork, st);
   };

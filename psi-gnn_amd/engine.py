@@ -206,23 +206,31 @@ class MeshPlan:
                   "psignn_plan_export")
         return out
 
+    def _grown(self, attr, base_query, n_layers):
+        """One scratch buffer per kind, grown in place of the old one when a deeper block needs more: the kind's own floats
+        plus the layer workspace of a multi-layer block (``psignn_f_layers_workspace_floats``)."""
+        extra = int(nat.lib().psignn_f_layers_workspace_floats(self.handle, int(n_layers)))
+        if extra < 0:
+            raise nat.NativeError(f"n_layers = {n_layers} is out of range")
+        n = int(base_query(self.handle)) + extra
+        buf = getattr(self, attr)
+        if buf is None or buf.numel() < n:
+            buf = torch.empty(n, dtype=torch.float32, device=self.device)
+            setattr(self, attr, buf)
+        return buf
+
     def workspace(self):
-        if self._work is None:
-            n = int(nat.lib().psignn_f_workspace_floats(self.handle))
-            self._work = torch.empty(n, dtype=torch.float32, device=self.device)
-        return self._work
+        return self._grown("_work", nat.lib().psignn_f_workspace_floats, 1)
 
-    def pgrad_workspace(self):
-        if self._pwork is None:
-            n = int(nat.lib().psignn_f_param_vjp_workspace_floats(self.handle))
-            self._pwork = torch.empty(n, dtype=torch.float32, device=self.device)
-        return self._pwork
+    def derivative_workspace(self, n_layers):
+        """Scratch of the JVP / VJP entry points: ``workspace()``'s buffer, grown for a multi-layer block's layer states."""
+        return self._grown("_work", nat.lib().psignn_f_workspace_floats, n_layers)
 
-    def vjp_backward_workspace(self):
-        if self._jwork is None:
-            n = int(nat.lib().psignn_f_vjp_backward_workspace_floats(self.handle))
-            self._jwork = torch.empty(n, dtype=torch.float32, device=self.device)
-        return self._jwork
+    def pgrad_workspace(self, n_layers=1):
+        return self._grown("_pwork", nat.lib().psignn_f_param_vjp_workspace_floats, n_layers)
+
+    def vjp_backward_workspace(self, n_layers=1):
+        return self._grown("_jwork", nat.lib().psignn_f_vjp_backward_workspace_floats, n_layers)
 
     def permute(self, t, to_plan=True):
         """Rows of an (N, cols) float tensor between the caller's numbering and plan order."""
@@ -331,13 +339,13 @@ class FixedPointMap:
         with torch.cuda.device(Hc.device):
             nat.check(nat.lib().psignn_f_jvp(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
                                              nat.ptr(Hc), nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(Vc),
-                                             nat.ptr(out), nat.ptr(self.plan.workspace()),
+                                             nat.ptr(out), nat.ptr(self.plan.derivative_workspace(self.weights.n_layers)),
                                              nat.stream_ptr(Hc.device)), "psignn_f_jvp")
         return out
 
     def jvp_p(self, Hp, Vp, out=None):
-        """J_f(Hp) Vp with everything in plan order (tiled plans: single-layer dirichlet, mixed of any depth).  ``out``: a
-        contiguous (N, d) float32 tensor to write into (e.g. a row of a Krylov basis)."""
+        """J_f(Hp) Vp with everything in plan order (tiled plans, any depth; a multi-layer dirichlet block evaluates its layer
+        states first).  ``out``: a contiguous (N, d) float32 tensor to write into (e.g. a row of a Krylov basis)."""
         if self._p is None:
             self.fp(Hp)
         _, prbp, nrmp = self._p
@@ -347,9 +355,15 @@ class FixedPointMap:
         elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != Hc.numel():
             raise nat.NativeError("jvp_p: out must be a contiguous float32 tensor of the state's size")
         with torch.cuda.device(Hc.device):
-            nat.check(nat.lib().psignn_f_jvp_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
-                                               nat.ptr(Hc), nat.ptr(prbp), nat.ptr(nrmp), nat.ptr(Vc), nat.ptr(out),
-                                               nat.stream_ptr(Hc.device)), "psignn_f_jvp_p")
+            if self.weights.mixed or self.weights.n_layers == 1:
+                nat.check(nat.lib().psignn_f_jvp_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                                   nat.ptr(Hc), nat.ptr(prbp), nat.ptr(nrmp), nat.ptr(Vc), nat.ptr(out),
+                                                   nat.stream_ptr(Hc.device)), "psignn_f_jvp_p")
+            else:
+                nat.check(nat.lib().psignn_f_jvp_pw(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                                    nat.ptr(Hc), nat.ptr(prbp), nat.ptr(nrmp), nat.ptr(Vc), nat.ptr(out),
+                                                    nat.ptr(self.plan.derivative_workspace(self.weights.n_layers)),
+                                                    nat.stream_ptr(Hc.device)), "psignn_f_jvp_pw")
         return out
 
     # ---- one idle Broyden solver kept between solves of this map (utilities.solver.broyden without keep_trace / solver_obj):
@@ -399,12 +413,13 @@ class FixedPointMap:
         with torch.cuda.device(Hc.device):
             nat.check(nat.lib().psignn_f_vjp(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
                                              nat.ptr(Hc), nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(Wc), nat.ptr(out),
-                                             nat.ptr(self.plan.workspace()), nat.stream_ptr(Hc.device)),
+                                             nat.ptr(self.plan.derivative_workspace(self.weights.n_layers)),
+                                             nat.stream_ptr(Hc.device)),
                       "psignn_f_vjp")
         return out
 
     def vjp_p(self, Hp, Wp):
-        """vjp with Hp, Wp and the result in plan order (tiled kernels: single-layer dirichlet plans, mixed plans)."""
+        """vjp with Hp, Wp and the result in plan order (tiled kernels where the plan has tiles, any depth)."""
         if self._p is None:
             self.fp(Hp)
         _, prbp, nrmp = self._p
@@ -413,12 +428,13 @@ class FixedPointMap:
         with torch.cuda.device(Hc.device):
             nat.check(nat.lib().psignn_f_vjp_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
                                                nat.ptr(Hc), nat.ptr(prbp), nat.ptr(nrmp), nat.ptr(Wc), nat.ptr(out),
-                                               nat.ptr(self.plan.workspace()), nat.stream_ptr(Hc.device)),
+                                               nat.ptr(self.plan.derivative_workspace(self.weights.n_layers)),
+                                               nat.stream_ptr(Hc.device)),
                       "psignn_f_vjp_p")
         return out
 
     def param_vjp_p(self, Hp, Wp):
-        """(flat parameter gradient, Wp^T df/dh) at Hp, everything in plan order (tiled dirichlet plans).
+        """(flat parameter gradient, Wp^T df/dh) at Hp, everything in plan order (tiled dirichlet plans, any depth).
 
         The flat gradient follows the leading section of the packed weights; ``unpack_param_grads`` names it."""
         if self._p is None:
@@ -429,7 +445,7 @@ class FixedPointMap:
         grad = torch.empty(int(l.psignn_param_grad_size(int(self.weights.mixed), self.weights.n_layers)),
                            dtype=torch.float32, device=Hc.device)
         out = torch.empty_like(Hc)
-        work = self.plan.pgrad_workspace()
+        work = self.plan.pgrad_workspace(self.weights.n_layers)
         with torch.cuda.device(Hc.device):
             nat.check(l.psignn_f_param_vjp_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
                                              nat.ptr(Hc), nat.ptr(prbp), nat.ptr(Wc), nat.ptr(grad), nat.ptr(out),
@@ -439,23 +455,32 @@ class FixedPointMap:
     def param_vjp(self, H, Wv):
         """What ``loss.backward()`` leaves in the ``deqdss.f`` parameters for new_H = f(H) with cotangent Wv
         (dirichlet/psignn/model.py:203-225; mixed/psignn/model.py likewise): ({name: grad}, Wv^T df/dH) in the
-        caller's numbering.  Single-layer blocks of both families, tiled or not."""
+        caller's numbering.  Both families, any depth, tiled or not."""
+        grads, out, _ = self.param_vjp_init(H, Wv, with_init=False)
+        return grads, out
+
+    def param_vjp_init(self, H, Wv, with_init=True):
+        """``param_vjp`` and the gradient w.r.t. h_initial: ({name: grad}, Wv^T df/dH, Wv^T df/dH_init).  The latter is the
+        Dirichlet rows of the cotangent on every layer's output (those rows are copies of h_initial after every layer,
+        model.py:298); for a single-layer block, Wv on the Dirichlet rows."""
         Hc, Wc = _f32c(H), _f32c(Wv)
         l = nat.lib()
         grad = torch.empty(int(l.psignn_param_grad_size(int(self.weights.mixed), self.weights.n_layers)),
                            dtype=torch.float32, device=Hc.device)
         out = torch.empty_like(Hc)
+        g_init = torch.empty_like(Hc) if with_init else None
         with torch.cuda.device(Hc.device):
-            nat.check(l.psignn_f_param_vjp(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
-                                           nat.ptr(Hc), nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(Wc), nat.ptr(grad),
-                                           nat.ptr(out), nat.ptr(self.plan.pgrad_workspace()),
-                                           nat.stream_ptr(Hc.device)), "psignn_f_param_vjp")
-        return unpack_param_grads(grad, self.weights.n_layers, self.weights.mixed), out
+            nat.check(l.psignn_f_param_vjp_ex(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                              nat.ptr(Hc), nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(Wc), nat.ptr(grad),
+                                              nat.ptr(out), nat.ptr(g_init),
+                                              nat.ptr(self.plan.pgrad_workspace(self.weights.n_layers)),
+                                              nat.stream_ptr(Hc.device)), "psignn_f_param_vjp_ex")
+        return unpack_param_grads(grad, self.weights.n_layers, self.weights.mixed), out, g_init
 
     def vjp_backward(self, H, V, Gbar):
         """Gradient of  Gbar . (J_f(H)^T V)  with Gbar held constant: ({name: grad}, d / dH) -- what autograd's double
         backward computes for ``autograd.grad(f(H), H, V, create_graph=True)`` (jac_loss_estimate,
-        dirichlet/psignn/model.py:416-435).  Single-layer blocks of both families, caller's numbering."""
+        dirichlet/psignn/model.py:416-435).  Both families, any depth, caller's numbering."""
         Hc, Vc, Gc = _f32c(H), _f32c(V), _f32c(Gbar)
         l = nat.lib()
         grad = torch.empty(int(l.psignn_param_grad_size(int(self.weights.mixed), self.weights.n_layers)),
@@ -464,7 +489,7 @@ class FixedPointMap:
         with torch.cuda.device(Hc.device):
             nat.check(l.psignn_f_vjp_backward(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
                                               nat.ptr(Hc), nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(Vc), nat.ptr(Gc), nat.ptr(grad),
-                                              nat.ptr(out), nat.ptr(self.plan.vjp_backward_workspace()),
+                                              nat.ptr(out), nat.ptr(self.plan.vjp_backward_workspace(self.weights.n_layers)),
                                               nat.stream_ptr(Hc.device)), "psignn_f_vjp_backward")
         return unpack_param_grads(grad, self.weights.n_layers, self.weights.mixed), out
 
@@ -704,9 +729,16 @@ def dss_step_p(plan: "MeshPlan", wflat, t: int, alpha: float, hp, bprime_p):
 
 
 def unpack_param_grads(flat, n_layers=1, mixed=False):
-    """Name the entries of a flat parameter gradient (layout = leading section of ``pack_weights``)."""
-    if n_layers != 1:
-        raise nat.NativeError("parameter gradients are implemented for single-layer blocks")
+    """Name the entries of a flat parameter gradient (layout = leading section of ``pack_weights``): the shared modules,
+    then every layer's ``phi_to_list.k`` / ``phi_from_list.k`` / ``update_list.k`` (layer k's section starts k layer sizes
+    after layer 0's), then, mixed family, ``phi_neumann`` / ``update_neumann`` behind the last layer."""
+    if not 1 <= int(n_layers) <= 64:
+        raise nat.NativeError(f"n_layers = {n_layers} is out of range")
+    l = nat.lib()
+    size = int(l.psignn_param_grad_size(int(mixed), int(n_layers)))
+    lsz = int(l.psignn_param_grad_size(int(mixed), 2)) - int(l.psignn_param_grad_size(int(mixed), 1))
+    if flat.numel() != size:
+        raise nat.NativeError(f"flat gradient has {flat.numel()} entries, expected {size}")
     p = 3 if mixed else 2
     cat, ein = 3 * D + p, 2 * D + 3
     out, o = {}, 0
@@ -722,18 +754,19 @@ def unpack_param_grads(flat, n_layers=1, mixed=False):
     take("laynorm.bias", D)
     take("alpha.0.weight", 1, cat)
     take("alpha.0.bias", 1)
-    o = 64
-    for phi in ("phi_to_list", "phi_from_list"):
-        take(f"{phi}.0.mlp.mlp.0.weight", D, ein)
-        take(f"{phi}.0.mlp.mlp.0.bias", D)
-        take(f"{phi}.0.mlp.mlp.2.weight", D, D)
-        take(f"{phi}.0.mlp.mlp.2.bias", D)
-    take("update_list.0.mlp.0.weight", D, cat)
-    take("update_list.0.mlp.0.bias", D)
-    take("update_list.0.mlp.2.weight", D, D)
-    take("update_list.0.mlp.2.bias", D)
+    for k in range(int(n_layers)):
+        o = 64 + k * lsz
+        for phi in ("phi_to_list", "phi_from_list"):
+            take(f"{phi}.{k}.mlp.mlp.0.weight", D, ein)
+            take(f"{phi}.{k}.mlp.mlp.0.bias", D)
+            take(f"{phi}.{k}.mlp.mlp.2.weight", D, D)
+            take(f"{phi}.{k}.mlp.mlp.2.bias", D)
+        take(f"update_list.{k}.mlp.0.weight", D, cat)
+        take(f"update_list.{k}.mlp.0.bias", D)
+        take(f"update_list.{k}.mlp.2.weight", D, D)
+        take(f"update_list.{k}.mlp.2.bias", D)
     if mixed:
-        o += 244   # fold slots of the layer
+        o = 64 + int(n_layers) * lsz   # behind the last layer (its fold slots included)
         take("phi_neumann.mlp.mlp.0.weight", D, ein)
         take("phi_neumann.mlp.mlp.0.bias", D)
         take("phi_neumann.mlp.mlp.2.weight", D, D)

@@ -143,8 +143,8 @@ class _DEQFn(torch.autograd.Function):
     """new_H = f(H*) with H* = solver(f, H_init), differentiable the way the reference's training variant is
     (dirichlet/psignn/model.py:184-225): the forward solve runs without a graph; backward replaces the incoming
     gradient by the solution y of  y = J_f(H*)^T y + grad  (the reference's ``backward_hook``) and pushes y through
-    one application of f: parameter gradients from the HIP parameter-VJP kernels, and y on the Dirichlet rows for
-    ``H_init`` (those rows of f are copies of ``H_init``, model.py:298)."""
+    one application of f: parameter gradients from the HIP parameter-VJP kernels, and for ``H_init`` the Dirichlet
+    rows of the cotangent on every layer's output (those rows are copies of ``H_init`` after each layer, model.py:298)."""
 
     @staticmethod
     def forward(ctx, H_init, deq, batch, names, *params):
@@ -177,10 +177,8 @@ class _DEQFn(torch.autograd.Function):
         deq.last_backward = out_bw
         _log(deq.path_logs, "backward_iteration.csv", "\n{} \t {}".format(out_bw["lowest"], out_bw["nstep"]))
         y = out_bw["result"]
-        grads, _ = ctx.fmap.param_vjp(H_star, y)
-        tags = ctx.batch.tags.reshape(y.shape[0], -1)
-        col = 1 if deq.f.mixed else 0   # one-hot [interior, dirichlet, neumann] in the mixed family
-        g_init = torch.where(tags[:, col:col + 1] == 1, y, torch.zeros_like(y))
+        # g_init: the Dirichlet rows of the cotangent on every layer's output (f copies them from H_init after each layer)
+        grads, _, g_init = ctx.fmap.param_vjp_init(H_star, y)
         return (g_init, None, None, None) + tuple(grads[n] for n in ctx.names)
 
 
@@ -232,8 +230,6 @@ class DeepEquilibrium(nn.Module):
         The Jacobian regulariser carries its gradient w.r.t. the parameters of f (``_JacLossFn``; the reference's launch
         scripts train with ``jac_weight 1.0``)."""
         if torch.is_grad_enabled():
-            if self.f.n_layers != 1:
-                raise nat.NativeError("the training path is implemented for single-layer blocks")
             named = list(self.f.named_parameters())
             new_H = _DEQFn.apply(H_init, self, batch, tuple(n for n, _ in named), *[p for _, p in named])
             H_star = self.last_forward["result"]
@@ -318,7 +314,7 @@ class DeepEquilibrium(nn.Module):
             lin = self._linearization(fmap, H_star) if linearize else None
         if lin is not None:
             return lin.vjp_p, fmap.to_plan, fmap.from_plan
-        if fmap.plan.tiled and (fmap.weights.mixed or fmap.weights.n_layers == 1):
+        if fmap.plan.tiled:
             Hp = fmap.to_plan(H_star)
             return (lambda w: fmap.vjp_p(Hp, w)), fmap.to_plan, fmap.from_plan
         ident = lambda t: t
