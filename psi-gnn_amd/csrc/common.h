@@ -148,6 +148,9 @@ struct psignn_plan {
 
 #define TILE_MAX 256      // nodes per tile = threads per block of the tile kernel
 #define HALO_CAP 512      // halo entries stored per tile
+// Mixed plans: tile + halo rows at most 682, the 240-byte LDS rows of the Neumann tiles' JVP (k_jvp_tile) in 160 KiB.
+// The tile builder keeps a mixed plan with more rows untiled, so that every tile kernel runs on every tiled plan.
+#define MIXED_ROW_CAP (160 * 1024 / (60 * 4))
 #define ELL_EMPTY 0xFFFFu
 
 int psignn_tiles_build(psignn_plan* p, const float* d_pos, int tile_target, hipStream_t st);

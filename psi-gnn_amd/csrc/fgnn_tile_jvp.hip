@@ -514,7 +514,7 @@ int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const
     using L = WLayout<3>;
     const int lofs = L::layer(nl - 1), tofs = L::tp_layer(nl, true, nl - 1), tnofs = L::tp_neu(nl);
     const int na = (int)p->n_tiles_plain, nb = (int)(p->n_tiles - p->n_tiles_plain);
-    ARG_CHECK((size_t)p->max_rows * 60 * 4 <= 160 * 1024, "tile + halo rows exceed the LDS budget of the tiled JVP");
+    ARG_CHECK(p->max_rows <= MIXED_ROW_CAP, "tile + halo rows exceed the LDS budget of the tiled JVP");
     if (na > 0 && (groups & 1)) {   // tiles without Neumann nodes: 160-byte LDS rows, no Neumann branch
       const int chunk = (int)cdiv(na, 8);
       LAUNCH("k_jvp_tile", st, (k_jvp_tile<3, false, false><<<(unsigned)(chunk * 8), TILE_THREADS, (size_t)p->max_rows * 40 * 4, st>>>(

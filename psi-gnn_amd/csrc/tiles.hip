@@ -15,8 +15,8 @@
 //   3. per tile: halo = sorted distinct out-of-tile neighbours (both directions)
 //   4. per slice: pair-merged ELL slot-rows x 64 lanes: one 16-byte slot per neighbour {LDS row, IN/OUT, attr}
 //      (see 'pair-merged ELL' below), in the canonical neighbour order of the CSR/CSC plan
-// If a structure limit is exceeded (cell > SORT_CAP nodes, halo > HALO_CAP, degree > 255) the plan
-// stays untiled and the global-gather kernels (fgnn.hip) are used.
+// If a structure limit is exceeded (cell > SORT_CAP nodes, > CAND_CAP halo candidates, halo > HALO_CAP, > 255 slots, or, on
+// mixed plans, tile + halo > MIXED_ROW_CAP = 682 rows) the plan stays untiled and the global-gather kernels (fgnn.hip) are used.
 #include "common.h"
 #include <math.h>
 #include <string.h>
@@ -152,7 +152,8 @@ __global__ __launch_bounds__(256) void k_halo(const int32_t* __restrict__ tile_p
                                               const int32_t* __restrict__ inv, const int32_t* __restrict__ csr_ptr,
                                               const int32_t* __restrict__ csr_nbr, const int32_t* __restrict__ csc_ptr,
                                               const int32_t* __restrict__ csc_nbr, int32_t* __restrict__ halo,
-                                              int32_t* __restrict__ halo_cnt, int32_t* __restrict__ misc /* [0] err [1] max rows */) {
+                                              int32_t* __restrict__ halo_cnt, int row_cap,
+                                              int32_t* __restrict__ misc /* [0] err [1] max rows */) {
   __shared__ int32_t cand[CAND_CAP];
   __shared__ uint8_t keep[CAND_CAP];
   __shared__ int32_t n_cand, n_keep;
@@ -198,6 +199,7 @@ __global__ __launch_bounds__(256) void k_halo(const int32_t* __restrict__ tile_p
   if (threadIdx.x == 0) {
     halo_cnt[tile] = n_keep;
     if (n_keep > HALO_CAP) atomicOr(&misc[0], 4);
+    if ((t1 - t0) + n_keep > row_cap) atomicOr(&misc[0], 16);
     atomicMax(&misc[1], (t1 - t0) + n_keep);
   }
 }
@@ -484,7 +486,8 @@ static int tiles_build_mode(psignn_plan* p, const float* d_pos, int tile_target,
   k_inverse_perm<<<gn, TB, 0, st>>>(N, p->perm, p->inv, p->flags, p->flags_p);
   // ---- 3. halos
   k_halo<<<(unsigned)p->n_tiles, TB, 0, st>>>(p->tile_ptr, p->perm, p->inv, p->csr_ptr, p->csr_nbr, p->csc_ptr,
-                                               p->csc_nbr, p->halo, p->halo_cnt, misc);
+                                               p->csc_nbr, p->halo, p->halo_cnt,
+                                               p->mixed ? MIXED_ROW_CAP : TILE_MAX + HALO_CAP, misc);
   // ---- 4. slices / ELL
   k_slice_deg<<<(unsigned)cdiv(p->n_slices, 4), TB, 0, st>>>(p->n_slices, slice_tile, p->tile_slice, p->tile_ptr,
                                                               p->perm, p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr,
@@ -493,7 +496,7 @@ static int tiles_build_mode(psignn_plan* p, const float* d_pos, int tile_target,
   HT(hipMemcpyAsync(h_deg.data(), p->slice_deg, p->n_slices, hipMemcpyDeviceToHost, st));
   HT(hipMemcpyAsync(h_misc, misc, 8, hipMemcpyDeviceToHost, st));
   HT(hipStreamSynchronize(st));
-  if (h_misc[0]) goto done;  // halo or degree limit exceeded: stay untiled
+  if (h_misc[0]) goto done;  // candidate, halo, row or slot limit exceeded: stay untiled
   p->max_rows = h_misc[1];
   h_slice_off.resize(p->n_slices + 1);
   h_slice_off[0] = 0;
