@@ -407,6 +407,17 @@ int psignn_broyden_ext_finish(psignn_broyden_t* s, float* d_result, psignn_solve
                               double* h_rel_trace, double* h_abs_trace, void* stream);
 /* Same, for a problem that is not tied to a mesh plan (any vector length). */
 int psignn_broyden_create_n(psignn_broyden_t** out, int64_t n_elems, int seq_len, int threshold, int keep_trace);
+/* One constructor for every solver kind, with the element type of the stored rank-one pairs.  plan != NULL: a solver for that mesh
+ * (n_elems, seq_len: 0 or the plan's N * d, d; shard_elems as in psignn_broyden_create_for_batch); plan == NULL: a vector of n_elems
+ * elements, as psignn_broyden_create_n.  history = 0: fp32 pairs -- the same solver as create / create_n / create_for_batch give;
+ * history = 1: bf16 pairs, each rounded to nearest even when it is written, every quantity derived from a new pair taking its rounded
+ * value (so B = -I + sum U_j V_j^T over the stored bf16 values), arithmetic, iterate and update in fp32: half the pair memory and
+ * half the bytes each iteration streams; always the unfolded three-sweep update, not batchable (psignn_broyden_batchable = 0).
+ * Other values: PSIGNN_EINVAL.  psignn_broyden_get_pair returns a bf16 pair widened (exactly) to fp32.
+ * replaces: broyden(f, x0, threshold, eps) (dirichlet/psignn/utilities/solver.py:116-207) with its Us / VTs (:134-135, written at
+ *           :190-191) stored in bfloat16 instead of the iterate's dtype. */
+int psignn_broyden_create_opts(psignn_broyden_t** out, const psignn_plan_t* plan, int64_t n_elems, int seq_len, int threshold,
+                               int keep_trace, int64_t shard_elems, int history);
 
 /* ------------------------------------------------------------------------------------------
  * Picard iteration and Anderson acceleration: the vector work, norms, stop tests and the small bordered solve on the

@@ -43,8 +43,8 @@ def solve_shard_batched(model, meshes, device, indices=None, group=8):
     test per mesh).  Each mesh's result is bit-identical to its own solve with a solver of the same configuration
     (``DeviceBroyden(..., shard_elems=...)``: the sweeps' reduction shapes are sized for the shard) and agrees with the plain
     ``solve_shard`` path to solver tolerance; both families (a shard is all dirichlet or all mixed, as every dataset of the
-    reference is).  Meshes the batched solver cannot take together (untiled plans, different size classes, multi-layer blocks)
-    are solved one by one -- decided on the host before anything is allocated or launched; errors of the batched solve raise."""
+    reference is).  Meshes the batched solver cannot take together (untiled plans, different size classes, multi-layer blocks,
+    a bf16 ``broyden_history_dtype``) are solved one by one -- decided on the host before anything is allocated or launched; errors of the batched solve raise."""
     import importlib
     eng = importlib.import_module(__package__ + ".engine")
     slv = importlib.import_module(__package__ + ".utilities.solver")
@@ -61,7 +61,9 @@ def solve_shard_batched(model, meshes, device, indices=None, group=8):
             solved = None
             # batchable? decided on the host BEFORE any solver state is allocated: tiled plans of one family, single-layer
             # block; then (solvers exist, nothing solved yet) one size class.  Anything the batched solve raises is a real error.
+            # (a bf16 pair history is not batched: the batched kernels sweep fp32 pairs only)
             if (cfg["solver"] is slv.broyden and len(ids) > 1 and all(f.plan.tiled for f in fmaps)
+                    and cfg.get("broyden_history_dtype", torch.float32) == torch.float32
                     and len({f.plan.mixed for f in fmaps}) == 1 and fmaps[0].weights.n_layers == 1):
                 total = sum(f.plan.N for f in fmaps) * eng.D
                 solvers = [eng.DeviceBroyden(plan=f.plan, threshold=cfg["fw_thres"], keep_trace=False, shard_elems=total)

@@ -96,7 +96,9 @@ struct psignn_broyden {
   Status* h_st = nullptr;   // pinned host mirror
   size_t bytes = 0;
   int ext_iter = 0;
-  int64_t ld = 0;           // row pitch (floats) of U and V
+  int64_t ld = 0;           // row pitch (elements) of U and V
+  int hist = 0;             // element type of the stored pairs U, V: 0 fp32, 1 bf16 (psignn_broyden_create_opts; the buffers are then
+                            // __bf16 behind the float pointers, and the update always runs the unfolded three-sweep form)
   int stop_abs = 0;         // stop_mode of the next solve
   int64_t size_hint = 0;    // elements of ALL vectors swept together (batched shard): picks the vector width / j-split
   int plan_order = 1;       // 0 while iterates are kept in the caller's numbering (adjoint solve on the gather kernels)
@@ -386,8 +388,8 @@ __global__ __launch_bounds__(RB) void k_reduce_check(Status* st, const float* __
 // a, and U c / U b need only c and b: sweep 1 reads U for a; sweep 2 reads V ONCE for c, b AND V a; sweep 3 reads U for
 // U c, U b -- three single-array sweeps instead of four, the same arithmetic on every element and the same partial-sum shapes
 // (results bit-identical to the two-pass form; tests/test_gpu_parity.py::test_three_sweep_update_is_bitwise_identical).
-template <int VEC>
-__device__ __forceinline__ void sweep_u1_body(int64_t M, int k, const Status* __restrict__ st, const float* __restrict__ U,
+template <int VEC, class P = float>   // P: element type of the stored pairs (float, or __bf16 for a bf16-history solver)
+__device__ __forceinline__ void sweep_u1_body(int64_t M, int k, const Status* __restrict__ st, const P* __restrict__ U,
                                               const float* __restrict__ dxv, float* __restrict__ part, int ldp, int64_t ld) {
   __shared__ PairStash<1> sh;
   if (__builtin_amdgcn_readfirstlane(st->done)) return;
@@ -426,6 +428,11 @@ __global__ __launch_bounds__(TB) void k_sweep_u1(int64_t M, int k, const Status*
                                                  const float* __restrict__ dxv, float* __restrict__ part, int ldp, int64_t ld) {
   sweep_u1_body<VEC>(M, k, st, U, dxv, part, ldp, ld);
 }
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_sweep_u1_bf16(int64_t M, int k, const Status* __restrict__ st, const __bf16* __restrict__ U,
+                                                      const float* __restrict__ dxv, float* __restrict__ part, int ldp, int64_t ld) {
+  sweep_u1_body<VEC, __bf16>(M, k, st, U, dxv, part, ldp, ld);
+}
 
 // grid (max(k, 1), RA + 1): blocks (j, r < RA): row chunk r of column j of the a partials; block (0, RA): the iteration's bookkeeping (as k_reduce_check's)
 __device__ __forceinline__ void reduce_a_check_body(Status* st, const float* __restrict__ part, int nrows, int ldp, int thr, int k,
@@ -460,9 +467,10 @@ __global__ __launch_bounds__(RB) void k_reduce_a_check(Status* st, const float* 
 }
 
 // sweep 2: reads V once: partials of c_j = V_j.dg, b_j = V_j.g AND vT = -dx + sum_j a_j V_j; then vT's part of axpy_finish
-// (vT.dg with the raw vT, NaN -> 0, vT.g; V[k] = vT; block partials into part2)
-template <int VEC>
-__device__ __forceinline__ void sweep_v_body(int64_t M, int k, const Status* __restrict__ st, float* __restrict__ V,
+// (vT.dg with the raw vT, NaN -> 0, vT.g; V[k] = vT; block partials into part2).  bf16 pairs (P = __bf16): vT is rounded to bf16
+// first, and s, beta and V[k] all take the rounded value
+template <int VEC, class P = float>
+__device__ __forceinline__ void sweep_v_body(int64_t M, int k, const Status* __restrict__ st, P* __restrict__ V,
                                              const float* __restrict__ dxv, const float* __restrict__ dgv,
                                              const float* __restrict__ gv, const float* __restrict__ coef,
                                              float* __restrict__ part, int64_t pstride, int ldp, float* __restrict__ part2, int nblk, int64_t ld,
@@ -553,6 +561,7 @@ __device__ __forceinline__ void sweep_v_body(int64_t M, int k, const Status* __r
   if (act) {
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
+      av[i] = pair_round<P>(av[i]);      // (fp32 pairs: no-op)
       p1 = fmaf(av[i], dg[i], p1);       // with the raw vT, as the reference divides before scrubbing
       av[i] = (av[i] != av[i]) ? 0.f : av[i];
       p2 = fmaf(av[i], g[i], p2);
@@ -568,6 +577,14 @@ __global__ __launch_bounds__(TB) void k_sweep_v(int64_t M, int k, const Status* 
                                                 float* __restrict__ part, int64_t pstride, int ldp, float* __restrict__ part2, int nblk,
                                                 int64_t ld, int thr) {
   sweep_v_body<VEC>(M, k, st, V, dxv, dgv, gv, coef, part, pstride, ldp, part2, nblk, ld, thr);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_sweep_v_bf16(int64_t M, int k, const Status* __restrict__ st, __bf16* __restrict__ V,
+                                                     const float* __restrict__ dxv, const float* __restrict__ dgv,
+                                                     const float* __restrict__ gv, const float* __restrict__ coef,
+                                                     float* __restrict__ part, int64_t pstride, int ldp, float* __restrict__ part2, int nblk,
+                                                     int64_t ld, int thr) {
+  sweep_v_body<VEC, __bf16>(M, k, st, V, dxv, dgv, gv, coef, part, pstride, ldp, part2, nblk, ld, thr);
 }
 
 // grid (max(k, 1), 3): blocks (j, 0 | 1): coef_c[j], coef_b[j]; block (0, 2): s = vT.dg, beta = vT.g from sweep 2's block partials
@@ -599,9 +616,10 @@ __global__ __launch_bounds__(RB) void k_reduce_cb(Status* __restrict__ st, const
 }
 
 // sweep 3: reads U once: D1 = dx + dg - sum_j c_j U_j, D2 = g - sum_j b_j U_j, and -- s and beta being known by now -- the
-// final step of the update in the same registers: u = D1 / s (NaN -> 0) -> U[k], update = D2 - u * beta (k_final's arithmetic)
-template <int VEC>
-__device__ __forceinline__ void sweep_u2_body(int64_t M, int k, const Status* __restrict__ st, float* __restrict__ U,
+// final step of the update in the same registers: u = D1 / s (NaN -> 0) -> U[k], update = D2 - u * beta (k_final's arithmetic).
+// bf16 pairs (P = __bf16): u is rounded to bf16 before the update uses it
+template <int VEC, class P = float>
+__device__ __forceinline__ void sweep_u2_body(int64_t M, int k, const Status* __restrict__ st, P* __restrict__ U,
                                               float* __restrict__ upd, const float* __restrict__ dgv,
                                               const float* __restrict__ gv, const float* __restrict__ coef, int thr, int64_t ld) {
   if (__builtin_amdgcn_readfirstlane(st->done)) return;
@@ -651,6 +669,7 @@ __device__ __forceinline__ void sweep_u2_body(int64_t M, int k, const Status* __
   for (int i = 0; i < VEC; ++i) {
     float q = a1[i] / sv;
     q = (q != q) ? 0.f : q;
+    q = pair_round<P>(q);   // (fp32 pairs: no-op)
     a1[i] = q;
     a2[i] = fmaf(-q, beta, a2[i]);
   }
@@ -662,6 +681,12 @@ __global__ __launch_bounds__(TB) void k_sweep_u2(int64_t M, int k, const Status*
                                                  float* __restrict__ upd, const float* __restrict__ dgv,
                                                  const float* __restrict__ gv, const float* __restrict__ coef, int thr, int64_t ld) {
   sweep_u2_body<VEC>(M, k, st, U, upd, dgv, gv, coef, thr, ld);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_sweep_u2_bf16(int64_t M, int k, const Status* __restrict__ st, __bf16* __restrict__ U,
+                                                      float* __restrict__ upd, const float* __restrict__ dgv,
+                                                      const float* __restrict__ gv, const float* __restrict__ coef, int thr, int64_t ld) {
+  sweep_u2_body<VEC, __bf16>(M, k, st, U, upd, dgv, gv, coef, thr, ld);
 }
 
 // Sweep 3 with the NEXT iteration's first sweep folded in (k <= U2D_KMAX stored pairs).  a_j(next) = U_j . update_new needs
@@ -1230,6 +1255,13 @@ static int broyden_alloc(psignn_broyden* s) {
     }
     if (const char* e = getenv("PSIGNN_UVU")) if (atoi(e) == 0) s->uvu = 0;
   }
+  if (s->hist) {
+    // bf16 pairs: always the unfolded three-sweep form (the two-pass form and the folded sweep 3 have no bf16 variant), 16 floats per
+    // lane where the fp32 rules pick that width, else 4 floats unsplit; PSIGNN_UVU / PSIGNN_U2D_* do not apply
+    s->uvu = 1;
+    s->vec_u = (s->vec == 16 && s->jgroups == 1 && s->vec_ax == 16) ? 16 : 4;
+    s->nblk_u = (int)cdiv(s->M, (int64_t)s->vec_u * TB);
+  }
   s->npart_u = s->nblk_u * (TB / 64);
   s->nblk4 = (int)cdiv(s->M, (int64_t)4 * TB);
   const bool fold_ok = s->uvu != 0;
@@ -1246,6 +1278,7 @@ static int broyden_alloc(psignn_broyden* s) {
   if (const char* e = getenv("PSIGNN_U2D_KMAX")) s->u2d_kmax = fold_ok ? std::max(0, std::min(kmax_cap, atoi(e))) : 0;
   s->u2d_keep = s->u2d_kmax > 0 ? 16 : 0;
   if (const char* e = getenv("PSIGNN_U2D_KEEP")) s->u2d_keep = s->u2d_kmax > 0 ? std::max(0, std::min(s->u2d_kmax, atoi(e))) : 0;
+  if (s->hist) s->u2d_kmax = s->u2d_keep = 0;
   if (s->u2d_kmax > 0 && !s->u2d_reg) {
     // more than 64 KB of dynamic LDS has to be asked for, per device (the attribute belongs to the device's code object)
     int dev = 0;
@@ -1259,10 +1292,12 @@ static int broyden_alloc(psignn_broyden* s) {
   s->ldp = (s->thr + 63) / 64 * 64;
   s->pstride = (int64_t)std::max(std::max(s->nblk, s->nblk_u), std::max(s->nblk_ax, 1)) * s->ldp;
   size_t nx = s->keep_trace ? thr + 2 : 3;
-  s->ld = (s->M + 63) / 64 * 64;  // row pitch of U and V: every stored vector starts on a 256-byte boundary
+  // row pitch of U and V: every stored vector starts on a 256-byte boundary (64 fp32 / 128 bf16 elements)
+  s->ld = s->hist ? (s->M + 127) / 128 * 128 : (s->M + 63) / 64 * 64;
   size_t ld = (size_t)s->ld;
+  const size_t pb = s->hist ? 2 : 4;   // bytes per stored pair element
   struct { void** p; size_t n; } allocs[] = {
-      {(void**)&s->U, thr * ld * 4},  {(void**)&s->V, thr * ld * 4},   {(void**)&s->xbuf, nx * M * 4},
+      {(void**)&s->U, thr * ld * pb},  {(void**)&s->V, thr * ld * pb},   {(void**)&s->xbuf, nx * M * 4},
       {(void**)&s->gbuf[0], M * 4},   {(void**)&s->gbuf[1], M * 4},   {(void**)&s->upd, M * 4},
       {(void**)&s->fx, M * 4},        {(void**)&s->part, 3 * (size_t)s->pstride * 4 + 16}, {(void**)&s->parta, (size_t)s->nblk4 * PARTA_LD * 4 + 16},
       {(void**)&s->coef, (3 + RA) * thr * 4 + 16}, {(void**)&s->st, sizeof(Status)},
@@ -1317,16 +1352,29 @@ extern "C" void psignn_broyden_destroy(psignn_broyden_t* s) {
   delete s;
 }
 
-extern "C" int psignn_broyden_create_n(psignn_broyden_t** out, int64_t n_elems, int seq_len, int threshold, int keep_trace) {
+// One constructor behind the four entry points.  plan == NULL: a vector of n_elems elements (seq_len = d of the (N, d) iterate);
+// otherwise the plan's N * d (n_elems, seq_len: 0 or equal to the plan's).  shard_elems > 0: sized for a batched shard
+// (psignn_broyden_create_for_batch).  history: element type of the stored pairs, 0 fp32, 1 bf16.
+extern "C" int psignn_broyden_create_opts(psignn_broyden_t** out, const psignn_plan_t* plan, int64_t n_elems, int seq_len, int threshold,
+                                          int keep_trace, int64_t shard_elems, int history) {
   ARG_CHECK(out, "out is NULL");
   *out = nullptr;
-  ARG_CHECK(n_elems > 0 && threshold > 0 && seq_len > 0, "bad sizes");
-  ARG_CHECK(cdiv(n_elems, 16 * TB) * (TB / 64) < (int64_t)INT32_MAX, "vector too long");
+  ARG_CHECK(history == 0 || history == 1, "history: 0 = fp32 pairs, 1 = bf16 pairs");
+  if (plan) {
+    ARG_CHECK(threshold > 0 && shard_elems >= 0, "bad arguments");
+    ARG_CHECK((n_elems == 0 || n_elems == plan->N * D) && (seq_len == 0 || seq_len == D), "n_elems / seq_len do not match the plan");
+  } else {
+    ARG_CHECK(n_elems > 0 && threshold > 0 && seq_len > 0 && shard_elems >= 0, "bad sizes");
+    ARG_CHECK(cdiv(n_elems, 16 * TB) * (TB / 64) < (int64_t)INT32_MAX, "vector too long");
+  }
   psignn_broyden* s = new psignn_broyden();
-  s->M = n_elems;
-  s->seq_len = seq_len;
+  s->size_hint = shard_elems;
+  s->plan = plan;
+  s->M = plan ? plan->N * D : n_elems;
+  s->seq_len = plan ? D : seq_len;
   s->thr = threshold;
   s->keep_trace = keep_trace;
+  s->hist = history;
   int rc = broyden_alloc(s);
   if (rc) {
     psignn_broyden_destroy(s);
@@ -1336,30 +1384,19 @@ extern "C" int psignn_broyden_create_n(psignn_broyden_t** out, int64_t n_elems, 
   return PSIGNN_OK;
 }
 
-extern "C" int psignn_broyden_create_for_batch(psignn_broyden_t** out, const psignn_plan_t* plan, int threshold, int keep_trace,
-                                               int64_t shard_elems);
+extern "C" int psignn_broyden_create_n(psignn_broyden_t** out, int64_t n_elems, int seq_len, int threshold, int keep_trace) {
+  return psignn_broyden_create_opts(out, nullptr, n_elems, seq_len, threshold, keep_trace, 0, 0);
+}
+
 extern "C" int psignn_broyden_create(psignn_broyden_t** out, const psignn_plan_t* plan, int threshold, int keep_trace) {
-  return psignn_broyden_create_for_batch(out, plan, threshold, keep_trace, 0);
+  return psignn_broyden_create_opts(out, plan, 0, 0, threshold, keep_trace, 0, 0);
 }
 extern "C" int psignn_broyden_create_for_batch(psignn_broyden_t** out, const psignn_plan_t* plan, int threshold, int keep_trace,
                                                int64_t shard_elems) {
   ARG_CHECK(out, "out is NULL");
   *out = nullptr;
-  ARG_CHECK(plan && threshold > 0 && shard_elems >= 0, "bad arguments");
-  psignn_broyden* s = new psignn_broyden();
-  s->size_hint = shard_elems;
-  s->plan = plan;
-  s->M = plan->N * D;
-  s->seq_len = D;
-  s->thr = threshold;
-  s->keep_trace = keep_trace;
-  int rc = broyden_alloc(s);
-  if (rc) {
-    psignn_broyden_destroy(s);
-    return rc;
-  }
-  *out = s;
-  return PSIGNN_OK;
+  ARG_CHECK(plan, "bad arguments");
+  return psignn_broyden_create_opts(out, plan, 0, 0, threshold, keep_trace, shard_elems, 0);
 }
 
 extern "C" size_t psignn_broyden_bytes(const psignn_broyden_t* s) { return s ? s->bytes : 0; }
@@ -1374,6 +1411,8 @@ extern "C" int psignn_broyden_set_stop_mode(psignn_broyden_t* s, int abs_mode) {
 static inline int sel_off_cur() { return offsetof(Status, cur) / 4; }
 static inline int sel_off_low() { return offsetof(Status, low) / 4; }
 static inline int sel_off_nxt() { return offsetof(Status, nxt) / 4; }
+
+static inline __bf16* bf16_pairs(float* p) { return reinterpret_cast<__bf16*>(p); }   // U, V of a bf16-history solver
 
 // everything of one iteration after fx = f(x_next) is available; k = pairs stored so far
 // fused_npart > 0: the f kernel already produced g, dg and the norm partials (fused_npart entries each)
@@ -1392,7 +1431,10 @@ static void launch_update(psignn_broyden* s, int k, double eps, hipStream_t st, 
     if (k == 0) s->a_ready = 0;
     // a_j of this iteration: pairs j >= a_from were delivered by the folded sweep 3 of the last iteration, the others need sweep 1
     const int a_from = s->a_ready ? s->a_from : kd;
-    if (std::min(a_from, kd) > 0) {
+    if (std::min(a_from, kd) > 0 && s->hist) {
+      PROF_BYTES((2 * (int64_t)kd + 4) * s->M);   // kd bf16 columns of U + dx
+      VLAUNCH("k_sweep_u1_bf16", st, s->vec_u, k_sweep_u1_bf16, (gu, TB, 0, st), s->M, kd, s->st, bf16_pairs(s->U), s->upd, s->part, s->ldp, s->ld);
+    } else if (std::min(a_from, kd) > 0) {
       PROF_BYTES((std::min(a_from, kd) + 1) * (int64_t)s->M * 4);   // its columns of U + dx
       VLAUNCH("k_sweep_u1", st, s->vec_u, k_sweep_u1, (gu, TB, 0, st), s->M, std::min(a_from, kd), s->st, s->U, s->upd, s->part, s->ldp, s->ld);
     }
@@ -1403,6 +1445,14 @@ static void launch_update(psignn_broyden* s, int k, double eps, hipStream_t st, 
     if (k >= s->thr) return;
     // (iteration thr's stop test has just fired: the two sweeps below return at once and state no bytes)
     const bool last = k + 1 >= s->thr;
+    if (s->hist) {   // bf16 pairs: unfolded three-sweep form, pairs at 2 bytes (broyden_alloc: u2d_kmax = 0)
+      PROF_BYTES(last ? 0 : (2 * (int64_t)k + 14) * s->M);   // k bf16 columns of V + dx, dg, g; writes V[k]
+      VLAUNCH("k_sweep_v_bf16", st, s->vec_u, k_sweep_v_bf16, (gu, TB, 0, st), s->M, k, s->st, bf16_pairs(s->V), s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
+      LAUNCH("k_reduce_cb", st, (k_reduce_cb<<<dim3(std::max(k, 1), 3), RB, 0, st>>>(s->st, s->part, s->nblk_u, s->pstride, s->ldp, s->thr, k, s->coef, s->part2, s->nblk_u)));
+      PROF_BYTES(last ? 0 : (2 * (int64_t)k + 18) * s->M);   // k bf16 columns of U + update, dg, g; writes U[k], update
+      VLAUNCH("k_sweep_u2_bf16", st, s->vec_u, k_sweep_u2_bf16, (gu, TB, 0, st), s->M, k, s->st, bf16_pairs(s->U), s->upd, gold, gnew, s->coef, s->thr, s->ld);
+      return;
+    }
     PROF_BYTES(last ? 0 : (k + 4) * (int64_t)s->M * 4);   // k columns of V + dx, dg, g; writes V[k]
     VLAUNCH("k_sweep_v", st, s->vec_u, k_sweep_v, (gu, TB, 0, st), s->M, k, s->st, s->V, s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
     LAUNCH("k_reduce_cb", st, (k_reduce_cb<<<dim3(std::max(k, 1), 3), RB, 0, st>>>(s->st, s->part, s->nblk_u, s->pstride, s->ldp, s->thr, k, s->coef, s->part2, s->nblk_u)));
@@ -1700,6 +1750,7 @@ extern "C" int psignn_broyden_batchable(int n, psignn_broyden_t* const* sv) {
   for (int m = 0; m < n; ++m) {
     const psignn_broyden* s = sv[m];
     if (!s || !s->plan || !s->plan->tiled || s->plan->mixed != s0->plan->mixed) return 0;
+    if (s->hist) return 0;   // the batched kernels sweep fp32 pairs only
     if (!(s->vec == s0->vec && s->vec_ax == s0->vec_ax && s->uvu == s0->uvu && s->vec_u == s0->vec_u && s->thr == s0->thr &&
           s->u2d_kmax == s0->u2d_kmax && s->u2d_keep == s0->u2d_keep && s->u2d_reg == s0->u2d_reg))
       return 0;
@@ -1721,6 +1772,7 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
   for (int m = 0; m < n; ++m) {
     const psignn_broyden* s = sv[m];
     ARG_CHECK(s && s->plan && s->plan->tiled, "batched solve: tiled plans only");
+    ARG_CHECK(!s->hist, "batched solve: fp32 pair history only (psignn_broyden_batchable)");
     ARG_CHECK(s->plan->mixed == s0->plan->mixed, "batched solve: one boundary-condition family per shard");
     ARG_CHECK(s->vec == s0->vec && s->vec_ax == s0->vec_ax && s->uvu == s0->uvu && s->vec_u == s0->vec_u && s->thr == s0->thr &&
                   s->u2d_kmax == s0->u2d_kmax && s->u2d_keep == s0->u2d_keep && s->u2d_reg == s0->u2d_reg,
@@ -2004,6 +2056,10 @@ extern "C" int psignn_broyden_get_iterate(const psignn_broyden_t* s, int i, floa
   return PSIGNN_OK;
 }
 
+__global__ __launch_bounds__(TB) void k_widen_bf16(int64_t M, const __bf16* __restrict__ src, float* __restrict__ dst) {
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < M; i += (int64_t)gridDim.x * TB) dst[i] = (float)src[i];
+}
+
 // Stored rank-one pair j of the last solve: which = 0 -> U_j, 1 -> V_j (the reference's Us[..., j] / VTs[:, j], solver.py:134-135,190-191);
 // which = 2 -> the current `update` vector (solver.py:136,192; j ignored).  Caller's numbering.  Read-out for diagnostics and for the parity tests, which check the Broyden recurrences of every
 // update form on the device's own state (tests/test_gpu_solver_forms.py).
@@ -2015,6 +2071,14 @@ extern "C" int psignn_broyden_get_pair(const psignn_broyden_t* s, int j, int whi
     return PSIGNN_OK;
   }
   ARG_CHECK(which == 2 || (j >= 0 && j < s->thr), "pair index out of range");
+  if (s->hist && which != 2) {   // bf16 pair: widened (exactly) to fp32
+    const __bf16* row = bf16_pairs(which ? s->V : s->U) + (int64_t)j * s->ld;
+    float* dst = s->plan && s->plan_order ? s->fx : d_dst;
+    k_widen_bf16<<<(unsigned)std::min<int64_t>(cdiv(s->M, TB), 4096), TB, 0, (hipStream_t)stream>>>(s->M, row, dst);
+    HIP_TRY(hipGetLastError());
+    if (s->plan && s->plan_order) return psignn_plan_permute(s->plan, s->fx, D, d_dst, 0, stream);
+    return PSIGNN_OK;
+  }
   const float* row = which == 2 ? s->upd : (which ? s->V : s->U) + (int64_t)j * s->ld;
   if (s->plan && s->plan_order) {
     HIP_TRY(hipMemcpyAsync(s->fx, row, (size_t)s->M * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));

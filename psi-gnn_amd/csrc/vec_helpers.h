@@ -112,6 +112,46 @@ __device__ __forceinline__ void stv(float* __restrict__ p, int64_t e0, int64_t M
   }
 }
 
+// ---- bf16 storage of the Broyden pairs (opt-in history, solver.hip) --------------------------------------------------------------
+// The same thread -> element mapping as ldv / stv: a lane moves 4 contiguous elements per row (8 bytes, one dwordx2), a wave 512
+// contiguous bytes.  Widening bf16 -> fp32 is exact (the 16 bits become the high half of the float); narrowing is a plain cast,
+// round to nearest even with NaN kept a NaN (v_cvt_pk_bf16_f32).  Arithmetic stays fp32.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+// the value a pair element of type P holds once stored: identity for fp32 pairs, bf16 rounding otherwise
+template <class P>
+__device__ __forceinline__ float pair_round(float x) { return x; }
+template <>
+__device__ __forceinline__ float pair_round<__bf16>(float x) { return (float)(__bf16)x; }
+template <int VEC>
+__device__ __forceinline__ void ldv_stream(const __bf16* __restrict__ p, int64_t e0, int64_t M, float* r) {
+#pragma unroll
+  for (int i = 0; i < VEC / 4; ++i) {
+    const int64_t o = e0 + i * 256;
+    if (o + 4 <= M) {
+      const bf16x4 t = *reinterpret_cast<const bf16x4*>(p + o);
+      r[4 * i] = (float)t.x; r[4 * i + 1] = (float)t.y; r[4 * i + 2] = (float)t.z; r[4 * i + 3] = (float)t.w;
+    } else {  // tail
+#pragma unroll
+      for (int c = 0; c < 4; ++c) r[4 * i + c] = (o + c < M) ? (float)p[o + c] : 0.f;
+    }
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void stv(__bf16* __restrict__ p, int64_t e0, int64_t M, const float* r) {
+#pragma unroll
+  for (int i = 0; i < VEC / 4; ++i) {
+    const int64_t o = e0 + i * 256;
+    if (o + 4 <= M) {
+      const bf16x4 t = {(__bf16)r[4 * i], (__bf16)r[4 * i + 1], (__bf16)r[4 * i + 2], (__bf16)r[4 * i + 3]};
+      *reinterpret_cast<bf16x4*>(p + o) = t;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (o + c < M) p[o + c] = (__bf16)r[4 * i + c];
+    }
+  }
+}
+
 template <int STRIDE = 1>
 __device__ inline double block_sum_partials(const float* __restrict__ p, int n, double* sh) {
   // fixed summation shape (lane-strided, 4 independent accumulators, then a tree): reproducible, and the

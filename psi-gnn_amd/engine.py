@@ -369,14 +369,16 @@ class FixedPointMap:
     # ---- one idle Broyden solver kept between solves of this map (utilities.solver.broyden without keep_trace / solver_obj):
     # creating and destroying the 2 * threshold state vectors costs 2.2 ms per call at 1M nodes and threshold 20 -- a quarter of
     # such a solve (profiles/r3_cold_solve_probe.txt).  Bounded by PSIGNN_SOLVER_CACHE_GB (default 16; 0 disables).
-    def borrow_broyden(self, threshold):
+    # The idle solver is keyed on (threshold, history dtype): a bf16-history call never gets an fp32 solver, nor the reverse.
+    def borrow_broyden(self, threshold, history_dtype=torch.float32):
         sv = getattr(self, "_idle_broyden", None)
         self._idle_broyden = None
-        if sv is not None and sv.threshold == int(threshold) and not sv.keep_trace:
+        if (sv is not None and sv.threshold == int(threshold) and not sv.keep_trace
+                and getattr(sv, "history_dtype", torch.float32) == history_dtype):
             return sv
         if sv is not None:
             sv.close()
-        return DeviceBroyden(plan=self.plan, threshold=threshold, keep_trace=False)
+        return DeviceBroyden(plan=self.plan, threshold=threshold, keep_trace=False, history_dtype=history_dtype)
 
     def return_broyden(self, sv):
         import os
@@ -939,17 +941,43 @@ class Linearization:
             pass
 
 
+# element type of the stored Broyden pairs -> ``history`` of psignn_broyden_create_opts
+_HISTORY_CODES = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def history_code(history_dtype) -> int:
+    """0 for ``torch.float32`` (the default), 1 for ``torch.bfloat16``; any other dtype raises ValueError (on the host, before
+    anything is allocated)."""
+    if history_dtype not in _HISTORY_CODES:
+        raise ValueError(f"Broyden history dtype {history_dtype!r}: torch.float32 or torch.bfloat16")
+    return _HISTORY_CODES[history_dtype]
+
+
 class DeviceBroyden:
-    def __init__(self, plan=None, threshold=50, keep_trace=False, n_elems=None, seq_len=D, device=None, shard_elems=0):
+    def __init__(self, plan=None, threshold=50, keep_trace=False, n_elems=None, seq_len=D, device=None, shard_elems=0,
+                 history_dtype=torch.float32):
         """``shard_elems`` > 0: the solver will run inside ``broyden_solve_batch`` with others; its reduction shapes are sized
-        for the whole shard (sum of N * d), and its single-mesh solves give the same bits as the batched ones."""
+        for the whole shard (sum of N * d), and its single-mesh solves give the same bits as the batched ones.
+
+        ``history_dtype``: element type of the stored rank-one pairs U_j, V_j.  ``torch.bfloat16`` halves their memory and the
+        bytes every iteration streams (``psignn_broyden_create_opts``, history = 1): each pair is rounded to bf16 when it is
+        written and the new pair's derived values use the rounded one; iterate, update and arithmetic stay fp32.  Such a solver
+        is never batched (``shard_batchable`` is False)."""
+        hist = history_code(history_dtype)
         h = C.c_void_p()
         self.plan = plan
         self.threshold = int(threshold)
         self.keep_trace = bool(keep_trace)
+        self.history_dtype = history_dtype
         self.device = plan.device if plan is not None else device
         with torch.cuda.device(self.device):
-            if plan is not None:
+            if hist:
+                nat.check(nat.lib().psignn_broyden_create_opts(
+                    C.byref(h), plan.handle if plan is not None else None, 0 if plan is not None else int(n_elems),
+                    0 if plan is not None else int(seq_len), self.threshold, int(keep_trace), int(shard_elems), hist),
+                    "psignn_broyden_create_opts")
+                self.M = plan.N * D if plan is not None else int(n_elems)
+            elif plan is not None:
                 nat.check(nat.lib().psignn_broyden_create_for_batch(C.byref(h), plan.handle, self.threshold, int(keep_trace),
                                                                      int(shard_elems)), "psignn_broyden_create_for_batch")
                 self.M = plan.N * D

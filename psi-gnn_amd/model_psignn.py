@@ -11,7 +11,9 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
   key ``"bw_linearize"`` (default False): the implicit backward, the power method and the Jacobian estimate linearise f
   once at H* and apply the transposed stored linearisation (``engine.Linearization.vjp_p``) where the plan allows it.  On the
   mixed family it gains nothing yet: its transposed product is the tiled VJP at the state the build kept, so the key only adds one
-  build per call there.
+  build per call there.  An optional key ``"broyden_history_dtype"`` (default ``torch.float32``; ``torch.bfloat16`` allowed): the
+  element type of the stored Broyden pairs of the forward and the adjoint solve (``utilities.solver.broyden(...,
+  history_dtype=...)``); it applies when the configured solver is ``utilities.solver.broyden`` and has no effect with any other.
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
   and shapes are identical.
 * ``batch`` is any object with the PyG ``Data`` attributes (see ``data/meshdata.py``), already on the GPU.
@@ -152,14 +154,15 @@ class _DEQFn(torch.autograd.Function):
         H0 = H_init.detach()
         fmap = deq.f.bind(H0, batch)
         if cfg["solver"] is _solver.broyden:   # forward solver state kept between training steps on the same plan
+            hdt = deq.history_dtype()
             old = getattr(deq, "_fw_key", None)
-            if old is None or old[0] is not fmap.plan or old[1] != cfg["fw_thres"]:
+            if old is None or old[0] is not fmap.plan or old[1] != cfg["fw_thres"] or old[2] != hdt:
                 if getattr(deq, "_fw_solver", None) is not None:
                     deq._fw_solver.close()
-                deq._fw_solver = engine.DeviceBroyden(plan=fmap.plan, threshold=cfg["fw_thres"], keep_trace=False)
-                deq._fw_key = (fmap.plan, cfg["fw_thres"])
+                deq._fw_solver = engine.DeviceBroyden(plan=fmap.plan, threshold=cfg["fw_thres"], keep_trace=False, history_dtype=hdt)
+                deq._fw_key = (fmap.plan, cfg["fw_thres"], hdt)
             out_fw = _solver.broyden(fmap, H0, threshold=cfg["fw_thres"], eps=cfg["fw_tol"], keep_trace=False,
-                                     solver_obj=deq._fw_solver)
+                                     solver_obj=deq._fw_solver, history_dtype=hdt)
         else:
             out_fw = cfg["solver"](fmap, H0, threshold=cfg["fw_thres"], eps=cfg["fw_tol"])
         H_star = out_fw["result"]
@@ -218,9 +221,20 @@ class DeepEquilibrium(nn.Module):
         self.config_deq = config_deq
         self.path_logs = self.config_deq.get("path_logs")
 
+    def history_dtype(self):
+        """Element type of the stored Broyden pairs (config key ``broyden_history_dtype``, default ``torch.float32``)."""
+        return self.config_deq.get("broyden_history_dtype", torch.float32)
+
+    def _solver_kwargs(self):
+        # broyden_history_dtype reaches utilities.solver.broyden only; other solvers take the reference's arguments as they are
+        if self.config_deq["solver"] is _solver.broyden and self.history_dtype() != torch.float32:
+            return {"history_dtype": self.history_dtype()}
+        return {}
+
     def forward(self, H_init, batch):
         return self.config_deq["solver"](self.f.bind(H_init, batch), H_init,
-                                         threshold=self.config_deq["fw_thres"], eps=self.config_deq["fw_tol"])
+                                         threshold=self.config_deq["fw_thres"], eps=self.config_deq["fw_tol"],
+                                         **self._solver_kwargs())
 
     inference = forward  # dirichlet/psignn/model.py:245-253
 
@@ -286,12 +300,13 @@ class DeepEquilibrium(nn.Module):
         if self.config_deq["solver"] is _solver.broyden:  # whole adjoint solve on the device
             # the solver state (2 * bw_thres * N * d floats) is kept between calls on the same plan: a training loop
             # would otherwise allocate and free it once per step
-            key = (fmap.plan, self.config_deq["bw_thres"])
+            key = (fmap.plan, self.config_deq["bw_thres"], self.history_dtype())
             old = getattr(self, "_bw_key", None)
-            if old is None or old[0] is not key[0] or old[1] != key[1]:
+            if old is None or old[0] is not key[0] or old[1:] != key[1:]:
                 if getattr(self, "_bw_solver", None) is not None:
                     self._bw_solver.close()
-                self._bw_solver = engine.DeviceBroyden(plan=fmap.plan, threshold=self.config_deq["bw_thres"], keep_trace=False)
+                self._bw_solver = engine.DeviceBroyden(plan=fmap.plan, threshold=self.config_deq["bw_thres"], keep_trace=False,
+                                                       history_dtype=key[2])
                 self._bw_key = key
             sv = self._bw_solver
             out = sv.solve_adjoint(fmap, H_star, g, self.config_deq["bw_tol"], lin=lin)
@@ -367,6 +382,9 @@ class _Base(nn.Module):
         self.config_deq = {k: self.config[k] for k in ("solver", "fw_tol", "fw_thres", "bw_tol", "bw_thres", "path_logs")}
         if "bw_linearize" in self.config:   # optional, like "bc": the transposed stored linearisation in the backward routes
             self.config_deq["bw_linearize"] = bool(self.config["bw_linearize"])
+        if "broyden_history_dtype" in self.config:   # optional: bf16 storage of the Broyden pairs (utilities.solver.broyden only)
+            engine.history_code(self.config["broyden_history_dtype"])   # (ValueError for any other dtype)
+            self.config_deq["broyden_history_dtype"] = self.config["broyden_history_dtype"]
         self.deqdss = DeepEquilibrium(
             function=Function(n_layers=self.config["n_layers"], latent_dim=d, edge_features_dim=3,
                               second_member_dim=3 if self.mixed else 2, activation=nn.ReLU(), mixed=self.mixed),

@@ -18,7 +18,7 @@ import os
 import torch
 
 from .. import _native as nat
-from ..engine import D, TRACE_BUDGET_BYTES, DeviceBroyden, DeviceFixedPointIter, FixedPointMap
+from ..engine import D, TRACE_BUDGET_BYTES, DeviceBroyden, DeviceFixedPointIter, FixedPointMap, history_code
 
 
 class _NoTrace:
@@ -59,7 +59,7 @@ class _LazyTrace:
 
 
 def broyden(f, x0, threshold, eps=1e-3, stop_mode="rel", ls=False, name="unknown", keep_trace=None,
-            poll_every=8, solver_obj=None):
+            poll_every=8, solver_obj=None, history_dtype=torch.float32):
     """Broyden's method on g(x) = f(x) - x  (reference: utilities/solver.py:116-207).
 
     Same contract as the reference: ``result`` is the lowest-``stop_mode`` iterate x (not f(x)), ``nstep`` its
@@ -68,9 +68,16 @@ def broyden(f, x0, threshold, eps=1e-3, stop_mode="rel", ls=False, name="unknown
     iterations.  ``ls=True`` (Armijo line search, solver.py:20-94; no call site of the reference enables it) runs the
     host-driven loop -- the trial points need extra f evaluations between the device steps -- also for a
     ``FixedPointMap``.
+
+    ``history_dtype`` (not in the reference): element type of the stored rank-one pairs, ``torch.float32`` (default) or
+    ``torch.bfloat16`` -- half the solver memory and half the bytes each iteration streams, on both paths (``DeviceBroyden``).
+    ``solver_obj`` must then have been made with the same dtype.
     """
     if stop_mode not in ("rel", "abs"):
         raise ValueError(f"stop_mode {stop_mode!r}")
+    history_code(history_dtype)   # (ValueError for any other dtype, before the device is touched)
+    if solver_obj is not None and getattr(solver_obj, "history_dtype", torch.float32) != history_dtype:
+        raise ValueError(f"solver_obj stores its pairs as {solver_obj.history_dtype}, the call asks for {history_dtype}")
     nat.require_cuda(x0, "x0")
     if x0.dim() != 2:
         raise nat.NativeError(f"x0 must be (N, d), got {tuple(x0.shape)}")
@@ -85,9 +92,10 @@ def broyden(f, x0, threshold, eps=1e-3, stop_mode="rel", ls=False, name="unknown
         # on one map do not re-allocate their state
         pooled = solver_obj is None and not keep_trace
         if pooled:
-            solver = f.borrow_broyden(threshold)
+            solver = f.borrow_broyden(threshold, history_dtype)
         else:
-            solver = solver_obj if solver_obj is not None else DeviceBroyden(plan=f.plan, threshold=threshold, keep_trace=keep_trace)
+            solver = solver_obj if solver_obj is not None else DeviceBroyden(plan=f.plan, threshold=threshold, keep_trace=keep_trace,
+                                                                             history_dtype=history_dtype)
         solver.set_stop_mode(stop_mode)
         try:
             out = solver.solve(f, eps, poll_every=poll_every)
@@ -99,7 +107,7 @@ def broyden(f, x0, threshold, eps=1e-3, stop_mode="rel", ls=False, name="unknown
         x_init = f.h0
     else:
         solver = DeviceBroyden(threshold=threshold, keep_trace=keep_trace, n_elems=M, seq_len=x0.shape[1],
-                               device=x0.device)
+                               device=x0.device, history_dtype=history_dtype)
         solver.set_stop_mode(stop_mode)
         out = solver.solve_callable(f, x0, eps, ls=ls)
         x_init = x0
