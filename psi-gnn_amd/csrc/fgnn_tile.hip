@@ -12,36 +12,12 @@
 // The second Phi layer (W2 S + deg b2) is linear and is folded into the consumers' first-layer weights on
 // the host (WLayout fold block).  All node tensors are in PLAN order; the solver keeps its state there.
 // weight loads of mv2 pinned chunk by chunk (tile_helpers.h; A/B in profiles/r3_ab_mv2.txt: fused step 75.8 -> 73.4 us, plain f unchanged)
-#ifndef MV2_LAUNDER
 #define MV2_LAUNDER 2
-#endif
-#ifndef MV2_CH
 #define MV2_CH 10
-#endif
 #include "tile_helpers.h"
-#ifndef TILE_WPE
-#define TILE_WPE 0    // > 0: __attribute__((amdgpu_waves_per_eu(TILE_WPE, TILE_WPE))) on k_f_tile: the register allocator is held to 96 VGPRs (5 waves per SIMD)
-#endif
-#ifndef FUSED_WPE
-#define FUSED_WPE 0   // > 0: the FUSED instantiations only are held to this many waves per SIMD (6 = 80 VGPRs; they need 83 - 86)
-#endif
-#if FUSED_WPE
-#define TILE_WPE_ATTR __attribute__((amdgpu_waves_per_eu(FUSED ? FUSED_WPE : 1, FUSED ? FUSED_WPE : 8)))
-#elif TILE_WPE
-#define TILE_WPE_ATTR __attribute__((amdgpu_waves_per_eu(TILE_WPE, TILE_WPE)))
-#else
-#define TILE_WPE_ATTR
-#endif
-#ifndef X_RELOAD
-#define X_RELOAD 1    // 1: park the node state in memory during the slot walk (A/B: scripts/ab_edge.sh)
-#endif
-#ifndef EDGE_CLAMP
-#define EDGE_CLAMP 1  // relu folded into the clamp bit of the last edge fma (tile_helpers.h: edge_pass_both_clamp)
-#endif
-#ifndef EDGE_BOTH
-#define EDGE_BOTH 1   // both edge directions in one slot walk (edge_pass_both); 0: one walk per direction.  A/B on one
-                      // box, 1M nodes: plain f 61.5 vs 62.9 us, fused Broyden step 99.5 vs 104 us
-#endif
+// Occupancy caps were measured and removed (profiles/r2_f_tile_ab_runs.txt): k_f_tile held to 96 VGPRs ran plain f in 59.8 vs
+// 58.0 us, the fused instantiations held to 80 VGPRs for a sixth wave 89.6 vs 88.8 us, the batched kernel held to six waves 57.4
+// vs 50.7 us at 8 x 50k nodes.
 
 template <bool MIXED>
 struct TileRow {
@@ -84,7 +60,6 @@ __device__ __forceinline__ void lds_load10at(const float* __restrict__ p, float*
 // matrix cores (v_mfma_f32_16x16x4_f32) or packed VALU.
 #include <stdlib.h>
 #include <string.h>
-#include <algorithm>
 // Default form: packed VALU everywhere.  A/Bs on one box (1M-node mesh) after the scalar-load phase barriers removed the
 // SGPR spills of the VALU form: dirichlet plain f 64.6 us (valu) vs 67.7 us (mfma); fused Broyden step 102 us (valu) vs
 // 122-125 us (mfma: it has to re-load x and update for stage 2, which the VALU form gets for free from its stage-1
@@ -118,14 +93,10 @@ struct FuseArgs {
   long long* stamps;  // diagnostics (psignn_prof_tile_stamps): per tile and wave 8 constant-rate (100 MHz) clock stamps, else NULL
 };
 
-// Wave priority per phase: TILE_PRIO = p0 + 4 p1 + 16 p2 + 64 p3 sets s_setprio(p) at the start of stage 1 / after the barrier (slot
-// walk) / at the node update / at the epilogue; 0 = never touched.  15: the phases that ISSUE memory requests (stage 1, slot walk)
-// go ahead of the purely arithmetic node update of other waves -- plain f 52.0 -> 50.4 us over four interleaved runs each, fused
-// step unchanged (profiles/r3_ab_prio.txt); the other placements measured there are within noise.
-#ifndef TILE_PRIO
-#define TILE_PRIO 15
-#endif
-#define PRIO_AT(ph) do { if (TILE_PRIO) __builtin_amdgcn_s_setprio((TILE_PRIO >> (2 * (ph))) & 3); } while (0)
+// Wave priority per phase: s_setprio(3) at the start of stage 1 and after the barrier (slot walk), s_setprio(0) at the node update
+// and at the epilogue.  The phases that ISSUE memory requests go ahead of the purely arithmetic node update of other waves -- plain
+// f 52.0 -> 50.4 us over four interleaved runs each, fused step unchanged (profiles/r3_ab_prio.txt); the other placements measured
+// there were within noise.
 // In-kernel phase stamps (diagnostics only; one lane per wave writes s_memtime values)
 #ifndef TILE_STAMPS
 #define TILE_STAMPS 0   // build with -DTILE_STAMPS=1 for scripts/tile_phases.py (the stamps cost registers and issue slots)
@@ -173,7 +144,7 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   constexpr int RS = TileRow<MIXED>::RS;
   const int tile = tile_list ? tile_list[slot] : slot;   // mixed plans: a sub-list of the tiles (see launch_mixed)
   STAMP(0);
-  PRIO_AT(0);
+  __builtin_amdgcn_s_setprio(3);
   const int tid = threadIdx.x;
   // tile -> node range: arithmetic when the plan's tiles are uniform chunks (always, since round 2; the table stays for
   // tile sizes that are not a multiple of 64)
@@ -190,10 +161,6 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
 
   // ---- stage 1: neighbour-side projections of tile + halo rows -> LDS
   float x[D];
-  uint4 slot0 = make_uint4(ELL_EMPTY, 0u, 0u, 0u);   // slot row 0 of this lane / prefetch witness (SLOT_PREFETCH below)
-  unsigned slot_touch = 0;
-  (void)slot0;
-  (void)slot_touch;
   if constexpr (MFMA1) {
     // Dense node-feature x weight product on the matrix cores: out[row][o] = sum_k x[row][k] W1j[o][k] as
     // v_mfma_f32_16x16x4_f32 tiles with the WEIGHTS as the A operand (A[i = output][k]) and the node rows as B
@@ -258,34 +225,9 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   // other tile skips a third of its stage-1 work
   bool tile_neu = false;
   if (MIXED) tile_neu = __syncthreads_or(tid < n_t ? (C->flags_p[t0 + tid] & FLAG_NEUMANN) : 0) != 0;
-#ifndef HALO_SPLIT
-#define HALO_SPLIT 1   // 1: halo rows of stage 1 shared out as half rows over all four waves (see below); 0: round 1's loop
-#endif
-#ifndef SLOT_PREFETCH
-#define SLOT_PREFETCH 0   // 0 (default): stage 2 requests its slot rows itself; 2: flag byte and slot row 0 requested before the
-                          // stage-1 barrier (measured: plain f 53.6 vs 53.2 us, fused step 95.0 vs 90.1 us -- no gain); 1: the wave's slot rows are requested before stage 1 (row 0 kept, the rest pulled towards L2).
-                          // Measured (1M nodes, plain f): 64.7 - 65.2 us with, 57.5 - 58.2 us without -- the extra pass over the
-                          // slot records costs more than the walk's misses; kept for A/B runs
-#endif
-#if HALO_SPLIT
-#if SLOT_PREFETCH == 1
-  // (experiment, off) every wave requests ALL its slot rows ahead of the h rows: row 0 stays in registers for the walk, the
-  // others are only pulled towards L2 / L1 (their first words are folded into a value that is looked at once and never acted
-  // on).  Measured: 64.7 - 65.2 us vs 57.5 - 58.2 us without -- the second pass over the slot records costs more than the
-  // walk's misses.
-  if ((tid & ~63) < n_t) {
-    const int pslice = (tn ? tile * (tn >> 6) : C->tile_slice[tile]) + (tid >> 6);
-    const uint4* pslots = C->ell + (int64_t)C->slice_off[pslice] * 64 + (tid & 63);
-    const int pn = C->slice_deg[pslice];
-    if (pn > 0) {   // (the fused Broyden step has no four registers to spare across stage 1: it only touches row 0 as well)
-      if (FUSED) slot_touch ^= pslots[0].x;
-      else slot0 = pslots[0];
-    }
-#pragma unroll
-    for (int r = 1; r < 8; ++r)
-      if (r < pn) slot_touch ^= pslots[(int64_t)r * 64].x;
-  }
-#endif
+  // Slot rows requested ahead of stage 2 were measured and removed: all of the wave's rows before stage 1, plain f 64.7 - 65.2 vs
+  // 57.5 - 58.2 us (profiles/r2_f_tile_ab_runs.txt); row 0 just before the stage-1 barrier, plain f 53.6 vs 53.2 us, fused step
+  // 95.0 vs 90.1 us.
   // own row first: every lane's loads are in flight before any projection starts
   const int32_t hidx_w = (tid >> 6 & 1) * 64 + (tid & 63);   // this lane's halo slot inside a 128-row batch
   int32_t hnode = 0;
@@ -312,11 +254,6 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
     }
 #pragma unroll
     for (int o = 0; o < D; ++o) x[o] = xr[o];
-#if SLOT_PREFETCH
-    // the prefetch loads were issued before the h row and return in order: looking at their witness here costs no extra
-    // wait and frees its register before the projections (never true: slot words are < 2^18)
-    if (slot_touch == 0xDEADBEEFu) xr[0] = 0.f;
-#endif
     v2f ta[5], tb[5];
 #pragma unroll
     for (int p = 0; p < 5; ++p) ta[p] = tb[p] = splat(0.f);
@@ -340,10 +277,11 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
       reinterpret_cast<float2*>(q + 7)[0] = make_float2(ta[4].x, ta[4].y);
     }
   }
-  // Halo rows.  A tile of 256 nodes has ~110 of them: as whole rows they are a second round for waves 0 and 1 only, with
-  // the other two waves parked at the barrier (stamps: 4.0 vs 2.5 us in stage 1, 1.7 us of barrier wait).  Shared out as
-  // HALF rows instead -- waves 0, 1 project the Phi_to half of halo rows [64 (w & 1), +64), waves 2, 3 the Phi_from half --
-  // every wave does one 10 x 10 block per 128 halo rows: the same number of wave instructions, half the critical path.
+  // Halo rows.  A tile of 256 nodes has ~110 of them: as whole rows (round 1's loop, measured and removed:
+  // profiles/r2_f_tile_ab_runs.txt) they were a second round for waves 0 and 1 only, with the other two waves parked at the
+  // barrier (stamps: 4.0 vs 2.5 us in stage 1, 1.7 us of barrier wait).  Shared out as HALF rows instead -- waves 0, 1 project the
+  // Phi_to half of halo rows [64 (w & 1), +64), waves 2, 3 the Phi_from half -- every wave does one 10 x 10 block per 128 halo
+  // rows: the same number of wave instructions, half the critical path.
   {
     const int half = __builtin_amdgcn_readfirstlane(tid >> 7);   // wave-uniform: 0 Phi_to columns, 1 Phi_from columns
     for (int hb = 0; hb < n_h; hb += 128) {
@@ -406,61 +344,16 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
       }
     }
   }
-#else
-  for (int row = tid; row < n_t + n_h; row += TILE_THREADS) {
-    const int64_t node = row < n_t ? (int64_t)(t0 + row) : (int64_t)hl[row - n_t];
-    float xr[D];
-    load10(h + node * D, xr);
-    if (FUSED) {  // x_next = x_cur + update (line_search with on=False: step 1, solver.py:85-94)
-      float ur[D];
-      load10(fa.upd + node * D, ur);
-#pragma unroll
-      for (int o = 0; o < D; ++o) xr[o] += ur[o];
-    }
-    if (row == tid) {
-#pragma unroll
-      for (int o = 0; o < D; ++o) x[o] = xr[o];
-    }
-    v2f ta[5], tb[5];
-#pragma unroll
-    for (int p = 0; p < 5; ++p) ta[p] = tb[p] = splat(0.f);
-    PHASE();
-    mv2<D>(T + L::T_W1J_TO, xr, ta);
-    PHASE();
-    mv2<D>(T + L::T_W1J_FR, xr, tb);
-    float4* q = reinterpret_cast<float4*>(lds + row * RS);
-    q[0] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
-    q[1] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
-    q[2] = make_float4(ta[4].x, ta[4].y, tb[0].x, tb[0].y);
-    q[3] = make_float4(tb[1].x, tb[1].y, tb[2].x, tb[2].y);
-    q[4] = make_float4(tb[3].x, tb[3].y, tb[4].x, tb[4].y);
-    if (MIXED && tile_neu) {
-#pragma unroll
-      for (int p = 0; p < 5; ++p) ta[p] = splat(0.f);
-      PHASE();
-      mv2<D>(TN + L::N_W1J, xr, ta);
-      q[5] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
-      q[6] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
-      reinterpret_cast<float2*>(q + 7)[0] = make_float2(ta[4].x, ta[4].y);
-    }
   }
-#endif
-  }
-  // stage 2's first loads -- the node's flag byte and slot row 0 -- are requested BEFORE the barrier: both sit on the
-  // critical path right behind it (flag -> Dirichlet branch -> slot pointer -> first record), an HBM round trip each
+  // stage 2's first load -- the node's flag byte -- is requested BEFORE the barrier: it sits on the critical path right behind
+  // it (flag -> Dirichlet branch -> slot pointer -> first record), an HBM round trip
   const bool active = tid < n_t;
   const int64_t n = (int64_t)t0 + (active ? tid : 0);
   const uint8_t fl = C->flags_p[n];
-#if HALO_SPLIT && SLOT_PREFETCH == 2
-  if (!MFMA1 && active) {
-    const int pslice = (tn ? tile * (tn >> 6) : C->tile_slice[tile]) + __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (C->slice_deg[pslice] > 0) slot0 = C->ell[(int64_t)C->slice_off[pslice] * 64 + (tid & 63)];
-  }
-#endif
   STAMP(1);
   __syncthreads();
   STAMP(2);
-  PRIO_AT(1);
+  __builtin_amdgcn_s_setprio(3);
   if (!FUSED && tid >= n_t) return;
 
   // ---- stage 2: one tile node per lane
@@ -485,7 +378,6 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   float deg_in, deg_out;
 #pragma unroll
   for (int p = 0; p < 5; ++p) S_to[p] = S_fr[p] = splat(0.f);
-#if X_RELOAD
   // the node state is not needed during the slot walk: park it in memory (the fused step writes x_next to its slot of the
   // iterate buffer anyway) and read it back afterwards -- ten VGPRs less in the loop
   const float* xsrc = h + n * D;
@@ -494,8 +386,8 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
     store10(xn, x);
     xsrc = xn;
   }
-#endif
-#if EDGE_BOTH
+  // both edge directions in one slot walk, relu folded into the clamp bit of the last edge fma (tile_helpers.h).  One walk per
+  // direction was measured and removed: plain f 62.9 vs 61.5 us, fused step 104 vs 99.5 us.
   {
     v2f Pi2[5];
     ld5(T + L::T_B1_TO, Pi);
@@ -505,33 +397,12 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
     PHASE();
     mv2<D>(T + L::T_W1I_FR, x, Pi2);
     PHASE();
-#if EDGE_CLAMP
-#if HALO_SPLIT && SLOT_PREFETCH
-    edge_pass_both_clamp<RS>(slots, nslots, lds, T + L::T_A_TO, T + L::T_A_FR, Pi, Pi2, S_to, S_fr, deg_in, deg_out,
-                             (MFMA1 || (FUSED && SLOT_PREFETCH == 1)) ? nullptr : &slot0);
-#else
     edge_pass_both_clamp<RS>(slots, nslots, lds, T + L::T_A_TO, T + L::T_A_FR, Pi, Pi2, S_to, S_fr, deg_in, deg_out);
-#endif
-#else
-    edge_pass_both<RS>(slots, nslots, lds, T + L::T_A_TO, T + L::T_A_FR, Pi, Pi2, S_to, S_fr, deg_in, deg_out);
-#endif
     PHASE();
   }
   STAMP(3);
-  PRIO_AT(2);
-#if X_RELOAD
+  __builtin_amdgcn_s_setprio(0);
   load10(xsrc, x);
-#endif
-#else
-  ld5(T + L::T_B1_TO, Pi);
-  PHASE();
-  mv2<D>(T + L::T_W1I_TO, x, Pi);
-  deg_in = edge_pass<RS, 0, SLOT_IN>(slots, nslots, lds, T + L::T_A_TO, Pi, S_to);
-  ld5(T + L::T_B1_FR, Pi);
-  PHASE();
-  mv2<D>(T + L::T_W1I_FR, x, Pi);
-  deg_out = edge_pass<RS, D, SLOT_OUT>(slots, nslots, lds, T + L::T_A_FR, Pi, S_fr);
-#endif
 
   v2f y2[5];
   if (MIXED && (fl & FLAG_NEUMANN)) {
@@ -628,7 +499,7 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   }
   }  // !dirichlet && active
   STAMP(4);
-  PRIO_AT(3);
+  __builtin_amdgcn_s_setprio(0);
   if (!FUSED) {
     store10(out + n * D, y);
     STAMP(5);
@@ -645,7 +516,7 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
       sf = fmaf(y[o], y[o], sf);
     }
     store10(fa.gnew + n * D, gn);
-    if (!X_RELOAD || dirichlet) store10(fa.xbuf + (int64_t)fa.st[fa.off_nxt] * fa.M + n * D, x);
+    if (dirichlet) store10(fa.xbuf + (int64_t)fa.st[fa.off_nxt] * fa.M + n * D, x);
   }
   // one partial pair per tile: wave shuffles, then the 4 wave sums through LDS in a fixed order
   sg = wave_sum_f(sg);
@@ -668,26 +539,16 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
 // atomic work queue whose next index is fetched during the current tile -- to fill the tail the phase stamps show: 60.9 - 62.2
 // and 62.6 - 64.8 us against 57.7 - 58.7 us for this form on the 1M-node mesh; the loop state also cost the fused variant its
 // fifth wave.  Removed; profiles/r2_f_tile_ab_runs.txt keeps the runs.)
-#ifndef TILE_CTX_VALUE
-#define TILE_CTX_VALUE 1   // 1: the tile pointers travel as a by-value struct in the kernel arguments; 0: behind a device
-                           // pointer (scalar loads next to each use).  Measured, 1M nodes: plain f 52.6 - 53.9 us by value vs
-                           // 54.9 - 57.7 us by pointer, fused step 94.0 vs 97.7 us
-#endif
-#if TILE_CTX_VALUE
-#define TILE_CTX_PARAM const TileCtx Cv
-#define TILE_CTX_USE const TileCtx* __restrict__ C = &Cv;
-#else
-#define TILE_CTX_PARAM const TileCtx* __restrict__ C
-#define TILE_CTX_USE
-#endif
+// The tile pointers travel as a by-value struct in the kernel arguments.  Passing them behind a device pointer was measured and
+// removed (profiles/r2_f_tile_ab_runs.txt): plain f 54.9 - 57.7 vs 52.6 - 53.9 us, fused step 97.7 vs 94.0 us.
 template <int P, bool MIXED, bool FUSED, bool MFMA1>
-__global__ __launch_bounds__(TILE_THREADS) TILE_WPE_ATTR void k_f_tile(FuseArgs fa, int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
-                                                TILE_CTX_PARAM, const float* __restrict__ W, int lofs, int tofs,
+__global__ __launch_bounds__(TILE_THREADS) void k_f_tile(FuseArgs fa, int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
+                                                const TileCtx Cv, const float* __restrict__ W, int lofs, int tofs,
                                                 int tnofs, int apply_ln, const float* __restrict__ h,
                                                 const int32_t* __restrict__ hsel, int64_t hstride,
                                                 const float* __restrict__ h0, const float* __restrict__ prb,
                                                 const float* __restrict__ nrm, float* __restrict__ out) {
-  TILE_CTX_USE
+  const TileCtx* __restrict__ C = &Cv;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (FUSED && fa.st[fa.off_done]) return;
   const int slot = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
@@ -703,16 +564,8 @@ static unsigned tile_grid(int chunk);
 // tile_base[m] + n_tiles[m])); a workgroup looks its slot's mesh up, loads that mesh's pointers from its descriptor and runs
 // the same tile body as the single-mesh kernel -- same arithmetic per node, same per-tile norm partials.  A mesh whose stop
 // test has fired is skipped tile by tile.
-#ifndef BATCH_WPE
-#define BATCH_WPE 0   // > 0: the batched fused kernel is held to this many waves per SIMD (A/B in profiles/r2_f_tile_ab_runs.txt)
-#endif
-#if BATCH_WPE
-#define BATCH_WPE_ATTR __attribute__((amdgpu_waves_per_eu(BATCH_WPE, BATCH_WPE)))
-#else
-#define BATCH_WPE_ATTR
-#endif
 template <int P, bool MIXED>
-__global__ __launch_bounds__(TILE_THREADS) BATCH_WPE_ATTR void k_f_tile_batch(const BatchDesc* __restrict__ descs, int n_mesh, int n_slots, int chunk,
+__global__ __launch_bounds__(TILE_THREADS) void k_f_tile_batch(const BatchDesc* __restrict__ descs, int n_mesh, int n_slots, int chunk,
                                                               int off_done, int off_cur, int off_nxt, int par,
                                                               const float* __restrict__ W, int lofs, int tofs, int tnofs) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -757,48 +610,8 @@ __global__ void k_permute_rows(int64_t N, int cols, const int32_t* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------ host
-#if TILE_CTX_VALUE
-#define TILE_ARGS p->h_ctx
-#else
-#define TILE_ARGS p->d_ctx
-#endif
-
 // Grid of a tile-kernel launch over `chunk` tiles per XCD: one workgroup per tile, a multiple of 8.
 static unsigned tile_grid(int chunk) { return (unsigned)(chunk * 8); }
-
-// ---- experiments behind run-time knobs ("the bound of k_f_tile"; defaults leave the launch unchanged)
-// PSIGNN_TILE_ORDER = cost: inside each XCD's run of tiles, launch the tiles with the most work first (stage-1 rows + slot
-// rows), so that the launch ends on its shortest tiles.  Results are tile-order invariant (norm partials are stored per tile).
-static const int32_t* tile_cost_order(const psignn_plan* p, int chunk, hipStream_t st) {
-  KNOB_INT(mode, [] { const char* e = getenv("PSIGNN_TILE_ORDER"); return (int)(e && strcmp(e, "cost") == 0); }());
-  if (!mode || p->mixed) return nullptr;
-  if (p->tile_order_cost) return p->tile_order_cost;
-  const int64_t nt = p->n_tiles;
-  std::vector<int32_t> tptr(nt + 1), tsl(nt + 1), hc(nt), order(nt);
-  std::vector<uint8_t> deg(p->n_slices);
-  if (hipMemcpy(tptr.data(), p->tile_ptr, (nt + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(tsl.data(), p->tile_slice, (nt + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(hc.data(), p->halo_cnt, nt * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(deg.data(), p->slice_deg, p->n_slices, hipMemcpyDeviceToHost) != hipSuccess)
-    return nullptr;
-  std::vector<int64_t> cost(nt);
-  for (int64_t t = 0; t < nt; ++t) {
-    int dmax = 0;
-    for (int s = tsl[t]; s < tsl[t + 1]; ++s) dmax = std::max(dmax, (int)deg[s]);
-    cost[t] = (int64_t)(tptr[t + 1] - tptr[t] + hc[t]) + 16 * (int64_t)dmax;   // a slot row costs ~ 60 instructions, a staged row ~ 4 per lane
-  }
-  for (int64_t t = 0; t < nt; ++t) order[t] = (int32_t)t;
-  for (int x = 0; x < 8; ++x) {
-    const int64_t a = std::min<int64_t>(nt, (int64_t)x * chunk), b = std::min<int64_t>(nt, (int64_t)(x + 1) * chunk);
-    std::stable_sort(order.begin() + a, order.begin() + b, [&](int32_t u, int32_t v) { return cost[u] > cost[v]; });
-  }
-  int32_t* d = nullptr;
-  if (hipMalloc((void**)&d, nt * 4) != hipSuccess) return nullptr;
-  if (hipMemcpy(d, order.data(), nt * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-  p->tile_order_cost = d;
-  (void)st;
-  return d;
-}
 
 static FuseArgs plain_args() {
   FuseArgs a{};
@@ -827,12 +640,12 @@ static void launch_mixed(const psignn_plan* p, const FuseArgs& fa, const char* n
   if (na > 0) {
     const int chunk = (int)cdiv(na, 8);
     LAUNCH(name, st, (k_f_tile<3, false, FUSED, false><<<tile_grid(chunk), TILE_THREADS, (size_t)p->max_rows * TileRow<false>::RS * 4, st>>>(
-        fa, na, chunk, p->tile_order, TILE_ARGS, W, lofs, tofs, tnofs, 1, h, hsel, hstride, h0, prb, nrm, out)));
+        fa, na, chunk, p->tile_order, p->h_ctx, W, lofs, tofs, tnofs, 1, h, hsel, hstride, h0, prb, nrm, out)));
   }
   if (nb > 0) {
     const int chunk = (int)cdiv(nb, 8);
     LAUNCH(name, st, (k_f_tile<3, true, FUSED, false><<<tile_grid(chunk), TILE_THREADS, (size_t)p->max_rows * TileRow<true>::RS * 4, st>>>(
-        fa, nb, chunk, list_b, TILE_ARGS, W, lofs, tofs, tnofs, 1, h, hsel, hstride, h0, prb, nrm, out)));
+        fa, nb, chunk, list_b, p->h_ctx, W, lofs, tofs, tnofs, 1, h, hsel, hstride, h0, prb, nrm, out)));
   }
 }
 
@@ -852,15 +665,14 @@ int psignn_f_tile_forward(const psignn_plan* p, const float* W, int nl, const fl
     if (stage1_mfma(false, true)) {  // single launch, MFMA stage 1 (PSIGNN_STAGE1=mfma)
       size_t lds = (size_t)p->max_rows * TileRow<true>::RS * 4;
       LAUNCH("k_f_tile", st, (k_f_tile<3, true, false, true><<<grid, TILE_THREADS, lds, st>>>(
-        plain_args(), (int)p->n_tiles, chunk, nullptr, TILE_ARGS, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), L::tp_neu(nl), 1,
+        plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), L::tp_neu(nl), 1,
         h, hsel, hstride, h0, prb, nrm, out)));
     } else {
       launch_mixed<false>(p, plain_args(), "k_f_tile", W, nl, h, hsel, hstride, h0, prb, nrm, out, st);
     }
   } else {
     using L = WLayout<2>;
-    size_t lds = std::max((size_t)p->max_rows * TileRow<false>::RS * 4, tile_lds_min());
-    const int32_t* tlist = tile_cost_order(p, chunk, st);
+    size_t lds = (size_t)p->max_rows * TileRow<false>::RS * 4;
     ARG_CHECK(nl == 1 || work, "multi-layer evaluation needs a workspace");
     float* pp[2] = {work, work ? work + p->N * D : nullptr};
     const float* cur = h;
@@ -868,11 +680,11 @@ int psignn_f_tile_forward(const psignn_plan* p, const float* W, int nl, const fl
       float* dst = (l == nl - 1) ? out : pp[l & 1];
       if (stage1_mfma(false, false))
         LAUNCH("k_f_tile", st, (k_f_tile<2, false, false, true><<<grid, TILE_THREADS, lds, st>>>(
-            plain_args(), (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, cur,
+            plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, cur,
             l == 0 ? hsel : nullptr, hstride, h0, prb, nrm, dst)));
       else
         LAUNCH("k_f_tile", st, (k_f_tile<2, false, false, false><<<grid, TILE_THREADS, lds, st>>>(
-            plain_args(), (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, cur,
+            plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, cur,
             l == 0 ? hsel : nullptr, hstride, h0, prb, nrm, dst)));
       cur = dst;
     }
@@ -891,16 +703,15 @@ int psignn_f_tile_layer(const psignn_plan* p, const float* W, int nl, int l, con
   using L = WLayout<2>;
   const int chunk = (int)cdiv(p->n_tiles, 8);
   const unsigned grid = tile_grid(chunk);
-  size_t lds = std::max((size_t)p->max_rows * TileRow<false>::RS * 4, tile_lds_min());
-  const int32_t* tlist = tile_cost_order(p, chunk, st);
+  size_t lds = (size_t)p->max_rows * TileRow<false>::RS * 4;
   PROF_BYTES(89 * p->N + 20 * p->Ep);   // B_f of one layer (psignn_f_tile_forward)
   if (stage1_mfma(false, false))
     LAUNCH("k_f_tile_layer", st, (k_f_tile<2, false, false, true><<<grid, TILE_THREADS, lds, st>>>(
-        plain_args(), (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, h,
+        plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, h,
         nullptr, 0, h0, prb, nullptr, out)));
   else
     LAUNCH("k_f_tile_layer", st, (k_f_tile<2, false, false, false><<<grid, TILE_THREADS, lds, st>>>(
-        plain_args(), (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, h,
+        plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, h,
         nullptr, 0, h0, prb, nullptr, out)));
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
@@ -923,22 +734,21 @@ int psignn_f_tile_fused(const psignn_plan* p, const float* W, int nl, float* xbu
     if (stage1_mfma(true, true)) {
       size_t lds = (size_t)p->max_rows * TileRow<true>::RS * 4;
       LAUNCH("k_f_tile_fused", st, (k_f_tile<3, true, true, true><<<grid, TILE_THREADS, lds, st>>>(
-        fa, (int)p->n_tiles, chunk, nullptr, TILE_ARGS, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), L::tp_neu(nl), 1, xbuf,
+        fa, (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), L::tp_neu(nl), 1, xbuf,
         nullptr, 0, h0, prb, nrm, nullptr)));
     } else {
       launch_mixed<true>(p, fa, "k_f_tile_fused", W, nl, xbuf, nullptr, 0, h0, prb, nrm, nullptr, st);
     }
   } else {
     using L = WLayout<2>;
-    size_t lds = std::max((size_t)p->max_rows * TileRow<false>::RS * 4, tile_lds_min());
-    const int32_t* tlist = tile_cost_order(p, chunk, st);
+    size_t lds = (size_t)p->max_rows * TileRow<false>::RS * 4;
     if (stage1_mfma(true, false))
       LAUNCH("k_f_tile_fused", st, (k_f_tile<2, false, true, true><<<grid, TILE_THREADS, lds, st>>>(
-        fa, (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(0), L::tp_layer(nl, false, 0), 0, 1, xbuf, nullptr, 0, h0, prb, nrm,
+        fa, (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(0), L::tp_layer(nl, false, 0), 0, 1, xbuf, nullptr, 0, h0, prb, nrm,
         nullptr)));
     else
       LAUNCH("k_f_tile_fused", st, (k_f_tile<2, false, true, false><<<grid, TILE_THREADS, lds, st>>>(
-        fa, (int)p->n_tiles, chunk, tlist, TILE_ARGS, W, L::layer(0), L::tp_layer(nl, false, 0), 0, 1, xbuf, nullptr, 0, h0, prb, nrm,
+        fa, (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(0), L::tp_layer(nl, false, 0), 0, 1, xbuf, nullptr, 0, h0, prb, nrm,
         nullptr)));
   }
   HIP_TRY(hipGetLastError());

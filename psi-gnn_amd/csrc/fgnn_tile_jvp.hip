@@ -16,10 +16,6 @@
 #include "tile_helpers.h"
 #include <stdlib.h>
 #include <string.h>
-#include <algorithm>
-#ifndef JVP_STAGE1_DEFAULT_MFMA
-#define JVP_STAGE1_DEFAULT_MFMA 0   // A/B at 1M nodes: 114 us (mfma) vs 100 us (valu)
-#endif
 
 __device__ __forceinline__ void lds_row10(const float* __restrict__ row, v2f* r) {  // 16-byte aligned
   float4 v0 = reinterpret_cast<const float4*>(row)[0], v1 = reinterpret_cast<const float4*>(row)[1];
@@ -76,20 +72,6 @@ __device__ __forceinline__ float edge_pass_jvp(const uint4* __restrict__ slots, 
   return deg;
 }
 
-#ifndef JVP_WAVES
-#define JVP_WAVES 0   // > 0: hold the register allocator to this many waves per SIMD (A/B in DESIGN.md)
-#endif
-#if JVP_WAVES > 0
-#define JVP_OCC __attribute__((amdgpu_waves_per_eu(JVP_WAVES, JVP_WAVES)))
-#else
-#define JVP_OCC
-#endif
-#ifndef JVP_PRIO
-#define JVP_PRIO 1   // 1: s_setprio(3) through stage 1 and the slot walk, 0 from the node update on (86.4 -> 83.6 us; k_jvp_lin: 49.2 -> 50.7, left off; profiles/r3_ab_prio_jvp.txt)
-#endif
-#ifndef JVP_XRELOAD
-#define JVP_XRELOAD 1
-#endif
 __device__ __forceinline__ v2f pk_mul_clamp(v2f a, v2f b) {   // clamp(a * b, 0, 1)
   v2f r;
   asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
@@ -179,8 +161,10 @@ __device__ __forceinline__ void edge_pass_jvp_both(const uint4* __restrict__ slo
 }
 
 // LN = false: the LayerNorm-off form of an intermediate layer of a multi-layer dirichlet block (launched as "k_jvp_tile_noln")
+// Holding the register allocator to four / five waves per SIMD was measured and removed (profiles/r2_f_tile_ab_runs.txt):
+// scratch spills, jvp_p 146 / 294 vs 95.7 us.
 template <int P, bool MIXED, bool MFMA1, bool LN = true>
-__global__ __launch_bounds__(TILE_THREADS) JVP_OCC void k_jvp_tile(int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
+__global__ __launch_bounds__(TILE_THREADS) void k_jvp_tile(int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
                                                            const int32_t* __restrict__ tile_ptr,
                                                            const int32_t* __restrict__ tile_slice,
                                                            const int32_t* __restrict__ halo, const int32_t* __restrict__ halo_cnt,
@@ -210,8 +194,9 @@ __global__ __launch_bounds__(TILE_THREADS) JVP_OCC void k_jvp_tile(int n_tiles, 
   const int32_t* hl = halo + (int64_t)tile * HALO_CAP;
   const float* T = W + tofs;
   const int doff = MIXED ? 2 * D : (n_t + n_h) * RS;   // floats from a node's value row to its tangent row
-  // ---- stage 1
-  if (JVP_PRIO) __builtin_amdgcn_s_setprio(3);
+  // ---- stage 1.  Wave priority 3 through stage 1 and the slot walk, 0 from the node update on: 86.4 -> 83.6 us
+  // (profiles/r3_ab_prio_jvp.txt)
+  __builtin_amdgcn_s_setprio(3);
   float x[D], dx[D];
   if constexpr (MFMA1) {
     // Both dense products of stage 1 -- state rows and tangent rows times the neighbour-side weights -- on the matrix
@@ -391,13 +376,13 @@ __global__ __launch_bounds__(TILE_THREADS) JVP_OCC void k_jvp_tile(int n_tiles, 
     edge_pass_jvp_both<RS>(slots, nslots, lds, T + L::T_A_TO, T + L::T_A_FR, Pi, dPi, Pi2, dPi2, S_to, dS_to, S_fr, dS_fr, deg_in,
                            deg_out, doff);
   }
-#if JVP_XRELOAD
-  PHASE();   // x / dx are not needed during the walk: re-read them (L2 hits) instead of holding 20 VGPRs across it
+  // x / dx are not needed during the walk: re-read them (L2 hits) instead of holding 20 VGPRs across it.  Holding them was
+  // measured and removed (profiles/r2_f_tile_ab_runs.txt): jvp_p 104.3 vs 94.9 us.
+  PHASE();
   load10(h + n * D, x);
   load10(tv + n * D, dx);
-#endif
   // ---- gate and update MLP (second Phi layer folded), values and tangents
-  if (JVP_PRIO) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
   const float* Wf = W + lofs + L::L_FOLD;
   const float* Wa = W + L::AL_W;
   const float* sto = reinterpret_cast<const float*>(S_to);
@@ -538,12 +523,12 @@ int psignn_f_tile_jvp_layer(const psignn_plan* p, const float* W, int nl, int l,
   ARG_CHECK(p && p->tiled && !p->mixed && l >= 0 && l < nl, "tiled JVP layer: dirichlet plans, 0 <= layer < n_layers");
   using L = WLayout<2>;
   const int chunk = (int)cdiv(p->n_tiles, 8);
-  const size_t lds = std::max((size_t)p->max_rows * 40 * 4, tile_lds_min());
+  const size_t lds = (size_t)p->max_rows * 40 * 4;
   ARG_CHECK(lds <= 160 * 1024, "tile + halo rows exceed the LDS budget of the tiled JVP");
-  // stage-1 form: PSIGNN_JVP_STAGE1 = mfma | valu (default: see the A/B in DESIGN.md)
+  // stage-1 form: PSIGNN_JVP_STAGE1 = mfma | valu; valu by default (A/B at 1M nodes: 114 us mfma vs 100 us valu)
   KNOB_INT(use_mfma, [] {
     const char* e = getenv("PSIGNN_JVP_STAGE1");
-    return e ? (int)(strcmp(e, "mfma") == 0) : (int)JVP_STAGE1_DEFAULT_MFMA;
+    return (int)(e && strcmp(e, "mfma") == 0);
   }());
   const int lofs = L::layer(l), tofs = L::tp_layer(nl, false, l);
 #define JVP_LAYER_ARGS (int)p->n_tiles, chunk, nullptr, JVP_TILE_ARGS, W, lofs, tofs, 0, h, prb, nullptr, v, out

@@ -37,13 +37,10 @@
 // stored form of the Neumann rows, a third mask set per slot, is not written yet).
 //
 // weight loads of mv2 pinned chunk by chunk (tile_helpers.h; A/B in profiles/r3_ab_mv2.txt: k_jvp_lin 53 -> 48.5 us)
-#ifndef MV2_LAUNDER
 #define MV2_LAUNDER 2
-#endif
 #include "tile_helpers.h"
 #include <stdlib.h>
 #include <string.h>
-#include <algorithm>
 
 #define LIN_REC 24            // floats per node record
 #define LIN_CHUNK 8           // slot dwords requested at once by the product kernel (a slice has ~6 slot rows)
@@ -319,22 +316,9 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lin_build(int n_tiles, int chu
 // ------------------------------------------------------------------------------------------------------------------
 // Product: out = J_f(h) v from the stored linearisation
 // ------------------------------------------------------------------------------------------------------------------
-#ifndef LIN_PRIO
-#define LIN_PRIO 0   // 1: s_setprio(3) through stage 1 and the slot walk, 0 from the node update on (as k_f_tile's TILE_PRIO = 15)
-#endif
-#ifndef LIN_REC_EARLY
-#define LIN_REC_EARLY 0   // 1: node record requested before the slot walk (127 VGPRs, four waves per SIMD)
-#endif
-#ifndef LIN_WAVES
-#define LIN_WAVES 0   // > 0: hold the register allocator to this many waves per SIMD
-#endif
-#if LIN_WAVES > 0
-#define LIN_OCC __attribute__((amdgpu_waves_per_eu(LIN_WAVES, LIN_WAVES)))
-#else
-#define LIN_OCC
-#endif
+// Wave priorities per phase as in k_f_tile were measured and removed (profiles/r3_ab_prio_jvp.txt): k_jvp_lin 49.2 -> 50.7 us.
 template <int P>
-__global__ __launch_bounds__(TILE_THREADS) LIN_OCC void k_jvp_lin(int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
+__global__ __launch_bounds__(TILE_THREADS) void k_jvp_lin(int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
                                                                   const TileCtx C, const float* __restrict__ W,
                                                                   int lofs, int tofs, const uint32_t* __restrict__ slot,
                                                                   const float* __restrict__ rec,
@@ -353,7 +337,6 @@ __global__ __launch_bounds__(TILE_THREADS) LIN_OCC void k_jvp_lin(int n_tiles, i
   const int32_t* hl = C.halo + (int64_t)tile * HALO_CAP;
   const float* T = W + tofs;
   float dx[D];
-  if (LIN_PRIO) __builtin_amdgcn_s_setprio(3);
   lin_stage1<P>(T, tv, t0, n_t, n_h, hl, lds, dx);
   __syncthreads();
   if (tid >= n_t) return;
@@ -380,9 +363,6 @@ __global__ __launch_bounds__(TILE_THREADS) LIN_OCC void k_jvp_lin(int n_tiles, i
     for (int i = 0; i < LIN_CHUNK; ++i) sw[i] = si[(int64_t)min(i, nslots - 1) * 64];
   }
   const float4* rp = reinterpret_cast<const float4*>(rec + n * LIN_REC);
-#if LIN_REC_EARLY
-  const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];   // requested ahead of the walk
-#endif
   v2f dPt[5], dPf[5], dS_to[5], dS_fr[5];
 #pragma unroll
   for (int p = 0; p < 5; ++p) dPt[p] = dPf[p] = dS_to[p] = dS_fr[p] = splat(0.f);
@@ -417,12 +397,11 @@ __global__ __launch_bounds__(TILE_THREADS) LIN_OCC void k_jvp_lin(int n_tiles, i
     }
   }
   // ---- tangent of the gate, the update MLP and LayerNorm
-  if (LIN_PRIO) __builtin_amdgcn_s_setprio(0);
-#if !LIN_REC_EARLY
-  PHASE();   // the node record and v's own row are not needed during the walk: read them here instead of holding 34 VGPRs across it
+  // the node record and v's own row are not needed during the walk: read them here instead of holding 34 VGPRs across it (the
+  // record requested before the walk took 127 VGPRs, four waves per SIMD; removed)
+  PHASE();
   const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];
   load10(tv + n * D, dx);
-#endif
   const float* Wf = W + lofs + L::L_FOLD;
   const float* Wa = W + L::AL_W;
   const float* dsto = reinterpret_cast<const float*>(dS_to);
@@ -822,7 +801,7 @@ extern "C" int psignn_lin_jvp(const psignn_lin_t* s, const float* W, int nl, con
   const psignn_plan* p = s->plan;
   ARG_CHECK(p->mixed ? nl >= 1 : nl == 1, "linearised JVP: single-layer blocks (mixed plans: the last layer)");
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = std::max((size_t)p->max_rows * 20 * 4, tile_lds_min());
+  const size_t lds = (size_t)p->max_rows * 20 * 4;
   if (p->mixed) {
     using L = WLayout<3>;
     const int na = (int)p->n_tiles_plain;
@@ -904,7 +883,7 @@ extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, con
   }
   using L = WLayout<2>;
   const int chunk = (int)cdiv(p->n_tiles, 8);
-  const size_t lds = std::max((size_t)p->max_rows * 20 * 4, tile_lds_min());
+  const size_t lds = (size_t)p->max_rows * 20 * 4;
   // w (tile + halo rows), out (40 N each), flags, node records (tile + halo rows), slot and transposed slot dwords
   PROF_BYTES((int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 8);
   LAUNCH("k_vjp_lin", st, (k_vjp_lin<2><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(

@@ -51,9 +51,6 @@ struct Status {
 // (block_sum_col, vec_helpers.h: RB = 1 024 threads per reduce block was tried for the column reads:
 // k_reduce_cb 9.7 vs 8.3 us, k_reduce_a_check unchanged -- a block's time is the 64-byte sectors it pulls through ONE CU, not
 // its load rounds; what helps is more blocks per column, RA below.)
-#ifndef SWEEP_V_AHEAD
-#define SWEEP_V_AHEAD 0   // 1: sweep 2 (16 floats per lane) requests the next pair's row before it works on the current one (A/B: slower)
-#endif
 #define RB 256
 #define RA 8     // row chunks per column of the a-reduction: coef_a arrives as RA partial sums that sweep 2 adds up itself
 struct psignn_broyden {
@@ -102,10 +99,6 @@ struct psignn_broyden {
   int stop_abs = 0;         // stop_mode of the next solve
   int64_t size_hint = 0;    // elements of ALL vectors swept together (batched shard): picks the vector width / j-split
   int plan_order = 1;       // 0 while iterates are kept in the caller's numbering (adjoint solve on the gather kernels)
-  // PSIGNN_GRAPH=1 (experiment): the launches of each poll_every-iteration chunk captured into a HIP
-  // graph, cached per chunk and re-used by later solves with the same arguments
-  std::vector<hipGraphExec_t> graphs;
-  uint64_t graph_key = 0;
 };
 
 __global__ void k_init_status(Status* st, double* rel_trace, double* abs_trace, int thr, int stop_abs = 0) {
@@ -278,7 +271,6 @@ __device__ void check_block(Status* st, const float* __restrict__ part, int npar
   *st = s;
 }
 
-#define DOTS_PART4 1   // (historic switch of the partials layout; the three-sweep forms below assume the current one)
 // dots pass: per-block partials of a_j = dx.U_j, c_j = V_j.dg, b_j = V_j.g   for j < k
 template <int VEC>
 __device__ __forceinline__ void dots_body(int64_t M, int k, const Status* __restrict__ st,
@@ -531,31 +523,14 @@ __device__ __forceinline__ void sweep_v_body(int64_t M, int k, const Status* __r
       stash_flush<2>(sh, q + 1, rows);
     }
   };
-  if (SWEEP_V_AHEAD && VEC == 16) {
-    // (experiment, off) Two pairs' rows in flight per wave: the sweep holds 96 VGPRs = five waves per SIMD with ONE 4 KB row per wave
-    // in flight; requesting the row of pair j + 1 before pair j is worked on (two register buffers, loop unrolled by two) doubles the
-    // bytes in flight per wave but costs a wave per SIMD (128 VGPRs).  Measured, interleaved on one box (profiles/r3_ab_sweepv.txt):
-    // K = 20 94.4 -> 99.5 us (0.69 -> 0.65), K = 100 361 -> 384 us -- the fifth wave is worth more than the second row.
-    float va[VEC], vb[VEC];
+  // One pair's row in flight per wave (96 VGPRs, five waves per SIMD).  Two rows in flight (128 VGPRs) were measured and removed
+  // (profiles/r3_ab_sweepv.txt): K = 20 94.4 -> 99.5 us, K = 100 361 -> 384 us -- the fifth wave is worth more than the second row.
+  for (int j = 0; j < k; ++j) {
+    float v[VEC];
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) va[i] = vb[i] = 0.f;
-    if (act && k > 0) ldv_stream<VEC>(V, e0, M, va);
-    int j = 0;
-    for (; j + 1 < k; j += 2) {
-      if (act) ldv_stream<VEC>(V + (int64_t)(j + 1) * ld, e0, M, vb);
-      step(j, va);
-      if (act && j + 2 < k) ldv_stream<VEC>(V + (int64_t)(j + 2) * ld, e0, M, va);
-      step(j + 1, vb);
-    }
-    if (j < k) step(j, va);
-  } else {
-    for (int j = 0; j < k; ++j) {
-      float v[VEC];
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) v[i] = 0.f;
-      if (act) ldv_stream<VEC>(V + (int64_t)j * ld, e0, M, v);
-      step(j, v);
-    }
+    for (int i = 0; i < VEC; ++i) v[i] = 0.f;
+    if (act) ldv_stream<VEC>(V + (int64_t)j * ld, e0, M, v);
+    step(j, v);
   }
   float p1 = 0.f, p2 = 0.f;
   if (act) {
@@ -696,9 +671,7 @@ __global__ __launch_bounds__(TB) void k_sweep_u2_bf16(int64_t M, int k, const St
 // the following iteration then needs no sweep over U for a (V and U read once each while k is small -- all of a K = 20
 // solve).  Direct dot products, exact; other partial-sum shapes than k_sweep_u1 (4 floats per lane here), so the last bits of
 // a differ from the three-sweep form's.  Writes one row of per-block partials: part[block * PARTA_LD + (j - j_keep0)].
-#ifndef U2D_UNROLL
 #define U2D_UNROLL 8   // stored pairs whose loads are in flight together (one wave per SIMD has to keep the memory pipe busy alone)
-#endif
 __device__ __forceinline__ void sweep_u2d_body(int64_t M, int k, const Status* __restrict__ st, float* __restrict__ U,
                                                float* __restrict__ upd, const float* __restrict__ dgv,
                                                const float* __restrict__ gv, const float* __restrict__ coef, int thr,
@@ -1247,14 +1220,12 @@ static int broyden_alloc(psignn_broyden* s) {
   // three-sweep update (launch_update): where an UNSPLIT sweep covers the chip -- long vectors at 16 floats per lane, mid-size
   // vectors and shards of short vectors at the 4-float width of their axpy pass.  PSIGNN_UVU=0|1 overrides (A/B, tests).
   s->uvu = 0;
-  if (DOTS_PART4) {
-    if (s->vec == 16 && s->jgroups == 1 && s->vec_ax == 16) {
-      s->uvu = 1; s->vec_u = 16; s->nblk_u = s->nblk;
-    } else if (s->vec_ax == 4 && s->vec == 16) {
-      s->uvu = 1; s->vec_u = 4; s->nblk_u = s->nblk_ax;
-    }
-    if (const char* e = getenv("PSIGNN_UVU")) if (atoi(e) == 0) s->uvu = 0;
+  if (s->vec == 16 && s->jgroups == 1 && s->vec_ax == 16) {
+    s->uvu = 1; s->vec_u = 16; s->nblk_u = s->nblk;
+  } else if (s->vec_ax == 4 && s->vec == 16) {
+    s->uvu = 1; s->vec_u = 4; s->nblk_u = s->nblk_ax;
   }
+  if (const char* e = getenv("PSIGNN_UVU")) if (atoi(e) == 0) s->uvu = 0;
   if (s->hist) {
     // bf16 pairs: always the unfolded three-sweep form (the two-pass form and the folded sweep 3 have no bf16 variant), 16 floats per
     // lane where the fp32 rules pick that width, else 4 floats unsplit; PSIGNN_UVU / PSIGNN_U2D_* do not apply
@@ -1347,8 +1318,6 @@ extern "C" void psignn_broyden_destroy(psignn_broyden_t* s) {
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (s->h_st) (void)hipHostFree(s->h_st);
-  for (hipGraphExec_t g : s->graphs)
-    if (g) (void)hipGraphExecDestroy(g);
   delete s;
 }
 
@@ -1573,42 +1542,8 @@ extern "C" int psignn_broyden_solve(psignn_broyden_t* s, const float* W, int nl,
   VPLAIN(s->vec, k_begin, (g, TB, 0, st), s->M, s->h0p, s->fx, s->xbuf, s->gbuf[0], s->upd);
   const bool fused = p->tiled && (nl == 1 || p->mixed);
   const int32_t* st_words = reinterpret_cast<const int32_t*>(s->st);
-  KNOB_INT(use_graph, [] { const char* e = getenv("PSIGNN_GRAPH"); return (int)(e && atoi(e) != 0); }());
-  if (use_graph && fused && !g_prof_on) {
-    // one graph per chunk of poll_every iterations (the iteration index is a kernel argument); every kernel returns at once
-    // when the device-side done flag is set, so a chunk that overshoots the stop is harmless
-    uint64_t key = (uint64_t)(uintptr_t)W * 1000003u ^ (uint64_t)(uintptr_t)nrmp * 7919u ^ (uint64_t)nl * 31u ^ (uint64_t)poll_every;
-    double e = eps;
-    key ^= *reinterpret_cast<uint64_t*>(&e);
-    if (key != s->graph_key) {
-      for (hipGraphExec_t g : s->graphs)
-        if (g) (void)hipGraphExecDestroy(g);
-      s->graphs.clear();
-      s->graph_key = key;
-    }
-    const int nchunk = (int)cdiv(s->thr, poll_every);
-    s->graphs.resize(nchunk, nullptr);
-    for (int c = 0; c < nchunk; ++c) {
-      if (!s->graphs[c]) {
-        hipGraph_t graph;
-        HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        for (int it = c * poll_every; it < std::min(s->thr, (c + 1) * poll_every); ++it) {
-          rc = psignn_f_tile_fused(p, W, nl, s->xbuf, s->M, st_words, offsetof(Status, done) / 4, sel_off_cur(), sel_off_nxt(),
-                                   s->upd, s->gbuf[(it + 1) & 1], s->h0p, s->prbp, nrmp, s->nrm_part, st);
-          if (rc >= 0) launch_update(s, it, eps, st, rc);
-        }
-        HIP_TRY(hipStreamEndCapture(st, &graph));
-        if (rc < 0) return rc;
-        HIP_TRY(hipGraphInstantiate(&s->graphs[c], graph, nullptr, nullptr, 0));
-        HIP_TRY(hipGraphDestroy(graph));
-      }
-      HIP_TRY(hipGraphLaunch(s->graphs[c], st));
-      rc = read_status(s, st);
-      if (rc) return rc;
-      if (s->h_st->done) break;
-    }
-    return finish(s, d_result, info, h_rel, h_abs, st);
-  }
+  // (Replaying each poll_every chunk of iterations from a captured HIP graph was measured and removed: no gain,
+  // profiles/r1_hip_graph_probe.json.)
   for (int it = 0; it < s->thr; ++it) {
     if (fused) {
       // one kernel: x_next = x_cur + update, f(x_next), g_new, dg, x_next and the norm partials

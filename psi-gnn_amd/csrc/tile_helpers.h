@@ -13,9 +13,7 @@
 // Workgroup = 4 waves = TILE_MAX lanes.  (A fifth wave that only helps with the halo rows of stage 1 was tried:
 // 79 us instead of 67 us per 1M-node evaluation -- it costs a wave slot per workgroup for the whole residency.)
 #define TILE_THREADS 256
-#ifndef EDGE_PD
 #define EDGE_PD 2   // prefetch distance of the slot loads in edge_pass
-#endif
 
 // Compiler-level memory barrier between the phases of a kernel.  The tile kernels read > 1 000 wave-uniform weights;
 // fully unrolled, the compiler hoists all their scalar loads to the top and then spills hundreds of SGPRs into VGPR
@@ -43,8 +41,9 @@ __device__ __forceinline__ v2f splat(float a) { return (v2f){a, a}; }
 // offset that went through an empty asm (always 0) to the block's pointer per chunk makes the chunk's loads data-dependent on
 // that statement: they cannot move above it.  (Laundering the pointer itself loses its no-alias property: vector loads, 256 VGPRs.)
 #ifndef MV2_LAUNDER
-#define MV2_LAUNDER 0   // 0: barrier only; 1: offset re-made per chunk; 2: ... by a statement that also waits for the chunk before.  Chosen per
-                        // file (fgnn_tile.hip, fgnn_tile_lin.hip: 2); which form leaves fewest parked SGPRs differs from kernel to kernel
+#define MV2_LAUNDER 0   // 0: barrier only; 2: offset re-made per chunk by a statement that also waits for the chunk before.  Chosen per
+                        // file (fgnn_tile.hip, fgnn_tile_lin.hip: 2); which form leaves fewest parked SGPRs differs from kernel to kernel.
+                        // The offset re-made without the wait was measured and removed (profiles/r3_ab_mv2.txt, MV2_LAUNDER=1).
 #endif
 template <int K>
 __device__ __forceinline__ void mv2(const float* __restrict__ WT, const float* x, v2f* acc, const float after = 0.f) {
@@ -55,22 +54,15 @@ __device__ __forceinline__ void mv2(const float* __restrict__ WT, const float* x
   // hoisted over it nor can the statement itself float above the arithmetic it waits for.  `after`: a value of the caller's that
   // the first chunk has to wait for (e.g. the last output of an independent product issued just before).
   int zero = 0;
-#if MV2_LAUNDER == 2
   asm volatile("" : "+s"(zero) : "v"(acc[0]), "v"(acc[4]), "v"(after));
-#else
-  asm volatile("" : "+s"(zero));
-#endif
   w += zero;
 #endif
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     if (MV2_CH > 0 && k > 0 && k % MV2_CH == 0) {
       PHASE();
-#if MV2_LAUNDER == 2
+#if MV2_LAUNDER
       asm volatile("" : "+s"(zero) : "v"(acc[0]), "v"(acc[4]));
-      w += zero;
-#elif MV2_LAUNDER
-      asm volatile("" : "+s"(zero));
       w += zero;
 #endif
     }
@@ -154,9 +146,6 @@ __device__ __forceinline__ float edge_pass(const uint4* __restrict__ slots, int 
 // value underflows below 2^-126, i.e. |z| < 2^-86) turns relu(z) = 2^40 clamp(2^-40 z) for every |z| < 2^40 ~ 1e12.
 // NaN clamps to 0, as v_max(NaN, 0) did.  The attr values a0, a1, a2 are broadcast from the halves of two register
 // pairs with op_sel (the compiler would spend six v_mov per slot on duplicating them).
-#ifndef CLAMP_PD
-#define CLAMP_PD 1    // slot records loaded this many rounds ahead in edge_pass_both_clamp (1 or 2)
-#endif
 #define RELU_SCALE 9.094947017729282e-13f   // 2^-40
 #define RELU_UNSCALE 1099511627776.f        // 2^40
 __device__ __forceinline__ v2f pk_fma_lo(v2f w, v2f a, v2f z) {  // z + w * (a.x, a.x)
@@ -175,12 +164,17 @@ __device__ __forceinline__ v2f pk_fma_lo_clamp(v2f w, v2f a, v2f z) {  // clamp(
   return r;
 }
 
-// edge_pass_both with the clamp form: S_to / S_fr come back UNSCALED (multiplied by 2^40 at the end).
+// Both directions of the neighbour sum in ONE walk over the slots: a pair-merged slot is decoded once, its 80-byte LDS row
+// [to | from] is read once, and the IN half (Phi_to, mirrored attr weights) and the OUT half (Phi_from) are evaluated back
+// to back.  Needs both attr blocks (60 wave-uniform floats) in SGPRs for the whole loop -- affordable once the phase
+// barriers keep every other scalar load out of the loop's live range.  S_to / S_fr come back UNSCALED (multiplied by 2^40
+// at the end).  Slot records are loaded one round ahead; two rounds ahead was measured and removed (profiles/r2_f_tile_ab_runs.txt:
+// plain f 61.0 - 62.6 vs 57.5 - 58.8 us).
 template <int RS>
 __device__ __forceinline__ void edge_pass_both_clamp(const uint4* __restrict__ slots, int nslots, const float* __restrict__ lds,
                                                      const float* __restrict__ AT_to, const float* __restrict__ AT_fr,
                                                      const v2f* Pi_to, const v2f* Pi_fr, v2f* S_to, v2f* S_fr,
-                                                     float& deg_in, float& deg_out, const uint4* first = nullptr) {
+                                                     float& deg_in, float& deg_out) {
   v2f wt[15], wf[15], pt[5], pf[5];
 #pragma unroll
   for (int i = 0; i < 15; ++i) {
@@ -195,12 +189,9 @@ __device__ __forceinline__ void edge_pass_both_clamp(const uint4* __restrict__ s
   }
   deg_in = deg_out = 0.f;
   if (nslots <= 0) return;
-  uint4 c0 = first ? *first : slots[0];   // `first`: slot row 0, loaded by the caller ahead of time
-#if CLAMP_PD == 2
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-#endif
+  uint4 c0 = slots[0];
   for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + CLAMP_PD, nslots - 1) * 64];
+    const uint4 nx = slots[(int64_t)min(r + 1, nslots - 1) * 64];
     const unsigned w = c0.x;
     if ((w & 0xFFFFu) != ELL_EMPTY) {
       const v2f a01 = (v2f){__uint_as_float(c0.y), __uint_as_float(c0.z)} * sc;
@@ -236,77 +227,12 @@ __device__ __forceinline__ void edge_pass_both_clamp(const uint4* __restrict__ s
         for (int p = 0; p < 5; ++p) S_fr[p] += z[p];
       }
     }
-#if CLAMP_PD == 2
-    c0 = c1;
-    c1 = nx;
-#else
     c0 = nx;
-#endif
   }
   const v2f us = splat(RELU_UNSCALE);
 #pragma unroll
   for (int p = 0; p < 5; ++p) {
     S_to[p] *= us;
     S_fr[p] *= us;
-  }
-}
-
-// Both directions of the neighbour sum in ONE walk over the slots: a pair-merged slot is decoded once, its 80-byte LDS row
-// [to | from] is read once, and the IN half (Phi_to, mirrored attr weights) and the OUT half (Phi_from) are evaluated back
-// to back.  Needs both attr blocks (60 wave-uniform floats) in SGPRs for the whole loop -- affordable once the phase
-// barriers keep every other scalar load out of the loop's live range.
-template <int RS>
-__device__ __forceinline__ void edge_pass_both(const uint4* __restrict__ slots, int nslots, const float* __restrict__ lds,
-                                               const float* __restrict__ AT_to, const float* __restrict__ AT_fr,
-                                               const v2f* Pi_to, const v2f* Pi_fr, v2f* S_to, v2f* S_fr, float& deg_in,
-                                               float& deg_out) {
-  v2f wt[15], wf[15];
-#pragma unroll
-  for (int i = 0; i < 15; ++i) {
-    wt[i] = reinterpret_cast<const v2f*>(AT_to)[i];
-    wf[i] = reinterpret_cast<const v2f*>(AT_fr)[i];
-  }
-  deg_in = deg_out = 0.f;
-  if (nslots <= 0) return;
-  uint4 c0 = slots[0];
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 2, nslots - 1) * 64];
-    const unsigned w = c0.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY) {
-      const v2f a0 = splat(__uint_as_float(c0.y)), a1 = splat(__uint_as_float(c0.z)), a2 = splat(__uint_as_float(c0.w));
-      const float4* row = reinterpret_cast<const float4*>(lds + (int)(w & 0xFFFFu) * RS);
-      const float4 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3], v4 = row[4];
-      if (w & SLOT_IN) {
-        v2f z[5] = {(v2f){v0.x, v0.y}, (v2f){v0.z, v0.w}, (v2f){v1.x, v1.y}, (v2f){v1.z, v1.w}, (v2f){v2.x, v2.y}};
-        deg_in += 1.f;
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] += Pi_to[p];
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wt[p], a0, z[p]);
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wt[5 + p], a1, z[p]);
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wt[10 + p], a2, z[p]);
-#pragma unroll
-        for (int p = 0; p < 5; ++p) S_to[p] += __builtin_elementwise_max(z[p], splat(0.f));
-      }
-      if (w & SLOT_OUT) {
-        v2f z[5] = {(v2f){v2.z, v2.w}, (v2f){v3.x, v3.y}, (v2f){v3.z, v3.w}, (v2f){v4.x, v4.y}, (v2f){v4.z, v4.w}};
-        deg_out += 1.f;
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] += Pi_fr[p];
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wf[p], a0, z[p]);
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wf[5 + p], a1, z[p]);
-#pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wf[10 + p], a2, z[p]);
-#pragma unroll
-        for (int p = 0; p < 5; ++p) S_fr[p] += __builtin_elementwise_max(z[p], splat(0.f));
-      }
-    }
-    c0 = c1;
-    c1 = nx;
   }
 }

@@ -10,20 +10,12 @@
 // Sum over the 64 lanes of a wave, the same value in every lane, fixed association (bitwise reproducible):
 // quad pairs, quads, half rows, rows of 16 as DPP operands of the adds (no LDS-path permutes), then the four row sums
 // through v_readlane.  The xor-shuffle form (`__shfl_xor` = ds_bpermute_b32, six dependent LDS round trips per value) held the
-// dots pass 10 % behind the axpy pass; -DWAVE_SUM_SHFL=1 rebuilds it for A/B runs.
-#ifndef WAVE_SUM_SHFL
-#define WAVE_SUM_SHFL 0
-#endif
+// dots pass 10 % behind the axpy pass; it was removed (profiles/r2_batch_sweep_ab.txt).
 template <int CTRL>
 __device__ __forceinline__ float dpp_perm(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 __device__ __forceinline__ float wave_sum(float v) {
-#if WAVE_SUM_SHFL
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-#else
   v += dpp_perm<0xB1>(v);    // quad_perm:[1,0,3,2]
   v += dpp_perm<0x4E>(v);    // quad_perm:[2,3,0,1]
   v += dpp_perm<0x141>(v);   // row_half_mirror
@@ -34,7 +26,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 32));
   const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vi, 48));
   return (r0 + r1) + (r2 + r3);
-#endif
 }
 
 // Two per-lane values -> ONE pair per block (wave shuffles, then the 4 wave sums through LDS, fixed order).
@@ -75,25 +66,10 @@ __device__ __forceinline__ void ldv(const float* __restrict__ p, int64_t e0, int
     }
   }
 }
-// Loads of the U / V sweeps.  Non-temporal loads were measured and REJECTED: although every byte is read once
-// per pass, k_dots / k_axpy at N = 1M, k = 0..49 took 557 / 550 us per launch with nt against 365 / 382 us with
-// default-policy loads (round 1, MI355X).  -DPSIGNN_NT_SWEEPS=1 rebuilds the nt variant for A/B timing.
-#ifndef PSIGNN_NT_SWEEPS
-#define PSIGNN_NT_SWEEPS 0
-#endif
-typedef float f4v __attribute__((ext_vector_type(4)));
+// Loads of the U / V sweeps (fp32 pairs here, bf16 pairs below).  Non-temporal loads were measured and removed (round 1, DESIGN.md
+// section 4): k_dots / k_axpy at N = 1M, k = 0..49 took 557 / 550 us per launch with them against 365 / 382 us with default-policy loads.
 template <int VEC>
 __device__ __forceinline__ void ldv_stream(const float* __restrict__ p, int64_t e0, int64_t M, float* r) {
-#if PSIGNN_NT_SWEEPS
-  if (e0 + (VEC / 4 - 1) * 256 + 4 <= M) {
-#pragma unroll
-    for (int i = 0; i < VEC / 4; ++i) {
-      f4v t = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p + e0 + i * 256));
-      r[4 * i] = t.x; r[4 * i + 1] = t.y; r[4 * i + 2] = t.z; r[4 * i + 3] = t.w;
-    }
-    return;
-  }
-#endif
   ldv<VEC>(p, e0, M, r);
 }
 

@@ -1,10 +1,6 @@
 #!/bin/bash
-# Runs ON THE GPU BOX: occupancy sweep and SQ counters of the linearised JVP (k_jvp_lin) and of its build pass, 1M nodes
+# Runs ON THE GPU BOX: SQ counters of the linearised JVP (k_jvp_lin) and of its build pass, 1M nodes
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-echo "== occupancy sweep (workgroups per CU = floor(160 KB / LDS request); default request 25.9 KB -> 6)"
-for mn in 0 30000 38000 50000 62000; do
-  echo "LDS_MIN=$mn: $(PSIGNN_TILE_LDS_MIN=$mn timeout -k 10 200 python3 scripts/prof_f.py 1000000 50 0 dirichlet adjoint 2>&1 | grep -E 'lin jvp|jvp_p' | tr '\n' ' ')"
-done
 echo "== SQ counters (mean per launch)"
 OUT=gpurun_out/r3_pmc_lin
 rm -rf $OUT && mkdir -p $OUT
