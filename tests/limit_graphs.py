@@ -285,3 +285,18 @@ def check_tiles(got, want64, want32, perm, tile_ptr, tau, what, named=()):
     assert bad.size == 0, (what, {int(t): (float(e[t]), float(bound[t])) for t in bad[:8]})
     k = int(np.argmax(e))
     return float(e[k]), float(e32[k])
+
+
+def check_params(got, want64, want32, tau, what):
+    """Parameter gradients tensor by tensor: e_k = |got_k - want_k| / max(|want_k|, 1e-4 scale) (scale: the largest |want_k|)
+    <= max(tau, 16 e32_k), e32_k the same measure of the float32 oracle.  Returns (worst e_k, its e32_k)."""
+    scale = max(float(t.double().norm()) for t in want64.values())
+    err = lambda a, b: float((a.detach().cpu().double() - b.double()).norm()) / max(float(b.double().norm()), 1e-4 * scale)
+    bad, worst = {}, (0.0, 0.0)
+    for k, w in want64.items():
+        e, e32 = err(got[k], w), err(want32[k], w)
+        if not e <= max(tau, 16 * e32):
+            bad[k] = (e, e32)
+        worst = max(worst, (e, e32))
+    assert not bad, (what, bad)
+    return worst

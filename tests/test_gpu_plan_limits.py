@@ -83,15 +83,7 @@ class Run:
         print(f"LIMITS {self.name} {op}: worst tile {e:.2e} (fp32 oracle {e32:.2e}) named {named}")
 
     def check_params(self, op, got, want64, want32, tau):
-        scale = max(float(t.double().norm()) for t in want64.values())
-        err = lambda a, b: float((a.detach().cpu().double() - b.double()).norm()) / max(float(b.double().norm()), 1e-4 * scale)
-        bad, worst = {}, (0.0, 0.0)
-        for k, w in want64.items():
-            e, e32 = err(got[k], w), err(want32[k], w)
-            if not e <= max(tau, 16 * e32):
-                bad[k] = (e, e32)
-            worst = max(worst, (e, e32))
-        assert not bad, (self.name, op, bad)
+        worst = lg.check_params(got, want64, want32, tau, f"{self.name} {op}")
         self.report[op] = worst
         print(f"LIMITS {self.name} {op}: worst tensor {worst[0]:.2e} (fp32 oracle {worst[1]:.2e})")
 
