@@ -154,7 +154,8 @@ int psignn_f_jvp(const psignn_plan_t* plan, const float* d_weights, int n_layers
  * psignn_lin_build evaluates the value path of f once and stores what the Jacobian needs (relu masks of every edge direction as
  * wave-level bit masks, per-node gate / update / LayerNorm quantities); psignn_lin_jvp then applies J_f(h) as a linear operator,
  * at about half the cost of psignn_f_jvp.  Tiled plans; dirichlet: single-layer blocks; mixed (d_normals_plan required; the tiles
- * holding Neumann nodes run the direct kernel at a copy of the state kept by the build).  h, prb, normals, v, out in PLAN order
+ * holding Neumann nodes run the direct kernel at a copy of the state kept by the build, unless the handle stores the Neumann rows:
+ * psignn_lin_create_opts below).  h, prb, normals, v, out in PLAN order
  * (psignn_plan_permute).  The handle keeps a pointer to the plan: destroy it before the plan.
  * replaces: nothing executable in the reference (see psignn_f_jvp); same product as psignn_f_jvp up to fp32 summation order. */
 typedef struct psignn_lin psignn_lin_t;
@@ -171,12 +172,25 @@ int psignn_lin_jvp(const psignn_lin_t* lin, const float* d_weights, int n_layers
  * counts them; the build and psignn_lin_jvp do not use them).  A handle is single-stream: its build and its products (which may write
  * the handle's transposed masks on the first call after a build) must be issued on one stream, or ordered by the caller.  A plan whose
  * slots the reverse map cannot pair is refused (PSIGNN_EINVAL) rather than answered without some edges.  Mixed plans: the tiled VJP
- * at the state kept by the build (no cheaper than psignn_f_vjp_p there; no stored form of the Neumann rows yet), d_work =
+ * at the state kept by the build (no cheaper than psignn_f_vjp_p there; psignn_lin_create_opts below stores the Neumann rows instead), d_work =
  * psignn_f_workspace_floats(plan) floats of scratch; dirichlet plans ignore d_work.  Errors: not built, in-place, wrong depth.
  * replaces: torch.autograd.grad(new_H, H, v) at one fixed state H*: the backward hook (dirichlet/psignn/model.py:210-223), the power
  *           method (:437-452) and the Hutchinson estimate (:416-435); same product as psignn_f_vjp_p up to fp32 summation order. */
 int psignn_lin_vjp(const psignn_lin_t* lin, const float* d_weights, int n_layers, const float* d_w_plan, float* d_out_plan,
                    float* d_work, void* stream);
+/* psignn_lin_create with options.  neumann_stored = 0 is psignn_lin_create.  neumann_stored = 1 on a mixed plan stores the Neumann
+ * rows as well: the build runs every tile through the build kernel (a Neumann row keeps the relu masks of Phi_neumann's first layer
+ * on its OUT slots in the Phi_from bit field of its slot dwords, and 1 / sqrt(var + eps), the hidden relu mask of update_neumann and
+ * y_hat in its node record), psignn_lin_jvp applies that stored operator on the tiles holding Neumann nodes too (no direct kernel),
+ * and psignn_lin_vjp is its exact transpose from the same dwords and records (no tiled VJP; d_work is accepted and ignored).  Such a
+ * handle keeps no copy of h / prb / normals (psignn_lin_bytes reports what is held).  On a dirichlet plan the option is accepted and
+ * changes nothing.  psignn_lin_neumann_stored: 1 when the handle stores the Neumann rows (mixed plan and option on), else 0.
+ * replaces: torch.autograd.grad(new_H, H, v) at one fixed state of the mixed family, whose Neumann rows are
+ *           LayerNorm(update_neumann([h, Phi_neumann(h), prb, normal])) (mixed/psignn/model.py:225,233-236,241): the backward hook,
+ *           the power method and the Hutchinson estimate of mixed/psignn/model.py; same products as psignn_f_jvp / psignn_f_vjp_p
+ *           up to fp32 summation order. */
+int psignn_lin_create_opts(psignn_lin_t** out, const psignn_plan_t* plan, int neumann_stored);
+int psignn_lin_neumann_stored(const psignn_lin_t* lin);
 
 /* Vector-Jacobian product out = w^T (df/dh) at h (both families), as two gather passes over the plan's
  * CSR/CSC lists (no atomics).  d_normals: (N,2) for mixed plans, else NULL.

@@ -62,6 +62,8 @@ SIGNATURES = {
     "psignn_lin_build": (_INT, [_P, _P, _INT, _P, _P, _P, _P]),
     "psignn_lin_jvp": (_INT, [_P, _P, _INT, _P, _P, _P]),
     "psignn_lin_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P]),
+    "psignn_lin_create_opts": (_INT, [_P, _P, _INT]),
+    "psignn_lin_neumann_stored": (_INT, [_P]),
     "psignn_f_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P]),
     "psignn_f_vjp_p": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P]),
     "psignn_param_grad_size": (_I64, [_INT, _INT]),

@@ -16,9 +16,9 @@
 //
 // Against k_jvp_tile at 1M nodes: ~0.4 x the VALU instructions per wave, 80-byte LDS rows (tangent projections only: six
 // workgroups per CU instead of three), about the same bytes (the 96-byte node record replaces the h row, the 16-byte slot records
-// shrink to 4 bytes).  Dirichlet plans with a single-layer block; mixed plans: the tiles WITHOUT Neumann nodes (all but the boundary
-// tiles) go through the stored linearisation, the few tiles holding Neumann nodes through k_jvp_tile at the state kept from the build
-// (a Neumann row needs a third mask set per slot; not worth a second record format for ~2 % of the tiles).
+// shrink to 4 bytes).  Dirichlet plans with a single-layer block; mixed plans by default: the tiles WITHOUT Neumann nodes (all but the
+// boundary tiles) go through the stored linearisation, the few tiles holding Neumann nodes through k_jvp_tile at the state kept from
+// the build; with the Neumann rows stored (below) every tile goes through the stored form.
 //
 // Transposed product (psignn_lin_vjp, k_vjp_lin): out = J_f(h)^T w from the SAME masks and node records, so that it is the exact
 // transpose of psignn_lin_jvp (masks recomputed from projections could flip where a pre-activation is ~0).  Per node n, the node-local
@@ -33,8 +33,24 @@
 // matched per edge direction: the Phi_to and Phi_from masks of one pair may come from two different slots of n's row.
 // Both arrays are allocated on the first psignn_lin_vjp: the build and psignn_lin_jvp do not change.  One launch per product:
 // stage 1 computes c for the tile and halo rows into 80-byte LDS rows (halo rows recomputed per tile), stage 2 walks the slots from
-// u's side (a gather: fixed order, no atomics, bitwise reproducible).  Mixed plans: the tiled VJP at the state kept by the build (a
-// stored form of the Neumann rows, a third mask set per slot, is not written yet).
+// u's side (a gather: fixed order, no atomics, bitwise reproducible).  Mixed plans: the tiled VJP at the state kept by the build.
+//
+// Neumann rows stored (psignn_lin_create_opts(.., neumann_stored = 1), mixed plans, opt-in): a Neumann row is REPLACED by
+// LayerNorm(update_neumann([h, Phi_neumann(h), prb, normal])) (mixed/psignn/model.py:225,233-236,241 of the reference), so its
+// Phi_to / Phi_from masks are never used and Phi_neumann sums over the row's OUT edges -- the edge set of Phi_from.  No third mask
+// set is needed: the row keeps Phi_neumann's first-layer relu masks in the Phi_from bit field of its slot dwords (Phi_to bits 0) and
+// {1 / sqrt(var + eps), hidden relu mask of update_neumann, y_hat[10]} in its 24-float record; which rows are Neumann rows comes from
+// the plan's node flags.  Then every tile goes through the stored form and the handle keeps no copy of the state:
+//   build   k_lin_build<3> on the plan's first tile group, k_lin_build<3, true> on the tiles holding Neumann nodes (144-byte LDS
+//           rows [Pj_to | Pj_from | Pj_neu | pad]; the Neumann branch repeats k_jvp_tile's value path operation by operation)
+//   J v     k_jvp_lin<3> / k_jvp_lin<3, true> on the same two groups:  J v [n] = LN'( N2 (1[q > 0] (N1h v_n + G_n dS_n)) ),
+//           dS_n = sum over n's OUT slots of mask (W1i_neu v_n + W1j_neu v_u); only the second group pays for the third LDS column
+//   J^T w   k_vjp_lin_mixed<3>, ONE launch; per tile the plain or the Neumann form by "a Neumann row among the tile's own and HALO
+//           rows" (a tile without Neumann nodes of its own still receives c_neu of a halo row): c[n] = [0 | c_neu[n]] keeps the 80-byte LDS rows; bit 30 of a
+//           transposed slot dword marks a Neumann partner (k_lin_rev<true>), whose masked c_neu goes to a third sum, applied through
+//           W1j_neu^T; a Neumann row's own side is W1i_neu^T (cnt . c_neu).  The tile list is made once per handle (k_lin_vgroup + the
+//           host), Neumann tiles on the first workgroups.
+// Every kernel instantiation that exists without the option is unchanged (NEU = false is the code as it was).
 //
 // weight loads of mv2 pinned chunk by chunk (tile_helpers.h; A/B in profiles/r3_ab_mv2.txt: k_jvp_lin 53 -> 48.5 us)
 #define MV2_LAUNDER 2
@@ -57,15 +73,25 @@ struct psignn_lin {
   mutable uint32_t* tslot = nullptr;  // (ell_rows, 64) transposed slot dwords, masks re-filled once per build
   mutable int tfilled = 0;            // tslot holds the masks of the last build
   mutable size_t tbytes = 0;
+  // mixed plans, Neumann rows stored (psignn_lin_create_opts): no state copies; the transposed product's tile groups
+  int neu = 0;
+  int32_t* vlist = nullptr;           // (8 cdiv(n_tiles, 8)) tile list of k_vjp_lin_mixed
+  int n_vplain = 0;                   // tiles without a Neumann row among tile + halo
 };
+#define LIN_RS_NEU 36         // floats per LDS row of the tiles holding Neumann nodes: [Pj_to | Pj_from | Pj_neu | pad 6].  A
+                              // ds_read_b128 is served over 16 slots of 16 bytes: a 144-byte row starts on slot 9 r mod 16, an odd
+                              // stride -- sixteen consecutive rows on sixteen different slots, as the 80-byte rows (5 r mod 16); the
+                              // 120-byte payload unpadded would misalign the b128 reads and 128 bytes put every row on slot 0
 
 // Stage 1 of both kernels: rows [Pj_to | Pj_from] = W1j_{to,from} src[node] of the tile's own and halo nodes -> 80-byte LDS rows
 // (own row by its lane; halo rows as HALF rows over all four waves, as in k_f_tile).  Returns the lane's own src row in x.
-template <int P>
+// NEU: 144-byte rows with a third column Pj_neu = W1j_neu src[node] (the Phi_neumann projection a Neumann row's OUT slots read)
+template <int P, bool NEU = false>
 __device__ __forceinline__ void lin_stage1(const float* __restrict__ T, const float* __restrict__ src, const int32_t t0, const int n_t,
-                                           const int n_h, const int32_t* __restrict__ hl, float* __restrict__ lds, float* x) {
+                                           const int n_h, const int32_t* __restrict__ hl, float* __restrict__ lds, float* x,
+                                           const float* __restrict__ TN = nullptr) {
   using L = WLayout<P>;
-  constexpr int RS = 20;
+  constexpr int RS = NEU ? LIN_RS_NEU : 20;
   const int tid = threadIdx.x;
   const int32_t hidx_w = (tid >> 6 & 1) * 64 + (tid & 63);
   int32_t hnode = 0;
@@ -89,6 +115,21 @@ __device__ __forceinline__ void lin_stage1(const float* __restrict__ T, const fl
     q[2] = make_float4(ta[4].x, ta[4].y, tb[0].x, tb[0].y);
     q[3] = make_float4(tb[1].x, tb[1].y, tb[2].x, tb[2].y);
     q[4] = make_float4(tb[3].x, tb[3].y, tb[4].x, tb[4].y);
+  }
+  if constexpr (NEU) {   // third column of the own and the halo rows, one row per thread
+    for (int row = tid; row < n_t + n_h; row += TILE_THREADS) {
+      float xq[D];
+      load10(src + (row < n_t ? (int64_t)(t0 + row) : (int64_t)hl[row - n_t]) * D, xq);
+      v2f tc[5];
+#pragma unroll
+      for (int p = 0; p < 5; ++p) tc[p] = splat(0.f);
+      PHASE();
+      mv2<D>(TN + L::N_W1J, xq, tc);
+      float4* q = reinterpret_cast<float4*>(lds + row * RS + 2 * D);
+      q[0] = make_float4(tc[0].x, tc[0].y, tc[1].x, tc[1].y);
+      q[1] = make_float4(tc[2].x, tc[2].y, tc[3].x, tc[3].y);
+      reinterpret_cast<float2*>(q + 2)[0] = make_float2(tc[4].x, tc[4].y);
+    }
   }
   const int half = __builtin_amdgcn_readfirstlane(tid >> 7);   // 0: Phi_to columns, 1: Phi_from columns
   for (int hb = 0; hb < n_h; hb += 128) {
@@ -127,14 +168,19 @@ __device__ __forceinline__ void lin_stage1(const float* __restrict__ T, const fl
 // ------------------------------------------------------------------------------------------------------------------
 // Build: the value path of f at h (same formulas and operation order as k_jvp_tile's value half), storing what J_f(h) needs.
 // ------------------------------------------------------------------------------------------------------------------
-template <int P>
+// NEU (the tiles of a mixed plan that hold Neumann nodes, handles that store the Neumann rows): 144-byte LDS rows with the
+// Phi_neumann column; a Neumann row stores the relu masks of Phi_neumann's first layer on its OUT slots in the Phi_from bit field
+// (Phi_to bits 0: the row is REPLACED by LayerNorm(update_neumann(..)), its Phi_to / Phi_from sums are never used) and the record
+// {0, 0, 1 / sqrt(var + eps), hidden relu mask of update_neumann, 0 x 10, y_hat[10]} -- the value path of k_jvp_tile's Neumann branch.
+template <int P, bool NEU = false>
 __global__ __launch_bounds__(TILE_THREADS) void k_lin_build(int n_tiles, int chunk, const int32_t* __restrict__ tile_list, const TileCtx C,
                                                             const float* __restrict__ W,
                                                             int lofs, int tofs, const float* __restrict__ h,
                                                             const float* __restrict__ prb, uint32_t* __restrict__ slot,
-                                                            float* __restrict__ rec) {
+                                                            float* __restrict__ rec, int tnofs = 0,
+                                                            const float* __restrict__ nrm = nullptr) {
   using L = WLayout<P>;
-  constexpr int RS = 20;
+  constexpr int RS = NEU ? LIN_RS_NEU : 20;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int slot_ = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
   if (slot_ >= n_tiles) return;
@@ -149,17 +195,114 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lin_build(int n_tiles, int chu
   float x[D];
 #pragma unroll
   for (int o = 0; o < D; ++o) x[o] = 0.f;
-  lin_stage1<P>(T, h, t0, n_t, n_h, hl, lds, x);
+  lin_stage1<P, NEU>(T, h, t0, n_t, n_h, hl, lds, x, W + tnofs);
   __syncthreads();
   if (tid >= n_t) return;
   const int lane = tid & 63;
   const int64_t n = (int64_t)t0 + tid;
-  if (C.flags_p[n] & FLAG_DIRICHLET) return;   // (the product kernel writes zeros for such a row without looking at its slots)
+  const uint8_t fl = C.flags_p[n];
+  if (fl & FLAG_DIRICHLET) return;   // (the product kernel writes zeros for such a row without looking at its slots)
   const int slice = __builtin_amdgcn_readfirstlane((tn ? tile * (tn >> 6) : C.tile_slice[tile]) + (tid >> 6));
   const int srow0 = C.slice_off[slice];
   const int nslots = C.slice_deg[slice];
   const uint4* slots = C.ell + (int64_t)srow0 * 64 + lane;
   uint32_t* so = slot + (int64_t)srow0 * 64 + lane;
+  if constexpr (NEU) {
+    if (fl & FLAG_NEUMANN) {
+      // ---- Neumann row: y = N2 relu(q) + nb2, q = nb1 + deg gN + N1h x + Gn S_n + N1p [prb | normal]; formulas and operation
+      // order of k_jvp_tile's Neumann branch (edge_pass_jvp: z = Pi + Pj, then the three attr fmas)
+      const float* TN = W + tnofs;
+      v2f Pi[5], S_n[5], wa[15];
+      ld5(TN + L::N_B1, Pi);
+#pragma unroll
+      for (int p = 0; p < 5; ++p) S_n[p] = splat(0.f);
+      PHASE();
+      mv2<D>(TN + L::N_W1I, x, Pi);
+#pragma unroll
+      for (int i = 0; i < 15; ++i) wa[i] = reinterpret_cast<const v2f*>(TN + L::N_A)[i];
+      float deg_out = 0.f;
+      for (int r = 0; r < nslots; ++r) {
+        const uint4 c0 = slots[(int64_t)r * 64];
+        const unsigned w = c0.x;
+        unsigned word = 0;
+        if ((w & 0xFFFFu) != ELL_EMPTY) {
+          word = w & 0xFFFFu;
+          if (w & SLOT_OUT) {
+            const v2f a0 = splat(__uint_as_float(c0.y)), a1 = splat(__uint_as_float(c0.z)), a2 = splat(__uint_as_float(c0.w));
+            const float4* rp = reinterpret_cast<const float4*>(lds + (int)word * RS + 2 * D);
+            const float4 v0 = rp[0], v1 = rp[1];
+            const float2 v2 = reinterpret_cast<const float2*>(rp + 2)[0];
+            v2f z[5] = {(v2f){v0.x, v0.y}, (v2f){v0.z, v0.w}, (v2f){v1.x, v1.y}, (v2f){v1.z, v1.w}, (v2f){v2.x, v2.y}};
+            deg_out += 1.f;
+#pragma unroll
+            for (int p = 0; p < 5; ++p) z[p] = Pi[p] + z[p];
+#pragma unroll
+            for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
+#pragma unroll
+            for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[5 + p], a1, z[p]);
+#pragma unroll
+            for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[10 + p], a2, z[p]);
+#pragma unroll
+            for (int p = 0; p < 5; ++p) {
+              S_n[p] += __builtin_elementwise_max(z[p], splat(0.f));
+              word |= (z[p].x > 0.f ? 1u : 0u) << (20 + 2 * p);
+              word |= (z[p].y > 0.f ? 1u : 0u) << (21 + 2 * p);
+            }
+          }
+        }
+        so[(int64_t)r * 64] = word;
+      }
+      v2f q[5], gN[5], y2[5];
+      ld5(TN + L::N_NB1, q);
+      ld5(TN + L::N_gN, gN);
+#pragma unroll
+      for (int p = 0; p < 5; ++p) q[p] = __builtin_elementwise_fma(splat(deg_out), gN[p], q[p]);
+      PHASE();
+      mv2<D>(TN + L::N_N1H, x, q);
+      PHASE();
+      mv2<D>(TN + L::N_GN, reinterpret_cast<const float*>(S_n), q);
+      float pq[P + 2];
+#pragma unroll
+      for (int k = 0; k < P; ++k) pq[k] = prb[n * P + k];
+      pq[P] = nrm[n * 2];
+      pq[P + 1] = nrm[n * 2 + 1];
+      PHASE();
+      mv2<P + 2>(TN + L::N_N1P, pq, q);
+      unsigned hm = 0;
+#pragma unroll
+      for (int p = 0; p < 5; ++p) {
+        hm |= (q[p].x > 0.f ? 1u : 0u) << (2 * p);
+        hm |= (q[p].y > 0.f ? 1u : 0u) << (2 * p + 1);
+        q[p] = __builtin_elementwise_max(q[p], splat(0.f));
+      }
+      ld5(TN + L::N_NB2, y2);
+      PHASE();
+      mv2<D>(TN + L::N_N2, reinterpret_cast<const float*>(q), y2);
+      const float* y = reinterpret_cast<const float*>(y2);
+      float mu = 0.f;
+#pragma unroll
+      for (int o = 0; o < D; ++o) mu += y[o];
+      mu *= (1.f / D);
+      float var = 0.f;
+#pragma unroll
+      for (int o = 0; o < D; ++o) {
+        const float c = y[o] - mu;
+        var = fmaf(c, c, var);
+      }
+      var *= (1.f / D);
+      const float rs = 1.f / sqrtf(var + 1e-5f);
+      float yh[D];
+#pragma unroll
+      for (int o = 0; o < D; ++o) yh[o] = (y[o] - mu) * rs;
+      float4* rp = reinterpret_cast<float4*>(rec + n * LIN_REC);
+      rp[0] = make_float4(0.f, 0.f, rs, __uint_as_float(hm));
+      rp[1] = rp[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+      rp[3] = make_float4(0.f, 0.f, yh[0], yh[1]);
+      rp[4] = make_float4(yh[2], yh[3], yh[4], yh[5]);
+      rp[5] = make_float4(yh[6], yh[7], yh[8], yh[9]);
+      return;
+    }
+  }
   // ---- neighbour sums and masks
   v2f S_to[5], S_fr[5], pt[5], pf[5], wt[15], wf[15];
   {
@@ -317,14 +460,17 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lin_build(int n_tiles, int chu
 // Product: out = J_f(h) v from the stored linearisation
 // ------------------------------------------------------------------------------------------------------------------
 // Wave priorities per phase as in k_f_tile were measured and removed (profiles/r3_ab_prio_jvp.txt): k_jvp_lin 49.2 -> 50.7 us.
-template <int P>
+// NEU (tiles holding Neumann nodes, Neumann rows stored): a Neumann row's walk sums its Phi_from bit field over the third LDS column,
+//   J v = LN'( N2 (1[q > 0] (N1h v_n + G_n dS_n)) ),  dS_n = sum over the OUT slots of mask (W1i_neu v_n + W1j_neu v_u)
+template <int P, bool NEU = false>
 __global__ __launch_bounds__(TILE_THREADS) void k_jvp_lin(int n_tiles, int chunk, const int32_t* __restrict__ tile_list,
                                                                   const TileCtx C, const float* __restrict__ W,
                                                                   int lofs, int tofs, const uint32_t* __restrict__ slot,
                                                                   const float* __restrict__ rec,
-                                                                  const float* __restrict__ tv, float* __restrict__ out) {
+                                                                  const float* __restrict__ tv, float* __restrict__ out,
+                                                                  int tnofs = 0) {
   using L = WLayout<P>;
-  constexpr int RS = 20;
+  constexpr int RS = NEU ? LIN_RS_NEU : 20;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int slot_ = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
   if (slot_ >= n_tiles) return;
@@ -337,12 +483,13 @@ __global__ __launch_bounds__(TILE_THREADS) void k_jvp_lin(int n_tiles, int chunk
   const int32_t* hl = C.halo + (int64_t)tile * HALO_CAP;
   const float* T = W + tofs;
   float dx[D];
-  lin_stage1<P>(T, tv, t0, n_t, n_h, hl, lds, dx);
+  lin_stage1<P, NEU>(T, tv, t0, n_t, n_h, hl, lds, dx, W + tnofs);
   __syncthreads();
   if (tid >= n_t) return;
   const int64_t n = (int64_t)t0 + tid;
   float dy[D];
-  if (C.flags_p[n] & FLAG_DIRICHLET) {
+  const uint8_t fl = C.flags_p[n];
+  if (fl & FLAG_DIRICHLET) {
 #pragma unroll
     for (int o = 0; o < D; ++o) dy[o] = 0.f;
     store10(out + n * D, dy);
@@ -370,6 +517,17 @@ __global__ __launch_bounds__(TILE_THREADS) void k_jvp_lin(int n_tiles, int chunk
   mv2<D>(T + L::T_W1I_TO, dx, dPt);
   PHASE();
   mv2<D>(T + L::T_W1I_FR, dx, dPf);
+  bool neu = false;
+  if constexpr (NEU) {   // a Neumann row: its (only) bit field is Phi_neumann's -- own projection and neighbour column of Phi_neumann
+    neu = fl & FLAG_NEUMANN;
+    v2f dPn[5];
+#pragma unroll
+    for (int p = 0; p < 5; ++p) dPn[p] = splat(0.f);
+    PHASE();
+    mv2<D>(W + tnofs + L::N_W1I, dx, dPn);
+#pragma unroll
+    for (int p = 0; p < 5; ++p) dPf[p] = neu ? dPn[p] : dPf[p];
+  }
   for (int r0 = 0; r0 < nslots; r0 += LIN_CHUNK) {
 #pragma unroll
     for (int i = 0; i < LIN_CHUNK; ++i) {
@@ -377,8 +535,15 @@ __global__ __launch_bounds__(TILE_THREADS) void k_jvp_lin(int n_tiles, int chunk
         const uint32_t w = sw[i];
         const float4* q = reinterpret_cast<const float4*>(lds + (int)(w & 1023u) * RS);
         const float4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3], v4 = q[4];
-        const float d[20] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y,
-                             v2.z, v2.w, v3.x, v3.y, v3.z, v3.w, v4.x, v4.y, v4.z, v4.w};
+        float d[20] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y,
+                       v2.z, v2.w, v3.x, v3.y, v3.z, v3.w, v4.x, v4.y, v4.z, v4.w};
+        if constexpr (NEU) {
+          const float4 v5 = q[5], v6 = q[6];
+          const float2 v7 = reinterpret_cast<const float2*>(q + 7)[0];
+          const float e[D] = {v5.x, v5.y, v5.z, v5.w, v6.x, v6.y, v6.z, v6.w, v7.x, v7.y};
+#pragma unroll
+          for (int o = 0; o < D; ++o) d[D + o] = neu ? e[o] : d[D + o];
+        }
 #pragma unroll
         for (int p = 0; p < 5; ++p) {
           const v2f a = (v2f){d[2 * p], d[2 * p + 1]} + dPt[p];
@@ -402,6 +567,38 @@ __global__ __launch_bounds__(TILE_THREADS) void k_jvp_lin(int n_tiles, int chunk
   PHASE();
   const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3], r4 = rp[4], r5 = rp[5];
   load10(tv + n * D, dx);
+  if constexpr (NEU) {
+    if (neu) {   // dS_fr holds dS_n
+      const float* TN = W + tnofs;
+      const unsigned hm = __float_as_uint(r0.w);
+      v2f dq[5], dy2[5];
+#pragma unroll
+      for (int p = 0; p < 5; ++p) dq[p] = dy2[p] = splat(0.f);
+      PHASE();
+      mv2<D>(TN + L::N_N1H, dx, dq);
+      PHASE();
+      mv2<D>(TN + L::N_GN, reinterpret_cast<const float*>(dS_fr), dq);
+#pragma unroll
+      for (int p = 0; p < 5; ++p)
+        dq[p] = (v2f){(hm >> (2 * p)) & 1u ? dq[p].x : 0.f, (hm >> (2 * p + 1)) & 1u ? dq[p].y : 0.f};
+      PHASE();
+      mv2<D>(TN + L::N_N2, reinterpret_cast<const float*>(dq), dy2);
+      const float* dyn = reinterpret_cast<const float*>(dy2);
+      const float yh[D] = {r3.z, r3.w, r4.x, r4.y, r4.z, r4.w, r5.x, r5.y, r5.z, r5.w};
+      float dm = 0.f, yd = 0.f;
+#pragma unroll
+      for (int o = 0; o < D; ++o) {
+        dm += dyn[o];
+        yd = fmaf(yh[o], dyn[o], yd);
+      }
+      dm *= (1.f / D);
+      yd *= (1.f / D);
+#pragma unroll
+      for (int o = 0; o < D; ++o) dy[o] = W[L::LN_G + o] * r0.z * (dyn[o] - dm - yh[o] * yd);
+      store10(out + n * D, dy);
+      return;
+    }
+  }
   const float* Wf = W + lofs + L::L_FOLD;
   const float* Wa = W + L::AL_W;
   const float* dsto = reinterpret_cast<const float*>(dS_to);
@@ -527,22 +724,65 @@ __device__ __forceinline__ void lin_node_back(const float* __restrict__ W, const
   }
 }
 
+// The same for a Neumann row (Neumann rows stored): the transpose of LN'( N2 (hm . (N1h v + G_n dS_n)) ).  c = [0 | c_neu], the
+// cotangent of dS_n in the Phi_from half (the row has no Phi_to / Phi_from sums); dx = N1h^T dq.
+template <int P>
+__device__ __forceinline__ void lin_node_back_neu(const float* __restrict__ W, const float* __restrict__ TN, const float* wv,
+                                                  const float* __restrict__ recp, float* c, float* dx) {
+  using L = WLayout<P>;
+  const float4* rp = reinterpret_cast<const float4*>(recp);
+  const float4 r0 = rp[0], r3 = rp[3], r4 = rp[4], r5 = rp[5];
+  const float yh[D] = {r3.z, r3.w, r4.x, r4.y, r4.z, r4.w, r5.x, r5.y, r5.z, r5.w};
+  const float rs = r0.z;
+  const unsigned hm = __float_as_uint(r0.w);
+  float a[D], ma = 0.f, my = 0.f;
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    a[o] = W[L::LN_G + o] * rs * wv[o];
+    ma += a[o];
+    my = fmaf(yh[o], a[o], my);
+  }
+  ma *= (1.f / D);
+  my *= (1.f / D);
+  float dyb[D], dqb[D];
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    dyb[o] = a[o] - ma - yh[o] * my;
+    dqb[o] = 0.f;
+  }
+  PHASE();
+  mvT<D>(TN + L::N_N2, dyb, dqb);
+#pragma unroll
+  for (int k = 0; k < D; ++k) dqb[k] = (hm >> k) & 1u ? dqb[k] : 0.f;
+#pragma unroll
+  for (int k = 0; k < 2 * D; ++k) c[k] = 0.f;
+  PHASE();
+  mvT<D>(TN + L::N_GN, dqb, c + D);
+  if (dx) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) dx[k] = 0.f;
+    PHASE();
+    mvT<D>(TN + L::N_N1H, dqb, dx);
+  }
+}
+
 // One launch per product.  Stage 1: [c_to | c_fr] of every tile and halo row -> 80-byte LDS rows (the own row by its lane, which
 // keeps its direct term; halo rows over all threads).  Stage 2, node u: own edges through the counts of its own mask bits (a node's
 // cotangent of dS is the same on all its slots), neighbour edges through the transposed slot dwords (tslot: the LDS row of the
 // neighbour n | n's masks of the pair's slot in n's ELL row): gathered from u's side, fixed order, no atomics.
 //   out[u] = dx[u] + W1i_to^T (cnt_to[u] . c_to[u]) + W1i_fr^T (cnt_fr[u] . c_fr[u])
 //          + W1j_to^T sum_n m_to(n; u -> n) . c_to[n] + W1j_fr^T sum_n m_fr(n; n -> u) . c_fr[n]
-template <int P>
-__global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk, const TileCtx C, const float* __restrict__ W,
-                                                          int lofs, int tofs, const uint32_t* __restrict__ slot,
-                                                          const uint32_t* __restrict__ tslot, const float* __restrict__ rec,
-                                                          const float* __restrict__ tw, float* __restrict__ out) {
+// One tile of the product (k_vjp_lin: dirichlet plans; k_vjp_lin_mixed: mixed plans with the Neumann rows stored).  NEU: a tile with a
+// Neumann row among its own and halo rows (a tile without Neumann nodes of its own can have one in its halo).  A Neumann row n has c[n] = [0 | c_neu[n]]; a slot of u whose partner is a
+// Neumann row (bit 30 of the transposed slot dword) adds its masked c_neu to a third sum, and
+//   out[u] += W1j_neu^T sum_{Neumann n -> u} m_neu(n's OUT slot of the pair) . c_neu[n];  a Neumann u's own side is W1i_neu^T (cnt . c_neu[u])
+template <int P, bool NEU>
+__device__ __forceinline__ void vjp_lin_tile(const int tile, float* __restrict__ lds, const TileCtx& C, const float* __restrict__ W,
+                                             int lofs, int tofs, const uint32_t* __restrict__ slot,
+                                             const uint32_t* __restrict__ tslot, const float* __restrict__ rec,
+                                             const float* __restrict__ tw, float* __restrict__ out, int tnofs) {
   using L = WLayout<P>;
   constexpr int RS = 20;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-  if (tile >= n_tiles) return;
   const int tid = threadIdx.x;
   const int tn = C.tile_nodes;
   const int32_t t0 = tn ? tile * tn : C.tile_ptr[tile];
@@ -559,7 +799,20 @@ __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk
     float c[2 * D];
 #pragma unroll
     for (int o = 0; o < 2 * D; ++o) c[o] = 0.f;
-    if (!(C.flags_p[node] & FLAG_DIRICHLET)) {   // a Dirichlet row is a copy of H_init: no cotangent flows through it
+    const uint8_t fl = C.flags_p[node];
+    if constexpr (NEU) {
+      // (one inlined copy of each node-local backward: a halo row's direct term is computed and dropped)
+      if (!(fl & FLAG_DIRICHLET)) {   // (Dirichlet wins, as in the tile kernels)
+        float wv[D], dn[D];
+        load10(tw + node * D, wv);
+        if (fl & FLAG_NEUMANN) lin_node_back_neu<P>(W, W + tnofs, wv, rec + node * LIN_REC, c, dn);
+        else lin_node_back<P>(W, T, lofs, wv, rec + node * LIN_REC, c, dn);
+        if (row < n_t) {
+#pragma unroll
+          for (int o = 0; o < D; ++o) dx[o] = dn[o];
+        }
+      }
+    } else if (!(fl & FLAG_DIRICHLET)) {   // a Dirichlet row is a copy of H_init: no cotangent flows through it
       float wv[D];
       load10(tw + node * D, wv);
       if (row < n_t) lin_node_back<P>(W, T, lofs, wv, rec + node * LIN_REC, c, dx);
@@ -581,9 +834,11 @@ __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk
   // own mask bits counted in 4-bit fields, one chunk at a time: nib[j] sums bits 10 + j + 4 i (i < 5) of the node's slot dwords
   const bool own = !(C.flags_p[n] & FLAG_DIRICHLET);   // (a Dirichlet row's own slot dwords are not written by the build)
   unsigned cnt_lo[5] = {0u, 0u, 0u, 0u, 0u}, cnt_hi[5] = {0u, 0u, 0u, 0u, 0u};   // two 16-bit counts per word: bits 10 .. 19 | 20 .. 29
-  v2f at[5], af[5];
+  v2f at[5], af[5], an[NEU ? 5 : 1];
 #pragma unroll
   for (int p = 0; p < 5; ++p) at[p] = af[p] = splat(0.f);
+#pragma unroll
+  for (int p = 0; p < (NEU ? 5 : 1); ++p) an[p] = splat(0.f);
   for (int r0 = 0; r0 < nslots; r0 += LIN_CHUNK) {
     uint32_t sw[LIN_CHUNK], xw[LIN_CHUNK];
 #pragma unroll
@@ -606,7 +861,13 @@ __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk
           const int m0 = __builtin_amdgcn_sbfe(w, 10 + 2 * p, 1), m1 = __builtin_amdgcn_sbfe(w, 11 + 2 * p, 1);
           const int m2 = __builtin_amdgcn_sbfe(w, 20 + 2 * p, 1), m3 = __builtin_amdgcn_sbfe(w, 21 + 2 * p, 1);
           at[p] += (v2f){__int_as_float(__float_as_int(d[2 * p]) & m0), __int_as_float(__float_as_int(d[2 * p + 1]) & m1)};
-          af[p] += (v2f){__int_as_float(__float_as_int(d[10 + 2 * p]) & m2), __int_as_float(__float_as_int(d[11 + 2 * p]) & m3)};
+          if constexpr (NEU) {   // partner is a Neumann row: its Phi_from field holds Phi_neumann's masks, its c row c_neu
+            const int nm = __builtin_amdgcn_sbfe(w, 30, 1);
+            af[p] += (v2f){__int_as_float(__float_as_int(d[10 + 2 * p]) & m2 & ~nm), __int_as_float(__float_as_int(d[11 + 2 * p]) & m3 & ~nm)};
+            an[p] += (v2f){__int_as_float(__float_as_int(d[10 + 2 * p]) & m2 & nm), __int_as_float(__float_as_int(d[11 + 2 * p]) & m3 & nm)};
+          } else {
+            af[p] += (v2f){__int_as_float(__float_as_int(d[10 + 2 * p]) & m2), __int_as_float(__float_as_int(d[11 + 2 * p]) & m3)};
+          }
         }
         const uint32_t s = sw[i];
 #pragma unroll
@@ -632,15 +893,54 @@ __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk
     gt[o] = (float)((cnt_lo[o >> 1] >> (16 * (o & 1))) & 0xFFFFu) * co[o];
     gf[o] = (float)((cnt_hi[o >> 1] >> (16 * (o & 1))) & 0xFFFFu) * co[D + o];
   }
-  PHASE();
-  mvT<D>(T + L::T_W1I_TO, gt, dx);
-  PHASE();
-  mvT<D>(T + L::T_W1I_FR, gf, dx);
+  if (NEU && (C.flags_p[n] & (FLAG_DIRICHLET | FLAG_NEUMANN)) == FLAG_NEUMANN) {   // (gt = 0: the row's Phi_to bits and c_to are 0)
+    PHASE();
+    mvT<D>(W + tnofs + L::N_W1I, gf, dx);
+  } else {
+    PHASE();
+    mvT<D>(T + L::T_W1I_TO, gt, dx);
+    PHASE();
+    mvT<D>(T + L::T_W1I_FR, gf, dx);
+  }
   PHASE();
   mvT<D>(T + L::T_W1J_TO, reinterpret_cast<const float*>(at), dx);
   PHASE();
   mvT<D>(T + L::T_W1J_FR, reinterpret_cast<const float*>(af), dx);
+  if constexpr (NEU) {
+    PHASE();
+    mvT<D>(W + tnofs + L::N_W1J, reinterpret_cast<const float*>(an), dx);
+  }
   store10(out + n * D, dx);
+}
+
+template <int P>
+__global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk, const TileCtx C, const float* __restrict__ W,
+                                                          int lofs, int tofs, const uint32_t* __restrict__ slot,
+                                                          const uint32_t* __restrict__ tslot, const float* __restrict__ rec,
+                                                          const float* __restrict__ tw, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (tile >= n_tiles) return;
+  vjp_lin_tile<P, false>(tile, lds, C, W, lofs, tofs, slot, tslot, rec, tw, out, 0);
+}
+
+// Mixed plans, Neumann rows stored: ONE launch over the handle's tile list (chunk * 8 entries; -1 = none).  An entry with LIN_VNEU set
+// is a tile with a Neumann row among its own and halo rows and runs the Neumann form, every other tile the plain form -- a
+// workgroup-uniform branch between the two inlined bodies.  The list puts the (few, longer-running) Neumann tiles on the first
+// workgroups of the grid, round-robin over the eight XCDs, so that they start first and the plain tiles fill in behind them: as a
+// launch of their own they took as long as a single tile takes (21 us for 80 tiles at 582k nodes) behind 43 us of plain tiles.
+#define LIN_VNEU 0x40000000
+template <int P>
+__global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin_mixed(int chunk, const int32_t* __restrict__ tile_list, const TileCtx C,
+                                                                const float* __restrict__ W, int lofs, int tofs, int tnofs,
+                                                                const uint32_t* __restrict__ slot, const uint32_t* __restrict__ tslot,
+                                                                const float* __restrict__ rec, const float* __restrict__ tw,
+                                                                float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int32_t e = tile_list[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];
+  if (e < 0) return;
+  if (e & LIN_VNEU) vjp_lin_tile<P, true>(e & (LIN_VNEU - 1), lds, C, W, lofs, tofs, slot, tslot, rec, tw, out, tnofs);
+  else vjp_lin_tile<P, false>(e, lds, C, W, lofs, tofs, slot, tslot, rec, tw, out, tnofs);
 }
 
 // Reverse slot map, once per handle, matched per edge DIRECTION (merge_slots in tiles.hip may pair a node's slots differently on the
@@ -660,6 +960,8 @@ __device__ __forceinline__ int32_t lin_tile_of(const int32_t* __restrict__ a, in
   }
   return lo;
 }
+// NEU: bit 30 of tslot[s] = the slot's neighbour is a Neumann row (kept by k_lin_tfill)
+template <bool NEU = false>
 __global__ __launch_bounds__(256) void k_lin_rev(int64_t n_slices, int n_tiles, const TileCtx C, int2* __restrict__ rev,
                                                  uint32_t* __restrict__ tslot, int32_t* __restrict__ bad) {
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -706,6 +1008,7 @@ __global__ __launch_bounds__(256) void k_lin_rev(int64_t n_slices, int n_tiles, 
         if (want_fr && found.y < 0 && (e2 & SLOT_OUT) && k_in-- == 0) found.y = (int32_t)idx2;
       }
       if ((want_to && found.x < 0) || (want_fr && found.y < 0)) atomicOr(bad, 1);
+      if (NEU && (C.flags_p[nb] & FLAG_NEUMANN)) li |= 1u << 30;
     }
     rev[idx] = found;
     tslot[idx] = li;
@@ -718,23 +1021,83 @@ __global__ __launch_bounds__(256) void k_lin_tfill(int64_t n, const int2* __rest
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int2 r = rev[i];
-  tslot[i] = (tslot[i] & 1023u) | (r.x >= 0 ? slot[r.x] & 0x000FFC00u : 0u) | (r.y >= 0 ? slot[r.y] & 0x3FF00000u : 0u);
+  tslot[i] = (tslot[i] & 0x400003FFu) | (r.x >= 0 ? slot[r.x] & 0x000FFC00u : 0u) | (r.y >= 0 ? slot[r.y] & 0x3FF00000u : 0u);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
 int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
                              const float* v, float* out, int groups, hipStream_t st);
 
-extern "C" int psignn_lin_create(psignn_lin_t** out, const psignn_plan_t* p) {
+// flag[tile] = 1: a Neumann row among the tile's own and halo rows (the transposed product's tile groups, once per handle)
+__global__ __launch_bounds__(64) void k_lin_vgroup(const TileCtx C, int32_t* __restrict__ flag) {
+  const int tile = blockIdx.x;
+  const int32_t t0 = C.tile_ptr[tile];
+  const int n_t = C.tile_ptr[tile + 1] - t0, n_h = C.halo_cnt[tile];
+  const int32_t* hl = C.halo + (int64_t)tile * HALO_CAP;
+  bool any = false;
+  for (int row = threadIdx.x; row < n_t + n_h; row += 64) {
+    const uint8_t fl = C.flags_p[row < n_t ? t0 + row : hl[row - n_t]];
+    any |= (fl & (FLAG_DIRICHLET | FLAG_NEUMANN)) == FLAG_NEUMANN;
+  }
+  if (__ballot(any) != 0ull && threadIdx.x == 0) flag[tile] = 1;
+}
+
+extern "C" int psignn_lin_create(psignn_lin_t** out, const psignn_plan_t* p) { return psignn_lin_create_opts(out, p, 0); }
+
+extern "C" int psignn_lin_neumann_stored(const psignn_lin_t* s) { return s ? s->neu : 0; }
+
+extern "C" int psignn_lin_create_opts(psignn_lin_t** out, const psignn_plan_t* p, int neumann_stored) {
   ARG_CHECK(out && p, "NULL argument");
+  ARG_CHECK(neumann_stored == 0 || neumann_stored == 1, "neumann_stored is 0 or 1");
   ARG_CHECK(p->tiled, "linearised JVP: tiled plans (other plans use psignn_f_jvp)");
   ARG_CHECK(p->max_rows <= 1024, "tile + halo rows exceed the 10-bit row field of the stored slots");
   psignn_lin* s = new psignn_lin();
   s->plan = p;
+  s->neu = p->mixed && neumann_stored;
   const size_t b_slot = (size_t)(p->ell_rows + 1) * 64 * 4, b_rec = (size_t)p->N * LIN_REC * 4;
-  const size_t b_state = p->mixed ? (size_t)p->N * (D + 3 + 2) * 4 : 0;
+  const size_t b_state = s->neu ? (size_t)cdiv(p->n_tiles, 8) * 8 * 4 : p->mixed ? (size_t)p->N * (D + 3 + 2) * 4 : 0;
   bool ok = hipMalloc((void**)&s->slot, b_slot) == hipSuccess && hipMalloc((void**)&s->rec, b_rec) == hipSuccess;
-  if (ok && p->mixed)
+  if (ok && s->neu) {
+    // tile list of the transposed product (k_vjp_lin_mixed): per-tile flags on the device, arranged on the host, once per handle
+    const size_t nt = (size_t)p->n_tiles, chunk = (size_t)cdiv((int64_t)nt, 8), nl = chunk * 8;
+    ok = hipMalloc((void**)&s->vlist, (nl > nt ? nl : nt) * 4 + 4) == hipSuccess;
+    if (ok && nt > 0) {
+      int32_t* fl = (int32_t*)malloc(nt * 4);
+      int32_t* ord = (int32_t*)malloc(nl * 4);
+      hipError_t e = fl && ord ? hipMemset(s->vlist, 0, nt * 4) : hipErrorOutOfMemory;
+      if (e == hipSuccess) {
+        k_lin_vgroup<<<(unsigned)nt, 64>>>(p->h_ctx, s->vlist);
+        e = hipMemcpy(fl, s->vlist, nt * 4, hipMemcpyDeviceToHost);
+      }
+      if (e == hipSuccess) {
+        // workgroup b of the grid reads entry (b & 7) * chunk + (b >> 3): the j-th Neumann tile goes where workgroup j reads, the
+        // plain tiles fill the other entries in ascending order (neighbouring tiles stay on one XCD, as in the other tile kernels)
+        for (size_t i = 0; i < nl; ++i) ord[i] = -1;
+        size_t j = 0;
+        for (size_t t = 0; t < nt; ++t)
+          if (fl[t]) {
+            ord[(j & 7) * chunk + (j >> 3)] = (int32_t)t | LIN_VNEU;
+            ++j;
+          }
+        s->n_vplain = (int)(nt - j);
+        size_t pos = 0;
+        for (size_t t = 0; t < nt; ++t)
+          if (!fl[t]) {
+            while (ord[pos] != -1) ++pos;
+            ord[pos] = (int32_t)t;
+          }
+        e = hipMemcpy(s->vlist, ord, nl * 4, hipMemcpyHostToDevice);
+      }
+      free(fl);
+      free(ord);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        psignn_lin_destroy(s);
+        psignn_set_error("psignn_lin_create_opts: tile list of the transposed product -> %s", hipGetErrorString(e));
+        return PSIGNN_EHIP;
+      }
+    }
+  } else if (ok && p->mixed)
     ok = hipMalloc((void**)&s->h, (size_t)p->N * D * 4) == hipSuccess && hipMalloc((void**)&s->prb, (size_t)p->N * 3 * 4) == hipSuccess &&
          hipMalloc((void**)&s->nrm, (size_t)p->N * 2 * 4) == hipSuccess;
   if (!ok) {
@@ -750,7 +1113,7 @@ extern "C" int psignn_lin_create(psignn_lin_t** out, const psignn_plan_t* p) {
 
 extern "C" void psignn_lin_destroy(psignn_lin_t* s) {
   if (!s) return;
-  for (void* q : {(void*)s->slot, (void*)s->rec, (void*)s->h, (void*)s->prb, (void*)s->nrm, (void*)s->rev, (void*)s->tslot})
+  for (void* q : {(void*)s->slot, (void*)s->rec, (void*)s->h, (void*)s->prb, (void*)s->nrm, (void*)s->rev, (void*)s->tslot, (void*)s->vlist})
     if (q) (void)hipFree(q);
   delete s;
 }
@@ -769,13 +1132,26 @@ extern "C" int psignn_lin_build(psignn_lin_t* s, const float* W, int nl, const f
   const size_t lds = (size_t)p->max_rows * 20 * 4;
   if (p->mixed) {
     using L = WLayout<3>;
-    const int na = (int)p->n_tiles_plain;
-    HIP_TRY(hipMemcpyAsync(s->h, h, (size_t)p->N * D * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->prb, prb, (size_t)p->N * 3 * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->nrm, nrm, (size_t)p->N * 2 * 4, hipMemcpyDeviceToDevice, st));
+    const int na = (int)p->n_tiles_plain, nb = (int)(p->n_tiles - p->n_tiles_plain);
+    if (s->neu) {
+      if (nb > 0) {   // the tiles holding Neumann nodes: 144-byte LDS rows, Neumann rows stored
+        const int chunk = (int)cdiv(nb, 8);
+        // the group's share of the plan by tiles (node counts per group are not kept on the host), normals included (8 N)
+        PROF_BYTES(((70 * p->N + 20 * p->Ep) + (int64_t)p->N * LIN_REC * 4 + (int64_t)p->ell_rows * 64 * 4) * nb / p->n_tiles);
+        LAUNCH("k_lin_build_neu", st, (k_lin_build<3, true><<<(unsigned)(chunk * 8), TILE_THREADS, (size_t)p->max_rows * LIN_RS_NEU * 4, st>>>(
+            nb, chunk, p->tile_order + na, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), h, prb, s->slot, s->rec,
+            L::tp_neu(nl), nrm)));
+      }
+    } else {
+      HIP_TRY(hipMemcpyAsync(s->h, h, (size_t)p->N * D * 4, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(s->prb, prb, (size_t)p->N * 3 * 4, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(s->nrm, nrm, (size_t)p->N * 2 * 4, hipMemcpyDeviceToDevice, st));
+    }
     if (na > 0) {
       const int chunk = (int)cdiv(na, 8);
-      PROF_BYTES((62 * p->N + 20 * p->Ep) + (int64_t)p->N * LIN_REC * 4 + (int64_t)p->ell_rows * 64 * 4);
+      // (Neumann rows stored: the plain group's share by tiles; otherwise the launch is the handle's only build launch)
+      PROF_BYTES(((62 * p->N + 20 * p->Ep) + (int64_t)p->N * LIN_REC * 4 + (int64_t)p->ell_rows * 64 * 4) * (s->neu ? na : p->n_tiles) /
+                 p->n_tiles);
       LAUNCH("k_lin_build", st, (k_lin_build<3><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
           na, chunk, p->tile_order, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), h, prb, s->slot, s->rec)));
     }
@@ -807,12 +1183,21 @@ extern "C" int psignn_lin_jvp(const psignn_lin_t* s, const float* W, int nl, con
     const int na = (int)p->n_tiles_plain;
     if (na > 0) {
       const int chunk = (int)cdiv(na, 8);
-      PROF_BYTES((int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 4);
+      PROF_BYTES(((int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 4) * (s->neu ? na : p->n_tiles) / p->n_tiles);
       LAUNCH("k_jvp_lin", st, (k_jvp_lin<3><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
           na, chunk, p->tile_order, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), s->slot, s->rec, v, out)));
     }
-    int rc = psignn_f_tile_jvp_groups(p, W, nl, s->h, s->prb, s->nrm, v, out, 2, st);   // the tiles holding Neumann nodes
-    if (rc) return rc;
+    const int nb = (int)(p->n_tiles - p->n_tiles_plain);
+    if (!s->neu) {
+      int rc = psignn_f_tile_jvp_groups(p, W, nl, s->h, s->prb, s->nrm, v, out, 2, st);   // the tiles holding Neumann nodes
+      if (rc) return rc;
+    } else if (nb > 0) {   // the same stored operator on the tiles holding Neumann nodes (144-byte LDS rows)
+      const int chunk = (int)cdiv(nb, 8);
+      PROF_BYTES(((int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 4) * nb / p->n_tiles);   // share by tiles
+      LAUNCH("k_jvp_lin_neu", st, (k_jvp_lin<3, true><<<(unsigned)(chunk * 8), TILE_THREADS, (size_t)p->max_rows * LIN_RS_NEU * 4, st>>>(
+          nb, chunk, p->tile_order + na, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), s->slot, s->rec, v, out,
+          L::tp_neu(nl))));
+    }
   } else {
     using L = WLayout<2>;
     const int chunk = (int)cdiv(p->n_tiles, 8);
@@ -827,7 +1212,8 @@ extern "C" int psignn_lin_jvp(const psignn_lin_t* s, const float* W, int nl, con
 
 // w, out in PLAN order: out = J_f(h)^T w for the h of the last psignn_lin_build.  Dirichlet plans: k_vjp_lin (one launch; on the first
 // call after a build also k_lin_tfill, on the first call of the handle k_lin_rev and the two transposed arrays).  Mixed plans: the
-// tiled VJP (psignn_f_tile_vjp, work = the plan workspace) at the state kept by the build -- no stored form of the Neumann rows yet.
+// tiled VJP (psignn_f_tile_vjp, work = the plan workspace) at the state kept by the build; with the Neumann rows stored
+// (psignn_lin_create_opts) one k_vjp_lin_mixed launch over the handle's tile list, work ignored.
 int psignn_f_tile_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* w,
                       float* out, float* work, hipStream_t st);
 
@@ -838,7 +1224,7 @@ extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, con
   const psignn_plan* p = s->plan;
   ARG_CHECK(p->mixed ? nl >= 1 : nl == 1, "linearised VJP: single-layer blocks (mixed plans: the last layer)");
   hipStream_t st = (hipStream_t)stream;
-  if (p->mixed) {
+  if (p->mixed && !s->neu) {
     ARG_CHECK(work, "mixed plan: the transposed product needs the plan workspace");
     return psignn_f_tile_vjp(p, W, nl, s->h, s->prb, s->nrm, w, out, work, st);
   }
@@ -859,9 +1245,14 @@ extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, con
     HIP_TRY(hipMemsetAsync(s->rev, 0xFF, nb * 8, st));
     HIP_TRY(hipMemsetAsync(bad, 0, 4, st));
     HIP_TRY(hipMemsetAsync(s->tslot, 0, nb * 4, st));
-    if (p->n_slices > 0)
-      LAUNCH("k_lin_rev", st, (k_lin_rev<<<(unsigned)cdiv(p->n_slices * 64, 256), 256, 0, st>>>(
-          p->n_slices, (int)p->n_tiles, p->h_ctx, s->rev, s->tslot, bad)));
+    if (p->n_slices > 0) {
+      if (s->neu)
+        LAUNCH("k_lin_rev", st, (k_lin_rev<true><<<(unsigned)cdiv(p->n_slices * 64, 256), 256, 0, st>>>(
+            p->n_slices, (int)p->n_tiles, p->h_ctx, s->rev, s->tslot, bad)));
+      else
+        LAUNCH("k_lin_rev", st, (k_lin_rev<false><<<(unsigned)cdiv(p->n_slices * 64, 256), 256, 0, st>>>(
+            p->n_slices, (int)p->n_tiles, p->h_ctx, s->rev, s->tslot, bad)));
+    }
     int32_t h_bad = 0;   // (once per handle)
     HIP_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -881,9 +1272,22 @@ extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, con
       LAUNCH("k_lin_tfill", st, (k_lin_tfill<<<(unsigned)cdiv(n_sl, 256), 256, 0, st>>>(n_sl, s->rev, s->slot, s->tslot)));
     s->tfilled = 1;
   }
+  const size_t lds = (size_t)p->max_rows * 20 * 4;
+  if (s->neu) {   // mixed plan, Neumann rows stored: one launch, the Neumann form on the tiles with a Neumann row among tile + halo
+    using L = WLayout<3>;
+    const int chunk = (int)cdiv(p->n_tiles, 8);
+    if (chunk > 0) {
+      // w, out (40 N each), flags, node records, slot and transposed slot dwords
+      PROF_BYTES((int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 8);
+      LAUNCH("k_vjp_lin_mixed", st, (k_vjp_lin_mixed<3><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
+          chunk, s->vlist, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), L::tp_neu(nl), s->slot, s->tslot, s->rec, w,
+          out)));
+    }
+    HIP_TRY(hipGetLastError());
+    return PSIGNN_OK;
+  }
   using L = WLayout<2>;
   const int chunk = (int)cdiv(p->n_tiles, 8);
-  const size_t lds = (size_t)p->max_rows * 20 * 4;
   // w (tile + halo rows), out (40 N each), flags, node records (tile + halo rows), slot and transposed slot dwords
   PROF_BYTES((int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 8);
   LAUNCH("k_vjp_lin", st, (k_vjp_lin<2><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(

@@ -284,6 +284,8 @@ class FixedPointMap:
             raise nat.NativeError(f"shape mismatch: prb_data {tuple(self.prb.shape)}, h_initial {tuple(self.h0.shape)}")
         self._p = None  # plan-order copies of h0 / prb / normals, made on first use
 
+    lin_neumann = "direct"   # what ``linearize_p`` gives a new Linearization (the model sets its ``lin_neumann`` config value)
+
     # -- plan-order fast path (no permutation passes per call) -------------------------------------
     def to_plan(self, H):
         return self.plan.permute(H, True)
@@ -396,15 +398,17 @@ class FixedPointMap:
         """True when ``linearize_p`` applies: tiled plan; dirichlet family: single-layer block (csrc/fgnn_tile_lin.hip)."""
         return bool(self.plan.tiled) and (bool(self.plan.mixed) or self.weights.n_layers == 1)
 
-    def linearize_p(self, Hp, lin=None):
+    def linearize_p(self, Hp, lin=None, neumann=None):
         """Linearisation of f at ``Hp`` (plan order) for solvers that apply J_f(Hp) to many vectors: one pass stores the relu
         masks and per-node gate / update / LayerNorm quantities, ``lin.jvp_p(Vp)`` then applies the Jacobian as a linear
         operator (about half the cost of ``jvp_p``, same product up to fp32 summation order).  ``lin``: a Linearization of this
-        map to rebuild at the new state (keeps its device buffers)."""
+        map to rebuild at the new state (keeps its device buffers).  ``neumann`` (a new handle only): ``"direct"`` or
+        ``"stored"`` as in ``Linearization``; None -> the map's ``lin_neumann`` (``"direct"`` unless set)."""
+        neumann = check_lin_neumann(self.lin_neumann if neumann is None else neumann)
         if self._p is None:
             self.fp(Hp)
         if lin is None:
-            lin = Linearization(self)
+            lin = Linearization(self, neumann=neumann)
         lin.build(Hp)
         return lin
 
@@ -877,18 +881,38 @@ def residual(plan: MeshPlan, u, y):
 TRACE_BUDGET_BYTES = 8 << 30  # keep every iterate only while (thr+2)*N*d*4 stays under this
 
 
-class Linearization:
-    """Stored linearisation of a FixedPointMap at one state (psignn_lin_* in include/psignn_hip.h)."""
+LIN_NEUMANN = ("direct", "stored")
 
-    def __init__(self, fmap):
+
+def check_lin_neumann(value):
+    """``"direct"`` / ``"stored"`` as given; ValueError for anything else (a host check: nothing is allocated)."""
+    if not isinstance(value, str) or value not in LIN_NEUMANN:
+        raise ValueError(f"lin_neumann / neumann must be one of {LIN_NEUMANN}, got {value!r}")
+    return value
+
+
+class Linearization:
+    """Stored linearisation of a FixedPointMap at one state (psignn_lin_* in include/psignn_hip.h).
+
+    ``neumann`` (mixed family; ignored for dirichlet plans): ``"direct"`` -- the tiles holding Neumann nodes run the direct
+    JVP kernel and ``vjp_p`` the tiled VJP, both at a copy of the state kept by the build; ``"stored"`` -- the Neumann rows are
+    stored like every other row: ``jvp_p`` is one linear operator on all tiles and ``vjp_p`` its exact transpose, no state
+    copy.  ``neumann_stored`` tells which form the handle holds."""
+
+    def __init__(self, fmap, neumann="direct"):
+        neumann = check_lin_neumann(neumann)
         if not fmap.can_linearize():
             raise nat.NativeError("linearize_p: tiled plans (dirichlet family: single-layer blocks); use jvp_p otherwise")
         self.fmap = fmap
         h = C.c_void_p()
         with torch.cuda.device(fmap.weights.flat.device):
-            nat.check(nat.lib().psignn_lin_create(C.byref(h), fmap.plan.handle), "psignn_lin_create")
+            if neumann == "stored":
+                nat.check(nat.lib().psignn_lin_create_opts(C.byref(h), fmap.plan.handle, 1), "psignn_lin_create_opts")
+            else:
+                nat.check(nat.lib().psignn_lin_create(C.byref(h), fmap.plan.handle), "psignn_lin_create")
         self.handle = h
         self.bytes = int(nat.lib().psignn_lin_bytes(h))
+        self.neumann_stored = bool(nat.lib().psignn_lin_neumann_stored(h))
 
     def build(self, Hp):
         fm = self.fmap
@@ -924,7 +948,8 @@ class Linearization:
             raise nat.NativeError("vjp_p: out must be a contiguous float32 tensor of the state's size")
         with torch.cuda.device(Wc.device):
             nat.check(nat.lib().psignn_lin_vjp(self.handle, nat.ptr(fm.weights.flat), fm.weights.n_layers, nat.ptr(Wc),
-                                               nat.ptr(out), nat.ptr(fm.plan.workspace() if fm.plan.mixed else None),
+                                               nat.ptr(out),
+                                               nat.ptr(fm.plan.workspace() if fm.plan.mixed and not self.neumann_stored else None),
                                                nat.stream_ptr(Wc.device)),
                       "psignn_lin_vjp")
         return out

@@ -10,8 +10,11 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
   ``"bc"`` = ``"dirichlet"`` | ``"mixed"`` selects the family (the reference uses two copies of the file).  An optional
   key ``"bw_linearize"`` (default False): the implicit backward, the power method and the Jacobian estimate linearise f
   once at H* and apply the transposed stored linearisation (``engine.Linearization.vjp_p``) where the plan allows it.  On the
-  mixed family it gains nothing yet: its transposed product is the tiled VJP at the state the build kept, so the key only adds one
-  build per call there.  An optional key ``"broyden_history_dtype"`` (default ``torch.float32``; ``torch.bfloat16`` allowed): the
+  mixed family it gains nothing by itself: its transposed product is the tiled VJP at the state the build kept, so the key only adds
+  one build per call there -- unless the optional key ``"lin_neumann"`` is ``"stored"`` (default ``"direct"``; ignored for the
+  dirichlet family): every Linearization the model creates (implicit backward, power method, Jacobian estimate, the Newton-Krylov
+  route of ``utilities.solver``) then stores the Neumann rows too, and its products are the stored operator and its exact transpose
+  on every tile (``engine.Linearization(fmap, neumann="stored")``).  An optional key ``"broyden_history_dtype"`` (default ``torch.float32``; ``torch.bfloat16`` allowed): the
   element type of the stored Broyden pairs of the forward and the adjoint solve (``utilities.solver.broyden(...,
   history_dtype=...)``); it applies when the configured solver is ``utilities.solver.broyden`` and has no effect with any other.
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
@@ -135,7 +138,11 @@ class Function(nn.Module):
         """The map H -> f(H, h_initial, batch) as a device object the solvers understand."""
         plan = engine.plan_for(batch)
         nrm = getattr(batch, "unit_normal_vector", None) if self.mixed else None
-        return engine.FixedPointMap(plan, self.packed(h_initial.device), h_initial, batch.prb_data, nrm)
+        fmap = engine.FixedPointMap(plan, self.packed(h_initial.device), h_initial, batch.prb_data, nrm)
+        fmap.lin_neumann = self.lin_neumann
+        return fmap
+
+    lin_neumann = "direct"   # the model's ``lin_neumann`` config value: what the maps bound here give a new Linearization
 
     def forward(self, h, h_initial, batch):
         return self.bind(h_initial, batch)(h)
@@ -277,10 +284,11 @@ class DeepEquilibrium(nn.Module):
         if not fmap.can_linearize():
             return None
         lin = getattr(self, "_bw_lin", None)
-        if lin is None or lin.fmap.plan is not fmap.plan:
+        want = fmap.plan.mixed and fmap.lin_neumann == "stored"
+        if lin is None or lin.fmap.plan is not fmap.plan or lin.neumann_stored != want:
             if lin is not None:
                 lin.close()
-            lin = self._bw_lin = engine.Linearization(fmap)
+            lin = self._bw_lin = engine.Linearization(fmap, neumann=fmap.lin_neumann)
         lin.fmap = fmap   # this call's weights and boundary data
         return fmap.linearize_p(fmap.to_plan(H_star), lin)
 
@@ -382,6 +390,8 @@ class _Base(nn.Module):
         self.config_deq = {k: self.config[k] for k in ("solver", "fw_tol", "fw_thres", "bw_tol", "bw_thres", "path_logs")}
         if "bw_linearize" in self.config:   # optional, like "bc": the transposed stored linearisation in the backward routes
             self.config_deq["bw_linearize"] = bool(self.config["bw_linearize"])
+        if "lin_neumann" in self.config:   # optional: the stored linearisation keeps the mixed family's Neumann rows too
+            self.config_deq["lin_neumann"] = engine.check_lin_neumann(self.config["lin_neumann"])   # (ValueError otherwise)
         if "broyden_history_dtype" in self.config:   # optional: bf16 storage of the Broyden pairs (utilities.solver.broyden only)
             engine.history_code(self.config["broyden_history_dtype"])   # (ValueError for any other dtype)
             self.config_deq["broyden_history_dtype"] = self.config["broyden_history_dtype"]
@@ -389,6 +399,7 @@ class _Base(nn.Module):
             function=Function(n_layers=self.config["n_layers"], latent_dim=d, edge_features_dim=3,
                               second_member_dim=3 if self.mixed else 2, activation=nn.ReLU(), mixed=self.mixed),
             config_deq=self.config_deq)
+        self.deqdss.f.lin_neumann = self.config_deq.get("lin_neumann", "direct")
         self.mse_loss = nn.MSELoss()
 
     # -- helpers -------------------------------------------------------------------------------
