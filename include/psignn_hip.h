@@ -254,6 +254,18 @@ int psignn_f_vjp_backward(const psignn_plan_t* plan, const float* d_weights, int
                           const float* d_prb, const float* d_normals, const float* d_v, const float* d_gbar, float* d_grad,
                           float* d_grad_h, float* d_work, void* stream);
 
+/* The same gradient on the tile structures, every node tensor (d_h, d_prb, d_v, d_gbar, d_grad_h) in PLAN order
+ * (psignn_plan_permute) -- the double backward loss.backward() runs through jac_loss_estimate,
+ * dirichlet/psignn/model.py:416-435, training_class.py:156-159 -- as two tile kernels and the record reduction.
+ * psignn_f_vjp_backward_tiled_ok: 1 where this form applies (tiled plan of the dirichlet family, n_layers == 1), else 0
+ * (also for a NULL plan); where it is 0, psignn_f_vjp_backward_p is an argument error and launches nothing.  d_grad as above;
+ * d_work: psignn_f_vjp_backward_p_workspace_floats(plan) floats. */
+int psignn_f_vjp_backward_tiled_ok(const psignn_plan_t* plan, int n_layers);
+int64_t psignn_f_vjp_backward_p_workspace_floats(const psignn_plan_t* plan);
+int psignn_f_vjp_backward_p(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h,
+                            const float* d_prb, const float* d_v, const float* d_gbar, float* d_grad, float* d_grad_h,
+                            float* d_work, void* stream);
+
 /* Backward of psignn_mlp2 and of psignn_residual: what autograd runs for the autoencoder and residual terms of
  * the training loss (dirichlet/psignn/model.py:58-99).  d_gflat = gradients of [W1 | b1 | W2 | b2];
  * d_gx (n, din) may be NULL.  psignn_residual_t: out = A^T r with the caller's a_ij (E floats, edge_index order). */

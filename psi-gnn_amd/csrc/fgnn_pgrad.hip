@@ -481,6 +481,46 @@ extern "C" int psignn_f_vjp_backward(const psignn_plan_t* p, const float* W, int
   return PSIGNN_OK;
 }
 
+// ---- the same product on the tile structures, plan order (kernels in fgnn_tile_jr.hip): tiled plans of the dirichlet family,
+// single-layer block
+int psignn_jr_tiled_ok(const psignn_plan* p, int nl);
+int psignn_jr_tile_records(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* v,
+                           const float* gbar, float* out_h, float* B, float* rec, hipStream_t st);
+
+extern "C" int psignn_f_vjp_backward_tiled_ok(const psignn_plan_t* p, int nl) { return psignn_jr_tiled_ok(p, nl); }
+
+extern "C" int64_t psignn_f_vjp_backward_p_workspace_floats(const psignn_plan_t* p) {
+  if (!p) return 0;
+  int npw;
+  const int nblk = pgrad_blocks(2 * p->N, &npw);
+  // B rows (N * 60) + two records per node + partial tiles
+  return p->N * (6 * D + 2 * TabF::NG * 16) + (int64_t)nblk * TabF::NT * 256;
+}
+
+// h, prb, v, gbar and d_grad_h in PLAN order; d_grad as psignn_f_vjp_backward's.  Two tile kernels and the reduction of the
+// 2 N records: four launches.
+extern "C" int psignn_f_vjp_backward_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
+                                       const float* v, const float* gbar, float* d_grad, float* d_grad_h, float* work,
+                                       void* stream) {
+  ARG_CHECK(p && W && h && prb && v && gbar && d_grad && d_grad_h && work, "NULL argument");
+  ARG_CHECK(psignn_jr_tiled_ok(p, nl),
+            "plan-order backward of the VJP: tiled plans of the dirichlet family, single-layer block (psignn_f_vjp_backward otherwise)");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t N = p->N;
+  float* B = work;
+  float* rec = B + N * 6 * D;
+  float* part = rec + 2 * N * TabF::NG * 16;
+  int npw;
+  const int nblk = pgrad_blocks(2 * N, &npw);
+  int rc = psignn_jr_tile_records(p, W, h, prb, v, gbar, d_grad_h, B, rec, st);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<2>::base_total(nl, false) * 4, st));
+  LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabF><<<nblk, 256, 0, st>>>(2 * N, npw, rec, part)));
+  LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabF::NT * 8, 256, 0, st>>>(nblk, TabF::NT, part, d_grad, MapF())));
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
 // ---- DS-GPS: backward of one recurrent update (kernels in gather_backward.hip)
 struct TabG {  // groups: see gather_backward.hip
   static constexpr int NG = 20, NT = 19;

@@ -232,6 +232,10 @@ class MeshPlan:
     def vjp_backward_workspace(self, n_layers=1):
         return self._grown("_jwork", nat.lib().psignn_f_vjp_backward_workspace_floats, n_layers)
 
+    def vjp_backward_p_workspace(self):
+        """Scratch of the plan-order (tile) backward of the VJP; shares ``vjp_backward_workspace()``'s buffer."""
+        return self._grown("_jwork", nat.lib().psignn_f_vjp_backward_p_workspace_floats, 1)
+
     def permute(self, t, to_plan=True):
         """Rows of an (N, cols) float tensor between the caller's numbering and plan order."""
         tc = _f32c(t)
@@ -285,6 +289,7 @@ class FixedPointMap:
         self._p = None  # plan-order copies of h0 / prb / normals, made on first use
 
     lin_neumann = "direct"   # what ``linearize_p`` gives a new Linearization (the model sets its ``lin_neumann`` config value)
+    jac_backward = "gather"  # the route the Jacobian regulariser's backward takes (the model sets its ``jac_backward`` config value)
 
     # -- plan-order fast path (no permutation passes per call) -------------------------------------
     def to_plan(self, H):
@@ -483,10 +488,39 @@ class FixedPointMap:
                                               nat.stream_ptr(Hc.device)), "psignn_f_param_vjp_ex")
         return unpack_param_grads(grad, self.weights.n_layers, self.weights.mixed), out, g_init
 
-    def vjp_backward(self, H, V, Gbar):
+    def can_tile_vjp_backward(self):
+        """True when ``vjp_backward_p`` applies: tiled plan of the dirichlet family, single-layer block (csrc/fgnn_tile_jr.hip)."""
+        return bool(nat.lib().psignn_f_vjp_backward_tiled_ok(self.plan.handle, int(self.weights.n_layers)))
+
+    def vjp_backward_p(self, Hp, Vp, Gp):
+        """``vjp_backward`` on the tile kernels with Hp, Vp, Gp and the returned d / dH in plan order:
+        (flat parameter gradient, d / dH).  ``unpack_param_grads`` names the flat gradient.  Where
+        ``can_tile_vjp_backward()`` is false this raises ``NativeError`` and launches nothing."""
+        if not self.can_tile_vjp_backward():
+            raise nat.NativeError("vjp_backward_p: the tile form needs a tiled plan of the dirichlet family and a single-layer "
+                                  "block (vjp_backward takes every plan)")
+        if self._p is None:
+            self.fp(Hp)
+        _, prbp, _ = self._p
+        Hc, Vc, Gc = _f32c(Hp), _f32c(Vp), _f32c(Gp)
+        l = nat.lib()
+        grad = torch.empty(int(l.psignn_param_grad_size(0, self.weights.n_layers)), dtype=torch.float32, device=Hc.device)
+        out = torch.empty_like(Hc)
+        with torch.cuda.device(Hc.device):
+            nat.check(l.psignn_f_vjp_backward_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                                nat.ptr(Hc), nat.ptr(prbp), nat.ptr(Vc), nat.ptr(Gc), nat.ptr(grad), nat.ptr(out),
+                                                nat.ptr(self.plan.vjp_backward_p_workspace()), nat.stream_ptr(Hc.device)),
+                      "psignn_f_vjp_backward_p")
+        return grad, out
+
+    def vjp_backward(self, H, V, Gbar, tiled=False):
         """Gradient of  Gbar . (J_f(H)^T V)  with Gbar held constant: ({name: grad}, d / dH) -- what autograd's double
         backward computes for ``autograd.grad(f(H), H, V, create_graph=True)`` (jac_loss_estimate,
-        dirichlet/psignn/model.py:416-435).  Both families, any depth, caller's numbering."""
+        dirichlet/psignn/model.py:416-435).  Both families, any depth, caller's numbering.  ``tiled=True``: the tile
+        kernels (permute in, ``vjp_backward_p``, permute out); ``NativeError`` where ``can_tile_vjp_backward()`` is false."""
+        if tiled:
+            flat, out_p = self.vjp_backward_p(self.to_plan(H), self.to_plan(V), self.to_plan(Gbar))
+            return unpack_param_grads(flat, self.weights.n_layers, self.weights.mixed), self.from_plan(out_p)
         Hc, Vc, Gc = _f32c(H), _f32c(V), _f32c(Gbar)
         l = nat.lib()
         grad = torch.empty(int(l.psignn_param_grad_size(int(self.weights.mixed), self.weights.n_layers)),
@@ -882,6 +916,16 @@ TRACE_BUDGET_BYTES = 8 << 30  # keep every iterate only while (thr+2)*N*d*4 stay
 
 
 LIN_NEUMANN = ("direct", "stored")
+
+
+JAC_BACKWARD = ("gather", "tiled")
+
+
+def check_jac_backward(value):
+    """``"gather"`` / ``"tiled"`` as given; ValueError for anything else (a host check: nothing is allocated)."""
+    if not isinstance(value, str) or value not in JAC_BACKWARD:
+        raise ValueError(f"jac_backward must be one of {JAC_BACKWARD}, got {value!r}")
+    return value
 
 
 def check_lin_neumann(value):

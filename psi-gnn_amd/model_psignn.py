@@ -17,6 +17,9 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
   on every tile (``engine.Linearization(fmap, neumann="stored")``).  An optional key ``"broyden_history_dtype"`` (default ``torch.float32``; ``torch.bfloat16`` allowed): the
   element type of the stored Broyden pairs of the forward and the adjoint solve (``utilities.solver.broyden(...,
   history_dtype=...)``); it applies when the configured solver is ``utilities.solver.broyden`` and has no effect with any other.
+  An optional key ``"jac_backward"`` = ``"gather"`` (default) | ``"tiled"``: the backward of the Jacobian regulariser
+  (``_JacLossFn``) on the tile kernels (``FixedPointMap.vjp_backward(..., tiled=True)``) where the map has that form -- tiled plan,
+  dirichlet family, single-layer block -- and on the gather kernels everywhere else; any other value raises ``ValueError``.
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
   and shapes are identical.
 * ``batch`` is any object with the PyG ``Data`` attributes (see ``data/meshdata.py``), already on the GPU.
@@ -140,9 +143,11 @@ class Function(nn.Module):
         nrm = getattr(batch, "unit_normal_vector", None) if self.mixed else None
         fmap = engine.FixedPointMap(plan, self.packed(h_initial.device), h_initial, batch.prb_data, nrm)
         fmap.lin_neumann = self.lin_neumann
+        fmap.jac_backward = self.jac_backward
         return fmap
 
     lin_neumann = "direct"   # the model's ``lin_neumann`` config value: what the maps bound here give a new Linearization
+    jac_backward = "gather"  # the model's ``jac_backward`` config value: the route ``_JacLossFn.backward`` takes on these maps
 
     def forward(self, h, h_initial, batch):
         return self.bind(h_initial, batch)(h)
@@ -195,7 +200,8 @@ class _DEQFn(torch.autograd.Function):
 class _JacLossFn(torch.autograd.Function):
     """jac_loss = |v^T J_f(H*)|^2 / (N d) with its gradient w.r.t. the parameters of f: the reference builds the VJP with
     ``create_graph=True`` (jac_loss_estimate, dirichlet/psignn/model.py:416-435) and lets ``loss.backward()`` run the
-    double backward; here backward is the HIP backward-of-the-VJP (csrc/gather_backward.hip).  H* is a leaf in the
+    double backward; here backward is the HIP backward-of-the-VJP (csrc/gather_backward.hip; with the config key
+    ``jac_backward = "tiled"`` its tile form, csrc/fgnn_tile_jr.hip, where the map has one).  H* is a leaf in the
     reference (model.py:204), so nothing flows back into the solve."""
 
     @staticmethod
@@ -208,7 +214,9 @@ class _JacLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         H_star, v, g = ctx.saved_tensors
-        grads, _ = ctx.fmap.vjp_backward(H_star, v, g * (2.0 * grad_out / H_star.numel()))
+        # "tiled": the tile kernels where the map has that form; the gather kernels otherwise (untiled plan, mixed family, n_layers > 1)
+        tiled = ctx.fmap.jac_backward == "tiled" and ctx.fmap.can_tile_vjp_backward()
+        grads, _ = ctx.fmap.vjp_backward(H_star, v, g * (2.0 * grad_out / H_star.numel()), tiled=tiled)
         return (None, None, None, None) + tuple(grads[n] for n in ctx.names)
 
 
@@ -392,6 +400,8 @@ class _Base(nn.Module):
             self.config_deq["bw_linearize"] = bool(self.config["bw_linearize"])
         if "lin_neumann" in self.config:   # optional: the stored linearisation keeps the mixed family's Neumann rows too
             self.config_deq["lin_neumann"] = engine.check_lin_neumann(self.config["lin_neumann"])   # (ValueError otherwise)
+        if "jac_backward" in self.config:   # optional: the Jacobian regulariser's backward on the tile kernels where the plan has them
+            self.config_deq["jac_backward"] = engine.check_jac_backward(self.config["jac_backward"])   # (ValueError otherwise)
         if "broyden_history_dtype" in self.config:   # optional: bf16 storage of the Broyden pairs (utilities.solver.broyden only)
             engine.history_code(self.config["broyden_history_dtype"])   # (ValueError for any other dtype)
             self.config_deq["broyden_history_dtype"] = self.config["broyden_history_dtype"]
@@ -400,6 +410,7 @@ class _Base(nn.Module):
                               second_member_dim=3 if self.mixed else 2, activation=nn.ReLU(), mixed=self.mixed),
             config_deq=self.config_deq)
         self.deqdss.f.lin_neumann = self.config_deq.get("lin_neumann", "direct")
+        self.deqdss.f.jac_backward = self.config_deq.get("jac_backward", "gather")
         self.mse_loss = nn.MSELoss()
 
     # -- helpers -------------------------------------------------------------------------------
