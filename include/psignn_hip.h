@@ -407,6 +407,30 @@ int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* d_weights, in
 int psignn_broyden_solve_adjoint_lin(psignn_broyden_t* s, const psignn_lin_t* lin, const float* d_weights, int n_layers,
                                      const float* d_grad, double eps, int poll_every, float* d_result,
                                      psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
+/* Batched adjoint solve: the lockstep form of psignn_broyden_solve_adjoint_lin for the n meshes of one shard.  Per iteration ONE launch
+ * per pass over all meshes: x_next, the batched transposed product of the stored linearisations (out_m = J_m^T y_m), the residual
+ * (J^T y + grad) - y with its norm partials, and the update chain psignn_broyden_solve_batch issues; every mesh keeps its own status
+ * block, traces and stop test (a mesh whose test has fired is skipped while the others go on).  For every mesh n_iter, nstep,
+ * stop_reason, both traces and the result are bit-identical to psignn_broyden_solve_adjoint_lin with the same solver object on that
+ * mesh alone.  solvers[i] was created from mesh i's plan with shard_elems (psignn_broyden_create_for_batch), lins[i] was made for
+ * that plan and built at the mesh's h*; the lazy first-call work of psignn_lin_vjp runs per handle before the loop.  Single-layer
+ * blocks.  A shard psignn_broyden_adjoint_batchable does not take is PSIGNN_EINVAL with nothing launched.
+ * replaces: the R replicas of the reference's DataParallel training step (dirichlet/psignn/main.py:106, mixed/psignn/main.py:106), each
+ *           running the backward hook of DeepEquilibrium.forward (dirichlet/psignn/model.py:210-223) as an independent fixed-point
+ *           problem with its own Broyden matrix and stop test.
+ * Arrays of n device / host pointers; d_grads[i], d_results[i] in the caller's numbering; h_rel_trace[i] / h_abs_trace[i]: `threshold`
+ * doubles each (arrays may be NULL). */
+int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** solvers, const psignn_lin_t* const* lins, const float* d_weights,
+                                           int n_layers, const float* const* d_grads, double eps, int poll_every,
+                                           float* const* d_results, psignn_solve_info_t* h_infos, double* const* h_rel_trace,
+                                           double* const* h_abs_trace, void* stream);
+/* 1 when psignn_broyden_solve_adjoint_lin_batch takes these solvers and linearisations together: all that psignn_broyden_batchable
+ * asks of the solvers, and every lins[i] was made for solvers[i]'s plan, has been built, and holds a form the batched product takes
+ * (dirichlet handles; mixed handles only with the Neumann rows stored, psignn_lin_create_opts(.., 1)).  0 otherwise, also for NULL
+ * arguments -- a host-side question, asked before a shard is handed over.
+ * replaces: nothing in the reference (its DataParallel replicas, dirichlet/psignn/main.py:106, each run their own backward hook,
+ *           dirichlet/psignn/model.py:210-223, whatever the meshes are). */
+int psignn_broyden_adjoint_batchable(int n, psignn_broyden_t* const* solvers, const psignn_lin_t* const* lins);
 /* Copy iterate i (0..n_iter) of the last solve to d_dst (needs keep_trace). */
 int psignn_broyden_get_iterate(const psignn_broyden_t* s, int i, float* d_dst, void* stream);
 /* Copy stored rank-one pair j (0 .. pairs stored - 1) of the last solve to d_dst: which = 0 -> U_j, 1 -> V_j; which = 2 -> the current

@@ -109,6 +109,10 @@ SIGNATURES = {
                                           C.POINTER(_P), C.POINTER(SolveInfo), C.POINTER(C.POINTER(C.c_double)),
                                           C.POINTER(C.POINTER(C.c_double)), _P]),
     "psignn_broyden_batchable": (_INT, [_INT, C.POINTER(_P)]),
+    "psignn_broyden_solve_adjoint_lin_batch": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P), _P, _INT, C.POINTER(_P), C.c_double, _INT,
+                                               C.POINTER(_P), C.POINTER(SolveInfo), C.POINTER(C.POINTER(C.c_double)),
+                                               C.POINTER(C.POINTER(C.c_double)), _P]),
+    "psignn_broyden_adjoint_batchable": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P)]),
     "psignn_broyden_get_iterate": (_INT, [_P, _INT, _P, _P]),
     "psignn_broyden_get_pair": (_INT, [_P, _INT, _INT, _P, _P]),
     "psignn_broyden_ext_begin": (_INT, [_P, _P, _P, _P]),

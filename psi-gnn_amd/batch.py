@@ -5,6 +5,11 @@ a list of graphs is split over devices, and the per-replica scalar losses are av
 (``training_class.py:156-159``).  Meshes are independent fixed-point problems, so inference shards them
 round-robin over ranks and every rank solves its own; the only collective that exists on the reference's path —
 the loss mean over replicas — is one tiny all-reduce (RCCL over xGMI on GPUs, gloo in the CPU tests).
+
+Training has the same replica semantics on ONE GPU: ``loader.DataParallel(net, replicas=R)`` cuts a list of graphs into R union
+batches and ``ModelDEQDSS.forward`` solves them as R independent fixed-point problems in lockstep — the forward solves through
+``engine.broyden_solve_batch`` (what ``solve_shard_batched`` below uses for inference), the adjoint solves through
+``engine.broyden_solve_adjoint_batch`` — with the losses stacked to shape ``(R,)`` for the trainer's mean.
 """
 from __future__ import annotations
 

@@ -200,4 +200,22 @@ struct BatchDesc {
   int32_t nblk4, pad_;         // its blocks (4 floats per lane)
   const float* nrmp;           // mixed family: unit normals in plan order (NULL for dirichlet plans)
   int64_t pstride;             // plane stride of the dot partials (solver.hip: part = 3 planes of (blocks, ldp))
+  // batched adjoint solve (psignn_broyden_solve_adjoint_lin_batch): the map's value, the permuted right-hand side, the copy of the
+  // iterate the product reads, and the entries of nrm_part the stop test sums (forward: one pair per tile; adjoint: one per block of
+  // the unfused residual)
+  float *fx, *xcopy;
+  const float* grad;
+  int32_t n_nrm, pad2_;
+};
+
+// Batched transposed product of stored linearisations (fgnn_tile_lin.hip k_vjp_lin_batch): one descriptor per mesh of a shard
+struct LinBatchDesc {
+  const struct TileCtx* ctx;
+  const uint32_t *slot, *tslot;   // the handle's slot dwords and their transposed form
+  const float* rec;               // its node records
+  const int32_t* vlist;           // mixed handle (Neumann rows stored): its tile list; NULL for a dirichlet handle
+  const float* w;                 // out = J^T w, plan order
+  float* out;
+  const int32_t* st;              // the mesh's Status block, int32 view (done flag)
+  int32_t n_slots, slot_base;     // the mesh's entries of the shard's slot list / its first entry
 };

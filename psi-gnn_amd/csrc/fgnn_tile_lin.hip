@@ -943,6 +943,34 @@ __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin_mixed(int chunk, const
   else vjp_lin_tile<P, false>(e, lds, C, W, lofs, tofs, slot, tslot, rec, tw, out, tnofs);
 }
 
+// Batched transposed product (solver.hip psignn_broyden_solve_adjoint_lin_batch): ONE launch computes out_m = J_m^T w_m for every
+// mesh m of a shard.  The tile entries of all meshes form one slot list (mesh m owns slots [slot_base[m], slot_base[m] + n_slots[m]):
+// its tiles in order for a dirichlet handle, its own tile list -- chunk * 8 entries, -1 = none, LIN_VNEU = the Neumann form -- for a
+// mixed handle with the Neumann rows stored); a workgroup looks its slot's mesh up, loads that mesh's plan context, linearisation
+// arrays and vectors from its descriptor and runs the same tile body as k_vjp_lin / k_vjp_lin_mixed: a tile's rows depend on nothing
+// but the tile, so every mesh's product has the bits of its own launch.  A mesh whose stop test has fired is skipped tile by tile.
+template <int P>
+__global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin_batch(const LinBatchDesc* __restrict__ descs, int n_mesh, int n_slots, int chunk,
+                                                                int off_done, const float* __restrict__ W, int lofs, int tofs, int tnofs) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int slot = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (slot >= n_slots) return;
+  int m = 0;
+  while (m + 1 < n_mesh && descs[m + 1].slot_base <= slot) ++m;   // wave-uniform scalar walk (a shard has few meshes)
+  const LinBatchDesc& d = descs[m];
+  if (d.st[off_done]) return;
+  int32_t e = slot - d.slot_base;
+  if constexpr (P == 3) {
+    e = d.vlist[e];
+    if (e < 0) return;
+    if (e & LIN_VNEU) {
+      vjp_lin_tile<P, true>(e & (LIN_VNEU - 1), lds, *d.ctx, W, lofs, tofs, d.slot, d.tslot, d.rec, d.w, d.out, tnofs);
+      return;
+    }
+  }
+  vjp_lin_tile<P, false>(e, lds, *d.ctx, W, lofs, tofs, d.slot, d.tslot, d.rec, d.w, d.out, tnofs);
+}
+
 // Reverse slot map, once per handle, matched per edge DIRECTION (merge_slots in tiles.hip may pair a node's slots differently on the
 // two sides: with u -> n twice and n -> u once, mirrored, u's row is [OUT-only, MERGED] and n's [IN-only, IN-only, OUT-only]):
 //   u's slot s carries OUT (edge u -> n), the k-th such slot of u towards n  <->  the k-th IN-carrying slot of n towards u:
@@ -1217,17 +1245,10 @@ extern "C" int psignn_lin_jvp(const psignn_lin_t* s, const float* W, int nl, con
 int psignn_f_tile_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* w,
                       float* out, float* work, hipStream_t st);
 
-extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, const float* w, float* out, float* work, void* stream) {
-  ARG_CHECK(s && W && w && out, "NULL argument");
-  ARG_CHECK(s->built, "psignn_lin_build has not run");
-  ARG_CHECK(w != out, "in-place product is not supported");
+// The transposed product's lazy work: on the first call of the handle the two transposed arrays and k_lin_rev, on the first call after a
+// build k_lin_tfill.  (The batched product runs it per handle in its prologue, never inside the lockstep loop.)
+static int lin_vjp_prepare(const psignn_lin* s, hipStream_t st) {
   const psignn_plan* p = s->plan;
-  ARG_CHECK(p->mixed ? nl >= 1 : nl == 1, "linearised VJP: single-layer blocks (mixed plans: the last layer)");
-  hipStream_t st = (hipStream_t)stream;
-  if (p->mixed && !s->neu) {
-    ARG_CHECK(work, "mixed plan: the transposed product needs the plan workspace");
-    return psignn_f_tile_vjp(p, W, nl, s->h, s->prb, s->nrm, w, out, work, st);
-  }
   const int64_t n_sl = p->ell_rows * 64;
   if (!s->tslot) {
     const size_t nb = (size_t)(p->ell_rows + 1) * 64, b = nb * 4 + nb * 8 + 4;
@@ -1272,6 +1293,21 @@ extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, con
       LAUNCH("k_lin_tfill", st, (k_lin_tfill<<<(unsigned)cdiv(n_sl, 256), 256, 0, st>>>(n_sl, s->rev, s->slot, s->tslot)));
     s->tfilled = 1;
   }
+  return PSIGNN_OK;
+}
+
+extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, const float* w, float* out, float* work, void* stream) {
+  ARG_CHECK(s && W && w && out, "NULL argument");
+  ARG_CHECK(s->built, "psignn_lin_build has not run");
+  ARG_CHECK(w != out, "in-place product is not supported");
+  const psignn_plan* p = s->plan;
+  ARG_CHECK(p->mixed ? nl >= 1 : nl == 1, "linearised VJP: single-layer blocks (mixed plans: the last layer)");
+  hipStream_t st = (hipStream_t)stream;
+  if (p->mixed && !s->neu) {
+    ARG_CHECK(work, "mixed plan: the transposed product needs the plan workspace");
+    return psignn_f_tile_vjp(p, W, nl, s->h, s->prb, s->nrm, w, out, work, st);
+  }
+  if (int rc = lin_vjp_prepare(s, st)) return rc;
   const size_t lds = (size_t)p->max_rows * 20 * 4;
   if (s->neu) {   // mixed plan, Neumann rows stored: one launch, the Neumann form on the tiles with a Neumann row among tile + halo
     using L = WLayout<3>;
@@ -1297,3 +1333,49 @@ extern "C" int psignn_lin_vjp(const psignn_lin_t* s, const float* W, int nl, con
 }
 
 const psignn_plan* psignn_lin_plan(const psignn_lin_t* s) { return s ? s->plan : nullptr; }
+
+// ---- batched transposed product (solver.hip)
+// 1 when the batch product takes this handle for a solver of plan p: made for p, built, dirichlet or mixed with the Neumann rows stored
+int psignn_lin_batch_ok(const psignn_lin_t* s, const psignn_plan* p) {
+  return s && p && s->plan == p && s->built && (!p->mixed || s->neu) ? 1 : 0;
+}
+
+// algorithmic bytes of one transposed product of the handle (as psignn_lin_vjp states them)
+int64_t psignn_lin_vjp_bytes(const psignn_lin_t* s) {
+  const psignn_plan* p = s->plan;
+  return (int64_t)p->N * (81 + LIN_REC * 4) + (int64_t)p->ell_rows * 64 * 8;
+}
+
+// The handle's part of its mesh descriptor (d->w, d->out, d->st, d->slot_base are the caller's), after the lazy work of psignn_lin_vjp
+int psignn_lin_batch_fill(const psignn_lin_t* s, LinBatchDesc* d, hipStream_t st) {
+  ARG_CHECK(s && d && s->built, "psignn_lin_build has not run");
+  const psignn_plan* p = s->plan;
+  ARG_CHECK(!p->mixed || s->neu, "batched transposed product: mixed handles need the Neumann rows stored");
+  if (int rc = lin_vjp_prepare(s, st)) return rc;
+  d->ctx = p->d_ctx;
+  d->slot = s->slot;
+  d->tslot = s->tslot;
+  d->rec = s->rec;
+  d->vlist = s->neu ? s->vlist : nullptr;
+  d->n_slots = s->neu ? (int32_t)cdiv(p->n_tiles, 8) * 8 : (int32_t)p->n_tiles;
+  return PSIGNN_OK;
+}
+
+// descs: device array of n_mesh descriptors of ONE family; max_rows: largest tile + halo row count over the meshes (LDS size)
+int psignn_lin_vjp_batch(const LinBatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed, int off_done,
+                         hipStream_t st) {
+  const int chunk = (int)cdiv(n_slots, 8);
+  if (chunk <= 0) return PSIGNN_OK;
+  const size_t lds = (size_t)max_rows * 20 * 4;
+  if (mixed) {
+    using L = WLayout<3>;
+    LAUNCH("k_vjp_lin_batch", st, (k_vjp_lin_batch<3><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
+        d_descs, n_mesh, n_slots, chunk, off_done, W, L::layer(0), L::tp_layer(1, true, 0), L::tp_neu(1))));
+  } else {
+    using L = WLayout<2>;
+    LAUNCH("k_vjp_lin_batch", st, (k_vjp_lin_batch<2><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(
+        d_descs, n_mesh, n_slots, chunk, off_done, W, L::layer(0), L::tp_layer(1, false, 0), 0)));
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}

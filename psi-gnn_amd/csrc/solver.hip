@@ -132,8 +132,8 @@ __global__ __launch_bounds__(TB) void k_begin(int64_t M, const float* __restrict
 
 // x_next = x_cur + upd   (line_search with on=False: s = 1, solver.py:85-94)
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_xnext(int64_t M, const Status* __restrict__ st, float* __restrict__ xb,
-                                              const float* __restrict__ upd, float* __restrict__ copy_out) {
+__device__ __forceinline__ void xnext_body(int64_t M, const Status* __restrict__ st, float* __restrict__ xb,
+                                           const float* __restrict__ upd, float* __restrict__ copy_out) {
   if (st->done) return;
   int64_t e0 = elem0<VEC>();
   if (e0 >= M) return;
@@ -146,6 +146,11 @@ __global__ __launch_bounds__(TB) void k_xnext(int64_t M, const Status* __restric
   for (int i = 0; i < VEC; ++i) a[i] += b[i];
   stv<VEC>(xn, e0, M, a);
   if (copy_out) stv<VEC>(copy_out, e0, M, a);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_xnext(int64_t M, const Status* __restrict__ st, float* __restrict__ xb,
+                                              const float* __restrict__ upd, float* __restrict__ copy_out) {
+  xnext_body<VEC>(M, st, xb, upd, copy_out);
 }
 
 // line search (solver.py:61-94, ls=True): trial point x_cur + s * upd -> out; commit: the step becomes upd <- s * upd
@@ -1594,7 +1599,7 @@ __global__ __launch_bounds__(TB) void kb_dots(const BatchDesc* __restrict__ desc
 __global__ __launch_bounds__(RB) void kb_reduce_check(const BatchDesc* __restrict__ descs, int k, double eps) {
   __shared__ double sh[RB];
   const BatchDesc& d = descs[blockIdx.z];
-  reduce_check_body(reinterpret_cast<Status*>(d.st), d.part, d.nblk, d.pstride, (d.thr + 63) / 64 * 64, d.thr, k, d.coef, d.nrm_part, d.n_tiles, d.rel_trace,
+  reduce_check_body(reinterpret_cast<Status*>(d.st), d.part, d.nblk, d.pstride, (d.thr + 63) / 64 * 64, d.thr, k, d.coef, d.nrm_part, d.n_nrm, d.rel_trace,
                     d.abs_trace, eps, d.seq_len, d.keep_trace, sh);
 }
 template <int VEC>
@@ -1632,7 +1637,7 @@ __global__ __launch_bounds__(TB) void kb_sweep_u1(const BatchDesc* __restrict__ 
 __global__ __launch_bounds__(RB) void kb_reduce_a_check(const BatchDesc* __restrict__ descs, int k, double eps, int a_from) {
   __shared__ double sh[RB];
   const BatchDesc& d = descs[blockIdx.z];
-  reduce_a_check_body(reinterpret_cast<Status*>(d.st), d.part, d.nblk_u, (d.thr + 63) / 64 * 64, d.thr, k, d.coef, d.nrm_part, d.n_tiles, d.rel_trace,
+  reduce_a_check_body(reinterpret_cast<Status*>(d.st), d.part, d.nblk_u, (d.thr + 63) / 64 * 64, d.thr, k, d.coef, d.nrm_part, d.n_nrm, d.rel_trace,
                       d.abs_trace, eps, d.seq_len, d.keep_trace, sh, d.parta, d.nblk4, a_from);
 }
 __global__ __launch_bounds__(TB) void kb_sweep_u2d(const BatchDesc* __restrict__ descs, int k, int j_keep0, int par) {
@@ -1673,6 +1678,74 @@ __global__ void kb_all_done(const BatchDesc* __restrict__ descs, int n, int off_
   }
 }
 
+// Everything of one lockstep iteration after every mesh's g_new and norm partials are available (k = pairs stored so far, the same
+// for all meshes): the update chain of launch_update, one launch per pass over the shard.  Issued by the forward batched solve and by
+// the batched adjoint solve.
+struct BatchShape {
+  int n = 0, max_g = 0, max_ga = 0, max_gu = 0, max_g4 = 0, max_G = 1, thr = 0;
+  bool own_width = false;
+  int64_t Mtot4 = 0;          // bytes of one state vector, summed over the shard (profiling records)
+  bool a_ready = false;       // a of the next iteration comes (partly) from the folded sweep 3
+  int a_from_next = 0;
+};
+static void launch_update_batch(const psignn_broyden* s0, BatchShape& sh, const BatchDesc* d_descs, int k, double eps, hipStream_t st) {
+  const int thr = sh.thr, par = k & 1;
+  const int kd = k >= thr ? 0 : k;
+  if (s0->uvu) {
+    const dim3 gu((unsigned)sh.max_gu, 1, (unsigned)sh.n);
+    // (all meshes of the shard carry the same number of stored pairs: one a_from / keep window for the launch)
+    const int a_from = sh.a_ready ? sh.a_from_next : kd;
+    if (std::min(a_from, kd) > 0) {
+      PROF_BYTES((std::min(a_from, kd) + 1) * sh.Mtot4);
+      VLAUNCH("k_sweep_u1", st, s0->vec_u, kb_sweep_u1, (gu, TB, 0, st), d_descs, std::min(a_from, kd));
+    }
+    LAUNCH("k_reduce_check", st, (kb_reduce_a_check<<<dim3((unsigned)std::max(kd, 1), RA + 1, (unsigned)sh.n), RB, 0, st>>>(d_descs, kd, eps, a_from)));
+    sh.a_ready = false;
+    const bool last = k + 1 >= thr;   // the stop test of iteration thr has fired: the sweeps below return at once
+    PROF_BYTES(last ? 0 : (k + 4) * sh.Mtot4);
+    VLAUNCH("k_sweep_v", st, s0->vec_u, kb_sweep_v, (gu, TB, 0, st), d_descs, k, par);
+    LAUNCH("k_reduce_cb", st, (kb_reduce_cb<<<dim3((unsigned)std::max(k, 1), 3, (unsigned)sh.n), RB, 0, st>>>(d_descs, k)));
+    const int keep0 = k <= s0->u2d_kmax ? 0 : k - s0->u2d_keep;
+    if (s0->u2d_kmax > 0 && (k <= s0->u2d_kmax || s0->u2d_keep > 0) && k + 1 < thr) {
+      PROF_BYTES((k + 5) * sh.Mtot4);
+      const int nk = k - keep0;
+      const dim3 g4((unsigned)sh.max_g4, 1, (unsigned)sh.n);
+      if (s0->u2d_reg) {
+        if (nk <= 8) LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<8><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
+        else if (nk <= 16) LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<16><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
+        else LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<24><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
+      } else {
+        const size_t lds = (size_t)std::max(nk, 1) * TB * 16;
+        LAUNCH("k_sweep_u2d", st, (kb_sweep_u2d<<<g4, TB, lds, st>>>(d_descs, k, keep0, par)));
+      }
+      sh.a_ready = true;
+      sh.a_from_next = keep0;
+    } else {
+      PROF_BYTES(last ? 0 : (k + 5) * sh.Mtot4);
+      VLAUNCH("k_sweep_u2", st, s0->vec_u, kb_sweep_u2, (gu, TB, 0, st), d_descs, k, par);
+    }
+  } else {
+  if (kd > 0) {
+    PROF_BYTES((2 * kd + 3) * sh.Mtot4);
+    VLAUNCH("k_dots", st, s0->vec, kb_dots, (dim3((unsigned)sh.max_g, (unsigned)sh.max_G, (unsigned)sh.n), TB, 0, st), d_descs, kd, par);
+  }
+  LAUNCH("k_reduce_check", st, (kb_reduce_check<<<dim3((unsigned)std::max(kd, 1), 4, (unsigned)sh.n), RB, 0, st>>>(d_descs, kd, eps)));
+  if (sh.own_width) {
+    PROF_BYTES(k + 1 >= thr ? 0 : (2 * k + 6) * sh.Mtot4);
+    VLAUNCH("k_axpy", st, s0->vec_ax, kb_axpy, (dim3((unsigned)sh.max_ga, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, 1, par);
+    PROF_BYTES(k + 1 >= thr ? 0 : 4 * sh.Mtot4);
+    VLAUNCH("k_final", st, s0->vec_ax, kb_final, (dim3((unsigned)sh.max_ga, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, 1);
+  } else {
+    PROF_BYTES(k + 1 >= thr ? 0 : (2 * k + 6) * sh.Mtot4);
+    VLAUNCH("k_axpy", st, s0->vec, kb_axpy, (dim3((unsigned)sh.max_g, (unsigned)sh.max_G, (unsigned)sh.n), TB, 0, st), d_descs, k, 0, par);
+    if (sh.max_G > 1 && k >= 4 * 2)   // some mesh may split from k = 4 * jgroups on (jgroups >= 2)
+      VLAUNCH("k_axpy_combine", st, s0->vec, kb_axpy_combine, (dim3((unsigned)sh.max_g, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, par);
+    PROF_BYTES(k + 1 >= thr ? 0 : 4 * sh.Mtot4);
+    VLAUNCH("k_final", st, s0->vec, kb_final, (dim3((unsigned)sh.max_g, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, 0);
+  }
+  }
+}
+
 int psignn_f_tile_fused_batch(const BatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed,
                               int off_done, int off_cur, int off_nxt, int par, hipStream_t st);
 
@@ -1703,7 +1776,10 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
   if (poll_every <= 0) poll_every = 8;
   // one vector width / split layout / threshold for the whole shard (meshes of one shard are of one size class)
   const psignn_broyden* s0 = sv[0];
-  int max_g = 0, max_ga = 0, max_gu = 0, max_g4 = 0, max_G = 1, max_rows = 0, n_slots = 0;
+  BatchShape sh;
+  sh.n = n;
+  sh.thr = s0->thr;
+  int max_rows = 0, n_slots = 0;
   for (int m = 0; m < n; ++m) {
     const psignn_broyden* s = sv[m];
     ARG_CHECK(s && s->plan && s->plan->tiled, "batched solve: tiled plans only");
@@ -1714,17 +1790,18 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
               "batched solve: meshes of different size classes (vector width / threshold differ)");
     ARG_CHECK(h0[m] && prb[m], "NULL argument");
     ARG_CHECK(!s->plan->mixed || (nrm && nrm[m]), "mixed plans need unit normals");
-    max_g = std::max(max_g, s->nblk);
-    max_ga = std::max(max_ga, s->nblk_ax);
-    max_gu = std::max(max_gu, s->nblk_u);
-    max_G = std::max(max_G, s->jgroups);
+    sh.max_g = std::max(sh.max_g, s->nblk);
+    sh.max_ga = std::max(sh.max_ga, s->nblk_ax);
+    sh.max_gu = std::max(sh.max_gu, s->nblk_u);
+    sh.max_g4 = std::max(sh.max_g4, s->nblk4);
+    sh.max_G = std::max(sh.max_G, s->jgroups);
     max_rows = std::max(max_rows, s->plan->max_rows);
     n_slots += (int)s->plan->n_tiles;
   }
-  const bool own_width = s0->vec_ax != s0->vec;
-  int64_t Mtot4 = 0, bf_tot = 0;   // bytes of one state vector / of one fused f evaluation, summed over the shard (profiling records)
+  sh.own_width = s0->vec_ax != s0->vec;
+  int64_t bf_tot = 0;   // bytes of one fused f evaluation, summed over the shard (profiling records)
   for (int m = 0; m < n; ++m) {
-    Mtot4 += sv[m]->M * 4;
+    sh.Mtot4 += sv[m]->M * 4;
     bf_tot += (sv[m]->plan->mixed ? 102 : 89) * sv[m]->plan->N + 20 * sv[m]->plan->Ep + 8 * sv[m]->M;
   }
   // ---- per mesh: status, plan-order inputs, g0 = f(x0) - x0 (exactly the single-mesh prologue)
@@ -1750,7 +1827,7 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
     d.ctx = p->d_ctx; d.h0p = s->h0p; d.prbp = s->prbp;
     d.part2 = s->part2; d.nblk_u = s->nblk_u; d.npart_u = s->npart_u;
     d.parta = s->parta; d.nblk4 = s->nblk4; d.pad_ = 0; d.nrmp = nrmp; d.pstride = s->pstride;
-    max_g4 = std::max(max_g4, s->nblk4);
+    d.fx = s->fx; d.xcopy = s->h0p; d.grad = nullptr; d.n_nrm = (int)p->n_tiles; d.pad2_ = 0;
     base += (int)p->n_tiles;
   }
   BatchDesc* d_descs = nullptr;
@@ -1775,68 +1852,12 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
   BT(hipMemcpyAsync(d_descs, hd.data(), sizeof(BatchDesc) * n, hipMemcpyHostToDevice, st));
   const int off_done = offsetof(Status, done) / 4;
   const int thr = s0->thr;
-  bool a_ready = false;
-  int a_from_next = 0;
   for (int it = 0; it < thr; ++it) {
     PROF_BYTES(bf_tot);
     const int par = it & 1;
     rc = psignn_f_tile_fused_batch(d_descs, n, n_slots, max_rows, W, s0->plan->mixed, off_done, sel_off_cur(), sel_off_nxt(), par, st);
     if (rc) { cleanup(); return rc; }
-    const int k = it;
-    const int kd = k >= thr ? 0 : k;
-    if (s0->uvu) {
-      const dim3 gu((unsigned)max_gu, 1, (unsigned)n);
-      // (all meshes of the shard carry the same number of stored pairs: one a_from / keep window for the launch)
-      const int a_from = a_ready ? a_from_next : kd;
-      if (std::min(a_from, kd) > 0) {
-        PROF_BYTES((std::min(a_from, kd) + 1) * Mtot4);
-        VLAUNCH("k_sweep_u1", st, s0->vec_u, kb_sweep_u1, (gu, TB, 0, st), d_descs, std::min(a_from, kd));
-      }
-      LAUNCH("k_reduce_check", st, (kb_reduce_a_check<<<dim3((unsigned)std::max(kd, 1), RA + 1, (unsigned)n), RB, 0, st>>>(d_descs, kd, eps, a_from)));
-      a_ready = false;
-      const bool last = k + 1 >= thr;   // the stop test of iteration thr has fired: the sweeps below return at once
-      PROF_BYTES(last ? 0 : (k + 4) * Mtot4);
-      VLAUNCH("k_sweep_v", st, s0->vec_u, kb_sweep_v, (gu, TB, 0, st), d_descs, k, par);
-      LAUNCH("k_reduce_cb", st, (kb_reduce_cb<<<dim3((unsigned)std::max(k, 1), 3, (unsigned)n), RB, 0, st>>>(d_descs, k)));
-      const int keep0 = k <= s0->u2d_kmax ? 0 : k - s0->u2d_keep;
-      if (s0->u2d_kmax > 0 && (k <= s0->u2d_kmax || s0->u2d_keep > 0) && k + 1 < thr) {
-        PROF_BYTES((k + 5) * Mtot4);
-        const int nk = k - keep0;
-        const dim3 g4((unsigned)max_g4, 1, (unsigned)n);
-        if (s0->u2d_reg) {
-          if (nk <= 8) LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<8><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
-          else if (nk <= 16) LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<16><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
-          else LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<24><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
-        } else {
-          const size_t lds = (size_t)std::max(nk, 1) * TB * 16;
-          LAUNCH("k_sweep_u2d", st, (kb_sweep_u2d<<<g4, TB, lds, st>>>(d_descs, k, keep0, par)));
-        }
-        a_ready = true;
-        a_from_next = keep0;
-      } else {
-        PROF_BYTES(last ? 0 : (k + 5) * Mtot4);
-        VLAUNCH("k_sweep_u2", st, s0->vec_u, kb_sweep_u2, (gu, TB, 0, st), d_descs, k, par);
-      }
-    } else {
-    if (kd > 0) {
-      PROF_BYTES((2 * kd + 3) * Mtot4);
-      VLAUNCH("k_dots", st, s0->vec, kb_dots, (dim3((unsigned)max_g, (unsigned)max_G, (unsigned)n), TB, 0, st), d_descs, kd, par);
-    }
-    LAUNCH("k_reduce_check", st, (kb_reduce_check<<<dim3((unsigned)std::max(kd, 1), 4, (unsigned)n), RB, 0, st>>>(d_descs, kd, eps)));
-    if (own_width) {
-      PROF_BYTES(k + 1 >= thr ? 0 : (2 * k + 6) * Mtot4);
-      VLAUNCH("k_axpy", st, s0->vec_ax, kb_axpy, (dim3((unsigned)max_ga, 1, (unsigned)n), TB, 0, st), d_descs, k, 1, par);
-      PROF_BYTES(k + 1 >= thr ? 0 : 4 * Mtot4);
-      VLAUNCH("k_final", st, s0->vec_ax, kb_final, (dim3((unsigned)max_ga, 1, (unsigned)n), TB, 0, st), d_descs, k, 1);
-    } else {
-      PROF_BYTES(k + 1 >= thr ? 0 : (2 * k + 6) * Mtot4);
-      VLAUNCH("k_axpy", st, s0->vec, kb_axpy, (dim3((unsigned)max_g, (unsigned)max_G, (unsigned)n), TB, 0, st), d_descs, k, 0, par);
-      if (max_G > 1 && k >= 4 * 2)   // some mesh may split from k = 4 * jgroups on (jgroups >= 2)
-        VLAUNCH("k_axpy_combine", st, s0->vec, kb_axpy_combine, (dim3((unsigned)max_g, 1, (unsigned)n), TB, 0, st), d_descs, k, par);
-      PROF_BYTES(k + 1 >= thr ? 0 : 4 * Mtot4);
-      VLAUNCH("k_final", st, s0->vec, kb_final, (dim3((unsigned)max_g, 1, (unsigned)n), TB, 0, st), d_descs, k, 0);
-    }
-    }
+    launch_update_batch(s0, sh, d_descs, it, eps, st);
     if ((it + 1) % poll_every == 0 || it + 1 == thr) {
       kb_all_done<<<1, 64, 0, st>>>(d_descs, n, off_done, d_done);
       BT(hipMemcpyAsync(h_done, d_done, 4, hipMemcpyDeviceToHost, st));
@@ -1976,6 +1997,179 @@ extern "C" int psignn_broyden_solve_adjoint_lin(psignn_broyden_t* s, const psign
   if ((rc = psignn_plan_permute(p, grad, D, gr_p, 1, st))) return rc;
   auto vjp = [&](const float* y, float* out) { return psignn_lin_vjp(lin, W, nl, y, out, s->fwork, st); };
   return adjoint_loop(s, gr_p, eps, poll_every, vjp, d_result, info, h_rel, h_abs, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// Batched adjoint solve: the lockstep form of adjoint_loop for the meshes of one shard (the replicas of the reference's DataParallel
+// training step, */psignn/main.py:106, each with the backward hook of model.py:210-223).  Per iteration: x_next of every mesh, ONE
+// batched transposed product of the stored linearisations (fgnn_tile_lin.hip k_vjp_lin_batch), g_new = (J^T y + grad) - y with the norm
+// partials, then the update chain the forward batched solve issues.  Blocks run the single-mesh bodies on their mesh's descriptor, so
+// every mesh has the bits of psignn_broyden_solve_adjoint_lin on the same solver object.
+// ------------------------------------------------------------------------------------------
+template <int VEC>
+__global__ __launch_bounds__(TB) void kb_xnext(const BatchDesc* __restrict__ descs) {
+  const BatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk) return;
+  xnext_body<VEC>(d.M, reinterpret_cast<const Status*>(d.st), d.xbuf, d.upd, d.xcopy);
+}
+// k_addv and k_resid in one pass: f = fx + grad, g_new = f - x_next (per element the same two fp32 operations in the same order; f is
+// not needed again, so it is not written back), per-block partials of |g_new|^2 and |f|^2
+template <int VEC>
+__global__ __launch_bounds__(TB) void kb_addv_resid(const BatchDesc* __restrict__ descs, int par) {
+  const BatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk) return;
+  const Status* st = reinterpret_cast<const Status*>(d.st);
+  if (st->done) return;
+  const int64_t M = d.M;
+  int64_t e0 = elem0<VEC>();
+  float sg = 0.f, sf = 0.f;
+  if (e0 < M) {
+    const float* xn = d.xbuf + (int64_t)st->nxt * M;
+    float x[VEC], f[VEC], gr[VEC];
+    ldv<VEC>(xn, e0, M, x);
+    ldv<VEC>(d.fx, e0, M, f);
+    ldv<VEC>(d.grad, e0, M, gr);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      const float fi = f[i] + gr[i];
+      const float gn = fi - x[i];
+      sg = fmaf(gn, gn, sg);
+      sf = fmaf(fi, fi, sf);
+      x[i] = gn;
+    }
+    stv<VEC>(bd_gnew(d, par), e0, M, x);
+  }
+  block_pair_store(sg, sf, d.nrm_part, d.nblk);
+}
+
+int psignn_lin_batch_ok(const psignn_lin_t* lin, const psignn_plan* p);
+int psignn_lin_batch_fill(const psignn_lin_t* lin, LinBatchDesc* d, hipStream_t st);
+int64_t psignn_lin_vjp_bytes(const psignn_lin_t* lin);
+int psignn_lin_vjp_batch(const LinBatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed, int off_done,
+                         hipStream_t st);
+
+// 1 when psignn_broyden_solve_adjoint_lin_batch takes these solvers and handles together: all that psignn_broyden_batchable asks, and
+// every lins[i] was made for solvers[i]'s plan, has been built and holds a form the batch product takes (dirichlet; mixed only with
+// the Neumann rows stored).  A host-side question; 0 also for NULL arguments.
+extern "C" int psignn_broyden_adjoint_batchable(int n, psignn_broyden_t* const* sv, const psignn_lin_t* const* lins) {
+  if (n <= 0 || !sv || !lins) return 0;
+  if (!psignn_broyden_batchable(n, sv)) return 0;
+  for (int m = 0; m < n; ++m)
+    if (!psignn_lin_batch_ok(lins[m], sv[m]->plan)) return 0;
+  return 1;
+}
+
+extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** sv, const psignn_lin_t* const* lins, const float* W, int nl,
+                                                      const float* const* grads, double eps, int poll_every, float* const* d_results,
+                                                      psignn_solve_info_t* infos, double* const* h_rel, double* const* h_abs,
+                                                      void* stream) {
+  ARG_CHECK(n > 0 && sv && lins && W && grads, "bad arguments");
+  ARG_CHECK(nl == 1, "the batched adjoint solve runs single-layer blocks");
+  // (nothing is launched for a shard the lockstep does not take)
+  ARG_CHECK(psignn_broyden_adjoint_batchable(n, sv, lins),
+            "batched adjoint solve: solvers / linearisations are not batchable (psignn_broyden_adjoint_batchable)");
+  for (int m = 0; m < n; ++m) ARG_CHECK(grads[m], "NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (poll_every <= 0) poll_every = 8;
+  const psignn_broyden* s0 = sv[0];
+  BatchShape sh;
+  sh.n = n;
+  sh.thr = s0->thr;
+  sh.own_width = s0->vec_ax != s0->vec;
+  int max_rows = 0, n_slots = 0;
+  int64_t bv_tot = 0;   // bytes of one transposed product, summed over the shard (profiling records)
+  // ---- per mesh: the lazy work of the transposed product, status, permuted right-hand side, y0 = 0 (the single-mesh prologue)
+  std::vector<BatchDesc> hd(n);
+  std::vector<LinBatchDesc> hl(n);
+  int rc;
+  for (int m = 0; m < n; ++m) {
+    psignn_broyden* s = sv[m];
+    const psignn_plan* p = s->plan;
+    sh.max_g = std::max(sh.max_g, s->nblk);
+    sh.max_ga = std::max(sh.max_ga, s->nblk_ax);
+    sh.max_gu = std::max(sh.max_gu, s->nblk_u);
+    sh.max_g4 = std::max(sh.max_g4, s->nblk4);
+    sh.max_G = std::max(sh.max_G, s->jgroups);
+    sh.Mtot4 += s->M * 4;
+    max_rows = std::max(max_rows, p->max_rows);
+    LinBatchDesc& l = hl[m];
+    if ((rc = psignn_lin_batch_fill(lins[m], &l, st))) return rc;
+    bv_tot += psignn_lin_vjp_bytes(lins[m]);
+    s->plan_order = 1;
+    float* gr_p = s->fwork + p->N * 5 * D;   // fwork = [B (40N) | (10N) | grad_p (10N) | ...], as in the single-mesh solve
+    if ((rc = psignn_plan_permute(p, grads[m], D, gr_p, 1, st))) return rc;
+    k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
+    HIP_TRY(hipMemsetAsync(s->h0p, 0, (size_t)s->M * 4, st));
+    VPLAIN(s->vec, k_begin, ((unsigned)s->nblk, TB, 0, st), s->M, s->h0p, gr_p, s->xbuf, s->gbuf[0], s->upd);
+    BatchDesc& d = hd[m];
+    d.M = s->M; d.ld = s->ld; d.nblk = s->nblk; d.npart = s->npart; d.nblk_ax = s->nblk_ax; d.jgroups = s->jgroups;
+    d.thr = s->thr; d.seq_len = s->seq_len; d.keep_trace = s->keep_trace; d.n_tiles = (int)p->n_tiles; d.tile_base = 0;
+    d.st = reinterpret_cast<int32_t*>(s->st);
+    d.U = s->U; d.V = s->V; d.xbuf = s->xbuf; d.g0 = s->gbuf[0]; d.g1 = s->gbuf[1]; d.upd = s->upd; d.part = s->part; d.coef = s->coef;
+    d.nrm_part = s->nrm_part; d.jpart = s->jpart; d.rel_trace = s->rel_trace; d.abs_trace = s->abs_trace;
+    d.ctx = p->d_ctx; d.h0p = s->h0p; d.prbp = s->prbp;
+    d.part2 = s->part2; d.nblk_u = s->nblk_u; d.npart_u = s->npart_u;
+    d.parta = s->parta; d.nblk4 = s->nblk4; d.pad_ = 0; d.nrmp = nullptr; d.pstride = s->pstride;
+    d.fx = s->fx; d.xcopy = s->h0p; d.grad = gr_p; d.n_nrm = s->nblk; d.pad2_ = 0;   // the unfused residual: one norm pair per block
+    l.w = s->h0p;
+    l.out = s->fx;
+    l.st = d.st;
+    l.slot_base = n_slots;
+    n_slots += l.n_slots;
+  }
+  BatchDesc* d_descs = nullptr;
+  LinBatchDesc* d_lin = nullptr;
+  int32_t *d_done = nullptr, *h_done = nullptr;
+  auto cleanup = [&]() {
+    if (d_descs) (void)hipFree(d_descs);
+    if (d_lin) (void)hipFree(d_lin);
+    if (d_done) (void)hipFree(d_done);
+    if (h_done) (void)hipHostFree(h_done);
+  };
+#define BT(expr)                                                                          \
+  do {                                                                                    \
+    hipError_t _e = (expr);                                                               \
+    if (_e != hipSuccess) {                                                               \
+      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+      cleanup();                                                                          \
+      return PSIGNN_EHIP;                                                                 \
+    }                                                                                     \
+  } while (0)
+  BT(hipMalloc((void**)&d_descs, sizeof(BatchDesc) * n));
+  BT(hipMalloc((void**)&d_lin, sizeof(LinBatchDesc) * n));
+  BT(hipMalloc((void**)&d_done, 4));
+  BT(hipHostMalloc((void**)&h_done, 4));
+  BT(hipMemcpyAsync(d_descs, hd.data(), sizeof(BatchDesc) * n, hipMemcpyHostToDevice, st));
+  BT(hipMemcpyAsync(d_lin, hl.data(), sizeof(LinBatchDesc) * n, hipMemcpyHostToDevice, st));
+  // (the descriptors are read from pageable host vectors: they must have left the host before the vectors can go)
+  BT(hipStreamSynchronize(st));
+  const int off_done = offsetof(Status, done) / 4;
+  const int thr = s0->thr;
+  const dim3 gv((unsigned)sh.max_g, 1, (unsigned)n);
+  for (int it = 0; it < thr; ++it) {
+    const int par = it & 1;
+    PROF_BYTES(3 * sh.Mtot4);
+    VLAUNCH("k_xnext", st, s0->vec, kb_xnext, (gv, TB, 0, st), d_descs);
+    PROF_BYTES(bv_tot);
+    rc = psignn_lin_vjp_batch(d_lin, n, n_slots, max_rows, W, s0->plan->mixed, off_done, st);
+    if (rc) { cleanup(); return rc; }
+    PROF_BYTES(4 * sh.Mtot4);
+    VLAUNCH("k_addv_resid", st, s0->vec, kb_addv_resid, (gv, TB, 0, st), d_descs, par);
+    launch_update_batch(s0, sh, d_descs, it, eps, st);
+    if ((it + 1) % poll_every == 0 || it + 1 == thr) {
+      kb_all_done<<<1, 64, 0, st>>>(d_descs, n, off_done, d_done);
+      BT(hipMemcpyAsync(h_done, d_done, 4, hipMemcpyDeviceToHost, st));
+      BT(hipStreamSynchronize(st));
+      if (*h_done) break;
+    }
+  }
+  rc = PSIGNN_OK;
+  for (int m = 0; m < n && rc == PSIGNN_OK; ++m)
+    rc = finish(sv[m], d_results ? d_results[m] : nullptr, infos ? &infos[m] : nullptr, h_rel ? h_rel[m] : nullptr,
+                h_abs ? h_abs[m] : nullptr, st);
+  cleanup();
+#undef BT
+  return rc;
 }
 
 extern "C" int psignn_broyden_get_iterate(const psignn_broyden_t* s, int i, float* d_dst, void* stream) {

@@ -1269,6 +1269,58 @@ def broyden_solve_batch(solvers, fmaps, eps, poll_every=8):
     return outs
 
 
+def adjoint_batchable(solvers, lins) -> bool:
+    """Whether ``broyden_solve_adjoint_batch`` takes these solvers and linearisations together
+    (``psignn_broyden_adjoint_batchable``): all that ``shard_batchable`` asks of the solvers, and every ``lins[i]`` was made for
+    ``solvers[i]``'s plan, has been built and holds a form the batched transposed product takes (dirichlet; mixed only with
+    ``neumann="stored"``).  A host-side decision -- real errors of the batched solve still raise."""
+    n = len(solvers)
+    if n == 0 or len(lins) != n or any(l is None or l.handle is None for l in lins):
+        return False
+    sv = (C.c_void_p * n)(*[s.handle.value for s in solvers])
+    lv = (C.c_void_p * n)(*[l.handle.value for l in lins])
+    return bool(nat.lib().psignn_broyden_adjoint_batchable(n, sv, lv))
+
+
+def broyden_solve_adjoint_batch(solvers, lins, grads, eps, poll_every=8):
+    """One lockstep device solve of the adjoint fixed points y_i = J_i^T y_i + grads[i] of several independent meshes
+    (``psignn_broyden_solve_adjoint_lin_batch``): ``solvers[i]`` is a ``DeviceBroyden`` of the plan ``lins[i]`` was made for
+    (created with ``shard_elems``), ``lins[i]`` a ``Linearization`` built at mesh i's H*.  ``grads`` and the results are in the
+    caller's numbering.  Returns the list of per-mesh result dicts of ``DeviceBroyden.solve_adjoint`` -- each bit-identical to
+    ``solvers[i].solve_adjoint(..., lin=lins[i])`` on that mesh alone.  A shard ``adjoint_batchable`` does not take raises
+    ``NativeError`` with nothing launched."""
+    n = len(solvers)
+    if n == 0:
+        return []
+    if len(lins) != n or len(grads) != n:
+        raise nat.NativeError("one Linearization and one gradient per solver")
+    w0 = lins[0].fmap.weights
+    for s, l in zip(solvers, lins):
+        if l.fmap.weights is not w0 and l.fmap.weights.flat.data_ptr() != w0.flat.data_ptr():
+            raise nat.NativeError("batched adjoint solve: all meshes must share one packed weight buffer")
+        if s.plan is not l.fmap.plan:
+            raise nat.NativeError("batched adjoint solve: solver and linearisation were made for different plans")
+    dev = solvers[0].device
+    gr = [_f32c(g) for g in grads]
+    results = [torch.empty_like(g) for g in gr]
+    arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
+    infos = (nat.SolveInfo * n)()
+    rel = [(C.c_double * s.threshold)() for s in solvers]
+    abs_ = [(C.c_double * s.threshold)() for s in solvers]
+    dpp = lambda rows: (C.POINTER(C.c_double) * n)(*[C.cast(r, C.POINTER(C.c_double)) for r in rows])
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().psignn_broyden_solve_adjoint_lin_batch(
+            n, arr([s.handle.value for s in solvers]), arr([l.handle.value for l in lins]), nat.ptr(w0.flat), w0.n_layers,
+            arr([nat.ptr(g) for g in gr]), float(eps), int(poll_every), arr([nat.ptr(r) for r in results]), infos,
+            dpp(rel), dpp(abs_), nat.stream_ptr(dev)), "psignn_broyden_solve_adjoint_lin_batch")
+    outs = []
+    for i, s in enumerate(solvers):
+        o = s._collect(infos[i], rel[i], abs_[i], results[i].shape, dev)
+        o["result"] = results[i]
+        outs.append(o)
+    return outs
+
+
 # ---------------------------------------------------------------------------------------------
 # Picard / Anderson on the device (csrc/fpiter.hip)
 # ---------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@
 * ``DataParallel(module)`` keeps the reference's calling convention -- ``model(list_of_graphs)``, ``model.module`` -- but
   is one process per GPU by design: the list is collated into ONE union batch on the module's device (what PyG's
   DataParallel does on each of its devices) and handed to the module.  Multi-GPU data parallelism is done with one process
-  per GPU and ``training_class.allreduce_mean_grads`` (RCCL), not with replica threads.
+  per GPU and ``training_class.allreduce_mean_grads`` (RCCL), not with replica threads.  ``DataParallel(module, replicas=R)``
+  gives the reference's R independent replicas on ONE GPU: R union batches, solved in lockstep (see the class).
 """
 from __future__ import annotations
 
@@ -41,9 +42,18 @@ class DataLoader(DataListLoader):
 
 
 class DataParallel(nn.Module):
-    def __init__(self, module, device_ids=None, output_device=None):
+    """``replicas = 1`` (default): the list is collated into one union batch.  ``replicas = R > 1``: the reference's
+    ``num_gpus = R`` semantics on one GPU (``dirichlet/psignn/main.py:106``) -- the list is cut into ``min(R, len(list))``
+    contiguous chunks of near-equal graph count (the first ``len % R`` chunks hold one graph more), each collated to a union
+    batch of its own, and the module is handed the list of them: R independent fixed-point problems solved in lockstep
+    (``ModelDEQDSS.forward`` on a list), every value of the returned ``loss_dic`` of shape ``(R,)``."""
+
+    def __init__(self, module, device_ids=None, output_device=None, replicas=1):
         super().__init__()
+        if int(replicas) < 1:
+            raise ValueError(f"replicas must be >= 1, got {replicas!r}")
         self.module = module
+        self.replicas = int(replicas)
 
     def _device(self):
         return next(self.module.parameters()).device
@@ -52,6 +62,16 @@ class DataParallel(nn.Module):
         if isinstance(data_list, (list, tuple)):
             if len(data_list) == 0:
                 raise ValueError("DataParallel received an empty list of graphs")
+            if self.replicas > 1:
+                graphs, dev = list(data_list), self._device()
+                r = min(self.replicas, len(graphs))
+                base, extra = divmod(len(graphs), r)
+                chunks, at = [], 0
+                for i in range(r):
+                    n = base + (1 if i < extra else 0)
+                    chunks.append(graphs[at] if n == 1 else collate(graphs[at:at + n]))
+                    at += n
+                return self.module([c.to(dev) for c in chunks])
             batch = data_list[0] if len(data_list) == 1 else collate(list(data_list))
         else:
             batch = data_list

@@ -23,6 +23,10 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
   and shapes are identical.
 * ``batch`` is any object with the PyG ``Data`` attributes (see ``data/meshdata.py``), already on the GPU.
+* ``ModelDEQDSS.forward`` also takes a list / tuple of batches: the R replicas of the reference's ``DataParallel`` call
+  (``dirichlet/psignn/main.py:106``), R independent fixed-point problems solved in lockstep
+  (``DeepEquilibrium.train_forward_replicas``; ``loader.DataParallel(net, replicas=R)`` builds the list), every ``loss_dic`` value
+  of shape ``(R,)``.  A single batch behaves as it always did.
 
 The numerical work — encoder/decoder MLPs, the GNN block f, the Broyden root-find, the residual
 SpMV — runs in libpsignn_hip.so.  No torch_geometric / torch_sparse.
@@ -197,6 +201,103 @@ class _DEQFn(torch.autograd.Function):
         return (g_init, None, None, None) + tuple(grads[n] for n in ctx.names)
 
 
+class _ReplicaSlot:
+    """What one replica slot of ``DeepEquilibrium.train_forward_replicas`` keeps between training steps: its forward and
+    adjoint solver (``_fw_solver`` / ``_bw_solver``) and its linearisation handle (``_bw_lin``), keyed and replaced like the
+    single-batch ones of ``DeepEquilibrium``, whose solver-side methods it borrows (so that the sequential fallback is the
+    existing single-mesh route, one slot after the other)."""
+
+    def __init__(self, deq, index):
+        self.f, self.config_deq, self.path_logs = deq.f, deq.config_deq, deq.path_logs
+        self.index, self.sink = index, None
+        self._last_backward = None
+
+    @property
+    def last_backward(self):
+        return self._last_backward
+
+    @last_backward.setter
+    def last_backward(self, out):
+        self._last_backward = out
+        if self.sink is not None:   # the model's per-replica list of this step
+            self.sink[self.index] = out
+
+    def solver(self, which, plan, threshold, hdt, shard_elems):
+        """The slot's ``which`` = "fw" | "bw" solver for (plan, threshold, history dtype, shard size); closed and remade when
+        the key changes."""
+        key = (plan, threshold, hdt, shard_elems)
+        old = getattr(self, f"_{which}_key", None)
+        if old is None or old[0] is not plan or old[1:] != key[1:]:
+            sv = getattr(self, f"_{which}_solver", None)
+            if sv is not None:
+                sv.close()
+            setattr(self, f"_{which}_solver", engine.DeviceBroyden(plan=plan, threshold=threshold, keep_trace=False,
+                                                                  shard_elems=shard_elems, history_dtype=hdt))
+            setattr(self, f"_{which}_key", key)
+        return getattr(self, f"_{which}_solver")
+
+    def close(self):
+        for name in ("_fw_solver", "_bw_solver", "_bw_lin"):
+            obj = getattr(self, name, None)
+            if obj is not None:
+                obj.close()
+                setattr(self, name, None)
+        self._fw_key = self._bw_key = None
+
+
+class _DEQReplicasFn(torch.autograd.Function):
+    """``_DEQFn`` over R replicas at once (the reference's ``DataParallel`` replicas, dirichlet/psignn/main.py:106, each with
+    the backward hook of model.py:210-223): the R forward solves run in lockstep (``engine.broyden_solve_batch``); backward
+    builds R linearisations, each at its H*, and solves the R adjoint fixed points in lockstep
+    (``engine.broyden_solve_adjoint_batch``), then pushes each y_r through one application of f and adds the parameter
+    gradients up in replica order.  Where ``engine.shard_batchable`` / ``engine.adjoint_batchable`` say no, the same solver
+    objects run one mesh after the other."""
+
+    @staticmethod
+    def forward(ctx, deq, batches, names, *tensors):
+        R = len(batches)
+        cfg = deq.config_deq
+        H0s = [t.detach() for t in tensors[:R]]
+        fmaps = [deq.f.bind(h, b) for h, b in zip(H0s, batches)]
+        slots = deq._replica_slots(R)
+        shard = sum(f.plan.N for f in fmaps) * engine.D
+        solvers = [sl.solver("fw", f.plan, cfg["fw_thres"], torch.float32, shard) for sl, f in zip(slots, fmaps)]
+        if engine.shard_batchable(solvers):
+            outs = engine.broyden_solve_batch(solvers, fmaps, cfg["fw_tol"])
+        else:
+            outs = [sv.solve(f, cfg["fw_tol"]) for sv, f in zip(solvers, fmaps)]
+        for o in outs:
+            o.update(eps=cfg["fw_tol"], threshold=cfg["fw_thres"])
+            _log(deq.path_logs, "forward_iteration.csv", "\n{} \t {}".format(o["lowest"], o["nstep"]))
+        deq.last_forward = outs
+        ctx.deq, ctx.fmaps, ctx.names, ctx.slots, ctx.shard = deq, fmaps, names, slots, shard
+        H_stars = [o["result"] for o in outs]
+        ctx.save_for_backward(*H_stars)
+        return tuple(f(h) for f, h in zip(fmaps, H_stars))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        deq, fmaps, slots = ctx.deq, ctx.fmaps, ctx.slots
+        cfg = deq.config_deq
+        H_stars = ctx.saved_tensors
+        gs = [torch.zeros_like(h) if g is None else g.contiguous() for g, h in zip(grads, H_stars)]
+        lins = [sl._linearization(f, h) for sl, f, h in zip(slots, fmaps, H_stars)]
+        solvers = [sl.solver("bw", f.plan, cfg["bw_thres"], torch.float32, ctx.shard) for sl, f in zip(slots, fmaps)]
+        if engine.adjoint_batchable(solvers, lins):
+            outs = engine.broyden_solve_adjoint_batch(solvers, lins, gs, cfg["bw_tol"])
+        else:
+            outs = [sv.solve_adjoint(f, h, g, cfg["bw_tol"], lin=l) for sv, f, h, g, l in zip(solvers, fmaps, H_stars, gs, lins)]
+        total, g_inits = None, []
+        for r, (o, f, h) in enumerate(zip(outs, fmaps, H_stars)):
+            o.update(eps=cfg["bw_tol"], threshold=cfg["bw_thres"])
+            deq.last_backward[r] = o
+            _log(deq.path_logs, "backward_iteration.csv", "\n{} \t {}".format(o["lowest"], o["nstep"]))
+            pg, _, g_init = f.param_vjp_init(h, o["result"])
+            g_inits.append(g_init)
+            total = pg if total is None else {n: total[n] + pg[n] for n in ctx.names}
+        return (None, None, None) + tuple(g_inits) + tuple(total[n] for n in ctx.names)
+
+
 class _JacLossFn(torch.autograd.Function):
     """jac_loss = |v^T J_f(H*)|^2 / (N d) with its gradient w.r.t. the parameters of f: the reference builds the VJP with
     ``create_graph=True`` (jac_loss_estimate, dirichlet/psignn/model.py:416-435) and lets ``loss.backward()`` run the
@@ -284,6 +385,78 @@ class DeepEquilibrium(nn.Module):
                                                linearize=shared)
                 _log(self.path_logs, "spectral_radius.csv", "\n{}".format(sradius.item()))
         return new_H, jac_loss
+
+    # ---- R replicas in one step (the reference's DataParallel call with num_gpus = R, dirichlet/psignn/main.py:106)
+    def _replica_slots(self, R):
+        slots = self.__dict__.setdefault("_slots", [])
+        while len(slots) < R:
+            slots.append(_ReplicaSlot(self, len(slots)))
+        for sl in slots[R:]:   # fewer replicas than before: their device buffers go
+            sl.close()
+        del slots[R:]
+        return slots
+
+    def lockstep_applies(self, fmaps):
+        """Whether R replicas go through the batched solvers: a host-side decision on the bound maps, before anything is
+        allocated.  No: a solver other than ``utilities.solver.broyden``, an untiled plan, ``n_layers > 1``, a bf16 pair
+        history, both families in one call, a mixed plan without ``lin_neumann = "stored"``.  (Solvers of one call share one
+        size class by construction: all are sized for the whole shard.)"""
+        if self.config_deq["solver"] is not _solver.broyden or self.history_dtype() != torch.float32:
+            return False
+        if any(not f.plan.tiled or f.weights.n_layers != 1 or not f.can_linearize() for f in fmaps):
+            return False
+        if any(bool(f.plan.mixed) != bool(fmaps[0].plan.mixed) for f in fmaps):
+            return False
+        return not fmaps[0].plan.mixed or all(f.lin_neumann == "stored" for f in fmaps)
+
+    def train_forward_replicas(self, H_inits, batches, generator=None):
+        """``(list of new_H_star, list of jacobian_loss)`` for R replicas, each an independent fixed-point problem with its own
+        Broyden matrix and stop test -- what the reference's ``DataParallel`` does with ``num_gpus = R``
+        (dirichlet/psignn/main.py:106, training_class.py:156-159), on one GPU.  One autograd function over all replicas: the R
+        forward solves run in lockstep (``engine.broyden_solve_batch``), the backward builds one linearisation per replica at its
+        H* and solves the R adjoint equations in lockstep (``engine.broyden_solve_adjoint_batch``); in this mode the backward is
+        therefore the linearised one whatever ``bw_linearize`` says (it is the only batched product), and the mixed family needs
+        ``lin_neumann = "stored"``.  Where the lockstep does not apply (``lockstep_applies``: solver other than broyden, untiled
+        plan, ``n_layers > 1``, bf16 history, both families, mixed without stored Neumann rows; or ``engine.shard_batchable`` /
+        ``engine.adjoint_batchable`` say no) the replicas are solved one after the other through the single-mesh paths; the
+        result has replica semantics either way.  The Jacobian regulariser stays per replica (``_JacLossFn``), its probes drawn
+        in replica order from ``generator`` and kept as ``last_probes``; ``last_forward`` / ``last_backward`` are lists of the
+        solver dicts, the CSV log lines are written per replica.
+
+        Memory: every replica slot keeps its forward and its adjoint solver between steps, ``2 * thr * N_r * d`` floats each
+        (``thr`` = ``fw_thres`` / ``bw_thres``, ``N_r`` the nodes of replica r's union batch), and one linearisation handle;
+        they are keyed by plan, threshold and history dtype and closed when the key changes."""
+        R = len(batches)
+        if R == 0 or len(H_inits) != R:
+            raise ValueError("train_forward_replicas: one H_init per batch, at least one batch")
+        if not torch.is_grad_enabled():   # validation: the existing branch, one replica after the other
+            pairs, fw = [], []
+            for h, b in zip(H_inits, batches):
+                pairs.append(self.train_forward(h, b, generator=generator))
+                fw.append(self.last_forward)
+            self.last_forward = fw
+            return [p[0] for p in pairs], [p[1] for p in pairs]
+        named = list(self.f.named_parameters())
+        names, params = tuple(n for n, _ in named), [p for _, p in named]
+        fmaps = [self.f.bind(h.detach(), b) for h, b in zip(H_inits, batches)]
+        slots = self._replica_slots(R)
+        self.last_backward = [None] * R
+        if self.lockstep_applies(fmaps):
+            new_Hs = list(_DEQReplicasFn.apply(self, tuple(batches), names, *H_inits, *params))
+        else:
+            new_Hs, fw = [], []
+            for sl, h, b in zip(slots, H_inits, batches):
+                sl.sink = self.last_backward
+                new_Hs.append(_DEQFn.apply(h, sl, b, names, *params))
+                fw.append(sl.last_forward)
+            self.last_forward = fw
+        H_stars = [o["result"] for o in self.last_forward]
+        self.last_probes, jac = [], []
+        for f, h in zip(fmaps, H_stars):
+            v = torch.randn(h.shape, device=h.device, generator=generator)
+            self.last_probes.append(v)
+            jac.append(_JacLossFn.apply(f, h, v, names, *params))
+        return new_Hs, jac
 
     # ---- adjoint side of the reference's training variant (dirichlet/psignn/model.py:204-241), on the VJP kernel
     def _linearization(self, fmap, H_star):
@@ -377,6 +550,11 @@ class DeepEquilibrium(nn.Module):
             val = (vj * ev).sum() / (ev * ev).sum()
             ev = vj / vj.norm()
         return from_p(ev), val.abs()
+
+
+for _name in ("history_dtype", "_linearization", "_linearize_default", "implicit_backward"):
+    setattr(_ReplicaSlot, _name, getattr(DeepEquilibrium, _name))
+del _name
 
 
 # ----------------------------------------------------------------------------------------------
@@ -500,6 +678,8 @@ class ModelDEQDSS(_Base):
     ``inference``, ``iterative_inference``."""
 
     def forward(self, batch):
+        if isinstance(batch, (list, tuple)):
+            return self._forward_replicas(list(batch))
         if self.training and torch.is_grad_enabled():
             return self._train_forward(batch)
         with torch.no_grad():  # validation branch of DeepEquilibrium.forward (model.py:227-241): one more f on H*
@@ -532,6 +712,35 @@ class ModelDEQDSS(_Base):
                     "autoencoder_loss": autoencoder_loss, "mse_loss": self.mse_loss(u_final, batch.sol),
                     "mse_dirichlet": self.mse_loss(u_final[idx, :], batch.x[idx, :])}
         return u_final, loss_dic
+
+    def _forward_replicas(self, batches):
+        """A list of R union batches = the R replicas of the reference's ``DataParallel`` call (dirichlet/psignn/main.py:106):
+        ``(list of u_final, loss_dic)`` with every value of ``loss_dic`` stacked to shape ``(R,)`` -- what PyG's gather hands
+        the trainer, whose ``.mean()`` makes the parameter gradient the mean of the replicas' gradients.  Training mode with
+        gradients: ``DeepEquilibrium.train_forward_replicas``; otherwise each batch through the validation branch."""
+        if len(batches) == 0:
+            raise ValueError("forward received an empty list of batches")
+        if not (self.training and torch.is_grad_enabled()):
+            outs = [self.forward(b) for b in batches]
+            keys = outs[0][1].keys()
+            return [u for u, _ in outs], {k: torch.stack([torch.as_tensor(d[k], device=u.device) for u, d in outs]) for k in keys}
+        ae = self.autoencoder
+        for b in batches:
+            nat.require_cuda(b.x, "batch.x")
+        h_inits = [ae.encoder(b.x) for b in batches]
+        h_finals, jac = self.deqdss.train_forward_replicas(h_inits, batches)
+        us, dics = [], []
+        for batch, h_final, jacobian_loss in zip(batches, h_finals, jac):   # per replica the terms of _train_forward
+            u_final = ae.decoder(h_final)
+            u_d, h_d = u_final.detach(), h_final.detach()
+            idx = torch.where(batch.tags == 1)[0]
+            dics.append({"residual_loss": self.residual_loss(u_final, batch), "jacobian_loss": jacobian_loss,
+                         "encoder_loss": self.mse_loss(ae.encoder(u_d), h_d),
+                         "autoencoder_loss": self.mse_loss(ae.decoder(ae.encoder(u_d).detach()), u_d),
+                         "mse_loss": self.mse_loss(u_final, batch.sol),
+                         "mse_dirichlet": self.mse_loss(u_final[idx, :], batch.x[idx, :])})
+            us.append(u_final)
+        return us, {k: torch.stack([d[k] for d in dics]) for k in dics[0]}
 
     def iterative_inference(self, batch):
         return self._iterative(batch)
