@@ -11,8 +11,10 @@
  * PSIGNN_E* code; psignn_last_error() returns a message for the calling thread.
  *
  * Unless stated otherwise calls are asynchronous on `stream` and perform no host sync.
- * Tensors are dense row-major float32; node states are (N, 10) — the latent width d = 10 is
- * the only value the reference ever trains (SURVEY.md "d") and is fixed at compile time.
+ * Tensors are dense row-major float32; node states are (N, d) — the latent width d is fixed at
+ * compile time (PSIGNN_D).  d = 10 is the only value the reference ever trains (SURVEY.md "d") and
+ * is what libpsignn_hip.so is built for; libpsignn_hip_d<w>.so is the same source built with
+ * -DPSIGNN_D=<w> (even widths from 4 to 16) and holds the forward-inference entry points only.
  */
 #ifndef PSIGNN_HIP_H
 #define PSIGNN_HIP_H
@@ -24,7 +26,9 @@
 extern "C" {
 #endif
 
+#ifndef PSIGNN_D
 #define PSIGNN_D 10            /* latent_dim */
+#endif
 #define PSIGNN_EDGE_F 3        /* edge_features_dim */
 
 #define PSIGNN_OK 0
@@ -35,6 +39,9 @@ extern "C" {
 
 const char* psignn_last_error(void);
 int psignn_version(void);
+/* The latent width this library was compiled for (PSIGNN_D): 10 for libpsignn_hip.so.  A weight buffer, a state or a
+ * solver made for one width must never reach a library of another; psignn_weights_size() reports this width's total. */
+int psignn_latent_dim(void);
 /* Re-read the PSIGNN_* environment knobs at their next use (they are cached after the first read).  The knobs select
  * alternative forms of a kernel for A/B measurements and tests (MFMA stage 1, Hilbert tiling, gather kernels for the mixed
  * family, ...); a normal run sets none of them.  No reference counterpart. */

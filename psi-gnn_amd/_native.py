@@ -14,7 +14,37 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpsignn_hip.so")
 
-D = 10
+D = 10   # the default latent width: libpsignn_hip.so, every entry point
+# Other widths: libpsignn_hip_d<w>.so, the forward translation units built once more with -DPSIGNN_D=<w> (csrc/Makefile).  They
+# hold forward inference only -- f, the solvers that need only f -- and ``lib(w)`` binds what they export.
+SUPPORTED_WIDTHS = (8, 10, 16)
+
+
+def lib_path(width: int = D) -> str:
+    return LIB_PATH if width == D else os.path.join(_HERE, f"libpsignn_hip_d{int(width)}.so")
+
+
+def check_width(width) -> int:
+    """``width`` as an int if a library is built for it, NativeError naming the supported widths otherwise."""
+    try:
+        ok = int(width) == width and int(width) in SUPPORTED_WIDTHS
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise NativeError(f"latent_dim {width!r} is not supported: the HIP kernels are built for latent_dim in {SUPPORTED_WIDTHS} "
+                          f"({D}: everything; the others: forward inference only)")
+    return int(width)
+
+
+def forward_only_error(width, what) -> "NativeError":
+    return NativeError(f"{what}: latent_dim {width} has forward inference only (f, the encoder / decoder and the solvers that need "
+                       f"only f); derivatives, training and the baselines exist at latent_dim {D}")
+
+
+def require_default_width(width, what):
+    """Raise the "forward inference only" error unless ``width`` is the default one.  Host side, before any native call."""
+    if int(width) != D:
+        raise forward_only_error(width, what)
 
 
 class NativeError(RuntimeError):
@@ -34,6 +64,7 @@ _INT = C.c_int
 SIGNATURES = {
     "psignn_last_error": (C.c_char_p, []),
     "psignn_version": (_INT, []),
+    "psignn_latent_dim": (_INT, []),
     "psignn_plan_create": (_INT, [C.POINTER(_P), _I64, _I64, _P, _P, _P, _P, _INT, _P, _INT, _P]),
     "psignn_plan_is_tiled": (_INT, [_P]),
     "psignn_plan_num_tiles": (_I64, [_P]),
@@ -153,40 +184,41 @@ SIGNATURES = {
 }
 
 
-def prof_enable(on: bool):
-    lib().psignn_prof_enable(int(on))
+def prof_enable(on: bool, width: int = D):
+    """Launch records of the library of ``width`` (each library keeps its own)."""
+    lib(width).psignn_prof_enable(int(on))
 
 
-def prof_collect(with_bytes=False):
-    """{kernel name: (calls, total_ms)} of everything launched since the last collect (HIP events); ``with_bytes``:
-    (calls, total_ms, algorithmic bytes as stated at the launch sites)."""
-    l = lib()
+def prof_collect(with_bytes=False, width: int = D):
+    """{kernel name: (calls, total_ms)} of everything the library of ``width`` launched since the last collect (HIP events);
+    ``with_bytes``: (calls, total_ms, algorithmic bytes as stated at the launch sites)."""
+    l = lib(width)
     out = {}
     for i in range(l.psignn_prof_collect()):
         name = C.create_string_buffer(64)
         calls, ms, byts = _I64(0), C.c_double(0.0), _I64(0)
-        check(l.psignn_prof_get2(i, name, 64, C.byref(calls), C.byref(ms), C.byref(byts)), "psignn_prof_get2")
+        check(l.psignn_prof_get2(i, name, 64, C.byref(calls), C.byref(ms), C.byref(byts)), "psignn_prof_get2", l)
         out[name.value.decode()] = (int(calls.value), float(ms.value), int(byts.value)) if with_bytes else (int(calls.value), float(ms.value))
     return out
 
-def prof_launch_log():
+def prof_launch_log(width: int = D):
     """[(kernel name, ms, algorithmic bytes)] of the launches of the last ``prof_collect``, in launch order."""
-    l = lib()
+    l = lib(width)
     out = []
     for i in range(l.psignn_prof_launch(0, None, 0, None, None)):
         name = C.create_string_buffer(64)
         ms, byts = C.c_double(0.0), _I64(0)
-        check(l.psignn_prof_launch(i, name, 64, C.byref(ms), C.byref(byts)), "psignn_prof_launch")
+        check(l.psignn_prof_launch(i, name, 64, C.byref(ms), C.byref(byts)), "psignn_prof_launch", l)
         out.append((name.value.decode(), float(ms.value), int(byts.value)))
     return out
 
 
-_lib = None
+_libs = {}   # latent width -> loaded library
 
 
-def _build_once():
-    """A source checkout without the built library (the .so is kept out of git): compile it in place when hipcc is there.
-    Nothing else is attempted -- without the library every entry point raises."""
+def _build_once(path=LIB_PATH):
+    """A source checkout without the built libraries (the .so files are kept out of git): compile them in place when hipcc is
+    there (one make builds every width).  Nothing else is attempted -- without the library every entry point raises."""
     import shutil
     import subprocess
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -196,37 +228,54 @@ def _build_once():
     import fcntl
     with open(os.path.join(csrc, ".build.lock"), "w") as lock:   # one builder when several ranks start together
         fcntl.flock(lock, fcntl.LOCK_EX)
-        if not os.path.exists(LIB_PATH):
-            print(f"[psi-gnn_amd] {os.path.basename(LIB_PATH)} missing: building it with {hipcc} (make -C {csrc})", flush=True)
+        if not os.path.exists(path):
+            print(f"[psi-gnn_amd] {os.path.basename(path)} missing: building it with {hipcc} (make -C {csrc})", flush=True)
             r = subprocess.run(["make", "-C", csrc, "-j8", f"HIPCC={hipcc}"], stdout=subprocess.PIPE,
                                stderr=subprocess.STDOUT, text=True)
-            if r.returncode != 0 or not os.path.exists(LIB_PATH):
-                raise NativeError(f"building {LIB_PATH} failed (make exit code {r.returncode}); last lines of its output:\n"
+            if r.returncode != 0 or not os.path.exists(path):
+                raise NativeError(f"building {path} failed (make exit code {r.returncode}); last lines of its output:\n"
                                   + "\n".join(r.stdout.splitlines()[-25:]))
 
 
-def lib():
-    """Load the shared library (once).  Raises NativeError if it has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            _build_once()
-        if not os.path.exists(LIB_PATH):
+def _absent(name, width):
+    def raise_forward_only(*args, **kwargs):
+        raise forward_only_error(width, name)
+    return raise_forward_only
+
+
+def lib(width: int = D):
+    """Load the shared library of a latent width (once each; ``lib()`` is the default width's, with every entry point).  A width
+    library binds the entry points it exports; any other name of ``SIGNATURES`` raises the "forward inference only" error when
+    called.  Raises NativeError for an unsupported width or if the library has not been built."""
+    l = _libs.get(width)
+    if l is None:
+        width = check_width(width)
+        path = lib_path(width)
+        if not os.path.exists(path):
+            _build_once(path)
+        if not os.path.exists(path):
             raise NativeError(
-                f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C psi-gnn_amd/csrc`.  There is no CPU fallback for the HIP path.")
-        l = C.CDLL(LIB_PATH)
+        l = C.CDLL(path)
         for name, (res, args) in SIGNATURES.items():
+            if width != D and not hasattr(l, name):
+                setattr(l, name, _absent(name, width))
+                continue
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
-        _lib = l
-    return _lib
+        if l.psignn_latent_dim() != width:
+            raise NativeError(f"{path} was built for latent_dim {l.psignn_latent_dim()}, not {width}")
+        l.width = width
+        _libs[width] = l
+    return l
 
 
-def check(rc: int, what: str = ""):
+def check(rc: int, what: str = "", l=None):
+    """``l``: the library the call went to (each keeps its own last-error text); the default width's when omitted."""
     if rc != 0:
-        msg = lib().psignn_last_error().decode("utf-8", "replace")
+        msg = (l or lib()).psignn_last_error().decode("utf-8", "replace")
         raise NativeError(f"{what} failed (code {rc}): {msg}")
 
 

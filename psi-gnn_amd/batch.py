@@ -70,8 +70,9 @@ def solve_shard_batched(model, meshes, device, indices=None, group=8):
             if (cfg["solver"] is slv.broyden and len(ids) > 1 and all(f.plan.tiled for f in fmaps)
                     and cfg.get("broyden_history_dtype", torch.float32) == torch.float32
                     and len({f.plan.mixed for f in fmaps}) == 1 and fmaps[0].weights.n_layers == 1):
-                total = sum(f.plan.N for f in fmaps) * eng.D
-                solvers = [eng.DeviceBroyden(plan=f.plan, threshold=cfg["fw_thres"], keep_trace=False, shard_elems=total)
+                total = sum(f.plan.N for f in fmaps) * fmaps[0].width
+                solvers = [eng.DeviceBroyden(plan=f.plan, threshold=cfg["fw_thres"], keep_trace=False, shard_elems=total,
+                                             width=f.width)
                            for f in fmaps]
                 try:
                     if eng.shard_batchable(solvers):

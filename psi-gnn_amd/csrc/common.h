@@ -7,6 +7,12 @@
 #include "../../include/psignn_hip.h"
 
 #define D PSIGNN_D
+// The latent width is a compile-time constant.  libpsignn_hip.so is built for 10 (every derivative kernel exists at that width
+// only); libpsignn_hip_d<w>.so compiles the forward translation units again for another even width (Makefile).  Rows of D floats
+// move as D/2 float2 (global) or as 16-byte quads (LDS), and the packed-fp32 node arithmetic holds a row as NPAIR = D/2 register
+// pairs -- hence even; the upper bound keeps the row arrays of the tile kernel (8 live NPAIR-pair vectors) inside the register file.
+static_assert(D % 2 == 0 && D >= 4 && D <= 16, "PSIGNN_D: an even latent width from 4 to 16");
+#define NPAIR (D / 2)   // register pairs of one latent row
 
 void psignn_set_error(const char* fmt, ...);
 
@@ -42,10 +48,11 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------------------------------------
 // Weight pack layout (floats).  All blocks are nn.Linear (out,in) row-major.
-//   shared : ln_gamma[10] ln_beta[10] alpha_w[30+P] alpha_b[1]            (padded to SHARED_SZ)
+// Written for D = 10 (the numbers in brackets); every size and offset is an expression in D:
+//   shared : ln_gamma[D] ln_beta[D] alpha_w[3D+P] alpha_b[1]              (padded to SHARED_SZ, a multiple of 16: 64)
 //   layer l: phi_to{W1[10x23] b1[10] W2[10x10] b2[10]}  phi_from{...}  update{U1[10x(30+P)] c1[10] U2[10x10] c2[10]}
-//            fold{G_to[10x10] g_to[10] G_fr[10x10] g_fr[10] a_to[10] a_fr[10] ab_to ab_fr}          (FOLD_SZ 244)
-//   mixed  : phi_neu{...350}  upd_neu{N1[10x25] n1[10] N2[10x10] n2[10]}  nfold{G_n[10x10] g_n[10]} (NFOLD_SZ 112)
+//            fold{G_to[10x10] g_to[10] G_fr[10x10] g_fr[10] a_to[10] a_fr[10] ab_to ab_fr}          (FOLD_SZ 244: padded to 4)
+//   mixed  : phi_neu{...350}  upd_neu{N1[10x25] n1[10] N2[10x10] n2[10]}  nfold{G_n[10x10] g_n[10]} (NFOLD_SZ 112: padded to 4)
 // P = second_member_dim = 2 (dirichlet) / 3 (mixed).
 // fold blocks are derived on the host (engine.pack_weights): the second Phi layer is linear, so
 //   U1[:, mp_to cols] (W2_to S + deg b2_to) = G_to S + deg g_to   with G_to = U1_to W2_to, g_to = U1_to b2_to
@@ -55,17 +62,18 @@ template <int P>
 struct WLayout {
   static constexpr int CAT = 3 * D + P;       // 32 / 33
   static constexpr int EIN = 2 * D + 3;       // 23
-  static constexpr int LN_G = 0, LN_B = 10, AL_W = 20, AL_B = 20 + CAT;
-  static constexpr int SHARED_SZ = 64;
+  static constexpr int LN_G = 0, LN_B = D, AL_W = 2 * D, AL_B = 2 * D + CAT;
+  static constexpr int SHARED_SZ = (2 * D + 3 * D + 3 + 1 + 15) / 16 * 16;   // sized for P = 3 in both families: 64
   static constexpr int PHI_SZ = D * EIN + D + D * D + D;  // 350
   static constexpr int PHI_W1 = 0, PHI_B1 = D * EIN, PHI_W2 = D * EIN + D, PHI_B2 = D * EIN + D + D * D;
   static constexpr int UPD_SZ = D * CAT + D + D * D + D;
   static constexpr int UPD_W1 = 0, UPD_B1 = D * CAT, UPD_W2 = D * CAT + D, UPD_B2 = D * CAT + D + D * D;
-  static constexpr int FOLD_SZ = 244;
-  static constexpr int F_GTO = 0, F_gTO = 100, F_GFR = 110, F_gFR = 210, F_ATO = 220, F_AFR = 230, F_ABTO = 240, F_ABFR = 241;
+  static constexpr int F_GTO = 0, F_gTO = D * D, F_GFR = D * D + D, F_gFR = 2 * D * D + D, F_ATO = 2 * D * D + 2 * D,
+                       F_AFR = 2 * D * D + 3 * D, F_ABTO = 2 * D * D + 4 * D, F_ABFR = 2 * D * D + 4 * D + 1;
+  static constexpr int FOLD_SZ = (2 * D * D + 4 * D + 2 + 3) / 4 * 4;
   static constexpr int LAYER_SZ = 2 * PHI_SZ + UPD_SZ + FOLD_SZ;
   static constexpr int L_TO = 0, L_FROM = PHI_SZ, L_UPD = 2 * PHI_SZ, L_FOLD = 2 * PHI_SZ + UPD_SZ;
-  static constexpr int NFOLD_SZ = 112, NF_G = 0, NF_g = 100;
+  static constexpr int NFOLD_SZ = (D * D + D + 3) / 4 * 4, NF_G = 0, NF_g = D * D;
   static constexpr int NEU_CAT = 2 * D + P + 2;  // 25 (mixed only)
   static constexpr int NEU_SZ = D * NEU_CAT + D + D * D + D;
   static constexpr int NEU_W1 = 0, NEU_B1 = D * NEU_CAT, NEU_W2 = D * NEU_CAT + D, NEU_B2 = D * NEU_CAT + D + D * D;
@@ -79,17 +87,31 @@ struct WLayout {
   // ---- transposed section (tile kernel): every matrix again as [in k][out o], o fastest, so that the outputs
   // (o, o+1) of one input k are adjacent -> one SGPR pair feeds a v_pk_fma_f32.  FP32 peak on CDNA needs the
   // packed form; the scalar form issues at half the rate.  Derived on the host (engine.pack_weights).
-  static constexpr int T_W1J_TO = 0, T_W1J_FR = 100, T_W1I_TO = 200, T_W1I_FR = 300, T_A_TO = 400, T_A_FR = 430,
-                       T_B1_TO = 460, T_B1_FR = 470, T_U1H = 480, T_GTO = 580, T_GFR = 680, T_U1P = 780, T_HB = 810,
-                       T_gTO = 820, T_gFR = 830, T_U2 = 840, T_C2 = 940, TPL_SZ = 950;
-  static constexpr int N_W1J = 0, N_W1I = 100, N_A = 200, N_B1 = 230, N_N1H = 240, N_GN = 340, N_N1P = 440,
-                       N_NB1 = 490, N_gN = 500, N_N2 = 510, N_NB2 = 610, TPN_SZ = 620;
+  // Blocks: D x D matrices, 3 x D edge-attr blocks, D-vectors; U1P / N1P hold 3 / 5 input rows in both families (P <= 3).
+  static constexpr int DD = D * D;
+  static constexpr int T_W1J_TO = 0, T_W1J_FR = DD, T_W1I_TO = 2 * DD, T_W1I_FR = 3 * DD, T_A_TO = 4 * DD,
+                       T_A_FR = T_A_TO + 3 * D, T_B1_TO = T_A_FR + 3 * D, T_B1_FR = T_B1_TO + D, T_U1H = T_B1_FR + D,
+                       T_GTO = T_U1H + DD, T_GFR = T_GTO + DD, T_U1P = T_GFR + DD, T_HB = T_U1P + 3 * D, T_gTO = T_HB + D,
+                       T_gFR = T_gTO + D, T_U2 = T_gFR + D, T_C2 = T_U2 + DD, TPL_SZ = T_C2 + D;
+  static constexpr int N_W1J = 0, N_W1I = DD, N_A = 2 * DD, N_B1 = N_A + 3 * D, N_N1H = N_B1 + D, N_GN = N_N1H + DD,
+                       N_N1P = N_GN + DD, N_NB1 = N_N1P + 5 * D, N_gN = N_NB1 + D, N_N2 = N_gN + D, N_NB2 = N_N2 + DD,
+                       TPN_SZ = N_NB2 + D;
   __host__ __device__ static constexpr int tp_layer(int nl, bool mixed, int l) { return base_total(nl, mixed) + l * TPL_SZ; }
   __host__ __device__ static constexpr int tp_neu(int nl) { return base_total(nl, true) + nl * TPL_SZ; }
   __host__ __device__ static constexpr int total(int nl, bool mixed) {
     return base_total(nl, mixed) + nl * TPL_SZ + (mixed ? TPN_SZ : 0);
   }
 };
+#if PSIGNN_D == 10   // the layout every derivative kernel, test and stored profile was written against
+static_assert(WLayout<2>::SHARED_SZ == 64 && WLayout<3>::AL_B == 53 && WLayout<2>::PHI_SZ == 350 && WLayout<2>::FOLD_SZ == 244 &&
+              WLayout<2>::F_ABFR == 241 && WLayout<3>::NFOLD_SZ == 112 && WLayout<2>::LAYER_SZ == 1384 && WLayout<3>::LAYER_SZ == 1394 &&
+              WLayout<2>::T_U1P == 780 && WLayout<2>::T_C2 == 940 && WLayout<2>::TPL_SZ == 950 && WLayout<3>::N_NB1 == 490 &&
+              WLayout<3>::TPN_SZ == 620 && WLayout<2>::total(1, false) == 2398 && WLayout<3>::total(1, true) == 3860,
+              "weight layout at D = 10");
+#endif
+// every block of the transposed section starts on an 8-byte boundary (read as float2 pairs)
+static_assert(WLayout<2>::total(1, false) % 2 == 0 && WLayout<3>::base_total(1, true) % 2 == 0 && WLayout<2>::LAYER_SZ % 2 == 0,
+              "transposed weight blocks are read as float2");
 
 // Iteration-invariant pointers of a tiled plan, kept in DEVICE memory and handed to the tile kernels as one pointer.
 // As separate kernel arguments they are all live from the kernel's first instruction; the f kernel needs ~60 SGPRs for

@@ -18,7 +18,7 @@
 
 // ------------------------------------------------------------------------------------------
 // Kernel 1: neighbour-side projections.  NPH = number of Phi modules (2 dirichlet, 3 mixed).
-// Pj row layout: [to(10) | from(10) | neu(10)]; with JVP the tangent rows follow at +N*NPH*10.
+// Pj row layout: [to(D) | from(D) | neu(D)]; with JVP the tangent rows follow at +N*NPH*D.
 // ------------------------------------------------------------------------------------------
 template <int P, bool MIXED, bool JVP>
 __global__ __launch_bounds__(256) void k_project(int64_t N, const float* __restrict__ W, int lofs, int nofs,
@@ -31,26 +31,26 @@ __global__ __launch_bounds__(256) void k_project(int64_t N, const float* __restr
   if (n >= N) return;
   if (hsel) h += (int64_t)(*hsel) * hstride;  // iterate buffer chosen on the device (solver.hip)
   float x[D], t[D];
-  load10(h + n * D, x);
+  loadD(h + n * D, x);
   float* row = Pj + n * (NPH * D);
-  matvec10<D, false>(W + lofs + L::L_TO + L::PHI_W1, L::EIN, D, x, t);
-  store10(row, t);
-  matvec10<D, false>(W + lofs + L::L_FROM + L::PHI_W1, L::EIN, D, x, t);
-  store10(row + D, t);
+  matvecD<D, false>(W + lofs + L::L_TO + L::PHI_W1, L::EIN, D, x, t);
+  storeD(row, t);
+  matvecD<D, false>(W + lofs + L::L_FROM + L::PHI_W1, L::EIN, D, x, t);
+  storeD(row + D, t);
   if (MIXED) {
-    matvec10<D, false>(W + nofs + L::PHI_W1, L::EIN, D, x, t);
-    store10(row + 2 * D, t);
+    matvecD<D, false>(W + nofs + L::PHI_W1, L::EIN, D, x, t);
+    storeD(row + 2 * D, t);
   }
   if (JVP) {
-    load10(v + n * D, x);
+    loadD(v + n * D, x);
     float* drow = Pj + (N + n) * (NPH * D);
-    matvec10<D, false>(W + lofs + L::L_TO + L::PHI_W1, L::EIN, D, x, t);
-    store10(drow, t);
-    matvec10<D, false>(W + lofs + L::L_FROM + L::PHI_W1, L::EIN, D, x, t);
-    store10(drow + D, t);
+    matvecD<D, false>(W + lofs + L::L_TO + L::PHI_W1, L::EIN, D, x, t);
+    storeD(drow, t);
+    matvecD<D, false>(W + lofs + L::L_FROM + L::PHI_W1, L::EIN, D, x, t);
+    storeD(drow + D, t);
     if (MIXED) {
-      matvec10<D, false>(W + nofs + L::PHI_W1, L::EIN, D, x, t);
-      store10(drow + 2 * D, t);
+      matvecD<D, false>(W + nofs + L::PHI_W1, L::EIN, D, x, t);
+      storeD(drow + 2 * D, t);
     }
   }
 }
@@ -72,8 +72,8 @@ __device__ __forceinline__ void seg_sum(int32_t beg, int32_t end, const int32_t*
     int64_t u = nbr[i];
     float a0 = attr[3 * (int64_t)i], a1 = attr[3 * (int64_t)i + 1], a2 = attr[3 * (int64_t)i + 2];
     float pj[D], dpj[D];
-    load10(Pj + u * (NPH * D) + col, pj);
-    if (JVP) load10(Pj + (N + u) * (NPH * D) + col, dpj);
+    loadD(Pj + u * (NPH * D) + col, pj);
+    if (JVP) loadD(Pj + (N + u) * (NPH * D) + col, dpj);
 #pragma unroll
     for (int o = 0; o < D; ++o) {
       float z = Pi[o] + pj[o];
@@ -113,15 +113,15 @@ __global__ __launch_bounds__(256) void k_node(int64_t N, const float* __restrict
 #pragma unroll
       for (int o = 0; o < D; ++o) r[o] = 0.f;
     } else {
-      load10(h0 + n * D, r);
+      loadD(h0 + n * D, r);
     }
-    store10(out + n * D, r);
+    storeD(out + n * D, r);
     return;
   }
   if (hsel) h += (int64_t)(*hsel) * hstride;
   float x[D], dx[D];
-  load10(h + n * D, x);
-  if (JVP) load10(v + n * D, dx);
+  loadD(h + n * D, x);
+  if (JVP) loadD(v + n * D, dx);
 
   const float* Wto = W + lofs + L::L_TO;
   const float* Wfr = W + lofs + L::L_FROM;
@@ -132,32 +132,32 @@ __global__ __launch_bounds__(256) void k_node(int64_t N, const float* __restrict
   {
 #pragma unroll
     for (int o = 0; o < D; ++o) Pi[o] = Wto[L::PHI_B1 + o];
-    matvec10<D, true>(Wto + L::PHI_W1, L::EIN, 0, x, Pi);
-    if (JVP) matvec10<D, false>(Wto + L::PHI_W1, L::EIN, 0, dx, dPi);
+    matvecD<D, true>(Wto + L::PHI_W1, L::EIN, 0, x, Pi);
+    if (JVP) matvecD<D, false>(Wto + L::PHI_W1, L::EIN, 0, dx, dPi);
     int32_t b = csc_ptr[n], e = csc_ptr[n + 1];
     seg_sum<NPH, JVP>(b, e, csc_nbr, csc_attr, Wto + L::PHI_W1, L::EIN, Pj, N, 0, Pi, dPi, S, dS);
     float deg = (float)(e - b);
 #pragma unroll
     for (int o = 0; o < D; ++o) mp_to[o] = deg * Wto[L::PHI_B2 + o];
-    matvec10<D, true>(Wto + L::PHI_W2, D, 0, S, mp_to);
-    if (JVP) matvec10<D, false>(Wto + L::PHI_W2, D, 0, dS, dmp_to);
+    matvecD<D, true>(Wto + L::PHI_W2, D, 0, S, mp_to);
+    if (JVP) matvecD<D, false>(Wto + L::PHI_W2, D, 0, dS, dmp_to);
   }
   // ---- Phi_from: aggregate at the row index over the node's out-edges (CSR)
   const int32_t rb = csr_ptr[n], re = csr_ptr[n + 1];
   {
 #pragma unroll
     for (int o = 0; o < D; ++o) Pi[o] = Wfr[L::PHI_B1 + o];
-    matvec10<D, true>(Wfr + L::PHI_W1, L::EIN, 0, x, Pi);
-    if (JVP) matvec10<D, false>(Wfr + L::PHI_W1, L::EIN, 0, dx, dPi);
+    matvecD<D, true>(Wfr + L::PHI_W1, L::EIN, 0, x, Pi);
+    if (JVP) matvecD<D, false>(Wfr + L::PHI_W1, L::EIN, 0, dx, dPi);
     seg_sum<NPH, JVP>(rb, re, csr_nbr, csr_attr, Wfr + L::PHI_W1, L::EIN, Pj, N, D, Pi, dPi, S, dS);
     float deg = (float)(re - rb);
 #pragma unroll
     for (int o = 0; o < D; ++o) mp_fr[o] = deg * Wfr[L::PHI_B2 + o];
-    matvec10<D, true>(Wfr + L::PHI_W2, D, 0, S, mp_fr);
-    if (JVP) matvec10<D, false>(Wfr + L::PHI_W2, D, 0, dS, dmp_fr);
+    matvecD<D, true>(Wfr + L::PHI_W2, D, 0, S, mp_fr);
+    if (JVP) matvecD<D, false>(Wfr + L::PHI_W2, D, 0, dS, dmp_fr);
   }
-  if (mp_out && mp_which == 0) { store10(mp_out + n * D, mp_to); return; }
-  if (mp_out && mp_which == 1) { store10(mp_out + n * D, mp_fr); return; }
+  if (mp_out && mp_which == 0) { storeD(mp_out + n * D, mp_to); return; }
+  if (mp_out && mp_which == 1) { storeD(mp_out + n * D, mp_fr); return; }
 
   float y[D], dy[D];
   bool neumann = MIXED && (fl & FLAG_NEUMANN);
@@ -168,40 +168,40 @@ __global__ __launch_bounds__(256) void k_node(int64_t N, const float* __restrict
     float mp_n[D], dmp_n[D];
 #pragma unroll
     for (int o = 0; o < D; ++o) Pi[o] = Wn[L::PHI_B1 + o];
-    matvec10<D, true>(Wn + L::PHI_W1, L::EIN, 0, x, Pi);
-    if (JVP) matvec10<D, false>(Wn + L::PHI_W1, L::EIN, 0, dx, dPi);
+    matvecD<D, true>(Wn + L::PHI_W1, L::EIN, 0, x, Pi);
+    if (JVP) matvecD<D, false>(Wn + L::PHI_W1, L::EIN, 0, dx, dPi);
     seg_sum<NPH, JVP>(rb, re, csr_nbr, csr_attr, Wn + L::PHI_W1, L::EIN, Pj, N, 2 * D, Pi, dPi, S, dS);
     float deg = (float)(re - rb);
 #pragma unroll
     for (int o = 0; o < D; ++o) mp_n[o] = deg * Wn[L::PHI_B2 + o];
-    matvec10<D, true>(Wn + L::PHI_W2, D, 0, S, mp_n);
-    if (JVP) matvec10<D, false>(Wn + L::PHI_W2, D, 0, dS, dmp_n);
-    if (mp_out) { store10(mp_out + n * D, mp_n); return; }
+    matvecD<D, true>(Wn + L::PHI_W2, D, 0, S, mp_n);
+    if (JVP) matvecD<D, false>(Wn + L::PHI_W2, D, 0, dS, dmp_n);
+    if (mp_out) { storeD(mp_out + n * D, mp_n); return; }
     // cat_n = [h | mp_neu | prb(3) | normal(2)]
     float hid[D], dhid[D];
 #pragma unroll
     for (int o = 0; o < D; ++o) hid[o] = Un[L::NEU_B1 + o];
-    matvec10<D, true>(Un + L::NEU_W1, L::NEU_CAT, 0, x, hid);
-    matvec10<D, true>(Un + L::NEU_W1, L::NEU_CAT, D, mp_n, hid);
+    matvecD<D, true>(Un + L::NEU_W1, L::NEU_CAT, 0, x, hid);
+    matvecD<D, true>(Un + L::NEU_W1, L::NEU_CAT, D, mp_n, hid);
     float pq[P + 2];
 #pragma unroll
     for (int k = 0; k < P; ++k) pq[k] = prb[n * P + k];
     pq[P] = nrm[n * 2];
     pq[P + 1] = nrm[n * 2 + 1];
-    matvec10<P + 2, true>(Un + L::NEU_W1, L::NEU_CAT, 2 * D, pq, hid);
+    matvecD<P + 2, true>(Un + L::NEU_W1, L::NEU_CAT, 2 * D, pq, hid);
     if (JVP) {
-      matvec10<D, false>(Un + L::NEU_W1, L::NEU_CAT, 0, dx, dhid);
-      matvec10<D, true>(Un + L::NEU_W1, L::NEU_CAT, D, dmp_n, dhid);
+      matvecD<D, false>(Un + L::NEU_W1, L::NEU_CAT, 0, dx, dhid);
+      matvecD<D, true>(Un + L::NEU_W1, L::NEU_CAT, D, dmp_n, dhid);
 #pragma unroll
       for (int o = 0; o < D; ++o) dhid[o] = hid[o] > 0.f ? dhid[o] : 0.f;
-      matvec10<D, false>(Un + L::NEU_W2, D, 0, dhid, dy);
+      matvecD<D, false>(Un + L::NEU_W2, D, 0, dhid, dy);
     }
 #pragma unroll
     for (int o = 0; o < D; ++o) {
       hid[o] = fmaxf(hid[o], 0.f);
       y[o] = Un[L::NEU_B2 + o];
     }
-    matvec10<D, true>(Un + L::NEU_W2, D, 0, hid, y);
+    matvecD<D, true>(Un + L::NEU_W2, D, 0, hid, y);
   } else {
     // ---- gate + update MLP on cat = [h | mp_to | mp_from | prb]
     const float* Wu = W + lofs + L::L_UPD;
@@ -222,10 +222,10 @@ __global__ __launch_bounds__(256) void k_node(int64_t N, const float* __restrict
     float hid[D], dhid[D], upd[D];
 #pragma unroll
     for (int o = 0; o < D; ++o) hid[o] = Wu[L::UPD_B1 + o];
-    matvec10<D, true>(Wu + L::UPD_W1, L::CAT, 0, x, hid);
-    matvec10<D, true>(Wu + L::UPD_W1, L::CAT, D, mp_to, hid);
-    matvec10<D, true>(Wu + L::UPD_W1, L::CAT, 2 * D, mp_fr, hid);
-    matvec10<P, true>(Wu + L::UPD_W1, L::CAT, 3 * D, pq, hid);
+    matvecD<D, true>(Wu + L::UPD_W1, L::CAT, 0, x, hid);
+    matvecD<D, true>(Wu + L::UPD_W1, L::CAT, D, mp_to, hid);
+    matvecD<D, true>(Wu + L::UPD_W1, L::CAT, 2 * D, mp_fr, hid);
+    matvecD<P, true>(Wu + L::UPD_W1, L::CAT, 3 * D, pq, hid);
     if (JVP) {
 #pragma unroll
       for (int k = 0; k < D; ++k) dal = fmaf(Wa[k], dx[k], dal);
@@ -234,9 +234,9 @@ __global__ __launch_bounds__(256) void k_node(int64_t N, const float* __restrict
 #pragma unroll
       for (int k = 0; k < D; ++k) dal = fmaf(Wa[2 * D + k], dmp_fr[k], dal);
       dal *= al * (1.f - al);
-      matvec10<D, false>(Wu + L::UPD_W1, L::CAT, 0, dx, dhid);
-      matvec10<D, true>(Wu + L::UPD_W1, L::CAT, D, dmp_to, dhid);
-      matvec10<D, true>(Wu + L::UPD_W1, L::CAT, 2 * D, dmp_fr, dhid);
+      matvecD<D, false>(Wu + L::UPD_W1, L::CAT, 0, dx, dhid);
+      matvecD<D, true>(Wu + L::UPD_W1, L::CAT, D, dmp_to, dhid);
+      matvecD<D, true>(Wu + L::UPD_W1, L::CAT, 2 * D, dmp_fr, dhid);
 #pragma unroll
       for (int o = 0; o < D; ++o) dhid[o] = hid[o] > 0.f ? dhid[o] : 0.f;
     }
@@ -245,12 +245,12 @@ __global__ __launch_bounds__(256) void k_node(int64_t N, const float* __restrict
       hid[o] = fmaxf(hid[o], 0.f);
       upd[o] = Wu[L::UPD_B2 + o];
     }
-    matvec10<D, true>(Wu + L::UPD_W2, D, 0, hid, upd);
+    matvecD<D, true>(Wu + L::UPD_W2, D, 0, hid, upd);
 #pragma unroll
     for (int o = 0; o < D; ++o) y[o] = fmaf(al, upd[o], x[o]);
     if (JVP) {
       float dupd[D];
-      matvec10<D, false>(Wu + L::UPD_W2, D, 0, dhid, dupd);
+      matvecD<D, false>(Wu + L::UPD_W2, D, 0, dhid, dupd);
 #pragma unroll
       for (int o = 0; o < D; ++o) dy[o] = dx[o] + dal * upd[o] + al * dupd[o];
     }
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256) void k_node(int64_t N, const float* __restrict
       for (int o = 0; o < D; ++o) dy[o] = W[L::LN_G + o] * rs * (dy[o] - dm - y[o] * yd);
     }
   }
-  store10(out + n * D, JVP ? dy : y);
+  storeD(out + n * D, JVP ? dy : y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -299,8 +299,8 @@ extern "C" int64_t psignn_weights_size(int mixed, int n_layers) {
 
 extern "C" int64_t psignn_f_workspace_floats(const psignn_plan_t* p) {
   if (!p) return -1;
-  // Pj (value + tangent rows, up to 3 Phi modules) + two (N,10) ping-pong buffers for n_layers > 1;
-  // the VJP keeps Pj (30) + B (60) rows per node
+  // Pj (value + tangent rows, up to 3 Phi modules) + two (N,D) ping-pong buffers for n_layers > 1;
+  // the VJP keeps Pj (3 D) + B (6 D) rows per node
   return p->N * (10 * D);
 }
 
@@ -432,6 +432,7 @@ extern "C" int psignn_phi(const psignn_plan_t* p, const float* W, int nl, int la
   return PSIGNN_OK;
 }
 
+#if PSIGNN_D == 10   // derivatives exist at the default width only: a width library (libpsignn_hip_d<w>.so) ends here
 int psignn_f_tile_jvp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* v,
                       float* out, hipStream_t st);
 int psignn_f_layers_jvp_stateless(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* v,
@@ -504,3 +505,4 @@ extern "C" int psignn_f_jvp(const psignn_plan_t* p, const float* W, int nl, cons
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
+#endif  // PSIGNN_D == 10

@@ -5,6 +5,7 @@
 //   stage 1  every lane takes one row of the tile + halo (<= 256 + HALO_CAP rows): loads h (tile rows are
 //            one coalesced 40 B/lane stream, halo rows a short indexed gather), projects it with the
 //            neighbour-side weights W1j_{to,from[,neu]} and parks the 80-byte result row in LDS
+//            (byte counts for the default width D = 10: rows are 4 D bytes in memory, 8 D / 12 D in LDS)
 //   stage 2  every lane owns one tile node and walks its pair-merged ELL slots (tiles.hip): one coalesced
 //            16-byte load {LDS row, IN/OUT, edge_attr} and one LDS row read (5 x ds_read_b128) serve BOTH
 //            directions of a neighbour; relu terms are summed in the plan's canonical order (no atomics,
@@ -13,7 +14,7 @@
 // the host (WLayout fold block).  All node tensors are in PLAN order; the solver keeps its state there.
 // weight loads of mv2 pinned chunk by chunk (tile_helpers.h; A/B in profiles/r3_ab_mv2.txt: fused step 75.8 -> 73.4 us, plain f unchanged)
 #define MV2_LAUNDER 2
-#define MV2_CH 10
+#define MV2_CH (100 / PSIGNN_D)   // at most ~100 weights of a block in flight: 10 inputs at D = 10, 6 at 16, the whole 8 x 8 block at 8
 #include "tile_helpers.h"
 // Occupancy caps were measured and removed (profiles/r2_f_tile_ab_runs.txt): k_f_tile held to 96 VGPRs ran plain f in 59.8 vs
 // 58.0 us, the fused instantiations held to 80 VGPRs for a sixth wave 89.6 vs 88.8 us, the batched kernel held to six waves 57.4
@@ -21,43 +22,51 @@
 
 template <bool MIXED>
 struct TileRow {
-  static constexpr int RS = MIXED ? 32 : 20;  // floats per LDS row: [to 10 | from 10] (| neu 10 | pad 2)
+  static constexpr int RS = MIXED ? (3 * D + 3) / 4 * 4 : 2 * D;  // floats per LDS row: [to D | from D] (| neu D | pad to 16 bytes)
 };
+static_assert(TileRow<false>::RS % 4 == 0 && TileRow<true>::RS % 4 == 0, "LDS rows are read as 16-byte quads");
+#if PSIGNN_D == 10
+static_assert(TileRow<false>::RS == 20 && TileRow<true>::RS == 32, "LDS rows at D = 10");
+#endif
+// the largest requests a tiled plan can make fit the 160 KiB of a CU at every width: the plan's row limits are width-free
+static_assert((TILE_MAX + HALO_CAP) * TileRow<false>::RS * 4 <= 160 * 1024 && MIXED_ROW_CAP * TileRow<true>::RS * 4 <= 160 * 1024,
+              "LDS rows of the f kernel at the plan's row limits");
 
-__device__ __forceinline__ void lds_store20(float* __restrict__ p, const float* __restrict__ a, const float* __restrict__ b) {
-  float4* q = reinterpret_cast<float4*>(p);
-  q[0] = make_float4(a[0], a[1], a[2], a[3]);
-  q[1] = make_float4(a[4], a[5], a[6], a[7]);
-  q[2] = make_float4(a[8], a[9], b[0], b[1]);
-  q[3] = make_float4(b[2], b[3], b[4], b[5]);
-  q[4] = make_float4(b[6], b[7], b[8], b[9]);
-}
-__device__ __forceinline__ void lds_load20(const float* __restrict__ p, float* __restrict__ a, float* __restrict__ b) {
-  const float4* q = reinterpret_cast<const float4*>(p);
-  float4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3], v4 = q[4];
-  a[0] = v0.x; a[1] = v0.y; a[2] = v0.z; a[3] = v0.w;
-  a[4] = v1.x; a[5] = v1.y; a[6] = v1.z; a[7] = v1.w;
-  a[8] = v2.x; a[9] = v2.y; b[0] = v2.z; b[1] = v2.w;
-  b[2] = v3.x; b[3] = v3.y; b[4] = v3.z; b[5] = v3.w;
-  b[6] = v4.x; b[7] = v4.y; b[8] = v4.z; b[9] = v4.w;
-}
-__device__ __forceinline__ void lds_store10at(float* __restrict__ p, const float* __restrict__ t) {  // 8-byte aligned
-  float2* q = reinterpret_cast<float2*>(p);
+// LDS row helpers.  A row starts on a 16-byte boundary; a segment of D floats (NPAIR register pairs) at float offset OFF starts on
+// one too when OFF is a multiple of 4, else (D = 2 mod 4, second segment) at 8 mod 16.
+// [a | b] = 2 D floats from the row's start: NPAIR quads (D = 10: 5 x ds_write_b128)
+__device__ __forceinline__ void lds_store_row2(float* __restrict__ rowp, const v2f* a, const v2f* b) {
+  float4* q = reinterpret_cast<float4*>(rowp);
+  v2f c[2 * NPAIR];
 #pragma unroll
-  for (int i = 0; i < 5; ++i) q[i] = make_float2(t[2 * i], t[2 * i + 1]);
-}
-__device__ __forceinline__ void lds_load10at(const float* __restrict__ p, float* __restrict__ t) {
-  const float2* q = reinterpret_cast<const float2*>(p);
+  for (int p = 0; p < NPAIR; ++p) {
+    c[p] = a[p];
+    c[NPAIR + p] = b[p];
+  }
 #pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    float2 v = q[i];
-    t[2 * i] = v.x;
-    t[2 * i + 1] = v.y;
+  for (int i = 0; i < NPAIR; ++i) q[i] = make_float4(c[2 * i].x, c[2 * i].y, c[2 * i + 1].x, c[2 * i + 1].y);
+}
+// one segment: quads and, when D is not a multiple of 4, one b64 -- at the end of an aligned segment (D = 10: b128, b128, b64),
+// at the start of one that begins at 8 mod 16 (b64, b128, b128)
+template <int OFF>
+__device__ __forceinline__ void lds_store_row(float* __restrict__ rowp, const v2f* t) {
+  static_assert(OFF % 4 == 0 || (OFF % 2 == 0 && D % 4 == 2), "segment start");
+  if constexpr (OFF % 4 == 0) {
+    float4* q = reinterpret_cast<float4*>(rowp + OFF);
+#pragma unroll
+    for (int i = 0; i < D / 4; ++i) q[i] = make_float4(t[2 * i].x, t[2 * i].y, t[2 * i + 1].x, t[2 * i + 1].y);
+    if (D % 4) reinterpret_cast<float2*>(rowp + OFF)[NPAIR - 1] = make_float2(t[NPAIR - 1].x, t[NPAIR - 1].y);
+  } else {
+    reinterpret_cast<float2*>(rowp + OFF)[0] = make_float2(t[0].x, t[0].y);
+    float4* q = reinterpret_cast<float4*>(rowp + OFF + 2);
+#pragma unroll
+    for (int i = 0; i < D / 4; ++i) q[i] = make_float4(t[2 * i + 1].x, t[2 * i + 1].y, t[2 * i + 2].x, t[2 * i + 2].y);
   }
 }
 
 // Stage 1 exists in two forms, chosen per launch (env PSIGNN_STAGE1 = mfma | valu overrides the default):
-// matrix cores (v_mfma_f32_16x16x4_f32) or packed VALU.
+// matrix cores (v_mfma_f32_16x16x4_f32) or packed VALU.  The matrix-core form is written for D = 10 (K padded to 12, 20 / 30
+// outputs in two M-tiles) and exists in that build only: at another width the knob has no effect.
 #include <stdlib.h>
 #include <string.h>
 // Default form: packed VALU everywhere.  A/Bs on one box (1M-node mesh) after the scalar-load phase barriers removed the
@@ -66,7 +75,13 @@ __device__ __forceinline__ void lds_load10at(const float* __restrict__ p, float*
 // registers); mixed plain f 102.9 (valu) vs 102.2 (mfma) in one launch, 81.8 us (valu) once the tiles without Neumann
 // nodes run with 80-byte LDS rows (launch_mixed).  Before the barriers the VALU form spilled ~200 SGPRs and lost: 68.2 vs
 // 66.3 us.  The MFMA form stays selectable (PSIGNN_STAGE1=mfma) for A/B runs.
+constexpr bool MFMA_FORM = D == 10;   // template argument of the launches the knob selects: the VALU form again at another width
 static int stage1_mfma(bool fused, bool mixed) {
+#if PSIGNN_D != 10
+  (void)fused;
+  (void)mixed;
+  return 0;
+#else
   KNOB_INT(forced, [] {
     const char* e = getenv("PSIGNN_STAGE1");
     return !e ? -1 : (strcmp(e, "mfma") == 0 ? 1 : 0);
@@ -75,6 +90,7 @@ static int stage1_mfma(bool fused, bool mixed) {
   (void)fused;
   (void)mixed;
   return 0;   // the MFMA form is kept for A/B runs (PSIGNN_STAGE1=mfma); see the comment above
+#endif
 }
 
 // Broyden fusion (solver.hip): the kernel forms x_next = x_cur + update while loading, and its epilogue
@@ -162,6 +178,7 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   // ---- stage 1: neighbour-side projections of tile + halo rows -> LDS
   float x[D];
   if constexpr (MFMA1) {
+#if PSIGNN_D == 10
     // Dense node-feature x weight product on the matrix cores: out[row][o] = sum_k x[row][k] W1j[o][k] as
     // v_mfma_f32_16x16x4_f32 tiles with the WEIGHTS as the A operand (A[i = output][k]) and the node rows as B
     // (B[k][j = row]): a lane then receives D[i = 4 (lane>>4) + r][j = lane&15], r = 0..3 -- four consecutive
@@ -212,14 +229,17 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
       }
     }
     if (tid < n_t) {  // this lane's own node state for stage 2 (L1/L2-hot: the rows were just read above)
-      load10(h + (int64_t)(t0 + tid) * D, x);
+      loadD(h + (int64_t)(t0 + tid) * D, x);
       if (FUSED) {
         float ur[D];
-        load10(fa.upd + (int64_t)(t0 + tid) * D, ur);
+        loadD(fa.upd + (int64_t)(t0 + tid) * D, ur);
 #pragma unroll
         for (int o = 0; o < D; ++o) x[o] += ur[o];
       }
     }
+#else
+    static_assert(!MFMA1, "the matrix-core stage 1 exists at D = 10 only");
+#endif
   } else {
   // mixed family: the Phi_neumann projections are only read by Neumann lanes, i.e. in the few boundary tiles -- every
   // other tile skips a third of its stage-1 work
@@ -233,14 +253,14 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   int32_t hnode = 0;
   if (hidx_w < n_h) hnode = hl[hidx_w];                        // halo index of the first batch, ahead of its use
   float xr[D], xh[D];
-  if (tid < n_t) load10(h + (int64_t)(t0 + tid) * D, xr);
+  if (tid < n_t) loadD(h + (int64_t)(t0 + tid) * D, xr);
   // the first batch's halo row is requested before the own row is projected (the phase barriers below would otherwise keep
   // its load behind that arithmetic): one more memory round trip off stage 1's critical path
   if (hidx_w < n_h) {
-    load10(h + (int64_t)hnode * D, xh);
+    loadD(h + (int64_t)hnode * D, xh);
     if (FUSED) {
       float uh[D];
-      load10(fa.upd + (int64_t)hnode * D, uh);
+      loadD(fa.upd + (int64_t)hnode * D, uh);
 #pragma unroll
       for (int o = 0; o < D; ++o) xh[o] += uh[o];
     }
@@ -248,39 +268,33 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   if (tid < n_t) {
     if (FUSED) {  // x_next = x_cur + update (line_search with on=False: step 1, solver.py:85-94)
       float ur[D];
-      load10(fa.upd + (int64_t)(t0 + tid) * D, ur);
+      loadD(fa.upd + (int64_t)(t0 + tid) * D, ur);
 #pragma unroll
       for (int o = 0; o < D; ++o) xr[o] += ur[o];
     }
 #pragma unroll
     for (int o = 0; o < D; ++o) x[o] = xr[o];
-    v2f ta[5], tb[5];
+    v2f ta[NPAIR], tb[NPAIR];
 #pragma unroll
-    for (int p = 0; p < 5; ++p) ta[p] = tb[p] = splat(0.f);
+    for (int p = 0; p < NPAIR; ++p) ta[p] = tb[p] = splat(0.f);
     PHASE();
     mv2<D>(T + L::T_W1J_TO, xr, ta);
     PHASE();
     mv2<D>(T + L::T_W1J_FR, xr, tb);
-    float4* q = reinterpret_cast<float4*>(lds + tid * RS);
-    q[0] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
-    q[1] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
-    q[2] = make_float4(ta[4].x, ta[4].y, tb[0].x, tb[0].y);
-    q[3] = make_float4(tb[1].x, tb[1].y, tb[2].x, tb[2].y);
-    q[4] = make_float4(tb[3].x, tb[3].y, tb[4].x, tb[4].y);
+    float* rowp = lds + tid * RS;
+    lds_store_row2(rowp, ta, tb);
     if (MIXED && tile_neu) {
 #pragma unroll
-      for (int p = 0; p < 5; ++p) ta[p] = splat(0.f);
+      for (int p = 0; p < NPAIR; ++p) ta[p] = splat(0.f);
       PHASE();
       mv2<D>(TN + L::N_W1J, xr, ta);
-      q[5] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
-      q[6] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
-      reinterpret_cast<float2*>(q + 7)[0] = make_float2(ta[4].x, ta[4].y);
+      lds_store_row<2 * D>(rowp, ta);
     }
   }
   // Halo rows.  A tile of 256 nodes has ~110 of them: as whole rows (round 1's loop, measured and removed:
   // profiles/r2_f_tile_ab_runs.txt) they were a second round for waves 0 and 1 only, with the other two waves parked at the
   // barrier (stamps: 4.0 vs 2.5 us in stage 1, 1.7 us of barrier wait).  Shared out as HALF rows instead -- waves 0, 1 project the
-  // Phi_to half of halo rows [64 (w & 1), +64), waves 2, 3 the Phi_from half -- every wave does one 10 x 10 block per 128 halo
+  // Phi_to half of halo rows [64 (w & 1), +64), waves 2, 3 the Phi_from half -- every wave does one D x D block per 128 halo
   // rows: the same number of wave instructions, half the critical path.
   {
     const int half = __builtin_amdgcn_readfirstlane(tid >> 7);   // wave-uniform: 0 Phi_to columns, 1 Phi_from columns
@@ -293,31 +307,25 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
 #pragma unroll
           for (int o = 0; o < D; ++o) xr[o] = xh[o];
         } else {
-          load10(h + (int64_t)hnode * D, xr);
+          loadD(h + (int64_t)hnode * D, xr);
           if (FUSED) {
             float ur[D];
-            load10(fa.upd + (int64_t)hnode * D, ur);
+            loadD(fa.upd + (int64_t)hnode * D, ur);
 #pragma unroll
             for (int o = 0; o < D; ++o) xr[o] += ur[o];
           }
         }
-        v2f ta[5];
+        v2f ta[NPAIR];
 #pragma unroll
-        for (int p = 0; p < 5; ++p) ta[p] = splat(0.f);
+        for (int p = 0; p < NPAIR; ++p) ta[p] = splat(0.f);
         PHASE();
         float* rowp = lds + (n_t + idx) * RS;
         if (half == 0) {
           mv2<D>(T + L::T_W1J_TO, xr, ta);
-          float4* q = reinterpret_cast<float4*>(rowp);                 // floats 0..9: b128, b128, b64
-          q[0] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
-          q[1] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
-          reinterpret_cast<float2*>(rowp + 8)[0] = make_float2(ta[4].x, ta[4].y);
+          lds_store_row<0>(rowp, ta);   // floats 0..D-1 (D = 10: b128, b128, b64)
         } else {
           mv2<D>(T + L::T_W1J_FR, xr, ta);
-          reinterpret_cast<float2*>(rowp + 10)[0] = make_float2(ta[0].x, ta[0].y);   // floats 10..19: b64, b128, b128
-          float4* q = reinterpret_cast<float4*>(rowp + 12);
-          q[0] = make_float4(ta[1].x, ta[1].y, ta[2].x, ta[2].y);
-          q[1] = make_float4(ta[3].x, ta[3].y, ta[4].x, ta[4].y);
+          lds_store_row<D>(rowp, ta);   // floats D..2D-1 (D = 10: b64, b128, b128)
         }
       }
     }
@@ -325,22 +333,19 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
       for (int idx = tid; idx < n_h; idx += TILE_THREADS) {
         const int64_t node = hl[idx];
         float xr[D];
-        load10(h + node * D, xr);
+        loadD(h + node * D, xr);
         if (FUSED) {
           float ur[D];
-          load10(fa.upd + node * D, ur);
+          loadD(fa.upd + node * D, ur);
 #pragma unroll
           for (int o = 0; o < D; ++o) xr[o] += ur[o];
         }
-        v2f ta[5];
+        v2f ta[NPAIR];
 #pragma unroll
-        for (int p = 0; p < 5; ++p) ta[p] = splat(0.f);
+        for (int p = 0; p < NPAIR; ++p) ta[p] = splat(0.f);
         PHASE();
         mv2<D>(TN + L::N_W1J, xr, ta);
-        float4* q = reinterpret_cast<float4*>(lds + (n_t + idx) * RS);
-        q[5] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
-        q[6] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
-        reinterpret_cast<float2*>(q + 7)[0] = make_float2(ta[4].x, ta[4].y);
+        lds_store_row<2 * D>(lds + (n_t + idx) * RS, ta);
       }
     }
   }
@@ -360,9 +365,9 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   float y[D];
   const bool dirichlet = fl & FLAG_DIRICHLET;
   if (dirichlet) {  // Dirichlet rows <- h_initial rows (model.py:298)
-    load10(h0 + n * D, y);
+    loadD(h0 + n * D, y);
     if (!FUSED) {
-      store10(out + n * D, y);
+      storeD(out + n * D, y);
       return;
     }
   }
@@ -374,26 +379,26 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   const int nslots = C->slice_deg[slice];
 
   // target-side projection (bias included) + neighbour sum
-  v2f Pi[5], S_to[5], S_fr[5];
+  v2f Pi[NPAIR], S_to[NPAIR], S_fr[NPAIR];
   float deg_in, deg_out;
 #pragma unroll
-  for (int p = 0; p < 5; ++p) S_to[p] = S_fr[p] = splat(0.f);
+  for (int p = 0; p < NPAIR; ++p) S_to[p] = S_fr[p] = splat(0.f);
   // the node state is not needed during the slot walk: park it in memory (the fused step writes x_next to its slot of the
   // iterate buffer anyway) and read it back afterwards -- ten VGPRs less in the loop
   const float* xsrc = h + n * D;
   if (FUSED) {
     float* xn = fa.xbuf + (int64_t)fa.st[fa.off_nxt] * fa.M + n * D;
-    store10(xn, x);
+    storeD(xn, x);
     xsrc = xn;
   }
   // both edge directions in one slot walk, relu folded into the clamp bit of the last edge fma (tile_helpers.h).  One walk per
   // direction was measured and removed: plain f 62.9 vs 61.5 us, fused step 104 vs 99.5 us.
   {
-    v2f Pi2[5];
-    ld5(T + L::T_B1_TO, Pi);
+    v2f Pi2[NPAIR];
+    ldD(T + L::T_B1_TO, Pi);
     PHASE();
     mv2<D>(T + L::T_W1I_TO, x, Pi);
-    ld5(T + L::T_B1_FR, Pi2);
+    ldD(T + L::T_B1_FR, Pi2);
     PHASE();
     mv2<D>(T + L::T_W1I_FR, x, Pi2);
     PHASE();
@@ -402,22 +407,22 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   }
   STAMP(3);
   __builtin_amdgcn_s_setprio(0);
-  load10(xsrc, x);
+  loadD(xsrc, x);
 
-  v2f y2[5];
+  v2f y2[NPAIR];
   if (MIXED && (fl & FLAG_NEUMANN)) {
     // Phi_neumann (Phi_from type: out-edges) + update_neumann: the row is REPLACED (mixed/psignn/model.py:236,241)
-    v2f S_n[5], hid[5], gN[5];
-    ld5(TN + L::N_B1, Pi);
+    v2f S_n[NPAIR], hid[NPAIR], gN[NPAIR];
+    ldD(TN + L::N_B1, Pi);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) S_n[p] = splat(0.f);
+    for (int p = 0; p < NPAIR; ++p) S_n[p] = splat(0.f);
     PHASE();
     mv2<D>(TN + L::N_W1I, x, Pi);
     edge_pass<RS, 2 * D, SLOT_OUT>(slots, nslots, lds, TN + L::N_A, Pi, S_n);
-    ld5(TN + L::N_NB1, hid);
-    ld5(TN + L::N_gN, gN);
+    ldD(TN + L::N_NB1, hid);
+    ldD(TN + L::N_gN, gN);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) hid[p] = __builtin_elementwise_fma(splat(deg_out), gN[p], hid[p]);
+    for (int p = 0; p < NPAIR; ++p) hid[p] = __builtin_elementwise_fma(splat(deg_out), gN[p], hid[p]);
     PHASE();
     mv2<D>(TN + L::N_N1H, x, hid);
     PHASE();
@@ -430,8 +435,8 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
     PHASE();
     mv2<P + 2>(TN + L::N_N1P, pq, hid);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) hid[p] = __builtin_elementwise_max(hid[p], splat(0.f));
-    ld5(TN + L::N_NB2, y2);
+    for (int p = 0; p < NPAIR; ++p) hid[p] = __builtin_elementwise_max(hid[p], splat(0.f));
+    ldD(TN + L::N_NB2, y2);
     PHASE();
     mv2<D>(TN + L::N_N2, reinterpret_cast<const float*>(hid), y2);
   } else {
@@ -453,12 +458,12 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
 #pragma unroll
     for (int k = 0; k < P; ++k) al = fmaf(Wa[3 * D + k], pq[k], al);
     al = 1.f / (1.f + expf(-al));
-    v2f hid[5], g1[5], g2[5], upd[5];
-    ld5(T + L::T_HB, hid);
-    ld5(T + L::T_gTO, g1);
-    ld5(T + L::T_gFR, g2);
+    v2f hid[NPAIR], g1[NPAIR], g2[NPAIR], upd[NPAIR];
+    ldD(T + L::T_HB, hid);
+    ldD(T + L::T_gTO, g1);
+    ldD(T + L::T_gFR, g2);
 #pragma unroll
-    for (int p = 0; p < 5; ++p)
+    for (int p = 0; p < NPAIR; ++p)
       hid[p] = __builtin_elementwise_fma(splat(deg_in), g1[p], __builtin_elementwise_fma(splat(deg_out), g2[p], hid[p]));
     PHASE();
     mv2<D>(T + L::T_U1H, x, hid);
@@ -469,15 +474,15 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
     PHASE();
     mv2<P>(T + L::T_U1P, pq, hid);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) hid[p] = __builtin_elementwise_max(hid[p], splat(0.f));
-    ld5(T + L::T_C2, upd);
+    for (int p = 0; p < NPAIR; ++p) hid[p] = __builtin_elementwise_max(hid[p], splat(0.f));
+    ldD(T + L::T_C2, upd);
     PHASE();
     mv2<D>(T + L::T_U2, reinterpret_cast<const float*>(hid), upd);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) y2[p] = __builtin_elementwise_fma(splat(al), upd[p], (v2f){x[2 * p], x[2 * p + 1]});
+    for (int p = 0; p < NPAIR; ++p) y2[p] = __builtin_elementwise_fma(splat(al), upd[p], (v2f){x[2 * p], x[2 * p + 1]});
   }
 #pragma unroll
-  for (int p = 0; p < 5; ++p) {
+  for (int p = 0; p < NPAIR; ++p) {
     y[2 * p] = y2[p].x;
     y[2 * p + 1] = y2[p].y;
   }
@@ -501,7 +506,7 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
   STAMP(4);
   __builtin_amdgcn_s_setprio(0);
   if (!FUSED) {
-    store10(out + n * D, y);
+    storeD(out + n * D, y);
     STAMP(5);
     return;
   }
@@ -515,8 +520,8 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
       sg = fmaf(gn[o], gn[o], sg);
       sf = fmaf(y[o], y[o], sf);
     }
-    store10(fa.gnew + n * D, gn);
-    if (dirichlet) store10(fa.xbuf + (int64_t)fa.st[fa.off_nxt] * fa.M + n * D, x);
+    storeD(fa.gnew + n * D, gn);
+    if (dirichlet) storeD(fa.xbuf + (int64_t)fa.st[fa.off_nxt] * fa.M + n * D, x);
   }
   // one partial pair per tile: wave shuffles, then the 4 wave sums through LDS in a fixed order
   sg = wave_sum_f(sg);
@@ -659,12 +664,12 @@ int psignn_f_tile_forward(const psignn_plan* p, const float* W, int nl, const fl
   const int chunk = (int)cdiv(p->n_tiles, 8);
   const unsigned grid = tile_grid(chunk);
   // B_f: h, h' (40 N each), prb (8 / 12 N), flags and, mixed, normals; 20 bytes per directed non-self edge
-  PROF_BYTES(((p->mixed ? 102 : 89) * p->N + 20 * p->Ep) * (p->mixed ? 1 : nl));
+  PROF_BYTES(((p->mixed ? 8 * D + 22 : 8 * D + 9) * p->N + 20 * p->Ep) * (p->mixed ? 1 : nl));   // 102 / 89 N at D = 10
   if (p->mixed) {
     using L = WLayout<3>;
     if (stage1_mfma(false, true)) {  // single launch, MFMA stage 1 (PSIGNN_STAGE1=mfma)
       size_t lds = (size_t)p->max_rows * TileRow<true>::RS * 4;
-      LAUNCH("k_f_tile", st, (k_f_tile<3, true, false, true><<<grid, TILE_THREADS, lds, st>>>(
+      LAUNCH("k_f_tile", st, (k_f_tile<3, true, false, MFMA_FORM><<<grid, TILE_THREADS, lds, st>>>(
         plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), L::tp_neu(nl), 1,
         h, hsel, hstride, h0, prb, nrm, out)));
     } else {
@@ -679,7 +684,7 @@ int psignn_f_tile_forward(const psignn_plan* p, const float* W, int nl, const fl
     for (int l = 0; l < nl; ++l) {
       float* dst = (l == nl - 1) ? out : pp[l & 1];
       if (stage1_mfma(false, false))
-        LAUNCH("k_f_tile", st, (k_f_tile<2, false, false, true><<<grid, TILE_THREADS, lds, st>>>(
+        LAUNCH("k_f_tile", st, (k_f_tile<2, false, false, MFMA_FORM><<<grid, TILE_THREADS, lds, st>>>(
             plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, cur,
             l == 0 ? hsel : nullptr, hstride, h0, prb, nrm, dst)));
       else
@@ -704,9 +709,9 @@ int psignn_f_tile_layer(const psignn_plan* p, const float* W, int nl, int l, con
   const int chunk = (int)cdiv(p->n_tiles, 8);
   const unsigned grid = tile_grid(chunk);
   size_t lds = (size_t)p->max_rows * TileRow<false>::RS * 4;
-  PROF_BYTES(89 * p->N + 20 * p->Ep);   // B_f of one layer (psignn_f_tile_forward)
+  PROF_BYTES((8 * D + 9) * p->N + 20 * p->Ep);   // B_f of one layer (psignn_f_tile_forward)
   if (stage1_mfma(false, false))
-    LAUNCH("k_f_tile_layer", st, (k_f_tile<2, false, false, true><<<grid, TILE_THREADS, lds, st>>>(
+    LAUNCH("k_f_tile_layer", st, (k_f_tile<2, false, false, MFMA_FORM><<<grid, TILE_THREADS, lds, st>>>(
         plain_args(), (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(l), L::tp_layer(nl, false, l), 0, l == nl - 1, h,
         nullptr, 0, h0, prb, nullptr, out)));
   else
@@ -728,12 +733,12 @@ int psignn_f_tile_fused(const psignn_plan* p, const float* W, int nl, float* xbu
   const unsigned grid = tile_grid(chunk);
   const int npart = (int)p->n_tiles;
   FuseArgs fa{upd, gnew, xbuf, st_words, off_done, off_cur, off_nxt, M, part, npart, g_tile_stamps};
-  PROF_BYTES((p->mixed ? 102 : 89) * p->N + 20 * p->Ep + 8 * M);   // B_f + update read, g_new written (x_next replaces f(x))
+  PROF_BYTES((p->mixed ? 8 * D + 22 : 8 * D + 9) * p->N + 20 * p->Ep + 8 * M);   // B_f + update read, g_new written (x_next replaces f(x))
   if (p->mixed) {
     using L = WLayout<3>;
     if (stage1_mfma(true, true)) {
       size_t lds = (size_t)p->max_rows * TileRow<true>::RS * 4;
-      LAUNCH("k_f_tile_fused", st, (k_f_tile<3, true, true, true><<<grid, TILE_THREADS, lds, st>>>(
+      LAUNCH("k_f_tile_fused", st, (k_f_tile<3, true, true, MFMA_FORM><<<grid, TILE_THREADS, lds, st>>>(
         fa, (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(nl - 1), L::tp_layer(nl, true, nl - 1), L::tp_neu(nl), 1, xbuf,
         nullptr, 0, h0, prb, nrm, nullptr)));
     } else {
@@ -743,7 +748,7 @@ int psignn_f_tile_fused(const psignn_plan* p, const float* W, int nl, float* xbu
     using L = WLayout<2>;
     size_t lds = (size_t)p->max_rows * TileRow<false>::RS * 4;
     if (stage1_mfma(true, false))
-      LAUNCH("k_f_tile_fused", st, (k_f_tile<2, false, true, true><<<grid, TILE_THREADS, lds, st>>>(
+      LAUNCH("k_f_tile_fused", st, (k_f_tile<2, false, true, MFMA_FORM><<<grid, TILE_THREADS, lds, st>>>(
         fa, (int)p->n_tiles, chunk, nullptr, p->h_ctx, W, L::layer(0), L::tp_layer(nl, false, 0), 0, 1, xbuf, nullptr, 0, h0, prb, nrm,
         nullptr)));
     else

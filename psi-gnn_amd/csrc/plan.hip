@@ -22,6 +22,7 @@ void psignn_set_error(const char* fmt, ...) {
 }
 extern "C" const char* psignn_last_error(void) { return g_err.c_str(); }
 extern "C" int psignn_version(void) { return 100; }
+extern "C" int psignn_latent_dim(void) { return D; }
 int g_knob_epoch = 0;
 extern "C" void psignn_reload_knobs(void) { ++g_knob_epoch; }
 

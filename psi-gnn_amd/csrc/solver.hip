@@ -1802,7 +1802,7 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
   int64_t bf_tot = 0;   // bytes of one fused f evaluation, summed over the shard (profiling records)
   for (int m = 0; m < n; ++m) {
     sh.Mtot4 += sv[m]->M * 4;
-    bf_tot += (sv[m]->plan->mixed ? 102 : 89) * sv[m]->plan->N + 20 * sv[m]->plan->Ep + 8 * sv[m]->M;
+    bf_tot += (sv[m]->plan->mixed ? 8 * D + 22 : 8 * D + 9) * sv[m]->plan->N + 20 * sv[m]->plan->Ep + 8 * sv[m]->M;
   }
   // ---- per mesh: status, plan-order inputs, g0 = f(x0) - x0 (exactly the single-mesh prologue)
   std::vector<BatchDesc> hd(n);
@@ -1875,6 +1875,7 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
 }
 
 
+#if PSIGNN_D == 10   // the adjoint solves need the transposed products, which exist at the default width only
 // ---- adjoint fixed point  y = J_f(h*)^T y + grad  (the reference's backward hook, dirichlet/psignn/model.py:210-223)
 template <int VEC>
 __global__ __launch_bounds__(TB) void k_addv(int64_t M, const Status* __restrict__ st, float* __restrict__ a,
@@ -2171,6 +2172,8 @@ extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** 
 #undef BT
   return rc;
 }
+#endif  // PSIGNN_D == 10
+
 
 extern "C" int psignn_broyden_get_iterate(const psignn_broyden_t* s, int i, float* d_dst, void* stream) {
   ARG_CHECK(s && d_dst, "NULL argument");

@@ -27,8 +27,8 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v2f splat(float a) { return (v2f){a, a}; }
 
-// acc[p] += WT[k][2p..2p+1] * x[k],  p < 5, k < K
-// A 10 x 10 block is 100 wave-uniform weights -- with the wave's other live SGPRs more than the 102 there are, and the
+// acc[p] += WT[k][2p..2p+1] * x[k],  p < NPAIR (= D / 2: 5 at the default width), k < K
+// A 10 x 10 block is 100 wave-uniform weights (D x D in general) -- with the wave's other live SGPRs more than the 102 there are, and the
 // compiler, which loads a whole block ahead of its first use, then parks the excess in VGPR lanes (v_writelane /
 // v_readlane: 36 VALU slots per stage-1 round in round 1's build).  A compiler barrier every MV2_CH inputs keeps at most
 // MV2_CH x 10 weights in flight.
@@ -54,7 +54,7 @@ __device__ __forceinline__ void mv2(const float* __restrict__ WT, const float* x
   // hoisted over it nor can the statement itself float above the arithmetic it waits for.  `after`: a value of the caller's that
   // the first chunk has to wait for (e.g. the last output of an independent product issued just before).
   int zero = 0;
-  asm volatile("" : "+s"(zero) : "v"(acc[0]), "v"(acc[4]), "v"(after));
+  asm volatile("" : "+s"(zero) : "v"(acc[0]), "v"(acc[NPAIR - 1]), "v"(after));
   w += zero;
 #endif
 #pragma unroll
@@ -62,19 +62,24 @@ __device__ __forceinline__ void mv2(const float* __restrict__ WT, const float* x
     if (MV2_CH > 0 && k > 0 && k % MV2_CH == 0) {
       PHASE();
 #if MV2_LAUNDER
-      asm volatile("" : "+s"(zero) : "v"(acc[0]), "v"(acc[4]));
+      asm volatile("" : "+s"(zero) : "v"(acc[0]), "v"(acc[NPAIR - 1]));
       w += zero;
 #endif
     }
     const v2f xs = splat(x[k]);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) acc[p] = __builtin_elementwise_fma(w[k * 5 + p], xs, acc[p]);
+    for (int p = 0; p < NPAIR; ++p) acc[p] = __builtin_elementwise_fma(w[k * NPAIR + p], xs, acc[p]);
   }
 }
-__device__ __forceinline__ void ld5(const float* __restrict__ p, v2f* r) {  // 10 wave-uniform floats (8-byte aligned)
+__device__ __forceinline__ void ldD(const float* __restrict__ p, v2f* r) {  // D wave-uniform floats (8-byte aligned): NPAIR pairs
   const v2f* q = reinterpret_cast<const v2f*>(p);
 #pragma unroll
-  for (int i = 0; i < 5; ++i) r[i] = q[i];
+  for (int i = 0; i < NPAIR; ++i) r[i] = q[i];
+}
+__device__ __forceinline__ void ld5(const float* __restrict__ p, v2f* r) { ldD(p, r); }   // its name in the width-10-only files
+// pair i of a row held as 16-byte quads: (x, y) of quad i / 2 for even i, (z, w) for odd i
+__device__ __forceinline__ v2f quad_pair(const float4* v, int i) {
+  return (i & 1) ? (v2f){v[i >> 1].z, v[i >> 1].w} : (v2f){v[i >> 1].x, v[i >> 1].y};
 }
 
 // One direction of the neighbour sum for this lane's node:
@@ -87,39 +92,48 @@ template <int RS, int COL, unsigned MASK>
 __device__ __forceinline__ float edge_pass(const uint4* __restrict__ slots, int nslots, const float* __restrict__ lds,
                                            const float* __restrict__ AT, const v2f* Pi, v2f* S) {
   float deg = 0.f;
-  v2f wa[15];
+  v2f wa[3 * NPAIR];
 #pragma unroll
-  for (int i = 0; i < 15; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
+  for (int i = 0; i < 3 * NPAIR; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
   auto one = [&](const uint4 s) {
     const unsigned w = s.x;
     if ((w & 0xFFFFu) != ELL_EMPTY && (w & MASK)) {
       const v2f a0 = splat(__uint_as_float(s.y)), a1 = splat(__uint_as_float(s.z)), a2 = splat(__uint_as_float(s.w));
       const float* row = lds + (int)(w & 0xFFFFu) * RS + COL;
-      v2f pj[5];
-      if (COL % 4 == 0) {  // 16-byte aligned start: b128, b128, b64
-        float4 v0 = reinterpret_cast<const float4*>(row)[0], v1 = reinterpret_cast<const float4*>(row)[1];
-        float2 v2 = reinterpret_cast<const float2*>(row)[4];
-        pj[0] = (v2f){v0.x, v0.y}; pj[1] = (v2f){v0.z, v0.w}; pj[2] = (v2f){v1.x, v1.y}; pj[3] = (v2f){v1.z, v1.w};
-        pj[4] = (v2f){v2.x, v2.y};
-      } else {             // start at 8 mod 16: b64, b128, b128
-        float2 v0 = reinterpret_cast<const float2*>(row)[0];
-        float4 v1 = reinterpret_cast<const float4*>(row + 2)[0], v2 = reinterpret_cast<const float4*>(row + 2)[1];
-        pj[0] = (v2f){v0.x, v0.y}; pj[1] = (v2f){v1.x, v1.y}; pj[2] = (v2f){v1.z, v1.w}; pj[3] = (v2f){v2.x, v2.y};
-        pj[4] = (v2f){v2.z, v2.w};
+      v2f pj[NPAIR];
+      if (COL % 4 == 0) {  // 16-byte aligned start: D / 4 b128 and, when D is not a multiple of 4, a b64 (D = 10: b128, b128, b64)
+        float4 v[D / 4];
+#pragma unroll
+        for (int q = 0; q < D / 4; ++q) v[q] = reinterpret_cast<const float4*>(row)[q];
+#pragma unroll
+        for (int p = 0; p < D / 4 * 2; ++p) pj[p] = quad_pair(v, p);
+        if (D % 4) {
+          float2 t = reinterpret_cast<const float2*>(row)[NPAIR - 1];
+          pj[NPAIR - 1] = (v2f){t.x, t.y};
+        }
+      } else {             // start at 8 mod 16 (D = 2 mod 4 only): b64, then D / 4 b128 (D = 10: b64, b128, b128)
+        static_assert(COL % 4 == 0 || D % 4 == 2, "a row segment starting at 8 mod 16 has 4 q + 2 floats");
+        float2 t = reinterpret_cast<const float2*>(row)[0];
+        float4 v[D / 4];
+#pragma unroll
+        for (int q = 0; q < D / 4; ++q) v[q] = reinterpret_cast<const float4*>(row + 2)[q];
+        pj[0] = (v2f){t.x, t.y};
+#pragma unroll
+        for (int p = 0; p < D / 4 * 2; ++p) pj[1 + p] = quad_pair(v, p);
       }
       deg += 1.f;
-      // five independent chains, written stage by stage so that dependent packed ops are never back to back
-      v2f z[5];
+      // NPAIR independent chains, written stage by stage so that dependent packed ops are never back to back
+      v2f z[NPAIR];
 #pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = Pi[p] + pj[p];
+      for (int p = 0; p < NPAIR; ++p) z[p] = Pi[p] + pj[p];
 #pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
+      for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
 #pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[5 + p], a1, z[p]);
+      for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[NPAIR + p], a1, z[p]);
 #pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[10 + p], a2, z[p]);
+      for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[2 * NPAIR + p], a2, z[p]);
 #pragma unroll
-      for (int p = 0; p < 5; ++p) S[p] += __builtin_elementwise_max(z[p], splat(0.f));
+      for (int p = 0; p < NPAIR; ++p) S[p] += __builtin_elementwise_max(z[p], splat(0.f));
     }
   };
   // software pipeline, distance EDGE_PD: the 16-byte slot loads are unconditional (index clamped, never branched
@@ -164,9 +178,9 @@ __device__ __forceinline__ v2f pk_fma_lo_clamp(v2f w, v2f a, v2f z) {  // clamp(
   return r;
 }
 
-// Both directions of the neighbour sum in ONE walk over the slots: a pair-merged slot is decoded once, its 80-byte LDS row
+// Both directions of the neighbour sum in ONE walk over the slots: a pair-merged slot is decoded once, its 80-byte (8 D) LDS row
 // [to | from] is read once, and the IN half (Phi_to, mirrored attr weights) and the OUT half (Phi_from) are evaluated back
-// to back.  Needs both attr blocks (60 wave-uniform floats) in SGPRs for the whole loop -- affordable once the phase
+// to back.  Needs both attr blocks (6 D = 60 wave-uniform floats) in SGPRs for the whole loop -- affordable once the phase
 // barriers keep every other scalar load out of the loop's live range.  S_to / S_fr come back UNSCALED (multiplied by 2^40
 // at the end).  Slot records are loaded one round ahead; two rounds ahead was measured and removed (profiles/r2_f_tile_ab_runs.txt:
 // plain f 61.0 - 62.6 vs 57.5 - 58.8 us).
@@ -175,15 +189,15 @@ __device__ __forceinline__ void edge_pass_both_clamp(const uint4* __restrict__ s
                                                      const float* __restrict__ AT_to, const float* __restrict__ AT_fr,
                                                      const v2f* Pi_to, const v2f* Pi_fr, v2f* S_to, v2f* S_fr,
                                                      float& deg_in, float& deg_out) {
-  v2f wt[15], wf[15], pt[5], pf[5];
+  v2f wt[3 * NPAIR], wf[3 * NPAIR], pt[NPAIR], pf[NPAIR];
 #pragma unroll
-  for (int i = 0; i < 15; ++i) {
+  for (int i = 0; i < 3 * NPAIR; ++i) {
     wt[i] = reinterpret_cast<const v2f*>(AT_to)[i];
     wf[i] = reinterpret_cast<const v2f*>(AT_fr)[i];
   }
   const v2f sc = splat(RELU_SCALE);
 #pragma unroll
-  for (int p = 0; p < 5; ++p) {
+  for (int p = 0; p < NPAIR; ++p) {
     pt[p] = Pi_to[p] * sc;
     pf[p] = Pi_fr[p] * sc;
   }
@@ -197,41 +211,47 @@ __device__ __forceinline__ void edge_pass_both_clamp(const uint4* __restrict__ s
       const v2f a01 = (v2f){__uint_as_float(c0.y), __uint_as_float(c0.z)} * sc;
       const v2f a2 = (v2f){__uint_as_float(c0.w) * RELU_SCALE, 0.f};
       const float4* row = reinterpret_cast<const float4*>(lds + (int)(w & 0xFFFFu) * RS);
-      const float4 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3], v4 = row[4];
+      float4 v[NPAIR];   // [to D | from D] = NPAIR quads
+#pragma unroll
+      for (int q = 0; q < NPAIR; ++q) v[q] = row[q];
       if (w & SLOT_IN) {
-        v2f z[5] = {(v2f){v0.x, v0.y}, (v2f){v0.z, v0.w}, (v2f){v1.x, v1.y}, (v2f){v1.z, v1.w}, (v2f){v2.x, v2.y}};
+        v2f z[NPAIR];
+#pragma unroll
+        for (int p = 0; p < NPAIR; ++p) z[p] = quad_pair(v, p);
         deg_in += 1.f;
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(z[p], sc, pt[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(z[p], sc, pt[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = pk_fma_lo(wt[p], a01, z[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = pk_fma_lo(wt[p], a01, z[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = pk_fma_hi(wt[5 + p], a01, z[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = pk_fma_hi(wt[NPAIR + p], a01, z[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = pk_fma_lo_clamp(wt[10 + p], a2, z[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = pk_fma_lo_clamp(wt[2 * NPAIR + p], a2, z[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) S_to[p] += z[p];
+        for (int p = 0; p < NPAIR; ++p) S_to[p] += z[p];
       }
       if (w & SLOT_OUT) {
-        v2f z[5] = {(v2f){v2.z, v2.w}, (v2f){v3.x, v3.y}, (v2f){v3.z, v3.w}, (v2f){v4.x, v4.y}, (v2f){v4.z, v4.w}};
+        v2f z[NPAIR];
+#pragma unroll
+        for (int p = 0; p < NPAIR; ++p) z[p] = quad_pair(v, NPAIR + p);
         deg_out += 1.f;
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(z[p], sc, pf[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(z[p], sc, pf[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = pk_fma_lo(wf[p], a01, z[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = pk_fma_lo(wf[p], a01, z[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = pk_fma_hi(wf[5 + p], a01, z[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = pk_fma_hi(wf[NPAIR + p], a01, z[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) z[p] = pk_fma_lo_clamp(wf[10 + p], a2, z[p]);
+        for (int p = 0; p < NPAIR; ++p) z[p] = pk_fma_lo_clamp(wf[2 * NPAIR + p], a2, z[p]);
 #pragma unroll
-        for (int p = 0; p < 5; ++p) S_fr[p] += z[p];
+        for (int p = 0; p < NPAIR; ++p) S_fr[p] += z[p];
       }
     }
     c0 = nx;
   }
   const v2f us = splat(RELU_UNSCALE);
 #pragma unroll
-  for (int p = 0; p < 5; ++p) {
+  for (int p = 0; p < NPAIR; ++p) {
     S_to[p] *= us;
     S_fr[p] *= us;
   }

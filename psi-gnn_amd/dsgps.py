@@ -82,8 +82,7 @@ class ModelDSGPS(nn.Module):
         self.config = dict(config)
         self.mixed = (self.config.get("bc") == "mixed") if mixed is None else bool(mixed)
         d, p = self.config["latent_dim"], 3 if self.mixed else 2
-        if d != engine.D:
-            raise nat.NativeError(f"HIP kernels are built for latent_dim = {engine.D}")
+        nat.require_default_width(nat.check_width(d), "the DS-GPS baseline")
         self.laynorm = nn.LayerNorm(d)   # declared (and checkpointed) by the reference, unused in its forward
         self.phi_to = Phi_to([2 * d + 3, d, d], nn.ReLU())
         self.phi_from = Phi_from([2 * d + 3, d, d], nn.ReLU())

@@ -83,8 +83,7 @@ class DeepStatisticalSolver(nn.Module):
         super().__init__()
         self.config = dict(config)
         d, k = self.config["latent_dim"], self.config["k"]
-        if d != engine.D:
-            raise nat.NativeError(f"HIP kernels are built for latent_dim = {engine.D}")
+        nat.require_default_width(nat.check_width(d), "the DSS baseline")
         self.phi_to_list = nn.ModuleList([Phi_to([2 * d + 1, d, d], nn.ReLU()) for _ in range(k)])
         self.phi_from_list = nn.ModuleList([Phi_from([2 * d + 1, d, d], nn.ReLU()) for _ in range(k)])
         self.psi_list = nn.ModuleList([Psi([3 * d + 3, d, d], nn.ReLU()) for _ in range(k)])

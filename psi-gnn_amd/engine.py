@@ -14,7 +14,13 @@ import torch
 
 from . import _native as nat
 
-D = nat.D
+D = nat.D                                # the default latent width (libpsignn_hip.so: every entry point)
+SUPPORTED_WIDTHS = nat.SUPPORTED_WIDTHS  # widths with a library; other than D: forward inference only (libpsignn_hip_d<w>.so)
+
+
+def width_of(sd) -> int:
+    """Latent width of a reference state dict (``deqdss.f.laynorm.weight``); NativeError listing the supported widths otherwise."""
+    return nat.check_width(sd["deqdss.f.laynorm.weight"].numel())
 
 
 # ---------------------------------------------------------------------------------------------
@@ -32,20 +38,24 @@ def pack_weights(sd, device=None) -> torch.Tensor:
     """Flatten the ``deqdss.f.*`` tensors of a reference state_dict into the kernel layout.
 
     Key layout of the reference: dirichlet/psignn/model.py:265-277 (mixed/psignn/model.py:198-214),
-    SURVEY §8b.  Order (csrc/common.h): shared{ln_gamma, ln_beta, alpha_w, alpha_b} padded to 64;
+    SURVEY §8b.  Order (csrc/common.h): shared{ln_gamma, ln_beta, alpha_w, alpha_b} padded to a multiple of 16 (64 at d = 10);
     per layer phi_to{W1,b1,W2,b2} phi_from{..} update{U1,c1,U2,c2}; mixed tail phi_neumann, update_neumann.
+    The latent width d is read from the state dict; every size below is WLayout's expression in d (at d = 10: 64, 244, 112,
+    950, 620), and ``PackedWeights`` checks the total against the library of that width.
     """
+    D = width_of(sd)   # (shadows the module's default width: the layout below is written in terms of this state dict's)
     mixed = is_mixed_state_dict(sd)
     nl = n_layers_of(sd)
     P = "deqdss.f."
     g = lambda k: sd[P + k].detach().to("cpu", torch.float32).reshape(-1)
     p = 3 if mixed else 2
-    if sd[P + "laynorm.weight"].numel() != D:
-        raise nat.NativeError(f"latent_dim {sd[P + 'laynorm.weight'].numel()} != {D}: the HIP kernels are built for d = {D}")
+    rup = lambda n, k: (n + k - 1) // k * k
+    shared_sz, fold_sz, nfold_sz = rup(5 * D + 4, 16), rup(2 * D * D + 4 * D + 2, 4), rup(D * D + D, 4)
+    tpl_sz, tpn_sz = 8 * D * D + 15 * D, 5 * D * D + 12 * D
     if sd[P + "alpha.0.weight"].numel() != 3 * D + p:
         raise nat.NativeError("alpha gate width does not match the boundary-condition family")
     shared = torch.cat([g("laynorm.weight"), g("laynorm.bias"), g("alpha.0.weight"), g("alpha.0.bias")])
-    parts = [torch.nn.functional.pad(shared, (0, 64 - shared.numel()))]
+    parts = [torch.nn.functional.pad(shared, (0, shared_sz - shared.numel()))]
     for l in range(nl):
         for phi in ("phi_to_list", "phi_from_list"):
             parts += [g(f"{phi}.{l}.mlp.mlp.0.weight"), g(f"{phi}.{l}.mlp.mlp.0.bias"),
@@ -64,7 +74,7 @@ def pack_weights(sd, device=None) -> torch.Tensor:
         for phi, c0 in (("phi_to_list", D), ("phi_from_list", 2 * D)):
             fold.append((wa[c0:c0 + D] @ m(f"{phi}.{l}.mlp.mlp.2.bias")).reshape(1))
         fold = torch.cat(fold).to(torch.float32)
-        parts.append(torch.nn.functional.pad(fold, (0, 244 - fold.numel())))
+        parts.append(torch.nn.functional.pad(fold, (0, fold_sz - fold.numel())))
     if mixed:
         parts += [g("phi_neumann.mlp.mlp.0.weight"), g("phi_neumann.mlp.mlp.0.bias"),
                   g("phi_neumann.mlp.mlp.2.weight"), g("phi_neumann.mlp.mlp.2.bias"),
@@ -74,7 +84,7 @@ def pack_weights(sd, device=None) -> torch.Tensor:
         N1 = m("update_neumann.mlp.0.weight")
         nf = torch.cat([(N1[:, D:2 * D] @ m("phi_neumann.mlp.mlp.2.weight")).reshape(-1),
                         N1[:, D:2 * D] @ m("phi_neumann.mlp.mlp.2.bias")]).to(torch.float32)
-        parts.append(torch.nn.functional.pad(nf, (0, 112 - nf.numel())))
+        parts.append(torch.nn.functional.pad(nf, (0, nfold_sz - nf.numel())))
     # ---- transposed section for the tile kernel: [in k][out o] blocks (WLayout::T_* / N_*)
     m = lambda k: sd[P + k].detach().to("cpu", torch.float64)
     f32 = lambda t: t.to(torch.float32).reshape(-1)
@@ -93,11 +103,11 @@ def pack_weights(sd, device=None) -> torch.Tensor:
         tp = [f32(Wt[:, D:2 * D].t()), f32(Wf[:, D:2 * D].t()), f32(Wt[:, :D].t()), f32(Wf[:, :D].t()),
               f32(Wt[:, 2 * D:].t() * mir), f32(Wf[:, 2 * D:].t()),
               f32(m(f"phi_to_list.{l}.mlp.mlp.0.bias")), f32(m(f"phi_from_list.{l}.mlp.mlp.0.bias")),
-              f32(U1[:, :D].t()), f32(G_to.t()), f32(G_fr.t()), padto(U1[:, 3 * D:].t(), 30),
+              f32(U1[:, :D].t()), f32(G_to.t()), f32(G_fr.t()), padto(U1[:, 3 * D:].t(), 3 * D),
               f32(m(f"update_list.{l}.mlp.0.bias")), f32(g_to), f32(g_fr), f32(U2.t()),
               f32(m(f"update_list.{l}.mlp.2.bias"))]
         tp = torch.cat(tp)
-        assert tp.numel() == 950
+        assert tp.numel() == tpl_sz
         parts.append(tp)
     if mixed:
         Wn, N1, N2 = m("phi_neumann.mlp.mlp.0.weight"), m("update_neumann.mlp.0.weight"), m("update_neumann.mlp.2.weight")
@@ -105,9 +115,9 @@ def pack_weights(sd, device=None) -> torch.Tensor:
         gn = N1[:, D:2 * D] @ m("phi_neumann.mlp.mlp.2.bias")
         tn = torch.cat([f32(Wn[:, D:2 * D].t()), f32(Wn[:, :D].t()), f32(Wn[:, 2 * D:].t()),
                         f32(m("phi_neumann.mlp.mlp.0.bias")), f32(N1[:, :D].t()), f32(Gn.t()),
-                        padto(N1[:, 2 * D:].t(), 50), f32(m("update_neumann.mlp.0.bias")), f32(gn), f32(N2.t()),
+                        padto(N1[:, 2 * D:].t(), 5 * D), f32(m("update_neumann.mlp.0.bias")), f32(gn), f32(N2.t()),
                         f32(m("update_neumann.mlp.2.bias"))])
-        assert tn.numel() == 620
+        assert tn.numel() == tpn_sz
         parts.append(tn)
     flat = torch.cat(parts).contiguous()
     return flat if device is None else flat.to(device)
@@ -117,10 +127,12 @@ class PackedWeights:
     def __init__(self, sd, device):
         self.mixed = is_mixed_state_dict(sd)
         self.n_layers = n_layers_of(sd)
+        self.width = width_of(sd)
+        self.lib = nat.lib(self.width)   # the library these weights are packed for; the maps made from them call it
         self.flat = pack_weights(sd, device)
-        expect = nat.lib().psignn_weights_size(int(self.mixed), self.n_layers)
+        expect = self.lib.psignn_weights_size(int(self.mixed), self.n_layers)
         if self.flat.numel() != expect:
-            raise nat.NativeError(f"packed weight length {self.flat.numel()} != native layout {expect}")
+            raise nat.NativeError(f"packed weight length {self.flat.numel()} != native layout {expect} at latent_dim {self.width}")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -206,35 +218,41 @@ class MeshPlan:
                   "psignn_plan_export")
         return out
 
-    def _grown(self, attr, base_query, n_layers):
-        """One scratch buffer per kind, grown in place of the old one when a deeper block needs more: the kind's own floats
-        plus the layer workspace of a multi-layer block (``psignn_f_layers_workspace_floats``)."""
-        extra = int(nat.lib().psignn_f_layers_workspace_floats(self.handle, int(n_layers)))
-        if extra < 0:
-            raise nat.NativeError(f"n_layers = {n_layers} is out of range")
-        n = int(base_query(self.handle)) + extra
+    def _grown(self, attr, query, n_layers, lib=None):
+        """One scratch buffer per kind, grown in place of the old one when more is needed: ``lib``'s own count for the kind
+        (``query``: the name of its ``*_workspace_floats`` entry) plus, at the default width, the layer workspace of a
+        multi-layer block (``psignn_f_layers_workspace_floats``; the width libraries hold no derivative of a layer chain)."""
+        lib = lib or nat.lib()
+        n = int(getattr(lib, query)(self.handle))
+        if lib.width == D:
+            extra = int(lib.psignn_f_layers_workspace_floats(self.handle, int(n_layers)))
+            if extra < 0:
+                raise nat.NativeError(f"n_layers = {n_layers} is out of range")
+            n += extra
         buf = getattr(self, attr)
         if buf is None or buf.numel() < n:
             buf = torch.empty(n, dtype=torch.float32, device=self.device)
             setattr(self, attr, buf)
         return buf
 
-    def workspace(self):
-        return self._grown("_work", nat.lib().psignn_f_workspace_floats, 1)
+    def workspace(self, lib=None):
+        """Scratch of f.  The plan itself is width-free (one plan serves maps of every latent width); the scratch is sized by
+        the library that is about to use it (``lib``: a ``nat.lib(width)``, default the default width's) and only ever grows."""
+        return self._grown("_work", "psignn_f_workspace_floats", 1, lib)
 
     def derivative_workspace(self, n_layers):
         """Scratch of the JVP / VJP entry points: ``workspace()``'s buffer, grown for a multi-layer block's layer states."""
-        return self._grown("_work", nat.lib().psignn_f_workspace_floats, n_layers)
+        return self._grown("_work", "psignn_f_workspace_floats", n_layers)
 
     def pgrad_workspace(self, n_layers=1):
-        return self._grown("_pwork", nat.lib().psignn_f_param_vjp_workspace_floats, n_layers)
+        return self._grown("_pwork", "psignn_f_param_vjp_workspace_floats", n_layers)
 
     def vjp_backward_workspace(self, n_layers=1):
-        return self._grown("_jwork", nat.lib().psignn_f_vjp_backward_workspace_floats, n_layers)
+        return self._grown("_jwork", "psignn_f_vjp_backward_workspace_floats", n_layers)
 
     def vjp_backward_p_workspace(self):
         """Scratch of the plan-order (tile) backward of the VJP; shares ``vjp_backward_workspace()``'s buffer."""
-        return self._grown("_jwork", nat.lib().psignn_f_vjp_backward_p_workspace_floats, 1)
+        return self._grown("_jwork", "psignn_f_vjp_backward_p_workspace_floats", 1)
 
     def permute(self, t, to_plan=True):
         """Rows of an (N, cols) float tensor between the caller's numbering and plan order."""
@@ -278,14 +296,16 @@ class FixedPointMap:
             raise nat.NativeError("boundary-condition family of the weights and of the batch differ "
                                   f"(weights mixed={weights.mixed}, batch mixed={plan.mixed})")
         self.plan, self.weights = plan, weights
+        self.width, self.lib = weights.width, weights.lib
         self.h0 = _f32c(h_initial)
         self.prb = _f32c(prb_data)
         self.nrm = None if normals is None else _f32c(normals)
         if plan.mixed and self.nrm is None:
             raise nat.NativeError("mixed problems need batch.unit_normal_vector")
         exp_p = 3 if plan.mixed else 2
-        if self.prb.shape != (plan.N, exp_p) or self.h0.shape != (plan.N, D):
-            raise nat.NativeError(f"shape mismatch: prb_data {tuple(self.prb.shape)}, h_initial {tuple(self.h0.shape)}")
+        if self.prb.shape != (plan.N, exp_p) or self.h0.shape != (plan.N, self.width):
+            raise nat.NativeError(f"shape mismatch: prb_data {tuple(self.prb.shape)}, h_initial {tuple(self.h0.shape)} "
+                                  f"(weights of latent_dim {self.width})")
         self._p = None  # plan-order copies of h0 / prb / normals, made on first use
 
     lin_neumann = "direct"   # what ``linearize_p`` gives a new Linearization (the model sets its ``lin_neumann`` config value)
@@ -298,31 +318,38 @@ class FixedPointMap:
     def from_plan(self, Hp):
         return self.plan.permute(Hp, False)
 
+    def _forward_only(self, what):
+        nat.require_default_width(self.width, what)
+
+    def _state(self, H, name="H"):
+        Hc = _f32c(H)
+        if Hc.shape != (self.plan.N, self.width):
+            raise nat.NativeError(f"{name} has shape {tuple(Hc.shape)}, expected {(self.plan.N, self.width)}")
+        return Hc
+
     def fp(self, Hp):
         """f in plan order: Hp and the result are numbered like the plan's tiles (see MeshPlan.permute)."""
         if self._p is None:
             self._p = (self.to_plan(self.h0), self.to_plan(self.prb), None if self.nrm is None else self.to_plan(self.nrm))
         h0p, prbp, nrmp = self._p
-        Hc = _f32c(Hp)
+        Hc = self._state(Hp, "Hp")
         out = torch.empty_like(Hc)
         with torch.cuda.device(Hc.device):
-            nat.check(nat.lib().psignn_f_forward_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
-                                                   nat.ptr(Hc), nat.ptr(h0p), nat.ptr(prbp), nat.ptr(nrmp),
-                                                   nat.ptr(out), nat.ptr(self.plan.workspace()),
-                                                   nat.stream_ptr(Hc.device)), "psignn_f_forward_p")
+            nat.check(self.lib.psignn_f_forward_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                                  nat.ptr(Hc), nat.ptr(h0p), nat.ptr(prbp), nat.ptr(nrmp),
+                                                  nat.ptr(out), nat.ptr(self.plan.workspace(self.lib)),
+                                                  nat.stream_ptr(Hc.device)), "psignn_f_forward_p", self.lib)
         return out
 
     def __call__(self, H):
         nat.require_cuda(H, "H")
-        Hc = _f32c(H)
-        if Hc.shape != (self.plan.N, D):
-            raise nat.NativeError(f"H has shape {tuple(Hc.shape)}, expected {(self.plan.N, D)}")
+        Hc = self._state(H)
         out = torch.empty_like(Hc)
         with torch.cuda.device(Hc.device):
-            nat.check(nat.lib().psignn_f_forward(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
-                                                 nat.ptr(Hc), nat.ptr(self.h0), nat.ptr(self.prb), nat.ptr(self.nrm),
-                                                 nat.ptr(out), nat.ptr(self.plan.workspace()),
-                                                 nat.stream_ptr(Hc.device)), "psignn_f_forward")
+            nat.check(self.lib.psignn_f_forward(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                                nat.ptr(Hc), nat.ptr(self.h0), nat.ptr(self.prb), nat.ptr(self.nrm),
+                                                nat.ptr(out), nat.ptr(self.plan.workspace(self.lib)),
+                                                nat.stream_ptr(Hc.device)), "psignn_f_forward", self.lib)
         return out
 
     def picard_p(self, Hp, n):
@@ -330,17 +357,18 @@ class FixedPointMap:
         if self._p is None:
             self.fp(Hp)
         h0p, prbp, nrmp = self._p
-        x = _f32c(Hp).clone()
+        x = self._state(Hp, "Hp").clone()
         tmp = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            nat.check(nat.lib().psignn_picard_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
-                                                nat.ptr(x), nat.ptr(tmp), nat.ptr(h0p), nat.ptr(prbp), nat.ptr(nrmp),
-                                                nat.ptr(self.plan.workspace()), int(n), nat.stream_ptr(x.device)),
-                      "psignn_picard_p")
+            nat.check(self.lib.psignn_picard_p(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                               nat.ptr(x), nat.ptr(tmp), nat.ptr(h0p), nat.ptr(prbp), nat.ptr(nrmp),
+                                               nat.ptr(self.plan.workspace(self.lib)), int(n), nat.stream_ptr(x.device)),
+                      "psignn_picard_p", self.lib)
         return x
 
     def jvp(self, H, V):
         """Analytic J_f(H) V."""
+        self._forward_only("jvp")
         Hc, Vc = _f32c(H), _f32c(V)
         out = torch.empty_like(Hc)
         with torch.cuda.device(Hc.device):
@@ -353,6 +381,7 @@ class FixedPointMap:
     def jvp_p(self, Hp, Vp, out=None):
         """J_f(Hp) Vp with everything in plan order (tiled plans, any depth; a multi-layer dirichlet block evaluates its layer
         states first).  ``out``: a contiguous (N, d) float32 tensor to write into (e.g. a row of a Krylov basis)."""
+        self._forward_only("jvp_p")
         if self._p is None:
             self.fp(Hp)
         _, prbp, nrmp = self._p
@@ -385,7 +414,7 @@ class FixedPointMap:
             return sv
         if sv is not None:
             sv.close()
-        return DeviceBroyden(plan=self.plan, threshold=threshold, keep_trace=False, history_dtype=history_dtype)
+        return DeviceBroyden(plan=self.plan, threshold=threshold, keep_trace=False, history_dtype=history_dtype, width=self.width)
 
     def return_broyden(self, sv):
         import os
@@ -401,7 +430,7 @@ class FixedPointMap:
 
     def can_linearize(self):
         """True when ``linearize_p`` applies: tiled plan; dirichlet family: single-layer block (csrc/fgnn_tile_lin.hip)."""
-        return bool(self.plan.tiled) and (bool(self.plan.mixed) or self.weights.n_layers == 1)
+        return self.width == D and bool(self.plan.tiled) and (bool(self.plan.mixed) or self.weights.n_layers == 1)
 
     def linearize_p(self, Hp, lin=None, neumann=None):
         """Linearisation of f at ``Hp`` (plan order) for solvers that apply J_f(Hp) to many vectors: one pass stores the relu
@@ -410,6 +439,7 @@ class FixedPointMap:
         map to rebuild at the new state (keeps its device buffers).  ``neumann`` (a new handle only): ``"direct"`` or
         ``"stored"`` as in ``Linearization``; None -> the map's ``lin_neumann`` (``"direct"`` unless set)."""
         neumann = check_lin_neumann(self.lin_neumann if neumann is None else neumann)
+        self._forward_only("linearize_p")
         if self._p is None:
             self.fp(Hp)
         if lin is None:
@@ -419,6 +449,7 @@ class FixedPointMap:
 
     def vjp(self, H, Wv):
         """Wv^T J_f(H): what ``autograd.grad(f(H), H, Wv)`` returns in the reference (model.py:214,432,449)."""
+        self._forward_only("vjp")
         Hc, Wc = _f32c(H), _f32c(Wv)
         out = torch.empty_like(Hc)
         with torch.cuda.device(Hc.device):
@@ -431,6 +462,7 @@ class FixedPointMap:
 
     def vjp_p(self, Hp, Wp):
         """vjp with Hp, Wp and the result in plan order (tiled kernels where the plan has tiles, any depth)."""
+        self._forward_only("vjp_p")
         if self._p is None:
             self.fp(Hp)
         _, prbp, nrmp = self._p
@@ -448,6 +480,7 @@ class FixedPointMap:
         """(flat parameter gradient, Wp^T df/dh) at Hp, everything in plan order (tiled dirichlet plans, any depth).
 
         The flat gradient follows the leading section of the packed weights; ``unpack_param_grads`` names it."""
+        self._forward_only("param_vjp_p")
         if self._p is None:
             self.fp(Hp)
         _, prbp, _ = self._p
@@ -467,6 +500,7 @@ class FixedPointMap:
         """What ``loss.backward()`` leaves in the ``deqdss.f`` parameters for new_H = f(H) with cotangent Wv
         (dirichlet/psignn/model.py:203-225; mixed/psignn/model.py likewise): ({name: grad}, Wv^T df/dH) in the
         caller's numbering.  Both families, any depth, tiled or not."""
+        self._forward_only("param_vjp")
         grads, out, _ = self.param_vjp_init(H, Wv, with_init=False)
         return grads, out
 
@@ -474,6 +508,7 @@ class FixedPointMap:
         """``param_vjp`` and the gradient w.r.t. h_initial: ({name: grad}, Wv^T df/dH, Wv^T df/dH_init).  The latter is the
         Dirichlet rows of the cotangent on every layer's output (those rows are copies of h_initial after every layer,
         model.py:298); for a single-layer block, Wv on the Dirichlet rows."""
+        self._forward_only("param_vjp_init")
         Hc, Wc = _f32c(H), _f32c(Wv)
         l = nat.lib()
         grad = torch.empty(int(l.psignn_param_grad_size(int(self.weights.mixed), self.weights.n_layers)),
@@ -490,12 +525,13 @@ class FixedPointMap:
 
     def can_tile_vjp_backward(self):
         """True when ``vjp_backward_p`` applies: tiled plan of the dirichlet family, single-layer block (csrc/fgnn_tile_jr.hip)."""
-        return bool(nat.lib().psignn_f_vjp_backward_tiled_ok(self.plan.handle, int(self.weights.n_layers)))
+        return self.width == D and bool(nat.lib().psignn_f_vjp_backward_tiled_ok(self.plan.handle, int(self.weights.n_layers)))
 
     def vjp_backward_p(self, Hp, Vp, Gp):
         """``vjp_backward`` on the tile kernels with Hp, Vp, Gp and the returned d / dH in plan order:
         (flat parameter gradient, d / dH).  ``unpack_param_grads`` names the flat gradient.  Where
         ``can_tile_vjp_backward()`` is false this raises ``NativeError`` and launches nothing."""
+        self._forward_only("vjp_backward_p")
         if not self.can_tile_vjp_backward():
             raise nat.NativeError("vjp_backward_p: the tile form needs a tiled plan of the dirichlet family and a single-layer "
                                   "block (vjp_backward takes every plan)")
@@ -518,6 +554,7 @@ class FixedPointMap:
         backward computes for ``autograd.grad(f(H), H, V, create_graph=True)`` (jac_loss_estimate,
         dirichlet/psignn/model.py:416-435).  Both families, any depth, caller's numbering.  ``tiled=True``: the tile
         kernels (permute in, ``vjp_backward_p``, permute out); ``NativeError`` where ``can_tile_vjp_backward()`` is false."""
+        self._forward_only("vjp_backward")
         if tiled:
             flat, out_p = self.vjp_backward_p(self.to_plan(H), self.to_plan(V), self.to_plan(Gbar))
             return unpack_param_grads(flat, self.weights.n_layers, self.weights.mixed), self.from_plan(out_p)
@@ -538,9 +575,9 @@ class FixedPointMap:
         Hc = _f32c(H)
         out = torch.empty_like(Hc)
         with torch.cuda.device(Hc.device):
-            nat.check(nat.lib().psignn_phi(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
-                                           layer, which, nat.ptr(Hc), nat.ptr(out), nat.ptr(self.plan.workspace()),
-                                           nat.stream_ptr(Hc.device)), "psignn_phi")
+            nat.check(self.lib.psignn_phi(self.plan.handle, nat.ptr(self.weights.flat), self.weights.n_layers,
+                                           layer, which, nat.ptr(Hc), nat.ptr(out), nat.ptr(self.plan.workspace(self.lib)),
+                                           nat.stream_ptr(Hc.device)), "psignn_phi", self.lib)
         return out
 
 
@@ -945,6 +982,7 @@ class Linearization:
 
     def __init__(self, fmap, neumann="direct"):
         neumann = check_lin_neumann(neumann)
+        nat.require_default_width(getattr(fmap, "width", D), "Linearization")
         if not fmap.can_linearize():
             raise nat.NativeError("linearize_p: tiled plans (dirichlet family: single-layer blocks); use jvp_p otherwise")
         self.fmap = fmap
@@ -1024,8 +1062,11 @@ def history_code(history_dtype) -> int:
 
 class DeviceBroyden:
     def __init__(self, plan=None, threshold=50, keep_trace=False, n_elems=None, seq_len=D, device=None, shard_elems=0,
-                 history_dtype=torch.float32):
-        """``shard_elems`` > 0: the solver will run inside ``broyden_solve_batch`` with others; its reduction shapes are sized
+                 history_dtype=torch.float32, width=None):
+        """``width``: the latent width of the maps this solver will serve (default: the default width; a plan-less solver is flat
+        over its ``n_elems`` and takes any ``seq_len``).  The solver is made by that width's library and refuses a map of another.
+
+        ``shard_elems`` > 0: the solver will run inside ``broyden_solve_batch`` with others; its reduction shapes are sized
         for the whole shard (sum of N * d), and its single-mesh solves give the same bits as the batched ones.
 
         ``history_dtype``: element type of the stored rank-one pairs U_j, V_j.  ``torch.bfloat16`` halves their memory and the
@@ -1034,6 +1075,7 @@ class DeviceBroyden:
         is never batched (``shard_batchable`` is False)."""
         hist = history_code(history_dtype)
         h = C.c_void_p()
+        self.width = D if width is None else nat.check_width(width)
         self.plan = plan
         self.threshold = int(threshold)
         self.keep_trace = bool(keep_trace)
@@ -1041,35 +1083,49 @@ class DeviceBroyden:
         self.device = plan.device if plan is not None else device
         with torch.cuda.device(self.device):
             if hist:
-                nat.check(nat.lib().psignn_broyden_create_opts(
+                self._check(self.lib.psignn_broyden_create_opts(
                     C.byref(h), plan.handle if plan is not None else None, 0 if plan is not None else int(n_elems),
                     0 if plan is not None else int(seq_len), self.threshold, int(keep_trace), int(shard_elems), hist),
                     "psignn_broyden_create_opts")
-                self.M = plan.N * D if plan is not None else int(n_elems)
+                self.M = plan.N * self.width if plan is not None else int(n_elems)
             elif plan is not None:
-                nat.check(nat.lib().psignn_broyden_create_for_batch(C.byref(h), plan.handle, self.threshold, int(keep_trace),
+                self._check(self.lib.psignn_broyden_create_for_batch(C.byref(h), plan.handle, self.threshold, int(keep_trace),
                                                                      int(shard_elems)), "psignn_broyden_create_for_batch")
-                self.M = plan.N * D
+                self.M = plan.N * self.width
             else:
-                nat.check(nat.lib().psignn_broyden_create_n(C.byref(h), int(n_elems), int(seq_len), self.threshold,
+                self._check(self.lib.psignn_broyden_create_n(C.byref(h), int(n_elems), int(seq_len), self.threshold,
                                                             int(keep_trace)), "psignn_broyden_create_n")
                 self.M = int(n_elems)
         self.handle = h
-        self._fin = weakref.finalize(self, nat.lib().psignn_broyden_destroy, h)
+        self._fin = weakref.finalize(self, self.lib.psignn_broyden_destroy, h)
+
+    width = D   # (class default: a solver object filled in by hand around a native handle is a default-width one)
+
+    @property
+    def lib(self):
+        """The library this solver was made by: its latent width's."""
+        return nat.lib(self.width)
+
+    def _check(self, rc, what=""):
+        nat.check(rc, what, self.lib)
+
+    def _same_width(self, fmap):
+        if getattr(fmap, "lib", None) is not self.lib:
+            raise nat.NativeError(f"solver of latent_dim {self.width} was handed a map of latent_dim {getattr(fmap, 'width', '?')}")
 
     def close(self):
         self._fin()
 
     @property
     def nbytes(self):
-        return int(nat.lib().psignn_broyden_bytes(self.handle))
+        return int(self.lib.psignn_broyden_bytes(self.handle))
 
     def set_stop_mode(self, stop_mode: str):
         """"rel" (default, every call site of the reference) or "abs" (solver.py:116,140,174)."""
         if stop_mode not in ("rel", "abs"):
             raise nat.NativeError(f"stop_mode {stop_mode!r}: 'rel' or 'abs'")
         self.stop_mode = stop_mode
-        nat.check(nat.lib().psignn_broyden_set_stop_mode(self.handle, int(stop_mode == "abs")), "psignn_broyden_set_stop_mode")
+        self._check(self.lib.psignn_broyden_set_stop_mode(self.handle, int(stop_mode == "abs")), "psignn_broyden_set_stop_mode")
 
     def _collect(self, info, rel, abs_, shape, dev):
         n_it = info.n_iter
@@ -1083,12 +1139,13 @@ class DeviceBroyden:
         return out
 
     def solve(self, fmap: FixedPointMap, eps, poll_every=8):
+        self._same_width(fmap)
         result = torch.empty_like(fmap.h0)
         info = nat.SolveInfo()
         rel = (C.c_double * self.threshold)()
         abs_ = (C.c_double * self.threshold)()
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().psignn_broyden_solve(
+            self._check(self.lib.psignn_broyden_solve(
                 self.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(fmap.h0), nat.ptr(fmap.prb),
                 nat.ptr(fmap.nrm), float(eps), int(poll_every), nat.ptr(result), C.byref(info), rel, abs_,
                 nat.stream_ptr(self.device)), "psignn_broyden_solve")
@@ -1099,6 +1156,8 @@ class DeviceBroyden:
     def solve_adjoint(self, fmap: FixedPointMap, h_star, grad, eps, poll_every=8, lin=None):
         """y = J_f(h*)^T y + grad, y_0 = 0, entirely on the device (VJP kernel inside the Broyden loop).  ``lin``: a Linearization
         of ``fmap`` built at h* (plan order, on this solver's plan); the loop then applies ``lin.vjp_p`` and ``h_star`` is not read."""
+        nat.require_default_width(self.width, "solve_adjoint")
+        self._same_width(fmap)
         hs, gr = _f32c(h_star), _f32c(grad)
         result = torch.empty_like(gr)
         info = nat.SolveInfo()
@@ -1106,14 +1165,14 @@ class DeviceBroyden:
         abs_ = (C.c_double * self.threshold)()
         with torch.cuda.device(self.device):
             if lin is not None:
-                nat.check(nat.lib().psignn_broyden_solve_adjoint_lin(
+                self._check(self.lib.psignn_broyden_solve_adjoint_lin(
                     self.handle, lin.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(gr), float(eps),
                     int(poll_every), nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device)),
                     "psignn_broyden_solve_adjoint_lin")
                 out = self._collect(info, rel, abs_, result.shape, result.device)
                 out["result"] = result
                 return out
-            nat.check(nat.lib().psignn_broyden_solve_adjoint(
+            self._check(self.lib.psignn_broyden_solve_adjoint(
                 self.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(hs), nat.ptr(fmap.prb),
                 nat.ptr(fmap.nrm), nat.ptr(gr), float(eps), int(poll_every), nat.ptr(result), C.byref(info), rel, abs_,
                 nat.stream_ptr(self.device)), "psignn_broyden_solve_adjoint")
@@ -1124,7 +1183,7 @@ class DeviceBroyden:
     def iterate(self, i, like):
         dst = torch.empty_like(like)
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().psignn_broyden_get_iterate(self.handle, int(i), nat.ptr(dst),
+            self._check(self.lib.psignn_broyden_get_iterate(self.handle, int(i), nat.ptr(dst),
                                                            nat.stream_ptr(self.device)), "psignn_broyden_get_iterate")
         return dst
 
@@ -1133,7 +1192,7 @@ class DeviceBroyden:
         utilities/solver.py:190-191) or, ``which="update"``, the current update vector (``j`` ignored); caller's numbering."""
         dst = torch.empty_like(like)
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().psignn_broyden_get_pair(self.handle, int(j), {"U": 0, "V": 1, "update": 2, "parta": 3}[which], nat.ptr(dst),
+            self._check(self.lib.psignn_broyden_get_pair(self.handle, int(j), {"U": 0, "V": 1, "update": 2, "parta": 3}[which], nat.ptr(dst),
                                                         nat.stream_ptr(self.device)), "psignn_broyden_get_pair")
         return dst
 
@@ -1149,7 +1208,7 @@ class DeviceBroyden:
 
         def phi(s):
             xt = torch.empty_like(like)
-            nat.check(lib.psignn_broyden_ext_trial_x(self.handle, float(s), nat.ptr(xt), sp), "ext_trial_x")
+            self._check(lib.psignn_broyden_ext_trial_x(self.handle, float(s), nat.ptr(xt), sp), "ext_trial_x")
             fx = _f32c(f(xt.clone()))
             g = fx - xt
             val = float(g.norm()) ** 2 if bool(torch.isfinite(g).all()) else float("inf")
@@ -1183,10 +1242,10 @@ class DeviceBroyden:
         """Generic f (any Python callable on device tensors): one f call per iteration from the host (ls=True: plus the
         trial evaluations of the Armijo line search)."""
         x0c = _f32c(x0)
-        lib, sp = nat.lib(), nat.stream_ptr(self.device)
+        lib, sp = self.lib, nat.stream_ptr(self.device)
         with torch.cuda.device(self.device):
             fx = _f32c(f(x0c))
-            nat.check(lib.psignn_broyden_ext_begin(self.handle, nat.ptr(x0c), nat.ptr(fx), sp), "ext_begin")
+            self._check(lib.psignn_broyden_ext_begin(self.handle, nat.ptr(x0c), nat.ptr(fx), sp), "ext_begin")
             done = C.c_int(0)
             xn = torch.empty_like(x0c)
             phi_cur = float((fx - x0c).norm()) ** 2 if ls else 0.0
@@ -1196,18 +1255,18 @@ class DeviceBroyden:
                     s, fx_s, phi_s = self._armijo_step(f, phi_cur, lib, sp, x0c)
                     self.ls_steps.append(s)
                     if s != 1.0:
-                        nat.check(lib.psignn_broyden_ext_scale_step(self.handle, float(s), sp), "ext_scale_step")
-                    nat.check(lib.psignn_broyden_ext_next_x(self.handle, nat.ptr(xn), sp), "ext_next_x")
+                        self._check(lib.psignn_broyden_ext_scale_step(self.handle, float(s), sp), "ext_scale_step")
+                    self._check(lib.psignn_broyden_ext_next_x(self.handle, nat.ptr(xn), sp), "ext_next_x")
                     fx = fx_s if fx_s is not None else _f32c(f(xn.clone()))
                     phi_cur = phi_s if phi_s is not None else float((fx - xn).norm()) ** 2
-                    nat.check(lib.psignn_broyden_ext_update(self.handle, nat.ptr(fx), float(eps), C.byref(done), sp),
+                    self._check(lib.psignn_broyden_ext_update(self.handle, nat.ptr(fx), float(eps), C.byref(done), sp),
                               "ext_update")
                     if done.value:
                         break
                     continue
-                nat.check(lib.psignn_broyden_ext_next_x(self.handle, nat.ptr(xn), sp), "ext_next_x")
+                self._check(lib.psignn_broyden_ext_next_x(self.handle, nat.ptr(xn), sp), "ext_next_x")
                 fx = _f32c(f(xn.clone()))
-                nat.check(lib.psignn_broyden_ext_update(self.handle, nat.ptr(fx), float(eps), C.byref(done), sp),
+                self._check(lib.psignn_broyden_ext_update(self.handle, nat.ptr(fx), float(eps), C.byref(done), sp),
                           "ext_update")
                 if done.value:
                     break
@@ -1215,7 +1274,7 @@ class DeviceBroyden:
             info = nat.SolveInfo()
             rel = (C.c_double * self.threshold)()
             abs_ = (C.c_double * self.threshold)()
-            nat.check(lib.psignn_broyden_ext_finish(self.handle, nat.ptr(result), C.byref(info), rel, abs_, sp),
+            self._check(lib.psignn_broyden_ext_finish(self.handle, nat.ptr(result), C.byref(info), rel, abs_, sp),
                       "ext_finish")
         out = self._collect(info, rel, abs_, result.shape, result.device)
         out["result"] = result
@@ -1228,8 +1287,10 @@ def shard_batchable(solvers) -> bool:
     n = len(solvers)
     if n == 0:
         return False
+    if any(s.lib is not solvers[0].lib for s in solvers):   # solvers of different latent widths never share a shard
+        return False
     arr = (C.c_void_p * n)(*[s.handle.value for s in solvers])
-    return bool(nat.lib().psignn_broyden_batchable(n, arr))
+    return bool(solvers[0].lib.psignn_broyden_batchable(n, arr))
 
 
 def broyden_solve_batch(solvers, fmaps, eps, poll_every=8):
@@ -1247,6 +1308,8 @@ def broyden_solve_batch(solvers, fmaps, eps, poll_every=8):
             raise nat.NativeError("batched solve: all meshes must share one packed weight buffer")
         if s.plan is not f.plan:
             raise nat.NativeError("batched solve: solver and map were built from different plans")
+        if s.lib is not w0.lib or f.lib is not w0.lib:
+            raise nat.NativeError("batched solve: solvers and maps of one latent width only")
     dev = solvers[0].device
     thr = solvers[0].threshold
     results = [torch.empty_like(f.h0) for f in fmaps]
@@ -1256,11 +1319,11 @@ def broyden_solve_batch(solvers, fmaps, eps, poll_every=8):
     abs_ = [(C.c_double * s.threshold)() for s in solvers]
     dpp = lambda rows: (C.POINTER(C.c_double) * n)(*[C.cast(r, C.POINTER(C.c_double)) for r in rows])
     with torch.cuda.device(dev):
-        nat.check(nat.lib().psignn_broyden_solve_batch(
+        nat.check(w0.lib.psignn_broyden_solve_batch(
             n, arr([s.handle.value for s in solvers]), nat.ptr(w0.flat), w0.n_layers, arr([nat.ptr(f.h0) for f in fmaps]),
             arr([nat.ptr(f.prb) for f in fmaps]), arr([nat.ptr(f.nrm) for f in fmaps]) if w0.mixed else None,
             float(eps), int(poll_every), arr([nat.ptr(r) for r in results]), infos,
-            dpp(rel), dpp(abs_), nat.stream_ptr(dev)), "psignn_broyden_solve_batch")
+            dpp(rel), dpp(abs_), nat.stream_ptr(dev)), "psignn_broyden_solve_batch", w0.lib)
     outs = []
     for i, s in enumerate(solvers):
         o = s._collect(infos[i], rel[i], abs_[i], results[i].shape, dev)
@@ -1274,6 +1337,8 @@ def adjoint_batchable(solvers, lins) -> bool:
     (``psignn_broyden_adjoint_batchable``): all that ``shard_batchable`` asks of the solvers, and every ``lins[i]`` was made for
     ``solvers[i]``'s plan, has been built and holds a form the batched transposed product takes (dirichlet; mixed only with
     ``neumann="stored"``).  A host-side decision -- real errors of the batched solve still raise."""
+    if any(getattr(s, "width", D) != D for s in solvers):   # the adjoint solves exist at the default width only
+        return False
     n = len(solvers)
     if n == 0 or len(lins) != n or any(l is None or l.handle is None for l in lins):
         return False
@@ -1329,15 +1394,18 @@ class DeviceFixedPointIter:
     (utilities/solver.py:301-341, :215-293) on the device.  The caller evaluates f between the calls; nothing is read back
     per iteration unless asked (``poll``)."""
 
-    def __init__(self, n_elems, device, m=2, threshold=50, keep_trace=False):
+    def __init__(self, n_elems, device, m=2, threshold=50, keep_trace=False, width=None):
+        """``width``: the latent width of the map being iterated (default: the default width): the state lives in that
+        width's library, like the map's other handles.  The arithmetic is flat over ``n_elems``."""
         h = C.c_void_p()
+        self.lib = nat.lib(D if width is None else width)
         self.device, self.M, self.m = device, int(n_elems), int(m)
         self.threshold, self.keep_trace = int(threshold), bool(keep_trace)
         with torch.cuda.device(device):
-            nat.check(nat.lib().psignn_fpiter_create(C.byref(h), self.M, self.m, self.threshold, int(self.keep_trace)),
-                      "psignn_fpiter_create")
+            nat.check(self.lib.psignn_fpiter_create(C.byref(h), self.M, self.m, self.threshold, int(self.keep_trace)),
+                      "psignn_fpiter_create", self.lib)
         self.handle = h
-        self._fin = weakref.finalize(self, nat.lib().psignn_fpiter_destroy, h)
+        self._fin = weakref.finalize(self, self.lib.psignn_fpiter_destroy, h)
 
     def close(self):
         self._fin()
@@ -1347,42 +1415,42 @@ class DeviceFixedPointIter:
 
     def poll(self):
         d = C.c_int(0)
-        nat.check(nat.lib().psignn_fpiter_poll(self.handle, C.byref(d), self._sp()), "psignn_fpiter_poll")
+        nat.check(self.lib.psignn_fpiter_poll(self.handle, C.byref(d), self._sp()), "psignn_fpiter_poll", self.lib)
         return bool(d.value)
 
     # Picard
     def picard_begin(self, x0):
-        nat.check(nat.lib().psignn_picard_begin(self.handle, nat.ptr(x0), self._sp()), "psignn_picard_begin")
+        nat.check(self.lib.psignn_picard_begin(self.handle, nat.ptr(x0), self._sp()), "psignn_picard_begin", self.lib)
 
     def picard_current(self, like):
         x = torch.empty_like(like)
-        nat.check(nat.lib().psignn_picard_current_x(self.handle, nat.ptr(x), self._sp()), "psignn_picard_current_x")
+        nat.check(self.lib.psignn_picard_current_x(self.handle, nat.ptr(x), self._sp()), "psignn_picard_current_x", self.lib)
         return x
 
     def picard_update(self, fx, eps):
-        nat.check(nat.lib().psignn_picard_update(self.handle, nat.ptr(fx), float(eps), None, self._sp()), "psignn_picard_update")
+        nat.check(self.lib.psignn_picard_update(self.handle, nat.ptr(fx), float(eps), None, self._sp()), "psignn_picard_update", self.lib)
 
     # Anderson
     def anderson_begin(self, x0, f0, f1, lam, beta, stop_abs):
-        nat.check(nat.lib().psignn_anderson_begin(self.handle, nat.ptr(x0), nat.ptr(f0), nat.ptr(f1), float(lam), float(beta),
-                                                  int(stop_abs), self._sp()), "psignn_anderson_begin")
+        nat.check(self.lib.psignn_anderson_begin(self.handle, nat.ptr(x0), nat.ptr(f0), nat.ptr(f1), float(lam), float(beta),
+                                                  int(stop_abs), self._sp()), "psignn_anderson_begin", self.lib)
 
     def anderson_next(self, like):
         x = torch.empty_like(like)
-        nat.check(nat.lib().psignn_anderson_next_x(self.handle, nat.ptr(x), self._sp()), "psignn_anderson_next_x")
+        nat.check(self.lib.psignn_anderson_next_x(self.handle, nat.ptr(x), self._sp()), "psignn_anderson_next_x", self.lib)
         return x
 
     def anderson_update(self, fx, eps):
-        nat.check(nat.lib().psignn_anderson_update(self.handle, nat.ptr(fx), float(eps), None, self._sp()),
-                  "psignn_anderson_update")
+        nat.check(self.lib.psignn_anderson_update(self.handle, nat.ptr(fx), float(eps), None, self._sp()),
+                  "psignn_anderson_update", self.lib)
 
     def finish(self, like):
         result = torch.empty_like(like)
         info = nat.SolveInfo()
         n = self.threshold + 2
         rel, abs_, low = (C.c_double * n)(), (C.c_double * n)(), (C.c_int32 * n)()
-        nat.check(nat.lib().psignn_fpiter_finish(self.handle, nat.ptr(result), C.byref(info), rel, abs_, low, self._sp()),
-                  "psignn_fpiter_finish")
+        nat.check(self.lib.psignn_fpiter_finish(self.handle, nat.ptr(result), C.byref(info), rel, abs_, low, self._sp()),
+                  "psignn_fpiter_finish", self.lib)
         k = int(info.n_iter)
         return {"result": result, "n_iter": k, "nstep": int(info.nstep), "lowest": float(info.lowest),
                 "lowest_abs": float(info.lowest_abs), "stop_reason": int(info.stop_reason),
@@ -1390,7 +1458,7 @@ class DeviceFixedPointIter:
 
     def iterate(self, i, like):
         dst = torch.empty_like(like)
-        nat.check(nat.lib().psignn_fpiter_get_iterate(self.handle, int(i), nat.ptr(dst), self._sp()), "psignn_fpiter_get_iterate")
+        nat.check(self.lib.psignn_fpiter_get_iterate(self.handle, int(i), nat.ptr(dst), self._sp()), "psignn_fpiter_get_iterate", self.lib)
         return dst
 
 

@@ -118,8 +118,10 @@ class Function(nn.Module):
     def __init__(self, n_layers=None, latent_dim=None, edge_features_dim=None, second_member_dim=None,
                  activation=None, mixed=False):
         super().__init__()
-        if latent_dim != engine.D or edge_features_dim != 3:
-            raise nat.NativeError(f"HIP kernels are built for latent_dim={engine.D}, edge_features_dim=3")
+        if edge_features_dim != 3:
+            raise nat.NativeError("HIP kernels are built for edge_features_dim=3")
+        # latent_dim: engine.SUPPORTED_WIDTHS.  engine.D has every path; the other widths forward inference only
+        self.latent_dim = nat.check_width(latent_dim)
         self.n_layers, self.mixed = n_layers, mixed
         d, p = latent_dim, second_member_dim
         self.laynorm = nn.LayerNorm(d)
@@ -175,7 +177,8 @@ class _DEQFn(torch.autograd.Function):
             if old is None or old[0] is not fmap.plan or old[1] != cfg["fw_thres"] or old[2] != hdt:
                 if getattr(deq, "_fw_solver", None) is not None:
                     deq._fw_solver.close()
-                deq._fw_solver = engine.DeviceBroyden(plan=fmap.plan, threshold=cfg["fw_thres"], keep_trace=False, history_dtype=hdt)
+                deq._fw_solver = engine.DeviceBroyden(plan=fmap.plan, threshold=cfg["fw_thres"], keep_trace=False, history_dtype=hdt,
+                                                      width=fmap.width)
                 deq._fw_key = (fmap.plan, cfg["fw_thres"], hdt)
             out_fw = _solver.broyden(fmap, H0, threshold=cfg["fw_thres"], eps=cfg["fw_tol"], keep_trace=False,
                                      solver_obj=deq._fw_solver, history_dtype=hdt)
@@ -360,6 +363,7 @@ class DeepEquilibrium(nn.Module):
         The Jacobian regulariser carries its gradient w.r.t. the parameters of f (``_JacLossFn``; the reference's launch
         scripts train with ``jac_weight 1.0``)."""
         if torch.is_grad_enabled():
+            nat.require_default_width(self.f.latent_dim, "training (the implicit backward)")
             named = list(self.f.named_parameters())
             new_H = _DEQFn.apply(H_init, self, batch, tuple(n for n, _ in named), *[p for _, p in named])
             H_star = self.last_forward["result"]
@@ -429,6 +433,8 @@ class DeepEquilibrium(nn.Module):
         R = len(batches)
         if R == 0 or len(H_inits) != R:
             raise ValueError("train_forward_replicas: one H_init per batch, at least one batch")
+        if torch.is_grad_enabled():
+            nat.require_default_width(self.f.latent_dim, "training (the implicit backward)")
         if not torch.is_grad_enabled():   # validation: the existing branch, one replica after the other
             pairs, fw = [], []
             for h, b in zip(H_inits, batches):
@@ -483,6 +489,7 @@ class DeepEquilibrium(nn.Module):
         """Solve y = J_f(H*)^T y + grad with the configured solver (the reference's backward hook, model.py:210-223):
         returns the solver dict; ``out["result"]`` is the gradient w.r.t. the fixed point's input.  With ``bw_linearize``
         the map is the transposed product of one linearisation of f at H* (where ``fmap.can_linearize()``)."""
+        nat.require_default_width(self.f.latent_dim, "implicit_backward")
         fmap = self.f.bind(H_init, batch)
         g = grad.contiguous()
         lin = self._linearization(fmap, H_star) if self._linearize_default(None) else None
@@ -528,6 +535,7 @@ class DeepEquilibrium(nn.Module):
         """Hutchinson estimate of tr(J^T J) / (N d) (model.py:416-435) with the VJP kernel.  ``probes``: the Gaussian
         vectors to use instead of drawing ``vecs`` of them (so that a test can fix them).  ``linearize``: None -> the
         ``bw_linearize`` config value; True / False; or a Linearization built at H*."""
+        nat.require_default_width(self.f.latent_dim, "jac_loss_estimate")
         fmap = self.f.bind(H_init, batch)
         vjp, to_p, _ = self._vjp_in_plan_order(fmap, H_star, self._linearize_default(linearize))
         acc = 0.0
@@ -541,6 +549,7 @@ class DeepEquilibrium(nn.Module):
         """Spectral-radius estimate of J by power iteration on v^T J (model.py:437-452).  ``v0``: start vector instead
         of a Gaussian draw.  ``linearize``: None -> the ``bw_linearize`` config value; True / False; or a Linearization
         built at H*."""
+        nat.require_default_width(self.f.latent_dim, "power_method")
         fmap = self.f.bind(H_init, batch)
         vjp, to_p, from_p = self._vjp_in_plan_order(fmap, H_star, self._linearize_default(linearize))
         ev = to_p(torch.randn(H_star.shape, device=H_star.device, generator=generator) if v0 is None else v0)
@@ -571,7 +580,7 @@ class _Base(nn.Module):
         self.config.setdefault("solver", _solver.broyden)
         for k, v in (("fw_tol", 1e-5), ("fw_thres", 300), ("bw_tol", 1e-8), ("bw_thres", 300), ("path_logs", None)):
             self.config.setdefault(k, v)
-        d = self.config["latent_dim"]
+        d = nat.check_width(self.config["latent_dim"])   # engine.SUPPORTED_WIDTHS; NativeError naming them otherwise
         self.autoencoder = Autoencoder(hidden_channels=[1, d, d], activation=nn.ReLU())
         self.config_deq = {k: self.config[k] for k in ("solver", "fw_tol", "fw_thres", "bw_tol", "bw_thres", "path_logs")}
         if "bw_linearize" in self.config:   # optional, like "bc": the transposed stored linearisation in the backward routes
@@ -678,6 +687,11 @@ class ModelDEQDSS(_Base):
     ``inference``, ``iterative_inference``."""
 
     def forward(self, batch):
+        # At a width other than engine.D there is forward inference only: no training step, and not this method's validation
+        # branch either (its jacobian_loss is a transposed Jacobian product) -- ``inference`` / ``iterative_inference`` are the
+        # entry points there.  Decided here, before anything is launched.
+        nat.require_default_width(self.config["latent_dim"], "ModelDEQDSS.forward (training step / validation with jacobian_loss; "
+                                  "use inference() or iterative_inference())")
         if isinstance(batch, (list, tuple)):
             return self._forward_replicas(list(batch))
         if self.training and torch.is_grad_enabled():

@@ -95,7 +95,7 @@ def broyden(f, x0, threshold, eps=1e-3, stop_mode="rel", ls=False, name="unknown
             solver = f.borrow_broyden(threshold, history_dtype)
         else:
             solver = solver_obj if solver_obj is not None else DeviceBroyden(plan=f.plan, threshold=threshold, keep_trace=keep_trace,
-                                                                             history_dtype=history_dtype)
+                                                                             history_dtype=history_dtype, width=f.width)
         solver.set_stop_mode(stop_mode)
         try:
             out = solver.solve(f, eps, poll_every=poll_every)
@@ -169,7 +169,8 @@ def forward_iteration(f, z0, eps=1.e-5, threshold=50, keep_trace=None, poll_ever
     M = x0.numel()
     if keep_trace is None:
         keep_trace = (threshold + 3) * M * 4 <= TRACE_BUDGET_BYTES
-    it = DeviceFixedPointIter(M, x0.device, m=1, threshold=threshold, keep_trace=keep_trace)
+    it = DeviceFixedPointIter(M, x0.device, m=1, threshold=threshold, keep_trace=keep_trace,
+                              width=getattr(f, "width", None))
     with torch.cuda.device(x0.device):
         it.picard_begin(x0)
         for i in range(threshold + 1):
@@ -204,7 +205,8 @@ def anderson(f, x0, m=2, lam=1e-4, threshold=50, eps=1e-3, stop_mode="rel", beta
     M = xp.numel()
     if keep_trace is None:
         keep_trace = (threshold + 3) * M * 4 <= TRACE_BUDGET_BYTES
-    it = DeviceFixedPointIter(M, xp.device, m=m, threshold=threshold, keep_trace=keep_trace)
+    it = DeviceFixedPointIter(M, xp.device, m=m, threshold=threshold, keep_trace=keep_trace,
+                              width=getattr(f, "width", None))
     c = lambda t: t.to(torch.float32).contiguous()
     with torch.cuda.device(xp.device):
         f0 = c(F(xp))
@@ -238,6 +240,7 @@ def newton(f, z0, eps=1.e-5, threshold=50):
     """
     if not isinstance(f, FixedPointMap):
         raise nat.NativeError("newton needs the analytic JVP of a FixedPointMap")
+    nat.require_default_width(f.width, "newton")
     from .newton_blocks import block_newton_map
     g = block_newton_map(f)
     r = forward_iteration(g, z0, eps=eps, threshold=threshold)
@@ -270,6 +273,7 @@ def newton_krylov(f, x0, threshold=30, eps=1e-5, inner_m=200, inner_tol=1e-2, ma
     evaluations (the unit comparable to one Broyden iteration), ``n_krylov`` = Krylov steps per outer iteration."""
     if not isinstance(f, FixedPointMap):
         raise nat.NativeError("newton_krylov needs the analytic JVP of a FixedPointMap")
+    nat.require_default_width(f.width, "newton_krylov")
     nat.require_cuda(x0, "x0")
     if not f.plan.tiled:
         raise nat.NativeError("newton_krylov runs on tiled plans (the plan-order JVP)")
