@@ -540,6 +540,47 @@ int psignn_gmres_history(psignn_gmres_t* s, double* h_res /* m_max + 1 */, void*
 int psignn_gmres_reorth_count(psignn_gmres_t* s, int* h_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Restarted GMRES for the adjoint system of the implicit backward (opt-in; model config key bw_solver = "gmres").
+ * replaces: the backward hook of DeepEquilibrium.forward (dirichlet/psignn/model.py:210-223), which solves the LINEAR system
+ *           y = J_f(h*)^T y + grad with Broyden (bw_tol 1e-8 is below fp32 resolution: that solve always runs its whole budget and
+ *           keeps 2 * bw_thres vectors).  Here: GMRES with restart length m = m_max of the handle, (m + 1) basis vectors, the same
+ *           products.  A departure from the reference's algorithm, not from what it solves.
+ * Per cycle, all on the stream: r = (J^T y + grad) - y and rel = |r| / (|J^T y + grad| + 1e-9) -- the Broyden solver's measure, so
+ * eps means what bw_tol means --, then up to m Arnoldi steps on the raw products (classical Gram-Schmidt twice, second pass
+ * conditional; Givens; shift 1) until the least-squares residual is <= eps / 2 * |J^T y + grad|, then y -= V z.  The first cycle
+ * starts from y = 0 and spends no product on its residual.  The solve ends at a cycle's check on rel < eps (stop_reason 1), on
+ * rel > 1/2 of the previous cycle's rel (2: stagnation at the working precision) or when max_products are spent (0; one product is
+ * kept back for the last residual, so `lowest` is always a measured value).  The result is the iterate with the lowest rel.
+ * Every reduction has a fixed shape: the same call gives the same bits, and poll_every (how often the host looks at the cycle flag;
+ * <= 0: 8) changes neither bits nor counts.  Synchronous at the end.
+ * h_rel_trace / h_abs_trace: one entry per cycle, host arrays of max_products / 2 + 3 doubles (may be NULL). */
+typedef struct {
+  int32_t products;     /* transposed products spent */
+  int32_t cycles;       /* restart cycles begun = entries of the traces */
+  int32_t stop_reason;  /* 0 budget, 1 rel < eps, 2 stagnation */
+  int32_t n_reorth;     /* Arnoldi steps whose second Gram-Schmidt pass ran */
+  double lowest;        /* rel of the returned iterate */
+  double lowest_abs;    /* its |r| */
+} psignn_gmres_adjoint_info_t;
+/* Floats of d_work for a solve on `plan` with blocks of n_layers (operator scratch, iterate, best iterate, plan-order copies of the
+ * inputs, the layer states of a multi-layer dirichlet block); -1 on bad arguments.  (model.py:210-223: none of this is kept there.) */
+int64_t psignn_gmres_adjoint_workspace_floats(const psignn_plan_t* plan, int n_layers);
+/* The solve with the VJP kernels as the map (model.py:210-223, autograd.grad(new_H, H, y) per step there): tiled plans run in plan
+ * order on psignn_f_vjp_p (multi-layer dirichlet blocks: the layer states once, then the backward layers per product), untiled plans
+ * on psignn_f_vjp; both families, any n_layers -- the choice psignn_broyden_solve_adjoint makes.  The handle was created for
+ * n_elems = N * d of the plan.  All tensors in the caller's numbering. */
+int psignn_gmres_solve_adjoint(psignn_gmres_t* s, const psignn_plan_t* plan, const float* d_weights, int n_layers,
+                               const float* d_h_star, const float* d_prb, const float* d_normals, const float* d_grad, double eps,
+                               int max_products, int poll_every, float* d_work, float* d_result,
+                               psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
+/* The same with psignn_lin_vjp as the map (model.py:210-223 with the Jacobian at H* linearised once): h* is the state `lin` was last
+ * built at; both families, lin_neumann = "stored" handles included.  d_work is sized for the linearisation's plan. */
+int psignn_gmres_solve_adjoint_lin(psignn_gmres_t* s, const psignn_lin_t* lin, const float* d_weights, int n_layers,
+                                   const float* d_grad, double eps, int max_products, int poll_every, float* d_work,
+                                   float* d_result, psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line;
  * replaces: the reference's only instrumentation, time.time() around the model call,
  * tests/special_geo/spec_geo_2.py:313-317).  Off by default.

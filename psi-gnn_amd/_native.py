@@ -56,6 +56,11 @@ class SolveInfo(C.Structure):
                 ("stop_reason", C.c_int32), ("lowest", C.c_double), ("lowest_abs", C.c_double)]
 
 
+class GmresAdjointInfo(C.Structure):
+    _fields_ = [("products", C.c_int32), ("cycles", C.c_int32), ("stop_reason", C.c_int32), ("n_reorth", C.c_int32),
+                ("lowest", C.c_double), ("lowest_abs", C.c_double)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _INT = C.c_int
@@ -174,6 +179,11 @@ SIGNATURES = {
     "psignn_gmres_solution": (_INT, [_P, _INT, _P, C.c_double, _P, C.POINTER(C.c_double), _P]),
     "psignn_gmres_history": (_INT, [_P, C.POINTER(C.c_double), _P]),
     "psignn_gmres_reorth_count": (_INT, [_P, C.POINTER(C.c_int), _P]),
+    "psignn_gmres_adjoint_workspace_floats": (_I64, [_P, _INT]),
+    "psignn_gmres_solve_adjoint": (_INT, [_P, _P, _P, _INT, _P, _P, _P, _P, C.c_double, _INT, _INT, _P, _P,
+                                          C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_gmres_solve_adjoint_lin": (_INT, [_P, _P, _P, _INT, _P, C.c_double, _INT, _INT, _P, _P,
+                                              C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_prof_enable": (None, [_INT]),
     "psignn_reload_knobs": (None, []),
     "psignn_prof_tile_stamps": (None, [_P]),

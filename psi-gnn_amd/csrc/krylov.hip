@@ -48,6 +48,25 @@ struct psignn_gmres {
   GmresState* st = nullptr;
   GmresState* h_st = nullptr;
   size_t bytes = 0;
+  // restarted solve of the adjoint system (end of this file): solve-level state and per-cycle traces, allocated by the first such solve
+  struct AdjState* ast = nullptr;
+  struct AdjState* h_ast = nullptr;
+  double *a_rel = nullptr, *a_abs = nullptr;
+  int a_cap = 0;             // entries of each trace
+};
+
+// Solve-level state of the restarted adjoint solve (one per handle, device memory; GmresState above is re-armed every cycle)
+struct AdjState {
+  int32_t cycles;       // restart cycles begun = entries of the traces
+  int32_t products;     // transposed products spent: Arnoldi steps that ran + one per cycle after the first
+  int32_t done;         // the solve is over (GmresState::done is raised with it: every gated kernel then returns)
+  int32_t stop;         // 0 budget, 1 tolerance, 2 stagnation
+  int32_t steps_left;   // Arnoldi steps this cycle may take (<= m; the budget keeps one product for the next cycle's residual)
+  int32_t improved;     // this cycle's iterate has the lowest rel so far: k_ag_keep copies it
+  int32_t n_reorth;     // copy of GmresState::n_reorth at the last check
+  int32_t pad;
+  double prev_rel, lowest, lowest_abs;
+  double rnorm;         // |r| of this cycle (row 0 is divided by it)
 };
 
 __global__ void k_gm_init(GmresState* st, double* g, double* res_hist, int m) {
@@ -220,7 +239,8 @@ __global__ __launch_bounds__(TB) void k_gm_decide(GmresState* st, const float* _
 __global__ __launch_bounds__(TB) void k_gm_finish(GmresState* st, const float* __restrict__ npartial, int nblk, int j, int m,
                                                   double* __restrict__ H, double* __restrict__ cs, double* __restrict__ sn,
                                                   double* __restrict__ g, const double* __restrict__ hcol,
-                                                  double* __restrict__ res_hist, double eta, double shift) {
+                                                  double* __restrict__ res_hist, double eta, double shift,
+                                                  const int32_t* __restrict__ limit) {
   __shared__ double sh[TB];
   if (st->done) return;
   const double s2 = block_sum_partials(npartial, nblk, sh);
@@ -250,6 +270,7 @@ __global__ __launch_bounds__(TB) void k_gm_finish(GmresState* st, const float* _
   st->k = j + 1;
   res_hist[j + 1] = resid;
   if (resid <= eta * st->beta) st->done = 1;
+  if (limit && j + 1 >= *limit) st->done = 1;   // the adjoint solve's per-cycle step allowance (a device value; NULL: none)
   if (!(hn > 0.0)) {   // lucky breakdown: the Krylov space is invariant, the least-squares solution is exact
     st->done = 1;
     st->breakdown = 1;
@@ -343,7 +364,11 @@ extern "C" void psignn_gmres_destroy(psignn_gmres_t* s) {
   void* ptrs[] = {s->part, s->coef, s->H, s->cs, s->sn, s->g, s->hcol, s->y, s->res_hist, s->st};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
+  void* aptrs[] = {s->ast, s->a_rel, s->a_abs};
+  for (void* q : aptrs)
+    if (q) (void)hipFree(q);
   if (s->h_st) (void)hipHostFree(s->h_st);
+  if (s->h_ast) (void)hipHostFree(s->h_ast);
   delete s;
 }
 
@@ -409,11 +434,9 @@ extern "C" int psignn_gmres_begin(psignn_gmres_t* s, const float* d_b, void* str
   return PSIGNN_OK;
 }
 
-// Arnoldi step j: basis slot j + 1 holds the caller's raw product P = (operator applied to v_j); the Krylov operator is
-// A v = P - shift * v (shift = 1 for A = J_f - I).  h_done (may be NULL): synchronous read of the stop flag.
-extern "C" int psignn_gmres_step(psignn_gmres_t* s, int j, double shift, double eta, int* h_done, void* stream) {
-  ARG_CHECK(s && j >= 0 && j < s->m, "step index outside the basis");
-  hipStream_t st = (hipStream_t)stream;
+// The launch sequence of Arnoldi step j (psignn_gmres_step below; the adjoint solve at the end of this file).  `limit`: device int,
+// the step count at which the cycle ends whatever the residual (NULL: none).
+static void gm_step_launch(psignn_gmres* s, int j, double shift, double eta, const int32_t* limit, hipStream_t st) {
   const unsigned g = (unsigned)s->nblk;
   float* w = s->V + (size_t)(j + 1) * s->ld;
   KNOB_INT(always, [] { const char* e = getenv("PSIGNN_GMRES_REORTH"); return e && strcmp(e, "always") == 0 ? 1 : 0; }());
@@ -423,8 +446,16 @@ extern "C" int psignn_gmres_step(psignn_gmres_t* s, int j, double shift, double 
     VLAUNCH("k_gm_axpy", st, s->vec, k_gm_axpy, (g, TB, 0, st), s->M, s->ld, j, s->st, s->V, w, s->coef, s->part, s->nblk, pass);
     if (pass == 0) LAUNCH("k_gm_decide", st, (k_gm_decide<<<1, TB, 0, st>>>(s->st, s->part, s->nblk, always)));
   }
-  LAUNCH("k_gm_finish", st, (k_gm_finish<<<1, TB, 0, st>>>(s->st, s->part, s->nblk, j, s->m, s->H, s->cs, s->sn, s->g, s->hcol, s->res_hist, eta, shift)));
+  LAUNCH("k_gm_finish", st, (k_gm_finish<<<1, TB, 0, st>>>(s->st, s->part, s->nblk, j, s->m, s->H, s->cs, s->sn, s->g, s->hcol, s->res_hist, eta, shift, limit)));
   VLAUNCH("k_gm_scale", st, s->vec, k_gm_scale, (g, TB, 0, st), s->M, w, w, &s->st->hn, s->st, 1);
+}
+
+// Arnoldi step j: basis slot j + 1 holds the caller's raw product P = (operator applied to v_j); the Krylov operator is
+// A v = P - shift * v (shift = 1 for A = J_f - I).  h_done (may be NULL): synchronous read of the stop flag.
+extern "C" int psignn_gmres_step(psignn_gmres_t* s, int j, double shift, double eta, int* h_done, void* stream) {
+  ARG_CHECK(s && j >= 0 && j < s->m, "step index outside the basis");
+  hipStream_t st = (hipStream_t)stream;
+  gm_step_launch(s, j, shift, eta, nullptr, st);
   if (h_done) {
     HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(GmresState), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -467,4 +498,287 @@ extern "C" int psignn_gmres_history(psignn_gmres_t* s, double* h_res, void* stre
   HIP_TRY(hipMemcpyAsync(h_res, s->res_hist, (size_t)(s->m + 1) * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return PSIGNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Restarted GMRES for the adjoint system of the implicit backward,  y = J_f(h*)^T y + grad  <=>  (J^T - I) y = -grad
+// (the reference's backward hook, dirichlet/psignn/model.py:210-223, solves this LINEAR system with Broyden).  Opt-in.
+// Per restart cycle, all on the stream:
+//   begin  (k_ag_begin) : f(y) = J^T y + grad, r = f(y) - y -> basis row 0, block partials of |r|^2 and |f(y)|^2.  The first cycle
+//                         has y = 0: r = grad, no product.
+//   check  (k_ag_check) : one block.  rel = |r| / (|f(y)| + 1e-9), the measure of the Broyden solver; traces; the solve ends on
+//                         rel < eps, on rel > 1/2 of the previous cycle's rel (stagnation at the working precision) or on a spent
+//                         budget.  Otherwise the Arnoldi state is re-armed: g_0 = |r|, inner target |residual| <= eps / 2 |f(y)|.
+//   keep   (k_ag_keep)  : y_best = y when this cycle's rel is the lowest so far (the result is y_best).
+//   Arnoldi             : up to m steps of gm_step_launch on the raw products J^T v_j (shift 1); the product runs ungated, every
+//                         other kernel returns once GmresState::done is up (cycle over, or solve over).
+//   end                 : y -= V z, z the least-squares solution of (J^T - I) z = r (k_gm_backsolve, k_gm_combine).
+// The host reads the solve state after every check and the cycle flag every poll_every products; it only ever skips launches that
+// would return at once, so the bits and the counts do not depend on poll_every.  Reductions have a fixed shape: reproducible.
+// ------------------------------------------------------------------------------------------
+__global__ void k_ag_init(AdjState* as) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    as->cycles = 0; as->products = 0; as->done = 0; as->stop = 0; as->steps_left = 0; as->improved = 0; as->n_reorth = 0; as->pad = 0;
+    as->prev_rel = 0.0; as->lowest = 0.0; as->lowest_abs = 0.0; as->rnorm = 0.0;
+  }
+}
+
+// r = f(y) - y -> r0, f(y) = jty + grad (first: y := 0, f(y) = grad); partials of |r|^2 and |f(y)|^2, one pair per block
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_ag_begin(int64_t M, const AdjState* __restrict__ as, float* __restrict__ y,
+                                                 const float* __restrict__ jty, const float* __restrict__ grad,
+                                                 float* __restrict__ r0, float* __restrict__ part, int nblk, int first) {
+  if (as->done) return;
+  int64_t e0 = elem0<VEC>();
+  float sr = 0.f, sf = 0.f;
+  if (e0 < M) {
+    float f[VEC], a[VEC];
+    ldv<VEC>(grad, e0, M, f);
+    if (first) {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) a[i] = 0.f;
+      stv<VEC>(y, e0, M, a);
+    } else {
+      float t[VEC];
+      ldv<VEC>(jty, e0, M, t);
+      ldv<VEC>(y, e0, M, a);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) f[i] += t[i];
+    }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      sf = fmaf(f[i], f[i], sf);
+      f[i] -= a[i];
+      sr = fmaf(f[i], f[i], sr);
+    }
+    stv<VEC>(r0, e0, M, f);
+  }
+  block_pair_store(sr, sf, part, nblk);
+}
+
+// One block: the stop tests of the solve and the re-arming of the cycle
+__global__ __launch_bounds__(TB) void k_ag_check(AdjState* as, GmresState* st, const float* __restrict__ part, int nblk,
+                                                 double* __restrict__ g, double* __restrict__ rel_trace,
+                                                 double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
+  __shared__ double sh[TB];
+  if (as->done) return;
+  const double sr = block_sum_partials(part, nblk, sh);
+  const double sf = block_sum_partials(part + nblk, nblk, sh);
+  if (threadIdx.x != 0) return;
+  const double nr = (double)(float)sqrt(sr), nf = (double)(float)sqrt(sf);
+  const double rel = nr / (nf + 1e-9);
+  const int c = as->cycles;
+  const int products = as->products + (c > 0 ? st->k + 1 : 0);   // the last cycle's steps and this cycle's residual
+  as->products = products;
+  as->cycles = c + 1;
+  as->n_reorth = st->n_reorth;
+  if (c < cap) {
+    rel_trace[c] = rel;
+    abs_trace[c] = nr;
+  }
+  const int better = c == 0 || rel < as->lowest;
+  as->improved = better;
+  if (better) {
+    as->lowest = rel;
+    as->lowest_abs = nr;
+  }
+  const int left = min(m, max_products - products - 1);
+  int done = 1, stop = 0;
+  if (rel < eps || nr == 0.0) stop = 1;   // (a zero right-hand side: y = 0 is the answer)
+  else if (c > 0 && !(rel <= 0.5 * as->prev_rel)) stop = 2;   // (a NaN stops here too)
+  else if (left <= 0) stop = 0;
+  else done = 0;
+  as->prev_rel = rel;
+  as->done = done;
+  as->stop = stop;
+  as->steps_left = done ? 0 : left;
+  as->rnorm = nr;
+  st->done = done;
+  if (!done) {
+    st->k = 0; st->breakdown = 0; st->reorth = 1;
+    st->beta = nf;          // k_gm_finish stops the cycle at |residual| <= eta * beta with eta = eps / 2
+    st->resid = nr; st->hn = 0.0; st->n0sq = 0.0;
+    g[0] = nr;
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_ag_keep(int64_t M, const AdjState* __restrict__ as, const float* __restrict__ y,
+                                                float* __restrict__ ybest) {
+  if (!as->improved) return;
+  int64_t e0 = elem0<VEC>();
+  if (e0 >= M) return;
+  float x[VEC];
+  ldv<VEC>(y, e0, M, x);
+  stv<VEC>(ybest, e0, M, x);
+}
+
+int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
+                          hipStream_t st, bool gather);
+int psignn_f_layers_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w, float* out,
+                        float* work, float* lw, hipStream_t st);
+const psignn_plan* psignn_lin_plan(const psignn_lin_t* lin);
+
+static inline int64_t seg(int64_t n) { return (n + 63) / 64 * 64; }   // workspace segments start on 256-byte boundaries
+
+// work = [ operator scratch | y | J^T y | y_best | grad_p | h*_p | prb_p | normals_p | layer states ]
+struct AdjWork {
+  float *fwork, *y, *fy, *ybest, *grad_p, *hs_p, *prbp, *nrmp, *lwork;
+  int64_t total;
+};
+static AdjWork adj_work(const psignn_plan* p, int nl, float* base) {
+  const int64_t N = p->N, M = N * D;
+  AdjWork w;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { float* q = base ? base + o : nullptr; o += seg(n); return q; };
+  w.fwork = take(psignn_f_workspace_floats(p));
+  w.y = take(M); w.fy = take(M); w.ybest = take(M); w.grad_p = take(M); w.hs_p = take(M);
+  w.prbp = take(N * 3); w.nrmp = take(N * 2);
+  w.lwork = take(!p->mixed && nl > 1 ? psignn_f_layers_workspace_floats(p, nl) : 0);
+  w.total = o;
+  return w;
+}
+
+extern "C" int64_t psignn_gmres_adjoint_workspace_floats(const psignn_plan_t* p, int n_layers) {
+  if (!p || n_layers < 1 || n_layers > 64) return -1;
+  return adj_work(p, n_layers, nullptr).total;
+}
+
+static int adj_prepare(psignn_gmres* s, int max_products) {
+  const int cap = max_products / 2 + 3;   // a cycle after the first spends at least two products
+  if (!s->ast) {
+    if (hipMalloc((void**)&s->ast, sizeof(AdjState)) != hipSuccess || hipHostMalloc((void**)&s->h_ast, sizeof(AdjState)) != hipSuccess) {
+      psignn_set_error("gmres adjoint: allocation of the solve state failed");
+      return PSIGNN_ENOMEM;
+    }
+    s->bytes += sizeof(AdjState);
+  }
+  if (s->a_cap < cap) {
+    if (s->a_rel) (void)hipFree(s->a_rel);
+    if (s->a_abs) (void)hipFree(s->a_abs);
+    s->a_rel = s->a_abs = nullptr;
+    s->bytes -= (size_t)s->a_cap * 16;
+    s->a_cap = 0;
+    if (hipMalloc((void**)&s->a_rel, (size_t)cap * 8) != hipSuccess || hipMalloc((void**)&s->a_abs, (size_t)cap * 8) != hipSuccess) {
+      psignn_set_error("gmres adjoint: allocation of the traces failed");
+      return PSIGNN_ENOMEM;
+    }
+    s->a_cap = cap;
+    s->bytes += (size_t)cap * 16;
+  }
+  return PSIGNN_OK;
+}
+
+// vjp(w, out): out = J_f(h*)^T w in the solve's numbering.  grad, y, fy, ybest: that numbering too.  res_plan: the plan whose order the
+// solve runs in (the result goes back to the caller's numbering), or NULL.
+template <class F>
+static int adjoint_gmres_loop(psignn_gmres* s, const float* grad, double eps, int max_products, int poll_every, F&& vjp, const AdjWork& w,
+                              const psignn_plan* res_plan, float* d_result, psignn_gmres_adjoint_info_t* info, double* h_rel,
+                              double* h_abs, hipStream_t st) {
+  if (poll_every <= 0) poll_every = 8;
+  int rc = adj_prepare(s, max_products);
+  if (rc) return rc;
+  const unsigned g = (unsigned)s->nblk;
+  const int64_t vb = s->M * 4;
+  k_gm_init<<<4, TB, 0, st>>>(s->st, s->g, s->res_hist, s->m);
+  k_ag_init<<<1, 64, 0, st>>>(s->ast);
+  for (int cycle = 0;; ++cycle) {
+    if (cycle > 0 && (rc = vjp(w.y, w.fy))) return rc;
+    PROF_BYTES(cycle ? 4 * vb : 3 * vb);
+    VLAUNCH("k_ag_begin", st, s->vec, k_ag_begin, (g, TB, 0, st), s->M, s->ast, w.y, w.fy, grad, s->V, s->part, s->nblk, cycle == 0);
+    LAUNCH("k_ag_check", st, (k_ag_check<<<1, TB, 0, st>>>(s->ast, s->st, s->part, s->nblk, s->g, s->a_rel, s->a_abs, s->a_cap, eps,
+                                                          max_products, s->m)));
+    PROF_BYTES(2 * vb);
+    VLAUNCH("k_ag_keep", st, s->vec, k_ag_keep, (g, TB, 0, st), s->M, s->ast, w.y, w.ybest);
+    VLAUNCH("k_gm_scale", st, s->vec, k_gm_scale, (g, TB, 0, st), s->M, s->V, s->V, &s->ast->rnorm, s->st, 1);
+    HIP_TRY(hipMemcpyAsync(s->h_ast, s->ast, sizeof(AdjState), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (s->h_ast->done) break;
+    const int steps = s->h_ast->steps_left;
+    for (int j = 0; j < steps; ++j) {
+      if ((rc = vjp(s->V + (size_t)j * s->ld, s->V + (size_t)(j + 1) * s->ld))) return rc;
+      gm_step_launch(s, j, 1.0, 0.5 * eps, &s->ast->steps_left, st);
+      if ((j + 1) % poll_every == 0 && j + 1 < steps) {
+        HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(GmresState), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (s->h_st->done) break;
+      }
+    }
+    LAUNCH("k_gm_backsolve", st, (k_gm_backsolve<<<1, 64, 0, st>>>(s->st, 0, s->m, s->H, s->g, s->y, s->coef)));
+    VLAUNCH("k_gm_combine", st, s->vec, k_gm_combine, (g, TB, 0, st), s->M, s->ld, s->st, 0, s->V, s->coef, w.y, -1.f, w.y);
+  }
+  if (d_result) {
+    if (res_plan) {
+      if ((rc = psignn_plan_permute(res_plan, w.ybest, D, d_result, 0, st))) return rc;
+    } else {
+      HIP_TRY(hipMemcpyAsync(d_result, w.ybest, (size_t)vb, hipMemcpyDeviceToDevice, st));
+    }
+  }
+  const AdjState& h = *s->h_ast;
+  const int n = std::min(h.cycles, s->a_cap);
+  if (h_rel && n > 0) HIP_TRY(hipMemcpyAsync(h_rel, s->a_rel, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  if (h_abs && n > 0) HIP_TRY(hipMemcpyAsync(h_abs, s->a_abs, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (info) {
+    info->products = h.products;
+    info->cycles = h.cycles;
+    info->stop_reason = h.stop;
+    info->n_reorth = h.n_reorth;
+    info->lowest = h.lowest;
+    info->lowest_abs = h.lowest_abs;
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
+extern "C" int psignn_gmres_solve_adjoint(psignn_gmres_t* s, const psignn_plan_t* p, const float* W, int nl, const float* h_star,
+                                          const float* prb, const float* nrm, const float* grad, double eps, int max_products,
+                                          int poll_every, float* d_work, float* d_result, psignn_gmres_adjoint_info_t* info,
+                                          double* h_rel, double* h_abs, void* stream) {
+  ARG_CHECK(s && p && W && h_star && prb && grad && d_work, "NULL argument");
+  ARG_CHECK(s->M == p->N * D, "the GMRES handle was made for another vector length than the plan's N * d");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
+  ARG_CHECK(max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  const AdjWork w = adj_work(p, nl, d_work);
+  // tiled plans: the whole solve in plan order; otherwise the caller's numbering (as psignn_broyden_solve_adjoint chooses)
+  const bool tiled = p->tiled;
+  const bool layers = !p->mixed && nl > 1;
+  int rc;
+  if (tiled) {
+    if ((rc = psignn_plan_permute(p, h_star, D, w.hs_p, 1, st))) return rc;
+    if ((rc = psignn_plan_permute(p, grad, D, w.grad_p, 1, st))) return rc;
+    if ((rc = psignn_plan_permute(p, prb, p->mixed ? 3 : 2, w.prbp, 1, st))) return rc;
+    if (p->mixed) {
+      if ((rc = psignn_plan_permute(p, nrm, 2, w.nrmp, 1, st))) return rc;
+      nrm = w.nrmp;
+    }
+    h_star = w.hs_p;
+    grad = w.grad_p;
+    prb = w.prbp;
+  }
+  if (layers && (rc = psignn_f_layer_states(p, W, nl, h_star, prb, w.lwork, w.fwork, st, false))) return rc;
+  auto vjp = [&](const float* y, float* out) {
+    if (layers) return psignn_f_layers_vjp(p, W, nl, h_star, prb, y, out, w.fwork, w.lwork, st);
+    return tiled ? psignn_f_vjp_p(p, W, nl, h_star, prb, nrm, y, out, w.fwork, st)
+                 : psignn_f_vjp(p, W, nl, h_star, prb, nrm, y, out, w.fwork, st);
+  };
+  return adjoint_gmres_loop(s, grad, eps, max_products, poll_every, vjp, w, tiled ? p : nullptr, d_result, info, h_rel, h_abs, st);
+}
+
+extern "C" int psignn_gmres_solve_adjoint_lin(psignn_gmres_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad,
+                                              double eps, int max_products, int poll_every, float* d_work, float* d_result,
+                                              psignn_gmres_adjoint_info_t* info, double* h_rel, double* h_abs, void* stream) {
+  ARG_CHECK(s && lin && W && grad && d_work, "NULL argument");
+  const psignn_plan* p = psignn_lin_plan(lin);
+  ARG_CHECK(p && s->M == p->N * D, "the GMRES handle was made for another vector length than the linearisation's plan");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  const AdjWork w = adj_work(p, nl, d_work);
+  int rc;
+  if ((rc = psignn_plan_permute(p, grad, D, w.grad_p, 1, st))) return rc;
+  auto vjp = [&](const float* y, float* out) { return psignn_lin_vjp(lin, W, nl, y, out, w.fwork, st); };
+  return adjoint_gmres_loop(s, w.grad_p, eps, max_products, poll_every, vjp, w, p, d_result, info, h_rel, h_abs, st);
 }

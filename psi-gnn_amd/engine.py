@@ -965,6 +965,22 @@ def check_jac_backward(value):
     return value
 
 
+BW_SOLVERS = (None, "gmres")
+
+
+def check_bw_solver(value, m=None, bw_thres=None):
+    """The ``bw_solver`` config value as given: ``None`` (the implicit backward runs ``config["solver"]``, the reference's route)
+    or ``"gmres"`` (restarted GMRES on the adjoint system, ``DeviceGmres.solve_adjoint``); NativeError naming the accepted
+    values for anything else.  With ``m`` and ``bw_thres``: the restart length ``bw_gmres_m`` must be an int in 2..``bw_thres``.
+    A host check: nothing is allocated."""
+    if value is not None and not (isinstance(value, str) and value in BW_SOLVERS):
+        raise nat.NativeError(f"bw_solver must be one of {BW_SOLVERS}, got {value!r}")
+    if m is not None:
+        if isinstance(m, bool) or not isinstance(m, int) or not 2 <= m <= int(bw_thres):
+            raise nat.NativeError(f"bw_gmres_m must be an int in 2..bw_thres (= {bw_thres}), got {m!r}")
+    return value
+
+
 def check_lin_neumann(value):
     """``"direct"`` / ``"stored"`` as given; ValueError for anything else (a host check: nothing is allocated)."""
     if not isinstance(value, str) or value not in LIN_NEUMANN:
@@ -1465,9 +1481,13 @@ class DeviceFixedPointIter:
 # ---------------------------------------------------------------------------------------------
 # GMRES on the device (csrc/krylov.hip)
 # ---------------------------------------------------------------------------------------------
+GMRES_STOPS = ("budget", "tolerance", "stagnation")   # stop_reason of psignn_gmres_adjoint_info_t
+
+
 class DeviceGmres:
     """Krylov workspace of ``newton_krylov``: the basis is a torch tensor (rows are handed to the JVP kernel as views),
-    everything else -- Gram-Schmidt sweeps, Hessenberg / Givens least squares, stop flag -- lives in the library."""
+    everything else -- Gram-Schmidt sweeps, Hessenberg / Givens least squares, stop flag -- lives in the library.
+    ``solve_adjoint`` runs the restarted solve of the implicit backward's adjoint system on the same workspace."""
 
     def __init__(self, n_elems, device, m_max):
         self.M, self.m, self.device = int(n_elems), int(m_max), device
@@ -1481,6 +1501,53 @@ class DeviceGmres:
 
     def close(self):
         self._fin()
+        self._work = self._work_key = None
+
+    _work = _work_key = None
+
+    @property
+    def nbytes(self):
+        """Solver state in bytes: the (m + 1) basis vectors and the adjoint solve's workspace, if one has been made."""
+        return self.V.numel() * 4 + (self._work.numel() * 4 if self._work is not None else 0)
+
+    def solve_adjoint(self, fmap, h_star, grad, eps, max_products, lin=None, poll_every=8):
+        """y = J_f(h*)^T y + grad by restarted GMRES (restart length = this object's ``m_max``), y_0 = 0, entirely on the device
+        (psignn_gmres_solve_adjoint / _lin in include/psignn_hip.h).  ``eps`` is a bound on the Broyden solver's measure
+        |f(y) - y| / (|f(y)| + 1e-9); the solve also ends when a cycle no longer halves it (the working precision is reached) or
+        when ``max_products`` transposed products are spent.  ``lin``: a Linearization of ``fmap`` built at h*; the products
+        then are ``lin.vjp_p`` and ``h_star`` is not read.  Returns the dict of ``DeviceBroyden.solve_adjoint``: ``result`` (the
+        caller's numbering, the iterate with the lowest measure), ``nstep`` = products spent, ``lowest``, ``rel_trace`` /
+        ``abs_trace`` with one entry per cycle, plus ``n_cycles``, ``stop`` (one of ``GMRES_STOPS``) and ``n_reorth``."""
+        nat.require_default_width(getattr(fmap, "width", D), "solve_adjoint")
+        plan, nl = fmap.plan, fmap.weights.n_layers
+        if plan.N * D != self.M:
+            raise nat.NativeError(f"DeviceGmres of {self.M} elements was handed a map of {plan.N * D}")
+        hs, gr = _f32c(h_star), _f32c(grad)
+        result = torch.empty_like(gr)
+        info = nat.GmresAdjointInfo()
+        cap = int(max_products) // 2 + 3
+        rel, abs_ = (C.c_double * cap)(), (C.c_double * cap)()
+        lib = nat.lib()
+        with torch.cuda.device(self.device):
+            if self._work_key is None or self._work_key[0] is not plan or self._work_key[1] != nl:
+                n = int(lib.psignn_gmres_adjoint_workspace_floats(plan.handle, nl))
+                if n < 0:
+                    raise nat.NativeError("psignn_gmres_adjoint_workspace_floats: bad plan or n_layers")
+                self._work, self._work_key = torch.empty(n, dtype=torch.float32, device=self.device), (plan, nl)
+            if lin is not None:
+                nat.check(lib.psignn_gmres_solve_adjoint_lin(
+                    self.handle, lin.handle, nat.ptr(fmap.weights.flat), nl, nat.ptr(gr), float(eps), int(max_products),
+                    int(poll_every), nat.ptr(self._work), nat.ptr(result), C.byref(info), rel, abs_, self._sp()),
+                    "psignn_gmres_solve_adjoint_lin")
+            else:
+                nat.check(lib.psignn_gmres_solve_adjoint(
+                    self.handle, plan.handle, nat.ptr(fmap.weights.flat), nl, nat.ptr(hs), nat.ptr(fmap.prb), nat.ptr(fmap.nrm),
+                    nat.ptr(gr), float(eps), int(max_products), int(poll_every), nat.ptr(self._work), nat.ptr(result),
+                    C.byref(info), rel, abs_, self._sp()), "psignn_gmres_solve_adjoint")
+        n = min(int(info.cycles), cap)
+        return {"result": result, "nstep": int(info.products), "lowest": float(info.lowest), "lowest_abs": float(info.lowest_abs),
+                "rel_trace": list(rel[:n]), "abs_trace": list(abs_[:n]), "n_cycles": int(info.cycles),
+                "stop": GMRES_STOPS[int(info.stop_reason)], "n_reorth": int(info.n_reorth), "prot_break": False}
 
     def row(self, j, shape):
         return self.V[j, :self.M].view(shape)

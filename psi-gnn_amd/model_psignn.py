@@ -20,6 +20,12 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
   An optional key ``"jac_backward"`` = ``"gather"`` (default) | ``"tiled"``: the backward of the Jacobian regulariser
   (``_JacLossFn``) on the tile kernels (``FixedPointMap.vjp_backward(..., tiled=True)``) where the map has that form -- tiled plan,
   dirichlet family, single-layer block -- and on the gather kernels everywhere else; any other value raises ``ValueError``.
+  An optional key ``"bw_solver"`` = ``None`` (default: the implicit backward runs ``config["solver"]`` like the reference) |
+  ``"gmres"``: the backward's linear system y = J^T y + grad is solved by restarted GMRES on the device
+  (``engine.DeviceGmres.solve_adjoint``; restart length ``"bw_gmres_m"``, an int in 2..``bw_thres``, default 50 or ``bw_thres`` if that is less) with ``bw_tol`` as
+  its tolerance and ``bw_thres`` as its budget of transposed products; with ``bw_linearize`` on the stored linearisation where the plan
+  has one, on the VJP kernels otherwise.  A departure from the reference's algorithm, hence opt-in; any other value raises
+  ``NativeError``.  The forward solve, ``power_method`` and ``jac_loss_estimate`` are untouched by it.
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
   and shapes are identical.
 * ``batch`` is any object with the PyG ``Data`` attributes (see ``data/meshdata.py``), already on the GPU.
@@ -240,12 +246,12 @@ class _ReplicaSlot:
         return getattr(self, f"_{which}_solver")
 
     def close(self):
-        for name in ("_fw_solver", "_bw_solver", "_bw_lin"):
+        for name in ("_fw_solver", "_bw_solver", "_bw_lin", "_bw_gmres"):
             obj = getattr(self, name, None)
             if obj is not None:
                 obj.close()
                 setattr(self, name, None)
-        self._fw_key = self._bw_key = None
+        self._fw_key = self._bw_key = self._bw_gmres_key = None
 
 
 class _DEQReplicasFn(torch.autograd.Function):
@@ -402,10 +408,12 @@ class DeepEquilibrium(nn.Module):
 
     def lockstep_applies(self, fmaps):
         """Whether R replicas go through the batched solvers: a host-side decision on the bound maps, before anything is
-        allocated.  No: a solver other than ``utilities.solver.broyden``, an untiled plan, ``n_layers > 1``, a bf16 pair
+        allocated.  No: a solver other than ``utilities.solver.broyden``, ``bw_solver = "gmres"``, an untiled plan, ``n_layers > 1``, a bf16 pair
         history, both families in one call, a mixed plan without ``lin_neumann = "stored"``.  (Solvers of one call share one
         size class by construction: all are sized for the whole shard.)"""
         if self.config_deq["solver"] is not _solver.broyden or self.history_dtype() != torch.float32:
+            return False
+        if self.config_deq.get("bw_solver") is not None:   # the GMRES adjoint solve has no lockstep form
             return False
         if any(not f.plan.tiled or f.weights.n_layers != 1 or not f.can_linearize() for f in fmaps):
             return False
@@ -423,7 +431,8 @@ class DeepEquilibrium(nn.Module):
         ``lin_neumann = "stored"``.  Where the lockstep does not apply (``lockstep_applies``: solver other than broyden, untiled
         plan, ``n_layers > 1``, bf16 history, both families, mixed without stored Neumann rows; or ``engine.shard_batchable`` /
         ``engine.adjoint_batchable`` say no) the replicas are solved one after the other through the single-mesh paths; the
-        result has replica semantics either way.  The Jacobian regulariser stays per replica (``_JacLossFn``), its probes drawn
+        result has replica semantics either way.  With ``bw_solver = "gmres"`` the replicas are solved one after the other, forward
+        and backward: no lockstep GMRES exists, and each slot keeps its own GMRES handle and basis.  The Jacobian regulariser stays per replica (``_JacLossFn``), its probes drawn
         in replica order from ``generator`` and kept as ``last_probes``; ``last_forward`` / ``last_backward`` are lists of the
         solver dicts, the CSV log lines are written per replica.
 
@@ -488,11 +497,26 @@ class DeepEquilibrium(nn.Module):
     def implicit_backward(self, H_star, H_init, batch, grad):
         """Solve y = J_f(H*)^T y + grad with the configured solver (the reference's backward hook, model.py:210-223):
         returns the solver dict; ``out["result"]`` is the gradient w.r.t. the fixed point's input.  With ``bw_linearize``
-        the map is the transposed product of one linearisation of f at H* (where ``fmap.can_linearize()``)."""
+        the map is the transposed product of one linearisation of f at H* (where ``fmap.can_linearize()``).  With
+        ``bw_solver = "gmres"`` the system is solved by restarted GMRES instead (``engine.DeviceGmres.solve_adjoint``, restart
+        length ``bw_gmres_m``): ``bw_tol`` is its tolerance, ``bw_thres`` its budget of transposed products."""
         nat.require_default_width(self.f.latent_dim, "implicit_backward")
         fmap = self.f.bind(H_init, batch)
         g = grad.contiguous()
         lin = self._linearization(fmap, H_star) if self._linearize_default(None) else None
+        if self.config_deq.get("bw_solver") == "gmres":   # opt-in: the linear system by restarted GMRES, whatever config["solver"] is
+            # handle and basis ((m + 1) * N * d floats) are kept between calls on the same plan, like the Broyden adjoint solver's state
+            m = int(self.config_deq.get("bw_gmres_m", 50))
+            key = (fmap.plan, m)
+            old = getattr(self, "_bw_gmres_key", None)
+            if old is None or old[0] is not key[0] or old[1] != m:
+                if getattr(self, "_bw_gmres", None) is not None:
+                    self._bw_gmres.close()
+                self._bw_gmres = engine.DeviceGmres(fmap.plan.N * engine.D, fmap.plan.device, m)
+                self._bw_gmres_key = key
+            out = self._bw_gmres.solve_adjoint(fmap, H_star, g, self.config_deq["bw_tol"], self.config_deq["bw_thres"], lin=lin)
+            out.update(eps=self.config_deq["bw_tol"], threshold=self.config_deq["bw_thres"])
+            return out
         if self.config_deq["solver"] is _solver.broyden:  # whole adjoint solve on the device
             # the solver state (2 * bw_thres * N * d floats) is kept between calls on the same plan: a training loop
             # would otherwise allocate and free it once per step
@@ -561,7 +585,7 @@ class DeepEquilibrium(nn.Module):
         return from_p(ev), val.abs()
 
 
-for _name in ("history_dtype", "_linearization", "_linearize_default", "implicit_backward"):
+for _name in ("history_dtype", "_linearization", "_linearize_default", "implicit_backward"):   # (implicit_backward: both bw_solver routes)
     setattr(_ReplicaSlot, _name, getattr(DeepEquilibrium, _name))
 del _name
 
@@ -589,6 +613,10 @@ class _Base(nn.Module):
             self.config_deq["lin_neumann"] = engine.check_lin_neumann(self.config["lin_neumann"])   # (ValueError otherwise)
         if "jac_backward" in self.config:   # optional: the Jacobian regulariser's backward on the tile kernels where the plan has them
             self.config_deq["jac_backward"] = engine.check_jac_backward(self.config["jac_backward"])   # (ValueError otherwise)
+        if "bw_solver" in self.config or "bw_gmres_m" in self.config:   # optional: restarted GMRES for the implicit backward
+            m = self.config.get("bw_gmres_m", min(50, int(self.config["bw_thres"])))   # (50: the restart length at which the CPU probe's error matched Broyden's)
+            self.config_deq["bw_solver"] = engine.check_bw_solver(self.config.get("bw_solver"), m, self.config["bw_thres"])   # (NativeError otherwise)
+            self.config_deq["bw_gmres_m"] = m
         if "broyden_history_dtype" in self.config:   # optional: bf16 storage of the Broyden pairs (utilities.solver.broyden only)
             engine.history_code(self.config["broyden_history_dtype"])   # (ValueError for any other dtype)
             self.config_deq["broyden_history_dtype"] = self.config["broyden_history_dtype"]
