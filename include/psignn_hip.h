@@ -579,6 +579,38 @@ int psignn_gmres_solve_adjoint_lin(psignn_gmres_t* s, const psignn_lin_t* lin, c
                                    const float* d_grad, double eps, int max_products, int poll_every, float* d_work,
                                    float* d_result, psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace,
                                    void* stream);
+/* A GMRES handle that will be used inside psignn_gmres_solve_adjoint_lin_batch together with others: shard_elems = the sum of n_elems
+ * over the shard (>= n_elems).  The vector width of its sweeps follows shard_elems by the rule psignn_gmres_create applies to n_elems,
+ * so that all handles of a shard share one; everything else is psignn_gmres_create.  Its single solves
+ * (psignn_gmres_solve_adjoint / _lin) use that width too, hence give the same bits as its batched ones.
+ * replaces: nothing in the reference (dirichlet/psignn/main.py:106: its DataParallel replicas share no solver state;
+ *           dirichlet/psignn/model.py:210-223 keeps none between calls). */
+int psignn_gmres_create_for_batch(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis, int64_t shard_elems);
+/* 1 when psignn_gmres_solve_adjoint_lin_batch takes these handles and linearisations together: all handles have one vector width and
+ * one restart length m_max, every lins[i] has been built and holds a form the batched transposed product takes (dirichlet handles;
+ * mixed handles only with the Neumann rows stored, psignn_lin_create_opts(.., 1)), solvers[i] was made for the N * d of lins[i]'s plan,
+ * all plans are of one boundary-condition family and no handle appears twice.  0 otherwise, also for NULL arguments -- a host-side
+ * question, asked before a shard is handed over.
+ * replaces: nothing in the reference (its DataParallel replicas, dirichlet/psignn/main.py:106, each run their own backward hook,
+ *           dirichlet/psignn/model.py:210-223, whatever the meshes are). */
+int psignn_gmres_adjoint_batchable(int n, psignn_gmres_t* const* solvers, const psignn_lin_t* const* lins);
+/* Batched restarted GMRES: the lockstep form of psignn_gmres_solve_adjoint_lin for the n replicas of one shard.  The restart cycles
+ * are aligned across the replicas and every pass is ONE launch over all of them (blockIdx.z = replica): the cycle's residual product
+ * and each Arnoldi step's product through the batched transposed product of the stored linearisations, then begin / check / keep /
+ * scale, the Gram-Schmidt passes, finish, back-solve and combine.  Every replica keeps its own cycle and solve state, step allowance,
+ * stop tests and traces; one whose cycle or solve is over is skipped while the others go on.  Per cycle the host reads every replica's
+ * done flag and step allowance once, and every poll_every steps (<= 0: 8) one all-cycles-over flag.  For every replica the result,
+ * products, cycles, stop_reason, n_reorth, lowest, lowest_abs and both traces are bit-identical to psignn_gmres_solve_adjoint_lin with
+ * the same handle on that replica alone, for any poll_every.  d_works[i]: psignn_gmres_adjoint_workspace_floats(plan_i, 1) floats.
+ * Single-layer blocks.  A shard psignn_gmres_adjoint_batchable does not take is PSIGNN_EINVAL with nothing launched.
+ * replaces: the R replicas of the reference's DataParallel training step (dirichlet/psignn/main.py:106, mixed/psignn/main.py:106), each
+ *           running the backward hook of DeepEquilibrium.forward (dirichlet/psignn/model.py:210-223) as an independent linear system.
+ * Arrays of n device / host pointers; d_grads[i], d_results[i] in the caller's numbering; h_rel_trace[i] / h_abs_trace[i]:
+ * max_products / 2 + 3 doubles each (arrays may be NULL). */
+int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** solvers, const psignn_lin_t* const* lins, const float* d_weights,
+                                         int n_layers, const float* const* d_grads, double eps, int max_products, int poll_every,
+                                         float* const* d_works, float* const* d_results, psignn_gmres_adjoint_info_t* h_infos,
+                                         double* const* h_rel_trace, double* const* h_abs_trace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line;

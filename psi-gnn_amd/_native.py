@@ -184,6 +184,11 @@ SIGNATURES = {
                                           C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_gmres_solve_adjoint_lin": (_INT, [_P, _P, _P, _INT, _P, C.c_double, _INT, _INT, _P, _P,
                                               C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_gmres_create_for_batch": (_INT, [C.POINTER(_P), _I64, _I64, _INT, _P, _I64]),
+    "psignn_gmres_adjoint_batchable": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P)]),
+    "psignn_gmres_solve_adjoint_lin_batch": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P), _P, _INT, C.POINTER(_P), C.c_double, _INT, _INT,
+                                                    C.POINTER(_P), C.POINTER(_P), C.POINTER(GmresAdjointInfo),
+                                                    C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)), _P]),
     "psignn_prof_enable": (None, [_INT]),
     "psignn_reload_knobs": (None, []),
     "psignn_prof_tile_stamps": (None, [_P]),

@@ -241,3 +241,18 @@ struct LinBatchDesc {
   const int32_t* st;              // the mesh's Status block, int32 view (done flag)
   int32_t n_slots, slot_base;     // the mesh's entries of the shard's slot list / its first entry
 };
+
+// Batched restarted GMRES for the adjoint system (krylov.hip psignn_gmres_solve_adjoint_lin_batch): one descriptor per replica of a
+// shard.  Every kernel of the solve is launched ONCE for the shard with blockIdx.z = replica; a block loads its replica's descriptor
+// and then runs the single-handle kernel's body, so each replica has the bits of its own solve.
+struct GmresBatchDesc {
+  int64_t M, ld;
+  int32_t nblk, ldp, m, cap;   // cap: entries of each trace
+  float *V, *part, *coef;      // the handle's basis, dot partials, coefficients
+  double *H, *cs, *sn, *g, *hcol, *y, *res_hist;
+  struct GmresState* st;       // cycle state
+  struct AdjState* ast;        // solve state
+  float *yv, *fy, *ybest;      // the replica's iterate, J^T y, best iterate (its workspace, plan order)
+  const float* grad;           // permuted right-hand side
+  double *rel_trace, *abs_trace;
+};

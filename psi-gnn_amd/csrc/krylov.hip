@@ -19,6 +19,8 @@
 // = 2 (j + 1) + O(1) vector passes per step, 4 (j + 1) when the second pass runs.  Reductions: fixed-shape partial sums in a fixed order (reproducible).
 #include "vec_helpers.h"
 #include <algorithm>
+#include <stddef.h>
+#include <vector>
 #include <stdlib.h>
 #include <string.h>
 
@@ -69,15 +71,22 @@ struct AdjState {
   double rnorm;         // |r| of this cycle (row 0 is divided by it)
 };
 
-__global__ void k_gm_init(GmresState* st, double* g, double* res_hist, int m) {
+// (every kernel of the restarted adjoint solve keeps its code in a *_body function: the single-handle kernel and its batched form,
+// one launch for the replicas of a shard at the end of this file, both call it)
+// (bd, gd: the launch's blockDim.x and gridDim.x, read by the kernel -- inside a device function the compiler lowers blockDim.x to
+// its form for non-uniform work-groups)
+__device__ __forceinline__ void gm_init_body(GmresState* st, double* g, double* res_hist, int m, unsigned bd, unsigned gd) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     st->k = 0; st->done = 0; st->breakdown = 0; st->reorth = 1; st->pad = 0; st->beta = 0.0; st->resid = 0.0; st->hn = 0.0;
     st->n0sq = 0.0; st->n_reorth = 0;
   }
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= m + 1; i += gridDim.x * blockDim.x) {
+  for (int i = blockIdx.x * bd + threadIdx.x; i <= m + 1; i += gd * bd) {
     g[i] = 0.0;
     res_hist[i] = 0.0;
   }
+}
+__global__ void k_gm_init(GmresState* st, double* g, double* res_hist, int m) {
+  gm_init_body(st, g, res_hist, m, blockDim.x, gridDim.x);
 }
 
 // partials of <a, a> (one per block): part[blockIdx.x]
@@ -114,8 +123,8 @@ __global__ __launch_bounds__(TB) void k_gm_begin(GmresState* st, const float* __
 
 // dst = src * (1 / scale), scale = sqrt of a device double (beta or hn)
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_gm_scale(int64_t M, const float* __restrict__ src, float* __restrict__ dst,
-                                                 const double* __restrict__ scale, const GmresState* __restrict__ st, int gate) {
+__device__ __forceinline__ void gm_scale_body(int64_t M, const float* __restrict__ src, float* __restrict__ dst,
+                                              const double* __restrict__ scale, const GmresState* __restrict__ st, int gate) {
   if (gate && st->done) return;
   int64_t e0 = elem0<VEC>();
   if (e0 >= M) return;
@@ -126,14 +135,19 @@ __global__ __launch_bounds__(TB) void k_gm_scale(int64_t M, const float* __restr
   for (int i = 0; i < VEC; ++i) x[i] *= inv;
   stv<VEC>(dst, e0, M, x);
 }
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_scale(int64_t M, const float* __restrict__ src, float* __restrict__ dst,
+                                                 const double* __restrict__ scale, const GmresState* __restrict__ st, int gate) {
+  gm_scale_body<VEC>(M, src, dst, scale, st, gate);
+}
 
 // dots pass: optional first transform w <- w - shift * v_j (stored back); per-BLOCK partials of <v_i, w>, i <= j, written as
 // coalesced rows part[block * ldp + i] (vec_helpers.h PairStash: round 2's one 4-byte store per wave and basis vector cost the
 // sweep 8 % of its rate).  pass 0 also leaves the partials of |w|^2 in column j + 1; pass 1 returns at once unless st->reorth
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_gm_dots(int64_t M, int64_t ld, int j, float shift, const GmresState* __restrict__ st,
-                                                const float* __restrict__ V, float* __restrict__ w, float* __restrict__ part,
-                                                int ldp, int pass) {
+__device__ __forceinline__ void gm_dots_body(int64_t M, int64_t ld, int j, float shift, const GmresState* __restrict__ st,
+                                             const float* __restrict__ V, float* __restrict__ w, float* __restrict__ part,
+                                             int ldp, int pass) {
   __shared__ PairStash<1> sh;
   if (st->done || (pass && !st->reorth)) return;
   int64_t e0 = elem0<VEC>();
@@ -178,11 +192,17 @@ __global__ __launch_bounds__(TB) void k_gm_dots(int64_t M, int64_t ld, int j, fl
     }
   }
 }
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_dots(int64_t M, int64_t ld, int j, float shift, const GmresState* __restrict__ st,
+                                                const float* __restrict__ V, float* __restrict__ w, float* __restrict__ part,
+                                                int ldp, int pass) {
+  gm_dots_body<VEC>(M, ld, j, shift, st, V, w, part, ldp, pass);
+}
 
 // one block per coefficient: coef[i] = sum over the blocks of column i of the partials (rounded to float like the vectors they scale)
 // (pass 0: one more block, i = n_coef, sums the |w|^2 column into st->n0sq)
-__global__ __launch_bounds__(TB) void k_gm_reduce(GmresState* __restrict__ st, const float* __restrict__ part, int nrows, int ldp,
-                                                  float* __restrict__ coef, double* __restrict__ hcol, int accumulate, int n_coef) {
+__device__ __forceinline__ void gm_reduce_body(GmresState* __restrict__ st, const float* __restrict__ part, int nrows, int ldp,
+                                               float* __restrict__ coef, double* __restrict__ hcol, int accumulate, int n_coef) {
   __shared__ double sh[TB];
   if (st->done || (accumulate && !st->reorth)) return;
   const int i = blockIdx.x;
@@ -197,12 +217,16 @@ __global__ __launch_bounds__(TB) void k_gm_reduce(GmresState* __restrict__ st, c
     hcol[i] = accumulate ? hcol[i] + (double)c : (double)c;
   }
 }
+__global__ __launch_bounds__(TB) void k_gm_reduce(GmresState* __restrict__ st, const float* __restrict__ part, int nrows, int ldp,
+                                                  float* __restrict__ coef, double* __restrict__ hcol, int accumulate, int n_coef) {
+  gm_reduce_body(st, part, nrows, ldp, coef, hcol, accumulate, n_coef);
+}
 
 // axpy pass: w -= sum_{i <= j} coef[i] v_i ; partials of |w|^2 (one per block)
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_gm_axpy(int64_t M, int64_t ld, int j, const GmresState* __restrict__ st,
-                                                const float* __restrict__ V, float* __restrict__ w,
-                                                const float* __restrict__ coef, float* __restrict__ npartial, int nblk, int pass) {
+__device__ __forceinline__ void gm_axpy_body(int64_t M, int64_t ld, int j, const GmresState* __restrict__ st,
+                                             const float* __restrict__ V, float* __restrict__ w,
+                                             const float* __restrict__ coef, float* __restrict__ npartial, int nblk, int pass) {
   if (st->done || (pass && !st->reorth)) return;
   int64_t e0 = elem0<VEC>();
   float s = 0.f, z = 0.f;
@@ -222,9 +246,15 @@ __global__ __launch_bounds__(TB) void k_gm_axpy(int64_t M, int64_t ld, int j, co
   }
   block_pair_store(s, z, npartial, nblk);
 }
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_axpy(int64_t M, int64_t ld, int j, const GmresState* __restrict__ st,
+                                                const float* __restrict__ V, float* __restrict__ w,
+                                                const float* __restrict__ coef, float* __restrict__ npartial, int nblk, int pass) {
+  gm_axpy_body<VEC>(M, ld, j, st, V, w, coef, npartial, nblk, pass);
+}
 
 // One block, between the passes: does the first pass's result need the second one?  |w'|^2 < 1/2 |w|^2 (DGKS); `always` != 0: yes.
-__global__ __launch_bounds__(TB) void k_gm_decide(GmresState* st, const float* __restrict__ npartial, int nblk, int always) {
+__device__ __forceinline__ void gm_decide_body(GmresState* st, const float* __restrict__ npartial, int nblk, int always) {
   __shared__ double sh[TB];
   if (st->done) return;
   const double n1sq = block_sum_partials(npartial, nblk, sh);
@@ -234,13 +264,16 @@ __global__ __launch_bounds__(TB) void k_gm_decide(GmresState* st, const float* _
     st->n_reorth += r;
   }
 }
+__global__ __launch_bounds__(TB) void k_gm_decide(GmresState* st, const float* __restrict__ npartial, int nblk, int always) {
+  gm_decide_body(st, npartial, nblk, always);
+}
 
 // One block: finish column j of the Hessenberg matrix and the least-squares update.
-__global__ __launch_bounds__(TB) void k_gm_finish(GmresState* st, const float* __restrict__ npartial, int nblk, int j, int m,
-                                                  double* __restrict__ H, double* __restrict__ cs, double* __restrict__ sn,
-                                                  double* __restrict__ g, const double* __restrict__ hcol,
-                                                  double* __restrict__ res_hist, double eta, double shift,
-                                                  const int32_t* __restrict__ limit) {
+__device__ __forceinline__ void gm_finish_body(GmresState* st, const float* __restrict__ npartial, int nblk, int j, int m,
+                                               double* __restrict__ H, double* __restrict__ cs, double* __restrict__ sn,
+                                               double* __restrict__ g, const double* __restrict__ hcol,
+                                               double* __restrict__ res_hist, double eta, double shift,
+                                               const int32_t* __restrict__ limit) {
   __shared__ double sh[TB];
   if (st->done) return;
   const double s2 = block_sum_partials(npartial, nblk, sh);
@@ -276,10 +309,17 @@ __global__ __launch_bounds__(TB) void k_gm_finish(GmresState* st, const float* _
     st->breakdown = 1;
   }
 }
+__global__ __launch_bounds__(TB) void k_gm_finish(GmresState* st, const float* __restrict__ npartial, int nblk, int j, int m,
+                                                  double* __restrict__ H, double* __restrict__ cs, double* __restrict__ sn,
+                                                  double* __restrict__ g, const double* __restrict__ hcol,
+                                                  double* __restrict__ res_hist, double eta, double shift,
+                                                  const int32_t* __restrict__ limit) {
+  gm_finish_body(st, npartial, nblk, j, m, H, cs, sn, g, hcol, res_hist, eta, shift, limit);
+}
 
 // One block: y = R^{-1} g for the first k columns
-__global__ void k_gm_backsolve(const GmresState* __restrict__ st, int k_override, int m, const double* __restrict__ H,
-                               const double* __restrict__ g, double* __restrict__ y, float* __restrict__ coef) {
+__device__ __forceinline__ void gm_backsolve_body(const GmresState* __restrict__ st, int k_override, int m, const double* __restrict__ H,
+                                                  const double* __restrict__ g, double* __restrict__ y, float* __restrict__ coef) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const int k = k_override > 0 ? min(k_override, st->k) : st->k;
   for (int i = k - 1; i >= 0; --i) {
@@ -291,12 +331,16 @@ __global__ void k_gm_backsolve(const GmresState* __restrict__ st, int k_override
   for (int i = 0; i < k; ++i) coef[i] = (float)y[i];
   for (int i = k; i <= m; ++i) coef[i] = 0.f;
 }
+__global__ void k_gm_backsolve(const GmresState* __restrict__ st, int k_override, int m, const double* __restrict__ H,
+                               const double* __restrict__ g, double* __restrict__ y, float* __restrict__ coef) {
+  gm_backsolve_body(st, k_override, m, H, g, y, coef);
+}
 
 // dst = base + scale * sum_{i < k} coef[i] v_i   (base may be NULL: dst = the combination)
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_gm_combine(int64_t M, int64_t ld, const GmresState* __restrict__ st, int k_override,
-                                                   const float* __restrict__ V, const float* __restrict__ coef,
-                                                   const float* __restrict__ base, float scale, float* __restrict__ dst) {
+__device__ __forceinline__ void gm_combine_body(int64_t M, int64_t ld, const GmresState* __restrict__ st, int k_override,
+                                                const float* __restrict__ V, const float* __restrict__ coef,
+                                                const float* __restrict__ base, float scale, float* __restrict__ dst) {
   int64_t e0 = elem0<VEC>();
   if (e0 >= M) return;
   const int k = k_override > 0 ? min(k_override, st->k) : st->k;
@@ -320,6 +364,12 @@ __global__ __launch_bounds__(TB) void k_gm_combine(int64_t M, int64_t ld, const 
     for (int q = 0; q < VEC; ++q) acc[q] *= scale;
   }
   stv<VEC>(dst, e0, M, acc);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_combine(int64_t M, int64_t ld, const GmresState* __restrict__ st, int k_override,
+                                                   const float* __restrict__ V, const float* __restrict__ coef,
+                                                   const float* __restrict__ base, float scale, float* __restrict__ dst) {
+  gm_combine_body<VEC>(M, ld, st, k_override, V, coef, base, scale, dst);
 }
 
 // g = fx - x ; partials of |g|^2 and |fx|^2 (one pair per block); optionally b = -g
@@ -372,7 +422,8 @@ extern "C" void psignn_gmres_destroy(psignn_gmres_t* s) {
   delete s;
 }
 
-extern "C" int psignn_gmres_create(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis) {
+// width_elems: the length the vector width is chosen for (the handle's own, or the whole shard's: psignn_gmres_create_for_batch)
+static int gmres_create(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis, int64_t width_elems) {
   ARG_CHECK(out, "out is NULL");
   *out = nullptr;
   ARG_CHECK(n_elems > 0 && m_max > 0 && d_basis, "bad arguments");
@@ -382,7 +433,7 @@ extern "C" int psignn_gmres_create(psignn_gmres_t** out, int64_t n_elems, int64_
   s->ld = ld;
   s->m = m_max;
   s->V = d_basis;
-  s->vec = n_elems >= ((int64_t)3 << 18) ? 16 : 4;
+  s->vec = width_elems >= ((int64_t)3 << 18) ? 16 : 4;
   s->nblk = (int)cdiv(n_elems, (int64_t)s->vec * TB);
   s->npart = s->nblk * (TB / 64);
   s->ldp = (m_max + 2 + 63) / 64 * 64;
@@ -407,6 +458,19 @@ extern "C" int psignn_gmres_create(psignn_gmres_t** out, int64_t n_elems, int64_
   }
   *out = s;
   return PSIGNN_OK;
+}
+
+extern "C" int psignn_gmres_create(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis) {
+  return gmres_create(out, n_elems, ld, m_max, d_basis, n_elems);
+}
+
+// A handle that will run inside psignn_gmres_solve_adjoint_lin_batch: the vector width follows the shard's length, so that all
+// handles of a shard share one (as psignn_broyden_create_for_batch does for the Broyden solvers)
+extern "C" int psignn_gmres_create_for_batch(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis,
+                                             int64_t shard_elems) {
+  if (out) *out = nullptr;
+  ARG_CHECK(shard_elems >= n_elems, "shard_elems is the sum of the shard's vector lengths: at least n_elems");
+  return gmres_create(out, n_elems, ld, m_max, d_basis, shard_elems);
 }
 
 // g = fx - x (d_g, may be NULL), b = -g (d_neg_g, may be NULL), h_norms[0] = |g|, h_norms[1] = |fx| (synchronous read)
@@ -516,18 +580,19 @@ extern "C" int psignn_gmres_history(psignn_gmres_t* s, double* h_res, void* stre
 // The host reads the solve state after every check and the cycle flag every poll_every products; it only ever skips launches that
 // would return at once, so the bits and the counts do not depend on poll_every.  Reductions have a fixed shape: reproducible.
 // ------------------------------------------------------------------------------------------
-__global__ void k_ag_init(AdjState* as) {
+__device__ __forceinline__ void ag_init_body(AdjState* as) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     as->cycles = 0; as->products = 0; as->done = 0; as->stop = 0; as->steps_left = 0; as->improved = 0; as->n_reorth = 0; as->pad = 0;
     as->prev_rel = 0.0; as->lowest = 0.0; as->lowest_abs = 0.0; as->rnorm = 0.0;
   }
 }
+__global__ void k_ag_init(AdjState* as) { ag_init_body(as); }
 
 // r = f(y) - y -> r0, f(y) = jty + grad (first: y := 0, f(y) = grad); partials of |r|^2 and |f(y)|^2, one pair per block
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_ag_begin(int64_t M, const AdjState* __restrict__ as, float* __restrict__ y,
-                                                 const float* __restrict__ jty, const float* __restrict__ grad,
-                                                 float* __restrict__ r0, float* __restrict__ part, int nblk, int first) {
+__device__ __forceinline__ void ag_begin_body(int64_t M, const AdjState* __restrict__ as, float* __restrict__ y,
+                                              const float* __restrict__ jty, const float* __restrict__ grad,
+                                              float* __restrict__ r0, float* __restrict__ part, int nblk, int first) {
   if (as->done) return;
   int64_t e0 = elem0<VEC>();
   float sr = 0.f, sf = 0.f;
@@ -555,11 +620,17 @@ __global__ __launch_bounds__(TB) void k_ag_begin(int64_t M, const AdjState* __re
   }
   block_pair_store(sr, sf, part, nblk);
 }
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_ag_begin(int64_t M, const AdjState* __restrict__ as, float* __restrict__ y,
+                                                 const float* __restrict__ jty, const float* __restrict__ grad,
+                                                 float* __restrict__ r0, float* __restrict__ part, int nblk, int first) {
+  ag_begin_body<VEC>(M, as, y, jty, grad, r0, part, nblk, first);
+}
 
 // One block: the stop tests of the solve and the re-arming of the cycle
-__global__ __launch_bounds__(TB) void k_ag_check(AdjState* as, GmresState* st, const float* __restrict__ part, int nblk,
-                                                 double* __restrict__ g, double* __restrict__ rel_trace,
-                                                 double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
+__device__ __forceinline__ void ag_check_body(AdjState* as, GmresState* st, const float* __restrict__ part, int nblk,
+                                              double* __restrict__ g, double* __restrict__ rel_trace,
+                                              double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
   __shared__ double sh[TB];
   if (as->done) return;
   const double sr = block_sum_partials(part, nblk, sh);
@@ -601,16 +672,26 @@ __global__ __launch_bounds__(TB) void k_ag_check(AdjState* as, GmresState* st, c
     g[0] = nr;
   }
 }
+__global__ __launch_bounds__(TB) void k_ag_check(AdjState* as, GmresState* st, const float* __restrict__ part, int nblk,
+                                                 double* __restrict__ g, double* __restrict__ rel_trace,
+                                                 double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
+  ag_check_body(as, st, part, nblk, g, rel_trace, abs_trace, cap, eps, max_products, m);
+}
 
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_ag_keep(int64_t M, const AdjState* __restrict__ as, const float* __restrict__ y,
-                                                float* __restrict__ ybest) {
+__device__ __forceinline__ void ag_keep_body(int64_t M, const AdjState* __restrict__ as, const float* __restrict__ y,
+                                             float* __restrict__ ybest) {
   if (!as->improved) return;
   int64_t e0 = elem0<VEC>();
   if (e0 >= M) return;
   float x[VEC];
   ldv<VEC>(y, e0, M, x);
   stv<VEC>(ybest, e0, M, x);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_ag_keep(int64_t M, const AdjState* __restrict__ as, const float* __restrict__ y,
+                                                float* __restrict__ ybest) {
+  ag_keep_body<VEC>(M, as, y, ybest);
 }
 
 int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
@@ -781,4 +862,298 @@ extern "C" int psignn_gmres_solve_adjoint_lin(psignn_gmres_t* s, const psignn_li
   if ((rc = psignn_plan_permute(p, grad, D, w.grad_p, 1, st))) return rc;
   auto vjp = [&](const float* y, float* out) { return psignn_lin_vjp(lin, W, nl, y, out, w.fwork, st); };
   return adjoint_gmres_loop(s, w.grad_p, eps, max_products, poll_every, vjp, w, p, d_result, info, h_rel, h_abs, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// Lockstep form of the restarted adjoint solve for the replicas of one shard (the R replicas of the reference's DataParallel training
+// step, */psignn/main.py:106, each running the backward hook of model.py:210-223).  The cycles are aligned across the replicas: every
+// kernel above is launched ONCE per pass with blockIdx.z = replica; a block loads its replica's GmresBatchDesc (common.h) and runs the
+// single-handle body on it -- same block -> element mapping, same partial-sum shapes, same reduction order --, so every replica has
+// the bits of psignn_gmres_solve_adjoint_lin on the same handle.  The gates are the single kernels', per replica (AdjState::done,
+// GmresState::done, reorth, improved): a replica whose solve or cycle is over costs one descriptor load per block.  The grid's x
+// extent is the largest nblk of the shard; a block past its replica's extent returns.  Products: k_vjp_lin_batch on a device table
+// of (m + 2) rows of n LinBatchDesc, uploaded once per solve -- row j < m maps basis row j to row j + 1 and is gated by the replica's
+// GmresState, the last row maps y to J^T y and is gated by its AdjState.
+// ------------------------------------------------------------------------------------------
+__global__ void k_gm_init_batch(const GmresBatchDesc* __restrict__ descs) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  gm_init_body(d.st, d.g, d.res_hist, d.m, blockDim.x, gridDim.x);
+}
+__global__ void k_ag_init_batch(const GmresBatchDesc* __restrict__ descs) { ag_init_body(descs[blockIdx.z].ast); }
+
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_ag_begin_batch(const GmresBatchDesc* __restrict__ descs, int first) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk) return;
+  ag_begin_body<VEC>(d.M, d.ast, d.yv, d.fy, d.grad, d.V, d.part, d.nblk, first);
+}
+// (a replica whose solve ended in an earlier cycle: `improved` is lowered, so that the keep pass of this and every later cycle
+// returns at once instead of copying the unchanged iterate again)
+__global__ __launch_bounds__(TB) void k_ag_check_batch(const GmresBatchDesc* __restrict__ descs, double eps, int max_products) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if (d.ast->done) {
+    if (threadIdx.x == 0) d.ast->improved = 0;
+    return;
+  }
+  ag_check_body(d.ast, d.st, d.part, d.nblk, d.g, d.rel_trace, d.abs_trace, d.cap, eps, max_products, d.m);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_ag_keep_batch(const GmresBatchDesc* __restrict__ descs) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk) return;
+  ag_keep_body<VEC>(d.M, d.ast, d.yv, d.ybest);
+}
+// row 0: the cycle's residual divided by AdjState::rnorm; row j + 1 of Arnoldi step j: divided by GmresState::hn
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_scale_batch(const GmresBatchDesc* __restrict__ descs, int row) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk) return;
+  float* w = d.V + (int64_t)row * d.ld;
+  gm_scale_body<VEC>(d.M, w, w, row == 0 ? &d.ast->rnorm : &d.st->hn, d.st, 1);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_dots_batch(const GmresBatchDesc* __restrict__ descs, int j, int pass) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk) return;
+  gm_dots_body<VEC>(d.M, d.ld, j, 0.f, d.st, d.V, d.V + (int64_t)(j + 1) * d.ld, d.part, d.ldp, pass);
+}
+__global__ __launch_bounds__(TB) void k_gm_reduce_batch(const GmresBatchDesc* __restrict__ descs, int accumulate, int n_coef) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  gm_reduce_body(d.st, d.part, d.nblk, d.ldp, d.coef, d.hcol, accumulate, n_coef);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_axpy_batch(const GmresBatchDesc* __restrict__ descs, int j, int pass) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk) return;
+  gm_axpy_body<VEC>(d.M, d.ld, j, d.st, d.V, d.V + (int64_t)(j + 1) * d.ld, d.coef, d.part, d.nblk, pass);
+}
+__global__ __launch_bounds__(TB) void k_gm_decide_batch(const GmresBatchDesc* __restrict__ descs, int always) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  gm_decide_body(d.st, d.part, d.nblk, always);
+}
+__global__ __launch_bounds__(TB) void k_gm_finish_batch(const GmresBatchDesc* __restrict__ descs, int j, double eta, double shift) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  gm_finish_body(d.st, d.part, d.nblk, j, d.m, d.H, d.cs, d.sn, d.g, d.hcol, d.res_hist, eta, shift, &d.ast->steps_left);
+}
+// end of a cycle: y -= V z.  (The single solve leaves its loop before these two once the solve is over; here the replica's blocks return.)
+__global__ void k_gm_backsolve_batch(const GmresBatchDesc* __restrict__ descs) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if (d.ast->done) return;
+  gm_backsolve_body(d.st, 0, d.m, d.H, d.g, d.y, d.coef);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_gm_combine_batch(const GmresBatchDesc* __restrict__ descs) {
+  const GmresBatchDesc& d = descs[blockIdx.z];
+  if ((int)blockIdx.x >= d.nblk || d.ast->done) return;
+  gm_combine_body<VEC>(d.M, d.ld, d.st, 0, d.V, d.coef, d.yv, -1.f, d.yv);
+}
+// after a cycle's check: out[2 r] = replica r's AdjState::done, out[2 r + 1] = its steps_left
+__global__ void k_ag_gather_batch(const GmresBatchDesc* __restrict__ descs, int n, int32_t* __restrict__ out) {
+  for (int r = threadIdx.x; r < n; r += blockDim.x) {
+    out[2 * r] = descs[r].ast->done;
+    out[2 * r + 1] = descs[r].ast->steps_left;
+  }
+}
+// *all_done = 1 when every replica's cycle is over (kb_all_done of the batched Broyden solve, on GmresState::done)
+__global__ void k_gm_all_done_batch(const GmresBatchDesc* __restrict__ descs, int n, int32_t* __restrict__ all_done) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    int a = 1;
+    for (int r = 0; r < n; ++r) a &= descs[r].st->done != 0;
+    *all_done = a;
+  }
+}
+
+int psignn_lin_batch_ok(const psignn_lin_t* lin, const psignn_plan* p);
+int psignn_lin_batch_fill(const psignn_lin_t* lin, LinBatchDesc* d, hipStream_t st);
+int64_t psignn_lin_vjp_bytes(const psignn_lin_t* lin);
+int psignn_lin_vjp_batch(const LinBatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed, int off_done,
+                         hipStream_t st);
+
+// 1 when psignn_gmres_solve_adjoint_lin_batch takes these handles and linearisations together: one vector width and one restart
+// length, every lins[i] built and of a form the batched product takes (psignn_lin_batch_ok), handle i made for the length of lins[i]'s
+// plan, all plans of one family.  A host-side question; 0 also for NULL arguments.
+extern "C" int psignn_gmres_adjoint_batchable(int n, psignn_gmres_t* const* sv, const psignn_lin_t* const* lins) {
+  if (n <= 0 || !sv || !lins) return 0;
+  for (int r = 0; r < n; ++r) {
+    if (!sv[r] || !lins[r]) return 0;
+    const psignn_plan* p = psignn_lin_plan(lins[r]);
+    if (!p || !psignn_lin_batch_ok(lins[r], p)) return 0;
+    if (sv[r]->vec != sv[0]->vec || sv[r]->m != sv[0]->m) return 0;
+    if (sv[r]->M != p->N * D) return 0;
+    if (p->mixed != psignn_lin_plan(lins[0])->mixed) return 0;
+    for (int q = 0; q < r; ++q)
+      if (sv[q] == sv[r]) return 0;   // one handle per replica: its state cannot serve two
+  }
+  return 1;
+}
+
+// The batched launch sequence of Arnoldi step j (gm_step_launch, one launch per pass over the shard)
+static void gm_step_launch_batch(const GmresBatchDesc* dd, int n, int vec, unsigned max_g, int j, double shift, double eta,
+                                 hipStream_t st) {
+  const dim3 gv(max_g, 1, (unsigned)n);
+  KNOB_INT(always, [] { const char* e = getenv("PSIGNN_GMRES_REORTH"); return e && strcmp(e, "always") == 0 ? 1 : 0; }());
+  for (int pass = 0; pass < 2; ++pass) {
+    VLAUNCH("k_gm_dots_batch", st, vec, k_gm_dots_batch, (gv, TB, 0, st), dd, j, pass);
+    LAUNCH("k_gm_reduce_batch", st, (k_gm_reduce_batch<<<dim3((unsigned)(j + 1 + (pass == 0)), 1, (unsigned)n), TB, 0, st>>>(dd, pass, j + 1)));
+    VLAUNCH("k_gm_axpy_batch", st, vec, k_gm_axpy_batch, (gv, TB, 0, st), dd, j, pass);
+    if (pass == 0) LAUNCH("k_gm_decide_batch", st, (k_gm_decide_batch<<<dim3(1, 1, (unsigned)n), TB, 0, st>>>(dd, always)));
+  }
+  LAUNCH("k_gm_finish_batch", st, (k_gm_finish_batch<<<dim3(1, 1, (unsigned)n), TB, 0, st>>>(dd, j, eta, shift)));
+  VLAUNCH("k_gm_scale_batch", st, vec, k_gm_scale_batch, (gv, TB, 0, st), dd, j + 1);
+}
+
+extern "C" int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** sv, const psignn_lin_t* const* lins, const float* W, int nl,
+                                                    const float* const* grads, double eps, int max_products, int poll_every,
+                                                    float* const* d_works, float* const* d_results,
+                                                    psignn_gmres_adjoint_info_t* infos, double* const* h_rel, double* const* h_abs,
+                                                    void* stream) {
+  ARG_CHECK(n > 0 && sv && lins && W && grads && d_works, "bad arguments");
+  ARG_CHECK(nl == 1, "the batched adjoint solve runs single-layer blocks");
+  ARG_CHECK(max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
+  // (nothing is launched for a shard the lockstep does not take)
+  ARG_CHECK(psignn_gmres_adjoint_batchable(n, sv, lins),
+            "batched GMRES adjoint solve: handles / linearisations are not batchable (psignn_gmres_adjoint_batchable)");
+  for (int r = 0; r < n; ++r) ARG_CHECK(grads[r] && d_works[r], "NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (poll_every <= 0) poll_every = 8;
+  const int m = sv[0]->m, vec = sv[0]->vec;
+  const int mixed = psignn_lin_plan(lins[0])->mixed;
+  int rc;
+  for (int r = 0; r < n; ++r)
+    if ((rc = adj_prepare(sv[r], max_products))) return rc;
+  // ---- per replica: the lazy work of the transposed product, the permuted right-hand side, its descriptor and its column of the
+  // product table
+  std::vector<GmresBatchDesc> hd(n);
+  std::vector<LinBatchDesc> tab((size_t)(m + 2) * n);
+  std::vector<AdjWork> works(n);
+  int max_rows = 0, n_slots = 0, max_g = 0;
+  int64_t bv_tot = 0, vb_tot = 0;   // bytes of one transposed product / of one state vector, summed over the shard (profiling records)
+  for (int r = 0; r < n; ++r) {
+    psignn_gmres* s = sv[r];
+    const psignn_plan* p = psignn_lin_plan(lins[r]);
+    const AdjWork w = works[r] = adj_work(p, 1, d_works[r]);
+    LinBatchDesc l;
+    if ((rc = psignn_lin_batch_fill(lins[r], &l, st))) return rc;
+    if ((rc = psignn_plan_permute(p, grads[r], D, w.grad_p, 1, st))) return rc;
+    bv_tot += psignn_lin_vjp_bytes(lins[r]);
+    vb_tot += s->M * 4;
+    max_rows = std::max(max_rows, p->max_rows);
+    max_g = std::max(max_g, s->nblk);
+    GmresBatchDesc& d = hd[r];
+    d.M = s->M; d.ld = s->ld; d.nblk = s->nblk; d.ldp = s->ldp; d.m = s->m; d.cap = s->a_cap;
+    d.V = s->V; d.part = s->part; d.coef = s->coef;
+    d.H = s->H; d.cs = s->cs; d.sn = s->sn; d.g = s->g; d.hcol = s->hcol; d.y = s->y; d.res_hist = s->res_hist;
+    d.st = s->st; d.ast = s->ast;
+    d.yv = w.y; d.fy = w.fy; d.ybest = w.ybest; d.grad = w.grad_p;
+    d.rel_trace = s->a_rel; d.abs_trace = s->a_abs;
+    l.slot_base = n_slots;
+    n_slots += l.n_slots;
+    for (int j = 0; j < m; ++j) {   // Arnoldi step j: basis row j -> row j + 1, skipped once the replica's cycle is over
+      LinBatchDesc& t = tab[(size_t)j * n + r];
+      t = l;
+      t.w = s->V + (size_t)j * s->ld;
+      t.out = s->V + (size_t)(j + 1) * s->ld;
+      t.st = reinterpret_cast<const int32_t*>(s->st);
+    }
+    for (int j = m; j < m + 2; ++j) {   // the last row: the cycle's residual product y -> J^T y, skipped once the replica's solve is over
+      LinBatchDesc& t = tab[(size_t)j * n + r];
+      t = l;
+      t.w = w.y;
+      t.out = w.fy;
+      t.st = reinterpret_cast<const int32_t*>(s->ast);
+    }
+  }
+  const int off_cycle = offsetof(GmresState, done) / 4, off_solve = offsetof(AdjState, done) / 4;
+  GmresBatchDesc* d_descs = nullptr;
+  LinBatchDesc* d_tab = nullptr;
+  int32_t *d_flags = nullptr, *h_flags = nullptr;   // [2 r] done, [2 r + 1] steps_left; [2 n] every cycle over
+  auto cleanup = [&]() {
+    if (d_descs) (void)hipFree(d_descs);
+    if (d_tab) (void)hipFree(d_tab);
+    if (d_flags) (void)hipFree(d_flags);
+    if (h_flags) (void)hipHostFree(h_flags);
+  };
+#define BT(expr)                                                                          \
+  do {                                                                                    \
+    hipError_t _e = (expr);                                                               \
+    if (_e != hipSuccess) {                                                               \
+      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+      cleanup();                                                                          \
+      return PSIGNN_EHIP;                                                                 \
+    }                                                                                     \
+  } while (0)
+  const size_t flag_bytes = (size_t)(2 * n + 1) * 4;
+  BT(hipMalloc((void**)&d_descs, sizeof(GmresBatchDesc) * n));
+  BT(hipMalloc((void**)&d_tab, sizeof(LinBatchDesc) * tab.size()));
+  BT(hipMalloc((void**)&d_flags, flag_bytes));
+  BT(hipHostMalloc((void**)&h_flags, flag_bytes));
+  BT(hipMemcpyAsync(d_descs, hd.data(), sizeof(GmresBatchDesc) * n, hipMemcpyHostToDevice, st));
+  BT(hipMemcpyAsync(d_tab, tab.data(), sizeof(LinBatchDesc) * tab.size(), hipMemcpyHostToDevice, st));
+  // (the descriptors are read from pageable host vectors: they must have left the host before the vectors can go)
+  BT(hipStreamSynchronize(st));
+  const dim3 gv((unsigned)max_g, 1, (unsigned)n), g1(1, 1, (unsigned)n);
+  k_gm_init_batch<<<dim3(4, 1, (unsigned)n), TB, 0, st>>>(d_descs);
+  k_ag_init_batch<<<g1, 64, 0, st>>>(d_descs);
+  for (int cycle = 0;; ++cycle) {
+    if (cycle > 0) {
+      PROF_BYTES(bv_tot);
+      rc = psignn_lin_vjp_batch(d_tab + (size_t)(m + 1) * n, n, n_slots, max_rows, W, mixed, off_solve, st);
+      if (rc) { cleanup(); return rc; }
+    }
+    PROF_BYTES(cycle ? 4 * vb_tot : 3 * vb_tot);
+    VLAUNCH("k_ag_begin_batch", st, vec, k_ag_begin_batch, (gv, TB, 0, st), d_descs, cycle == 0);
+    LAUNCH("k_ag_check_batch", st, (k_ag_check_batch<<<g1, TB, 0, st>>>(d_descs, eps, max_products)));
+    PROF_BYTES(2 * vb_tot);
+    VLAUNCH("k_ag_keep_batch", st, vec, k_ag_keep_batch, (gv, TB, 0, st), d_descs);
+    VLAUNCH("k_gm_scale_batch", st, vec, k_gm_scale_batch, (gv, TB, 0, st), d_descs, 0);
+    k_ag_gather_batch<<<1, 64, 0, st>>>(d_descs, n, d_flags);
+    BT(hipMemcpyAsync(h_flags, d_flags, (size_t)(2 * n) * 4, hipMemcpyDeviceToHost, st));
+    BT(hipStreamSynchronize(st));
+    int steps = 0;   // the largest allowance among the replicas still solving; 0: all are done
+    for (int r = 0; r < n; ++r)
+      if (!h_flags[2 * r]) steps = std::max(steps, h_flags[2 * r + 1]);
+    if (steps <= 0) break;
+    for (int j = 0; j < steps; ++j) {
+      PROF_BYTES(bv_tot);
+      rc = psignn_lin_vjp_batch(d_tab + (size_t)j * n, n, n_slots, max_rows, W, mixed, off_cycle, st);
+      if (rc) { cleanup(); return rc; }
+      gm_step_launch_batch(d_descs, n, vec, (unsigned)max_g, j, 1.0, 0.5 * eps, st);
+      if ((j + 1) % poll_every == 0 && j + 1 < steps) {
+        k_gm_all_done_batch<<<1, 64, 0, st>>>(d_descs, n, d_flags + 2 * n);
+        BT(hipMemcpyAsync(h_flags + 2 * n, d_flags + 2 * n, 4, hipMemcpyDeviceToHost, st));
+        BT(hipStreamSynchronize(st));
+        if (h_flags[2 * n]) break;
+      }
+    }
+    LAUNCH("k_gm_backsolve_batch", st, (k_gm_backsolve_batch<<<g1, 64, 0, st>>>(d_descs)));
+    VLAUNCH("k_gm_combine_batch", st, vec, k_gm_combine_batch, (gv, TB, 0, st), d_descs);
+  }
+  // ---- per replica what adjoint_gmres_loop gives: the result in the caller's numbering, the traces, the counts
+  for (int r = 0; r < n; ++r) BT(hipMemcpyAsync(sv[r]->h_ast, sv[r]->ast, sizeof(AdjState), hipMemcpyDeviceToHost, st));
+  BT(hipStreamSynchronize(st));
+  for (int r = 0; r < n; ++r) {
+    psignn_gmres* s = sv[r];
+    if (d_results && d_results[r]) {
+      rc = psignn_plan_permute(psignn_lin_plan(lins[r]), works[r].ybest, D, d_results[r], 0, st);
+      if (rc) { cleanup(); return rc; }
+    }
+    const int nc = std::min(s->h_ast->cycles, s->a_cap);
+    if (h_rel && h_rel[r] && nc > 0) BT(hipMemcpyAsync(h_rel[r], s->a_rel, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+    if (h_abs && h_abs[r] && nc > 0) BT(hipMemcpyAsync(h_abs[r], s->a_abs, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+  }
+  BT(hipStreamSynchronize(st));
+  if (infos)
+    for (int r = 0; r < n; ++r) {
+      const AdjState& h = *sv[r]->h_ast;
+      infos[r].products = h.products;
+      infos[r].cycles = h.cycles;
+      infos[r].stop_reason = h.stop;
+      infos[r].n_reorth = h.n_reorth;
+      infos[r].lowest = h.lowest;
+      infos[r].lowest_abs = h.lowest_abs;
+    }
+  BT(hipGetLastError());
+  cleanup();
+#undef BT
+  return PSIGNN_OK;
 }

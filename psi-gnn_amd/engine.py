@@ -981,6 +981,17 @@ def check_bw_solver(value, m=None, bw_thres=None):
     return value
 
 
+def check_bw_gmres_lockstep(value, bw_solver):
+    """The ``bw_gmres_lockstep`` config value as a bool: the replicas of a ``DataParallel(replicas=R)`` step solve their GMRES
+    adjoint systems in lockstep (``gmres_solve_adjoint_batch``).  It needs ``bw_solver = "gmres"``: NativeError naming both keys
+    otherwise.  A host check: nothing is allocated."""
+    if not isinstance(value, bool):
+        raise nat.NativeError(f"bw_gmres_lockstep must be a bool, got {value!r}")
+    if value and bw_solver != "gmres":
+        raise nat.NativeError(f'bw_gmres_lockstep = True needs bw_solver = "gmres" (bw_solver is {bw_solver!r})')
+    return value
+
+
 def check_lin_neumann(value):
     """``"direct"`` / ``"stored"`` as given; ValueError for anything else (a host check: nothing is allocated)."""
     if not isinstance(value, str) or value not in LIN_NEUMANN:
@@ -1487,15 +1498,22 @@ GMRES_STOPS = ("budget", "tolerance", "stagnation")   # stop_reason of psignn_gm
 class DeviceGmres:
     """Krylov workspace of ``newton_krylov``: the basis is a torch tensor (rows are handed to the JVP kernel as views),
     everything else -- Gram-Schmidt sweeps, Hessenberg / Givens least squares, stop flag -- lives in the library.
-    ``solve_adjoint`` runs the restarted solve of the implicit backward's adjoint system on the same workspace."""
+    ``solve_adjoint`` runs the restarted solve of the implicit backward's adjoint system on the same workspace.
+    ``shard_elems``: the summed length of the shard this handle will share a ``gmres_solve_adjoint_batch`` call with
+    (``psignn_gmres_create_for_batch``: the vector width follows the shard); ``None``: a handle sized for itself."""
 
-    def __init__(self, n_elems, device, m_max):
+    def __init__(self, n_elems, device, m_max, shard_elems=None):
         self.M, self.m, self.device = int(n_elems), int(m_max), device
+        self.shard_elems = None if shard_elems is None else int(shard_elems)
         self.ld = (self.M + 63) // 64 * 64
         self.V = torch.empty((self.m + 1, self.ld), dtype=torch.float32, device=device)
         h = C.c_void_p()
         with torch.cuda.device(device):
-            nat.check(nat.lib().psignn_gmres_create(C.byref(h), self.M, self.ld, self.m, nat.ptr(self.V)), "psignn_gmres_create")
+            if self.shard_elems is None:
+                nat.check(nat.lib().psignn_gmres_create(C.byref(h), self.M, self.ld, self.m, nat.ptr(self.V)), "psignn_gmres_create")
+            else:   # sized for a shard of ``gmres_solve_adjoint_batch``: one vector width for all its handles
+                nat.check(nat.lib().psignn_gmres_create_for_batch(C.byref(h), self.M, self.ld, self.m, nat.ptr(self.V),
+                                                                  self.shard_elems), "psignn_gmres_create_for_batch")
         self.handle = h
         self._fin = weakref.finalize(self, nat.lib().psignn_gmres_destroy, h)
 
@@ -1529,11 +1547,7 @@ class DeviceGmres:
         rel, abs_ = (C.c_double * cap)(), (C.c_double * cap)()
         lib = nat.lib()
         with torch.cuda.device(self.device):
-            if self._work_key is None or self._work_key[0] is not plan or self._work_key[1] != nl:
-                n = int(lib.psignn_gmres_adjoint_workspace_floats(plan.handle, nl))
-                if n < 0:
-                    raise nat.NativeError("psignn_gmres_adjoint_workspace_floats: bad plan or n_layers")
-                self._work, self._work_key = torch.empty(n, dtype=torch.float32, device=self.device), (plan, nl)
+            self._workspace(plan, nl)
             if lin is not None:
                 nat.check(lib.psignn_gmres_solve_adjoint_lin(
                     self.handle, lin.handle, nat.ptr(fmap.weights.flat), nl, nat.ptr(gr), float(eps), int(max_products),
@@ -1544,6 +1558,19 @@ class DeviceGmres:
                     self.handle, plan.handle, nat.ptr(fmap.weights.flat), nl, nat.ptr(hs), nat.ptr(fmap.prb), nat.ptr(fmap.nrm),
                     nat.ptr(gr), float(eps), int(max_products), int(poll_every), nat.ptr(self._work), nat.ptr(result),
                     C.byref(info), rel, abs_, self._sp()), "psignn_gmres_solve_adjoint")
+        return self._collect(info, rel, abs_, cap, result)
+
+    def _workspace(self, plan, nl):
+        """The adjoint solve's workspace for (plan, n_layers), kept between solves (call inside ``torch.cuda.device``)."""
+        if self._work_key is None or self._work_key[0] is not plan or self._work_key[1] != nl:
+            n = int(nat.lib().psignn_gmres_adjoint_workspace_floats(plan.handle, nl))
+            if n < 0:
+                raise nat.NativeError("psignn_gmres_adjoint_workspace_floats: bad plan or n_layers")
+            self._work, self._work_key = torch.empty(n, dtype=torch.float32, device=self.device), (plan, nl)
+        return self._work
+
+    @staticmethod
+    def _collect(info, rel, abs_, cap, result):
         n = min(int(info.cycles), cap)
         return {"result": result, "nstep": int(info.products), "lowest": float(info.lowest), "lowest_abs": float(info.lowest_abs),
                 "rel_trace": list(rel[:n]), "abs_trace": list(abs_[:n]), "n_cycles": int(info.cycles),
@@ -1587,3 +1614,58 @@ class DeviceGmres:
         h = (C.c_double * (self.m + 1))()
         nat.check(nat.lib().psignn_gmres_history(self.handle, h, self._sp()), "psignn_gmres_history")
         return list(h)
+
+
+def gmres_adjoint_batchable(solvers, lins) -> bool:
+    """Whether ``gmres_solve_adjoint_batch`` takes these ``DeviceGmres`` handles and linearisations together
+    (``psignn_gmres_adjoint_batchable``): one vector width and one restart length, every ``lins[i]`` built and of a form the batched
+    transposed product takes (dirichlet; mixed only with ``neumann="stored"``), ``solvers[i]`` made for the length of ``lins[i]``'s
+    plan, one family, single-layer blocks.  A host-side decision -- real errors of the batched solve still raise."""
+    n = len(solvers)
+    if n == 0 or len(lins) != n or any(l is None or l.handle is None for l in lins):
+        return False
+    if any(l.fmap.weights.n_layers != 1 for l in lins):   # the batched solve runs single-layer blocks
+        return False
+    sv = (C.c_void_p * n)(*[s.handle.value for s in solvers])
+    lv = (C.c_void_p * n)(*[l.handle.value for l in lins])
+    return bool(nat.lib().psignn_gmres_adjoint_batchable(n, sv, lv))
+
+
+def gmres_solve_adjoint_batch(solvers, lins, grads, eps, max_products, poll_every=8):
+    """One lockstep device solve of the adjoint systems y_i = J_i^T y_i + grads[i] of several independent meshes by restarted GMRES
+    (``psignn_gmres_solve_adjoint_lin_batch``): ``solvers[i]`` is a ``DeviceGmres`` of the length of the plan ``lins[i]`` was made
+    for (created with ``shard_elems``), ``lins[i]`` a ``Linearization`` built at mesh i's H*.  ``grads`` and the results are in the
+    caller's numbering.  Returns the list of per-mesh result dicts of ``DeviceGmres.solve_adjoint`` -- each bit-identical to
+    ``solvers[i].solve_adjoint(..., lin=lins[i])`` on that mesh alone, whatever ``poll_every``.  Each handle keeps its workspace, as
+    in ``solve_adjoint``.  A shard ``gmres_adjoint_batchable`` does not take raises ``NativeError`` with nothing launched."""
+    n = len(solvers)
+    if n == 0:
+        return []
+    if len(lins) != n or len(grads) != n:
+        raise nat.NativeError("one Linearization and one gradient per solver")
+    if any(l is None or l.handle is None for l in lins):
+        raise nat.NativeError("batched GMRES adjoint solve: every replica needs a Linearization")
+    w0 = lins[0].fmap.weights
+    for s, l in zip(solvers, lins):
+        if l.fmap.weights is not w0 and l.fmap.weights.flat.data_ptr() != w0.flat.data_ptr():
+            raise nat.NativeError("batched GMRES adjoint solve: all meshes must share one packed weight buffer")
+        if s.M != l.fmap.plan.N * D:
+            raise nat.NativeError(f"batched GMRES adjoint solve: DeviceGmres of {s.M} elements was handed a linearisation of "
+                                  f"{l.fmap.plan.N * D}")
+    dev = solvers[0].device
+    gr = [_f32c(g) for g in grads]
+    results = [torch.empty_like(g) for g in gr]
+    arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
+    infos = (nat.GmresAdjointInfo * n)()
+    cap = int(max_products) // 2 + 3
+    rel = [(C.c_double * cap)() for _ in solvers]
+    abs_ = [(C.c_double * cap)() for _ in solvers]
+    dpp = lambda rows: (C.POINTER(C.c_double) * n)(*[C.cast(r, C.POINTER(C.c_double)) for r in rows])
+    with torch.cuda.device(dev):
+        works = [s._workspace(l.fmap.plan, w0.n_layers) for s, l in zip(solvers, lins)]
+        nat.check(nat.lib().psignn_gmres_solve_adjoint_lin_batch(
+            n, arr([s.handle.value for s in solvers]), arr([l.handle.value for l in lins]), nat.ptr(w0.flat), w0.n_layers,
+            arr([nat.ptr(g) for g in gr]), float(eps), int(max_products), int(poll_every), arr([nat.ptr(w) for w in works]),
+            arr([nat.ptr(r) for r in results]), infos, dpp(rel), dpp(abs_), nat.stream_ptr(dev)),
+            "psignn_gmres_solve_adjoint_lin_batch")
+    return [DeviceGmres._collect(infos[i], rel[i], abs_[i], cap, results[i]) for i in range(n)]

@@ -26,6 +26,10 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
   its tolerance and ``bw_thres`` as its budget of transposed products; with ``bw_linearize`` on the stored linearisation where the plan
   has one, on the VJP kernels otherwise.  A departure from the reference's algorithm, hence opt-in; any other value raises
   ``NativeError``.  The forward solve, ``power_method`` and ``jac_loss_estimate`` are untouched by it.
+  An optional key ``"bw_gmres_lockstep"`` (bool, default False; True needs ``bw_solver = "gmres"``, ``NativeError`` naming both keys
+  otherwise): the replicas of a list call take the lockstep route with the GMRES adjoint solve -- forward solves through
+  ``engine.broyden_solve_batch``, the R adjoint systems through ``engine.gmres_solve_adjoint_batch`` -- where
+  ``DeepEquilibrium.lockstep_applies`` says yes; without it replicas with ``bw_solver = "gmres"`` are solved one after the other.
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
   and shapes are identical.
 * ``batch`` is any object with the PyG ``Data`` attributes (see ``data/meshdata.py``), already on the GPU.
@@ -245,6 +249,19 @@ class _ReplicaSlot:
             setattr(self, f"_{which}_key", key)
         return getattr(self, f"_{which}_solver")
 
+    def gmres(self, plan, m, shard_elems):
+        """The slot's GMRES handle for (plan, restart length, shard size), keyed and replaced like ``solver()``.  It shares the
+        attribute of the single-batch route's handle (``implicit_backward``), whose key has no shard size: either route remakes
+        the handle the other left."""
+        key = (plan, m, shard_elems)
+        old = getattr(self, "_bw_gmres_key", None)
+        if old is None or len(old) != 3 or old[0] is not plan or old[1:] != key[1:]:
+            if getattr(self, "_bw_gmres", None) is not None:
+                self._bw_gmres.close()
+            self._bw_gmres = engine.DeviceGmres(plan.N * engine.D, plan.device, m, shard_elems=shard_elems)
+            self._bw_gmres_key = key
+        return self._bw_gmres
+
     def close(self):
         for name in ("_fw_solver", "_bw_solver", "_bw_lin", "_bw_gmres"):
             obj = getattr(self, name, None)
@@ -258,9 +275,10 @@ class _DEQReplicasFn(torch.autograd.Function):
     """``_DEQFn`` over R replicas at once (the reference's ``DataParallel`` replicas, dirichlet/psignn/main.py:106, each with
     the backward hook of model.py:210-223): the R forward solves run in lockstep (``engine.broyden_solve_batch``); backward
     builds R linearisations, each at its H*, and solves the R adjoint fixed points in lockstep
-    (``engine.broyden_solve_adjoint_batch``), then pushes each y_r through one application of f and adds the parameter
-    gradients up in replica order.  Where ``engine.shard_batchable`` / ``engine.adjoint_batchable`` say no, the same solver
-    objects run one mesh after the other."""
+    (``engine.broyden_solve_adjoint_batch``; with ``bw_solver = "gmres"`` and ``bw_gmres_lockstep`` the R restarted GMRES solves,
+    ``engine.gmres_solve_adjoint_batch`` on each slot's GMRES handle), then pushes each y_r through one application of f and adds
+    the parameter gradients up in replica order.  Where ``engine.shard_batchable`` / ``engine.adjoint_batchable`` /
+    ``engine.gmres_adjoint_batchable`` say no, the same solver objects run one mesh after the other."""
 
     @staticmethod
     def forward(ctx, deq, batches, names, *tensors):
@@ -291,11 +309,20 @@ class _DEQReplicasFn(torch.autograd.Function):
         H_stars = ctx.saved_tensors
         gs = [torch.zeros_like(h) if g is None else g.contiguous() for g, h in zip(grads, H_stars)]
         lins = [sl._linearization(f, h) for sl, f, h in zip(slots, fmaps, H_stars)]
-        solvers = [sl.solver("bw", f.plan, cfg["bw_thres"], torch.float32, ctx.shard) for sl, f in zip(slots, fmaps)]
-        if engine.adjoint_batchable(solvers, lins):
-            outs = engine.broyden_solve_adjoint_batch(solvers, lins, gs, cfg["bw_tol"])
+        if cfg.get("bw_gmres_lockstep"):   # (with bw_solver = "gmres": checked when the model was made)
+            m = int(cfg.get("bw_gmres_m", 50))
+            solvers = [sl.gmres(f.plan, m, ctx.shard) for sl, f in zip(slots, fmaps)]
+            if engine.gmres_adjoint_batchable(solvers, lins):
+                outs = engine.gmres_solve_adjoint_batch(solvers, lins, gs, cfg["bw_tol"], cfg["bw_thres"])
+            else:
+                outs = [sv.solve_adjoint(f, h, g, cfg["bw_tol"], cfg["bw_thres"], lin=l)
+                        for sv, f, h, g, l in zip(solvers, fmaps, H_stars, gs, lins)]
         else:
-            outs = [sv.solve_adjoint(f, h, g, cfg["bw_tol"], lin=l) for sv, f, h, g, l in zip(solvers, fmaps, H_stars, gs, lins)]
+            solvers = [sl.solver("bw", f.plan, cfg["bw_thres"], torch.float32, ctx.shard) for sl, f in zip(slots, fmaps)]
+            if engine.adjoint_batchable(solvers, lins):
+                outs = engine.broyden_solve_adjoint_batch(solvers, lins, gs, cfg["bw_tol"])
+            else:
+                outs = [sv.solve_adjoint(f, h, g, cfg["bw_tol"], lin=l) for sv, f, h, g, l in zip(solvers, fmaps, H_stars, gs, lins)]
         total, g_inits = None, []
         for r, (o, f, h) in enumerate(zip(outs, fmaps, H_stars)):
             o.update(eps=cfg["bw_tol"], threshold=cfg["bw_thres"])
@@ -408,13 +435,13 @@ class DeepEquilibrium(nn.Module):
 
     def lockstep_applies(self, fmaps):
         """Whether R replicas go through the batched solvers: a host-side decision on the bound maps, before anything is
-        allocated.  No: a solver other than ``utilities.solver.broyden``, ``bw_solver = "gmres"``, an untiled plan, ``n_layers > 1``, a bf16 pair
-        history, both families in one call, a mixed plan without ``lin_neumann = "stored"``.  (Solvers of one call share one
-        size class by construction: all are sized for the whole shard.)"""
+        allocated.  No: a solver other than ``utilities.solver.broyden``, ``bw_solver = "gmres"`` without ``bw_gmres_lockstep``, an
+        untiled plan, ``n_layers > 1``, a bf16 pair history, both families in one call, a mixed plan without
+        ``lin_neumann = "stored"``.  (Solvers of one call share one size class by construction: all are sized for the whole shard.)"""
         if self.config_deq["solver"] is not _solver.broyden or self.history_dtype() != torch.float32:
             return False
-        if self.config_deq.get("bw_solver") is not None:   # the GMRES adjoint solve has no lockstep form
-            return False
+        if self.config_deq.get("bw_solver") is not None and not self.config_deq.get("bw_gmres_lockstep"):
+            return False   # the GMRES adjoint solve takes its lockstep form only with the key (decided before the maps are looked at)
         if any(not f.plan.tiled or f.weights.n_layers != 1 or not f.can_linearize() for f in fmaps):
             return False
         if any(bool(f.plan.mixed) != bool(fmaps[0].plan.mixed) for f in fmaps):
@@ -432,7 +459,10 @@ class DeepEquilibrium(nn.Module):
         plan, ``n_layers > 1``, bf16 history, both families, mixed without stored Neumann rows; or ``engine.shard_batchable`` /
         ``engine.adjoint_batchable`` say no) the replicas are solved one after the other through the single-mesh paths; the
         result has replica semantics either way.  With ``bw_solver = "gmres"`` the replicas are solved one after the other, forward
-        and backward: no lockstep GMRES exists, and each slot keeps its own GMRES handle and basis.  The Jacobian regulariser stays per replica (``_JacLossFn``), its probes drawn
+        and backward, each slot keeping its own GMRES handle and basis -- unless ``bw_gmres_lockstep`` is set: the lockstep route
+        then applies under the same conditions, its backward solving the R adjoint systems by restarted GMRES in lockstep
+        (``engine.gmres_solve_adjoint_batch``; the handles are sized for the shard) or, where ``engine.gmres_adjoint_batchable``
+        says no, with the same handles one after the other.  The Jacobian regulariser stays per replica (``_JacLossFn``), its probes drawn
         in replica order from ``generator`` and kept as ``last_probes``; ``last_forward`` / ``last_backward`` are lists of the
         solver dicts, the CSV log lines are written per replica.
 
@@ -509,7 +539,7 @@ class DeepEquilibrium(nn.Module):
             m = int(self.config_deq.get("bw_gmres_m", 50))
             key = (fmap.plan, m)
             old = getattr(self, "_bw_gmres_key", None)
-            if old is None or old[0] is not key[0] or old[1] != m:
+            if old is None or len(old) != 2 or old[0] is not key[0] or old[1] != m:
                 if getattr(self, "_bw_gmres", None) is not None:
                     self._bw_gmres.close()
                 self._bw_gmres = engine.DeviceGmres(fmap.plan.N * engine.D, fmap.plan.device, m)
@@ -617,6 +647,9 @@ class _Base(nn.Module):
             m = self.config.get("bw_gmres_m", min(50, int(self.config["bw_thres"])))   # (50: the restart length at which the CPU probe's error matched Broyden's)
             self.config_deq["bw_solver"] = engine.check_bw_solver(self.config.get("bw_solver"), m, self.config["bw_thres"])   # (NativeError otherwise)
             self.config_deq["bw_gmres_m"] = m
+        if "bw_gmres_lockstep" in self.config:   # optional: replicas with bw_solver = "gmres" solve their adjoint systems in lockstep
+            self.config_deq["bw_gmres_lockstep"] = engine.check_bw_gmres_lockstep(self.config["bw_gmres_lockstep"],
+                                                                                 self.config.get("bw_solver"))   # (NativeError otherwise)
         if "broyden_history_dtype" in self.config:   # optional: bf16 storage of the Broyden pairs (utilities.solver.broyden only)
             engine.history_code(self.config["broyden_history_dtype"])   # (ValueError for any other dtype)
             self.config_deq["broyden_history_dtype"] = self.config["broyden_history_dtype"]

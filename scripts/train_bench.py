@@ -3,6 +3,7 @@ hexagon meshes -- forward Broyden solve, on-device adjoint solve, parameter-VJP,
 the CPU oracle's restated training step (autograd + restated broyden) timed beside it on the same batch.
 
     python3 scripts/train_bench.py [graphs_per_batch=50] [hex_n=13] [steps=5] [cpu=1] [jac_weight=0] [family=dirichlet|mixed] [replicas=R]
+                                   [bw_solver=gmres] [lockstep=1]
 
 replicas=R (anywhere on the line): R union batches of graphs_per_batch graphs each.  One step over the R batches as replicas in
 lockstep (``net(list_of_batches)``: batched forward and adjoint solves, the reference's ``DataParallel`` with ``num_gpus = R``) is
@@ -10,7 +11,9 @@ timed beside R sequential single-batch steps over the same batches -- the single
 same with ``bw_linearize`` (the lockstep's backward is always the linearised one) --, the three alternated step by step in one
 process, median of ``steps``.  Every sequential route keeps one model per batch, so that no route re-allocates solver state
 between steps.  The CPU oracle is not timed in this mode.  route=lockstep|sequential|sequential_lin restricts the run to one route
-(a profiler run of that route in a process of its own).
+(a profiler run of that route in a process of its own).  bw_solver=gmres (with replicas=R): every route's implicit backward is the
+restarted GMRES solve (``bw_solver = "gmres"``); the replica step then solves its replicas one after the other unless lockstep=1
+is given too (``bw_gmres_lockstep = True``: the GMRES adjoint solves of the replicas in lockstep).
 
 jac_weight = 1 is what the reference's launch scripts use (launch_local.sh:24): the step then also runs the backward of
 the VJP (csrc/gather_backward.hip).
@@ -30,7 +33,7 @@ sys.path.insert(0, ROOT)
 pkg = lambda n="": importlib.import_module("psi-gnn_amd" + ("." + n if n else ""))
 
 
-def replicas_main(argv, R, only=None):
+def replicas_main(argv, R, only=None, bw_solver=None, gmres_lockstep=False):
     import statistics
     import numpy as np
     B = int(argv[1]) if len(argv) > 1 else 50
@@ -49,6 +52,8 @@ def replicas_main(argv, R, only=None):
 
     def trainer(**kw):
         cfg = dict(latent_dim=10, n_layers=1, solver=solver.broyden, fw_tol=1e-5, fw_thres=500, bw_tol=1e-8, bw_thres=500, **kw)
+        if bw_solver is not None:
+            cfg["bw_solver"] = bw_solver
         if mixed:
             cfg["lin_neumann"] = "stored"
         net = (pkg("mixed") if mixed else pkg("model_psignn")).ModelDEQDSS(cfg)
@@ -58,7 +63,7 @@ def replicas_main(argv, R, only=None):
                                sched_step_deq=0.5, sched_step_ae=0.5, path_ckpt=None, min_loss_save=1e9, max_epochs=0,
                                gradient_clip=1e-2, sup_weight=0.0, jac_weight=jw))
 
-    lock = trainer() if only in (None, "lockstep") else None
+    lock = trainer(**({"bw_gmres_lockstep": True, "bw_linearize": True} if gmres_lockstep else {})) if only in (None, "lockstep") else None
     seq = [trainer() for _ in range(R)] if only in (None, "sequential") else []
     seq_lin = [trainer(bw_linearize=True) for _ in range(R)] if only in (None, "sequential_lin") else []
     routes = {"lockstep": lambda: lock.train_step(batches),
@@ -89,17 +94,17 @@ def replicas_main(argv, R, only=None):
     med = {k: statistics.median(v) for k, v in times.items()}
     out = {"workload": f"training step ({'mixed' if mixed else 'dirichlet'} family), {R} replicas, each a union batch of {B} hexagon meshes "
                        f"(n={n}): {batches[0].num_nodes} nodes per replica; fw_tol 1e-5 / bw_tol 1e-8, thresholds 500, jac_weight {jw}",
-           "replicas": R, "steps": steps, "s_per_step_median": med, "s_per_step_all": times, "one_more_step_profiled": kern}
+           "replicas": R, "bw_solver": bw_solver, "bw_gmres_lockstep": gmres_lockstep, "steps": steps, "s_per_step_median": med, "s_per_step_all": times, "one_more_step_profiled": kern}
     if only is None:
         out.update(lockstep_over_sequential=med["lockstep"] / med["sequential"],
                    lockstep_over_sequential_lin=med["lockstep"] / med["sequential_lin"])
     if lock is not None:
         dq = lock.net.deqdss
-        out.update(lockstep_fw_nstep=[o["nstep"] for o in dq.last_forward], lockstep_bw_n_iter=[o["n_iter"] for o in dq.last_backward])
+        out.update(lockstep_fw_nstep=[o["nstep"] for o in dq.last_forward], lockstep_bw_n_iter=[o.get("n_iter", o["nstep"]) for o in dq.last_backward])
     if seq:
-        out["sequential_bw_n_iter"] = [t.net.deqdss.last_backward["n_iter"] for t in seq]
+        out["sequential_bw_n_iter"] = [t.net.deqdss.last_backward.get("n_iter", t.net.deqdss.last_backward["nstep"]) for t in seq]
     if seq_lin:
-        out["sequential_lin_bw_n_iter"] = [t.net.deqdss.last_backward["n_iter"] for t in seq_lin]
+        out["sequential_lin_bw_n_iter"] = [t.net.deqdss.last_backward.get("n_iter", t.net.deqdss.last_backward["nstep"]) for t in seq_lin]
     print(json.dumps(out))
 
 
@@ -107,8 +112,10 @@ def main():
     rs = [a for a in sys.argv if a.startswith("replicas=")]
     if rs:
         ro = [a.split("=", 1)[1] for a in sys.argv if a.startswith("route=")]
-        return replicas_main([a for a in sys.argv if not a.startswith(("replicas=", "route="))], int(rs[0].split("=", 1)[1]),
-                             ro[0] if ro else None)
+        opt = {a.split("=", 1)[0]: a.split("=", 1)[1] for a in sys.argv if a.startswith(("bw_solver=", "lockstep="))}
+        return replicas_main([a for a in sys.argv if not a.startswith(("replicas=", "route=", "bw_solver=", "lockstep="))],
+                             int(rs[0].split("=", 1)[1]), ro[0] if ro else None, bw_solver=opt.get("bw_solver"),
+                             gmres_lockstep=opt.get("lockstep", "0") not in ("0", ""))
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 13
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
