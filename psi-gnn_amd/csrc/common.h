@@ -46,6 +46,42 @@ extern int g_knob_epoch;
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Owner of one array for the span of a call: alloc(n) once, get(), freed by the destructor -- so that HIP_TRY and `return rc` may
+// leave the function anywhere.  Neither copyable nor movable.
+template <class T, hipError_t (*Alloc)(void**, size_t), hipError_t (*Free)(void*)>
+class ScopedArray {
+ public:
+  ScopedArray() = default;
+  ScopedArray(const ScopedArray&) = delete;
+  ScopedArray& operator=(const ScopedArray&) = delete;
+  ~ScopedArray() { if (p_) (void)Free(p_); }
+  hipError_t alloc(size_t n) {
+    if (p_) return hipErrorInvalidValue;
+    const hipError_t e = Alloc(reinterpret_cast<void**>(&p_), n * sizeof(T));
+    if (e != hipSuccess) p_ = nullptr;
+    return e;
+  }
+  T* get() const { return p_; }
+
+ private:
+  T* p_ = nullptr;
+};
+static inline hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+static inline hipError_t device_free(void* p) { return hipFree(p); }
+static inline hipError_t pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes); }
+static inline hipError_t pinned_free(void* p) { return hipHostFree(p); }
+template <class T> using DeviceArray = ScopedArray<T, device_alloc, device_free>;   // device memory
+template <class T> using PinnedArray = ScopedArray<T, pinned_alloc, pinned_free>;   // pinned host memory
+
+// Copy n descriptors to the device and wait: they are read from pageable host memory, which must have left the host before its
+// owner can go.
+template <class T>
+static inline int upload_wait(T* d_dst, const T* h_src, size_t n, hipStream_t st) {
+  HIP_TRY(hipMemcpyAsync(d_dst, h_src, sizeof(T) * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return PSIGNN_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Weight pack layout (floats).  All blocks are nn.Linear (out,in) row-major.
 // Written for D = 10 (the numbers in brackets); every size and offset is an expression in D:

@@ -750,6 +750,35 @@ static int adj_prepare(psignn_gmres* s, int max_products) {
   return PSIGNN_OK;
 }
 
+// The read-out at the end of a solve, single or lockstep (s->h_ast holds the final solve state): the best iterate in the caller's
+// numbering (res_plan: the plan whose order the solve ran in, or NULL), the traces up to min(cycles, a_cap) entries, the counts.
+static int adjoint_gmres_read_out(psignn_gmres* s, const psignn_plan* res_plan, const float* ybest, float* d_result,
+                                  psignn_gmres_adjoint_info_t* info, double* h_rel, double* h_abs, hipStream_t st) {
+  int rc;
+  if (d_result) {
+    if (res_plan) {
+      if ((rc = psignn_plan_permute(res_plan, ybest, D, d_result, 0, st))) return rc;
+    } else {
+      HIP_TRY(hipMemcpyAsync(d_result, ybest, (size_t)s->M * 4, hipMemcpyDeviceToDevice, st));
+    }
+  }
+  const AdjState& h = *s->h_ast;
+  const int n = std::min(h.cycles, s->a_cap);
+  if (h_rel && n > 0) HIP_TRY(hipMemcpyAsync(h_rel, s->a_rel, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  if (h_abs && n > 0) HIP_TRY(hipMemcpyAsync(h_abs, s->a_abs, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (info) {
+    info->products = h.products;
+    info->cycles = h.cycles;
+    info->stop_reason = h.stop;
+    info->n_reorth = h.n_reorth;
+    info->lowest = h.lowest;
+    info->lowest_abs = h.lowest_abs;
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
 // vjp(w, out): out = J_f(h*)^T w in the solve's numbering.  grad, y, fy, ybest: that numbering too.  res_plan: the plan whose order the
 // solve runs in (the result goes back to the caller's numbering), or NULL.
 template <class F>
@@ -788,28 +817,7 @@ static int adjoint_gmres_loop(psignn_gmres* s, const float* grad, double eps, in
     LAUNCH("k_gm_backsolve", st, (k_gm_backsolve<<<1, 64, 0, st>>>(s->st, 0, s->m, s->H, s->g, s->y, s->coef)));
     VLAUNCH("k_gm_combine", st, s->vec, k_gm_combine, (g, TB, 0, st), s->M, s->ld, s->st, 0, s->V, s->coef, w.y, -1.f, w.y);
   }
-  if (d_result) {
-    if (res_plan) {
-      if ((rc = psignn_plan_permute(res_plan, w.ybest, D, d_result, 0, st))) return rc;
-    } else {
-      HIP_TRY(hipMemcpyAsync(d_result, w.ybest, (size_t)vb, hipMemcpyDeviceToDevice, st));
-    }
-  }
-  const AdjState& h = *s->h_ast;
-  const int n = std::min(h.cycles, s->a_cap);
-  if (h_rel && n > 0) HIP_TRY(hipMemcpyAsync(h_rel, s->a_rel, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  if (h_abs && n > 0) HIP_TRY(hipMemcpyAsync(h_abs, s->a_abs, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (info) {
-    info->products = h.products;
-    info->cycles = h.cycles;
-    info->stop_reason = h.stop;
-    info->n_reorth = h.n_reorth;
-    info->lowest = h.lowest;
-    info->lowest_abs = h.lowest_abs;
-  }
-  HIP_TRY(hipGetLastError());
-  return PSIGNN_OK;
+  return adjoint_gmres_read_out(s, res_plan, w.ybest, d_result, info, h_rel, h_abs, st);
 }
 
 extern "C" int psignn_gmres_solve_adjoint(psignn_gmres_t* s, const psignn_plan_t* p, const float* W, int nl, const float* h_star,
@@ -987,7 +995,8 @@ extern "C" int psignn_gmres_adjoint_batchable(int n, psignn_gmres_t* const* sv, 
   return 1;
 }
 
-// The batched launch sequence of Arnoldi step j (gm_step_launch, one launch per pass over the shard)
+// The batched launch sequence of Arnoldi step j (gm_step_launch, one launch per pass over the shard).  The step has no schedule to
+// decide -- seven launches, no forms, no stated bytes --, so the two sequences stand side by side instead of behind a chain and two targets.
 static void gm_step_launch_batch(const GmresBatchDesc* dd, int n, int vec, unsigned max_g, int j, double shift, double eta,
                                  hipStream_t st) {
   const dim3 gv(max_g, 1, (unsigned)n);
@@ -1064,33 +1073,19 @@ extern "C" int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** sv, 
     }
   }
   const int off_cycle = offsetof(GmresState, done) / 4, off_solve = offsetof(AdjState, done) / 4;
-  GmresBatchDesc* d_descs = nullptr;
-  LinBatchDesc* d_tab = nullptr;
-  int32_t *d_flags = nullptr, *h_flags = nullptr;   // [2 r] done, [2 r + 1] steps_left; [2 n] every cycle over
-  auto cleanup = [&]() {
-    if (d_descs) (void)hipFree(d_descs);
-    if (d_tab) (void)hipFree(d_tab);
-    if (d_flags) (void)hipFree(d_flags);
-    if (h_flags) (void)hipHostFree(h_flags);
-  };
-#define BT(expr)                                                                          \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      cleanup();                                                                          \
-      return PSIGNN_EHIP;                                                                 \
-    }                                                                                     \
-  } while (0)
-  const size_t flag_bytes = (size_t)(2 * n + 1) * 4;
-  BT(hipMalloc((void**)&d_descs, sizeof(GmresBatchDesc) * n));
-  BT(hipMalloc((void**)&d_tab, sizeof(LinBatchDesc) * tab.size()));
-  BT(hipMalloc((void**)&d_flags, flag_bytes));
-  BT(hipHostMalloc((void**)&h_flags, flag_bytes));
-  BT(hipMemcpyAsync(d_descs, hd.data(), sizeof(GmresBatchDesc) * n, hipMemcpyHostToDevice, st));
-  BT(hipMemcpyAsync(d_tab, tab.data(), sizeof(LinBatchDesc) * tab.size(), hipMemcpyHostToDevice, st));
-  // (the descriptors are read from pageable host vectors: they must have left the host before the vectors can go)
-  BT(hipStreamSynchronize(st));
+  DeviceArray<GmresBatchDesc> descs_mem;
+  DeviceArray<LinBatchDesc> tab_mem;
+  DeviceArray<int32_t> d_flags_mem;   // [2 r] done, [2 r + 1] steps_left; [2 n] every cycle over
+  PinnedArray<int32_t> h_flags_mem;
+  HIP_TRY(descs_mem.alloc(n));
+  HIP_TRY(tab_mem.alloc(tab.size()));
+  HIP_TRY(d_flags_mem.alloc(2 * n + 1));
+  HIP_TRY(h_flags_mem.alloc(2 * n + 1));
+  GmresBatchDesc* const d_descs = descs_mem.get();
+  LinBatchDesc* const d_tab = tab_mem.get();
+  int32_t *const d_flags = d_flags_mem.get(), *const h_flags = h_flags_mem.get();
+  if ((rc = upload_wait(d_descs, hd.data(), hd.size(), st))) return rc;
+  if ((rc = upload_wait(d_tab, tab.data(), tab.size(), st))) return rc;
   const dim3 gv((unsigned)max_g, 1, (unsigned)n), g1(1, 1, (unsigned)n);
   k_gm_init_batch<<<dim3(4, 1, (unsigned)n), TB, 0, st>>>(d_descs);
   k_ag_init_batch<<<g1, 64, 0, st>>>(d_descs);
@@ -1098,7 +1093,7 @@ extern "C" int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** sv, 
     if (cycle > 0) {
       PROF_BYTES(bv_tot);
       rc = psignn_lin_vjp_batch(d_tab + (size_t)(m + 1) * n, n, n_slots, max_rows, W, mixed, off_solve, st);
-      if (rc) { cleanup(); return rc; }
+      if (rc) return rc;
     }
     PROF_BYTES(cycle ? 4 * vb_tot : 3 * vb_tot);
     VLAUNCH("k_ag_begin_batch", st, vec, k_ag_begin_batch, (gv, TB, 0, st), d_descs, cycle == 0);
@@ -1107,8 +1102,8 @@ extern "C" int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** sv, 
     VLAUNCH("k_ag_keep_batch", st, vec, k_ag_keep_batch, (gv, TB, 0, st), d_descs);
     VLAUNCH("k_gm_scale_batch", st, vec, k_gm_scale_batch, (gv, TB, 0, st), d_descs, 0);
     k_ag_gather_batch<<<1, 64, 0, st>>>(d_descs, n, d_flags);
-    BT(hipMemcpyAsync(h_flags, d_flags, (size_t)(2 * n) * 4, hipMemcpyDeviceToHost, st));
-    BT(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(h_flags, d_flags, (size_t)(2 * n) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     int steps = 0;   // the largest allowance among the replicas still solving; 0: all are done
     for (int r = 0; r < n; ++r)
       if (!h_flags[2 * r]) steps = std::max(steps, h_flags[2 * r + 1]);
@@ -1116,44 +1111,24 @@ extern "C" int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** sv, 
     for (int j = 0; j < steps; ++j) {
       PROF_BYTES(bv_tot);
       rc = psignn_lin_vjp_batch(d_tab + (size_t)j * n, n, n_slots, max_rows, W, mixed, off_cycle, st);
-      if (rc) { cleanup(); return rc; }
+      if (rc) return rc;
       gm_step_launch_batch(d_descs, n, vec, (unsigned)max_g, j, 1.0, 0.5 * eps, st);
       if ((j + 1) % poll_every == 0 && j + 1 < steps) {
         k_gm_all_done_batch<<<1, 64, 0, st>>>(d_descs, n, d_flags + 2 * n);
-        BT(hipMemcpyAsync(h_flags + 2 * n, d_flags + 2 * n, 4, hipMemcpyDeviceToHost, st));
-        BT(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(h_flags + 2 * n, d_flags + 2 * n, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         if (h_flags[2 * n]) break;
       }
     }
     LAUNCH("k_gm_backsolve_batch", st, (k_gm_backsolve_batch<<<g1, 64, 0, st>>>(d_descs)));
     VLAUNCH("k_gm_combine_batch", st, vec, k_gm_combine_batch, (gv, TB, 0, st), d_descs);
   }
-  // ---- per replica what adjoint_gmres_loop gives: the result in the caller's numbering, the traces, the counts
-  for (int r = 0; r < n; ++r) BT(hipMemcpyAsync(sv[r]->h_ast, sv[r]->ast, sizeof(AdjState), hipMemcpyDeviceToHost, st));
-  BT(hipStreamSynchronize(st));
-  for (int r = 0; r < n; ++r) {
-    psignn_gmres* s = sv[r];
-    if (d_results && d_results[r]) {
-      rc = psignn_plan_permute(psignn_lin_plan(lins[r]), works[r].ybest, D, d_results[r], 0, st);
-      if (rc) { cleanup(); return rc; }
-    }
-    const int nc = std::min(s->h_ast->cycles, s->a_cap);
-    if (h_rel && h_rel[r] && nc > 0) BT(hipMemcpyAsync(h_rel[r], s->a_rel, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
-    if (h_abs && h_abs[r] && nc > 0) BT(hipMemcpyAsync(h_abs[r], s->a_abs, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
-  }
-  BT(hipStreamSynchronize(st));
-  if (infos)
-    for (int r = 0; r < n; ++r) {
-      const AdjState& h = *sv[r]->h_ast;
-      infos[r].products = h.products;
-      infos[r].cycles = h.cycles;
-      infos[r].stop_reason = h.stop;
-      infos[r].n_reorth = h.n_reorth;
-      infos[r].lowest = h.lowest;
-      infos[r].lowest_abs = h.lowest_abs;
-    }
-  BT(hipGetLastError());
-  cleanup();
-#undef BT
+  // ---- per replica what adjoint_gmres_loop gives
+  for (int r = 0; r < n; ++r) HIP_TRY(hipMemcpyAsync(sv[r]->h_ast, sv[r]->ast, sizeof(AdjState), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int r = 0; r < n; ++r)
+    if ((rc = adjoint_gmres_read_out(sv[r], psignn_lin_plan(lins[r]), works[r].ybest, d_results ? d_results[r] : nullptr,
+                                     infos ? &infos[r] : nullptr, h_rel ? h_rel[r] : nullptr, h_abs ? h_abs[r] : nullptr, st)))
+      return rc;
   return PSIGNN_OK;
 }

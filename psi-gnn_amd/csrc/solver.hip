@@ -380,7 +380,7 @@ __global__ __launch_bounds__(RB) void k_reduce_check(Status* st, const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Three-sweep form of the update (long vectors; launch_update_uvu).  The two-pass form reads U and V twice per iteration:
+// Three-sweep form of the update (long vectors; update_chain).  The two-pass form reads U and V twice per iteration:
 // dots (a = U^T dx, c = V^T dg, b = V^T g), then axpy (vT = -dx + V a, D1 = dx + dg - U c, D2 = g - U b).  But V a needs only
 // a, and U c / U b need only c and b: sweep 1 reads U for a; sweep 2 reads V ONCE for c, b AND V a; sweep 3 reads U for
 // U c, U b -- three single-array sweeps instead of four, the same arithmetic on every element and the same partial-sum shapes
@@ -1222,7 +1222,7 @@ static int broyden_alloc(psignn_broyden* s) {
     s->vec_ax = 4;
     s->nblk_ax = (int)cdiv(s->M, (int64_t)4 * TB);
   }
-  // three-sweep update (launch_update): where an UNSPLIT sweep covers the chip -- long vectors at 16 floats per lane, mid-size
+  // three-sweep update (update_chain): where an UNSPLIT sweep covers the chip -- long vectors at 16 floats per lane, mid-size
   // vectors and shards of short vectors at the 4-float width of their axpy pass.  PSIGNN_UVU=0|1 overrides (A/B, tests).
   s->uvu = 0;
   if (s->vec == 16 && s->jgroups == 1 && s->vec_ax == 16) {
@@ -1388,98 +1388,146 @@ static inline int sel_off_nxt() { return offsetof(Status, nxt) / 4; }
 
 static inline __bf16* bf16_pairs(float* p) { return reinterpret_cast<__bf16*>(p); }   // U, V of a bf16-history solver
 
-// everything of one iteration after fx = f(x_next) is available; k = pairs stored so far
-// fused_npart > 0: the f kernel already produced g, dg and the norm partials (fused_npart entries each)
-static void launch_update(psignn_broyden* s, int k, double eps, hipStream_t st, int fused_npart = 0) {
-  unsigned g = (unsigned)s->nblk;
-  float* const gnew = s->gbuf[(k + 1) & 1];        // g of the iterate just evaluated
-  const float* const gold = s->gbuf[k & 1];        // g of the iterate before it
-  if (!fused_npart) {
-    PROF_BYTES(3 * (int64_t)s->M * 4);
-    VLAUNCH("k_resid", st, s->vec, k_resid, (g, TB, 0, st), s->M, s->st, s->xbuf, s->fx, gnew, s->nrm_part, s->nblk);
-  }
-  const int np = fused_npart ? fused_npart : s->nblk;  // one partial pair per block / per tile
-  if (s->uvu) {
-    const int kd = k >= s->thr ? 0 : k;
-    const unsigned gu = (unsigned)s->nblk_u;
-    if (k == 0) s->a_ready = 0;
+// ------------------------------------------------------------------------------------------
+// The update chain: everything of one iteration after g_new and the norm partials are available; k = pairs stored so far.
+// The schedule stands here once -- two-pass or three-sweep form, which a_j the folded sweep 3 of the last iteration delivered
+// (a_ready / a_from), the keep window and its KB, LDS or register fold, the `last` gate, the split over pair groups with its combine
+// launch, the own-width axpy pass, and the algorithmic bytes of every launch.  A target knows HOW a pass is launched: SingleTarget
+// (the k_* kernels on one solver's fields) and ShardTarget (the kb_* kernels, one launch per pass over a shard, below).  Both run
+// the same *_body functions, so a mesh has the same bits either way.
+// ------------------------------------------------------------------------------------------
+template <class Target>
+static void update_chain(Target& t, int k, double eps) {
+  const psignn_broyden& c = t.size_class();
+  const int thr = c.thr;
+  const int64_t vb = t.vec_bytes();                    // one state vector (summed over a shard)
+  const int64_t pe = vb / 4 * t.pair_elem_bytes();     // one stored vector U_j / V_j
+  const int kd = k >= thr ? 0 : k;   // the threshold stop is about to fire: no slot left for another pair
+  const bool last = k + 1 >= thr;    // (iteration thr's stop test has just fired: the passes after it return at once and state no bytes)
+  if (c.uvu) {
+    if (k == 0) t.a_ready() = 0;
     // a_j of this iteration: pairs j >= a_from were delivered by the folded sweep 3 of the last iteration, the others need sweep 1
-    const int a_from = s->a_ready ? s->a_from : kd;
-    if (std::min(a_from, kd) > 0 && s->hist) {
-      PROF_BYTES((2 * (int64_t)kd + 4) * s->M);   // kd bf16 columns of U + dx
-      VLAUNCH("k_sweep_u1_bf16", st, s->vec_u, k_sweep_u1_bf16, (gu, TB, 0, st), s->M, kd, s->st, bf16_pairs(s->U), s->upd, s->part, s->ldp, s->ld);
-    } else if (std::min(a_from, kd) > 0) {
-      PROF_BYTES((std::min(a_from, kd) + 1) * (int64_t)s->M * 4);   // its columns of U + dx
-      VLAUNCH("k_sweep_u1", st, s->vec_u, k_sweep_u1, (gu, TB, 0, st), s->M, std::min(a_from, kd), s->st, s->U, s->upd, s->part, s->ldp, s->ld);
+    // (all meshes of a shard carry the same number of stored pairs: one a_from / keep window for the launch)
+    const int a_from = t.a_ready() ? t.a_from() : kd;
+    const int n1 = std::min(a_from, kd);
+    if (n1 > 0) {
+      PROF_BYTES(n1 * pe + vb);   // its columns of U + dx
+      t.sweep_u1(n1);
     }
-    LAUNCH("k_reduce_check", st, (k_reduce_a_check<<<dim3(std::max(kd, 1), RA + 1), RB, 0, st>>>(
-        s->st, s->part, s->nblk_u, s->ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace,
-        s->parta, s->nblk4, a_from)));
-    s->a_ready = 0;
-    if (k >= s->thr) return;
-    // (iteration thr's stop test has just fired: the two sweeps below return at once and state no bytes)
-    const bool last = k + 1 >= s->thr;
-    if (s->hist) {   // bf16 pairs: unfolded three-sweep form, pairs at 2 bytes (broyden_alloc: u2d_kmax = 0)
-      PROF_BYTES(last ? 0 : (2 * (int64_t)k + 14) * s->M);   // k bf16 columns of V + dx, dg, g; writes V[k]
-      VLAUNCH("k_sweep_v_bf16", st, s->vec_u, k_sweep_v_bf16, (gu, TB, 0, st), s->M, k, s->st, bf16_pairs(s->V), s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
-      LAUNCH("k_reduce_cb", st, (k_reduce_cb<<<dim3(std::max(k, 1), 3), RB, 0, st>>>(s->st, s->part, s->nblk_u, s->pstride, s->ldp, s->thr, k, s->coef, s->part2, s->nblk_u)));
-      PROF_BYTES(last ? 0 : (2 * (int64_t)k + 18) * s->M);   // k bf16 columns of U + update, dg, g; writes U[k], update
-      VLAUNCH("k_sweep_u2_bf16", st, s->vec_u, k_sweep_u2_bf16, (gu, TB, 0, st), s->M, k, s->st, bf16_pairs(s->U), s->upd, gold, gnew, s->coef, s->thr, s->ld);
-      return;
-    }
-    PROF_BYTES(last ? 0 : (k + 4) * (int64_t)s->M * 4);   // k columns of V + dx, dg, g; writes V[k]
-    VLAUNCH("k_sweep_v", st, s->vec_u, k_sweep_v, (gu, TB, 0, st), s->M, k, s->st, s->V, s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
-    LAUNCH("k_reduce_cb", st, (k_reduce_cb<<<dim3(std::max(k, 1), 3), RB, 0, st>>>(s->st, s->part, s->nblk_u, s->pstride, s->ldp, s->thr, k, s->coef, s->part2, s->nblk_u)));
-    const int keep0 = k <= s->u2d_kmax ? 0 : k - s->u2d_keep;      // few stored pairs: all kept; later the most recent ones
-    if (s->u2d_kmax > 0 && (k <= s->u2d_kmax || s->u2d_keep > 0) && k + 1 < s->thr) {
-      PROF_BYTES((k + 5) * (int64_t)s->M * 4);   // k columns of U + update, dg, g; writes U[k], update (whichever form runs)
+    t.reduce_a_check(kd, eps, a_from);
+    t.a_ready() = 0;
+    if (k >= thr) return;
+    PROF_BYTES(last ? 0 : (k + 1) * pe + 3 * vb);   // k columns of V + dx, dg, g; writes V[k]
+    t.sweep_v(k);
+    t.reduce_cb(k);
+    const int keep0 = k <= c.u2d_kmax ? 0 : k - c.u2d_keep;      // few stored pairs: all kept; later the most recent ones
+    if (c.u2d_kmax > 0 && (k <= c.u2d_kmax || c.u2d_keep > 0) && !last) {
+      PROF_BYTES((k + 1) * pe + 4 * vb);   // k columns of U + update, dg, g; writes U[k], update (whichever form runs)
       const int nk = k - keep0;
-      if (s->u2d_reg) {
-#define U2R_ARGS s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta, s->ld, keep0
-        if (nk <= 8) LAUNCH("k_sweep_u2d", st, (k_sweep_u2r<8><<<(unsigned)s->nblk4, TB, 0, st>>>(U2R_ARGS)));
-        else if (nk <= 16) LAUNCH("k_sweep_u2d", st, (k_sweep_u2r<16><<<(unsigned)s->nblk4, TB, 0, st>>>(U2R_ARGS)));
-        else LAUNCH("k_sweep_u2d", st, (k_sweep_u2r<24><<<(unsigned)s->nblk4, TB, 0, st>>>(U2R_ARGS)));
-#undef U2R_ARGS
-      } else {
-        const size_t lds = (size_t)std::max(nk, 1) * TB * 16;
-        LAUNCH("k_sweep_u2d", st, (k_sweep_u2d<<<(unsigned)s->nblk4, TB, lds, st>>>(s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta,
-                                                                                    s->ld, keep0)));
-      }
-      s->a_ready = 1;
-      s->a_from = keep0;
+      if (!c.u2d_reg) t.sweep_u2d(k, keep0, (size_t)std::max(nk, 1) * TB * 16);
+      else if (nk <= 8) t.template sweep_u2r<8>(k, keep0);
+      else if (nk <= 16) t.template sweep_u2r<16>(k, keep0);
+      else t.template sweep_u2r<24>(k, keep0);
+      t.a_ready() = 1;
+      t.a_from() = keep0;
     } else {
-      PROF_BYTES(last ? 0 : (k + 5) * (int64_t)s->M * 4);
-      VLAUNCH("k_sweep_u2", st, s->vec_u, k_sweep_u2, (gu, TB, 0, st), s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->ld);
+      PROF_BYTES(last ? 0 : (k + 1) * pe + 4 * vb);
+      t.sweep_u2(k);
     }
     return;
   }
   // split of the sweeps over the stored pairs: only when there are enough pairs to share out
-  const int G = (s->jgroups > 1 && k >= 4 * s->jgroups) ? s->jgroups : 1;
-  const int js = (int)cdiv(std::max(k, 1), G);
-  const int kd = k >= s->thr ? 0 : k;  // the threshold stop is about to fire: no slot left for another pair
+  const int G = t.groups(k);
   if (kd > 0) {
-    PROF_BYTES((2 * kd + 3) * (int64_t)s->M * 4);
-    VLAUNCH("k_dots", st, s->vec, k_dots, (dim3(g, G), TB, 0, st), s->M, kd, s->st, s->U, s->V, s->upd, gold, gnew, s->part, s->pstride, s->ldp, js, s->ld);
+    PROF_BYTES((2 * kd + 3) * vb);
+    t.dots(kd, G);
   }
-  LAUNCH("k_reduce_check", st, (k_reduce_check<<<dim3(std::max(kd, 1), 4), RB, 0, st>>>(
-      s->st, s->part, s->nblk, s->pstride, s->ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace)));
-  if (k >= s->thr) return;
-  if (s->vec_ax != s->vec) {  // unsplit, own width
-    const unsigned ga = (unsigned)s->nblk_ax;
-    PROF_BYTES(k + 1 >= s->thr ? 0 : (2 * k + 6) * (int64_t)s->M * 4);
-    VLAUNCH("k_axpy", st, s->vec_ax, k_axpy, (dim3(ga, 1), TB, 0, st), s->M, k, s->st, s->U, s->V, s->upd, gold, gnew, s->coef, s->thr, s->part, s->nblk_ax, std::max(k, 1), s->jpart, s->ld);
-    PROF_BYTES(k + 1 >= s->thr ? 0 : 4 * (int64_t)s->M * 4);
-    VLAUNCH("k_final", st, s->vec_ax, k_final, (ga, TB, 0, st), s->M, k, s->st, s->U, s->upd, s->ld, s->part, s->nblk_ax);
-    return;
+  t.reduce_check(kd, eps);
+  if (k >= thr) return;
+  const bool own_width = c.vec_ax != c.vec;   // the axpy / final passes run unsplit at their own vector width (broyden_alloc)
+  const int Ga = own_width ? 1 : G;
+  PROF_BYTES(last ? 0 : (2 * k + (Ga > 1 ? 3 * Ga : 6)) * vb);   // split: every block row writes its three partial vectors
+  t.axpy(k, Ga, own_width);
+  if (!own_width && t.combine_due(k, G)) {
+    PROF_BYTES(last || G <= 1 ? 0 : (3 * G + 6) * vb);
+    t.combine(k, G);
   }
-  PROF_BYTES(k + 1 >= s->thr ? 0 : (2 * k + (G > 1 ? 3 * G : 6)) * (int64_t)s->M * 4);   // split: every block row writes its three partial vectors
-  VLAUNCH("k_axpy", st, s->vec, k_axpy, (dim3(g, G), TB, 0, st), s->M, k, s->st, s->U, s->V, s->upd, gold, gnew, s->coef, s->thr, s->part, s->nblk, js, s->jpart, s->ld);
-  if (G > 1) {
-    PROF_BYTES(k + 1 >= s->thr ? 0 : (3 * G + 6) * (int64_t)s->M * 4);
-    VLAUNCH("k_axpy_combine", st, s->vec, k_axpy_combine, (g, TB, 0, st), s->M, k, G, s->st, s->jpart, s->U, s->V, s->upd, gold, gnew, s->part, s->nblk, s->ld);
+  PROF_BYTES(last ? 0 : 4 * vb);
+  t.final_pass(k, own_width);
+}
+
+// One solver.  Owns the bf16-history variants of the three sweeps (broyden_alloc: always the unfolded three-sweep form).
+struct SingleTarget {
+  psignn_broyden* s;
+  hipStream_t st;
+  float* gnew;         // g of the iterate just evaluated
+  const float* gold;   // g of the iterate before it
+  int np;              // norm partials the stop test sums: one pair per block of k_resid / per tile of the fused f kernel
+  const psignn_broyden& size_class() const { return *s; }
+  int64_t vec_bytes() const { return s->M * 4; }
+  int pair_elem_bytes() const { return s->hist ? 2 : 4; }
+  int& a_ready() { return s->a_ready; }
+  int& a_from() { return s->a_from; }
+  int groups(int k) const { return (s->jgroups > 1 && k >= 4 * s->jgroups) ? s->jgroups : 1; }
+  bool combine_due(int, int G) const { return G > 1; }
+  unsigned gu() const { return (unsigned)s->nblk_u; }
+
+  void sweep_u1(int n1) {
+    if (s->hist) VLAUNCH("k_sweep_u1_bf16", st, s->vec_u, k_sweep_u1_bf16, (gu(), TB, 0, st), s->M, n1, s->st, bf16_pairs(s->U), s->upd, s->part, s->ldp, s->ld);
+    else VLAUNCH("k_sweep_u1", st, s->vec_u, k_sweep_u1, (gu(), TB, 0, st), s->M, n1, s->st, s->U, s->upd, s->part, s->ldp, s->ld);
   }
-  PROF_BYTES(k + 1 >= s->thr ? 0 : 4 * (int64_t)s->M * 4);
-  VLAUNCH("k_final", st, s->vec, k_final, (g, TB, 0, st), s->M, k, s->st, s->U, s->upd, s->ld, s->part, s->nblk);
+  void reduce_a_check(int kd, double eps, int a_from) {
+    LAUNCH("k_reduce_check", st, (k_reduce_a_check<<<dim3(std::max(kd, 1), RA + 1), RB, 0, st>>>(
+        s->st, s->part, s->nblk_u, s->ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace,
+        s->parta, s->nblk4, a_from)));
+  }
+  void sweep_v(int k) {
+    if (s->hist) VLAUNCH("k_sweep_v_bf16", st, s->vec_u, k_sweep_v_bf16, (gu(), TB, 0, st), s->M, k, s->st, bf16_pairs(s->V), s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
+    else VLAUNCH("k_sweep_v", st, s->vec_u, k_sweep_v, (gu(), TB, 0, st), s->M, k, s->st, s->V, s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
+  }
+  void reduce_cb(int k) {
+    LAUNCH("k_reduce_cb", st, (k_reduce_cb<<<dim3(std::max(k, 1), 3), RB, 0, st>>>(s->st, s->part, s->nblk_u, s->pstride, s->ldp, s->thr, k, s->coef, s->part2, s->nblk_u)));
+  }
+  template <int KB>
+  void sweep_u2r(int k, int keep0) {
+    LAUNCH("k_sweep_u2d", st, (k_sweep_u2r<KB><<<(unsigned)s->nblk4, TB, 0, st>>>(s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta, s->ld, keep0)));
+  }
+  void sweep_u2d(int k, int keep0, size_t lds) {
+    LAUNCH("k_sweep_u2d", st, (k_sweep_u2d<<<(unsigned)s->nblk4, TB, lds, st>>>(s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta, s->ld, keep0)));
+  }
+  void sweep_u2(int k) {
+    if (s->hist) VLAUNCH("k_sweep_u2_bf16", st, s->vec_u, k_sweep_u2_bf16, (gu(), TB, 0, st), s->M, k, s->st, bf16_pairs(s->U), s->upd, gold, gnew, s->coef, s->thr, s->ld);
+    else VLAUNCH("k_sweep_u2", st, s->vec_u, k_sweep_u2, (gu(), TB, 0, st), s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->ld);
+  }
+  void dots(int kd, int G) {
+    VLAUNCH("k_dots", st, s->vec, k_dots, (dim3((unsigned)s->nblk, G), TB, 0, st), s->M, kd, s->st, s->U, s->V, s->upd, gold, gnew, s->part, s->pstride, s->ldp, (int)cdiv(kd, G), s->ld);
+  }
+  void reduce_check(int kd, double eps) {
+    LAUNCH("k_reduce_check", st, (k_reduce_check<<<dim3(std::max(kd, 1), 4), RB, 0, st>>>(
+        s->st, s->part, s->nblk, s->pstride, s->ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace)));
+  }
+  void axpy(int k, int G, bool own_width) {
+    const int nb = own_width ? s->nblk_ax : s->nblk;
+    VLAUNCH("k_axpy", st, own_width ? s->vec_ax : s->vec, k_axpy, (dim3((unsigned)nb, G), TB, 0, st), s->M, k, s->st, s->U, s->V, s->upd, gold, gnew, s->coef, s->thr, s->part, nb, (int)cdiv(std::max(k, 1), G), s->jpart, s->ld);
+  }
+  void combine(int k, int G) {
+    VLAUNCH("k_axpy_combine", st, s->vec, k_axpy_combine, ((unsigned)s->nblk, TB, 0, st), s->M, k, G, s->st, s->jpart, s->U, s->V, s->upd, gold, gnew, s->part, s->nblk, s->ld);
+  }
+  void final_pass(int k, bool own_width) {
+    const int nb = own_width ? s->nblk_ax : s->nblk;
+    VLAUNCH("k_final", st, own_width ? s->vec_ax : s->vec, k_final, ((unsigned)nb, TB, 0, st), s->M, k, s->st, s->U, s->upd, s->ld, s->part, nb);
+  }
+};
+
+// One iteration's update of one solver, after fx = f(x_next) is available.
+// fused_npart > 0: the f kernel already produced g and the norm partials (fused_npart entries each)
+static void launch_update(psignn_broyden* s, int k, double eps, hipStream_t st, int fused_npart = 0) {
+  SingleTarget t{s, st, s->gbuf[(k + 1) & 1], s->gbuf[k & 1], fused_npart ? fused_npart : s->nblk};
+  if (!fused_npart) {
+    PROF_BYTES(3 * (int64_t)s->M * 4);
+    VLAUNCH("k_resid", st, s->vec, k_resid, ((unsigned)s->nblk, TB, 0, st), s->M, s->st, s->xbuf, s->fx, t.gnew, s->nrm_part, s->nblk);
+  }
+  update_chain(t, k, eps);
 }
 
 static int read_status(psignn_broyden* s, hipStream_t st) {
@@ -1678,80 +1726,108 @@ __global__ void kb_all_done(const BatchDesc* __restrict__ descs, int n, int off_
   }
 }
 
-// Everything of one lockstep iteration after every mesh's g_new and norm partials are available (k = pairs stored so far, the same
-// for all meshes): the update chain of launch_update, one launch per pass over the shard.  Issued by the forward batched solve and by
-// the batched adjoint solve.
+// The shard's grid extents and profiling sizes, and the folded sweep's bookkeeping across the lockstep iterations
 struct BatchShape {
-  int n = 0, max_g = 0, max_ga = 0, max_gu = 0, max_g4 = 0, max_G = 1, thr = 0;
-  bool own_width = false;
+  int n = 0, max_g = 0, max_ga = 0, max_gu = 0, max_g4 = 0, max_G = 1;
   int64_t Mtot4 = 0;          // bytes of one state vector, summed over the shard (profiling records)
-  bool a_ready = false;       // a of the next iteration comes (partly) from the folded sweep 3
+  int a_ready = 0;            // a of the next iteration comes (partly) from the folded sweep 3
   int a_from_next = 0;
 };
-static void launch_update_batch(const psignn_broyden* s0, BatchShape& sh, const BatchDesc* d_descs, int k, double eps, hipStream_t st) {
-  const int thr = sh.thr, par = k & 1;
-  const int kd = k >= thr ? 0 : k;
-  if (s0->uvu) {
-    const dim3 gu((unsigned)sh.max_gu, 1, (unsigned)sh.n);
-    // (all meshes of the shard carry the same number of stored pairs: one a_from / keep window for the launch)
-    const int a_from = sh.a_ready ? sh.a_from_next : kd;
-    if (std::min(a_from, kd) > 0) {
-      PROF_BYTES((std::min(a_from, kd) + 1) * sh.Mtot4);
-      VLAUNCH("k_sweep_u1", st, s0->vec_u, kb_sweep_u1, (gu, TB, 0, st), d_descs, std::min(a_from, kd));
-    }
-    LAUNCH("k_reduce_check", st, (kb_reduce_a_check<<<dim3((unsigned)std::max(kd, 1), RA + 1, (unsigned)sh.n), RB, 0, st>>>(d_descs, kd, eps, a_from)));
-    sh.a_ready = false;
-    const bool last = k + 1 >= thr;   // the stop test of iteration thr has fired: the sweeps below return at once
-    PROF_BYTES(last ? 0 : (k + 4) * sh.Mtot4);
-    VLAUNCH("k_sweep_v", st, s0->vec_u, kb_sweep_v, (gu, TB, 0, st), d_descs, k, par);
-    LAUNCH("k_reduce_cb", st, (kb_reduce_cb<<<dim3((unsigned)std::max(k, 1), 3, (unsigned)sh.n), RB, 0, st>>>(d_descs, k)));
-    const int keep0 = k <= s0->u2d_kmax ? 0 : k - s0->u2d_keep;
-    if (s0->u2d_kmax > 0 && (k <= s0->u2d_kmax || s0->u2d_keep > 0) && k + 1 < thr) {
-      PROF_BYTES((k + 5) * sh.Mtot4);
-      const int nk = k - keep0;
-      const dim3 g4((unsigned)sh.max_g4, 1, (unsigned)sh.n);
-      if (s0->u2d_reg) {
-        if (nk <= 8) LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<8><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
-        else if (nk <= 16) LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<16><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
-        else LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<24><<<g4, TB, 0, st>>>(d_descs, k, keep0, par)));
-      } else {
-        const size_t lds = (size_t)std::max(nk, 1) * TB * 16;
-        LAUNCH("k_sweep_u2d", st, (kb_sweep_u2d<<<g4, TB, lds, st>>>(d_descs, k, keep0, par)));
-      }
-      sh.a_ready = true;
-      sh.a_from_next = keep0;
-    } else {
-      PROF_BYTES(last ? 0 : (k + 5) * sh.Mtot4);
-      VLAUNCH("k_sweep_u2", st, s0->vec_u, kb_sweep_u2, (gu, TB, 0, st), d_descs, k, par);
-    }
-  } else {
-  if (kd > 0) {
-    PROF_BYTES((2 * kd + 3) * sh.Mtot4);
-    VLAUNCH("k_dots", st, s0->vec, kb_dots, (dim3((unsigned)sh.max_g, (unsigned)sh.max_G, (unsigned)sh.n), TB, 0, st), d_descs, kd, par);
+static BatchShape shard_shape(int n, psignn_broyden_t* const* sv) {
+  BatchShape sh;
+  sh.n = n;
+  for (int m = 0; m < n; ++m) {
+    const psignn_broyden* s = sv[m];
+    sh.max_g = std::max(sh.max_g, s->nblk);
+    sh.max_ga = std::max(sh.max_ga, s->nblk_ax);
+    sh.max_gu = std::max(sh.max_gu, s->nblk_u);
+    sh.max_g4 = std::max(sh.max_g4, s->nblk4);
+    sh.max_G = std::max(sh.max_G, s->jgroups);
+    sh.Mtot4 += s->M * 4;
   }
-  LAUNCH("k_reduce_check", st, (kb_reduce_check<<<dim3((unsigned)std::max(kd, 1), 4, (unsigned)sh.n), RB, 0, st>>>(d_descs, kd, eps)));
-  if (sh.own_width) {
-    PROF_BYTES(k + 1 >= thr ? 0 : (2 * k + 6) * sh.Mtot4);
-    VLAUNCH("k_axpy", st, s0->vec_ax, kb_axpy, (dim3((unsigned)sh.max_ga, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, 1, par);
-    PROF_BYTES(k + 1 >= thr ? 0 : 4 * sh.Mtot4);
-    VLAUNCH("k_final", st, s0->vec_ax, kb_final, (dim3((unsigned)sh.max_ga, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, 1);
-  } else {
-    PROF_BYTES(k + 1 >= thr ? 0 : (2 * k + 6) * sh.Mtot4);
-    VLAUNCH("k_axpy", st, s0->vec, kb_axpy, (dim3((unsigned)sh.max_g, (unsigned)sh.max_G, (unsigned)sh.n), TB, 0, st), d_descs, k, 0, par);
-    if (sh.max_G > 1 && k >= 4 * 2)   // some mesh may split from k = 4 * jgroups on (jgroups >= 2)
-      VLAUNCH("k_axpy_combine", st, s0->vec, kb_axpy_combine, (dim3((unsigned)sh.max_g, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, par);
-    PROF_BYTES(k + 1 >= thr ? 0 : 4 * sh.Mtot4);
-    VLAUNCH("k_final", st, s0->vec, kb_final, (dim3((unsigned)sh.max_g, 1, (unsigned)sh.n), TB, 0, st), d_descs, k, 0);
+  return sh;
+}
+
+// The meshes of one shard in lockstep: one launch per pass, grid z = mesh, the largest extent of the shard in x (and max_G block rows
+// in the split passes); a block past its mesh's extent returns.  fp32 pairs only (psignn_broyden_batchable): there is no bf16 code here.
+// Issued by the forward batched solve and by the batched adjoint solve.
+struct ShardTarget {
+  const psignn_broyden* s0;   // the shard's size class (same_size_class)
+  BatchShape& sh;
+  const BatchDesc* dd;
+  hipStream_t st;
+  const psignn_broyden& size_class() const { return *s0; }
+  int64_t vec_bytes() const { return sh.Mtot4; }
+  int pair_elem_bytes() const { return 4; }
+  int& a_ready() { return sh.a_ready; }
+  int& a_from() { return sh.a_from_next; }
+  // (stated bytes: the split of the largest jgroups; each block takes its own mesh's split from the descriptor)
+  int groups(int k) const { return (sh.max_G > 1 && k >= 4 * sh.max_G) ? sh.max_G : 1; }
+  bool combine_due(int k, int) const { return sh.max_G > 1 && k >= 4 * 2; }   // some mesh may split from k = 4 * jgroups on (jgroups >= 2)
+  dim3 grid(int x, int y = 1) const { return dim3((unsigned)x, (unsigned)y, (unsigned)sh.n); }
+
+  void sweep_u1(int n1) { VLAUNCH("k_sweep_u1", st, s0->vec_u, kb_sweep_u1, (grid(sh.max_gu), TB, 0, st), dd, n1); }
+  void reduce_a_check(int kd, double eps, int a_from) {
+    LAUNCH("k_reduce_check", st, (kb_reduce_a_check<<<grid(std::max(kd, 1), RA + 1), RB, 0, st>>>(dd, kd, eps, a_from)));
   }
+  void sweep_v(int k) { VLAUNCH("k_sweep_v", st, s0->vec_u, kb_sweep_v, (grid(sh.max_gu), TB, 0, st), dd, k, k & 1); }
+  void reduce_cb(int k) { LAUNCH("k_reduce_cb", st, (kb_reduce_cb<<<grid(std::max(k, 1), 3), RB, 0, st>>>(dd, k))); }
+  template <int KB>
+  void sweep_u2r(int k, int keep0) { LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<KB><<<grid(sh.max_g4), TB, 0, st>>>(dd, k, keep0, k & 1))); }
+  void sweep_u2d(int k, int keep0, size_t lds) { LAUNCH("k_sweep_u2d", st, (kb_sweep_u2d<<<grid(sh.max_g4), TB, lds, st>>>(dd, k, keep0, k & 1))); }
+  void sweep_u2(int k) { VLAUNCH("k_sweep_u2", st, s0->vec_u, kb_sweep_u2, (grid(sh.max_gu), TB, 0, st), dd, k, k & 1); }
+  void dots(int kd, int) { VLAUNCH("k_dots", st, s0->vec, kb_dots, (grid(sh.max_g, sh.max_G), TB, 0, st), dd, kd, kd & 1); }
+  void reduce_check(int kd, double eps) { LAUNCH("k_reduce_check", st, (kb_reduce_check<<<grid(std::max(kd, 1), 4), RB, 0, st>>>(dd, kd, eps))); }
+  void axpy(int k, int, bool own_width) {
+    if (own_width) VLAUNCH("k_axpy", st, s0->vec_ax, kb_axpy, (grid(sh.max_ga), TB, 0, st), dd, k, 1, k & 1);
+    else VLAUNCH("k_axpy", st, s0->vec, kb_axpy, (grid(sh.max_g, sh.max_G), TB, 0, st), dd, k, 0, k & 1);
   }
+  void combine(int k, int) { VLAUNCH("k_axpy_combine", st, s0->vec, kb_axpy_combine, (grid(sh.max_g), TB, 0, st), dd, k, k & 1); }
+  void final_pass(int k, bool own_width) {
+    VLAUNCH("k_final", st, own_width ? s0->vec_ax : s0->vec, kb_final, (grid(own_width ? sh.max_ga : sh.max_g), TB, 0, st), dd, k, own_width ? 1 : 0);
+  }
+};
+
+// ---- what the two batched solves share around the chain
+// the fields of a mesh's descriptor that both solves set alike; the caller adds tile_base, nrmp, grad and n_nrm
+static void fill_desc(const psignn_broyden* s, BatchDesc& d) {
+  d.M = s->M; d.ld = s->ld; d.nblk = s->nblk; d.npart = s->npart; d.nblk_ax = s->nblk_ax; d.jgroups = s->jgroups;
+  d.thr = s->thr; d.seq_len = s->seq_len; d.keep_trace = s->keep_trace; d.n_tiles = (int)s->plan->n_tiles;
+  d.st = reinterpret_cast<int32_t*>(s->st);
+  d.U = s->U; d.V = s->V; d.xbuf = s->xbuf; d.g0 = s->gbuf[0]; d.g1 = s->gbuf[1]; d.upd = s->upd; d.part = s->part; d.coef = s->coef;
+  d.nrm_part = s->nrm_part; d.jpart = s->jpart; d.rel_trace = s->rel_trace; d.abs_trace = s->abs_trace;
+  d.ctx = s->plan->d_ctx; d.h0p = s->h0p; d.prbp = s->prbp;
+  d.part2 = s->part2; d.nblk_u = s->nblk_u; d.npart_u = s->npart_u;
+  d.parta = s->parta; d.nblk4 = s->nblk4; d.pad_ = 0; d.pstride = s->pstride;
+  d.fx = s->fx; d.xcopy = s->h0p; d.pad2_ = 0;
+}
+// the host's poll: *h_done = 1 when every mesh's stop test has fired
+static int shard_all_done(const BatchDesc* d_descs, int n, int32_t* d_done, int32_t* h_done, hipStream_t st) {
+  kb_all_done<<<1, 64, 0, st>>>(d_descs, n, offsetof(Status, done) / 4, d_done);
+  HIP_TRY(hipMemcpyAsync(h_done, d_done, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return PSIGNN_OK;
+}
+static int shard_finish(int n, psignn_broyden_t** sv, float* const* d_results, psignn_solve_info_t* infos, double* const* h_rel,
+                        double* const* h_abs, hipStream_t st) {
+  int rc = PSIGNN_OK;
+  for (int m = 0; m < n && rc == PSIGNN_OK; ++m)
+    rc = finish(sv[m], d_results ? d_results[m] : nullptr, infos ? &infos[m] : nullptr, h_rel ? h_rel[m] : nullptr,
+                h_abs ? h_abs[m] : nullptr, st);
+  return rc;
 }
 
 int psignn_f_tile_fused_batch(const BatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed,
                               int off_done, int off_cur, int off_nxt, int par, hipStream_t st);
 
+// one size class: the vector width / split layout / threshold / fold limits that broyden_alloc derives from the shard size
+static bool same_size_class(const psignn_broyden* a, const psignn_broyden* b) {
+  return a->vec == b->vec && a->vec_ax == b->vec_ax && a->uvu == b->uvu && a->vec_u == b->vec_u && a->thr == b->thr &&
+         a->u2d_kmax == b->u2d_kmax && a->u2d_keep == b->u2d_keep && a->u2d_reg == b->u2d_reg;
+}
+
 // 1 when psignn_broyden_solve_batch takes these solvers together: tiled plans of ONE boundary-condition family and one size
-// class (the vector width / split layout / threshold / fold limits that broyden_alloc derives from the shard size) -- a host-side
-// question, asked before the solve so that a shard the batched solver cannot take is not an error path.
+// class, fp32 pairs -- a host-side question, asked before the solve so that a shard the batched solver cannot take is not an error path.
 extern "C" int psignn_broyden_batchable(int n, psignn_broyden_t* const* sv) {
   if (n <= 0 || !sv || !sv[0] || !sv[0]->plan) return 0;
   const psignn_broyden* s0 = sv[0];
@@ -1759,9 +1835,7 @@ extern "C" int psignn_broyden_batchable(int n, psignn_broyden_t* const* sv) {
     const psignn_broyden* s = sv[m];
     if (!s || !s->plan || !s->plan->tiled || s->plan->mixed != s0->plan->mixed) return 0;
     if (s->hist) return 0;   // the batched kernels sweep fp32 pairs only
-    if (!(s->vec == s0->vec && s->vec_ax == s0->vec_ax && s->uvu == s0->uvu && s->vec_u == s0->vec_u && s->thr == s0->thr &&
-          s->u2d_kmax == s0->u2d_kmax && s->u2d_keep == s0->u2d_keep && s->u2d_reg == s0->u2d_reg))
-      return 0;
+    if (!same_size_class(s, s0)) return 0;
   }
   return 1;
 }
@@ -1772,44 +1846,26 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
                                           double* const* h_abs, void* stream) {
   ARG_CHECK(n > 0 && sv && W && h0 && prb, "bad arguments");
   ARG_CHECK(nl == 1, "the batched solver runs single-layer blocks");
+  ARG_CHECK(psignn_broyden_batchable(n, sv),
+            "batched solve: tiled plans of one boundary-condition family and one size class, fp32 pair history (psignn_broyden_batchable)");
+  for (int m = 0; m < n; ++m) {
+    ARG_CHECK(h0[m] && prb[m], "NULL argument");
+    ARG_CHECK(!sv[m]->plan->mixed || (nrm && nrm[m]), "mixed plans need unit normals");
+  }
   hipStream_t st = (hipStream_t)stream;
   if (poll_every <= 0) poll_every = 8;
-  // one vector width / split layout / threshold for the whole shard (meshes of one shard are of one size class)
   const psignn_broyden* s0 = sv[0];
-  BatchShape sh;
-  sh.n = n;
-  sh.thr = s0->thr;
+  BatchShape sh = shard_shape(n, sv);
   int max_rows = 0, n_slots = 0;
-  for (int m = 0; m < n; ++m) {
-    const psignn_broyden* s = sv[m];
-    ARG_CHECK(s && s->plan && s->plan->tiled, "batched solve: tiled plans only");
-    ARG_CHECK(!s->hist, "batched solve: fp32 pair history only (psignn_broyden_batchable)");
-    ARG_CHECK(s->plan->mixed == s0->plan->mixed, "batched solve: one boundary-condition family per shard");
-    ARG_CHECK(s->vec == s0->vec && s->vec_ax == s0->vec_ax && s->uvu == s0->uvu && s->vec_u == s0->vec_u && s->thr == s0->thr &&
-                  s->u2d_kmax == s0->u2d_kmax && s->u2d_keep == s0->u2d_keep && s->u2d_reg == s0->u2d_reg,
-              "batched solve: meshes of different size classes (vector width / threshold differ)");
-    ARG_CHECK(h0[m] && prb[m], "NULL argument");
-    ARG_CHECK(!s->plan->mixed || (nrm && nrm[m]), "mixed plans need unit normals");
-    sh.max_g = std::max(sh.max_g, s->nblk);
-    sh.max_ga = std::max(sh.max_ga, s->nblk_ax);
-    sh.max_gu = std::max(sh.max_gu, s->nblk_u);
-    sh.max_g4 = std::max(sh.max_g4, s->nblk4);
-    sh.max_G = std::max(sh.max_G, s->jgroups);
-    max_rows = std::max(max_rows, s->plan->max_rows);
-    n_slots += (int)s->plan->n_tiles;
-  }
-  sh.own_width = s0->vec_ax != s0->vec;
   int64_t bf_tot = 0;   // bytes of one fused f evaluation, summed over the shard (profiling records)
-  for (int m = 0; m < n; ++m) {
-    sh.Mtot4 += sv[m]->M * 4;
-    bf_tot += (sv[m]->plan->mixed ? 8 * D + 22 : 8 * D + 9) * sv[m]->plan->N + 20 * sv[m]->plan->Ep + 8 * sv[m]->M;
-  }
   // ---- per mesh: status, plan-order inputs, g0 = f(x0) - x0 (exactly the single-mesh prologue)
   std::vector<BatchDesc> hd(n);
-  int rc, base = 0;
+  int rc;
   for (int m = 0; m < n; ++m) {
     psignn_broyden* s = sv[m];
     const psignn_plan* p = s->plan;
+    max_rows = std::max(max_rows, p->max_rows);
+    bf_tot += (p->mixed ? 8 * D + 22 : 8 * D + 9) * p->N + 20 * p->Ep + 8 * s->M;
     s->plan_order = 1;
     k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
     if ((rc = psignn_plan_permute(p, h0[m], D, s->h0p, 1, st))) return rc;
@@ -1819,59 +1875,31 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
     if ((rc = psignn_f_eval_p(p, W, nl, s->h0p, nullptr, 0, s->h0p, s->prbp, nrmp, s->fx, s->fwork, st))) return rc;
     VPLAIN(s->vec, k_begin, ((unsigned)s->nblk, TB, 0, st), s->M, s->h0p, s->fx, s->xbuf, s->gbuf[0], s->upd);
     BatchDesc& d = hd[m];
-    d.M = s->M; d.ld = s->ld; d.nblk = s->nblk; d.npart = s->npart; d.nblk_ax = s->nblk_ax; d.jgroups = s->jgroups;
-    d.thr = s->thr; d.seq_len = s->seq_len; d.keep_trace = s->keep_trace; d.n_tiles = (int)p->n_tiles; d.tile_base = base;
-    d.st = reinterpret_cast<int32_t*>(s->st);
-    d.U = s->U; d.V = s->V; d.xbuf = s->xbuf; d.g0 = s->gbuf[0]; d.g1 = s->gbuf[1]; d.upd = s->upd; d.part = s->part; d.coef = s->coef;
-    d.nrm_part = s->nrm_part; d.jpart = s->jpart; d.rel_trace = s->rel_trace; d.abs_trace = s->abs_trace;
-    d.ctx = p->d_ctx; d.h0p = s->h0p; d.prbp = s->prbp;
-    d.part2 = s->part2; d.nblk_u = s->nblk_u; d.npart_u = s->npart_u;
-    d.parta = s->parta; d.nblk4 = s->nblk4; d.pad_ = 0; d.nrmp = nrmp; d.pstride = s->pstride;
-    d.fx = s->fx; d.xcopy = s->h0p; d.grad = nullptr; d.n_nrm = (int)p->n_tiles; d.pad2_ = 0;
-    base += (int)p->n_tiles;
+    fill_desc(s, d);
+    d.tile_base = n_slots; d.nrmp = nrmp; d.grad = nullptr; d.n_nrm = (int)p->n_tiles;   // the fused f kernel: one norm pair per tile
+    n_slots += (int)p->n_tiles;
   }
-  BatchDesc* d_descs = nullptr;
-  int32_t *d_done = nullptr, *h_done = nullptr;
-  auto cleanup = [&]() {
-    if (d_descs) (void)hipFree(d_descs);
-    if (d_done) (void)hipFree(d_done);
-    if (h_done) (void)hipHostFree(h_done);
-  };
-#define BT(expr)                                                                          \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      cleanup();                                                                          \
-      return PSIGNN_EHIP;                                                                 \
-    }                                                                                     \
-  } while (0)
-  BT(hipMalloc((void**)&d_descs, sizeof(BatchDesc) * n));
-  BT(hipMalloc((void**)&d_done, 4));
-  BT(hipHostMalloc((void**)&h_done, 4));
-  BT(hipMemcpyAsync(d_descs, hd.data(), sizeof(BatchDesc) * n, hipMemcpyHostToDevice, st));
-  const int off_done = offsetof(Status, done) / 4;
+  DeviceArray<BatchDesc> d_descs;
+  DeviceArray<int32_t> d_done;
+  PinnedArray<int32_t> h_done;
+  HIP_TRY(d_descs.alloc(n));
+  HIP_TRY(d_done.alloc(1));
+  HIP_TRY(h_done.alloc(1));
+  if ((rc = upload_wait(d_descs.get(), hd.data(), n, st))) return rc;
+  ShardTarget t{s0, sh, d_descs.get(), st};
   const int thr = s0->thr;
   for (int it = 0; it < thr; ++it) {
     PROF_BYTES(bf_tot);
-    const int par = it & 1;
-    rc = psignn_f_tile_fused_batch(d_descs, n, n_slots, max_rows, W, s0->plan->mixed, off_done, sel_off_cur(), sel_off_nxt(), par, st);
-    if (rc) { cleanup(); return rc; }
-    launch_update_batch(s0, sh, d_descs, it, eps, st);
+    rc = psignn_f_tile_fused_batch(d_descs.get(), n, n_slots, max_rows, W, s0->plan->mixed, offsetof(Status, done) / 4, sel_off_cur(),
+                                   sel_off_nxt(), it & 1, st);
+    if (rc) return rc;
+    update_chain(t, it, eps);
     if ((it + 1) % poll_every == 0 || it + 1 == thr) {
-      kb_all_done<<<1, 64, 0, st>>>(d_descs, n, off_done, d_done);
-      BT(hipMemcpyAsync(h_done, d_done, 4, hipMemcpyDeviceToHost, st));
-      BT(hipStreamSynchronize(st));
-      if (*h_done) break;
+      if ((rc = shard_all_done(d_descs.get(), n, d_done.get(), h_done.get(), st))) return rc;
+      if (*h_done.get()) break;
     }
   }
-  rc = PSIGNN_OK;
-  for (int m = 0; m < n && rc == PSIGNN_OK; ++m)
-    rc = finish(sv[m], d_results ? d_results[m] : nullptr, infos ? &infos[m] : nullptr, h_rel ? h_rel[m] : nullptr,
-                h_abs ? h_abs[m] : nullptr, st);
-  cleanup();
-#undef BT
-  return rc;
+  return shard_finish(n, sv, d_results, infos, h_rel, h_abs, st);
 }
 
 
@@ -2073,10 +2101,7 @@ extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** 
   hipStream_t st = (hipStream_t)stream;
   if (poll_every <= 0) poll_every = 8;
   const psignn_broyden* s0 = sv[0];
-  BatchShape sh;
-  sh.n = n;
-  sh.thr = s0->thr;
-  sh.own_width = s0->vec_ax != s0->vec;
+  BatchShape sh = shard_shape(n, sv);
   int max_rows = 0, n_slots = 0;
   int64_t bv_tot = 0;   // bytes of one transposed product, summed over the shard (profiling records)
   // ---- per mesh: the lazy work of the transposed product, status, permuted right-hand side, y0 = 0 (the single-mesh prologue)
@@ -2086,12 +2111,6 @@ extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** 
   for (int m = 0; m < n; ++m) {
     psignn_broyden* s = sv[m];
     const psignn_plan* p = s->plan;
-    sh.max_g = std::max(sh.max_g, s->nblk);
-    sh.max_ga = std::max(sh.max_ga, s->nblk_ax);
-    sh.max_gu = std::max(sh.max_gu, s->nblk_u);
-    sh.max_g4 = std::max(sh.max_g4, s->nblk4);
-    sh.max_G = std::max(sh.max_G, s->jgroups);
-    sh.Mtot4 += s->M * 4;
     max_rows = std::max(max_rows, p->max_rows);
     LinBatchDesc& l = hl[m];
     if ((rc = psignn_lin_batch_fill(lins[m], &l, st))) return rc;
@@ -2103,74 +2122,42 @@ extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** 
     HIP_TRY(hipMemsetAsync(s->h0p, 0, (size_t)s->M * 4, st));
     VPLAIN(s->vec, k_begin, ((unsigned)s->nblk, TB, 0, st), s->M, s->h0p, gr_p, s->xbuf, s->gbuf[0], s->upd);
     BatchDesc& d = hd[m];
-    d.M = s->M; d.ld = s->ld; d.nblk = s->nblk; d.npart = s->npart; d.nblk_ax = s->nblk_ax; d.jgroups = s->jgroups;
-    d.thr = s->thr; d.seq_len = s->seq_len; d.keep_trace = s->keep_trace; d.n_tiles = (int)p->n_tiles; d.tile_base = 0;
-    d.st = reinterpret_cast<int32_t*>(s->st);
-    d.U = s->U; d.V = s->V; d.xbuf = s->xbuf; d.g0 = s->gbuf[0]; d.g1 = s->gbuf[1]; d.upd = s->upd; d.part = s->part; d.coef = s->coef;
-    d.nrm_part = s->nrm_part; d.jpart = s->jpart; d.rel_trace = s->rel_trace; d.abs_trace = s->abs_trace;
-    d.ctx = p->d_ctx; d.h0p = s->h0p; d.prbp = s->prbp;
-    d.part2 = s->part2; d.nblk_u = s->nblk_u; d.npart_u = s->npart_u;
-    d.parta = s->parta; d.nblk4 = s->nblk4; d.pad_ = 0; d.nrmp = nullptr; d.pstride = s->pstride;
-    d.fx = s->fx; d.xcopy = s->h0p; d.grad = gr_p; d.n_nrm = s->nblk; d.pad2_ = 0;   // the unfused residual: one norm pair per block
+    fill_desc(s, d);
+    d.tile_base = 0; d.nrmp = nullptr; d.grad = gr_p; d.n_nrm = s->nblk;   // the unfused residual: one norm pair per block
     l.w = s->h0p;
     l.out = s->fx;
     l.st = d.st;
     l.slot_base = n_slots;
     n_slots += l.n_slots;
   }
-  BatchDesc* d_descs = nullptr;
-  LinBatchDesc* d_lin = nullptr;
-  int32_t *d_done = nullptr, *h_done = nullptr;
-  auto cleanup = [&]() {
-    if (d_descs) (void)hipFree(d_descs);
-    if (d_lin) (void)hipFree(d_lin);
-    if (d_done) (void)hipFree(d_done);
-    if (h_done) (void)hipHostFree(h_done);
-  };
-#define BT(expr)                                                                          \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      cleanup();                                                                          \
-      return PSIGNN_EHIP;                                                                 \
-    }                                                                                     \
-  } while (0)
-  BT(hipMalloc((void**)&d_descs, sizeof(BatchDesc) * n));
-  BT(hipMalloc((void**)&d_lin, sizeof(LinBatchDesc) * n));
-  BT(hipMalloc((void**)&d_done, 4));
-  BT(hipHostMalloc((void**)&h_done, 4));
-  BT(hipMemcpyAsync(d_descs, hd.data(), sizeof(BatchDesc) * n, hipMemcpyHostToDevice, st));
-  BT(hipMemcpyAsync(d_lin, hl.data(), sizeof(LinBatchDesc) * n, hipMemcpyHostToDevice, st));
-  // (the descriptors are read from pageable host vectors: they must have left the host before the vectors can go)
-  BT(hipStreamSynchronize(st));
-  const int off_done = offsetof(Status, done) / 4;
+  DeviceArray<BatchDesc> d_descs;
+  DeviceArray<LinBatchDesc> d_lin;
+  DeviceArray<int32_t> d_done;
+  PinnedArray<int32_t> h_done;
+  HIP_TRY(d_descs.alloc(n));
+  HIP_TRY(d_lin.alloc(n));
+  HIP_TRY(d_done.alloc(1));
+  HIP_TRY(h_done.alloc(1));
+  if ((rc = upload_wait(d_descs.get(), hd.data(), n, st))) return rc;
+  if ((rc = upload_wait(d_lin.get(), hl.data(), n, st))) return rc;
+  ShardTarget t{s0, sh, d_descs.get(), st};
   const int thr = s0->thr;
-  const dim3 gv((unsigned)sh.max_g, 1, (unsigned)n);
+  const dim3 gv = t.grid(sh.max_g);
   for (int it = 0; it < thr; ++it) {
-    const int par = it & 1;
     PROF_BYTES(3 * sh.Mtot4);
-    VLAUNCH("k_xnext", st, s0->vec, kb_xnext, (gv, TB, 0, st), d_descs);
+    VLAUNCH("k_xnext", st, s0->vec, kb_xnext, (gv, TB, 0, st), d_descs.get());
     PROF_BYTES(bv_tot);
-    rc = psignn_lin_vjp_batch(d_lin, n, n_slots, max_rows, W, s0->plan->mixed, off_done, st);
-    if (rc) { cleanup(); return rc; }
+    rc = psignn_lin_vjp_batch(d_lin.get(), n, n_slots, max_rows, W, s0->plan->mixed, offsetof(Status, done) / 4, st);
+    if (rc) return rc;
     PROF_BYTES(4 * sh.Mtot4);
-    VLAUNCH("k_addv_resid", st, s0->vec, kb_addv_resid, (gv, TB, 0, st), d_descs, par);
-    launch_update_batch(s0, sh, d_descs, it, eps, st);
+    VLAUNCH("k_addv_resid", st, s0->vec, kb_addv_resid, (gv, TB, 0, st), d_descs.get(), it & 1);
+    update_chain(t, it, eps);
     if ((it + 1) % poll_every == 0 || it + 1 == thr) {
-      kb_all_done<<<1, 64, 0, st>>>(d_descs, n, off_done, d_done);
-      BT(hipMemcpyAsync(h_done, d_done, 4, hipMemcpyDeviceToHost, st));
-      BT(hipStreamSynchronize(st));
-      if (*h_done) break;
+      if ((rc = shard_all_done(d_descs.get(), n, d_done.get(), h_done.get(), st))) return rc;
+      if (*h_done.get()) break;
     }
   }
-  rc = PSIGNN_OK;
-  for (int m = 0; m < n && rc == PSIGNN_OK; ++m)
-    rc = finish(sv[m], d_results ? d_results[m] : nullptr, infos ? &infos[m] : nullptr, h_rel ? h_rel[m] : nullptr,
-                h_abs ? h_abs[m] : nullptr, st);
-  cleanup();
-#undef BT
-  return rc;
+  return shard_finish(n, sv, d_results, infos, h_rel, h_abs, st);
 }
 #endif  // PSIGNN_D == 10
 

@@ -1154,7 +1154,7 @@ class DeviceBroyden:
         self.stop_mode = stop_mode
         self._check(self.lib.psignn_broyden_set_stop_mode(self.handle, int(stop_mode == "abs")), "psignn_broyden_set_stop_mode")
 
-    def _collect(self, info, rel, abs_, shape, dev):
+    def _result(self, info, rel, abs_, result):
         n_it = info.n_iter
         low = float(info.lowest_abs if getattr(self, "stop_mode", "rel") == "abs" else info.lowest)
         out = {"nstep": int(info.nstep), "n_iter": int(n_it), "lowest": low,
@@ -1162,7 +1162,7 @@ class DeviceBroyden:
         # reference pads both traces to threshold+1 entries with the lowest values (solver.py:195-197)
         rel_l = list(rel[:n_it]) + [float(info.lowest)] * (self.threshold + 1 - n_it)
         abs_l = list(abs_[:n_it]) + [float(info.lowest_abs)] * (self.threshold + 1 - n_it)
-        out["rel_trace"], out["abs_trace"] = rel_l, abs_l
+        out["rel_trace"], out["abs_trace"], out["result"] = rel_l, abs_l, result
         return out
 
     def solve(self, fmap: FixedPointMap, eps, poll_every=8):
@@ -1176,9 +1176,7 @@ class DeviceBroyden:
                 self.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(fmap.h0), nat.ptr(fmap.prb),
                 nat.ptr(fmap.nrm), float(eps), int(poll_every), nat.ptr(result), C.byref(info), rel, abs_,
                 nat.stream_ptr(self.device)), "psignn_broyden_solve")
-        out = self._collect(info, rel, abs_, result.shape, result.device)
-        out["result"] = result
-        return out
+        return self._result(info, rel, abs_, result)
 
     def solve_adjoint(self, fmap: FixedPointMap, h_star, grad, eps, poll_every=8, lin=None):
         """y = J_f(h*)^T y + grad, y_0 = 0, entirely on the device (VJP kernel inside the Broyden loop).  ``lin``: a Linearization
@@ -1196,16 +1194,12 @@ class DeviceBroyden:
                     self.handle, lin.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(gr), float(eps),
                     int(poll_every), nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device)),
                     "psignn_broyden_solve_adjoint_lin")
-                out = self._collect(info, rel, abs_, result.shape, result.device)
-                out["result"] = result
-                return out
+                return self._result(info, rel, abs_, result)
             self._check(self.lib.psignn_broyden_solve_adjoint(
                 self.handle, nat.ptr(fmap.weights.flat), fmap.weights.n_layers, nat.ptr(hs), nat.ptr(fmap.prb),
                 nat.ptr(fmap.nrm), nat.ptr(gr), float(eps), int(poll_every), nat.ptr(result), C.byref(info), rel, abs_,
                 nat.stream_ptr(self.device)), "psignn_broyden_solve_adjoint")
-        out = self._collect(info, rel, abs_, result.shape, result.device)
-        out["result"] = result
-        return out
+        return self._result(info, rel, abs_, result)
 
     def iterate(self, i, like):
         dst = torch.empty_like(like)
@@ -1303,9 +1297,39 @@ class DeviceBroyden:
             abs_ = (C.c_double * self.threshold)()
             self._check(lib.psignn_broyden_ext_finish(self.handle, nat.ptr(result), C.byref(info), rel, abs_, sp),
                       "ext_finish")
-        out = self._collect(info, rel, abs_, result.shape, result.device)
-        out["result"] = result
-        return out
+        return self._result(info, rel, abs_, result)
+
+
+class _ShardCall:
+    """ctypes marshalling of one lockstep solve of n meshes (the three ``*_batch`` wrappers below): the check that all meshes share
+    one packed weight buffer (``what`` names the solve in its message), the info array, one ``c_double`` trace row per mesh with
+    the pointer-to-pointer arrays the library fills them through, pointer arrays, and the zip into per-mesh result dicts."""
+
+    def __init__(self, what, weights, info_type, trace_lens):
+        self.n, self.w0 = len(weights), weights[0]
+        if any(w is not self.w0 and w.flat.data_ptr() != self.w0.flat.data_ptr() for w in weights):
+            raise nat.NativeError(f"{what}: all meshes must share one packed weight buffer")
+        self.infos = (info_type * self.n)()
+        self.rel = [(C.c_double * k)() for k in trace_lens]
+        self.abs_ = [(C.c_double * k)() for k in trace_lens]
+
+    def arr(self, ptrs):
+        return (C.c_void_p * self.n)(*ptrs)
+
+    def handles(self, objs):
+        return self.arr([o.handle.value for o in objs])
+
+    def tensors(self, ts):
+        return self.arr([nat.ptr(t) for t in ts])
+
+    def traces(self):
+        """(rel, abs) as ``double* const*``."""
+        dpp = lambda rows: (C.POINTER(C.c_double) * self.n)(*[C.cast(r, C.POINTER(C.c_double)) for r in rows])
+        return dpp(self.rel), dpp(self.abs_)
+
+    def collect(self, result_of, results):
+        """``[result_of[i](info, rel, abs_, result) for mesh i]``."""
+        return [f(self.infos[i], self.rel[i], self.abs_[i], results[i]) for i, f in enumerate(result_of)]
 
 
 def shard_batchable(solvers) -> bool:
@@ -1329,34 +1353,22 @@ def broyden_solve_batch(solvers, fmaps, eps, poll_every=8):
         return []
     if len(fmaps) != n:
         raise nat.NativeError("one FixedPointMap per solver")
-    w0 = fmaps[0].weights
+    call = _ShardCall("batched solve", [f.weights for f in fmaps], nat.SolveInfo, [s.threshold for s in solvers])
+    w0 = call.w0
     for s, f in zip(solvers, fmaps):
-        if f.weights is not w0 and f.weights.flat.data_ptr() != w0.flat.data_ptr():
-            raise nat.NativeError("batched solve: all meshes must share one packed weight buffer")
         if s.plan is not f.plan:
             raise nat.NativeError("batched solve: solver and map were built from different plans")
         if s.lib is not w0.lib or f.lib is not w0.lib:
             raise nat.NativeError("batched solve: solvers and maps of one latent width only")
     dev = solvers[0].device
-    thr = solvers[0].threshold
     results = [torch.empty_like(f.h0) for f in fmaps]
-    arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-    infos = (nat.SolveInfo * n)()
-    rel = [(C.c_double * s.threshold)() for s in solvers]
-    abs_ = [(C.c_double * s.threshold)() for s in solvers]
-    dpp = lambda rows: (C.POINTER(C.c_double) * n)(*[C.cast(r, C.POINTER(C.c_double)) for r in rows])
     with torch.cuda.device(dev):
         nat.check(w0.lib.psignn_broyden_solve_batch(
-            n, arr([s.handle.value for s in solvers]), nat.ptr(w0.flat), w0.n_layers, arr([nat.ptr(f.h0) for f in fmaps]),
-            arr([nat.ptr(f.prb) for f in fmaps]), arr([nat.ptr(f.nrm) for f in fmaps]) if w0.mixed else None,
-            float(eps), int(poll_every), arr([nat.ptr(r) for r in results]), infos,
-            dpp(rel), dpp(abs_), nat.stream_ptr(dev)), "psignn_broyden_solve_batch", w0.lib)
-    outs = []
-    for i, s in enumerate(solvers):
-        o = s._collect(infos[i], rel[i], abs_[i], results[i].shape, dev)
-        o["result"] = results[i]
-        outs.append(o)
-    return outs
+            n, call.handles(solvers), nat.ptr(w0.flat), w0.n_layers, call.tensors([f.h0 for f in fmaps]),
+            call.tensors([f.prb for f in fmaps]), call.tensors([f.nrm for f in fmaps]) if w0.mixed else None,
+            float(eps), int(poll_every), call.tensors(results), call.infos, *call.traces(), nat.stream_ptr(dev)),
+            "psignn_broyden_solve_batch", w0.lib)
+    return call.collect([s._result for s in solvers], results)
 
 
 def adjoint_batchable(solvers, lins) -> bool:
@@ -1386,31 +1398,20 @@ def broyden_solve_adjoint_batch(solvers, lins, grads, eps, poll_every=8):
         return []
     if len(lins) != n or len(grads) != n:
         raise nat.NativeError("one Linearization and one gradient per solver")
-    w0 = lins[0].fmap.weights
+    call = _ShardCall("batched adjoint solve", [l.fmap.weights for l in lins], nat.SolveInfo, [s.threshold for s in solvers])
+    w0 = call.w0
     for s, l in zip(solvers, lins):
-        if l.fmap.weights is not w0 and l.fmap.weights.flat.data_ptr() != w0.flat.data_ptr():
-            raise nat.NativeError("batched adjoint solve: all meshes must share one packed weight buffer")
         if s.plan is not l.fmap.plan:
             raise nat.NativeError("batched adjoint solve: solver and linearisation were made for different plans")
     dev = solvers[0].device
     gr = [_f32c(g) for g in grads]
     results = [torch.empty_like(g) for g in gr]
-    arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-    infos = (nat.SolveInfo * n)()
-    rel = [(C.c_double * s.threshold)() for s in solvers]
-    abs_ = [(C.c_double * s.threshold)() for s in solvers]
-    dpp = lambda rows: (C.POINTER(C.c_double) * n)(*[C.cast(r, C.POINTER(C.c_double)) for r in rows])
     with torch.cuda.device(dev):
         nat.check(nat.lib().psignn_broyden_solve_adjoint_lin_batch(
-            n, arr([s.handle.value for s in solvers]), arr([l.handle.value for l in lins]), nat.ptr(w0.flat), w0.n_layers,
-            arr([nat.ptr(g) for g in gr]), float(eps), int(poll_every), arr([nat.ptr(r) for r in results]), infos,
-            dpp(rel), dpp(abs_), nat.stream_ptr(dev)), "psignn_broyden_solve_adjoint_lin_batch")
-    outs = []
-    for i, s in enumerate(solvers):
-        o = s._collect(infos[i], rel[i], abs_[i], results[i].shape, dev)
-        o["result"] = results[i]
-        outs.append(o)
-    return outs
+            n, call.handles(solvers), call.handles(lins), nat.ptr(w0.flat), w0.n_layers, call.tensors(gr), float(eps),
+            int(poll_every), call.tensors(results), call.infos, *call.traces(), nat.stream_ptr(dev)),
+            "psignn_broyden_solve_adjoint_lin_batch")
+    return call.collect([s._result for s in solvers], results)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1558,7 +1559,7 @@ class DeviceGmres:
                     self.handle, plan.handle, nat.ptr(fmap.weights.flat), nl, nat.ptr(hs), nat.ptr(fmap.prb), nat.ptr(fmap.nrm),
                     nat.ptr(gr), float(eps), int(max_products), int(poll_every), nat.ptr(self._work), nat.ptr(result),
                     C.byref(info), rel, abs_, self._sp()), "psignn_gmres_solve_adjoint")
-        return self._collect(info, rel, abs_, cap, result)
+        return self._result(info, rel, abs_, result)
 
     def _workspace(self, plan, nl):
         """The adjoint solve's workspace for (plan, n_layers), kept between solves (call inside ``torch.cuda.device``)."""
@@ -1570,8 +1571,8 @@ class DeviceGmres:
         return self._work
 
     @staticmethod
-    def _collect(info, rel, abs_, cap, result):
-        n = min(int(info.cycles), cap)
+    def _result(info, rel, abs_, result):
+        n = min(int(info.cycles), len(rel))
         return {"result": result, "nstep": int(info.products), "lowest": float(info.lowest), "lowest_abs": float(info.lowest_abs),
                 "rel_trace": list(rel[:n]), "abs_trace": list(abs_[:n]), "n_cycles": int(info.cycles),
                 "stop": GMRES_STOPS[int(info.stop_reason)], "n_reorth": int(info.n_reorth), "prot_break": False}
@@ -1645,27 +1646,20 @@ def gmres_solve_adjoint_batch(solvers, lins, grads, eps, max_products, poll_ever
         raise nat.NativeError("one Linearization and one gradient per solver")
     if any(l is None or l.handle is None for l in lins):
         raise nat.NativeError("batched GMRES adjoint solve: every replica needs a Linearization")
-    w0 = lins[0].fmap.weights
+    cap = int(max_products) // 2 + 3
+    call = _ShardCall("batched GMRES adjoint solve", [l.fmap.weights for l in lins], nat.GmresAdjointInfo, [cap] * n)
+    w0 = call.w0
     for s, l in zip(solvers, lins):
-        if l.fmap.weights is not w0 and l.fmap.weights.flat.data_ptr() != w0.flat.data_ptr():
-            raise nat.NativeError("batched GMRES adjoint solve: all meshes must share one packed weight buffer")
         if s.M != l.fmap.plan.N * D:
             raise nat.NativeError(f"batched GMRES adjoint solve: DeviceGmres of {s.M} elements was handed a linearisation of "
                                   f"{l.fmap.plan.N * D}")
     dev = solvers[0].device
     gr = [_f32c(g) for g in grads]
     results = [torch.empty_like(g) for g in gr]
-    arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-    infos = (nat.GmresAdjointInfo * n)()
-    cap = int(max_products) // 2 + 3
-    rel = [(C.c_double * cap)() for _ in solvers]
-    abs_ = [(C.c_double * cap)() for _ in solvers]
-    dpp = lambda rows: (C.POINTER(C.c_double) * n)(*[C.cast(r, C.POINTER(C.c_double)) for r in rows])
     with torch.cuda.device(dev):
         works = [s._workspace(l.fmap.plan, w0.n_layers) for s, l in zip(solvers, lins)]
         nat.check(nat.lib().psignn_gmres_solve_adjoint_lin_batch(
-            n, arr([s.handle.value for s in solvers]), arr([l.handle.value for l in lins]), nat.ptr(w0.flat), w0.n_layers,
-            arr([nat.ptr(g) for g in gr]), float(eps), int(max_products), int(poll_every), arr([nat.ptr(w) for w in works]),
-            arr([nat.ptr(r) for r in results]), infos, dpp(rel), dpp(abs_), nat.stream_ptr(dev)),
-            "psignn_gmres_solve_adjoint_lin_batch")
-    return [DeviceGmres._collect(infos[i], rel[i], abs_[i], cap, results[i]) for i in range(n)]
+            n, call.handles(solvers), call.handles(lins), nat.ptr(w0.flat), w0.n_layers, call.tensors(gr), float(eps),
+            int(max_products), int(poll_every), call.tensors(works), call.tensors(results), call.infos, *call.traces(),
+            nat.stream_ptr(dev)), "psignn_gmres_solve_adjoint_lin_batch")
+    return call.collect([s._result for s in solvers], results)

@@ -296,12 +296,13 @@ def test_fused_device_solve_is_the_host_driven_solve(dev, monkeypatch):
     sv.close()
 
 
-@pytest.mark.parametrize("envname", ["reg", "lds", "window_from_5", "lds_max"])
+@pytest.mark.parametrize("envname", ["reg", "lds", "window_from_5", "lds_max", "no_fold", "two_pass"])
 def test_batched_shard_in_the_window_regime(envname, dev, monkeypatch):
     """``psignn_broyden_solve_batch`` through 48 iterations (window regime from k = 25; from k = 5 with the small limits) on a
     shard of 8 x 10 267-node meshes -- the shapes of BASELINE configs[3] (shard-sized reductions, 4 floats per lane): every mesh
     bit-identical to its own fused solve with the same solver object, that one bit-identical to the host-driven solve, and the
-    host-driven solve satisfies the recurrences."""
+    host-driven solve satisfies the recurrences.  ``no_fold`` / ``two_pass``: the shard's plain sweep 3 and its two-pass form with
+    the axpy pass at its own width."""
     eng = pkg("engine")
     _setenv(monkeypatch, ENVS[envname])
     sd = load_weights("dirichlet")
@@ -327,3 +328,40 @@ def test_batched_shard_in_the_window_regime(envname, dev, monkeypatch):
     _check_run(rec, sv, (4, 5, 6, 24, 25, 26, 46), f"shard/{envname}")
     sv.close()
     _setenv(monkeypatch, {})
+
+
+def test_batched_shard_at_the_narrow_width_splits_the_axpy_pass(dev, monkeypatch):
+    """A ragged shard of three small meshes (together below 768 Ki elements: 4 floats per lane, two-pass form, sweeps split over
+    8 groups of stored pairs), 48 iterations: from k = 4 * 8 = 32 on the shard runs the split axpy pass and its combine launch.
+    Every mesh bit-identical -- result, iterates on both sides of k = 32, ``rel_trace`` -- to its own fused solve on the same
+    solver object."""
+    eng, nat = pkg("engine"), pkg("_native")
+    _setenv(monkeypatch, {})
+    sd = load_weights("dirichlet")
+    fms = [_mesh_map(n, s, dev, sd, phase=0.37 * s) for s, n in enumerate((26, 34, 30))]
+    for f in fms[1:]:
+        f.weights = fms[0].weights                                 # one packed weight buffer for the shard
+    total = sum(f.plan.N for f in fms) * 10
+    assert total < 768 * 1024 and len({f.plan.N for f in fms}) == 3 and all(f.plan.tiled for f in fms)
+    solvers = [eng.DeviceBroyden(plan=f.plan, threshold=K, keep_trace=True, shard_elems=total) for f in fms]
+    assert eng.shard_batchable(solvers)
+    nat.prof_enable(True)
+    nat.prof_collect()
+    outs = eng.broyden_solve_batch(solvers, fms, 0.0)
+    ran = nat.prof_collect()
+    nat.prof_enable(False)
+    assert "k_dots" in ran and "k_sweep_v" not in ran, sorted(ran)     # the two-pass form ...
+    assert ran["k_axpy_combine"][0] == K - 8 and ran["k_axpy"][0] == K, ran   # ... and the combine, launched from k = 8 on (it works from k = 32)
+    its = (1, 31, 32, 33, K)
+    its_b = [[sv.iterate(i, f.h0) for i in its] for sv, f in zip(solvers, fms)]
+    for m, (sv, fm) in enumerate(zip(solvers, fms)):
+        assert outs[m]["n_iter"] == K
+        nat.prof_collect()
+        nat.prof_enable(True)
+        single = sv.solve(fm, 0.0)
+        ran1 = nat.prof_collect()
+        nat.prof_enable(False)
+        assert ran1["k_axpy_combine"][0] == K - 32, ran1              # the mesh's own solve splits from k = 32: jgroups = 8
+        assert single["rel_trace"] == outs[m]["rel_trace"] and torch.equal(single["result"], outs[m]["result"]), m
+        assert all(torch.equal(sv.iterate(i, fm.h0), x) for i, x in zip(its, its_b[m])), m
+        sv.close()
