@@ -512,6 +512,48 @@ int psignn_fpiter_finish(psignn_fpiter_t* s, float* d_result, psignn_solve_info_
                          double* h_abs_trace, int32_t* h_low_idx, void* stream);
 /* Iterate i of the last run (keep_trace): Picard z_i; Anderson the trial point of loop index i (i >= 2). */
 int psignn_fpiter_get_iterate(const psignn_fpiter_t* s, int i, float* d_dst, void* stream);
+/* A handle for one mesh of a shard that psignn_anderson_solve_batch / psignn_picard_solve_batch will solve together: as
+ * psignn_fpiter_create, except that the vector width (4 or 16 floats per lane) follows shard_elems = the sum of N * d over the shard
+ * (>= n_elems) and not n_elems, so that all handles of a shard share one; blocks, partials and the row stride stay the mesh's own.  It
+ * also holds the rows the lockstep solves keep per mesh (the map's value, its plan-order inputs).  The stepwise calls above work on such
+ * a handle and give the bits of the lockstep solve.
+ * replaces: the per-graph state of forward_iteration / anderson (dirichlet/psignn/utilities/solver.py:301-341, :215-293) when the
+ *           graphs of one device's share of a batch (dirichlet/psignn/main.py:106) are solved side by side. */
+int psignn_fpiter_create_for_batch(psignn_fpiter_t** out, int64_t n_elems, int m, int threshold, int keep_trace, int64_t shard_elems);
+/* 1 when the lockstep solves below take these handles and plans together: n >= 1, all plans tiled and of one boundary-condition family,
+ * handles[i] made by psignn_fpiter_create_for_batch for the length of plans[i], one vector width, one m, one threshold and
+ * keep_trace == 0.  0 otherwise, also for NULL arguments -- asked on the host before a shard is handed over, so that "not batchable" is
+ * a decision and not an error code.
+ * replaces: nothing in the reference (its DataParallel call takes any list of graphs, dirichlet/psignn/main.py:106;
+ *           mixed/psignn/main.py:106). */
+int psignn_fpiter_batchable(int n, psignn_fpiter_t* const* handles, const psignn_plan_t* const* plans);
+/* Lockstep Anderson acceleration of the n meshes of one shard with the HIP GNN block as the map: x0 = h_initial, f0 = f(x0),
+ * f1 = f(f0), then the loop k = 2 .. threshold - 1, every pass -- Gram partials, bordered solve, mix, f, norms, stop test, gated copy of
+ * the lowest iterate -- ONE launch over all meshes.  Every mesh keeps its own status block, traces, stop test and lowest iterate; a mesh
+ * that has stopped is skipped by every later launch.  The all-done word is read every poll_every passes (<= 0: 8); results do not depend
+ * on it.  Per mesh the result, info, traces and h_low_idx are those of psignn_anderson_begin / next_x / update / psignn_fpiter_finish
+ * on the same handle around psignn_f_forward_p, bit for bit.  Tensors in the caller's numbering, as psignn_broyden_solve_batch takes
+ * them (d_normals: NULL for dirichlet shards).  A shard psignn_fpiter_batchable refuses, n_layers != 1 and m < 2 are PSIGNN_EINVAL with
+ * nothing launched.
+ * replaces: anderson(f, x0, m, lam, threshold, eps, stop_mode, beta) (dirichlet/psignn/utilities/solver.py:215-293) called once per
+ *           graph by DeepEquilibrium.forward (dirichlet/psignn/model.py:189, test/model_psignn.py:226) for the graphs of one device's
+ *           share of a batch (dirichlet/psignn/main.py:106, test/test_func.py:68-120).
+ * Arrays of n device / host pointers; h_rel_trace[i] / h_abs_trace[i]: threshold + 2 doubles, h_low_idx[i]: threshold + 2 int32 (arrays
+ * may be NULL). */
+int psignn_anderson_solve_batch(int n, psignn_fpiter_t** handles, const psignn_plan_t* const* plans, const float* d_weights,
+                                int n_layers, const float* const* d_h_initial, const float* const* d_prb,
+                                const float* const* d_normals, double lam, double beta, int stop_abs, double eps, int poll_every,
+                                float* const* d_results, psignn_solve_info_t* h_infos, double* const* h_rel_trace,
+                                double* const* h_abs_trace, int32_t* const* h_low_idx, void* stream);
+/* The same for the Picard iteration z <- f(z) from z0 = h_initial: per pass f, norms, the gated move to the next iterate and the stop
+ * test, one launch each over the shard, up to threshold + 1 evaluations; per mesh the bits of psignn_picard_begin / current_x / update /
+ * psignn_fpiter_finish on the same handle.
+ * replaces: forward_iteration(f, z0, eps, threshold) (dirichlet/psignn/utilities/solver.py:301-341) called once per graph
+ *           (--solver forward_iteration) for the graphs of one device's share of a batch (dirichlet/psignn/main.py:106). */
+int psignn_picard_solve_batch(int n, psignn_fpiter_t** handles, const psignn_plan_t* const* plans, const float* d_weights, int n_layers,
+                              const float* const* d_h_initial, const float* const* d_prb, const float* const* d_normals, double eps,
+                              int poll_every, float* const* d_results, psignn_solve_info_t* h_infos, double* const* h_rel_trace,
+                              double* const* h_abs_trace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * GMRES on the device for the Newton-Krylov solver (BASELINE configs[4]: "Newton-Krylov JVP path").

@@ -171,6 +171,15 @@ SIGNATURES = {
     "psignn_fpiter_finish": (_INT, [_P, _P, C.POINTER(SolveInfo), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.POINTER(C.c_int32), _P]),
     "psignn_fpiter_get_iterate": (_INT, [_P, _INT, _P, _P]),
+    "psignn_fpiter_create_for_batch": (_INT, [C.POINTER(_P), _I64, _INT, _INT, _INT, _I64]),
+    "psignn_fpiter_batchable": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P)]),
+    "psignn_anderson_solve_batch": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P), _P, _INT, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                           C.c_double, C.c_double, _INT, C.c_double, _INT, C.POINTER(_P), C.POINTER(SolveInfo),
+                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)),
+                                           C.POINTER(C.POINTER(C.c_int32)), _P]),
+    "psignn_picard_solve_batch": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P), _P, _INT, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                         C.c_double, _INT, C.POINTER(_P), C.POINTER(SolveInfo), C.POINTER(C.POINTER(C.c_double)),
+                                         C.POINTER(C.POINTER(C.c_double)), _P]),
     "psignn_gmres_create": (_INT, [C.POINTER(_P), _I64, _I64, _INT, _P]),
     "psignn_gmres_destroy": (None, [_P]),
     "psignn_residual_norms": (_INT, [_P, _P, _P, _P, _P, C.POINTER(C.c_double), _P]),

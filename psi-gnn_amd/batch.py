@@ -49,7 +49,10 @@ def solve_shard_batched(model, meshes, device, indices=None, group=8):
     (``DeviceBroyden(..., shard_elems=...)``: the sweeps' reduction shapes are sized for the shard) and agrees with the plain
     ``solve_shard`` path to solver tolerance; both families (a shard is all dirichlet or all mixed, as every dataset of the
     reference is).  Meshes the batched solver cannot take together (untiled plans, different size classes, multi-layer blocks,
-    a bf16 ``broyden_history_dtype``) are solved one by one -- decided on the host before anything is allocated or launched; errors of the batched solve raise."""
+    a bf16 ``broyden_history_dtype``) are solved one by one -- decided on the host before anything is allocated or launched; errors of the batched solve raise.
+    With ``solver`` = ``anderson`` / ``forward_iteration`` a group is solved in lockstep only when the model's ``fp_lockstep`` key is
+    set (``DeepEquilibrium.fp_lockstep_applies``: tiled plans of one family, single-layer block, more than one mesh), through
+    ``utilities.solver.anderson_batch`` / ``forward_iteration_batch``; without the key, one by one as before."""
     import importlib
     eng = importlib.import_module(__package__ + ".engine")
     slv = importlib.import_module(__package__ + ".utilities.solver")
@@ -80,6 +83,9 @@ def solve_shard_batched(model, meshes, device, indices=None, group=8):
                 finally:
                     for sv in solvers:
                         sv.close()
+            # fp_lockstep (solver = anderson / forward_iteration): the same host-side decision, then one lockstep solve of the group
+            if solved is None and net.deqdss.fp_lockstep_applies(fmaps):
+                solved = net.deqdss.fp_lockstep_solve(fmaps)
             for k, i in enumerate(ids):
                 if solved is not None:
                     h_final, nstep = solved[k]["result"], solved[k]["nstep"]

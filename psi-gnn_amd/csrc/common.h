@@ -292,3 +292,20 @@ struct GmresBatchDesc {
   const float* grad;           // permuted right-hand side
   double *rel_trace, *abs_trace;
 };
+
+// Batched Picard / Anderson (fpiter.hip psignn_anderson_solve_batch / psignn_picard_solve_batch): one descriptor per mesh of a shard.
+// Every kernel of the iteration is launched ONCE for the shard with blockIdx.z = mesh and runs the single-handle kernel's body on the
+// mesh's descriptor; the map is one plain tile launch over the shard's slot list (fgnn_tile.hip k_f_tile_plain_batch), which reads ring
+// row X[row] or F[row] of the mesh and writes its scratch row fx.  Each mesh has the bits of its own stepwise solve.
+struct FpBatchDesc {
+  int64_t M, ld;
+  int32_t nblk, npart, n_tiles, tile_base;
+  float *X, *F, *low, *part;   // the handle's ring slots, lowest iterate, partials
+  float* fx;                   // the map's value at the current trial point (plan order)
+  struct FpStatus* st;         // the mesh's status block
+  const int32_t* st32;         // ... and its int32 view (done flag of the tile launch)
+  double *rel_trace, *abs_trace;
+  int32_t* low_idx;
+  const struct TileCtx* ctx;
+  const float *h0p, *prbp, *nrmp;   // plan-order inputs of the map (nrmp: NULL for dirichlet plans)
+};

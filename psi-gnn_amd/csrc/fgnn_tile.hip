@@ -605,6 +605,67 @@ int psignn_f_tile_fused_batch(const BatchDesc* d_descs, int n_mesh, int n_slots,
   return PSIGNN_OK;
 }
 
+// Batched plain f (fpiter.hip psignn_anderson_solve_batch / psignn_picard_solve_batch; single layer, LayerNorm applied): ONE launch
+// evaluates f of every mesh of a shard at ring row `in_row` of its X (in_f = 0) or F (in_f = 1) slots and writes the mesh's fx row.
+// The slot list and the descriptor walk are k_f_tile_batch's; the tile body is the plain single-mesh kernel's, so every mesh has the
+// bits of psignn_f_forward_p on its own plan.  A mesh whose stop test has fired is skipped tile by tile.
+template <int P, bool MIXED>
+__global__ __launch_bounds__(TILE_THREADS) void k_f_tile_plain_batch(const FpBatchDesc* __restrict__ descs, int n_mesh, int n_slots,
+                                                                    int chunk, int off_done, int in_f, int in_row,
+                                                                    const float* __restrict__ W, int lofs, int tofs, int tnofs) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int slot = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (slot >= n_slots) return;
+  int m = 0;
+  while (m + 1 < n_mesh && descs[m + 1].tile_base <= slot) ++m;   // wave-uniform scalar walk (a shard has few meshes)
+  const FpBatchDesc& d = descs[m];
+  if (d.st32[off_done]) return;
+  const float* h = (in_f ? d.F : d.X) + (int64_t)in_row * d.ld;
+  f_tile_body<P, MIXED, false, false>(FuseArgs{}, slot - d.tile_base, nullptr, d.ctx, W, lofs, tofs, tnofs, 1, h, nullptr, 0, d.h0p,
+                                      d.prbp, d.nrmp, d.fx, lds);
+}
+
+// Dynamic LDS beyond 64 KiB is asked for once per device (width 16: 768 rows of a dirichlet tile are 98 304 B); the largest request a
+// tiled plan can make, so that one grant serves every shard.
+static bool plain_batch_lds_granted() {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  static int state[64] = {0};   // 0 unknown, 1 granted, -1 refused
+  if (state[dev] == 0) {
+    const int want_d = (TILE_MAX + HALO_CAP) * TileRow<false>::RS * 4, want_m = MIXED_ROW_CAP * TileRow<true>::RS * 4;
+    const bool ok =
+        hipFuncSetAttribute((const void*)k_f_tile_plain_batch<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, want_d) == hipSuccess &&
+        hipFuncSetAttribute((const void*)k_f_tile_plain_batch<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, want_m) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    state[dev] = ok ? 1 : -1;
+  }
+  return state[dev] > 0;
+}
+
+// descs: device array of n_mesh descriptors; max_rows: largest tile + halo row count over the meshes (LDS size).  Mixed shards run the
+// full kernel in tile order, as psignn_f_tile_fused_batch does.  Records as the single-mesh plain launch does ("k_f_tile").
+int psignn_f_tile_plain_batch(const FpBatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed, int off_done,
+                              int in_f, int in_row, hipStream_t st) {
+  const int chunk = (int)cdiv(n_slots, 8);
+  const size_t lds = (size_t)max_rows * (mixed ? TileRow<true>::RS : TileRow<false>::RS) * 4;
+  ARG_CHECK(max_rows > 0 && max_rows <= (mixed ? MIXED_ROW_CAP : TILE_MAX + HALO_CAP), "tile rows beyond the plan's limits");
+  if (lds > 64 * 1024 && !plain_batch_lds_granted()) {
+    psignn_set_error("batched plain f: %zu bytes of dynamic LDS were refused", lds);
+    return PSIGNN_EHIP;
+  }
+  if (mixed) {
+    using L = WLayout<3>;
+    LAUNCH("k_f_tile", st, (k_f_tile_plain_batch<3, true><<<tile_grid(chunk), TILE_THREADS, lds, st>>>(
+        d_descs, n_mesh, n_slots, chunk, off_done, in_f, in_row, W, L::layer(0), L::tp_layer(1, true, 0), L::tp_neu(1))));
+  } else {
+    using L = WLayout<2>;
+    LAUNCH("k_f_tile", st, (k_f_tile_plain_batch<2, false><<<tile_grid(chunk), TILE_THREADS, lds, st>>>(
+        d_descs, n_mesh, n_slots, chunk, off_done, in_f, in_row, W, L::layer(0), L::tp_layer(1, false, 0), 0)));
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
 // gather of node rows between the caller's numbering and the plan order: dst[i] = src[map[i]]
 __global__ void k_permute_rows(int64_t N, int cols, const int32_t* __restrict__ map, const float* __restrict__ src,
                                float* __restrict__ dst) {

@@ -1422,16 +1422,24 @@ class DeviceFixedPointIter:
     (utilities/solver.py:301-341, :215-293) on the device.  The caller evaluates f between the calls; nothing is read back
     per iteration unless asked (``poll``)."""
 
-    def __init__(self, n_elems, device, m=2, threshold=50, keep_trace=False, width=None):
+    def __init__(self, n_elems, device, m=2, threshold=50, keep_trace=False, width=None, shard_elems=None):
         """``width``: the latent width of the map being iterated (default: the default width): the state lives in that
-        width's library, like the map's other handles.  The arithmetic is flat over ``n_elems``."""
+        width's library, like the map's other handles.  The arithmetic is flat over ``n_elems``.
+        ``shard_elems``: the summed length of the shard this handle will share an ``anderson_solve_batch`` /
+        ``picard_solve_batch`` call with (``psignn_fpiter_create_for_batch``: the vector width follows the shard, and the handle
+        holds the rows the lockstep solves keep per mesh); ``None``: a handle sized for itself."""
         h = C.c_void_p()
         self.lib = nat.lib(D if width is None else width)
         self.device, self.M, self.m = device, int(n_elems), int(m)
         self.threshold, self.keep_trace = int(threshold), bool(keep_trace)
+        self.shard_elems = None if shard_elems is None else int(shard_elems)
         with torch.cuda.device(device):
-            nat.check(self.lib.psignn_fpiter_create(C.byref(h), self.M, self.m, self.threshold, int(self.keep_trace)),
-                      "psignn_fpiter_create", self.lib)
+            if self.shard_elems is None:
+                nat.check(self.lib.psignn_fpiter_create(C.byref(h), self.M, self.m, self.threshold, int(self.keep_trace)),
+                          "psignn_fpiter_create", self.lib)
+            else:
+                nat.check(self.lib.psignn_fpiter_create_for_batch(C.byref(h), self.M, self.m, self.threshold, int(self.keep_trace),
+                                                                  self.shard_elems), "psignn_fpiter_create_for_batch", self.lib)
         self.handle = h
         self._fin = weakref.finalize(self, self.lib.psignn_fpiter_destroy, h)
 
@@ -1479,6 +1487,10 @@ class DeviceFixedPointIter:
         rel, abs_, low = (C.c_double * n)(), (C.c_double * n)(), (C.c_int32 * n)()
         nat.check(self.lib.psignn_fpiter_finish(self.handle, nat.ptr(result), C.byref(info), rel, abs_, low, self._sp()),
                   "psignn_fpiter_finish", self.lib)
+        return self._result(info, rel, abs_, low, result)
+
+    @staticmethod
+    def _result(info, rel, abs_, low, result):
         k = int(info.n_iter)
         return {"result": result, "n_iter": k, "nstep": int(info.nstep), "lowest": float(info.lowest),
                 "lowest_abs": float(info.lowest_abs), "stop_reason": int(info.stop_reason),
@@ -1488,6 +1500,91 @@ class DeviceFixedPointIter:
         dst = torch.empty_like(like)
         nat.check(self.lib.psignn_fpiter_get_iterate(self.handle, int(i), nat.ptr(dst), self._sp()), "psignn_fpiter_get_iterate", self.lib)
         return dst
+
+
+def check_fp_lockstep(value, solver, accepted):
+    """The ``fp_lockstep`` config value as a bool: the meshes of a shard (``batch.solve_shard_batched``, the replicas of a
+    ``DataParallel(replicas=R)`` step) run their Anderson / Picard forward solves in lockstep (``anderson_solve_batch`` /
+    ``picard_solve_batch``).  It needs ``solver`` to be one of ``accepted`` (``utilities.solver.anderson`` and
+    ``forward_iteration``, handed in by the model): NativeError naming both keys otherwise.  A host check: nothing is allocated."""
+    if not isinstance(value, bool):
+        raise nat.NativeError(f"fp_lockstep must be a bool, got {value!r}")
+    if value and not any(solver is a for a in accepted):
+        raise nat.NativeError(f"fp_lockstep = True needs solver in ({', '.join(a.__name__ for a in accepted)}) "
+                              f"(solver is {getattr(solver, '__name__', solver)!r})")
+    return value
+
+
+def fpiter_batchable(iters, fmaps) -> bool:
+    """Whether ``anderson_solve_batch`` / ``picard_solve_batch`` take these handles and maps together
+    (``psignn_fpiter_batchable``): tiled plans of one family, every ``iters[i]`` made with ``shard_elems`` for the length of
+    ``fmaps[i]``'s plan, one vector width, one ``m``, one threshold, no kept trace; and, on the host, one latent width and
+    single-layer weights.  A host-side decision -- real errors of the lockstep solves still raise."""
+    n = len(iters)
+    if n == 0 or len(fmaps) != n:
+        return False
+    lib = iters[0].lib
+    if any(it.lib is not lib for it in iters) or any(f.lib is not lib or f.weights.n_layers != 1 for f in fmaps):
+        return False
+    hv = (C.c_void_p * n)(*[it.handle.value for it in iters])
+    pv = (C.c_void_p * n)(*[f.plan.handle.value for f in fmaps])
+    return bool(lib.psignn_fpiter_batchable(n, hv, pv))
+
+
+def _fp_shard_call(what, iters, fmaps):
+    """Marshalling shared by the two lockstep fixed-point solves; NativeError (nothing launched) for a shard that is not batchable."""
+    n = len(iters)
+    if len(fmaps) != n:
+        raise nat.NativeError("one FixedPointMap per handle")
+    call = _ShardCall(what, [f.weights for f in fmaps], nat.SolveInfo, [it.threshold + 2 for it in iters])
+    if not fpiter_batchable(iters, fmaps):
+        raise nat.NativeError(f"{what}: handles / maps are not batchable (engine.fpiter_batchable): tiled plans of one family, "
+                              "single-layer weights, handles made with shard_elems for their plans, one vector width, one m, one "
+                              "threshold, no kept trace")
+    plans = call.arr([f.plan.handle.value for f in fmaps])
+    return call, plans
+
+
+def anderson_solve_batch(iters, fmaps, eps, lam=1e-4, beta=1.0, stop_mode="rel", poll_every=8):
+    """One lockstep Anderson solve of several independent meshes (``psignn_anderson_solve_batch``) from x0 = each map's
+    ``h0``: ``iters[i]`` is a ``DeviceFixedPointIter(fmaps[i].plan.N * width, ..., shard_elems=...)``.  Returns one dict per mesh
+    with the fields of ``DeviceFixedPointIter.finish`` (result in the caller's numbering) -- each bit-identical to driving that
+    handle through ``anderson_begin / anderson_next / anderson_update / finish`` around ``fmap.fp`` on that mesh alone.  A shard
+    ``fpiter_batchable`` does not take raises ``NativeError`` with nothing launched."""
+    if stop_mode not in ("rel", "abs"):
+        raise ValueError(f"stop_mode {stop_mode!r}")
+    if len(iters) == 0:
+        return []
+    call, plans = _fp_shard_call("lockstep anderson solve", iters, fmaps)
+    w0, dev = call.w0, iters[0].device
+    results = [torch.empty_like(f.h0) for f in fmaps]
+    lows = [(C.c_int32 * (it.threshold + 2))() for it in iters]
+    lpp = (C.POINTER(C.c_int32) * call.n)(*[C.cast(r, C.POINTER(C.c_int32)) for r in lows])
+    with torch.cuda.device(dev):
+        nat.check(w0.lib.psignn_anderson_solve_batch(
+            call.n, call.handles(iters), plans, nat.ptr(w0.flat), w0.n_layers, call.tensors([f.h0 for f in fmaps]),
+            call.tensors([f.prb for f in fmaps]), call.tensors([f.nrm for f in fmaps]) if w0.mixed else None, float(lam), float(beta),
+            int(stop_mode == "abs"), float(eps), int(poll_every), call.tensors(results), call.infos, *call.traces(), lpp,
+            nat.stream_ptr(dev)), "psignn_anderson_solve_batch", w0.lib)
+    return [DeviceFixedPointIter._result(call.infos[i], call.rel[i], call.abs_[i], lows[i], results[i]) for i in range(call.n)]
+
+
+def picard_solve_batch(iters, fmaps, eps, poll_every=8):
+    """One lockstep Picard solve z <- f(z) of several independent meshes (``psignn_picard_solve_batch``) from z0 = each map's
+    ``h0``; handles and result dicts as ``anderson_solve_batch`` (``low_idx`` is all zeros: Picard keeps no lowest iterate)."""
+    if len(iters) == 0:
+        return []
+    call, plans = _fp_shard_call("lockstep picard solve", iters, fmaps)
+    w0, dev = call.w0, iters[0].device
+    results = [torch.empty_like(f.h0) for f in fmaps]
+    with torch.cuda.device(dev):
+        nat.check(w0.lib.psignn_picard_solve_batch(
+            call.n, call.handles(iters), plans, nat.ptr(w0.flat), w0.n_layers, call.tensors([f.h0 for f in fmaps]),
+            call.tensors([f.prb for f in fmaps]), call.tensors([f.nrm for f in fmaps]) if w0.mixed else None, float(eps),
+            int(poll_every), call.tensors(results), call.infos, *call.traces(), nat.stream_ptr(dev)),
+            "psignn_picard_solve_batch", w0.lib)
+    zeros = [0] * (max(it.threshold for it in iters) + 2)
+    return [DeviceFixedPointIter._result(call.infos[i], call.rel[i], call.abs_[i], zeros, results[i]) for i in range(call.n)]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -30,6 +30,11 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
   otherwise): the replicas of a list call take the lockstep route with the GMRES adjoint solve -- forward solves through
   ``engine.broyden_solve_batch``, the R adjoint systems through ``engine.gmres_solve_adjoint_batch`` -- where
   ``DeepEquilibrium.lockstep_applies`` says yes; without it replicas with ``bw_solver = "gmres"`` are solved one after the other.
+  An optional key ``"fp_lockstep"`` (bool, default False; True needs ``solver`` = ``utilities.solver.anderson`` or
+  ``forward_iteration``, ``NativeError`` naming both keys otherwise): the forward solves of a shard -- ``batch.solve_shard_batched``,
+  the replicas of a list call -- run in one lockstep Anderson / Picard solve (``utilities.solver.anderson_batch`` /
+  ``forward_iteration_batch``) where ``DeepEquilibrium.fp_lockstep_applies`` says yes (tiled plans of one family, single-layer block,
+  more than one mesh); the backward is untouched, and without the key every mesh is solved on its own as before.
 * ``load_state_dict(ckpt["state_dict"])`` of a reference checkpoint works unchanged: parameter names
   and shapes are identical.
 * ``batch`` is any object with the PyG ``Data`` attributes (see ``data/meshdata.py``), already on the GPU.
@@ -192,6 +197,8 @@ class _DEQFn(torch.autograd.Function):
                 deq._fw_key = (fmap.plan, cfg["fw_thres"], hdt)
             out_fw = _solver.broyden(fmap, H0, threshold=cfg["fw_thres"], eps=cfg["fw_tol"], keep_trace=False,
                                      solver_obj=deq._fw_solver, history_dtype=hdt)
+        elif getattr(deq, "presolved", None) is not None:   # a replica slot whose forward solve ran in lockstep with the others'
+            out_fw, deq.presolved = deq.presolved, None
         else:
             out_fw = cfg["solver"](fmap, H0, threshold=cfg["fw_thres"], eps=cfg["fw_tol"])
         H_star = out_fw["result"]
@@ -448,6 +455,21 @@ class DeepEquilibrium(nn.Module):
             return False
         return not fmaps[0].plan.mixed or all(f.lin_neumann == "stored" for f in fmaps)
 
+    def fp_lockstep_applies(self, fmaps):
+        """Whether the forward solves of these maps go through the lockstep Anderson / Picard solve: ``fp_lockstep`` is set (the
+        solver is then ``anderson`` or ``forward_iteration``: checked when the model was made), more than one mesh, tiled plans of
+        one family, single-layer weights.  A host-side decision, before anything is allocated; ``engine.fpiter_batchable`` is asked
+        again by the solve itself."""
+        if not self.config_deq.get("fp_lockstep") or len(fmaps) < 2:
+            return False
+        if any(not f.plan.tiled or f.weights.n_layers != 1 for f in fmaps):
+            return False
+        return all(bool(f.plan.mixed) == bool(fmaps[0].plan.mixed) for f in fmaps)
+
+    def fp_lockstep_solve(self, fmaps):
+        """The solver dicts of the lockstep forward solve of ``fmaps`` (``utilities.solver.lockstep_batch``), from each map's h0."""
+        return _solver.lockstep_batch(self.config_deq["solver"], fmaps, self.config_deq["fw_tol"], self.config_deq["fw_thres"])
+
     def train_forward_replicas(self, H_inits, batches, generator=None):
         """``(list of new_H_star, list of jacobian_loss)`` for R replicas, each an independent fixed-point problem with its own
         Broyden matrix and stop test -- what the reference's ``DataParallel`` does with ``num_gpus = R``
@@ -490,8 +512,12 @@ class DeepEquilibrium(nn.Module):
             new_Hs = list(_DEQReplicasFn.apply(self, tuple(batches), names, *H_inits, *params))
         else:
             new_Hs, fw = [], []
-            for sl, h, b in zip(slots, H_inits, batches):
+            # fp_lockstep: the R forward solves (anderson / forward_iteration) in one lockstep solve; each slot's _DEQFn then takes
+            # its solver dict instead of solving again, and the backward is the slot's own, as without the key
+            pre = self.fp_lockstep_solve(fmaps) if self.fp_lockstep_applies(fmaps) else [None] * R
+            for sl, h, b, o in zip(slots, H_inits, batches, pre):
                 sl.sink = self.last_backward
+                sl.presolved = o
                 new_Hs.append(_DEQFn.apply(h, sl, b, names, *params))
                 fw.append(sl.last_forward)
             self.last_forward = fw
@@ -650,6 +676,9 @@ class _Base(nn.Module):
         if "bw_gmres_lockstep" in self.config:   # optional: replicas with bw_solver = "gmres" solve their adjoint systems in lockstep
             self.config_deq["bw_gmres_lockstep"] = engine.check_bw_gmres_lockstep(self.config["bw_gmres_lockstep"],
                                                                                  self.config.get("bw_solver"))   # (NativeError otherwise)
+        if "fp_lockstep" in self.config:   # optional: shards solved by anderson / forward_iteration run in lockstep
+            self.config_deq["fp_lockstep"] = engine.check_fp_lockstep(self.config["fp_lockstep"], self.config["solver"],
+                                                                     (_solver.anderson, _solver.forward_iteration))   # (NativeError otherwise)
         if "broyden_history_dtype" in self.config:   # optional: bf16 storage of the Broyden pairs (utilities.solver.broyden only)
             engine.history_code(self.config["broyden_history_dtype"])   # (ValueError for any other dtype)
             self.config_deq["broyden_history_dtype"] = self.config["broyden_history_dtype"]

@@ -18,7 +18,8 @@ import os
 import torch
 
 from .. import _native as nat
-from ..engine import D, TRACE_BUDGET_BYTES, DeviceBroyden, DeviceFixedPointIter, FixedPointMap, history_code
+from ..engine import (D, TRACE_BUDGET_BYTES, DeviceBroyden, DeviceFixedPointIter, FixedPointMap, anderson_solve_batch, history_code,
+                      picard_solve_batch)
 
 
 class _NoTrace:
@@ -228,6 +229,79 @@ def anderson(f, x0, m=2, lam=1e-4, threshold=50, eps=1e-3, stop_mode="rel", beta
     trace = _LazyIterates(it, out["low_idx"], x0, shape, from_p)
     return {"result": from_p(out["result"]).reshape(shape), "lowest": low, "nstep": out["nstep"], "prot_break": False,
             "abs_trace": ab, "rel_trace": rel, "xest_trace": trace, "eps": eps, "threshold": threshold}
+
+
+def _shard_iters(fmaps, m, threshold):
+    """One ``DeviceFixedPointIter`` per map, sized for the shard (``shard_elems`` = the summed state length)."""
+    for f in fmaps:
+        if not isinstance(f, FixedPointMap):
+            raise nat.NativeError("the lockstep fixed-point solves take engine.FixedPointMap objects")
+    total = sum(f.plan.N * f.width for f in fmaps)
+    return [DeviceFixedPointIter(f.plan.N * f.width, f.h0.device, m=m, threshold=threshold, keep_trace=False, width=f.width,
+                                 shard_elems=total) for f in fmaps]
+
+
+def _anderson_dict(out, x0, eps, threshold, stop_mode):
+    """The dict ``anderson`` returns from a ``DeviceFixedPointIter.finish``-shaped dict whose result is in the caller's numbering;
+    no iterates are kept."""
+    n = out["n_iter"]
+    low = out["lowest_abs"] if stop_mode == "abs" else out["lowest"]
+    rel, ab = out["rel_trace"], out["abs_trace"]
+    if out["stop_reason"] == 1:   # early stop: pad as solver.py:279-282 (threshold - 1 - k entries, k = last loop index)
+        pad = threshold - 1 - (n + 1)
+        rel = rel + [out["lowest"]] * pad
+        ab = ab + [out["lowest_abs"]] * pad
+    return {"result": out["result"].reshape(x0.shape), "lowest": low, "nstep": out["nstep"], "prot_break": False,
+            "abs_trace": ab, "rel_trace": rel, "xest_trace": _NO_TRACE, "eps": eps, "threshold": threshold}
+
+
+def anderson_batch(fmaps, m=2, lam=1e-4, threshold=50, eps=1e-3, stop_mode="rel", beta=1.0, poll_every=8):
+    """``anderson(f, f.h0, ...)`` for every map of a shard in ONE lockstep device solve (``engine.anderson_solve_batch``: every pass
+    of the iteration is one launch over all meshes, own stop test and lowest iterate per mesh).  Returns a list of dicts shaped
+    like ``anderson``'s, traces padded the same way after an early stop, ``xest_trace`` the no-trace object; each mesh has the
+    bits of its own stepwise solve on a handle of the shard's vector width.  A shard the lockstep solve does not take (untiled
+    plan, both families, multi-layer weights) raises ``NativeError`` with nothing launched."""
+    if stop_mode not in ("rel", "abs"):
+        raise ValueError(f"stop_mode {stop_mode!r}")
+    if len(fmaps) == 0:
+        return []
+    iters = _shard_iters(fmaps, m, threshold)
+    try:
+        outs = anderson_solve_batch(iters, fmaps, eps, lam=lam, beta=beta, stop_mode=stop_mode, poll_every=poll_every)
+    finally:
+        for it in iters:
+            it.close()
+    return [_anderson_dict(o, f.h0, eps, threshold, stop_mode) for o, f in zip(outs, fmaps)]
+
+
+def forward_iteration_batch(fmaps, eps=1.e-5, threshold=50, poll_every=8):
+    """``forward_iteration(f, f.h0, ...)`` for every map of a shard in one lockstep device solve
+    (``engine.picard_solve_batch``); a list of dicts shaped like ``forward_iteration``'s, ``xest_trace`` the no-trace object."""
+    if len(fmaps) == 0:
+        return []
+    iters = _shard_iters(fmaps, 1, threshold)
+    try:
+        outs = picard_solve_batch(iters, fmaps, eps, poll_every=poll_every)
+    finally:
+        for it in iters:
+            it.close()
+    res = []
+    for o, f in zip(outs, fmaps):
+        dev = f.h0.device
+        rel = list(torch.tensor(o["rel_trace"], dtype=torch.float32, device=dev).unbind())
+        ab = list(torch.tensor(o["abs_trace"], dtype=torch.float32, device=dev).unbind())
+        res.append({"result": o["result"].reshape(f.h0.shape), "lowest": rel[-1], "abs_trace": ab, "rel_trace": rel,
+                    "xest_trace": _NO_TRACE, "nstep": o["nstep"], "eps": eps, "threshold": threshold})
+    return res
+
+
+def lockstep_batch(solver, fmaps, eps, threshold):
+    """The lockstep form of ``solver`` (``anderson`` / ``forward_iteration``, with the arguments the models pass) over a shard."""
+    if solver is anderson:
+        return anderson_batch(fmaps, threshold=threshold, eps=eps)
+    if solver is forward_iteration:
+        return forward_iteration_batch(fmaps, eps=eps, threshold=threshold)
+    raise nat.NativeError(f"no lockstep form of solver {getattr(solver, '__name__', solver)!r}")
 
 
 def newton(f, z0, eps=1.e-5, threshold=50):
