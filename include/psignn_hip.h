@@ -655,6 +655,43 @@ int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** solvers, const 
                                          double* const* h_rel_trace, double* const* h_abs_trace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Reference solve of the discrete Poisson system A u = y on the device: Jacobi-preconditioned conjugate gradient in float64 on the
+ * plan's own matrix structure (csrc/poisson_cg.hip).  The ground truth `sol` of the accuracy metric mse_loss(u, batch.sol), at any size.
+ * replaces: the direct solve of the reference's dataset builder (dirichlet/dataset/extract_data.py: solve(a == L, u, bc), LU; mixed:
+ *           mixed/dataset/extract_data.py) and this repository's host stand-in for it, data/hexmesh.py _solve (scipy spsolve).
+ * Rows with node flag bit0 (Dirichlet) are fixed, x_i = y_i, and none of their entries is read; the free rows F solve the lifted system
+ * A_FF x_F = b, b = y_F - A_FD y_D (the mixed family's Neumann rows are free rows).  The handle keeps its own float64 copy of the
+ * values (a 64-row sliced ELL in the plan's canonical column order), made once from d_a_ij in edge_index order, float32 (widened
+ * exactly) or float64; the plan is not needed after create.
+ * create checks what conjugate gradients need and fails with PSIGNN_EINVAL otherwise: every free-free entry has its transposed entry
+ * and max |a_ij - a_ji| <= 1e-6 * max |a_ij| (a symmetric input rounds symmetrically: a valid matrix has defect 0), every free row has
+ * a diagonal > 0, every value on a free row is finite.  Synchronous.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct psignn_cg psignn_cg_t;
+typedef struct {
+  int32_t n_iter;       /* iterations run */
+  int32_t converged;    /* 1: |r| <= tol |b| was met; 0: max_iter spent, or p.Ap <= 0 met (the iterate before it is returned) */
+  double rel;           /* |r| / |b| of the recurrence residual at the end */
+  double true_rel;      /* |(y - A x)_F| / |b|, recomputed from the returned x */
+  double b_norm;        /* |b|, the lifted right-hand side on F */
+  double sym_defect;    /* max |a_ij - a_ji| over the free-free entries, measured at create */
+} psignn_cg_info_t;
+int psignn_cg_create(psignn_cg_t** out, const psignn_plan_t* plan, const void* d_a_ij /* (E) edge_index order */, int a_is_f64,
+                     void* stream);
+void psignn_cg_destroy(psignn_cg_t* s);
+/* One solve, all vectors and scalars float64 on the device: per iteration q = A p (the direction p = z + beta p is formed inside this
+ * launch), alpha, then x += alpha p, r -= alpha q, z = r / diag(A), then beta, the stop test |r| <= tol |b| and the trace entry: four
+ * dependent launches, every reduction per-block partials summed by one block in a fixed order (no floating-point atomics: the same call
+ * gives the same bits).  The host only reads a done flag every poll_every iterations (<= 0: 50); launches queued beyond the last
+ * iteration return at once, so result, n_iter and trace do not depend on poll_every.  max_iter bounds the iterations (0: none).
+ * |b| = 0 gives x_F = 0 with n_iter 0; a start that meets the test gives n_iter 0.  d_y: (N) float32 or float64.  d_x0: (N) start
+ * (free rows are read) or NULL for zeros; may be d_sol.  d_sol: (N) float64, caller's numbering, holds the iterate during the solve.
+ * h_res_trace: |r| / |b| after each iteration, entry 0 the start; n_iter + 1 entries are written.  Synchronous at the end. */
+int psignn_cg_solve(psignn_cg_t* s, const void* d_y, int y_is_f64, const double* d_x0 /* NULL: zeros on free rows */, double tol,
+                    int max_iter, int poll_every, double* d_sol /* (N) caller's numbering */, psignn_cg_info_t* h_info,
+                    double* h_res_trace /* max_iter + 1 doubles or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line;
  * replaces: the reference's only instrumentation, time.time() around the model call,
  * tests/special_geo/spec_geo_2.py:313-317).  Off by default.

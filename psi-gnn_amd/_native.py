@@ -61,6 +61,11 @@ class GmresAdjointInfo(C.Structure):
                 ("lowest", C.c_double), ("lowest_abs", C.c_double)]
 
 
+class CgInfo(C.Structure):
+    _fields_ = [("n_iter", C.c_int32), ("converged", C.c_int32), ("rel", C.c_double), ("true_rel", C.c_double),
+                ("b_norm", C.c_double), ("sym_defect", C.c_double)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _INT = C.c_int
@@ -198,6 +203,9 @@ SIGNATURES = {
     "psignn_gmres_solve_adjoint_lin_batch": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P), _P, _INT, C.POINTER(_P), C.c_double, _INT, _INT,
                                                     C.POINTER(_P), C.POINTER(_P), C.POINTER(GmresAdjointInfo),
                                                     C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double)), _P]),
+    "psignn_cg_create": (_INT, [C.POINTER(_P), _P, _P, _INT, _P]),
+    "psignn_cg_destroy": (None, [_P]),
+    "psignn_cg_solve": (_INT, [_P, _P, _INT, _P, C.c_double, _INT, _INT, _P, C.POINTER(CgInfo), C.POINTER(C.c_double), _P]),
     "psignn_prof_enable": (None, [_INT]),
     "psignn_reload_knobs": (None, []),
     "psignn_prof_tile_stamps": (None, [_P]),

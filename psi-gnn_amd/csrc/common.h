@@ -176,6 +176,7 @@ struct psignn_plan {
   uint8_t* flags = nullptr;                        // (N)
   int32_t *a_ptr = nullptr, *a_col = nullptr;      // full CSR of A (self loops included)
   float* a_val = nullptr;
+  int32_t* a_eid = nullptr;                        // (E) original edge id of every full-CSR entry (poisson_cg.hip gathers its fp64 values by it)
   int max_deg = 0;
 
   // ---- tile structures (tiles.hip); valid when tiled != 0 -------------------------------------

@@ -278,7 +278,7 @@ static int dmalloc(T** p, size_t n) {
 extern "C" void psignn_plan_destroy(psignn_plan_t* p) {
   if (!p) return;
   void* ptrs[] = {p->csr_ptr, p->csr_nbr, p->csr_eid, p->csc_ptr, p->csc_nbr, p->csc_eid, p->csr_attr,
-                  p->csc_attr, p->flags,   p->a_ptr,   p->a_col,   p->a_val};
+                  p->csc_attr, p->flags,   p->a_ptr,   p->a_col,   p->a_val,   p->a_eid};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   psignn_tiles_free(p);
@@ -301,12 +301,11 @@ extern "C" int psignn_plan_create(psignn_plan_t** out, int64_t N, int64_t E, con
   p->E = E;
   p->mixed = tags_cols == 3;
   int rc = 0;
-  int32_t *deg = nullptr, *bsum = nullptr, *a_eid = nullptr, *misc = nullptr;
+  int32_t *deg = nullptr, *bsum = nullptr, *misc = nullptr;
   const unsigned TB = 256;
   auto fail = [&](int code) {
     if (deg) (void)hipFree(deg);
     if (bsum) (void)hipFree(bsum);
-    if (a_eid) (void)hipFree(a_eid);
     if (misc) (void)hipFree(misc);
     psignn_plan_destroy(p);
     return code;
@@ -357,23 +356,23 @@ extern "C" int psignn_plan_create(psignn_plan_t** out, int64_t N, int64_t E, con
   TRY(dmalloc(&p->csc_attr, 3 * Ep));
   TRY(dmalloc(&p->a_col, (size_t)E));
   TRY(dmalloc(&p->a_val, (size_t)E));
-  TRY(dmalloc(&a_eid, (size_t)E));
+  TRY(dmalloc(&p->a_eid, (size_t)E));
   if (hipMemsetAsync(deg, 0, 3 * N * sizeof(int32_t), st) != hipSuccess) return fail(PSIGNN_EHIP);
   if (E > 0) {
     k_fill<<<dim3((unsigned)cdiv(E, TB)), TB, 0, st>>>(E, d_ei, p->csr_ptr, p->csc_ptr, p->a_ptr, deg, deg + N,
                                                         deg + 2 * N, p->csr_nbr, p->csr_eid, p->csc_nbr,
-                                                        p->csc_eid, p->a_col, a_eid);
+                                                        p->csc_eid, p->a_col, p->a_eid);
     unsigned gn = (unsigned)cdiv(N, TB);
     k_canon<<<gn, TB, 0, st>>>(N, p->csr_ptr, p->csr_nbr, p->csr_eid, misc + 1);
     k_canon<<<gn, TB, 0, st>>>(N, p->csc_ptr, p->csc_nbr, p->csc_eid, misc + 1);
-    k_canon<<<gn, TB, 0, st>>>(N, p->a_ptr, p->a_col, a_eid, nullptr);
+    k_canon<<<gn, TB, 0, st>>>(N, p->a_ptr, p->a_col, p->a_eid, nullptr);
     if (Ep > 0) {
       unsigned ge = (unsigned)cdiv((int64_t)Ep, TB);
       k_gather_attr<<<ge, TB, 0, st>>>((int64_t)Ep, p->csr_eid, d_attr, p->csr_attr);
       k_gather_attr<<<ge, TB, 0, st>>>((int64_t)Ep, p->csc_eid, d_attr, p->csc_attr);
     }
     if (d_aij)
-      k_gather_val<<<dim3((unsigned)cdiv(E, TB)), TB, 0, st>>>(E, a_eid, d_aij, p->a_val);
+      k_gather_val<<<dim3((unsigned)cdiv(E, TB)), TB, 0, st>>>(E, p->a_eid, d_aij, p->a_val);
     else if (hipMemsetAsync(p->a_val, 0, E * sizeof(float), st) != hipSuccess)
       return fail(PSIGNN_EHIP);
   }
@@ -385,7 +384,6 @@ extern "C" int psignn_plan_create(psignn_plan_t** out, int64_t N, int64_t E, con
   p->max_deg = h_misc[1];
   (void)hipFree(deg);
   (void)hipFree(bsum);
-  (void)hipFree(a_eid);
   (void)hipFree(misc);
 #undef TRY
   if (tile_target >= 0 && Ep > 0) {

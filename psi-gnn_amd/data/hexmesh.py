@@ -158,9 +158,32 @@ def _solve(A, rhs, compute_sol):
     return spsolve(A.tocsc(), rhs)
 
 
+def _solve_on_device(data, val, rhs):
+    """``sol`` by the device's float64 conjugate-gradient solve (engine.PoissonCG) of the float64 matrix values and right-hand
+    side, as assembled -- before the cast to the dataset's dtype.  Needs a GPU: there is no host fallback for this value."""
+    from .. import _native as nat
+    from .. import engine
+    if not torch.cuda.is_available():
+        raise nat.NativeError('compute_sol="device" solves on the current GPU and none is available; compute_sol=True solves on '
+                              "the host")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cg = engine.PoissonCG(engine.MeshPlan(data.to(dev), tile_target=-1), torch.from_numpy(np.ascontiguousarray(val)).to(dev))
+    try:
+        # 1e-12: two decades below the solver's default, so that the float32 cast of the result is the cast of the direct solve
+        out = cg.solve(torch.from_numpy(np.ascontiguousarray(rhs)).to(dev), tol=1e-12)
+    finally:
+        cg.close()
+    if not out["converged"]:
+        raise nat.NativeError(f'compute_sol="device": the conjugate-gradient solve stopped after {out["n_iter"]} iterations at a '
+                              f'relative residual of {out["rel"]:.3e}')
+    return out["result"][:, 0].cpu().numpy()
+
+
 def make_from_triangulation(pos, tri, dirichlet_mask, seed=0, radius=1.0, mixed=False,
                             normals=None, compute_sol=True, dtype=torch.float32, coeffs=None) -> MeshData:
     """Assemble one Poisson problem on an arbitrary P1 triangulation and emit the reader schema.
+    ``compute_sol``: True: ``sol`` by the host's direct solve; False: zeros; "device": by the float64 conjugate-gradient solve on the
+    current GPU (``engine.PoissonCG``; NativeError without a GPU) -- the one that is still quick at a million nodes.
     ``coeffs`` = (param_f[3], param_g[6]) overrides the seeded draw (to rebuild a problem the reference recorded)."""
     N = pos.shape[0]
     K, M = p1_assemble(pos, tri)
@@ -170,7 +193,10 @@ def make_from_triangulation(pos, tri, dirichlet_mask, seed=0, radius=1.0, mixed=
     gv = _g_expr(pg, xs, ys)
     rhs = M @ fv
     A, rhs = _apply_dirichlet(K, rhs, dirichlet_mask, gv)
-    sol = _solve(A, rhs, compute_sol)
+    on_device = isinstance(compute_sol, str)
+    if on_device and compute_sol != "device":
+        raise ValueError(f'compute_sol must be True, False or "device", not {compute_sol!r}')
+    sol = _solve(A, rhs, compute_sol and not on_device)
     row, col, val, dist = _edges_of(A, pos)
 
     if not mixed:
@@ -199,6 +225,8 @@ def make_from_triangulation(pos, tri, dirichlet_mask, seed=0, radius=1.0, mixed=
         prb_data=t(prb), tags=t(tags), pos=t(pos))
     if unv is not None:
         data.unit_normal_vector = t(unv)
+    if on_device:
+        data.sol = t(_solve_on_device(data, val, rhs)[:, None])
     return data
 
 
@@ -222,7 +250,7 @@ def vertex_normals(pos, tri):
 
 
 def make_hex_problem(n: int, seed: int = 0, mixed: bool = False, warp: float = 0.15,
-                     phase: float | None = None, compute_sol: bool = True,
+                     phase: float | None = None, compute_sol: bool | str = True,
                      dtype=torch.float32, hsize: float = HSIZE, radius: float | None = None) -> MeshData:
     """One synthetic Poisson problem on the warped hexagon with ``3n^2+3n+1`` nodes.
 

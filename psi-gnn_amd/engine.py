@@ -1760,3 +1760,86 @@ def gmres_solve_adjoint_batch(solvers, lins, grads, eps, max_products, poll_ever
             int(max_products), int(poll_every), call.tensors(works), call.tensors(results), call.infos, *call.traces(),
             nat.stream_ptr(dev)), "psignn_gmres_solve_adjoint_lin_batch")
     return call.collect([s._result for s in solvers], results)
+
+
+# ---------------------------------------------------------------------------------------------
+# reference solve of A u = y (csrc/poisson_cg.hip)
+# ---------------------------------------------------------------------------------------------
+def _f64_or_f32(t, name):
+    """A float32 or float64 device tensor as a flat contiguous one plus its is-float64 flag (other dtypes go to float64)."""
+    nat.require_cuda(t, name)
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float64)
+    return t.reshape(-1).contiguous(), int(t.dtype == torch.float64)
+
+
+def default_cg_max_iter(n_nodes: int) -> int:
+    """max(1000, 20 ceil(sqrt(N))): Jacobi-PCG on 2-D P1 Poisson needs about 1/2 sqrt(kappa) ln(2 / tol) iterations with
+    sqrt(kappa) ~ 0.64 sqrt(N) -- about 7 600 at 1M nodes and tol = 1e-10, so the cap leaves about 2.6x headroom."""
+    return max(1000, 20 * int(np.ceil(np.sqrt(n_nodes))))
+
+
+class PoissonCG:
+    """Device-native solve of the discrete Poisson system ``A u = y`` of a plan's mesh: Jacobi-preconditioned conjugate gradient
+    in float64 (``psignn_cg_*`` in include/psignn_hip.h) -- what ``scipy.sparse.linalg.spsolve`` is to ``data.hexmesh._solve``,
+    at any size.  ``a_ij``: the (E,) or (E, 1) values in ``edge_index`` order, float32 (widened exactly) or float64; the
+    handle keeps its own float64 copy.  Rows the plan flags as Dirichlet are fixed to ``y``; the others solve the lifted
+    system.  Raises ``NativeError`` when the matrix is not symmetric with a positive diagonal on its free rows."""
+
+    def __init__(self, plan: MeshPlan, a_ij):
+        a, a64 = _f64_or_f32(a_ij, "a_ij")
+        if a.numel() != plan.E:
+            raise nat.NativeError(f"a_ij has {a.numel()} values, the plan {plan.E} edges")
+        self.plan, self.N, self.device = plan, plan.N, plan.device
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_cg_create(C.byref(h), plan.handle, nat.ptr(a), a64, nat.stream_ptr(self.device)),
+                      "psignn_cg_create")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_cg_destroy, h)
+
+    def close(self):
+        self._fin()
+        self.handle = None
+
+    def solve(self, y, x0=None, tol=1e-10, max_iter=None, poll_every=50):
+        """``y``: (N,) or (N, 1), float32 or float64.  ``x0``: start on the free rows (default zeros).  Stops on
+        ``|r| <= tol |b|`` (b: the lifted right-hand side on the free rows) or after ``max_iter`` iterations (default
+        ``default_cg_max_iter(N)``).  Returns ``result`` (N, 1) float64 in the caller's numbering, ``n_iter``, ``converged``,
+        ``rel`` (recurrence residual), ``true_rel`` (|(y - A x)_F| / |b| recomputed from the result), ``res_trace``
+        (n_iter + 1 relative residuals), ``b_norm`` and ``sym_defect``.  Deterministic; ``poll_every`` (how often the host
+        looks at the done flag) changes nothing in the result."""
+        if self.handle is None:
+            raise nat.NativeError("PoissonCG is closed")
+        yc, y64 = _f64_or_f32(y, "y")
+        if yc.numel() != self.N:
+            raise nat.NativeError(f"y has {yc.numel()} entries, the plan {self.N} nodes")
+        if max_iter is None:
+            max_iter = default_cg_max_iter(self.N)
+        max_iter = int(max_iter)
+        x0c = None
+        if x0 is not None:
+            nat.require_cuda(x0, "x0")
+            x0c = x0.to(torch.float64).reshape(-1).contiguous()
+            if x0c.numel() != self.N:
+                raise nat.NativeError(f"x0 has {x0c.numel()} entries, the plan {self.N} nodes")
+        result = torch.empty((self.N, 1), dtype=torch.float64, device=self.device)
+        info = nat.CgInfo()
+        trace = (C.c_double * (max(max_iter, 0) + 1))()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_cg_solve(self.handle, nat.ptr(yc), y64, nat.ptr(x0c), float(tol), max_iter, int(poll_every),
+                                                nat.ptr(result), C.byref(info), trace, nat.stream_ptr(self.device)),
+                      "psignn_cg_solve")
+        n = int(info.n_iter)
+        return {"result": result, "n_iter": n, "converged": bool(info.converged), "rel": float(info.rel),
+                "true_rel": float(info.true_rel), "res_trace": list(trace[:n + 1]), "b_norm": float(info.b_norm),
+                "sym_defect": float(info.sym_defect)}
+
+
+def poisson_solve(batch, tol=1e-10, **kw):
+    """``PoissonCG(plan_for(batch), batch.a_ij).solve(batch.y, tol=tol, **kw)``.  A union batch is one block-diagonal system."""
+    cg = PoissonCG(plan_for(batch), batch.a_ij)
+    try:
+        return cg.solve(batch.y, tol=tol, **kw)
+    finally:
+        cg.close()
