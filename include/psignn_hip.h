@@ -113,12 +113,14 @@ int64_t psignn_weights_size(int mixed, int n_layers);
  *           mixed/psignn/model.py:216-245) including both/all three MessagePassing.propagate
  *           passes, the gated update MLP, LayerNorm and the Dirichlet/Neumann row handling.
  * d_prb: (N,2) dirichlet / (N,3) mixed.  d_normals: (N,2) mixed only, else NULL.
- * d_work: scratch of psignn_f_workspace_floats(plan) floats.  d_out must not alias d_h.
+ * d_work: scratch of psignn_f_workspace_floats(plan) floats (what each form keeps in it: the f-workspace views of
+ * csrc/workspace.h -- ws::FFwd, ws::FVjp, ws::Adapter; every workspace of this header is laid out there, by the function that
+ * also answers its size query).  d_out must not alias d_h.
  * ------------------------------------------------------------------------------------------ */
 int64_t psignn_f_workspace_floats(const psignn_plan_t* plan);
 
 /* Extra scratch the derivatives of a multi-layer block need: dirichlet, the layer states h_1..h_{L-1}, the tangents and
- * cotangents carried between layers and a single-layer weight view, (4 n_layers + 1) * N * 10 + 4096 floats; mixed (whose
+ * cotangents carried between layers and a single-layer weight view, (4 n_layers + 1) * N * 10 + 4096 floats (ws::LayerWork); mixed (whose
  * iterated layer is the last one), the weight view alone; 0 for single-layer blocks.  A derivative entry point that takes
  * d_work is then given its own workspace (psignn_f_workspace_floats for psignn_f_jvp / _jvp_pw / _vjp / _vjp_p,
  * psignn_f_param_vjp_workspace_floats for the parameter VJPs, psignn_f_vjp_backward_workspace_floats for the backward of the
@@ -229,7 +231,7 @@ int psignn_f_vjp_p(const psignn_plan_t* plan, const float* d_weights, int n_laye
  * cotangent (dirichlet/psignn/model.py:203-225, training_class.py:150-163).  d_grad receives
  * psignn_param_grad_size(mixed, n_layers) floats laid out like the leading (un-derived) section of the packed
  * weights: shared{ln_gamma, ln_beta, alpha_w, alpha_b} | phi_to{W1,b1,W2,b2} | phi_from | update{U1,c1,U2,c2};
- * derived (fold) slots stay zero.  d_work: psignn_f_param_vjp_workspace_floats(plan) floats. */
+ * derived (fold) slots stay zero.  d_work: psignn_f_param_vjp_workspace_floats(plan) floats (ws::pv_work, ws::pv_adapter). */
 int64_t psignn_param_grad_size(int mixed, int n_layers);
 int64_t psignn_f_param_vjp_workspace_floats(const psignn_plan_t* plan);
 /* the same in the caller's numbering and for every plan and depth: tiled plans of both families run the tile kernels in
@@ -255,7 +257,7 @@ int psignn_f_param_vjp_p(const psignn_plan_t* plan, const float* d_weights, int 
  * jac_loss_estimate -- autograd.grad(f0, z0, v, create_graph=True), dirichlet/psignn/model.py:416-435 -- when the
  * Jacobian regulariser is part of the loss (jac_weight, training_class.py:156-159): with g = J^T v and
  * jac_loss = |g|^2 / (N d), pass gbar = (d loss / d jac_loss) * 2 g / (N d).  Caller's numbering; blocks of both
- * families and any depth (multi-layer: d_work grows by psignn_f_layers_workspace_floats) (mixed: d_normals required, d_grad also covers phi_neumann | update_neumann).  d_work: psignn_f_vjp_backward_workspace_floats(plan) floats. */
+ * families and any depth (multi-layer: d_work grows by psignn_f_layers_workspace_floats) (mixed: d_normals required, d_grad also covers phi_neumann | update_neumann).  d_work: psignn_f_vjp_backward_workspace_floats(plan) floats (ws::JrWork). */
 int64_t psignn_f_vjp_backward_workspace_floats(const psignn_plan_t* plan);
 int psignn_f_vjp_backward(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h,
                           const float* d_prb, const float* d_normals, const float* d_v, const float* d_gbar, float* d_grad,
@@ -266,7 +268,7 @@ int psignn_f_vjp_backward(const psignn_plan_t* plan, const float* d_weights, int
  * dirichlet/psignn/model.py:416-435, training_class.py:156-159 -- as two tile kernels and the record reduction.
  * psignn_f_vjp_backward_tiled_ok: 1 where this form applies (tiled plan of the dirichlet family, n_layers == 1), else 0
  * (also for a NULL plan); where it is 0, psignn_f_vjp_backward_p is an argument error and launches nothing.  d_grad as above;
- * d_work: psignn_f_vjp_backward_p_workspace_floats(plan) floats. */
+ * d_work: psignn_f_vjp_backward_p_workspace_floats(plan) floats (ws::JrWork, tile form). */
 int psignn_f_vjp_backward_tiled_ok(const psignn_plan_t* plan, int n_layers);
 int64_t psignn_f_vjp_backward_p_workspace_floats(const psignn_plan_t* plan);
 int psignn_f_vjp_backward_p(const psignn_plan_t* plan, const float* d_weights, int n_layers, const float* d_h,
@@ -286,7 +288,7 @@ int psignn_residual_t(const psignn_plan_t* plan, const float* d_a_ij, const floa
  *   c = [h | Phi_to(h) | Phi_from(h) | prb], Dirichlet rows <- d_h0 rows; mixed plans: Neumann rows <-
  *   update_neumann([h | Phi_neumann(h) | prb | normal]) (d_normals required),
  * starting from d_h0 (the encoder state).  Tiled plans.  d_weights: psignn_dsgps_weights_size(mixed) floats
- * (layout in csrc/dsgps_tile.hip, built by engine.pack_dsgps); d_work: 4 * N * 10 floats.
+ * (layout in csrc/dsgps_tile.hip, built by engine.pack_dsgps); d_work: 4 * N * 10 floats (ws::DsgpsWork).
  * psignn_dsgps_step_p: a single update with all node tensors in plan order. */
 int64_t psignn_dsgps_weights_size(int mixed);
 int psignn_dsgps_forward(const psignn_plan_t* plan, const float* d_weights, int k, const float* d_h0, const float* d_prb,
@@ -300,7 +302,7 @@ int psignn_dsgps_step_p(const psignn_plan_t* plan, const float* d_weights, const
  * phi_neumann | update_neumann; psignn_param_grad_size(mixed, 1)) followed by [Wz (10 x (30+P)) | bz | Wr | br | Wc | bc].
  * d_phi_weights: those modules in the f_theta weight layout (psignn_weights_size(mixed, 1) floats; only their blocks are
  * read); d_gate_weights: [Wz | bz | Wr | br | Wc | bc] as nn.Linear stores them.  d_normals: mixed plans.
- * d_work: psignn_dsgps_step_backward_workspace_floats(plan). */
+ * d_work: psignn_dsgps_step_backward_workspace_floats(plan) floats (ws::dsgps_bw_work). */
 int64_t psignn_dsgps_grad_size(int mixed);
 int64_t psignn_dsgps_step_backward_workspace_floats(const psignn_plan_t* plan);
 int psignn_dsgps_step_backward(const psignn_plan_t* plan, const float* d_phi_weights, const float* d_gate_weights,
@@ -310,7 +312,7 @@ int psignn_dsgps_step_backward(const psignn_plan_t* plan, const float* d_phi_wei
 /* DSS, the Deep Statistical Solver baseline (dirichlet/dss/model.py:97-120): k updates with per-step weights
  *   h <- h + alpha * Psi_t([h | Phi_to_t(h) | Phi_from_t(h) | b'_norm]),  H_0 = 0,
  * on a tiled plan created with edge_attr = (0, 0, a_ij_norm) (the scalar edge feature of DSS).  d_weights:
- * psignn_dss_weights_size(k) floats (layout in csrc/dss_tile.hip, built by engine.pack_dss); d_work: N * 23 floats. */
+ * psignn_dss_weights_size(k) floats (layout in csrc/dss_tile.hip, built by engine.pack_dss); d_work: N * 23 floats (ws::DssWork). */
 int64_t psignn_dss_weights_size(int k);
 int psignn_dss_forward(const psignn_plan_t* plan, const float* d_weights, int k, float alpha, const float* d_bprime_norm,
                        float* d_out, float* d_work, void* stream);
@@ -322,7 +324,7 @@ int psignn_dss_step_p(const psignn_plan_t* plan, const float* d_weights, int t, 
  * modules in the f_theta weight layout with three node inputs (psignn_weights_size(1, 1)-style layout without Neumann blocks:
  * phi W1 padded to (10, 23) with the edge-feature weight in column 22, Psi in the update slots; engine.pack_dss_train builds
  * it).  d_grad: psignn_dss_grad_size() floats in that layout; d_out_h = w^T dh'/dh.
- * d_work: psignn_dss_step_backward_workspace_floats(plan). */
+ * d_work: psignn_dss_step_backward_workspace_floats(plan) floats (ws::dss_bw_work). */
 int64_t psignn_dss_grad_size(void);
 int64_t psignn_dss_step_backward_workspace_floats(const psignn_plan_t* plan);
 int psignn_dss_step_backward(const psignn_plan_t* plan, const float* d_weights_t, float alpha, const float* d_h,
@@ -605,7 +607,7 @@ typedef struct {
   double lowest_abs;    /* its |r| */
 } psignn_gmres_adjoint_info_t;
 /* Floats of d_work for a solve on `plan` with blocks of n_layers (operator scratch, iterate, best iterate, plan-order copies of the
- * inputs, the layer states of a multi-layer dirichlet block); -1 on bad arguments.  (model.py:210-223: none of this is kept there.) */
+ * inputs, the layer states of a multi-layer dirichlet block: ws::AdjWork); -1 on bad arguments.  (model.py:210-223: none of this is kept there.) */
 int64_t psignn_gmres_adjoint_workspace_floats(const psignn_plan_t* plan, int n_layers);
 /* The solve with the VJP kernels as the map (model.py:210-223, autograd.grad(new_H, H, y) per step there): tiled plans run in plan
  * order on psignn_f_vjp_p (multi-layer dirichlet blocks: the layer states once, then the backward layers per product), untiled plans

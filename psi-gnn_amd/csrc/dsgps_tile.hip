@@ -16,6 +16,7 @@
 //   480  W2_to^T 100 | 580 b2_to | 590 W2_from^T | 690 b2_from
 //   700  Wz^T 320 | 1020 bz | 1030 Wr^T 320 | 1350 br | 1360 Wc^T 320 | 1680 bc    -- total 1690
 #include "tile_helpers.h"
+#include "internal.h"
 
 template <int PP>
 struct DsL {
@@ -234,7 +235,7 @@ static void dsgps_launch(const psignn_plan* p, const float* W, const float* cur,
 }
 
 // k updates from d_h0 (the encoder state; also the Dirichlet rows of every iterate).  d_h0, d_prb, d_normals, d_out in
-// the caller's numbering (d_normals: mixed plans only); d_work: 4 * N * 10 floats.  k = 0 copies d_h0.
+// the caller's numbering (d_normals: mixed plans only); d_work: 4 * N * 10 floats (ws::DsgpsWork).  k = 0 copies d_h0.
 extern "C" int psignn_dsgps_forward(const psignn_plan_t* p, const float* W, int k, const float* d_h0, const float* d_prb,
                                     const float* d_normals, float* d_out, float* d_work, void* stream) {
   ARG_CHECK(p && W && d_h0 && d_prb && d_out && d_work, "NULL argument");
@@ -242,25 +243,18 @@ extern "C" int psignn_dsgps_forward(const psignn_plan_t* p, const float* W, int 
   ARG_CHECK(!p->mixed || d_normals, "mixed plan needs unit normals");
   ARG_CHECK(p->tiled, "DS-GPS kernels need a tiled plan (mesh positions)");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t N = p->N;
-  const int P = p->mixed ? 3 : 2;
-  float* h0p = d_work;
-  float* a = h0p + N * D;
-  float* b = a + N * D;
-  float* prbp = b + N * D;   // (N, P)
-  float* nrmp = prbp + N * P;  // (N, 2), mixed
+  const ws::DsgpsWork w = ws::dsgps_work(p->N, p->mixed, d_work);
+  ws::Adapter o{nullptr, w.h0, nullptr, nullptr, w.prb, w.nrm};
   int rc;
-  if ((rc = psignn_plan_permute(p, d_h0, D, h0p, 1, stream))) return rc;
-  if ((rc = psignn_plan_permute(p, d_prb, P, prbp, 1, stream))) return rc;
-  if (p->mixed && (rc = psignn_plan_permute(p, d_normals, 2, nrmp, 1, stream))) return rc;
-  const float* cur = h0p;
+  if ((rc = psignn_to_plan(p, d_h0, nullptr, d_prb, d_normals, o, st))) return rc;
+  const float* cur = o.h;
   for (int i = 0; i < k; ++i) {
-    float* dst = (i & 1) ? b : a;
-    dsgps_launch(p, W, cur, h0p, prbp, p->mixed ? nrmp : nullptr, dst, st);
+    float* dst = (i & 1) ? w.b : w.a;
+    dsgps_launch(p, W, cur, o.h, o.prb, o.nrm, dst, st);
     cur = dst;
   }
   HIP_TRY(hipGetLastError());
-  return psignn_plan_permute(p, cur, D, d_out, 0, stream);
+  return psignn_from_plan(p, cur, d_out, st);
 }
 
 // One update in PLAN order (state, H_0, prb and normals already permuted): for callers that keep every iterate

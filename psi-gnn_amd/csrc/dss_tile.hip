@@ -12,6 +12,7 @@
 //   460 b1_to | 470 b1_from | 480 W2_to^T 100 | 580 b2_to | 590 W2_from^T 100 | 690 b2_from |
 //   700 P1^T (33 x 10) 330 | 1030 c1 | 1040 P2^T 100 | 1140 c2                                   -- 1150 per step
 #include "tile_helpers.h"
+#include "workspace.h"
 
 namespace dss {
 constexpr int W1J_TO = 0, W1J_FR = 100, W1I_TO = 200, W1I_FR = 300, A_TO = 400, A_FR = 430, B1_TO = 460, B1_FR = 470;
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_dss_tile(int n_tiles, int chun
 extern "C" int64_t psignn_dss_weights_size(int k) { return (int64_t)k * dss::STEP; }
 
 // k updates from H_0 = 0 with per-step weights.  d_bprime (N, 3) and d_out (N, 10) in the caller's numbering;
-// d_work: N * 23 floats.  The plan must have been created with edge_attr = (0, 0, a_ij_norm).
+// d_work: N * 23 floats (ws::DssWork).  The plan must have been created with edge_attr = (0, 0, a_ij_norm).
 extern "C" int psignn_dss_forward(const psignn_plan_t* p, const float* W, int k, float alpha, const float* d_bprime,
                                   float* d_out, float* d_work, void* stream) {
   ARG_CHECK(p && W && d_bprime && d_out && d_work, "NULL argument");
@@ -130,9 +131,8 @@ extern "C" int psignn_dss_forward(const psignn_plan_t* p, const float* W, int k,
   ARG_CHECK(p->tiled, "DSS kernels need a tiled plan (mesh positions)");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = p->N;
-  float* a = d_work;
-  float* b = a + N * D;
-  float* bpp = b + N * D;  // (N, 3)
+  const ws::DssWork w = ws::dss_work(N, d_work);
+  float *a = w.a, *b = w.b, *bpp = w.bprime;  // bprime: (N, 3)
   int rc;
   if ((rc = psignn_plan_permute(p, d_bprime, dss::P, bpp, 1, stream))) return rc;
   HIP_TRY(hipMemsetAsync(a, 0, (size_t)N * D * 4, st));

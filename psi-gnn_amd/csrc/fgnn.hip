@@ -13,6 +13,7 @@
 #include "common.h"
 
 #include "fgnn_common.h"
+#include "internal.h"
 #include <string.h>
 #include <stdlib.h>
 
@@ -297,12 +298,7 @@ extern "C" int64_t psignn_weights_size(int mixed, int n_layers) {
   return mixed ? WLayout<3>::total(n_layers, true) : WLayout<2>::total(n_layers, false);
 }
 
-extern "C" int64_t psignn_f_workspace_floats(const psignn_plan_t* p) {
-  if (!p) return -1;
-  // Pj (value + tangent rows, up to 3 Phi modules) + two (N,D) ping-pong buffers for n_layers > 1;
-  // the VJP keeps Pj (3 D) + B (6 D) rows per node
-  return p->N * (10 * D);
-}
+extern "C" int64_t psignn_f_workspace_floats(const psignn_plan_t* p) { return p ? ws::f_total(p->N) : -1; }
 
 template <int P, bool MIXED, bool JVP>
 static void launch_layer(const psignn_plan* p, const float* W, int n_layers, int layer, int apply_ln,
@@ -342,7 +338,8 @@ int psignn_f_forward_sel(const psignn_plan_t* p, const float* W, int nl, const f
     launch_layer<3, true, false>(p, W, nl, nl - 1, 1, h, h0, prb, nrm, nullptr, out, work, nullptr, 0, st, hsel,
                                  hstride);
   } else {
-    float* pp[2] = {work + p->N * (2 * 3 * D), work + p->N * (2 * 3 * D + D)};
+    const ws::FFwd g = ws::f_fwd(p->N, false, work, ws::f_total(p->N));
+    float* const* pp = g.pp;
     const float* cur = h;
     for (int l = 0; l < nl; ++l) {
       float* dst = (l == nl - 1) ? out : pp[l & 1];
@@ -354,10 +351,6 @@ int psignn_f_forward_sel(const psignn_plan_t* p, const float* W, int nl, const f
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
-
-int psignn_f_tile_forward(const psignn_plan* p, const float* W, int nl, const float* h, const int32_t* hsel,
-                          int64_t hstride, const float* h0, const float* prb, const float* nrm, float* out,
-                          float* work, hipStream_t st);
 
 // Evaluation with every node tensor in PLAN order (the solver's internal numbering): tiled kernel when the
 // plan has tile structures, global-gather kernels otherwise (then plan order == caller order).
@@ -401,20 +394,10 @@ extern "C" int psignn_f_forward(const psignn_plan_t* p, const float* W, int nl, 
   int rc = f_args_ok(p, W, nl, h, prb, nrm, out, work);
   if (rc) return rc;
   ARG_CHECK(h0 != nullptr, "h_initial is NULL");
-  const int64_t N = p->N;
-  const int P = p->mixed ? 3 : 2;
-  float* hp = work;
-  float* h0p = hp + N * D;
-  float* outp = h0p + N * D;
-  float* prbp = outp + N * D;
-  float* nrmp = prbp + N * 3;
-  float* rest = nrmp + N * 2;
-  if ((rc = psignn_plan_permute(p, h, D, hp, 1, stream))) return rc;
-  if ((rc = psignn_plan_permute(p, h0, D, h0p, 1, stream))) return rc;
-  if ((rc = psignn_plan_permute(p, prb, P, prbp, 1, stream))) return rc;
-  if (p->mixed && (rc = psignn_plan_permute(p, nrm, 2, nrmp, 1, stream))) return rc;
-  if ((rc = psignn_f_tile_forward(p, W, nl, hp, nullptr, 0, h0p, prbp, p->mixed ? nrmp : nullptr, outp, rest, st))) return rc;
-  return psignn_plan_permute(p, outp, D, out, 0, stream);
+  ws::Adapter a = ws::f_adapter(p->N, false, work);
+  if ((rc = psignn_to_plan(p, h, h0, prb, nrm, a, st))) return rc;
+  if ((rc = psignn_f_tile_forward(p, W, nl, a.h, nullptr, 0, a.x, a.prb, a.nrm, a.out, a.rest, st))) return rc;
+  return psignn_from_plan(p, a.out, out, st);
 }
 
 extern "C" int psignn_phi(const psignn_plan_t* p, const float* W, int nl, int layer, int which, const float* h,
@@ -433,10 +416,6 @@ extern "C" int psignn_phi(const psignn_plan_t* p, const float* W, int nl, int la
 }
 
 #if PSIGNN_D == 10   // derivatives exist at the default width only: a width library (libpsignn_hip_d<w>.so) ends here
-int psignn_f_tile_jvp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* v,
-                      float* out, hipStream_t st);
-int psignn_f_layers_jvp_stateless(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* v,
-                                  float* out, float* work, float* lw, hipStream_t st);
 
 // Layer l of a dirichlet block on the gather kernels (caller numbering): its value at h (v == NULL; h0 = h_initial's
 // Dirichlet rows) or its tangent along v.  LayerNorm on the last layer only.
@@ -481,21 +460,12 @@ extern "C" int psignn_f_jvp(const psignn_plan_t* p, const float* W, int nl, cons
   float* lw = layers ? work + psignn_f_workspace_floats(p) : nullptr;
   KNOB_INT(mixed_tiled, [] { const char* e = getenv("PSIGNN_MIXED_JVP"); return (int)!(e && strcmp(e, "gather") == 0); }());
   if (p->tiled && (p->mixed ? mixed_tiled : 1)) {  // caller numbering -> plan order -> tiled kernel -> caller numbering
-    const int64_t N = p->N;
-    const int P = p->mixed ? 3 : 2;
-    float* hp = work;
-    float* vp = hp + N * D;
-    float* op = vp + N * D;
-    float* pp = op + N * D;  // (N, P)
-    float* np = pp + N * 3;  // (N, 2) unit normals of a mixed plan
-    if ((rc = psignn_plan_permute(p, h, D, hp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, v, D, vp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, prb, P, pp, 1, stream))) return rc;
-    if (p->mixed && (rc = psignn_plan_permute(p, nrm, 2, np, 1, stream))) return rc;
-    if (layers) rc = psignn_f_layers_jvp_stateless(p, W, nl, hp, pp, vp, op, nullptr, lw, st);   // tile kernels: no scratch
-    else rc = psignn_f_tile_jvp(p, W, nl, hp, pp, p->mixed ? np : nullptr, vp, op, st);
+    ws::Adapter a = ws::f_adapter(p->N, false, work);
+    if ((rc = psignn_to_plan(p, h, v, prb, nrm, a, st))) return rc;
+    if (layers) rc = psignn_f_layers_jvp_stateless(p, W, nl, a.h, a.prb, a.x, a.out, nullptr, lw, st);   // tile kernels: no scratch
+    else rc = psignn_f_tile_jvp(p, W, nl, a.h, a.prb, a.nrm, a.x, a.out, st);
     if (rc) return rc;
-    return psignn_plan_permute(p, op, D, out, 0, stream);
+    return psignn_from_plan(p, a.out, out, st);
   }
   if (layers) return psignn_f_layers_jvp_stateless(p, W, nl, h, prb, v, out, work, lw, st);
   if (p->mixed)

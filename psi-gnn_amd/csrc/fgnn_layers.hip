@@ -15,32 +15,14 @@
 // fixed point -- each state a solver, the implicit backward or a training step differentiates at.
 // Every step is a gather kernel or a tile kernel with a fixed walk order: no atomics, bitwise reproducible.
 #include "fgnn_common.h"
+#include "internal.h"
 
-int psignn_f_tile_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* h0, const float* prb,
-                        float* out, hipStream_t st);
-int psignn_f_gather_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* h0,
-                          const float* prb, const float* v, float* out, float* work, hipStream_t st);
-int psignn_f_tile_jvp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
-                            const float* v, float* out, hipStream_t st);
-int psignn_f_tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb, const float* w,
-                            float* out, float* work, float* rec, hipStream_t st);
-int psignn_f_gather_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
-                              const float* w, float* out, float* work, hipStream_t st);
-
-// Layer workspace, in (N, 10) slots: the states h_1..h_{L-1}, then slots the chains carry between layers -- the JVP / VJP use
-// two, the parameter VJP three (+ the h_initial cotangent in plan order), the backward of the VJP 3L + 1 (the cotangents
-// w_1..w_{L-1}, the tangents gbar_1..gbar_{L-1}, the direct terms c_0..c_{L-1}, two carried cotangents, one product) --
-// followed by a single-layer view of the weights (LAYER_VIEW floats, psignn_f_layer_view).
-#define LAYER_VIEW 4096
-static_assert(WLayout<3>::base_total(1, true) <= LAYER_VIEW, "single-layer weight view");
+// Layer workspace (ws::LayerWork): the states h_1..h_{L-1}, the rows the chains carry between layers, and a single-layer view of
+// the weights (psignn_f_layer_view).
+static_assert(WLayout<3>::base_total(1, true) <= ws::LAYER_VIEW, "single-layer weight view");
 extern "C" int64_t psignn_f_layers_workspace_floats(const psignn_plan_t* p, int n_layers) {
   if (!p || n_layers < 1 || n_layers > 64) return -1;
-  if (n_layers == 1) return 0;
-  if (p->mixed) return LAYER_VIEW;   // a mixed block differentiates its last layer only: one weight view
-  return (int64_t)(4 * n_layers + 1) * p->N * D + LAYER_VIEW;
-}
-float* psignn_f_layer_view_slot(const psignn_plan* p, int nl, float* lw) {
-  return p->mixed ? lw : lw + (int64_t)(4 * nl + 1) * p->N * D;
+  return ws::layer_work(p->N, n_layers, p->mixed, nullptr).total;
 }
 
 // dst <- the single-layer weights of layer l in the base layout ([shared | layer l | mixed: phi_neumann, update_neumann, fold]):
@@ -93,10 +75,10 @@ int psignn_f_add_rows(const psignn_plan* p, const float* a, const float* b, floa
 int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
                           hipStream_t st, bool gather) {
   ARG_CHECK(p && !p->mixed && nl > 1 && lw, "layer states: multi-layer dirichlet blocks");
-  const int64_t ND = p->N * D;
+  const ws::LayerWork L = ws::layer_work(p->N, nl, false, lw);
   const float* cur = h;
   for (int l = 0; l + 1 < nl; ++l) {
-    float* dst = lw + l * ND;
+    float* dst = L.state(l + 1);
     int rc = (p->tiled && !gather) ? psignn_f_tile_layer(p, W, nl, l, cur, h, prb, dst, st)
                                    : psignn_f_gather_layer(p, W, nl, l, cur, h, prb, nullptr, dst, work, st);
     if (rc) return rc;
@@ -109,12 +91,11 @@ int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const fl
 // kernels that run (plan order on tiled plans)
 int psignn_f_layers_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w, float* out,
                         float* work, float* lw, hipStream_t st) {
-  const int64_t ND = p->N * D;
-  float* tb[2] = {lw + (nl - 1) * ND, lw + nl * ND};
+  const ws::LayerWork L = ws::layer_work(p->N, nl, false, lw);
   const float* cur = w;
   for (int k = nl - 1; k >= 0; --k) {
-    const float* hk = k == 0 ? h : lw + (k - 1) * ND;
-    float* dst = k == 0 ? out : tb[(nl - 1 - k) & 1];
+    const float* hk = k == 0 ? h : L.state(k);
+    float* dst = k == 0 ? out : L.tb[(nl - 1 - k) & 1];
     int rc = p->tiled ? psignn_f_tile_vjp_layer(p, W, nl, k, hk, prb, cur, dst, work, nullptr, st)
                       : psignn_f_gather_vjp_layer(p, W, nl, k, hk, prb, cur, dst, work, st);
     if (rc) return rc;
@@ -126,12 +107,11 @@ int psignn_f_layers_vjp(const psignn_plan* p, const float* W, int nl, const floa
 // out = J_f(h) v, layer states in lw
 int psignn_f_layers_jvp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* v, float* out,
                         float* work, float* lw, hipStream_t st) {
-  const int64_t ND = p->N * D;
-  float* tb[2] = {lw + (nl - 1) * ND, lw + nl * ND};
+  const ws::LayerWork L = ws::layer_work(p->N, nl, false, lw);
   const float* cur = v;
   for (int k = 0; k < nl; ++k) {
-    const float* hk = k == 0 ? h : lw + (k - 1) * ND;
-    float* dst = k == nl - 1 ? out : tb[k & 1];
+    const float* hk = k == 0 ? h : L.state(k);
+    float* dst = k == nl - 1 ? out : L.tb[k & 1];
     int rc = p->tiled ? psignn_f_tile_jvp_layer(p, W, nl, k, hk, prb, cur, dst, st)
                       : psignn_f_gather_layer(p, W, nl, k, hk, hk, prb, cur, dst, work, st);
     if (rc) return rc;
@@ -140,8 +120,8 @@ int psignn_f_layers_jvp(const psignn_plan* p, const float* W, int nl, const floa
   return PSIGNN_OK;
 }
 
-// Stateless forms (evaluate the layer states, then the chain).  lw = work + psignn_f_workspace_floats(plan): a caller of a
-// multi-layer dirichlet derivative passes psignn_f_workspace_floats + psignn_f_layers_workspace_floats floats of work.
+// Stateless forms (evaluate the layer states, then the chain).  lw: the layer workspace, which a caller of a multi-layer
+// dirichlet derivative appends to the entry point's own workspace.
 int psignn_f_layers_vjp_stateless(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w,
                                   float* out, float* work, float* lw, hipStream_t st) {
   int rc = psignn_f_layer_states(p, W, nl, h, prb, lw, work, st, false);
@@ -151,4 +131,23 @@ int psignn_f_layers_jvp_stateless(const psignn_plan* p, const float* W, int nl, 
                                   float* out, float* work, float* lw, hipStream_t st) {
   int rc = psignn_f_layer_states(p, W, nl, h, prb, lw, work, st, false);
   return rc ? rc : psignn_f_layers_jvp(p, W, nl, h, prb, v, out, work, lw, st);
+}
+
+// ---- the operator of an adjoint solve (internal.h)
+int AdjointOp::setup(const psignn_plan* p_, const float* W_, int nl_, const float* h_star, const float* prb_, const float* nrm_,
+                     const float* grad_, ws::Adapter rows, float* fwork_, float* lwork_, hipStream_t st_) {
+  p = p_; W = W_; nl = nl_; fwork = fwork_; lwork = lwork_; st = st_;
+  tiled = p->tiled;
+  layers = !p->mixed && nl > 1;
+  h = h_star; prb = prb_; nrm = nrm_; grad = grad_;
+  int rc;
+  if (tiled) {
+    if ((rc = psignn_to_plan(p, h_star, grad_, prb_, nrm_, rows, st))) return rc;
+    h = rows.h; grad = rows.x; prb = rows.prb; nrm = rows.nrm;
+  }
+  return layers ? psignn_f_layer_states(p, W, nl, h, prb, lwork, fwork, st, false) : PSIGNN_OK;
+}
+int AdjointOp::operator()(const float* y, float* out) const {
+  if (layers) return psignn_f_layers_vjp(p, W, nl, h, prb, y, out, fwork, lwork, st);
+  return tiled ? psignn_f_vjp_p(p, W, nl, h, prb, nrm, y, out, fwork, st) : psignn_f_vjp(p, W, nl, h, prb, nrm, y, out, fwork, st);
 }

@@ -14,15 +14,12 @@
 //   3. k_pgrad_reduce: sum of the per-block partial tiles (fp64) and scatter into the flat gradient, laid out like
 //      the base section of the packed weights (WLayout: shared | phi_to | phi_from | update).
 #include "fgnn_common.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <string.h>
 
-#define PGREC 320
 #define PG_TILES 16
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-int psignn_f_tile_vjp_rec(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
-                          const float* w, float* out, float* work, float* rec, hipStream_t st);
 
 // Record tables: accumulator tile t = (A group, B group) of the record; A group -1 = the constant row (column sums).
 struct TabF {  // f_theta: 20 groups (layout in k_vjp_tile_a), 16 tiles
@@ -52,6 +49,8 @@ struct TabM {  // two-layer MLP: groups {x|1, hid|1, d hid, d y}, tiles (d hid) 
   __host__ __device__ static constexpr int a(int t) { return t == 0 ? 2 : 3; }
   __host__ __device__ static constexpr int b(int t) { return t == 0 ? 0 : 1; }
 };
+static_assert(TabF::NG * 16 == ws::REC_F && TabF::NT == ws::NT_F && ws::PGREC == ws::REC_F && TabX::NG * 16 == ws::REC_X &&
+              TabX::NT == ws::NT_X && TabM::NG * 16 == ws::REC_M && TabM::NT == ws::NT_M, "record sizes of workspace.h");
 
 template <class Tab>
 __global__ __launch_bounds__(256) void k_pgrad_outer(int64_t N, int nodes_per_wave, const float* __restrict__ rec,
@@ -240,7 +239,17 @@ __global__ __launch_bounds__(256) void k_pgrad_reduce_acc(int nblk, int nt, cons
   if (sub == 0 && off >= 0) grad[off] += (float)s;
 }
 
-static inline int pgrad_blocks(int64_t N, int* nodes_per_wave);
+using ws::pgrad_blocks;
+
+// records of n_rec nodes -> the flat gradient: the MFMA outer products, then the fp64 sum of the partial tiles (ws::pg_part of them)
+template <class Tab, class Map>
+static void pg_reduce(int64_t n_rec, const float* rec, float* part, float* grad, hipStream_t st, Map map = Map(),
+                      const char* outer = "k_pgrad_outer", const char* reduce = "k_pgrad_reduce") {
+  int npw;
+  const int nblk = pgrad_blocks(n_rec, &npw);
+  LAUNCH(outer, st, (k_pgrad_outer<Tab><<<nblk, 256, 0, st>>>(n_rec, npw, rec, part)));
+  LAUNCH(reduce, st, (k_pgrad_reduce<<<Tab::NT * 8, 256, 0, st>>>(Tab::NT <= 16 ? nblk : nblk * 4, Tab::NT, part, grad, map)));
+}
 
 // records of n_rec nodes -> layer l's section of the flat gradient (shift = l * LAYER_SZ): dirichlet, added to it (the layers
 // of a multi-layer block in turn); mixed, written (only the last layer acts)
@@ -259,104 +268,66 @@ static void pg_reduce_layer(const psignn_plan* p, int64_t n_rec, const float* re
   }
 }
 
-static inline int pgrad_blocks(int64_t N, int* nodes_per_wave) {
-  // a wave owns >= 64 nodes (multiple of 4); at most 1024 blocks of 4 waves
-  int64_t npw = std::max<int64_t>(64, cdiv(cdiv(N, (int64_t)4096), (int64_t)4) * 4);
-  *nodes_per_wave = (int)npw;
-  return (int)cdiv(N, npw * 4);
-}
-
-int psignn_f_gather_vjp_rec(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
-                            const float* w, float* out, float* work, float* rec, hipStream_t st);
-int psignn_f_gather_vjp_rec_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
-                                  const float* nrm, const float* w, float* out, float* work, float* rec, hipStream_t st);
-int psignn_f_tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb, const float* w,
-                            float* out, float* work, float* rec, hipStream_t st);
-int psignn_f_gather_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
-                              const float* w, float* out, float* work, hipStream_t st);
-int psignn_f_gather_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* h0,
-                          const float* prb, const float* v, float* out, float* work, hipStream_t st);
-int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
-                          hipStream_t st, bool gather);
-int psignn_f_layer_view(const psignn_plan* p, const float* W, int nl, int l, float* dst, hipStream_t st);
-float* psignn_f_layer_view_slot(const psignn_plan* p, int nl, float* lw);
-int psignn_f_dir_acc(const psignn_plan* p, const uint8_t* flags, const float* src, float* dst, int first, hipStream_t st);
-int psignn_f_add_rows(const psignn_plan* p, const float* a, const float* b, float* out, hipStream_t st);
-
 // Parameter VJP of a multi-layer dirichlet block (n_layers = L > 1): w_L = w, and for k = L-1 .. 0 the single-layer record pass
 // of layer k at (h_k, w_{k+1}) gives w_k = J_k^T w_{k+1} and layer k's records, reduced into layer k's section (alpha, shared,
 // accumulates over the layers in this fixed order; laynorm's records are zero except on the last layer).  d_init (optional):
 // the h_initial cotangent, the Dirichlet rows of w_L, ..., w_1 (the rows every layer copies from h_initial).  tiles: every
-// tensor in plan order, tile kernels; otherwise the caller's order and the gather kernels.  work: >= N * (90 + 320) floats +
-// the partial tiles; lw: psignn_f_layers_workspace_floats(p, L) floats.
+// tensor in plan order, tile kernels; otherwise the caller's order and the gather kernels.  v: the scratch | records | partial
+// tiles of the pass (ws::pv_work with 9 scratch rows); lw: psignn_f_layers_workspace_floats(p, L) floats.
 static int param_vjp_layers(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w,
-                            float* d_grad, float* d_out_h, float* d_init, float* work, float* lw, bool tiles, hipStream_t st) {
+                            float* d_grad, float* d_out_h, float* d_init, const ws::RecWork& v, float* lw, bool tiles,
+                            hipStream_t st) {
   using L = WLayout<2>;
-  const int64_t N = p->N, ND = N * D;
-  float* scratch = work;                 // tiles: B (N, 40); gather: Pj + B (N, 60)
-  float* rec = work + N * 9 * D;
-  float* part = rec + N * PGREC;
+  const int64_t N = p->N;
+  const ws::LayerWork lay = ws::layer_work(N, nl, false, lw);
   const uint8_t* flags = tiles ? p->flags_p : p->flags;
-  int rc = psignn_f_layer_states(p, W, nl, h, prb, lw, scratch, st, !tiles);
+  int rc = psignn_f_layer_states(p, W, nl, h, prb, lw, v.scratch, st, !tiles);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)L::base_total(nl, false) * 4, st));
-  float* tb[2] = {lw + (nl - 1) * ND, lw + nl * ND};
   const float* cur = w;
   for (int k = nl - 1; k >= 0; --k) {
     if (d_init && (rc = psignn_f_dir_acc(p, flags, cur, d_init, k == nl - 1, st))) return rc;
-    const float* hk = k == 0 ? h : lw + (k - 1) * ND;
-    float* dst = k == 0 ? d_out_h : tb[(nl - 1 - k) & 1];
-    rc = tiles ? psignn_f_tile_vjp_layer(p, W, nl, k, hk, prb, cur, dst, scratch, rec, st)
-               : psignn_f_gather_vjp_rec_layer(p, W, nl, k, hk, prb, nullptr, cur, dst, scratch, rec, st);
+    const float* hk = k == 0 ? h : lay.state(k);
+    float* dst = k == 0 ? d_out_h : lay.tb[(nl - 1 - k) & 1];
+    rc = tiles ? psignn_f_tile_vjp_layer(p, W, nl, k, hk, prb, cur, dst, v.scratch, v.rec, st)
+               : psignn_f_gather_vjp_rec_layer(p, W, nl, k, hk, prb, nullptr, cur, dst, v.scratch, v.rec, st);
     if (rc) return rc;
-    pg_reduce_layer(p, N, rec, part, d_grad, k * L::LAYER_SZ, st);
+    pg_reduce_layer(p, N, v.rec, v.part, d_grad, k * L::LAYER_SZ, st);
     cur = dst;
   }
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
 
-extern "C" int64_t psignn_f_param_vjp_workspace_floats(const psignn_plan_t* p) {
-  if (!p) return 0;
-  int npw;
-  const int nblk = pgrad_blocks(p->N, &npw);
-  // VJP scratch (<= N * 90) + plan-order copies (<= N * 36) + records (N * 480 mixed) + partial tiles (per wave for mixed)
-  return p->N * (9 * D + 36 + TabX::NG * 16) + (int64_t)nblk * 4 * TabX::NT * 256;
-}
+extern "C" int64_t psignn_f_param_vjp_workspace_floats(const psignn_plan_t* p) { return p ? ws::pv_total(p->N) : 0; }
 
 extern "C" int64_t psignn_param_grad_size(int mixed, int nl) {
   return mixed ? WLayout<3>::base_total(nl, true) : WLayout<2>::base_total(nl, false);
 }
 
-// Tiled plans of both families, everything in PLAN order: the tiled VJP kernels in record mode, then the MFMA reduction of the
-// records (dirichlet: 20 groups, 16 tiles; mixed: 30 groups, 24 tiles -- the Neumann factors of fgnn_vjp.hip's PgRec).
-static int param_vjp_tiled(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
-                           const float* w, float* d_grad, float* d_out_h, float* work, hipStream_t st) {
-  const int64_t N = p->N;
-  float* B = work;
-  float* rec = B + N * 4 * D;
-  int npw;
-  const int nblk = pgrad_blocks(N, &npw);
-  int rc = psignn_f_tile_vjp_rec(p, W, nl, h, prb, nrm, w, d_out_h, B, rec, st);
-  if (rc) return rc;
+// The records of one single-layer pass (n_rec = N; the backward of the VJP: 2 N) -> the flat gradient, zeroed first.  Dirichlet:
+// 20 groups, 16 tiles; mixed: 30 groups, 24 tiles (the Neumann factors of fgnn_vjp.hip's PgRec), and of a multi-layer block the
+// last layer acts alone (mixed/psignn/model.py:221-245): its section, the earlier layers stay zero.
+static int pg_reduce_block(const psignn_plan* p, int nl, int64_t n_rec, const float* rec, float* part, float* d_grad,
+                           hipStream_t st) {
   if (p->mixed) {
-    float* part = rec + N * TabX::NG * 16;
     HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<3>::base_total(nl, true) * 4, st));
-    if (nl > 1) {   // the last layer acts alone (mixed/psignn/model.py:221-245): its section, the earlier layers stay zero
-      pg_reduce_layer(p, N, rec, part, d_grad, (nl - 1) * WLayout<3>::LAYER_SZ, st);
-      HIP_TRY(hipGetLastError());
-      return PSIGNN_OK;
-    }
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabX><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabX::NT * 8, 256, 0, st>>>(nblk * 4, TabX::NT, part, d_grad, MapX())));
+    if (nl > 1) pg_reduce_layer(p, n_rec, rec, part, d_grad, (nl - 1) * WLayout<3>::LAYER_SZ, st);
+    else pg_reduce<TabX, MapX>(n_rec, rec, part, d_grad, st);
   } else {
-    float* part = rec + N * PGREC;
     HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<2>::base_total(nl, false) * 4, st));
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabF><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabF::NT * 8, 256, 0, st>>>(nblk, TabF::NT, part, d_grad, MapF())));
+    pg_reduce<TabF, MapF>(n_rec, rec, part, d_grad, st);
   }
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
+}
+
+// Tiled plans of both families, everything in PLAN order: the tiled VJP kernels in record mode, then the MFMA reduction of the
+// records.  v: ws::pv_work with 4 scratch rows (the tile VJP's B).
+static int param_vjp_tiled(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
+                           const float* w, float* d_grad, float* d_out_h, const ws::RecWork& v, hipStream_t st) {
+  int rc = psignn_f_tile_vjp_rec(p, W, nl, h, prb, nrm, w, d_out_h, v.scratch, v.rec, st);
+  return rc ? rc : pg_reduce_block(p, nl, p->N, v.rec, v.part, d_grad, st);
 }
 
 // h, prb, w in PLAN order.  d_grad: psignn_param_grad_size floats (fold slots left zero); d_out_h: (N, 10) = w^T df/dh.
@@ -365,15 +336,14 @@ extern "C" int psignn_f_param_vjp_p(const psignn_plan_t* p, const float* W, int 
   ARG_CHECK(p && W && h && prb && w && d_grad && d_out_h && work, "NULL argument");
   ARG_CHECK(p->tiled && !p->mixed && nl >= 1 && nl <= 64,
             "plan-order parameter gradients: tiled dirichlet plans (mixed plans: psignn_f_param_vjp, which takes the normals)");
+  const int64_t total = ws::pv_total(p->N);
   if (nl > 1)   // work: psignn_f_param_vjp_workspace_floats + psignn_f_layers_workspace_floats
-    return param_vjp_layers(p, W, nl, h, prb, w, d_grad, d_out_h, nullptr, work, work + psignn_f_param_vjp_workspace_floats(p),
+    return param_vjp_layers(p, W, nl, h, prb, w, d_grad, d_out_h, nullptr, ws::pv_work(p->N, false, 9, work, total), work + total,
                             true, (hipStream_t)stream);
-  return param_vjp_tiled(p, W, nl, h, prb, nullptr, w, d_grad, d_out_h, work, (hipStream_t)stream);
+  return param_vjp_tiled(p, W, nl, h, prb, nullptr, w, d_grad, d_out_h, ws::pv_work(p->N, false, 4, work, total), (hipStream_t)stream);
 }
 
 // ---- backward of the VJP (the Jacobian regulariser's gradient; kernels and derivation in gather_backward.hip)
-int psignn_jacreg_records(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* nrm,
-                          const float* v, const float* gbar, float* out_h, float* work, float* rec, hipStream_t st, int ln);
 
 // Backward of the VJP of a multi-layer dirichlet block (caller's numbering, gather kernels).  phi = gbar . (J^T v) with
 // J = J_{L-1} ... J_0:  w_L = v, w_k = J_k^T w_{k+1};  gbar_0 = gbar, gbar_{k+1} = J_k gbar_k.
@@ -381,61 +351,48 @@ int psignn_jacreg_records(const psignn_plan* p, const float* W, const float* h, 
 //      single-layer weight view of layer k -> layer k's parameter terms and c_k = d/dh_k with h_k held;
 //   2. back through the forward chain: a_{L-1} = c_{L-1}, a_k = c_k + J_k^T a_{k+1} with layer k's parameter-VJP terms at
 //      (h_k, a_{k+1});  d phi / d h = a_0.
-// Layer workspace slots: states (L-1) | w_1..w_{L-1} | gbar_1..gbar_{L-1} | c_0..c_{L-1} | two carried a | one product.
+// Layer workspace: ws::LayerWork's second reading (states | w_k | gbar_k | c_k | two carried a | one product).
 static int vjp_backward_layers(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* v,
-                               const float* gbar, float* d_grad, float* d_grad_h, float* work, float* lw, hipStream_t st) {
+                               const float* gbar, float* d_grad, float* d_grad_h, const ws::JrWork& jw, float* lw, hipStream_t st) {
   using L = WLayout<2>;
-  const int64_t N = p->N, ND = N * D;
-  float* S = lw;
-  float* Wc = S + (nl - 1) * ND;
-  float* G = Wc + (nl - 1) * ND;
-  float* C = G + (nl - 1) * ND;
-  float* A = C + nl * ND;
-  float* T = A + 2 * ND;
-  float* view = psignn_f_layer_view_slot(p, nl, lw);
-  float* rec = work + N * 17 * D;
-  float* part2 = rec + 2 * N * PGREC;   // after the two record sets of the double backward
-  float* part1 = rec + N * PGREC;       // after the one record set of a parameter-VJP pass
-  auto s_ = [&](int k) -> const float* { return k == 0 ? h : S + (k - 1) * ND; };
+  const ws::LayerWork lay = ws::layer_work(p->N, nl, false, lw);
+  const int64_t N = p->N;
+  float *S = lay.S, *Wc = lay.Wc, *G = lay.G, *C = lay.C, *A = lay.A, *T = lay.T, *view = lay.view;
+  float *work = jw.scratch, *rec = jw.rec1, *part2 = jw.part2, *part1 = jw.part1;   // rec: both record sets, or the first alone
+  auto s_ = [&](int k) -> const float* { return k == 0 ? h : lay.state(k); };
   int rc = psignn_f_layer_states(p, W, nl, h, prb, S, work, st, true);
   if (rc) return rc;
   const float* cur = v;
   for (int k = nl - 1; k >= 1; --k) {
-    if ((rc = psignn_f_gather_vjp_layer(p, W, nl, k, s_(k), prb, cur, Wc + (k - 1) * ND, work, st))) return rc;
-    cur = Wc + (k - 1) * ND;
+    if ((rc = psignn_f_gather_vjp_layer(p, W, nl, k, s_(k), prb, cur, lay.row(Wc, k - 1), work, st))) return rc;
+    cur = lay.row(Wc, k - 1);
   }
   cur = gbar;
   for (int k = 0; k + 1 < nl; ++k) {
-    if ((rc = psignn_f_gather_layer(p, W, nl, k, s_(k), s_(k), prb, cur, G + k * ND, work, st))) return rc;
-    cur = G + k * ND;
+    if ((rc = psignn_f_gather_layer(p, W, nl, k, s_(k), s_(k), prb, cur, lay.row(G, k), work, st))) return rc;
+    cur = lay.row(G, k);
   }
   HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)L::base_total(nl, false) * 4, st));
   for (int k = 0; k < nl; ++k) {
     if ((rc = psignn_f_layer_view(p, W, nl, k, view, st))) return rc;
-    const float* wk1 = k == nl - 1 ? v : Wc + k * ND;
-    const float* gk = k == 0 ? gbar : G + (k - 1) * ND;
-    if ((rc = psignn_jacreg_records(p, view, s_(k), prb, nullptr, wk1, gk, C + k * ND, work, rec, st, k == nl - 1))) return rc;
+    const float* wk1 = k == nl - 1 ? v : lay.row(Wc, k);
+    const float* gk = k == 0 ? gbar : lay.row(G, k - 1);
+    if ((rc = psignn_jacreg_records(p, view, s_(k), prb, nullptr, wk1, gk, lay.row(C, k), work, rec, jw.rec2, st, k == nl - 1))) return rc;
     pg_reduce_layer(p, 2 * N, rec, part2, d_grad, k * L::LAYER_SZ, st);
   }
-  const float* a = C + (nl - 1) * ND;
+  const float* a = lay.row(C, nl - 1);
   for (int k = nl - 2; k >= 0; --k) {
     if ((rc = psignn_f_gather_vjp_rec_layer(p, W, nl, k, s_(k), prb, nullptr, a, T, work, rec, st))) return rc;
     pg_reduce_layer(p, N, rec, part1, d_grad, k * L::LAYER_SZ, st);
-    float* dst = k == 0 ? d_grad_h : A + (k & 1) * ND;
-    if ((rc = psignn_f_add_rows(p, C + k * ND, T, dst, st))) return rc;
+    float* dst = k == 0 ? d_grad_h : lay.row(A, k & 1);
+    if ((rc = psignn_f_add_rows(p, lay.row(C, k), T, dst, st))) return rc;
     a = dst;
   }
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
 
-extern "C" int64_t psignn_f_vjp_backward_workspace_floats(const psignn_plan_t* p) {
-  if (!p) return 0;
-  int npw;
-  const int nblk = pgrad_blocks(2 * p->N, &npw);
-  // scratch (<= N * 170) + two records per node + partial tiles (per wave for the mixed family)
-  return p->N * (17 * D + 2 * TabX::NG * 16) + (int64_t)nblk * 4 * TabX::NT * 256;
-}
+extern "C" int64_t psignn_f_vjp_backward_workspace_floats(const psignn_plan_t* p) { return p ? ws::jr_work(p->N, true, false, nullptr).total : 0; }
 
 // Gradient of  phi = gbar . (J_f(h)^T v) = v^T J_f(h) gbar  (gbar constant) w.r.t. the parameters (d_grad, layout of
 // psignn_f_param_vjp) and w.r.t. h (d_grad_h): what autograd's double backward leaves after
@@ -448,53 +405,27 @@ extern "C" int psignn_f_vjp_backward(const psignn_plan_t* p, const float* W, int
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = p->N;
-  float* rec = work + N * 17 * D;
-  int npw;
-  const int nblk = pgrad_blocks(2 * N, &npw);
+  const ws::JrWork jw = ws::jr_work(N, p->mixed, false, work);
   // n_layers > 1: work holds psignn_f_vjp_backward_workspace_floats + psignn_f_layers_workspace_floats floats
-  float* lw = work + psignn_f_vjp_backward_workspace_floats(p);
-  if (nl > 1 && !p->mixed) return vjp_backward_layers(p, W, nl, h, prb, v, gbar, d_grad, d_grad_h, work, lw, st);
+  float* lw = work + jw.total;
+  if (nl > 1 && !p->mixed) return vjp_backward_layers(p, W, nl, h, prb, v, gbar, d_grad, d_grad_h, jw, lw, st);
   int rc;
   if (nl > 1) {   // mixed: the last layer acts alone -> the single-layer form on a view of it, into its section
-    float* view = psignn_f_layer_view_slot(p, nl, lw);
+    float* view = ws::layer_work(N, nl, true, lw).view;
     if ((rc = psignn_f_layer_view(p, W, nl, nl - 1, view, st))) return rc;
-    if ((rc = psignn_jacreg_records(p, view, h, prb, nrm, v, gbar, d_grad_h, work, rec, st, 1))) return rc;
-    HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<3>::base_total(nl, true) * 4, st));
-    pg_reduce_layer(p, 2 * N, rec, rec + 2 * N * TabX::NG * 16, d_grad, (nl - 1) * WLayout<3>::LAYER_SZ, st);
-    HIP_TRY(hipGetLastError());
-    return PSIGNN_OK;
+    W = view;
   }
-  rc = psignn_jacreg_records(p, W, h, prb, nrm, v, gbar, d_grad_h, work, rec, st, 1);
-  if (rc) return rc;
-  if (p->mixed) {
-    float* part = rec + 2 * N * TabX::NG * 16;
-    HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<3>::base_total(nl, true) * 4, st));
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabX><<<nblk, 256, 0, st>>>(2 * N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabX::NT * 8, 256, 0, st>>>(nblk * 4, TabX::NT, part, d_grad, MapX())));
-  } else {
-    float* part = rec + 2 * N * TabF::NG * 16;
-    HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<2>::base_total(nl, false) * 4, st));
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabF><<<nblk, 256, 0, st>>>(2 * N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabF::NT * 8, 256, 0, st>>>(nblk, TabF::NT, part, d_grad, MapF())));
-  }
-  HIP_TRY(hipGetLastError());
-  return PSIGNN_OK;
+  if ((rc = psignn_jacreg_records(p, W, h, prb, nrm, v, gbar, d_grad_h, jw.scratch, jw.rec1, jw.rec2, st, 1))) return rc;
+  return pg_reduce_block(p, nl, 2 * N, jw.rec1, jw.part2, d_grad, st);
 }
 
 // ---- the same product on the tile structures, plan order (kernels in fgnn_tile_jr.hip): tiled plans of the dirichlet family,
 // single-layer block
-int psignn_jr_tiled_ok(const psignn_plan* p, int nl);
-int psignn_jr_tile_records(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* v,
-                           const float* gbar, float* out_h, float* B, float* rec, hipStream_t st);
 
 extern "C" int psignn_f_vjp_backward_tiled_ok(const psignn_plan_t* p, int nl) { return psignn_jr_tiled_ok(p, nl); }
 
 extern "C" int64_t psignn_f_vjp_backward_p_workspace_floats(const psignn_plan_t* p) {
-  if (!p) return 0;
-  int npw;
-  const int nblk = pgrad_blocks(2 * p->N, &npw);
-  // B rows (N * 60) + two records per node + partial tiles
-  return p->N * (6 * D + 2 * TabF::NG * 16) + (int64_t)nblk * TabF::NT * 256;
+  return p ? ws::jr_work(p->N, false, true, nullptr).total : 0;
 }
 
 // h, prb, v, gbar and d_grad_h in PLAN order; d_grad as psignn_f_vjp_backward's.  Two tile kernels and the reduction of the
@@ -506,19 +437,9 @@ extern "C" int psignn_f_vjp_backward_p(const psignn_plan_t* p, const float* W, i
   ARG_CHECK(psignn_jr_tiled_ok(p, nl),
             "plan-order backward of the VJP: tiled plans of the dirichlet family, single-layer block (psignn_f_vjp_backward otherwise)");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t N = p->N;
-  float* B = work;
-  float* rec = B + N * 6 * D;
-  float* part = rec + 2 * N * TabF::NG * 16;
-  int npw;
-  const int nblk = pgrad_blocks(2 * N, &npw);
-  int rc = psignn_jr_tile_records(p, W, h, prb, v, gbar, d_grad_h, B, rec, st);
-  if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<2>::base_total(nl, false) * 4, st));
-  LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabF><<<nblk, 256, 0, st>>>(2 * N, npw, rec, part)));
-  LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabF::NT * 8, 256, 0, st>>>(nblk, TabF::NT, part, d_grad, MapF())));
-  HIP_TRY(hipGetLastError());
-  return PSIGNN_OK;
+  const ws::JrWork jw = ws::jr_work(p->N, false, true, work);
+  int rc = psignn_jr_tile_records(p, W, h, prb, v, gbar, d_grad_h, jw.scratch, jw.rec1, st);
+  return rc ? rc : pg_reduce_block(p, nl, 2 * p->N, jw.rec1, jw.part2, d_grad, st);
 }
 
 // ---- DS-GPS: backward of one recurrent update (kernels in gather_backward.hip)
@@ -572,17 +493,13 @@ struct MapG {
   }
 };
 
-int psignn_dsgps_step_records(const psignn_plan* p, const float* Wf, const float* Wg, const float* h, const float* prb,
-                              const float* nrm, const float* w, float* out_h, float* work, float* rec, hipStream_t st);
-
 extern "C" int64_t psignn_dsgps_grad_size(int mixed) {
   return mixed ? WLayout<3>::base_total(1, true) + 3 * (D * (3 * D + 3) + D) : WLayout<2>::base_total(1, false) + 3 * (D * (3 * D + 2) + D);
 }
+static_assert(TabG::NG * 16 == ws::REC_G && TabG::NT == ws::NT_G && TabGX::NG * 16 == ws::REC_GX && TabGX::NT == ws::NT_GX,
+              "record sizes of workspace.h");
 extern "C" int64_t psignn_dsgps_step_backward_workspace_floats(const psignn_plan_t* p) {
-  if (!p) return 0;
-  int npw;
-  const int nblk = pgrad_blocks(p->N, &npw);
-  return p->N * (17 * D + TabGX::NG * 16) + (int64_t)nblk * 4 * TabGX::NT * 256;
+  return p ? ws::dsgps_bw_work(p->N, true, nullptr).total : 0;
 }
 
 // w^T (d h' / d theta) -> d_grad (psignn_dsgps_grad_size floats) and w^T (d h' / d h) -> d_out_h for one DS-GPS update
@@ -595,35 +512,21 @@ extern "C" int psignn_dsgps_step_backward(const psignn_plan_t* p, const float* d
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = p->N;
-  float* rec = work + N * 17 * D;
-  int npw;
-  const int nblk = pgrad_blocks(N, &npw);
-  int rc = psignn_dsgps_step_records(p, d_phi_weights, d_gate_weights, h, prb, nrm, w, d_out_h, work, rec, st);
+  const ws::RecWork v = ws::dsgps_bw_work(N, p->mixed, work);
+  int rc = psignn_dsgps_step_records(p, d_phi_weights, d_gate_weights, h, prb, nrm, w, d_out_h, v.scratch, v.rec, st);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)psignn_dsgps_grad_size(p->mixed) * 4, st));
-  if (p->mixed) {
-    float* part = rec + N * TabGX::NG * 16;
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabGX><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabGX::NT * 8, 256, 0, st>>>(nblk * 4, TabGX::NT, part, d_grad, MapG<3>())));
-  } else {
-    float* part = rec + N * TabG::NG * 16;
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabG><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabG::NT * 8, 256, 0, st>>>(nblk * 4, TabG::NT, part, d_grad, MapG<2>())));
-  }
+  if (p->mixed) pg_reduce<TabGX, MapG<3>>(N, v.rec, v.part, d_grad, st);
+  else pg_reduce<TabG, MapG<2>>(N, v.rec, v.part, d_grad, st);
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
 
 // ---- DSS: backward of one update (kernels in gather_backward.hip); gradient in the f_theta layout with three node inputs
-int psignn_dss_step_records(const psignn_plan* p, const float* Wf, float alpha, const float* h, const float* bp,
-                            const float* w, float* out_h, float* work, float* rec, hipStream_t st);
 
 extern "C" int64_t psignn_dss_grad_size(void) { return WLayout<3>::base_total(1, false); }
 extern "C" int64_t psignn_dss_step_backward_workspace_floats(const psignn_plan_t* p) {
-  if (!p) return 0;
-  int npw;
-  const int nblk = pgrad_blocks(p->N, &npw);
-  return p->N * (13 * D + PGREC) + (int64_t)nblk * TabF::NT * 256;
+  return p ? ws::dss_bw_work(p->N, nullptr).total : 0;
 }
 
 // w^T (d h' / d theta_t) -> d_grad (psignn_dss_grad_size floats: shared | phi_to{W1 (10x23: columns 20, 21 unused, 22 = the
@@ -635,16 +538,11 @@ extern "C" int psignn_dss_step_backward(const psignn_plan_t* p, const float* d_w
   ARG_CHECK(p && d_weights_t && h && bprime && w && d_grad && d_out_h && work, "NULL argument");
   ARG_CHECK(!p->mixed, "DSS plans carry no boundary-condition tags");
   hipStream_t st = (hipStream_t)stream;
-  const int64_t N = p->N;
-  float* rec = work + N * 13 * D;
-  float* part = rec + N * PGREC;
-  int npw;
-  const int nblk = pgrad_blocks(N, &npw);
-  int rc = psignn_dss_step_records(p, d_weights_t, alpha, h, bprime, w, d_out_h, work, rec, st);
+  const ws::RecWork v = ws::dss_bw_work(p->N, work);
+  int rc = psignn_dss_step_records(p, d_weights_t, alpha, h, bprime, w, d_out_h, v.scratch, v.rec, st);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)psignn_dss_grad_size() * 4, st));
-  LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabF><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
-  LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabF::NT * 8, 256, 0, st>>>(nblk, TabF::NT, part, d_grad, MapX())));
+  pg_reduce<TabF, MapX>(p->N, v.rec, v.part, d_grad, st);
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
@@ -709,11 +607,7 @@ __global__ __launch_bounds__(256) void k_mlp2_bwd(int64_t n, int din, int hid, i
     for (int i = 0; i < 4; ++i) q[a * 4 + i] = make_float4(g[a][4 * i], g[a][4 * i + 1], g[a][4 * i + 2], g[a][4 * i + 3]);
 }
 
-extern "C" int64_t psignn_mlp2_backward_workspace_floats(int64_t n) {
-  int npw;
-  const int nblk = pgrad_blocks(n, &npw);
-  return n * 64 + (int64_t)nblk * TabM::NT * 256;
-}
+extern "C" int64_t psignn_mlp2_backward_workspace_floats(int64_t n) { return ws::mlp2_bw_work(n, nullptr).total; }
 
 // d_gflat: [W1 (hid, din) | b1 (hid) | W2 (dout, hid) | b2 (dout)] gradients; d_gx (n, din) may be NULL.
 extern "C" int psignn_mlp2_backward(const float* x, const float* gy, int64_t n, int din, int hid, int dout, const float* w1,
@@ -724,13 +618,9 @@ extern "C" int psignn_mlp2_backward(const float* x, const float* gy, int64_t n, 
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(d_gflat, 0, (size_t)(hid * din + hid + dout * hid + dout) * 4, st));
   if (n == 0) return PSIGNN_OK;
-  float* rec = work;
-  float* part = rec + n * 64;
-  int npw;
-  const int nblk = pgrad_blocks(n, &npw);
-  LAUNCH("k_mlp2_bwd", st, (k_mlp2_bwd<<<(unsigned)cdiv(n, (int64_t)256), 256, 0, st>>>(n, din, hid, dout, x, gy, w1, b1, w2, d_gx, rec)));
-  LAUNCH("k_pgrad_outer_mlp", st, (k_pgrad_outer<TabM><<<nblk, 256, 0, st>>>(n, npw, rec, part)));
-  LAUNCH("k_pgrad_reduce_mlp", st, (k_pgrad_reduce<<<TabM::NT * 8, 256, 0, st>>>(nblk, TabM::NT, part, d_gflat, MapM{din, hid, dout})));
+  const ws::RecWork v = ws::mlp2_bw_work(n, work);
+  LAUNCH("k_mlp2_bwd", st, (k_mlp2_bwd<<<(unsigned)cdiv(n, (int64_t)256), 256, 0, st>>>(n, din, hid, dout, x, gy, w1, b1, w2, d_gx, v.rec)));
+  pg_reduce<TabM>(n, v.rec, v.part, d_gflat, st, MapM{din, hid, dout}, "k_pgrad_outer_mlp", "k_pgrad_reduce_mlp");
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
@@ -759,9 +649,6 @@ extern "C" int psignn_residual_t(const psignn_plan_t* p, const float* d_a_ij, co
   return PSIGNN_OK;
 }
 
-extern "C" int psignn_f_param_vjp_ex(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
-                                     const float* nrm, const float* w, float* d_grad, float* d_out_h, float* d_out_init,
-                                     float* work, void* stream);
 // Caller-order parameter-VJP for every plan: tiled plans of both families run the tiled kernels (permutation passes around
 // them; mixed family since round 3); untiled plans run the global-gather kernels in PG mode.  d_normals: mixed only.
 extern "C" int psignn_f_param_vjp(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
@@ -784,60 +671,30 @@ extern "C" int psignn_f_param_vjp_ex(const psignn_plan_t* p, const float* W, int
   const int64_t N = p->N;
   int rc;
   if (d_out_init && (p->mixed || nl == 1) && (rc = psignn_f_dir_acc(p, p->flags, w, d_out_init, 1, st))) return rc;
+  const int64_t total = ws::pv_total(N);
   if (nl > 1 && !p->mixed) {
-    float* lw = work + psignn_f_param_vjp_workspace_floats(p);
-    if (!p->tiled) return param_vjp_layers(p, W, nl, h, prb, w, d_grad, d_out_h, d_out_init, work, lw, false, st);
-    float* hp = work;
-    float* wp = hp + N * D;
-    float* op = wp + N * D;
-    float* pp = op + N * D;   // (N, 2)
-    float* rest = pp + N * 2;
-    float* ip = lw + (nl + 1) * N * D;   // the h_initial cotangent in plan order
-    if ((rc = psignn_plan_permute(p, h, D, hp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, w, D, wp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, prb, 2, pp, 1, stream))) return rc;
-    if ((rc = param_vjp_layers(p, W, nl, hp, pp, wp, d_grad, op, d_out_init ? ip : nullptr, rest, lw, true, st))) return rc;
-    if (d_out_init && (rc = psignn_plan_permute(p, ip, D, d_out_init, 0, stream))) return rc;
-    return psignn_plan_permute(p, op, D, d_out_h, 0, stream);
+    float* lw = work + total;
+    if (!p->tiled)
+      return param_vjp_layers(p, W, nl, h, prb, w, d_grad, d_out_h, d_out_init, ws::pv_work(N, false, 9, work, total), lw, false, st);
+    ws::Adapter a = ws::pv_adapter(N, false, work);
+    float* ip = ws::layer_work(N, nl, false, lw).init;   // the h_initial cotangent in plan order
+    if ((rc = psignn_to_plan(p, h, w, prb, nullptr, a, st))) return rc;
+    if ((rc = param_vjp_layers(p, W, nl, a.h, a.prb, a.x, d_grad, a.out, d_out_init ? ip : nullptr,
+                               ws::pv_work(N, false, 9, a.rest, a.rest_floats), lw, true, st)))
+      return rc;
+    if (d_out_init && (rc = psignn_from_plan(p, ip, d_out_init, st))) return rc;
+    return psignn_from_plan(p, a.out, d_out_h, st);
   }
   KNOB_INT(mixed_tiled, [] { const char* e = getenv("PSIGNN_MIXED_PGRAD"); return (int)!(e && strcmp(e, "gather") == 0); }());
   if (p->tiled && (!p->mixed || mixed_tiled)) {
-    const int P = p->mixed ? 3 : 2;
-    float* hp = work;
-    float* wp = hp + N * D;
-    float* op = wp + N * D;
-    float* pp = op + N * D;  // (N, 2 | 3)
-    float* np_ = pp + N * P; // (N, 2) unit normals, mixed plans
-    float* rest = np_ + (p->mixed ? N * 2 : 0);
-    rest += (4 - ((rest - work) & 3)) & 3;   // the VJP's B rows are read as float4
-    if ((rc = psignn_plan_permute(p, h, D, hp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, w, D, wp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, prb, P, pp, 1, stream))) return rc;
-    if (p->mixed && (rc = psignn_plan_permute(p, nrm, 2, np_, 1, stream))) return rc;
-    if ((rc = param_vjp_tiled(p, W, nl, hp, pp, p->mixed ? np_ : nullptr, wp, d_grad, op, rest, st))) return rc;
-    return psignn_plan_permute(p, op, D, d_out_h, 0, stream);
+    ws::Adapter a = ws::pv_adapter(N, p->mixed, work);
+    if ((rc = psignn_to_plan(p, h, w, prb, nrm, a, st))) return rc;
+    if ((rc = param_vjp_tiled(p, W, nl, a.h, a.prb, a.nrm, a.x, d_grad, a.out, ws::pv_work(N, p->mixed, 4, a.rest, a.rest_floats), st)))
+      return rc;
+    return psignn_from_plan(p, a.out, d_out_h, st);
   }
-  float* scratch = work;                      // Pj + B: N * 90 floats at most
-  float* rec = scratch + N * 9 * D;
-  int npw;
-  const int nblk = pgrad_blocks(N, &npw);
-  if ((rc = psignn_f_gather_vjp_rec(p, W, nl, h, prb, nrm, w, d_out_h, scratch, rec, st))) return rc;
-  if (p->mixed) {
-    float* part = rec + N * TabX::NG * 16;
-    HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<3>::base_total(nl, true) * 4, st));
-    if (nl > 1) {   // the last layer's section (mixed/psignn/model.py:221-245)
-      pg_reduce_layer(p, N, rec, part, d_grad, (nl - 1) * WLayout<3>::LAYER_SZ, st);
-      HIP_TRY(hipGetLastError());
-      return PSIGNN_OK;
-    }
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabX><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabX::NT * 8, 256, 0, st>>>(nblk * 4, TabX::NT, part, d_grad, MapX())));
-  } else {
-    float* part = rec + N * TabF::NG * 16;
-    HIP_TRY(hipMemsetAsync(d_grad, 0, (size_t)WLayout<2>::base_total(nl, false) * 4, st));
-    LAUNCH("k_pgrad_outer", st, (k_pgrad_outer<TabF><<<nblk, 256, 0, st>>>(N, npw, rec, part)));
-    LAUNCH("k_pgrad_reduce", st, (k_pgrad_reduce<<<TabF::NT * 8, 256, 0, st>>>(nblk, TabF::NT, part, d_grad, MapF())));
-  }
-  HIP_TRY(hipGetLastError());
-  return PSIGNN_OK;
+  const ws::RecWork v = ws::pv_work(N, p->mixed, 9, work, total);   // scratch: the gather VJP's Pj | B
+  // (the layer a single-layer pass differentiates: the last one of a mixed block)
+  if ((rc = psignn_f_gather_vjp_rec_layer(p, W, nl, p->mixed ? nl - 1 : 0, h, prb, nrm, w, d_out_h, v.scratch, v.rec, st))) return rc;
+  return pg_reduce_block(p, nl, N, v.rec, v.part, d_grad, st);
 }

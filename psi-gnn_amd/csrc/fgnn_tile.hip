@@ -16,6 +16,7 @@
 #define MV2_LAUNDER 2
 #define MV2_CH (100 / PSIGNN_D)   // at most ~100 weights of a block in flight: 10 inputs at D = 10, 6 at 16, the whole 8 x 8 block at 8
 #include "tile_helpers.h"
+#include "internal.h"
 // Occupancy caps were measured and removed (profiles/r2_f_tile_ab_runs.txt): k_f_tile held to 96 VGPRs ran plain f in 59.8 vs
 // 58.0 us, the fused instantiations held to 80 VGPRs for a sixth wave 89.6 vs 88.8 us, the batched kernel held to six waves 57.4
 // vs 50.7 us at 8 x 50k nodes.
@@ -740,7 +741,8 @@ int psignn_f_tile_forward(const psignn_plan* p, const float* W, int nl, const fl
     using L = WLayout<2>;
     size_t lds = (size_t)p->max_rows * TileRow<false>::RS * 4;
     ARG_CHECK(nl == 1 || work, "multi-layer evaluation needs a workspace");
-    float* pp[2] = {work, work ? work + p->N * D : nullptr};
+    const ws::FFwd ft = ws::f_fwd(p->N, true, work, 0);   // NULL without a workspace (single layer)
+    float* const* pp = ft.pp;
     const float* cur = h;
     for (int l = 0; l < nl; ++l) {
       float* dst = (l == nl - 1) ? out : pp[l & 1];

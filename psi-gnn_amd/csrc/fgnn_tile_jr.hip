@@ -22,6 +22,7 @@
 // The records are reduced by k_pgrad_outer<TabF> / k_pgrad_reduce (fgnn_pgrad.hip) over 2 N rows, unchanged.
 #include "tile_helpers.h"
 #include "jr_node.h"
+#include "internal.h"
 
 #define JR_REC 320   // floats per record (20 groups of 16)
 #define JR_RS 20     // pass A: floats per LDS row [Pj_to | Pj_from]

@@ -14,6 +14,7 @@
 // Phi_neumann columns, which tiles WITH Neumann nodes stage as 20 more floats per LDS row (tiles without run the 160-byte
 // form in a launch of their own, like k_f_tile).
 #include "tile_helpers.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -482,10 +483,6 @@ __global__ __launch_bounds__(TILE_THREADS) void k_jvp_tile(int n_tiles, int chun
 // h, prb, nrm (mixed plans), v, out in PLAN order.
 // groups (mixed plans): bit 0 = tiles without Neumann nodes, bit 1 = tiles holding Neumann nodes (fgnn_tile_lin.hip applies the
 // stored linearisation on the first group and this kernel on the second)
-int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
-                             const float* v, float* out, int groups, hipStream_t st);
-int psignn_f_tile_jvp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
-                            const float* v, float* out, hipStream_t st);
 int psignn_f_tile_jvp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
                       const float* v, float* out, hipStream_t st) {
   return psignn_f_tile_jvp_groups(p, W, nl, h, prb, nrm, v, out, 3, st);

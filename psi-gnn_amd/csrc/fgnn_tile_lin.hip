@@ -55,6 +55,7 @@
 // weight loads of mv2 pinned chunk by chunk (tile_helpers.h; A/B in profiles/r3_ab_mv2.txt: k_jvp_lin 53 -> 48.5 us)
 #define MV2_LAUNDER 2
 #include "tile_helpers.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -1053,9 +1054,6 @@ __global__ __launch_bounds__(256) void k_lin_tfill(int64_t n, const int2* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
-                             const float* v, float* out, int groups, hipStream_t st);
-
 // flag[tile] = 1: a Neumann row among the tile's own and halo rows (the transposed product's tile groups, once per handle)
 __global__ __launch_bounds__(64) void k_lin_vgroup(const TileCtx C, int32_t* __restrict__ flag) {
   const int tile = blockIdx.x;
@@ -1242,8 +1240,6 @@ extern "C" int psignn_lin_jvp(const psignn_lin_t* s, const float* W, int nl, con
 // call after a build also k_lin_tfill, on the first call of the handle k_lin_rev and the two transposed arrays).  Mixed plans: the
 // tiled VJP (psignn_f_tile_vjp, work = the plan workspace) at the state kept by the build; with the Neumann rows stored
 // (psignn_lin_create_opts) one k_vjp_lin_mixed launch over the handle's tile list, work ignored.
-int psignn_f_tile_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* w,
-                      float* out, float* work, hipStream_t st);
 
 // The transposed product's lazy work: on the first call of the handle the two transposed arrays and k_lin_rev, on the first call after a
 // build k_lin_tfill.  (The batched product runs it per handle in its prologue, never inside the lockstep loop.)

@@ -20,6 +20,7 @@
 // accumulates into a third sum, out[u] += W1j_neu^T acc_n.  A tile without Neumann rows among tile + halo skips all of it.
 // All tensors in plan order.  The parameter-gradient records (PG) exist for the dirichlet family only.
 #include "fgnn_common.h"
+#include "internal.h"
 
 #define SLOT_IN 0x10000u
 #define SLOT_OUT 0x20000u

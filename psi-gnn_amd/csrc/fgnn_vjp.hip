@@ -22,6 +22,7 @@
 // (mixed/psignn/model.py:236,241), so its cotangent flows through that branch only (Phi_neumann is of the
 // Phi_from type: out-edges of n; pass 2 adds acc_n over u's in-edges).
 #include "fgnn_common.h"
+#include "internal.h"
 #include <string.h>
 #include <stdlib.h>
 
@@ -570,8 +571,8 @@ static void launch_vjp(const psignn_plan* p, const float* W, int nl, const float
   const bool ln = MIXED || layer == nl - 1;
   const int lofs = L::layer(layer), nofs = L::phi_neu(nl), unofs = L::upd_neu(nl);
   const unsigned grid = (unsigned)cdiv(p->N, 256);
-  float* Pj = work;                            // (N, 20 | 30)
-  float* B = work + p->N * (MIXED ? 3 : 2) * D;  // (N, 40 | 60)
+  const ws::FVjp v = ws::f_vjp(p->N, MIXED, work, 0);   // Pj (N, 20 | 30) | B (N, 40 | 60)
+  float *Pj = v.Pj, *B = v.B;
   LAUNCH("k_vjp_project", st, (k_vjp_project<P, MIXED><<<grid, 256, 0, st>>>(p->N, W, lofs, nofs, h, Pj)));
   if (ln) {
     LAUNCH(PG ? "k_pgrad_local" : "k_vjp_local", st, (k_vjp_local<P, MIXED, PG><<<grid, 256, 0, st>>>(
@@ -589,17 +590,6 @@ static void launch_vjp(const psignn_plan* p, const float* W, int nl, const float
       p->N, W, lofs, nofs, p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr, Pj, B, out, rec)));
 }
 
-// global-gather VJP that also fills the parameter-gradient records (caller's numbering); work: N * 90 floats, rec: N * 320 | 480
-int psignn_f_gather_vjp_rec(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm,
-                            const float* w, float* out, float* work, float* rec, hipStream_t st) {
-  if (p->mixed)
-    launch_vjp<3, true, true>(p, W, nl, h, prb, nrm, w, out, work, st, rec);
-  else
-    launch_vjp<2, false, true>(p, W, nl, h, prb, nrm, w, out, work, st, rec);
-  HIP_TRY(hipGetLastError());
-  return PSIGNN_OK;
-}
-
 // layer l of a dirichlet block on the gather kernels (caller numbering), LayerNorm on the last layer only; work: N * 60 floats
 int psignn_f_gather_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
                               const float* w, float* out, float* work, hipStream_t st) {
@@ -609,7 +599,8 @@ int psignn_f_gather_vjp_layer(const psignn_plan* p, const float* W, int nl, int 
   return PSIGNN_OK;
 }
 
-// record mode of layer l (dirichlet: any layer, LayerNorm on the last only; mixed: l = nl - 1); work: N * 90 floats
+// global-gather VJP that also fills the parameter-gradient records (caller's numbering), at layer l (dirichlet: any layer,
+// LayerNorm on the last only; mixed: l = nl - 1); work: ws::f_vjp (N * 90 floats at most), rec: N * 320 | 480
 int psignn_f_gather_vjp_rec_layer(const psignn_plan* p, const float* W, int nl, int l, const float* h, const float* prb,
                                   const float* nrm, const float* w, float* out, float* work, float* rec, hipStream_t st) {
   ARG_CHECK(l >= 0 && l < nl && (!p->mixed || l == nl - 1), "gather VJP records: bad layer");
@@ -620,11 +611,6 @@ int psignn_f_gather_vjp_rec_layer(const psignn_plan* p, const float* W, int nl, 
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
-
-int psignn_f_tile_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* nrm, const float* w,
-                      float* out, float* work, hipStream_t st);
-int psignn_f_layers_vjp_stateless(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w,
-                                  float* out, float* work, float* lw, hipStream_t st);
 
 // plan-order VJP: tiled kernels where the plan has tiles, gather kernels otherwise.  Multi-layer dirichlet blocks chain the
 // single-layer VJPs (fgnn_layers.hip); their work holds psignn_f_workspace_floats + psignn_f_layers_workspace_floats floats.
@@ -652,23 +638,13 @@ extern "C" int psignn_f_vjp(const psignn_plan_t* p, const float* W, int nl, cons
   KNOB_INT(mixed_tiled, [] { const char* e = getenv("PSIGNN_MIXED_VJP"); return (int)!(e && strcmp(e, "gather") == 0); }());
   if (p->tiled && (p->mixed ? mixed_tiled : 1)) {
     // caller numbering -> plan order -> tiled kernels -> caller numbering
-    const int64_t N = p->N;
-    const int P = p->mixed ? 3 : 2;
-    float* Bw = work;                 // (N, 40)
-    float* hp = Bw + N * 4 * D;
-    float* wp = hp + N * D;
-    float* op = wp + N * D;
-    float* pp = op + N * D;           // (N, P)
-    float* np = pp + N * 3;           // (N, 2) unit normals of a mixed plan
+    ws::Adapter a = ws::f_adapter(p->N, true, work);
     int rc;
-    if ((rc = psignn_plan_permute(p, h, D, hp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, w, D, wp, 1, stream))) return rc;
-    if ((rc = psignn_plan_permute(p, prb, P, pp, 1, stream))) return rc;
-    if (p->mixed && (rc = psignn_plan_permute(p, nrm, 2, np, 1, stream))) return rc;
-    if (layers) rc = psignn_f_layers_vjp_stateless(p, W, nl, hp, pp, wp, op, Bw, lw, st);
-    else rc = psignn_f_tile_vjp(p, W, nl, hp, pp, p->mixed ? np : nullptr, wp, op, Bw, st);
+    if ((rc = psignn_to_plan(p, h, w, prb, nrm, a, st))) return rc;
+    if (layers) rc = psignn_f_layers_vjp_stateless(p, W, nl, a.h, a.prb, a.x, a.out, a.B, lw, st);
+    else rc = psignn_f_tile_vjp(p, W, nl, a.h, a.prb, a.nrm, a.x, a.out, a.B, st);
     if (rc) return rc;
-    return psignn_plan_permute(p, op, D, out, 0, stream);
+    return psignn_from_plan(p, a.out, out, st);
   }
   if (layers) return psignn_f_layers_vjp_stateless(p, W, nl, h, prb, w, out, work, lw, st);
   if (p->mixed)

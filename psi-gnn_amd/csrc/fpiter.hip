@@ -14,6 +14,7 @@
 // Picard: x <- f(x) with abs = |x - f(x)|, rel = abs / |f(x)| after every evaluation, stop when rel <= eps.
 // Reductions use fixed-shape partial sums in a fixed order: bitwise reproducible.
 #include "vec_helpers.h"
+#include "internal.h"
 #include <algorithm>
 #include <vector>
 
@@ -773,9 +774,6 @@ __global__ void k_fp_all_done_batch(const FpBatchDesc* __restrict__ descs, int n
     *all_done = a;
   }
 }
-
-int psignn_f_tile_plain_batch(const FpBatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed, int off_done,
-                              int in_f, int in_row, hipStream_t st);
 
 // 1 when psignn_anderson_solve_batch / psignn_picard_solve_batch take these handles and plans together: tiled plans of one family,
 // handle i made for a shard (psignn_fpiter_create_for_batch) and for the length of plans[i], one vector width, one history length, one

@@ -32,6 +32,7 @@
 // 236,241) -- piecewise linear up to LayerNorm, so its only second-order term is LayerNorm's; its factors go to the
 // record groups 20..29 of the mixed parameter-VJP (fgnn_vjp.hip PgRec).
 #include "jr_node.h"
+#include "workspace.h"
 
 #define PHASE() asm volatile("" ::: "memory")
 
@@ -55,6 +56,8 @@ struct JrDims {
   static constexpr int NB = MIXED ? 6 : 4;      // B row: Pt, Pf, dS_to, dS_fr [, Pn, dS_n]
   static constexpr int REC = MIXED ? 480 : 320;
 };
+static_assert(JrDims<true>::REC == ws::REC_X && JrDims<false>::REC == ws::REC_F && JrDims<true>::PJ == 6 * ws::W &&
+              JrDims<false>::PJ == 4 * ws::W && JrDims<true>::NB == 6 && JrDims<false>::NB == 4, "ws::jr_scratch / ws::JrWork");
 
 
 // neighbour-side projections of h (primal) and gbar (tangent): P[n] = { W1j_m h_n : m } { W1j_m gbar_n : m }
@@ -534,16 +537,12 @@ __global__ __launch_bounds__(256) void k_jr_edge_remote(int64_t N, const float* 
 
 template <int P, bool MIXED>
 static void jr_launch(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* nrm, const float* v,
-                      const float* gbar, float* out_h, float* work, float* rec, hipStream_t st, bool ln = true) {
+                      const float* gbar, float* out_h, float* work, float* rec1, float* rec2, hipStream_t st, bool ln = true) {
   using J = JrDims<MIXED>;
   const int64_t N = p->N;
   const unsigned grid = (unsigned)cdiv(N, 256);
-  float* Pb = work;
-  float* cb = Pb + N * J::PJ;
-  float* B = cb + N * 4 * D;
-  float* dir = B + N * J::NB * D;
-  float* rec1 = rec;
-  float* rec2 = rec + N * J::REC;
+  const ws::JrScratch sc = ws::jr_scratch(N, MIXED, work);
+  float *Pb = sc.P, *cb = sc.cb, *B = sc.B, *dir = sc.dir;
 #define JR_CSR p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr
   LAUNCH("k_jr_project", st, (k_jr_project<P, MIXED><<<grid, 256, 0, st>>>(N, W, h, gbar, Pb)));
   LAUNCH("k_jr_tangent", st, (k_jr_tangent<P, MIXED><<<grid, 256, 0, st>>>(N, W, JR_CSR, p->flags, h, gbar, Pb, cb, rec1, rec2)));
@@ -563,16 +562,17 @@ static void jr_launch(const psignn_plan* p, const float* W, const float* h, cons
 #undef JR_CSR
 }
 
-// work: P (N, 40 | 60) | cb (N, 40) | B (N, 40 | 60) | dir (N, 10)  (<= N * 170 floats);  rec: (2 N, 320 | 480) = R1 then R2;
+// work: ws::jr_scratch (<= N * 170 floats);  rec1, rec2: (N, 320 | 480) each, the two record sets (ws::JrWork);
 // out_h: (N, 10) = d phi / d h
 // ln = 0: the LayerNorm-off form (an intermediate layer of a multi-layer dirichlet block).  W: a single-layer weight view.
 int psignn_jacreg_records(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* nrm,
-                          const float* v, const float* gbar, float* out_h, float* work, float* rec, hipStream_t st, int ln) {
+                          const float* v, const float* gbar, float* out_h, float* work, float* rec1, float* rec2, hipStream_t st,
+                          int ln) {
   ARG_CHECK(ln || !p->mixed, "the LayerNorm-off backward of the VJP is a dirichlet-family form");
   if (p->mixed)
-    jr_launch<3, true>(p, W, h, prb, nrm, v, gbar, out_h, work, rec, st);
+    jr_launch<3, true>(p, W, h, prb, nrm, v, gbar, out_h, work, rec1, rec2, st);
   else
-    jr_launch<2, false>(p, W, h, prb, nrm, v, gbar, out_h, work, rec, st, ln != 0);
+    jr_launch<2, false>(p, W, h, prb, nrm, v, gbar, out_h, work, rec1, rec2, st, ln != 0);
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
@@ -772,13 +772,10 @@ __global__ __launch_bounds__(256) void k_ds_node_bwd(int64_t N, const float* __r
 template <int P, bool MIXED>
 static void ds_launch(const psignn_plan* p, const float* Wf, const float* Wg, const float* h, const float* prb, const float* nrm,
                       const float* w, float* out_h, float* work, float* rec, hipStream_t st) {
-  using J = JrDims<MIXED>;
   const int64_t N = p->N;
   const unsigned grid = (unsigned)cdiv(N, 256);
-  float* Pb = work;
-  float* cb = Pb + N * J::PJ;
-  float* B = cb + N * 4 * D;
-  float* dir = B + N * J::NB * D;
+  const ws::JrScratch sc = ws::jr_scratch(N, MIXED, work);
+  float *Pb = sc.P, *cb = sc.cb, *B = sc.B, *dir = sc.dir;
 #define JR_CSR p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr
   LAUNCH("k_jr_project", st, (k_jr_project<P, MIXED><<<grid, 256, 0, st>>>(N, Wf, h, h, Pb)));
   LAUNCH("k_ds_phi", st, (k_ds_phi<P, MIXED><<<grid, 256, 0, st>>>(N, Wf, JR_CSR, p->flags, h, Pb, cb, rec)));
@@ -788,7 +785,7 @@ static void ds_launch(const psignn_plan* p, const float* Wf, const float* Wg, co
 #undef JR_CSR
 }
 
-// work: P (N, 40 | 60) | cb (N, 40) | B (N, 40 | 60) | dir (N, 10);  rec: (N, 320 | 480);  out_h: (N, 10) = w^T d step / d h
+// work: ws::jr_scratch;  rec: (N, 320 | 480);  out_h: (N, 10) = w^T d step / d h
 int psignn_dsgps_step_records(const psignn_plan* p, const float* Wf, const float* Wg, const float* h, const float* prb,
                               const float* nrm, const float* w, float* out_h, float* work, float* rec, hipStream_t st) {
   if (p->mixed)
@@ -862,16 +859,13 @@ __global__ __launch_bounds__(256) void k_dss_node_bwd(int64_t N, const float* __
   jr_zero(r, 14, 16);
 }
 
-// work: P (N, 40) | cb (N, 40) | B (N, 40) | dir (N, 10);  rec: (N, 320);  out_h: (N, 10) = w^T d step / d h
+// work: ws::jr_scratch (dirichlet shape);  rec: (N, 320);  out_h: (N, 10) = w^T d step / d h
 int psignn_dss_step_records(const psignn_plan* p, const float* Wf, float alpha, const float* h, const float* bp,
                             const float* w, float* out_h, float* work, float* rec, hipStream_t st) {
-  using J = JrDims<false>;
   const int64_t N = p->N;
   const unsigned grid = (unsigned)cdiv(N, 256);
-  float* Pb = work;
-  float* cb = Pb + N * J::PJ;
-  float* B = cb + N * 4 * D;
-  float* dir = B + N * J::NB * D;
+  const ws::JrScratch sc = ws::jr_scratch(N, false, work);
+  float *Pb = sc.P, *cb = sc.cb, *B = sc.B, *dir = sc.dir;
 #define JR_CSR p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr
   LAUNCH("k_jr_project", st, (k_jr_project<3, false><<<grid, 256, 0, st>>>(N, Wf, h, h, Pb)));
   LAUNCH("k_ds_phi", st, (k_ds_phi<3, false><<<grid, 256, 0, st>>>(N, Wf, JR_CSR, p->flags, h, Pb, cb, rec)));

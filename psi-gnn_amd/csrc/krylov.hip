@@ -18,6 +18,7 @@
 //   scale       : v_{j+1} = w / |w|
 // = 2 (j + 1) + O(1) vector passes per step, 4 (j + 1) when the second pass runs.  Reductions: fixed-shape partial sums in a fixed order (reproducible).
 #include "vec_helpers.h"
+#include "internal.h"
 #include <algorithm>
 #include <stddef.h>
 #include <vector>
@@ -694,31 +695,8 @@ __global__ __launch_bounds__(TB) void k_ag_keep(int64_t M, const AdjState* __res
   ag_keep_body<VEC>(M, as, y, ybest);
 }
 
-int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
-                          hipStream_t st, bool gather);
-int psignn_f_layers_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w, float* out,
-                        float* work, float* lw, hipStream_t st);
-const psignn_plan* psignn_lin_plan(const psignn_lin_t* lin);
-
-static inline int64_t seg(int64_t n) { return (n + 63) / 64 * 64; }   // workspace segments start on 256-byte boundaries
-
-// work = [ operator scratch | y | J^T y | y_best | grad_p | h*_p | prb_p | normals_p | layer states ]
-struct AdjWork {
-  float *fwork, *y, *fy, *ybest, *grad_p, *hs_p, *prbp, *nrmp, *lwork;
-  int64_t total;
-};
-static AdjWork adj_work(const psignn_plan* p, int nl, float* base) {
-  const int64_t N = p->N, M = N * D;
-  AdjWork w;
-  int64_t o = 0;
-  auto take = [&](int64_t n) { float* q = base ? base + o : nullptr; o += seg(n); return q; };
-  w.fwork = take(psignn_f_workspace_floats(p));
-  w.y = take(M); w.fy = take(M); w.ybest = take(M); w.grad_p = take(M); w.hs_p = take(M);
-  w.prbp = take(N * 3); w.nrmp = take(N * 2);
-  w.lwork = take(!p->mixed && nl > 1 ? psignn_f_layers_workspace_floats(p, nl) : 0);
-  w.total = o;
-  return w;
-}
+using ws::AdjWork;   // work = [ operator scratch | y | J^T y | y_best | grad_p | h*_p | prb_p | normals_p | layer states ]
+static AdjWork adj_work(const psignn_plan* p, int nl, float* base) { return ws::adj_work(p->N, nl, p->mixed, base); }
 
 extern "C" int64_t psignn_gmres_adjoint_workspace_floats(const psignn_plan_t* p, int n_layers) {
   if (!p || n_layers < 1 || n_layers > 64) return -1;
@@ -831,29 +809,10 @@ extern "C" int psignn_gmres_solve_adjoint(psignn_gmres_t* s, const psignn_plan_t
   ARG_CHECK(max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
   hipStream_t st = (hipStream_t)stream;
   const AdjWork w = adj_work(p, nl, d_work);
-  // tiled plans: the whole solve in plan order; otherwise the caller's numbering (as psignn_broyden_solve_adjoint chooses)
-  const bool tiled = p->tiled;
-  const bool layers = !p->mixed && nl > 1;
-  int rc;
-  if (tiled) {
-    if ((rc = psignn_plan_permute(p, h_star, D, w.hs_p, 1, st))) return rc;
-    if ((rc = psignn_plan_permute(p, grad, D, w.grad_p, 1, st))) return rc;
-    if ((rc = psignn_plan_permute(p, prb, p->mixed ? 3 : 2, w.prbp, 1, st))) return rc;
-    if (p->mixed) {
-      if ((rc = psignn_plan_permute(p, nrm, 2, w.nrmp, 1, st))) return rc;
-      nrm = w.nrmp;
-    }
-    h_star = w.hs_p;
-    grad = w.grad_p;
-    prb = w.prbp;
-  }
-  if (layers && (rc = psignn_f_layer_states(p, W, nl, h_star, prb, w.lwork, w.fwork, st, false))) return rc;
-  auto vjp = [&](const float* y, float* out) {
-    if (layers) return psignn_f_layers_vjp(p, W, nl, h_star, prb, y, out, w.fwork, w.lwork, st);
-    return tiled ? psignn_f_vjp_p(p, W, nl, h_star, prb, nrm, y, out, w.fwork, st)
-                 : psignn_f_vjp(p, W, nl, h_star, prb, nrm, y, out, w.fwork, st);
-  };
-  return adjoint_gmres_loop(s, grad, eps, max_products, poll_every, vjp, w, tiled ? p : nullptr, d_result, info, h_rel, h_abs, st);
+  AdjointOp op;   // tiled plans: the whole solve in plan order; otherwise the caller's numbering
+  int rc = op.setup(p, W, nl, h_star, prb, nrm, grad, ws::Adapter{w.fwork, w.hs_p, w.grad_p, nullptr, w.prbp, w.nrmp}, w.fwork, w.lwork, st);
+  if (rc) return rc;
+  return adjoint_gmres_loop(s, op.grad, eps, max_products, poll_every, op, w, op.tiled ? p : nullptr, d_result, info, h_rel, h_abs, st);
 }
 
 extern "C" int psignn_gmres_solve_adjoint_lin(psignn_gmres_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad,
@@ -970,12 +929,6 @@ __global__ void k_gm_all_done_batch(const GmresBatchDesc* __restrict__ descs, in
     *all_done = a;
   }
 }
-
-int psignn_lin_batch_ok(const psignn_lin_t* lin, const psignn_plan* p);
-int psignn_lin_batch_fill(const psignn_lin_t* lin, LinBatchDesc* d, hipStream_t st);
-int64_t psignn_lin_vjp_bytes(const psignn_lin_t* lin);
-int psignn_lin_vjp_batch(const LinBatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed, int off_done,
-                         hipStream_t st);
 
 // 1 when psignn_gmres_solve_adjoint_lin_batch takes these handles and linearisations together: one vector width and one restart
 // length, every lins[i] built and of a form the batched product takes (psignn_lin_batch_ok), handle i made for the length of lins[i]'s

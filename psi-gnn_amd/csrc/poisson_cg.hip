@@ -24,11 +24,10 @@
 // then the four waves in a fixed order), then one block sums the partials in a fixed order.  No floating-point atomics: the same call
 // gives the same bits.
 #include "common.h"
+#include "internal.h"
 #include <math.h>
 
 #define CG_TB 256   // threads per block: 4 slices of 64 rows, one partial sum per block
-
-int psignn_exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* bsum, hipStream_t st);
 
 struct CgState {
   double rz, pq, alpha, beta, rr, bb, bnorm, true_rr;

@@ -15,6 +15,7 @@
 // status block; the host only polls a done flag.  Reductions use fixed-shape partial sums ->
 // bitwise reproducible run to run.
 #include "vec_helpers.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <math.h>
 #include <algorithm>
@@ -1157,15 +1158,6 @@ __global__ __launch_bounds__(TB) void k_copy_sel(int64_t M, const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------ host
-// f kernels with a device-selected input buffer (fgnn.hip)
-int psignn_f_eval_p(const psignn_plan_t* p, const float* W, int nl, const float* hbase, const int32_t* d_sel,
-                    int64_t stride, const float* h0, const float* prb, const float* nrm, float* out, float* work,
-                    hipStream_t st);
-
-int psignn_f_tile_fused(const psignn_plan* p, const float* W, int nl, float* xbuf, int64_t M, const int32_t* st_words,
-                        int off_done, int off_cur, int off_nxt, const float* upd, float* gnew,
-                        const float* h0, const float* prb, const float* nrm, float* part, hipStream_t st);
-
 #define U2R_KB_MAX 24
 #define U2D_LDS_KMAX (PARTA_LD - 1)   // LDS form: k - j_keep0 + 1 <= PARTA_LD partials per row
 static_assert(U2R_KB_MAX + 1 <= PARTA_LD, "the register fold's kept pairs must fit a partials row");
@@ -1817,9 +1809,6 @@ static int shard_finish(int n, psignn_broyden_t** sv, float* const* d_results, p
   return rc;
 }
 
-int psignn_f_tile_fused_batch(const BatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed,
-                              int off_done, int off_cur, int off_nxt, int par, hipStream_t st);
-
 // one size class: the vector width / split layout / threshold / fold limits that broyden_alloc derives from the shard size
 static bool same_size_class(const psignn_broyden* a, const psignn_broyden* b) {
   return a->vec == b->vec && a->vec_ax == b->vec_ax && a->uvu == b->uvu && a->vec_u == b->vec_u && a->thr == b->thr &&
@@ -1919,15 +1908,6 @@ __global__ __launch_bounds__(TB) void k_addv(int64_t M, const Status* __restrict
   stv<VEC>(a, e0, M, x);
 }
 
-extern "C" int psignn_f_vjp(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
-                            const float* nrm, const float* w, float* out, float* work, void* stream);
-extern "C" int psignn_f_vjp_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const float* prb,
-                              const float* nrm, const float* w, float* out, float* work, void* stream);
-int psignn_f_layer_states(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, float* lw, float* work,
-                          hipStream_t st, bool gather);
-int psignn_f_layers_vjp(const psignn_plan* p, const float* W, int nl, const float* h, const float* prb, const float* w, float* out,
-                        float* work, float* lw, hipStream_t st);
-
 // The Broyden loop of the adjoint solve; vjp(y, out): out = J_f(h*)^T y in the solve's numbering
 template <class F>
 static int adjoint_loop(psignn_broyden* s, const float* grad, double eps, int poll_every, F&& vjp, float* d_result,
@@ -1962,14 +1942,9 @@ extern "C" int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* W,
   ARG_CHECK(W && h_star && prb && grad, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
   const psignn_plan* p = s->plan;
-  // tiled plans: the whole solve in plan order; otherwise the caller's numbering
-  const bool tiled = p->tiled;
-  // multi-layer dirichlet block: the layer states h_1..h_{L-1} at h* are evaluated once per solve into solver-owned memory,
-  // each product then runs the L backward layers only (fgnn_layers.hip)
-  const bool layers = !p->mixed && nl > 1;
   ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
-  if (layers) {
+  if (!p->mixed && nl > 1) {   // the layer states of a multi-layer dirichlet block live in solver-owned memory
     const int64_t need = psignn_f_layers_workspace_floats(p, nl);
     if (s->lwork_floats < need) {
       if (s->lwork) HIP_TRY(hipFree(s->lwork));
@@ -1985,33 +1960,17 @@ extern "C" int psignn_broyden_solve_adjoint(psignn_broyden_t* s, const float* W,
       s->bytes += (size_t)need * 4;
     }
   }
-  s->plan_order = tiled ? 1 : 0;
-  int rc;
-  if (tiled) {  // plan-order copies: h* -> fwork tail, prb -> prbp, grad -> dg (free until the first update)
-    float* hs_p = s->fwork + p->N * 4 * D;        // fwork = [B (40N) | h*_p (10N) | grad_p (10N) | ...]
-    float* gr_p = hs_p + p->N * D;
-    if ((rc = psignn_plan_permute(p, h_star, D, hs_p, 1, st))) return rc;
-    if ((rc = psignn_plan_permute(p, grad, D, gr_p, 1, st))) return rc;
-    if ((rc = psignn_plan_permute(p, prb, p->mixed ? 3 : 2, s->prbp, 1, st))) return rc;
-    if (p->mixed) {
-      if ((rc = psignn_plan_permute(p, nrm, 2, s->nrmp, 1, st))) return rc;
-      nrm = s->nrmp;
-    }
-    h_star = hs_p;
-    grad = gr_p;
-    prb = s->prbp;
-  }
-  if (layers && (rc = psignn_f_layer_states(p, W, nl, h_star, prb, s->lwork, s->fwork, st, false))) return rc;
-  auto vjp = [&](const float* y, float* out) {
-    if (layers) return psignn_f_layers_vjp(p, W, nl, h_star, prb, y, out, s->fwork, s->lwork, st);
-    return tiled ? psignn_f_vjp_p(p, W, nl, h_star, prb, nrm, y, out, s->fwork, st)
-                 : psignn_f_vjp(p, W, nl, h_star, prb, nrm, y, out, s->fwork, st);
-  };
-  return adjoint_loop(s, grad, eps, poll_every, vjp, d_result, info, h_rel, h_abs, st);
+  s->plan_order = p->tiled ? 1 : 0;
+  ws::Adapter rows = ws::f_adjoint(p->N, s->fwork);   // plan-order h* and grad behind the operator's scratch
+  rows.prb = s->prbp;
+  rows.nrm = s->nrmp;
+  AdjointOp op;
+  int rc = op.setup(p, W, nl, h_star, prb, nrm, grad, rows, s->fwork, s->lwork, st);
+  if (rc) return rc;
+  return adjoint_loop(s, op.grad, eps, poll_every, op, d_result, info, h_rel, h_abs, st);
 }
 
 // Same solve with the transposed product of a stored linearisation (psignn_lin_vjp) as the map; h* = the state lin was built at
-const psignn_plan* psignn_lin_plan(const psignn_lin_t* lin);
 extern "C" int psignn_broyden_solve_adjoint_lin(psignn_broyden_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad,
                                                 double eps, int poll_every, float* d_result, psignn_solve_info_t* info,
                                                 double* h_rel, double* h_abs, void* stream) {
@@ -2021,7 +1980,7 @@ extern "C" int psignn_broyden_solve_adjoint_lin(psignn_broyden_t* s, const psign
   hipStream_t st = (hipStream_t)stream;
   const psignn_plan* p = s->plan;
   s->plan_order = 1;
-  float* gr_p = s->fwork + p->N * 5 * D;   // fwork = [B (40N) | (10N) | grad_p (10N) | ...], as above
+  float* gr_p = ws::f_adjoint(p->N, s->fwork).x;
   int rc;
   if ((rc = psignn_plan_permute(p, grad, D, gr_p, 1, st))) return rc;
   auto vjp = [&](const float* y, float* out) { return psignn_lin_vjp(lin, W, nl, y, out, s->fwork, st); };
@@ -2071,11 +2030,6 @@ __global__ __launch_bounds__(TB) void kb_addv_resid(const BatchDesc* __restrict_
   block_pair_store(sg, sf, d.nrm_part, d.nblk);
 }
 
-int psignn_lin_batch_ok(const psignn_lin_t* lin, const psignn_plan* p);
-int psignn_lin_batch_fill(const psignn_lin_t* lin, LinBatchDesc* d, hipStream_t st);
-int64_t psignn_lin_vjp_bytes(const psignn_lin_t* lin);
-int psignn_lin_vjp_batch(const LinBatchDesc* d_descs, int n_mesh, int n_slots, int max_rows, const float* W, int mixed, int off_done,
-                         hipStream_t st);
 
 // 1 when psignn_broyden_solve_adjoint_lin_batch takes these solvers and handles together: all that psignn_broyden_batchable asks, and
 // every lins[i] was made for solvers[i]'s plan, has been built and holds a form the batch product takes (dirichlet; mixed only with
@@ -2116,7 +2070,7 @@ extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** 
     if ((rc = psignn_lin_batch_fill(lins[m], &l, st))) return rc;
     bv_tot += psignn_lin_vjp_bytes(lins[m]);
     s->plan_order = 1;
-    float* gr_p = s->fwork + p->N * 5 * D;   // fwork = [B (40N) | (10N) | grad_p (10N) | ...], as in the single-mesh solve
+    float* gr_p = ws::f_adjoint(p->N, s->fwork).x;
     if ((rc = psignn_plan_permute(p, grads[m], D, gr_p, 1, st))) return rc;
     k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
     HIP_TRY(hipMemsetAsync(s->h0p, 0, (size_t)s->M * 4, st));

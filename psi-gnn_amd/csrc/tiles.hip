@@ -18,6 +18,7 @@
 // If a structure limit is exceeded (cell > SORT_CAP nodes, > CAND_CAP halo candidates, halo > HALO_CAP, > 255 slots, or, on
 // mixed plans, tile + halo > MIXED_ROW_CAP = 682 rows) the plan stays untiled and the global-gather kernels (fgnn.hip) are used.
 #include "common.h"
+#include "internal.h"
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -334,7 +335,6 @@ __global__ __launch_bounds__(256) void k_ell_fill(int64_t n_slices, const int32_
 }
 
 // ---------------------------------------------------------------- host
-int psignn_exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* bsum, hipStream_t st);
 
 void psignn_tiles_free(psignn_plan* p) {
   void* ptrs[] = {p->perm, p->inv, p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt,
