@@ -694,6 +694,63 @@ int psignn_cg_solve(psignn_cg_t* s, const void* d_y, int y_is_f64, const double*
                     double* h_res_trace /* max_iter + 1 doubles or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The forward path in float64 on the device: f, the encoder / decoder MLP and a Broyden solve with every scalar on the device
+ * (csrc/fgnn_f64.hip, csrc/solver_f64.hip).  The float64 fixed point h* -- the truth the fp32 path is measured against -- at any size.
+ * Default-width library only (latent width 10).  Nothing here shares arithmetic, weight layout or kernels with the fp32 entry points.
+ * replaces: the reference run with --precision double (dirichlet/psignn/utilities/utils.py:28, passed to the reader in
+ *           dirichlet/psignn/main.py:59-67), i.e. Function.forward (dirichlet/psignn/model.py:279-300, mixed/psignn/model.py:216-245),
+ *           Encoder / Decoder (model.py:370-392) and broyden (utilities/solver.py:116-207) on float64 tensors.
+ *
+ * Weights: a flat float64 buffer of the deqdss.f.* tensors in state-dict order, each nn.Linear (out, in) row-major, no padding:
+ *   laynorm.weight[10] laynorm.bias[10] alpha.0.weight[30+P] alpha.0.bias[1]
+ *   per layer l: phi_to_list.l.mlp.mlp.{0.weight[10x23] 0.bias[10] 2.weight[10x10] 2.bias[10]}, phi_from_list.l.mlp.mlp.{same},
+ *                update_list.l.mlp.{0.weight[10x(30+P)] 0.bias[10] 2.weight[10x10] 2.bias[10]}
+ *   mixed only:  phi_neumann.mlp.mlp.{as phi_to}, update_neumann.mlp.{0.weight[10x(22+P)] 0.bias[10] 2.weight[10x10] 2.bias[10]}
+ * with P = 2 (dirichlet) / 3 (mixed).  psignn_f64_weights_size is that length (1193 / 1924 for one layer; -1 for n_layers < 1) and
+ * needs no GPU.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct psignn_f64 psignn_f64_t;
+int64_t psignn_f64_weights_size(int mixed, int n_layers);
+/* The handle keeps its own float64 copy of edge_attr, made once from d_edge_attr ((E, 3) in edge_index order, float32 -- widened
+ * exactly -- or float64) in the plan's canonical order: per node its out-edges and its in-edges, self loops removed, ascending edge id.
+ * It borrows the plan, which must outlive it.  Synchronous. */
+int psignn_f64_create(psignn_f64_t** out, const psignn_plan_t* plan, const void* d_edge_attr /* (E,3) edge_index order */,
+                      int attr_is_f64, void* stream);
+void psignn_f64_destroy(psignn_f64_t* f);
+/* d_out = f(d_h; d_h_initial, d_prb, d_normals): SURVEY a1-a4 as the reference writes them -- per edge the whole message MLP on
+ * [x_i | x_j | a_e], summed per node over the plan's CSC (Phi_to) / CSR (Phi_from, Phi_neumann); gate, update MLP, LayerNorm on the last
+ * layer, Dirichlet rows from d_h_initial, the mixed family's Neumann rows replaced by update_neumann and its layer loop that never
+ * reassigns h (the last layer on h is the block).  All arrays float64, caller's numbering, on tiled and untiled plans alike; any
+ * degree, duplicate and one-directional edges.  One node per lane, no atomics: the same call gives the same bits.  d_out != d_h. */
+int psignn_f64_forward(psignn_f64_t* f, const double* d_weights, int n_layers, const double* d_h, const double* d_h_initial,
+                       const double* d_prb, const double* d_normals /* NULL for dirichlet plans */, double* d_out, void* stream);
+/* out (n, dout) = W2 relu(W1 x + b1) + b2 in float64, W1 (hid, din), W2 (dout, hid); din, hid, dout <= 16.
+ * replaces: Encoder / Decoder (model.py:370-392) on float64 tensors. */
+int psignn_mlp2_f64(const double* d_x, int64_t n, int din, int hid, int dout, const double* d_w1, const double* d_b1,
+                    const double* d_w2, const double* d_b2, double* d_out, void* stream);
+
+/* Broyden in float64 (reference recurrences: ls = False, stop mode "rel"): rel = |g| / (|g + x| + 1e-9); the lowest-rel iterate is
+ * kept; stops on rel < eps, on the 30-step plateau rule at 3 eps, on the protective break at rel_0 * 1e3 * d, or after `threshold`
+ * steps; NaN -> 0 in the new pair; update = g - U (V^T g) with the new pair included.
+ * replaces: broyden(f, x0, threshold, eps) on float64 tensors (utilities/solver.py:116-207, matvec / rmatvec :96-114).
+ * create allocates the pairs in float64, 2 * threshold * N * d * 8 bytes, and fails with PSIGNN_ENOMEM and a message naming that size
+ * when it cannot.  The solver borrows the map handle (and through it the plan). */
+typedef struct psignn_broyden64 psignn_broyden64_t;
+int psignn_broyden64_create(psignn_broyden64_t** out, psignn_f64_t* f, int threshold);
+void psignn_broyden64_destroy(psignn_broyden64_t* s);
+size_t psignn_broyden64_bytes(const psignn_broyden64_t* s);
+/* One solve from d_x0.  Every dot, norm, coefficient and stop test is on the device; the update is the two-pass form (one sweep of the
+ * stored pairs for the coefficients, one for the combinations); every reduction is per-block partials summed by one block in a fixed
+ * order (no floating-point atomics: the same call gives the same bits).  The host reads one done flag every poll_every iterations
+ * (<= 0: 16); launches queued past the last iteration return at once, so nothing in the result depends on poll_every.
+ * d_result: (N, d) float64, the lowest-rel iterate (d_x0 itself if no step went below 1e8).  h_info: as psignn_broyden_solve
+ * (nstep: the 1-based step of the lowest iterate; n_iter: steps taken).  h_rel_trace / h_abs_trace: `threshold` doubles each or NULL;
+ * n_iter entries are written, entry i after step i + 1.  Synchronous at the end. */
+int psignn_broyden64_solve(psignn_broyden64_t* s, const double* d_weights, int n_layers, const double* d_x0,
+                           const double* d_h_initial, const double* d_prb, const double* d_normals, double eps, int poll_every,
+                           double* d_result, psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line;
  * replaces: the reference's only instrumentation, time.time() around the model call,
  * tests/special_geo/spec_geo_2.py:313-317).  Off by default.

@@ -206,6 +206,16 @@ SIGNATURES = {
     "psignn_cg_create": (_INT, [C.POINTER(_P), _P, _P, _INT, _P]),
     "psignn_cg_destroy": (None, [_P]),
     "psignn_cg_solve": (_INT, [_P, _P, _INT, _P, C.c_double, _INT, _INT, _P, C.POINTER(CgInfo), C.POINTER(C.c_double), _P]),
+    "psignn_f64_weights_size": (_I64, [_INT, _INT]),
+    "psignn_f64_create": (_INT, [C.POINTER(_P), _P, _P, _INT, _P]),
+    "psignn_f64_destroy": (None, [_P]),
+    "psignn_f64_forward": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P]),
+    "psignn_mlp2_f64": (_INT, [_P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _P, _P]),
+    "psignn_broyden64_create": (_INT, [C.POINTER(_P), _P, _INT]),
+    "psignn_broyden64_destroy": (None, [_P]),
+    "psignn_broyden64_bytes": (C.c_size_t, [_P]),
+    "psignn_broyden64_solve": (_INT, [_P, _P, _INT, _P, _P, _P, _P, C.c_double, _INT, _P, C.POINTER(SolveInfo),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_prof_enable": (None, [_INT]),
     "psignn_reload_knobs": (None, []),
     "psignn_prof_tile_stamps": (None, [_P]),

@@ -80,6 +80,11 @@ int psignn_dsgps_step_records(const psignn_plan* p, const float* Wf, const float
 int psignn_dss_step_records(const psignn_plan* p, const float* Wf, float alpha, const float* h, const float* bp, const float* w,
                             float* out_h, float* work, float* rec, hipStream_t st);
 
+// ---- fgnn_f64.hip
+const psignn_plan* psignn_f64_plan(const psignn_f64_t* f);
+int psignn_f64_eval(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb, const double* nrm,
+                    double* out, const int32_t* done, hipStream_t st);
+
 // ---- plan.hip
 int psignn_exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* bsum, hipStream_t st);
 

@@ -1843,3 +1843,184 @@ def poisson_solve(batch, tol=1e-10, **kw):
         return cg.solve(batch.y, tol=tol, **kw)
     finally:
         cg.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# the forward path in float64 (csrc/fgnn_f64.hip, csrc/solver_f64.hip): the float64 fixed point h* on the device
+# ---------------------------------------------------------------------------------------------
+def _f64c(t, name):
+    """A device tensor as a contiguous float64 one (float32 widens exactly)."""
+    nat.require_cuda(t, name)
+    return t.to(torch.float64).contiguous()
+
+
+def pack_weights64(sd) -> torch.Tensor:
+    """The ``deqdss.f.*`` tensors of a reference state dict as one flat float64 CPU tensor, in state-dict order with nothing
+    padded, folded or transposed (layout: include/psignn_hip.h, "The forward path in float64"): laynorm, alpha, then per layer
+    phi_to / phi_from / update, then (mixed) phi_neumann / update_neumann; each block weight, bias, weight, bias."""
+    P = "deqdss.f."
+    g = lambda k: sd[P + k].detach().to("cpu", torch.float64).reshape(-1)
+    mlp = lambda prefix: [g(f"{prefix}.0.weight"), g(f"{prefix}.0.bias"), g(f"{prefix}.2.weight"), g(f"{prefix}.2.bias")]
+    parts = [g("laynorm.weight"), g("laynorm.bias"), g("alpha.0.weight"), g("alpha.0.bias")]
+    for l in range(n_layers_of(sd)):
+        parts += mlp(f"phi_to_list.{l}.mlp.mlp") + mlp(f"phi_from_list.{l}.mlp.mlp") + mlp(f"update_list.{l}.mlp")
+    if is_mixed_state_dict(sd):
+        parts += mlp("phi_neumann.mlp.mlp") + mlp("update_neumann.mlp")
+    return torch.cat(parts).contiguous()
+
+
+class PackedWeights64:
+    """Float64 weights of f for ``FixedPointMap64``.  Default latent width only: a state dict of another supported width raises
+    the "forward inference only" ``NativeError`` of that width's library."""
+
+    def __init__(self, sd, device=None):
+        self.mixed = is_mixed_state_dict(sd)
+        self.n_layers = n_layers_of(sd)
+        self.width = width_of(sd)
+        expect = nat.lib(self.width).psignn_f64_weights_size(int(self.mixed), self.n_layers)   # a width library: raises
+        if sd["deqdss.f.alpha.0.weight"].numel() != 3 * self.width + (3 if self.mixed else 2):
+            raise nat.NativeError("alpha gate width does not match the boundary-condition family")
+        flat = pack_weights64(sd)
+        if flat.numel() != expect:
+            raise nat.NativeError(f"packed float64 weight length {flat.numel()} != native layout {expect}")
+        self.flat = flat if device is None else flat.to(device)
+
+
+def mlp2_64(x, w1, b1, w2, b2):
+    """relu(x W1^T + b1) W2^T + b2 in float64 (``psignn_mlp2_f64``): the encoder / decoder of the float64 path.  Inputs of any
+    float dtype are widened; the result is float64."""
+    xc = _f64c(x, "x")
+    if xc.dim() != 2 or w1.shape[1] != xc.shape[1] or w2.shape[1] != w1.shape[0]:
+        raise nat.NativeError(f"mlp2_64: x {tuple(x.shape)}, W1 {tuple(w1.shape)}, W2 {tuple(w2.shape)} do not chain")
+    n, din = xc.shape
+    hid, dout = w1.shape[0], w2.shape[0]
+    out = torch.empty((n, dout), dtype=torch.float64, device=xc.device)
+    dv = lambda t: t.detach().to(xc.device, torch.float64).contiguous()
+    w1, b1, w2, b2 = dv(w1), dv(b1), dv(w2), dv(b2)
+    with torch.cuda.device(xc.device):
+        nat.check(nat.lib().psignn_mlp2_f64(nat.ptr(xc), n, din, hid, dout, nat.ptr(w1), nat.ptr(b1), nat.ptr(w2), nat.ptr(b2),
+                                            nat.ptr(out), nat.stream_ptr(xc.device)), "psignn_mlp2_f64")
+    return out
+
+
+class FixedPointMap64:
+    """``H -> f(H, H_init, batch)`` in float64 on the device: (N, 10) float64 -> (N, 10) float64 in the caller's numbering, on
+    tiled and untiled plans alike.  ``edge_attr``: the batch's (E, 3) array in ``edge_index`` order, float32 (widened exactly) or
+    float64; the native handle keeps its own float64 copy in the plan's canonical order.  ``h_initial``, ``prb_data``,
+    ``normals``: float32 (widened exactly) or float64.  Shape and family mismatches raise ``NativeError`` before any native
+    call."""
+
+    def __init__(self, plan, weights64, h_initial, prb_data, edge_attr, normals=None):
+        if plan.mixed != weights64.mixed:
+            raise nat.NativeError("boundary-condition family of the weights and of the batch differ "
+                                  f"(weights mixed={weights64.mixed}, batch mixed={plan.mixed})")
+        if plan.mixed and normals is None:
+            raise nat.NativeError("mixed problems need batch.unit_normal_vector")
+        exp_p = 3 if plan.mixed else 2
+        if (tuple(prb_data.shape) != (plan.N, exp_p) or tuple(h_initial.shape) != (plan.N, D)
+                or tuple(edge_attr.shape) != (plan.E, 3) or (normals is not None and tuple(normals.shape) != (plan.N, 2))):
+            raise nat.NativeError(f"shape mismatch: prb_data {tuple(prb_data.shape)}, h_initial {tuple(h_initial.shape)}, "
+                                  f"edge_attr {tuple(edge_attr.shape)} for a plan of {plan.N} nodes and {plan.E} edges")
+        self.plan, self.weights, self.device = plan, weights64, plan.device
+        self.h0 = _f64c(h_initial, "h_initial")
+        self.prb = _f64c(prb_data, "prb_data")
+        self.nrm = None if normals is None or not plan.mixed else _f64c(normals, "normals")
+        self.wflat = weights64.flat.to(self.device)
+        ea, ea64 = _f64_or_f32(edge_attr, "edge_attr")
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_f64_create(C.byref(h), plan.handle, nat.ptr(ea), ea64, nat.stream_ptr(self.device)),
+                      "psignn_f64_create")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_f64_destroy, h)
+
+    def close(self):
+        self._fin()
+        self.handle = None
+
+    def _state(self, H, name="H"):
+        if self.handle is None:
+            raise nat.NativeError("FixedPointMap64 is closed")
+        if tuple(H.shape) != (self.plan.N, D):
+            raise nat.NativeError(f"{name} has shape {tuple(H.shape)}, expected {(self.plan.N, D)}")
+        return _f64c(H, name)
+
+    def __call__(self, H):
+        Hc = self._state(H)
+        out = torch.empty_like(Hc)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_f64_forward(self.handle, nat.ptr(self.wflat), self.weights.n_layers, nat.ptr(Hc),
+                                                   nat.ptr(self.h0), nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(out),
+                                                   nat.stream_ptr(self.device)), "psignn_f64_forward")
+        return out
+
+
+class DeviceBroyden64:
+    """Broyden root-find of ``f(x) - x`` in float64 with every scalar on the device (``psignn_broyden64_*``): the reference's
+    recurrences (``ls=False``, stop mode ``rel``) on a ``FixedPointMap64``.  The pairs are stored in float64,
+    ``2 * threshold * N * 10 * 8`` bytes; creation raises ``NativeError`` naming that size when the device cannot hold them."""
+
+    def __init__(self, fmap64, threshold):
+        if getattr(fmap64, "handle", None) is None:
+            raise nat.NativeError("DeviceBroyden64 needs an open FixedPointMap64")
+        self.fmap, self.threshold, self.device = fmap64, int(threshold), fmap64.device
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_broyden64_create(C.byref(h), fmap64.handle, self.threshold), "psignn_broyden64_create")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_broyden64_destroy, h)
+
+    def close(self):
+        self._fin()
+        self.handle = None
+
+    @property
+    def nbytes(self):
+        return int(nat.lib().psignn_broyden64_bytes(self.handle))
+
+    def solve(self, x0, eps, poll_every=16):
+        """From ``x0`` ((N, 10), float32 widened exactly or float64).  Returns ``result`` (the lowest-rel iterate, float64),
+        ``lowest``, ``nstep`` (the 1-based step of that iterate), ``n_iter`` (steps taken), ``prot_break``, ``stop_reason``
+        (0 threshold, 1 rel < eps, 2 plateau, 3 protective break) and ``rel_trace`` / ``abs_trace`` (entry i: after step i + 1;
+        padded to ``threshold + 1`` entries with the lowest values as the reference pads them).  Deterministic; ``poll_every``
+        (how often the host looks at the done flag) changes nothing in the result."""
+        if self.handle is None or self.fmap.handle is None:
+            raise nat.NativeError("DeviceBroyden64 (or its map) is closed")
+        fm = self.fmap
+        x0c = fm._state(x0, "x0")
+        result = torch.empty_like(x0c)
+        info = nat.SolveInfo()
+        rel = (C.c_double * self.threshold)()
+        abs_ = (C.c_double * self.threshold)()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_broyden64_solve(
+                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(x0c), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                float(eps), int(poll_every), nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device)),
+                "psignn_broyden64_solve")
+        n_it = int(info.n_iter)
+        pad = self.threshold + 1 - n_it
+        return {"result": result, "lowest": float(info.lowest), "nstep": int(info.nstep), "n_iter": n_it,
+                "prot_break": bool(info.prot_break), "stop_reason": int(info.stop_reason),
+                "rel_trace": list(rel[:n_it]) + [float(info.lowest)] * pad,
+                "abs_trace": list(abs_[:n_it]) + [float(info.lowest_abs)] * pad}
+
+
+def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16):
+    """encoder -> float64 Broyden solve -> decoder, all in float64 on the device, for a device batch and a reference state dict
+    (default latent width).  Returns the solver's dictionary plus ``h0`` (the encoded start) and ``u`` (the decoded result)."""
+    w = PackedWeights64(state_dict)
+    ae = lambda k: state_dict["autoencoder." + k]
+    enc = [ae(f"encoder.mlp.mlp.{i}.{p}") for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
+    dec = [ae(f"decoder.mlp.mlp.{i}.{p}") for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
+    plan = plan_for(batch)
+    h0 = mlp2_64(batch.x, *enc)
+    fmap = FixedPointMap64(plan, w, h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
+    solver = DeviceBroyden64(fmap, threshold)
+    try:
+        out = solver.solve(h0, eps, poll_every)
+    finally:
+        solver.close()
+        fmap.close()
+    out["h0"] = h0
+    out["u"] = mlp2_64(out["result"], *dec)
+    return out
