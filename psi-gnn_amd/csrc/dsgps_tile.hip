@@ -48,7 +48,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_dsgps_tile(int n_tiles, int ch
   constexpr int RS = MIXED ? 32 : 20;
   const float* TN = W + dsl::NEU;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);  // XCD-contiguous tile runs, as in k_f_tile
+  const int tile = xcd_tile_slot(chunk);  // XCD-contiguous tile runs, as in k_f_tile
   if (tile >= n_tiles) return;
   const int tid = threadIdx.x;
   const int32_t t0 = tile_ptr[tile];
@@ -225,12 +225,10 @@ static void dsgps_launch(const psignn_plan* p, const float* W, const float* cur,
   const unsigned grid = (unsigned)(chunk * 8);
   if (p->mixed) {
     LAUNCH("k_dsgps_tile", st, (k_dsgps_tile<3, true><<<grid, TILE_THREADS, (size_t)p->max_rows * 32 * 4, st>>>(
-        (int)p->n_tiles, chunk, p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt, p->slice_off, p->slice_deg, p->ell,
-        p->flags_p, W, cur, h0p, prbp, nrmp, dst)));
+        (int)p->n_tiles, chunk, PLAN_TILES_FLAGS(p), W, cur, h0p, prbp, nrmp, dst)));
   } else {
     LAUNCH("k_dsgps_tile", st, (k_dsgps_tile<2, false><<<grid, TILE_THREADS, (size_t)p->max_rows * 20 * 4, st>>>(
-        (int)p->n_tiles, chunk, p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt, p->slice_off, p->slice_deg, p->ell,
-        p->flags_p, W, cur, h0p, prbp, nrmp, dst)));
+        (int)p->n_tiles, chunk, PLAN_TILES_FLAGS(p), W, cur, h0p, prbp, nrmp, dst)));
   }
 }
 

@@ -12,7 +12,7 @@
 //   460 b1_to | 470 b1_from | 480 W2_to^T 100 | 580 b2_to | 590 W2_from^T 100 | 690 b2_from |
 //   700 P1^T (33 x 10) 330 | 1030 c1 | 1040 P2^T 100 | 1140 c2                                   -- 1150 per step
 #include "tile_helpers.h"
-#include "workspace.h"
+#include "internal.h"
 
 namespace dss {
 constexpr int W1J_TO = 0, W1J_FR = 100, W1I_TO = 200, W1I_FR = 300, A_TO = 400, A_FR = 430, B1_TO = 460, B1_FR = 470;
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_dss_tile(int n_tiles, int chun
                                                            float* __restrict__ out) {
   constexpr int RS = 20;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int tile = xcd_tile_slot(chunk);
   if (tile >= n_tiles) return;
   const int tid = threadIdx.x;
   const int32_t t0 = tile_ptr[tile];
@@ -143,8 +143,7 @@ extern "C" int psignn_dss_forward(const psignn_plan_t* p, const float* W, int k,
   for (int i = 0; i < k; ++i) {
     float* dst = (cur == a) ? b : a;
     LAUNCH("k_dss_tile", st, (k_dss_tile<<<grid, TILE_THREADS, lds, st>>>(
-        (int)p->n_tiles, chunk, p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt, p->slice_off, p->slice_deg, p->ell,
-        W + (int64_t)i * dss::STEP, alpha, cur, bpp, dst)));
+        (int)p->n_tiles, chunk, PLAN_TILES(p), W + (int64_t)i * dss::STEP, alpha, cur, bpp, dst)));
     cur = dst;
   }
   HIP_TRY(hipGetLastError());
@@ -162,8 +161,7 @@ extern "C" int psignn_dss_step_p(const psignn_plan_t* p, const float* W, int t, 
   hipStream_t st = (hipStream_t)stream;
   const int chunk = (int)cdiv(p->n_tiles, 8);
   LAUNCH("k_dss_tile", st, (k_dss_tile<<<(unsigned)(chunk * 8), TILE_THREADS, (size_t)p->max_rows * 20 * 4, st>>>(
-      (int)p->n_tiles, chunk, p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt, p->slice_off, p->slice_deg, p->ell,
-      W + (int64_t)t * dss::STEP, alpha, d_h, d_bprime_p, d_out)));
+      (int)p->n_tiles, chunk, PLAN_TILES(p), W + (int64_t)t * dss::STEP, alpha, d_h, d_bprime_p, d_out)));
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }

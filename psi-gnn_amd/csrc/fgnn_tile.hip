@@ -557,7 +557,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_f_tile(FuseArgs fa, int n_tile
   const TileCtx* __restrict__ C = &Cv;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (FUSED && fa.st[fa.off_done]) return;
-  const int slot = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot = xcd_tile_slot(chunk);
   if (slot >= n_tiles) return;
   f_tile_body<P, MIXED, FUSED, MFMA1>(fa, slot, tile_list, C, W, lofs, tofs, tnofs, apply_ln, h, hsel, hstride, h0, prb, nrm, out,
                                       lds);
@@ -575,7 +575,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_f_tile_batch(const BatchDesc* 
                                                               int off_done, int off_cur, int off_nxt, int par,
                                                               const float* __restrict__ W, int lofs, int tofs, int tnofs) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int slot = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot = xcd_tile_slot(chunk);
   if (slot >= n_slots) return;
   int m = 0;
   while (m + 1 < n_mesh && descs[m + 1].tile_base <= slot) ++m;   // wave-uniform scalar walk (a shard has few meshes)
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_f_tile_plain_batch(const FpBat
                                                                     int chunk, int off_done, int in_f, int in_row,
                                                                     const float* __restrict__ W, int lofs, int tofs, int tnofs) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int slot = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot = xcd_tile_slot(chunk);
   if (slot >= n_slots) return;
   int m = 0;
   while (m + 1 < n_mesh && descs[m + 1].tile_base <= slot) ++m;   // wave-uniform scalar walk (a shard has few meshes)

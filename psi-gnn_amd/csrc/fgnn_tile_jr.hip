@@ -28,26 +28,6 @@
 #define JR_RS 20     // pass A: floats per LDS row [Pj_to | Pj_from]
 #define JR_BS 30     // pass B: floats per LDS row [P | dS | dS'] = half a B row
 
-__device__ __forceinline__ void jr_row10(const float* __restrict__ row, v2f* r) {  // 16-byte aligned
-  float4 v0 = reinterpret_cast<const float4*>(row)[0], v1 = reinterpret_cast<const float4*>(row)[1];
-  float2 v2 = reinterpret_cast<const float2*>(row)[4];
-  r[0] = (v2f){v0.x, v0.y}; r[1] = (v2f){v0.z, v0.w}; r[2] = (v2f){v1.x, v1.y}; r[3] = (v2f){v1.z, v1.w};
-  r[4] = (v2f){v2.x, v2.y};
-}
-__device__ __forceinline__ void jr_row10u(const float* __restrict__ row, v2f* r) {  // 8 mod 16
-  float2 v0 = reinterpret_cast<const float2*>(row)[0];
-  float4 v1 = reinterpret_cast<const float4*>(row + 2)[0], v2 = reinterpret_cast<const float4*>(row + 2)[1];
-  r[0] = (v2f){v0.x, v0.y}; r[1] = (v2f){v1.x, v1.y}; r[2] = (v2f){v1.z, v1.w}; r[3] = (v2f){v2.x, v2.y};
-  r[4] = (v2f){v2.z, v2.w};
-}
-__device__ __forceinline__ void jr_row10h(const float* __restrict__ row, v2f* r) {  // 8-byte aligned only
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const float2 t = reinterpret_cast<const float2*>(row)[i];
-    r[i] = (v2f){t.x, t.y};
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- pass A
 // One Phi module over the slots carrying MASK, z = Pi + row[COL..] + AT . a:
 //   S[o] += relu(z),  cnt[o] += 1[z > 0],  m[c * 5 + p] += 1[z > 0] a_c,  Tj[o] += 1[z > 0] drow[COL + o]
@@ -58,48 +38,27 @@ __device__ __forceinline__ float jr_pass_fwd(const uint4* __restrict__ slots, in
                                              v2f* cnt, v2f* m) {
   float deg = 0.f;
   v2f wa[15];
-#pragma unroll
-  for (int i = 0; i < 15; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
-  if (nslots <= 0) return deg;
-  uint4 c0 = slots[0];
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 2, nslots - 1) * 64];
-    const unsigned w = c0.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY && (w & MASK)) {
-      const v2f a0 = splat(__uint_as_float(c0.y)), a1 = splat(__uint_as_float(c0.z)), a2 = splat(__uint_as_float(c0.w));
-      const float* row = lds + (int)(w & 0xFFFFu) * JR_RS + COL;
+  ld_attr(AT, wa);
+  for (SlotWalk<EDGE_PD, MASK> w(slots, nslots); w.more(); w.step())
+    if (w.live()) {
+      const SlotAttr a = slot_attr(w.slot());
+      const float* row = lds + w.row() * JR_RS;
       v2f pj[5], dpj[5], z[5];
-      if (COL % 4 == 0) {
-        jr_row10(row, pj);
-        jr_row10(row + doff, dpj);
-      } else {
-        jr_row10u(row, pj);
-        jr_row10u(row + doff, dpj);
-      }
+      lds_row<COL>(row, pj);
+      lds_row<COL>(row + doff, dpj);   // (doff is a multiple of the row stride: same alignment)
       deg += 1.f;
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = Pi[p] + pj[p];
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[5 + p], a1, z[p]);
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[10 + p], a2, z[p]);
+      edge_preact(wa, a, Pi, pj, z);
 #pragma unroll
       for (int p = 0; p < 5; ++p) {
         S[p] += __builtin_elementwise_max(z[p], splat(0.f));
         const v2f mk = (v2f){z[p].x > 0.f ? 1.f : 0.f, z[p].y > 0.f ? 1.f : 0.f};
         cnt[p] += mk;
         Tj[p] = __builtin_elementwise_fma(mk, dpj[p], Tj[p]);
-        m[p] = __builtin_elementwise_fma(mk, a0, m[p]);
-        m[5 + p] = __builtin_elementwise_fma(mk, a1, m[5 + p]);
-        m[10 + p] = __builtin_elementwise_fma(mk, a2, m[10 + p]);
+        m[p] = __builtin_elementwise_fma(mk, a.a0, m[p]);
+        m[5 + p] = __builtin_elementwise_fma(mk, a.a1, m[5 + p]);
+        m[10 + p] = __builtin_elementwise_fma(mk, a.a2, m[10 + p]);
       }
     }
-    c0 = c1;
-    c1 = nx;
-  }
   return deg;
 }
 
@@ -116,7 +75,7 @@ __global__ __launch_bounds__(256) void k_jr_tile_a(int n_tiles, int chunk, int64
   using L = WLayout<P>;
   constexpr bool LN = true;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int tile = xcd_tile_slot(chunk);
   if (tile >= n_tiles) return;
   const int tid = threadIdx.x;
   const int32_t t0 = tile_ptr[tile];
@@ -329,22 +288,18 @@ template <unsigned MASK>
 __device__ __forceinline__ void jr_pass_rev(const uint4* __restrict__ slots, int nslots, const float* __restrict__ lds,
                                             const float* __restrict__ AT, float flip, const v2f* Pj, v2f* acc, v2f* acc2) {
   v2f wa[15];
-#pragma unroll
-  for (int i = 0; i < 15; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
-  if (nslots <= 0) return;
-  uint4 c0 = slots[0];
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 2, nslots - 1) * 64];
-    const unsigned w = c0.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY && (w & MASK)) {
+  ld_attr(AT, wa);
+  for (SlotWalk<EDGE_PD, MASK> w(slots, nslots); w.more(); w.step())
+    if (w.live()) {
+      // (the chain of edge_preact, written out: through the helper k_jr_tile_b needs 108 VGPRs instead of 104 and ran 1 % slower)
+      const uint4& c0 = w.slot();
       const v2f a0 = splat(flip * __uint_as_float(c0.y)), a1 = splat(flip * __uint_as_float(c0.z));
       const v2f a2 = splat(__uint_as_float(c0.w));
-      const float* row = lds + (int)(w & 0xFFFFu) * JR_BS;
+      const float* row = lds + w.row() * JR_BS;   // 120-byte rows: 8-byte aligned only
       v2f pi[5], ds[5], ds2[5], z[5];
-      jr_row10h(row, pi);
-      jr_row10h(row + D, ds);
-      jr_row10h(row + 2 * D, ds2);
+      lds_row8(row, pi);
+      lds_row8(row + D, ds);
+      lds_row8(row + 2 * D, ds2);
 #pragma unroll
       for (int p = 0; p < 5; ++p) z[p] = pi[p] + Pj[p];
 #pragma unroll
@@ -359,9 +314,6 @@ __device__ __forceinline__ void jr_pass_rev(const uint4* __restrict__ slots, int
         acc2[p] += (v2f){z[p].x > 0.f ? ds2[p].x : 0.f, z[p].y > 0.f ? ds2[p].y : 0.f};
       }
     }
-    c0 = c1;
-    c1 = nx;
-  }
 }
 
 // lds: (n_t + n_h) x 120 bytes
@@ -375,7 +327,7 @@ __global__ __launch_bounds__(256) void k_jr_tile_b(int n_tiles, int chunk, int64
                                                    float* __restrict__ rec) {
   using L = WLayout<P>;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int tile = xcd_tile_slot(chunk);
   if (tile >= n_tiles) return;
   const int tid = threadIdx.x;
   const int32_t t0 = tile_ptr[tile];
@@ -467,18 +419,16 @@ int psignn_jr_tile_records(const psignn_plan* p, const float* W, const float* h,
   if (lds_a > 64 * 1024 || lds_b > 64 * 1024)
     ARG_CHECK(jr_tile_lds_granted(cap_a, cap_b), "the device refused the dynamic LDS of the tiled backward of the VJP");
   const int tofs = L::tp_layer(1, false, 0);
-#define JR_PLAN p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt, p->slice_off, p->slice_deg, p->ell
   // pass A reads h, gbar, v (40 N each), prb (8 N), flags, writes B (240 N), the node-local d phi / d h (40 N) and the two
   // records less their groups 12, 13 (2 x 1 152 N); 20 bytes per directed edge (slot + attr)
   PROF_BYTES((int64_t)N * (129 + 240 + 40 + 2 * (JR_REC - 32) * 4) + 20 * p->Ep);
-  LAUNCH("k_jr_tile_a", st, (k_jr_tile_a<2><<<grid, TILE_THREADS, lds_a, st>>>((int)p->n_tiles, chunk, N, JR_PLAN, p->flags_p, W, tofs, h,
-                                                                                 prb, v, gbar, B, out_h, rec)));
+  LAUNCH("k_jr_tile_a", st, (k_jr_tile_a<2><<<grid, TILE_THREADS, lds_a, st>>>(
+      (int)p->n_tiles, chunk, N, PLAN_TILES_FLAGS(p), W, tofs, h, prb, v, gbar, B, out_h, rec)));
   // pass B reads h (40 N), B (240 N) and the partial d phi / d h (40 N), writes it (40 N) and groups 12, 13 of both records
   // (256 N); 20 bytes per directed edge
   PROF_BYTES((int64_t)N * (40 + 240 + 40 + 40 + 256) + 20 * p->Ep);
-  LAUNCH("k_jr_tile_b", st, (k_jr_tile_b<2><<<grid, TILE_THREADS, lds_b, st>>>((int)p->n_tiles, chunk, N, JR_PLAN, W, tofs, h, B, out_h,
-                                                                                 rec)));
-#undef JR_PLAN
+  LAUNCH("k_jr_tile_b", st, (k_jr_tile_b<2><<<grid, TILE_THREADS, lds_b, st>>>(
+      (int)p->n_tiles, chunk, N, PLAN_TILES(p), W, tofs, h, B, out_h, rec)));
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }

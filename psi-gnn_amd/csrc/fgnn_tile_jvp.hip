@@ -18,48 +18,22 @@
 #include <stdlib.h>
 #include <string.h>
 
-__device__ __forceinline__ void lds_row10(const float* __restrict__ row, v2f* r) {  // 16-byte aligned
-  float4 v0 = reinterpret_cast<const float4*>(row)[0], v1 = reinterpret_cast<const float4*>(row)[1];
-  float2 v2 = reinterpret_cast<const float2*>(row)[4];
-  r[0] = (v2f){v0.x, v0.y}; r[1] = (v2f){v0.z, v0.w}; r[2] = (v2f){v1.x, v1.y}; r[3] = (v2f){v1.z, v1.w};
-  r[4] = (v2f){v2.x, v2.y};
-}
-__device__ __forceinline__ void lds_row10u(const float* __restrict__ row, v2f* r) {  // 8 mod 16
-  float2 v0 = reinterpret_cast<const float2*>(row)[0];
-  float4 v1 = reinterpret_cast<const float4*>(row + 2)[0], v2 = reinterpret_cast<const float4*>(row + 2)[1];
-  r[0] = (v2f){v0.x, v0.y}; r[1] = (v2f){v1.x, v1.y}; r[2] = (v2f){v1.z, v1.w}; r[3] = (v2f){v2.x, v2.y};
-  r[4] = (v2f){v2.z, v2.w};
-}
-
 // S[o] += relu(z), dS[o] += 1[z > 0] (dPi[o] + row[DCOL + o]) over the slots carrying MASK; z = Pi + row[COL..] + AT . a
 template <int RS, int COL, int DCOL, unsigned MASK>
 __device__ __forceinline__ float edge_pass_jvp(const uint4* __restrict__ slots, int nslots, const float* __restrict__ lds,
                                                const float* __restrict__ AT, const v2f* Pi, const v2f* dPi, v2f* S, v2f* dS) {
   float deg = 0.f;
   v2f wa[15];
-#pragma unroll
-  for (int i = 0; i < 15; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
-  if (nslots <= 0) return deg;
-  uint4 c0 = slots[0];
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 2, nslots - 1) * 64];
-    const unsigned w = c0.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY && (w & MASK)) {
-      const v2f a0 = splat(__uint_as_float(c0.y)), a1 = splat(__uint_as_float(c0.z)), a2 = splat(__uint_as_float(c0.w));
-      const float* row = lds + (int)(w & 0xFFFFu) * RS;
+  ld_attr(AT, wa);
+  for (SlotWalk<EDGE_PD, MASK> w(slots, nslots); w.more(); w.step())
+    if (w.live()) {
+      const SlotAttr a = slot_attr(w.slot());
+      const float* row = lds + w.row() * RS;
       v2f pj[5], dpj[5], z[5];
-      if (COL % 4 == 0) lds_row10(row + COL, pj); else lds_row10u(row + COL, pj);
-      if (DCOL % 4 == 0) lds_row10(row + DCOL, dpj); else lds_row10u(row + DCOL, dpj);
+      lds_row<COL>(row, pj);
+      lds_row<DCOL>(row, dpj);
       deg += 1.f;
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = Pi[p] + pj[p];
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[5 + p], a1, z[p]);
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[10 + p], a2, z[p]);
+      edge_preact(wa, a, Pi, pj, z);
 #pragma unroll
       for (int p = 0; p < 5; ++p) {
         S[p] += __builtin_elementwise_max(z[p], splat(0.f));
@@ -67,9 +41,6 @@ __device__ __forceinline__ float edge_pass_jvp(const uint4* __restrict__ slots, 
         dS[p] += (v2f){z[p].x > 0.f ? t.x : 0.f, z[p].y > 0.f ? t.y : 0.f};
       }
     }
-    c0 = c1;
-    c1 = nx;
-  }
   return deg;
 }
 
@@ -184,7 +155,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_jvp_tile(int n_tiles, int chun
   // 5 r mod 16 -- every slot, sixteen consecutive rows conflict-free -- as in k_f_tile.
   constexpr int RS = MIXED ? 60 : 20;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int slot_ = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot_ = xcd_tile_slot(chunk);
   if (slot_ >= n_tiles) return;
   const int tile = tile_list ? tile_list[slot_] : slot_;
   const float* TN = W + tnofs;
@@ -491,7 +462,6 @@ int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const
                              const float* v, float* out, int groups, hipStream_t st) {
   ARG_CHECK(p && p->tiled && (nl == 1 || p->mixed), "tiled JVP: tiled plans, single-layer blocks (mixed: any depth, last layer)");
   ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
-#define JVP_TILE_ARGS p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt, p->slice_off, p->slice_deg, p->ell, p->flags_p
   if (p->mixed) {
     using L = WLayout<3>;
     const int lofs = L::layer(nl - 1), tofs = L::tp_layer(nl, true, nl - 1), tnofs = L::tp_neu(nl);
@@ -500,12 +470,12 @@ int psignn_f_tile_jvp_groups(const psignn_plan* p, const float* W, int nl, const
     if (na > 0 && (groups & 1)) {   // tiles without Neumann nodes: 160-byte LDS rows, no Neumann branch
       const int chunk = (int)cdiv(na, 8);
       LAUNCH("k_jvp_tile", st, (k_jvp_tile<3, false, false><<<(unsigned)(chunk * 8), TILE_THREADS, (size_t)p->max_rows * 40 * 4, st>>>(
-          na, chunk, p->tile_order, JVP_TILE_ARGS, W, lofs, tofs, tnofs, h, prb, nrm, v, out)));
+          na, chunk, p->tile_order, PLAN_TILES_FLAGS(p), W, lofs, tofs, tnofs, h, prb, nrm, v, out)));
     }
     if (nb > 0 && (groups & 2)) {
       const int chunk = (int)cdiv(nb, 8);
       LAUNCH("k_jvp_tile", st, (k_jvp_tile<3, true, false><<<(unsigned)(chunk * 8), TILE_THREADS, (size_t)p->max_rows * 60 * 4, st>>>(
-          nb, chunk, p->tile_order + na, JVP_TILE_ARGS, W, lofs, tofs, tnofs, h, prb, nrm, v, out)));
+          nb, chunk, p->tile_order + na, PLAN_TILES_FLAGS(p), W, lofs, tofs, tnofs, h, prb, nrm, v, out)));
     }
     HIP_TRY(hipGetLastError());
     return PSIGNN_OK;
@@ -528,7 +498,7 @@ int psignn_f_tile_jvp_layer(const psignn_plan* p, const float* W, int nl, int l,
     return (int)(e && strcmp(e, "mfma") == 0);
   }());
   const int lofs = L::layer(l), tofs = L::tp_layer(nl, false, l);
-#define JVP_LAYER_ARGS (int)p->n_tiles, chunk, nullptr, JVP_TILE_ARGS, W, lofs, tofs, 0, h, prb, nullptr, v, out
+#define JVP_LAYER_ARGS (int)p->n_tiles, chunk, nullptr, PLAN_TILES_FLAGS(p), W, lofs, tofs, 0, h, prb, nullptr, v, out
   if (l == nl - 1) {
     if (use_mfma)
       LAUNCH("k_jvp_tile", st, (k_jvp_tile<2, false, true><<<(unsigned)(chunk * 8), TILE_THREADS, lds, st>>>(JVP_LAYER_ARGS)));

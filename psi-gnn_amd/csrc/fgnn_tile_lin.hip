@@ -183,7 +183,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_lin_build(int n_tiles, int chu
   using L = WLayout<P>;
   constexpr int RS = NEU ? LIN_RS_NEU : 20;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int slot_ = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot_ = xcd_tile_slot(chunk);
   if (slot_ >= n_tiles) return;
   const int tile = tile_list ? tile_list[slot_] : slot_;   // mixed plans: the tiles without Neumann nodes
   const int tid = threadIdx.x;
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_jvp_lin(int n_tiles, int chunk
   using L = WLayout<P>;
   constexpr int RS = NEU ? LIN_RS_NEU : 20;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int slot_ = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot_ = xcd_tile_slot(chunk);
   if (slot_ >= n_tiles) return;
   const int tile = tile_list ? tile_list[slot_] : slot_;
   const int tid = threadIdx.x;
@@ -920,7 +920,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin(int n_tiles, int chunk
                                                           const uint32_t* __restrict__ tslot, const float* __restrict__ rec,
                                                           const float* __restrict__ tw, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int tile = xcd_tile_slot(chunk);
   if (tile >= n_tiles) return;
   vjp_lin_tile<P, false>(tile, lds, C, W, lofs, tofs, slot, tslot, rec, tw, out, 0);
 }
@@ -938,7 +938,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin_mixed(int chunk, const
                                                                 const float* __restrict__ rec, const float* __restrict__ tw,
                                                                 float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int32_t e = tile_list[(blockIdx.x & 7) * chunk + (blockIdx.x >> 3)];
+  const int32_t e = tile_list[xcd_tile_slot(chunk)];
   if (e < 0) return;
   if (e & LIN_VNEU) vjp_lin_tile<P, true>(e & (LIN_VNEU - 1), lds, C, W, lofs, tofs, slot, tslot, rec, tw, out, tnofs);
   else vjp_lin_tile<P, false>(e, lds, C, W, lofs, tofs, slot, tslot, rec, tw, out, tnofs);
@@ -954,7 +954,7 @@ template <int P>
 __global__ __launch_bounds__(TILE_THREADS) void k_vjp_lin_batch(const LinBatchDesc* __restrict__ descs, int n_mesh, int n_slots, int chunk,
                                                                 int off_done, const float* __restrict__ W, int lofs, int tofs, int tnofs) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int slot = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot = xcd_tile_slot(chunk);
   if (slot >= n_slots) return;
   int m = 0;
   while (m + 1 < n_mesh && descs[m + 1].slot_base <= slot) ++m;   // wave-uniform scalar walk (a shard has few meshes)
@@ -1096,13 +1096,13 @@ extern "C" int psignn_lin_create_opts(psignn_lin_t** out, const psignn_plan_t* p
         e = hipMemcpy(fl, s->vlist, nt * 4, hipMemcpyDeviceToHost);
       }
       if (e == hipSuccess) {
-        // workgroup b of the grid reads entry (b & 7) * chunk + (b >> 3): the j-th Neumann tile goes where workgroup j reads, the
+        // workgroup b of the grid reads entry xcd_slot(b, chunk): the j-th Neumann tile goes where workgroup j reads, the
         // plain tiles fill the other entries in ascending order (neighbouring tiles stay on one XCD, as in the other tile kernels)
         for (size_t i = 0; i < nl; ++i) ord[i] = -1;
         size_t j = 0;
         for (size_t t = 0; t < nt; ++t)
           if (fl[t]) {
-            ord[(j & 7) * chunk + (j >> 3)] = (int32_t)t | LIN_VNEU;
+            ord[xcd_slot((unsigned)j, (int)chunk)] = (int32_t)t | LIN_VNEU;
             ++j;
           }
         s->n_vplain = (int)(nt - j);

@@ -19,58 +19,25 @@
 // flag beside the B rows in LDS: an IN slot (edge n -> u) whose sender n is a Neumann row uses Phi_neumann's weights and
 // accumulates into a third sum, out[u] += W1j_neu^T acc_n.  A tile without Neumann rows among tile + halo skips all of it.
 // All tensors in plan order.  The parameter-gradient records (PG) exist for the dirichlet family only.
-#include "fgnn_common.h"
+#define MV2_CH 0   // mv2 without chunk barriers: this file bounds the scalar-load hoisting with a PHASE() per product
+#include "tile_helpers.h"
 #include "internal.h"
 
-#define SLOT_IN 0x10000u
-#define SLOT_OUT 0x20000u
 #define VT 256
-#define PHASE() asm volatile("" ::: "memory")   // bounds scalar-load hoisting (see tile_helpers.h)
 #define PGREC 320   // floats per node of a parameter-gradient record: 20 groups of 16 (layout in k_vjp_tile_a)
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2f splat2(float a) { return (v2f){a, a}; }
-
-// acc[p] += WT[k][2p..2p+1] * x[k]   (transposed weight section: [in k][out o], o fastest)
-template <int K>
-__device__ __forceinline__ void mvf(const float* __restrict__ WT, const float* x, v2f* acc) {
-  const v2f* w = reinterpret_cast<const v2f*>(WT);
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const v2f xs = splat2(x[k]);
-#pragma unroll
-    for (int p = 0; p < 5; ++p) acc[p] = __builtin_elementwise_fma(w[k * 5 + p], xs, acc[p]);
-  }
-}
 // acc[p] += W[o*ld + off + 2p..2p+1] * g[o]   (ORIGINAL (out,in) layout = the transposed product, k pairs adjacent)
 template <int NO>
 __device__ __forceinline__ void mvb(const float* __restrict__ W, int ld, int off, const float* g, v2f* acc) {
 #pragma unroll
   for (int o = 0; o < NO; ++o) {
-    const v2f gs = splat2(g[o]);
+    const v2f gs = splat(g[o]);
 #pragma unroll
     for (int p = 0; p < 5; ++p) {
       const v2f w = (v2f){W[o * ld + off + 2 * p], W[o * ld + off + 2 * p + 1]};
       acc[p] = __builtin_elementwise_fma(w, gs, acc[p]);
     }
   }
-}
-__device__ __forceinline__ void ldu5(const float* __restrict__ p, v2f* r) {
-  const v2f* q = reinterpret_cast<const v2f*>(p);
-#pragma unroll
-  for (int i = 0; i < 5; ++i) r[i] = q[i];
-}
-__device__ __forceinline__ void row10(const float* __restrict__ row, v2f* pj) {  // 10 floats at a 16-byte aligned LDS address
-  float4 v0 = reinterpret_cast<const float4*>(row)[0], v1 = reinterpret_cast<const float4*>(row)[1];
-  float2 v2 = reinterpret_cast<const float2*>(row)[4];
-  pj[0] = (v2f){v0.x, v0.y}; pj[1] = (v2f){v0.z, v0.w}; pj[2] = (v2f){v1.x, v1.y}; pj[3] = (v2f){v1.z, v1.w};
-  pj[4] = (v2f){v2.x, v2.y};
-}
-__device__ __forceinline__ void row10u(const float* __restrict__ row, v2f* pj) {  // 8-byte aligned start
-  float2 v0 = reinterpret_cast<const float2*>(row)[0];
-  float4 v1 = reinterpret_cast<const float4*>(row + 2)[0], v2 = reinterpret_cast<const float4*>(row + 2)[1];
-  pj[0] = (v2f){v0.x, v0.y}; pj[1] = (v2f){v1.x, v1.y}; pj[2] = (v2f){v1.z, v1.w}; pj[3] = (v2f){v2.x, v2.y};
-  pj[4] = (v2f){v2.z, v2.w};
 }
 
 // ---------------------------------------------------------------------------------------------- pass A
@@ -81,43 +48,26 @@ __device__ __forceinline__ float pass_fwd(const uint4* __restrict__ slots, int n
                                           const float* __restrict__ AT, const v2f* Pi, v2f* S, v2f* cnt, v2f* m) {
   float deg = 0.f;
   v2f wa[15];
-#pragma unroll
-  for (int i = 0; i < 15; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
-  if (nslots <= 0) return deg;
-  uint4 c0 = slots[0];
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 2, nslots - 1) * 64];
-    const unsigned w = c0.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY && (w & MASK)) {
-      const v2f a0 = splat2(__uint_as_float(c0.y)), a1 = splat2(__uint_as_float(c0.z)), a2 = splat2(__uint_as_float(c0.w));
-      const float* row = lds + (int)(w & 0xFFFFu) * RS + COL;
+  ld_attr(AT, wa);
+  for (SlotWalk<EDGE_PD, MASK> w(slots, nslots); w.more(); w.step())
+    if (w.live()) {
+      const SlotAttr a = slot_attr(w.slot());
       v2f pj[5], z[5];
-      if (COL % 4 == 0) row10(row, pj); else row10u(row, pj);
+      lds_row<COL>(lds + w.row() * RS, pj);
       deg += 1.f;
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = Pi[p] + pj[p];
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[5 + p], a1, z[p]);
-#pragma unroll
-      for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[10 + p], a2, z[p]);
+      edge_preact(wa, a, Pi, pj, z);
 #pragma unroll
       for (int p = 0; p < 5; ++p) {
-        S[p] += __builtin_elementwise_max(z[p], splat2(0.f));
+        S[p] += __builtin_elementwise_max(z[p], splat(0.f));
         const v2f mk = (v2f){z[p].x > 0.f ? 1.f : 0.f, z[p].y > 0.f ? 1.f : 0.f};
         cnt[p] += mk;
         if (PG) {
-          m[p] = __builtin_elementwise_fma(mk, a0, m[p]);
-          m[5 + p] = __builtin_elementwise_fma(mk, a1, m[5 + p]);
-          m[10 + p] = __builtin_elementwise_fma(mk, a2, m[10 + p]);
+          m[p] = __builtin_elementwise_fma(mk, a.a0, m[p]);
+          m[5 + p] = __builtin_elementwise_fma(mk, a.a1, m[5 + p]);
+          m[10 + p] = __builtin_elementwise_fma(mk, a.a2, m[10 + p]);
         }
       }
     }
-    c0 = c1;
-    c1 = nx;
-  }
   return deg;
 }
 
@@ -178,7 +128,7 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
   constexpr int REC = P == 3 ? 480 : PGREC;
   constexpr int RS = MIXED ? 32 : 20;   // [Pj_to 10 | Pj_from 10 (| Pj_neu 10 | pad 2)]
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int slot_ = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int slot_ = xcd_tile_slot(chunk);
   if (slot_ >= n_tiles) return;
   const int tile = tile_list ? tile_list[slot_] : slot_;
   const int tid = threadIdx.x;
@@ -199,11 +149,11 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
     }
     v2f ta[5], tb[5];
 #pragma unroll
-    for (int p = 0; p < 5; ++p) ta[p] = tb[p] = splat2(0.f);
+    for (int p = 0; p < 5; ++p) ta[p] = tb[p] = splat(0.f);
     PHASE();
-    mvf<D>(T + L::T_W1J_TO, xr, ta);
+    mv2<D>(T + L::T_W1J_TO, xr, ta);
     PHASE();
-    mvf<D>(T + L::T_W1J_FR, xr, tb);
+    mv2<D>(T + L::T_W1J_FR, xr, tb);
     float4* q = reinterpret_cast<float4*>(lds + row * RS);
     q[0] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
     q[1] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
@@ -212,9 +162,9 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
     q[4] = make_float4(tb[3].x, tb[3].y, tb[4].x, tb[4].y);
     if (MIXED) {
 #pragma unroll
-      for (int p = 0; p < 5; ++p) ta[p] = splat2(0.f);
+      for (int p = 0; p < 5; ++p) ta[p] = splat(0.f);
       PHASE();
-      mvf<D>(W + tnofs + L::N_W1J, xr, ta);
+      mv2<D>(W + tnofs + L::N_W1J, xr, ta);
       q[5] = make_float4(ta[0].x, ta[0].y, ta[1].x, ta[1].y);
       q[6] = make_float4(ta[2].x, ta[2].y, ta[3].x, ta[3].y);
       q[7] = make_float4(ta[4].x, ta[4].y, 0.f, 0.f);
@@ -252,35 +202,35 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
     v2f Pn[5], S_n[5], c_n[5], m_n[PG ? 15 : 1];
     if (PG) {
 #pragma unroll
-      for (int i = 0; i < 15; ++i) m_n[PG ? i : 0] = splat2(0.f);
+      for (int i = 0; i < 15; ++i) m_n[PG ? i : 0] = splat(0.f);
     }
-    ldu5(TN + L::N_B1, Pn);
+    ld5(TN + L::N_B1, Pn);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) S_n[p] = c_n[p] = splat2(0.f);
+    for (int p = 0; p < 5; ++p) S_n[p] = c_n[p] = splat(0.f);
     PHASE();
-    mvf<D>(TN + L::N_W1I, x, Pn);
+    mv2<D>(TN + L::N_W1I, x, Pn);
     const float deg_out = pass_fwd<RS, 2 * D, SLOT_OUT, PG>(slots, nslots, lds, TN + L::N_A, Pn, S_n, c_n, m_n);
     v2f q2[5], gN[5], hid2[5], y2[5];
-    ldu5(TN + L::N_NB1, q2);
-    ldu5(TN + L::N_gN, gN);
+    ld5(TN + L::N_NB1, q2);
+    ld5(TN + L::N_gN, gN);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) q2[p] = __builtin_elementwise_fma(splat2(deg_out), gN[p], q2[p]);
+    for (int p = 0; p < 5; ++p) q2[p] = __builtin_elementwise_fma(splat(deg_out), gN[p], q2[p]);
     PHASE();
-    mvf<D>(TN + L::N_N1H, x, q2);
+    mv2<D>(TN + L::N_N1H, x, q2);
     PHASE();
-    mvf<D>(TN + L::N_GN, reinterpret_cast<const float*>(S_n), q2);
+    mv2<D>(TN + L::N_GN, reinterpret_cast<const float*>(S_n), q2);
     float pq[P + 2];
 #pragma unroll
     for (int k = 0; k < P; ++k) pq[k] = prb[n * P + k];
     pq[P] = nrm[n * 2];
     pq[P + 1] = nrm[n * 2 + 1];
     PHASE();
-    mvf<P + 2>(TN + L::N_N1P, pq, q2);
+    mv2<P + 2>(TN + L::N_N1P, pq, q2);
 #pragma unroll
-    for (int p = 0; p < 5; ++p) hid2[p] = __builtin_elementwise_max(q2[p], splat2(0.f));
-    ldu5(TN + L::N_NB2, y2);
+    for (int p = 0; p < 5; ++p) hid2[p] = __builtin_elementwise_max(q2[p], splat(0.f));
+    ld5(TN + L::N_NB2, y2);
     PHASE();
-    mvf<D>(TN + L::N_N2, reinterpret_cast<const float*>(hid2), y2);
+    mv2<D>(TN + L::N_N2, reinterpret_cast<const float*>(hid2), y2);
     float y[D], w[D], dy[D], mu = 0.f;
 #pragma unroll
     for (int o = 0; o < D; ++o) {
@@ -291,7 +241,7 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
     ln_fwd_bwd<L>(W, mu, y, w, dy);
     v2f dq2[5], g[5], dS_n[5];
 #pragma unroll
-    for (int p = 0; p < 5; ++p) dq2[p] = g[p] = dS_n[p] = splat2(0.f);
+    for (int p = 0; p < 5; ++p) dq2[p] = g[p] = dS_n[p] = splat(0.f);
     PHASE();
     mvb<D>(Un + L::NEU_W2, D, 0, dy, dq2);
     float dq[D];
@@ -345,7 +295,7 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
       rec_group(r + 24 * 16, gn, D);                                                    // 24: sum of masked cotangents, own out-edges
       v2f dm[5];
 #pragma unroll
-      for (int p = 0; p < 5; ++p) dm[p] = splat2(0.f);
+      for (int p = 0; p < 5; ++p) dm[p] = splat(0.f);
       PHASE();
       mvb<D>(Un + L::NEU_W1, L::NEU_CAT, D, dq, dm);
       rec_group(r + 25 * 16, reinterpret_cast<const float*>(dm), D);                    // 25: d mp_n
@@ -371,17 +321,17 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
   v2f m_to[PG ? 15 : 1], m_fr[PG ? 15 : 1];
   if (PG) {
 #pragma unroll
-    for (int i = 0; i < 15; ++i) m_to[PG ? i : 0] = m_fr[PG ? i : 0] = splat2(0.f);
+    for (int i = 0; i < 15; ++i) m_to[PG ? i : 0] = m_fr[PG ? i : 0] = splat(0.f);
   }
-  ldu5(T + L::T_B1_TO, Pt);
-  ldu5(T + L::T_B1_FR, Pf);
+  ld5(T + L::T_B1_TO, Pt);
+  ld5(T + L::T_B1_FR, Pf);
 #pragma unroll
-  for (int p = 0; p < 5; ++p) S_to[p] = S_fr[p] = c_to[p] = c_fr[p] = splat2(0.f);
+  for (int p = 0; p < 5; ++p) S_to[p] = S_fr[p] = c_to[p] = c_fr[p] = splat(0.f);
   PHASE();
-  mvf<D>(T + L::T_W1I_TO, x, Pt);
+  mv2<D>(T + L::T_W1I_TO, x, Pt);
   const float deg_in = pass_fwd<RS, 0, SLOT_IN, PG>(slots, nslots, lds, T + L::T_A_TO, Pt, S_to, c_to, m_to);
   PHASE();
-  mvf<D>(T + L::T_W1I_FR, x, Pf);
+  mv2<D>(T + L::T_W1I_FR, x, Pf);
   const float deg_out = pass_fwd<RS, D, SLOT_OUT, PG>(slots, nslots, lds, T + L::T_A_FR, Pf, S_fr, c_fr, m_fr);
   const float* Wf = W + lofs + L::L_FOLD;
   const float* Wu = W + lofs + L::L_UPD;
@@ -402,25 +352,25 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
   for (int k = 0; k < P; ++k) al = fmaf(Wa[3 * D + k], pq[k], al);
   al = 1.f / (1.f + expf(-al));
   v2f q2[5], g1[5], g2[5], upd2[5], hid2[5];
-  ldu5(T + L::T_HB, q2);
-  ldu5(T + L::T_gTO, g1);
-  ldu5(T + L::T_gFR, g2);
+  ld5(T + L::T_HB, q2);
+  ld5(T + L::T_gTO, g1);
+  ld5(T + L::T_gFR, g2);
 #pragma unroll
   for (int p = 0; p < 5; ++p)
-    q2[p] = __builtin_elementwise_fma(splat2(deg_in), g1[p], __builtin_elementwise_fma(splat2(deg_out), g2[p], q2[p]));
+    q2[p] = __builtin_elementwise_fma(splat(deg_in), g1[p], __builtin_elementwise_fma(splat(deg_out), g2[p], q2[p]));
   PHASE();
-  mvf<D>(T + L::T_U1H, x, q2);
+  mv2<D>(T + L::T_U1H, x, q2);
   PHASE();
-  mvf<D>(T + L::T_GTO, sto, q2);
+  mv2<D>(T + L::T_GTO, sto, q2);
   PHASE();
-  mvf<D>(T + L::T_GFR, sfr, q2);
+  mv2<D>(T + L::T_GFR, sfr, q2);
   PHASE();
-  mvf<P>(T + L::T_U1P, pq, q2);
+  mv2<P>(T + L::T_U1P, pq, q2);
 #pragma unroll
-  for (int p = 0; p < 5; ++p) hid2[p] = __builtin_elementwise_max(q2[p], splat2(0.f));
-  ldu5(T + L::T_C2, upd2);
+  for (int p = 0; p < 5; ++p) hid2[p] = __builtin_elementwise_max(q2[p], splat(0.f));
+  ld5(T + L::T_C2, upd2);
   PHASE();
-  mvf<D>(T + L::T_U2, reinterpret_cast<const float*>(hid2), upd2);
+  mv2<D>(T + L::T_U2, reinterpret_cast<const float*>(hid2), upd2);
   const float* qf = reinterpret_cast<const float*>(q2);
   const float* upd = reinterpret_cast<const float*>(upd2);
   float y[D], mu = 0.f;
@@ -451,7 +401,7 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
   // ---- update MLP, gate, folded second Phi layer
   v2f dq2[5];
 #pragma unroll
-  for (int p = 0; p < 5; ++p) dq2[p] = splat2(0.f);
+  for (int p = 0; p < 5; ++p) dq2[p] = splat(0.f);
   PHASE();
   mvb<D>(Wu + L::UPD_W2, D, 0, dupd, dq2);
   float dq[D];
@@ -462,9 +412,9 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
   v2f dS_to[5], dS_fr[5];
 #pragma unroll
   for (int p = 0; p < 5; ++p) {
-    g[p] = __builtin_elementwise_fma((v2f){Wa[2 * p], Wa[2 * p + 1]}, splat2(dal), g[p]);
-    dS_to[p] = (v2f){Wf[L::F_ATO + 2 * p], Wf[L::F_ATO + 2 * p + 1]} * splat2(dal);
-    dS_fr[p] = (v2f){Wf[L::F_AFR + 2 * p], Wf[L::F_AFR + 2 * p + 1]} * splat2(dal);
+    g[p] = __builtin_elementwise_fma((v2f){Wa[2 * p], Wa[2 * p + 1]}, splat(dal), g[p]);
+    dS_to[p] = (v2f){Wf[L::F_ATO + 2 * p], Wf[L::F_ATO + 2 * p + 1]} * splat(dal);
+    dS_fr[p] = (v2f){Wf[L::F_AFR + 2 * p], Wf[L::F_AFR + 2 * p + 1]} * splat(dal);
   }
   PHASE();
   mvb<D>(Wf + L::F_GTO, D, 0, dq, dS_to);   // dS_to[k] = sum_o G_to[o][k] dq[o] + a_to[k] dal
@@ -522,12 +472,12 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
     rec_group(r + 128, gf, D);                                                 // 8: same, out-edges
     v2f dm[5];
 #pragma unroll
-    for (int p = 0; p < 5; ++p) dm[p] = (v2f){Wa[D + 2 * p], Wa[D + 2 * p + 1]} * splat2(dal);
+    for (int p = 0; p < 5; ++p) dm[p] = (v2f){Wa[D + 2 * p], Wa[D + 2 * p + 1]} * splat(dal);
     PHASE();
     mvb<D>(Wu + L::UPD_W1, L::CAT, D, dq, dm);
     rec_group(r + 144, reinterpret_cast<const float*>(dm), D);                 // 9: d mp_to
 #pragma unroll
-    for (int p = 0; p < 5; ++p) dm[p] = (v2f){Wa[2 * D + 2 * p], Wa[2 * D + 2 * p + 1]} * splat2(dal);
+    for (int p = 0; p < 5; ++p) dm[p] = (v2f){Wa[2 * D + 2 * p], Wa[2 * D + 2 * p + 1]} * splat(dal);
     PHASE();
     mvb<D>(Wu + L::UPD_W1, L::CAT, 2 * D, dq, dm);
     rec_group(r + 160, reinterpret_cast<const float*>(dm), D);                 // 10: d mp_from
@@ -577,21 +527,18 @@ template <int RS, int PC, int DC, unsigned MASK>
 __device__ __forceinline__ void pass_rev(const uint4* __restrict__ slots, int nslots, const float* __restrict__ lds,
                                          const float* __restrict__ AT, float flip, const v2f* Pj, v2f* acc) {
   v2f wa[15];
-#pragma unroll
-  for (int i = 0; i < 15; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
-  if (nslots <= 0) return;
-  uint4 c0 = slots[0];
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 2, nslots - 1) * 64];
-    const unsigned w = c0.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY && (w & MASK)) {
-      const v2f a0 = splat2(flip * __uint_as_float(c0.y)), a1 = splat2(flip * __uint_as_float(c0.z));
-      const v2f a2 = splat2(__uint_as_float(c0.w));
-      const float* row = lds + (int)(w & 0xFFFFu) * RS;
+  ld_attr(AT, wa);
+  for (SlotWalk<EDGE_PD, MASK> w(slots, nslots); w.more(); w.step())
+    if (w.live()) {
+      // (the chain of edge_preact, written out: through the helper k_vjp_tile_b<2, false, false> needs 84 VGPRs instead of 80,
+      // five waves per SIMD instead of six)
+      const uint4& c0 = w.slot();
+      const v2f a0 = splat(flip * __uint_as_float(c0.y)), a1 = splat(flip * __uint_as_float(c0.z));
+      const v2f a2 = splat(__uint_as_float(c0.w));
+      const float* row = lds + w.row() * RS;
       v2f pi[5], ds[5], z[5];
-      if (PC % 4 == 0) row10(row + PC, pi); else row10u(row + PC, pi);
-      if (DC % 4 == 0) row10(row + DC, ds); else row10u(row + DC, ds);
+      lds_row<PC>(row, pi);
+      lds_row<DC>(row, ds);
 #pragma unroll
       for (int p = 0; p < 5; ++p) z[p] = pi[p] + Pj[p];
 #pragma unroll
@@ -603,29 +550,17 @@ __device__ __forceinline__ void pass_rev(const uint4* __restrict__ slots, int ns
 #pragma unroll
       for (int p = 0; p < 5; ++p) acc[p] += (v2f){z[p].x > 0.f ? ds[p].x : 0.f, z[p].y > 0.f ? ds[p].y : 0.f};
     }
-    c0 = c1;
-    c1 = nx;
-  }
 }
 
-// IN slots of a mixed plan: the sender n of edge (n -> u) is an interior row (Phi_from: weights AF, projection Pjf, sum af) or
-// a Neumann row (Phi_neumann: AN, Pjn, an) -- nflag[row] tells; both kinds keep Pi and dS in the second half of their B row.
 // one IN slot seen from the receiver: acc[o] += 1[row[o] + Pj[o] + AT . (-a0, -a1, a2) > 0] * row[10 + o]   (half-row [P | dS])
 __device__ __forceinline__ void rev_slot_in(const float* __restrict__ row, const float* __restrict__ AT, const uint4& c, const v2f* Pj,
                                             v2f* acc) {
   const v2f* wa = reinterpret_cast<const v2f*>(AT);   // wave-uniform address: the weights stay in scalar registers
-  const v2f a0 = splat2(-__uint_as_float(c.y)), a1 = splat2(-__uint_as_float(c.z)), a2 = splat2(__uint_as_float(c.w));
+  const SlotAttr a = slot_attr(c, -1.f);
   v2f pi[5], ds[5], z[5];
-  row10(row, pi);
-  row10u(row + D, ds);
-#pragma unroll
-  for (int p = 0; p < 5; ++p) z[p] = pi[p] + Pj[p];
-#pragma unroll
-  for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
-#pragma unroll
-  for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[5 + p], a1, z[p]);
-#pragma unroll
-  for (int p = 0; p < 5; ++p) z[p] = __builtin_elementwise_fma(wa[10 + p], a2, z[p]);
+  lds_row<0>(row, pi);
+  lds_row<D>(row, ds);
+  edge_preact(wa, a, pi, Pj, z);
 #pragma unroll
   for (int p = 0; p < 5; ++p) acc[p] += (v2f){z[p].x > 0.f ? ds[p].x : 0.f, z[p].y > 0.f ? ds[p].y : 0.f};
 }
@@ -637,21 +572,12 @@ __device__ __forceinline__ void pass_rev_in_mixed(const uint4* __restrict__ slot
                                                   const int32_t* __restrict__ nflag, const float* __restrict__ AF,
                                                   const float* __restrict__ AN, const v2f* Pjf, const v2f* Pjn, v2f* af,
                                                   v2f* an) {
-  if (nslots <= 0) return;
-  uint4 c0 = slots[0];
-  uint4 c1 = slots[(int64_t)min(1, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 2, nslots - 1) * 64];
-    const unsigned w = c0.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY && (w & SLOT_IN)) {
-      const int ri = (int)(w & 0xFFFFu);
-      const float* row = lds + ri * RS;
-      if (nflag[ri] != 0) rev_slot_in(row, AN, c0, Pjn, an);   // (rare: boundary rows only)
-      else rev_slot_in(row, AF, c0, Pjf, af);
+  for (SlotWalk<EDGE_PD, SLOT_IN> w(slots, nslots); w.more(); w.step())
+    if (w.live()) {
+      const float* row = lds + w.row() * RS;
+      if (nflag[w.row()] != 0) rev_slot_in(row, AN, w.slot(), Pjn, an);   // (rare: boundary rows only)
+      else rev_slot_in(row, AF, w.slot(), Pjf, af);
     }
-    c0 = c1;
-    c1 = nx;
-  }
 }
 
 template <int P, bool MIXED, bool PG>
@@ -670,7 +596,7 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_b(int n_tiles, int chunk, const
   // fit a CU where three did (the kernel needs < 96 VGPRs: LDS was what held it at three waves per SIMD); same bytes from memory.
   constexpr int RS = 20;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int tile = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  const int tile = xcd_tile_slot(chunk);
   if (tile >= n_tiles) return;
   const int tid = threadIdx.x;
   const int32_t t0 = tile_ptr[tile];
@@ -710,26 +636,26 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_b(int n_tiles, int chunk, const
   load10(h + u * D, x);
   v2f Pj[5], at[5], af[5], an[5];
 #pragma unroll
-  for (int p = 0; p < 5; ++p) Pj[p] = at[p] = af[p] = an[p] = splat2(0.f);
+  for (int p = 0; p < 5; ++p) Pj[p] = at[p] = af[p] = an[p] = splat(0.f);
   // OUT slots: edge (u -> n) is an in-edge of n (Phi_to of n): Pt[n], dS_to[n] = first half row, attr = the slot's own
   // (T_A_TO holds the mirrored rows -> flip = -1 restores the plain attr weights)
   PHASE();
-  mvf<D>(T + L::T_W1J_TO, x, Pj);
+  mv2<D>(T + L::T_W1J_TO, x, Pj);
   pass_rev<RS, 0, D, SLOT_OUT>(slots, nslots, lds, T + L::T_A_TO, -1.f, Pj, at);
   __syncthreads();   // every wave is done with the first halves
   stage(1);
   __syncthreads();
   // IN slots: edge (n -> u) is an out-edge of n (Phi_from of n): Pf[n], dS_fr[n] = second half row, attr = mirror of the slot's
 #pragma unroll
-  for (int p = 0; p < 5; ++p) Pj[p] = splat2(0.f);
+  for (int p = 0; p < 5; ++p) Pj[p] = splat(0.f);
   PHASE();
-  mvf<D>(T + L::T_W1J_FR, x, Pj);
+  mv2<D>(T + L::T_W1J_FR, x, Pj);
   if (MIXED && tile_neu) {
     v2f Pjn[5];
 #pragma unroll
-    for (int p = 0; p < 5; ++p) Pjn[p] = splat2(0.f);
+    for (int p = 0; p < 5; ++p) Pjn[p] = splat(0.f);
     PHASE();
-    mvf<D>(W + tnofs + L::N_W1J, x, Pjn);
+    mv2<D>(W + tnofs + L::N_W1J, x, Pjn);
     pass_rev_in_mixed<RS>(slots, nslots, lds, nflag, T + L::T_A_FR, W + tnofs + L::N_A, Pj, Pjn, af, an);
   } else {
     pass_rev<RS, 0, D, SLOT_IN>(slots, nslots, lds, T + L::T_A_FR, -1.f, Pj, af);
@@ -774,7 +700,6 @@ static int tile_vjp_launch(const psignn_plan* p, const float* W, int nl, const f
   const unsigned grid = (unsigned)(chunk * 8);
   const size_t lds_b = (size_t)p->max_rows * (20 + (p->mixed ? 1 : 0)) * 4;
   ARG_CHECK(lds_b <= 160 * 1024, "tile + halo rows exceed the LDS budget of the tiled VJP");
-#define VJP_PLAN p->tile_ptr, p->tile_slice, p->halo, p->halo_cnt, p->slice_off, p->slice_deg, p->ell, p->flags_p
   if (p->mixed) {
     using L = WLayout<3>;
     const int lofs = L::layer(nl - 1), tofs = L::tp_layer(nl, true, nl - 1), tnofs = L::tp_neu(nl);
@@ -783,26 +708,26 @@ static int tile_vjp_launch(const psignn_plan* p, const float* W, int nl, const f
       const int ch = (int)cdiv(na, 8);
       if (rec)
         LAUNCH("k_pgrad_tile_a", st, (k_vjp_tile_a<3, false, true><<<(unsigned)(ch * 8), VT, (size_t)p->max_rows * 20 * 4, st>>>(
-            na, ch, p->tile_order, VJP_PLAN, W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
+            na, ch, p->tile_order, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
       else
         LAUNCH("k_vjp_tile_a", st, (k_vjp_tile_a<3, false, false><<<(unsigned)(ch * 8), VT, (size_t)p->max_rows * 20 * 4, st>>>(
-            na, ch, p->tile_order, VJP_PLAN, W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
+            na, ch, p->tile_order, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
     }
     if (nb > 0) {
       const int ch = (int)cdiv(nb, 8);
       if (rec)
         LAUNCH("k_pgrad_tile_a", st, (k_vjp_tile_a<3, true, true><<<(unsigned)(ch * 8), VT, (size_t)p->max_rows * 32 * 4, st>>>(
-            nb, ch, p->tile_order + na, VJP_PLAN, W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
+            nb, ch, p->tile_order + na, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
       else
         LAUNCH("k_vjp_tile_a", st, (k_vjp_tile_a<3, true, false><<<(unsigned)(ch * 8), VT, (size_t)p->max_rows * 32 * 4, st>>>(
-            nb, ch, p->tile_order + na, VJP_PLAN, W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
+            nb, ch, p->tile_order + na, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, tnofs, h, prb, nrm, w, work, out, rec)));
     }
     if (rec)
       LAUNCH("k_pgrad_tile_b", st, (k_vjp_tile_b<3, true, true><<<grid, VT, lds_b, st>>>(
-          (int)p->n_tiles, chunk, VJP_PLAN, W, nl, lofs, tofs, tnofs, h, work, out, rec)));
+          (int)p->n_tiles, chunk, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, tnofs, h, work, out, rec)));
     else
       LAUNCH("k_vjp_tile_b", st, (k_vjp_tile_b<3, true, false><<<grid, VT, lds_b, st>>>(
-          (int)p->n_tiles, chunk, VJP_PLAN, W, nl, lofs, tofs, tnofs, h, work, out, rec)));
+          (int)p->n_tiles, chunk, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, tnofs, h, work, out, rec)));
     HIP_TRY(hipGetLastError());
     return PSIGNN_OK;
   }
@@ -821,8 +746,8 @@ static int tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, c
   const size_t lds_b = (size_t)p->max_rows * 20 * 4;
   ARG_CHECK(lds_b <= 160 * 1024, "tile + halo rows exceed the LDS budget of the tiled VJP");
   const int lofs = L::layer(l), tofs = L::tp_layer(nl, false, l);
-#define VJP_ARGS_A (int)p->n_tiles, chunk, nullptr, VJP_PLAN, W, nl, lofs, tofs, 0, h, prb, nullptr, w, work, out, rec
-#define VJP_ARGS_B (int)p->n_tiles, chunk, VJP_PLAN, W, nl, lofs, tofs, 0, h, work, out, rec
+#define VJP_ARGS_A (int)p->n_tiles, chunk, nullptr, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, 0, h, prb, nullptr, w, work, out, rec
+#define VJP_ARGS_B (int)p->n_tiles, chunk, PLAN_TILES_FLAGS(p), W, nl, lofs, tofs, 0, h, work, out, rec
   if (l == nl - 1) {
     if (rec) {
       LAUNCH("k_pgrad_tile_a", st, (k_vjp_tile_a<2, false, true><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));

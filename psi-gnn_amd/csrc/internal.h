@@ -4,6 +4,11 @@
 #include "common.h"
 #include "workspace.h"
 
+// ---- the tile structures of a plan as the leading pointer arguments of a tile kernel (the order of TileCtx, common.h),
+// without and with the plan-order flags
+#define PLAN_TILES(p) (p)->tile_ptr, (p)->tile_slice, (p)->halo, (p)->halo_cnt, (p)->slice_off, (p)->slice_deg, (p)->ell
+#define PLAN_TILES_FLAGS(p) PLAN_TILES(p), (p)->flags_p
+
 // ---- fgnn.hip
 int psignn_f_eval_p(const psignn_plan_t* p, const float* W, int nl, const float* h, const int32_t* hsel, int64_t hstride,
                     const float* h0, const float* prb, const float* nrm, float* out, float* work, hipStream_t st);

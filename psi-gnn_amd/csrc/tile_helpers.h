@@ -1,5 +1,7 @@
-// Device helpers shared by the tile kernels (fgnn_tile.hip, dsgps_tile.hip): packed-fp32 matvecs on the transposed
-// weight blocks and the pair-merged slot walk of one edge direction (gfx950).
+// The one device header of every tile kernel (fgnn_tile, fgnn_tile_jvp, fgnn_tile_vjp, fgnn_tile_jr, fgnn_tile_lin, dsgps_tile,
+// dss_tile; gfx950): packed-fp32 matvecs on the transposed weight blocks, the XCD tile-slot order, and the pieces of a walk over
+// the pair-merged slots of one edge direction -- the pipelined walk itself (SlotWalk), the LDS row loader (lds_row / lds_row8)
+// and the edge pre-activation (ld_attr, slot_attr, edge_preact).
 #pragma once
 #include "fgnn_common.h"
 
@@ -13,7 +15,7 @@
 // Workgroup = 4 waves = TILE_MAX lanes.  (A fifth wave that only helps with the halo rows of stage 1 was tried:
 // 79 us instead of 67 us per 1M-node evaluation -- it costs a wave slot per workgroup for the whole residency.)
 #define TILE_THREADS 256
-#define EDGE_PD 2   // prefetch distance of the slot loads in edge_pass
+#define EDGE_PD 2   // prefetch distance of the slot loads of every single-direction walk (SlotWalk)
 
 // Compiler-level memory barrier between the phases of a kernel.  The tile kernels read > 1 000 wave-uniform weights;
 // fully unrolled, the compiler hoists all their scalar loads to the top and then spills hundreds of SGPRs into VGPR
@@ -31,7 +33,7 @@ __device__ __forceinline__ v2f splat(float a) { return (v2f){a, a}; }
 // A 10 x 10 block is 100 wave-uniform weights (D x D in general) -- with the wave's other live SGPRs more than the 102 there are, and the
 // compiler, which loads a whole block ahead of its first use, then parks the excess in VGPR lanes (v_writelane /
 // v_readlane: 36 VALU slots per stage-1 round in round 1's build).  A compiler barrier every MV2_CH inputs keeps at most
-// MV2_CH x 10 weights in flight.
+// MV2_CH x 10 weights in flight.  MV2_CH 0 (fgnn_tile_vjp.hip): no chunk barriers, the caller's PHASE() per product is the bound.
 #ifndef MV2_CH
 #define MV2_CH 5
 #endif
@@ -59,7 +61,7 @@ __device__ __forceinline__ void mv2(const float* __restrict__ WT, const float* x
 #endif
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    if (MV2_CH > 0 && k > 0 && k % MV2_CH == 0) {
+    if (MV2_CH > 0 && k > 0 && k % (MV2_CH > 0 ? MV2_CH : 1) == 0) {   // (MV2_CH 0: no chunk barriers)
       PHASE();
 #if MV2_LAUNDER
       asm volatile("" : "+s"(zero) : "v"(acc[0]), "v"(acc[NPAIR - 1]));
@@ -82,6 +84,107 @@ __device__ __forceinline__ v2f quad_pair(const float4* v, int i) {
   return (i & 1) ? (v2f){v[i >> 1].z, v[i >> 1].w} : (v2f){v[i >> 1].x, v[i >> 1].y};
 }
 
+// Workgroup b of a grid of 8 * chunk runs tile slot (b & 7) * chunk + (b >> 3): workgroups are dealt round-robin to the eight
+// XCDs, so each XCD's L2 sees one contiguous run of `chunk` tiles.
+__host__ __device__ __forceinline__ unsigned xcd_slot(unsigned b, int chunk) { return (b & 7) * chunk + (b >> 3); }
+__device__ __forceinline__ unsigned xcd_tile_slot(int chunk) { return xcd_slot(blockIdx.x, chunk); }
+
+// ---- the pieces of a single-direction slot walk ------------------------------------------------------------------
+// D floats of an LDS row as NPAIR pairs: row (16-byte aligned) + COL.  The column is a template parameter so that the
+// choice between the two load shapes is made at compile time.
+template <int COL>
+__device__ __forceinline__ void lds_row(const float* __restrict__ row, v2f* pj) {
+  row += COL;
+  if (COL % 4 == 0) {  // 16-byte aligned start: D / 4 b128 and, when D is not a multiple of 4, a b64 (D = 10: b128, b128, b64)
+    float4 v[D / 4];
+#pragma unroll
+    for (int q = 0; q < D / 4; ++q) v[q] = reinterpret_cast<const float4*>(row)[q];
+#pragma unroll
+    for (int p = 0; p < D / 4 * 2; ++p) pj[p] = quad_pair(v, p);
+    if (D % 4) {
+      float2 t = reinterpret_cast<const float2*>(row)[NPAIR - 1];
+      pj[NPAIR - 1] = (v2f){t.x, t.y};
+    }
+  } else {             // start at 8 mod 16 (D = 2 mod 4 only): b64, then D / 4 b128 (D = 10: b64, b128, b128)
+    static_assert(COL % 4 == 0 || D % 4 == 2, "a row segment starting at 8 mod 16 has 4 q + 2 floats");
+    float2 t = reinterpret_cast<const float2*>(row)[0];
+    float4 v[D / 4];
+#pragma unroll
+    for (int q = 0; q < D / 4; ++q) v[q] = reinterpret_cast<const float4*>(row + 2)[q];
+    pj[0] = (v2f){t.x, t.y};
+#pragma unroll
+    for (int p = 0; p < D / 4 * 2; ++p) pj[1 + p] = quad_pair(v, p);
+  }
+}
+// the same from a row that is only 8-byte aligned (120-byte rows): NPAIR b64
+__device__ __forceinline__ void lds_row8(const float* __restrict__ row, v2f* pj) {
+#pragma unroll
+  for (int i = 0; i < NPAIR; ++i) {
+    const float2 t = reinterpret_cast<const float2*>(row)[i];
+    pj[i] = (v2f){t.x, t.y};
+  }
+}
+
+// the attr block AT (3 x D wave-uniform floats, transposed) of one Phi module
+__device__ __forceinline__ void ld_attr(const float* __restrict__ AT, v2f* wa) {
+#pragma unroll
+  for (int i = 0; i < 3 * NPAIR; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
+}
+// the attr (a0, a1, a2) of a slot, each splat over a pair; the reverse passes multiply `flip` into a0, a1 before the splat
+struct SlotAttr { v2f a0, a1, a2; };
+__device__ __forceinline__ SlotAttr slot_attr(const uint4& s) {
+  return {splat(__uint_as_float(s.y)), splat(__uint_as_float(s.z)), splat(__uint_as_float(s.w))};
+}
+__device__ __forceinline__ SlotAttr slot_attr(const uint4& s, float flip) {
+  return {splat(flip * __uint_as_float(s.y)), splat(flip * __uint_as_float(s.z)), splat(__uint_as_float(s.w))};
+}
+// z = x + y + AT . (a0, a1, a2): NPAIR independent chains, written stage by stage so that dependent packed ops are never back
+// to back
+__device__ __forceinline__ void edge_preact(const v2f* wa, const SlotAttr& a, const v2f* x, const v2f* y, v2f* z) {
+#pragma unroll
+  for (int p = 0; p < NPAIR; ++p) z[p] = x[p] + y[p];
+#pragma unroll
+  for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[p], a.a0, z[p]);
+#pragma unroll
+  for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[NPAIR + p], a.a1, z[p]);
+#pragma unroll
+  for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[2 * NPAIR + p], a.a2, z[p]);
+}
+
+// The walk over this lane's slots, as the state of a for loop:
+//   for (SlotWalk<PD, MASK> w(slots, nslots); w.more(); w.step())
+//     if (w.live()) { ... w.slot() ... w.row() ... }
+// live(): the current slot is not empty and carries MASK; row(): its LDS row index.  Software pipeline of distance PD (at
+// PD = 2: c0, c1, then nx = slots[min(r + 2, nslots - 1) * 64]): the 16-byte slot loads are unconditional (index clamped,
+// never branched on) so the compiler keeps them whole and places their waits PD - 1 iterations later.  (A struct of scalars and
+// not a callable: a closure holds the addresses of the caller's accumulator arrays, which kept them in scratch memory in the
+// walk with two weight blocks, pass_rev_in_mixed.)
+template <int PD, unsigned MASK>
+struct SlotWalk {
+  const uint4* __restrict__ slots;
+  int nslots, r;
+  uint4 c[PD], nx;
+  __device__ __forceinline__ SlotWalk(const uint4* __restrict__ slots_, int nslots_) : slots(slots_), nslots(nslots_), r(0) {
+    if (nslots <= 0) return;
+#pragma unroll
+    for (int i = 0; i < PD; ++i) c[i] = slots[(int64_t)min(i, nslots - 1) * 64];
+  }
+  __device__ __forceinline__ bool more() {   // also issues the load PD slots ahead
+    if (r >= nslots) return false;
+    nx = slots[(int64_t)min(r + PD, nslots - 1) * 64];
+    return true;
+  }
+  __device__ __forceinline__ bool live() const { return (c[0].x & 0xFFFFu) != ELL_EMPTY && (c[0].x & MASK); }
+  __device__ __forceinline__ const uint4& slot() const { return c[0]; }
+  __device__ __forceinline__ int row() const { return (int)(c[0].x & 0xFFFFu); }
+  __device__ __forceinline__ void step() {
+#pragma unroll
+    for (int i = 0; i + 1 < PD; ++i) c[i] = c[i + 1];
+    c[PD - 1] = nx;
+    ++r;
+  }
+};
+
 // One direction of the neighbour sum for this lane's node:
 //   S[o] += relu(Pi[o] + row[COL + o] + AT[:, o] . (a0, a1, a2))   over the slots that carry `MASK`
 // (AT = W1[:, 20:23]^T; for in-edges its first two rows are stored negated, because an in-edge's attr is the
@@ -93,62 +196,17 @@ __device__ __forceinline__ float edge_pass(const uint4* __restrict__ slots, int 
                                            const float* __restrict__ AT, const v2f* Pi, v2f* S) {
   float deg = 0.f;
   v2f wa[3 * NPAIR];
-#pragma unroll
-  for (int i = 0; i < 3 * NPAIR; ++i) wa[i] = reinterpret_cast<const v2f*>(AT)[i];
-  auto one = [&](const uint4 s) {
-    const unsigned w = s.x;
-    if ((w & 0xFFFFu) != ELL_EMPTY && (w & MASK)) {
-      const v2f a0 = splat(__uint_as_float(s.y)), a1 = splat(__uint_as_float(s.z)), a2 = splat(__uint_as_float(s.w));
-      const float* row = lds + (int)(w & 0xFFFFu) * RS + COL;
-      v2f pj[NPAIR];
-      if (COL % 4 == 0) {  // 16-byte aligned start: D / 4 b128 and, when D is not a multiple of 4, a b64 (D = 10: b128, b128, b64)
-        float4 v[D / 4];
-#pragma unroll
-        for (int q = 0; q < D / 4; ++q) v[q] = reinterpret_cast<const float4*>(row)[q];
-#pragma unroll
-        for (int p = 0; p < D / 4 * 2; ++p) pj[p] = quad_pair(v, p);
-        if (D % 4) {
-          float2 t = reinterpret_cast<const float2*>(row)[NPAIR - 1];
-          pj[NPAIR - 1] = (v2f){t.x, t.y};
-        }
-      } else {             // start at 8 mod 16 (D = 2 mod 4 only): b64, then D / 4 b128 (D = 10: b64, b128, b128)
-        static_assert(COL % 4 == 0 || D % 4 == 2, "a row segment starting at 8 mod 16 has 4 q + 2 floats");
-        float2 t = reinterpret_cast<const float2*>(row)[0];
-        float4 v[D / 4];
-#pragma unroll
-        for (int q = 0; q < D / 4; ++q) v[q] = reinterpret_cast<const float4*>(row + 2)[q];
-        pj[0] = (v2f){t.x, t.y};
-#pragma unroll
-        for (int p = 0; p < D / 4 * 2; ++p) pj[1 + p] = quad_pair(v, p);
-      }
+  ld_attr(AT, wa);
+  for (SlotWalk<EDGE_PD, MASK> w(slots, nslots); w.more(); w.step())
+    if (w.live()) {
+      const SlotAttr a = slot_attr(w.slot());
+      v2f pj[NPAIR], z[NPAIR];
+      lds_row<COL>(lds + w.row() * RS, pj);
       deg += 1.f;
-      // NPAIR independent chains, written stage by stage so that dependent packed ops are never back to back
-      v2f z[NPAIR];
-#pragma unroll
-      for (int p = 0; p < NPAIR; ++p) z[p] = Pi[p] + pj[p];
-#pragma unroll
-      for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[p], a0, z[p]);
-#pragma unroll
-      for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[NPAIR + p], a1, z[p]);
-#pragma unroll
-      for (int p = 0; p < NPAIR; ++p) z[p] = __builtin_elementwise_fma(wa[2 * NPAIR + p], a2, z[p]);
+      edge_preact(wa, a, Pi, pj, z);
 #pragma unroll
       for (int p = 0; p < NPAIR; ++p) S[p] += __builtin_elementwise_max(z[p], splat(0.f));
     }
-  };
-  // software pipeline, distance EDGE_PD: the 16-byte slot loads are unconditional (index clamped, never branched
-  // on) so the compiler keeps them whole and places their waits EDGE_PD - 1 iterations later
-  if (nslots <= 0) return deg;
-  uint4 c[EDGE_PD];
-#pragma unroll
-  for (int i = 0; i < EDGE_PD; ++i) c[i] = slots[(int64_t)min(i, nslots - 1) * 64];
-  for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + EDGE_PD, nslots - 1) * 64];
-    one(c[0]);
-#pragma unroll
-    for (int i = 0; i + 1 < EDGE_PD; ++i) c[i] = c[i + 1];
-    c[EDGE_PD - 1] = nx;
-  }
   return deg;
 }
 
