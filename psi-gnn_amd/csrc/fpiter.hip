@@ -15,6 +15,7 @@
 // Reductions use fixed-shape partial sums in a fixed order: bitwise reproducible.
 #include "vec_helpers.h"
 #include "internal.h"
+#include "solver_shapes.h"
 #include <algorithm>
 #include <vector>
 
@@ -56,7 +57,6 @@ struct psignn_fpiter {
 
 // The kernels' bodies are device functions: the single-handle kernels below call them with their own arguments, the *_batch kernels
 // (further down) with the fields of descs[blockIdx.z] -- the same block -> element mapping and the same partial-sum shapes either way.
-// (k_and_gram, k_and_solve and k_and_mix keep their text and stand next to a copy of it for the batch kernels: see there.)
 __device__ __forceinline__ void fp_init_body(FpStatus* st, double* rel_trace, double* abs_trace, int32_t* low_idx, int thr, int stop_abs,
                                              int k0) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -153,60 +153,6 @@ __global__ __launch_bounds__(TB) void k_picard_check(FpStatus* st, const float* 
 
 // Anderson: gram partials.  Pair index p = j (j + 1) / 2 + i for i <= j.
 template <int VEC>
-__global__ __launch_bounds__(TB) void k_and_gram(int64_t M, int64_t ld, int n, const FpStatus* __restrict__ st,
-                                                 const float* __restrict__ X, const float* __restrict__ F,
-                                                 float* __restrict__ part, int npart) {
-  if (st->done) return;
-  int64_t e0 = elem0<VEC>();
-  const bool act = e0 < M;
-  float acc[FP_NPAIR];
-#pragma unroll
-  for (int p = 0; p < FP_NPAIR; ++p) acc[p] = 0.f;
-  if (act) {
-    // n <= FP_MAX_M rows of VEC floats would not fit in registers for n = 8, VEC = 16: walk the span in float4 pieces
-#pragma unroll 1
-    for (int q = 0; q < VEC / 4; ++q) {
-      const int64_t o = e0 + q * 256;
-      float g[FP_MAX_M][4];
-#pragma unroll
-      for (int i = 0; i < FP_MAX_M; ++i) {
-        if (i < n) {
-          if (o + 4 <= M) {   // rows start on 256-byte boundaries (ld is a multiple of 64): aligned float4
-            const float4 fv = *reinterpret_cast<const float4*>(F + (int64_t)i * ld + o);
-            const float4 xv = *reinterpret_cast<const float4*>(X + (int64_t)i * ld + o);
-            g[i][0] = fv.x - xv.x; g[i][1] = fv.y - xv.y; g[i][2] = fv.z - xv.z; g[i][3] = fv.w - xv.w;
-          } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) g[i][c] = (o + c < M) ? F[(int64_t)i * ld + o + c] - X[(int64_t)i * ld + o + c] : 0.f;
-          }
-        } else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) g[i][c] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < FP_MAX_M; ++j)
-#pragma unroll
-        for (int i = 0; i <= j; ++i) {
-          float s = acc[j * (j + 1) / 2 + i];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) s = fmaf(g[i][c], g[j][c], s);
-          acc[j * (j + 1) / 2 + i] = s;
-        }
-    }
-  }
-  const int w = blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
-  const int npairs = n * (n + 1) / 2;
-#pragma unroll
-  for (int p = 0; p < FP_NPAIR; ++p) {
-    if (p < npairs) {   // wave-uniform
-      const float s = wave_sum(acc[p]);
-      if ((threadIdx.x & 63) == 0) part[(int64_t)p * npart + w] = s;
-    }
-  }
-}
-// The same text once more for k_and_gram_batch: with one shared body k_and_gram<4> took 86 VGPRs instead of 84.
-template <int VEC>
 __device__ __forceinline__ void and_gram_body(int64_t M, int64_t ld, int n, const FpStatus* __restrict__ st,
                                               const float* __restrict__ X, const float* __restrict__ F, float* __restrict__ part,
                                               int npart) {
@@ -260,56 +206,14 @@ __device__ __forceinline__ void and_gram_body(int64_t M, int64_t ld, int n, cons
   }
 }
 
-// One block: alpha of the bordered system (solver.py:252-256) in float64.
-__global__ __launch_bounds__(TB) void k_and_solve(FpStatus* st, const float* __restrict__ part, int npart, int n, double lam) {
-  __shared__ double sh[TB];
-  __shared__ double gram[FP_NPAIR];
-  if (st->done) return;
-  const int npairs = n * (n + 1) / 2;
-  for (int p = 0; p < npairs; ++p) {
-    const double s = block_sum_partials(part + (int64_t)p * npart, npart, sh);
-    if (threadIdx.x == 0) gram[p] = (double)(float)s;   // torch.bmm result is fp32
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const int d = n + 1;
-  double A[(FP_MAX_M + 1) * (FP_MAX_M + 2)];   // augmented [H | y], row-major, d x (d + 1)
-  for (int r = 0; r < d; ++r)
-    for (int c = 0; c <= d; ++c) A[r * (d + 1) + c] = 0.0;
-  for (int i = 1; i < d; ++i) A[0 * (d + 1) + i] = A[i * (d + 1) + 0] = 1.0;
-  for (int j = 0; j < n; ++j)
-    for (int i = 0; i <= j; ++i) {
-      const double v = gram[j * (j + 1) / 2 + i];
-      A[(i + 1) * (d + 1) + (j + 1)] = v;
-      A[(j + 1) * (d + 1) + (i + 1)] = v;
-    }
-  for (int i = 0; i < n; ++i) A[(i + 1) * (d + 1) + (i + 1)] += lam;
-  A[0 * (d + 1) + d] = 1.0;
-  for (int c = 0; c < d; ++c) {   // Gaussian elimination with partial pivoting
-    int piv = c;
-    for (int r = c + 1; r < d; ++r)
-      if (fabs(A[r * (d + 1) + c]) > fabs(A[piv * (d + 1) + c])) piv = r;
-    if (piv != c)
-      for (int q = 0; q <= d; ++q) {
-        const double t = A[c * (d + 1) + q];
-        A[c * (d + 1) + q] = A[piv * (d + 1) + q];
-        A[piv * (d + 1) + q] = t;
-      }
-    const double pv = A[c * (d + 1) + c];
-    for (int r = c + 1; r < d; ++r) {
-      const double f = A[r * (d + 1) + c] / pv;
-      for (int q = c; q <= d; ++q) A[r * (d + 1) + q] -= f * A[c * (d + 1) + q];
-    }
-  }
-  double sol[FP_MAX_M + 1];
-  for (int r = d - 1; r >= 0; --r) {
-    double s = A[r * (d + 1) + d];
-    for (int q = r + 1; q < d; ++q) s -= A[r * (d + 1) + q] * sol[q];
-    sol[r] = s / A[r * (d + 1) + r];
-  }
-  for (int i = 0; i < n; ++i) st->alpha[i] = (double)(float)sol[i + 1];
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_and_gram(int64_t M, int64_t ld, int n, const FpStatus* __restrict__ st,
+                                                 const float* __restrict__ X, const float* __restrict__ F,
+                                                 float* __restrict__ part, int npart) {
+  and_gram_body<VEC>(M, ld, n, st, X, F, part, npart);
 }
-// The same text once more for k_and_solve_batch: with one shared body k_and_solve took 52 SGPRs instead of 53.
+
+// One block: alpha of the bordered system (solver.py:252-256) in float64.
 __device__ __forceinline__ void and_solve_body(FpStatus* st, const float* __restrict__ part, int npart, int n, double lam) {
   __shared__ double sh[TB];
   __shared__ double gram[FP_NPAIR];
@@ -359,36 +263,11 @@ __device__ __forceinline__ void and_solve_body(FpStatus* st, const float* __rest
   for (int i = 0; i < n; ++i) st->alpha[i] = (double)(float)sol[i + 1];
 }
 
-// X[slot] = beta * sum alpha_i F_i + (1 - beta) * sum alpha_i X_i ; also written to `out` (the caller's trial point)
-template <int VEC>
-__global__ __launch_bounds__(TB) void k_and_mix(int64_t M, int64_t ld, int n, int slot, const FpStatus* __restrict__ st,
-                                                float* __restrict__ X, const float* __restrict__ F, float beta,
-                                                float* __restrict__ out, float* __restrict__ trace_dst) {
-  if (st->done) return;
-  int64_t e0 = elem0<VEC>();
-  if (e0 >= M) return;
-  float accf[VEC], accx[VEC], t[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) accf[i] = accx[i] = 0.f;
-  for (int i = 0; i < n; ++i) {
-    const float a = (float)st->alpha[i];
-    ldv<VEC>(F + (int64_t)i * ld, e0, M, t);
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) accf[c] = fmaf(a, t[c], accf[c]);
-    if (beta != 1.f) {
-      ldv<VEC>(X + (int64_t)i * ld, e0, M, t);
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) accx[c] = fmaf(a, t[c], accx[c]);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) accf[c] = beta * accf[c] + (1.f - beta) * accx[c];
-  stv<VEC>(X + (int64_t)slot * ld, e0, M, accf);
-  if (out) stv<VEC>(out, e0, M, accf);
-  if (trace_dst) stv<VEC>(trace_dst, e0, M, accf);
+__global__ __launch_bounds__(TB) void k_and_solve(FpStatus* st, const float* __restrict__ part, int npart, int n, double lam) {
+  and_solve_body(st, part, npart, n, lam);
 }
-// The same text once more for k_and_mix_batch (its last statement spelled out): with one shared body k_and_mix<16> took 76 VGPRs
-// instead of 78.
+
+// X[slot] = beta * sum alpha_i F_i + (1 - beta) * sum alpha_i X_i ; also written to `out` (the caller's trial point)
 template <int VEC>
 __device__ __forceinline__ void and_mix_body(int64_t M, int64_t ld, int n, int slot, const FpStatus* __restrict__ st,
                                              float* __restrict__ X, const float* __restrict__ F, float beta, float* __restrict__ out,
@@ -410,13 +289,19 @@ __device__ __forceinline__ void and_mix_body(int64_t M, int64_t ld, int n, int s
       for (int c = 0; c < VEC; ++c) accx[c] = fmaf(a, t[c], accx[c]);
     }
   }
-  // (k_and_mix's "beta * accf + (1 - beta) * accx" as the compiler contracts it there: the X term rounded, then one fma with the F
-  // term.  Left to -ffp-contract=fast this copy was contracted the other way round and lost the bits of the single kernel at beta != 1.)
+  // ("beta * accf + (1 - beta) * accx" with the X term rounded, then one fma with the F term, spelled out: -ffp-contract=fast contracts
+  // the plain expression one way or the other depending on the kernel around it, and the stepwise and lockstep solves must share bits.)
 #pragma unroll
   for (int c = 0; c < VEC; ++c) accf[c] = fmaf(beta, accf[c], (1.f - beta) * accx[c]);
   stv<VEC>(X + (int64_t)slot * ld, e0, M, accf);
   if (out) stv<VEC>(out, e0, M, accf);
   if (trace_dst) stv<VEC>(trace_dst, e0, M, accf);
+}
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_and_mix(int64_t M, int64_t ld, int n, int slot, const FpStatus* __restrict__ st,
+                                                float* __restrict__ X, const float* __restrict__ F, float beta,
+                                                float* __restrict__ out, float* __restrict__ trace_dst) {
+  and_mix_body<VEC>(M, ld, n, slot, st, X, F, beta, out, trace_dst);
 }
 
 // Anderson bookkeeping (solver.py:262-283).
@@ -493,10 +378,8 @@ static int fpiter_create(psignn_fpiter_t** out, int64_t n_elems, int m, int thre
   s->m = m;
   s->thr = threshold;
   s->keep_trace = keep_trace;
-  s->vec = width_elems >= ((int64_t)3 << 18) ? 16 : 4;
-  s->nblk = (int)cdiv(n_elems, (int64_t)s->vec * TB);
-  s->npart = s->nblk * (TB / 64);
-  s->ld = (n_elems + 63) / 64 * 64;
+  const shapes::VecShape v = shapes::vec_shape(n_elems, width_elems);
+  s->vec = v.vec; s->nblk = v.nblk; s->npart = v.npart; s->ld = v.ld;
   const size_t ld = (size_t)s->ld, thr = (size_t)threshold;
   const size_t rows = for_batch ? (size_t)(n_elems / D + 1) : 0;   // node rows of the mesh the handle is for (n_elems = N * d)
   struct { void** p; size_t n; } allocs[] = {

@@ -19,6 +19,7 @@
 // = 2 (j + 1) + O(1) vector passes per step, 4 (j + 1) when the second pass runs.  Reductions: fixed-shape partial sums in a fixed order (reproducible).
 #include "vec_helpers.h"
 #include "internal.h"
+#include "solver_shapes.h"
 #include <algorithm>
 #include <stddef.h>
 #include <vector>
@@ -434,9 +435,8 @@ static int gmres_create(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m
   s->ld = ld;
   s->m = m_max;
   s->V = d_basis;
-  s->vec = width_elems >= ((int64_t)3 << 18) ? 16 : 4;
-  s->nblk = (int)cdiv(n_elems, (int64_t)s->vec * TB);
-  s->npart = s->nblk * (TB / 64);
+  const shapes::VecShape v = shapes::vec_shape(n_elems, width_elems);
+  s->vec = v.vec; s->nblk = v.nblk; s->npart = v.npart;
   s->ldp = (m_max + 2 + 63) / 64 * 64;
   const size_t m = (size_t)m_max;
   struct { void** p; size_t n; } allocs[] = {

@@ -16,6 +16,7 @@
 // bitwise reproducible run to run.
 #include "vec_helpers.h"
 #include "internal.h"
+#include "solver_shapes.h"
 #include <stdlib.h>
 #include <math.h>
 #include <algorithm>
@@ -46,24 +47,19 @@ struct Status {
 // in LDS, and after every 64 pairs (and after the last one) the block's first 64 threads add the four waves' values in a fixed
 // order and store ONE contiguous row segment: part[plane][block * ldp + j].  Same bench: 0.76.  The reduce kernels read a
 // column of that (blocks x pairs) matrix per pair -- 64-byte sectors from L2, a quarter as many elements as before.
-#define PARTA_LD 32            // row pitch of the folded sweep's partials: one entry per kept pair, so at most 32 kept pairs --
-                               // U2R_KB_MAX + 1 = 25 in the register form, U2D_LDS_KMAX + 1 = 32 in the LDS form (k_sweep_u2d drops
-                               // entries past the pitch, and k_reduce_a_check would read the next block's row in their place)
 // (block_sum_col, vec_helpers.h: RB = 1 024 threads per reduce block was tried for the column reads:
 // k_reduce_cb 9.7 vs 8.3 us, k_reduce_a_check unchanged -- a block's time is the 64-byte sectors it pulls through ONE CU, not
-// its load rounds; what helps is more blocks per column, RA below.)
+// its load rounds; what helps is more blocks per column, RA in solver_shapes.h.)
 #define RB 256
-#define RA 8     // row chunks per column of the a-reduction: coef_a arrives as RA partial sums that sweep 2 adds up itself
+static_assert(shapes::THREADS == TB && sizeof(Status) == shapes::STATUS_BYTES, "solver_shapes.h sizes the launches and the status block");
+// Sizes and launch shapes (shape: solver_shapes.h, derived once at creation), buffers, and the state of a solve.
 struct psignn_broyden {
   const psignn_plan* plan = nullptr;
   int64_t M = 0;
   int seq_len = D;
   int thr = 0;
   int keep_trace = 0;
-  int vec = 16;             // elements per thread of the vector kernels
-  int nblk = 0, npart = 0;
-  int vec_ax = 0, nblk_ax = 0;  // axpy / final pass: own vector width on mid-size vectors (see broyden_alloc)
-  int jgroups = 1;          // block rows of the U/V sweeps (short vectors are also split over the stored pairs)
+  shapes::BroydenShape shape;
   float* jpart = nullptr;   // (jgroups, 3, M) partial axpy sums when jgroups > 1
   float *U = nullptr, *V = nullptr;
   float* xbuf = nullptr;    // (thr+2, M) with trace, else (3, M)
@@ -76,25 +72,17 @@ struct psignn_broyden {
   int64_t lwork_floats = 0;
   float* nrm_part = nullptr;  // norm partials of the f / residual kernel: 2 * nn floats
   float* part2 = nullptr;     // three-sweep update: block partials of vT.dg, vT.g (2 * nblk floats)
-  int uvu = 0;                // the update runs as three single-array sweeps U, V, U (broyden_alloc)
-  int vec_u = 0, nblk_u = 0, npart_u = 0;   // their vector width / blocks / per-wave partials per stored pair
-  int u2d_kmax = 0, nblk4 = 0, a_ready = 0; // k_sweep_u2d: up to this many stored pairs are all kept; its blocks; a of the next iteration comes (partly) from it
-  int u2d_keep = 0, a_from = 0;             // beyond u2d_kmax: the most recent u2d_keep pairs are kept; pairs before a_from still need sweep 1
-  int u2d_reg = 1;                          // kept values in registers (k_sweep_u2r<KB>, the default) or in per-thread LDS slots (k_sweep_u2d; PSIGNN_U2D_FORM=lds)
-  float* parta = nullptr;                   // its per-block partials of a: (nblk4, PARTA_LD) -- entry q of a row = pair j_keep0 + q
-  int nn_cap = 0;
+  int a_ready = 0, a_from = 0;              // a of the next iteration comes (partly) from the folded sweep 3; pairs before a_from still need sweep 1
+  float* parta = nullptr;                   // the folded sweep's per-block partials of a: (nblk4, PARTA_LD) -- entry q of a row = pair j_keep0 + q
   float *h0p = nullptr, *prbp = nullptr, *nrmp = nullptr;  // plan-order copies of h_initial, prb_data, normals
   float* part = nullptr;    // dot partials: 3 planes (a, c, b) of (blocks, ldp) -- one value per BLOCK and stored pair, pairs contiguous
                             // (pair_rows below); its head is reused for the axpy pass's s, beta partials
-  int ldp = 0;              // row pitch of a plane: thr rounded up to 64
-  int64_t pstride = 0;      // plane stride (floats): max blocks of any sweep form x ldp
   float* coef = nullptr;    // (3 + RA, thr): a, c, b; then the RA row-chunk sums of a (three-sweep forms: what sweep 2 reads)
   Status* st = nullptr;     // device
   double *rel_trace = nullptr, *abs_trace = nullptr;  // device, thr entries
   Status* h_st = nullptr;   // pinned host mirror
   size_t bytes = 0;
   int ext_iter = 0;
-  int64_t ld = 0;           // row pitch (elements) of U and V
   int hist = 0;             // element type of the stored pairs U, V: 0 fp32, 1 bf16 (psignn_broyden_create_opts; the buffers are then
                             // __bf16 behind the float pointers, and the update always runs the unfolded three-sweep form)
   int stop_abs = 0;         // stop_mode of the next solve
@@ -1158,9 +1146,6 @@ __global__ __launch_bounds__(TB) void k_copy_sel(int64_t M, const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------ host
-#define U2R_KB_MAX 24
-#define U2D_LDS_KMAX (PARTA_LD - 1)   // LDS form: k - j_keep0 + 1 <= PARTA_LD partials per row
-static_assert(U2R_KB_MAX + 1 <= PARTA_LD, "the register fold's kept pairs must fit a partials row");
 __global__ __launch_bounds__(TB) void kb_sweep_u2d(const BatchDesc* __restrict__ descs, int k, int j_keep0, int par);
 // LDS form of the folded sweep: up to U2D_LDS_KMAX = 31 pairs x 16 B x 256 threads of dynamic LDS; asked for once per device
 static bool u2d_lds_attr(int dev) {
@@ -1178,128 +1163,33 @@ static bool u2d_lds_attr(int dev) {
   return state[dev] > 0;
 }
 
+// Shapes and sizes are broyden_shape's (solver_shapes.h); here: the one question it leaves to the device, and the allocations.
 static int broyden_alloc(psignn_broyden* s) {
-  size_t M = (size_t)s->M, thr = (size_t)s->thr;
-  // 16 floats per lane from 768 K elements up, 4 below (PSIGNN_VEC16_MIN overrides).  Re-tuned after the coalesced lane
-  // mapping, Broyden iterations/s with 4 vs 16 (dirichlet meshes, K = 100): 27 k nodes 12 790 / 10 156, 50 k 8 283 /
-  // 7 826, 100 k 4 578 / 4 972, 200 k 2 608 / 2 806, 400 k 1 416 / 1 551 (the old switch point was 4 M elements)
-  const int64_t vec16_min = [] {
-    const char* e = getenv("PSIGNN_VEC16_MIN");
-    return e ? (int64_t)atoll(e) : (int64_t)3 << 18;
-  }();
-  // A solver that will run inside a batched solve (size_hint = elements of the whole shard) sizes its sweeps for the
-  // aggregate: the shard's blocks fill the chip together, so the long-vector width applies and the sweeps need no split
-  // over the stored pairs.  Its single-mesh solves use the same shapes, hence the same bits as its batched ones.
-  const int64_t eff = std::max<int64_t>(s->M, s->size_hint);
-  s->vec = eff >= vec16_min ? 16 : 4;
-  s->nblk = (int)cdiv(s->M, (int64_t)s->vec * TB);
-  const int64_t eff_blk = cdiv(eff, (int64_t)s->vec * TB);
-  s->jgroups = eff_blk >= 768 ? 1 : (int)std::min<int64_t>(8, cdiv(768, eff_blk));
-  // Shard of short vectors (8 x 50 k nodes: 123 blocks per mesh, 983 together): the chip is covered, but every block then walks
-  // all stored pairs alone; the dots pass split 4 ways over the pairs and the axpy pass unsplit at 4 floats per lane
-  // (3 930 blocks) measured 305 / 310 us against 325 / 313 us per launch (K = 100; profiles/r2_batch_sweep_ab.txt)
-  const bool short_shard = s->size_hint > s->M && s->vec == 16 && s->nblk < 512;
-  if (short_shard) s->jgroups = 4;
-  if (const char* e = getenv("PSIGNN_JGROUPS")) s->jgroups = std::max(1, std::min(8, atoi(e)));   // A/B knob
-  s->npart = s->nblk * (TB / 64);
-  // Mid-size vectors (16 floats per lane, but too few blocks to fill the chip): the dots pass is split over the stored
-  // pairs (free: every pair's partial sums are independent), the axpy pass would need a combine launch after such a split
-  // -- it runs unsplit with 4 floats per lane instead (100 k nodes: 91 us vs 79 + 20 us).  The thread -> element mapping
-  // is per kernel; only the pair partials that k_final reads must follow the axpy pass's block count.
-  s->vec_ax = s->vec;
-  s->nblk_ax = s->nblk;
-  const char* e_ax = getenv("PSIGNN_VEC_AX4");   // A/B knob: 1 forces the 4-float unsplit axpy pass, 0 forbids it
-  if (e_ax ? (atoi(e_ax) != 0 && s->vec == 16)
-           : (s->vec == 16 && s->jgroups > 1 && (short_shard || cdiv(s->M, (int64_t)4 * TB) >= 512))) {
-    s->vec_ax = 4;
-    s->nblk_ax = (int)cdiv(s->M, (int64_t)4 * TB);
-  }
-  // three-sweep update (update_chain): where an UNSPLIT sweep covers the chip -- long vectors at 16 floats per lane, mid-size
-  // vectors and shards of short vectors at the 4-float width of their axpy pass.  PSIGNN_UVU=0|1 overrides (A/B, tests).
-  s->uvu = 0;
-  if (s->vec == 16 && s->jgroups == 1 && s->vec_ax == 16) {
-    s->uvu = 1; s->vec_u = 16; s->nblk_u = s->nblk;
-  } else if (s->vec_ax == 4 && s->vec == 16) {
-    s->uvu = 1; s->vec_u = 4; s->nblk_u = s->nblk_ax;
-  }
-  if (const char* e = getenv("PSIGNN_UVU")) if (atoi(e) == 0) s->uvu = 0;
-  if (s->hist) {
-    // bf16 pairs: always the unfolded three-sweep form (the two-pass form and the folded sweep 3 have no bf16 variant), 16 floats per
-    // lane where the fp32 rules pick that width, else 4 floats unsplit; PSIGNN_UVU / PSIGNN_U2D_* do not apply
-    s->uvu = 1;
-    s->vec_u = (s->vec == 16 && s->jgroups == 1 && s->vec_ax == 16) ? 16 : 4;
-    s->nblk_u = (int)cdiv(s->M, (int64_t)s->vec_u * TB);
-  }
-  s->npart_u = s->nblk_u * (TB / 64);
-  s->nblk4 = (int)cdiv(s->M, (int64_t)4 * TB);
-  const bool fold_ok = s->uvu != 0;
-  // folded sweep 3: kept values in registers (default; at most U2R_KB_MAX pairs) or in LDS (PSIGNN_U2D_FORM=lds: the round-2 form, A/B and tests)
-  // Registers where the launch has several rounds of blocks (>= 2 048 blocks of 1 024 floats: 8 per CU); on shorter vectors every
-  // block is resident at once, all waves then load together and reduce together, and the LDS form's two rounds overlap better
-  // (100k nodes, K = 100: 56.5 vs 64.8 us per launch; profiles/r3_ab_u2d.txt).  M >= 2^30 floats: the register form's 32-bit lane
-  // offsets do not reach.
-  s->u2d_reg = cdiv(eff, (int64_t)4 * TB) >= 2048 && s->M < ((int64_t)1 << 30);
-  if (const char* e = getenv("PSIGNN_U2D_FORM")) s->u2d_reg = ((e[0] == 'l' || e[0] == 'L') ? 0 : 1) && s->M < ((int64_t)1 << 30);
-  // (LDS form: at most U2D_LDS_KMAX, so that k - keep0 + 1 kept pairs -- all k + 1 up to u2d_kmax, u2d_keep + 1 beyond -- fit PARTA_LD)
-  const int kmax_cap = s->u2d_reg ? U2R_KB_MAX : U2D_LDS_KMAX;
-  s->u2d_kmax = fold_ok ? 24 : 0;   // LDS form: 96 KB per block at most; 20 ... 32 measure alike at K = 50, K = 20 needs >= 19
-  if (const char* e = getenv("PSIGNN_U2D_KMAX")) s->u2d_kmax = fold_ok ? std::max(0, std::min(kmax_cap, atoi(e))) : 0;
-  s->u2d_keep = s->u2d_kmax > 0 ? 16 : 0;
-  if (const char* e = getenv("PSIGNN_U2D_KEEP")) s->u2d_keep = s->u2d_kmax > 0 ? std::max(0, std::min(s->u2d_kmax, atoi(e))) : 0;
-  if (s->hist) s->u2d_kmax = s->u2d_keep = 0;
-  if (s->u2d_kmax > 0 && !s->u2d_reg) {
+  shapes::BroydenShape& sh = s->shape;
+  sh = shapes::broyden_shape(s->M, s->size_hint, s->thr, s->hist, s->keep_trace, s->plan ? s->plan->N : 0, s->plan ? s->plan->n_tiles : 0,
+                             shapes::knobs_from_env());
+  if (sh.wants_big_lds()) {
     // more than 64 KB of dynamic LDS has to be asked for, per device (the attribute belongs to the device's code object)
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (!u2d_lds_attr(dev)) {   // not granted: stay within the default 64 KB (16 B x 256 threads x 15 pairs + the kernel's static 512 B)
-      s->u2d_kmax = std::min(s->u2d_kmax, 15);
-      s->u2d_keep = std::min(s->u2d_keep, 15);
-    }
+    if (!u2d_lds_attr(dev)) sh.cap_to_default_lds();
   }
-  s->nn_cap = std::max<int>(std::max(s->nblk, s->nblk_ax), s->plan ? (int)s->plan->n_tiles : 0);
-  s->ldp = (s->thr + 63) / 64 * 64;
-  s->pstride = (int64_t)std::max(std::max(s->nblk, s->nblk_u), std::max(s->nblk_ax, 1)) * s->ldp;
-  size_t nx = s->keep_trace ? thr + 2 : 3;
-  // row pitch of U and V: every stored vector starts on a 256-byte boundary (64 fp32 / 128 bf16 elements)
-  s->ld = s->hist ? (s->M + 127) / 128 * 128 : (s->M + 63) / 64 * 64;
-  size_t ld = (size_t)s->ld;
-  const size_t pb = s->hist ? 2 : 4;   // bytes per stored pair element
+  const shapes::BroydenShape::Bytes& b = sh.bytes;
   struct { void** p; size_t n; } allocs[] = {
-      {(void**)&s->U, thr * ld * pb},  {(void**)&s->V, thr * ld * pb},   {(void**)&s->xbuf, nx * M * 4},
-      {(void**)&s->gbuf[0], M * 4},   {(void**)&s->gbuf[1], M * 4},   {(void**)&s->upd, M * 4},
-      {(void**)&s->fx, M * 4},        {(void**)&s->part, 3 * (size_t)s->pstride * 4 + 16}, {(void**)&s->parta, (size_t)s->nblk4 * PARTA_LD * 4 + 16},
-      {(void**)&s->coef, (3 + RA) * thr * 4 + 16}, {(void**)&s->st, sizeof(Status)},
-      {(void**)&s->nrm_part, 2 * (size_t)s->nn_cap * 4 + 16}, {(void**)&s->part2, 2 * (size_t)std::max(s->nblk, s->nblk_u) * 4 + 16},
-      {(void**)&s->rel_trace, thr * 8 + 8}, {(void**)&s->abs_trace, thr * 8 + 8}};
+      {(void**)&s->U, b.U},  {(void**)&s->V, b.V},   {(void**)&s->xbuf, b.xbuf},
+      {(void**)&s->gbuf[0], b.gbuf0},   {(void**)&s->gbuf[1], b.gbuf1},   {(void**)&s->upd, b.upd},
+      {(void**)&s->fx, b.fx},        {(void**)&s->part, b.part}, {(void**)&s->parta, b.parta},
+      {(void**)&s->coef, b.coef}, {(void**)&s->st, b.st},
+      {(void**)&s->nrm_part, b.nrm_part}, {(void**)&s->part2, b.part2},
+      {(void**)&s->rel_trace, b.rel_trace}, {(void**)&s->abs_trace, b.abs_trace},
+      {(void**)&s->jpart, b.jpart}, {(void**)&s->fwork, b.fwork}, {(void**)&s->h0p, b.h0p}, {(void**)&s->prbp, b.prbp}, {(void**)&s->nrmp, b.nrmp}};
   for (auto& a : allocs) {
-    if (hipMalloc(a.p, a.n ? a.n : 16) != hipSuccess) {
+    if (a.n == 0) continue;   // (jpart, fwork and the plan-order inputs: only where the shape sizes them)
+    if (hipMalloc(a.p, a.n) != hipSuccess) {
       psignn_set_error("broyden: hipMalloc of %zu bytes failed (U+V need 2*thr*N*d*4 bytes)", a.n);
       return PSIGNN_ENOMEM;
     }
     s->bytes += a.n;
-  }
-  if (s->jgroups > 1 && s->vec_ax == s->vec) {  // scratch of a split axpy pass
-    size_t jb = (size_t)s->jgroups * 3 * M * 4;
-    if (hipMalloc((void**)&s->jpart, jb) != hipSuccess) {
-      psignn_set_error("broyden: hipMalloc of the split-sweep scratch failed");
-      return PSIGNN_ENOMEM;
-    }
-    s->bytes += jb;
-  }
-  if (s->plan) {
-    size_t wf = (size_t)psignn_f_workspace_floats(s->plan) * 4;
-    if (hipMalloc((void**)&s->fwork, wf) != hipSuccess) {
-      psignn_set_error("broyden: hipMalloc of f workspace failed");
-      return PSIGNN_ENOMEM;
-    }
-    s->bytes += wf;
-    size_t N = (size_t)s->plan->N;
-    if (hipMalloc((void**)&s->h0p, M * 4) != hipSuccess || hipMalloc((void**)&s->prbp, N * 3 * 4) != hipSuccess ||
-        hipMalloc((void**)&s->nrmp, N * 2 * 4) != hipSuccess) {
-      psignn_set_error("broyden: hipMalloc of plan-order inputs failed");
-      return PSIGNN_ENOMEM;
-    }
-    s->bytes += M * 4 + N * 20;
   }
   if (hipHostMalloc((void**)&s->h_st, sizeof(Status)) != hipSuccess) {
     psignn_set_error("broyden: hipHostMalloc failed");
@@ -1380,144 +1270,81 @@ static inline int sel_off_nxt() { return offsetof(Status, nxt) / 4; }
 
 static inline __bf16* bf16_pairs(float* p) { return reinterpret_cast<__bf16*>(p); }   // U, V of a bf16-history solver
 
-// ------------------------------------------------------------------------------------------
-// The update chain: everything of one iteration after g_new and the norm partials are available; k = pairs stored so far.
-// The schedule stands here once -- two-pass or three-sweep form, which a_j the folded sweep 3 of the last iteration delivered
-// (a_ready / a_from), the keep window and its KB, LDS or register fold, the `last` gate, the split over pair groups with its combine
-// launch, the own-width axpy pass, and the algorithmic bytes of every launch.  A target knows HOW a pass is launched: SingleTarget
-// (the k_* kernels on one solver's fields) and ShardTarget (the kb_* kernels, one launch per pass over a shard, below).  Both run
+// The update chain (shapes::update_chain, solver_shapes.h) decides what one iteration runs; its two targets here launch it.  Both run
 // the same *_body functions, so a mesh has the same bits either way.
-// ------------------------------------------------------------------------------------------
-template <class Target>
-static void update_chain(Target& t, int k, double eps) {
-  const psignn_broyden& c = t.size_class();
-  const int thr = c.thr;
-  const int64_t vb = t.vec_bytes();                    // one state vector (summed over a shard)
-  const int64_t pe = vb / 4 * t.pair_elem_bytes();     // one stored vector U_j / V_j
-  const int kd = k >= thr ? 0 : k;   // the threshold stop is about to fire: no slot left for another pair
-  const bool last = k + 1 >= thr;    // (iteration thr's stop test has just fired: the passes after it return at once and state no bytes)
-  if (c.uvu) {
-    if (k == 0) t.a_ready() = 0;
-    // a_j of this iteration: pairs j >= a_from were delivered by the folded sweep 3 of the last iteration, the others need sweep 1
-    // (all meshes of a shard carry the same number of stored pairs: one a_from / keep window for the launch)
-    const int a_from = t.a_ready() ? t.a_from() : kd;
-    const int n1 = std::min(a_from, kd);
-    if (n1 > 0) {
-      PROF_BYTES(n1 * pe + vb);   // its columns of U + dx
-      t.sweep_u1(n1);
-    }
-    t.reduce_a_check(kd, eps, a_from);
-    t.a_ready() = 0;
-    if (k >= thr) return;
-    PROF_BYTES(last ? 0 : (k + 1) * pe + 3 * vb);   // k columns of V + dx, dg, g; writes V[k]
-    t.sweep_v(k);
-    t.reduce_cb(k);
-    const int keep0 = k <= c.u2d_kmax ? 0 : k - c.u2d_keep;      // few stored pairs: all kept; later the most recent ones
-    if (c.u2d_kmax > 0 && (k <= c.u2d_kmax || c.u2d_keep > 0) && !last) {
-      PROF_BYTES((k + 1) * pe + 4 * vb);   // k columns of U + update, dg, g; writes U[k], update (whichever form runs)
-      const int nk = k - keep0;
-      if (!c.u2d_reg) t.sweep_u2d(k, keep0, (size_t)std::max(nk, 1) * TB * 16);
-      else if (nk <= 8) t.template sweep_u2r<8>(k, keep0);
-      else if (nk <= 16) t.template sweep_u2r<16>(k, keep0);
-      else t.template sweep_u2r<24>(k, keep0);
-      t.a_ready() = 1;
-      t.a_from() = keep0;
-    } else {
-      PROF_BYTES(last ? 0 : (k + 1) * pe + 4 * vb);
-      t.sweep_u2(k);
-    }
-    return;
-  }
-  // split of the sweeps over the stored pairs: only when there are enough pairs to share out
-  const int G = t.groups(k);
-  if (kd > 0) {
-    PROF_BYTES((2 * kd + 3) * vb);
-    t.dots(kd, G);
-  }
-  t.reduce_check(kd, eps);
-  if (k >= thr) return;
-  const bool own_width = c.vec_ax != c.vec;   // the axpy / final passes run unsplit at their own vector width (broyden_alloc)
-  const int Ga = own_width ? 1 : G;
-  PROF_BYTES(last ? 0 : (2 * k + (Ga > 1 ? 3 * Ga : 6)) * vb);   // split: every block row writes its three partial vectors
-  t.axpy(k, Ga, own_width);
-  if (!own_width && t.combine_due(k, G)) {
-    PROF_BYTES(last || G <= 1 ? 0 : (3 * G + 6) * vb);
-    t.combine(k, G);
-  }
-  PROF_BYTES(last ? 0 : 4 * vb);
-  t.final_pass(k, own_width);
-}
+using shapes::update_chain;
 
-// One solver.  Owns the bf16-history variants of the three sweeps (broyden_alloc: always the unfolded three-sweep form).
+// One solver.  Owns the bf16-history variants of the three sweeps (broyden_shape: always the unfolded three-sweep form).
 struct SingleTarget {
   psignn_broyden* s;
   hipStream_t st;
   float* gnew;         // g of the iterate just evaluated
   const float* gold;   // g of the iterate before it
   int np;              // norm partials the stop test sums: one pair per block of k_resid / per tile of the fused f kernel
-  const psignn_broyden& size_class() const { return *s; }
+  const shapes::BroydenShape& size_class() const { return s->shape; }
+  void bytes(int64_t b) const { PROF_BYTES(b); }
   int64_t vec_bytes() const { return s->M * 4; }
   int pair_elem_bytes() const { return s->hist ? 2 : 4; }
   int& a_ready() { return s->a_ready; }
   int& a_from() { return s->a_from; }
-  int groups(int k) const { return (s->jgroups > 1 && k >= 4 * s->jgroups) ? s->jgroups : 1; }
+  int groups(int k) const { return (s->shape.jgroups > 1 && k >= 4 * s->shape.jgroups) ? s->shape.jgroups : 1; }
   bool combine_due(int, int G) const { return G > 1; }
-  unsigned gu() const { return (unsigned)s->nblk_u; }
+  unsigned gu() const { return (unsigned)s->shape.nblk_u; }
 
   void sweep_u1(int n1) {
-    if (s->hist) VLAUNCH("k_sweep_u1_bf16", st, s->vec_u, k_sweep_u1_bf16, (gu(), TB, 0, st), s->M, n1, s->st, bf16_pairs(s->U), s->upd, s->part, s->ldp, s->ld);
-    else VLAUNCH("k_sweep_u1", st, s->vec_u, k_sweep_u1, (gu(), TB, 0, st), s->M, n1, s->st, s->U, s->upd, s->part, s->ldp, s->ld);
+    if (s->hist) VLAUNCH("k_sweep_u1_bf16", st, s->shape.vec_u, k_sweep_u1_bf16, (gu(), TB, 0, st), s->M, n1, s->st, bf16_pairs(s->U), s->upd, s->part, s->shape.ldp, s->shape.ld);
+    else VLAUNCH("k_sweep_u1", st, s->shape.vec_u, k_sweep_u1, (gu(), TB, 0, st), s->M, n1, s->st, s->U, s->upd, s->part, s->shape.ldp, s->shape.ld);
   }
   void reduce_a_check(int kd, double eps, int a_from) {
     LAUNCH("k_reduce_check", st, (k_reduce_a_check<<<dim3(std::max(kd, 1), RA + 1), RB, 0, st>>>(
-        s->st, s->part, s->nblk_u, s->ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace,
-        s->parta, s->nblk4, a_from)));
+        s->st, s->part, s->shape.nblk_u, s->shape.ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace,
+        s->parta, s->shape.nblk4, a_from)));
   }
   void sweep_v(int k) {
-    if (s->hist) VLAUNCH("k_sweep_v_bf16", st, s->vec_u, k_sweep_v_bf16, (gu(), TB, 0, st), s->M, k, s->st, bf16_pairs(s->V), s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
-    else VLAUNCH("k_sweep_v", st, s->vec_u, k_sweep_v, (gu(), TB, 0, st), s->M, k, s->st, s->V, s->upd, gold, gnew, s->coef, s->part, s->pstride, s->ldp, s->part2, s->nblk_u, s->ld, s->thr);
+    if (s->hist) VLAUNCH("k_sweep_v_bf16", st, s->shape.vec_u, k_sweep_v_bf16, (gu(), TB, 0, st), s->M, k, s->st, bf16_pairs(s->V), s->upd, gold, gnew, s->coef, s->part, s->shape.pstride, s->shape.ldp, s->part2, s->shape.nblk_u, s->shape.ld, s->thr);
+    else VLAUNCH("k_sweep_v", st, s->shape.vec_u, k_sweep_v, (gu(), TB, 0, st), s->M, k, s->st, s->V, s->upd, gold, gnew, s->coef, s->part, s->shape.pstride, s->shape.ldp, s->part2, s->shape.nblk_u, s->shape.ld, s->thr);
   }
   void reduce_cb(int k) {
-    LAUNCH("k_reduce_cb", st, (k_reduce_cb<<<dim3(std::max(k, 1), 3), RB, 0, st>>>(s->st, s->part, s->nblk_u, s->pstride, s->ldp, s->thr, k, s->coef, s->part2, s->nblk_u)));
+    LAUNCH("k_reduce_cb", st, (k_reduce_cb<<<dim3(std::max(k, 1), 3), RB, 0, st>>>(s->st, s->part, s->shape.nblk_u, s->shape.pstride, s->shape.ldp, s->thr, k, s->coef, s->part2, s->shape.nblk_u)));
   }
   template <int KB>
   void sweep_u2r(int k, int keep0) {
-    LAUNCH("k_sweep_u2d", st, (k_sweep_u2r<KB><<<(unsigned)s->nblk4, TB, 0, st>>>(s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta, s->ld, keep0)));
+    LAUNCH("k_sweep_u2d", st, (k_sweep_u2r<KB><<<(unsigned)s->shape.nblk4, TB, 0, st>>>(s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta, s->shape.ld, keep0)));
   }
   void sweep_u2d(int k, int keep0, size_t lds) {
-    LAUNCH("k_sweep_u2d", st, (k_sweep_u2d<<<(unsigned)s->nblk4, TB, lds, st>>>(s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta, s->ld, keep0)));
+    LAUNCH("k_sweep_u2d", st, (k_sweep_u2d<<<(unsigned)s->shape.nblk4, TB, lds, st>>>(s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->parta, s->shape.ld, keep0)));
   }
   void sweep_u2(int k) {
-    if (s->hist) VLAUNCH("k_sweep_u2_bf16", st, s->vec_u, k_sweep_u2_bf16, (gu(), TB, 0, st), s->M, k, s->st, bf16_pairs(s->U), s->upd, gold, gnew, s->coef, s->thr, s->ld);
-    else VLAUNCH("k_sweep_u2", st, s->vec_u, k_sweep_u2, (gu(), TB, 0, st), s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->ld);
+    if (s->hist) VLAUNCH("k_sweep_u2_bf16", st, s->shape.vec_u, k_sweep_u2_bf16, (gu(), TB, 0, st), s->M, k, s->st, bf16_pairs(s->U), s->upd, gold, gnew, s->coef, s->thr, s->shape.ld);
+    else VLAUNCH("k_sweep_u2", st, s->shape.vec_u, k_sweep_u2, (gu(), TB, 0, st), s->M, k, s->st, s->U, s->upd, gold, gnew, s->coef, s->thr, s->shape.ld);
   }
   void dots(int kd, int G) {
-    VLAUNCH("k_dots", st, s->vec, k_dots, (dim3((unsigned)s->nblk, G), TB, 0, st), s->M, kd, s->st, s->U, s->V, s->upd, gold, gnew, s->part, s->pstride, s->ldp, (int)cdiv(kd, G), s->ld);
+    VLAUNCH("k_dots", st, s->shape.vec, k_dots, (dim3((unsigned)s->shape.nblk, G), TB, 0, st), s->M, kd, s->st, s->U, s->V, s->upd, gold, gnew, s->part, s->shape.pstride, s->shape.ldp, (int)cdiv(kd, G), s->shape.ld);
   }
   void reduce_check(int kd, double eps) {
     LAUNCH("k_reduce_check", st, (k_reduce_check<<<dim3(std::max(kd, 1), 4), RB, 0, st>>>(
-        s->st, s->part, s->nblk, s->pstride, s->ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace)));
+        s->st, s->part, s->shape.nblk, s->shape.pstride, s->shape.ldp, s->thr, kd, s->coef, s->nrm_part, np, s->rel_trace, s->abs_trace, eps, s->seq_len, s->keep_trace)));
   }
   void axpy(int k, int G, bool own_width) {
-    const int nb = own_width ? s->nblk_ax : s->nblk;
-    VLAUNCH("k_axpy", st, own_width ? s->vec_ax : s->vec, k_axpy, (dim3((unsigned)nb, G), TB, 0, st), s->M, k, s->st, s->U, s->V, s->upd, gold, gnew, s->coef, s->thr, s->part, nb, (int)cdiv(std::max(k, 1), G), s->jpart, s->ld);
+    const int nb = own_width ? s->shape.nblk_ax : s->shape.nblk;
+    VLAUNCH("k_axpy", st, own_width ? s->shape.vec_ax : s->shape.vec, k_axpy, (dim3((unsigned)nb, G), TB, 0, st), s->M, k, s->st, s->U, s->V, s->upd, gold, gnew, s->coef, s->thr, s->part, nb, (int)cdiv(std::max(k, 1), G), s->jpart, s->shape.ld);
   }
   void combine(int k, int G) {
-    VLAUNCH("k_axpy_combine", st, s->vec, k_axpy_combine, ((unsigned)s->nblk, TB, 0, st), s->M, k, G, s->st, s->jpart, s->U, s->V, s->upd, gold, gnew, s->part, s->nblk, s->ld);
+    VLAUNCH("k_axpy_combine", st, s->shape.vec, k_axpy_combine, ((unsigned)s->shape.nblk, TB, 0, st), s->M, k, G, s->st, s->jpart, s->U, s->V, s->upd, gold, gnew, s->part, s->shape.nblk, s->shape.ld);
   }
   void final_pass(int k, bool own_width) {
-    const int nb = own_width ? s->nblk_ax : s->nblk;
-    VLAUNCH("k_final", st, own_width ? s->vec_ax : s->vec, k_final, ((unsigned)nb, TB, 0, st), s->M, k, s->st, s->U, s->upd, s->ld, s->part, nb);
+    const int nb = own_width ? s->shape.nblk_ax : s->shape.nblk;
+    VLAUNCH("k_final", st, own_width ? s->shape.vec_ax : s->shape.vec, k_final, ((unsigned)nb, TB, 0, st), s->M, k, s->st, s->U, s->upd, s->shape.ld, s->part, nb);
   }
 };
 
 // One iteration's update of one solver, after fx = f(x_next) is available.
 // fused_npart > 0: the f kernel already produced g and the norm partials (fused_npart entries each)
 static void launch_update(psignn_broyden* s, int k, double eps, hipStream_t st, int fused_npart = 0) {
-  SingleTarget t{s, st, s->gbuf[(k + 1) & 1], s->gbuf[k & 1], fused_npart ? fused_npart : s->nblk};
+  SingleTarget t{s, st, s->gbuf[(k + 1) & 1], s->gbuf[k & 1], fused_npart ? fused_npart : s->shape.nblk};
   if (!fused_npart) {
     PROF_BYTES(3 * (int64_t)s->M * 4);
-    VLAUNCH("k_resid", st, s->vec, k_resid, ((unsigned)s->nblk, TB, 0, st), s->M, s->st, s->xbuf, s->fx, t.gnew, s->nrm_part, s->nblk);
+    VLAUNCH("k_resid", st, s->shape.vec, k_resid, ((unsigned)s->shape.nblk, TB, 0, st), s->M, s->st, s->xbuf, s->fx, t.gnew, s->nrm_part, s->shape.nblk);
   }
   update_chain(t, k, eps);
 }
@@ -1530,15 +1357,15 @@ static int read_status(psignn_broyden* s, hipStream_t st) {
 
 static int finish(psignn_broyden* s, float* d_result, psignn_solve_info_t* info, double* h_rel, double* h_abs,
                   hipStream_t st) {
-  unsigned g = (unsigned)s->nblk;
+  unsigned g = (unsigned)s->shape.nblk;
   int rc = 0;
   if (d_result) {
     const int32_t* sel_low = reinterpret_cast<const int32_t*>(s->st) + sel_off_low();
     if (s->plan && s->plan_order) {  // iterates live in plan order: select into fx, then back to the caller's numbering
-      VPLAIN(s->vec, k_copy_sel, (g, TB, 0, st), s->M, s->xbuf, sel_low, 0, s->fx);
+      VPLAIN(s->shape.vec, k_copy_sel, (g, TB, 0, st), s->M, s->xbuf, sel_low, 0, s->fx);
       if ((rc = psignn_plan_permute(s->plan, s->fx, D, d_result, 0, st))) return rc;
     } else {
-      VPLAIN(s->vec, k_copy_sel, (g, TB, 0, st), s->M, s->xbuf, sel_low, 0, d_result);
+      VPLAIN(s->shape.vec, k_copy_sel, (g, TB, 0, st), s->M, s->xbuf, sel_low, 0, d_result);
     }
   }
   if ((rc = read_status(s, st))) return rc;
@@ -1572,7 +1399,7 @@ extern "C" int psignn_broyden_solve(psignn_broyden_t* s, const float* W, int nl,
   hipStream_t st = (hipStream_t)stream;
   s->plan_order = 1;
   if (poll_every <= 0) poll_every = 8;
-  unsigned g = (unsigned)s->nblk;
+  unsigned g = (unsigned)s->shape.nblk;
   const int32_t* sel_nxt = reinterpret_cast<const int32_t*>(s->st) + sel_off_nxt();
   k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
   // node tensors into plan order once per solve (identity copy on an untiled plan)
@@ -1584,7 +1411,7 @@ extern "C" int psignn_broyden_solve(psignn_broyden_t* s, const float* W, int nl,
   const float* nrmp = p->mixed ? s->nrmp : nullptr;
   // gx0 = f(x0) - x0, update = gx0 (solver.py:131-136)
   if ((rc = psignn_f_eval_p(p, W, nl, s->h0p, nullptr, 0, s->h0p, s->prbp, nrmp, s->fx, s->fwork, st))) return rc;
-  VPLAIN(s->vec, k_begin, (g, TB, 0, st), s->M, s->h0p, s->fx, s->xbuf, s->gbuf[0], s->upd);
+  VPLAIN(s->shape.vec, k_begin, (g, TB, 0, st), s->M, s->h0p, s->fx, s->xbuf, s->gbuf[0], s->upd);
   const bool fused = p->tiled && (nl == 1 || p->mixed);
   const int32_t* st_words = reinterpret_cast<const int32_t*>(s->st);
   // (Replaying each poll_every chunk of iterations from a captured HIP graph was measured and removed: no gain,
@@ -1598,7 +1425,7 @@ extern "C" int psignn_broyden_solve(psignn_broyden_t* s, const float* W, int nl,
       launch_update(s, it, eps, st, rc);
     } else {
       PROF_BYTES(3 * (int64_t)s->M * 4);
-      VLAUNCH("k_xnext", st, s->vec, k_xnext, (g, TB, 0, st), s->M, s->st, s->xbuf, s->upd, nullptr);
+      VLAUNCH("k_xnext", st, s->shape.vec, k_xnext, (g, TB, 0, st), s->M, s->st, s->xbuf, s->upd, nullptr);
       rc = psignn_f_eval_p(p, W, nl, s->xbuf, sel_nxt, s->M, s->h0p, s->prbp, nrmp, s->fx, s->fwork, st);
       if (rc) return rc;
       launch_update(s, it, eps, st);
@@ -1645,7 +1472,7 @@ __global__ __launch_bounds__(RB) void kb_reduce_check(const BatchDesc* __restric
 template <int VEC>
 __global__ __launch_bounds__(TB) void kb_axpy(const BatchDesc* __restrict__ descs, int k, int own_width, int par) {
   const BatchDesc& d = descs[blockIdx.z];
-  // own_width: the axpy / final passes run unsplit with their own vector width (broyden_alloc: vec_ax != vec)
+  // own_width: the axpy / final passes run unsplit with their own vector width (broyden_shape: vec_ax != vec)
   const int G = own_width ? 1 : batch_groups(d, k);
   const int nb = own_width ? d.nblk_ax : d.nblk;
   if ((int)blockIdx.x >= nb || (int)blockIdx.y >= G) return;
@@ -1729,13 +1556,13 @@ static BatchShape shard_shape(int n, psignn_broyden_t* const* sv) {
   BatchShape sh;
   sh.n = n;
   for (int m = 0; m < n; ++m) {
-    const psignn_broyden* s = sv[m];
-    sh.max_g = std::max(sh.max_g, s->nblk);
-    sh.max_ga = std::max(sh.max_ga, s->nblk_ax);
-    sh.max_gu = std::max(sh.max_gu, s->nblk_u);
-    sh.max_g4 = std::max(sh.max_g4, s->nblk4);
-    sh.max_G = std::max(sh.max_G, s->jgroups);
-    sh.Mtot4 += s->M * 4;
+    const shapes::BroydenShape& c = sv[m]->shape;
+    sh.max_g = std::max(sh.max_g, c.nblk);
+    sh.max_ga = std::max(sh.max_ga, c.nblk_ax);
+    sh.max_gu = std::max(sh.max_gu, c.nblk_u);
+    sh.max_g4 = std::max(sh.max_g4, c.nblk4);
+    sh.max_G = std::max(sh.max_G, c.jgroups);
+    sh.Mtot4 += sv[m]->M * 4;
   }
   return sh;
 }
@@ -1748,7 +1575,8 @@ struct ShardTarget {
   BatchShape& sh;
   const BatchDesc* dd;
   hipStream_t st;
-  const psignn_broyden& size_class() const { return *s0; }
+  const shapes::BroydenShape& size_class() const { return s0->shape; }
+  void bytes(int64_t b) const { PROF_BYTES(b); }
   int64_t vec_bytes() const { return sh.Mtot4; }
   int pair_elem_bytes() const { return 4; }
   int& a_ready() { return sh.a_ready; }
@@ -1758,39 +1586,40 @@ struct ShardTarget {
   bool combine_due(int k, int) const { return sh.max_G > 1 && k >= 4 * 2; }   // some mesh may split from k = 4 * jgroups on (jgroups >= 2)
   dim3 grid(int x, int y = 1) const { return dim3((unsigned)x, (unsigned)y, (unsigned)sh.n); }
 
-  void sweep_u1(int n1) { VLAUNCH("k_sweep_u1", st, s0->vec_u, kb_sweep_u1, (grid(sh.max_gu), TB, 0, st), dd, n1); }
+  void sweep_u1(int n1) { VLAUNCH("k_sweep_u1", st, s0->shape.vec_u, kb_sweep_u1, (grid(sh.max_gu), TB, 0, st), dd, n1); }
   void reduce_a_check(int kd, double eps, int a_from) {
     LAUNCH("k_reduce_check", st, (kb_reduce_a_check<<<grid(std::max(kd, 1), RA + 1), RB, 0, st>>>(dd, kd, eps, a_from)));
   }
-  void sweep_v(int k) { VLAUNCH("k_sweep_v", st, s0->vec_u, kb_sweep_v, (grid(sh.max_gu), TB, 0, st), dd, k, k & 1); }
+  void sweep_v(int k) { VLAUNCH("k_sweep_v", st, s0->shape.vec_u, kb_sweep_v, (grid(sh.max_gu), TB, 0, st), dd, k, k & 1); }
   void reduce_cb(int k) { LAUNCH("k_reduce_cb", st, (kb_reduce_cb<<<grid(std::max(k, 1), 3), RB, 0, st>>>(dd, k))); }
   template <int KB>
   void sweep_u2r(int k, int keep0) { LAUNCH("k_sweep_u2d", st, (kb_sweep_u2r<KB><<<grid(sh.max_g4), TB, 0, st>>>(dd, k, keep0, k & 1))); }
   void sweep_u2d(int k, int keep0, size_t lds) { LAUNCH("k_sweep_u2d", st, (kb_sweep_u2d<<<grid(sh.max_g4), TB, lds, st>>>(dd, k, keep0, k & 1))); }
-  void sweep_u2(int k) { VLAUNCH("k_sweep_u2", st, s0->vec_u, kb_sweep_u2, (grid(sh.max_gu), TB, 0, st), dd, k, k & 1); }
-  void dots(int kd, int) { VLAUNCH("k_dots", st, s0->vec, kb_dots, (grid(sh.max_g, sh.max_G), TB, 0, st), dd, kd, kd & 1); }
+  void sweep_u2(int k) { VLAUNCH("k_sweep_u2", st, s0->shape.vec_u, kb_sweep_u2, (grid(sh.max_gu), TB, 0, st), dd, k, k & 1); }
+  void dots(int kd, int) { VLAUNCH("k_dots", st, s0->shape.vec, kb_dots, (grid(sh.max_g, sh.max_G), TB, 0, st), dd, kd, kd & 1); }
   void reduce_check(int kd, double eps) { LAUNCH("k_reduce_check", st, (kb_reduce_check<<<grid(std::max(kd, 1), 4), RB, 0, st>>>(dd, kd, eps))); }
   void axpy(int k, int, bool own_width) {
-    if (own_width) VLAUNCH("k_axpy", st, s0->vec_ax, kb_axpy, (grid(sh.max_ga), TB, 0, st), dd, k, 1, k & 1);
-    else VLAUNCH("k_axpy", st, s0->vec, kb_axpy, (grid(sh.max_g, sh.max_G), TB, 0, st), dd, k, 0, k & 1);
+    if (own_width) VLAUNCH("k_axpy", st, s0->shape.vec_ax, kb_axpy, (grid(sh.max_ga), TB, 0, st), dd, k, 1, k & 1);
+    else VLAUNCH("k_axpy", st, s0->shape.vec, kb_axpy, (grid(sh.max_g, sh.max_G), TB, 0, st), dd, k, 0, k & 1);
   }
-  void combine(int k, int) { VLAUNCH("k_axpy_combine", st, s0->vec, kb_axpy_combine, (grid(sh.max_g), TB, 0, st), dd, k, k & 1); }
+  void combine(int k, int) { VLAUNCH("k_axpy_combine", st, s0->shape.vec, kb_axpy_combine, (grid(sh.max_g), TB, 0, st), dd, k, k & 1); }
   void final_pass(int k, bool own_width) {
-    VLAUNCH("k_final", st, own_width ? s0->vec_ax : s0->vec, kb_final, (grid(own_width ? sh.max_ga : sh.max_g), TB, 0, st), dd, k, own_width ? 1 : 0);
+    VLAUNCH("k_final", st, own_width ? s0->shape.vec_ax : s0->shape.vec, kb_final, (grid(own_width ? sh.max_ga : sh.max_g), TB, 0, st), dd, k, own_width ? 1 : 0);
   }
 };
 
 // ---- what the two batched solves share around the chain
 // the fields of a mesh's descriptor that both solves set alike; the caller adds tile_base, nrmp, grad and n_nrm
 static void fill_desc(const psignn_broyden* s, BatchDesc& d) {
-  d.M = s->M; d.ld = s->ld; d.nblk = s->nblk; d.npart = s->npart; d.nblk_ax = s->nblk_ax; d.jgroups = s->jgroups;
+  const shapes::BroydenShape& c = s->shape;
+  d.M = s->M; d.ld = c.ld; d.nblk = c.nblk; d.npart = c.npart; d.nblk_ax = c.nblk_ax; d.jgroups = c.jgroups;
   d.thr = s->thr; d.seq_len = s->seq_len; d.keep_trace = s->keep_trace; d.n_tiles = (int)s->plan->n_tiles;
   d.st = reinterpret_cast<int32_t*>(s->st);
   d.U = s->U; d.V = s->V; d.xbuf = s->xbuf; d.g0 = s->gbuf[0]; d.g1 = s->gbuf[1]; d.upd = s->upd; d.part = s->part; d.coef = s->coef;
   d.nrm_part = s->nrm_part; d.jpart = s->jpart; d.rel_trace = s->rel_trace; d.abs_trace = s->abs_trace;
   d.ctx = s->plan->d_ctx; d.h0p = s->h0p; d.prbp = s->prbp;
-  d.part2 = s->part2; d.nblk_u = s->nblk_u; d.npart_u = s->npart_u;
-  d.parta = s->parta; d.nblk4 = s->nblk4; d.pad_ = 0; d.pstride = s->pstride;
+  d.part2 = s->part2; d.nblk_u = c.nblk_u; d.npart_u = c.npart_u;
+  d.parta = s->parta; d.nblk4 = c.nblk4; d.pad_ = 0; d.pstride = c.pstride;
   d.fx = s->fx; d.xcopy = s->h0p; d.pad2_ = 0;
 }
 // the host's poll: *h_done = 1 when every mesh's stop test has fired
@@ -1809,12 +1638,6 @@ static int shard_finish(int n, psignn_broyden_t** sv, float* const* d_results, p
   return rc;
 }
 
-// one size class: the vector width / split layout / threshold / fold limits that broyden_alloc derives from the shard size
-static bool same_size_class(const psignn_broyden* a, const psignn_broyden* b) {
-  return a->vec == b->vec && a->vec_ax == b->vec_ax && a->uvu == b->uvu && a->vec_u == b->vec_u && a->thr == b->thr &&
-         a->u2d_kmax == b->u2d_kmax && a->u2d_keep == b->u2d_keep && a->u2d_reg == b->u2d_reg;
-}
-
 // 1 when psignn_broyden_solve_batch takes these solvers together: tiled plans of ONE boundary-condition family and one size
 // class, fp32 pairs -- a host-side question, asked before the solve so that a shard the batched solver cannot take is not an error path.
 extern "C" int psignn_broyden_batchable(int n, psignn_broyden_t* const* sv) {
@@ -1824,7 +1647,7 @@ extern "C" int psignn_broyden_batchable(int n, psignn_broyden_t* const* sv) {
     const psignn_broyden* s = sv[m];
     if (!s || !s->plan || !s->plan->tiled || s->plan->mixed != s0->plan->mixed) return 0;
     if (s->hist) return 0;   // the batched kernels sweep fp32 pairs only
-    if (!same_size_class(s, s0)) return 0;
+    if (!s->shape.same_size_class(s0->shape)) return 0;
   }
   return 1;
 }
@@ -1862,7 +1685,7 @@ extern "C" int psignn_broyden_solve_batch(int n, psignn_broyden_t** sv, const fl
     if (p->mixed && (rc = psignn_plan_permute(p, nrm[m], 2, s->nrmp, 1, st))) return rc;
     const float* nrmp = p->mixed ? s->nrmp : nullptr;
     if ((rc = psignn_f_eval_p(p, W, nl, s->h0p, nullptr, 0, s->h0p, s->prbp, nrmp, s->fx, s->fwork, st))) return rc;
-    VPLAIN(s->vec, k_begin, ((unsigned)s->nblk, TB, 0, st), s->M, s->h0p, s->fx, s->xbuf, s->gbuf[0], s->upd);
+    VPLAIN(s->shape.vec, k_begin, ((unsigned)s->shape.nblk, TB, 0, st), s->M, s->h0p, s->fx, s->xbuf, s->gbuf[0], s->upd);
     BatchDesc& d = hd[m];
     fill_desc(s, d);
     d.tile_base = n_slots; d.nrmp = nrmp; d.grad = nullptr; d.n_nrm = (int)p->n_tiles;   // the fused f kernel: one norm pair per tile
@@ -1913,17 +1736,17 @@ template <class F>
 static int adjoint_loop(psignn_broyden* s, const float* grad, double eps, int poll_every, F&& vjp, float* d_result,
                         psignn_solve_info_t* info, double* h_rel, double* h_abs, hipStream_t st) {
   if (poll_every <= 0) poll_every = 8;
-  unsigned g = (unsigned)s->nblk;
+  unsigned g = (unsigned)s->shape.nblk;
   int rc;
   k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
   // y0 = 0, map(y0) = grad  ->  g0 = grad, update = grad  (solver.py:131-136 with f(0) = grad)
   HIP_TRY(hipMemsetAsync(s->h0p, 0, (size_t)s->M * 4, st));
-  VPLAIN(s->vec, k_begin, (g, TB, 0, st), s->M, s->h0p, grad, s->xbuf, s->gbuf[0], s->upd);
+  VPLAIN(s->shape.vec, k_begin, (g, TB, 0, st), s->M, s->h0p, grad, s->xbuf, s->gbuf[0], s->upd);
   for (int it = 0; it < s->thr; ++it) {
     // x_next = x + update, kept also in h0p (fixed address for the VJP kernels)
-    VLAUNCH("k_xnext", st, s->vec, k_xnext, (g, TB, 0, st), s->M, s->st, s->xbuf, s->upd, s->h0p);
+    VLAUNCH("k_xnext", st, s->shape.vec, k_xnext, (g, TB, 0, st), s->M, s->st, s->xbuf, s->upd, s->h0p);
     if ((rc = vjp(s->h0p, s->fx))) return rc;
-    VLAUNCH("k_addv", st, s->vec, k_addv, (g, TB, 0, st), s->M, s->st, s->fx, grad);
+    VLAUNCH("k_addv", st, s->shape.vec, k_addv, (g, TB, 0, st), s->M, s->st, s->fx, grad);
     launch_update(s, it, eps, st);
     if ((it + 1) % poll_every == 0 || it + 1 == s->thr) {
       rc = read_status(s, st);
@@ -2074,10 +1897,10 @@ extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** 
     if ((rc = psignn_plan_permute(p, grads[m], D, gr_p, 1, st))) return rc;
     k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
     HIP_TRY(hipMemsetAsync(s->h0p, 0, (size_t)s->M * 4, st));
-    VPLAIN(s->vec, k_begin, ((unsigned)s->nblk, TB, 0, st), s->M, s->h0p, gr_p, s->xbuf, s->gbuf[0], s->upd);
+    VPLAIN(s->shape.vec, k_begin, ((unsigned)s->shape.nblk, TB, 0, st), s->M, s->h0p, gr_p, s->xbuf, s->gbuf[0], s->upd);
     BatchDesc& d = hd[m];
     fill_desc(s, d);
-    d.tile_base = 0; d.nrmp = nullptr; d.grad = gr_p; d.n_nrm = s->nblk;   // the unfused residual: one norm pair per block
+    d.tile_base = 0; d.nrmp = nullptr; d.grad = gr_p; d.n_nrm = s->shape.nblk;   // the unfused residual: one norm pair per block
     l.w = s->h0p;
     l.out = s->fx;
     l.st = d.st;
@@ -2099,12 +1922,12 @@ extern "C" int psignn_broyden_solve_adjoint_lin_batch(int n, psignn_broyden_t** 
   const dim3 gv = t.grid(sh.max_g);
   for (int it = 0; it < thr; ++it) {
     PROF_BYTES(3 * sh.Mtot4);
-    VLAUNCH("k_xnext", st, s0->vec, kb_xnext, (gv, TB, 0, st), d_descs.get());
+    VLAUNCH("k_xnext", st, s0->shape.vec, kb_xnext, (gv, TB, 0, st), d_descs.get());
     PROF_BYTES(bv_tot);
     rc = psignn_lin_vjp_batch(d_lin.get(), n, n_slots, max_rows, W, s0->plan->mixed, offsetof(Status, done) / 4, st);
     if (rc) return rc;
     PROF_BYTES(4 * sh.Mtot4);
-    VLAUNCH("k_addv_resid", st, s0->vec, kb_addv_resid, (gv, TB, 0, st), d_descs.get(), it & 1);
+    VLAUNCH("k_addv_resid", st, s0->shape.vec, kb_addv_resid, (gv, TB, 0, st), d_descs.get(), it & 1);
     update_chain(t, it, eps);
     if ((it + 1) % poll_every == 0 || it + 1 == thr) {
       if ((rc = shard_all_done(d_descs.get(), n, d_done.get(), h_done.get(), st))) return rc;
@@ -2121,10 +1944,10 @@ extern "C" int psignn_broyden_get_iterate(const psignn_broyden_t* s, int i, floa
   ARG_CHECK(s->keep_trace, "solver was created without keep_trace");
   ARG_CHECK(i >= 0 && i <= s->thr, "iterate index out of range");
   if (s->plan && s->plan_order) {
-    VPLAIN(s->vec, k_copy_sel, ((unsigned)s->nblk, TB, 0, (hipStream_t)stream), s->M, s->xbuf, nullptr, i, s->fx);
+    VPLAIN(s->shape.vec, k_copy_sel, ((unsigned)s->shape.nblk, TB, 0, (hipStream_t)stream), s->M, s->xbuf, nullptr, i, s->fx);
     return psignn_plan_permute(s->plan, s->fx, D, d_dst, 0, stream);
   }
-  VPLAIN(s->vec, k_copy_sel, ((unsigned)s->nblk, TB, 0, (hipStream_t)stream), s->M, s->xbuf, nullptr, i, d_dst);
+  VPLAIN(s->shape.vec, k_copy_sel, ((unsigned)s->shape.nblk, TB, 0, (hipStream_t)stream), s->M, s->xbuf, nullptr, i, d_dst);
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
@@ -2140,19 +1963,19 @@ extern "C" int psignn_broyden_get_pair(const psignn_broyden_t* s, int j, int whi
   ARG_CHECK(s && d_dst, "NULL argument");
   ARG_CHECK(which >= 0 && which <= 3, "which: 0 = U_j, 1 = V_j, 2 = the current update vector, 3 = partials of the folded sweep");
   if (which == 3) {   // diagnostics: the (nblk4, PARTA_LD) per-block partials of a, as they are (d_dst: at least that many floats)
-    HIP_TRY(hipMemcpyAsync(d_dst, s->parta, (size_t)std::min<int64_t>(s->M, (int64_t)s->nblk4 * PARTA_LD) * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(d_dst, s->parta, (size_t)std::min<int64_t>(s->M, (int64_t)s->shape.nblk4 * PARTA_LD) * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PSIGNN_OK;
   }
   ARG_CHECK(which == 2 || (j >= 0 && j < s->thr), "pair index out of range");
   if (s->hist && which != 2) {   // bf16 pair: widened (exactly) to fp32
-    const __bf16* row = bf16_pairs(which ? s->V : s->U) + (int64_t)j * s->ld;
+    const __bf16* row = bf16_pairs(which ? s->V : s->U) + (int64_t)j * s->shape.ld;
     float* dst = s->plan && s->plan_order ? s->fx : d_dst;
     k_widen_bf16<<<(unsigned)std::min<int64_t>(cdiv(s->M, TB), 4096), TB, 0, (hipStream_t)stream>>>(s->M, row, dst);
     HIP_TRY(hipGetLastError());
     if (s->plan && s->plan_order) return psignn_plan_permute(s->plan, s->fx, D, d_dst, 0, stream);
     return PSIGNN_OK;
   }
-  const float* row = which == 2 ? s->upd : (which ? s->V : s->U) + (int64_t)j * s->ld;
+  const float* row = which == 2 ? s->upd : (which ? s->V : s->U) + (int64_t)j * s->shape.ld;
   if (s->plan && s->plan_order) {
     HIP_TRY(hipMemcpyAsync(s->fx, row, (size_t)s->M * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return psignn_plan_permute(s->plan, s->fx, D, d_dst, 0, stream);
@@ -2166,26 +1989,26 @@ extern "C" int psignn_broyden_ext_begin(psignn_broyden_t* s, const float* d_x0, 
   ARG_CHECK(s && d_x0 && d_fx0, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
   k_init_status<<<4, TB, 0, st>>>(s->st, s->rel_trace, s->abs_trace, s->thr, s->stop_abs);
-  VPLAIN(s->vec, k_begin, ((unsigned)s->nblk, TB, 0, st), s->M, d_x0, d_fx0, s->xbuf, s->gbuf[0], s->upd);
+  VPLAIN(s->shape.vec, k_begin, ((unsigned)s->shape.nblk, TB, 0, st), s->M, d_x0, d_fx0, s->xbuf, s->gbuf[0], s->upd);
   s->ext_iter = 0;
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
 extern "C" int psignn_broyden_ext_next_x(psignn_broyden_t* s, float* d_x_new, void* stream) {
   ARG_CHECK(s && d_x_new, "NULL argument");
-  VPLAIN(s->vec, k_xnext, ((unsigned)s->nblk, TB, 0, (hipStream_t)stream), s->M, s->st, s->xbuf, s->upd, d_x_new);
+  VPLAIN(s->shape.vec, k_xnext, ((unsigned)s->shape.nblk, TB, 0, (hipStream_t)stream), s->M, s->st, s->xbuf, s->upd, d_x_new);
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
 extern "C" int psignn_broyden_ext_trial_x(psignn_broyden_t* s, double step, float* d_x_trial, void* stream) {
   ARG_CHECK(s && d_x_trial, "NULL argument");
-  VPLAIN(s->vec, k_xtrial, ((unsigned)s->nblk, TB, 0, (hipStream_t)stream), s->M, s->st, s->xbuf, s->upd, (float)step, d_x_trial, 0);
+  VPLAIN(s->shape.vec, k_xtrial, ((unsigned)s->shape.nblk, TB, 0, (hipStream_t)stream), s->M, s->st, s->xbuf, s->upd, (float)step, d_x_trial, 0);
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
 extern "C" int psignn_broyden_ext_scale_step(psignn_broyden_t* s, double step, void* stream) {
   ARG_CHECK(s, "NULL argument");
-  VPLAIN(s->vec, k_xtrial, ((unsigned)s->nblk, TB, 0, (hipStream_t)stream), s->M, s->st, s->xbuf, s->upd, (float)step, nullptr, 1);
+  VPLAIN(s->shape.vec, k_xtrial, ((unsigned)s->shape.nblk, TB, 0, (hipStream_t)stream), s->M, s->st, s->xbuf, s->upd, (float)step, nullptr, 1);
   s->a_ready = 0;   // the update changed: a = U^T dx has to be swept again
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;

@@ -22,11 +22,14 @@ A missed pair, a wrong coefficient, a stale `a`, an uncovered element range are 
 Besides: the first iterations against ``oracle.broyden`` (before the chaos), the converged iterate against the closed form
 b / (1 - c), bit-equality of the register and LDS forms of the folded sweep, and bit-equality of batched, fused single-mesh
 and host-driven solves, which carries the check over to ``psignn_broyden_solve`` and ``psignn_broyden_solve_batch``."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
-from conftest import load_weights, pkg, rel_l2
+from conftest import GOLDEN, load_weights, pkg, rel_l2
 from oracle import psignn_oracle as orc
 from recurrences import _check_iteration
 
@@ -264,6 +267,57 @@ def test_lds_fold_keeps_at_most_a_row_of_partials(dev, monkeypatch):
     _setenv(monkeypatch, {})
     (ra, xa), (rb, xb) = runs["lds_max"], runs["ask_38"]
     assert ra == rb and all(torch.equal(p, q) for p, q in zip(xa, xb))
+
+
+_CHAIN = {"k_sweep_u1", "k_sweep_v", "k_sweep_u2", "k_sweep_u2d", "k_reduce_check", "k_reduce_cb", "k_dots", "k_axpy", "k_axpy_combine", "k_final"}
+
+
+@pytest.fixture(scope="module")
+def schedule_table():
+    with open(os.path.join(GOLDEN, "broyden_schedule.json")) as f:
+        return {r["case"]: r for r in json.load(f)}
+
+
+@pytest.mark.parametrize("case", ["m4090", "width_switch", "above_reg_fold"])
+def test_library_runs_the_recorded_schedule(case, schedule_table, dev, monkeypatch):
+    """The built library against rows of tests/golden/broyden_schedule.json -- the table csrc/solver_shapes.h is checked against on
+    the CPU (tests/test_host_solver_shapes.py): ``nbytes`` of the handle and, per iteration of a solve with eps = 0, the update
+    chain's launches with their stated bytes.  M = 4 090: two-pass form, 4 floats per lane, a partial last block, the split and
+    its combine launch from k = 32.  M = 3 << 18, 28 iterations: the three-sweep form at the width switch, the fold crossing
+    k = 24 into the window.  M = 2 047 * 1 024 + 1, the shortest vector with the fold in registers: KB = 8 / 16 / 24 all occur."""
+    eng, nat = pkg("engine"), pkg("_native")
+    row = schedule_table[case]
+    M, thr = row["M"], row["thr"]
+    assert row["env"] == {} and row["n_tiles"] == 0 and row["hist"] == 0
+    _setenv(monkeypatch, {})
+    monkeypatch.delenv("PSIGNN_VEC16_MIN", raising=False)
+    monkeypatch.delenv("PSIGNN_VEC_AX4", raising=False)
+    gen = torch.Generator().manual_seed(0)
+    seq = 10 if M % 10 == 0 else 1                 # (as the table was recorded)
+    shape = (M // seq, seq)
+    c, b, x0 = (t.to(dev) for t in (0.05 + 0.945 * torch.rand(shape, generator=gen), torch.randn(shape, generator=gen), torch.randn(shape, generator=gen)))
+    sv = eng.DeviceBroyden(threshold=thr, keep_trace=bool(row["keep_trace"]), n_elems=M, seq_len=seq, device=dev)
+    assert sv.nbytes == row["nbytes"]
+    nat.prof_enable(True)
+    nat.prof_collect()
+    try:
+        out = sv.solve_callable(lambda x: c * x + b, x0, 0.0)
+        nat.prof_collect(with_bytes=True)
+        log = nat.prof_launch_log()
+    finally:
+        nat.prof_enable(False)
+    sv.close()
+    assert out["n_iter"] == thr
+    iters = []
+    for name, _, byts in log:
+        if name == "k_resid":                      # the head of every iteration of a host-driven solve
+            iters.append([])
+        elif name in _CHAIN:
+            assert byts % M == 0, (name, byts)
+            iters[-1].append([name, byts // M])
+    assert iters == row["iters"]
+    if case == "above_reg_fold":                   # kept pairs k - keep0: 0 .. 24 while all are kept, then the window of 16
+        assert sum(n == "k_sweep_u2d" for it in iters for n, _ in it) == thr - 1
 
 
 def _mesh_map(n, seed, dev, sd, phase=0.0):
