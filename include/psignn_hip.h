@@ -665,9 +665,14 @@ int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** solvers, const 
  * A_FF x_F = b, b = y_F - A_FD y_D (the mixed family's Neumann rows are free rows).  The handle keeps its own float64 copy of the
  * values (a 64-row sliced ELL in the plan's canonical column order), made once from d_a_ij in edge_index order, float32 (widened
  * exactly) or float64; the plan is not needed after create.
- * create checks what conjugate gradients need and fails with PSIGNN_EINVAL otherwise: every free-free entry has its transposed entry
- * and max |a_ij - a_ji| <= 1e-6 * max |a_ij| (a symmetric input rounds symmetrically: a valid matrix has defect 0), every free row has
- * a diagonal > 0, every value on a free row is finite.  Synchronous.
+ * A position (i, j) may be given more than once (edge_index may repeat a pair): A_ij is the SUM of the entries given for it, added in
+ * edge-id order in float64.  The solve multiplies by those sums, and symmetry, sym_defect and max |a_ij| below are judged on them: v, v
+ * against a single v is unsymmetric (2v != v); v/2, v/2 against a single v is symmetric.
+ * create checks what conjugate gradients need and fails with PSIGNN_EINVAL otherwise: every free-free position has its transposed
+ * position and max |A_ij - A_ji| <= 1e-6 * max |A_ij| (a symmetric input rounds symmetrically: a valid matrix without repeated positions
+ * has defect 0; sums of differently split pieces may differ by their rounding), every free row has a diagonal (the sum of its self
+ * loops) > 0, every value on a free row is finite -- the entries in Dirichlet columns included, the entries of Dirichlet rows not: those
+ * are never read and may hold anything.  Synchronous.
  * ------------------------------------------------------------------------------------------ */
 typedef struct psignn_cg psignn_cg_t;
 typedef struct {
@@ -676,7 +681,7 @@ typedef struct {
   double rel;           /* |r| / |b| of the recurrence residual at the end */
   double true_rel;      /* |(y - A x)_F| / |b|, recomputed from the returned x */
   double b_norm;        /* |b|, the lifted right-hand side on F */
-  double sym_defect;    /* max |a_ij - a_ji| over the free-free entries, measured at create */
+  double sym_defect;    /* max |A_ij - A_ji| over the free-free positions (repeated entries summed), measured at create */
 } psignn_cg_info_t;
 int psignn_cg_create(psignn_cg_t** out, const psignn_plan_t* plan, const void* d_a_ij /* (E) edge_index order */, int a_is_f64,
                      void* stream);

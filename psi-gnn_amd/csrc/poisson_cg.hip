@@ -133,9 +133,13 @@ __global__ void __launch_bounds__(CG_TB) k_cg_fill(int64_t N, int64_t n_slices, 
   if (i < N) diag[i] = free_row ? dg : 0.0;   // 0 marks a Dirichlet row for the update kernel (a free row's diagonal is checked > 0)
 }
 
-// Symmetry and definiteness evidence of A_FF: for every free-free off-diagonal entry (i, j) the transposed entry (j, i) is found by
-// binary search in row j (columns ascending); block partials of max |a_ij - a_ji| and max |a_ij|; bad |= 1 missing transposed entry,
-// 2 diagonal of a free row not > 0, 4 a value that is not finite.
+// Symmetry and definiteness evidence of A_FF.  A position given more than once is a run of equal columns in its row (the plan keeps
+// every entry, ordered by (column, edge id)), and A is the SUM of a run -- that is what k_cg_fill's diagonal and every product with the
+// ELL compute -- so the evidence is taken on sums: the first entry of a run adds up its run, finds the run of the transposed position
+// (j, i) by binary search in row j, adds that up and compares the two sums; the later entries of a run only get the finiteness test.
+// A run of one entry sums to that entry, so a matrix without repeated positions is judged by the same arithmetic as entry by entry.
+// Block partials of max |A_ij - A_ji| and max |A_ij|; bad |= 1 missing transposed position, 2 diagonal of a free row not > 0, 4 a
+// value that is not finite.
 __global__ void __launch_bounds__(CG_TB) k_cg_check(int64_t N, const uint8_t* __restrict__ flags, const int32_t* __restrict__ a_ptr,
                                                     const int32_t* __restrict__ a_col, const double* __restrict__ csr_val,
                                                     const double* __restrict__ diag, double* __restrict__ part_def,
@@ -146,20 +150,29 @@ __global__ void __launch_bounds__(CG_TB) k_cg_check(int64_t N, const uint8_t* __
   int32_t b = 0;
   if (i < N && !(flags[i] & FLAG_DIRICHLET)) {
     if (!(diag[i] > 0.0)) b |= 2;
-    for (int32_t k = a_ptr[i]; k < a_ptr[i + 1]; ++k) {
+    const int32_t k0 = a_ptr[i], k1 = a_ptr[i + 1];
+    for (int32_t k = k0; k < k1; ++k) {
       const int32_t j = a_col[k];
-      const double v = csr_val[k];
+      double v = csr_val[k];
       if (!isfinite(v)) b |= 4;
+      if (k > k0 && a_col[k - 1] == j) continue;   // a later entry of a run: summed by the run's first entry
       if (flags[j] & FLAG_DIRICHLET) continue;
+      for (int32_t m = k + 1; m < k1 && a_col[m] == j; ++m) v += csr_val[m];
       amax = fmax(amax, fabs(v));
       if (j == (int32_t)i) continue;
-      int32_t lo = a_ptr[j], hi = a_ptr[j + 1];
-      while (lo < hi) {
+      const int32_t j1 = a_ptr[j + 1];
+      int32_t lo = a_ptr[j], hi = j1;
+      while (lo < hi) {   // lower bound: the first entry of the transposed run
         const int32_t mid = lo + ((hi - lo) >> 1);
         if (a_col[mid] < (int32_t)i) lo = mid + 1; else hi = mid;
       }
-      if (lo < a_ptr[j + 1] && a_col[lo] == (int32_t)i) def = fmax(def, fabs(v - csr_val[lo]));
-      else b |= 1;
+      if (lo < j1 && a_col[lo] == (int32_t)i) {
+        double t = csr_val[lo];
+        for (int32_t m = lo + 1; m < j1 && a_col[m] == (int32_t)i; ++m) t += csr_val[m];
+        def = fmax(def, fabs(v - t));
+      } else {
+        b |= 1;
+      }
     }
   }
   if (b) atomicOr(bad, b);

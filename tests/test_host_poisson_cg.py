@@ -93,3 +93,93 @@ def test_host_solution_is_still_spsolve_exactly():
     assert torch.equal(data.make_hex_problem(n).sol, want)
     assert torch.equal(data.make_hex_problem(n, compute_sol=True).sol, want)
     assert torch.equal(data.make_hex_problem(n, compute_sol=False).sol, torch.zeros_like(want))
+
+
+# ------------------------------------------------------------------------------------------------ the reference pieces of
+# tests/test_gpu_poisson_cg_structure.py, held to that file's own gates without a device
+import poisson_cg_ref as ref
+
+TOL = 1e-12
+
+
+@pytest.mark.parametrize("name", ref.STRUCTURE_CASES)
+def test_numpy_recurrences_meet_the_gate_of_the_device_test(name):
+    """|x - u|_F / |u|_F <= kappa_gershgorin true_rel against lifted_direct, for pcg_trace at the device test's tol."""
+    _, A, y, dmask, u, kappa = ref.structure_case(name)
+    x, trace = ref.pcg_trace(A, y, dmask, TOL, 1000)
+    true_rel = ref.true_rel_of(A, y, dmask, x)
+    err, lim = ref.gate(x, u, dmask, kappa, true_rel)
+    print(f"{name}: iterations {len(trace) - 1} true_rel {true_rel:.3e} err {err:.3e} bound {lim:.3e} (kappa <= {kappa:.2f})")
+    assert trace[-1] <= TOL and true_rel <= 10 * TOL
+    assert err <= lim and kappa <= 9.0 * (1 + 1e-6)   # float32 rounding of the hub's diagonal moves rho = 0.8 by 1e-7
+    assert np.array_equal(x[dmask], y[dmask])
+
+
+def test_structure_cases_reach_the_paths_they_are_named_for():
+    depth = lambda A, dmask, s: int((np.diff(A.indptr)[64 * s:64 * s + 64] * ~dmask[64 * s:64 * s + 64]).max())
+    _, A, _, dmask = ref.structure_case("hub321")[:4]
+    lens = np.diff(A.indptr)
+    assert A.shape[0] == 321 and lens[0] == 321 and not dmask[0] and set(lens[1:]) == {3, 4}
+    assert [depth(A, dmask, s) for s in range(6)] == [321, 0, 4, 4, 4, 3]           # a deep lane, a depth-0 slice, a one-row tail slice
+    assert dmask[64:128].all() and dmask[300:].sum() == 3 and not dmask[320]
+    _, A, _, dmask = ref.structure_case("lonely")[:4]
+    lens, free = np.diff(A.indptr), ~dmask
+    assert A.shape[0] == 130 and (lens[free] == 1).sum() == 6                       # free rows that hold their diagonal only
+    assert np.flatnonzero(free[64:128]).tolist() == [63] and np.flatnonzero(free[128:]).tolist() == [0]
+    rows = ref.one_by_one_rows(A, dmask)
+    assert [int(i) for i in rows] == [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 63, 127, 128] and free.sum() - len(rows) == 48
+    assert sorted(set(lens[free])) == [1, 2, 3, 4]
+    for N, nblk, n_slices in ((65536, 256, 1024), (65537, 257, 1025)):
+        mesh, A, _, dmask = ref.structure_case(f"band{N}")[:4]
+        r, c = mesh.edge_index.numpy()
+        assert A.shape[0] == N and -(-N // 256) == nblk and -(-N // 64) == n_slices
+        assert np.abs(r - c).max() == 11 and 0.09 < dmask.mean() < 0.11
+        assert len({depth(A, dmask, s) for s in range(n_slices)}) > 3
+
+
+def test_lifted_direct_solves_the_free_rows_and_direct_does_not():
+    _, A, y, dmask, u, _ = ref.structure_case("hub321")
+    F = ~dmask
+    assert np.array_equal(u[dmask], y[dmask])
+    assert np.linalg.norm((A @ u - y)[F]) <= 1e-13 * np.linalg.norm(y[F])
+    w = ref.direct(A, y)                                   # solves the Dirichlet rows too: another system
+    assert np.linalg.norm((w - u)[F]) > 1e-3 * np.linalg.norm(u[F])
+
+
+@pytest.mark.parametrize("name", ["hub321", "hub321_f32", "lonely"])
+def test_gershgorin_bounds_the_condition_number(name):
+    _, A, _, dmask, _, kappa = ref.structure_case(name)
+    true = ref.kappa_scaled(A, dmask)
+    print(f"{name}: cond(D^-1/2 A_FF D^-1/2) {true:.3f} <= {kappa:.3f}")
+    assert 1.0 <= true <= kappa * (1 + 1e-12)
+
+
+def test_symmetry_evidence_is_taken_on_summed_entries():
+    mesh, _, _, dmask = ref.structure_case("hub321")[:4]
+    r, c, a = ref.entries_of(mesh)
+    amax = float(np.abs(a[~dmask[r] & ~dmask[c]]).max())
+    assert ref.symmetry_evidence(r, c, a, dmask) == (0.0, amax, False)
+    bad = ref.refused_matrices(r, c, a, dmask)
+    (r1, c1, a1), _ = bad["v, v against v"]                 # 2 v against v
+    k = len(r)
+    assert ref.symmetry_evidence(r1, c1, a1, dmask)[0] == abs(a1[k]) > 1e-6 * amax
+    assert ref.symmetry_evidence(*bad["no transposed entry"][0], dmask)[2] is True
+    half = a1.copy()
+    i = int(np.flatnonzero((r == r1[k]) & (c == c1[k]))[0])
+    half[i] = half[k] = a[i] / 2                            # v / 2 + v / 2 against v
+    assert ref.symmetry_evidence(r1, c1, half, dmask) == (0.0, amax, False)
+    rp, cp, ap = ref.in_pieces(r, c, a, np.random.default_rng(9))
+    S = ref.summed_entries(rp, cp, ap)
+    assert len(S) == len(r) and len(rp) > 1.9 * len(r)
+    assert max(abs(S[(i, j)] - v) for i, j, v in zip(r.tolist(), c.tolist(), a.tolist())) <= 2.0 ** -52 * amax
+    defect, am, missing = ref.symmetry_evidence(rp, cp, ap, dmask)
+    assert 0.0 < defect <= 1e-15 * amax and am == amax and not missing
+
+
+def test_numpy_recurrences_stop_before_a_breakdown():
+    A = ref.sp.csr_matrix(np.array([[1.0, 2.0], [2.0, 1.0]]))
+    x, trace = ref.pcg_trace(A, np.array([1.0, 0.0]), np.zeros(2, bool), TOL, 10)
+    assert x.tolist() == [1.0, 0.0] and trace == [1.0, 2.0]
+    x0 = np.array([0.5, -0.25])
+    x, trace = ref.pcg_trace(A, np.array([1.0, 0.0]), np.zeros(2, bool), TOL, 0, x0=x0)
+    assert x.tolist() == x0.tolist() and trace == [1.25]   # max_iter 0: the start; r_0 = (1, 0) - A x_0 = (1, -0.75)
