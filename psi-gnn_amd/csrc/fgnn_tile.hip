@@ -403,7 +403,7 @@ __device__ __forceinline__ void f_tile_body(const FuseArgs& fa, const int slot, 
     PHASE();
     mv2<D>(T + L::T_W1I_FR, x, Pi2);
     PHASE();
-    edge_pass_both_clamp<RS>(slots, nslots, lds, T + L::T_A_TO, T + L::T_A_FR, Pi, Pi2, S_to, S_fr, deg_in, deg_out);
+    edge_pass_both_clamp<RS, FUSED && !MIXED>(slots, nslots, lds, T + L::T_A_TO, T + L::T_A_FR, Pi, Pi2, S_to, S_fr, deg_in, deg_out);
     PHASE();
   }
   STAMP(3);

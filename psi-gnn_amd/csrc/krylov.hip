@@ -177,7 +177,7 @@ __device__ __forceinline__ void gm_dots_body(int64_t M, int64_t ld, int j, float
     if (i <= j) {
       if (act) {
         float v[VEC];
-        ldv_stream<VEC>(V + (int64_t)i * ld, e0, M, v);
+        ldv<VEC>(V + (int64_t)i * ld, e0, M, v);
 #pragma unroll
         for (int c = 0; c < VEC; ++c) s = fmaf(v[c], x[c], s);
       }
@@ -238,7 +238,7 @@ __device__ __forceinline__ void gm_axpy_body(int64_t M, int64_t ld, int j, const
     for (int i = 0; i <= j; ++i) {
       const float c = coef[i];
       float v[VEC];
-      ldv_stream<VEC>(V + (int64_t)i * ld, e0, M, v);
+      ldv<VEC>(V + (int64_t)i * ld, e0, M, v);
 #pragma unroll
       for (int q = 0; q < VEC; ++q) x[q] = fmaf(-c, v[q], x[q]);
     }
@@ -352,7 +352,7 @@ __device__ __forceinline__ void gm_combine_body(int64_t M, int64_t ld, const Gmr
   for (int i = 0; i < k; ++i) {
     const float c = coef[i];
     float v[VEC];
-    ldv_stream<VEC>(V + (int64_t)i * ld, e0, M, v);
+    ldv<VEC>(V + (int64_t)i * ld, e0, M, v);
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = fmaf(c, v[q], acc[q]);
   }

@@ -266,6 +266,7 @@ __device__ void check_block(Status* st, const float* __restrict__ part, int npar
 }
 
 // dots pass: per-block partials of a_j = dx.U_j, c_j = V_j.dg, b_j = V_j.g   for j < k
+// (the two-pass form -- short vectors, whose history stays in the cache -- reads and writes U and V with the default policy)
 template <int VEC>
 __device__ __forceinline__ void dots_body(int64_t M, int k, const Status* __restrict__ st,
                                              const float* __restrict__ U, const float* __restrict__ V,
@@ -298,8 +299,8 @@ __device__ __forceinline__ void dots_body(int64_t M, int k, const Status* __rest
     float u[VEC], v[VEC];
     float sa = 0.f, sc = 0.f, sb = 0.f;
     if (act) {
-      ldv_stream<VEC>(U + (int64_t)j * ld, e0, M, u);
-      ldv_stream<VEC>(V + (int64_t)j * ld, e0, M, v);
+      ldv<VEC>(U + (int64_t)j * ld, e0, M, u);
+      ldv<VEC>(V + (int64_t)j * ld, e0, M, v);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         sa = fmaf(dx[i], u[i], sa);
@@ -535,7 +536,7 @@ __device__ __forceinline__ void sweep_v_body(int64_t M, int k, const Status* __r
       av[i] = (av[i] != av[i]) ? 0.f : av[i];
       p2 = fmaf(av[i], g[i], p2);
     }
-    stv<VEC>(V + (int64_t)k * ld, e0, M, av);
+    stv_stream<VEC>(V + (int64_t)k * ld, e0, M, av);
   }
   block_pair_store(p1, p2, part2, nblk);
 }
@@ -642,7 +643,7 @@ __device__ __forceinline__ void sweep_u2_body(int64_t M, int k, const Status* __
     a1[i] = q;
     a2[i] = fmaf(-q, beta, a2[i]);
   }
-  stv<VEC>(U + (int64_t)k * ld, e0, M, a1);
+  stv_stream<VEC>(U + (int64_t)k * ld, e0, M, a1);
   stv<VEC>(upd, e0, M, a2);
 }
 template <int VEC>
@@ -780,6 +781,24 @@ __device__ __forceinline__ void st4_so(float* __restrict__ base, uint32_t boff, 
   f4g t = {v.x, v.y, v.z, v.w};
   *reinterpret_cast<__attribute__((address_space(1))) f4g*>(rb + boff) = t;
 }
+// streaming twins (same saddr form, non-temporal policy; see ldv_stream in vec_helpers.h): the U columns a register-fold sweep
+// reads once, and its store of the new column U[k].  No width gate here: the register fold runs where the vector or the shard has
+// at least 2 048 blocks of 1 024 floats (2M floats; solver_shapes.h), whatever the width of the other sweeps.  Smallest measured
+// points (profiles/stream_policy_ab.txt): a 270 901-node mesh at K = 20 (432 MB of history; the fold 32.9 -> 31.4 us) and a
+// 230 000-node mesh at K = 8, whose history (<= 147 MB) fits the Infinity Cache: level with the plain policy (15.5 -> 15.6 us).
+// Batched shards of 2M - 3M floats at small K are not measured.
+__device__ __forceinline__ float4 ld4_so_stream(const float* __restrict__ base, uint32_t boff) {
+  uint64_t rb = reinterpret_cast<uint64_t>(base);
+  asm("" : "+s"(rb));
+  const f4g t = __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) f4g*>(rb + boff));
+  return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ void st4_so_stream(float* __restrict__ base, uint32_t boff, float4 v) {
+  uint64_t rb = reinterpret_cast<uint64_t>(base);
+  asm("" : "+s"(rb));
+  f4g t = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(t, reinterpret_cast<__attribute__((address_space(1))) f4g*>(rb + boff));
+}
 __device__ __forceinline__ float rfl(float v) {   // wave-uniform value -> SGPR
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
@@ -794,7 +813,7 @@ __device__ __forceinline__ void u2r_kept(float (&a1)[4], float (&a2)[4], int k, 
   float4 kp[NK > 0 ? NK : 1];
   const float* Ub = U + (int64_t)j_keep0 * ld;
 #pragma unroll
-  for (int q = 0; q < NK; ++q) kp[q] = ld4_so(Ub + (int64_t)q * ld, off);
+  for (int q = 0; q < NK; ++q) kp[q] = ld4_so_stream(Ub + (int64_t)q * ld, off);
   if (FIRST) {   // all pairs are kept (j_keep0 = 0): the three state vectors are requested in the same burst as the NK rows of U
     const float4 x = ld4_so(upd, off), go = ld4_so(dgv, off), g = ld4_so(gv, off);
     a1[0] = x.x + (g.x - go.x); a1[1] = x.y + (g.y - go.y); a1[2] = x.z + (g.z - go.z); a1[3] = x.w + (g.w - go.w);
@@ -825,7 +844,7 @@ __device__ __forceinline__ void u2r_kept(float (&a1)[4], float (&a2)[4], int k, 
     a1[i] = q;
     a2[i] = fmaf(-q, beta, a2[i]);
   }
-  st4_so(U + (int64_t)k * ld, off, make_float4(a1[0], a1[1], a1[2], a1[3]));
+  st4_so_stream(U + (int64_t)k * ld, off, make_float4(a1[0], a1[1], a1[2], a1[3]));
   st4_so(upd, off, make_float4(a2[0], a2[1], a2[2], a2[3]));
 #pragma unroll
   for (int q = 0; q < NK; ++q) {
@@ -880,7 +899,7 @@ __device__ __forceinline__ void sweep_u2r_body(int64_t M, int k, const Status* _
         // the batched kernel a per-pair scalar read is a vector load whose latency sits inside the loop (see u2r_kept)
         const float cv = coef[(1 + half) * thr + j + lane8];
 #pragma unroll
-        for (int q = 0; q < U2D_UNROLL; ++q) u[q] = ld4_so(Uj + (int64_t)q * ld, off);
+        for (int q = 0; q < U2D_UNROLL; ++q) u[q] = ld4_so_stream(Uj + (int64_t)q * ld, off);
 #pragma unroll
         for (int q = 0; q < U2D_UNROLL; ++q) {
           const float cc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cv), q));
@@ -892,7 +911,7 @@ __device__ __forceinline__ void sweep_u2r_body(int64_t M, int k, const Status* _
       for (; j < j_keep0; ++j) {
         const float cc = rfl(coef[thr + j]), cb = rfl(coef[2 * thr + j]);
         asm volatile("" : "+v"(off));
-        const float4 u = ld4_so(U + (int64_t)j * ld, off);
+        const float4 u = ld4_so_stream(U + (int64_t)j * ld, off);
         a1[0] = fmaf(-cc, u.x, a1[0]); a1[1] = fmaf(-cc, u.y, a1[1]); a1[2] = fmaf(-cc, u.z, a1[2]); a1[3] = fmaf(-cc, u.w, a1[3]);
         a2[0] = fmaf(-cb, u.x, a2[0]); a2[1] = fmaf(-cb, u.y, a2[1]); a2[2] = fmaf(-cb, u.z, a2[2]); a2[3] = fmaf(-cb, u.w, a2[3]);
       }
@@ -1018,8 +1037,8 @@ __device__ __forceinline__ void axpy_body(int64_t M, int k, const Status* __rest
     for (int j = j0; j < j1; ++j) {
       float u[VEC], v[VEC];
       float ca = coef[j], cc = coef[thr + j], cb = coef[2 * thr + j];
-      ldv_stream<VEC>(U + (int64_t)j * ld, e0, M, u);
-      ldv_stream<VEC>(V + (int64_t)j * ld, e0, M, v);
+      ldv<VEC>(U + (int64_t)j * ld, e0, M, u);
+      ldv<VEC>(V + (int64_t)j * ld, e0, M, v);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         av[i] = fmaf(ca, v[i], av[i]);

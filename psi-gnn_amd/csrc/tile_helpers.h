@@ -236,13 +236,28 @@ __device__ __forceinline__ v2f pk_fma_lo_clamp(v2f w, v2f a, v2f z) {  // clamp(
   return r;
 }
 
+// One 16-byte slot record.  STREAM: requested with the non-temporal policy (global_load_dwordx4 ... nt).  The fused dirichlet Broyden
+// step asks for it: its records are read once per iteration with the whole history streamed in between -- 69.8 -> 66.7 us per step
+// at 1M nodes (profiles/stream_policy_ab.txt).  Back-to-back plain f, whose records stay in the Infinity Cache, lost 5 - 8 % with it
+// (50.2 -> 52.5 - 54 us) and keeps the default policy, as does every other kernel that walks the slots.
+template <bool STREAM>
+__device__ __forceinline__ uint4 ld_slot(const uint4* __restrict__ p) {
+  if constexpr (STREAM) {
+    typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
+    const u32x4s t = __builtin_nontemporal_load(reinterpret_cast<const u32x4s*>(p));
+    return make_uint4(t.x, t.y, t.z, t.w);
+  } else {
+    return *p;
+  }
+}
+
 // Both directions of the neighbour sum in ONE walk over the slots: a pair-merged slot is decoded once, its 80-byte (8 D) LDS row
 // [to | from] is read once, and the IN half (Phi_to, mirrored attr weights) and the OUT half (Phi_from) are evaluated back
 // to back.  Needs both attr blocks (6 D = 60 wave-uniform floats) in SGPRs for the whole loop -- affordable once the phase
 // barriers keep every other scalar load out of the loop's live range.  S_to / S_fr come back UNSCALED (multiplied by 2^40
 // at the end).  Slot records are loaded one round ahead; two rounds ahead was measured and removed (profiles/r2_f_tile_ab_runs.txt:
 // plain f 61.0 - 62.6 vs 57.5 - 58.8 us).
-template <int RS>
+template <int RS, bool STREAM = false>
 __device__ __forceinline__ void edge_pass_both_clamp(const uint4* __restrict__ slots, int nslots, const float* __restrict__ lds,
                                                      const float* __restrict__ AT_to, const float* __restrict__ AT_fr,
                                                      const v2f* Pi_to, const v2f* Pi_fr, v2f* S_to, v2f* S_fr,
@@ -261,9 +276,9 @@ __device__ __forceinline__ void edge_pass_both_clamp(const uint4* __restrict__ s
   }
   deg_in = deg_out = 0.f;
   if (nslots <= 0) return;
-  uint4 c0 = slots[0];
+  uint4 c0 = ld_slot<STREAM>(slots);
   for (int r = 0; r < nslots; ++r) {
-    const uint4 nx = slots[(int64_t)min(r + 1, nslots - 1) * 64];
+    const uint4 nx = ld_slot<STREAM>(slots + (int64_t)min(r + 1, nslots - 1) * 64);
     const unsigned w = c0.x;
     if ((w & 0xFFFFu) != ELL_EMPTY) {
       const v2f a01 = (v2f){__uint_as_float(c0.y), __uint_as_float(c0.z)} * sc;

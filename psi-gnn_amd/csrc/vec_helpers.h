@@ -66,11 +66,33 @@ __device__ __forceinline__ void ldv(const float* __restrict__ p, int64_t e0, int
     }
   }
 }
-// Loads of the U / V sweeps (fp32 pairs here, bf16 pairs below).  Non-temporal loads were measured and removed (round 1, DESIGN.md
-// section 4): k_dots / k_axpy at N = 1M, k = 0..49 took 557 / 550 us per launch with them against 365 / 382 us with default-policy loads.
+// Load of a stored pair column (U_j, V_j) in the Broyden sweeps: read once per sweep, gigabytes per iteration on long vectors.
+// ldv_stream<16> -- the sweeps of the long form (one block row: M >= 768 * 4 096 floats) -- requests the whole rows with the
+// non-temporal policy (global_load_dwordx4 ... nt), the ragged tail plain.  Measured on the current sweeps (1M nodes,
+// profiles/stream_policy_ab.txt): k_sweep_v 96.5 -> 83.3 us at K = 20, 198 -> 173 us at K = 50; k_sweep_u1 152 -> 130 us.  (Round 1
+// had measured such loads as slower, 557 / 550 against 365 / 382 us in k_dots / k_axpy -- on the lane mapping of that time, 16
+// contiguous floats per lane; it does not hold for coalesced 16-byte rows.)
+// ldv_stream<4> IS ldv<4>, despite the name, and so are the bf16 overloads below: a non-temporal line stays out of the 256 MiB
+// Infinity Cache, and with the policy at every width the sweeps of a 100k-node solve (M = 1M floats, history cache-resident
+// for most of its iterations) ran 7 - 18 % slower.  The width is a proxy the shape already computes, not the cache condition:
+// sweeps at 4 floats per lane also serve vectors of up to 3.1M floats whose history (2 k M floats) outgrows the cache within a few
+// pairs -- those were not measured with the policy and stay plain.  krylov.hip's basis vectors use ldv (policy measured there:
+// 9 % faster at 1M nodes, 13 % slower at 100k, both at 16 floats per lane).
+typedef float f32x4s __attribute__((ext_vector_type(4)));
 template <int VEC>
 __device__ __forceinline__ void ldv_stream(const float* __restrict__ p, int64_t e0, int64_t M, float* r) {
-  ldv<VEC>(p, e0, M, r);
+  if (VEC != 16) return ldv<VEC>(p, e0, M, r);
+#pragma unroll
+  for (int i = 0; i < VEC / 4; ++i) {
+    const int64_t o = e0 + i * 256;
+    if (o + 4 <= M) {
+      const f32x4s t = __builtin_nontemporal_load(reinterpret_cast<const f32x4s*>(p + o));
+      r[4 * i] = t.x; r[4 * i + 1] = t.y; r[4 * i + 2] = t.z; r[4 * i + 3] = t.w;
+    } else {  // tail
+#pragma unroll
+      for (int c = 0; c < 4; ++c) r[4 * i + c] = (o + c < M) ? p[o + c] : 0.f;
+    }
+  }
 }
 
 template <int VEC>
@@ -80,6 +102,24 @@ __device__ __forceinline__ void stv(float* __restrict__ p, int64_t e0, int64_t M
     const int64_t o = e0 + i * 256;
     if (o + 4 <= M) {
       *reinterpret_cast<float4*>(p + o) = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (o + c < M) p[o + c] = r[4 * i + c];
+    }
+  }
+}
+// Store of the new pair column (U[k], V[k]) of the three-sweep form, the same policy under the same condition (stv_stream<4> is
+// stv<4>): written once, read next by the following iteration's sweeps with everything else in between (global_store_dwordx4 ... nt)
+template <int VEC>
+__device__ __forceinline__ void stv_stream(float* __restrict__ p, int64_t e0, int64_t M, const float* r) {
+  if (VEC != 16) return stv<VEC>(p, e0, M, r);
+#pragma unroll
+  for (int i = 0; i < VEC / 4; ++i) {
+    const int64_t o = e0 + i * 256;
+    if (o + 4 <= M) {
+      const f32x4s t = {r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]};
+      __builtin_nontemporal_store(t, reinterpret_cast<f32x4s*>(p + o));
     } else {
 #pragma unroll
       for (int c = 0; c < 4; ++c)
@@ -127,6 +167,8 @@ __device__ __forceinline__ void stv(__bf16* __restrict__ p, int64_t e0, int64_t 
     }
   }
 }
+template <int VEC>   // (bf16 pairs: default policy)
+__device__ __forceinline__ void stv_stream(__bf16* __restrict__ p, int64_t e0, int64_t M, const float* r) { stv<VEC>(p, e0, M, r); }
 
 template <int STRIDE = 1>
 __device__ inline double block_sum_partials(const float* __restrict__ p, int n, double* sh) {
