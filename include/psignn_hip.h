@@ -570,6 +570,9 @@ int psignn_picard_solve_batch(int n, psignn_fpiter_t** handles, const psignn_pla
 typedef struct psignn_gmres psignn_gmres_t;
 int psignn_gmres_create(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis);
 void psignn_gmres_destroy(psignn_gmres_t* s);
+/* Device bytes the handle allocated itself (the caller's basis not counted): Hessenberg / Givens state and the dot partials, one row
+ * per block of the vector kernels -- so two handles of one n_elems and m_max differ here exactly when their vector widths differ. */
+size_t psignn_gmres_bytes(const psignn_gmres_t* s);
 /* g = fx - x -> d_g (may be NULL), -g -> d_neg_g (may be NULL); h_norms[0] = |g|, h_norms[1] = |fx|.  Synchronous. */
 int psignn_residual_norms(psignn_gmres_t* s, const float* d_x, const float* d_fx, float* d_g, float* d_neg_g, double* h_norms,
                           void* stream);

@@ -187,6 +187,7 @@ SIGNATURES = {
                                          C.POINTER(C.POINTER(C.c_double)), _P]),
     "psignn_gmres_create": (_INT, [C.POINTER(_P), _I64, _I64, _INT, _P]),
     "psignn_gmres_destroy": (None, [_P]),
+    "psignn_gmres_bytes": (C.c_size_t, [_P]),
     "psignn_residual_norms": (_INT, [_P, _P, _P, _P, _P, C.POINTER(C.c_double), _P]),
     "psignn_gmres_begin": (_INT, [_P, _P, _P]),
     "psignn_gmres_step": (_INT, [_P, _INT, C.c_double, C.c_double, C.POINTER(_INT), _P]),

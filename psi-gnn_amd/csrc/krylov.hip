@@ -474,6 +474,9 @@ extern "C" int psignn_gmres_create_for_batch(psignn_gmres_t** out, int64_t n_ele
   return gmres_create(out, n_elems, ld, m_max, d_basis, shard_elems);
 }
 
+// Device bytes the handle allocated itself (not the caller's basis): the dot partials follow the handle's blocks, hence its vector width
+extern "C" size_t psignn_gmres_bytes(const psignn_gmres_t* s) { return s ? s->bytes : 0; }
+
 // g = fx - x (d_g, may be NULL), b = -g (d_neg_g, may be NULL), h_norms[0] = |g|, h_norms[1] = |fx| (synchronous read)
 extern "C" int psignn_residual_norms(psignn_gmres_t* s, const float* d_x, const float* d_fx, float* d_g, float* d_neg_g,
                                      double* h_norms, void* stream) {

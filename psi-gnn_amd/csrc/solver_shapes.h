@@ -36,7 +36,9 @@ struct Knob {
   int64_t v = 0;
 };
 struct Knobs {
-  Knob vec16_min;   // PSIGNN_VEC16_MIN: elements from which the sweeps take 16 floats per lane
+  Knob vec16_min;   // PSIGNN_VEC16_MIN: elements from which the sweeps take 16 floats per lane -- of the Broyden handle only (broyden_shape);
+                    // gmres_create (krylov.hip) and the fixed-point iteration handle (fpiter.hip) call vec_shape with the compiled-in
+                    // VEC16_MIN, and a test selects their width with shard_elems (*_create_for_batch)
   Knob jgroups;     // PSIGNN_JGROUPS: pair groups of the split sweeps, 1 .. 8
   Knob vec_ax4;     // PSIGNN_VEC_AX4: 1 forces the 4-float unsplit axpy pass, 0 forbids it
   Knob uvu;         // PSIGNN_UVU: 0 forbids the three-sweep form

@@ -1623,8 +1623,11 @@ class DeviceGmres:
 
     @property
     def nbytes(self):
-        """Solver state in bytes: the (m + 1) basis vectors and the adjoint solve's workspace, if one has been made."""
-        return self.V.numel() * 4 + (self._work.numel() * 4 if self._work is not None else 0)
+        """Solver state in bytes: the (m + 1) basis vectors, what the library allocated for the handle (``psignn_gmres_bytes``: the
+        dot partials, one row per block, so this differs between the two vector widths) and the adjoint solve's workspace, if one
+        has been made."""
+        return (self.V.numel() * 4 + int(nat.lib().psignn_gmres_bytes(self.handle))
+                + (self._work.numel() * 4 if self._work is not None else 0))
 
     def solve_adjoint(self, fmap, h_star, grad, eps, max_products, lin=None, poll_every=8):
         """y = J_f(h*)^T y + grad by restarted GMRES (restart length = this object's ``m_max``), y_0 = 0, entirely on the device

@@ -13,8 +13,10 @@ from oracle import psignn_oracle as orc
 FIXTURES = ("hex13_dirichlet_s0", "hex26_dirichlet_s0", "hex13_mixed_s1")
 
 
-def gmres_adjoint(vjp, grad, eps, max_products, m=50):
-    """Solve y = vjp(y) + grad from y = 0.  Returns the solver dict of ``engine.DeviceGmres.solve_adjoint``."""
+def gmres_adjoint(vjp, grad, eps, max_products, m=50, device=None):
+    """Solve y = vjp(y) + grad from y = 0.  Returns the solver dict of ``engine.DeviceGmres.solve_adjoint``.  ``device``: where the
+    basis is allocated (default: the CPU, where the stored problems live); with ``grad`` and ``vjp`` on a GPU the vector work runs
+    there as plain torch, the small Hessenberg problem stays on the CPU in float64 either way."""
     shape = grad.shape
     b = grad.reshape(-1)
     op = lambda v: vjp(v.view(shape)).reshape(-1)
@@ -47,7 +49,7 @@ def gmres_adjoint(vjp, grad, eps, max_products, m=50):
             stop = "budget"
             break
         prev_rel = rel
-        V = torch.zeros((left + 1, b.numel()), dtype=b.dtype)
+        V = torch.zeros((left + 1, b.numel()), dtype=b.dtype, device=device)
         V[0] = r / nr
         R = torch.zeros((left + 1, left), dtype=torch.float64)
         g = torch.zeros(left + 1, dtype=torch.float64)
@@ -60,11 +62,11 @@ def gmres_adjoint(vjp, grad, eps, max_products, m=50):
             n0 = float(w.double() @ w.double())
             h1 = V[:j + 1] @ w
             w = w - h1 @ V[:j + 1]
-            h = h1.double()
+            h = h1.double().cpu()
             if not float(w.double() @ w.double()) >= 0.5 * n0:   # Daniel-Gragg-Kaufman-Stewart
                 h2 = V[:j + 1] @ w
                 w = w - h2 @ V[:j + 1]
-                h = h + h2.double()
+                h = h + h2.double().cpu()
                 n_reorth += 1
             hn = float(w.norm())
             col = torch.cat([h, torch.tensor([hn], dtype=torch.float64)])
@@ -90,7 +92,7 @@ def gmres_adjoint(vjp, grad, eps, max_products, m=50):
         for i in range(k - 1, -1, -1):
             s = g[i] - R[i, i + 1:k] @ z[i + 1:k]
             z[i] = s / R[i, i] if float(R[i, i]) != 0.0 else 0.0
-        y = y - z.to(b.dtype) @ V[:k]   # (J^T - I) z = r: the correction that cancels r is -z
+        y = y - z.to(b.dtype).to(V.device) @ V[:k]   # (J^T - I) z = r: the correction that cancels r is -z
     return {"result": best.view(shape), "nstep": products, "lowest": lowest, "rel_trace": rel_trace, "abs_trace": abs_trace,
             "n_cycles": cycles, "stop": stop, "n_reorth": n_reorth}
 

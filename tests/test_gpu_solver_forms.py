@@ -31,11 +31,11 @@ import torch
 
 from conftest import GOLDEN, load_weights, pkg, rel_l2
 from oracle import psignn_oracle as orc
-from recurrences import _check_iteration
+# K = 48 iterations per solve: the window regime starts at k = 25 with the default limits
+from recurrences import K, _check_run, _Recorder, _run_recorded   # noqa: F401  (test_gpu_broyden_bf16.py takes _Recorder from here)
 
 pytestmark = pytest.mark.gpu
 
-K = 48          # iterations per solve: the window regime starts at k = 25 with the default limits
 ENVS = {
     "default": {},                                                  # fold in registers on long vectors / big shards, in LDS below; all pairs kept to k = 24, then a window of 16
     "reg": {"PSIGNN_U2D_FORM": "reg"},                              # k_sweep_u2r<KB>
@@ -54,59 +54,6 @@ def _setenv(monkeypatch, env):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-
-
-class _Recorder:
-    """Wraps f for ``DeviceBroyden.solve_callable``: keeps every evaluation point and, from the second call on, the solver's
-    update vector at the time of the call (= dx of that iteration: x_new = x + update has just been formed)."""
-
-    def __init__(self, f, back=lambda t: t):
-        self.f, self.back, self.solver = f, back, None
-        self.X, self.DX = [], []
-
-    def __call__(self, x):
-        if self.X:
-            self.DX.append(self.solver.pair(0, self.back(x), "update"))
-        self.X.append(self.back(x).clone())
-        return self.f(x)
-
-
-def _run_recorded(eng, f, x0, n_elems=None, plan=None, shard_elems=0, back=lambda t: t):
-    rec = _Recorder(f, back)
-    if plan is not None:
-        sv = eng.DeviceBroyden(plan=plan, threshold=K, keep_trace=True, shard_elems=shard_elems)
-    else:
-        sv = eng.DeviceBroyden(threshold=K, keep_trace=True, n_elems=n_elems, seq_len=x0.shape[1], device=x0.device)
-    rec.solver = sv
-    out = sv.solve_callable(rec, x0, 0.0)
-    assert out["n_iter"] == K and out["stop_reason"] == 0, (out["n_iter"], out["stop_reason"])
-    rec.DX.append(sv.pair(0, back(x0), "update"))        # the update formed by the last iteration
-    return rec, sv, out
-
-
-def _check_run(rec, sv, its, label):
-    """rec.X[i] = iterate i (i = 0 .. K), rec.DX[i] = update that led from iterate i to i + 1 (and DX[K] the one after)."""
-    X, DX = rec.X, rec.DX
-    assert len(X) == K + 1 and len(DX) == K + 1
-    for i in (1, K // 2, K):                                      # the recorded points are the solver's iterates
-        assert torch.equal(sv.iterate(i, X[0]), X[i])
-    kmax = max(its)
-    Ucpu = torch.stack([sv.pair(j, X[0], "U").reshape(-1).cpu() for j in range(kmax + 1)])
-    Vcpu = torch.stack([sv.pair(j, X[0], "V").reshape(-1).cpu() for j in range(kmax + 1)])
-    U64, V64 = Ucpu.double(), Vcpu.double()
-    G = {}
-
-    def gof(i):                                                   # g_i = f(x_i) - x_i in float32, as k_resid forms it
-        if i not in G:
-            xi = X[i]
-            G[i] = (rec.f(rec.fwd(xi)) if hasattr(rec, "fwd") else rec.f(xi))
-            G[i] = (rec.back(G[i]) - xi).reshape(-1).cpu()
-        return G[i]
-
-    for it in its:       # iteration `it` (0-based): k = it stored pairs, x_it -> x_{it+1}, stores pair `it`, forms update it+1
-        g_new, g_old = gof(it + 1), gof(it)
-        _check_iteration(it, Ucpu[:it], Vcpu[:it], U64[:it], V64[:it], DX[it].reshape(-1).cpu(), g_new - g_old, g_new, Vcpu[it], Ucpu[it],
-                         DX[it + 1].reshape(-1).cpu(), f"{label} it={it}")
 
 
 def _linear(N, cmax, dev, seed=0):
