@@ -786,6 +786,41 @@ int psignn_f64_vjp(psignn_f64_t* f, const double* d_weights, int n_layers, const
                    const double* d_add /* NULL: none */, double* d_out, double* d_work, int64_t work_doubles, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The adjoint solve of the implicit backward in float64 on the device, y = J_f(h*)^T y + grad from y = 0: the solve the reference's
+ * --precision switch also puts in double precision, and the truth the fp32 adjoint solves are measured against, at any size.
+ * The map is psignn_f64_vjp with d_add = grad.  Default-width library only.  All arrays float64 in the caller's numbering;
+ * d_work: the caller's psignn_f64_deriv_workspace_doubles(f, n_layers, 1) doubles (smaller: PSIGNN_ENOMEM naming the bytes).
+ * ------------------------------------------------------------------------------------------ */
+/* Broyden on the adjoint system: the recurrences, stop tests, traces and h_info of psignn_broyden64_solve, on the map above.  One
+ * product per step; launches queued past the last step return at once (the product's too), so nothing depends on poll_every.
+ * replaces: the backward hook in double precision, dirichlet/psignn/model.py:210-223:
+ *           broyden(lambda y: autograd.grad(new_H, H, y) + grad, zeros_like(grad), threshold = bw_thres, eps = bw_tol). */
+int psignn_broyden64_solve_adjoint(psignn_broyden64_t* s, const double* d_weights, int n_layers, const double* d_h_star,
+                                   const double* d_h_initial, const double* d_prb, const double* d_normals, const double* d_grad,
+                                   double eps, int poll_every, double* d_work, int64_t work_doubles, double* d_result,
+                                   psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
+/* Restarted GMRES(m) on the adjoint system (csrc/krylov_f64.hip): the cycle logic, stop reasons, counts and traces of
+ * psignn_gmres_solve_adjoint above, with vectors, basis, coefficients and partials in float64 and every scalar on the device
+ * (Givens part: csrc/gmres_dense.h).  create allocates the basis, (m + 1) * N * d * 8 bytes, and fails with PSIGNN_ENOMEM and a
+ * message naming that size when it cannot.  The solver borrows the map handle (and through it the plan).
+ * replaces: the linear system of the backward hook, dirichlet/psignn/model.py:210-223, which the reference solves with Broyden. */
+typedef struct psignn_gmres64 psignn_gmres64_t;
+int psignn_gmres64_create(psignn_gmres64_t** out, psignn_f64_t* f, int m /* restart length, 1 .. 4096 */);
+void psignn_gmres64_destroy(psignn_gmres64_t* s);   /* (model.py:210-223: nothing is kept there between solves) */
+size_t psignn_gmres64_bytes(const psignn_gmres64_t* s);   /* device bytes of the handle (model.py:210-223 has no counterpart) */
+/* One solve.  eps bounds |f(y) - y| / (|f(y)| + 1e-9), f(y) = J^T y + grad, measured at the head of every cycle; the solve ends
+ * there on rel < eps (stop_reason 1), on a cycle that did not halve rel (2) or when max_products are spent (0; one product is kept
+ * back for the last residual).  d_result: the iterate with the lowest rel.  The host reads the solve state once per cycle and the
+ * cycle flag every poll_every Arnoldi steps (<= 0: 8); kernels queued past the end of a cycle return at once, so neither bits nor
+ * counts depend on poll_every; no floating-point atomics, fixed-shape reductions: the same call gives the same bits.
+ * h_rel_trace / h_abs_trace: one entry per cycle, host arrays of max_products / 2 + 3 doubles (may be NULL).  Synchronous at the end.
+ * replaces: the solve of dirichlet/psignn/model.py:210-223 in double precision, by another method. */
+int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* d_weights, int n_layers, const double* d_h_star,
+                                 const double* d_h_initial, const double* d_prb, const double* d_normals, const double* d_grad,
+                                 double eps, int max_products, int poll_every, double* d_work, int64_t work_doubles, double* d_result,
+                                 psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line;
  * replaces: the reference's only instrumentation, time.time() around the model call,
  * tests/special_geo/spec_geo_2.py:313-317).  Off by default.

@@ -20,6 +20,8 @@
 //          c_to, over m's CSC entries the x_j side of Phi_from with c_from (Neumann neighbours: Phi_neumann with c_neu); every ReLU
 //          mask recomputed from h.  Optionally + a vector to add, which makes the map of the adjoint system y -> J^T y + grad one call.
 // ReLU': 1 where the pre-activation is > 0 (torch's threshold_backward).
+// Every kernel takes the done flag of a solver (NULL: none) and returns at once when it is set: psignn_f64_vjp_gated is the product of
+// the float64 adjoint solves (solver_f64.hip, krylov_f64.hip), whose launches queued past the end of a solve or cycle change nothing.
 #include "common.h"
 #include "internal.h"
 #include <math.h>
@@ -199,8 +201,10 @@ __global__ __launch_bounds__(256) void k_f64_jvp_layer(int64_t N, const double* 
                                                        const uint8_t* __restrict__ flags, const double* __restrict__ h,
                                                        const double* __restrict__ v, const double* __restrict__ h0,
                                                        const double* __restrict__ prb, const double* __restrict__ nrm,
-                                                       double* __restrict__ out_h, double* __restrict__ out_v) {
+                                                       double* __restrict__ out_h, double* __restrict__ out_v,
+                                                       const int32_t* __restrict__ done) {
   using L = W64<P>;
+  if (done && *done) return;
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const uint8_t fl = flags[n];
@@ -337,9 +341,11 @@ __global__ __launch_bounds__(256) void k_f64_vjp_node(int64_t N, const double* _
                                                       const int32_t* __restrict__ csc_nbr, const double* __restrict__ csc_attr,
                                                       const uint8_t* __restrict__ flags, const double* __restrict__ h,
                                                       const double* __restrict__ prb, const double* __restrict__ nrm,
-                                                      const double* __restrict__ w, double* __restrict__ loc, double* __restrict__ C) {
+                                                      const double* __restrict__ w, double* __restrict__ loc, double* __restrict__ C,
+                                                      const int32_t* __restrict__ done) {
   using L = W64<P>;
   constexpr int CW = MIXED ? 3 * D : 2 * D;
+  if (done && *done) return;
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const uint8_t fl = flags[n];
@@ -501,9 +507,11 @@ __global__ __launch_bounds__(256) void k_f64_vjp_edge(int64_t N, const double* _
                                                       const int32_t* __restrict__ csc_nbr, const double* __restrict__ csc_attr,
                                                       const uint8_t* __restrict__ flags, const double* __restrict__ h,
                                                       const double* __restrict__ loc, const double* __restrict__ C,
-                                                      const double* __restrict__ add, double* __restrict__ out) {
+                                                      const double* __restrict__ add, double* __restrict__ out,
+                                                      const int32_t* __restrict__ done) {
   using L = W64<2>;
   constexpr int CW = MIXED ? 3 * D : 2 * D;
+  if (done && *done) return;
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= N) return;
   double x[D], g[D];
@@ -546,7 +554,8 @@ __global__ __launch_bounds__(256) void k_f64_vjp_edge(int64_t N, const double* _
 
 // one layer's value (out_h, may be NULL) and, with v, its tangent (out_v)
 static void jvp_launch(const psignn_f64* f, const double* W, int nl, int l, int apply_ln, const double* h, const double* v,
-                       const double* h0, const double* prb, const double* nrm, double* out_h, double* out_v, hipStream_t st) {
+                       const double* h0, const double* prb, const double* nrm, double* out_h, double* out_v, const int32_t* done,
+                       hipStream_t st) {
   const psignn_plan* p = f->p;
   const unsigned g = (unsigned)cdiv(p->N, 256);
   // algorithmic bytes: both edge lists once (neighbour id, 3 attributes, the neighbour's row and tangent row), per node its rows
@@ -555,23 +564,24 @@ static void jvp_launch(const psignn_f64* f, const double* W, int nl, int l, int 
     using L = W64<3>;
     LAUNCH("k_f64_jvp_layer", st,
            (k_f64_jvp_layer<3, true, true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, v, h0, prb,
-                                                             nrm, out_h, out_v)));
+                                                             nrm, out_h, out_v, done)));
   } else if (v) {
     using L = W64<2>;
     LAUNCH("k_f64_jvp_layer", st,
            (k_f64_jvp_layer<2, false, true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, v, h0,
-                                                              prb, nrm, out_h, out_v)));
+                                                              prb, nrm, out_h, out_v, done)));
   } else {
     using L = W64<2>;
     LAUNCH("k_f64_state_layer", st,
            (k_f64_jvp_layer<2, false, false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, nullptr,
-                                                               h0, prb, nrm, out_h, nullptr)));
+                                                               h0, prb, nrm, out_h, nullptr, done)));
   }
 }
 
 // both passes of one layer: out = J_l(h)^T w (+ add)
 static void vjp_launch(const psignn_f64* f, const double* W, int nl, int l, int apply_ln, const double* h, const double* prb,
-                       const double* nrm, const double* w, double* loc, double* C, const double* add, double* out, hipStream_t st) {
+                       const double* nrm, const double* w, double* loc, double* C, const double* add, double* out, const int32_t* done,
+                       hipStream_t st) {
   const psignn_plan* p = f->p;
   const unsigned g = (unsigned)cdiv(p->N, 256);
   const int cw = p->mixed ? 3 * D : 2 * D;
@@ -580,23 +590,23 @@ static void vjp_launch(const psignn_f64* f, const double* W, int nl, int l, int 
     using L = W64<3>;
     LAUNCH("k_f64_vjp_node", st,
            (k_f64_vjp_node<3, true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb, nrm, w, loc,
-                                                      C)));
+                                                      C, done)));
   } else {
     using L = W64<2>;
     LAUNCH("k_f64_vjp_node", st,
            (k_f64_vjp_node<2, false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb, nrm, w, loc,
-                                                       C)));
+                                                       C, done)));
   }
   // both edge lists once (neighbour id and flag, 3 attributes, the neighbour's row and its cotangent), per node h, loc, out (, add)
   PROF_BYTES(2 * p->Ep * (4 + 1 + 24 + 16 * D) + p->N * (8 * 3 * D + (add ? 8 * D : 0) + 8));
   if (p->mixed) {
     using L = W64<3>;
     LAUNCH("k_f64_vjp_edge", st,
-           (k_f64_vjp_edge<true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, loc, C, add, out)));
+           (k_f64_vjp_edge<true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, loc, C, add, out, done)));
   } else {
     using L = W64<2>;
     LAUNCH("k_f64_vjp_edge", st,
-           (k_f64_vjp_edge<false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, loc, C, add, out)));
+           (k_f64_vjp_edge<false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, loc, C, add, out, done)));
   }
 }
 
@@ -631,7 +641,7 @@ extern "C" int psignn_f64_jvp(psignn_f64_t* f, const double* W, int nl, const do
   if (f->p->N == 0) return PSIGNN_OK;
   hipStream_t st = (hipStream_t)stream;
   if (!f64_chain(f, nl)) {
-    jvp_launch(f, W, nl, nl - 1, 1, h, v, h0, prb, nrm, nullptr, out, st);
+    jvp_launch(f, W, nl, nl - 1, 1, h, v, h0, prb, nrm, nullptr, out, nullptr, st);
   } else {
     const int64_t row = f->p->N * D;
     const double *ch = h, *cv = v;
@@ -639,9 +649,44 @@ extern "C" int psignn_f64_jvp(psignn_f64_t* f, const double* W, int nl, const do
       const bool last = l == nl - 1;
       double* dh = last ? nullptr : work + (l & 1) * row;
       double* dv = last ? out : work + (2 + (l & 1)) * row;
-      jvp_launch(f, W, nl, l, last, ch, cv, h0, prb, nrm, dh, dv, st);
+      jvp_launch(f, W, nl, l, last, ch, cv, h0, prb, nrm, dh, dv, nullptr, st);
       ch = dh;
       cv = dv;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
+// The product with the flag of a solver (internal.h): every launch returns at once when *done is set (NULL: no flag).
+int psignn_f64_vjp_gated(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                         const double* nrm, const double* w, const double* add, double* out, double* work, int64_t work_doubles,
+                         const int32_t* done, hipStream_t st) {
+  ARG_CHECK(f && W && h && h0 && prb && w && out && work, "NULL argument");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
+  ARG_CHECK(out != h && out != w && out != add, "out must not alias h, w or add");
+  const int rc = work_check("psignn_f64_vjp", psignn_f64_deriv_workspace_doubles(f, nl, 1), work, work_doubles);
+  if (rc) return rc;
+  if (f->p->N == 0) return PSIGNN_OK;
+  const int64_t row = f->p->N * D;
+  double *loc = work, *C = work + row;
+  if (!f64_chain(f, nl)) {
+    vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, w, loc, C, add, out, done, st);
+  } else {
+    // the states h_1 .. h_{L-1} at h, then the chain backwards; cotangents of the inner layers in a ping-pong
+    double *states = work + 3 * row, *pp = work + (3 + nl - 1) * row;
+    const double* cur = h;
+    for (int l = 0; l + 1 < nl; ++l) {
+      jvp_launch(f, W, nl, l, 0, cur, nullptr, h0, prb, nullptr, states + l * row, nullptr, done, st);
+      cur = states + l * row;
+    }
+    const double* cw = w;
+    for (int l = nl - 1; l >= 0; --l) {
+      double* dst = l == 0 ? out : pp + (l & 1) * row;
+      vjp_launch(f, W, nl, l, l == nl - 1, l == 0 ? h : states + (l - 1) * row, prb, nrm, cw, loc, C, l == 0 ? add : nullptr, dst,
+                 done, st);
+      cw = dst;
     }
   }
   HIP_TRY(hipGetLastError());
@@ -651,33 +696,5 @@ extern "C" int psignn_f64_jvp(psignn_f64_t* f, const double* W, int nl, const do
 extern "C" int psignn_f64_vjp(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
                               const double* nrm, const double* w, const double* add, double* out, double* work,
                               int64_t work_doubles, void* stream) {
-  ARG_CHECK(f && W && h && h0 && prb && w && out && work, "NULL argument");
-  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
-  ARG_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
-  ARG_CHECK(out != h && out != w && out != add, "out must not alias h, w or add");
-  const int rc = work_check(__func__, psignn_f64_deriv_workspace_doubles(f, nl, 1), work, work_doubles);
-  if (rc) return rc;
-  if (f->p->N == 0) return PSIGNN_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t row = f->p->N * D;
-  double *loc = work, *C = work + row;
-  if (!f64_chain(f, nl)) {
-    vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, w, loc, C, add, out, st);
-  } else {
-    // the states h_1 .. h_{L-1} at h, then the chain backwards; cotangents of the inner layers in a ping-pong
-    double *states = work + 3 * row, *pp = work + (3 + nl - 1) * row;
-    const double* cur = h;
-    for (int l = 0; l + 1 < nl; ++l) {
-      jvp_launch(f, W, nl, l, 0, cur, nullptr, h0, prb, nullptr, states + l * row, nullptr, st);
-      cur = states + l * row;
-    }
-    const double* cw = w;
-    for (int l = nl - 1; l >= 0; --l) {
-      double* dst = l == 0 ? out : pp + (l & 1) * row;
-      vjp_launch(f, W, nl, l, l == nl - 1, l == 0 ? h : states + (l - 1) * row, prb, nrm, cw, loc, C, l == 0 ? add : nullptr, dst, st);
-      cw = dst;
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  return PSIGNN_OK;
+  return psignn_f64_vjp_gated(f, W, nl, h, h0, prb, nrm, w, add, out, work, work_doubles, nullptr, (hipStream_t)stream);
 }

@@ -1,0 +1,47 @@
+// The small dense part of GMRES in float64, host and device: the Hessenberg least-squares problem by Givens rotations.
+//
+// replaces: nothing executable in the reference (its backward hook, dirichlet/psignn/model.py:210-223, solves the adjoint system
+//           with Broyden); the statements are those of gmres_adjoint in tests/adjoint_gmres_ref.py, one to one.
+//
+// R is column-major with leading dimension ld >= k + 1: column j holds the j + 1 entries of the rotated column (upper triangle).
+// Includes nothing from the project: tests/host/gmres_dense_check.cpp compiles it with a host compiler and checks it against a
+// least-squares solve of random Hessenberg matrices.
+#pragma once
+#include <math.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define GMD_HD __host__ __device__
+#else
+#define GMD_HD
+#endif
+
+// Column j of the Hessenberg matrix, col[0 .. j + 1] (the shift already on col[j], the new vector's norm in col[j + 1]): apply the
+// j earlier rotations, form rotation j (cs[j], sn[j]; (1, 0) for a zero pair), leave the rotated column in col (col[j] = r,
+// col[j + 1] = 0) and update g[j], g[j + 1].  Returns |g[j + 1]|, the residual of the least-squares problem after j + 1 columns.
+GMD_HD inline double gmd_column(int j, double* col, double* cs, double* sn, double* g) {
+  for (int i = 0; i < j; ++i) {
+    const double t = cs[i] * col[i] + sn[i] * col[i + 1];
+    col[i + 1] = -sn[i] * col[i] + cs[i] * col[i + 1];
+    col[i] = t;
+  }
+  const double a = col[j], b = col[j + 1];
+  const double r = hypot(a, b);
+  const double c = r > 0.0 ? a / r : 1.0, s = r > 0.0 ? b / r : 0.0;
+  cs[j] = c;
+  sn[j] = s;
+  col[j] = r;
+  col[j + 1] = 0.0;
+  g[j + 1] = -s * g[j];
+  g[j] = c * g[j];
+  return fabs(g[j + 1]);
+}
+
+// z = R^{-1} g for the first k columns; a zero pivot gives z_i = 0.
+GMD_HD inline void gmd_backsolve(int k, int ld, const double* R, const double* g, double* z) {
+  for (int i = k - 1; i >= 0; --i) {
+    double s = g[i];
+    for (int q = i + 1; q < k; ++q) s -= R[(long long)q * ld + i] * z[q];
+    const double d = R[(long long)i * ld + i];
+    z[i] = d != 0.0 ? s / d : 0.0;
+  }
+}

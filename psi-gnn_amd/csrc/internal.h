@@ -90,6 +90,12 @@ const psignn_plan* psignn_f64_plan(const psignn_f64_t* f);
 int psignn_f64_eval(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb, const double* nrm,
                     double* out, const int32_t* done, hipStream_t st);
 
+// ---- fgnn_f64_deriv.hip
+// psignn_f64_vjp with a solver's flag: every launch of the product returns at once when *done is set (NULL: no flag)
+int psignn_f64_vjp_gated(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                         const double* nrm, const double* w, const double* add, double* out, double* work, int64_t work_doubles,
+                         const int32_t* done, hipStream_t st);
+
 // ---- plan.hip
 int psignn_exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* bsum, hipStream_t st);
 

@@ -1,0 +1,527 @@
+// Restarted GMRES in float64 for the adjoint system of the implicit backward, y = J_f(h*)^T y + grad, every scalar on the device
+// (gfx950): the float64 adjoint at any size -- what AdjointProblem.truth() of tests/adjoint_gmres_ref.py is on the CPU oracle.
+//
+// replaces: the backward hook's solve run in double precision (dirichlet/psignn/model.py:210-223; the reference solves this LINEAR
+//           system with Broyden, psignn_broyden64_solve_adjoint is that).  The cycle logic is gmres_adjoint of
+//           tests/adjoint_gmres_ref.py statement by statement, which is also what adjoint_gmres_loop of krylov.hip does in fp32.
+//
+// Per restart cycle, all on the stream (the map is psignn_f64_vjp with add = grad, fgnn_f64_deriv.hip):
+//   k_ag64_begin   f(y) = J^T y + grad (first cycle: y = 0, f = grad, no product), r = f(y) - y -> basis row 0, block partials of
+//                  |r|^2 and |f(y)|^2
+//   k_ag64_check   one block: rel = |r| / (|f(y)| + 1e-9), traces, lowest; the solve ends on rel < eps (or r = 0), on a cycle that
+//                  did not halve rel, or on a spent budget (one product is kept back for the next cycle's residual); otherwise the
+//                  cycle is armed: g_0 = |r|, steps_left = min(m, budget left)
+//   k_ag64_keep    y_best <- y when this cycle's rel is the lowest so far
+//   k_gm64_scale   v_0 = r / |r|
+//   Arnoldi step j on the raw product w = J^T v_j in basis row j + 1 (the shift sits on the Hessenberg's diagonal):
+//     k_gm64_dots    pass 1: h_i = <v_i, w>, i <= j, and |w|^2 -- a chunk of 1024 elements of w in LDS, a wave per basis vector,
+//                    16 bytes per lane, the basis read once
+//     k_gm64_reduce  one block per coefficient: the chunk partials in a fixed order
+//     k_gm64_axpy    w -= sum_i h_i v_i, 16 bytes per lane, the basis read once; block partials of |w'|^2
+//     k_gm64_decide  one block: the second pass runs when |w'|^2 < 1/2 |w|^2 (Daniel-Gragg-Kaufman-Stewart), decided here
+//     k_gm64_dots / k_gm64_reduce / k_gm64_axpy once more when it does (they return at once when it does not)
+//     k_gm64_finish  one block: column j = h1 + h2 - e_j, |w|; gmres_dense.h: earlier rotations, the new one, g; the cycle ends on
+//                    |g_{j+1}| <= eps / 2 |f(y)|, on steps_left or on |w| = 0
+//     k_gm64_scale   v_{j+1} = w / |w|
+//   k_gm64_backsolve, k_gm64_combine   z = R^{-1} g, y -= V z
+// Every kernel of the Arnoldi step, the product included, returns at once when the cycle's done flag is up, so what the host has
+// queued past the end of a cycle changes nothing.  The host reads the solve state after every check and the cycle flag every
+// poll_every Arnoldi steps: neither bits nor counts depend on poll_every.  Reductions: per-wave / per-block partials (shuffles in a
+// fixed order), then one block sums the partials in a fixed order.  No floating-point atomics: the same call gives the same bits.
+// Storage: vectors, basis (m + 1, M), coefficients and partials in float64.
+#include "common.h"
+#include "internal.h"
+#include "gmres_dense.h"
+#include <math.h>
+
+#if PSIGNN_D != 10
+#error "krylov_f64.hip is part of the default-width library only"
+#endif
+
+#define G64_TB 256
+#define G64_CHUNK 1024   // elements of a dots chunk: 8 x (64 lanes x 2 doubles)
+
+struct G64State {
+  // the cycle (re-armed by k_ag64_check)
+  int32_t k;            // Arnoldi steps completed
+  int32_t done;         // the cycle is over (or the solve): every gated kernel returns
+  int32_t reorth;       // this step's second Gram-Schmidt pass runs
+  int32_t n_reorth;     // steps of this solve whose second pass ran
+  // the solve
+  int32_t cycles;       // restart cycles begun = entries of the traces
+  int32_t products;     // transposed products spent
+  int32_t solved;       // the solve is over
+  int32_t stop;         // 0 budget, 1 tolerance, 2 stagnation
+  int32_t steps_left;   // Arnoldi steps this cycle may take
+  int32_t improved;     // this cycle's iterate has the lowest rel so far
+  double beta;          // |f(y)| of the cycle: the inner target is |g| <= eps / 2 * beta
+  double hn;            // |w| of the last step
+  double n0sq;          // |w|^2 before the first pass of the current step
+  double rnorm;         // |r| of the cycle
+  double prev_rel, lowest, lowest_abs;
+};
+
+struct psignn_gmres64 {
+  psignn_f64_t* f = nullptr;   // borrowed
+  int64_t N = 0, M = 0, nblk = 0, nchunk = 0;
+  int m = 0;
+  double* V = nullptr;      // (m + 1, M) basis
+  double* vec = nullptr;    // 3 vectors of M: y, f(y), y_best
+  double* part = nullptr;   // 2 planes of nblk block partials
+  double* partD = nullptr;  // (m + 2, nchunk) dot partials
+  double *coef = nullptr, *hcol = nullptr;   // (m + 2) each: this pass's coefficients; h1 + h2
+  double *R = nullptr, *cs = nullptr, *sn = nullptr, *g = nullptr, *z = nullptr;   // (m + 1, m) column-major; (m + 1) each
+  double *rel_trace = nullptr, *abs_trace = nullptr;   // (cap) device
+  int cap = 0;
+  G64State* st = nullptr;     // device
+  G64State* h_st = nullptr;   // pinned
+};
+
+// ------------------------------------------------------------------ reductions (fixed shape, fixed order)
+__device__ __forceinline__ double g64_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;   // lane 0 holds the sum
+}
+__device__ __forceinline__ double g64_block_sum(double v, double* sh /* 4 */) {
+  v = g64_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __syncthreads();
+  return s;
+}
+__device__ __forceinline__ double g64_final_sum(const double* __restrict__ part, int64_t n, double* sh) {
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += G64_TB) s += part[i];
+  return g64_block_sum(s, sh);
+}
+
+// ------------------------------------------------------------------ the head of a cycle
+__global__ void k_ag64_init(G64State* st) {
+  G64State s{};
+  *st = s;
+}
+
+// r = f(y) - y -> r0 (first: y <- 0, f(y) = grad); partials of |r|^2 and |f(y)|^2.  M is even: a lane's two elements are both
+// inside or both outside.
+__global__ void __launch_bounds__(G64_TB) k_ag64_begin(int64_t M, int64_t nblk, const G64State* __restrict__ st, double* __restrict__ y,
+                                                       const double* __restrict__ fy, const double* __restrict__ grad,
+                                                       double* __restrict__ r0, double* __restrict__ part, int first) {
+  if (st->solved) return;
+  __shared__ double sh[4];
+  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  double sr = 0.0, sf = 0.0;
+  if (e < M) {
+    double2 f, a, r;
+    if (first) {
+      f = *(const double2*)(grad + e);
+      a.x = 0.0;
+      a.y = 0.0;
+      *(double2*)(y + e) = a;
+    } else {
+      f = *(const double2*)(fy + e);
+      a = *(const double2*)(y + e);
+    }
+    r.x = f.x - a.x;
+    r.y = f.y - a.y;
+    *(double2*)(r0 + e) = r;
+    sr = fma(r.y, r.y, r.x * r.x);
+    sf = fma(f.y, f.y, f.x * f.x);
+  }
+  sr = g64_block_sum(sr, sh);
+  sf = g64_block_sum(sf, sh);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = sr;
+    part[nblk + blockIdx.x] = sf;
+  }
+}
+
+__global__ void __launch_bounds__(G64_TB) k_ag64_check(G64State* st, const double* __restrict__ part, int64_t nblk,
+                                                       double* __restrict__ g, double* __restrict__ rel_trace,
+                                                       double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
+  if (st->solved) return;
+  __shared__ double sh[4];
+  const double sr = g64_final_sum(part, nblk, sh);
+  const double sf = g64_final_sum(part + nblk, nblk, sh);
+  if (threadIdx.x != 0) return;
+  const double nr = sqrt(sr), nf = sqrt(sf);
+  const double rel = nr / (nf + 1e-9);
+  const int c = st->cycles;
+  const int products = st->products + (c > 0 ? st->k + 1 : 0);   // the last cycle's steps and this cycle's residual
+  st->products = products;
+  st->cycles = c + 1;
+  if (c < cap) {
+    rel_trace[c] = rel;
+    abs_trace[c] = nr;
+  }
+  const int better = c == 0 || rel < st->lowest;
+  st->improved = better;
+  if (better) {
+    st->lowest = rel;
+    st->lowest_abs = nr;
+  }
+  const int left = min(m, max_products - products - 1);
+  int done = 1, stop = 0;
+  if (rel < eps || nr == 0.0) stop = 1;                        // (a zero right-hand side: y = 0 is the answer)
+  else if (c > 0 && !(rel <= 0.5 * st->prev_rel)) stop = 2;   // (a NaN stops here too)
+  else if (left <= 0) stop = 0;
+  else done = 0;
+  st->prev_rel = rel;
+  st->solved = done;
+  st->stop = stop;
+  st->steps_left = done ? 0 : left;
+  st->rnorm = nr;
+  st->done = done;
+  if (!done) {
+    st->k = 0;
+    st->reorth = 1;
+    st->beta = nf;
+    st->hn = 0.0;
+    st->n0sq = 0.0;
+    g[0] = nr;
+  }
+}
+
+// not gated by the flags: the cycle that ends the solve may be the lowest one
+__global__ void __launch_bounds__(G64_TB) k_ag64_keep(int64_t M, const G64State* __restrict__ st, const double* __restrict__ y,
+                                                      double* __restrict__ ybest) {
+  if (!st->improved) return;
+  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  if (e < M) *(double2*)(ybest + e) = *(const double2*)(y + e);
+}
+
+// dst = src / *scale (|r| or |w|, a device double)
+__global__ void __launch_bounds__(G64_TB) k_gm64_scale(int64_t M, const G64State* __restrict__ st, const double* __restrict__ src,
+                                                       const double* __restrict__ scale, double* __restrict__ dst) {
+  if (st->done) return;
+  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  if (e >= M) return;
+  const double s = *scale;
+  double2 v = *(const double2*)(src + e);
+  v.x /= s;
+  v.y /= s;
+  *(double2*)(dst + e) = v;
+}
+
+// ------------------------------------------------------------------ one Arnoldi step
+// A lane past the end of the last chunk reads the chunk's first element (always inside) and drops the value.
+template <bool FULL>
+__device__ __forceinline__ double2 g64_ld2(const double* __restrict__ p, int64_t e, int64_t base, int64_t M) {
+  if (FULL) return *(const double2*)(p + e);
+  const bool in = e < M;
+  const double2 v = *(const double2*)(p + (in ? e : base));
+  double2 r;
+  r.x = in ? v.x : 0.0;
+  r.y = in ? v.y : 0.0;
+  return r;
+}
+// Block = chunk of G64_CHUNK elements of w in LDS; wave q takes rows q, q + 4, ... of the `rows` first basis rows (row j + 1 is w
+// itself: |w|^2 in the first pass).  A lane reads 8 double2 of the row (index (i * 64 + lane) * 2 within the chunk).
+// partD[row * nchunk + chunk].
+template <bool FULL>
+__device__ __forceinline__ void g64_dots_chunk(int64_t M, int64_t nchunk, int rows, const double* __restrict__ V,
+                                               const double* __restrict__ w, double* __restrict__ partD, double2* s_w) {
+  const int64_t base = (int64_t)blockIdx.x * G64_CHUNK;
+  for (int i = threadIdx.x; i < G64_CHUNK / 2; i += G64_TB) s_w[i] = g64_ld2<FULL>(w, base + 2 * i, base, M);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll 1
+  for (int r = wave; r < rows; r += G64_TB / 64) {
+    const double* Vr = V + (int64_t)r * M;
+    double2 v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = g64_ld2<FULL>(Vr, base + (int64_t)(i * 64 + lane) * 2, base, M);
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const double2 x = s_w[i * 64 + lane];
+      a = fma(v[i].x, x.x, a);
+      a = fma(v[i].y, x.y, a);
+    }
+    a = g64_wave_sum(a);
+    if (lane == 0) partD[(int64_t)r * nchunk + blockIdx.x] = a;
+  }
+}
+__global__ void __launch_bounds__(G64_TB) k_gm64_dots(int64_t M, int64_t nchunk, int j, int pass, const G64State* __restrict__ st,
+                                                      const double* __restrict__ V, double* __restrict__ partD) {
+  if (st->done || (pass && !st->reorth)) return;
+  __shared__ double2 s_w[G64_CHUNK / 2];
+  const double* w = V + (int64_t)(j + 1) * M;
+  const int rows = j + 1 + (pass == 0);
+  if (((int64_t)blockIdx.x + 1) * G64_CHUNK <= M) g64_dots_chunk<true>(M, nchunk, rows, V, w, partD, s_w);
+  else g64_dots_chunk<false>(M, nchunk, rows, V, w, partD, s_w);
+}
+
+// one block per coefficient: pass 1 h_i (and |w|^2 from row j + 1), pass 2 the correction, added to h_i
+__global__ void __launch_bounds__(G64_TB) k_gm64_reduce(int64_t nchunk, int j, int pass, G64State* __restrict__ st,
+                                                        const double* __restrict__ partD, double* __restrict__ coef,
+                                                        double* __restrict__ hcol) {
+  if (st->done || (pass && !st->reorth)) return;
+  __shared__ double sh[4];
+  const int r = blockIdx.x;
+  const double s = g64_final_sum(partD + (int64_t)r * nchunk, nchunk, sh);
+  if (threadIdx.x != 0) return;
+  if (r == j + 1) {
+    st->n0sq = s;
+  } else {
+    coef[r] = s;
+    hcol[r] = pass ? hcol[r] + s : s;
+  }
+}
+
+// w -= sum_{i <= j} coef_i v_i, two elements per lane, rows in ascending order; block partials of |w'|^2
+__global__ void __launch_bounds__(G64_TB) k_gm64_axpy(int64_t M, int j, int pass, const G64State* __restrict__ st,
+                                                      double* __restrict__ V, const double* __restrict__ coef,
+                                                      double* __restrict__ part) {
+  if (st->done || (pass && !st->reorth)) return;
+  __shared__ double sh[4];
+  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  double s = 0.0;
+  if (e < M) {
+    double2 acc = {0.0, 0.0};
+#pragma unroll 4
+    for (int i = 0; i <= j; ++i) {
+      const double c = coef[i];
+      const double2 v = *(const double2*)(V + (int64_t)i * M + e);
+      acc.x = fma(c, v.x, acc.x);
+      acc.y = fma(c, v.y, acc.y);
+    }
+    double* w = V + (int64_t)(j + 1) * M + e;
+    double2 x = *(const double2*)w;
+    x.x -= acc.x;
+    x.y -= acc.y;
+    *(double2*)w = x;
+    s = fma(x.y, x.y, x.x * x.x);
+  }
+  s = g64_block_sum(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(G64_TB) k_gm64_decide(G64State* st, const double* __restrict__ part, int64_t nblk) {
+  if (st->done) return;
+  __shared__ double sh[4];
+  const double s = g64_final_sum(part, nblk, sh);
+  if (threadIdx.x != 0) return;
+  const int r = !(s >= 0.5 * st->n0sq);
+  st->reorth = r;
+  st->n_reorth += r;
+}
+
+// One block: column j of the Hessenberg matrix and the least-squares update.  `part` holds |w|^2 of the last pass that ran.
+__global__ void __launch_bounds__(G64_TB) k_gm64_finish(G64State* st, const double* __restrict__ part, int64_t nblk, int j, int m,
+                                                        double eta, double* __restrict__ hcol, double* __restrict__ R,
+                                                        double* __restrict__ cs, double* __restrict__ sn, double* __restrict__ g) {
+  if (st->done) return;
+  __shared__ double sh[4];
+  const double s2 = g64_final_sum(part, nblk, sh);
+  if (threadIdx.x != 0) return;
+  const double hn = sqrt(s2);
+  st->hn = hn;
+  hcol[j] -= 1.0;   // Hessenberg of J^T - I from the Arnoldi relation of J^T
+  hcol[j + 1] = hn;
+  const double resid = gmd_column(j, hcol, cs, sn, g);
+  double* col = R + (int64_t)j * (m + 1);
+  for (int i = 0; i <= j; ++i) col[i] = hcol[i];
+  st->k = j + 1;
+  st->reorth = 1;
+  if (resid <= eta * st->beta || j + 1 >= st->steps_left || !(hn > 0.0)) st->done = 1;
+}
+
+// ------------------------------------------------------------------ the end of a cycle (not gated: the cycle's flag is up)
+__global__ void k_gm64_backsolve(const G64State* __restrict__ st, int m, const double* __restrict__ R, const double* __restrict__ g,
+                                 double* __restrict__ z) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  gmd_backsolve(st->k, m + 1, R, g, z);
+}
+// y -= sum_{i < k} z_i v_i
+__global__ void __launch_bounds__(G64_TB) k_gm64_combine(int64_t M, const G64State* __restrict__ st, const double* __restrict__ V,
+                                                         const double* __restrict__ z, double* __restrict__ y) {
+  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  if (e >= M) return;
+  const int k = st->k;
+  double2 acc = {0.0, 0.0};
+#pragma unroll 4
+  for (int i = 0; i < k; ++i) {
+    const double c = z[i];
+    const double2 v = *(const double2*)(V + (int64_t)i * M + e);
+    acc.x = fma(c, v.x, acc.x);
+    acc.y = fma(c, v.y, acc.y);
+  }
+  double2 x = *(const double2*)(y + e);
+  x.x -= acc.x;
+  x.y -= acc.y;
+  *(double2*)(y + e) = x;
+}
+
+// ------------------------------------------------------------------ host
+extern "C" void psignn_gmres64_destroy(psignn_gmres64_t* s) {
+  if (!s) return;
+  void* ptrs[] = {s->V, s->vec, s->part, s->partD, s->coef, s->hcol, s->R, s->cs, s->sn, s->g, s->z, s->rel_trace, s->abs_trace, s->st};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  if (s->h_st) (void)hipHostFree(s->h_st);
+  delete s;
+}
+
+extern "C" int psignn_gmres64_create(psignn_gmres64_t** out, psignn_f64_t* f, int m) {
+  ARG_CHECK(out != nullptr, "out is NULL");
+  *out = nullptr;
+  ARG_CHECK(f != nullptr, "the float64 map handle is NULL");
+  ARG_CHECK(m >= 1 && m <= 4096, "restart length out of range (1 .. 4096)");
+  const psignn_plan* p = psignn_f64_plan(f);
+  ARG_CHECK(p->N > 0, "the plan has no nodes");
+  psignn_gmres64* s = new psignn_gmres64();
+  s->f = f;
+  s->N = p->N;
+  s->M = p->N * D;
+  s->m = m;
+  s->nblk = cdiv(s->M, 2 * G64_TB);
+  s->nchunk = cdiv(s->M, G64_CHUNK);
+  const size_t basis_bytes = (size_t)(m + 1) * (size_t)s->M * sizeof(double);
+  if (hipMalloc((void**)&s->V, basis_bytes) != hipSuccess) {
+    (void)hipGetLastError();   // the failed allocation is reported here, not by the next launch
+    s->V = nullptr;
+    psignn_set_error("psignn_gmres64_create: cannot allocate the float64 basis: (m + 1) * N * d * 8 = %d * %lld * %d * 8 = %zu bytes",
+                     m + 1, (long long)s->N, D, basis_bytes);
+    psignn_gmres64_destroy(s);
+    return PSIGNN_ENOMEM;
+  }
+  auto fail = [&](int code) {
+    psignn_gmres64_destroy(s);
+    return code;
+  };
+#define G64_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t _e = (expr);                                                                  \
+    if (_e != hipSuccess) {                                                                  \
+      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+      return fail(PSIGNN_EHIP);                                                              \
+    }                                                                                        \
+  } while (0)
+  G64_TRY(hipMalloc((void**)&s->vec, (size_t)3 * s->M * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->part, (size_t)2 * s->nblk * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->partD, (size_t)(m + 2) * s->nchunk * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->coef, (size_t)(m + 2) * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->hcol, (size_t)(m + 2) * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->R, (size_t)(m + 1) * m * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->cs, (size_t)(m + 1) * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->sn, (size_t)(m + 1) * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->g, (size_t)(m + 1) * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->z, (size_t)(m + 1) * sizeof(double)));
+  G64_TRY(hipMalloc((void**)&s->st, sizeof(G64State)));
+  G64_TRY(hipHostMalloc((void**)&s->h_st, sizeof(G64State)));
+  *out = s;
+  return PSIGNN_OK;
+}
+
+extern "C" size_t psignn_gmres64_bytes(const psignn_gmres64_t* s) {
+  if (!s) return 0;
+  const size_t m = (size_t)s->m;
+  return ((m + 1) + 3) * (size_t)s->M * sizeof(double) +
+         ((size_t)2 * s->nblk + (m + 2) * (size_t)s->nchunk + 2 * (m + 2) + (m + 1) * m + 4 * (m + 1) + 2 * (size_t)s->cap) * sizeof(double) +
+         sizeof(G64State);
+}
+
+// the traces hold one entry per cycle; a cycle after the first spends at least two products
+static int g64_traces(psignn_gmres64* s, int max_products) {
+  const int cap = max_products / 2 + 3;
+  if (s->cap >= cap) return PSIGNN_OK;
+  if (s->rel_trace) (void)hipFree(s->rel_trace);
+  if (s->abs_trace) (void)hipFree(s->abs_trace);
+  s->rel_trace = s->abs_trace = nullptr;
+  s->cap = 0;
+  HIP_TRY(hipMalloc((void**)&s->rel_trace, (size_t)cap * sizeof(double)));
+  HIP_TRY(hipMalloc((void**)&s->abs_trace, (size_t)cap * sizeof(double)));
+  s->cap = cap;
+  return PSIGNN_OK;
+}
+
+extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W, int nl, const double* h_star, const double* h0,
+                                            const double* prb, const double* nrm, const double* grad, double eps, int max_products,
+                                            int poll_every, double* work, int64_t work_doubles, double* result,
+                                            psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace,
+                                            void* stream) {
+  ARG_CHECK(s && W && h_star && h0 && prb && grad && work && result && h_info, "NULL argument");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(eps >= 0.0 && eps < INFINITY, "eps must be finite and >= 0");
+  ARG_CHECK(max_products >= 1 && max_products <= (1 << 24), "max_products out of range");
+  if (poll_every <= 0) poll_every = 8;
+  int rc;
+  if ((rc = g64_traces(s, max_products))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t M = s->M, nblk = s->nblk;
+  const int m = s->m;
+  const unsigned g2 = (unsigned)nblk, gc = (unsigned)s->nchunk;
+  double *y = s->vec, *fy = s->vec + M, *ybest = s->vec + 2 * M;
+  const int32_t* cycle_done = &s->st->done;
+  auto product = [&](const double* x, double* out, const int32_t* done) {
+    return psignn_f64_vjp_gated(s->f, W, nl, h_star, h0, prb, nrm, x, nullptr, out, work, work_doubles, done, st);
+  };
+  k_ag64_init<<<1, 1, 0, st>>>(s->st);
+  for (int cycle = 0;; ++cycle) {
+    // the residual's product is not gated: the flag of the cycle that just ended is still up
+    if (cycle > 0 && (rc = psignn_f64_vjp_gated(s->f, W, nl, h_star, h0, prb, nrm, y, grad, fy, work, work_doubles, nullptr, st)))
+      return rc;
+    PROF_BYTES(3 * M * 8);
+    LAUNCH("k_ag64_begin", st, (k_ag64_begin<<<g2, G64_TB, 0, st>>>(M, nblk, s->st, y, fy, grad, s->V, s->part, cycle == 0)));
+    LAUNCH("k_ag64_check", st, (k_ag64_check<<<1, G64_TB, 0, st>>>(s->st, s->part, nblk, s->g, s->rel_trace, s->abs_trace, s->cap, eps,
+                                                                  max_products, m)));
+    PROF_BYTES(2 * M * 8);
+    LAUNCH("k_ag64_keep", st, (k_ag64_keep<<<g2, G64_TB, 0, st>>>(M, s->st, y, ybest)));
+    PROF_BYTES(2 * M * 8);
+    LAUNCH("k_gm64_scale", st, (k_gm64_scale<<<g2, G64_TB, 0, st>>>(M, s->st, s->V, &s->st->rnorm, s->V)));
+    HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(G64State), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (s->h_st->solved) break;
+    const int steps = s->h_st->steps_left;
+    if (steps < 1 || steps > m) {
+      psignn_set_error("psignn_gmres64_solve_adjoint: internal: %d Arnoldi steps allowed, restart length %d", steps, m);
+      return PSIGNN_EHIP;
+    }
+    for (int j = 0; j < steps; ++j) {
+      double* w = s->V + (size_t)(j + 1) * M;
+      if ((rc = product(s->V + (size_t)j * M, w, cycle_done))) return rc;
+      for (int pass = 0; pass < 2; ++pass) {
+        PROF_BYTES(((int64_t)j + 2 + (pass == 0)) * M * 8);
+        LAUNCH("k_gm64_dots", st, (k_gm64_dots<<<gc, G64_TB, 0, st>>>(M, s->nchunk, j, pass, s->st, s->V, s->partD)));
+        LAUNCH("k_gm64_reduce", st, (k_gm64_reduce<<<(unsigned)(j + 1 + (pass == 0)), G64_TB, 0, st>>>(s->nchunk, j, pass, s->st, s->partD,
+                                                                                                      s->coef, s->hcol)));
+        PROF_BYTES(((int64_t)j + 3) * M * 8);
+        LAUNCH("k_gm64_axpy", st, (k_gm64_axpy<<<g2, G64_TB, 0, st>>>(M, j, pass, s->st, s->V, s->coef, s->part)));
+        if (pass == 0) LAUNCH("k_gm64_decide", st, (k_gm64_decide<<<1, G64_TB, 0, st>>>(s->st, s->part, nblk)));
+      }
+      LAUNCH("k_gm64_finish", st, (k_gm64_finish<<<1, G64_TB, 0, st>>>(s->st, s->part, nblk, j, m, 0.5 * eps, s->hcol, s->R, s->cs, s->sn,
+                                                                      s->g)));
+      PROF_BYTES(2 * M * 8);
+      LAUNCH("k_gm64_scale", st, (k_gm64_scale<<<g2, G64_TB, 0, st>>>(M, s->st, w, &s->st->hn, w)));
+      if ((j + 1) % poll_every == 0 && j + 1 < steps) {
+        HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(G64State), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (s->h_st->done) break;
+      }
+    }
+    LAUNCH("k_gm64_backsolve", st, (k_gm64_backsolve<<<1, 64, 0, st>>>(s->st, m, s->R, s->g, s->z)));
+    PROF_BYTES(((int64_t)m + 2) * M * 8);
+    LAUNCH("k_gm64_combine", st, (k_gm64_combine<<<g2, G64_TB, 0, st>>>(M, s->st, s->V, s->z, y)));
+  }
+  HIP_TRY(hipGetLastError());
+  const G64State& h = *s->h_st;
+  if (h.cycles < 1 || h.products < 0 || h.products > max_products) {
+    psignn_set_error("psignn_gmres64_solve_adjoint: internal: %d cycles, %d products recorded, budget %d", h.cycles, h.products,
+                     max_products);
+    return PSIGNN_EHIP;
+  }
+  const int n = h.cycles < s->cap ? h.cycles : s->cap;
+  HIP_TRY(hipMemcpyAsync(result, ybest, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (h_rel_trace) HIP_TRY(hipMemcpyAsync(h_rel_trace, s->rel_trace, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (h_abs_trace) HIP_TRY(hipMemcpyAsync(h_abs_trace, s->abs_trace, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  h_info->products = h.products;
+  h_info->cycles = h.cycles;
+  h_info->stop_reason = h.stop;
+  h_info->n_reorth = h.n_reorth;
+  h_info->lowest = h.lowest;
+  h_info->lowest_abs = h.lowest_abs;
+  return PSIGNN_OK;
+}

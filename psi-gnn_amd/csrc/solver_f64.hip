@@ -4,6 +4,10 @@
 //           (dirichlet/psignn/utilities/solver.py:116-207 with matvec / rmatvec :96-114), as oracle/make_golden.py runs it for the
 //           stored fp64_result arrays.
 //
+// The host driver is one loop over an operator (b64_loop): f for the fixed point (psignn_broyden64_solve), y -> J_f(h*)^T y + grad
+// for the adjoint system of the implicit backward from y = 0 (psignn_broyden64_solve_adjoint; dirichlet/psignn/model.py:210-223
+// in double precision; the product is psignn_f64_vjp with add = grad, fgnn_f64_deriv.hip).
+//
 // The recurrences are the reference's, statement by statement (k = nstep - 1 stored pairs when step nstep is taken):
 //   x_new = x + update, dx = x_new - x, g_new = f(x_new) - x_new, dg = g_new - g
 //   abs = |g_new|, rel = abs / (|g_new + x_new| + 1e-9); the lowest-rel iterate is kept
@@ -439,13 +443,12 @@ extern "C" size_t psignn_broyden64_bytes(const psignn_broyden64_t* s) {
          ((size_t)2 * s->nblk + (size_t)s->threshold * 3 * (s->nchunk + 1) + (size_t)2 * s->threshold) * sizeof(double) + sizeof(B64State);
 }
 
-extern "C" int psignn_broyden64_solve(psignn_broyden64_t* s, const double* W, int nl, const double* x0, const double* h0,
-                                      const double* prb, const double* nrm, double eps, int poll_every, double* result,
-                                      psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream) {
-  ARG_CHECK(s && W && x0 && h0 && prb && result && h_info, "NULL argument");
-  ARG_CHECK(eps >= 0.0 && eps < INFINITY, "eps must be finite and >= 0");
+// One solve of g(x) = op(x) - x.  op(x, out, done): out = the map at x on the stream, its launches returning at once when *done is
+// set (NULL: no flag).  d_x0 == NULL: from x0 = 0.
+template <class Op>
+static int b64_loop(psignn_broyden64* s, Op&& op, const double* x0, double eps, int poll_every, double* result,
+                    psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, hipStream_t st) {
   if (poll_every <= 0) poll_every = 16;
-  hipStream_t st = (hipStream_t)stream;
   const int64_t M = s->M, nblk = s->nblk;
   const unsigned g1 = (unsigned)cdiv(M, B64_TB), g2 = (unsigned)nblk, gc = (unsigned)s->nchunk;
   double* x[2] = {s->vec, s->vec + M};
@@ -454,14 +457,18 @@ extern "C" int psignn_broyden64_solve(psignn_broyden64_t* s, const double* W, in
   const int32_t* done = &s->st->done;
   int rc;
   k_b64_init<<<1, 1, 0, st>>>(s->st);
+  if (!x0) {   // the zero start sits in the second iterate buffer, which step 1 overwrites
+    HIP_TRY(hipMemsetAsync(x[1], 0, (size_t)M * sizeof(double), st));
+    x0 = x[1];
+  }
   k_b64_load<<<g1, B64_TB, 0, st>>>(M, x0, x[0], result);
-  if ((rc = psignn_f64_eval(s->f, W, nl, x[0], h0, prb, nrm, fx, nullptr, st))) return rc;
+  if ((rc = op(x[0], fx, nullptr))) return rc;
   k_b64_begin<<<g1, B64_TB, 0, st>>>(M, fx, x[0], g[0], upd);
   for (int it = 1; it <= s->threshold; ++it) {
     const int o = (it - 1) & 1, n = it & 1, k = it - 1;
     PROF_BYTES(4 * M * 8);
     LAUNCH("k_b64_step", st, (k_b64_step<<<g2, B64_TB, 0, st>>>(M, s->st, x[o], upd, x[n], dx)));
-    if ((rc = psignn_f64_eval(s->f, W, nl, x[n], h0, prb, nrm, fx, done, st))) return rc;
+    if ((rc = op(x[n], fx, done))) return rc;
     PROF_BYTES(5 * M * 8);
     LAUNCH("k_b64_resid", st, (k_b64_resid<<<g2, B64_TB, 0, st>>>(M, nblk, s->st, fx, x[n], g[o], g[n], dg, s->part)));
     LAUNCH("k_b64_test", st, (k_b64_test<<<1, B64_TB, 0, st>>>(s->st, s->part, nblk, eps, s->threshold, s->rel_trace, s->abs_trace)));
@@ -490,7 +497,7 @@ extern "C" int psignn_broyden64_solve(psignn_broyden64_t* s, const double* W, in
   const B64State& h = *s->h_st;
   const int n_it = h.nstep;
   if (n_it < 0 || n_it > s->threshold) {
-    psignn_set_error("psignn_broyden64_solve: internal: %d iterations recorded, threshold %d", n_it, s->threshold);
+    psignn_set_error("psignn_broyden64: internal: %d iterations recorded, threshold %d", n_it, s->threshold);
     return PSIGNN_EHIP;
   }
   if (h_rel_trace && n_it > 0) HIP_TRY(hipMemcpy(h_rel_trace, s->rel_trace, (size_t)n_it * sizeof(double), hipMemcpyDeviceToHost));
@@ -502,4 +509,29 @@ extern "C" int psignn_broyden64_solve(psignn_broyden64_t* s, const double* W, in
   h_info->lowest = h.lowest;
   h_info->lowest_abs = h.lowest_abs;
   return PSIGNN_OK;
+}
+
+extern "C" int psignn_broyden64_solve(psignn_broyden64_t* s, const double* W, int nl, const double* x0, const double* h0,
+                                      const double* prb, const double* nrm, double eps, int poll_every, double* result,
+                                      psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream) {
+  ARG_CHECK(s && W && x0 && h0 && prb && result && h_info, "NULL argument");
+  ARG_CHECK(eps >= 0.0 && eps < INFINITY, "eps must be finite and >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  auto f = [&](const double* x, double* out, const int32_t* done) { return psignn_f64_eval(s->f, W, nl, x, h0, prb, nrm, out, done, st); };
+  return b64_loop(s, f, x0, eps, poll_every, result, h_info, h_rel_trace, h_abs_trace, st);
+}
+
+// The adjoint system of the implicit backward with the same recurrences: the map is y -> J_f(h*)^T y + grad, one psignn_f64_vjp with
+// add = grad per step (what the reference's hook hands to broyden, dirichlet/psignn/model.py:210-223), from y = 0.
+extern "C" int psignn_broyden64_solve_adjoint(psignn_broyden64_t* s, const double* W, int nl, const double* h_star, const double* h0,
+                                              const double* prb, const double* nrm, const double* grad, double eps, int poll_every,
+                                              double* work, int64_t work_doubles, double* result, psignn_solve_info_t* h_info,
+                                              double* h_rel_trace, double* h_abs_trace, void* stream) {
+  ARG_CHECK(s && W && h_star && h0 && prb && grad && work && result && h_info, "NULL argument");
+  ARG_CHECK(eps >= 0.0 && eps < INFINITY, "eps must be finite and >= 0");
+  hipStream_t st = (hipStream_t)stream;
+  auto f = [&](const double* y, double* out, const int32_t* done) {
+    return psignn_f64_vjp_gated(s->f, W, nl, h_star, h0, prb, nrm, y, grad, out, work, work_doubles, done, st);
+  };
+  return b64_loop(s, f, nullptr, eps, poll_every, result, h_info, h_rel_trace, h_abs_trace, st);
 }

@@ -2041,12 +2041,84 @@ class DeviceBroyden64:
                 self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(x0c), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
                 float(eps), int(poll_every), nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device)),
                 "psignn_broyden64_solve")
+        return self._result(info, rel, abs_, result)
+
+    def _result(self, info, rel, abs_, result):
         n_it = int(info.n_iter)
         pad = self.threshold + 1 - n_it
         return {"result": result, "lowest": float(info.lowest), "nstep": int(info.nstep), "n_iter": n_it,
                 "prot_break": bool(info.prot_break), "stop_reason": int(info.stop_reason),
                 "rel_trace": list(rel[:n_it]) + [float(info.lowest)] * pad,
                 "abs_trace": list(abs_[:n_it]) + [float(info.lowest_abs)] * pad}
+
+    def solve_adjoint(self, h_star, grad, eps, poll_every=16):
+        """``y = J_f(h*)^T y + grad`` from ``y = 0`` with the recurrences of ``solve`` (``psignn_broyden64_solve_adjoint``): the
+        reference's backward hook in double precision, one ``psignn_f64_vjp`` with ``add = grad`` per step.  ``h_star``, ``grad``:
+        (N, 10), float32 (widened exactly) or float64.  Returns the dict of ``solve``."""
+        if self.handle is None or self.fmap.handle is None:
+            raise nat.NativeError("DeviceBroyden64 (or its map) is closed")
+        fm = self.fmap
+        nat.require_default_width(getattr(getattr(fm, "weights", None), "width", D), "DeviceBroyden64.solve_adjoint")
+        hs, gr = fm._states((h_star, "h_star"), (grad, "grad"))
+        result = torch.empty_like(gr)
+        info = nat.SolveInfo()
+        rel = (C.c_double * self.threshold)()
+        abs_ = (C.c_double * self.threshold)()
+        work, n = fm._work(True)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_broyden64_solve_adjoint(
+                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(hs), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                nat.ptr(gr), float(eps), int(poll_every), nat.ptr(work), n, nat.ptr(result), C.byref(info), rel, abs_,
+                nat.stream_ptr(self.device)), "psignn_broyden64_solve_adjoint")
+        return self._result(info, rel, abs_, result)
+
+
+class DeviceGmres64:
+    """Restarted GMRES(m) in float64 for the adjoint system ``y = J_f(h*)^T y + grad`` on a ``FixedPointMap64``
+    (``psignn_gmres64_*``, csrc/krylov_f64.hip): the float64 adjoint at any size.  The basis is stored in float64,
+    ``(m + 1) * N * 10 * 8`` bytes; creation raises ``NativeError`` naming that size when the device cannot hold it."""
+
+    def __init__(self, fmap64, m):
+        if getattr(fmap64, "handle", None) is None:
+            raise nat.NativeError("DeviceGmres64 needs an open FixedPointMap64")
+        self.fmap, self.m, self.device = fmap64, int(m), fmap64.device
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_gmres64_create(C.byref(h), fmap64.handle, self.m), "psignn_gmres64_create")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_gmres64_destroy, h)
+
+    def close(self):
+        self._fin()
+        self.handle = None
+
+    @property
+    def nbytes(self):
+        return int(nat.lib().psignn_gmres64_bytes(self.handle))
+
+    def solve_adjoint(self, h_star, grad, eps, max_products, poll_every=8):
+        """From ``y = 0``; ``h_star``, ``grad``: (N, 10), float32 (widened exactly) or float64.  Returns the dict of
+        ``DeviceGmres.solve_adjoint`` with a float64 ``result``: ``nstep`` = products spent, ``lowest``, ``rel_trace`` /
+        ``abs_trace`` with one entry per cycle, ``n_cycles``, ``stop`` (one of ``GMRES_STOPS``), ``n_reorth``.  Deterministic;
+        ``poll_every`` changes neither bits nor counts."""
+        if self.handle is None or self.fmap.handle is None:
+            raise nat.NativeError("DeviceGmres64 (or its map) is closed")
+        if int(max_products) < 1:
+            raise nat.NativeError(f"max_products must be >= 1, got {max_products}")
+        fm = self.fmap
+        nat.require_default_width(getattr(getattr(fm, "weights", None), "width", D), "DeviceGmres64.solve_adjoint")
+        hs, gr = fm._states((h_star, "h_star"), (grad, "grad"))
+        result = torch.empty_like(gr)
+        info = nat.GmresAdjointInfo()
+        cap = int(max_products) // 2 + 3
+        rel, abs_ = (C.c_double * cap)(), (C.c_double * cap)()
+        work, n = fm._work(True)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_gmres64_solve_adjoint(
+                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(hs), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                nat.ptr(gr), float(eps), int(max_products), int(poll_every), nat.ptr(work), n, nat.ptr(result), C.byref(info),
+                rel, abs_, nat.stream_ptr(self.device)), "psignn_gmres64_solve_adjoint")
+        return DeviceGmres._result(info, rel, abs_, result)
 
 
 def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16):
@@ -2068,3 +2140,34 @@ def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16):
     out["h0"] = h0
     out["u"] = mlp2_64(out["result"], *dec)
     return out
+
+
+def adjoint64(batch, state_dict, h_star, grad, solver="gmres", eps=1e-11, m=50, max_products=2000, threshold=800):
+    """The adjoint of the implicit backward in float64 on the device, ``y = J_f(h*)^T y + grad``, for a device batch and a reference
+    state dict (default latent width): the encoder in float64, then ``solver="gmres"`` (``DeviceGmres64(m)``, budget
+    ``max_products``) or ``"broyden"`` (``DeviceBroyden64(threshold)``, the reference's own solver).  ``h_star``, ``grad``: (N, 10),
+    float32 (widened exactly) or float64.  Returns the solver's dictionary."""
+    if solver not in ("gmres", "broyden"):
+        raise nat.NativeError(f"adjoint64: solver must be 'gmres' or 'broyden', got {solver!r}")
+    nat.require_default_width(width_of(state_dict), "adjoint64")
+    n = int(batch.x.shape[0])
+    for t, name in ((h_star, "h_star"), (grad, "grad")):
+        if tuple(t.shape) != (n, D):
+            raise nat.NativeError(f"{name} has shape {tuple(t.shape)}, expected {(n, D)}")
+    w = PackedWeights64(state_dict)
+    ae = lambda k: state_dict["autoencoder." + k]
+    enc = [ae(f"encoder.mlp.mlp.{i}.{p}") for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
+    plan = plan_for(batch)
+    h0 = mlp2_64(batch.x, *enc)
+    fmap = FixedPointMap64(plan, w, h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
+    sv = None
+    try:
+        if solver == "gmres":
+            sv = DeviceGmres64(fmap, m)
+            return sv.solve_adjoint(h_star, grad, eps, max_products)
+        sv = DeviceBroyden64(fmap, threshold)
+        return sv.solve_adjoint(h_star, grad, eps)
+    finally:
+        if sv is not None:
+            sv.close()
+        fmap.close()

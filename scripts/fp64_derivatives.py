@@ -18,8 +18,8 @@ fw_tol 1e-5 / fw_thres 500 from h0 = encoder(x)) and with v, w, grad = randn (se
 * VGPRs / scratch / occupancy of the float64 derivative kernels, parsed from the compiler's ``-Rpass-analysis=kernel-resource-usage``
   remarks (``--resource-usage``, default profiles/fp64_deriv_resource_usage.txt).
 
-Nothing is gated.  A float64 adjoint solve does not exist on the device, so its steps, its ``lowest`` and the distance of the fp32
-adjoint solutions from it are recorded as "not measured".
+Nothing is gated.  This script predates the float64 adjoint solves and records their steps, their ``lowest`` and the distance of
+the fp32 adjoint solutions from them as "not measured"; scripts/fp64_adjoint.py measures those.
 
     python scripts/fp64_derivatives.py [--nodes 27000 100000 270000 1000000] [--out profiles/fp64_derivatives.json]
 """
