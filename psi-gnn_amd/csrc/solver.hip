@@ -253,7 +253,8 @@ __device__ void check_block(Status* st, const float* __restrict__ part, int npar
     }
     if (mx / mn < 1.3) reason = 2;
   }
-  if (reason < 0 && obj > (stop_abs ? s.abs0 * 1e6 : s.rel0 * 1e3) * seq_len) {
+  // (the reference forms protect_thres = 1e3 * seq_len first, then trace[0] * protect_thres: the same order here)
+  if (reason < 0 && obj > (stop_abs ? s.abs0 : s.rel0) * ((stop_abs ? 1e6 : 1e3) * seq_len)) {
     reason = 3;
     s.prot_break = 1;
   }

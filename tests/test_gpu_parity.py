@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from broyden_stop_ref import REASONS, assert_replay
 from conftest import CASES, load_case, load_weights, pkg, rel_l2
 from oracle import psignn_oracle as orc
 from plan_ref import plan_reference
@@ -372,10 +373,13 @@ def test_generic_callable_broyden_matches_oracle(dev):
     assert abs(out["nstep"] - ref["nstep"]) <= 2
     np.testing.assert_allclose(out["rel_trace"][:6], ref["rel_trace"][:6], rtol=1e-3)
     assert set(ref) <= set(out)
-    # protective break: an expanding map trips rel > rel0 * 1e3 * d (solver.py:181-183)
-    g_dev = lambda x: 30.0 * x + 1.0
+    # an expanding map, meant to trip rel > rel0 * 1e3 * d (solver.py:181-183); it runs to the threshold (the break itself is
+    # scripted in test_gpu_broyden_stop.py)
     o = solver.broyden(lambda x: torch.sin(50 * x) * 40 + x * x, torch.ones(50, 7, device=dev), threshold=40, eps=1e-12)
     assert o["n_iter"] <= 40 and len(o["rel_trace"]) == 41
+    # whatever ends this solve, the reference's rules replayed over its own traces must end it there, for that reason
+    rp = assert_replay(o, 1e-12, 40, 7, "rel", what="expanding map")
+    print(f"expanding map: {REASONS[rp['stop_reason']]} at step {o['n_iter']}, lowest at {o['nstep']}")
 
 
 def test_threshold_stop_and_trace_padding(dev):
