@@ -821,6 +821,47 @@ int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* d_weights, i
                                  psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Parameter gradients in float64 on the device (csrc/fgnn_f64_deriv.hip): the last link of loss.backward() in double precision, and
+ * the truth the fp32 parameter-gradient kernels are measured against, at any size.  Same handle, weights, numbering and rules as
+ * psignn_f64_vjp.  Every gradient is a sum over receiving nodes: one workgroup per chunk of psignn_f64_param_vjp_chunk_rows()
+ * consecutive rows of the caller's numbering adds its rows' outer products in ascending row order (per edge list: edge position by
+ * edge position) and writes one row of partials; the partial rows are then added in ascending order, 64 at a time, and those sums
+ * in ascending order again.  No floating-point atomics, and a summation order that depends on the graph alone: the same call gives
+ * the same bits, on tiled and untiled plans alike.  Default-width library only.
+ * ------------------------------------------------------------------------------------------ */
+/* Rows whose contributions one partial holds (the chunks start at row 0).
+ * replaces: nothing of the reference (dirichlet/psignn/model.py:203-225 sums in autograd's order). */
+int psignn_f64_param_vjp_chunk_rows(void);
+/* Doubles of d_work for psignn_f64_param_vjp: psignn_f64_deriv_workspace_doubles(f, n_layers, 1) for the product J^T w, then
+ * ceil(N / chunk_rows) * psignn_f64_weights_size(mixed, 1) for the partials.  -1 for a NULL handle or n_layers < 1.
+ * replaces: autograd's saved tensors of dirichlet/psignn/model.py:203-225. */
+int64_t psignn_f64_param_vjp_workspace_doubles(const psignn_f64_t* f, int n_layers);
+/* d_grad (psignn_f64_weights_size(mixed, n_layers) doubles, the layout of d_weights, nothing padded): the gradient of
+ * <d_w, f(d_h; d_h_initial)> with respect to every deqdss.f.* tensor.  d_out_h = J_f(d_h)^T d_w, the bits of psignn_f64_vjp.
+ * d_out_init (may be NULL) = d_w^T df/dh_initial: the Dirichlet rows of the cotangent on every layer's output, summed over the
+ * layers (single-layer block: d_w copied on the Dirichlet rows, 0 elsewhere).  Dirichlet family, n_layers > 1: the layer states at
+ * d_h, then the chain backwards, layer k's gradient at (h_k, w_{k+1}); alpha.0.* accumulates over the layers from the last to the
+ * first, laynorm.* comes from the last layer.  Mixed family: only the last layer's iteration reaches the output, so the earlier
+ * layers' sections are exact zeros.  d_out_h aliases neither d_h nor d_w; a d_work smaller than the query is PSIGNN_ENOMEM with a
+ * message naming the bytes.
+ * replaces: loss.backward() into the deqdss.f.* parameters after the hook has swapped in the adjoint solution, in double precision
+ *           (dirichlet/psignn/model.py:203-225; mixed/psignn/model.py likewise). */
+int psignn_f64_param_vjp(psignn_f64_t* f, const double* d_weights, int n_layers, const double* d_h, const double* d_h_initial,
+                         const double* d_prb, const double* d_normals /* NULL for dirichlet plans */, const double* d_w,
+                         double* d_grad, double* d_out_h, double* d_out_init /* NULL: skip */, double* d_work, int64_t work_doubles,
+                         void* stream);
+/* Doubles of d_work for psignn_mlp2_f64_backward: ceil(n / 128) * (hid * din + hid + dout * hid + dout); -1 for sizes out of range.
+ * replaces: autograd's saved tensors of Encoder / Decoder, dirichlet/psignn/model.py:370-392. */
+int64_t psignn_mlp2_f64_backward_workspace_doubles(int64_t n, int din, int hid, int dout);
+/* Backward of psignn_mlp2_f64 (din, hid, dout <= 16, any n): from d_x (n, din) and d_gy (n, dout), d_gx (n, din; NULL: skip) and
+ * d_gflat = [gW1 (hid, din) | gb1 | gW2 (dout, hid) | gb2] in float64.  Deterministic by the rule above: per-chunk partials of 128
+ * rows, added in a fixed order.
+ * replaces: autograd through Encoder / Decoder on float64 tensors, dirichlet/psignn/model.py:370-392. */
+int psignn_mlp2_f64_backward(const double* d_x, const double* d_gy, int64_t n, int din, int hid, int dout, const double* d_w1,
+                             const double* d_b1, const double* d_w2, double* d_gx, double* d_gflat, double* d_work,
+                             int64_t work_doubles, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line;
  * replaces: the reference's only instrumentation, time.time() around the model call,
  * tests/special_geo/spec_geo_2.py:313-317).  Off by default.

@@ -227,6 +227,11 @@ SIGNATURES = {
     "psignn_gmres64_bytes": (C.c_size_t, [_P]),
     "psignn_gmres64_solve_adjoint": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, C.c_double, _INT, _INT, _P, _I64, _P,
                                             C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_f64_param_vjp_chunk_rows": (_INT, []),
+    "psignn_f64_param_vjp_workspace_doubles": (_I64, [_P, _INT]),
+    "psignn_f64_param_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "psignn_mlp2_f64_backward_workspace_doubles": (_I64, [_I64, _INT, _INT, _INT]),
+    "psignn_mlp2_f64_backward": (_INT, [_P, _P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "psignn_prof_enable": (None, [_INT]),
     "psignn_reload_knobs": (None, []),
     "psignn_prof_tile_stamps": (None, [_P]),

@@ -698,3 +698,505 @@ extern "C" int psignn_f64_vjp(psignn_f64_t* f, const double* W, int nl, const do
                               int64_t work_doubles, void* stream) {
   return psignn_f64_vjp_gated(f, W, nl, h, h0, prb, nrm, w, add, out, work, work_doubles, nullptr, (hipStream_t)stream);
 }
+
+// =============================================================================================
+// Parameter gradients in float64: the gradient of <w, f_theta(h; h_initial)> with respect to every deqdss.f.* tensor, in the flat
+// layout of W64, and the backward of the encoder / decoder MLP.
+//
+// replaces: what loss.backward() leaves in the deqdss.f.* parameters once the hook has swapped in the adjoint solution
+//           (dirichlet/psignn/model.py:203-225, mixed likewise), run in double precision; autograd through Encoder / Decoder
+//           (model.py:370-392) on float64 tensors.
+//
+// Every parameter's gradient is a sum over RECEIVING nodes of outer products A (x) B, so nothing is scattered and nothing is added
+// atomically.  One workgroup owns PG_ROWS consecutive rows of the caller's numbering (a chunk), one row per lane:
+//   * the lane recomputes its node as pass A of J^T w does and keeps the cotangents of the gate, the update and the message sums;
+//   * in rounds, every lane writes the two factors of one kind of outer product to its LDS row (Dirichlet rows, rows past the end
+//     and rows the module does not act on: zeros), and after a barrier every thread, owning a few (o, k) entries of the module's
+//     weight and bias, walks the PG_ROWS rows in ascending order.  Node rounds: update W1 + gate, update W2 + LayerNorm,
+//     update_neumann; then per edge list one round per edge position j (the j-th in-edge of every row), until no row has one left;
+//   * the thread's sums are one row of per-chunk partials.
+// k_f64_pg_fold adds the partial rows of PG_FOLD consecutive chunks in ascending order, k_f64_pg_final adds those group sums in
+// ascending order into the gradient.  Chunk, group and round order are compile-time constants and the lists are the plan's canonical
+// ones, so the summation order depends on the graph alone: the same call gives the same bits, on tiled and untiled plans alike.
+// =============================================================================================
+#define PG_ROWS 128   // rows per chunk = threads per workgroup
+#define PG_RS 57      // doubles per LDS row: the widest round (update_neumann: 10 + 26 + 10 + 11); odd, so rows spread over the banks
+#define PG_FOLD 64    // chunks per group of the first reduction stage
+#define PG_MLP_RS 33  // psignn_mlp2_f64_backward: 16 + 16 + 1
+
+// acc[j] += sum over the chunk's rows r (ascending) of buf[r][aoff + o] * buf[r][boff + k] for the entries e = tid + j * PG_ROWS
+// < no * kw of one module, o = e / kw, k = e % kw; B's last column holds 1 (the bias).
+template <int RS, int NA>
+__device__ __forceinline__ void pg_acc(const double* buf, int aoff, int boff, int no, int kw, double* acc) {
+#pragma unroll
+  for (int j = 0; j < NA; ++j) {
+    const int e = (int)threadIdx.x + j * PG_ROWS;
+    if (e < no * kw) {
+      const double *pa = buf + aoff + e / kw, *pb = buf + boff + e % kw;
+      double s = acc[j];
+#pragma unroll 8
+      for (int r = 0; r < PG_ROWS; ++r) s = fma(pa[r * RS], pb[r * RS], s);
+      acc[j] = s;
+    }
+  }
+}
+// the thread's entries into the chunk's partial row: weight (no, kw - 1) row-major at wofs, bias (no) at bofs
+template <int NA>
+__device__ __forceinline__ void pg_put(double* pt, int wofs, int bofs, int no, int kw, const double* acc) {
+#pragma unroll
+  for (int j = 0; j < NA; ++j) {
+    const int e = (int)threadIdx.x + j * PG_ROWS;
+    if (e < no * kw) {
+      const int o = e / kw, k = e % kw;
+      pt[k < kw - 1 ? wofs + o * (kw - 1) + k : bofs + o] = acc[j];
+    }
+  }
+}
+
+// One Phi module over one edge list of the chunk's rows: round j holds the j-th entry of every row's list.
+// row: qm 0..9 | x_i 10..19, x_j 20..29, a 30..32, 1 | c 34..43 | relu(s) 44..53, 1
+__device__ __forceinline__ void pg_edges(const double* __restrict__ Wp, bool act, const double* x, const double* c,
+                                         const double* __restrict__ h, int32_t beg, int32_t end, const int32_t* __restrict__ nbr,
+                                         const double* __restrict__ attr, double* buf, double* row, double* pt, int base) {
+  using L = W64<2>;
+  double q[D], a1[2] = {0.0, 0.0}, a2[1] = {0.0};
+  d64_w2t(Wp, c, q);
+  for (int32_t j = 0;; ++j) {
+    const bool on = act && beg + j < end;
+    if (!__syncthreads_or(on)) break;   // also the barrier behind the previous round's reads
+    if (on) {
+      const int32_t i = beg + j;
+      double xj[D], a[3], s[D];
+      d64_row(h, nbr[i], xj);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a[k] = attr[3 * (int64_t)i + k];
+      d64_pre(Wp, x, xj, a, s);
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        row[k] = s[k] > 0.0 ? q[k] : 0.0;
+        row[10 + k] = x[k];
+        row[20 + k] = xj[k];
+        row[34 + k] = c[k];
+        row[44 + k] = fmax(s[k], 0.0);
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) row[30 + k] = a[k];
+      row[33] = 1.0;
+      row[54] = 1.0;
+    } else {
+      for (int k = 0; k < 55; ++k) row[k] = 0.0;
+    }
+    __syncthreads();
+    pg_acc<PG_RS, 2>(buf, 0, 10, D, L::EIN + 1, a1);
+    pg_acc<PG_RS, 1>(buf, 34, 44, D, D + 1, a2);
+  }
+  pg_put<2>(pt, base + L::PHI_W1, base + L::PHI_B1, D, L::EIN + 1, a1);
+  pg_put<1>(pt, base + L::PHI_W2, base + L::PHI_B2, D, D + 1, a2);
+}
+
+// One layer's parameter gradient at (h, w), per chunk: part (chunks, W64<P>::total(1, MIXED)) in the layout of a single-layer block.
+template <int P, bool MIXED>
+__global__ __launch_bounds__(PG_ROWS) void k_f64_pgrad(int64_t N, const double* __restrict__ W, int lofs, int nofs, int apply_ln,
+                                                       const int32_t* __restrict__ csr_ptr, const int32_t* __restrict__ csr_nbr,
+                                                       const double* __restrict__ csr_attr, const int32_t* __restrict__ csc_ptr,
+                                                       const int32_t* __restrict__ csc_nbr, const double* __restrict__ csc_attr,
+                                                       const uint8_t* __restrict__ flags, const double* __restrict__ h,
+                                                       const double* __restrict__ prb, const double* __restrict__ nrm,
+                                                       const double* __restrict__ w, double* __restrict__ part) {
+  using L = W64<P>;
+  constexpr int CW = MIXED ? 3 * D : 2 * D;
+  static_assert(10 + L::CAT + 1 + 1 <= PG_RS && 10 + L::NCAT + 1 + 10 + D + 1 <= PG_RS && D == 10, "LDS row of the rounds");
+  __shared__ double buf[PG_ROWS * PG_RS];
+  double* row = buf + threadIdx.x * PG_RS;
+  double* pt = part + (int64_t)blockIdx.x * L::total(1, MIXED);
+  const int64_t n = (int64_t)blockIdx.x * PG_ROWS + threadIdx.x;
+  const uint8_t fl = n < N ? flags[n] : (uint8_t)FLAG_DIRICHLET;   // a row past the end gives what a Dirichlet row gives: nothing
+  const bool live = !(fl & FLAG_DIRICHLET);
+  const bool neu = MIXED && live && (fl & FLAG_NEUMANN);
+  const bool upd = live && !neu;
+  // the factors of the node rounds; a row is an update row or a Neumann row, so the two kinds share them:
+  // q: cotangent of the hidden pre-activations; cat: the MLP's input; g: cotangent of the MLP's output; rp: relu(pre)
+  double x[D], c[CW], q[D], cat[L::CAT], g[D], rp[D], wy[D], gw[D], gal = 0.0;
+  int32_t rb = 0, re = 0, cb = 0, ce = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = q[k] = g[k] = rp[k] = wy[k] = gw[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < CW; ++k) c[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < L::CAT; ++k) cat[k] = 0.0;
+  if (live) {
+    double gy[D], pre[D], y[D];
+    d64_row(h, n, x);
+    d64_row(w, n, gy);
+    rb = csr_ptr[n], re = csr_ptr[n + 1], cb = csc_ptr[n], ce = csc_ptr[n + 1];
+    double al = 1.0;
+    const double* Wm = neu ? W + nofs + L::PHI_SZ : W + lofs + 2 * L::PHI_SZ;   // W1 | b1 | W2 | b2 of the row's MLP
+    int ncat, ob1, ow2, ob2;
+    if (neu) {
+      double mp[D];
+      d64_phi<false>(W + nofs, x, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, mp, nullptr);
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        cat[k] = x[k];
+        cat[D + k] = mp[k];
+      }
+#pragma unroll
+      for (int k = 0; k < P; ++k) cat[2 * D + k] = prb[n * P + k];
+      cat[2 * D + P] = nrm[2 * n];
+      cat[2 * D + P + 1] = nrm[2 * n + 1];
+      ncat = L::NCAT, ob1 = L::NEU_B1, ow2 = L::NEU_W2, ob2 = L::NEU_B2;
+    } else {
+#pragma unroll
+      for (int k = 0; k < D; ++k) cat[k] = x[k];
+      d64_phi<false>(W + lofs, x, nullptr, h, nullptr, cb, ce, csc_nbr, csc_attr, cat + D, nullptr);
+      d64_phi<false>(W + lofs + L::PHI_SZ, x, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, cat + 2 * D, nullptr);
+#pragma unroll
+      for (int k = 0; k < P; ++k) cat[3 * D + k] = prb[n * P + k];
+      al = W[L::AL_B];
+#pragma unroll
+      for (int k = 0; k < L::CAT; ++k) al = fma(W[L::AL_W + k], cat[k], al);
+      al = 1.0 / (1.0 + exp(-al));
+      ncat = L::CAT, ob1 = L::UPD_B1, ow2 = L::UPD_W2, ob2 = L::UPD_B2;
+    }
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+      double s = Wm[ob1 + o];
+#pragma unroll
+      for (int k = 0; k < L::CAT; ++k)
+        if (k < ncat) s = fma(Wm[o * ncat + k], cat[k], s);
+      pre[o] = s;
+      rp[o] = fmax(s, 0.0);
+    }
+    double sv[D];
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+      double s = Wm[ob2 + o];
+#pragma unroll
+      for (int k = 0; k < D; ++k) s = fma(Wm[ow2 + o * D + k], rp[k], s);
+      sv[o] = s;
+      y[o] = neu ? s : x[o] + al * s;
+    }
+    if (apply_ln) {
+      double yhat[D], m1 = 0.0, m2 = 0.0;
+      const double rs = d64_ln_stats(y, yhat);
+#pragma unroll
+      for (int o = 0; o < D; ++o) {
+        wy[o] = gy[o] * yhat[o];
+        gw[o] = gy[o];
+        gy[o] *= W[L::LN_G + o];
+        m1 += gy[o];
+        m2 = fma(gy[o], yhat[o], m2);
+      }
+      m1 /= D;
+      m2 /= D;
+#pragma unroll
+      for (int o = 0; o < D; ++o) gy[o] = rs * (gy[o] - m1 - yhat[o] * m2);
+    }
+    if (!neu) {   // y = x + al * s: cotangent of the gate's pre-activation
+#pragma unroll
+      for (int o = 0; o < D; ++o) gal = fma(gy[o], sv[o], gal);
+      gal *= al * (1.0 - al);
+    }
+#pragma unroll
+    for (int o = 0; o < D; ++o) g[o] = al * gy[o];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      double s = 0.0;
+#pragma unroll
+      for (int o = 0; o < D; ++o) s = fma(Wm[ow2 + o * D + k], g[o], s);
+      q[k] = pre[k] > 0.0 ? s : 0.0;
+    }
+    // cotangents of the message sums: cat[D .. 2D) (and [2D .. 3D) of an update row)
+    if (neu) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        double s = 0.0;
+#pragma unroll
+        for (int o = 0; o < D; ++o) s = fma(Wm[o * L::NCAT + D + k], q[o], s);
+        c[CW - D + k] = s;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 2 * D; ++k) {
+        double s = W[L::AL_W + D + k] * gal;
+#pragma unroll
+        for (int o = 0; o < D; ++o) s = fma(Wm[o * L::CAT + D + k], q[o], s);
+        c[k] = s;
+      }
+    }
+  }
+  const int ub = L::layer(0) + 2 * L::PHI_SZ;   // the update block of the partial row
+  // ---- round 1, update rows: q 0..9 | cat 10 .. 10 + CAT, 1 | gal 44
+  {
+    double a1[3] = {0.0, 0.0, 0.0}, a2[1] = {0.0};
+#pragma unroll
+    for (int k = 0; k < D; ++k) row[k] = upd ? q[k] : 0.0;
+#pragma unroll
+    for (int k = 0; k < L::CAT; ++k) row[10 + k] = cat[k];
+    row[10 + L::CAT] = 1.0;
+    row[44] = upd ? gal : 0.0;
+    __syncthreads();
+    pg_acc<PG_RS, 3>(buf, 0, 10, D, L::CAT + 1, a1);
+    pg_acc<PG_RS, 1>(buf, 44, 10, 1, L::CAT + 1, a2);
+    pg_put<3>(pt, ub, ub + L::UPD_B1, D, L::CAT + 1, a1);
+    pg_put<1>(pt, L::AL_W, L::AL_B, 1, L::CAT + 1, a2);
+    __syncthreads();
+  }
+  // ---- round 2: g 0..9 | relu(pre) 10..19, 1 | w * yhat 21..30, w 31..40 (LayerNorm: every row that is not Dirichlet)
+  {
+    double a1[1] = {0.0}, s = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      row[k] = upd ? g[k] : 0.0;
+      row[10 + k] = rp[k];
+      row[21 + k] = wy[k];
+      row[31 + k] = gw[k];
+    }
+    row[20] = 1.0;
+    __syncthreads();
+    pg_acc<PG_RS, 1>(buf, 0, 10, D, D + 1, a1);
+    pg_put<1>(pt, ub + L::UPD_W2, ub + L::UPD_B2, D, D + 1, a1);
+    if (threadIdx.x < 2 * D) {
+      for (int r = 0; r < PG_ROWS; ++r) s += buf[r * PG_RS + 21 + threadIdx.x];
+      pt[L::LN_G + threadIdx.x] = s;   // LN_G .. LN_B + D is one run
+    }
+    __syncthreads();
+  }
+  // ---- round 3, Neumann rows: q 0..9 | cat 10..34, 1 | g 36..45 | relu(pre) 46..55, 1
+  if (MIXED) {
+    const int nb = L::layer(1) + L::PHI_SZ;
+    double a1[3] = {0.0, 0.0, 0.0}, a2[1] = {0.0};
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      row[k] = neu ? q[k] : 0.0;
+      row[36 + k] = neu ? g[k] : 0.0;
+      row[46 + k] = rp[k];
+    }
+#pragma unroll
+    for (int k = 0; k < L::NCAT; ++k) row[10 + k] = cat[k];
+    row[10 + L::NCAT] = 1.0;
+    row[56] = 1.0;
+    __syncthreads();
+    pg_acc<PG_RS, 3>(buf, 0, 10, D, L::NCAT + 1, a1);
+    pg_acc<PG_RS, 1>(buf, 36, 46, D, D + 1, a2);
+    pg_put<3>(pt, nb, nb + L::NEU_B1, D, L::NCAT + 1, a1);
+    pg_put<1>(pt, nb + L::NEU_W2, nb + L::NEU_B2, D, D + 1, a2);
+  }
+  // ---- the messages: Phi_to over the CSC list, Phi_from (Neumann rows: Phi_neumann) over the CSR list
+  pg_edges(W + lofs, upd, x, c, h, cb, ce, csc_nbr, csc_attr, buf, row, pt, L::layer(0));
+  pg_edges(W + lofs + L::PHI_SZ, upd, x, c + D, h, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(0) + L::PHI_SZ);
+  if (MIXED) pg_edges(W + nofs, neu, x, c + 2 * D, h, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(1));
+}
+
+// first stage: the partial rows of PG_FOLD consecutive chunks, added in ascending order into the first of them
+__global__ __launch_bounds__(64) void k_f64_pg_fold(double* __restrict__ part, int64_t nch, int ps) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= ps) return;
+  const int64_t c0 = (int64_t)blockIdx.y * PG_FOLD, c1 = c0 + PG_FOLD < nch ? c0 + PG_FOLD : nch;
+  double s = part[c0 * ps + e];
+#pragma unroll 8
+  for (int64_t c = c0 + 1; c < c1; ++c) s += part[c * ps + e];
+  part[c0 * ps + e] = s;
+}
+// second stage: the group sums in ascending order, added to the gradient.  Entry e of the single-layer layout goes to the shared
+// section, to the layer's section at dl, or to the Neumann section at dn.
+__global__ __launch_bounds__(64) void k_f64_pg_final(const double* __restrict__ part, int64_t nch, int ps, int shared, int layer,
+                                                     int dl, int dn, double* __restrict__ grad) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= ps) return;
+  double s = part[e];
+#pragma unroll 8
+  for (int64_t c = PG_FOLD; c < nch; c += PG_FOLD) s += part[c * ps + e];
+  const int d = e < shared ? e : e < shared + layer ? dl + (e - shared) : dn + (e - shared - layer);
+  grad[d] += s;
+}
+
+// w^T df/dh_initial of one layer: the Dirichlet rows of the cotangent on the layer's output, 0 elsewhere
+__global__ __launch_bounds__(256) void k_f64_pg_init(int64_t N, const uint8_t* __restrict__ flags, const double* __restrict__ w,
+                                                     int accumulate, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * D) return;
+  if (flags[i / D] & FLAG_DIRICHLET)
+    out[i] = accumulate ? out[i] + w[i] : w[i];
+  else if (!accumulate)
+    out[i] = 0.0;
+}
+
+extern "C" int psignn_f64_param_vjp_chunk_rows(void) { return PG_ROWS; }
+
+static inline int64_t pg_part_doubles(const psignn_f64* f) {
+  return cdiv(f->p->N, PG_ROWS) * (f->p->mixed ? W64<3>::total(1, true) : W64<2>::total(1, false));
+}
+
+extern "C" int64_t psignn_f64_param_vjp_workspace_doubles(const psignn_f64_t* f, int n_layers) {
+  if (!f || n_layers < 1) return -1;
+  return psignn_f64_deriv_workspace_doubles(f, n_layers, 1) + pg_part_doubles(f);   // J^T w's own, then the per-chunk partials
+}
+
+static void pg_reduce(double* part, int64_t nch, int ps, int shared, int layer, int dl, int dn, double* grad, hipStream_t st) {
+  PROF_BYTES(nch * ps * 8);
+  LAUNCH("k_f64_pg_fold", st,
+         (k_f64_pg_fold<<<dim3((unsigned)cdiv(ps, 64), (unsigned)cdiv(nch, PG_FOLD)), 64, 0, st>>>(part, nch, ps)));
+  PROF_BYTES(cdiv(nch, PG_FOLD) * ps * 8 + 16 * ps);
+  LAUNCH("k_f64_pg_final", st,
+         (k_f64_pg_final<<<(unsigned)cdiv(ps, 64), 64, 0, st>>>(part, nch, ps, shared, layer, dl, dn, grad)));
+}
+
+// layer l's gradient at (h, w) added to grad, and (init) its share of w^T df/dh_initial
+static void pgrad_launch(const psignn_f64* f, const double* W, int nl, int l, int apply_ln, const double* h, const double* prb,
+                         const double* nrm, const double* w, double* part, double* grad, double* init, int init_acc, hipStream_t st) {
+  const psignn_plan* p = f->p;
+  const int64_t nch = cdiv(p->N, PG_ROWS);
+  // both edge lists twice (the node's forward, then the rounds: neighbour id, 3 attributes, the neighbour's row), per node h, w,
+  // flag, pointers and problem data; the partial rows
+  PROF_BYTES(4 * p->Ep * (4 + 24 + 8 * D) + p->N * (16 * D + 8 * (p->mixed ? 5 : 2) + 17) + pg_part_doubles(f) * 8);
+  if (p->mixed) {
+    using L = W64<3>;
+    LAUNCH("k_f64_pgrad", st,
+           (k_f64_pgrad<3, true><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb,
+                                                                    nrm, w, part)));
+    pg_reduce(part, nch, L::total(1, true), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
+  } else {
+    using L = W64<2>;
+    LAUNCH("k_f64_pgrad", st,
+           (k_f64_pgrad<2, false><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb,
+                                                                     nrm, w, part)));
+    pg_reduce(part, nch, L::total(1, false), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
+  }
+  if (init) {
+    PROF_BYTES(p->N * (1 + 16 * D));
+    LAUNCH("k_f64_pg_init", st,
+           (k_f64_pg_init<<<(unsigned)cdiv(p->N * D, 256), 256, 0, st>>>(p->N, p->flags, w, init_acc, init)));
+  }
+}
+
+extern "C" int psignn_f64_param_vjp(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                                    const double* nrm, const double* w, double* d_grad, double* d_out_h, double* d_out_init,
+                                    double* work, int64_t work_doubles, void* stream) {
+  ARG_CHECK(f && W && h && h0 && prb && w && d_grad && d_out_h, "NULL argument");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
+  ARG_CHECK(d_out_h != h && d_out_h != w, "d_out_h must not alias h or w");
+  ARG_CHECK(d_out_init != h && d_out_init != w && d_out_init != d_out_h, "d_out_init must not alias h, w or d_out_h");
+  const int rc = work_check(__func__, psignn_f64_param_vjp_workspace_doubles(f, nl), work, work_doubles);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_grad, 0, sizeof(double) * psignn_f64_weights_size(f->p->mixed, nl), st));
+  if (f->p->N == 0) return PSIGNN_OK;
+  const int64_t row = f->p->N * D;
+  double *loc = work, *C = work + row, *part = work + psignn_f64_deriv_workspace_doubles(f, nl, 1);
+  if (!f64_chain(f, nl)) {   // mixed: only the last layer's iteration reaches the output, the earlier layers' sections stay zero
+    pgrad_launch(f, W, nl, nl - 1, 1, h, prb, nrm, w, part, d_grad, d_out_init, 0, st);
+    vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, w, loc, C, nullptr, d_out_h, nullptr, st);
+  } else {
+    // as psignn_f64_vjp: the states, then the chain backwards; layer l's gradient at (h_l, w_{l+1}) before w_l = J_l^T w_{l+1}
+    double *states = work + 3 * row, *pp = work + (3 + nl - 1) * row;
+    const double* cur = h;
+    for (int l = 0; l + 1 < nl; ++l) {
+      jvp_launch(f, W, nl, l, 0, cur, nullptr, h0, prb, nullptr, states + l * row, nullptr, nullptr, st);
+      cur = states + l * row;
+    }
+    const double* cw = w;
+    for (int l = nl - 1; l >= 0; --l) {
+      const double* hl = l == 0 ? h : states + (l - 1) * row;
+      double* dst = l == 0 ? d_out_h : pp + (l & 1) * row;
+      pgrad_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, cw, part, d_grad, d_out_init, l != nl - 1, st);
+      vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, cw, loc, C, nullptr, dst, nullptr, st);
+      cw = dst;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// backward of psignn_mlp2_f64: y = W2 relu(W1 x + b1) + b2.  One row per lane, chunks of PG_ROWS rows, the same two-stage sum.
+// round 1: gh 0..15 | x 16 .. 16 + din, 1        round 2: gy 0..15 | relu(pre) 16 .. 16 + hid, 1
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PG_ROWS) void k_mlp2_f64_backward(const double* __restrict__ x, const double* __restrict__ gy, int64_t n,
+                                                               int din, int hid, int dout, const double* __restrict__ w1,
+                                                               const double* __restrict__ b1, const double* __restrict__ w2,
+                                                               double* __restrict__ gx, double* __restrict__ part) {
+  __shared__ double buf[PG_ROWS * PG_MLP_RS];
+  double* row = buf + threadIdx.x * PG_MLP_RS;
+  const int ps = hid * din + hid + dout * hid + dout;
+  double* pt = part + (int64_t)blockIdx.x * ps;
+  const int64_t i = (int64_t)blockIdx.x * PG_ROWS + threadIdx.x;
+  const bool live = i < n;
+  double xi[16], go[16], gh[16], rp[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    xi[k] = live && k < din ? x[i * din + k] : 0.0;
+    go[k] = live && k < dout ? gy[i * dout + k] : 0.0;
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    double s = 0.0, t = 0.0;
+    if (j < hid) {
+      s = b1[j];
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (k < din) s = fma(w1[j * din + k], xi[k], s);
+#pragma unroll
+      for (int o = 0; o < 16; ++o)
+        if (o < dout) t = fma(w2[o * hid + j], go[o], t);
+    }
+    rp[j] = live ? fmax(s, 0.0) : 0.0;
+    gh[j] = live && s > 0.0 ? t : 0.0;
+  }
+  if (gx && live) {
+    for (int k = 0; k < din; ++k) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (j < hid) s = fma(w1[j * din + k], gh[j], s);
+      gx[i * din + k] = s;
+    }
+  }
+  double a1[3] = {0.0, 0.0, 0.0}, a2[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    row[k] = gh[k];
+    row[16 + k] = xi[k];
+  }
+  row[16 + din] = 1.0;
+  __syncthreads();
+  pg_acc<PG_MLP_RS, 3>(buf, 0, 16, hid, din + 1, a1);
+  pg_put<3>(pt, 0, hid * din, hid, din + 1, a1);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    row[k] = go[k];
+    row[16 + k] = rp[k];
+  }
+  row[16 + hid] = 1.0;
+  __syncthreads();
+  pg_acc<PG_MLP_RS, 3>(buf, 0, 16, dout, hid + 1, a2);
+  pg_put<3>(pt, hid * din + hid, hid * din + hid + dout * hid, dout, hid + 1, a2);
+}
+
+extern "C" int64_t psignn_mlp2_f64_backward_workspace_doubles(int64_t n, int din, int hid, int dout) {
+  if (n < 0 || din < 1 || din > 16 || hid < 1 || hid > 16 || dout < 1 || dout > 16) return -1;
+  return cdiv(n, PG_ROWS) * (hid * din + hid + dout * hid + dout);
+}
+
+extern "C" int psignn_mlp2_f64_backward(const double* x, const double* gy, int64_t n, int din, int hid, int dout, const double* w1,
+                                        const double* b1, const double* w2, double* gx, double* gflat, double* work,
+                                        int64_t work_doubles, void* stream) {
+  ARG_CHECK(x && gy && w1 && b1 && w2 && gflat, "NULL argument");
+  ARG_CHECK(n >= 0 && din >= 1 && din <= 16 && hid >= 1 && hid <= 16 && dout >= 1 && dout <= 16, "bad sizes");
+  ARG_CHECK(gx != x && gx != gy, "gx must not alias x or gy");
+  const int rc = work_check(__func__, psignn_mlp2_f64_backward_workspace_doubles(n, din, hid, dout), work, work_doubles);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int ps = hid * din + hid + dout * hid + dout;
+  HIP_TRY(hipMemsetAsync(gflat, 0, sizeof(double) * ps, st));
+  if (n == 0) return PSIGNN_OK;
+  const int64_t nch = cdiv(n, PG_ROWS);
+  PROF_BYTES(n * 8 * (2 * din + dout) + nch * ps * 8);
+  LAUNCH("k_mlp2_f64_backward", st,
+         (k_mlp2_f64_backward<<<(unsigned)nch, PG_ROWS, 0, st>>>(x, gy, n, din, hid, dout, w1, b1, w2, gx, work)));
+  pg_reduce(work, nch, ps, ps, 0, 0, 0, gflat, st);
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}

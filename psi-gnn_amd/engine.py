@@ -7,6 +7,7 @@ device pointers.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 
 import numpy as np
@@ -1906,6 +1907,58 @@ def mlp2_64(x, w1, b1, w2, b2):
     return out
 
 
+def mlp2_64_backward(x, gy, w1, b1, w2, need_gx=True):
+    """Backward of ``mlp2_64`` in float64 (``psignn_mlp2_f64_backward``): (gx | None, gW1, gb1, gW2, gb2), the tuple of
+    ``mlp2_backward``.  Inputs of any float dtype are widened; per-chunk partials added in a fixed order, so deterministic."""
+    xc, gc = _f64c(x, "x"), _f64c(gy, "gy")
+    if (xc.dim() != 2 or gc.dim() != 2 or xc.shape[0] != gc.shape[0] or w1.shape[1] != xc.shape[1] or w2.shape[1] != w1.shape[0]
+            or gc.shape[1] != w2.shape[0] or b1.numel() != w1.shape[0]):
+        raise nat.NativeError(f"mlp2_64_backward: x {tuple(x.shape)}, gy {tuple(gy.shape)}, W1 {tuple(w1.shape)}, "
+                              f"W2 {tuple(w2.shape)} do not chain")
+    n, din = xc.shape
+    hid, dout = w1.shape[0], w2.shape[0]
+    l = nat.lib()
+    nw = int(l.psignn_mlp2_f64_backward_workspace_doubles(n, din, hid, dout))
+    if nw < 0:
+        raise nat.NativeError(f"mlp2_64_backward: sizes {din} -> {hid} -> {dout} are out of range (at most 16 each)")
+    dv = lambda t: t.detach().to(xc.device, torch.float64).contiguous()
+    w1, b1, w2 = dv(w1), dv(b1), dv(w2)
+    gx = torch.empty_like(xc) if need_gx else None
+    gflat = torch.empty(hid * din + hid + dout * hid + dout, dtype=torch.float64, device=xc.device)
+    work = torch.empty(nw, dtype=torch.float64, device=xc.device)
+    with torch.cuda.device(xc.device):
+        nat.check(l.psignn_mlp2_f64_backward(nat.ptr(xc), nat.ptr(gc), n, din, hid, dout, nat.ptr(w1), nat.ptr(b1), nat.ptr(w2),
+                                             nat.ptr(gx), nat.ptr(gflat), nat.ptr(work), nw, nat.stream_ptr(xc.device)),
+                  "psignn_mlp2_f64_backward")
+    o1, o2, o3 = hid * din, hid * din + hid, hid * din + hid + dout * hid
+    return gx, gflat[:o1].reshape(hid, din), gflat[o1:o2], gflat[o2:o3].reshape(dout, hid), gflat[o3:]
+
+
+def unpack_param_grads64(flat, n_layers=1, mixed=False):
+    """Name the entries of a flat float64 parameter gradient, the layout of ``pack_weights64`` (nothing padded, no fold slots):
+    the names of ``unpack_param_grads``."""
+    if not 1 <= int(n_layers) <= 64:
+        raise nat.NativeError(f"n_layers = {n_layers} is out of range")
+    p = 3 if mixed else 2
+    cat, ein, ncat = 3 * D + p, 2 * D + 3, 2 * D + p + 2
+    mlp = lambda prefix, k: [(f"{prefix}.0.weight", (D, k)), (f"{prefix}.0.bias", (D,)), (f"{prefix}.2.weight", (D, D)),
+                             (f"{prefix}.2.bias", (D,))]
+    items = [("laynorm.weight", (D,)), ("laynorm.bias", (D,)), ("alpha.0.weight", (1, cat)), ("alpha.0.bias", (1,))]
+    for k in range(int(n_layers)):
+        items += mlp(f"phi_to_list.{k}.mlp.mlp", ein) + mlp(f"phi_from_list.{k}.mlp.mlp", ein) + mlp(f"update_list.{k}.mlp", cat)
+    if mixed:
+        items += mlp("phi_neumann.mlp.mlp", ein) + mlp("update_neumann.mlp", ncat)
+    size = sum(math.prod(shape) for _, shape in items)
+    if flat.numel() != size:
+        raise nat.NativeError(f"flat gradient has {flat.numel()} entries, expected {size}")
+    out, o = {}, 0
+    for name, shape in items:
+        n = math.prod(shape)
+        out[name] = flat[o:o + n].reshape(shape)
+        o += n
+    return out
+
+
 class FixedPointMap64:
     """``H -> f(H, H_init, batch)`` in float64 on the device: (N, 10) float64 -> (N, 10) float64 in the caller's numbering, on
     tiled and untiled plans alike.  ``edge_attr``: the batch's (E, 3) array in ``edge_index`` order, float32 (widened exactly) or
@@ -1997,6 +2050,29 @@ class FixedPointMap64:
                                                nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(Wc), nat.ptr(Ac), nat.ptr(out),
                                                nat.ptr(work), n, nat.stream_ptr(self.device)), "psignn_f64_vjp")
         return out
+
+    def param_vjp(self, H, Wv, with_init=True):
+        """What ``loss.backward()`` leaves in the ``deqdss.f`` parameters for new_H = f(H) with cotangent Wv, in float64
+        (``psignn_f64_param_vjp``; dirichlet/psignn/model.py:203-225, mixed likewise): ({name: float64 grad}, ``J_f(H)^T Wv``,
+        ``Wv^T df/dH_init`` | None), the names those of ``FixedPointMap.param_vjp_init``.  H, Wv: (N, 10), float32 (widened exactly)
+        or float64.  Both families, any depth, tiled or not; no atomics and a fixed summation order, so deterministic."""
+        Hc, Wc = self._states((H, "H"), (Wv, "Wv"))
+        l = nat.lib()
+        nl, mixed = self.weights.n_layers, self.weights.mixed
+        n = int(l.psignn_f64_param_vjp_workspace_doubles(self.handle, nl))
+        if n < 0:
+            raise nat.NativeError("psignn_f64_param_vjp_workspace_doubles refused the handle")
+        work = self._deriv_work.get("param_vjp")
+        if work is None or work.numel() != n:   # made on first use, like the products' workspaces
+            work = self._deriv_work["param_vjp"] = torch.empty(n, dtype=torch.float64, device=self.device)
+        grad = torch.empty(int(l.psignn_f64_weights_size(int(mixed), nl)), dtype=torch.float64, device=self.device)
+        out = torch.empty_like(Hc)
+        g_init = torch.empty_like(Hc) if with_init else None
+        with torch.cuda.device(self.device):
+            nat.check(l.psignn_f64_param_vjp(self.handle, nat.ptr(self.wflat), nl, nat.ptr(Hc), nat.ptr(self.h0), nat.ptr(self.prb),
+                                             nat.ptr(self.nrm), nat.ptr(Wc), nat.ptr(grad), nat.ptr(out), nat.ptr(g_init),
+                                             nat.ptr(work), n, nat.stream_ptr(self.device)), "psignn_f64_param_vjp")
+        return unpack_param_grads64(grad, nl, mixed), out, g_init
 
 
 class DeviceBroyden64:
@@ -2171,3 +2247,34 @@ def adjoint64(batch, state_dict, h_star, grad, solver="gmres", eps=1e-11, m=50, 
         if sv is not None:
             sv.close()
         fmap.close()
+
+
+def implicit_grad64(batch, state_dict, h_star, grad, solver="gmres", eps=1e-11, m=50, max_products=2000, threshold=800, y=None):
+    """The implicit backward in float64 on the device, for any loss whose cotangent on ``f(h*)`` is ``grad``: the gradient with
+    respect to the ``deqdss.f.*`` parameters and the encoder parameters (dirichlet/psignn/model.py:203-225 and 370-392 in double
+    precision).  ``adjoint64``'s solve gives ``y`` (``y`` given: no solve, that ``y`` is used), then
+    ``FixedPointMap64.param_vjp(h_star, y)``, then ``mlp2_64_backward(batch.x, dH_init, encoder)``.  Returns ``{"grads": {full
+    state-dict name: float64 tensor}, "y", "dh" (``J_f(h*)^T y``), "adjoint": the solver's dictionary | None}``."""
+    if solver not in ("gmres", "broyden"):
+        raise nat.NativeError(f"adjoint64: solver must be 'gmres' or 'broyden', got {solver!r}")
+    nat.require_default_width(width_of(state_dict), "implicit_grad64")
+    n = int(batch.x.shape[0])
+    for t, name in ((h_star, "h_star"), (grad, "grad"), (y, "y")):
+        if t is not None and tuple(t.shape) != (n, D):
+            raise nat.NativeError(f"{name} has shape {tuple(t.shape)}, expected {(n, D)}")
+    adj = None
+    if y is None:
+        adj = adjoint64(batch, state_dict, h_star, grad, solver=solver, eps=eps, m=m, max_products=max_products, threshold=threshold)
+        y = adj["result"]
+    w = PackedWeights64(state_dict)
+    enc_names = [f"autoencoder.encoder.mlp.mlp.{i}.{p}" for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
+    enc = [state_dict[k] for k in enc_names]
+    h0 = mlp2_64(batch.x, *enc)
+    fmap = FixedPointMap64(plan_for(batch), w, h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
+    try:
+        named, dh, d_init = fmap.param_vjp(h_star, y)
+    finally:
+        fmap.close()
+    grads = {"deqdss.f." + k: t for k, t in named.items()}
+    grads.update(zip(enc_names, mlp2_64_backward(batch.x, d_init, *enc[:3], need_gx=False)[1:]))
+    return {"grads": grads, "y": y, "dh": dh, "adjoint": adj}
