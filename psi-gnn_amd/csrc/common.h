@@ -35,6 +35,16 @@ extern int g_knob_epoch;
       return PSIGNN_EHIP;                                                               \
     }                                                                                   \
   } while (0)
+// HIP_TRY with another way out: a create function passes the call that destroys its half-built handle and yields the code.
+// (Not HIP_TRY's body: an argument handed on to a second macro is expanded before # sees it, which would change the messages.)
+#define HIP_TRY_OR(expr, on_fail)                                                       \
+  do {                                                                                  \
+    hipError_t _e = (expr);                                                             \
+    if (_e != hipSuccess) {                                                             \
+      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+      return (on_fail);                                                                 \
+    }                                                                                   \
+  } while (0)
 
 #define ARG_CHECK(cond, msg)                                   \
   do {                                                         \

@@ -9,46 +9,14 @@
 //   * the arithmetic is written the way the reference writes it: per edge the whole message MLP([x_i | x_j | a_e]) -- first layer on the
 //     concatenated 23 inputs, ReLU, second layer with its bias -- and the messages summed per node; nothing is projected once per node,
 //     nothing is folded through the second layer, no transposed or packed weight block is read;
-//   * the weights are a flat float64 buffer in state-dict order (W64 below), not WLayout;
+//   * the weights are a flat float64 buffer in state-dict order (W64, f64_common.h), not WLayout;
 //   * gather form, one node per lane, in the CALLER's numbering: Phi_to sums over the node's in-edges (the plan's CSC), Phi_from and
 //     Phi_neumann over its out-edges (CSR), both without self loops and in the plan's canonical order (ascending edge id within a
 //     node) -- tiled and untiled plans alike, any degree, duplicate and one-directional edges;
 //   * no atomics: every sum has a fixed order, so the same call gives the same bits.
-// The handle keeps its own float64 copy of edge_attr in the order of those two lists.
-#include "common.h"
-#include "internal.h"
+// The handle (psignn_f64, f64_common.h) keeps its own float64 copy of edge_attr in the order of those two lists.
+#include "f64_common.h"
 #include <math.h>
-
-#if PSIGNN_D != 10
-#error "fgnn_f64.hip is part of the default-width library only"
-#endif
-
-// ---------------------------------------------------------------------------------------------
-// Weight layout (doubles): the deqdss.f.* tensors of the state dict, each nn.Linear (out, in) row-major, in this order
-//   laynorm.weight[10] laynorm.bias[10] alpha.0.weight[30+P] alpha.0.bias[1]
-//   per layer l: phi_to_list.l.mlp.mlp.{0.weight[10x23] 0.bias[10] 2.weight[10x10] 2.bias[10]}  phi_from_list.l.mlp.mlp.{same}
-//                update_list.l.mlp.{0.weight[10x(30+P)] 0.bias[10] 2.weight[10x10] 2.bias[10]}
-//   mixed only:  phi_neumann.mlp.mlp.{0.weight[10x23] 0.bias 2.weight 2.bias}  update_neumann.mlp.{0.weight[10x(22+P)] 0.bias 2.weight 2.bias}
-// P = 2 (dirichlet) / 3 (mixed).  No padding, nothing derived.
-// ---------------------------------------------------------------------------------------------
-template <int P>
-struct W64 {
-  static constexpr int CAT = 3 * D + P, EIN = 2 * D + 3, NCAT = 2 * D + P + 2;
-  static constexpr int LN_G = 0, LN_B = D, AL_W = 2 * D, AL_B = 2 * D + CAT, SHARED = 2 * D + CAT + 1;
-  static constexpr int PHI_W1 = 0, PHI_B1 = D * EIN, PHI_W2 = D * EIN + D, PHI_B2 = D * EIN + D + D * D, PHI_SZ = D * EIN + 2 * D + D * D;
-  static constexpr int UPD_B1 = D * CAT, UPD_W2 = D * CAT + D, UPD_B2 = D * CAT + D + D * D, UPD_SZ = D * CAT + 2 * D + D * D;
-  static constexpr int NEU_B1 = D * NCAT, NEU_W2 = D * NCAT + D, NEU_B2 = D * NCAT + D + D * D, NEU_SZ = D * NCAT + 2 * D + D * D;
-  static constexpr int LAYER = 2 * PHI_SZ + UPD_SZ;
-  __host__ __device__ static constexpr int layer(int l) { return SHARED + l * LAYER; }
-  __host__ __device__ static constexpr int total(int nl, bool mixed) { return SHARED + nl * LAYER + (mixed ? PHI_SZ + NEU_SZ : 0); }
-};
-static_assert(W64<2>::total(1, false) == 1193 && W64<3>::total(1, true) == 1924, "float64 weight layout at D = 10");
-
-struct psignn_f64 {
-  const psignn_plan* p = nullptr;   // borrowed: the plan outlives the handle
-  double *csr_attr = nullptr, *csc_attr = nullptr;   // (Ep, 3) each, in the order of the plan's csr_nbr / csc_nbr
-  double* pp[2] = {nullptr, nullptr};                // layer ping-pong of a multi-layer dirichlet block, made on first use
-};
 
 __global__ void k_f64_attr(int64_t Ep, const int32_t* __restrict__ eid, const void* __restrict__ attr, int is_f64,
                            double* __restrict__ out) {
@@ -288,8 +256,7 @@ static void f64_launch(const psignn_f64* f, const double* W, int nl, int l, int 
   PROF_BYTES(2 * p->Ep * (4 + 24 + 8 * D) + p->N * (16 * D + 8 * P + 17));
   LAUNCH("k_f64_layer", st,
          (k_f64_layer<P, MIXED><<<(unsigned)cdiv(p->N, 256), 256, 0, st>>>(
-             p->N, W, L::layer(l), L::layer(nl), apply_ln, p->csr_ptr, p->csr_nbr, f->csr_attr, p->csc_ptr, p->csc_nbr, f->csc_attr,
-             p->flags, h, h0, prb, nrm, out, done)));
+             p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, h0, prb, nrm, out, done)));
 }
 
 // f in the caller's numbering; done: see k_f64_layer

@@ -22,35 +22,9 @@
 // ReLU': 1 where the pre-activation is > 0 (torch's threshold_backward).
 // Every kernel takes the done flag of a solver (NULL: none) and returns at once when it is set: psignn_f64_vjp_gated is the product of
 // the float64 adjoint solves (solver_f64.hip, krylov_f64.hip), whose launches queued past the end of a solve or cycle change nothing.
-#include "common.h"
-#include "internal.h"
+// The weight layout W64 and the map handle psignn_f64 are those of fgnn_f64.hip: both files take them from f64_common.h.
+#include "f64_common.h"
 #include <math.h>
-
-#if PSIGNN_D != 10
-#error "fgnn_f64_deriv.hip is part of the default-width library only"
-#endif
-
-// The weight layout and the map handle of fgnn_f64.hip, repeated here token for token (that file is the pinned statement of the
-// float64 forward and stays as it is): the same class defined the same way in two translation units.  tests/test_host_f64_deriv.py
-// compares the two texts, so a field added there without being added here is a failing test, not a misread handle.
-template <int P>
-struct W64 {
-  static constexpr int CAT = 3 * D + P, EIN = 2 * D + 3, NCAT = 2 * D + P + 2;
-  static constexpr int LN_G = 0, LN_B = D, AL_W = 2 * D, AL_B = 2 * D + CAT, SHARED = 2 * D + CAT + 1;
-  static constexpr int PHI_W1 = 0, PHI_B1 = D * EIN, PHI_W2 = D * EIN + D, PHI_B2 = D * EIN + D + D * D, PHI_SZ = D * EIN + 2 * D + D * D;
-  static constexpr int UPD_B1 = D * CAT, UPD_W2 = D * CAT + D, UPD_B2 = D * CAT + D + D * D, UPD_SZ = D * CAT + 2 * D + D * D;
-  static constexpr int NEU_B1 = D * NCAT, NEU_W2 = D * NCAT + D, NEU_B2 = D * NCAT + D + D * D, NEU_SZ = D * NCAT + 2 * D + D * D;
-  static constexpr int LAYER = 2 * PHI_SZ + UPD_SZ;
-  __host__ __device__ static constexpr int layer(int l) { return SHARED + l * LAYER; }
-  __host__ __device__ static constexpr int total(int nl, bool mixed) { return SHARED + nl * LAYER + (mixed ? PHI_SZ + NEU_SZ : 0); }
-};
-static_assert(W64<2>::total(1, false) == 1193 && W64<3>::total(1, true) == 1924, "float64 weight layout at D = 10");
-
-struct psignn_f64 {
-  const psignn_plan* p = nullptr;   // borrowed: the plan outlives the handle
-  double *csr_attr = nullptr, *csc_attr = nullptr;   // (Ep, 3) each, in the order of the plan's csr_nbr / csc_nbr
-  double* pp[2] = {nullptr, nullptr};                // layer ping-pong of a multi-layer dirichlet block, made on first use
-};
 
 // ---------------------------------------------------------------------------------------------
 // per edge
@@ -187,6 +161,21 @@ __device__ __forceinline__ double d64_ln_stats(const double* y, double* yhat) {
 #pragma unroll
   for (int o = 0; o < D; ++o) yhat[o] = (y[o] - mu) * rs;
   return rs;
+}
+// gy, the cotangent of LayerNorm's output at y, back through it: gy <- rs (g - mean(g) - yhat mean(g yhat)), g = gamma * gy
+__device__ __forceinline__ void d64_ln_back(const double* __restrict__ gamma, const double* y, double* gy) {
+  double yhat[D], m1 = 0.0, m2 = 0.0;
+  const double rs = d64_ln_stats(y, yhat);
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    gy[o] *= gamma[o];
+    m1 += gy[o];
+    m2 = fma(gy[o], yhat[o], m2);
+  }
+  m1 /= D;
+  m2 /= D;
+#pragma unroll
+  for (int o = 0; o < D; ++o) gy[o] = rs * (gy[o] - m1 - yhat[o] * m2);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -387,18 +376,7 @@ __global__ __launch_bounds__(256) void k_f64_vjp_node(int64_t N, const double* _
           for (int k = 0; k < D; ++k) s = fma(Wn[L::NEU_W2 + o * D + k], fmax(pre[k], 0.0), s);
           y[o] = s;
         }
-        double yhat[D], m1 = 0.0, m2 = 0.0;
-        const double rs = d64_ln_stats(y, yhat);
-#pragma unroll
-        for (int o = 0; o < D; ++o) {
-          gy[o] *= W[L::LN_G + o];
-          m1 += gy[o];
-          m2 = fma(gy[o], yhat[o], m2);
-        }
-        m1 /= D;
-        m2 /= D;
-#pragma unroll
-        for (int o = 0; o < D; ++o) gy[o] = rs * (gy[o] - m1 - yhat[o] * m2);
+        d64_ln_back(W + L::LN_G, y, gy);
       }
       // y = N2 relu(N1 cat + n1) + n2
 #pragma unroll
@@ -445,20 +423,7 @@ __global__ __launch_bounds__(256) void k_f64_vjp_node(int64_t N, const double* _
         sv[o] = s;
         y[o] = x[o] + al * s;
       }
-      if (apply_ln) {
-        double yhat[D], m1 = 0.0, m2 = 0.0;
-        const double rs = d64_ln_stats(y, yhat);
-#pragma unroll
-        for (int o = 0; o < D; ++o) {
-          gy[o] *= W[L::LN_G + o];
-          m1 += gy[o];
-          m2 = fma(gy[o], yhat[o], m2);
-        }
-        m1 /= D;
-        m2 /= D;
-#pragma unroll
-        for (int o = 0; o < D; ++o) gy[o] = rs * (gy[o] - m1 - yhat[o] * m2);
-      }
+      if (apply_ln) d64_ln_back(W + L::LN_G, y, gy);
       // y = x + al * s: cotangents of the gate's pre-activation and of s
       double gal = 0.0;
 #pragma unroll
@@ -550,8 +515,6 @@ __global__ __launch_bounds__(256) void k_f64_vjp_edge(int64_t N, const double* _
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-#define F64_EDGES(f) (f)->p->csr_ptr, (f)->p->csr_nbr, (f)->csr_attr, (f)->p->csc_ptr, (f)->p->csc_nbr, (f)->csc_attr, (f)->p->flags
-
 // one layer's value (out_h, may be NULL) and, with v, its tangent (out_v)
 static void jvp_launch(const psignn_f64* f, const double* W, int nl, int l, int apply_ln, const double* h, const double* v,
                        const double* h0, const double* prb, const double* nrm, double* out_h, double* out_v, const int32_t* done,

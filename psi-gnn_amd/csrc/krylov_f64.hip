@@ -26,20 +26,12 @@
 //   k_gm64_backsolve, k_gm64_combine   z = R^{-1} g, y -= V z
 // Every kernel of the Arnoldi step, the product included, returns at once when the cycle's done flag is up, so what the host has
 // queued past the end of a cycle changes nothing.  The host reads the solve state after every check and the cycle flag every
-// poll_every Arnoldi steps: neither bits nor counts depend on poll_every.  Reductions: per-wave / per-block partials (shuffles in a
-// fixed order), then one block sums the partials in a fixed order.  No floating-point atomics: the same call gives the same bits.
+// poll_every Arnoldi steps: neither bits nor counts depend on poll_every.  Reductions (f64_common.h): per-wave / per-block partials,
+// then one block sums the partials, all in a fixed order: the same call gives the same bits.
 // Storage: vectors, basis (m + 1, M), coefficients and partials in float64.
-#include "common.h"
-#include "internal.h"
+#include "f64_common.h"
 #include "gmres_dense.h"
 #include <math.h>
-
-#if PSIGNN_D != 10
-#error "krylov_f64.hip is part of the default-width library only"
-#endif
-
-#define G64_TB 256
-#define G64_CHUNK 1024   // elements of a dots chunk: 8 x (64 lanes x 2 doubles)
 
 struct G64State {
   // the cycle (re-armed by k_ag64_check)
@@ -77,26 +69,6 @@ struct psignn_gmres64 {
   G64State* h_st = nullptr;   // pinned
 };
 
-// ------------------------------------------------------------------ reductions (fixed shape, fixed order)
-__device__ __forceinline__ double g64_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;   // lane 0 holds the sum
-}
-__device__ __forceinline__ double g64_block_sum(double v, double* sh /* 4 */) {
-  v = g64_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return s;
-}
-__device__ __forceinline__ double g64_final_sum(const double* __restrict__ part, int64_t n, double* sh) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += G64_TB) s += part[i];
-  return g64_block_sum(s, sh);
-}
-
 // ------------------------------------------------------------------ the head of a cycle
 __global__ void k_ag64_init(G64State* st) {
   G64State s{};
@@ -105,12 +77,12 @@ __global__ void k_ag64_init(G64State* st) {
 
 // r = f(y) - y -> r0 (first: y <- 0, f(y) = grad); partials of |r|^2 and |f(y)|^2.  M is even: a lane's two elements are both
 // inside or both outside.
-__global__ void __launch_bounds__(G64_TB) k_ag64_begin(int64_t M, int64_t nblk, const G64State* __restrict__ st, double* __restrict__ y,
+__global__ void __launch_bounds__(F64_TB) k_ag64_begin(int64_t M, int64_t nblk, const G64State* __restrict__ st, double* __restrict__ y,
                                                        const double* __restrict__ fy, const double* __restrict__ grad,
                                                        double* __restrict__ r0, double* __restrict__ part, int first) {
   if (st->solved) return;
   __shared__ double sh[4];
-  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   double sr = 0.0, sf = 0.0;
   if (e < M) {
     double2 f, a, r;
@@ -129,21 +101,21 @@ __global__ void __launch_bounds__(G64_TB) k_ag64_begin(int64_t M, int64_t nblk, 
     sr = fma(r.y, r.y, r.x * r.x);
     sf = fma(f.y, f.y, f.x * f.x);
   }
-  sr = g64_block_sum(sr, sh);
-  sf = g64_block_sum(sf, sh);
+  sr = f64_block_sum(sr, sh);
+  sf = f64_block_sum(sf, sh);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = sr;
     part[nblk + blockIdx.x] = sf;
   }
 }
 
-__global__ void __launch_bounds__(G64_TB) k_ag64_check(G64State* st, const double* __restrict__ part, int64_t nblk,
+__global__ void __launch_bounds__(F64_TB) k_ag64_check(G64State* st, const double* __restrict__ part, int64_t nblk,
                                                        double* __restrict__ g, double* __restrict__ rel_trace,
                                                        double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
   if (st->solved) return;
   __shared__ double sh[4];
-  const double sr = g64_final_sum(part, nblk, sh);
-  const double sf = g64_final_sum(part + nblk, nblk, sh);
+  const double sr = f64_final_sum(part, nblk, sh);
+  const double sf = f64_final_sum(part + nblk, nblk, sh);
   if (threadIdx.x != 0) return;
   const double nr = sqrt(sr), nf = sqrt(sf);
   const double rel = nr / (nf + 1e-9);
@@ -184,18 +156,18 @@ __global__ void __launch_bounds__(G64_TB) k_ag64_check(G64State* st, const doubl
 }
 
 // not gated by the flags: the cycle that ends the solve may be the lowest one
-__global__ void __launch_bounds__(G64_TB) k_ag64_keep(int64_t M, const G64State* __restrict__ st, const double* __restrict__ y,
+__global__ void __launch_bounds__(F64_TB) k_ag64_keep(int64_t M, const G64State* __restrict__ st, const double* __restrict__ y,
                                                       double* __restrict__ ybest) {
   if (!st->improved) return;
-  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   if (e < M) *(double2*)(ybest + e) = *(const double2*)(y + e);
 }
 
 // dst = src / *scale (|r| or |w|, a device double)
-__global__ void __launch_bounds__(G64_TB) k_gm64_scale(int64_t M, const G64State* __restrict__ st, const double* __restrict__ src,
+__global__ void __launch_bounds__(F64_TB) k_gm64_scale(int64_t M, const G64State* __restrict__ st, const double* __restrict__ src,
                                                        const double* __restrict__ scale, double* __restrict__ dst) {
   if (st->done) return;
-  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   if (e >= M) return;
   const double s = *scale;
   double2 v = *(const double2*)(src + e);
@@ -205,33 +177,22 @@ __global__ void __launch_bounds__(G64_TB) k_gm64_scale(int64_t M, const G64State
 }
 
 // ------------------------------------------------------------------ one Arnoldi step
-// A lane past the end of the last chunk reads the chunk's first element (always inside) and drops the value.
-template <bool FULL>
-__device__ __forceinline__ double2 g64_ld2(const double* __restrict__ p, int64_t e, int64_t base, int64_t M) {
-  if (FULL) return *(const double2*)(p + e);
-  const bool in = e < M;
-  const double2 v = *(const double2*)(p + (in ? e : base));
-  double2 r;
-  r.x = in ? v.x : 0.0;
-  r.y = in ? v.y : 0.0;
-  return r;
-}
-// Block = chunk of G64_CHUNK elements of w in LDS; wave q takes rows q, q + 4, ... of the `rows` first basis rows (row j + 1 is w
+// Block = chunk of F64_CHUNK elements of w in LDS; wave q takes rows q, q + 4, ... of the `rows` first basis rows (row j + 1 is w
 // itself: |w|^2 in the first pass).  A lane reads 8 double2 of the row (index (i * 64 + lane) * 2 within the chunk).
 // partD[row * nchunk + chunk].
 template <bool FULL>
 __device__ __forceinline__ void g64_dots_chunk(int64_t M, int64_t nchunk, int rows, const double* __restrict__ V,
                                                const double* __restrict__ w, double* __restrict__ partD, double2* s_w) {
-  const int64_t base = (int64_t)blockIdx.x * G64_CHUNK;
-  for (int i = threadIdx.x; i < G64_CHUNK / 2; i += G64_TB) s_w[i] = g64_ld2<FULL>(w, base + 2 * i, base, M);
+  const int64_t base = (int64_t)blockIdx.x * F64_CHUNK;
+  for (int i = threadIdx.x; i < F64_CHUNK / 2; i += F64_TB) s_w[i] = f64_ld2<FULL>(w, base + 2 * i, base, M);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll 1
-  for (int r = wave; r < rows; r += G64_TB / 64) {
+  for (int r = wave; r < rows; r += F64_TB / 64) {
     const double* Vr = V + (int64_t)r * M;
     double2 v[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = g64_ld2<FULL>(Vr, base + (int64_t)(i * 64 + lane) * 2, base, M);
+    for (int i = 0; i < 8; ++i) v[i] = f64_ld2<FULL>(Vr, base + (int64_t)(i * 64 + lane) * 2, base, M);
     double a = 0.0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -239,28 +200,28 @@ __device__ __forceinline__ void g64_dots_chunk(int64_t M, int64_t nchunk, int ro
       a = fma(v[i].x, x.x, a);
       a = fma(v[i].y, x.y, a);
     }
-    a = g64_wave_sum(a);
+    a = f64_wave_sum(a);
     if (lane == 0) partD[(int64_t)r * nchunk + blockIdx.x] = a;
   }
 }
-__global__ void __launch_bounds__(G64_TB) k_gm64_dots(int64_t M, int64_t nchunk, int j, int pass, const G64State* __restrict__ st,
+__global__ void __launch_bounds__(F64_TB) k_gm64_dots(int64_t M, int64_t nchunk, int j, int pass, const G64State* __restrict__ st,
                                                       const double* __restrict__ V, double* __restrict__ partD) {
   if (st->done || (pass && !st->reorth)) return;
-  __shared__ double2 s_w[G64_CHUNK / 2];
+  __shared__ double2 s_w[F64_CHUNK / 2];
   const double* w = V + (int64_t)(j + 1) * M;
   const int rows = j + 1 + (pass == 0);
-  if (((int64_t)blockIdx.x + 1) * G64_CHUNK <= M) g64_dots_chunk<true>(M, nchunk, rows, V, w, partD, s_w);
+  if (((int64_t)blockIdx.x + 1) * F64_CHUNK <= M) g64_dots_chunk<true>(M, nchunk, rows, V, w, partD, s_w);
   else g64_dots_chunk<false>(M, nchunk, rows, V, w, partD, s_w);
 }
 
 // one block per coefficient: pass 1 h_i (and |w|^2 from row j + 1), pass 2 the correction, added to h_i
-__global__ void __launch_bounds__(G64_TB) k_gm64_reduce(int64_t nchunk, int j, int pass, G64State* __restrict__ st,
+__global__ void __launch_bounds__(F64_TB) k_gm64_reduce(int64_t nchunk, int j, int pass, G64State* __restrict__ st,
                                                         const double* __restrict__ partD, double* __restrict__ coef,
                                                         double* __restrict__ hcol) {
   if (st->done || (pass && !st->reorth)) return;
   __shared__ double sh[4];
   const int r = blockIdx.x;
-  const double s = g64_final_sum(partD + (int64_t)r * nchunk, nchunk, sh);
+  const double s = f64_final_sum(partD + (int64_t)r * nchunk, nchunk, sh);
   if (threadIdx.x != 0) return;
   if (r == j + 1) {
     st->n0sq = s;
@@ -271,12 +232,12 @@ __global__ void __launch_bounds__(G64_TB) k_gm64_reduce(int64_t nchunk, int j, i
 }
 
 // w -= sum_{i <= j} coef_i v_i, two elements per lane, rows in ascending order; block partials of |w'|^2
-__global__ void __launch_bounds__(G64_TB) k_gm64_axpy(int64_t M, int j, int pass, const G64State* __restrict__ st,
+__global__ void __launch_bounds__(F64_TB) k_gm64_axpy(int64_t M, int j, int pass, const G64State* __restrict__ st,
                                                       double* __restrict__ V, const double* __restrict__ coef,
                                                       double* __restrict__ part) {
   if (st->done || (pass && !st->reorth)) return;
   __shared__ double sh[4];
-  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   double s = 0.0;
   if (e < M) {
     double2 acc = {0.0, 0.0};
@@ -294,14 +255,14 @@ __global__ void __launch_bounds__(G64_TB) k_gm64_axpy(int64_t M, int j, int pass
     *(double2*)w = x;
     s = fma(x.y, x.y, x.x * x.x);
   }
-  s = g64_block_sum(s, sh);
+  s = f64_block_sum(s, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-__global__ void __launch_bounds__(G64_TB) k_gm64_decide(G64State* st, const double* __restrict__ part, int64_t nblk) {
+__global__ void __launch_bounds__(F64_TB) k_gm64_decide(G64State* st, const double* __restrict__ part, int64_t nblk) {
   if (st->done) return;
   __shared__ double sh[4];
-  const double s = g64_final_sum(part, nblk, sh);
+  const double s = f64_final_sum(part, nblk, sh);
   if (threadIdx.x != 0) return;
   const int r = !(s >= 0.5 * st->n0sq);
   st->reorth = r;
@@ -309,12 +270,12 @@ __global__ void __launch_bounds__(G64_TB) k_gm64_decide(G64State* st, const doub
 }
 
 // One block: column j of the Hessenberg matrix and the least-squares update.  `part` holds |w|^2 of the last pass that ran.
-__global__ void __launch_bounds__(G64_TB) k_gm64_finish(G64State* st, const double* __restrict__ part, int64_t nblk, int j, int m,
+__global__ void __launch_bounds__(F64_TB) k_gm64_finish(G64State* st, const double* __restrict__ part, int64_t nblk, int j, int m,
                                                         double eta, double* __restrict__ hcol, double* __restrict__ R,
                                                         double* __restrict__ cs, double* __restrict__ sn, double* __restrict__ g) {
   if (st->done) return;
   __shared__ double sh[4];
-  const double s2 = g64_final_sum(part, nblk, sh);
+  const double s2 = f64_final_sum(part, nblk, sh);
   if (threadIdx.x != 0) return;
   const double hn = sqrt(s2);
   st->hn = hn;
@@ -335,9 +296,9 @@ __global__ void k_gm64_backsolve(const G64State* __restrict__ st, int m, const d
   gmd_backsolve(st->k, m + 1, R, g, z);
 }
 // y -= sum_{i < k} z_i v_i
-__global__ void __launch_bounds__(G64_TB) k_gm64_combine(int64_t M, const G64State* __restrict__ st, const double* __restrict__ V,
+__global__ void __launch_bounds__(F64_TB) k_gm64_combine(int64_t M, const G64State* __restrict__ st, const double* __restrict__ V,
                                                          const double* __restrict__ z, double* __restrict__ y) {
-  const int64_t e = ((int64_t)blockIdx.x * G64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   if (e >= M) return;
   const int k = st->k;
   double2 acc = {0.0, 0.0};
@@ -376,8 +337,8 @@ extern "C" int psignn_gmres64_create(psignn_gmres64_t** out, psignn_f64_t* f, in
   s->N = p->N;
   s->M = p->N * D;
   s->m = m;
-  s->nblk = cdiv(s->M, 2 * G64_TB);
-  s->nchunk = cdiv(s->M, G64_CHUNK);
+  s->nblk = cdiv(s->M, 2 * F64_TB);
+  s->nchunk = cdiv(s->M, F64_CHUNK);
   const size_t basis_bytes = (size_t)(m + 1) * (size_t)s->M * sizeof(double);
   if (hipMalloc((void**)&s->V, basis_bytes) != hipSuccess) {
     (void)hipGetLastError();   // the failed allocation is reported here, not by the next launch
@@ -391,26 +352,18 @@ extern "C" int psignn_gmres64_create(psignn_gmres64_t** out, psignn_f64_t* f, in
     psignn_gmres64_destroy(s);
     return code;
   };
-#define G64_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) {                                                                  \
-      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return fail(PSIGNN_EHIP);                                                              \
-    }                                                                                        \
-  } while (0)
-  G64_TRY(hipMalloc((void**)&s->vec, (size_t)3 * s->M * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->part, (size_t)2 * s->nblk * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->partD, (size_t)(m + 2) * s->nchunk * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->coef, (size_t)(m + 2) * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->hcol, (size_t)(m + 2) * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->R, (size_t)(m + 1) * m * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->cs, (size_t)(m + 1) * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->sn, (size_t)(m + 1) * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->g, (size_t)(m + 1) * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->z, (size_t)(m + 1) * sizeof(double)));
-  G64_TRY(hipMalloc((void**)&s->st, sizeof(G64State)));
-  G64_TRY(hipHostMalloc((void**)&s->h_st, sizeof(G64State)));
+  HIP_TRY_OR(hipMalloc((void**)&s->vec, (size_t)3 * s->M * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->part, (size_t)2 * s->nblk * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->partD, (size_t)(m + 2) * s->nchunk * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->coef, (size_t)(m + 2) * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->hcol, (size_t)(m + 2) * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->R, (size_t)(m + 1) * m * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->cs, (size_t)(m + 1) * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->sn, (size_t)(m + 1) * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->g, (size_t)(m + 1) * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->z, (size_t)(m + 1) * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->st, sizeof(G64State)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipHostMalloc((void**)&s->h_st, sizeof(G64State)), fail(PSIGNN_EHIP));
   *out = s;
   return PSIGNN_OK;
 }
@@ -464,13 +417,13 @@ extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W
     if (cycle > 0 && (rc = psignn_f64_vjp_gated(s->f, W, nl, h_star, h0, prb, nrm, y, grad, fy, work, work_doubles, nullptr, st)))
       return rc;
     PROF_BYTES(3 * M * 8);
-    LAUNCH("k_ag64_begin", st, (k_ag64_begin<<<g2, G64_TB, 0, st>>>(M, nblk, s->st, y, fy, grad, s->V, s->part, cycle == 0)));
-    LAUNCH("k_ag64_check", st, (k_ag64_check<<<1, G64_TB, 0, st>>>(s->st, s->part, nblk, s->g, s->rel_trace, s->abs_trace, s->cap, eps,
+    LAUNCH("k_ag64_begin", st, (k_ag64_begin<<<g2, F64_TB, 0, st>>>(M, nblk, s->st, y, fy, grad, s->V, s->part, cycle == 0)));
+    LAUNCH("k_ag64_check", st, (k_ag64_check<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, s->g, s->rel_trace, s->abs_trace, s->cap, eps,
                                                                   max_products, m)));
     PROF_BYTES(2 * M * 8);
-    LAUNCH("k_ag64_keep", st, (k_ag64_keep<<<g2, G64_TB, 0, st>>>(M, s->st, y, ybest)));
+    LAUNCH("k_ag64_keep", st, (k_ag64_keep<<<g2, F64_TB, 0, st>>>(M, s->st, y, ybest)));
     PROF_BYTES(2 * M * 8);
-    LAUNCH("k_gm64_scale", st, (k_gm64_scale<<<g2, G64_TB, 0, st>>>(M, s->st, s->V, &s->st->rnorm, s->V)));
+    LAUNCH("k_gm64_scale", st, (k_gm64_scale<<<g2, F64_TB, 0, st>>>(M, s->st, s->V, &s->st->rnorm, s->V)));
     HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(G64State), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (s->h_st->solved) break;
@@ -484,17 +437,17 @@ extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W
       if ((rc = product(s->V + (size_t)j * M, w, cycle_done))) return rc;
       for (int pass = 0; pass < 2; ++pass) {
         PROF_BYTES(((int64_t)j + 2 + (pass == 0)) * M * 8);
-        LAUNCH("k_gm64_dots", st, (k_gm64_dots<<<gc, G64_TB, 0, st>>>(M, s->nchunk, j, pass, s->st, s->V, s->partD)));
-        LAUNCH("k_gm64_reduce", st, (k_gm64_reduce<<<(unsigned)(j + 1 + (pass == 0)), G64_TB, 0, st>>>(s->nchunk, j, pass, s->st, s->partD,
+        LAUNCH("k_gm64_dots", st, (k_gm64_dots<<<gc, F64_TB, 0, st>>>(M, s->nchunk, j, pass, s->st, s->V, s->partD)));
+        LAUNCH("k_gm64_reduce", st, (k_gm64_reduce<<<(unsigned)(j + 1 + (pass == 0)), F64_TB, 0, st>>>(s->nchunk, j, pass, s->st, s->partD,
                                                                                                       s->coef, s->hcol)));
         PROF_BYTES(((int64_t)j + 3) * M * 8);
-        LAUNCH("k_gm64_axpy", st, (k_gm64_axpy<<<g2, G64_TB, 0, st>>>(M, j, pass, s->st, s->V, s->coef, s->part)));
-        if (pass == 0) LAUNCH("k_gm64_decide", st, (k_gm64_decide<<<1, G64_TB, 0, st>>>(s->st, s->part, nblk)));
+        LAUNCH("k_gm64_axpy", st, (k_gm64_axpy<<<g2, F64_TB, 0, st>>>(M, j, pass, s->st, s->V, s->coef, s->part)));
+        if (pass == 0) LAUNCH("k_gm64_decide", st, (k_gm64_decide<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk)));
       }
-      LAUNCH("k_gm64_finish", st, (k_gm64_finish<<<1, G64_TB, 0, st>>>(s->st, s->part, nblk, j, m, 0.5 * eps, s->hcol, s->R, s->cs, s->sn,
+      LAUNCH("k_gm64_finish", st, (k_gm64_finish<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, j, m, 0.5 * eps, s->hcol, s->R, s->cs, s->sn,
                                                                       s->g)));
       PROF_BYTES(2 * M * 8);
-      LAUNCH("k_gm64_scale", st, (k_gm64_scale<<<g2, G64_TB, 0, st>>>(M, s->st, w, &s->st->hn, w)));
+      LAUNCH("k_gm64_scale", st, (k_gm64_scale<<<g2, F64_TB, 0, st>>>(M, s->st, w, &s->st->hn, w)));
       if ((j + 1) % poll_every == 0 && j + 1 < steps) {
         HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(G64State), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -503,7 +456,7 @@ extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W
     }
     LAUNCH("k_gm64_backsolve", st, (k_gm64_backsolve<<<1, 64, 0, st>>>(s->st, m, s->R, s->g, s->z)));
     PROF_BYTES(((int64_t)m + 2) * M * 8);
-    LAUNCH("k_gm64_combine", st, (k_gm64_combine<<<g2, G64_TB, 0, st>>>(M, s->st, s->V, s->z, y)));
+    LAUNCH("k_gm64_combine", st, (k_gm64_combine<<<g2, F64_TB, 0, st>>>(M, s->st, s->V, s->z, y)));
   }
   HIP_TRY(hipGetLastError());
   const G64State& h = *s->h_st;

@@ -20,14 +20,11 @@
 //   k_cg_update  x += alpha p, r -= alpha q, z = r / diag, partials r.z and r.r
 //   k_cg_beta    beta, stop test |r| <= tol |b|, trace entry, iteration count                 (one block)
 // Every kernel returns at once when the done flag is set, so whatever the host has queued beyond the last iteration changes nothing:
-// result, n_iter and trace do not depend on poll_every.  Reductions: one partial per 256-row block (wave shuffles in a fixed order,
-// then the four waves in a fixed order), then one block sums the partials in a fixed order.  No floating-point atomics: the same call
-// gives the same bits.
-#include "common.h"
-#include "internal.h"
+// result, n_iter and trace do not depend on poll_every.  Reductions (f64_common.h): one partial per block of F64_TB = 256 rows (4
+// slices of 64: wave shuffles, then the four waves), then one block sums the partials, all in a fixed order: the same call gives the
+// same bits.
+#include "f64_common.h"
 #include <math.h>
-
-#define CG_TB 256   // threads per block: 4 slices of 64 rows, one partial sum per block
 
 struct CgState {
   double rz, pq, alpha, beta, rr, bb, bnorm, true_rr;
@@ -50,31 +47,6 @@ struct psignn_cg {
   double sym_defect = 0.0;
 };
 
-// ------------------------------------------------------------------ reductions (fixed shape, fixed order)
-__device__ __forceinline__ double cg_block_sum(double v, double* sh /* 4 */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return s;
-}
-__device__ __forceinline__ double cg_block_max(double v, double* sh /* 4 */) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-  __syncthreads();
-  return s;
-}
-// one block: the n block partials, each thread its stride in ascending order, then the block sum
-__device__ __forceinline__ double cg_final_sum(const double* __restrict__ part, int64_t n, double* sh) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += CG_TB) s += part[i];
-  return cg_block_sum(s, sh);
-}
 // the direction at one node from the previous direction and z -- the ONE expression both the node's own lane and every lane that
 // gathers the node as a column evaluate, so that all of them hold the same bits
 __device__ __forceinline__ double cg_dir(double beta, double p_old, double z) { return fma(beta, p_old, z); }
@@ -89,9 +61,9 @@ __global__ void k_cg_gather(int64_t E, const int32_t* __restrict__ eid, const vo
 }
 
 // depth[s] = longest FREE row of slice s (0 when all its rows are Dirichlet rows)
-__global__ void __launch_bounds__(CG_TB) k_cg_depth(int64_t N, int64_t n_slices, const uint8_t* __restrict__ flags,
-                                                    const int32_t* __restrict__ a_ptr, int32_t* __restrict__ depth) {
-  const int64_t i = (int64_t)blockIdx.x * CG_TB + threadIdx.x;
+__global__ void __launch_bounds__(F64_TB) k_cg_depth(int64_t N, int64_t n_slices, const uint8_t* __restrict__ flags,
+                                                     const int32_t* __restrict__ a_ptr, int32_t* __restrict__ depth) {
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
   int32_t len = 0;
   if (i < N && !(flags[i] & FLAG_DIRICHLET)) len = a_ptr[i + 1] - a_ptr[i];
 #pragma unroll
@@ -101,12 +73,12 @@ __global__ void __launch_bounds__(CG_TB) k_cg_depth(int64_t N, int64_t n_slices,
 }
 
 // one thread per ELL lane (n_slices * 64 of them, the tail past N included so that every slot is defined)
-__global__ void __launch_bounds__(CG_TB) k_cg_fill(int64_t N, int64_t n_slices, const uint8_t* __restrict__ flags,
-                                                   const int32_t* __restrict__ a_ptr, const int32_t* __restrict__ a_col,
-                                                   const double* __restrict__ csr_val, const int32_t* __restrict__ slice_off,
-                                                   double* __restrict__ ell_val, int32_t* __restrict__ ell_col,
-                                                   double* __restrict__ diag) {
-  const int64_t i = (int64_t)blockIdx.x * CG_TB + threadIdx.x;
+__global__ void __launch_bounds__(F64_TB) k_cg_fill(int64_t N, int64_t n_slices, const uint8_t* __restrict__ flags,
+                                                    const int32_t* __restrict__ a_ptr, const int32_t* __restrict__ a_col,
+                                                    const double* __restrict__ csr_val, const int32_t* __restrict__ slice_off,
+                                                    double* __restrict__ ell_val, int32_t* __restrict__ ell_col,
+                                                    double* __restrict__ diag) {
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
   const int64_t s = i >> 6;
   if (s >= n_slices) return;
   const int lane = (int)(i & 63);
@@ -140,12 +112,12 @@ __global__ void __launch_bounds__(CG_TB) k_cg_fill(int64_t N, int64_t n_slices, 
 // A run of one entry sums to that entry, so a matrix without repeated positions is judged by the same arithmetic as entry by entry.
 // Block partials of max |A_ij - A_ji| and max |A_ij|; bad |= 1 missing transposed position, 2 diagonal of a free row not > 0, 4 a
 // value that is not finite.
-__global__ void __launch_bounds__(CG_TB) k_cg_check(int64_t N, const uint8_t* __restrict__ flags, const int32_t* __restrict__ a_ptr,
-                                                    const int32_t* __restrict__ a_col, const double* __restrict__ csr_val,
-                                                    const double* __restrict__ diag, double* __restrict__ part_def,
-                                                    double* __restrict__ part_abs, int32_t* __restrict__ bad) {
+__global__ void __launch_bounds__(F64_TB) k_cg_check(int64_t N, const uint8_t* __restrict__ flags, const int32_t* __restrict__ a_ptr,
+                                                     const int32_t* __restrict__ a_col, const double* __restrict__ csr_val,
+                                                     const double* __restrict__ diag, double* __restrict__ part_def,
+                                                     double* __restrict__ part_abs, int32_t* __restrict__ bad) {
   __shared__ double sh[4];
-  const int64_t i = (int64_t)blockIdx.x * CG_TB + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
   double def = 0.0, amax = 0.0;
   int32_t b = 0;
   if (i < N && !(flags[i] & FLAG_DIRICHLET)) {
@@ -176,23 +148,23 @@ __global__ void __launch_bounds__(CG_TB) k_cg_check(int64_t N, const uint8_t* __
     }
   }
   if (b) atomicOr(bad, b);
-  def = cg_block_max(def, sh);
-  amax = cg_block_max(amax, sh);
+  def = f64_block_max(def, sh);
+  amax = f64_block_max(amax, sh);
   if (threadIdx.x == 0) {
     part_def[blockIdx.x] = def;
     part_abs[blockIdx.x] = amax;
   }
 }
-__global__ void __launch_bounds__(CG_TB) k_cg_check_fin(const double* __restrict__ part_def, const double* __restrict__ part_abs,
-                                                        int64_t nblk, double* __restrict__ out /* 2 */) {
+__global__ void __launch_bounds__(F64_TB) k_cg_check_fin(const double* __restrict__ part_def, const double* __restrict__ part_abs,
+                                                         int64_t nblk, double* __restrict__ out /* 2 */) {
   __shared__ double sh[4];
   double def = 0.0, amax = 0.0;
-  for (int64_t i = threadIdx.x; i < nblk; i += CG_TB) {
+  for (int64_t i = threadIdx.x; i < nblk; i += F64_TB) {
     def = fmax(def, part_def[i]);
     amax = fmax(amax, part_abs[i]);
   }
-  def = cg_block_max(def, sh);
-  amax = cg_block_max(amax, sh);
+  def = f64_block_max(def, sh);
+  amax = f64_block_max(amax, sh);
   if (threadIdx.x == 0) {
     out[0] = def;
     out[1] = amax;
@@ -212,13 +184,13 @@ __global__ void k_cg_load(int64_t N, const void* y, int y_is_f64, const double* 
 }
 
 // b = y_F - A_FD y_D, r = b - A_FF x_F, z = r / diag; partials b.b, r.r, r.z (planes 0, 1, 2)
-__global__ void __launch_bounds__(CG_TB) k_cg_begin(int64_t N, int64_t nblk, const int32_t* __restrict__ slice_off,
-                                                    const double* __restrict__ ell_val, const int32_t* __restrict__ ell_col,
-                                                    const uint8_t* __restrict__ flags, const double* __restrict__ diag,
-                                                    const double* __restrict__ yd, const double* __restrict__ x,
-                                                    double* __restrict__ r, double* __restrict__ z, double* __restrict__ part) {
+__global__ void __launch_bounds__(F64_TB) k_cg_begin(int64_t N, int64_t nblk, const int32_t* __restrict__ slice_off,
+                                                     const double* __restrict__ ell_val, const int32_t* __restrict__ ell_col,
+                                                     const uint8_t* __restrict__ flags, const double* __restrict__ diag,
+                                                     const double* __restrict__ yd, const double* __restrict__ x,
+                                                     double* __restrict__ r, double* __restrict__ z, double* __restrict__ part) {
   __shared__ double sh[4];
-  const int64_t i = (int64_t)blockIdx.x * CG_TB + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
   double bb = 0.0, rr = 0.0, rz = 0.0;
   if (i < N) {
     const double di = diag[i];
@@ -243,21 +215,21 @@ __global__ void __launch_bounds__(CG_TB) k_cg_begin(int64_t N, int64_t nblk, con
     r[i] = ri;
     z[i] = zi;
   }
-  bb = cg_block_sum(bb, sh);
-  rr = cg_block_sum(rr, sh);
-  rz = cg_block_sum(rz, sh);
+  bb = f64_block_sum(bb, sh);
+  rr = f64_block_sum(rr, sh);
+  rz = f64_block_sum(rz, sh);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = bb;
     part[nblk + blockIdx.x] = rr;
     part[2 * nblk + blockIdx.x] = rz;
   }
 }
-__global__ void __launch_bounds__(CG_TB) k_cg_begin_fin(CgState* st, const double* __restrict__ part, int64_t nblk, double tol,
-                                                        int max_iter, double* __restrict__ trace) {
+__global__ void __launch_bounds__(F64_TB) k_cg_begin_fin(CgState* st, const double* __restrict__ part, int64_t nblk, double tol,
+                                                         int max_iter, double* __restrict__ trace) {
   __shared__ double sh[4];
-  const double bb = cg_final_sum(part, nblk, sh);
-  const double rr = cg_final_sum(part + nblk, nblk, sh);
-  const double rz = cg_final_sum(part + 2 * nblk, nblk, sh);
+  const double bb = f64_final_sum(part, nblk, sh);
+  const double rr = f64_final_sum(part + nblk, nblk, sh);
+  const double rz = f64_final_sum(part + 2 * nblk, nblk, sh);
   if (threadIdx.x != 0) return;
   CgState s{};
   s.bb = bb;
@@ -282,14 +254,14 @@ __global__ void k_cg_zero_free(int64_t N, const CgState* __restrict__ st, const 
 }
 
 // ------------------------------------------------------------------ solve: one iteration
-__global__ void __launch_bounds__(CG_TB) k_cg_spmv(int64_t N, const CgState* __restrict__ st, const int32_t* __restrict__ slice_off,
-                                                   const double* __restrict__ ell_val, const int32_t* __restrict__ ell_col,
-                                                   const double* __restrict__ z, const double* __restrict__ p_old,
-                                                   double* __restrict__ p_new, double* __restrict__ q, double* __restrict__ part) {
+__global__ void __launch_bounds__(F64_TB) k_cg_spmv(int64_t N, const CgState* __restrict__ st, const int32_t* __restrict__ slice_off,
+                                                    const double* __restrict__ ell_val, const int32_t* __restrict__ ell_col,
+                                                    const double* __restrict__ z, const double* __restrict__ p_old,
+                                                    double* __restrict__ p_new, double* __restrict__ q, double* __restrict__ part) {
   if (st->done) return;
   __shared__ double sh[4];
   const double beta = st->beta;
-  const int64_t i = (int64_t)blockIdx.x * CG_TB + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
   double pq = 0.0;
   if (i < N) {
     const int lane = (int)(i & 63);
@@ -305,26 +277,26 @@ __global__ void __launch_bounds__(CG_TB) k_cg_spmv(int64_t N, const CgState* __r
     q[i] = acc;
     pq = pi * acc;
   }
-  pq = cg_block_sum(pq, sh);
+  pq = f64_block_sum(pq, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = pq;
 }
-__global__ void __launch_bounds__(CG_TB) k_cg_alpha(CgState* st, const double* __restrict__ part, int64_t nblk) {
+__global__ void __launch_bounds__(F64_TB) k_cg_alpha(CgState* st, const double* __restrict__ part, int64_t nblk) {
   if (st->done) return;
   __shared__ double sh[4];
-  const double pq = cg_final_sum(part, nblk, sh);
+  const double pq = f64_final_sum(part, nblk, sh);
   if (threadIdx.x != 0) return;
   st->pq = pq;
   if (pq > 0.0) st->alpha = st->rz / pq;
   else st->breakdown = st->done = 1;   // p.Ap <= 0 (or NaN): not positive definite at working precision; the iterate stays as it is
 }
-__global__ void __launch_bounds__(CG_TB) k_cg_update(int64_t N, int64_t nblk, const CgState* __restrict__ st,
-                                                     const double* __restrict__ p, const double* __restrict__ q,
-                                                     const double* __restrict__ diag, double* __restrict__ x, double* __restrict__ r,
-                                                     double* __restrict__ z, double* __restrict__ part) {
+__global__ void __launch_bounds__(F64_TB) k_cg_update(int64_t N, int64_t nblk, const CgState* __restrict__ st,
+                                                      const double* __restrict__ p, const double* __restrict__ q,
+                                                      const double* __restrict__ diag, double* __restrict__ x, double* __restrict__ r,
+                                                      double* __restrict__ z, double* __restrict__ part) {
   if (st->done) return;
   __shared__ double sh[4];
   const double alpha = st->alpha;
-  const int64_t i = (int64_t)blockIdx.x * CG_TB + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
   double rz = 0.0, rr = 0.0;
   if (i < N) {
     const double di = diag[i];
@@ -338,19 +310,19 @@ __global__ void __launch_bounds__(CG_TB) k_cg_update(int64_t N, int64_t nblk, co
       rr = ri * ri;
     }
   }
-  rz = cg_block_sum(rz, sh);
-  rr = cg_block_sum(rr, sh);
+  rz = f64_block_sum(rz, sh);
+  rr = f64_block_sum(rr, sh);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = rz;
     part[nblk + blockIdx.x] = rr;
   }
 }
-__global__ void __launch_bounds__(CG_TB) k_cg_beta(CgState* st, const double* __restrict__ part, int64_t nblk, double tol, int max_iter,
-                                                   double* __restrict__ trace) {
+__global__ void __launch_bounds__(F64_TB) k_cg_beta(CgState* st, const double* __restrict__ part, int64_t nblk, double tol, int max_iter,
+                                                    double* __restrict__ trace) {
   if (st->done) return;
   __shared__ double sh[4];
-  const double rz = cg_final_sum(part, nblk, sh);
-  const double rr = cg_final_sum(part + nblk, nblk, sh);
+  const double rz = f64_final_sum(part, nblk, sh);
+  const double rr = f64_final_sum(part + nblk, nblk, sh);
   if (threadIdx.x != 0) return;
   const int32_t it = st->iter + 1;
   st->iter = it;
@@ -363,12 +335,12 @@ __global__ void __launch_bounds__(CG_TB) k_cg_beta(CgState* st, const double* __
 }
 
 // ------------------------------------------------------------------ solve: the true residual |(y - A x)_F|^2
-__global__ void __launch_bounds__(CG_TB) k_cg_true_res(int64_t N, const int32_t* __restrict__ slice_off,
-                                                       const double* __restrict__ ell_val, const int32_t* __restrict__ ell_col,
-                                                       const double* __restrict__ diag, const double* __restrict__ yd,
-                                                       const double* __restrict__ x, double* __restrict__ part) {
+__global__ void __launch_bounds__(F64_TB) k_cg_true_res(int64_t N, const int32_t* __restrict__ slice_off,
+                                                        const double* __restrict__ ell_val, const int32_t* __restrict__ ell_col,
+                                                        const double* __restrict__ diag, const double* __restrict__ yd,
+                                                        const double* __restrict__ x, double* __restrict__ part) {
   __shared__ double sh[4];
-  const int64_t i = (int64_t)blockIdx.x * CG_TB + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
   double tt = 0.0;
   if (i < N && diag[i] != 0.0) {
     const int lane = (int)(i & 63);
@@ -381,12 +353,12 @@ __global__ void __launch_bounds__(CG_TB) k_cg_true_res(int64_t N, const int32_t*
     const double t = yd[i] - acc;
     tt = t * t;
   }
-  tt = cg_block_sum(tt, sh);
+  tt = f64_block_sum(tt, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = tt;
 }
-__global__ void __launch_bounds__(CG_TB) k_cg_finish(CgState* st, const double* __restrict__ part, int64_t nblk) {
+__global__ void __launch_bounds__(F64_TB) k_cg_finish(CgState* st, const double* __restrict__ part, int64_t nblk) {
   __shared__ double sh[4];
-  const double tt = cg_final_sum(part, nblk, sh);
+  const double tt = f64_final_sum(part, nblk, sh);
   if (threadIdx.x == 0) st->true_rr = tt;
 }
 
@@ -408,8 +380,8 @@ extern "C" int psignn_cg_create(psignn_cg_t** out, const psignn_plan_t* p, const
   ARG_CHECK(p->E > 0 && p->a_ptr && p->a_col && p->a_eid && p->flags, "the plan holds no matrix structure");
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = p->N, E = p->E;
-  const int64_t n_slices = cdiv(N, 64), nblk = cdiv(N, CG_TB);
-  const unsigned gn = (unsigned)nblk, gl = (unsigned)cdiv(n_slices * 64, CG_TB);
+  const int64_t n_slices = cdiv(N, 64), nblk = cdiv(N, F64_TB);
+  const unsigned gn = (unsigned)nblk, gl = (unsigned)cdiv(n_slices * 64, F64_TB);
   DeviceArray<double> csr_val, chk;
   DeviceArray<int32_t> depth, bsum, bad;
   psignn_cg* s = new psignn_cg();
@@ -421,25 +393,17 @@ extern "C" int psignn_cg_create(psignn_cg_t** out, const psignn_plan_t* p, const
     psignn_cg_destroy(s);
     return code;
   };
-#define CG_TRY(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) {                                                                  \
-      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return fail(PSIGNN_EHIP);                                                              \
-    }                                                                                        \
-  } while (0)
-  CG_TRY(csr_val.alloc((size_t)E));
-  CG_TRY(chk.alloc(2));
-  CG_TRY(depth.alloc((size_t)n_slices));
-  CG_TRY(bsum.alloc((size_t)cdiv(n_slices, 1024) + 2));
-  CG_TRY(bad.alloc(1));
-  CG_TRY(hipMalloc((void**)&s->flags, (size_t)N));
-  CG_TRY(hipMalloc((void**)&s->slice_off, (size_t)(n_slices + 1) * sizeof(int32_t)));
-  CG_TRY(hipMalloc((void**)&s->vec, (size_t)7 * N * sizeof(double)));
-  CG_TRY(hipMalloc((void**)&s->part, (size_t)3 * nblk * sizeof(double)));
-  CG_TRY(hipMalloc((void**)&s->st, sizeof(CgState)));
-  CG_TRY(hipHostMalloc((void**)&s->h_st, sizeof(CgState)));
+  HIP_TRY_OR(csr_val.alloc((size_t)E), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(chk.alloc(2), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(depth.alloc((size_t)n_slices), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(bsum.alloc((size_t)cdiv(n_slices, 1024) + 2), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(bad.alloc(1), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->flags, (size_t)N), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->slice_off, (size_t)(n_slices + 1) * sizeof(int32_t)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->vec, (size_t)7 * N * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->part, (size_t)3 * nblk * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->st, sizeof(CgState)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipHostMalloc((void**)&s->h_st, sizeof(CgState)), fail(PSIGNN_EHIP));
   s->d = s->vec;
   s->yd = s->vec + N;
   s->r = s->vec + 2 * N;
@@ -447,32 +411,31 @@ extern "C" int psignn_cg_create(psignn_cg_t** out, const psignn_plan_t* p, const
   s->q = s->vec + 4 * N;
   s->p0 = s->vec + 5 * N;
   s->p1 = s->vec + 6 * N;
-  CG_TRY(hipMemcpyAsync(s->flags, p->flags, (size_t)N, hipMemcpyDeviceToDevice, st));
-  CG_TRY(hipMemsetAsync(bad.get(), 0, sizeof(int32_t), st));
-  k_cg_gather<<<(unsigned)cdiv(E, CG_TB), CG_TB, 0, st>>>(E, p->a_eid, d_a_ij, a_is_f64, csr_val.get());
-  k_cg_depth<<<gl, CG_TB, 0, st>>>(N, n_slices, s->flags, p->a_ptr, depth.get());
+  HIP_TRY_OR(hipMemcpyAsync(s->flags, p->flags, (size_t)N, hipMemcpyDeviceToDevice, st), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMemsetAsync(bad.get(), 0, sizeof(int32_t), st), fail(PSIGNN_EHIP));
+  k_cg_gather<<<(unsigned)cdiv(E, F64_TB), F64_TB, 0, st>>>(E, p->a_eid, d_a_ij, a_is_f64, csr_val.get());
+  k_cg_depth<<<gl, F64_TB, 0, st>>>(N, n_slices, s->flags, p->a_ptr, depth.get());
   if ((rc = psignn_exclusive_scan(depth.get(), n_slices, s->slice_off, bsum.get(), st)) != 0) return fail(rc);
   int32_t h_rows = 0;
-  CG_TRY(hipMemcpyAsync(&h_rows, s->slice_off + n_slices, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  CG_TRY(hipStreamSynchronize(st));
+  HIP_TRY_OR(hipMemcpyAsync(&h_rows, s->slice_off + n_slices, sizeof(int32_t), hipMemcpyDeviceToHost, st), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipStreamSynchronize(st), fail(PSIGNN_EHIP));
   if (h_rows < 0 || h_rows > E) {   // a slice is as deep as one of its rows, so the sum never exceeds E
     psignn_set_error("psignn_cg_create: internal: %d ELL slot-rows for %lld entries", h_rows, (long long)E);
     return fail(PSIGNN_EHIP);
   }
   s->ell_rows = h_rows;
   const size_t slots = (size_t)(h_rows > 0 ? h_rows : 1) * 64;
-  CG_TRY(hipMalloc((void**)&s->ell_val, slots * sizeof(double)));
-  CG_TRY(hipMalloc((void**)&s->ell_col, slots * sizeof(int32_t)));
-  k_cg_fill<<<gl, CG_TB, 0, st>>>(N, n_slices, s->flags, p->a_ptr, p->a_col, csr_val.get(), s->slice_off, s->ell_val, s->ell_col, s->d);
-  k_cg_check<<<gn, CG_TB, 0, st>>>(N, s->flags, p->a_ptr, p->a_col, csr_val.get(), s->d, s->part, s->part + nblk, bad.get());
-  k_cg_check_fin<<<1, CG_TB, 0, st>>>(s->part, s->part + nblk, nblk, chk.get());
+  HIP_TRY_OR(hipMalloc((void**)&s->ell_val, slots * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->ell_col, slots * sizeof(int32_t)), fail(PSIGNN_EHIP));
+  k_cg_fill<<<gl, F64_TB, 0, st>>>(N, n_slices, s->flags, p->a_ptr, p->a_col, csr_val.get(), s->slice_off, s->ell_val, s->ell_col, s->d);
+  k_cg_check<<<gn, F64_TB, 0, st>>>(N, s->flags, p->a_ptr, p->a_col, csr_val.get(), s->d, s->part, s->part + nblk, bad.get());
+  k_cg_check_fin<<<1, F64_TB, 0, st>>>(s->part, s->part + nblk, nblk, chk.get());
   double h_chk[2] = {0.0, 0.0};
   int32_t h_bad = 0;
-  CG_TRY(hipGetLastError());
-  CG_TRY(hipMemcpyAsync(h_chk, chk.get(), sizeof(h_chk), hipMemcpyDeviceToHost, st));
-  CG_TRY(hipMemcpyAsync(&h_bad, bad.get(), sizeof(h_bad), hipMemcpyDeviceToHost, st));
-  CG_TRY(hipStreamSynchronize(st));
-#undef CG_TRY
+  HIP_TRY_OR(hipGetLastError(), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMemcpyAsync(h_chk, chk.get(), sizeof(h_chk), hipMemcpyDeviceToHost, st), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMemcpyAsync(&h_bad, bad.get(), sizeof(h_bad), hipMemcpyDeviceToHost, st), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipStreamSynchronize(st), fail(PSIGNN_EHIP));
   s->sym_defect = h_chk[0];
   if (h_bad & 4) {
     psignn_set_error("psignn_cg_create: a_ij holds a value that is not finite on a free row");
@@ -514,11 +477,11 @@ extern "C" int psignn_cg_solve(psignn_cg_t* s, const void* d_y, int y_is_f64, co
     s->trace_cap = (int64_t)max_iter + 1;
   }
   double* x = d_sol;   // the iterate lives in the caller's result array
-  k_cg_load<<<g, CG_TB, 0, st>>>(N, d_y, y_is_f64, d_x0, s->flags, s->yd, x, s->p0);
-  LAUNCH("k_cg_begin", st, (k_cg_begin<<<g, CG_TB, 0, st>>>(N, nblk, s->slice_off, s->ell_val, s->ell_col, s->flags, s->d, s->yd, x,
+  k_cg_load<<<g, F64_TB, 0, st>>>(N, d_y, y_is_f64, d_x0, s->flags, s->yd, x, s->p0);
+  LAUNCH("k_cg_begin", st, (k_cg_begin<<<g, F64_TB, 0, st>>>(N, nblk, s->slice_off, s->ell_val, s->ell_col, s->flags, s->d, s->yd, x,
                                                             s->r, s->z, s->part)));
-  k_cg_begin_fin<<<1, CG_TB, 0, st>>>(s->st, s->part, nblk, tol, max_iter, s->trace);
-  k_cg_zero_free<<<g, CG_TB, 0, st>>>(N, s->st, s->flags, x);
+  k_cg_begin_fin<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, tol, max_iter, s->trace);
+  k_cg_zero_free<<<g, F64_TB, 0, st>>>(N, s->st, s->flags, x);
   // algorithmic bytes of an iteration: every ELL slot once (8 + 4), z and p_old read, p and q written; then p, q, diag, x, r read,
   // x, r, z written
   const int64_t spmv_bytes = s->ell_rows * 64 * 12 + 4 * N * 8, update_bytes = 8 * N * 8;
@@ -526,20 +489,20 @@ extern "C" int psignn_cg_solve(psignn_cg_t* s, const void* d_y, int y_is_f64, co
     const double* p_old = (it & 1) ? s->p1 : s->p0;
     double* p_new = (it & 1) ? s->p0 : s->p1;
     PROF_BYTES(spmv_bytes);
-    LAUNCH("k_cg_spmv", st, (k_cg_spmv<<<g, CG_TB, 0, st>>>(N, s->st, s->slice_off, s->ell_val, s->ell_col, s->z, p_old, p_new, s->q,
+    LAUNCH("k_cg_spmv", st, (k_cg_spmv<<<g, F64_TB, 0, st>>>(N, s->st, s->slice_off, s->ell_val, s->ell_col, s->z, p_old, p_new, s->q,
                                                             s->part)));
-    LAUNCH("k_cg_alpha", st, (k_cg_alpha<<<1, CG_TB, 0, st>>>(s->st, s->part, nblk)));
+    LAUNCH("k_cg_alpha", st, (k_cg_alpha<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk)));
     PROF_BYTES(update_bytes);
-    LAUNCH("k_cg_update", st, (k_cg_update<<<g, CG_TB, 0, st>>>(N, nblk, s->st, p_new, s->q, s->d, x, s->r, s->z, s->part)));
-    LAUNCH("k_cg_beta", st, (k_cg_beta<<<1, CG_TB, 0, st>>>(s->st, s->part, nblk, tol, max_iter, s->trace)));
+    LAUNCH("k_cg_update", st, (k_cg_update<<<g, F64_TB, 0, st>>>(N, nblk, s->st, p_new, s->q, s->d, x, s->r, s->z, s->part)));
+    LAUNCH("k_cg_beta", st, (k_cg_beta<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, tol, max_iter, s->trace)));
     if ((it + 1) % poll_every == 0 && it + 1 < max_iter) {
       HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(CgState), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       if (s->h_st->done) break;
     }
   }
-  LAUNCH("k_cg_true_res", st, (k_cg_true_res<<<g, CG_TB, 0, st>>>(N, s->slice_off, s->ell_val, s->ell_col, s->d, s->yd, x, s->part)));
-  k_cg_finish<<<1, CG_TB, 0, st>>>(s->st, s->part, nblk);
+  LAUNCH("k_cg_true_res", st, (k_cg_true_res<<<g, F64_TB, 0, st>>>(N, s->slice_off, s->ell_val, s->ell_col, s->d, s->yd, x, s->part)));
+  k_cg_finish<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(CgState), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));

@@ -32,18 +32,10 @@
 // The two sweeps are the two-pass form: each reads the 2 k M stored doubles once, 16 bytes per lane, consecutive lanes consecutive
 // addresses.  Sweep 1 gives a wave one pair at a time over a chunk of 1024 elements whose dx, dg, g_new sit in LDS, so one wave
 // reduction serves 16 KiB of streamed history; sweep 2 gives a lane two elements and walks the pairs in ascending order.
-// Reductions: per-wave / per-block partials (shuffles in a fixed order), then one block sums the partials in a fixed order.  No
-// floating-point atomics: the same call gives the same bits.
-#include "common.h"
-#include "internal.h"
+// Reductions (f64_common.h): per-wave / per-block partials, then one block sums the partials, all in a fixed order: the same call
+// gives the same bits.
+#include "f64_common.h"
 #include <math.h>
-
-#if PSIGNN_D != 10
-#error "solver_f64.hip is part of the default-width library only"
-#endif
-
-#define B64_TB 256
-#define B64_CHUNK 1024   // elements of a sweep-1 chunk: 8 x (64 lanes x 2 doubles)
 
 struct B64State {
   double lowest, lowest_abs, den, ck;
@@ -64,25 +56,6 @@ struct psignn_broyden64 {
   B64State* h_st = nullptr;            // pinned
 };
 
-// ------------------------------------------------------------------ reductions (fixed shape, fixed order)
-__device__ __forceinline__ double b64_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;   // lane 0 holds the sum
-}
-__device__ __forceinline__ double b64_block_sum(double v, double* sh /* 4 */) {
-  v = b64_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return s;
-}
-__device__ __forceinline__ double b64_final_sum(const double* __restrict__ part, int64_t n, double* sh) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += B64_TB) s += part[i];
-  return b64_block_sum(s, sh);
-}
 __device__ __forceinline__ double b64_nan0(double v) { return v != v ? 0.0 : v; }
 
 // ------------------------------------------------------------------ start
@@ -111,10 +84,10 @@ __global__ void k_b64_begin(int64_t M, const double* __restrict__ fx, const doub
 }
 
 // ------------------------------------------------------------------ one iteration
-__global__ void __launch_bounds__(B64_TB) k_b64_step(int64_t M, const B64State* __restrict__ st, const double* __restrict__ xo,
+__global__ void __launch_bounds__(F64_TB) k_b64_step(int64_t M, const B64State* __restrict__ st, const double* __restrict__ xo,
                                                      const double* __restrict__ upd, double* __restrict__ xn, double* __restrict__ dx) {
   if (st->done) return;
-  const int64_t e = ((int64_t)blockIdx.x * B64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   if (e >= M) return;   // M is even: a lane's two elements are both inside or both outside
   const double2 a = *(const double2*)(xo + e), u = *(const double2*)(upd + e);
   double2 n, d;
@@ -126,13 +99,13 @@ __global__ void __launch_bounds__(B64_TB) k_b64_step(int64_t M, const B64State* 
   *(double2*)(dx + e) = d;
 }
 
-__global__ void __launch_bounds__(B64_TB) k_b64_resid(int64_t M, int64_t nblk, const B64State* __restrict__ st,
+__global__ void __launch_bounds__(F64_TB) k_b64_resid(int64_t M, int64_t nblk, const B64State* __restrict__ st,
                                                       const double* __restrict__ fx, const double* __restrict__ xn,
                                                       const double* __restrict__ go, double* __restrict__ gn, double* __restrict__ dg,
                                                       double* __restrict__ part) {
   if (st->done) return;
   __shared__ double sh[4];
-  const int64_t e = ((int64_t)blockIdx.x * B64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   double gg = 0.0, ss = 0.0;
   if (e < M) {
     const double2 f = *(const double2*)(fx + e), x = *(const double2*)(xn + e), o = *(const double2*)(go + e);
@@ -147,20 +120,20 @@ __global__ void __launch_bounds__(B64_TB) k_b64_resid(int64_t M, int64_t nblk, c
     gg = fma(g.y, g.y, g.x * g.x);
     ss = fma(s1, s1, s0 * s0);
   }
-  gg = b64_block_sum(gg, sh);
-  ss = b64_block_sum(ss, sh);
+  gg = f64_block_sum(gg, sh);
+  ss = f64_block_sum(ss, sh);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = gg;
     part[nblk + blockIdx.x] = ss;
   }
 }
 
-__global__ void __launch_bounds__(B64_TB) k_b64_test(B64State* st, const double* __restrict__ part, int64_t nblk, double eps,
+__global__ void __launch_bounds__(F64_TB) k_b64_test(B64State* st, const double* __restrict__ part, int64_t nblk, double eps,
                                                      int threshold, double* __restrict__ rel_trace, double* __restrict__ abs_trace) {
   if (st->done) return;
   __shared__ double sh[4];
-  const double gg = b64_final_sum(part, nblk, sh);
-  const double ss = b64_final_sum(part + nblk, nblk, sh);
+  const double gg = f64_final_sum(part, nblk, sh);
+  const double ss = f64_final_sum(part + nblk, nblk, sh);
   if (threadIdx.x != 0) return;
   const int32_t nstep = st->nstep + 1;
   st->nstep = nstep;
@@ -212,43 +185,32 @@ __global__ void k_b64_keep(int64_t M, const B64State* __restrict__ st, int it, c
   if (e < M) *(double2*)(result + e) = *(const double2*)(xn + e);
 }
 
-// Sweep 1.  Block = chunk of B64_CHUNK elements; its dx, dg, g_new in LDS; wave w takes pairs w, w + 4, ...  A lane reads 8 double2
+// Sweep 1.  Block = chunk of F64_CHUNK elements; its dx, dg, g_new in LDS; wave w takes pairs w, w + 4, ...  A lane reads 8 double2
 // of U_j and 8 of V_j (index (i * 64 + lane) * 2 within the chunk).  partA[(j * 3 + q) * nchunk + chunk].
-// A lane past the end of the last chunk reads the chunk's first element (always inside) and drops the value.
-template <bool FULL>
-__device__ __forceinline__ double2 b64_ld2(const double* __restrict__ p, int64_t e, int64_t base, int64_t M) {
-  if (FULL) return *(const double2*)(p + e);
-  const bool in = e < M;
-  const double2 v = *(const double2*)(p + (in ? e : base));
-  double2 r;
-  r.x = in ? v.x : 0.0;
-  r.y = in ? v.y : 0.0;
-  return r;
-}
 template <bool FULL>
 __device__ __forceinline__ void b64_dots_chunk(int64_t M, int64_t nchunk, int k, const double* __restrict__ U,
                                                const double* __restrict__ V, const double* __restrict__ dx,
                                                const double* __restrict__ dg, const double* __restrict__ gn,
                                                double* __restrict__ partA, double2* s_dx, double2* s_dg, double2* s_g) {
-  const int64_t base = (int64_t)blockIdx.x * B64_CHUNK;
-  for (int i = threadIdx.x; i < B64_CHUNK / 2; i += B64_TB) {
+  const int64_t base = (int64_t)blockIdx.x * F64_CHUNK;
+  for (int i = threadIdx.x; i < F64_CHUNK / 2; i += F64_TB) {
     const int64_t e = base + 2 * i;
-    s_dx[i] = b64_ld2<FULL>(dx, e, base, M);
-    s_dg[i] = b64_ld2<FULL>(dg, e, base, M);
-    s_g[i] = b64_ld2<FULL>(gn, e, base, M);
+    s_dx[i] = f64_ld2<FULL>(dx, e, base, M);
+    s_dg[i] = f64_ld2<FULL>(dg, e, base, M);
+    s_g[i] = f64_ld2<FULL>(gn, e, base, M);
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll 1
-  for (int j = wave; j < k; j += B64_TB / 64) {
+  for (int j = wave; j < k; j += F64_TB / 64) {
     const double* Uj = U + (int64_t)j * M;
     const double* Vj = V + (int64_t)j * M;
     double2 u[8], v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int64_t e = base + (int64_t)(i * 64 + lane) * 2;
-      u[i] = b64_ld2<FULL>(Uj, e, base, M);
-      v[i] = b64_ld2<FULL>(Vj, e, base, M);
+      u[i] = f64_ld2<FULL>(Uj, e, base, M);
+      v[i] = f64_ld2<FULL>(Vj, e, base, M);
     }
     double a = 0.0, b = 0.0, c = 0.0;
 #pragma unroll
@@ -261,9 +223,9 @@ __device__ __forceinline__ void b64_dots_chunk(int64_t M, int64_t nchunk, int k,
       c = fma(v[i].x, g.x, c);
       c = fma(v[i].y, g.y, c);
     }
-    a = b64_wave_sum(a);
-    b = b64_wave_sum(b);
-    c = b64_wave_sum(c);
+    a = f64_wave_sum(a);
+    b = f64_wave_sum(b);
+    c = f64_wave_sum(c);
     if (lane == 0) {
       double* o = partA + (int64_t)j * 3 * nchunk + blockIdx.x;
       o[0] = a;
@@ -272,26 +234,26 @@ __device__ __forceinline__ void b64_dots_chunk(int64_t M, int64_t nchunk, int k,
     }
   }
 }
-__global__ void __launch_bounds__(B64_TB) k_b64_dots(int64_t M, int64_t nchunk, int k, const B64State* __restrict__ st,
+__global__ void __launch_bounds__(F64_TB) k_b64_dots(int64_t M, int64_t nchunk, int k, const B64State* __restrict__ st,
                                                      const double* __restrict__ U, const double* __restrict__ V,
                                                      const double* __restrict__ dx, const double* __restrict__ dg,
                                                      const double* __restrict__ gn, double* __restrict__ partA) {
   if (st->done) return;
-  __shared__ double2 s_dx[B64_CHUNK / 2], s_dg[B64_CHUNK / 2], s_g[B64_CHUNK / 2];
-  if (((int64_t)blockIdx.x + 1) * B64_CHUNK <= M) b64_dots_chunk<true>(M, nchunk, k, U, V, dx, dg, gn, partA, s_dx, s_dg, s_g);
+  __shared__ double2 s_dx[F64_CHUNK / 2], s_dg[F64_CHUNK / 2], s_g[F64_CHUNK / 2];
+  if (((int64_t)blockIdx.x + 1) * F64_CHUNK <= M) b64_dots_chunk<true>(M, nchunk, k, U, V, dx, dg, gn, partA, s_dx, s_dg, s_g);
   else b64_dots_chunk<false>(M, nchunk, k, U, V, dx, dg, gn, partA, s_dx, s_dg, s_g);
 }
 
 // one block per stored pair: a_j, b_j, c_j
-__global__ void __launch_bounds__(B64_TB) k_b64_coef(int64_t nchunk, const B64State* __restrict__ st, const double* __restrict__ partA,
+__global__ void __launch_bounds__(F64_TB) k_b64_coef(int64_t nchunk, const B64State* __restrict__ st, const double* __restrict__ partA,
                                                      double* __restrict__ coef) {
   if (st->done) return;
   __shared__ double sh[4];
   const int j = blockIdx.x;
   const double* p = partA + (int64_t)j * 3 * nchunk;
-  const double a = b64_final_sum(p, nchunk, sh);
-  const double b = b64_final_sum(p + nchunk, nchunk, sh);
-  const double c = b64_final_sum(p + 2 * nchunk, nchunk, sh);
+  const double a = f64_final_sum(p, nchunk, sh);
+  const double b = f64_final_sum(p + nchunk, nchunk, sh);
+  const double c = f64_final_sum(p + 2 * nchunk, nchunk, sh);
   if (threadIdx.x == 0) {
     coef[3 * j] = a;
     coef[3 * j + 1] = b;
@@ -301,14 +263,14 @@ __global__ void __launch_bounds__(B64_TB) k_b64_coef(int64_t nchunk, const B64St
 
 // Sweep 2.  Two elements per lane, pairs in ascending order.  V[k] <- vT (NaN -> 0), w, t; partials of vT . dg (the raw vT: a NaN
 // there makes u NaN, which k_b64_apply zeroes, as in the reference) and of V_k . g_new (the stored, cleaned vT).
-__global__ void __launch_bounds__(B64_TB) k_b64_comb(int64_t M, int64_t nblk, int k, const B64State* __restrict__ st,
+__global__ void __launch_bounds__(F64_TB) k_b64_comb(int64_t M, int64_t nblk, int k, const B64State* __restrict__ st,
                                                      const double* __restrict__ U, double* __restrict__ V,
                                                      const double* __restrict__ coef, const double* __restrict__ dx,
                                                      const double* __restrict__ dg, const double* __restrict__ gn,
                                                      double* __restrict__ w, double* __restrict__ t, double* __restrict__ part) {
   if (st->done) return;
   __shared__ double sh[4];
-  const int64_t e = ((int64_t)blockIdx.x * B64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   double den = 0.0, ck = 0.0;
   if (e < M) {
     double2 sa = {0.0, 0.0}, sb = {0.0, 0.0}, sc = {0.0, 0.0};
@@ -339,19 +301,19 @@ __global__ void __launch_bounds__(B64_TB) k_b64_comb(int64_t M, int64_t nblk, in
     den = fma(vt.y, d.y, vt.x * d.x);
     ck = fma(vc.y, g.y, vc.x * g.x);
   }
-  den = b64_block_sum(den, sh);
-  ck = b64_block_sum(ck, sh);
+  den = f64_block_sum(den, sh);
+  ck = f64_block_sum(ck, sh);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = den;
     part[nblk + blockIdx.x] = ck;
   }
 }
 
-__global__ void __launch_bounds__(B64_TB) k_b64_den(B64State* st, const double* __restrict__ part, int64_t nblk) {
+__global__ void __launch_bounds__(F64_TB) k_b64_den(B64State* st, const double* __restrict__ part, int64_t nblk) {
   if (st->done) return;
   __shared__ double sh[4];
-  const double den = b64_final_sum(part, nblk, sh);
-  const double ck = b64_final_sum(part + nblk, nblk, sh);
+  const double den = f64_final_sum(part, nblk, sh);
+  const double ck = f64_final_sum(part + nblk, nblk, sh);
   if (threadIdx.x == 0) {
     st->den = den;
     st->ck = ck;
@@ -359,10 +321,10 @@ __global__ void __launch_bounds__(B64_TB) k_b64_den(B64State* st, const double* 
 }
 
 // u = w / (vT . dg), NaN -> 0, -> U_k; update = -(t + c_k u): the new pair's term is the last of the sum, as in the stored order
-__global__ void __launch_bounds__(B64_TB) k_b64_apply(int64_t M, int k, const B64State* __restrict__ st, const double* __restrict__ w,
+__global__ void __launch_bounds__(F64_TB) k_b64_apply(int64_t M, int k, const B64State* __restrict__ st, const double* __restrict__ w,
                                                       const double* __restrict__ t, double* __restrict__ U, double* __restrict__ upd) {
   if (st->done) return;
-  const int64_t e = ((int64_t)blockIdx.x * B64_TB + threadIdx.x) * 2;
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
   if (e >= M) return;
   const double den = st->den, ck = st->ck;
   const double2 ww = *(const double2*)(w + e), tt = *(const double2*)(t + e);
@@ -397,8 +359,8 @@ extern "C" int psignn_broyden64_create(psignn_broyden64_t** out, psignn_f64_t* f
   s->N = p->N;
   s->M = p->N * D;
   s->threshold = threshold;
-  s->nblk = cdiv(s->M, 2 * B64_TB);
-  s->nchunk = cdiv(s->M, B64_CHUNK);
+  s->nblk = cdiv(s->M, 2 * F64_TB);
+  s->nchunk = cdiv(s->M, F64_CHUNK);
   const size_t pair_bytes = (size_t)2 * threshold * (size_t)s->M * sizeof(double);
   double *dU = nullptr, *dV = nullptr;
   const bool got = hipMalloc((void**)&dU, pair_bytes / 2) == hipSuccess && hipMalloc((void**)&dV, pair_bytes / 2) == hipSuccess;
@@ -416,23 +378,14 @@ extern "C" int psignn_broyden64_create(psignn_broyden64_t** out, psignn_f64_t* f
     psignn_broyden64_destroy(s);
     return code;
   };
-#define B64_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) {                                                                  \
-      psignn_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return fail(PSIGNN_EHIP);                                                              \
-    }                                                                                        \
-  } while (0)
-  B64_TRY(hipMalloc((void**)&s->vec, (size_t)10 * s->M * sizeof(double)));
-  B64_TRY(hipMalloc((void**)&s->part, (size_t)2 * s->nblk * sizeof(double)));
-  B64_TRY(hipMalloc((void**)&s->partA, (size_t)threshold * 3 * s->nchunk * sizeof(double)));
-  B64_TRY(hipMalloc((void**)&s->coef, (size_t)threshold * 3 * sizeof(double)));
-  B64_TRY(hipMalloc((void**)&s->rel_trace, (size_t)threshold * sizeof(double)));
-  B64_TRY(hipMalloc((void**)&s->abs_trace, (size_t)threshold * sizeof(double)));
-  B64_TRY(hipMalloc((void**)&s->st, sizeof(B64State)));
-  B64_TRY(hipHostMalloc((void**)&s->h_st, sizeof(B64State)));
-#undef B64_TRY
+  HIP_TRY_OR(hipMalloc((void**)&s->vec, (size_t)10 * s->M * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->part, (size_t)2 * s->nblk * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->partA, (size_t)threshold * 3 * s->nchunk * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->coef, (size_t)threshold * 3 * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->rel_trace, (size_t)threshold * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->abs_trace, (size_t)threshold * sizeof(double)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipMalloc((void**)&s->st, sizeof(B64State)), fail(PSIGNN_EHIP));
+  HIP_TRY_OR(hipHostMalloc((void**)&s->h_st, sizeof(B64State)), fail(PSIGNN_EHIP));
   *out = s;
   return PSIGNN_OK;
 }
@@ -450,7 +403,7 @@ static int b64_loop(psignn_broyden64* s, Op&& op, const double* x0, double eps, 
                     psignn_solve_info_t* h_info, double* h_rel_trace, double* h_abs_trace, hipStream_t st) {
   if (poll_every <= 0) poll_every = 16;
   const int64_t M = s->M, nblk = s->nblk;
-  const unsigned g1 = (unsigned)cdiv(M, B64_TB), g2 = (unsigned)nblk, gc = (unsigned)s->nchunk;
+  const unsigned g1 = (unsigned)cdiv(M, F64_TB), g2 = (unsigned)nblk, gc = (unsigned)s->nchunk;
   double* x[2] = {s->vec, s->vec + M};
   double* g[2] = {s->vec + 2 * M, s->vec + 3 * M};
   double *fx = s->vec + 4 * M, *dx = s->vec + 5 * M, *dg = s->vec + 6 * M, *upd = s->vec + 7 * M, *w = s->vec + 8 * M, *t = s->vec + 9 * M;
@@ -461,29 +414,29 @@ static int b64_loop(psignn_broyden64* s, Op&& op, const double* x0, double eps, 
     HIP_TRY(hipMemsetAsync(x[1], 0, (size_t)M * sizeof(double), st));
     x0 = x[1];
   }
-  k_b64_load<<<g1, B64_TB, 0, st>>>(M, x0, x[0], result);
+  k_b64_load<<<g1, F64_TB, 0, st>>>(M, x0, x[0], result);
   if ((rc = op(x[0], fx, nullptr))) return rc;
-  k_b64_begin<<<g1, B64_TB, 0, st>>>(M, fx, x[0], g[0], upd);
+  k_b64_begin<<<g1, F64_TB, 0, st>>>(M, fx, x[0], g[0], upd);
   for (int it = 1; it <= s->threshold; ++it) {
     const int o = (it - 1) & 1, n = it & 1, k = it - 1;
     PROF_BYTES(4 * M * 8);
-    LAUNCH("k_b64_step", st, (k_b64_step<<<g2, B64_TB, 0, st>>>(M, s->st, x[o], upd, x[n], dx)));
+    LAUNCH("k_b64_step", st, (k_b64_step<<<g2, F64_TB, 0, st>>>(M, s->st, x[o], upd, x[n], dx)));
     if ((rc = op(x[n], fx, done))) return rc;
     PROF_BYTES(5 * M * 8);
-    LAUNCH("k_b64_resid", st, (k_b64_resid<<<g2, B64_TB, 0, st>>>(M, nblk, s->st, fx, x[n], g[o], g[n], dg, s->part)));
-    LAUNCH("k_b64_test", st, (k_b64_test<<<1, B64_TB, 0, st>>>(s->st, s->part, nblk, eps, s->threshold, s->rel_trace, s->abs_trace)));
-    k_b64_keep<<<g2, B64_TB, 0, st>>>(M, s->st, it, x[n], result);
+    LAUNCH("k_b64_resid", st, (k_b64_resid<<<g2, F64_TB, 0, st>>>(M, nblk, s->st, fx, x[n], g[o], g[n], dg, s->part)));
+    LAUNCH("k_b64_test", st, (k_b64_test<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, eps, s->threshold, s->rel_trace, s->abs_trace)));
+    k_b64_keep<<<g2, F64_TB, 0, st>>>(M, s->st, it, x[n], result);
     if (it < s->threshold) {   // the pair of the last allowed step is never used
       if (k > 0) {
         PROF_BYTES(((int64_t)2 * k + 3) * M * 8);
-        LAUNCH("k_b64_dots", st, (k_b64_dots<<<gc, B64_TB, 0, st>>>(M, s->nchunk, k, s->st, s->U, s->V, dx, dg, g[n], s->partA)));
-        LAUNCH("k_b64_coef", st, (k_b64_coef<<<(unsigned)k, B64_TB, 0, st>>>(s->nchunk, s->st, s->partA, s->coef)));
+        LAUNCH("k_b64_dots", st, (k_b64_dots<<<gc, F64_TB, 0, st>>>(M, s->nchunk, k, s->st, s->U, s->V, dx, dg, g[n], s->partA)));
+        LAUNCH("k_b64_coef", st, (k_b64_coef<<<(unsigned)k, F64_TB, 0, st>>>(s->nchunk, s->st, s->partA, s->coef)));
       }
       PROF_BYTES(((int64_t)2 * k + 6) * M * 8);
-      LAUNCH("k_b64_comb", st, (k_b64_comb<<<g2, B64_TB, 0, st>>>(M, nblk, k, s->st, s->U, s->V, s->coef, dx, dg, g[n], w, t, s->part)));
-      LAUNCH("k_b64_den", st, (k_b64_den<<<1, B64_TB, 0, st>>>(s->st, s->part, nblk)));
+      LAUNCH("k_b64_comb", st, (k_b64_comb<<<g2, F64_TB, 0, st>>>(M, nblk, k, s->st, s->U, s->V, s->coef, dx, dg, g[n], w, t, s->part)));
+      LAUNCH("k_b64_den", st, (k_b64_den<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk)));
       PROF_BYTES(4 * M * 8);
-      LAUNCH("k_b64_apply", st, (k_b64_apply<<<g2, B64_TB, 0, st>>>(M, k, s->st, w, t, s->U, upd)));
+      LAUNCH("k_b64_apply", st, (k_b64_apply<<<g2, F64_TB, 0, st>>>(M, k, s->st, w, t, s->U, upd)));
     }
     if (it % poll_every == 0 && it < s->threshold) {
       HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(B64State), hipMemcpyDeviceToHost, st));

@@ -30,11 +30,16 @@ hex60 (10 981) mixed       2.9e-16 / 8.9e-16     3.1e-16 / 4.4e-16     1.3e-15
 A ReLU mask differing between device and oracle would need a float64 pre-activation within ~1e-15 of zero; with ~1e6 of them that
 has probability ~1e-8, so no case is left out and no cap is used.
 """
+import importlib.util
+import os
+
+import numpy as np
 import pytest
 import torch
 
+import adjoint_gmres_ref as ref
 import limit_graphs as lg
-from conftest import load_case, load_weights, pkg, rel_l2
+from conftest import GOLDEN, ROOT, load_case, load_weights, pkg, rel_l2
 from oracle import psignn_oracle as orc
 from test_gpu_f64 import FIXTURES, Problem, _random_two_layer_mixed, fixture_problem, float64_default
 from test_gpu_plan_limits import _random_two_layer
@@ -160,3 +165,21 @@ def test_refusals_on_an_open_handle(dev):
     assert f"{need * 8} bytes" in lib.psignn_last_error().decode()
     assert vjp(1, H, x, None, out, need) == 0
     torch.cuda.synchronize(dev)
+
+
+# ----------------------------------------------------------------------------------------------------------------- 6
+def test_same_bits_as_the_recorded_build(dev):
+    """tests/golden/f64_deriv_parent.npz (scripts/record_f64_deriv_golden.py, recorded on the commit before W64, the handle and the
+    LayerNorm backward of csrc/fgnn_f64_deriv.hip were each stated once): J v, J^T w (with and without add), the J^T w of the
+    parameter VJP and the whole flat parameter gradient, on the three adjoint fixtures and the two-layer chain, bit for bit."""
+    spec = importlib.util.spec_from_file_location("record_f64_deriv_golden", os.path.join(ROOT, "scripts", "record_f64_deriv_golden.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    want = np.load(os.path.join(GOLDEN, "f64_deriv_parent.npz"))
+    assert tuple(rec.CASES)[:3] == ref.FIXTURES
+    seen = set()
+    for name in rec.CASES:
+        for key, got in rec.run_case(name, dev).items():
+            assert np.array_equal(got, want[f"{name}.{key}"]), (name, key)
+            seen.add(f"{name}.{key}")
+    assert seen == set(want.files)

@@ -153,6 +153,27 @@ def test_null_arguments_are_error_codes():
     lib.psignn_broyden64_destroy(None)
 
 
+def test_shared_definitions_live_in_one_header():
+    """``W64``, ``struct psignn_f64`` and the fixed-order reductions of the float64 path are defined once, in csrc/f64_common.h, and
+    every object file is rebuilt when that header changes: two translation units can never read the handle or the weights at
+    different offsets, or sum in different orders."""
+    csrc = os.path.join(ROOT, "psi-gnn_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    for head in ("template <int P>\nstruct W64 {", "struct psignn_f64 {"):
+        assert {f: t.count(head) for f, t in texts.items() if head in t} == {"f64_common.h": 1}, head
+    make = open(os.path.join(csrc, "Makefile")).read()
+    hdrs = re.search(r"^HDRS := (.*)$", make, re.M).group(1).split()
+    assert "f64_common.h" in hdrs
+    assert re.search(r"^%\.o: %\.hip \$\(HDRS\)$", make, re.M)
+    for f, t in texts.items():
+        if f.endswith(".hip"):
+            assert not re.search(r"\w+_(wave|block|final)_sum\((const )?double", t), f
+    assert len(re.findall(r"\w+_(?:wave|block|final)_sum\((?:const )?double", texts["f64_common.h"])) == 3
+    users = sorted(f for f, t in texts.items() if '#include "f64_common.h"' in t)
+    assert users == ["fgnn_f64.hip", "fgnn_f64_deriv.hip", "krylov_f64.hip", "poisson_cg.hip", "solver_f64.hip"]
+    assert "k_f64_pgrad" in texts["fgnn_f64_deriv.hip"]
+
+
 def test_python_signatures():
     eng = pkg("engine")
     sig = lambda f: inspect.signature(f).parameters

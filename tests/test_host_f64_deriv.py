@@ -91,17 +91,3 @@ def test_null_arguments_are_error_codes():
     assert "NULL" in lib.psignn_last_error().decode()
     assert lib.psignn_f64_deriv_workspace_doubles(None, 1, 0) == -1
     assert lib.psignn_f64_deriv_workspace_doubles(None, 1, 1) == -1
-
-
-def test_repeated_definitions_match_the_forward_file():
-    """csrc/fgnn_f64_deriv.hip repeats ``W64`` and ``struct psignn_f64`` of csrc/fgnn_f64.hip (one class, two translation units):
-    the two texts must stay identical, or the derivative kernels would read the handle and the weights at other offsets."""
-    src = lambda f: open(os.path.join(ROOT, "psi-gnn_amd", "csrc", f)).read()
-    fwd, der = src("fgnn_f64.hip"), src("fgnn_f64_deriv.hip")
-    for head in ("template <int P>\nstruct W64 {", "struct psignn_f64 {"):
-        blocks = []
-        for text in (fwd, der):
-            assert text.count(head) == 1, head
-            start = text.index(head)
-            blocks.append(text[start:text.index("\n};", start) + 3])
-        assert blocks[0] == blocks[1], head

@@ -161,24 +161,3 @@ def test_null_arguments_are_error_codes():
     assert q(0, 4, 10, 10) == 0 and q(1, 16, 16, 16) == q(128, 16, 16, 16) == 16 * 16 + 16 + 16 * 16 + 16
     assert q(129, 4, 10, 10) == 2 * (40 + 10 + 100 + 10)
     assert q(-1, 4, 10, 10) == -1 and q(5, 0, 10, 10) == -1 and q(5, 4, 17, 10) == -1 and q(5, 4, 10, 17) == -1
-
-
-def test_repeated_definitions_match_the_forward_file():
-    """Every translation unit that repeats ``W64`` / ``struct psignn_f64`` of csrc/fgnn_f64.hip repeats them token for token (the new
-    kernels live in csrc/fgnn_f64_deriv.hip, behind that file's copy), and each repeats them once."""
-    csrc = os.path.join(ROOT, "psi-gnn_amd", "csrc")
-    fwd = open(os.path.join(csrc, "fgnn_f64.hip")).read()
-    seen = 0
-    for f in sorted(os.listdir(csrc)):
-        if not f.endswith((".hip", ".h")) or f == "fgnn_f64.hip":
-            continue
-        text = open(os.path.join(csrc, f)).read()
-        for head in ("template <int P>\nstruct W64 {", "struct psignn_f64 {"):
-            if head not in text:
-                continue
-            seen += 1
-            assert text.count(head) == 1 and fwd.count(head) == 1, (f, head)
-            block = lambda t: t[t.index(head):t.index("\n};", t.index(head)) + 3]
-            assert block(text) == block(fwd), (f, head)
-    assert seen >= 2
-    assert "k_f64_pgrad" in open(os.path.join(csrc, "fgnn_f64_deriv.hip")).read()
