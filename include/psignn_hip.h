@@ -850,6 +850,29 @@ int psignn_f64_param_vjp(psignn_f64_t* f, const double* d_weights, int n_layers,
                          const double* d_prb, const double* d_normals /* NULL for dirichlet plans */, const double* d_w,
                          double* d_grad, double* d_out_h, double* d_out_init /* NULL: skip */, double* d_work, int64_t work_doubles,
                          void* stream);
+/* Doubles of d_work for psignn_f64_vjp_backward: N * 10 * (2 + 2 * cw) for (loc, C) of J^T v and their tangents (cw = 2, mixed 3),
+ * for a multi-layer dirichlet block N * 10 * (2 * (n_layers - 1) + 4) more (the layer states and their tangents, the ping-pongs of
+ * the cotangent and of its tangent), then ceil(N / chunk_rows) * psignn_f64_weights_size(mixed, 1) for the partials.  -1 for a NULL
+ * handle or n_layers < 1.
+ * replaces: autograd's saved tensors of the double backward, dirichlet/psignn/model.py:416-435. */
+int64_t psignn_f64_vjp_backward_workspace_doubles(const psignn_f64_t* f, int n_layers);
+/* Backward of the VJP in float64: for psi = <d_gbar, J_f(d_h)^T d_v> with d_gbar constant, d_grad (psignn_f64_weights_size(mixed,
+ * n_layers) doubles, the layout of d_weights) = d psi / d theta over every deqdss.f.* tensor, d_dh = d psi / d h, and d_jtv (may be
+ * NULL) = J_f(d_h)^T d_v, the bits of psignn_f64_vjp.  psi is the derivative along d_gbar of <d_v, f(h)>, so every cotangent of the
+ * reverse pass of psignn_f64_param_vjp travels with its tangent along dh = d_gbar: ReLU masks are constants of it, what remains is the
+ * curvature of the gate and of LayerNorm.  The parameter sums follow the rule above (chunks of chunk_rows rows in ascending order,
+ * partials added 64 at a time and then in ascending order, no floating-point atomics); a multi-layer dirichlet block is the chain
+ * forward with (h_k, t_k), t_0 = d_gbar, and backwards with (w_k, dw_k), alpha.0.* accumulating from the last layer to the first; a
+ * mixed block differentiates its last layer and leaves exact zeros in the earlier ones.  Both families, tiled or not, the caller's
+ * numbering; the same call gives the same bits.  d_dh and d_jtv alias none of d_h, d_v, d_gbar or each other; a d_work smaller than
+ * the query is PSIGNN_ENOMEM with a message naming the bytes.
+ * replaces: what loss.backward() does with the Jacobian regulariser, in double precision -- jac_loss_estimate,
+ *           dirichlet/psignn/model.py:416-435: autograd.grad(f0, z0, v, create_graph=True) and the backward of |v^T J|^2 / numel
+ *           (mixed/psignn/model.py likewise). */
+int psignn_f64_vjp_backward(psignn_f64_t* f, const double* d_weights, int n_layers, const double* d_h, const double* d_h_initial,
+                            const double* d_prb, const double* d_normals /* NULL for dirichlet plans */, const double* d_v,
+                            const double* d_gbar, double* d_grad, double* d_dh, double* d_jtv /* NULL: skip */, double* d_work,
+                            int64_t work_doubles, void* stream);
 /* Doubles of d_work for psignn_mlp2_f64_backward: ceil(n / 128) * (hid * din + hid + dout * hid + dout); -1 for sizes out of range.
  * replaces: autograd's saved tensors of Encoder / Decoder, dirichlet/psignn/model.py:370-392. */
 int64_t psignn_mlp2_f64_backward_workspace_doubles(int64_t n, int din, int hid, int dout);

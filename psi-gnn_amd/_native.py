@@ -230,6 +230,8 @@ SIGNATURES = {
     "psignn_f64_param_vjp_chunk_rows": (_INT, []),
     "psignn_f64_param_vjp_workspace_doubles": (_I64, [_P, _INT]),
     "psignn_f64_param_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "psignn_f64_vjp_backward_workspace_doubles": (_I64, [_P, _INT]),
+    "psignn_f64_vjp_backward": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "psignn_mlp2_f64_backward_workspace_doubles": (_I64, [_I64, _INT, _INT, _INT]),
     "psignn_mlp2_f64_backward": (_INT, [_P, _P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "psignn_prof_enable": (None, [_INT]),

@@ -1163,3 +1163,540 @@ extern "C" int psignn_mlp2_f64_backward(const double* x, const double* gy, int64
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
+
+// =============================================================================================
+// Backward of the VJP in float64: for a probe v and a constant gbar, psi(theta, h) = <gbar, J_f(h)^T v>; wanted are its gradient with
+// respect to every deqdss.f.* tensor and to h, and J^T v itself.
+//
+// replaces: the double backward loss.backward() runs for the Jacobian regulariser, in double precision -- jac_loss_estimate
+//           (dirichlet/psignn/model.py:416-435: autograd.grad(f0, z0, v, create_graph=True), then the backward of |v^T J|^2 / numel);
+//           mixed/psignn/model.py likewise.
+//
+// psi is the directional derivative along gbar of phi(theta, h) = <v, f(h)>, so its gradient is the tangent along dh = gbar of the
+// reverse pass above: every cotangent of pass A and of k_f64_pgrad travels with its tangent.  ReLU masks are constants of the tangent
+// (ReLU has no curvature), so what is left is the curvature of the gate (sigmoid x update) and of LayerNorm.
+//   k_f64_jr, per receiving node n in chunks of PG_ROWS rows: the node's forward with its tangent (d64_phi<true>), w_n and dw_n back
+//     through LayerNorm, gate and update (or update_neumann) with the product rule at every step; dloc[n], the tangent of the node-
+//     local part of J^T w; C[n] and dC[n], the cotangents of the message sums and their tangents; and the rounds of k_f64_pgrad, each
+//     run twice, dA (x) B then A (x) dB, into the same per-chunk partial row.
+//   pass B is linear in (loc, C) at fixed masks: k_f64_vjp_edge on (dloc, dC) is the tangent of J^T w.
+//   k_f64_pg_fold / k_f64_pg_final add the partial rows as they do for the first-order gradient.
+// A multi-layer dirichlet block is a chain: forward with k_f64_jvp_layer for (h_k, t_k), t_0 = gbar, then backwards with
+// (w_{k+1}, dw_{k+1}) -> (w_k, dw_k), w_L = v, dw_L = 0.  No atomics, a summation order that depends on the graph alone.
+// =============================================================================================
+// d64_ln_back with its tangent along dy: (gy, dgy) the cotangent of LayerNorm's output and its tangent, back through it at y.
+// yhat, dyh: the normalised row and its tangent (the factors of laynorm.weight's gradient).
+__device__ __forceinline__ void d64_ln_back_tan(const double* __restrict__ gamma, const double* y, const double* dy, double* gy,
+                                                double* dgy, double* yhat, double* dyh) {
+  const double rs = d64_ln_stats(y, yhat);
+  double a1 = 0.0, a2 = 0.0;
+#pragma unroll
+  for (int o = 0; o < D; ++o) a1 += dy[o];
+  a1 /= D;
+#pragma unroll
+  for (int o = 0; o < D; ++o) a2 = fma(yhat[o], dy[o] - a1, a2);
+  a2 /= D;
+#pragma unroll
+  for (int o = 0; o < D; ++o) dyh[o] = rs * ((dy[o] - a1) - yhat[o] * a2);
+  const double drs = -rs * rs * a2;   // d (var + eps)^(-1/2) = -rs^3 / 2 * dvar, dvar = 2 mean(yhat dy) / rs
+  double m1 = 0.0, m2 = 0.0, dm1 = 0.0, dm2 = 0.0;
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    gy[o] *= gamma[o];
+    dgy[o] *= gamma[o];
+    m1 += gy[o];
+    m2 = fma(gy[o], yhat[o], m2);
+    dm1 += dgy[o];
+    dm2 = fma(dgy[o], yhat[o], fma(gy[o], dyh[o], dm2));
+  }
+  m1 /= D;
+  m2 /= D;
+  dm1 /= D;
+  dm2 /= D;
+#pragma unroll
+  for (int o = 0; o < D; ++o) {
+    const double r = gy[o] - m1 - yhat[o] * m2;
+    const double dr = dgy[o] - dm1 - dyh[o] * m2 - yhat[o] * dm2;
+    gy[o] = rs * r;
+    dgy[o] = fma(drs, r, rs * dr);
+  }
+}
+
+// pg_edges with its tangent: per edge position two sub-rounds, dA (x) B then A (x) dB, in the row layout of pg_edges.  c, dc: the
+// lane's rows of C and dC (global; read only when act).
+__device__ __forceinline__ void jr_edges(const double* __restrict__ Wp, bool act, const double* x, const double* dx,
+                                         const double* __restrict__ cg, const double* __restrict__ dcg, const double* __restrict__ h,
+                                         const double* __restrict__ t, int32_t beg, int32_t end, const int32_t* __restrict__ nbr,
+                                         const double* __restrict__ attr, double* buf, double* row, double* pt, int base) {
+  using L = W64<2>;
+  double c[D], dc[D], q[D], dq[D], a1[2] = {0.0, 0.0}, a2[1] = {0.0};
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    c[k] = act ? cg[k] : 0.0;
+    dc[k] = act ? dcg[k] : 0.0;
+  }
+  d64_w2t(Wp, c, q);
+  d64_w2t(Wp, dc, dq);
+  for (int32_t j = 0;; ++j) {
+    const bool on = act && beg + j < end;
+    if (!__syncthreads_or(on)) break;   // also the barrier behind the previous round's reads
+    double xj[D], dxj[D], a[3], s[D], ds[D];
+    if (on) {
+      const int32_t i = beg + j;
+      const int64_t u = nbr[i];
+      d64_row(h, u, xj);
+      d64_row(t, u, dxj);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) a[k] = attr[3 * (int64_t)i + k];
+      d64_pre(Wp, x, xj, a, s);
+#pragma unroll
+      for (int o = 0; o < D; ++o) {
+        const double* w = Wp + L::PHI_W1 + o * L::EIN;
+        double r = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) r = fma(w[k], dx[k], r);
+#pragma unroll
+        for (int k = 0; k < D; ++k) r = fma(w[D + k], dxj[k], r);
+        ds[o] = s[o] > 0.0 ? r : 0.0;
+      }
+      // d qm (x) [x_i, x_j, a, 1]; dc (x) [relu(s), 1]
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        row[k] = s[k] > 0.0 ? dq[k] : 0.0;
+        row[10 + k] = x[k];
+        row[20 + k] = xj[k];
+        row[34 + k] = dc[k];
+        row[44 + k] = fmax(s[k], 0.0);
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) row[30 + k] = a[k];
+      row[33] = 1.0;
+      row[54] = 1.0;
+    } else {
+      for (int k = 0; k < 55; ++k) row[k] = 0.0;
+    }
+    __syncthreads();
+    pg_acc<PG_RS, 2>(buf, 0, 10, D, L::EIN + 1, a1);
+    pg_acc<PG_RS, 1>(buf, 34, 44, D, D + 1, a2);
+    __syncthreads();
+    if (on) {   // qm (x) [dx_i, dx_j, 0, 0]; c (x) [1[s > 0] ds, 0]
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        row[k] = s[k] > 0.0 ? q[k] : 0.0;
+        row[10 + k] = dx[k];
+        row[20 + k] = dxj[k];
+        row[34 + k] = c[k];
+        row[44 + k] = ds[k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) row[30 + k] = 0.0;
+      row[54] = 0.0;
+    }
+    __syncthreads();
+    pg_acc<PG_RS, 2>(buf, 0, 10, D, L::EIN + 1, a1);
+    pg_acc<PG_RS, 1>(buf, 34, 44, D, D + 1, a2);
+  }
+  pg_put<2>(pt, base + L::PHI_W1, base + L::PHI_B1, D, L::EIN + 1, a1);
+  pg_put<1>(pt, base + L::PHI_W2, base + L::PHI_B2, D, D + 1, a2);
+}
+
+// One layer at (h, t, w, dw): dloc (N, D), C and dC (N, CW) and the chunk's partial row of the parameter part.  dw NULL: zero.
+// ROWS: 0 every row (dirichlet plans); a mixed plan takes two passes, 1 the update rows (and zeros for every other row of dloc, C,
+// dC), then 2 the Neumann rows, each with a partial row of its own sections and zeros elsewhere.  One kind of row per pass keeps
+// the node's block on one code path and inside the register file: a value spilled inside a divergent region and read after it is
+// not safe for the lanes that sat the region out.
+template <int P, bool MIXED, int ROWS>
+__global__ __launch_bounds__(PG_ROWS) void k_f64_jr(int64_t N, const double* __restrict__ W, int lofs, int nofs, int apply_ln,
+                                                    const int32_t* __restrict__ csr_ptr, const int32_t* __restrict__ csr_nbr,
+                                                    const double* __restrict__ csr_attr, const int32_t* __restrict__ csc_ptr,
+                                                    const int32_t* __restrict__ csc_nbr, const double* __restrict__ csc_attr,
+                                                    const uint8_t* __restrict__ flags, const double* __restrict__ h,
+                                                    const double* __restrict__ t, const double* __restrict__ prb,
+                                                    const double* __restrict__ nrm, const double* __restrict__ w,
+                                                    const double* __restrict__ dw, double* __restrict__ C, double* __restrict__ dloc,
+                                                    double* __restrict__ dC, double* __restrict__ part) {
+  using L = W64<P>;
+  constexpr int CW = MIXED ? 3 * D : 2 * D;
+  static_assert(10 + L::CAT + 1 + 1 <= PG_RS && 10 + L::NCAT + 1 + 10 + D + 1 <= PG_RS && D == 10, "LDS row of the rounds");
+  __shared__ double buf[PG_ROWS * PG_RS];
+  double* row = buf + threadIdx.x * PG_RS;
+  double* pt = part + (int64_t)blockIdx.x * L::total(1, MIXED);
+  const int64_t n = (int64_t)blockIdx.x * PG_ROWS + threadIdx.x;
+  const uint8_t fl = n < N ? flags[n] : (uint8_t)FLAG_DIRICHLET;   // a row past the end gives what a Dirichlet row gives: nothing
+  static_assert(MIXED ? ROWS == 1 || ROWS == 2 : ROWS == 0, "a mixed plan takes the two passes, a dirichlet plan the one");
+  const bool neu_row = MIXED && (fl & FLAG_NEUMANN);
+  const bool live = !(fl & FLAG_DIRICHLET) && (ROWS == 0 || neu_row == (ROWS == 2));   // the rows of this pass
+  const bool neu = ROWS == 2 && live;
+  const bool upd = ROWS != 2 && live;
+  // the factors of the node rounds and their tangents (names as in k_f64_pgrad); lnA: d (w * yhat), lnB: dw.  Every round selects
+  // on live / upd / neu where it writes them: what a lane that skipped the block below holds in these registers is never read.
+  double x[D], dx[D], q[D], dq[D], cat[L::CAT], dcat[3 * D], g[D], dg[D], rp[D], drp[D], lnA[D], lnB[D], dgy[D], gal = 0.0, dgal = 0.0;
+  int32_t rb = 0, re = 0, cb = 0, ce = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = dx[k] = q[k] = dq[k] = g[k] = dg[k] = rp[k] = drp[k] = lnA[k] = lnB[k] = dgy[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < L::CAT; ++k) cat[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3 * D; ++k) dcat[k] = 0.0;
+  if (live) {
+    double gy[D], y[D], dy[D], sv[D], dsv[D];
+    unsigned mask = 0;
+    d64_row(h, n, x);
+    d64_row(t, n, dx);
+    d64_row(w, n, gy);
+#pragma unroll
+    for (int k = 0; k < D; ++k) dgy[k] = dw ? dw[n * D + k] : 0.0;
+    rb = csr_ptr[n], re = csr_ptr[n + 1], cb = csc_ptr[n], ce = csc_ptr[n + 1];
+    double al = 1.0, dal = 0.0;
+    const double* Wm = neu ? W + nofs + L::PHI_SZ : W + lofs + 2 * L::PHI_SZ;   // W1 | b1 | W2 | b2 of the row's MLP
+    int ncat, ob1, ow2, ob2;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      cat[k] = x[k];
+      dcat[k] = dx[k];
+    }
+    if (neu) {
+      d64_phi<true>(W + nofs, x, dx, h, t, rb, re, csr_nbr, csr_attr, cat + D, dcat + D);
+#pragma unroll
+      for (int k = 0; k < P; ++k) cat[2 * D + k] = prb[n * P + k];
+      cat[2 * D + P] = nrm[2 * n];
+      cat[2 * D + P + 1] = nrm[2 * n + 1];
+      ncat = L::NCAT, ob1 = L::NEU_B1, ow2 = L::NEU_W2, ob2 = L::NEU_B2;
+    } else {
+      d64_phi<true>(W + lofs, x, dx, h, t, cb, ce, csc_nbr, csc_attr, cat + D, dcat + D);
+      d64_phi<true>(W + lofs + L::PHI_SZ, x, dx, h, t, rb, re, csr_nbr, csr_attr, cat + 2 * D, dcat + 2 * D);
+#pragma unroll
+      for (int k = 0; k < P; ++k) cat[3 * D + k] = prb[n * P + k];
+      al = W[L::AL_B];
+#pragma unroll
+      for (int k = 0; k < L::CAT; ++k) al = fma(W[L::AL_W + k], cat[k], al);
+      al = 1.0 / (1.0 + exp(-al));
+#pragma unroll
+      for (int k = 0; k < 3 * D; ++k) dal = fma(W[L::AL_W + k], dcat[k], dal);
+      dal *= al * (1.0 - al);
+      ncat = L::CAT, ob1 = L::UPD_B1, ow2 = L::UPD_W2, ob2 = L::UPD_B2;
+    }
+    const int nd = neu ? 2 * D : 3 * D;   // inputs of the MLP that carry a tangent
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+      double s = Wm[ob1 + o], r = 0.0;
+#pragma unroll
+      for (int k = 0; k < L::CAT; ++k)
+        if (k < ncat) s = fma(Wm[o * ncat + k], cat[k], s);
+#pragma unroll
+      for (int k = 0; k < 3 * D; ++k)
+        if (k < nd) r = fma(Wm[o * ncat + k], dcat[k], r);
+      if (s > 0.0) mask |= 1u << o;
+      rp[o] = fmax(s, 0.0);
+      drp[o] = s > 0.0 ? r : 0.0;
+    }
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+      double s = Wm[ob2 + o], r = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        s = fma(Wm[ow2 + o * D + k], rp[k], s);
+        r = fma(Wm[ow2 + o * D + k], drp[k], r);
+      }
+      sv[o] = s;
+      dsv[o] = r;
+      y[o] = neu ? s : x[o] + al * s;
+      dy[o] = neu ? r : dx[o] + dal * s + al * r;
+    }
+    if (apply_ln) {
+      double yhat[D], dyh[D];
+#pragma unroll
+      for (int o = 0; o < D; ++o) {
+        lnA[o] = gy[o];
+        lnB[o] = dgy[o];
+      }
+      d64_ln_back_tan(W + L::LN_G, y, dy, gy, dgy, yhat, dyh);
+#pragma unroll
+      for (int o = 0; o < D; ++o) lnA[o] = fma(lnB[o], yhat[o], lnA[o] * dyh[o]);
+    }
+    if (!neu) {   // y = x + al * s: the gate's pre-activation gets (gy . s) al (1 - al)
+      double dot = 0.0, ddot = 0.0;
+#pragma unroll
+      for (int o = 0; o < D; ++o) {
+        dot = fma(gy[o], sv[o], dot);
+        ddot = fma(dgy[o], sv[o], fma(gy[o], dsv[o], ddot));
+      }
+      const double sp = al * (1.0 - al);
+      gal = dot * sp;
+      dgal = fma(ddot, sp, dot * (1.0 - 2.0 * al) * dal);
+    }
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+      g[o] = al * gy[o];
+      dg[o] = fma(dal, gy[o], al * dgy[o]);
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      double s = 0.0, r = 0.0;
+#pragma unroll
+      for (int o = 0; o < D; ++o) {
+        s = fma(Wm[ow2 + o * D + k], g[o], s);
+        r = fma(Wm[ow2 + o * D + k], dg[o], r);
+      }
+      const bool pos = (mask >> k) & 1u;
+      q[k] = pos ? s : 0.0;
+      dq[k] = pos ? r : 0.0;
+    }
+  }
+  const int ub = L::layer(0) + 2 * L::PHI_SZ;   // the update block of the partial row
+  // the rounds, in the order that lets go of the most registers first: 2 (LayerNorm), 3 (Neumann), 1 (update W1 and gate)
+  // ---- round 2: g 0..9 | relu(pre) 10..19, 1 | d (w * yhat) 21..30, dw 31..40 (LayerNorm: every row that is not Dirichlet)
+  {
+    double a1[1] = {0.0}, s = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      row[k] = upd ? dg[k] : 0.0;
+      row[10 + k] = live ? rp[k] : 0.0;
+      row[21 + k] = live ? lnA[k] : 0.0;
+      row[31 + k] = live ? lnB[k] : 0.0;
+    }
+    row[20] = 1.0;
+    __syncthreads();
+    pg_acc<PG_RS, 1>(buf, 0, 10, D, D + 1, a1);
+    if (threadIdx.x < 2 * D) {
+      for (int r = 0; r < PG_ROWS; ++r) s += buf[r * PG_RS + 21 + threadIdx.x];
+      pt[L::LN_G + threadIdx.x] = s;   // LN_G .. LN_B + D is one run
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      row[k] = upd ? g[k] : 0.0;
+      row[10 + k] = live ? drp[k] : 0.0;
+    }
+    row[20] = 0.0;
+    __syncthreads();
+    pg_acc<PG_RS, 1>(buf, 0, 10, D, D + 1, a1);
+    pg_put<1>(pt, ub + L::UPD_W2, ub + L::UPD_B2, D, D + 1, a1);
+    __syncthreads();
+  }
+  // ---- round 3, Neumann rows: q 0..9 | cat 10..34, 1 | g 36..45 | relu(pre) 46..55, 1
+  if (MIXED) {
+    const int nb = L::layer(1) + L::PHI_SZ;
+    double a1[3] = {0.0, 0.0, 0.0}, a2[1] = {0.0};
+    if (ROWS == 2) {   // the update pass leaves zeros in these sections
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        row[k] = neu ? dq[k] : 0.0;
+        row[36 + k] = neu ? dg[k] : 0.0;
+        row[46 + k] = live ? rp[k] : 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k < L::NCAT; ++k) row[10 + k] = live ? cat[k] : 0.0;
+      row[10 + L::NCAT] = 1.0;
+      row[56] = 1.0;
+      __syncthreads();
+      pg_acc<PG_RS, 3>(buf, 0, 10, D, L::NCAT + 1, a1);
+      pg_acc<PG_RS, 1>(buf, 36, 46, D, D + 1, a2);
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        row[k] = neu ? q[k] : 0.0;
+        row[36 + k] = neu ? g[k] : 0.0;
+        row[46 + k] = live ? drp[k] : 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k < L::NCAT + 1; ++k) row[10 + k] = live && k < 2 * D ? dcat[k] : 0.0;
+      row[56] = 0.0;
+      __syncthreads();
+      pg_acc<PG_RS, 3>(buf, 0, 10, D, L::NCAT + 1, a1);
+      pg_acc<PG_RS, 1>(buf, 36, 46, D, D + 1, a2);
+    }
+    pg_put<3>(pt, nb, nb + L::NEU_B1, D, L::NCAT + 1, a1);
+    pg_put<1>(pt, nb + L::NEU_W2, nb + L::NEU_B2, D, D + 1, a2);
+    __syncthreads();
+  }
+  // ---- round 1, update rows: q 0..9 | cat 10 .. 10 + CAT, 1 | gal 44; first (dq, dgal) with cat, then (q, gal) with dcat
+  {
+    double a1[3] = {0.0, 0.0, 0.0}, a2[1] = {0.0};
+    if (ROWS != 2) {   // the Neumann pass leaves zeros in these sections
+#pragma unroll
+      for (int k = 0; k < D; ++k) row[k] = upd ? dq[k] : 0.0;
+#pragma unroll
+      for (int k = 0; k < L::CAT; ++k) row[10 + k] = live ? cat[k] : 0.0;
+      row[10 + L::CAT] = 1.0;
+      row[44] = upd ? dgal : 0.0;
+      __syncthreads();
+      pg_acc<PG_RS, 3>(buf, 0, 10, D, L::CAT + 1, a1);
+      pg_acc<PG_RS, 1>(buf, 44, 10, 1, L::CAT + 1, a2);
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < D; ++k) row[k] = upd ? q[k] : 0.0;
+#pragma unroll
+      for (int k = 0; k < 3 * D; ++k) row[10 + k] = live ? dcat[k] : 0.0;
+#pragma unroll
+      for (int k = 3 * D; k < L::CAT + 1; ++k) row[10 + k] = 0.0;
+      row[44] = upd ? gal : 0.0;
+      __syncthreads();
+      pg_acc<PG_RS, 3>(buf, 0, 10, D, L::CAT + 1, a1);
+      pg_acc<PG_RS, 1>(buf, 44, 10, 1, L::CAT + 1, a2);
+    }
+    pg_put<3>(pt, ub, ub + L::UPD_B1, D, L::CAT + 1, a1);
+    pg_put<1>(pt, L::AL_W, L::AL_B, 1, L::CAT + 1, a2);
+    __syncthreads();
+  }
+  // ---- the cotangents of the message sums and of x with their tangents, after the node rounds have let go of their factors
+  if (live) {
+    double c[CW], dc[CW], dgx[D], qq[D];
+#pragma unroll
+    for (int k = 0; k < CW; ++k) c[k] = dc[k] = 0.0;
+    const double* Wm = neu ? W + nofs + L::PHI_SZ : W + lofs + 2 * L::PHI_SZ;
+    if (neu) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        double s = 0.0, r = 0.0, u = 0.0;
+#pragma unroll
+        for (int o = 0; o < D; ++o) {
+          s = fma(Wm[o * L::NCAT + D + k], q[o], s);
+          r = fma(Wm[o * L::NCAT + D + k], dq[o], r);
+          u = fma(Wm[o * L::NCAT + k], dq[o], u);
+        }
+        c[CW - D + k] = s;
+        dc[CW - D + k] = r;
+        dgx[k] = u;
+      }
+      d64_w2t(W + nofs, dc + CW - D, qq);
+      d64_phi_vjp_xi(W + nofs, x, h, rb, re, csr_nbr, csr_attr, qq, dgx);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3 * D; ++k) {
+        double s = W[L::AL_W + k] * gal, r = W[L::AL_W + k] * dgal;
+#pragma unroll
+        for (int o = 0; o < D; ++o) {
+          s = fma(Wm[o * L::CAT + k], q[o], s);
+          r = fma(Wm[o * L::CAT + k], dq[o], r);
+        }
+        if (k < D) {
+          dgx[k] = dgy[k] + r;
+        } else {
+          c[k - D] = s;
+          dc[k - D] = r;
+        }
+      }
+      d64_w2t(W + lofs, dc, qq);
+      d64_phi_vjp_xi(W + lofs, x, h, cb, ce, csc_nbr, csc_attr, qq, dgx);
+      d64_w2t(W + lofs + L::PHI_SZ, dc + D, qq);
+      d64_phi_vjp_xi(W + lofs + L::PHI_SZ, x, h, rb, re, csr_nbr, csr_attr, qq, dgx);
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) dloc[n * D + k] = dgx[k];
+#pragma unroll
+    for (int k = 0; k < CW; ++k) {
+      C[n * CW + k] = c[k];
+      dC[n * CW + k] = dc[k];
+    }
+  } else if (ROWS != 2 && n < N) {   // pass 2 leaves the rows of pass 1 alone
+#pragma unroll
+    for (int k = 0; k < D; ++k) dloc[n * D + k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < CW; ++k) C[n * CW + k] = dC[n * CW + k] = 0.0;
+  }
+  // ---- the messages: Phi_to over the CSC list, Phi_from (Neumann rows: Phi_neumann) over the CSR list; c and dc from the rows above
+  const double *cg = C + (live ? n : 0) * CW, *dcg = dC + (live ? n : 0) * CW;
+  jr_edges(W + lofs, upd, x, dx, cg, dcg, h, t, cb, ce, csc_nbr, csc_attr, buf, row, pt, L::layer(0));
+  jr_edges(W + lofs + L::PHI_SZ, upd, x, dx, cg + D, dcg + D, h, t, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(0) + L::PHI_SZ);
+  if (MIXED) jr_edges(W + nofs, neu, x, dx, cg + 2 * D, dcg + 2 * D, h, t, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(1));
+}
+
+extern "C" int64_t psignn_f64_vjp_backward_workspace_doubles(const psignn_f64_t* f, int n_layers) {
+  if (!f || n_layers < 1) return -1;
+  const int64_t row = f->p->N * D;
+  const int cw = f->p->mixed ? 3 : 2;
+  // loc, C of J^T v; dloc, dC; a chain: the states and their tangents, the ping-pongs of w and dw; the per-chunk partials
+  return row * (2 + 2 * cw) + (f64_chain(f, n_layers) ? row * (2 * (n_layers - 1) + 4) : 0) + pg_part_doubles(f);
+}
+
+// layer l at (h, t, w, dw): its share of the parameter part added to grad, and out = the tangent of J_l(h)^T w
+static void jr_launch(const psignn_f64* f, const double* W, int nl, int l, int apply_ln, const double* h, const double* t,
+                      const double* prb, const double* nrm, const double* w, const double* dw, double* C, double* dloc, double* dC,
+                      double* part, double* grad, double* out, hipStream_t st) {
+  const psignn_plan* p = f->p;
+  const int64_t nch = cdiv(p->N, PG_ROWS);
+  const unsigned g = (unsigned)cdiv(p->N, 256);
+  const int cw = p->mixed ? 3 * D : 2 * D;
+  // both edge lists three times (the forward with its tangent, the x_i side, the rounds: neighbour id, 3 attributes, the neighbour's
+  // row and -- twice -- its tangent row), per node h, t, w, dw, dloc, C and dC written and read again, flag, pointers and problem
+  // data; the partial rows
+  PROF_BYTES(2 * p->Ep * (3 * (4 + 24) + 40 * D) + p->N * (8 * (5 * D + 4 * cw) + 8 * (p->mixed ? 5 : 2) + 17) + pg_part_doubles(f) * 8);
+  if (p->mixed) {
+    using L = W64<3>;
+    LAUNCH("k_f64_jr", st,
+           (k_f64_jr<3, true, 1><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, t,
+                                                                    prb, nrm, w, dw, C, dloc, dC, part)));
+    pg_reduce(part, nch, L::total(1, true), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
+    // the Neumann rows: per node flag and pointers, the partial rows once more; the edge reads of the few Neumann rows are not
+    // counted (the host does not know how many there are)
+    PROF_BYTES(p->N * 17 + pg_part_doubles(f) * 8);
+    LAUNCH("k_f64_jr_neumann", st,
+           (k_f64_jr<3, true, 2><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, t,
+                                                                    prb, nrm, w, dw, C, dloc, dC, part)));
+    pg_reduce(part, nch, L::total(1, true), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
+  } else {
+    using L = W64<2>;
+    LAUNCH("k_f64_jr", st,
+           (k_f64_jr<2, false, 0><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, t, prb,
+                                                                  nrm, w, dw, C, dloc, dC, part)));
+    pg_reduce(part, nch, L::total(1, false), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
+  }
+  // pass B on (dloc, dC), masks at h: as in vjp_launch
+  PROF_BYTES(2 * p->Ep * (4 + 1 + 24 + 16 * D) + p->N * (8 * 3 * D + 8));
+  if (p->mixed) {
+    using L = W64<3>;
+    LAUNCH("k_f64_vjp_edge", st,
+           (k_f64_vjp_edge<true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, dloc, dC, nullptr, out,
+                                                    nullptr)));
+  } else {
+    using L = W64<2>;
+    LAUNCH("k_f64_vjp_edge", st,
+           (k_f64_vjp_edge<false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, dloc, dC, nullptr, out,
+                                                     nullptr)));
+  }
+}
+
+extern "C" int psignn_f64_vjp_backward(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                                       const double* nrm, const double* v, const double* gbar, double* d_grad, double* d_dh,
+                                       double* d_jtv, double* work, int64_t work_doubles, void* stream) {
+  ARG_CHECK(f && W && h && h0 && prb && v && gbar && d_grad && d_dh, "NULL argument");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
+  ARG_CHECK(d_dh != h && d_dh != v && d_dh != gbar, "d_dh must not alias h, v or gbar");
+  ARG_CHECK(d_jtv != h && d_jtv != v && d_jtv != gbar && d_jtv != d_dh, "d_jtv must not alias h, v, gbar or d_dh");
+  const int rc = work_check(__func__, psignn_f64_vjp_backward_workspace_doubles(f, nl), work, work_doubles);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_grad, 0, sizeof(double) * psignn_f64_weights_size(f->p->mixed, nl), st));
+  if (f->p->N == 0) return PSIGNN_OK;
+  const int64_t row = f->p->N * D;
+  const int cw = f->p->mixed ? 3 : 2;
+  double *loc = work, *C = work + row, *dloc = C + cw * row, *dC = dloc + row, *rest = dC + cw * row;
+  if (!f64_chain(f, nl)) {   // mixed: only the last layer's iteration reaches the output, the earlier layers' sections stay zero
+    jr_launch(f, W, nl, nl - 1, 1, h, gbar, prb, nrm, v, nullptr, C, dloc, dC, rest, d_grad, d_dh, st);
+    if (d_jtv) vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, v, loc, C, nullptr, d_jtv, nullptr, st);
+  } else {
+    // the states h_1 .. h_{L-1} at h with their tangents along gbar, then the chain backwards: layer l at (h_l, t_l, w_{l+1}, dw_{l+1})
+    double *states = rest, *tans = states + (nl - 1) * row, *wpp = tans + (nl - 1) * row, *dwpp = wpp + 2 * row, *part = dwpp + 2 * row;
+    const double *ch = h, *ct = gbar;
+    for (int l = 0; l + 1 < nl; ++l) {
+      jvp_launch(f, W, nl, l, 0, ch, ct, h0, prb, nullptr, states + l * row, tans + l * row, nullptr, st);
+      ch = states + l * row;
+      ct = tans + l * row;
+    }
+    const double *cw_ = v, *cdw = nullptr;
+    for (int l = nl - 1; l >= 0; --l) {
+      const double* hl = l == 0 ? h : states + (l - 1) * row;
+      const double* tl = l == 0 ? gbar : tans + (l - 1) * row;
+      double* ddst = l == 0 ? d_dh : dwpp + (l & 1) * row;
+      double* dst = l == 0 ? d_jtv : wpp + (l & 1) * row;
+      jr_launch(f, W, nl, l, l == nl - 1, hl, tl, prb, nrm, cw_, cdw, C, dloc, dC, part, d_grad, ddst, st);
+      if (dst) vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, cw_, loc, C, nullptr, dst, nullptr, st);
+      cw_ = dst;
+      cdw = ddst;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}

@@ -2074,6 +2074,28 @@ class FixedPointMap64:
                                              nat.ptr(work), n, nat.stream_ptr(self.device)), "psignn_f64_param_vjp")
         return unpack_param_grads64(grad, nl, mixed), out, g_init
 
+    def vjp_backward(self, H, V, Gbar):
+        """Backward of the VJP in float64 (``psignn_f64_vjp_backward``; jac_loss_estimate, dirichlet/psignn/model.py:416-435 with
+        ``create_graph=True``): for ``psi = <Gbar, J_f(H)^T V>`` with Gbar constant, ({name: float64 d psi / d theta}, ``d psi / dH``,
+        ``J_f(H)^T V``), the tuple and the names of ``FixedPointMap.vjp_backward``.  H, V, Gbar: (N, 10), float32 (widened exactly) or
+        float64.  Both families, any depth, tiled or not; no atomics and a fixed summation order, so deterministic."""
+        Hc, Vc, Gc = self._states((H, "H"), (V, "V"), (Gbar, "Gbar"))
+        l = nat.lib()
+        nl, mixed = self.weights.n_layers, self.weights.mixed
+        n = int(l.psignn_f64_vjp_backward_workspace_doubles(self.handle, nl))
+        if n < 0:
+            raise nat.NativeError("psignn_f64_vjp_backward_workspace_doubles refused the handle")
+        work = self._deriv_work.get("vjp_backward")
+        if work is None or work.numel() != n:   # made on first use, like the products' workspaces
+            work = self._deriv_work["vjp_backward"] = torch.empty(n, dtype=torch.float64, device=self.device)
+        grad = torch.empty(int(l.psignn_f64_weights_size(int(mixed), nl)), dtype=torch.float64, device=self.device)
+        dh, jtv = torch.empty_like(Hc), torch.empty_like(Hc)
+        with torch.cuda.device(self.device):
+            nat.check(l.psignn_f64_vjp_backward(self.handle, nat.ptr(self.wflat), nl, nat.ptr(Hc), nat.ptr(self.h0), nat.ptr(self.prb),
+                                                nat.ptr(self.nrm), nat.ptr(Vc), nat.ptr(Gc), nat.ptr(grad), nat.ptr(dh), nat.ptr(jtv),
+                                                nat.ptr(work), n, nat.stream_ptr(self.device)), "psignn_f64_vjp_backward")
+        return unpack_param_grads64(grad, nl, mixed), dh, jtv
+
 
 class DeviceBroyden64:
     """Broyden root-find of ``f(x) - x`` in float64 with every scalar on the device (``psignn_broyden64_*``): the reference's
@@ -2278,3 +2300,45 @@ def implicit_grad64(batch, state_dict, h_star, grad, solver="gmres", eps=1e-11, 
     grads = {"deqdss.f." + k: t for k, t in named.items()}
     grads.update(zip(enc_names, mlp2_64_backward(batch.x, d_init, *enc[:3], need_gx=False)[1:]))
     return {"grads": grads, "y": y, "dh": dh, "adjoint": adj}
+
+
+def jac_loss_grad64(batch, state_dict, h_star, probes):
+    """The Jacobian regulariser and its gradient in float64 on the device, for a device batch and a reference state dict (default
+    latent width): ``jac_loss = sum_i |J_f(h*)^T v_i|^2 / (n N d)`` over the n probes (jac_loss_estimate,
+    dirichlet/psignn/model.py:416-435, which draws one ``torch.randn`` probe; n = 1 is its value), and what ``loss.backward()``
+    derives from it: per probe ``FixedPointMap64.vjp_backward(h*, v_i, 2 J^T v_i / (n N d))``, summed in the order of the probes.
+    ``probes``: a sequence of (N, 10) tensors or one (n, N, 10) tensor, float32 (widened exactly) or float64; ``h_star``: (N, 10).
+    Returns ``{"jac_loss": float, "grads": {full state-dict name of every deqdss.f.* tensor: float64 tensor}, "dh": d jac_loss /
+    d h* -- what a caller adds to ``grad`` before ``implicit_grad64`` for the gradient of a step with the regulariser -- and "jtv":
+    (n, N, 10), the products J^T v_i}``."""
+    nat.require_default_width(width_of(state_dict), "jac_loss_grad64")
+    n = int(batch.x.shape[0])
+    if tuple(h_star.shape) != (n, D):
+        raise nat.NativeError(f"h_star has shape {tuple(h_star.shape)}, expected {(n, D)}")
+    probes = list(probes)
+    if not probes:
+        raise nat.NativeError("jac_loss_grad64: at least one probe is needed")
+    for i, v in enumerate(probes):
+        if tuple(v.shape) != (n, D):
+            raise nat.NativeError(f"probe {i} has shape {tuple(v.shape)}, expected {(n, D)}")
+    w = PackedWeights64(state_dict)
+    enc = [state_dict[f"autoencoder.encoder.mlp.mlp.{i}.{p}"] for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
+    h0 = mlp2_64(batch.x, *enc)
+    fmap = FixedPointMap64(plan_for(batch), w, h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
+    scale = 1.0 / (len(probes) * n * D)
+    loss, grads, dh, jtvs = 0.0, None, None, []
+    try:
+        for v in probes:
+            jtv = fmap.vjp(h_star, v)
+            named, d, again = fmap.vjp_backward(h_star, v, (2.0 * scale) * jtv)
+            loss += float((again * again).sum()) * scale
+            jtvs.append(again)
+            if grads is None:
+                grads, dh = named, d
+            else:
+                for k in grads:
+                    grads[k] = grads[k] + named[k]
+                dh = dh + d
+    finally:
+        fmap.close()
+    return {"jac_loss": loss, "grads": {"deqdss.f." + k: t for k, t in grads.items()}, "dh": dh, "jtv": torch.stack(jtvs)}
