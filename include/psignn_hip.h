@@ -873,6 +873,17 @@ int psignn_f64_vjp_backward(psignn_f64_t* f, const double* d_weights, int n_laye
                             const double* d_prb, const double* d_normals /* NULL for dirichlet plans */, const double* d_v,
                             const double* d_gbar, double* d_grad, double* d_dh, double* d_jtv /* NULL: skip */, double* d_work,
                             int64_t work_doubles, void* stream);
+/* psignn_f64_vjp_backward (the same launches, the same bits in every output it shares) and d_dinit (N, 10; may be NULL) = d psi /
+ * d h_initial.  A multi-layer dirichlet block copies the Dirichlet rows of h_initial into every layer state h_1 .. h_{L-1}, and J_f is
+ * evaluated at those states: d_dinit is the sum over them of the Dirichlet rows of the tangent of their cotangents.  Every other block
+ * (single layer; mixed, whose loop never reassigns h) has a Jacobian that does not depend on h_initial: exact zeros.  This is the path by
+ * which the Jacobian regulariser reaches the encoder.  d_dinit aliases none of the other arrays.
+ * replaces: loss.backward() from jac_loss_estimate, dirichlet/psignn/model.py:416-435, into H_init = encoder(x) of
+ *           DeepEquilibrium.forward (model.py:184-207), in double precision. */
+int psignn_f64_vjp_backward_init(psignn_f64_t* f, const double* d_weights, int n_layers, const double* d_h, const double* d_h_initial,
+                                 const double* d_prb, const double* d_normals /* NULL for dirichlet plans */, const double* d_v,
+                                 const double* d_gbar, double* d_grad, double* d_dh, double* d_jtv /* NULL: skip */,
+                                 double* d_dinit /* NULL: skip */, double* d_work, int64_t work_doubles, void* stream);
 /* Doubles of d_work for psignn_mlp2_f64_backward: ceil(n / 128) * (hid * din + hid + dout * hid + dout); -1 for sizes out of range.
  * replaces: autograd's saved tensors of Encoder / Decoder, dirichlet/psignn/model.py:370-392. */
 int64_t psignn_mlp2_f64_backward_workspace_doubles(int64_t n, int din, int hid, int dout);
@@ -883,6 +894,42 @@ int64_t psignn_mlp2_f64_backward_workspace_doubles(int64_t n, int din, int hid, 
 int psignn_mlp2_f64_backward(const double* d_x, const double* d_gy, int64_t n, int din, int hid, int dout, const double* d_w1,
                              const double* d_b1, const double* d_w2, double* d_gx, double* d_gflat, double* d_work,
                              int64_t work_doubles, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The losses of a training step in float64 on the device (csrc/poisson_cg.hip, beside the solve of the same system): the residual of the discrete Poisson system with its
+ * transpose, and a mean-square error with its gradient -- with the entries above, every link of ModelDEQDSS._train_forward and of its
+ * loss.backward() in double precision (engine.train_step64).  A = COO(edge_index, a_ij) including the diagonal; d_a_ij: the caller's
+ * (E) float64 values in edge_index order (the plan's own copy is fp32 and is not read).  Caller's numbering, tiled and untiled plans
+ * alike; any degree, duplicate and one-directional edges, nodes without a self loop.  No atomics, and sums whose order depends on
+ * the graph or on the length alone: the same call gives the same bits.  Default-width library only.
+ * ------------------------------------------------------------------------------------------ */
+/* d_r (N) = A d_u - d_y: one row per lane over the plan's full CSR (columns ascending, equal columns by edge id), repeated positions
+ * added entry after entry.  d_r aliases neither d_u nor d_y.
+ * replaces: residual_loss before its mean, dirichlet/psignn/model.py:157-167 (index_add_ over edge_index), as ModelDEQDSS.forward
+ *           calls it (model.py:58-99), on float64 tensors. */
+int psignn_residual_f64(const psignn_plan_t* plan, const double* d_a_ij /* (E) edge_index order */, const double* d_u,
+                        const double* d_y, double* d_r, void* stream);
+/* d_out (N) = A^T d_r: per column its in-edges in the plan's CSC order (sender ascending, equal senders by edge id), then the diagonal
+ * entries of its row of the full CSR -- psignn_residual_t in float64.  d_out must not alias d_r.
+ * replaces: autograd through residual_loss, dirichlet/psignn/model.py:157-167, in the backward of model.py:58-99, on float64 tensors. */
+int psignn_residual_t_f64(const psignn_plan_t* plan, const double* d_a_ij /* (E) edge_index order */, const double* d_r,
+                          double* d_out, void* stream);
+/* Elements whose squares one partial of psignn_mse_f64 holds (the chunks start at element 0).
+ * replaces: nothing of the reference (F.mse_loss of dirichlet/psignn/model.py:58-99 and the mean of model.py:157-167 sum in torch's order). */
+int psignn_mse_f64_chunk(void);
+/* Doubles of d_work for psignn_mse_f64: ceil(n_elems / chunk), one partial per chunk; -1 for n_elems < 1.
+ * replaces: nothing of the reference (model.py:157-167 and :58-99 keep no partial sums). */
+int64_t psignn_mse_f64_workspace_doubles(int64_t n_elems);
+/* *d_loss (one double on the device) = sum (d_a - d_b)^2 / scale_n over n_elems elements (d_b NULL: zeros), and, when d_grad is not
+ * NULL, d_grad = 2 (d_a - d_b) / scale_n element by element.  One partial per chunk (thread t of the block adds elements t, t + 256,
+ * ... of its chunk in ascending order, then the fixed block sum), then one block adds the partials in ascending stride order and
+ * divides once.  n_elems < 1, scale_n <= 0 and a NULL d_a / d_loss are PSIGNN_EINVAL; d_grad, d_loss and d_work alias nothing else;
+ * a d_work smaller than the query is PSIGNN_ENOMEM with a message naming the bytes.
+ * replaces: torch.mean(residual ** 2), dirichlet/psignn/model.py:157-167, and the F.mse_loss terms of ModelDEQDSS.forward
+ *           (model.py:58-99: encoder_loss, autoencoder_loss, mse_loss, mse_dirichlet) with their autograd, on float64 tensors. */
+int psignn_mse_f64(const double* d_a, const double* d_b /* NULL: zeros */, int64_t n_elems, double scale_n /* the divisor */,
+                   double* d_loss /* 1 double on the device */, double* d_grad /* NULL or n_elems */, double* d_work,
+                   int64_t work_doubles, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events on the launch stream (used by bench.py for the roofline line;

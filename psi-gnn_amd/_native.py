@@ -232,8 +232,14 @@ SIGNATURES = {
     "psignn_f64_param_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "psignn_f64_vjp_backward_workspace_doubles": (_I64, [_P, _INT]),
     "psignn_f64_vjp_backward": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "psignn_f64_vjp_backward_init": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "psignn_mlp2_f64_backward_workspace_doubles": (_I64, [_I64, _INT, _INT, _INT]),
     "psignn_mlp2_f64_backward": (_INT, [_P, _P, _I64, _INT, _INT, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "psignn_residual_f64": (_INT, [_P, _P, _P, _P, _P, _P]),
+    "psignn_residual_t_f64": (_INT, [_P, _P, _P, _P, _P]),
+    "psignn_mse_f64_chunk": (_INT, []),
+    "psignn_mse_f64_workspace_doubles": (_I64, [_I64]),
+    "psignn_mse_f64": (_INT, [_P, _P, _I64, C.c_double, _P, _P, _P, _I64, _P]),
     "psignn_prof_enable": (None, [_INT]),
     "psignn_reload_knobs": (None, []),
     "psignn_prof_tile_stamps": (None, [_P]),

@@ -1657,15 +1657,28 @@ static void jr_launch(const psignn_f64* f, const double* W, int nl, int l, int a
   }
 }
 
-extern "C" int psignn_f64_vjp_backward(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
-                                       const double* nrm, const double* v, const double* gbar, double* d_grad, double* d_dh,
-                                       double* d_jtv, double* work, int64_t work_doubles, void* stream) {
-  ARG_CHECK(f && W && h && h0 && prb && v && gbar && d_grad && d_dh, "NULL argument");
-  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
-  ARG_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
-  ARG_CHECK(d_dh != h && d_dh != v && d_dh != gbar, "d_dh must not alias h, v or gbar");
-  ARG_CHECK(d_jtv != h && d_jtv != v && d_jtv != gbar && d_jtv != d_dh, "d_jtv must not alias h, v, gbar or d_dh");
-  const int rc = work_check(__func__, psignn_f64_vjp_backward_workspace_doubles(f, nl), work, work_doubles);
+// d_dinit (may be NULL) = d psi / d h_initial: the Dirichlet rows of the tangents of the cotangents on the states h_1 .. h_{L-1} of a
+// multi-layer dirichlet block (those rows are copies of h_initial, and J_f is evaluated at them); zeros for every other block, whose
+// Jacobian does not depend on h_initial.
+// ARG_CHECK under the name of the entry point that was called
+#define JR_CHECK(cond, msg)                       \
+  do {                                            \
+    if (!(cond)) {                                \
+      psignn_set_error("%s: %s", who, msg);       \
+      return PSIGNN_EINVAL;                       \
+    }                                             \
+  } while (0)
+static int vjp_backward_impl(const char* who, psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0,
+                             const double* prb, const double* nrm, const double* v, const double* gbar, double* d_grad, double* d_dh,
+                             double* d_jtv, double* d_dinit, double* work, int64_t work_doubles, void* stream) {
+  JR_CHECK(f && W && h && h0 && prb && v && gbar && d_grad && d_dh, "NULL argument");
+  JR_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  JR_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
+  JR_CHECK(d_dh != h && d_dh != v && d_dh != gbar, "d_dh must not alias h, v or gbar");
+  JR_CHECK(d_jtv != h && d_jtv != v && d_jtv != gbar && d_jtv != d_dh, "d_jtv must not alias h, v, gbar or d_dh");
+  JR_CHECK(!d_dinit || (d_dinit != h && d_dinit != v && d_dinit != gbar && d_dinit != d_dh && d_dinit != d_jtv),
+            "d_dinit must not alias h, v, gbar, d_dh or d_jtv");
+  const int rc = work_check(who, psignn_f64_vjp_backward_workspace_doubles(f, nl), work, work_doubles);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipMemsetAsync(d_grad, 0, sizeof(double) * psignn_f64_weights_size(f->p->mixed, nl), st));
@@ -1674,6 +1687,7 @@ extern "C" int psignn_f64_vjp_backward(psignn_f64_t* f, const double* W, int nl,
   const int cw = f->p->mixed ? 3 : 2;
   double *loc = work, *C = work + row, *dloc = C + cw * row, *dC = dloc + row, *rest = dC + cw * row;
   if (!f64_chain(f, nl)) {   // mixed: only the last layer's iteration reaches the output, the earlier layers' sections stay zero
+    if (d_dinit) HIP_TRY(hipMemsetAsync(d_dinit, 0, sizeof(double) * row, st));
     jr_launch(f, W, nl, nl - 1, 1, h, gbar, prb, nrm, v, nullptr, C, dloc, dC, rest, d_grad, d_dh, st);
     if (d_jtv) vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, v, loc, C, nullptr, d_jtv, nullptr, st);
   } else {
@@ -1692,6 +1706,11 @@ extern "C" int psignn_f64_vjp_backward(psignn_f64_t* f, const double* W, int nl,
       double* ddst = l == 0 ? d_dh : dwpp + (l & 1) * row;
       double* dst = l == 0 ? d_jtv : wpp + (l & 1) * row;
       jr_launch(f, W, nl, l, l == nl - 1, hl, tl, prb, nrm, cw_, cdw, C, dloc, dC, part, d_grad, ddst, st);
+      if (d_dinit && l > 0) {   // ddst: the tangent of the cotangent on h_l, whose Dirichlet rows are h_initial's
+        PROF_BYTES(f->p->N * (1 + 16 * D));
+        LAUNCH("k_f64_pg_init", st,
+               (k_f64_pg_init<<<(unsigned)cdiv(row, 256), 256, 0, st>>>(f->p->N, f->p->flags, ddst, l != nl - 1, d_dinit)));
+      }
       if (dst) vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, cw_, loc, C, nullptr, dst, nullptr, st);
       cw_ = dst;
       cdw = ddst;
@@ -1699,4 +1718,17 @@ extern "C" int psignn_f64_vjp_backward(psignn_f64_t* f, const double* W, int nl,
   }
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
+}
+
+extern "C" int psignn_f64_vjp_backward(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                                       const double* nrm, const double* v, const double* gbar, double* d_grad, double* d_dh,
+                                       double* d_jtv, double* work, int64_t work_doubles, void* stream) {
+  return vjp_backward_impl(__func__, f, W, nl, h, h0, prb, nrm, v, gbar, d_grad, d_dh, d_jtv, nullptr, work, work_doubles, stream);
+}
+
+extern "C" int psignn_f64_vjp_backward_init(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0,
+                                            const double* prb, const double* nrm, const double* v, const double* gbar, double* d_grad,
+                                            double* d_dh, double* d_jtv, double* d_dinit, double* work, int64_t work_doubles,
+                                            void* stream) {
+  return vjp_backward_impl(__func__, f, W, nl, h, h0, prb, nrm, v, gbar, d_grad, d_dh, d_jtv, d_dinit, work, work_doubles, stream);
 }

@@ -517,3 +517,132 @@ extern "C" int psignn_cg_solve(psignn_cg_t* s, const void* d_y, int y_is_f64, co
   h_info->sym_defect = s->sym_defect;
   return PSIGNN_OK;
 }
+
+// =============================================================================================
+// The losses of a training step in float64, on the same matrix: the residual r = A u - y of the system above with its transpose
+// A^T r, and a mean-square error with its gradient.  With f, the MLPs and their backwards (fgnn_f64.hip, fgnn_f64_deriv.hip) these
+// close the chain of ModelDEQDSS._train_forward in double precision (engine.train_step64).
+//
+// replaces: residual_loss (dirichlet/psignn/model.py:157-167: index_add_ over edge_index with a_ij, the diagonal included) and the
+//           F.mse_loss terms of ModelDEQDSS.forward (model.py:58-99), with what autograd derives from them, on float64 tensors.
+//
+// Unlike the solve they read the plan's full CSR / CSC directly and gather the values by edge id from the caller's float64 a_ij on
+// every call (no handle, every row, Dirichlet rows included).  A truth path, bound by its gathers: one row (column) per lane,
+// coalesced index loads, nothing tuned further.  No atomics; every sum runs in an order that depends on the graph or on the length
+// alone, so the same call gives the same bits.
+// =============================================================================================
+static_assert(ws::MSE64_CHUNK == F64_CHUNK && F64_CHUNK % F64_TB == 0, "one mean-square-error partial per dots chunk");
+
+// r_i = sum_k a_ij[a_eid[k]] u[a_col[k]] - y_i over row i of the plan's full CSR (columns ascending, equal columns by edge id):
+// repeated positions are added entry after entry.  The values come from the caller's float64 a_ij; the plan's own copy is fp32.
+__global__ void __launch_bounds__(F64_TB) k_residual_f64(int64_t N, const int32_t* __restrict__ a_ptr, const int32_t* __restrict__ a_col,
+                                                          const int32_t* __restrict__ a_eid, const double* __restrict__ a_ij,
+                                                          const double* __restrict__ u, const double* __restrict__ y,
+                                                          double* __restrict__ r) {
+  const int64_t i = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
+  if (i >= N) return;
+  double s = 0.0;
+  for (int32_t k = a_ptr[i]; k < a_ptr[i + 1]; ++k) s += a_ij[a_eid[k]] * u[a_col[k]];
+  r[i] = s - y[i];
+}
+
+// out_c = sum over the in-edges of column c (csc order: sender ascending, equal senders by edge id) of a_ij[e] r[row(e)], then the
+// diagonal entries of row c in the full CSR's order: k_residual_t (fgnn_pgrad.hip) in float64, the diagonal read through a_eid too.
+__global__ void __launch_bounds__(F64_TB) k_residual_t_f64(int64_t N, const int32_t* __restrict__ csc_ptr,
+                                                            const int32_t* __restrict__ csc_nbr, const int32_t* __restrict__ csc_eid,
+                                                            const int32_t* __restrict__ a_ptr, const int32_t* __restrict__ a_col,
+                                                            const int32_t* __restrict__ a_eid, const double* __restrict__ a_ij,
+                                                            const double* __restrict__ r, double* __restrict__ out) {
+  const int64_t c = (int64_t)blockIdx.x * F64_TB + threadIdx.x;
+  if (c >= N) return;
+  double s = 0.0;
+  for (int32_t k = csc_ptr[c]; k < csc_ptr[c + 1]; ++k) s += a_ij[csc_eid[k]] * r[csc_nbr[k]];
+  const double rc = r[c];
+  for (int32_t k = a_ptr[c]; k < a_ptr[c + 1]; ++k)
+    if (a_col[k] == (int32_t)c) s += a_ij[a_eid[k]] * rc;
+  out[c] = s;
+}
+
+// Block = chunk of F64_CHUNK elements: thread t takes elements t, t + 256, ... of the chunk in ascending order (8-byte loads: the
+// length may be odd), then the block sum.  part[chunk] = sum (a - b)^2; grad = 2 (a - b) / scale_n, element by element.
+__global__ void __launch_bounds__(F64_TB) k_mse_f64(int64_t n, const double* __restrict__ a, const double* __restrict__ b, double scale_n,
+                                                     double* __restrict__ part, double* __restrict__ grad) {
+  __shared__ double sh[4];
+  const int64_t base = (int64_t)blockIdx.x * F64_CHUNK;
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < F64_CHUNK / F64_TB; ++i) {
+    const int64_t e = base + i * F64_TB + threadIdx.x;
+    if (e < n) {
+      const double d = b ? a[e] - b[e] : a[e];
+      s += d * d;
+      if (grad) grad[e] = (2.0 * d) / scale_n;
+    }
+  }
+  s = f64_block_sum(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// one block: the partials in ascending stride order, divided once
+__global__ void __launch_bounds__(F64_TB) k_mse_f64_final(const double* __restrict__ part, int64_t nchunk, double scale_n,
+                                                           double* __restrict__ loss) {
+  __shared__ double sh[4];
+  const double s = f64_final_sum(part, nchunk, sh);
+  if (threadIdx.x == 0) *loss = s / scale_n;
+}
+
+static int plan_has_matrix(const psignn_plan* p) { return p->a_ptr && p->a_col && p->a_eid && p->csc_ptr && p->csc_nbr && p->csc_eid; }
+
+extern "C" int psignn_residual_f64(const psignn_plan_t* p, const double* d_a_ij, const double* d_u, const double* d_y, double* d_r,
+                                   void* stream) {
+  ARG_CHECK(p && d_a_ij && d_u && d_y && d_r, "NULL argument");
+  ARG_CHECK(plan_has_matrix(p), "the plan holds no matrix structure");
+  ARG_CHECK(d_r != d_u && d_r != d_y, "d_r must not alias d_u or d_y");
+  if (p->N == 0) return PSIGNN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  PROF_BYTES(p->E * (4 + 4 + 8 + 8) + p->N * (4 + 8 + 8));
+  LAUNCH("k_residual_f64", st,
+         (k_residual_f64<<<(unsigned)cdiv(p->N, F64_TB), F64_TB, 0, st>>>(p->N, p->a_ptr, p->a_col, p->a_eid, d_a_ij, d_u, d_y, d_r)));
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
+extern "C" int psignn_residual_t_f64(const psignn_plan_t* p, const double* d_a_ij, const double* d_r, double* d_out, void* stream) {
+  ARG_CHECK(p && d_a_ij && d_r && d_out, "NULL argument");
+  ARG_CHECK(plan_has_matrix(p), "the plan holds no matrix structure");
+  ARG_CHECK(d_out != d_r, "d_out must not alias d_r");
+  if (p->N == 0) return PSIGNN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  PROF_BYTES(p->Ep * (4 + 4 + 8 + 8) + p->E * (4 + 4) + p->N * (8 + 8 + 8));
+  LAUNCH("k_residual_t_f64", st,
+         (k_residual_t_f64<<<(unsigned)cdiv(p->N, F64_TB), F64_TB, 0, st>>>(p->N, p->csc_ptr, p->csc_nbr, p->csc_eid, p->a_ptr, p->a_col,
+                                                                            p->a_eid, d_a_ij, d_r, d_out)));
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}
+
+extern "C" int psignn_mse_f64_chunk(void) { return F64_CHUNK; }
+
+extern "C" int64_t psignn_mse_f64_workspace_doubles(int64_t n_elems) { return n_elems < 1 ? -1 : ws::mse64_total(n_elems); }
+
+extern "C" int psignn_mse_f64(const double* d_a, const double* d_b, int64_t n_elems, double scale_n, double* d_loss, double* d_grad,
+                              double* d_work, int64_t work_doubles, void* stream) {
+  ARG_CHECK(d_a && d_loss, "NULL argument");
+  ARG_CHECK(n_elems >= 1, "n_elems must be at least 1");
+  ARG_CHECK(scale_n > 0.0, "scale_n must be positive");
+  ARG_CHECK(d_grad != d_a && (!d_grad || d_grad != d_b), "d_grad must not alias d_a or d_b");
+  ARG_CHECK(d_loss != d_a && d_loss != d_b && d_loss != d_grad, "d_loss must not alias d_a, d_b or d_grad");
+  const int64_t need = ws::mse64_total(n_elems);
+  if (!d_work || work_doubles < need) {
+    psignn_set_error("%s: the workspace holds %lld doubles, %lld are needed (%lld bytes)", __func__, (long long)(d_work ? work_doubles : 0),
+                     (long long)need, (long long)need * 8);
+    return PSIGNN_ENOMEM;
+  }
+  ARG_CHECK(d_work != d_a && d_work != d_b && d_work != d_grad && d_work != d_loss, "d_work must not alias an argument");
+  hipStream_t st = (hipStream_t)stream;
+  PROF_BYTES(n_elems * 8 * (1 + (d_b ? 1 : 0) + (d_grad ? 1 : 0)) + need * 8);
+  LAUNCH("k_mse_f64", st, (k_mse_f64<<<(unsigned)need, F64_TB, 0, st>>>(n_elems, d_a, d_b, scale_n, d_work, d_grad)));
+  LAUNCH("k_mse_f64_final", st, (k_mse_f64_final<<<1, F64_TB, 0, st>>>(d_work, need, scale_n, d_loss)));
+  HIP_TRY(hipGetLastError());
+  return PSIGNN_OK;
+}

@@ -182,4 +182,9 @@ inline AdjWork adj_work(int64_t N, int nl, bool mixed, float* base) {
   return c.done(AdjWork{take(f_total(N)), take(M), take(M), take(M), take(M), take(M), take(N * 3), take(N * 2),
                         take(mixed ? 0 : layer_work(N, nl, false, nullptr).total), 0});   // the operator of a mixed block needs no layer states
 }
+
+// ---- float64 mean-square error (psignn_mse_f64_workspace_doubles; DOUBLES, one segment): one partial per chunk of MSE64_CHUNK
+// elements, in chunk order; one block then adds them (poisson_cg.hip)
+constexpr int64_t MSE64_CHUNK = 1024;
+inline int64_t mse64_total(int64_t n_elems) { return (n_elems + MSE64_CHUNK - 1) / MSE64_CHUNK; }
 }  // namespace ws

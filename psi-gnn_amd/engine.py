@@ -2079,6 +2079,15 @@ class FixedPointMap64:
         ``create_graph=True``): for ``psi = <Gbar, J_f(H)^T V>`` with Gbar constant, ({name: float64 d psi / d theta}, ``d psi / dH``,
         ``J_f(H)^T V``), the tuple and the names of ``FixedPointMap.vjp_backward``.  H, V, Gbar: (N, 10), float32 (widened exactly) or
         float64.  Both families, any depth, tiled or not; no atomics and a fixed summation order, so deterministic."""
+        return self._vjp_backward(H, V, Gbar, False)[:3]
+
+    def vjp_backward_init(self, H, V, Gbar):
+        """``vjp_backward`` and ``d psi / dH_init`` as a fourth entry (``psignn_f64_vjp_backward_init``): the Dirichlet rows through
+        which the Jacobian of a multi-layer dirichlet block depends on ``H_init``; exact zeros for every other block.  The first three
+        entries have the bits of ``vjp_backward``."""
+        return self._vjp_backward(H, V, Gbar, True)
+
+    def _vjp_backward(self, H, V, Gbar, with_init):
         Hc, Vc, Gc = self._states((H, "H"), (V, "V"), (Gbar, "Gbar"))
         l = nat.lib()
         nl, mixed = self.weights.n_layers, self.weights.mixed
@@ -2090,11 +2099,16 @@ class FixedPointMap64:
             work = self._deriv_work["vjp_backward"] = torch.empty(n, dtype=torch.float64, device=self.device)
         grad = torch.empty(int(l.psignn_f64_weights_size(int(mixed), nl)), dtype=torch.float64, device=self.device)
         dh, jtv = torch.empty_like(Hc), torch.empty_like(Hc)
+        dinit = torch.empty_like(Hc) if with_init else None
+        lead = (self.handle, nat.ptr(self.wflat), nl, nat.ptr(Hc), nat.ptr(self.h0), nat.ptr(self.prb), nat.ptr(self.nrm), nat.ptr(Vc),
+                nat.ptr(Gc), nat.ptr(grad), nat.ptr(dh), nat.ptr(jtv))
         with torch.cuda.device(self.device):
-            nat.check(l.psignn_f64_vjp_backward(self.handle, nat.ptr(self.wflat), nl, nat.ptr(Hc), nat.ptr(self.h0), nat.ptr(self.prb),
-                                                nat.ptr(self.nrm), nat.ptr(Vc), nat.ptr(Gc), nat.ptr(grad), nat.ptr(dh), nat.ptr(jtv),
-                                                nat.ptr(work), n, nat.stream_ptr(self.device)), "psignn_f64_vjp_backward")
-        return unpack_param_grads64(grad, nl, mixed), dh, jtv
+            if with_init:
+                nat.check(l.psignn_f64_vjp_backward_init(*lead, nat.ptr(dinit), nat.ptr(work), n, nat.stream_ptr(self.device)),
+                          "psignn_f64_vjp_backward_init")
+            else:
+                nat.check(l.psignn_f64_vjp_backward(*lead, nat.ptr(work), n, nat.stream_ptr(self.device)), "psignn_f64_vjp_backward")
+        return unpack_param_grads64(grad, nl, mixed), dh, jtv, dinit
 
 
 class DeviceBroyden64:
@@ -2342,3 +2356,164 @@ def jac_loss_grad64(batch, state_dict, h_star, probes):
     finally:
         fmap.close()
     return {"jac_loss": loss, "grads": {"deqdss.f." + k: t for k, t in grads.items()}, "dh": dh, "jtv": torch.stack(jtvs)}
+
+
+# ---------------------------------------------------------------------------------------------
+# the losses of a training step in float64 (csrc/poisson_cg.hip) and the whole step in one call
+# ---------------------------------------------------------------------------------------------
+def _columns64(plan, a_ij, *named):
+    """``a_ij`` ((E,) or (E, 1)) and (N,) or (N, 1) tensors as flat contiguous float64 device tensors; every shape is checked before any
+    tensor is touched."""
+    for t, name in named:
+        if t.numel() != plan.N or t.dim() > 2 or (t.dim() == 2 and t.shape[1] != 1):
+            raise nat.NativeError(f"{name} has shape {tuple(t.shape)}, expected {(plan.N, 1)}")
+        if plan.N == 0:
+            raise nat.NativeError(f"{name} is empty")
+    if a_ij.numel() != plan.E:
+        raise nat.NativeError(f"a_ij has {a_ij.numel()} values, the plan {plan.E} edges")
+    return [_f64c(a_ij, "a_ij").reshape(-1)] + [_f64c(t, name).reshape(-1) for t, name in named]
+
+
+def residual64(plan, a_ij, u, y):
+    """``A u - y`` in float64 (``psignn_residual_f64``), A = COO(edge_index, a_ij) including the diagonal (model.py:157-167):
+    (N, 1) float64.  ``a_ij``: the (E,) or (E, 1) values in ``edge_index`` order; ``u``, ``y``: (N,) or (N, 1).  Inputs are float32
+    (widened exactly) or float64; the plan's own fp32 copy of ``a_ij`` is not read.  Deterministic."""
+    ac, uc, yc = _columns64(plan, a_ij, (u, "u"), (y, "y"))
+    out = torch.empty_like(uc)
+    with torch.cuda.device(uc.device):
+        nat.check(nat.lib().psignn_residual_f64(plan.handle, nat.ptr(ac), nat.ptr(uc), nat.ptr(yc), nat.ptr(out),
+                                                nat.stream_ptr(uc.device)), "psignn_residual_f64")
+    return out.reshape(-1, 1)
+
+
+def residual64_t(plan, a_ij, r):
+    """``A^T r`` in float64 (``psignn_residual_t_f64``): what autograd sends from the residual to ``u``.  Shapes and dtypes as
+    ``residual64``; (N, 1) float64.  Deterministic."""
+    ac, rc = _columns64(plan, a_ij, (r, "r"))
+    out = torch.empty_like(rc)
+    with torch.cuda.device(rc.device):
+        nat.check(nat.lib().psignn_residual_t_f64(plan.handle, nat.ptr(ac), nat.ptr(rc), nat.ptr(out), nat.stream_ptr(rc.device)),
+                  "psignn_residual_t_f64")
+    return out.reshape(-1, 1)
+
+
+def mse64(a, b=None, need_grad=False):
+    """``mean((a - b)^2)`` in float64 (``psignn_mse_f64``; ``b`` None: zeros): (loss as a 0-dim float64 device tensor,
+    ``2 (a - b) / a.numel()`` in the shape of ``a`` | None).  Inputs are float32 (widened exactly) or float64.  One partial per
+    chunk of ``psignn_mse_f64_chunk()`` elements, added in a fixed order: deterministic."""
+    if b is not None and tuple(b.shape) != tuple(a.shape):
+        raise nat.NativeError(f"mse64: a has shape {tuple(a.shape)}, b {tuple(b.shape)}")
+    n = a.numel()
+    if n == 0:
+        raise nat.NativeError("mse64: a is empty")
+    ac = _f64c(a, "a")
+    bc = None if b is None else _f64c(b, "b")
+    l = nat.lib()
+    nw = int(l.psignn_mse_f64_workspace_doubles(n))
+    loss = torch.empty((), dtype=torch.float64, device=ac.device)
+    grad = torch.empty_like(ac) if need_grad else None
+    work = torch.empty(nw, dtype=torch.float64, device=ac.device)
+    with torch.cuda.device(ac.device):
+        nat.check(l.psignn_mse_f64(nat.ptr(ac), nat.ptr(bc), n, float(n), nat.ptr(loss), nat.ptr(grad), nat.ptr(work), nw,
+                                   nat.stream_ptr(ac.device)), "psignn_mse_f64")
+    return loss, grad
+
+
+def train_step64(batch, state_dict, h_star=None, y=None, jac_weight=0.0, probe=None, fw_eps=1e-11, fw_threshold=1000, solver="gmres",
+                 eps=1e-11, m=50, max_products=2000, threshold=800):
+    """One training step of ``ModelDEQDSS`` in float64 on the device, for a device batch and a reference state dict (default latent
+    width): the losses of ``_train_forward`` (model.py:58-99) and what ``loss.backward()`` leaves in every parameter for
+    ``loss = residual_loss + jac_weight * jacobian_loss + encoder_loss + autoencoder_loss`` (training_class.py:155-159).
+
+    ``h_star`` given: the state the step is taken at; otherwise ``fixed_point64(fw_eps, fw_threshold)``.  ``y`` given: the adjoint
+    ``y = J^T y + grad_h`` is taken as solved by it; otherwise ``adjoint64(solver, eps, m, max_products, threshold)``.  ``probe``:
+    the (N, 10) probe of the Jacobian regulariser, for which the reference draws ``torch.randn``; H* is a leaf of it (model.py:204), so it
+    adds nothing to ``grad_h``.  ``jac_weight != 0`` needs a probe; a probe with ``jac_weight == 0`` still reports
+    ``jacobian_loss``.
+
+    The chain: ``new_H = f(h*)``, ``u = dec(new_H)``, ``r = A u - y_rhs`` and ``mean(r^2)`` (``residual64`` / ``mse64``), its
+    cotangent back through ``residual64_t`` and ``mlp2_64_backward`` to ``grad_h``; the encoder and autoencoder losses at constant
+    ``u`` / ``new_H``; ``implicit_grad64`` for f and the encoder; the composition of ``jac_loss_grad64`` for the regulariser, which reaches f's
+    parameters and, in a multi-layer dirichlet block, the encoder through ``H_init`` (``FixedPointMap64.vjp_backward_init``).
+
+    Returns ``loss`` (float), ``loss_dic`` (the six keys of ``_train_forward`` as floats; ``mse_loss`` is nan without ``batch.sol``),
+    ``grads`` (every name of the state dict -> float64 tensor, exact zeros where autograd leaves none), ``h_star``, ``new_h``,
+    ``u``, ``grad_h`` (the cotangent the backward hook receives), ``y``, ``forward`` / ``adjoint`` (the solvers' dictionaries, None
+    where the state was given)."""
+    nat.require_default_width(width_of(state_dict), "train_step64")
+    if solver not in ("gmres", "broyden"):
+        raise nat.NativeError(f"train_step64: solver must be 'gmres' or 'broyden', got {solver!r}")
+    jac_weight = float(jac_weight)
+    if jac_weight != 0.0 and probe is None:
+        raise nat.NativeError("train_step64: jac_weight != 0 needs a probe (the reference draws it with randn; a truth needs it handed in)")
+    n = int(batch.x.shape[0])
+    for t, name in ((h_star, "h_star"), (y, "y"), (probe, "probe")):
+        if t is not None and tuple(t.shape) != (n, D):
+            raise nat.NativeError(f"{name} has shape {tuple(t.shape)}, expected {(n, D)}")
+    ae = lambda which: [f"autoencoder.{which}.mlp.mlp.{i}.{p}" for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
+    enc_names, dec_names = ae("encoder"), ae("decoder")
+    enc, dec = [state_dict[k] for k in enc_names], [state_dict[k] for k in dec_names]
+    fw = None
+    if h_star is None:
+        fw = fixed_point64(batch, state_dict, eps=fw_eps, threshold=fw_threshold)
+        h_star = fw["result"]
+    h_star = _f64c(h_star, "h_star")
+    plan = plan_for(batch)
+    h0 = mlp2_64(batch.x, *enc)
+    fmap = FixedPointMap64(plan, PackedWeights64(state_dict), h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
+    try:
+        new_h = fmap(h_star)
+    finally:
+        fmap.close()
+    u = mlp2_64(new_h, *dec)
+    # residual term: down to the cotangent of new_H
+    res_loss, g_r = mse64(residual64(plan, batch.a_ij, u, batch.y), None, need_grad=True)
+    g_u = residual64_t(plan, batch.a_ij, g_r)
+    grad_h, *dec_g1 = mlp2_64_backward(new_h, g_u, *dec[:3])
+    # encoder and autoencoder terms, u and new_H (then e and u) held constant
+    e = mlp2_64(u, *enc)
+    enc_loss, g_e = mse64(e, new_h, need_grad=True)
+    enc_g2 = mlp2_64_backward(u, g_e, *enc[:3], need_gx=False)[1:]
+    back = mlp2_64(e, *dec)
+    ae_loss, g_d = mse64(back, u, need_grad=True)
+    dec_g2 = mlp2_64_backward(e, g_d, *dec[:3], need_gx=False)[1:]
+    # the implicit backward: f's parameters and, through dH_init, the encoder
+    imp = implicit_grad64(batch, state_dict, h_star, grad_h, solver=solver, eps=eps, m=m, max_products=max_products, threshold=threshold,
+                          y=y)
+    grads = dict(imp["grads"])
+    jac_loss = 0.0
+    if probe is not None:
+        # jac_loss_grad64 with one probe, and d psi / dH_init besides.  d psi / dH* goes nowhere: H* is a leaf of the regulariser
+        # (model.py:204).  H_init is not: a multi-layer dirichlet block evaluates its Jacobian at states that carry H_init's
+        # Dirichlet rows, so there the regulariser reaches the encoder as well; for every other block that cotangent is exact zeros.
+        scale = 1.0 / (n * D)
+        fmap = FixedPointMap64(plan, PackedWeights64(state_dict), h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
+        try:
+            named, _, jtv, d_init = fmap.vjp_backward_init(h_star, probe, (2.0 * scale) * fmap.vjp(h_star, probe))
+        finally:
+            fmap.close()
+        jac_loss = float((jtv * jtv).sum()) * scale
+        if jac_weight != 0.0:
+            for k, t in named.items():
+                grads["deqdss.f." + k] = grads["deqdss.f." + k] + jac_weight * t
+            if n_layers_of(state_dict) > 1 and not is_mixed_state_dict(state_dict):
+                for k, t in zip(enc_names, mlp2_64_backward(batch.x, d_init, *enc[:3], need_gx=False)[1:]):
+                    grads[k] = grads[k] + jac_weight * t
+    for k, t in zip(enc_names, enc_g2):
+        grads[k] = grads[k] + t
+    for k, a, b in zip(dec_names, dec_g1, dec_g2):
+        grads[k] = a + b
+    for k, t in state_dict.items():
+        if k not in grads:
+            grads[k] = torch.zeros(tuple(t.shape), dtype=torch.float64, device=u.device)
+        else:
+            grads[k] = grads[k].reshape(tuple(t.shape))
+    sol = getattr(batch, "sol", None)
+    idx = torch.where(batch.tags == 1)[0]   # model.py:87 (mixed: one-hot tags -> every row)
+    loss_dic = {"residual_loss": float(res_loss), "encoder_loss": float(enc_loss), "autoencoder_loss": float(ae_loss),
+                "mse_loss": float("nan") if sol is None else float(mse64(u, sol)[0]),
+                "mse_dirichlet": float(mse64(u[idx], batch.x[idx])[0]) if idx.numel() else float("nan"),
+                "jacobian_loss": float(jac_loss)}
+    loss = loss_dic["residual_loss"] + jac_weight * loss_dic["jacobian_loss"] + loss_dic["encoder_loss"] + loss_dic["autoencoder_loss"]
+    return {"loss": loss, "loss_dic": loss_dic, "grads": {k: grads[k] for k in state_dict}, "h_star": h_star, "new_h": new_h, "u": u,
+            "grad_h": grad_h, "y": imp["y"], "forward": fw, "adjoint": imp["adjoint"]}
