@@ -821,6 +821,84 @@ int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* d_weights, i
                                  psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Newton-Krylov in float64 on the device with a pseudo-transient shift (csrc/newton_f64.hip, csrc/krylov_f64.hip): a second float64
+ * solver for the fixed point of f beside psignn_broyden64_solve, for the sizes at which Broyden stalls (I - J_f is indefinite there;
+ * (1 + sigma) I - J_f with sigma large enough is not).  Default-width library only.  All arrays float64 in the caller's numbering.
+ * replaces: the reference's --precision run of solver(f, x0, threshold, eps), dirichlet/psignn/model.py:189 (DeepEquilibrium.forward
+ *           with config["solver"] = broyden / anderson on float64 tensors); the reference has no Newton method there.
+ * ------------------------------------------------------------------------------------------ */
+/* The shifted linear solve shift * delta = A delta + d_b from delta = 0, A = J_f(d_h) (transposed = 0, the product psignn_f64_jvp) or
+ * J_f(d_h)^T (transposed = 1, psignn_f64_vjp); shift finite and >= 1.  The handle, basis, kernels and cycle structure of
+ * psignn_gmres64_solve_adjoint, with three differences: the shift on the Hessenberg's diagonal is `shift`; the residual is
+ * r = A delta + b - shift * delta; the measure is the linear one, rel = |r| / |b|, the solve ending at the head of a cycle on
+ * rel <= eta (stop_reason 1), on a cycle that did not halve rel (2) or on a spent budget (0), a cycle on |g_{j+1}| <= eta * |b| (the
+ * target of an inexact Newton step; the adjoint solve keeps its eps / 2).
+ * b = 0: delta = 0, stop_reason 1, no product.  d_work: the larger of psignn_f64_deriv_workspace_doubles(f, n_layers, 0) and (.., 1)
+ * doubles (smaller: PSIGNN_ENOMEM naming the bytes).  h_info, traces (rel: the linear measure), poll_every, determinism: as
+ * psignn_gmres64_solve_adjoint.  d_result aliases neither d_h nor d_b.
+ * replaces: nothing the reference runs -- the linear system of a Newton step on f(x) - x of dirichlet/psignn/model.py:189 in double
+ *           precision (transposed = 0) and its dual (transposed = 1; shift 1: the system of model.py:210-223). */
+int psignn_gmres64_solve_shifted(psignn_gmres64_t* s, const double* d_weights, int n_layers, const double* d_h,
+                                 const double* d_h_initial, const double* d_prb, const double* d_normals, const double* d_b,
+                                 double shift, int transposed, double eta, int max_products, int poll_every, double* d_work,
+                                 int64_t work_doubles, double* d_result, psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace,
+                                 double* h_abs_trace, void* stream);
+/* The policy of the outer loop, host only (no device is touched): from the shift sigma of an attempted step and |g| before (g_old) and
+ * at the trial point (g_new), *accept and the next shift.  Reject when g_new is not finite or g_new > growth * g_old: the next shift is
+ * max(4 sigma, reject_floor).  Accept otherwise: sigma * g_new / g_old (switched evolution relaxation), exactly 0 when that is below
+ * sigma_off.
+ * replaces: nothing of the reference (dirichlet/psignn/model.py:189 calls solvers without a globalisation). */
+double psignn_newton64_policy(double sigma, double g_old, double g_new, double growth, double reject_floor, double sigma_off,
+                              int* accept);
+/* Options of one solve.  The defaults the Python layer documents (sigma0 1, eta 1e-2, max_products 200, growth 2, reject_floor 1/16,
+ * sigma_off 1e-8, max_rejects 8, threshold 50) are starting values from CPU runs on the stored fixtures, not tuned on a GPU. */
+typedef struct {
+  double eps;           /* the solve ends on rel = |g| / (|f(x)| + 1e-9) < eps, g = f(x) - x (Broyden's measure, stop mode "rel") */
+  double sigma0;        /* the first shift is 1 + sigma0 */
+  double eta;           /* tolerance of every linear solve, |r| <= eta |g| */
+  double growth, reject_floor, sigma_off;   /* psignn_newton64_policy */
+  int32_t threshold;    /* attempted steps at most */
+  int32_t max_products; /* budget of every linear solve */
+  int32_t max_rejects;  /* the solve ends after this many consecutive rejections */
+  int32_t poll_every;   /* of the linear solves (<= 0: 8); changes neither bits nor counts */
+} psignn_newton64_opts_t;
+#define PSIGNN_NEWTON_THRESHOLD 0
+#define PSIGNN_NEWTON_TOLERANCE 1
+#define PSIGNN_NEWTON_REJECTS 2
+typedef struct {
+  int32_t nstep;        /* the accepted step of the lowest-rel state (0: the start) */
+  int32_t n_iter;       /* attempted steps */
+  int32_t n_accepted;   /* accepted steps */
+  int32_t n_products;   /* products J v spent by all linear solves */
+  int32_t n_feval;      /* evaluations of f: 1 + n_iter */
+  int32_t stop_reason;  /* PSIGNN_NEWTON_* */
+  double lowest, lowest_abs;
+} psignn_newton64_info_t;
+/* The handle owns a GMRES64 handle of restart length m, six state vectors of N * d doubles (x, f(x), g, the trial point, its f,
+ * delta), block partials and the two norms the host reads per attempted step.  create fails with PSIGNN_ENOMEM and a message naming
+ * the bytes when the basis or the vectors do not fit.  The solver borrows the map handle (and through it the plan).
+ * replaces: nothing kept between calls at dirichlet/psignn/model.py:189. */
+typedef struct psignn_newton64 psignn_newton64_t;
+int psignn_newton64_create(psignn_newton64_t** out, psignn_f64_t* f, int m /* restart length, 1 .. 4096 */);
+void psignn_newton64_destroy(psignn_newton64_t* s);   /* (model.py:189: nothing is kept there between solves) */
+size_t psignn_newton64_bytes(const psignn_newton64_t* s);   /* device bytes of the handle (model.py:189 has no counterpart) */
+/* One solve from d_x0.  Attempted step n: psignn_gmres64_solve_shifted on (1 + sigma_n) delta = J_f(x_n) delta + g(x_n), the trial
+ * point x_n + delta, f there, |g| and |f| by per-block partials summed by one block in a fixed order (no atomics), read by the host,
+ * which decides with psignn_newton64_policy: a rejected step leaves the state untouched bit for bit.  Ends on rel < eps, after
+ * `threshold` attempted steps or `max_rejects` consecutive rejections.  d_result: the accepted state with the lowest rel (d_x0 when no
+ * step went below it).  Host arrays, each may be NULL: h_rel_trace / h_abs_trace, threshold + 1 doubles, the start and every accepted
+ * state; h_sigma_trace, threshold + 1 doubles, sigma_0 and the shift after every decision; h_trial_abs (|g| at every trial point),
+ * h_accepted, h_krylov (products per attempted step), h_lin_stop (stop_reason of its linear solve): threshold entries each.
+ * d_work as for psignn_gmres64_solve_shifted.  The same call gives the same bits, whatever poll_every.  Synchronous.
+ * replaces: solver(lambda H: f(H, H_init, batch), H_init, threshold, eps) of dirichlet/psignn/model.py:189 in double precision, by
+ *           another method. */
+int psignn_newton64_solve(psignn_newton64_t* s, const double* d_weights, int n_layers, const double* d_x0, const double* d_h_initial,
+                          const double* d_prb, const double* d_normals, const psignn_newton64_opts_t* opts, double* d_work,
+                          int64_t work_doubles, double* d_result, psignn_newton64_info_t* h_info, double* h_rel_trace,
+                          double* h_abs_trace, double* h_sigma_trace, double* h_trial_abs, int32_t* h_accepted, int32_t* h_krylov,
+                          int32_t* h_lin_stop, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Parameter gradients in float64 on the device (csrc/fgnn_f64_deriv.hip): the last link of loss.backward() in double precision, and
  * the truth the fp32 parameter-gradient kernels are measured against, at any size.  Same handle, weights, numbering and rules as
  * psignn_f64_vjp.  Every gradient is a sum over receiving nodes: one workgroup per chunk of psignn_f64_param_vjp_chunk_rows()

@@ -61,6 +61,17 @@ class GmresAdjointInfo(C.Structure):
                 ("lowest", C.c_double), ("lowest_abs", C.c_double)]
 
 
+class Newton64Opts(C.Structure):
+    _fields_ = [("eps", C.c_double), ("sigma0", C.c_double), ("eta", C.c_double), ("growth", C.c_double), ("reject_floor", C.c_double),
+                ("sigma_off", C.c_double), ("threshold", C.c_int32), ("max_products", C.c_int32), ("max_rejects", C.c_int32),
+                ("poll_every", C.c_int32)]
+
+
+class Newton64Info(C.Structure):
+    _fields_ = [("nstep", C.c_int32), ("n_iter", C.c_int32), ("n_accepted", C.c_int32), ("n_products", C.c_int32),
+                ("n_feval", C.c_int32), ("stop_reason", C.c_int32), ("lowest", C.c_double), ("lowest_abs", C.c_double)]
+
+
 class CgInfo(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("converged", C.c_int32), ("rel", C.c_double), ("true_rel", C.c_double),
                 ("b_norm", C.c_double), ("sym_defect", C.c_double)]
@@ -227,6 +238,15 @@ SIGNATURES = {
     "psignn_gmres64_bytes": (C.c_size_t, [_P]),
     "psignn_gmres64_solve_adjoint": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, C.c_double, _INT, _INT, _P, _I64, _P,
                                             C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_gmres64_solve_shifted": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, C.c_double, _INT, C.c_double, _INT, _INT, _P, _I64, _P,
+                                            C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_newton64_policy": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(_INT)]),
+    "psignn_newton64_create": (_INT, [C.POINTER(_P), _P, _INT]),
+    "psignn_newton64_destroy": (None, [_P]),
+    "psignn_newton64_bytes": (C.c_size_t, [_P]),
+    "psignn_newton64_solve": (_INT, [_P, _P, _INT, _P, _P, _P, _P, C.POINTER(Newton64Opts), _P, _I64, _P, C.POINTER(Newton64Info),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "psignn_f64_param_vjp_chunk_rows": (_INT, []),
     "psignn_f64_param_vjp_workspace_doubles": (_I64, [_P, _INT]),
     "psignn_f64_param_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),

@@ -593,18 +593,19 @@ static int work_check(const char* who, int64_t need, const double* work, int64_t
   return PSIGNN_OK;
 }
 
-extern "C" int psignn_f64_jvp(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
-                              const double* nrm, const double* v, double* out, double* work, int64_t work_doubles, void* stream) {
+// The product with the flag of a solver (internal.h): every launch returns at once when *done is set (NULL: no flag).
+int psignn_f64_jvp_gated(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                         const double* nrm, const double* v, double* out, double* work, int64_t work_doubles, const int32_t* done,
+                         hipStream_t st) {
   ARG_CHECK(f && W && h && h0 && prb && v && out, "NULL argument");
   ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
   ARG_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
   ARG_CHECK(out != h && out != v, "out must not alias h or v");
-  const int rc = work_check(__func__, psignn_f64_deriv_workspace_doubles(f, nl, 0), work, work_doubles);
+  const int rc = work_check("psignn_f64_jvp", psignn_f64_deriv_workspace_doubles(f, nl, 0), work, work_doubles);
   if (rc) return rc;
   if (f->p->N == 0) return PSIGNN_OK;
-  hipStream_t st = (hipStream_t)stream;
   if (!f64_chain(f, nl)) {
-    jvp_launch(f, W, nl, nl - 1, 1, h, v, h0, prb, nrm, nullptr, out, nullptr, st);
+    jvp_launch(f, W, nl, nl - 1, 1, h, v, h0, prb, nrm, nullptr, out, done, st);
   } else {
     const int64_t row = f->p->N * D;
     const double *ch = h, *cv = v;
@@ -612,7 +613,7 @@ extern "C" int psignn_f64_jvp(psignn_f64_t* f, const double* W, int nl, const do
       const bool last = l == nl - 1;
       double* dh = last ? nullptr : work + (l & 1) * row;
       double* dv = last ? out : work + (2 + (l & 1)) * row;
-      jvp_launch(f, W, nl, l, last, ch, cv, h0, prb, nrm, dh, dv, nullptr, st);
+      jvp_launch(f, W, nl, l, last, ch, cv, h0, prb, nrm, dh, dv, done, st);
       ch = dh;
       cv = dv;
     }
@@ -621,7 +622,12 @@ extern "C" int psignn_f64_jvp(psignn_f64_t* f, const double* W, int nl, const do
   return PSIGNN_OK;
 }
 
-// The product with the flag of a solver (internal.h): every launch returns at once when *done is set (NULL: no flag).
+extern "C" int psignn_f64_jvp(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                              const double* nrm, const double* v, double* out, double* work, int64_t work_doubles, void* stream) {
+  return psignn_f64_jvp_gated(f, W, nl, h, h0, prb, nrm, v, out, work, work_doubles, nullptr, (hipStream_t)stream);
+}
+
+// The transposed product with the flag of a solver, likewise.
 int psignn_f64_vjp_gated(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
                          const double* nrm, const double* w, const double* add, double* out, double* work, int64_t work_doubles,
                          const int32_t* done, hipStream_t st) {

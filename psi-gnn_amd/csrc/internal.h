@@ -91,10 +91,18 @@ int psignn_f64_eval(psignn_f64_t* f, const double* W, int nl, const double* h, c
                     double* out, const int32_t* done, hipStream_t st);
 
 // ---- fgnn_f64_deriv.hip
-// psignn_f64_vjp with a solver's flag: every launch of the product returns at once when *done is set (NULL: no flag)
+// psignn_f64_jvp / psignn_f64_vjp with a solver's flag: every launch of the product returns at once when *done is set (NULL: no flag)
+int psignn_f64_jvp_gated(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
+                         const double* nrm, const double* v, double* out, double* work, int64_t work_doubles, const int32_t* done,
+                         hipStream_t st);
 int psignn_f64_vjp_gated(psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0, const double* prb,
                          const double* nrm, const double* w, const double* add, double* out, double* work, int64_t work_doubles,
                          const int32_t* done, hipStream_t st);
+
+// ---- krylov_f64.hip: the vector kernels of the float64 Newton loop (newton_f64.hip).  part: 2 * psignn_nt64_blocks(M) doubles.
+int64_t psignn_nt64_blocks(int64_t M);
+void psignn_nt64_resid_norms(int64_t M, const double* fx, const double* x, double* g, double* part, double* norms, hipStream_t st);
+void psignn_nt64_add(int64_t M, const double* x, const double* d, double* xt, hipStream_t st);
 
 // ---- plan.hip
 int psignn_exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* bsum, hipStream_t st);

@@ -29,6 +29,11 @@
 // poll_every Arnoldi steps: neither bits nor counts depend on poll_every.  Reductions (f64_common.h): per-wave / per-block partials,
 // then one block sums the partials, all in a fixed order: the same call gives the same bits.
 // Storage: vectors, basis (m + 1, M), coefficients and partials in float64.
+//
+// psignn_gmres64_solve_shifted is the same loop on shift * delta = A delta + b, A = J_f(h) (psignn_f64_jvp) or J_f(h)^T, for the
+// Newton step of newton_f64.hip: k_ag64_begin<true> forms r = (A delta + b) - shift * delta from the raw product and the partials of
+// |r|^2 and |b|^2, k_ag64_check<true> tests the linear measure |r| / |b| <= eta, k_gm64_finish puts `shift` on the diagonal (the
+// adjoint solve passes 1.0, which rounds as h - 1 always did) and ends a cycle on |g_{j+1}| <= eta |b| (the adjoint solve: eps / 2).  The Newton loop's three vector kernels live at the end of this unit.
 #include "f64_common.h"
 #include "gmres_dense.h"
 #include <math.h>
@@ -77,8 +82,10 @@ __global__ void k_ag64_init(G64State* st) {
 
 // r = f(y) - y -> r0 (first: y <- 0, f(y) = grad); partials of |r|^2 and |f(y)|^2.  M is even: a lane's two elements are both
 // inside or both outside.
+// LIN, the shifted solve: fy holds the raw product A y, r = (A y + grad) - shift y, and the second partial is |grad|^2.
+template <bool LIN>
 __global__ void __launch_bounds__(F64_TB) k_ag64_begin(int64_t M, int64_t nblk, const G64State* __restrict__ st, double* __restrict__ y,
-                                                       const double* __restrict__ fy, const double* __restrict__ grad,
+                                                       const double* __restrict__ fy, const double* __restrict__ grad, double shift,
                                                        double* __restrict__ r0, double* __restrict__ part, int first) {
   if (st->solved) return;
   __shared__ double sh[4];
@@ -95,8 +102,19 @@ __global__ void __launch_bounds__(F64_TB) k_ag64_begin(int64_t M, int64_t nblk, 
       f = *(const double2*)(fy + e);
       a = *(const double2*)(y + e);
     }
-    r.x = f.x - a.x;
-    r.y = f.y - a.y;
+    if (LIN) {
+      const double2 b = *(const double2*)(grad + e);
+      if (!first) {
+        f.x += b.x;
+        f.y += b.y;
+      }
+      r.x = fma(-shift, a.x, f.x);
+      r.y = fma(-shift, a.y, f.y);
+      f = b;
+    } else {
+      r.x = f.x - a.x;
+      r.y = f.y - a.y;
+    }
     *(double2*)(r0 + e) = r;
     sr = fma(r.y, r.y, r.x * r.x);
     sf = fma(f.y, f.y, f.x * f.x);
@@ -109,6 +127,8 @@ __global__ void __launch_bounds__(F64_TB) k_ag64_begin(int64_t M, int64_t nblk, 
   }
 }
 
+// LIN, the shifted solve: the linear measure rel = |r| / |b| (0 when r = 0), met at rel <= eps
+template <bool LIN>
 __global__ void __launch_bounds__(F64_TB) k_ag64_check(G64State* st, const double* __restrict__ part, int64_t nblk,
                                                        double* __restrict__ g, double* __restrict__ rel_trace,
                                                        double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
@@ -118,7 +138,7 @@ __global__ void __launch_bounds__(F64_TB) k_ag64_check(G64State* st, const doubl
   const double sf = f64_final_sum(part + nblk, nblk, sh);
   if (threadIdx.x != 0) return;
   const double nr = sqrt(sr), nf = sqrt(sf);
-  const double rel = nr / (nf + 1e-9);
+  const double rel = LIN ? (nr == 0.0 ? 0.0 : nr / nf) : nr / (nf + 1e-9);
   const int c = st->cycles;
   const int products = st->products + (c > 0 ? st->k + 1 : 0);   // the last cycle's steps and this cycle's residual
   st->products = products;
@@ -135,7 +155,7 @@ __global__ void __launch_bounds__(F64_TB) k_ag64_check(G64State* st, const doubl
   }
   const int left = min(m, max_products - products - 1);
   int done = 1, stop = 0;
-  if (rel < eps || nr == 0.0) stop = 1;                        // (a zero right-hand side: y = 0 is the answer)
+  if ((LIN ? rel <= eps : rel < eps) || nr == 0.0) stop = 1;   // (a zero right-hand side: y = 0 is the answer)
   else if (c > 0 && !(rel <= 0.5 * st->prev_rel)) stop = 2;   // (a NaN stops here too)
   else if (left <= 0) stop = 0;
   else done = 0;
@@ -271,7 +291,7 @@ __global__ void __launch_bounds__(F64_TB) k_gm64_decide(G64State* st, const doub
 
 // One block: column j of the Hessenberg matrix and the least-squares update.  `part` holds |w|^2 of the last pass that ran.
 __global__ void __launch_bounds__(F64_TB) k_gm64_finish(G64State* st, const double* __restrict__ part, int64_t nblk, int j, int m,
-                                                        double eta, double* __restrict__ hcol, double* __restrict__ R,
+                                                        double eta, double shift, double* __restrict__ hcol, double* __restrict__ R,
                                                         double* __restrict__ cs, double* __restrict__ sn, double* __restrict__ g) {
   if (st->done) return;
   __shared__ double sh[4];
@@ -279,7 +299,7 @@ __global__ void __launch_bounds__(F64_TB) k_gm64_finish(G64State* st, const doub
   if (threadIdx.x != 0) return;
   const double hn = sqrt(s2);
   st->hn = hn;
-  hcol[j] -= 1.0;   // Hessenberg of J^T - I from the Arnoldi relation of J^T
+  hcol[j] -= shift;   // Hessenberg of A - shift I from the Arnoldi relation of A (the adjoint solve: shift = 1)
   hcol[j + 1] = hn;
   const double resid = gmd_column(j, hcol, cs, sn, g);
   double* col = R + (int64_t)j * (m + 1);
@@ -313,6 +333,65 @@ __global__ void __launch_bounds__(F64_TB) k_gm64_combine(int64_t M, const G64Sta
   x.x -= acc.x;
   x.y -= acc.y;
   *(double2*)(y + e) = x;
+}
+
+// ------------------------------------------------------------------ the vector kernels of the Newton loop (newton_f64.hip)
+// g = f(x) - x; partials of |g|^2 and |f(x)|^2.  M is even: a lane's two elements are both inside or both outside.
+__global__ void __launch_bounds__(F64_TB) k_nt64_resid(int64_t M, int64_t nblk, const double* __restrict__ fx,
+                                                       const double* __restrict__ x, double* __restrict__ g,
+                                                       double* __restrict__ part) {
+  __shared__ double sh[4];
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
+  double sg = 0.0, sf = 0.0;
+  if (e < M) {
+    const double2 f = *(const double2*)(fx + e), a = *(const double2*)(x + e);
+    double2 r;
+    r.x = f.x - a.x;
+    r.y = f.y - a.y;
+    *(double2*)(g + e) = r;
+    sg = fma(r.y, r.y, r.x * r.x);
+    sf = fma(f.y, f.y, f.x * f.x);
+  }
+  sg = f64_block_sum(sg, sh);
+  sf = f64_block_sum(sf, sh);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = sg;
+    part[nblk + blockIdx.x] = sf;
+  }
+}
+
+__global__ void __launch_bounds__(F64_TB) k_nt64_norms(const double* __restrict__ part, int64_t nblk, double* __restrict__ norms) {
+  __shared__ double sh[4];
+  const double sg = f64_final_sum(part, nblk, sh);
+  const double sf = f64_final_sum(part + nblk, nblk, sh);
+  if (threadIdx.x == 0) {
+    norms[0] = sqrt(sg);
+    norms[1] = sqrt(sf);
+  }
+}
+
+__global__ void __launch_bounds__(F64_TB) k_nt64_add(int64_t M, const double* __restrict__ x, const double* __restrict__ d,
+                                                     double* __restrict__ xt) {
+  const int64_t e = ((int64_t)blockIdx.x * F64_TB + threadIdx.x) * 2;
+  if (e >= M) return;
+  const double2 a = *(const double2*)(x + e), b = *(const double2*)(d + e);
+  double2 r;
+  r.x = a.x + b.x;
+  r.y = a.y + b.y;
+  *(double2*)(xt + e) = r;
+}
+
+// (internal.h) block partials of a vector of M doubles; g = fx - x with |g| and |fx| into norms[0 .. 1]; xt = x + d
+int64_t psignn_nt64_blocks(int64_t M) { return cdiv(M, 2 * F64_TB); }
+void psignn_nt64_resid_norms(int64_t M, const double* fx, const double* x, double* g, double* part, double* norms, hipStream_t st) {
+  const int64_t nblk = psignn_nt64_blocks(M);
+  PROF_BYTES(3 * M * 8);
+  LAUNCH("k_nt64_resid", st, (k_nt64_resid<<<(unsigned)nblk, F64_TB, 0, st>>>(M, nblk, fx, x, g, part)));
+  LAUNCH("k_nt64_norms", st, (k_nt64_norms<<<1, F64_TB, 0, st>>>(part, nblk, norms)));
+}
+void psignn_nt64_add(int64_t M, const double* x, const double* d, double* xt, hipStream_t st) {
+  PROF_BYTES(3 * M * 8);
+  LAUNCH("k_nt64_add", st, (k_nt64_add<<<(unsigned)psignn_nt64_blocks(M), F64_TB, 0, st>>>(M, x, d, xt)));
 }
 
 // ------------------------------------------------------------------ host
@@ -390,36 +469,34 @@ static int g64_traces(psignn_gmres64* s, int max_products) {
   return PSIGNN_OK;
 }
 
-extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W, int nl, const double* h_star, const double* h0,
-                                            const double* prb, const double* nrm, const double* grad, double eps, int max_products,
-                                            int poll_every, double* work, int64_t work_doubles, double* result,
-                                            psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace,
-                                            void* stream) {
-  ARG_CHECK(s && W && h_star && h0 && prb && grad && work && result && h_info, "NULL argument");
-  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
-  ARG_CHECK(eps >= 0.0 && eps < INFINITY, "eps must be finite and >= 0");
-  ARG_CHECK(max_products >= 1 && max_products <= (1 << 24), "max_products out of range");
+// One solve on the handle.  LIN = false: the adjoint system y = J^T y + grad with Broyden's measure (shift 1, transposed).
+// LIN = true: shift * y = A y + grad with the linear measure, A = J (transposed = 0) or J^T; the residual's product is then the raw
+// one and k_ag64_begin adds grad.  The launches of the adjoint solve are those it has always made.
+template <bool LIN>
+static int g64_solve(const char* who, psignn_gmres64* s, const double* W, int nl, const double* h_star, const double* h0,
+                     const double* prb, const double* nrm, const double* grad, double shift, int transposed, double eps,
+                     int max_products, int poll_every, double* work, int64_t work_doubles, double* result,
+                     psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace, hipStream_t st) {
   if (poll_every <= 0) poll_every = 8;
   int rc;
   if ((rc = g64_traces(s, max_products))) return rc;
-  hipStream_t st = (hipStream_t)stream;
   const int64_t M = s->M, nblk = s->nblk;
   const int m = s->m;
   const unsigned g2 = (unsigned)nblk, gc = (unsigned)s->nchunk;
   double *y = s->vec, *fy = s->vec + M, *ybest = s->vec + 2 * M;
   const int32_t* cycle_done = &s->st->done;
-  auto product = [&](const double* x, double* out, const int32_t* done) {
-    return psignn_f64_vjp_gated(s->f, W, nl, h_star, h0, prb, nrm, x, nullptr, out, work, work_doubles, done, st);
+  auto product = [&](const double* x, const double* add, double* out, const int32_t* done) {
+    if (transposed) return psignn_f64_vjp_gated(s->f, W, nl, h_star, h0, prb, nrm, x, add, out, work, work_doubles, done, st);
+    return psignn_f64_jvp_gated(s->f, W, nl, h_star, h0, prb, nrm, x, out, work, work_doubles, done, st);
   };
   k_ag64_init<<<1, 1, 0, st>>>(s->st);
   for (int cycle = 0;; ++cycle) {
     // the residual's product is not gated: the flag of the cycle that just ended is still up
-    if (cycle > 0 && (rc = psignn_f64_vjp_gated(s->f, W, nl, h_star, h0, prb, nrm, y, grad, fy, work, work_doubles, nullptr, st)))
-      return rc;
-    PROF_BYTES(3 * M * 8);
-    LAUNCH("k_ag64_begin", st, (k_ag64_begin<<<g2, F64_TB, 0, st>>>(M, nblk, s->st, y, fy, grad, s->V, s->part, cycle == 0)));
-    LAUNCH("k_ag64_check", st, (k_ag64_check<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, s->g, s->rel_trace, s->abs_trace, s->cap, eps,
-                                                                  max_products, m)));
+    if (cycle > 0 && (rc = product(y, LIN ? nullptr : grad, fy, nullptr))) return rc;
+    PROF_BYTES((3 + LIN) * M * 8);
+    LAUNCH("k_ag64_begin", st, (k_ag64_begin<LIN><<<g2, F64_TB, 0, st>>>(M, nblk, s->st, y, fy, grad, shift, s->V, s->part, cycle == 0)));
+    LAUNCH("k_ag64_check", st, (k_ag64_check<LIN><<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, s->g, s->rel_trace, s->abs_trace, s->cap,
+                                                                       eps, max_products, m)));
     PROF_BYTES(2 * M * 8);
     LAUNCH("k_ag64_keep", st, (k_ag64_keep<<<g2, F64_TB, 0, st>>>(M, s->st, y, ybest)));
     PROF_BYTES(2 * M * 8);
@@ -429,12 +506,12 @@ extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W
     if (s->h_st->solved) break;
     const int steps = s->h_st->steps_left;
     if (steps < 1 || steps > m) {
-      psignn_set_error("psignn_gmres64_solve_adjoint: internal: %d Arnoldi steps allowed, restart length %d", steps, m);
+      psignn_set_error("%s: internal: %d Arnoldi steps allowed, restart length %d", who, steps, m);
       return PSIGNN_EHIP;
     }
     for (int j = 0; j < steps; ++j) {
       double* w = s->V + (size_t)(j + 1) * M;
-      if ((rc = product(s->V + (size_t)j * M, w, cycle_done))) return rc;
+      if ((rc = product(s->V + (size_t)j * M, nullptr, w, cycle_done))) return rc;
       for (int pass = 0; pass < 2; ++pass) {
         PROF_BYTES(((int64_t)j + 2 + (pass == 0)) * M * 8);
         LAUNCH("k_gm64_dots", st, (k_gm64_dots<<<gc, F64_TB, 0, st>>>(M, s->nchunk, j, pass, s->st, s->V, s->partD)));
@@ -444,8 +521,8 @@ extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W
         LAUNCH("k_gm64_axpy", st, (k_gm64_axpy<<<g2, F64_TB, 0, st>>>(M, j, pass, s->st, s->V, s->coef, s->part)));
         if (pass == 0) LAUNCH("k_gm64_decide", st, (k_gm64_decide<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk)));
       }
-      LAUNCH("k_gm64_finish", st, (k_gm64_finish<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, j, m, 0.5 * eps, s->hcol, s->R, s->cs, s->sn,
-                                                                      s->g)));
+      LAUNCH("k_gm64_finish", st, (k_gm64_finish<<<1, F64_TB, 0, st>>>(s->st, s->part, nblk, j, m, LIN ? eps : 0.5 * eps, shift, s->hcol, s->R, s->cs,
+                                                                      s->sn, s->g)));
       PROF_BYTES(2 * M * 8);
       LAUNCH("k_gm64_scale", st, (k_gm64_scale<<<g2, F64_TB, 0, st>>>(M, s->st, w, &s->st->hn, w)));
       if ((j + 1) % poll_every == 0 && j + 1 < steps) {
@@ -461,8 +538,7 @@ extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W
   HIP_TRY(hipGetLastError());
   const G64State& h = *s->h_st;
   if (h.cycles < 1 || h.products < 0 || h.products > max_products) {
-    psignn_set_error("psignn_gmres64_solve_adjoint: internal: %d cycles, %d products recorded, budget %d", h.cycles, h.products,
-                     max_products);
+    psignn_set_error("%s: internal: %d cycles, %d products recorded, budget %d", who, h.cycles, h.products, max_products);
     return PSIGNN_EHIP;
   }
   const int n = h.cycles < s->cap ? h.cycles : s->cap;
@@ -477,4 +553,43 @@ extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W
   h_info->lowest = h.lowest;
   h_info->lowest_abs = h.lowest_abs;
   return PSIGNN_OK;
+}
+
+extern "C" int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* W, int nl, const double* h_star, const double* h0,
+                                            const double* prb, const double* nrm, const double* grad, double eps, int max_products,
+                                            int poll_every, double* work, int64_t work_doubles, double* result,
+                                            psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace,
+                                            void* stream) {
+  ARG_CHECK(s && W && h_star && h0 && prb && grad && work && result && h_info, "NULL argument");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(eps >= 0.0 && eps < INFINITY, "eps must be finite and >= 0");
+  ARG_CHECK(max_products >= 1 && max_products <= (1 << 24), "max_products out of range");
+  return g64_solve<false>(__func__, s, W, nl, h_star, h0, prb, nrm, grad, 1.0, 1, eps, max_products, poll_every, work, work_doubles,
+                          result, h_info, h_rel_trace, h_abs_trace, (hipStream_t)stream);
+}
+
+// The shifted linear solve shift * delta = A delta + b from delta = 0, A = J_f(h) (transposed = 0) or J_f(h)^T: the linear system of
+// a Newton step on g(x) = f(x) - x with a pseudo-transient shift, (1 + sigma) delta = J delta + g (newton_f64.hip), and its dual.
+// The handle, the basis, the kernels and the cycle structure of the adjoint solve; the shift on the Hessenberg's diagonal, the
+// residual r = A delta + b - shift * delta, the linear measure rel = |r| / |b| with rel <= eta as the tolerance and |g_{j+1}| <=
+// eta * |b| as the inner target (an inexact Newton step asks for no more; the head of the next cycle confirms it on the true residual).  The workspace is the larger of the two products'.
+extern "C" int psignn_gmres64_solve_shifted(psignn_gmres64_t* s, const double* W, int nl, const double* h, const double* h0,
+                                            const double* prb, const double* nrm, const double* b, double shift, int transposed,
+                                            double eta, int max_products, int poll_every, double* work, int64_t work_doubles,
+                                            double* result, psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace,
+                                            double* h_abs_trace, void* stream) {
+  ARG_CHECK(s && W && h && h0 && prb && b && result && h_info, "NULL argument");
+  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK(shift >= 1.0 && shift < INFINITY, "shift must be finite and >= 1");
+  ARG_CHECK(eta >= 0.0 && eta < INFINITY, "eta must be finite and >= 0");
+  ARG_CHECK(max_products >= 1 && max_products <= (1 << 24), "max_products out of range");
+  ARG_CHECK(result != h && result != b, "result must not alias h or b");
+  const int64_t need = ws::shifted64_total(psignn_f64_deriv_workspace_doubles(s->f, nl, 0), psignn_f64_deriv_workspace_doubles(s->f, nl, 1));
+  if (need > 0 && (!work || work_doubles < need)) {
+    psignn_set_error("%s: the workspace holds %lld doubles, %lld are needed (%lld bytes)", __func__, (long long)(work ? work_doubles : 0),
+                     (long long)need, (long long)need * 8);
+    return PSIGNN_ENOMEM;
+  }
+  return g64_solve<true>(__func__, s, W, nl, h, h0, prb, nrm, b, shift, transposed != 0, eta, max_products, poll_every, work, work_doubles,
+                         result, h_info, h_rel_trace, h_abs_trace, (hipStream_t)stream);
 }

@@ -187,4 +187,18 @@ inline AdjWork adj_work(int64_t N, int nl, bool mixed, float* base) {
 // elements, in chunk order; one block then adds them (poisson_cg.hip)
 constexpr int64_t MSE64_CHUNK = 1024;
 inline int64_t mse64_total(int64_t n_elems) { return (n_elems + MSE64_CHUNK - 1) / MSE64_CHUNK; }
+
+// ---- float64 Newton-Krylov (psignn_gmres64_solve_shifted, psignn_newton64_solve; DOUBLES)
+// The caller's product workspace: one region that either product carves as psignn_f64_deriv_workspace_doubles describes it -- the
+// larger of the J v and the J^T w counts (the solve runs one orientation per call).
+inline int64_t shifted64_total(int64_t jvp_doubles, int64_t vjp_doubles) { return jvp_doubles > vjp_doubles ? jvp_doubles : vjp_doubles; }
+// The Newton handle's own state, M = N * W doubles each, in this order, without padding:
+//   x | f(x) | g = f(x) - x | x_t (the trial point) | f(x_t) | delta (the step; g(x_t) once x_t is formed)
+// An accepted step swaps the roles of (x, f(x), g) and (x_t, f(x_t), delta); a rejected one writes only the last three.
+struct Newton64Vecs { double *x, *fx, *g, *xt, *fxt, *delta; int64_t total; };
+inline Newton64Vecs newton64_vecs(int64_t N, double* base) {
+  const int64_t M = N * W;
+  auto at = [&](int64_t k) { return base ? base + k * M : nullptr; };
+  return Newton64Vecs{at(0), at(1), at(2), at(3), at(4), at(5), 6 * M};
+}
 }  // namespace ws

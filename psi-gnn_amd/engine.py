@@ -2026,6 +2026,11 @@ class FixedPointMap64:
             have = self._deriv_work[transposed] = torch.empty(n, dtype=torch.float64, device=self.device)
         return (have if n else None), n
 
+    def _work_both(self):
+        """The workspace of a solve that runs either product: the larger of the two (``psignn_gmres64_solve_shifted``)."""
+        a, b = self._work(False), self._work(True)
+        return a if a[1] > b[1] else b
+
     def jvp(self, H, V):
         """``J_f(H) V`` in float64 (``psignn_f64_jvp``): H, V (N, 10), float32 (widened exactly) or float64; float64 comes out.
         Deterministic."""
@@ -2232,10 +2237,133 @@ class DeviceGmres64:
                 rel, abs_, nat.stream_ptr(self.device)), "psignn_gmres64_solve_adjoint")
         return DeviceGmres._result(info, rel, abs_, result)
 
+    def solve_shifted(self, h, b, shift=1.0, transposed=False, eta=1e-2, max_products=200, poll_every=8):
+        """``shift * delta = A delta + b`` from ``delta = 0`` (``psignn_gmres64_solve_shifted``), ``A = J_f(h)`` or, ``transposed``,
+        ``J_f(h)^T``: the linear system of a Newton step on ``f(x) - x`` with a pseudo-transient shift, and its dual.  ``shift`` finite
+        and >= 1; ``h``, ``b``: (N, 10), float32 (widened exactly) or float64.  Returns the dict of ``solve_adjoint``; ``rel_trace``
+        and ``lowest`` are the linear measure ``|A delta + b - shift delta| / |b|``, met at ``rel <= eta``.  ``b = 0`` gives
+        ``delta = 0`` without a product.  Deterministic; ``poll_every`` changes neither bits nor counts."""
+        if self.handle is None or self.fmap.handle is None:
+            raise nat.NativeError("DeviceGmres64 (or its map) is closed")
+        if int(max_products) < 1:
+            raise nat.NativeError(f"max_products must be >= 1, got {max_products}")
+        if not (math.isfinite(float(shift)) and float(shift) >= 1.0):
+            raise nat.NativeError(f"shift must be finite and >= 1, got {shift}")
+        if not (math.isfinite(float(eta)) and float(eta) >= 0.0):
+            raise nat.NativeError(f"eta must be finite and >= 0, got {eta}")
+        fm = self.fmap
+        nat.require_default_width(getattr(getattr(fm, "weights", None), "width", D), "DeviceGmres64.solve_shifted")
+        hs, bc = fm._states((h, "h"), (b, "b"))
+        result = torch.empty_like(bc)
+        info = nat.GmresAdjointInfo()
+        cap = int(max_products) // 2 + 3
+        rel, abs_ = (C.c_double * cap)(), (C.c_double * cap)()
+        work, n = fm._work_both()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_gmres64_solve_shifted(
+                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(hs), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                nat.ptr(bc), float(shift), int(bool(transposed)), float(eta), int(max_products), int(poll_every), nat.ptr(work), n,
+                nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device)), "psignn_gmres64_solve_shifted")
+        return DeviceGmres._result(info, rel, abs_, result)
 
-def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16):
-    """encoder -> float64 Broyden solve -> decoder, all in float64 on the device, for a device batch and a reference state dict
-    (default latent width).  Returns the solver's dictionary plus ``h0`` (the encoded start) and ``u`` (the decoded result)."""
+
+NEWTON_STOPS = ("threshold", "tolerance", "rejects")   # stop_reason of psignn_newton64_info_t
+
+
+def newton64_policy(sigma, g_old, g_new, growth=2.0, reject_floor=0.0625, sigma_off=1e-8):
+    """``psignn_newton64_policy`` (host only, no GPU needed): ``(accepted, next sigma)`` of one attempted step of
+    ``DeviceNewton64`` from the shift it ran with and ``|g|`` before and at the trial point."""
+    acc = C.c_int(0)
+    nxt = nat.lib().psignn_newton64_policy(float(sigma), float(g_old), float(g_new), float(growth), float(reject_floor),
+                                           float(sigma_off), C.byref(acc))
+    return bool(acc.value), float(nxt)
+
+
+class DeviceNewton64:
+    """Newton-Krylov root-find of ``g(x) = f(x) - x`` in float64 on a ``FixedPointMap64`` with a pseudo-transient shift
+    (``psignn_newton64_*``, csrc/newton_f64.hip): attempted step n solves ``(1 + sigma_n) delta = J_f(x_n) delta + g(x_n)`` with
+    ``DeviceGmres64.solve_shifted``'s solve (restart length ``m``), evaluates ``f`` at ``x_n + delta`` and lets
+    ``psignn_newton64_policy`` accept or reject from ``|g|`` there.  The basis is ``(m + 1) * N * 10 * 8`` bytes, the state six
+    vectors more; creation raises ``NativeError`` naming the bytes when the device cannot hold them.
+
+    The defaults of ``solve`` (``sigma0`` 1, ``eta`` 1e-2, ``max_products`` 200, ``growth`` 2, ``reject_floor`` 1/16, ``sigma_off``
+    1e-8, ``max_rejects`` 8, ``threshold`` 50, ``m`` 50) are starting values from float64 CPU runs on the stored fixtures.  They are
+    not tuned on a GPU."""
+
+    def __init__(self, fmap64, m=50):
+        if getattr(fmap64, "handle", None) is None:
+            raise nat.NativeError("DeviceNewton64 needs an open FixedPointMap64")
+        nat.require_default_width(getattr(getattr(fmap64, "weights", None), "width", D), "DeviceNewton64")
+        self.fmap, self.m, self.device = fmap64, int(m), fmap64.device
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_newton64_create(C.byref(h), fmap64.handle, self.m), "psignn_newton64_create")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_newton64_destroy, h)
+
+    def close(self):
+        self._fin()
+        self.handle = None
+
+    @property
+    def nbytes(self):
+        return int(nat.lib().psignn_newton64_bytes(self.handle))
+
+    def solve(self, x0, eps=1e-11, threshold=50, sigma0=1.0, eta=1e-2, max_products=200, growth=2.0, reject_floor=0.0625,
+              sigma_off=1e-8, max_rejects=8, poll_every=8):
+        """From ``x0`` ((N, 10), float32 widened exactly or float64).  Ends on ``rel = |g| / (|f(x)| + 1e-9) < eps`` (Broyden's
+        measure), after ``threshold`` attempted steps or after ``max_rejects`` consecutive rejections.  Returns ``result`` (the
+        accepted state with the lowest rel, float64, caller's numbering), ``lowest``, ``nstep`` (the accepted step of that state; 0:
+        the start), ``n_iter`` (attempted steps), ``n_products``, ``n_feval``, ``rel_trace`` / ``abs_trace`` (the start and every
+        accepted state), ``sigma_trace`` (``sigma0`` and the shift after every decision: entry i is the shift of attempted step i),
+        ``accepted``, ``trial_abs`` (``|g|`` at every trial point), ``krylov`` (products per attempted step), ``lin_stop`` (the
+        linear solve's stop reason per attempted step, one of ``GMRES_STOPS``) and ``stop_reason`` (one of ``NEWTON_STOPS``).
+        A rejected step leaves the state untouched bit for bit.  Deterministic; ``poll_every`` changes neither bits nor counts."""
+        if self.handle is None or self.fmap.handle is None:
+            raise nat.NativeError("DeviceNewton64 (or its map) is closed")
+        fm = self.fmap
+        nat.require_default_width(getattr(getattr(fm, "weights", None), "width", D), "DeviceNewton64.solve")
+        for v, name, low in ((eps, "eps", 0.0), (eta, "eta", 0.0), (sigma0, "sigma0", 0.0), (sigma_off, "sigma_off", 0.0)):
+            if not (math.isfinite(float(v)) and float(v) >= low):
+                raise nat.NativeError(f"{name} must be finite and >= {low:g}, got {v}")
+        for v, name in ((growth, "growth"), (reject_floor, "reject_floor")):
+            if not (math.isfinite(float(v)) and float(v) > 0.0):
+                raise nat.NativeError(f"{name} must be finite and > 0, got {v}")
+        for v, name in ((threshold, "threshold"), (max_products, "max_products"), (max_rejects, "max_rejects")):
+            if int(v) < 1:
+                raise nat.NativeError(f"{name} must be >= 1, got {v}")
+        x0c = fm._state(x0, "x0")
+        result = torch.empty_like(x0c)
+        T = int(threshold)
+        opts = nat.Newton64Opts(float(eps), float(sigma0), float(eta), float(growth), float(reject_floor), float(sigma_off), T,
+                                int(max_products), int(max_rejects), int(poll_every))
+        info = nat.Newton64Info()
+        rel, abs_, sig, trial = ((C.c_double * (T + 1))() for _ in range(4))
+        acc, kry, lst = ((C.c_int32 * T)() for _ in range(3))
+        work, n = fm._work_both()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_newton64_solve(
+                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(x0c), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                C.byref(opts), nat.ptr(work), n, nat.ptr(result), C.byref(info), rel, abs_, sig, trial, acc, kry, lst,
+                nat.stream_ptr(self.device)), "psignn_newton64_solve")
+        n_it, n_acc = int(info.n_iter), int(info.n_accepted)
+        return {"result": result, "lowest": float(info.lowest), "lowest_abs": float(info.lowest_abs), "nstep": int(info.nstep),
+                "n_iter": n_it, "n_products": int(info.n_products), "n_feval": int(info.n_feval),
+                "rel_trace": list(rel[:n_acc + 1]), "abs_trace": list(abs_[:n_acc + 1]), "sigma_trace": list(sig[:n_it + 1]),
+                "accepted": [bool(a) for a in acc[:n_it]], "trial_abs": list(trial[:n_it]), "krylov": list(kry[:n_it]),
+                "lin_stop": [GMRES_STOPS[int(c)] for c in lst[:n_it]], "stop_reason": NEWTON_STOPS[int(info.stop_reason)]}
+
+
+def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16, solver="broyden", **solver_kwargs):
+    """encoder -> float64 solve -> decoder, all in float64 on the device, for a device batch and a reference state dict (default
+    latent width).  ``solver="broyden"`` (the default): ``DeviceBroyden64(threshold)``.  ``solver="newton"``:
+    ``DeviceNewton64(m)`` from the encoder's ``h0`` with ``eps``, ``threshold`` (attempted steps at most) and ``poll_every`` as given
+    here; ``solver_kwargs`` are ``m`` and the other keywords of ``DeviceNewton64.solve``.
+    Returns the solver's dictionary plus ``h0`` (the encoded start) and ``u`` (the decoded result)."""
+    if solver not in ("broyden", "newton"):
+        raise nat.NativeError(f"fixed_point64: solver must be 'broyden' or 'newton', got {solver!r}")
+    if solver == "broyden" and solver_kwargs:
+        raise nat.NativeError(f"fixed_point64: solver 'broyden' takes no further keywords, got {sorted(solver_kwargs)}")
     w = PackedWeights64(state_dict)
     ae = lambda k: state_dict["autoencoder." + k]
     enc = [ae(f"encoder.mlp.mlp.{i}.{p}") for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
@@ -2243,11 +2371,18 @@ def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16):
     plan = plan_for(batch)
     h0 = mlp2_64(batch.x, *enc)
     fmap = FixedPointMap64(plan, w, h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
-    solver = DeviceBroyden64(fmap, threshold)
+    sv = None
     try:
-        out = solver.solve(h0, eps, poll_every)
+        if solver == "newton":
+            kw = dict(solver_kwargs)
+            sv = DeviceNewton64(fmap, kw.pop("m", 50))
+            out = sv.solve(h0, eps=eps, threshold=threshold, poll_every=poll_every, **kw)
+        else:
+            sv = DeviceBroyden64(fmap, threshold)
+            out = sv.solve(h0, eps, poll_every)
     finally:
-        solver.close()
+        if sv is not None:
+            sv.close()
         fmap.close()
     out["h0"] = h0
     out["u"] = mlp2_64(out["result"], *dec)
