@@ -46,13 +46,15 @@ extern int g_knob_epoch;
     }                                                                                   \
   } while (0)
 
-#define ARG_CHECK(cond, msg)                                   \
+// who: the entry point the message names (an implementation shared by two entry points passes the one that was called)
+#define ARG_CHECK_AS(who, cond, msg)                           \
   do {                                                         \
     if (!(cond)) {                                             \
-      psignn_set_error("%s: %s", __func__, msg);               \
+      psignn_set_error("%s: %s", who, msg);                    \
       return PSIGNN_EINVAL;                                    \
     }                                                          \
   } while (0)
+#define ARG_CHECK(cond, msg) ARG_CHECK_AS(__func__, cond, msg)
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

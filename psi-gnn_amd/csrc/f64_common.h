@@ -1,5 +1,6 @@
-// What the float64 reference path shares (gfx950): the weight layout and the map handle of fgnn_f64.hip / fgnn_f64_deriv.hip, and the
-// block shape and fixed-order reductions of solver_f64.hip, krylov_f64.hip and poisson_cg.hip.  Included by those five and nothing else.
+// What the float64 reference path shares (gfx950): the weight layout, the map handle and the family dispatch of fgnn_f64.hip /
+// fgnn_f64_deriv.hip (their arithmetic is f64_node.h's), and the block shape and fixed-order reductions of solver_f64.hip,
+// krylov_f64.hip and poisson_cg.hip.  Included by those five, by f64_node.h and by nothing else.
 #pragma once
 #include "common.h"
 #include "internal.h"
@@ -36,6 +37,22 @@ struct psignn_f64 {
 };
 // both edge lists and the node flags of a map handle, in the order every layer kernel takes them
 #define F64_EDGES(f) (f)->p->csr_ptr, (f)->p->csr_nbr, (f)->csr_attr, (f)->p->csc_ptr, (f)->p->csc_nbr, (f)->csc_attr, (f)->p->flags
+// The family of a plan: runs the statements with P, MIXED and L = W64<P> of a mixed plan (<3, true>) or a dirichlet one (<2, false>),
+// so that every launch picks its instantiation and the matching L::layer(l) / L::layer(nl) offsets in one place.
+#define F64_FAMILY(mixed, ...)                        \
+  do {                                                \
+    if (mixed) {                                      \
+      [[maybe_unused]] constexpr int P = 3;           \
+      [[maybe_unused]] constexpr bool MIXED = true;   \
+      using L [[maybe_unused]] = W64<3>;              \
+      __VA_ARGS__;                                    \
+    } else {                                          \
+      [[maybe_unused]] constexpr int P = 2;           \
+      [[maybe_unused]] constexpr bool MIXED = false;  \
+      using L [[maybe_unused]] = W64<2>;              \
+      __VA_ARGS__;                                    \
+    }                                                 \
+  } while (0)
 
 #define F64_TB 256       // threads per block of the vector and reduction kernels: four waves, one partial per block
 #define F64_CHUNK 1024   // elements of a dots chunk: 8 x (64 lanes x 2 doubles)

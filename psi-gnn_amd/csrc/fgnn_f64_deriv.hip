@@ -9,316 +9,27 @@
 // the reference, differentiated line by line; nothing shared with fgnn_tile_*.hip, fgnn_vjp.hip or WLayout; no atomics and a fixed
 // summation order, so the same call gives the same bits.
 //
-// J v: one launch per layer gives the layer's value and its tangent together (k_f64_jvp_layer), so a multi-layer dirichlet chain
-// stores no states.
+// The node block -- the per-edge pieces, the node's forward with or without a tangent, LayerNorm, the node's reverse -- is
+// f64_node.h's, stated once; the kernels here keep what is theirs: the loads, the stores and the LDS rounds.
+//
+// J v: one launch per layer gives the layer's value and its tangent together (k_f64_jvp_layer, f64_node.h), so a multi-layer
+// dirichlet chain stores no states.
 // J^T w: two gather passes, no scatter.  An edge (r, c) sits once in r's CSR list and once in c's CSC list with the same attribute
 // row, so what a scatter would add to the sending node is gathered there from the receiving nodes' records:
 //   pass A (k_f64_vjp_node), per receiving node n: the node's forward again, w_n back through LayerNorm, gate and update (or
-//          update_neumann), the node-local part of the result -- the x_i side of its own edges' messages included -- and the
+//          update_neumann) -- the shared forward and reverse pieces --, the node-local part of the result -- the x_i side of its own edges' messages included -- and the
 //          cotangents of its message sums C[n] = {c_to, c_from (, c_neu)}, zero on Dirichlet rows;
 //   pass B (k_f64_vjp_edge), per sending node m: over m's CSR entries the x_j side of Phi_to at the neighbour with the neighbour's
 //          c_to, over m's CSC entries the x_j side of Phi_from with c_from (Neumann neighbours: Phi_neumann with c_neu); every ReLU
 //          mask recomputed from h.  Optionally + a vector to add, which makes the map of the adjoint system y -> J^T y + grad one call.
-// ReLU': 1 where the pre-activation is > 0 (torch's threshold_backward).
 // Every kernel takes the done flag of a solver (NULL: none) and returns at once when it is set: psignn_f64_vjp_gated is the product of
 // the float64 adjoint solves (solver_f64.hip, krylov_f64.hip), whose launches queued past the end of a solve or cycle change nothing.
-// The weight layout W64 and the map handle psignn_f64 are those of fgnn_f64.hip: both files take them from f64_common.h.
+// The weight layout W64, the map handle psignn_f64 and the family dispatch F64_FAMILY are those of fgnn_f64.hip: both files take
+// them from f64_common.h.
 #include "f64_common.h"
+#include "f64_node.h"
 #include <math.h>
-
-// ---------------------------------------------------------------------------------------------
-// per edge
-// ---------------------------------------------------------------------------------------------
-// s = W1 [x_i; x_j; a] + b1, the pre-activations of one message (the order of fgnn_f64.hip's f64_message)
-__device__ __forceinline__ void d64_pre(const double* __restrict__ Wp, const double* xi, const double* xj, const double* a, double* s) {
-  using L = W64<2>;   // the Phi block has the same shape in both families
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    const double* w = Wp + L::PHI_W1 + o * L::EIN;
-    double t = Wp[L::PHI_B1 + o];
-#pragma unroll
-    for (int k = 0; k < D; ++k) t = fma(w[k], xi[k], t);
-#pragma unroll
-    for (int k = 0; k < D; ++k) t = fma(w[D + k], xj[k], t);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) t = fma(w[2 * D + k], a[k], t);
-    s[o] = t;
-  }
-}
-__device__ __forceinline__ void d64_row(const double* __restrict__ h, int64_t u, double* x) {
-#pragma unroll
-  for (int k = 0; k < D; ++k) x[k] = h[u * D + k];
-}
-// q = W2^T c: the cotangent of a message's hidden layer before the ReLU mask
-__device__ __forceinline__ void d64_w2t(const double* __restrict__ Wp, const double* c, double* q) {
-  using L = W64<2>;
-#pragma unroll
-  for (int k = 0; k < D; ++k) q[k] = 0.0;
-#pragma unroll
-  for (int o = 0; o < D; ++o)
-#pragma unroll
-    for (int k = 0; k < D; ++k) q[k] = fma(Wp[L::PHI_W2 + o * D + k], c[o], q[k]);
-}
-
-// Sum of the messages of one Phi module over one edge list of node n, and (TAN) of their tangents along (dx, v):
-// d message = W2 (1[s > 0] * (W1_i dx + W1_j v_u)).
-template <bool TAN>
-__device__ __forceinline__ void d64_phi(const double* __restrict__ Wp, const double* x, const double* dx, const double* __restrict__ h,
-                                        const double* __restrict__ v, int32_t beg, int32_t end, const int32_t* __restrict__ nbr,
-                                        const double* __restrict__ attr, double* mp, double* dmp) {
-  using L = W64<2>;
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    mp[o] = 0.0;
-    if (TAN) dmp[o] = 0.0;
-  }
-  for (int32_t i = beg; i < end; ++i) {
-    const int64_t u = nbr[i];
-    double xj[D], a[3], s[D], t[D];
-    d64_row(h, u, xj);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] = attr[3 * (int64_t)i + k];
-    d64_pre(Wp, x, xj, a, s);
-    if (TAN) {
-      double dxj[D];
-      d64_row(v, u, dxj);
-#pragma unroll
-      for (int o = 0; o < D; ++o) {
-        const double* w = Wp + L::PHI_W1 + o * L::EIN;
-        double r = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(w[k], dx[k], r);
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(w[D + k], dxj[k], r);
-        t[o] = s[o] > 0.0 ? r : 0.0;
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o) s[o] = fmax(s[o], 0.0);
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      const double* w = Wp + L::PHI_W2 + o * D;
-      double r = Wp[L::PHI_B2 + o];
-#pragma unroll
-      for (int k = 0; k < D; ++k) r = fma(w[k], s[k], r);
-      mp[o] += r;
-      if (TAN) {
-        double dr = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) dr = fma(w[k], t[k], dr);
-        dmp[o] += dr;
-      }
-    }
-  }
-}
-
-// x_i side of the messages node n receives over one edge list: gx += sum_e W1_i^T (1[s_e > 0] * q), q = W2^T c of the node
-__device__ __forceinline__ void d64_phi_vjp_xi(const double* __restrict__ Wp, const double* x, const double* __restrict__ h, int32_t beg,
-                                               int32_t end, const int32_t* __restrict__ nbr, const double* __restrict__ attr,
-                                               const double* q, double* gx) {
-  using L = W64<2>;
-  for (int32_t i = beg; i < end; ++i) {
-    double xj[D], a[3], s[D];
-    d64_row(h, nbr[i], xj);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) a[k] = attr[3 * (int64_t)i + k];
-    d64_pre(Wp, x, xj, a, s);
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      const double r = s[o] > 0.0 ? q[o] : 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) gx[k] = fma(Wp[L::PHI_W1 + o * L::EIN + k], r, gx[k]);
-    }
-  }
-}
-
-// x_j side of ONE message that neighbour u receives from node m (x = h[m]) with u's cotangent c: g += W1_j^T (1[s > 0] * W2^T c)
-__device__ __forceinline__ void d64_msg_vjp_xj(const double* __restrict__ Wp, const double* xu, const double* x, const double* a,
-                                               const double* c, double* g) {
-  using L = W64<2>;
-  double s[D], q[D];
-  d64_pre(Wp, xu, x, a, s);
-  d64_w2t(Wp, c, q);
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    const double r = s[o] > 0.0 ? q[o] : 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) g[k] = fma(Wp[L::PHI_W1 + o * L::EIN + D + k], r, g[k]);
-  }
-}
-
-// LayerNorm(10), eps 1e-5, biased variance (model.py:293): statistics of y; yhat = (y - mu) * rs
-__device__ __forceinline__ double d64_ln_stats(const double* y, double* yhat) {
-  double mu = 0.0;
-#pragma unroll
-  for (int o = 0; o < D; ++o) mu += y[o];
-  mu /= D;
-  double var = 0.0;
-#pragma unroll
-  for (int o = 0; o < D; ++o) var = fma(y[o] - mu, y[o] - mu, var);
-  var /= D;
-  const double rs = 1.0 / sqrt(var + 1e-5);
-#pragma unroll
-  for (int o = 0; o < D; ++o) yhat[o] = (y[o] - mu) * rs;
-  return rs;
-}
-// gy, the cotangent of LayerNorm's output at y, back through it: gy <- rs (g - mean(g) - yhat mean(g yhat)), g = gamma * gy
-__device__ __forceinline__ void d64_ln_back(const double* __restrict__ gamma, const double* y, double* gy) {
-  double yhat[D], m1 = 0.0, m2 = 0.0;
-  const double rs = d64_ln_stats(y, yhat);
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    gy[o] *= gamma[o];
-    m1 += gy[o];
-    m2 = fma(gy[o], yhat[o], m2);
-  }
-  m1 /= D;
-  m2 /= D;
-#pragma unroll
-  for (int o = 0; o < D; ++o) gy[o] = rs * (gy[o] - m1 - yhat[o] * m2);
-}
-
-// ---------------------------------------------------------------------------------------------
-// J v: one layer, one node per lane.  out_h (may be NULL): the layer's value; out_v: its tangent (TAN).  TAN = false is the plain
-// layer (the states of a multi-layer J^T w).  lofs / nofs: as k_f64_layer.
-// ---------------------------------------------------------------------------------------------
-template <int P, bool MIXED, bool TAN>
-__global__ __launch_bounds__(256) void k_f64_jvp_layer(int64_t N, const double* __restrict__ W, int lofs, int nofs, int apply_ln,
-                                                       const int32_t* __restrict__ csr_ptr, const int32_t* __restrict__ csr_nbr,
-                                                       const double* __restrict__ csr_attr, const int32_t* __restrict__ csc_ptr,
-                                                       const int32_t* __restrict__ csc_nbr, const double* __restrict__ csc_attr,
-                                                       const uint8_t* __restrict__ flags, const double* __restrict__ h,
-                                                       const double* __restrict__ v, const double* __restrict__ h0,
-                                                       const double* __restrict__ prb, const double* __restrict__ nrm,
-                                                       double* __restrict__ out_h, double* __restrict__ out_v,
-                                                       const int32_t* __restrict__ done) {
-  using L = W64<P>;
-  if (done && *done) return;
-  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  const uint8_t fl = flags[n];
-  if (fl & FLAG_DIRICHLET) {   // the row is h_initial's: tangent 0
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      if (out_h) out_h[n * D + o] = h0[n * D + o];
-      if (TAN) out_v[n * D + o] = 0.0;
-    }
-    return;
-  }
-  double x[D], dx[D], y[D], dy[D];
-  d64_row(h, n, x);
-  if (TAN) d64_row(v, n, dx);
-  const int32_t rb = csr_ptr[n], re = csr_ptr[n + 1];
-  if (MIXED && (fl & FLAG_NEUMANN)) {
-    double mp[D], dmp[D], cat[L::NCAT], hid[D], dhid[D];
-    d64_phi<TAN>(W + nofs, x, dx, h, v, rb, re, csr_nbr, csr_attr, mp, dmp);
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      cat[k] = x[k];
-      cat[D + k] = mp[k];
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) cat[2 * D + k] = prb[n * P + k];
-    cat[2 * D + P] = nrm[2 * n];
-    cat[2 * D + P + 1] = nrm[2 * n + 1];
-    const double* Wn = W + nofs + L::PHI_SZ;
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      double s = Wn[L::NEU_B1 + o];
-#pragma unroll
-      for (int k = 0; k < L::NCAT; ++k) s = fma(Wn[o * L::NCAT + k], cat[k], s);
-      if (TAN) {
-        double r = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(Wn[o * L::NCAT + k], dx[k], r);
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(Wn[o * L::NCAT + D + k], dmp[k], r);
-        dhid[o] = s > 0.0 ? r : 0.0;
-      }
-      hid[o] = fmax(s, 0.0);
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      double s = Wn[L::NEU_B2 + o], r = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) s = fma(Wn[L::NEU_W2 + o * D + k], hid[k], s);
-      y[o] = s;
-      if (TAN) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(Wn[L::NEU_W2 + o * D + k], dhid[k], r);
-        dy[o] = r;
-      }
-    }
-  } else {
-    double cat[L::CAT], dcat[3 * D], hid[D], dhid[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      cat[k] = x[k];
-      if (TAN) dcat[k] = dx[k];
-    }
-    d64_phi<TAN>(W + lofs, x, dx, h, v, csc_ptr[n], csc_ptr[n + 1], csc_nbr, csc_attr, cat + D, dcat + D);
-    d64_phi<TAN>(W + lofs + L::PHI_SZ, x, dx, h, v, rb, re, csr_nbr, csr_attr, cat + 2 * D, dcat + 2 * D);
-#pragma unroll
-    for (int k = 0; k < P; ++k) cat[3 * D + k] = prb[n * P + k];
-    double al = W[L::AL_B], dal = 0.0;
-#pragma unroll
-    for (int k = 0; k < L::CAT; ++k) al = fma(W[L::AL_W + k], cat[k], al);
-    al = 1.0 / (1.0 + exp(-al));
-    if (TAN) {
-#pragma unroll
-      for (int k = 0; k < 3 * D; ++k) dal = fma(W[L::AL_W + k], dcat[k], dal);
-      dal *= al * (1.0 - al);
-    }
-    const double* Wu = W + lofs + 2 * L::PHI_SZ;
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      double s = Wu[L::UPD_B1 + o];
-#pragma unroll
-      for (int k = 0; k < L::CAT; ++k) s = fma(Wu[o * L::CAT + k], cat[k], s);
-      if (TAN) {
-        double r = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3 * D; ++k) r = fma(Wu[o * L::CAT + k], dcat[k], r);
-        dhid[o] = s > 0.0 ? r : 0.0;
-      }
-      hid[o] = fmax(s, 0.0);
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      double s = Wu[L::UPD_B2 + o], r = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) s = fma(Wu[L::UPD_W2 + o * D + k], hid[k], s);
-      y[o] = x[o] + al * s;
-      if (TAN) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(Wu[L::UPD_W2 + o * D + k], dhid[k], r);
-        dy[o] = dx[o] + dal * s + al * r;
-      }
-    }
-  }
-  if (apply_ln) {
-    double yhat[D];
-    const double rs = d64_ln_stats(y, yhat);
-    if (TAN) {   // d yhat = rs (dyc - yhat mean(yhat dyc)), dyc = dy - mean(dy)
-      double m1 = 0.0, m2 = 0.0;
-#pragma unroll
-      for (int o = 0; o < D; ++o) m1 += dy[o];
-      m1 /= D;
-#pragma unroll
-      for (int o = 0; o < D; ++o) m2 = fma(yhat[o], dy[o] - m1, m2);
-      m2 /= D;
-#pragma unroll
-      for (int o = 0; o < D; ++o) dy[o] = rs * ((dy[o] - m1) - yhat[o] * m2) * W[L::LN_G + o];
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o) y[o] = yhat[o] * W[L::LN_G + o] + W[L::LN_B + o];
-  }
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    if (out_h) out_h[n * D + o] = y[o];
-    if (TAN) out_v[n * D + o] = dy[o];
-  }
-}
+#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
 // J^T w, pass A: per receiving node.  loc (N, D): the node-local part; C (N, CW): {c_to, c_from (, c_neu)}, CW = 2 D / 3 D.
@@ -338,121 +49,33 @@ __global__ __launch_bounds__(256) void k_f64_vjp_node(int64_t N, const double* _
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const uint8_t fl = flags[n];
-  double gx[D], c[CW];
+  double gx[D], c[3 * D];
 #pragma unroll
   for (int k = 0; k < D; ++k) gx[k] = 0.0;
 #pragma unroll
-  for (int k = 0; k < CW; ++k) c[k] = 0.0;
+  for (int k = 0; k < 3 * D; ++k) c[k] = 0.0;
   if (!(fl & FLAG_DIRICHLET)) {   // a Dirichlet row is h_initial's: nothing flows back through it
     double x[D], gy[D];
     d64_row(h, n, x);
     d64_row(w, n, gy);
     const int32_t rb = csr_ptr[n], re = csr_ptr[n + 1], cb = csc_ptr[n], ce = csc_ptr[n + 1];
-    if (MIXED && (fl & FLAG_NEUMANN)) {
-      double mp[D], cat[L::NCAT], pre[D], y[D], q[D];
-      d64_phi<false>(W + nofs, x, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, mp, nullptr);
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        cat[k] = x[k];
-        cat[D + k] = mp[k];
-      }
-#pragma unroll
-      for (int k = 0; k < P; ++k) cat[2 * D + k] = prb[n * P + k];
-      cat[2 * D + P] = nrm[2 * n];
-      cat[2 * D + P + 1] = nrm[2 * n + 1];
-      const double* Wn = W + nofs + L::PHI_SZ;
-#pragma unroll
-      for (int o = 0; o < D; ++o) {
-        double s = Wn[L::NEU_B1 + o];
-#pragma unroll
-        for (int k = 0; k < L::NCAT; ++k) s = fma(Wn[o * L::NCAT + k], cat[k], s);
-        pre[o] = s;
-      }
-      if (apply_ln) {
-#pragma unroll
-        for (int o = 0; o < D; ++o) {
-          double s = Wn[L::NEU_B2 + o];
-#pragma unroll
-          for (int k = 0; k < D; ++k) s = fma(Wn[L::NEU_W2 + o * D + k], fmax(pre[k], 0.0), s);
-          y[o] = s;
-        }
-        d64_ln_back(W + L::LN_G, y, gy);
-      }
-      // y = N2 relu(N1 cat + n1) + n2
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        double s = 0.0;
-#pragma unroll
-        for (int o = 0; o < D; ++o) s = fma(Wn[L::NEU_W2 + o * D + k], gy[o], s);
-        q[k] = pre[k] > 0.0 ? s : 0.0;
-      }
-#pragma unroll
-      for (int o = 0; o < D; ++o)
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          gx[k] = fma(Wn[o * L::NCAT + k], q[o], gx[k]);
-          c[2 * D + k] = fma(Wn[o * L::NCAT + D + k], q[o], c[2 * D + k]);
-        }
-      d64_w2t(W + nofs, c + 2 * D, q);
-      d64_phi_vjp_xi(W + nofs, x, h, rb, re, csr_nbr, csr_attr, q, gx);
-    } else {
-      double cat[L::CAT], pre[D], sv[D], y[D], gcat[3 * D], q[D];
-#pragma unroll
-      for (int k = 0; k < D; ++k) cat[k] = x[k];
-      d64_phi<false>(W + lofs, x, nullptr, h, nullptr, cb, ce, csc_nbr, csc_attr, cat + D, nullptr);
-      d64_phi<false>(W + lofs + L::PHI_SZ, x, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, cat + 2 * D, nullptr);
-#pragma unroll
-      for (int k = 0; k < P; ++k) cat[3 * D + k] = prb[n * P + k];
-      double al = W[L::AL_B];
-#pragma unroll
-      for (int k = 0; k < L::CAT; ++k) al = fma(W[L::AL_W + k], cat[k], al);
-      al = 1.0 / (1.0 + exp(-al));
-      const double* Wu = W + lofs + 2 * L::PHI_SZ;
-#pragma unroll
-      for (int o = 0; o < D; ++o) {
-        double s = Wu[L::UPD_B1 + o];
-#pragma unroll
-        for (int k = 0; k < L::CAT; ++k) s = fma(Wu[o * L::CAT + k], cat[k], s);
-        pre[o] = s;
-      }
-#pragma unroll
-      for (int o = 0; o < D; ++o) {
-        double s = Wu[L::UPD_B2 + o];
-#pragma unroll
-        for (int k = 0; k < D; ++k) s = fma(Wu[L::UPD_W2 + o * D + k], fmax(pre[k], 0.0), s);
-        sv[o] = s;
-        y[o] = x[o] + al * s;
-      }
-      if (apply_ln) d64_ln_back(W + L::LN_G, y, gy);
-      // y = x + al * s: cotangents of the gate's pre-activation and of s
-      double gal = 0.0;
-#pragma unroll
-      for (int o = 0; o < D; ++o) gal = fma(gy[o], sv[o], gal);
-      gal *= al * (1.0 - al);
-#pragma unroll
-      for (int k = 0; k < 3 * D; ++k) gcat[k] = W[L::AL_W + k] * gal;
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        double s = 0.0;
-#pragma unroll
-        for (int o = 0; o < D; ++o) s = fma(Wu[L::UPD_W2 + o * D + k], al * gy[o], s);
-        q[k] = pre[k] > 0.0 ? s : 0.0;
-      }
-#pragma unroll
-      for (int o = 0; o < D; ++o)
-#pragma unroll
-        for (int k = 0; k < 3 * D; ++k) gcat[k] = fma(Wu[o * L::CAT + k], q[o], gcat[k]);
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        gx[k] = gy[k] + gcat[k];
-        c[k] = gcat[D + k];
-        c[D + k] = gcat[2 * D + k];
-      }
-      d64_w2t(W + lofs, c, q);
-      d64_phi_vjp_xi(W + lofs, x, h, cb, ce, csc_nbr, csc_attr, q, gx);
-      d64_w2t(W + lofs + L::PHI_SZ, c + D, q);
-      d64_phi_vjp_xi(W + lofs + L::PHI_SZ, x, h, rb, re, csr_nbr, csr_attr, q, gx);
-    }
+    // The node's forward again, then back, one kind of row per branch.  The record (yhat: d64_ln_back's by-product) is declared here
+    // and shared by both branches, and the branch body is a lambda, not a helper template: either other form spills in <3, true>.
+    double cat[L::CAT], rp[D], sv[D], y[D], yhat[D], g[D], q[D], al, dal, gal;
+    unsigned mask;
+    auto back = [&](auto kind) __attribute__((always_inline)) {
+      constexpr bool NEU = decltype(kind)::value;
+      d64_node_fwd<P, false, NEU>(W, lofs, nofs, n, x, nullptr, h, nullptr, csr_ptr, csr_nbr, csr_attr, csc_ptr, csc_nbr, csc_attr, prb,
+                                  nrm, cat, nullptr, al, dal, mask, rp, nullptr, sv, nullptr, y, nullptr);
+      if (apply_ln) d64_ln_back(W + L::LN_G, y, gy, yhat);
+      d64_node_back_q<P, NEU>(W, lofs, nofs, mask, al, sv, gy, gal, g, q);
+      d64_node_back_c<P, NEU>(W, lofs, nofs, gal, q, gy, c, gx);
+      d64_node_back_xi<P, NEU>(W, lofs, nofs, x, h, rb, re, cb, ce, csr_nbr, csr_attr, csc_nbr, csc_attr, c, gx);
+    };
+    if (MIXED && (fl & FLAG_NEUMANN))
+      back(std::true_type{});
+    else
+      back(std::false_type{});
   }
 #pragma unroll
   for (int k = 0; k < D; ++k) loc[n * D + k] = gx[k];
@@ -523,22 +146,26 @@ static void jvp_launch(const psignn_f64* f, const double* W, int nl, int l, int 
   const unsigned g = (unsigned)cdiv(p->N, 256);
   // algorithmic bytes: both edge lists once (neighbour id, 3 attributes, the neighbour's row and tangent row), per node its rows
   PROF_BYTES(2 * p->Ep * (4 + 24 + (v ? 16 : 8) * D) + p->N * ((v ? 32 : 16) * D + 8 * (p->mixed ? 3 : 2) + 17));
-  if (p->mixed) {
-    using L = W64<3>;
-    LAUNCH("k_f64_jvp_layer", st,
-           (k_f64_jvp_layer<3, true, true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, v, h0, prb,
-                                                             nrm, out_h, out_v, done)));
-  } else if (v) {
-    using L = W64<2>;
-    LAUNCH("k_f64_jvp_layer", st,
-           (k_f64_jvp_layer<2, false, true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, v, h0,
-                                                              prb, nrm, out_h, out_v, done)));
-  } else {
-    using L = W64<2>;
-    LAUNCH("k_f64_state_layer", st,
-           (k_f64_jvp_layer<2, false, false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, nullptr,
-                                                               h0, prb, nrm, out_h, nullptr, done)));
-  }
+  if (v)
+    F64_FAMILY(p->mixed, LAUNCH("k_f64_jvp_layer", st,
+                                (k_f64_jvp_layer<P, MIXED, true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln,
+                                                                                  F64_EDGES(f), h, v, h0, prb, nrm, out_h, out_v, done))));
+  else
+    F64_FAMILY(p->mixed, LAUNCH("k_f64_state_layer", st,
+                                (k_f64_jvp_layer<P, MIXED, false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln,
+                                                                                   F64_EDGES(f), h, nullptr, h0, prb, nrm, out_h,
+                                                                                   nullptr, done))));
+}
+
+// pass B of one layer: out = loc + the x_j sides gathered from C (+ add)
+static void vjp_edge_launch(const psignn_f64* f, const double* W, int nl, int l, const double* h, const double* loc, const double* C,
+                            const double* add, double* out, const int32_t* done, hipStream_t st) {
+  const psignn_plan* p = f->p;
+  // both edge lists once (neighbour id and flag, 3 attributes, the neighbour's row and its cotangent), per node h, loc, out (, add)
+  PROF_BYTES(2 * p->Ep * (4 + 1 + 24 + 16 * D) + p->N * (8 * 3 * D + (add ? 8 * D : 0) + 8));
+  F64_FAMILY(p->mixed, LAUNCH("k_f64_vjp_edge", st,
+                              (k_f64_vjp_edge<MIXED><<<(unsigned)cdiv(p->N, 256), 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl),
+                                                                                              F64_EDGES(f), h, loc, C, add, out, done))));
 }
 
 // both passes of one layer: out = J_l(h)^T w (+ add)
@@ -546,35 +173,38 @@ static void vjp_launch(const psignn_f64* f, const double* W, int nl, int l, int 
                        const double* nrm, const double* w, double* loc, double* C, const double* add, double* out, const int32_t* done,
                        hipStream_t st) {
   const psignn_plan* p = f->p;
-  const unsigned g = (unsigned)cdiv(p->N, 256);
   const int cw = p->mixed ? 3 * D : 2 * D;
   PROF_BYTES(2 * p->Ep * (4 + 24 + 8 * D) + p->N * (8 * (3 * D + cw) + 8 * (p->mixed ? 3 : 2) + 17));
-  if (p->mixed) {
-    using L = W64<3>;
-    LAUNCH("k_f64_vjp_node", st,
-           (k_f64_vjp_node<3, true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb, nrm, w, loc,
-                                                      C, done)));
-  } else {
-    using L = W64<2>;
-    LAUNCH("k_f64_vjp_node", st,
-           (k_f64_vjp_node<2, false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb, nrm, w, loc,
-                                                       C, done)));
-  }
-  // both edge lists once (neighbour id and flag, 3 attributes, the neighbour's row and its cotangent), per node h, loc, out (, add)
-  PROF_BYTES(2 * p->Ep * (4 + 1 + 24 + 16 * D) + p->N * (8 * 3 * D + (add ? 8 * D : 0) + 8));
-  if (p->mixed) {
-    using L = W64<3>;
-    LAUNCH("k_f64_vjp_edge", st,
-           (k_f64_vjp_edge<true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, loc, C, add, out, done)));
-  } else {
-    using L = W64<2>;
-    LAUNCH("k_f64_vjp_edge", st,
-           (k_f64_vjp_edge<false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, loc, C, add, out, done)));
-  }
+  F64_FAMILY(p->mixed, LAUNCH("k_f64_vjp_node", st,
+                              (k_f64_vjp_node<P, MIXED><<<(unsigned)cdiv(p->N, 256), 256, 0, st>>>(
+                                  p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb, nrm, w, loc, C, done))));
+  vjp_edge_launch(f, W, nl, l, h, loc, C, add, out, done, st);
 }
 
 // Only a multi-layer dirichlet block is a chain: the mixed loop never reassigns h, so its last layer on h is the block.
 static inline bool f64_chain(const psignn_f64* f, int nl) { return !f->p->mixed && nl > 1; }
+
+// A block backwards.  A chain: the states h_1 .. h_{L-1} at h (t: with their tangents), then layer(l, end, h_l, t_l, w_{l+1}, dst)
+// for l = L-1 .. 0, which leaves w_l = J_l^T w_{l+1} in dst: the ping-pong pp for the inner layers, out for the last step
+// (end: l = 0).  Any other block: the one step, layer nl - 1 at h, straight into out; states, tans and pp are not touched.
+template <class Layer>
+static void f64_walk_back(const psignn_f64* f, const double* W, int nl, const double* h, const double* t, const double* h0,
+                          const double* prb, double* states, double* tans, const double* w, double* pp, double* out,
+                          const int32_t* done, hipStream_t st, Layer layer) {
+  const int64_t row = f->p->N * D;
+  const int first = f64_chain(f, nl) ? 0 : nl - 1;
+  const double *ch = h, *ct = t;
+  for (int l = first; l + 1 < nl; ++l) {
+    jvp_launch(f, W, nl, l, 0, ch, ct, h0, prb, nullptr, states + l * row, t ? tans + l * row : nullptr, done, st);
+    ch = states + l * row;
+    if (t) ct = tans + l * row;
+  }
+  for (int l = nl - 1; l >= first; --l) {
+    double* dst = l == first ? out : pp + (l & 1) * row;
+    layer(l, l == first, l == first ? h : states + (l - 1) * row, l == first || !t ? t : tans + (l - 1) * row, w, dst);
+    w = dst;
+  }
+}
 
 extern "C" int64_t psignn_f64_deriv_workspace_doubles(const psignn_f64_t* f, int n_layers, int transposed) {
   if (!f || n_layers < 1) return -1;
@@ -639,25 +269,12 @@ int psignn_f64_vjp_gated(psignn_f64_t* f, const double* W, int nl, const double*
   if (rc) return rc;
   if (f->p->N == 0) return PSIGNN_OK;
   const int64_t row = f->p->N * D;
-  double *loc = work, *C = work + row;
-  if (!f64_chain(f, nl)) {
-    vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, w, loc, C, add, out, done, st);
-  } else {
-    // the states h_1 .. h_{L-1} at h, then the chain backwards; cotangents of the inner layers in a ping-pong
-    double *states = work + 3 * row, *pp = work + (3 + nl - 1) * row;
-    const double* cur = h;
-    for (int l = 0; l + 1 < nl; ++l) {
-      jvp_launch(f, W, nl, l, 0, cur, nullptr, h0, prb, nullptr, states + l * row, nullptr, done, st);
-      cur = states + l * row;
-    }
-    const double* cw = w;
-    for (int l = nl - 1; l >= 0; --l) {
-      double* dst = l == 0 ? out : pp + (l & 1) * row;
-      vjp_launch(f, W, nl, l, l == nl - 1, l == 0 ? h : states + (l - 1) * row, prb, nrm, cw, loc, C, l == 0 ? add : nullptr, dst,
-                 done, st);
-      cw = dst;
-    }
-  }
+  const bool chain = f64_chain(f, nl);
+  double *loc = work, *C = work + row, *states = chain ? work + 3 * row : nullptr, *pp = chain ? work + (3 + nl - 1) * row : nullptr;
+  f64_walk_back(f, W, nl, h, nullptr, h0, prb, states, nullptr, w, pp, out, done, st,
+                [&](int l, bool end, const double* hl, const double*, const double* wl, double* dst) {
+                  vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, wl, loc, C, end ? add : nullptr, dst, done, st);
+                });
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
@@ -724,28 +341,42 @@ __device__ __forceinline__ void pg_put(double* pt, int wofs, int bofs, int no, i
 
 // One Phi module over one edge list of the chunk's rows: round j holds the j-th entry of every row's list.
 // row: qm 0..9 | x_i 10..19, x_j 20..29, a 30..32, 1 | c 34..43 | relu(s) 44..53, 1
-__device__ __forceinline__ void pg_edges(const double* __restrict__ Wp, bool act, const double* x, const double* c,
-                                         const double* __restrict__ h, int32_t beg, int32_t end, const int32_t* __restrict__ nbr,
-                                         const double* __restrict__ attr, double* buf, double* row, double* pt, int base) {
+// TAN (the backward of the VJP): per edge position two sub-rounds, dA (x) B then A (x) dB, in the same row layout.
+// c, dc: the lane's cotangents of the module's message sum and their tangents (read only when act).
+template <bool TAN>
+__device__ __forceinline__ void pg_edges(const double* __restrict__ Wp, bool act, const double* x, const double* dx, const double* cg,
+                                         const double* dcg, const double* __restrict__ h, const double* __restrict__ t, int32_t beg,
+                                         int32_t end, const int32_t* __restrict__ nbr, const double* __restrict__ attr, double* buf,
+                                         double* row, double* pt, int base) {
   using L = W64<2>;
-  double q[D], a1[2] = {0.0, 0.0}, a2[1] = {0.0};
+  double c[D], dc[D], q[D], dq[D], a1[2] = {0.0, 0.0}, a2[1] = {0.0};
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    c[k] = act ? cg[k] : 0.0;
+    if (TAN) dc[k] = act ? dcg[k] : 0.0;
+  }
   d64_w2t(Wp, c, q);
+  if (TAN) d64_w2t(Wp, dc, dq);
   for (int32_t j = 0;; ++j) {
     const bool on = act && beg + j < end;
     if (!__syncthreads_or(on)) break;   // also the barrier behind the previous round's reads
+    double xj[D], dxj[D], a[3], s[D], ds[D];
     if (on) {
       const int32_t i = beg + j;
-      double xj[D], a[3], s[D];
-      d64_row(h, nbr[i], xj);
+      const int64_t u = nbr[i];
+      d64_row(h, u, xj);
+      if (TAN) d64_row(t, u, dxj);
 #pragma unroll
       for (int k = 0; k < 3; ++k) a[k] = attr[3 * (int64_t)i + k];
       d64_pre(Wp, x, xj, a, s);
+      if (TAN) d64_pre_tan(Wp, s, dx, dxj, ds);
+      // (d) qm (x) [x_i, x_j, a, 1]; (d) c (x) [relu(s), 1]
 #pragma unroll
       for (int k = 0; k < D; ++k) {
-        row[k] = s[k] > 0.0 ? q[k] : 0.0;
+        row[k] = s[k] > 0.0 ? (TAN ? dq[k] : q[k]) : 0.0;
         row[10 + k] = x[k];
         row[20 + k] = xj[k];
-        row[34 + k] = c[k];
+        row[34 + k] = TAN ? dc[k] : c[k];
         row[44 + k] = fmax(s[k], 0.0);
       }
 #pragma unroll
@@ -758,9 +389,53 @@ __device__ __forceinline__ void pg_edges(const double* __restrict__ Wp, bool act
     __syncthreads();
     pg_acc<PG_RS, 2>(buf, 0, 10, D, L::EIN + 1, a1);
     pg_acc<PG_RS, 1>(buf, 34, 44, D, D + 1, a2);
+    if (TAN) {
+      __syncthreads();
+      if (on) {   // qm (x) [dx_i, dx_j, 0, 0]; c (x) [1[s > 0] ds, 0]
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          row[k] = s[k] > 0.0 ? q[k] : 0.0;
+          row[10 + k] = dx[k];
+          row[20 + k] = dxj[k];
+          row[34 + k] = c[k];
+          row[44 + k] = ds[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) row[30 + k] = 0.0;
+        row[54] = 0.0;
+      }
+      __syncthreads();
+      pg_acc<PG_RS, 2>(buf, 0, 10, D, L::EIN + 1, a1);
+      pg_acc<PG_RS, 1>(buf, 34, 44, D, D + 1, a2);
+    }
   }
   pg_put<2>(pt, base + L::PHI_W1, base + L::PHI_B1, D, L::EIN + 1, a1);
   pg_put<1>(pt, base + L::PHI_W2, base + L::PHI_B2, D, D + 1, a2);
+}
+
+// One row of k_f64_pgrad, of one kind, as pass A of J^T w takes it: forward again, then back.  Leaves the factors of the rounds:
+// cat, rp = relu(pre), gw = w and wy = w * yhat (LayerNorm's), gal, g, q and the cotangents c of the message sums.
+template <int P, bool NEU>
+__device__ __forceinline__ void pg_node_row(const double* W, int lofs, int nofs, int apply_ln, int64_t n, const double* x, double* gy,
+                                            const double* h, const int32_t* csr_ptr, const int32_t* csr_nbr, const double* csr_attr,
+                                            const int32_t* csc_ptr, const int32_t* csc_nbr, const double* csc_attr, const double* prb,
+                                            const double* nrm, double* cat, double* rp, double* gw, double* wy, double& gal, double* g,
+                                            double* q, double* c) {
+  using L = W64<P>;
+  double sv[D], y[D], al, dal;
+  unsigned mask;
+  d64_node_fwd<P, false, NEU>(W, lofs, nofs, n, x, nullptr, h, nullptr, csr_ptr, csr_nbr, csr_attr, csc_ptr, csc_nbr, csc_attr, prb, nrm,
+                              cat, nullptr, al, dal, mask, rp, nullptr, sv, nullptr, y, nullptr);
+  if (apply_ln) {   // laynorm.weight takes w * yhat, laynorm.bias w
+    double yhat[D];
+#pragma unroll
+    for (int o = 0; o < D; ++o) gw[o] = gy[o];
+    d64_ln_back(W + L::LN_G, y, gy, yhat);
+#pragma unroll
+    for (int o = 0; o < D; ++o) wy[o] = gw[o] * yhat[o];
+  }
+  d64_node_back_q<P, NEU>(W, lofs, nofs, mask, al, sv, gy, gal, g, q);
+  d64_node_back_c<P, NEU>(W, lofs, nofs, gal, q, nullptr, c, nullptr);
 }
 
 // One layer's parameter gradient at (h, w), per chunk: part (chunks, W64<P>::total(1, MIXED)) in the layout of a single-layer block.
@@ -773,7 +448,6 @@ __global__ __launch_bounds__(PG_ROWS) void k_f64_pgrad(int64_t N, const double* 
                                                        const double* __restrict__ prb, const double* __restrict__ nrm,
                                                        const double* __restrict__ w, double* __restrict__ part) {
   using L = W64<P>;
-  constexpr int CW = MIXED ? 3 * D : 2 * D;
   static_assert(10 + L::CAT + 1 + 1 <= PG_RS && 10 + L::NCAT + 1 + 10 + D + 1 <= PG_RS && D == 10, "LDS row of the rounds");
   __shared__ double buf[PG_ROWS * PG_RS];
   double* row = buf + threadIdx.x * PG_RS;
@@ -785,114 +459,25 @@ __global__ __launch_bounds__(PG_ROWS) void k_f64_pgrad(int64_t N, const double* 
   const bool upd = live && !neu;
   // the factors of the node rounds; a row is an update row or a Neumann row, so the two kinds share them:
   // q: cotangent of the hidden pre-activations; cat: the MLP's input; g: cotangent of the MLP's output; rp: relu(pre)
-  double x[D], c[CW], q[D], cat[L::CAT], g[D], rp[D], wy[D], gw[D], gal = 0.0;
+  double x[D], c[3 * D], q[D], cat[L::CAT], g[D], rp[D], wy[D], gw[D], gal = 0.0;
   int32_t rb = 0, re = 0, cb = 0, ce = 0;
 #pragma unroll
   for (int k = 0; k < D; ++k) x[k] = q[k] = g[k] = rp[k] = wy[k] = gw[k] = 0.0;
 #pragma unroll
-  for (int k = 0; k < CW; ++k) c[k] = 0.0;
+  for (int k = 0; k < 3 * D; ++k) c[k] = 0.0;
 #pragma unroll
   for (int k = 0; k < L::CAT; ++k) cat[k] = 0.0;
-  if (live) {
-    double gy[D], pre[D], y[D];
+  if (live) {   // the node as pass A of J^T w takes it: forward again, then back; one kind of row per branch
+    double gy[D];
     d64_row(h, n, x);
     d64_row(w, n, gy);
     rb = csr_ptr[n], re = csr_ptr[n + 1], cb = csc_ptr[n], ce = csc_ptr[n + 1];
-    double al = 1.0;
-    const double* Wm = neu ? W + nofs + L::PHI_SZ : W + lofs + 2 * L::PHI_SZ;   // W1 | b1 | W2 | b2 of the row's MLP
-    int ncat, ob1, ow2, ob2;
-    if (neu) {
-      double mp[D];
-      d64_phi<false>(W + nofs, x, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, mp, nullptr);
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        cat[k] = x[k];
-        cat[D + k] = mp[k];
-      }
-#pragma unroll
-      for (int k = 0; k < P; ++k) cat[2 * D + k] = prb[n * P + k];
-      cat[2 * D + P] = nrm[2 * n];
-      cat[2 * D + P + 1] = nrm[2 * n + 1];
-      ncat = L::NCAT, ob1 = L::NEU_B1, ow2 = L::NEU_W2, ob2 = L::NEU_B2;
-    } else {
-#pragma unroll
-      for (int k = 0; k < D; ++k) cat[k] = x[k];
-      d64_phi<false>(W + lofs, x, nullptr, h, nullptr, cb, ce, csc_nbr, csc_attr, cat + D, nullptr);
-      d64_phi<false>(W + lofs + L::PHI_SZ, x, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, cat + 2 * D, nullptr);
-#pragma unroll
-      for (int k = 0; k < P; ++k) cat[3 * D + k] = prb[n * P + k];
-      al = W[L::AL_B];
-#pragma unroll
-      for (int k = 0; k < L::CAT; ++k) al = fma(W[L::AL_W + k], cat[k], al);
-      al = 1.0 / (1.0 + exp(-al));
-      ncat = L::CAT, ob1 = L::UPD_B1, ow2 = L::UPD_W2, ob2 = L::UPD_B2;
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      double s = Wm[ob1 + o];
-#pragma unroll
-      for (int k = 0; k < L::CAT; ++k)
-        if (k < ncat) s = fma(Wm[o * ncat + k], cat[k], s);
-      pre[o] = s;
-      rp[o] = fmax(s, 0.0);
-    }
-    double sv[D];
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-      double s = Wm[ob2 + o];
-#pragma unroll
-      for (int k = 0; k < D; ++k) s = fma(Wm[ow2 + o * D + k], rp[k], s);
-      sv[o] = s;
-      y[o] = neu ? s : x[o] + al * s;
-    }
-    if (apply_ln) {
-      double yhat[D], m1 = 0.0, m2 = 0.0;
-      const double rs = d64_ln_stats(y, yhat);
-#pragma unroll
-      for (int o = 0; o < D; ++o) {
-        wy[o] = gy[o] * yhat[o];
-        gw[o] = gy[o];
-        gy[o] *= W[L::LN_G + o];
-        m1 += gy[o];
-        m2 = fma(gy[o], yhat[o], m2);
-      }
-      m1 /= D;
-      m2 /= D;
-#pragma unroll
-      for (int o = 0; o < D; ++o) gy[o] = rs * (gy[o] - m1 - yhat[o] * m2);
-    }
-    if (!neu) {   // y = x + al * s: cotangent of the gate's pre-activation
-#pragma unroll
-      for (int o = 0; o < D; ++o) gal = fma(gy[o], sv[o], gal);
-      gal *= al * (1.0 - al);
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o) g[o] = al * gy[o];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      double s = 0.0;
-#pragma unroll
-      for (int o = 0; o < D; ++o) s = fma(Wm[ow2 + o * D + k], g[o], s);
-      q[k] = pre[k] > 0.0 ? s : 0.0;
-    }
-    // cotangents of the message sums: cat[D .. 2D) (and [2D .. 3D) of an update row)
-    if (neu) {
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        double s = 0.0;
-#pragma unroll
-        for (int o = 0; o < D; ++o) s = fma(Wm[o * L::NCAT + D + k], q[o], s);
-        c[CW - D + k] = s;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 2 * D; ++k) {
-        double s = W[L::AL_W + D + k] * gal;
-#pragma unroll
-        for (int o = 0; o < D; ++o) s = fma(Wm[o * L::CAT + D + k], q[o], s);
-        c[k] = s;
-      }
-    }
+    if (neu)
+      pg_node_row<P, true>(W, lofs, nofs, apply_ln, n, x, gy, h, csr_ptr, csr_nbr, csr_attr, csc_ptr, csc_nbr, csc_attr, prb, nrm, cat, rp, gw,
+                           wy, gal, g, q, c);
+    else
+      pg_node_row<P, false>(W, lofs, nofs, apply_ln, n, x, gy, h, csr_ptr, csr_nbr, csr_attr, csc_ptr, csc_nbr, csc_attr, prb, nrm, cat, rp,
+                            gw, wy, gal, g, q, c);
   }
   const int ub = L::layer(0) + 2 * L::PHI_SZ;   // the update block of the partial row
   // ---- round 1, update rows: q 0..9 | cat 10 .. 10 + CAT, 1 | gal 44
@@ -952,9 +537,10 @@ __global__ __launch_bounds__(PG_ROWS) void k_f64_pgrad(int64_t N, const double* 
     pg_put<1>(pt, nb + L::NEU_W2, nb + L::NEU_B2, D, D + 1, a2);
   }
   // ---- the messages: Phi_to over the CSC list, Phi_from (Neumann rows: Phi_neumann) over the CSR list
-  pg_edges(W + lofs, upd, x, c, h, cb, ce, csc_nbr, csc_attr, buf, row, pt, L::layer(0));
-  pg_edges(W + lofs + L::PHI_SZ, upd, x, c + D, h, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(0) + L::PHI_SZ);
-  if (MIXED) pg_edges(W + nofs, neu, x, c + 2 * D, h, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(1));
+  pg_edges<false>(W + lofs, upd, x, nullptr, c, nullptr, h, nullptr, cb, ce, csc_nbr, csc_attr, buf, row, pt, L::layer(0));
+  pg_edges<false>(W + lofs + L::PHI_SZ, upd, x, nullptr, c + D, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, buf, row, pt,
+                  L::layer(0) + L::PHI_SZ);
+  if (MIXED) pg_edges<false>(W + nofs, neu, x, nullptr, c + 2 * D, nullptr, h, nullptr, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(1));
 }
 
 // first stage: the partial rows of PG_FOLD consecutive chunks, added in ascending order into the first of them
@@ -1019,19 +605,10 @@ static void pgrad_launch(const psignn_f64* f, const double* W, int nl, int l, in
   // both edge lists twice (the node's forward, then the rounds: neighbour id, 3 attributes, the neighbour's row), per node h, w,
   // flag, pointers and problem data; the partial rows
   PROF_BYTES(4 * p->Ep * (4 + 24 + 8 * D) + p->N * (16 * D + 8 * (p->mixed ? 5 : 2) + 17) + pg_part_doubles(f) * 8);
-  if (p->mixed) {
-    using L = W64<3>;
-    LAUNCH("k_f64_pgrad", st,
-           (k_f64_pgrad<3, true><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb,
-                                                                    nrm, w, part)));
-    pg_reduce(part, nch, L::total(1, true), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
-  } else {
-    using L = W64<2>;
-    LAUNCH("k_f64_pgrad", st,
-           (k_f64_pgrad<2, false><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, prb,
-                                                                     nrm, w, part)));
-    pg_reduce(part, nch, L::total(1, false), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
-  }
+  F64_FAMILY(p->mixed, LAUNCH("k_f64_pgrad", st,
+                              (k_f64_pgrad<P, MIXED><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln,
+                                                                                       F64_EDGES(f), h, prb, nrm, w, part)));
+             pg_reduce(part, nch, L::total(1, MIXED), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st));
   if (init) {
     PROF_BYTES(p->N * (1 + 16 * D));
     LAUNCH("k_f64_pg_init", st,
@@ -1054,26 +631,15 @@ extern "C" int psignn_f64_param_vjp(psignn_f64_t* f, const double* W, int nl, co
   if (f->p->N == 0) return PSIGNN_OK;
   const int64_t row = f->p->N * D;
   double *loc = work, *C = work + row, *part = work + psignn_f64_deriv_workspace_doubles(f, nl, 1);
-  if (!f64_chain(f, nl)) {   // mixed: only the last layer's iteration reaches the output, the earlier layers' sections stay zero
-    pgrad_launch(f, W, nl, nl - 1, 1, h, prb, nrm, w, part, d_grad, d_out_init, 0, st);
-    vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, w, loc, C, nullptr, d_out_h, nullptr, st);
-  } else {
-    // as psignn_f64_vjp: the states, then the chain backwards; layer l's gradient at (h_l, w_{l+1}) before w_l = J_l^T w_{l+1}
-    double *states = work + 3 * row, *pp = work + (3 + nl - 1) * row;
-    const double* cur = h;
-    for (int l = 0; l + 1 < nl; ++l) {
-      jvp_launch(f, W, nl, l, 0, cur, nullptr, h0, prb, nullptr, states + l * row, nullptr, nullptr, st);
-      cur = states + l * row;
-    }
-    const double* cw = w;
-    for (int l = nl - 1; l >= 0; --l) {
-      const double* hl = l == 0 ? h : states + (l - 1) * row;
-      double* dst = l == 0 ? d_out_h : pp + (l & 1) * row;
-      pgrad_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, cw, part, d_grad, d_out_init, l != nl - 1, st);
-      vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, cw, loc, C, nullptr, dst, nullptr, st);
-      cw = dst;
-    }
-  }
+  const bool chain = f64_chain(f, nl);   // states, pp: as psignn_f64_vjp lays them out
+  double *states = chain ? work + 3 * row : nullptr, *pp = chain ? work + (3 + nl - 1) * row : nullptr;
+  // layer l's gradient at (h_l, w_{l+1}) before w_l = J_l^T w_{l+1}.  mixed: only the last layer's iteration reaches the output, the
+  // earlier layers' sections stay zero
+  f64_walk_back(f, W, nl, h, nullptr, h0, prb, states, nullptr, w, pp, d_out_h, nullptr, st,
+                [&](int l, bool, const double* hl, const double*, const double* wl, double* dst) {
+                  pgrad_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, wl, part, d_grad, d_out_init, l != nl - 1, st);
+                  vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, wl, loc, C, nullptr, dst, nullptr, st);
+                });
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }
@@ -1190,123 +756,10 @@ extern "C" int psignn_mlp2_f64_backward(const double* x, const double* gy, int64
 // A multi-layer dirichlet block is a chain: forward with k_f64_jvp_layer for (h_k, t_k), t_0 = gbar, then backwards with
 // (w_{k+1}, dw_{k+1}) -> (w_k, dw_k), w_L = v, dw_L = 0.  No atomics, a summation order that depends on the graph alone.
 // =============================================================================================
-// d64_ln_back with its tangent along dy: (gy, dgy) the cotangent of LayerNorm's output and its tangent, back through it at y.
-// yhat, dyh: the normalised row and its tangent (the factors of laynorm.weight's gradient).
-__device__ __forceinline__ void d64_ln_back_tan(const double* __restrict__ gamma, const double* y, const double* dy, double* gy,
-                                                double* dgy, double* yhat, double* dyh) {
-  const double rs = d64_ln_stats(y, yhat);
-  double a1 = 0.0, a2 = 0.0;
-#pragma unroll
-  for (int o = 0; o < D; ++o) a1 += dy[o];
-  a1 /= D;
-#pragma unroll
-  for (int o = 0; o < D; ++o) a2 = fma(yhat[o], dy[o] - a1, a2);
-  a2 /= D;
-#pragma unroll
-  for (int o = 0; o < D; ++o) dyh[o] = rs * ((dy[o] - a1) - yhat[o] * a2);
-  const double drs = -rs * rs * a2;   // d (var + eps)^(-1/2) = -rs^3 / 2 * dvar, dvar = 2 mean(yhat dy) / rs
-  double m1 = 0.0, m2 = 0.0, dm1 = 0.0, dm2 = 0.0;
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    gy[o] *= gamma[o];
-    dgy[o] *= gamma[o];
-    m1 += gy[o];
-    m2 = fma(gy[o], yhat[o], m2);
-    dm1 += dgy[o];
-    dm2 = fma(dgy[o], yhat[o], fma(gy[o], dyh[o], dm2));
-  }
-  m1 /= D;
-  m2 /= D;
-  dm1 /= D;
-  dm2 /= D;
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    const double r = gy[o] - m1 - yhat[o] * m2;
-    const double dr = dgy[o] - dm1 - dyh[o] * m2 - yhat[o] * dm2;
-    gy[o] = rs * r;
-    dgy[o] = fma(drs, r, rs * dr);
-  }
-}
-
-// pg_edges with its tangent: per edge position two sub-rounds, dA (x) B then A (x) dB, in the row layout of pg_edges.  c, dc: the
-// lane's rows of C and dC (global; read only when act).
-__device__ __forceinline__ void jr_edges(const double* __restrict__ Wp, bool act, const double* x, const double* dx,
-                                         const double* __restrict__ cg, const double* __restrict__ dcg, const double* __restrict__ h,
-                                         const double* __restrict__ t, int32_t beg, int32_t end, const int32_t* __restrict__ nbr,
-                                         const double* __restrict__ attr, double* buf, double* row, double* pt, int base) {
-  using L = W64<2>;
-  double c[D], dc[D], q[D], dq[D], a1[2] = {0.0, 0.0}, a2[1] = {0.0};
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    c[k] = act ? cg[k] : 0.0;
-    dc[k] = act ? dcg[k] : 0.0;
-  }
-  d64_w2t(Wp, c, q);
-  d64_w2t(Wp, dc, dq);
-  for (int32_t j = 0;; ++j) {
-    const bool on = act && beg + j < end;
-    if (!__syncthreads_or(on)) break;   // also the barrier behind the previous round's reads
-    double xj[D], dxj[D], a[3], s[D], ds[D];
-    if (on) {
-      const int32_t i = beg + j;
-      const int64_t u = nbr[i];
-      d64_row(h, u, xj);
-      d64_row(t, u, dxj);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a[k] = attr[3 * (int64_t)i + k];
-      d64_pre(Wp, x, xj, a, s);
-#pragma unroll
-      for (int o = 0; o < D; ++o) {
-        const double* w = Wp + L::PHI_W1 + o * L::EIN;
-        double r = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(w[k], dx[k], r);
-#pragma unroll
-        for (int k = 0; k < D; ++k) r = fma(w[D + k], dxj[k], r);
-        ds[o] = s[o] > 0.0 ? r : 0.0;
-      }
-      // d qm (x) [x_i, x_j, a, 1]; dc (x) [relu(s), 1]
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        row[k] = s[k] > 0.0 ? dq[k] : 0.0;
-        row[10 + k] = x[k];
-        row[20 + k] = xj[k];
-        row[34 + k] = dc[k];
-        row[44 + k] = fmax(s[k], 0.0);
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) row[30 + k] = a[k];
-      row[33] = 1.0;
-      row[54] = 1.0;
-    } else {
-      for (int k = 0; k < 55; ++k) row[k] = 0.0;
-    }
-    __syncthreads();
-    pg_acc<PG_RS, 2>(buf, 0, 10, D, L::EIN + 1, a1);
-    pg_acc<PG_RS, 1>(buf, 34, 44, D, D + 1, a2);
-    __syncthreads();
-    if (on) {   // qm (x) [dx_i, dx_j, 0, 0]; c (x) [1[s > 0] ds, 0]
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        row[k] = s[k] > 0.0 ? q[k] : 0.0;
-        row[10 + k] = dx[k];
-        row[20 + k] = dxj[k];
-        row[34 + k] = c[k];
-        row[44 + k] = ds[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) row[30 + k] = 0.0;
-      row[54] = 0.0;
-    }
-    __syncthreads();
-    pg_acc<PG_RS, 2>(buf, 0, 10, D, L::EIN + 1, a1);
-    pg_acc<PG_RS, 1>(buf, 34, 44, D, D + 1, a2);
-  }
-  pg_put<2>(pt, base + L::PHI_W1, base + L::PHI_B1, D, L::EIN + 1, a1);
-  pg_put<1>(pt, base + L::PHI_W2, base + L::PHI_B2, D, D + 1, a2);
-}
-
 // One layer at (h, t, w, dw): dloc (N, D), C and dC (N, CW) and the chunk's partial row of the parameter part.  dw NULL: zero.
+// The node's forward and reverse with a tangent stand here in this kernel's own words.  With d64_node_fwd<P, true, .> of f64_node.h
+// and tangent forms of its reverse pieces in their place, all three instantiations compiled without scratch and without spills, and
+// still the sums of laynorm.* came back wrong and different from call to call on the device; the cause was not found.
 // ROWS: 0 every row (dirichlet plans); a mixed plan takes two passes, 1 the update rows (and zeros for every other row of dloc, C,
 // dC), then 2 the Neumann rows, each with a partial row of its own sections and zeros elsewhere.  One kind of row per pass keeps
 // the node's block on one code path and inside the register file: a value spilled inside a divergent region and read after it is
@@ -1376,7 +829,7 @@ __global__ __launch_bounds__(PG_ROWS) void k_f64_jr(int64_t N, const double* __r
       al = W[L::AL_B];
 #pragma unroll
       for (int k = 0; k < L::CAT; ++k) al = fma(W[L::AL_W + k], cat[k], al);
-      al = 1.0 / (1.0 + exp(-al));
+      al = d64_sigmoid(al);
 #pragma unroll
       for (int k = 0; k < 3 * D; ++k) dal = fma(W[L::AL_W + k], dcat[k], dal);
       dal *= al * (1.0 - al);
@@ -1603,9 +1056,9 @@ __global__ __launch_bounds__(PG_ROWS) void k_f64_jr(int64_t N, const double* __r
   }
   // ---- the messages: Phi_to over the CSC list, Phi_from (Neumann rows: Phi_neumann) over the CSR list; c and dc from the rows above
   const double *cg = C + (live ? n : 0) * CW, *dcg = dC + (live ? n : 0) * CW;
-  jr_edges(W + lofs, upd, x, dx, cg, dcg, h, t, cb, ce, csc_nbr, csc_attr, buf, row, pt, L::layer(0));
-  jr_edges(W + lofs + L::PHI_SZ, upd, x, dx, cg + D, dcg + D, h, t, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(0) + L::PHI_SZ);
-  if (MIXED) jr_edges(W + nofs, neu, x, dx, cg + 2 * D, dcg + 2 * D, h, t, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(1));
+  pg_edges<true>(W + lofs, upd, x, dx, cg, dcg, h, t, cb, ce, csc_nbr, csc_attr, buf, row, pt, L::layer(0));
+  pg_edges<true>(W + lofs + L::PHI_SZ, upd, x, dx, cg + D, dcg + D, h, t, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(0) + L::PHI_SZ);
+  if (MIXED) pg_edges<true>(W + nofs, neu, x, dx, cg + 2 * D, dcg + 2 * D, h, t, rb, re, csr_nbr, csr_attr, buf, row, pt, L::layer(1));
 }
 
 extern "C" int64_t psignn_f64_vjp_backward_workspace_doubles(const psignn_f64_t* f, int n_layers) {
@@ -1622,67 +1075,40 @@ static void jr_launch(const psignn_f64* f, const double* W, int nl, int l, int a
                       double* part, double* grad, double* out, hipStream_t st) {
   const psignn_plan* p = f->p;
   const int64_t nch = cdiv(p->N, PG_ROWS);
-  const unsigned g = (unsigned)cdiv(p->N, 256);
   const int cw = p->mixed ? 3 * D : 2 * D;
   // both edge lists three times (the forward with its tangent, the x_i side, the rounds: neighbour id, 3 attributes, the neighbour's
   // row and -- twice -- its tangent row), per node h, t, w, dw, dloc, C and dC written and read again, flag, pointers and problem
   // data; the partial rows
   PROF_BYTES(2 * p->Ep * (3 * (4 + 24) + 40 * D) + p->N * (8 * (5 * D + 4 * cw) + 8 * (p->mixed ? 5 : 2) + 17) + pg_part_doubles(f) * 8);
+  F64_FAMILY(p->mixed, LAUNCH("k_f64_jr", st,
+                              (k_f64_jr<P, MIXED, MIXED ? 1 : 0><<<(unsigned)nch, PG_ROWS, 0, st>>>(
+                                  p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, t, prb, nrm, w, dw, C, dloc, dC, part)));
+             pg_reduce(part, nch, L::total(1, MIXED), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st));
   if (p->mixed) {
-    using L = W64<3>;
-    LAUNCH("k_f64_jr", st,
-           (k_f64_jr<3, true, 1><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, t,
-                                                                    prb, nrm, w, dw, C, dloc, dC, part)));
-    pg_reduce(part, nch, L::total(1, true), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
     // the Neumann rows: per node flag and pointers, the partial rows once more; the edge reads of the few Neumann rows are not
     // counted (the host does not know how many there are)
+    using L = W64<3>;
     PROF_BYTES(p->N * 17 + pg_part_doubles(f) * 8);
     LAUNCH("k_f64_jr_neumann", st,
            (k_f64_jr<3, true, 2><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, t,
                                                                     prb, nrm, w, dw, C, dloc, dC, part)));
     pg_reduce(part, nch, L::total(1, true), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
-  } else {
-    using L = W64<2>;
-    LAUNCH("k_f64_jr", st,
-           (k_f64_jr<2, false, 0><<<(unsigned)nch, PG_ROWS, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), apply_ln, F64_EDGES(f), h, t, prb,
-                                                                  nrm, w, dw, C, dloc, dC, part)));
-    pg_reduce(part, nch, L::total(1, false), L::SHARED, L::LAYER, L::layer(l), L::layer(nl), grad, st);
   }
-  // pass B on (dloc, dC), masks at h: as in vjp_launch
-  PROF_BYTES(2 * p->Ep * (4 + 1 + 24 + 16 * D) + p->N * (8 * 3 * D + 8));
-  if (p->mixed) {
-    using L = W64<3>;
-    LAUNCH("k_f64_vjp_edge", st,
-           (k_f64_vjp_edge<true><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, dloc, dC, nullptr, out,
-                                                    nullptr)));
-  } else {
-    using L = W64<2>;
-    LAUNCH("k_f64_vjp_edge", st,
-           (k_f64_vjp_edge<false><<<g, 256, 0, st>>>(p->N, W, L::layer(l), L::layer(nl), F64_EDGES(f), h, dloc, dC, nullptr, out,
-                                                     nullptr)));
-  }
+  vjp_edge_launch(f, W, nl, l, h, dloc, dC, nullptr, out, nullptr, st);   // pass B on (dloc, dC), masks at h
 }
 
 // d_dinit (may be NULL) = d psi / d h_initial: the Dirichlet rows of the tangents of the cotangents on the states h_1 .. h_{L-1} of a
 // multi-layer dirichlet block (those rows are copies of h_initial, and J_f is evaluated at them); zeros for every other block, whose
 // Jacobian does not depend on h_initial.
-// ARG_CHECK under the name of the entry point that was called
-#define JR_CHECK(cond, msg)                       \
-  do {                                            \
-    if (!(cond)) {                                \
-      psignn_set_error("%s: %s", who, msg);       \
-      return PSIGNN_EINVAL;                       \
-    }                                             \
-  } while (0)
 static int vjp_backward_impl(const char* who, psignn_f64_t* f, const double* W, int nl, const double* h, const double* h0,
                              const double* prb, const double* nrm, const double* v, const double* gbar, double* d_grad, double* d_dh,
                              double* d_jtv, double* d_dinit, double* work, int64_t work_doubles, void* stream) {
-  JR_CHECK(f && W && h && h0 && prb && v && gbar && d_grad && d_dh, "NULL argument");
-  JR_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
-  JR_CHECK(!f->p->mixed || nrm, "mixed plan needs unit normals");
-  JR_CHECK(d_dh != h && d_dh != v && d_dh != gbar, "d_dh must not alias h, v or gbar");
-  JR_CHECK(d_jtv != h && d_jtv != v && d_jtv != gbar && d_jtv != d_dh, "d_jtv must not alias h, v, gbar or d_dh");
-  JR_CHECK(!d_dinit || (d_dinit != h && d_dinit != v && d_dinit != gbar && d_dinit != d_dh && d_dinit != d_jtv),
+  ARG_CHECK_AS(who, f && W && h && h0 && prb && v && gbar && d_grad && d_dh, "NULL argument");
+  ARG_CHECK_AS(who, nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK_AS(who, !f->p->mixed || nrm, "mixed plan needs unit normals");
+  ARG_CHECK_AS(who, d_dh != h && d_dh != v && d_dh != gbar, "d_dh must not alias h, v or gbar");
+  ARG_CHECK_AS(who, d_jtv != h && d_jtv != v && d_jtv != gbar && d_jtv != d_dh, "d_jtv must not alias h, v, gbar or d_dh");
+  ARG_CHECK_AS(who, !d_dinit || (d_dinit != h && d_dinit != v && d_dinit != gbar && d_dinit != d_dh && d_dinit != d_jtv),
             "d_dinit must not alias h, v, gbar, d_dh or d_jtv");
   const int rc = work_check(who, psignn_f64_vjp_backward_workspace_doubles(f, nl), work, work_doubles);
   if (rc) return rc;
@@ -1691,37 +1117,27 @@ static int vjp_backward_impl(const char* who, psignn_f64_t* f, const double* W, 
   if (f->p->N == 0) return PSIGNN_OK;
   const int64_t row = f->p->N * D;
   const int cw = f->p->mixed ? 3 : 2;
+  const bool chain = f64_chain(f, nl);
   double *loc = work, *C = work + row, *dloc = C + cw * row, *dC = dloc + row, *rest = dC + cw * row;
-  if (!f64_chain(f, nl)) {   // mixed: only the last layer's iteration reaches the output, the earlier layers' sections stay zero
-    if (d_dinit) HIP_TRY(hipMemsetAsync(d_dinit, 0, sizeof(double) * row, st));
-    jr_launch(f, W, nl, nl - 1, 1, h, gbar, prb, nrm, v, nullptr, C, dloc, dC, rest, d_grad, d_dh, st);
-    if (d_jtv) vjp_launch(f, W, nl, nl - 1, 1, h, prb, nrm, v, loc, C, nullptr, d_jtv, nullptr, st);
-  } else {
-    // the states h_1 .. h_{L-1} at h with their tangents along gbar, then the chain backwards: layer l at (h_l, t_l, w_{l+1}, dw_{l+1})
-    double *states = rest, *tans = states + (nl - 1) * row, *wpp = tans + (nl - 1) * row, *dwpp = wpp + 2 * row, *part = dwpp + 2 * row;
-    const double *ch = h, *ct = gbar;
-    for (int l = 0; l + 1 < nl; ++l) {
-      jvp_launch(f, W, nl, l, 0, ch, ct, h0, prb, nullptr, states + l * row, tans + l * row, nullptr, st);
-      ch = states + l * row;
-      ct = tans + l * row;
-    }
-    const double *cw_ = v, *cdw = nullptr;
-    for (int l = nl - 1; l >= 0; --l) {
-      const double* hl = l == 0 ? h : states + (l - 1) * row;
-      const double* tl = l == 0 ? gbar : tans + (l - 1) * row;
-      double* ddst = l == 0 ? d_dh : dwpp + (l & 1) * row;
-      double* dst = l == 0 ? d_jtv : wpp + (l & 1) * row;
-      jr_launch(f, W, nl, l, l == nl - 1, hl, tl, prb, nrm, cw_, cdw, C, dloc, dC, part, d_grad, ddst, st);
-      if (d_dinit && l > 0) {   // ddst: the tangent of the cotangent on h_l, whose Dirichlet rows are h_initial's
-        PROF_BYTES(f->p->N * (1 + 16 * D));
-        LAUNCH("k_f64_pg_init", st,
-               (k_f64_pg_init<<<(unsigned)cdiv(row, 256), 256, 0, st>>>(f->p->N, f->p->flags, ddst, l != nl - 1, d_dinit)));
-      }
-      if (dst) vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, cw_, loc, C, nullptr, dst, nullptr, st);
-      cw_ = dst;
-      cdw = ddst;
-    }
-  }
+  // a chain: the states and their tangents along gbar, the ping-pongs of w and dw, then the per-chunk partials
+  double *states = nullptr, *tans = nullptr, *wpp = nullptr, *dwpp = nullptr, *part = rest;
+  if (chain) states = rest, tans = states + (nl - 1) * row, wpp = tans + (nl - 1) * row, dwpp = wpp + 2 * row, part = dwpp + 2 * row;
+  if (d_dinit && !chain) HIP_TRY(hipMemsetAsync(d_dinit, 0, sizeof(double) * row, st));
+  // layer l at (h_l, t_l, w_{l+1}, dw_{l+1}).  mixed: only the last layer's iteration reaches the output, the earlier layers' sections
+  // stay zero
+  const double* cdw = nullptr;
+  f64_walk_back(f, W, nl, h, gbar, h0, prb, states, tans, v, wpp, d_jtv, nullptr, st,
+                [&](int l, bool end, const double* hl, const double* tl, const double* wl, double* dst) {
+                  double* ddst = end ? d_dh : dwpp + (l & 1) * row;
+                  jr_launch(f, W, nl, l, l == nl - 1, hl, tl, prb, nrm, wl, cdw, C, dloc, dC, part, d_grad, ddst, st);
+                  if (d_dinit && !end) {   // ddst: the tangent of the cotangent on h_l, whose Dirichlet rows are h_initial's
+                    PROF_BYTES(f->p->N * (1 + 16 * D));
+                    LAUNCH("k_f64_pg_init", st,
+                           (k_f64_pg_init<<<(unsigned)cdiv(row, 256), 256, 0, st>>>(f->p->N, f->p->flags, ddst, l != nl - 1, d_dinit)));
+                  }
+                  if (dst) vjp_launch(f, W, nl, l, l == nl - 1, hl, prb, nrm, wl, loc, C, nullptr, dst, nullptr, st);
+                  cdw = ddst;
+                });
   HIP_TRY(hipGetLastError());
   return PSIGNN_OK;
 }

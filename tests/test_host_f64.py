@@ -154,9 +154,10 @@ def test_null_arguments_are_error_codes():
 
 
 def test_shared_definitions_live_in_one_header():
-    """``W64``, ``struct psignn_f64`` and the fixed-order reductions of the float64 path are defined once, in csrc/f64_common.h, and
-    every object file is rebuilt when that header changes: two translation units can never read the handle or the weights at
-    different offsets, or sum in different orders."""
+    """``W64``, ``struct psignn_f64`` and the fixed-order reductions of the float64 path are defined once, in csrc/f64_common.h, the
+    node block of f_theta once, in csrc/f64_node.h, and every object file is rebuilt when either header changes: two translation
+    units can never read the handle or the weights at different offsets, sum in different orders, or state the gate, the update
+    and LayerNorm differently."""
     csrc = os.path.join(ROOT, "psi-gnn_amd", "csrc")
     texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
     for head in ("template <int P>\nstruct W64 {", "struct psignn_f64 {"):
@@ -170,8 +171,15 @@ def test_shared_definitions_live_in_one_header():
             assert not re.search(r"\w+_(wave|block|final)_sum\((const )?double", t), f
     assert len(re.findall(r"\w+_(?:wave|block|final)_sum\((?:const )?double", texts["f64_common.h"])) == 3
     users = sorted(f for f, t in texts.items() if '#include "f64_common.h"' in t)
-    assert users == ["fgnn_f64.hip", "fgnn_f64_deriv.hip", "krylov_f64.hip", "poisson_cg.hip", "solver_f64.hip"]
+    assert users == ["f64_node.h", "fgnn_f64.hip", "fgnn_f64_deriv.hip", "krylov_f64.hip", "poisson_cg.hip", "solver_f64.hip"]
     assert "k_f64_pgrad" in texts["fgnn_f64_deriv.hip"]
+    # the node block -- gate, update MLP, LayerNorm -- is stated once, in csrc/f64_node.h, which the map and its derivatives include
+    assert "f64_node.h" in hdrs
+    assert sorted(f for f, t in texts.items() if '#include "f64_node.h"' in t) == ["fgnn_f64.hip", "fgnn_f64_deriv.hip"]
+    f64_files = users + ["f64_common.h", "newton_f64.hip"]
+    for stmt in ("1.0 / (1.0 + exp(", "sqrt(var + 1e-5)"):   # the gate's sigmoid, the LayerNorm statistic
+        assert {f: texts[f].count(stmt) for f in f64_files if stmt in texts[f]} == {"f64_node.h": 1}, stmt
+    assert not [f for f, t in texts.items() if "k_f64_layer<" in t]
 
 
 def test_python_signatures():
