@@ -33,7 +33,7 @@ struct TabF {  // f_theta: 20 groups (layout in k_vjp_tile_a), 16 tiles
     return tab[t];
   }
 };
-struct TabX {  // f_theta, mixed family: 30 groups (extra groups in fgnn_vjp.hip PgRec), 24 tiles
+struct TabX {  // f_theta, mixed family: 30 groups (extra groups: the head of k_vjp_local, fgnn_vjp.hip), 24 tiles
   static constexpr int NG = 30, NT = 24;
   __host__ __device__ static constexpr int a(int t) {
     constexpr int tab[NT] = {6, 6, 6, 7, 8, 9, 10, 11, 12, 13, -1, -1, -1, -1, -1, -1, 23, 23, 24, 25, 26, 27, -1, -1};
@@ -49,7 +49,7 @@ struct TabM {  // two-layer MLP: groups {x|1, hid|1, d hid, d y}, tiles (d hid) 
   __host__ __device__ static constexpr int a(int t) { return t == 0 ? 2 : 3; }
   __host__ __device__ static constexpr int b(int t) { return t == 0 ? 0 : 1; }
 };
-static_assert(TabF::NG * 16 == ws::REC_F && TabF::NT == ws::NT_F && ws::PGREC == ws::REC_F && TabX::NG * 16 == ws::REC_X &&
+static_assert(TabF::NG * 16 == ws::REC_F && TabF::NT == ws::NT_F && TabX::NG * 16 == ws::REC_X &&
               TabX::NT == ws::NT_X && TabM::NG * 16 == ws::REC_M && TabM::NT == ws::NT_M, "record sizes of workspace.h");
 
 template <class Tab>
@@ -306,7 +306,7 @@ extern "C" int64_t psignn_param_grad_size(int mixed, int nl) {
 }
 
 // The records of one single-layer pass (n_rec = N; the backward of the VJP: 2 N) -> the flat gradient, zeroed first.  Dirichlet:
-// 20 groups, 16 tiles; mixed: 30 groups, 24 tiles (the Neumann factors of fgnn_vjp.hip's PgRec), and of a multi-layer block the
+// 20 groups, 16 tiles; mixed: 30 groups, 24 tiles (the Neumann factors, groups 20..29 of fgnn_vjp.hip), and of a multi-layer block the
 // last layer acts alone (mixed/psignn/model.py:221-245): its section, the earlier layers stay zero.
 static int pg_reduce_block(const psignn_plan* p, int nl, int64_t n_rec, const float* rec, float* part, float* d_grad,
                            hipStream_t st) {

@@ -24,7 +24,6 @@
 #include "jr_node.h"
 #include "internal.h"
 
-#define JR_REC 320   // floats per record (20 groups of 16)
 #define JR_RS 20     // pass A: floats per LDS row [Pj_to | Pj_from]
 #define JR_BS 30     // pass B: floats per LDS row [P | dS | dS'] = half a B row
 
@@ -123,22 +122,22 @@ __global__ __launch_bounds__(256) void k_jr_tile_a(int n_tiles, int chunk, int64
   __syncthreads();
   if (tid >= n_t) return;
   const int64_t n = (int64_t)t0 + tid;
-  float* r1 = rec + n * JR_REC;
-  float* r2 = rec + (N + n) * JR_REC;
+  float* r1 = rec + n * ws::rec_f(false);
+  float* r2 = rec + (N + n) * ws::rec_f(false);
   float* Bn = B + n * 2 * JR_BS;
   const uint8_t fl = flags[n];
-  jr_group(r1, x, D, 1.f);   // right factor of the W1 products, also for rows that only act as neighbours
-  jr_group(r2, gx, D);
+  rec_group(r1, x, D, 1.f);   // right factor of the W1 products, also for rows that only act as neighbours
+  rec_group(r2, gx, D);
   if (fl & FLAG_DIRICHLET) {   // constant row: sends nothing (groups 12, 13: pass B)
     float zero[D];
 #pragma unroll
     for (int o = 0; o < D; ++o) zero[o] = 0.f;
     store10(out + n * D, zero);
     for (int i = 0; i < 2 * JR_BS / 2; ++i) reinterpret_cast<float2*>(Bn)[i] = make_float2(0.f, 0.f);
-    jr_zero(r1, 1, 12);
-    jr_zero(r1, 14, JR_REC / 16);
-    jr_zero(r2, 1, 12);
-    jr_zero(r2, 14, JR_REC / 16);
+    rec_zero(r1, 1, 12);
+    rec_zero(r1, 14, ws::rec_f(false) / 16);
+    rec_zero(r2, 1, 12);
+    rec_zero(r2, 14, ws::rec_f(false) / 16);
     return;
   }
   const int lane = tid & 63;
@@ -169,8 +168,8 @@ __global__ __launch_bounds__(256) void k_jr_tile_a(int n_tiles, int chunk, int64
     const float* Pf_ = reinterpret_cast<const float*>(Pi);
 #pragma unroll
     for (int i = 0; i < 5; ++i) reinterpret_cast<float2*>(Bn)[i] = make_float2(Pf_[2 * i], Pf_[2 * i + 1]);
-    jr_group(r1 + 3 * 16, Sf, D, deg_in);
-    jr_group(r2 + 3 * 16, Tf, D);
+    rec_group(r1 + 3 * 16, Sf, D, deg_in);
+    rec_group(r2 + 3 * 16, Tf, D);
 #pragma unroll
     for (int o = 0; o < D; ++o) mpt[o] = deg_in * Wto[L::PHI_B2 + o];
     PHASE();
@@ -198,8 +197,8 @@ __global__ __launch_bounds__(256) void k_jr_tile_a(int n_tiles, int chunk, int64
     const float* Pf_ = reinterpret_cast<const float*>(Pi);
 #pragma unroll
     for (int i = 0; i < 5; ++i) reinterpret_cast<float2*>(Bn + JR_BS)[i] = make_float2(Pf_[2 * i], Pf_[2 * i + 1]);
-    jr_group(r1 + 4 * 16, Sf, D, deg_out);
-    jr_group(r2 + 4 * 16, Tf, D);
+    rec_group(r1 + 4 * 16, Sf, D, deg_out);
+    rec_group(r2 + 4 * 16, Tf, D);
 #pragma unroll
     for (int o = 0; o < D; ++o) mpf[o] = deg_out * Wfr[L::PHI_B2 + o];
     PHASE();
@@ -225,7 +224,7 @@ __global__ __launch_bounds__(256) void k_jr_tile_a(int n_tiles, int chunk, int64
   const float* cfr = reinterpret_cast<const float*>(c_fr);
   float dS[D], gt[D], gf[D];
   PHASE();
-  jr_matvecT<D, false>(Wto + L::PHI_W2, D, 0, ct, dS);
+  matvecT<D, false>(Wto + L::PHI_W2, D, 0, ct, dS);
   store10(Bn + D, dS);
   {
     // groups 16..19 of R1: dS[o] * (attr moments), index o * 3 + c as in the W1 attr block; the in-edges carry the mirrored attr.
@@ -243,7 +242,7 @@ __global__ __launch_bounds__(256) void k_jr_tile_a(int n_tiles, int chunk, int64
     for (int i = 0; i < 15; ++i) reinterpret_cast<float2*>(r1 + 16 * 16)[i] = make_float2(mo[2 * i], mo[2 * i + 1]);
   }
   PHASE();
-  jr_matvecT<D, false>(Wfr + L::PHI_W2, D, 0, cf, dS);
+  matvecT<D, false>(Wfr + L::PHI_W2, D, 0, cf, dS);
   store10(Bn + JR_BS + D, dS);
   {
     const float* mf = reinterpret_cast<const float*>(m_fr);
@@ -259,26 +258,26 @@ __global__ __launch_bounds__(256) void k_jr_tile_a(int n_tiles, int chunk, int64
 #pragma unroll
     for (int i = 0; i < 17; ++i) reinterpret_cast<float2*>(r1 + 16 * 16 + 30)[i] = make_float2(mo[2 * i], mo[2 * i + 1]);
   }
-  jr_group(r1 + 7 * 16, gt, D);
-  jr_group(r1 + 8 * 16, gf, D);
+  rec_group(r1 + 7 * 16, gt, D);
+  rec_group(r1 + 8 * 16, gf, D);
   PHASE();
-  jr_matvecT<D, true>(Wto + L::PHI_W1, L::EIN, 0, gt, ch);
+  matvecT<D, true>(Wto + L::PHI_W1, L::EIN, 0, gt, ch);
   PHASE();
-  jr_matvecT<D, true>(Wfr + L::PHI_W1, L::EIN, 0, gf, ch);
+  matvecT<D, true>(Wfr + L::PHI_W1, L::EIN, 0, gf, ch);
   store10(out + n * D, ch);
   PHASE();
-  jr_matvecT<D, false>(Wto + L::PHI_W2, D, 0, ct2, dS);
+  matvecT<D, false>(Wto + L::PHI_W2, D, 0, ct2, dS);
   store10(Bn + 2 * D, dS);
 #pragma unroll
   for (int o = 0; o < D; ++o) gt[o] = dS[o] * cto[o];
   PHASE();
-  jr_matvecT<D, false>(Wfr + L::PHI_W2, D, 0, cf2, dS);
+  matvecT<D, false>(Wfr + L::PHI_W2, D, 0, cf2, dS);
   store10(Bn + JR_BS + 2 * D, dS);
 #pragma unroll
   for (int o = 0; o < D; ++o) gf[o] = dS[o] * cfr[o];
-  jr_group(r2 + 7 * 16, gt, D);
-  jr_group(r2 + 8 * 16, gf, D);
-  jr_zero(r2, 16, JR_REC / 16);
+  rec_group(r2 + 7 * 16, gt, D);
+  rec_group(r2 + 8 * 16, gf, D);
+  rec_zero(r2, 16, ws::rec_f(false) / 16);
 }
 
 // ---------------------------------------------------------------------------------------------- pass B
@@ -371,18 +370,18 @@ __global__ __launch_bounds__(256) void k_jr_tile_b(int n_tiles, int chunk, int64
   jr_pass_rev<SLOT_IN>(slots, nslots, lds, T + L::T_A_FR, -1.f, Pj, af, af2);
   if (!active) return;
   // neighbour-side cotangent sums: the W1j gradients are sum_u acc[u] (x) x[u] (R1) + acc'[u] (x) gbar[u] (R2)
-  float* r1 = rec + u * JR_REC;
-  float* r2 = rec + (N + u) * JR_REC;
-  jr_group(r1 + 12 * 16, reinterpret_cast<const float*>(at), D);
-  jr_group(r1 + 13 * 16, reinterpret_cast<const float*>(af), D);
-  jr_group(r2 + 12 * 16, reinterpret_cast<const float*>(at2), D);
-  jr_group(r2 + 13 * 16, reinterpret_cast<const float*>(af2), D);
+  float* r1 = rec + u * ws::rec_f(false);
+  float* r2 = rec + (N + u) * ws::rec_f(false);
+  rec_group(r1 + 12 * 16, reinterpret_cast<const float*>(at), D);
+  rec_group(r1 + 13 * 16, reinterpret_cast<const float*>(af), D);
+  rec_group(r2 + 12 * 16, reinterpret_cast<const float*>(at2), D);
+  rec_group(r2 + 13 * 16, reinterpret_cast<const float*>(af2), D);
   float g[D];
   load10(out + u * D, g);
   PHASE();
-  jr_matvecT<D, true>(W + L::layer(0) + L::L_TO + L::PHI_W1, L::EIN, D, reinterpret_cast<const float*>(at), g);
+  matvecT<D, true>(W + L::layer(0) + L::L_TO + L::PHI_W1, L::EIN, D, reinterpret_cast<const float*>(at), g);
   PHASE();
-  jr_matvecT<D, true>(W + L::layer(0) + L::L_FROM + L::PHI_W1, L::EIN, D, reinterpret_cast<const float*>(af), g);
+  matvecT<D, true>(W + L::layer(0) + L::L_FROM + L::PHI_W1, L::EIN, D, reinterpret_cast<const float*>(af), g);
   store10(out + u * D, g);
 }
 
@@ -421,7 +420,7 @@ int psignn_jr_tile_records(const psignn_plan* p, const float* W, const float* h,
   const int tofs = L::tp_layer(1, false, 0);
   // pass A reads h, gbar, v (40 N each), prb (8 N), flags, writes B (240 N), the node-local d phi / d h (40 N) and the two
   // records less their groups 12, 13 (2 x 1 152 N); 20 bytes per directed edge (slot + attr)
-  PROF_BYTES((int64_t)N * (129 + 240 + 40 + 2 * (JR_REC - 32) * 4) + 20 * p->Ep);
+  PROF_BYTES((int64_t)N * (129 + 240 + 40 + 2 * (ws::rec_f(false) - 32) * 4) + 20 * p->Ep);
   LAUNCH("k_jr_tile_a", st, (k_jr_tile_a<2><<<grid, TILE_THREADS, lds_a, st>>>(
       (int)p->n_tiles, chunk, N, PLAN_TILES_FLAGS(p), W, tofs, h, prb, v, gbar, B, out_h, rec)));
   // pass B reads h (40 N), B (240 N) and the partial d phi / d h (40 N), writes it (40 N) and groups 12, 13 of both records

@@ -24,7 +24,6 @@
 #include "internal.h"
 
 #define VT 256
-#define PGREC 320   // floats per node of a parameter-gradient record: 20 groups of 16 (layout in k_vjp_tile_a)
 
 // acc[p] += W[o*ld + off + 2p..2p+1] * g[o]   (ORIGINAL (out,in) layout = the transposed product, k pairs adjacent)
 template <int NO>
@@ -71,19 +70,9 @@ __device__ __forceinline__ float pass_fwd(const uint4* __restrict__ slots, int n
   return deg;
 }
 
-// one 16-float group of a parameter-gradient record: v[0..n) then `tail`, then zeros
-__device__ __forceinline__ void rec_group(float* __restrict__ g, const float* v, int n, float t0 = 0.f, float t1 = 0.f,
-                                          float t2 = 0.f, float t3 = 0.f, float t4 = 0.f) {
-  float r[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-    r[i] = i < n ? v[i] : (i == n ? t0 : (i == n + 1 ? t1 : (i == n + 2 ? t2 : (i == n + 3 ? t3 : (i == n + 4 ? t4 : 0.f)))));
-  float4* q = reinterpret_cast<float4*>(g);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
-}
-
+// (the 16-float record groups: rec_group, fgnn_common.h)
 // LayerNorm forward + backward at one row: y -> normalised y (in place), dy = d loss / d y for the cotangent w of LN(y)
+// (the same statements stand inline in k_vjp_local, fgnn_vjp.hip; a fix made here is made there too)
 template <class L>
 __device__ __forceinline__ void ln_fwd_bwd(const float* __restrict__ W, float mu, float* y, const float* w, float* dy) {
   mu *= (1.f / D);
@@ -124,8 +113,8 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
                                                    const float* __restrict__ wv, float* __restrict__ B,
                                                    float* __restrict__ out, float* __restrict__ rec) {
   using L = WLayout<P>;
-  // record stride: 20 groups (dirichlet plans) / 30 (mixed plans, P = 3: the Neumann groups 20..29 of fgnn_vjp.hip's PgRec follow)
-  constexpr int REC = P == 3 ? 480 : PGREC;
+  // record stride: 20 groups (dirichlet plans) / 30 (mixed plans, P = 3: the Neumann groups 20..29 of fgnn_vjp.hip follow)
+  constexpr int REC = ws::rec_f(P == 3);
   constexpr int RS = MIXED ? 32 : 20;   // [Pj_to 10 | Pj_from 10 (| Pj_neu 10 | pad 2)]
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int slot_ = xcd_tile_slot(chunk);
@@ -272,7 +261,7 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_a(int n_tiles, int chunk, const
     }
     store10(out + n * D, go);
     if (PG) {
-      // ---- parameter-gradient record of a Neumann row (groups as fgnn_vjp.hip's PgRec): the interior branch's factors are zero
+      // ---- parameter-gradient record of a Neumann row (groups as in fgnn_vjp.hip): the interior branch's factors are zero
       float* r = rec + n * REC;
       const float* Wn = W + L::phi_neu(nl);
       float zero[D], mp[D], t[D];
@@ -590,7 +579,7 @@ __global__ __launch_bounds__(VT) void k_vjp_tile_b(int n_tiles, int chunk, const
                                                    const float* __restrict__ B, float* __restrict__ out,
                                                    float* __restrict__ rec) {
   using L = WLayout<P>;
-  constexpr int REC = P == 3 ? 480 : PGREC;
+  constexpr int REC = ws::rec_f(P == 3);
   // B row in memory: [Pt 10 | dS_to 10 | Pf 10 | dS_fr 10].  The OUT slots need the first half of the senders' rows, the IN slots the
   // second: the halves are staged one after the other into 80-byte LDS rows -- 26 KB per workgroup instead of 52, so six workgroups
   // fit a CU where three did (the kernel needs < 96 VGPRs: LDS was what held it at three waves per SIMD); same bytes from memory.
@@ -759,7 +748,7 @@ static int tile_vjp_layer(const psignn_plan* p, const float* W, int nl, int l, c
   } else {
     // pass A reads h, w (40 N each), prb (8 N), flags, writes B (160 N) and the node-local part (40 N) [+ the records];
     // 20 bytes per directed edge
-    PROF_BYTES(289 * p->N + 20 * p->Ep + (rec ? (int64_t)p->N * PGREC * 4 : 0));
+    PROF_BYTES(289 * p->N + 20 * p->Ep + (rec ? (int64_t)p->N * ws::REC_F * 4 : 0));
     if (rec)
       LAUNCH("k_pgrad_tile_a_noln", st, (k_vjp_tile_a<2, false, true, false><<<grid, VT, lds_a, st>>>(VJP_ARGS_A)));
     else

@@ -26,38 +26,6 @@
 #include <string.h>
 #include <stdlib.h>
 
-// The kernels below read ~1 500 wave-uniform weights.  Fully unrolled, the compiler hoists all their scalar loads to
-// the top and then spills > 1 000 SGPRs into VGPR lanes; in the record-writing (PG) instantiation of the mixed family
-// that went wrong on ROCm 7.2 (per-lane values came back as spilled weights).  A compiler-level memory barrier between
-// the phases keeps each phase's scalar loads next to their use (<= ~100 live SGPRs): no spills, and faster.
-#define PHASE() asm volatile("" ::: "memory")
-
-// out[k] (+)= sum_o W[o*ld + off + k] * g[o]   (transposed product, W wave-uniform)
-template <int K, bool ACC>
-__device__ __forceinline__ void matvecT(const float* __restrict__ W, int ld, int off, const float* g, float* out) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float s = ACC ? out[k] : 0.f;
-#pragma unroll
-    for (int o = 0; o < D; ++o) s = fmaf(W[o * ld + off + k], g[o], s);
-    out[k] = s;
-  }
-}
-
-// z[o] = Pi[o] + pj[o] + W1[o, 20:23] . a   (pre-activation of one edge; W1 = first Phi layer, ld = 23)
-__device__ __forceinline__ void edge_z(const float* __restrict__ W1, const float* Pi, const float* pj, float a0, float a1,
-                                       float a2, float* z) {
-  constexpr int EIN = 2 * D + 3;
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    float t = Pi[o] + pj[o];
-    t = fmaf(W1[o * EIN + 2 * D], a0, t);
-    t = fmaf(W1[o * EIN + 2 * D + 1], a1, t);
-    t = fmaf(W1[o * EIN + 2 * D + 2], a2, t);
-    z[o] = t;
-  }
-}
-
 // neighbour-side projections Pj[n] = { W1j_to h_n, W1j_fr h_n [, W1j_neu h_n] }
 template <int P, bool MIXED>
 __global__ __launch_bounds__(256) void k_vjp_project(int64_t N, const float* __restrict__ W, int lofs, int nofs,
@@ -81,24 +49,17 @@ __global__ __launch_bounds__(256) void k_vjp_project(int64_t N, const float* __r
 // Parameter-gradient records (PG mode; reduced by fgnn_pgrad.hip): 16-float groups per node.  Groups 0..19 as written by
 // the tiled kernels (fgnn_tile_vjp.hip); the mixed family appends 20: mp_n | prb | normal, 21: S_n | deg_out,
 // 22: hid_n | 1, 23: dq_n, 24: gn, 25: d mp_n, 26: dy_n, 27: acc_n (pass 2), 28..29: dS_n (.) attr.
-template <bool MIXED>
-struct PgRec {
-  static constexpr int NG = MIXED ? 30 : 20, SZ = 16 * NG;
-};
-__device__ __forceinline__ void pg_group(float* __restrict__ g, const float* v, int n, float t0 = 0.f, float t1 = 0.f,
-                                         float t2 = 0.f, float t3 = 0.f, float t4 = 0.f) {
-  float r[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-    r[i] = i < n ? v[i] : (i == n ? t0 : (i == n + 1 ? t1 : (i == n + 2 ? t2 : (i == n + 3 ? t3 : (i == n + 4 ? t4 : 0.f)))));
-  float4* q = reinterpret_cast<float4*>(g);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
-}
-__device__ __forceinline__ void pg_zero(float* __restrict__ g, int first, int last) {  // groups [first, last)
-  for (int i = first * 4; i < last * 4; ++i) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
+//
+// k_vjp_local keeps its own statement of the node block (unfolded gate, update MLP, Neumann update, LayerNorm and its backward).
+// The rule for taking a shared piece was: same bits, same occupancy, no more spills.
+//   - LayerNorm through a shared function form (statistics + first-order backward), in either row kind: other bits in <3, true, false, true> (the
+//     compiler pairs up the subtractions y - mean and no longer contracts them with the mean's multiply).
+//   - gate + update through a function form: occupancy changes in <2, false, false, true> and <3, true, false, true>
+//     (135 -> 113 / 114 VGPRs, 3 -> 4 waves per SIMD: not a loss, but not the same occupancy, so their timings would have to be
+//     made anew), and spilled SGPRs rise in <2, false, true, false> (320 -> 326) and <3, true, false, true> (402 -> 412).
+//   - Neumann update alone through a function form: <3, true, false, true> spills 432 SGPRs (402).
+// A LayerNorm fix made in ln_fwd_bwd (fgnn_tile_vjp.hip) is made here too.
+//
 // LN = false: the LayerNorm-off form of an intermediate layer of a multi-layer dirichlet block (launched as "k_vjp_local_noln"):
 // dy = w, and the record groups that feed laynorm (14, 15) stay zero
 template <int P, bool MIXED, bool PG, bool LN = true>
@@ -112,7 +73,7 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
                                                    float* __restrict__ B, float* __restrict__ out,
                                                    float* __restrict__ rec) {
   using L = WLayout<P>;
-  using R = PgRec<MIXED>;
+  constexpr int REC = ws::rec_f(MIXED);
   constexpr int NP = MIXED ? 3 : 2;   // Pj row = NP * 10 floats
   constexpr int NB = MIXED ? 6 : 4;   // B row  = NB * 10 floats
   int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -151,11 +112,11 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
     if (MIXED) store10(Bn + 5 * D, zero);
     store10(out + n * D, zero);
     if (PG) {  // a constant row still acts as a neighbour: its (x, 1) group feeds the W1j products of pass 2
-      float* r = rec + n * R::SZ;
-      pg_group(r, x, D, 1.f);
-      pg_zero(r, 1, 12);
-      pg_zero(r, 14, MIXED ? 27 : 20);
-      if (MIXED) pg_zero(r, 28, 30);
+      float* r = rec + n * REC;
+      rec_group(r, x, D, 1.f);
+      rec_zero(r, 1, 12);
+      rec_zero(r, 14, MIXED ? 27 : 20);
+      if (MIXED) rec_zero(r, 28, 30);
     }
     return;
   }
@@ -241,21 +202,21 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
     store10(Bn + 3 * D, zero);
     store10(Bn + 5 * D, dS_n);
     if (PG && MIXED) {  // everything but gn / the attr sums is known here: written before the second edge loop
-      float* r = rec + n * R::SZ;
+      float* r = rec + n * REC;
       float t[D];
-      pg_group(r, x, D, 1.f);
-      pg_zero(r, 1, 12);                                        // the interior branch's factors
+      rec_group(r, x, D, 1.f);
+      rec_zero(r, 1, 12);                                        // the interior branch's factors
 #pragma unroll
       for (int o = 0; o < D; ++o) t[o] = w[o] * y[o];
-      pg_group(r + 14 * 16, t, D);
-      pg_group(r + 15 * 16, w, D);
-      pg_zero(r, 16, 20);
-      pg_group(r + 20 * 16, mp_n, D, pq[0], pq[1], pq[2], pq[3], pq[4]);
-      pg_group(r + 21 * 16, S_n, D, (float)(oe - ob));
-      pg_group(r + 22 * 16, hid, D, 1.f);
-      pg_group(r + 23 * 16, dq, D);
-      pg_group(r + 25 * 16, dmp_n, D);
-      pg_group(r + 26 * 16, dy, D);
+      rec_group(r + 14 * 16, t, D);
+      rec_group(r + 15 * 16, w, D);
+      rec_zero(r, 16, 20);
+      rec_group(r + 20 * 16, mp_n, D, pq[0], pq[1], pq[2], pq[3], pq[4]);
+      rec_group(r + 21 * 16, S_n, D, (float)(oe - ob));
+      rec_group(r + 22 * 16, hid, D, 1.f);
+      rec_group(r + 23 * 16, dq, D);
+      rec_group(r + 25 * 16, dmp_n, D);
+      rec_group(r + 26 * 16, dy, D);
     }
     float gn[D], dsa[PG ? 32 : 1];
 #pragma unroll
@@ -284,8 +245,8 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
     matvecT<D, true>(Wn + L::PHI_W1, L::EIN, 0, gn, g);
     store10(out + n * D, g);
     if (PG && MIXED) {
-      float* r = rec + n * R::SZ;
-      pg_group(r + 24 * 16, gn, D);
+      float* r = rec + n * REC;
+      rec_group(r + 24 * 16, gn, D);
       dsa[PG ? 30 : 0] = dsa[PG ? 31 : 0] = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i)
@@ -461,35 +422,35 @@ __global__ __launch_bounds__(256) void k_vjp_local(int64_t N, const float* __res
   matvecT<D, true>(Wfr + L::PHI_W1, L::EIN, 0, gf, g);
   store10(out + n * D, g);
   if (PG) {
-    float* r = rec + n * R::SZ;
+    float* r = rec + n * REC;
     float t[D];
-    pg_group(r, x, D, 1.f);
-    pg_group(r + 16, mp_to, D, pq[0], pq[1], P > 2 ? pq[P - 1] : 0.f);
-    pg_group(r + 2 * 16, mp_fr, D);
-    pg_group(r + 3 * 16, S_to, D, (float)(ie - ib));
-    pg_group(r + 4 * 16, S_fr, D, (float)(oe - ob));
-    pg_group(r + 5 * 16, hid, D, 1.f);
-    pg_group(r + 6 * 16, dq, D, dal);
-    pg_group(r + 7 * 16, gt, D);
-    pg_group(r + 8 * 16, gf, D);
-    pg_group(r + 9 * 16, dmp_to, D);
-    pg_group(r + 10 * 16, dmp_fr, D);
-    pg_group(r + 11 * 16, dupd, D);
+    rec_group(r, x, D, 1.f);
+    rec_group(r + 16, mp_to, D, pq[0], pq[1], P > 2 ? pq[P - 1] : 0.f);
+    rec_group(r + 2 * 16, mp_fr, D);
+    rec_group(r + 3 * 16, S_to, D, (float)(ie - ib));
+    rec_group(r + 4 * 16, S_fr, D, (float)(oe - ob));
+    rec_group(r + 5 * 16, hid, D, 1.f);
+    rec_group(r + 6 * 16, dq, D, dal);
+    rec_group(r + 7 * 16, gt, D);
+    rec_group(r + 8 * 16, gf, D);
+    rec_group(r + 9 * 16, dmp_to, D);
+    rec_group(r + 10 * 16, dmp_fr, D);
+    rec_group(r + 11 * 16, dupd, D);
     if constexpr (LN) {
 #pragma unroll
       for (int o = 0; o < D; ++o) t[o] = w[o] * y[o];
-      pg_group(r + 14 * 16, t, D);
-      pg_group(r + 15 * 16, w, D);
+      rec_group(r + 14 * 16, t, D);
+      rec_group(r + 15 * 16, w, D);
     } else {
-      pg_zero(r, 14, 16);
+      rec_zero(r, 14, 16);
     }
     dsa[PG ? 60 : 0] = dsa[PG ? 61 : 0] = dsa[PG ? 62 : 0] = dsa[PG ? 63 : 0] = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
       reinterpret_cast<float4*>(r + 16 * 16)[i] = make_float4(dsa[PG ? 4 * i : 0], dsa[PG ? 4 * i + 1 : 0], dsa[PG ? 4 * i + 2 : 0], dsa[PG ? 4 * i + 3 : 0]);
     if (MIXED) {
-      pg_zero(r, 20, 27);
-      pg_zero(r, 28, 30);
+      rec_zero(r, 20, 27);
+      rec_zero(r, 28, 30);
     }
   }
 }
@@ -546,10 +507,10 @@ __global__ __launch_bounds__(256) void k_vjp_remote(int64_t N, const float* __re
     }
   }
   if (PG) {  // neighbour-side cotangent sums: W1j gradients are sum_u acc[u] (x) x[u]
-    float* r = rec + u * PgRec<MIXED>::SZ;
-    pg_group(r + 12 * 16, at, D);
-    pg_group(r + 13 * 16, af, D);
-    if (MIXED) pg_group(r + 27 * 16, an, D);
+    float* r = rec + u * ws::rec_f(MIXED);
+    rec_group(r + 12 * 16, at, D);
+    rec_group(r + 13 * 16, af, D);
+    if (MIXED) rec_group(r + 27 * 16, an, D);
   }
   float g[D];
   load10(out + u * D, g);
@@ -581,7 +542,7 @@ static void launch_vjp(const psignn_plan* p, const float* W, int nl, const float
   } else if constexpr (!MIXED) {
     // reads h, w (40 N each), prb (8 N), flags, CSR + CSC (4 + 4 + 12 bytes per edge each way), Pj per edge (80 bytes);
     // writes B (160 N) and the node-local part (40 N) [+ the records]
-    PROF_BYTES(289 * p->N + 120 * (int64_t)p->E + (PG ? (int64_t)p->N * PgRec<false>::SZ * 4 : 0));
+    PROF_BYTES(289 * p->N + 120 * (int64_t)p->E + (PG ? (int64_t)p->N * ws::REC_F * 4 : 0));
     LAUNCH(PG ? "k_pgrad_local_noln" : "k_vjp_local_noln", st, (k_vjp_local<2, false, PG, false><<<grid, 256, 0, st>>>(
         p->N, W, lofs, nofs, unofs, p->csr_ptr, p->csr_nbr, p->csr_attr, p->csc_ptr, p->csc_nbr, p->csc_attr, p->flags, h, prb,
         nrm, w, Pj, B, out, rec)));

@@ -30,34 +30,18 @@
 // Dirichlet rows of f are constants: no node-level terms, they only act as neighbours.
 // Mixed family: a Neumann row is update_neumann([h, Phi_neumann(h), prb, normal]) before LayerNorm (mixed/psignn/model.py:
 // 236,241) -- piecewise linear up to LayerNorm, so its only second-order term is LayerNorm's; its factors go to the
-// record groups 20..29 of the mixed parameter-VJP (fgnn_vjp.hip PgRec).
+// record groups 20..29 of the mixed parameter-VJP (fgnn_vjp.hip).
 #include "jr_node.h"
 #include "workspace.h"
 
-#define PHASE() asm volatile("" ::: "memory")
-
-// z[o] = Pi[o] + pj[o] + W1[o, 20:23] . a   (W1 = first Phi layer, row length 23)
-__device__ __forceinline__ void jr_edge_z(const float* __restrict__ W1, const float* Pi, const float* pj, float a0, float a1,
-                                          float a2, float* z) {
-  constexpr int EIN = 2 * D + 3;
-#pragma unroll
-  for (int o = 0; o < D; ++o) {
-    float t = Pi[o] + pj[o];
-    t = fmaf(W1[o * EIN + 2 * D], a0, t);
-    t = fmaf(W1[o * EIN + 2 * D + 1], a1, t);
-    t = fmaf(W1[o * EIN + 2 * D + 2], a2, t);
-    z[o] = t;
-  }
-}
 template <bool MIXED>
 struct JrDims {
   static constexpr int NP = MIXED ? 3 : 2;      // Phi modules: to, from [, neumann]
   static constexpr int PJ = 2 * NP * D;         // P row: NP primal projections, then NP tangent ones
   static constexpr int NB = MIXED ? 6 : 4;      // B row: Pt, Pf, dS_to, dS_fr [, Pn, dS_n]
-  static constexpr int REC = MIXED ? 480 : 320;
 };
-static_assert(JrDims<true>::REC == ws::REC_X && JrDims<false>::REC == ws::REC_F && JrDims<true>::PJ == 6 * ws::W &&
-              JrDims<false>::PJ == 4 * ws::W && JrDims<true>::NB == 6 && JrDims<false>::NB == 4, "ws::jr_scratch / ws::JrWork");
+static_assert(JrDims<true>::PJ == 6 * ws::W && JrDims<false>::PJ == 4 * ws::W && JrDims<true>::NB == 6 && JrDims<false>::NB == 4,
+              "ws::jr_scratch / ws::JrWork");
 
 
 // neighbour-side projections of h (primal) and gbar (tangent): P[n] = { W1j_m h_n : m } { W1j_m gbar_n : m }
@@ -109,7 +93,7 @@ __device__ __forceinline__ void jr_phi_tangent(const float* __restrict__ Wm, con
     const float* Pu = Pb + (int64_t)nbr[i] * PJ;
     load10(Pu + poff, pj);
     load10(Pu + toff, dj);
-    jr_edge_z(Wm + L::PHI_W1, Pi, pj, attr[3 * (int64_t)i], attr[3 * (int64_t)i + 1], attr[3 * (int64_t)i + 2], z);
+    edge_z(Wm + L::PHI_W1, Pi, pj, attr[3 * (int64_t)i], attr[3 * (int64_t)i + 1], attr[3 * (int64_t)i + 2], z);
 #pragma unroll
     for (int o = 0; o < D; ++o) {
       S[o] += fmaxf(z[o], 0.f);
@@ -146,27 +130,27 @@ __global__ __launch_bounds__(256) void k_jr_tangent(int64_t N, const float* __re
   load10(gb + n * D, gx);
   const int32_t ib = csc_ptr[n], ie = csc_ptr[n + 1], ob = csr_ptr[n], oe = csr_ptr[n + 1];
   float* c = cb + n * 4 * D;
-  float* r1 = rec1 + n * J::REC;
-  float* r2 = rec2 + n * J::REC;
+  float* r1 = rec1 + n * ws::rec_f(MIXED);
+  float* r2 = rec2 + n * ws::rec_f(MIXED);
   if (MIXED && (fl & FLAG_NEUMANN)) {  // Phi_neumann is of the Phi_from type: out-edges
     jr_phi_tangent<J::PJ>(W + L::phi_neu(1), x, gx, csr_nbr, csr_attr, ob, oe, Pb, 2 * D, J::NP * D + 2 * D, S, T, mp, tt);
     store10(c, mp);
     store10(c + 2 * D, tt);
-    jr_group(r1 + 21 * 16, S, D, (float)(oe - ob));
-    jr_group(r2 + 21 * 16, T, D);
+    rec_group(r1 + 21 * 16, S, D, (float)(oe - ob));
+    rec_group(r2 + 21 * 16, T, D);
     return;
   }
   jr_phi_tangent<J::PJ>(W + L::layer(0) + L::L_TO, x, gx, csc_nbr, csc_attr, ib, ie, Pb, 0, J::NP * D, S, T, mp, tt);
   store10(c, mp);
   store10(c + 2 * D, tt);
-  jr_group(r1 + 3 * 16, S, D, (float)(ie - ib));
-  jr_group(r2 + 3 * 16, T, D);
+  rec_group(r1 + 3 * 16, S, D, (float)(ie - ib));
+  rec_group(r2 + 3 * 16, T, D);
   PHASE();
   jr_phi_tangent<J::PJ>(W + L::layer(0) + L::L_FROM, x, gx, csr_nbr, csr_attr, ob, oe, Pb, D, J::NP * D + D, S, T, mp, tt);
   store10(c + D, mp);
   store10(c + 3 * D, tt);
-  jr_group(r1 + 4 * 16, S, D, (float)(oe - ob));
-  jr_group(r2 + 4 * 16, T, D);
+  rec_group(r1 + 4 * 16, S, D, (float)(oe - ob));
+  rec_group(r2 + 4 * 16, T, D);
 }
 
 // step 2: node-level second order.  dir1[n] = d psi / d c_h (the direct part of d phi / d h).
@@ -180,32 +164,31 @@ __global__ __launch_bounds__(256) void k_jr_node(int64_t N, const float* __restr
                                                  float* __restrict__ dir1, float* __restrict__ rec1,
                                                  float* __restrict__ rec2) {
   using L = WLayout<P>;
-  using J = JrDims<MIXED>;
-  constexpr int NG = J::REC / 16;
+  constexpr int NG = ws::rec_f(MIXED) / 16;
   int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const float* Wu = W + L::layer(0) + L::L_UPD;
   const float* Wa = W + L::AL_W;
-  float* r1 = rec1 + n * J::REC;
-  float* r2 = rec2 + n * J::REC;
+  float* r1 = rec1 + n * ws::rec_f(MIXED);
+  float* r2 = rec2 + n * ws::rec_f(MIXED);
   const uint8_t fl = flags[n];
   float x[D], gx[D];
   load10(h + n * D, x);
   load10(gb + n * D, gx);
-  jr_group(r1, x, D, 1.f);   // right factor of the W1 products, also for rows that only act as neighbours
-  jr_group(r2, gx, D);
+  rec_group(r1, x, D, 1.f);   // right factor of the W1 products, also for rows that only act as neighbours
+  rec_group(r2, gx, D);
   if (fl & FLAG_DIRICHLET) {
     float zero[D];
 #pragma unroll
     for (int o = 0; o < D; ++o) zero[o] = 0.f;
     store10(dir1 + n * D, zero);
-    jr_zero(r1, 1, 12);
-    jr_zero(r1, 14, MIXED ? 27 : NG);
-    jr_zero(r2, 1, 12);
-    jr_zero(r2, 14, MIXED ? 27 : NG);
+    rec_zero(r1, 1, 12);
+    rec_zero(r1, 14, MIXED ? 27 : NG);
+    rec_zero(r2, 1, 12);
+    rec_zero(r2, 14, MIXED ? 27 : NG);
     if (MIXED) {
-      jr_zero(r1, 28, NG);
-      jr_zero(r2, 28, NG);
+      rec_zero(r1, 28, NG);
+      rec_zero(r2, 28, NG);
     }
     return;
   }
@@ -230,15 +213,16 @@ __global__ __launch_bounds__(256) void k_jr_node(int64_t N, const float* __restr
 #undef JR_NODE_DIR
 #undef JR_NODE_BODY
   if (MIXED) {  // the Neumann branch's factors (27 comes from the remote pass)
-    jr_zero(r1, 20, 27);
-    jr_zero(r1, 28, NG);
-    jr_zero(r2, 20, 27);
-    jr_zero(r2, 28, NG);
+    rec_zero(r1, 20, 27);
+    rec_zero(r1, 28, NG);
+    rec_zero(r2, 20, 27);
+    rec_zero(r2, 28, NG);
   }
 }
 
 // step 2, Neumann rows of the mixed family (a kernel of its own: together with the interior branch the compiler would keep
 // > 1 000 spilled SGPRs alive)
+// (Its forward is its own statement of the unfolded Neumann update: the tangent and the record writes stand between its statements.)
 template <int P>
 __global__ __launch_bounds__(256) void k_jr_node_neumann(int64_t N, const float* __restrict__ W,
                                                          const uint8_t* __restrict__ flags, const float* __restrict__ h,
@@ -247,19 +231,18 @@ __global__ __launch_bounds__(256) void k_jr_node_neumann(int64_t N, const float*
                                                          const float* __restrict__ cb, float* __restrict__ dir1,
                                                          float* __restrict__ rec1, float* __restrict__ rec2) {
   using L = WLayout<P>;
-  using J = JrDims<true>;
   int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const uint8_t fl = flags[n];
   if ((fl & FLAG_DIRICHLET) || !(fl & FLAG_NEUMANN)) return;
-  float* r1 = rec1 + n * J::REC;
-  float* r2 = rec2 + n * J::REC;
+  float* r1 = rec1 + n * ws::rec_f(true);
+  float* r2 = rec2 + n * ws::rec_f(true);
   float x[D], gx[D], w[D], pq[P + 2];
   load10(h + n * D, x);
   load10(gb + n * D, gx);
   load10(v + n * D, w);
-  jr_group(r1, x, D, 1.f);
-  jr_group(r2, gx, D);
+  rec_group(r1, x, D, 1.f);
+  rec_group(r2, gx, D);
 #pragma unroll
   for (int k = 0; k < P; ++k) pq[k] = prb[n * P + k];
   // ------------------------------------------------ Neumann row: y = N2 relu(N1 [h, mp_n, prb, normal] + nb1) + nb2
@@ -282,8 +265,8 @@ __global__ __launch_bounds__(256) void k_jr_node_neumann(int64_t N, const float*
   matvec10<D, false>(Un + L::NEU_W1, L::NEU_CAT, 0, gx, dq);
   PHASE();
   matvec10<D, true>(Un + L::NEU_W1, L::NEU_CAT, D, tn, dq);
-  jr_group(r1 + 20 * 16, mpn, D, pq[0], pq[1], pq[2], pq[3], pq[P + 1]);
-  jr_group(r2 + 20 * 16, tn, D);
+  rec_group(r1 + 20 * 16, mpn, D, pq[0], pq[1], pq[2], pq[3], pq[P + 1]);
+  rec_group(r2 + 20 * 16, tn, D);
 #pragma unroll
   for (int o = 0; o < D; ++o) {
     hid[o] = fmaxf(q[o], 0.f);
@@ -294,40 +277,40 @@ __global__ __launch_bounds__(256) void k_jr_node_neumann(int64_t N, const float*
   matvec10<D, true>(Un + L::NEU_W2, D, 0, hid, y);
   PHASE();
   matvec10<D, false>(Un + L::NEU_W2, D, 0, dhid, dy);
-  jr_group(r1 + 22 * 16, hid, D, 1.f);
-  jr_group(r2 + 22 * 16, dhid, D);
+  rec_group(r1 + 22 * 16, hid, D, 1.f);
+  rec_group(r2 + 22 * 16, dhid, D);
   float ybar[D], dybar[D], gln[D];
   PHASE();
   jr_layernorm(W + L::LN_G, w, y, dy, ybar, dybar, gln);
-  jr_group(r1 + 14 * 16, gln, D);
-  jr_group(r1 + 26 * 16, ybar, D);
-  jr_group(r2 + 26 * 16, dybar, D);
+  rec_group(r1 + 14 * 16, gln, D);
+  rec_group(r1 + 26 * 16, ybar, D);
+  rec_group(r2 + 26 * 16, dybar, D);
   float qb[D], dqb[D], ch[D], cm[D];
   PHASE();
-  jr_matvecT<D, false>(Un + L::NEU_W2, D, 0, ybar, qb);
+  matvecT<D, false>(Un + L::NEU_W2, D, 0, ybar, qb);
   PHASE();
-  jr_matvecT<D, false>(Un + L::NEU_W2, D, 0, dybar, dqb);
+  matvecT<D, false>(Un + L::NEU_W2, D, 0, dybar, dqb);
 #pragma unroll
   for (int o = 0; o < D; ++o) {
     qb[o] = q[o] > 0.f ? qb[o] : 0.f;
     dqb[o] = q[o] > 0.f ? dqb[o] : 0.f;
   }
-  jr_group(r1 + 23 * 16, qb, D);
-  jr_group(r2 + 23 * 16, dqb, D);
+  rec_group(r1 + 23 * 16, qb, D);
+  rec_group(r2 + 23 * 16, dqb, D);
   PHASE();
-  jr_matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, 0, qb, ch);
+  matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, 0, qb, ch);
   PHASE();
-  jr_matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, D, qb, cm);
+  matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, D, qb, cm);
   store10(dir1 + n * D, ch);
-  jr_group(r1 + 25 * 16, cm, D);
+  rec_group(r1 + 25 * 16, cm, D);
   PHASE();
-  jr_matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, D, dqb, cm);
-  jr_group(r2 + 25 * 16, cm, D);
+  matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, D, dqb, cm);
+  rec_group(r2 + 25 * 16, cm, D);
   // the interior branch's factors; 12 / 13 / 27 come from the remote pass, 21 / 24 / 28.. from the edge passes
-  jr_zero(r1, 1, 12);
-  jr_zero(r1, 15, 20);
-  jr_zero(r2, 1, 12);
-  jr_zero(r2, 14, 20);
+  rec_zero(r1, 1, 12);
+  rec_zero(r1, 15, 20);
+  rec_zero(r2, 1, 12);
+  rec_zero(r2, 14, 20);
 }
 
 // masked cotangent sums of one Phi module over node n's own edges: gs = sum_e 1[z_e > 0] dS, and (ATTR) its
@@ -344,7 +327,7 @@ __device__ __forceinline__ void jr_phi_backward(const float* __restrict__ Wm, co
   for (int32_t i = eb; i < ee; ++i) {
     const float a0 = attr[3 * (int64_t)i], a1 = attr[3 * (int64_t)i + 1], a2 = attr[3 * (int64_t)i + 2];
     load10(Pb + (int64_t)nbr[i] * PJ + poff, pj);
-    jr_edge_z(Wm + L::PHI_W1, Pi, pj, a0, a1, a2, z);
+    edge_z(Wm + L::PHI_W1, Pi, pj, a0, a1, a2, z);
 #pragma unroll
     for (int o = 0; o < D; ++o) {
       const float m = z[o] > 0.f ? dS[o] : 0.f;
@@ -387,7 +370,7 @@ __global__ __launch_bounds__(256) void k_jr_edge_local(int64_t N, const float* _
     if (!TAN) store10(out + n * D, zero);
     return;
   }
-  float* r = rec + n * J::REC;
+  float* r = rec + n * ws::rec_f(MIXED);
   const int32_t ib = csc_ptr[n], ie = csc_ptr[n + 1], ob = csr_ptr[n], oe = csr_ptr[n + 1];
   float x[D], g[D];
   load10(h + n * D, x);
@@ -405,19 +388,19 @@ __global__ __launch_bounds__(256) void k_jr_edge_local(int64_t N, const float* _
     PHASE();
     matvec10<D, true>(Wn + L::PHI_W1, L::EIN, 0, x, Pn);
     PHASE();
-    jr_matvecT<D, false>(Wn + L::PHI_W2, D, 0, dmn, dSn);
+    matvecT<D, false>(Wn + L::PHI_W2, D, 0, dmn, dSn);
 #pragma unroll
     for (int k = 0; k < 4; ++k) store10(Bn + k * D, zero);
     store10(Bn + 4 * D, Pn);
     store10(Bn + 5 * D, dSn);
     jr_phi_backward<J::PJ, !TAN>(Wn, Pn, dSn, csr_nbr, csr_attr, ob, oe, Pb, 2 * D, gn, mom);
-    jr_group(r + 24 * 16, gn, D);
+    rec_group(r + 24 * 16, gn, D);
 #pragma unroll
     for (int i = 0; i < 8; ++i)
       reinterpret_cast<float4*>(r + 28 * 16)[i] = make_float4(mom[4 * i], mom[4 * i + 1], mom[4 * i + 2], mom[4 * i + 3]);
     if (!TAN) {
       PHASE();
-      jr_matvecT<D, true>(Wn + L::PHI_W1, L::EIN, 0, gn, g);
+      matvecT<D, true>(Wn + L::PHI_W1, L::EIN, 0, gn, g);
       store10(out + n * D, g);
     }
     return;
@@ -436,9 +419,9 @@ __global__ __launch_bounds__(256) void k_jr_edge_local(int64_t N, const float* _
   PHASE();
   matvec10<D, true>(Wfr + L::PHI_W1, L::EIN, 0, x, Pf);
   PHASE();
-  jr_matvecT<D, false>(Wto + L::PHI_W2, D, 0, dmt, dSt);
+  matvecT<D, false>(Wto + L::PHI_W2, D, 0, dmt, dSt);
   PHASE();
-  jr_matvecT<D, false>(Wfr + L::PHI_W2, D, 0, dmf, dSf);
+  matvecT<D, false>(Wfr + L::PHI_W2, D, 0, dmf, dSf);
   store10(Bn, Pt);
   store10(Bn + D, Pf);
   store10(Bn + 2 * D, dSt);
@@ -452,17 +435,17 @@ __global__ __launch_bounds__(256) void k_jr_edge_local(int64_t N, const float* _
   for (int i = 0; i < 64; ++i) mom[i] = 0.f;
   jr_phi_backward<J::PJ, !TAN>(Wto, Pt, dSt, csc_nbr, csc_attr, ib, ie, Pb, 0, gt, mom);
   jr_phi_backward<J::PJ, !TAN>(Wfr, Pf, dSf, csr_nbr, csr_attr, ob, oe, Pb, D, gf, mom + 30);
-  jr_group(r + 7 * 16, gt, D);
-  jr_group(r + 8 * 16, gf, D);
+  rec_group(r + 7 * 16, gt, D);
+  rec_group(r + 8 * 16, gf, D);
   mom[60] = mom[61] = mom[62] = mom[63] = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i)
     reinterpret_cast<float4*>(r + 16 * 16)[i] = make_float4(mom[4 * i], mom[4 * i + 1], mom[4 * i + 2], mom[4 * i + 3]);
   if (!TAN) {
     PHASE();
-    jr_matvecT<D, true>(Wto + L::PHI_W1, L::EIN, 0, gt, g);
+    matvecT<D, true>(Wto + L::PHI_W1, L::EIN, 0, gt, g);
     PHASE();
-    jr_matvecT<D, true>(Wfr + L::PHI_W1, L::EIN, 0, gf, g);
+    matvecT<D, true>(Wfr + L::PHI_W1, L::EIN, 0, gf, g);
     store10(out + n * D, g);
   }
 }
@@ -494,7 +477,7 @@ __global__ __launch_bounds__(256) void k_jr_edge_remote(int64_t N, const float* 
     float pt[D], ds[D];
     load10(Bn, pt);
     load10(Bn + 2 * D, ds);
-    jr_edge_z(Wto + L::PHI_W1, pt, pjt, csr_attr[3 * (int64_t)i], csr_attr[3 * (int64_t)i + 1], csr_attr[3 * (int64_t)i + 2], z);
+    edge_z(Wto + L::PHI_W1, pt, pjt, csr_attr[3 * (int64_t)i], csr_attr[3 * (int64_t)i + 1], csr_attr[3 * (int64_t)i + 2], z);
 #pragma unroll
     for (int o = 0; o < D; ++o) at[o] += z[o] > 0.f ? ds[o] : 0.f;
   }
@@ -505,31 +488,31 @@ __global__ __launch_bounds__(256) void k_jr_edge_remote(int64_t N, const float* 
     float pf[D], ds[D];
     load10(Bn + D, pf);
     load10(Bn + 3 * D, ds);
-    jr_edge_z(Wfr + L::PHI_W1, pf, pjf, a0, a1, a2, z);
+    edge_z(Wfr + L::PHI_W1, pf, pjf, a0, a1, a2, z);
 #pragma unroll
     for (int o = 0; o < D; ++o) af[o] += z[o] > 0.f ? ds[o] : 0.f;
     if (MIXED) {
       load10(Bn + 4 * D, pf);
       load10(Bn + 5 * D, ds);
-      jr_edge_z(Wn + L::PHI_W1, pf, pjn, a0, a1, a2, z);
+      edge_z(Wn + L::PHI_W1, pf, pjn, a0, a1, a2, z);
 #pragma unroll
       for (int o = 0; o < D; ++o) an[o] += z[o] > 0.f ? ds[o] : 0.f;
     }
   }
-  float* r = rec + u * J::REC;
-  jr_group(r + 12 * 16, at, D);
-  jr_group(r + 13 * 16, af, D);
-  if (MIXED) jr_group(r + 27 * 16, an, D);
+  float* r = rec + u * ws::rec_f(MIXED);
+  rec_group(r + 12 * 16, at, D);
+  rec_group(r + 13 * 16, af, D);
+  if (MIXED) rec_group(r + 27 * 16, an, D);
   if (!TAN) {
     float g[D];
     load10(out + u * D, g);
     PHASE();
-    jr_matvecT<D, true>(Wto + L::PHI_W1, L::EIN, D, at, g);
+    matvecT<D, true>(Wto + L::PHI_W1, L::EIN, D, at, g);
     PHASE();
-    jr_matvecT<D, true>(Wfr + L::PHI_W1, L::EIN, D, af, g);
+    matvecT<D, true>(Wfr + L::PHI_W1, L::EIN, D, af, g);
     if (MIXED) {
       PHASE();
-      jr_matvecT<D, true>(Wn + L::PHI_W1, L::EIN, D, an, g);
+      matvecT<D, true>(Wn + L::PHI_W1, L::EIN, D, an, g);
     }
     store10(out + u * D, g);
   }
@@ -538,7 +521,6 @@ __global__ __launch_bounds__(256) void k_jr_edge_remote(int64_t N, const float* 
 template <int P, bool MIXED>
 static void jr_launch(const psignn_plan* p, const float* W, const float* h, const float* prb, const float* nrm, const float* v,
                       const float* gbar, float* out_h, float* work, float* rec1, float* rec2, hipStream_t st, bool ln = true) {
-  using J = JrDims<MIXED>;
   const int64_t N = p->N;
   const unsigned grid = (unsigned)cdiv(N, 256);
   const ws::JrScratch sc = ws::jr_scratch(N, MIXED, work);
@@ -550,7 +532,7 @@ static void jr_launch(const psignn_plan* p, const float* W, const float* h, cons
     LAUNCH("k_jr_node", st, (k_jr_node<P, MIXED><<<grid, 256, 0, st>>>(N, W, p->flags, h, prb, nrm, v, gbar, cb, dir, rec1, rec2)));
   } else if constexpr (!MIXED) {
     // reads h, prb, v, gbar, cb (40 + 8 + 40 + 40 + 160 bytes per node), writes dir and the two node-level record sets
-    PROF_BYTES((int64_t)N * (288 + 40 + 2 * J::REC * 4));
+    PROF_BYTES((int64_t)N * (288 + 40 + 2 * ws::rec_f(MIXED) * 4));
     LAUNCH("k_jr_node_noln", st, (k_jr_node<P, false, false><<<grid, 256, 0, st>>>(N, W, p->flags, h, prb, nrm, v, gbar, cb, dir, rec1, rec2)));
   }
   if constexpr (MIXED)
@@ -605,20 +587,20 @@ __global__ __launch_bounds__(256) void k_ds_phi(int64_t N, const float* __restri
   float x[D], S[D], T[D], mp[D], tt[D];
   load10(h + n * D, x);
   float* c = cb + n * 4 * D;
-  float* r = rec + n * J::REC;
+  float* r = rec + n * ws::rec_f(MIXED);
   if (MIXED && (fl & FLAG_NEUMANN)) {
     jr_phi_tangent<J::PJ>(W + L::phi_neu(1), x, x, csr_nbr, csr_attr, csr_ptr[n], csr_ptr[n + 1], Pb, 2 * D, J::NP * D + 2 * D, S, T, mp, tt);
     store10(c, mp);
-    jr_group(r + 21 * 16, S, D, (float)(csr_ptr[n + 1] - csr_ptr[n]));
+    rec_group(r + 21 * 16, S, D, (float)(csr_ptr[n + 1] - csr_ptr[n]));
     return;
   }
   jr_phi_tangent<J::PJ>(W + L::layer(0) + L::L_TO, x, x, csc_nbr, csc_attr, csc_ptr[n], csc_ptr[n + 1], Pb, 0, J::NP * D, S, T, mp, tt);
   store10(c, mp);
-  jr_group(r + 3 * 16, S, D, (float)(csc_ptr[n + 1] - csc_ptr[n]));
+  rec_group(r + 3 * 16, S, D, (float)(csc_ptr[n + 1] - csc_ptr[n]));
   PHASE();
   jr_phi_tangent<J::PJ>(W + L::layer(0) + L::L_FROM, x, x, csr_nbr, csr_attr, csr_ptr[n], csr_ptr[n + 1], Pb, D, J::NP * D + D, S, T, mp, tt);
   store10(c + D, mp);
-  jr_group(r + 4 * 16, S, D, (float)(csr_ptr[n + 1] - csr_ptr[n]));
+  rec_group(r + 4 * 16, S, D, (float)(csr_ptr[n + 1] - csr_ptr[n]));
 }
 
 // gate pre-activation  out[o] = b[o] + W[o, 0:10] . a + W[o, 10:20] . mt + W[o, 20:30] . mf + W[o, 30:30+P] . pq
@@ -646,24 +628,23 @@ __global__ __launch_bounds__(256) void k_ds_node_bwd(int64_t N, const float* __r
                                                      const float* __restrict__ wv, const float* __restrict__ cb,
                                                      float* __restrict__ dir, float* __restrict__ rec) {
   using L = WLayout<P>;
-  using J = JrDims<MIXED>;
-  constexpr int NG = J::REC / 16;
+  constexpr int NG = ws::rec_f(MIXED) / 16;
   constexpr int CAT = 3 * D + P, GSZ = D * CAT + D;
   int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
-  float* r = rec + n * J::REC;
+  float* r = rec + n * ws::rec_f(MIXED);
   const uint8_t fl = flags[n];
   float x[D];
   load10(h + n * D, x);
-  jr_group(r, x, D, 1.f);
+  rec_group(r, x, D, 1.f);
   if (fl & FLAG_DIRICHLET) {  // the row is a copy of H_0: its cotangent goes there (host side), nothing flows through
     float zero[D];
 #pragma unroll
     for (int o = 0; o < D; ++o) zero[o] = 0.f;
     store10(dir + n * D, zero);
-    jr_zero(r, 1, 12);
-    jr_zero(r, 14, MIXED ? 27 : NG);
-    if (MIXED) jr_zero(r, 28, NG);
+    rec_zero(r, 1, 12);
+    rec_zero(r, 14, MIXED ? 27 : NG);
+    if (MIXED) rec_zero(r, 28, NG);
     return;
   }
   float w[D], pq[P + 2];
@@ -688,21 +669,21 @@ __global__ __launch_bounds__(256) void k_ds_node_bwd(int64_t N, const float* __r
 #pragma unroll
     for (int o = 0; o < D; ++o) hid[o] = fmaxf(q[o], 0.f);
     PHASE();
-    jr_matvecT<D, false>(Un + L::NEU_W2, D, 0, w, dq);
+    matvecT<D, false>(Un + L::NEU_W2, D, 0, w, dq);
 #pragma unroll
     for (int o = 0; o < D; ++o) dq[o] = q[o] > 0.f ? dq[o] : 0.f;
     PHASE();
-    jr_matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, 0, dq, g);
+    matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, 0, dq, g);
     PHASE();
-    jr_matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, D, dq, dm);
+    matvecT<D, false>(Un + L::NEU_W1, L::NEU_CAT, D, dq, dm);
     store10(dir + n * D, g);
-    jr_zero(r, 1, 12);
-    jr_zero(r, 14, 20);
-    jr_group(r + 20 * 16, mpn, D, pq[0], pq[1], pq[2], pq[3], pq[P + 1]);
-    jr_group(r + 22 * 16, hid, D, 1.f);
-    jr_group(r + 23 * 16, dq, D);
-    jr_group(r + 25 * 16, dm, D);
-    jr_group(r + 26 * 16, w, D);
+    rec_zero(r, 1, 12);
+    rec_zero(r, 14, 20);
+    rec_group(r + 20 * 16, mpn, D, pq[0], pq[1], pq[2], pq[3], pq[P + 1]);
+    rec_group(r + 22 * 16, hid, D, 1.f);
+    rec_group(r + 23 * 16, dq, D);
+    rec_group(r + 25 * 16, dm, D);
+    rec_group(r + 26 * 16, w, D);
     return;
   }
   const float* Wz = Wg;
@@ -711,8 +692,8 @@ __global__ __launch_bounds__(256) void k_ds_node_bwd(int64_t N, const float* __r
   float mt[D], mf[D];
   load10(cb + n * 4 * D, mt);
   load10(cb + n * 4 * D + D, mf);
-  jr_group(r + 16, mt, D, pq[0], pq[1], P > 2 ? pq[P - 1] : 0.f);
-  jr_group(r + 2 * 16, mf, D);
+  rec_group(r + 16, mt, D, pq[0], pq[1], P > 2 ? pq[P - 1] : 0.f);
+  rec_group(r + 2 * 16, mf, D);
   float z[D], rr[D], rx[D], co[D];
   ds_gate<P>(Wz, x, mt, mf, pq, z);
   PHASE();
@@ -725,7 +706,7 @@ __global__ __launch_bounds__(256) void k_ds_node_bwd(int64_t N, const float* __r
   }
   PHASE();
   ds_gate<P>(Wc, rx, mt, mf, pq, co);
-  jr_group(r + 5 * 16, rx, D, 1.f);
+  rec_group(r + 5 * 16, rx, D, 1.f);
   float dpc[D], dpz[D], dpr[D], dx[D], dmt[D], dmf[D], t[D];
 #pragma unroll
   for (int o = 0; o < D; ++o) {
@@ -734,38 +715,38 @@ __global__ __launch_bounds__(256) void k_ds_node_bwd(int64_t N, const float* __r
     dpz[o] = w[o] * co[o] * z[o] * (1.f - z[o]);
   }
   PHASE();
-  jr_matvecT<D, false>(Wc, CAT, 0, dpc, t);            // cotangent of r h
+  matvecT<D, false>(Wc, CAT, 0, dpc, t);            // cotangent of r h
   PHASE();
-  jr_matvecT<D, false>(Wc, CAT, D, dpc, dmt);
+  matvecT<D, false>(Wc, CAT, D, dpc, dmt);
   PHASE();
-  jr_matvecT<D, false>(Wc, CAT, 2 * D, dpc, dmf);
+  matvecT<D, false>(Wc, CAT, 2 * D, dpc, dmf);
 #pragma unroll
   for (int o = 0; o < D; ++o) {
     dpr[o] = t[o] * x[o] * rr[o] * (1.f - rr[o]);
     dx[o] = fmaf(t[o], rr[o], w[o]);                   // through r h, and the residual path h' = h + ...
   }
-  jr_group(r + 14 * 16, dpc, D);
+  rec_group(r + 14 * 16, dpc, D);
   PHASE();
-  jr_matvecT<D, true>(Wz, CAT, 0, dpz, dx);
+  matvecT<D, true>(Wz, CAT, 0, dpz, dx);
   PHASE();
-  jr_matvecT<D, true>(Wz, CAT, D, dpz, dmt);
+  matvecT<D, true>(Wz, CAT, D, dpz, dmt);
   PHASE();
-  jr_matvecT<D, true>(Wz, CAT, 2 * D, dpz, dmf);
+  matvecT<D, true>(Wz, CAT, 2 * D, dpz, dmf);
   PHASE();
-  jr_matvecT<D, true>(Wr, CAT, 0, dpr, dx);
+  matvecT<D, true>(Wr, CAT, 0, dpr, dx);
   PHASE();
-  jr_matvecT<D, true>(Wr, CAT, D, dpr, dmt);
+  matvecT<D, true>(Wr, CAT, D, dpr, dmt);
   PHASE();
-  jr_matvecT<D, true>(Wr, CAT, 2 * D, dpr, dmf);
+  matvecT<D, true>(Wr, CAT, 2 * D, dpr, dmf);
   store10(dir + n * D, dx);
-  jr_group(r + 6 * 16, dpz, D);
-  jr_group(r + 9 * 16, dmt, D);
-  jr_group(r + 10 * 16, dmf, D);
-  jr_group(r + 11 * 16, dpr, D);
-  jr_zero(r, 15, 16);
+  rec_group(r + 6 * 16, dpz, D);
+  rec_group(r + 9 * 16, dmt, D);
+  rec_group(r + 10 * 16, dmf, D);
+  rec_group(r + 11 * 16, dpr, D);
+  rec_zero(r, 15, 16);
   if (MIXED) {
-    jr_zero(r, 20, 27);
-    jr_zero(r, 28, NG);
+    rec_zero(r, 20, 27);
+    rec_zero(r, 28, NG);
   }
 }
 
@@ -808,11 +789,10 @@ __global__ __launch_bounds__(256) void k_dss_node_bwd(int64_t N, const float* __
                                                       const float* __restrict__ wv, const float* __restrict__ cb,
                                                       float* __restrict__ dir, float* __restrict__ rec) {
   using L = WLayout<3>;
-  using J = JrDims<false>;
   int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const float* Wu = Wf + L::layer(0) + L::L_UPD;
-  float* r = rec + n * J::REC;
+  float* r = rec + n * ws::rec_f(false);
   float x[D], mt[D], mf[D], w[D], pq[3];
   load10(h + n * D, x);
   load10(cb + n * 4 * D, mt);
@@ -820,9 +800,9 @@ __global__ __launch_bounds__(256) void k_dss_node_bwd(int64_t N, const float* __
   load10(wv + n * D, w);
 #pragma unroll
   for (int k = 0; k < 3; ++k) pq[k] = bp[n * 3 + k];
-  jr_group(r, x, D, 1.f);
-  jr_group(r + 16, mt, D, pq[0], pq[1], pq[2]);
-  jr_group(r + 2 * 16, mf, D);
+  rec_group(r, x, D, 1.f);
+  rec_group(r + 16, mt, D, pq[0], pq[1], pq[2]);
+  rec_group(r + 2 * 16, mf, D);
   float q[D], hid[D], du[D], dq[D], g[D], dmt[D], dmf[D];
 #pragma unroll
   for (int o = 0; o < D; ++o) q[o] = Wu[L::UPD_B1 + o];
@@ -841,22 +821,22 @@ __global__ __launch_bounds__(256) void k_dss_node_bwd(int64_t N, const float* __
     g[o] = w[o];   // residual path h' = h + ...
   }
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W2, D, 0, du, dq);
+  matvecT<D, false>(Wu + L::UPD_W2, D, 0, du, dq);
 #pragma unroll
   for (int o = 0; o < D; ++o) dq[o] = q[o] > 0.f ? dq[o] : 0.f;
   PHASE();
-  jr_matvecT<D, true>(Wu + L::UPD_W1, L::CAT, 0, dq, g);
+  matvecT<D, true>(Wu + L::UPD_W1, L::CAT, 0, dq, g);
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W1, L::CAT, D, dq, dmt);
+  matvecT<D, false>(Wu + L::UPD_W1, L::CAT, D, dq, dmt);
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W1, L::CAT, 2 * D, dq, dmf);
+  matvecT<D, false>(Wu + L::UPD_W1, L::CAT, 2 * D, dq, dmf);
   store10(dir + n * D, g);
-  jr_group(r + 5 * 16, hid, D, 1.f);
-  jr_group(r + 6 * 16, dq, D);
-  jr_group(r + 9 * 16, dmt, D);
-  jr_group(r + 10 * 16, dmf, D);
-  jr_group(r + 11 * 16, du, D);
-  jr_zero(r, 14, 16);
+  rec_group(r + 5 * 16, hid, D, 1.f);
+  rec_group(r + 6 * 16, dq, D);
+  rec_group(r + 9 * 16, dmt, D);
+  rec_group(r + 10 * 16, dmf, D);
+  rec_group(r + 11 * 16, du, D);
+  rec_zero(r, 14, 16);
 }
 
 // work: ws::jr_scratch (dirichlet shape);  rec: (N, 320);  out_h: (N, 10) = w^T d step / d h

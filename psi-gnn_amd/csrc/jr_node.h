@@ -6,7 +6,11 @@
 // one interior row as a block of statements -- the forward, the tangent (dc = [gx, tt, tf, 0]) and the reverse sweep of
 // psi = w . dN(c; dc) at c = [x, mpt, mpf, pq].  A textual block and not a function on purpose: as an inlined function the same
 // statements left k_jr_node with other registers and spills (119 / 118 VGPRs, 571 / 573 and 558 / 554 spilled SGPRs), and the
-// existing instantiations were to keep their code (profiles/jr_tiled_resource_usage.txt).
+// existing instantiations were to keep their code (profiles/jr_tiled_resource_usage.txt).  It calls the shared helpers of
+// fgnn_common.h (matvecT, rec_group, rec_zero) but keeps its own forward: its gate sums x, mp_to and mp_from interleaved per
+// index -- another summation order than k_node's or k_vjp_local's gate -- and the tangent and the record writes stand between its
+// statements.  So a function form shared with those kernels was not tried again and there are no newer figures than those above:
+// the statements differ in substance (other bits), which rules a shared forward out before registers are counted.
 //   in scope:  P, LN (template parameters), L = WLayout<P>, W (packed weights), Wu, Wa (update and gate blocks),
 //              float x[D], gx[D], w[D], pq[>= P], mpt[D], mpf[D], tt[D], tf[D];  float *r1, *r2 (the row's two records)
 //   writes:    the node-level groups 1, 2, 5, 6, 9, 10, 11, 14, 15 of r1 and r2 (0: the kernel; 3, 4, 7, 8, 12, 13, 16..19: the edge
@@ -18,39 +22,12 @@
 #define PSIGNN_JR_NODE_H
 #include "fgnn_common.h"
 
-#ifndef PHASE
-#define PHASE() asm volatile("" ::: "memory")
-#endif
-
-template <int K, bool ACC>
-__device__ __forceinline__ void jr_matvecT(const float* __restrict__ W, int ld, int off, const float* g, float* out) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    float s = ACC ? out[k] : 0.f;
-#pragma unroll
-    for (int o = 0; o < D; ++o) s = fmaf(W[o * ld + off + k], g[o], s);
-    out[k] = s;
-  }
-}
-// one 16-float record group: v[0..n) then up to five trailing values, rest 0
-__device__ __forceinline__ void jr_group(float* __restrict__ g, const float* v, int n, float t0 = 0.f, float t1 = 0.f,
-                                         float t2 = 0.f, float t3 = 0.f, float t4 = 0.f) {
-  float r[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-    r[i] = i < n ? v[i] : (i == n ? t0 : (i == n + 1 ? t1 : (i == n + 2 ? t2 : (i == n + 3 ? t3 : (i == n + 4 ? t4 : 0.f)))));
-  float4* q = reinterpret_cast<float4*>(g);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
-}
-__device__ __forceinline__ void jr_zero(float* __restrict__ g, int first, int last) {  // groups [first, last)
-  for (int i = first * 4; i < last * 4; ++i) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
 // LayerNorm of y with tangent dy and probe w: psi = sum_o w_o gamma_o dyhat_o.  Returns ybar = d psi / d y,
 // dybar = d psi / d dy (the first-order LayerNorm backward of w) and gln = d psi / d gamma.
 __device__ __forceinline__ void jr_layernorm(const float* __restrict__ W, const float* w, float* y, const float* dy, float* ybar,
                                              float* dybar, float* gln) {
+  // (the statistics are stated inline at every LayerNorm site of the float32 kernels: as a shared function they changed the bits of
+  // k_jr_node<2, false, true>, whose subtractions y - mean the compiler then pairs up and no longer contracts with the mean's multiply)
   float mu = 0.f, var = 0.f;
 #pragma unroll
   for (int o = 0; o < D; ++o) mu += y[o];
@@ -130,10 +107,10 @@ __device__ __forceinline__ void jr_layernorm(const float* __restrict__ W, const 
   matvec10<D, true>(Wu + L::UPD_W1, L::CAT, D, tt, dq);
   PHASE();
   matvec10<D, true>(Wu + L::UPD_W1, L::CAT, 2 * D, tf, dq);
-  jr_group(r1 + 16, mpt, D, pq[0], pq[1], P > 2 ? pq[P - 1] : 0.f);
-  jr_group(r1 + 2 * 16, mpf, D);
-  jr_group(r2 + 16, tt, D);
-  jr_group(r2 + 2 * 16, tf, D);
+  rec_group(r1 + 16, mpt, D, pq[0], pq[1], P > 2 ? pq[P - 1] : 0.f);
+  rec_group(r1 + 2 * 16, mpf, D);
+  rec_group(r2 + 16, tt, D);
+  rec_group(r2 + 2 * 16, tf, D);
 #pragma unroll
   for (int o = 0; o < D; ++o) {
     hid[o] = fmaxf(q[o], 0.f);
@@ -144,8 +121,8 @@ __device__ __forceinline__ void jr_layernorm(const float* __restrict__ W, const 
   matvec10<D, true>(Wu + L::UPD_W2, D, 0, hid, upd);
   PHASE();
   matvec10<D, false>(Wu + L::UPD_W2, D, 0, dhid, dupd);
-  jr_group(r1 + 5 * 16, hid, D, 1.f);
-  jr_group(r2 + 5 * 16, dhid, D);
+  rec_group(r1 + 5 * 16, hid, D, 1.f);
+  rec_group(r2 + 5 * 16, dhid, D);
   float y[D], dy[D], ybar[D], dybar[D], gln[D];
 #pragma unroll
   for (int o = 0; o < D; ++o) {
@@ -163,7 +140,7 @@ __device__ __forceinline__ void jr_layernorm(const float* __restrict__ W, const 
       gln[o] = 0.f;
     }
   }
-  jr_group(r1 + 14 * 16, gln, D);
+  rec_group(r1 + 14 * 16, gln, D);
   float albar = 0.f, dalbar = 0.f, ub[D], dub[D];
 #pragma unroll
   for (int o = 0; o < D; ++o) {
@@ -178,11 +155,11 @@ __device__ __forceinline__ void jr_layernorm(const float* __restrict__ W, const 
   const float abar = albar * sp;                         // adjoint of a
   float qb[D], dqb[D];
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W2, D, 0, ub, qb);
+  matvecT<D, false>(Wu + L::UPD_W2, D, 0, ub, qb);
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W2, D, 0, dub, dqb);
-  jr_group(r1 + 11 * 16, ub, D);
-  jr_group(r2 + 11 * 16, dub, D);
+  matvecT<D, false>(Wu + L::UPD_W2, D, 0, dub, dqb);
+  rec_group(r1 + 11 * 16, ub, D);
+  rec_group(r2 + 11 * 16, dub, D);
 #pragma unroll
   for (int o = 0; o < D; ++o) {
     qb[o] = q[o] > 0.f ? qb[o] : 0.f;
@@ -194,11 +171,11 @@ __device__ __forceinline__ void jr_layernorm(const float* __restrict__ W, const 
 #pragma unroll
   for (int k = 0; k < D; ++k) ch[k] = fmaf(Wa[k], abar, ybar[k]);
   PHASE();
-  jr_matvecT<D, true>(Wu + L::UPD_W1, L::CAT, 0, qb, ch);
+  matvecT<D, true>(Wu + L::UPD_W1, L::CAT, 0, qb, ch);
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W1, L::CAT, D, qb, ct);
+  matvecT<D, false>(Wu + L::UPD_W1, L::CAT, D, qb, ct);
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W1, L::CAT, 2 * D, qb, cf);
+  matvecT<D, false>(Wu + L::UPD_W1, L::CAT, 2 * D, qb, cf);
   PHASE();
 #pragma unroll
   for (int k = 0; k < D; ++k) {
@@ -206,22 +183,22 @@ __device__ __forceinline__ void jr_layernorm(const float* __restrict__ W, const 
     cf[k] = fmaf(Wa[2 * D + k], abar, cf[k]);
   }
   JR_NODE_DIR(ch);
-  jr_group(r1 + 6 * 16, qb, D, abar);
-  jr_group(r1 + 9 * 16, ct, D);
-  jr_group(r1 + 10 * 16, cf, D);
-  jr_zero(r1, 15, 16);
+  rec_group(r1 + 6 * 16, qb, D, abar);
+  rec_group(r1 + 9 * 16, ct, D);
+  rec_group(r1 + 10 * 16, cf, D);
+  rec_zero(r1, 15, 16);
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W1, L::CAT, D, dqb, ct2);
+  matvecT<D, false>(Wu + L::UPD_W1, L::CAT, D, dqb, ct2);
   PHASE();
-  jr_matvecT<D, false>(Wu + L::UPD_W1, L::CAT, 2 * D, dqb, cf2);
+  matvecT<D, false>(Wu + L::UPD_W1, L::CAT, 2 * D, dqb, cf2);
   PHASE();
 #pragma unroll
   for (int k = 0; k < D; ++k) {
     ct2[k] = fmaf(Wa[D + k], dabar, ct2[k]);
     cf2[k] = fmaf(Wa[2 * D + k], dabar, cf2[k]);
   }
-  jr_group(r2 + 6 * 16, dqb, D, dabar);
-  jr_group(r2 + 9 * 16, ct2, D);
-  jr_group(r2 + 10 * 16, cf2, D);
-  jr_zero(r2, 14, 16);
+  rec_group(r2 + 6 * 16, dqb, D, dabar);
+  rec_group(r2 + 9 * 16, ct2, D);
+  rec_group(r2 + 10 * 16, cf2, D);
+  rec_zero(r2, 14, 16);
 #endif

@@ -17,14 +17,6 @@
 #define TILE_THREADS 256
 #define EDGE_PD 2   // prefetch distance of the slot loads of every single-direction walk (SlotWalk)
 
-// Compiler-level memory barrier between the phases of a kernel.  The tile kernels read > 1 000 wave-uniform weights;
-// fully unrolled, the compiler hoists all their scalar loads to the top and then spills hundreds of SGPRs into VGPR
-// lanes (v_writelane / v_readlane = VALU issue slots in VALU-issue-bound kernels).  The barrier keeps each phase's
-// scalar loads next to their use.
-#ifndef PHASE
-#define PHASE() asm volatile("" ::: "memory")
-#endif
-
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v2f splat(float a) { return (v2f){a, a}; }

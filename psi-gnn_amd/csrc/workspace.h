@@ -17,8 +17,9 @@ constexpr int64_t W = PSIGNN_D;   // one latent row
 
 // Parameter-gradient records (static_assert'ed against the Tab* structs of fgnn_pgrad.hip): floats of one node's record and
 // 16 x 16 accumulator tiles of each table.  LAYER_VIEW: a single-layer view of the weights (fgnn_layers.hip).
-constexpr int64_t PGREC = 320, REC_F = 320, REC_X = 480, REC_G = 320, REC_GX = 480, REC_M = 64, LAYER_VIEW = 4096;
+constexpr int64_t REC_F = 320, REC_X = 480, REC_G = 320, REC_GX = 480, REC_M = 64, LAYER_VIEW = 4096;
 constexpr int NT_F = 16, NT_X = 24, NT_G = 19, NT_GX = 27, NT_M = 2;
+constexpr int rec_f(bool mixed) { return (int)(mixed ? REC_X : REC_F); }   // floats of one f_theta record on a plan of that family
 
 struct Carve {
   float* base;

@@ -1,11 +1,18 @@
-"""CRC-32 of the raw output bytes of every plan-order entry point that runs a tile kernel, on fixed seeds: one JSON line.
+"""CRC-32 of the raw output bytes of every entry point that runs a tile or gather kernel of the GNN block, on fixed seeds: one
+JSON line.
 
-The tile kernels use no atomics and fixed summation orders, so two builds of the library that compute the same statements
+These kernels use no atomics and fixed summation orders, so two builds of the library that compute the same statements
 give the same line; a differing CRC is a changed statement, not noise.  Entry points: FixedPointMap.fp, jvp_p, vjp_p,
 param_vjp_p and vjp_backward_p (the last two: dirichlet family; the mixed family's record kernels run under param_vjp),
-dsgps_step_p, dsgps_step_backward, dss_step_p, and Linearization.jvp_p / vjp_p; on make_hex_problem(13) (547 nodes, three
-tiles) and make_hex_problem(182) (about 100k nodes), both families.  Each call runs twice: "a,b" with a == b shows run-to-run
-identity.
+dsgps_step_p, dsgps_step_backward, dss_step_p, and Linearization.jvp_p / vjp_p; "flat.*": the caller-order entry points
+f, jvp, vjp, param_vjp_init and vjp_backward on an untiled plan (the global-gather kernels); "l2.*" / "l2flat.*"
+(dirichlet): vjp_p, param_vjp and vjp_backward of a two-layer block on the tiled and the untiled plan (the LayerNorm-off
+instantiations); "vjp_backward_gather" (mixed): the gather route of vjp_backward on the tiled plan.  vjp_backward takes the gather
+route unless tiled=True is passed, whatever the plan, so "l2.vjp_backward" runs the kernels of "l2flat.vjp_backward" and
+"vjp_backward_gather" those of the mixed "flat.vjp_backward": equal CRCs, kept as a check that the route does not depend on the
+plan's tiling, no further kernel reached.  On make_hex_problem(13)
+(547 nodes, three tiles) and make_hex_problem(182) (about 100k nodes), both families.  Each call runs twice: "a,b" with
+a == b shows run-to-run identity.
     python scripts/tile_bits.py [--out file.json]"""
 import argparse
 import importlib
@@ -26,6 +33,17 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 def weights(name, drop=()):
     w = np.load(os.path.join(GOLDEN, f"weights_{name}.npz"))
     return {k: torch.from_numpy(w[k]) for k in w.files if k not in drop}, w
+
+
+def stacked_dirichlet(sd, L):
+    """The dirichlet checkpoint with its layer 0 copied into layers 1..L-1 (tests/adjoint_gmres_ref.py's stacked_dirichlet)."""
+    out = dict(sd)
+    for k, t in sd.items():
+        for mod in ("phi_to_list", "phi_from_list", "update_list"):
+            if f".f.{mod}.0." in k:
+                for l in range(1, L):
+                    out[k.replace(f"{mod}.0.", f"{mod}.{l}.")] = t.clone()
+    return out
 
 
 def crc(out, c=0):
@@ -68,6 +86,23 @@ def psignn(n, mixed, dev):
     r["lin.jvp_p"] = twice(lambda: lin.jvp_p(Vp))
     r["lin.vjp_p"] = twice(lambda: lin.vjp_p(Wp))
     lin.close()
+    # caller-order entry points on an untiled plan: k_project, k_node, the gather k_vjp_* and k_jr_* kernels
+    Hd, Vd, Wd, Gd = (t.to(dev) for t in (h, v, wv, gb))
+    flat = eng.FixedPointMap(eng.MeshPlan(md, tile_target=-1), fm.weights, fm.h0, md.prb_data, nrm)
+    r["flat.f"] = twice(lambda: flat(Hd))
+    r["flat.jvp"] = twice(lambda: flat.jvp(Hd, Vd))
+    r["flat.vjp"] = twice(lambda: flat.vjp(Hd, Wd))
+    r["flat.param_vjp_init"] = twice(lambda: flat.param_vjp_init(Hd, Wd))
+    r["flat.vjp_backward"] = twice(lambda: flat.vjp_backward(Hd, Vd, Gd))
+    if mixed:   # the gather record kernels on a tiled plan (k_jr_node_neumann among them)
+        r["vjp_backward_gather"] = twice(lambda: fm.vjp_backward(Hd, Vd, Gd, tiled=False))
+    else:       # two-layer block (the checkpoint's layer stacked twice): the LayerNorm-off instantiations of layer 0
+        w2 = eng.PackedWeights(stacked_dirichlet(sd, 2), dev)
+        for tag, pl in (("l2", plan), ("l2flat", flat.plan)):
+            f2 = eng.FixedPointMap(pl, w2, h0.to(dev), md.prb_data, None)
+            r[tag + ".vjp_p"] = twice(lambda: f2.vjp_p(f2.to_plan(Hd), f2.to_plan(Wd)))
+            r[tag + ".param_vjp"] = twice(lambda: f2.param_vjp(Hd, Wd))
+            r[tag + ".vjp_backward"] = twice(lambda: f2.vjp_backward(Hd, Vd, Gd))
     ds, _ = weights("dsgps_mixed" if mixed else "dsgps", drop=("k",))
     h0p, prbp, nrmp = fm._p
     wd = eng.pack_dsgps(ds, dev)
