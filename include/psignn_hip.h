@@ -819,6 +819,37 @@ int psignn_gmres64_solve_adjoint(psignn_gmres64_t* s, const double* d_weights, i
                                  const double* d_h_initial, const double* d_prb, const double* d_normals, const double* d_grad,
                                  double eps, int max_products, int poll_every, double* d_work, int64_t work_doubles, double* d_result,
                                  psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
+/* Augmented restarts (LGMRES; Baker, Jessup, Manteuffel 2005) and a settable stall ratio for the float64 GMRES, opt-in; the method
+ * is stated in the header of csrc/krylov_f64.hip.  A solve keeps the `augment` newest corrections dy / |dy| of its cycles in a ring
+ * and, of the steps a cycle may take, spends the last ka = min(stored, augment, left - 1) on them: one product A zhat each, w = A zhat
+ * - shift zhat, orthogonalised against the basis like a Krylov vector.  The ring is cleared at the start of every solve.  stall: the
+ * solve ends at the head of a cycle c > 0 when !(rel <= stall * prev_rel); 0.5 is the rule of psignn_gmres64_solve_adjoint, 1.0
+ * stops only when a cycle does not lower rel at all.  {0, 0.5} launches the kernels of the entry points without options, with their
+ * arguments, and gives their bits.
+ * replaces: nothing of the reference; options of the solve that stands for dirichlet/psignn/model.py:210-223 in double precision. */
+typedef struct {
+  int32_t augment; /* corrections kept, 0 .. the handle's augment */
+  double stall;    /* in (0, 1] */
+} psignn_gmres64_opts_t;
+/* psignn_gmres_adjoint_info_t (shared with the fp32 solver, unchanged) plus the augmentation steps of the solve. */
+typedef struct {
+  int32_t products, cycles, stop_reason, n_reorth;
+  double lowest, lowest_abs;
+  int32_t n_aug;
+} psignn_gmres64_info_t;
+/* psignn_gmres64_create with a ring of augment + 1 vectors of N * d doubles, 0 <= augment <= min(m - 1, 8) (one slot more than a
+ * cycle reads, so that the cycle's correction is written while the kept ones are read); PSIGNN_ENOMEM names the ring's bytes when
+ * they do not fit.  augment = 0 is psignn_gmres64_create.  psignn_gmres64_bytes counts the ring.
+ * replaces: nothing kept between solves at dirichlet/psignn/model.py:210-223. */
+int psignn_gmres64_create_aug(psignn_gmres64_t** out, psignn_f64_t* f, int m, int augment);
+/* psignn_gmres64_solve_adjoint with options: opts->augment above the handle's, or stall outside (0, 1] or NaN, is PSIGNN_EINVAL
+ * before any launch.  Traces, poll_every, determinism, d_work and d_result as there.
+ * replaces: the solve of dirichlet/psignn/model.py:210-223 in double precision, by another method. */
+int psignn_gmres64_solve_adjoint_opts(psignn_gmres64_t* s, const double* d_weights, int n_layers, const double* d_h_star,
+                                      const double* d_h_initial, const double* d_prb, const double* d_normals, const double* d_grad,
+                                      double eps, int max_products, int poll_every, const psignn_gmres64_opts_t* opts, double* d_work,
+                                      int64_t work_doubles, double* d_result, psignn_gmres64_info_t* h_info, double* h_rel_trace,
+                                      double* h_abs_trace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Newton-Krylov in float64 on the device with a pseudo-transient shift (csrc/newton_f64.hip, csrc/krylov_f64.hip): a second float64
@@ -843,6 +874,15 @@ int psignn_gmres64_solve_shifted(psignn_gmres64_t* s, const double* d_weights, i
                                  double shift, int transposed, double eta, int max_products, int poll_every, double* d_work,
                                  int64_t work_doubles, double* d_result, psignn_gmres_adjoint_info_t* h_info, double* h_rel_trace,
                                  double* h_abs_trace, void* stream);
+/* psignn_gmres64_solve_shifted with the options of psignn_gmres64_solve_adjoint_opts (an augmentation step forms A zhat - shift zhat
+ * with this call's shift); refusals as there.
+ * replaces: nothing the reference runs -- the linear system of a Newton step on f(x) - x of dirichlet/psignn/model.py:189 in double
+ *           precision and its dual (shift 1: the system of model.py:210-223). */
+int psignn_gmres64_solve_shifted_opts(psignn_gmres64_t* s, const double* d_weights, int n_layers, const double* d_h,
+                                      const double* d_h_initial, const double* d_prb, const double* d_normals, const double* d_b,
+                                      double shift, int transposed, double eta, int max_products, int poll_every,
+                                      const psignn_gmres64_opts_t* opts, double* d_work, int64_t work_doubles, double* d_result,
+                                      psignn_gmres64_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
 /* The policy of the outer loop, host only (no device is touched): from the shift sigma of an attempted step and |g| before (g_old) and
  * at the trial point (g_new), *accept and the next shift.  Reject when g_new is not finite or g_new > growth * g_old: the next shift is
  * max(4 sigma, reject_floor).  Accept otherwise: sigma * g_new / g_old (switched evolution relaxation), exactly 0 when that is below
@@ -897,6 +937,19 @@ int psignn_newton64_solve(psignn_newton64_t* s, const double* d_weights, int n_l
                           int64_t work_doubles, double* d_result, psignn_newton64_info_t* h_info, double* h_rel_trace,
                           double* h_abs_trace, double* h_sigma_trace, double* h_trial_abs, int32_t* h_accepted, int32_t* h_krylov,
                           int32_t* h_lin_stop, void* stream);
+/* psignn_newton64_create whose GMRES64 handle comes from psignn_gmres64_create_aug(m, augment), and psignn_newton64_solve whose
+ * linear solves run psignn_gmres64_solve_shifted_opts with lin_opts (refused as there, before any launch).  lin_opts = {0, 0.5}
+ * gives the bits of psignn_newton64_solve.
+ * replaces: nothing kept between calls at dirichlet/psignn/model.py:189. */
+int psignn_newton64_create_aug(psignn_newton64_t** out, psignn_f64_t* f, int m, int augment);
+/* replaces: solver(lambda H: f(H, H_init, batch), H_init, threshold, eps) of dirichlet/psignn/model.py:189 in double precision, by
+ *           another method. */
+int psignn_newton64_solve_opts(psignn_newton64_t* s, const double* d_weights, int n_layers, const double* d_x0,
+                               const double* d_h_initial, const double* d_prb, const double* d_normals,
+                               const psignn_newton64_opts_t* opts, const psignn_gmres64_opts_t* lin_opts, double* d_work,
+                               int64_t work_doubles, double* d_result, psignn_newton64_info_t* h_info, double* h_rel_trace,
+                               double* h_abs_trace, double* h_sigma_trace, double* h_trial_abs, int32_t* h_accepted,
+                               int32_t* h_krylov, int32_t* h_lin_stop, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Parameter gradients in float64 on the device (csrc/fgnn_f64_deriv.hip): the last link of loss.backward() in double precision, and

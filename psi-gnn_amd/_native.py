@@ -61,6 +61,15 @@ class GmresAdjointInfo(C.Structure):
                 ("lowest", C.c_double), ("lowest_abs", C.c_double)]
 
 
+class Gmres64Opts(C.Structure):
+    _fields_ = [("augment", C.c_int32), ("stall", C.c_double)]
+
+
+class Gmres64Info(C.Structure):
+    _fields_ = [("products", C.c_int32), ("cycles", C.c_int32), ("stop_reason", C.c_int32), ("n_reorth", C.c_int32),
+                ("lowest", C.c_double), ("lowest_abs", C.c_double), ("n_aug", C.c_int32)]
+
+
 class Newton64Opts(C.Structure):
     _fields_ = [("eps", C.c_double), ("sigma0", C.c_double), ("eta", C.c_double), ("growth", C.c_double), ("reject_floor", C.c_double),
                 ("sigma_off", C.c_double), ("threshold", C.c_int32), ("max_products", C.c_int32), ("max_rejects", C.c_int32),
@@ -240,6 +249,12 @@ SIGNATURES = {
                                             C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_gmres64_solve_shifted": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, C.c_double, _INT, C.c_double, _INT, _INT, _P, _I64, _P,
                                             C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_gmres64_create_aug": (_INT, [C.POINTER(_P), _P, _INT, _INT]),
+    "psignn_gmres64_solve_adjoint_opts": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, C.c_double, _INT, _INT, C.POINTER(Gmres64Opts), _P, _I64,
+                                                 _P, C.POINTER(Gmres64Info), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_gmres64_solve_shifted_opts": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, C.c_double, _INT, C.c_double, _INT, _INT,
+                                                 C.POINTER(Gmres64Opts), _P, _I64, _P, C.POINTER(Gmres64Info), C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), _P]),
     "psignn_newton64_policy": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(_INT)]),
     "psignn_newton64_create": (_INT, [C.POINTER(_P), _P, _INT]),
     "psignn_newton64_destroy": (None, [_P]),
@@ -247,6 +262,10 @@ SIGNATURES = {
     "psignn_newton64_solve": (_INT, [_P, _P, _INT, _P, _P, _P, _P, C.POINTER(Newton64Opts), _P, _I64, _P, C.POINTER(Newton64Info),
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "psignn_newton64_create_aug": (_INT, [C.POINTER(_P), _P, _INT, _INT]),
+    "psignn_newton64_solve_opts": (_INT, [_P, _P, _INT, _P, _P, _P, _P, C.POINTER(Newton64Opts), C.POINTER(Gmres64Opts), _P, _I64, _P,
+                                          C.POINTER(Newton64Info), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "psignn_f64_param_vjp_chunk_rows": (_INT, []),
     "psignn_f64_param_vjp_workspace_doubles": (_I64, [_P, _INT]),
     "psignn_f64_param_vjp": (_INT, [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),

@@ -36,6 +36,27 @@ GMD_HD inline double gmd_column(int j, double* col, double* cs, double* sn, doub
   return fabs(g[j + 1]);
 }
 
+// ---- augmented restarts (LGMRES): the plan of a cycle and the ring of kept corrections, integers only.
+// tests/host/lgmres_plan_check.cpp compiles these with a host compiler and checks them over every small case.
+//
+// The plan: of the `left` steps a cycle may take, the last ka search the newest kept corrections, the first nk = left - ka are
+// Krylov steps; at least one Krylov step always runs.  `stored`: corrections in the ring; `augment`: how many the solve keeps.
+GMD_HD inline int lgm_plan_ka(int stored, int augment, int left) {
+  int ka = stored < augment ? stored : augment;
+  if (ka > left - 1) ka = left - 1;
+  return ka > 0 ? ka : 0;
+}
+GMD_HD inline int lgm_plan_nk(int stored, int augment, int left) { return left - lgm_plan_ka(stored, augment, left); }
+// The ring has nslots = (the handle's augment) + 1 slots and a head, the slot that is due: the next correction is written there,
+// which is never one of the <= nslots - 1 newest, so a cycle's combine may write it while it reads them.
+GMD_HD inline int lgm_slot_due(int head) { return head; }
+GMD_HD inline int lgm_slot_newest(int head, int nslots, int i /* 0: the newest; i < nslots - 1 */) {
+  int s = head - 1 - i;
+  return s < 0 ? s + nslots : s;
+}
+GMD_HD inline int lgm_push(int head, int nslots) { return head + 1 == nslots ? 0 : head + 1; }
+GMD_HD inline int lgm_stored_after_push(int stored, int augment) { return stored < augment ? stored + 1 : augment; }
+
 // z = R^{-1} g for the first k columns; a zero pivot gives z_i = 0.
 GMD_HD inline void gmd_backsolve(int k, int ld, const double* R, const double* g, double* z) {
   for (int i = k - 1; i >= 0; --i) {

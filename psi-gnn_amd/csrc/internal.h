@@ -103,6 +103,8 @@ int psignn_f64_vjp_gated(psignn_f64_t* f, const double* W, int nl, const double*
 int64_t psignn_nt64_blocks(int64_t M);
 void psignn_nt64_resid_norms(int64_t M, const double* fx, const double* x, double* g, double* part, double* norms, hipStream_t st);
 void psignn_nt64_add(int64_t M, const double* x, const double* d, double* xt, hipStream_t st);
+// corrections a solve on the handle may keep (psignn_gmres64_create_aug)
+int psignn_gmres64_augment(const psignn_gmres64_t* s);
 
 // ---- plan.hip
 int psignn_exclusive_scan(const int32_t* in, int64_t n, int32_t* out, int32_t* bsum, hipStream_t st);

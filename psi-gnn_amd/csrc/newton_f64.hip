@@ -56,13 +56,13 @@ extern "C" void psignn_newton64_destroy(psignn_newton64_t* s) {
   delete s;
 }
 
-extern "C" int psignn_newton64_create(psignn_newton64_t** out, psignn_f64_t* f, int m) {
-  ARG_CHECK(out != nullptr, "out is NULL");
+static int nt64_create(const char* who, psignn_newton64_t** out, psignn_f64_t* f, int m, int augment) {
+  ARG_CHECK_AS(who, out != nullptr, "out is NULL");
   *out = nullptr;
-  ARG_CHECK(f != nullptr, "the float64 map handle is NULL");
-  ARG_CHECK(m >= 1 && m <= 4096, "restart length out of range (1 .. 4096)");
+  ARG_CHECK_AS(who, f != nullptr, "the float64 map handle is NULL");
+  ARG_CHECK_AS(who, m >= 1 && m <= 4096, "restart length out of range (1 .. 4096)");
   const psignn_plan* p = psignn_f64_plan(f);
-  ARG_CHECK(p->N > 0, "the plan has no nodes");
+  ARG_CHECK_AS(who, p->N > 0, "the plan has no nodes");
   psignn_newton64* s = new psignn_newton64();
   s->f = f;
   s->N = p->N;
@@ -74,12 +74,13 @@ extern "C" int psignn_newton64_create(psignn_newton64_t** out, psignn_f64_t* f, 
     return code;
   };
   int rc;
-  if ((rc = psignn_gmres64_create(&s->gm, f, m))) return fail(rc);   // names the basis' bytes when they do not fit
+  // (names the basis' or the ring's bytes when they do not fit, and refuses an augment out of range)
+  if ((rc = augment ? psignn_gmres64_create_aug(&s->gm, f, m, augment) : psignn_gmres64_create(&s->gm, f, m))) return fail(rc);
   const size_t vec_bytes = (size_t)ws::newton64_vecs(s->N, nullptr).total * sizeof(double);
   if (hipMalloc((void**)&s->vec, vec_bytes) != hipSuccess) {
     (void)hipGetLastError();   // the failed allocation is reported here, not by the next launch
     s->vec = nullptr;
-    psignn_set_error("psignn_newton64_create: cannot allocate the float64 state vectors: 6 * N * d * 8 = 6 * %lld * %d * 8 = %zu bytes",
+    psignn_set_error("%s: cannot allocate the float64 state vectors: 6 * N * d * 8 = 6 * %lld * %d * 8 = %zu bytes", who,
                      (long long)s->N, D, vec_bytes);
     return fail(PSIGNN_ENOMEM);
   }
@@ -89,29 +90,37 @@ extern "C" int psignn_newton64_create(psignn_newton64_t** out, psignn_f64_t* f, 
   *out = s;
   return PSIGNN_OK;
 }
+extern "C" int psignn_newton64_create(psignn_newton64_t** out, psignn_f64_t* f, int m) { return nt64_create(__func__, out, f, m, 0); }
+extern "C" int psignn_newton64_create_aug(psignn_newton64_t** out, psignn_f64_t* f, int m, int augment) {
+  ARG_CHECK(augment >= 0, "augment out of range (0 .. min(m - 1, 8))");
+  return nt64_create(__func__, out, f, m, augment);
+}
 
 extern "C" size_t psignn_newton64_bytes(const psignn_newton64_t* s) {
   if (!s) return 0;
   return psignn_gmres64_bytes(s->gm) + ((size_t)6 * s->M + (size_t)2 * s->nblk + 2) * sizeof(double);
 }
 
-extern "C" int psignn_newton64_solve(psignn_newton64_t* s, const double* W, int nl, const double* x0, const double* h0,
-                                     const double* prb, const double* nrm, const psignn_newton64_opts_t* o, double* work,
-                                     int64_t work_doubles, double* result, psignn_newton64_info_t* h_info, double* h_rel_trace,
-                                     double* h_abs_trace, double* h_sigma_trace, double* h_trial_abs, int32_t* h_accepted,
-                                     int32_t* h_krylov, int32_t* h_lin_stop, void* stream) {
-  ARG_CHECK(s && W && x0 && h0 && prb && o && result && h_info, "NULL argument");
-  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
-  ARG_CHECK(o->eps >= 0.0 && o->eps < INFINITY, "eps must be finite and >= 0");
-  ARG_CHECK(o->eta >= 0.0 && o->eta < INFINITY, "eta must be finite and >= 0");
-  ARG_CHECK(o->sigma0 >= 0.0 && o->sigma0 < INFINITY, "sigma0 must be finite and >= 0");
-  ARG_CHECK(o->growth > 0.0 && o->growth < INFINITY, "growth must be finite and > 0");
-  ARG_CHECK(o->reject_floor > 0.0 && o->reject_floor < INFINITY, "reject_floor must be finite and > 0");
-  ARG_CHECK(o->sigma_off >= 0.0 && o->sigma_off < INFINITY, "sigma_off must be finite and >= 0");
-  ARG_CHECK(o->threshold >= 1 && o->threshold <= (1 << 20), "threshold out of range");
-  ARG_CHECK(o->max_rejects >= 1, "max_rejects must be >= 1");
-  ARG_CHECK(o->max_products >= 1 && o->max_products <= (1 << 24), "max_products out of range");
-  ARG_CHECK(result != x0, "result must not alias x0");
+// lo: the options of every linear solve ({0, 0.5}: the solves of psignn_newton64_solve)
+static int nt64_solve(const char* who, psignn_newton64_t* s, const double* W, int nl, const double* x0, const double* h0,
+                      const double* prb, const double* nrm, const psignn_newton64_opts_t* o, const psignn_gmres64_opts_t* lo,
+                      double* work, int64_t work_doubles, double* result, psignn_newton64_info_t* h_info, double* h_rel_trace,
+                      double* h_abs_trace, double* h_sigma_trace, double* h_trial_abs, int32_t* h_accepted, int32_t* h_krylov,
+                      int32_t* h_lin_stop, void* stream) {
+  ARG_CHECK_AS(who, s && W && x0 && h0 && prb && o && lo && result && h_info, "NULL argument");
+  ARG_CHECK_AS(who, lo->augment >= 0 && lo->augment <= psignn_gmres64_augment(s->gm), "augment out of range (0 .. the handle's augment)");
+  ARG_CHECK_AS(who, lo->stall > 0.0 && lo->stall <= 1.0, "stall must be in (0, 1]");   // (a NaN is not)
+  ARG_CHECK_AS(who, nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK_AS(who, o->eps >= 0.0 && o->eps < INFINITY, "eps must be finite and >= 0");
+  ARG_CHECK_AS(who, o->eta >= 0.0 && o->eta < INFINITY, "eta must be finite and >= 0");
+  ARG_CHECK_AS(who, o->sigma0 >= 0.0 && o->sigma0 < INFINITY, "sigma0 must be finite and >= 0");
+  ARG_CHECK_AS(who, o->growth > 0.0 && o->growth < INFINITY, "growth must be finite and > 0");
+  ARG_CHECK_AS(who, o->reject_floor > 0.0 && o->reject_floor < INFINITY, "reject_floor must be finite and > 0");
+  ARG_CHECK_AS(who, o->sigma_off >= 0.0 && o->sigma_off < INFINITY, "sigma_off must be finite and >= 0");
+  ARG_CHECK_AS(who, o->threshold >= 1 && o->threshold <= (1 << 20), "threshold out of range");
+  ARG_CHECK_AS(who, o->max_rejects >= 1, "max_rejects must be >= 1");
+  ARG_CHECK_AS(who, o->max_products >= 1 && o->max_products <= (1 << 24), "max_products out of range");
+  ARG_CHECK_AS(who, result != x0, "result must not alias x0");
   hipStream_t st = (hipStream_t)stream;
   const int64_t M = s->M;
   const size_t vbytes = (size_t)M * sizeof(double);
@@ -147,9 +156,9 @@ extern "C" int psignn_newton64_solve(psignn_newton64_t* s, const double* W, int 
       break;
     }
     if (n >= o->threshold) break;
-    psignn_gmres_adjoint_info_t lin;
-    if ((rc = psignn_gmres64_solve_shifted(s->gm, W, nl, x, h0, prb, nrm, g, 1.0 + sigma, 0, o->eta, o->max_products, o->poll_every, work,
-                                           work_doubles, delta, &lin, nullptr, nullptr, stream)))
+    psignn_gmres64_info_t lin;
+    if ((rc = psignn_gmres64_solve_shifted_opts(s->gm, W, nl, x, h0, prb, nrm, g, 1.0 + sigma, 0, o->eta, o->max_products, o->poll_every,
+                                                lo, work, work_doubles, delta, &lin, nullptr, nullptr, stream)))
       return rc;
     psignn_nt64_add(M, x, delta, xt, st);
     if ((rc = psignn_f64_eval(s->f, W, nl, xt, h0, prb, nrm, fxt, nullptr, st))) return rc;
@@ -197,4 +206,22 @@ extern "C" int psignn_newton64_solve(psignn_newton64_t* s, const double* W, int 
   h_info->lowest = lowest;
   h_info->lowest_abs = lowest_abs;
   return PSIGNN_OK;
+}
+extern "C" int psignn_newton64_solve(psignn_newton64_t* s, const double* W, int nl, const double* x0, const double* h0,
+                                     const double* prb, const double* nrm, const psignn_newton64_opts_t* o, double* work,
+                                     int64_t work_doubles, double* result, psignn_newton64_info_t* h_info, double* h_rel_trace,
+                                     double* h_abs_trace, double* h_sigma_trace, double* h_trial_abs, int32_t* h_accepted,
+                                     int32_t* h_krylov, int32_t* h_lin_stop, void* stream) {
+  const psignn_gmres64_opts_t plain = {0, 0.5};
+  return nt64_solve(__func__, s, W, nl, x0, h0, prb, nrm, o, &plain, work, work_doubles, result, h_info, h_rel_trace, h_abs_trace,
+                    h_sigma_trace, h_trial_abs, h_accepted, h_krylov, h_lin_stop, stream);
+}
+extern "C" int psignn_newton64_solve_opts(psignn_newton64_t* s, const double* W, int nl, const double* x0, const double* h0,
+                                          const double* prb, const double* nrm, const psignn_newton64_opts_t* o,
+                                          const psignn_gmres64_opts_t* lo, double* work, int64_t work_doubles, double* result,
+                                          psignn_newton64_info_t* h_info, double* h_rel_trace, double* h_abs_trace,
+                                          double* h_sigma_trace, double* h_trial_abs, int32_t* h_accepted, int32_t* h_krylov,
+                                          int32_t* h_lin_stop, void* stream) {
+  return nt64_solve(__func__, s, W, nl, x0, h0, prb, nrm, o, lo, work, work_doubles, result, h_info, h_rel_trace, h_abs_trace,
+                    h_sigma_trace, h_trial_abs, h_accepted, h_krylov, h_lin_stop, stream);
 }

@@ -2218,6 +2218,10 @@ class DeviceGmres64:
         ``DeviceGmres.solve_adjoint`` with a float64 ``result``: ``nstep`` = products spent, ``lowest``, ``rel_trace`` /
         ``abs_trace`` with one entry per cycle, ``n_cycles``, ``stop`` (one of ``GMRES_STOPS``), ``n_reorth``.  Deterministic;
         ``poll_every`` changes neither bits nor counts."""
+        return self._adjoint(h_star, grad, eps, max_products, poll_every, None)
+
+    def _adjoint(self, h_star, grad, eps, max_products, poll_every, opts):
+        """``opts``: None (``psignn_gmres64_solve_adjoint``) or a checked ``nat.Gmres64Opts`` (``..._opts``)."""
         if self.handle is None or self.fmap.handle is None:
             raise nat.NativeError("DeviceGmres64 (or its map) is closed")
         if int(max_products) < 1:
@@ -2226,16 +2230,19 @@ class DeviceGmres64:
         nat.require_default_width(getattr(getattr(fm, "weights", None), "width", D), "DeviceGmres64.solve_adjoint")
         hs, gr = fm._states((h_star, "h_star"), (grad, "grad"))
         result = torch.empty_like(gr)
-        info = nat.GmresAdjointInfo()
+        info = nat.GmresAdjointInfo() if opts is None else nat.Gmres64Info()
         cap = int(max_products) // 2 + 3
         rel, abs_ = (C.c_double * cap)(), (C.c_double * cap)()
         work, n = fm._work(True)
+        lead = (self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(hs), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                nat.ptr(gr), float(eps), int(max_products), int(poll_every))
+        tail = (nat.ptr(work), n, nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device))
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().psignn_gmres64_solve_adjoint(
-                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(hs), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
-                nat.ptr(gr), float(eps), int(max_products), int(poll_every), nat.ptr(work), n, nat.ptr(result), C.byref(info),
-                rel, abs_, nat.stream_ptr(self.device)), "psignn_gmres64_solve_adjoint")
-        return DeviceGmres._result(info, rel, abs_, result)
+            if opts is None:
+                nat.check(nat.lib().psignn_gmres64_solve_adjoint(*lead, *tail), "psignn_gmres64_solve_adjoint")
+            else:
+                nat.check(nat.lib().psignn_gmres64_solve_adjoint_opts(*lead, C.byref(opts), *tail), "psignn_gmres64_solve_adjoint_opts")
+        return self._dict(info, rel, abs_, result, opts)
 
     def solve_shifted(self, h, b, shift=1.0, transposed=False, eta=1e-2, max_products=200, poll_every=8):
         """``shift * delta = A delta + b`` from ``delta = 0`` (``psignn_gmres64_solve_shifted``), ``A = J_f(h)`` or, ``transposed``,
@@ -2243,6 +2250,10 @@ class DeviceGmres64:
         and >= 1; ``h``, ``b``: (N, 10), float32 (widened exactly) or float64.  Returns the dict of ``solve_adjoint``; ``rel_trace``
         and ``lowest`` are the linear measure ``|A delta + b - shift delta| / |b|``, met at ``rel <= eta``.  ``b = 0`` gives
         ``delta = 0`` without a product.  Deterministic; ``poll_every`` changes neither bits nor counts."""
+        return self._shifted(h, b, shift, transposed, eta, max_products, poll_every, None)
+
+    def _shifted(self, h, b, shift, transposed, eta, max_products, poll_every, opts):
+        """``opts``: None (``psignn_gmres64_solve_shifted``) or a checked ``nat.Gmres64Opts`` (``..._opts``)."""
         if self.handle is None or self.fmap.handle is None:
             raise nat.NativeError("DeviceGmres64 (or its map) is closed")
         if int(max_products) < 1:
@@ -2255,16 +2266,78 @@ class DeviceGmres64:
         nat.require_default_width(getattr(getattr(fm, "weights", None), "width", D), "DeviceGmres64.solve_shifted")
         hs, bc = fm._states((h, "h"), (b, "b"))
         result = torch.empty_like(bc)
-        info = nat.GmresAdjointInfo()
+        info = nat.GmresAdjointInfo() if opts is None else nat.Gmres64Info()
         cap = int(max_products) // 2 + 3
         rel, abs_ = (C.c_double * cap)(), (C.c_double * cap)()
         work, n = fm._work_both()
+        lead = (self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(hs), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                nat.ptr(bc), float(shift), int(bool(transposed)), float(eta), int(max_products), int(poll_every))
+        tail = (nat.ptr(work), n, nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device))
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().psignn_gmres64_solve_shifted(
-                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(hs), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
-                nat.ptr(bc), float(shift), int(bool(transposed)), float(eta), int(max_products), int(poll_every), nat.ptr(work), n,
-                nat.ptr(result), C.byref(info), rel, abs_, nat.stream_ptr(self.device)), "psignn_gmres64_solve_shifted")
-        return DeviceGmres._result(info, rel, abs_, result)
+            if opts is None:
+                nat.check(nat.lib().psignn_gmres64_solve_shifted(*lead, *tail), "psignn_gmres64_solve_shifted")
+            else:
+                nat.check(nat.lib().psignn_gmres64_solve_shifted_opts(*lead, C.byref(opts), *tail), "psignn_gmres64_solve_shifted_opts")
+        return self._dict(info, rel, abs_, result, opts)
+
+    @staticmethod
+    def _dict(info, rel, abs_, result, opts):
+        out = DeviceGmres._result(info, rel, abs_, result)
+        if opts is not None:
+            out["n_aug"], out["augment"] = int(info.n_aug), int(opts.augment)
+        return out
+
+
+AUGMENT_MAX = 8   # psignn_gmres64_create_aug
+
+
+def gmres64_opts(augment, stall, handle_augment, who):
+    """The checked ``psignn_gmres64_opts_t`` of one solve: ``augment`` (None: the handle's) in ``0 .. handle_augment``, ``stall`` in
+    ``(0, 1]``.  Raises ``NativeError`` before any native call."""
+    a = int(handle_augment if augment is None else augment)
+    if not 0 <= a <= int(handle_augment):
+        raise nat.NativeError(f"{who}: augment must be in 0 .. {int(handle_augment)} (the handle's), got {augment}")
+    st = float(stall)
+    if not 0.0 < st <= 1.0:   # (a NaN is not)
+        raise nat.NativeError(f"{who}: stall must be in (0, 1], got {stall}")
+    return nat.Gmres64Opts(a, st)
+
+
+def check_augment(augment, m, who):
+    if not 0 <= int(augment) <= min(int(m) - 1, AUGMENT_MAX):
+        raise nat.NativeError(f"{who}: augment must be in 0 .. min(m - 1, {AUGMENT_MAX}) = {min(int(m) - 1, AUGMENT_MAX)}, got {augment}")
+    return int(augment)
+
+
+class DeviceGmres64Aug(DeviceGmres64):
+    """``DeviceGmres64`` with augmented restarts (LGMRES) and a settable stall ratio (``psignn_gmres64_create_aug``,
+    ``psignn_gmres64_solve_*_opts``; the method: the header of csrc/krylov_f64.hip).  The handle holds a ring of ``augment + 1``
+    vectors beside the basis; a solve keeps the ``augment`` newest corrections of its cycles and searches them in the last steps of
+    the next cycle.  ``stall``: the solve ends on a cycle with ``not rel <= stall * prev_rel``; 0.5 is ``DeviceGmres64``'s rule, 1.0
+    stops only when a cycle does not lower ``rel``.  ``augment=0, stall=0.5`` launches the kernels of ``DeviceGmres64`` and gives its
+    bits.  A class of its own because the signatures of ``DeviceGmres64`` are pinned."""
+
+    def __init__(self, fmap64, m, augment=0):
+        if getattr(fmap64, "handle", None) is None:
+            raise nat.NativeError("DeviceGmres64Aug needs an open FixedPointMap64")
+        self.augment = check_augment(augment, m, "DeviceGmres64Aug")
+        self.fmap, self.m, self.device = fmap64, int(m), fmap64.device
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_gmres64_create_aug(C.byref(h), fmap64.handle, self.m, self.augment), "psignn_gmres64_create_aug")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_gmres64_destroy, h)
+
+    def solve_adjoint(self, h_star, grad, eps, max_products, poll_every=8, augment=None, stall=0.5):
+        """``DeviceGmres64.solve_adjoint`` with ``augment`` (None: the handle's) and ``stall``.  The dict gains ``n_aug`` (the
+        augmentation steps of the solve) and ``augment``."""
+        opts = gmres64_opts(augment, stall, self.augment, "DeviceGmres64Aug.solve_adjoint")
+        return self._adjoint(h_star, grad, eps, max_products, poll_every, opts)
+
+    def solve_shifted(self, h, b, shift=1.0, transposed=False, eta=1e-2, max_products=200, poll_every=8, augment=None, stall=0.5):
+        """``DeviceGmres64.solve_shifted`` with ``augment`` (None: the handle's) and ``stall``; the dict gains ``n_aug``, ``augment``."""
+        opts = gmres64_opts(augment, stall, self.augment, "DeviceGmres64Aug.solve_shifted")
+        return self._shifted(h, b, shift, transposed, eta, max_products, poll_every, opts)
 
 
 NEWTON_STOPS = ("threshold", "tolerance", "rejects")   # stop_reason of psignn_newton64_info_t
@@ -2319,6 +2392,10 @@ class DeviceNewton64:
         ``accepted``, ``trial_abs`` (``|g|`` at every trial point), ``krylov`` (products per attempted step), ``lin_stop`` (the
         linear solve's stop reason per attempted step, one of ``GMRES_STOPS``) and ``stop_reason`` (one of ``NEWTON_STOPS``).
         A rejected step leaves the state untouched bit for bit.  Deterministic; ``poll_every`` changes neither bits nor counts."""
+        return self._solve(x0, eps, threshold, sigma0, eta, max_products, growth, reject_floor, sigma_off, max_rejects, poll_every, None)
+
+    def _solve(self, x0, eps, threshold, sigma0, eta, max_products, growth, reject_floor, sigma_off, max_rejects, poll_every, lin_opts):
+        """``lin_opts``: None (``psignn_newton64_solve``) or a checked ``nat.Gmres64Opts`` (``psignn_newton64_solve_opts``)."""
         if self.handle is None or self.fmap.handle is None:
             raise nat.NativeError("DeviceNewton64 (or its map) is closed")
         fm = self.fmap
@@ -2341,11 +2418,14 @@ class DeviceNewton64:
         rel, abs_, sig, trial = ((C.c_double * (T + 1))() for _ in range(4))
         acc, kry, lst = ((C.c_int32 * T)() for _ in range(3))
         work, n = fm._work_both()
+        lead = (self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(x0c), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
+                C.byref(opts))
+        tail = (nat.ptr(work), n, nat.ptr(result), C.byref(info), rel, abs_, sig, trial, acc, kry, lst, nat.stream_ptr(self.device))
         with torch.cuda.device(self.device):
-            nat.check(nat.lib().psignn_newton64_solve(
-                self.handle, nat.ptr(fm.wflat), fm.weights.n_layers, nat.ptr(x0c), nat.ptr(fm.h0), nat.ptr(fm.prb), nat.ptr(fm.nrm),
-                C.byref(opts), nat.ptr(work), n, nat.ptr(result), C.byref(info), rel, abs_, sig, trial, acc, kry, lst,
-                nat.stream_ptr(self.device)), "psignn_newton64_solve")
+            if lin_opts is None:
+                nat.check(nat.lib().psignn_newton64_solve(*lead, *tail), "psignn_newton64_solve")
+            else:
+                nat.check(nat.lib().psignn_newton64_solve_opts(*lead, C.byref(lin_opts), *tail), "psignn_newton64_solve_opts")
         n_it, n_acc = int(info.n_iter), int(info.n_accepted)
         return {"result": result, "lowest": float(info.lowest), "lowest_abs": float(info.lowest_abs), "nstep": int(info.nstep),
                 "n_iter": n_it, "n_products": int(info.n_products), "n_feval": int(info.n_feval),
@@ -2354,11 +2434,36 @@ class DeviceNewton64:
                 "lin_stop": [GMRES_STOPS[int(c)] for c in lst[:n_it]], "stop_reason": NEWTON_STOPS[int(info.stop_reason)]}
 
 
+class DeviceNewton64Aug(DeviceNewton64):
+    """``DeviceNewton64`` whose linear solves are ``DeviceGmres64Aug``'s (``psignn_newton64_create_aug``,
+    ``psignn_newton64_solve_opts``): every linear solve keeps ``augment`` corrections and ends on ``lin_stall``.  ``augment=0,
+    lin_stall=0.5`` gives the bits of ``DeviceNewton64``.  A class of its own because the signatures of ``DeviceNewton64`` are pinned."""
+
+    def __init__(self, fmap64, m=50, augment=0):
+        if getattr(fmap64, "handle", None) is None:
+            raise nat.NativeError("DeviceNewton64Aug needs an open FixedPointMap64")
+        nat.require_default_width(getattr(getattr(fmap64, "weights", None), "width", D), "DeviceNewton64Aug")
+        self.augment = check_augment(augment, m, "DeviceNewton64Aug")
+        self.fmap, self.m, self.device = fmap64, int(m), fmap64.device
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().psignn_newton64_create_aug(C.byref(h), fmap64.handle, self.m, self.augment), "psignn_newton64_create_aug")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_newton64_destroy, h)
+
+    def solve(self, x0, eps=1e-11, threshold=50, sigma0=1.0, eta=1e-2, max_products=200, growth=2.0, reject_floor=0.0625,
+              sigma_off=1e-8, max_rejects=8, poll_every=8, lin_stall=0.5):
+        """``DeviceNewton64.solve``; every linear solve keeps the handle's ``augment`` corrections and ends on ``lin_stall``."""
+        lin = gmres64_opts(None, lin_stall, self.augment, "DeviceNewton64Aug.solve")
+        return self._solve(x0, eps, threshold, sigma0, eta, max_products, growth, reject_floor, sigma_off, max_rejects, poll_every, lin)
+
+
 def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16, solver="broyden", **solver_kwargs):
     """encoder -> float64 solve -> decoder, all in float64 on the device, for a device batch and a reference state dict (default
     latent width).  ``solver="broyden"`` (the default): ``DeviceBroyden64(threshold)``.  ``solver="newton"``:
     ``DeviceNewton64(m)`` from the encoder's ``h0`` with ``eps``, ``threshold`` (attempted steps at most) and ``poll_every`` as given
-    here; ``solver_kwargs`` are ``m`` and the other keywords of ``DeviceNewton64.solve``.
+    here; ``solver_kwargs`` are ``m`` and the other keywords of ``DeviceNewton64.solve``; with ``augment`` or ``lin_stall`` among
+    them the solver is ``DeviceNewton64Aug(m, augment)``.
     Returns the solver's dictionary plus ``h0`` (the encoded start) and ``u`` (the decoded result)."""
     if solver not in ("broyden", "newton"):
         raise nat.NativeError(f"fixed_point64: solver must be 'broyden' or 'newton', got {solver!r}")
@@ -2375,7 +2480,10 @@ def fixed_point64(batch, state_dict, eps=1e-11, threshold=1000, poll_every=16, s
     try:
         if solver == "newton":
             kw = dict(solver_kwargs)
-            sv = DeviceNewton64(fmap, kw.pop("m", 50))
+            if "augment" in kw or "lin_stall" in kw:
+                sv = DeviceNewton64Aug(fmap, kw.pop("m", 50), kw.pop("augment", 0))
+            else:
+                sv = DeviceNewton64(fmap, kw.pop("m", 50))
             out = sv.solve(h0, eps=eps, threshold=threshold, poll_every=poll_every, **kw)
         else:
             sv = DeviceBroyden64(fmap, threshold)
@@ -2414,6 +2522,32 @@ def adjoint64(batch, state_dict, h_star, grad, solver="gmres", eps=1e-11, m=50, 
             return sv.solve_adjoint(h_star, grad, eps, max_products)
         sv = DeviceBroyden64(fmap, threshold)
         return sv.solve_adjoint(h_star, grad, eps)
+    finally:
+        if sv is not None:
+            sv.close()
+        fmap.close()
+
+
+def adjoint64_aug(batch, state_dict, h_star, grad, eps=1e-11, m=50, max_products=2000, augment=0, stall=0.5):
+    """``adjoint64(solver="gmres")`` on ``DeviceGmres64Aug(m, augment)`` with ``stall``: the dict gains ``n_aug`` and ``augment``.
+    (``implicit_grad64(..., y=adjoint64_aug(...)["result"])`` turns it into parameter gradients.)"""
+    nat.require_default_width(width_of(state_dict), "adjoint64_aug")
+    n = int(batch.x.shape[0])
+    for t, name in ((h_star, "h_star"), (grad, "grad")):
+        if tuple(t.shape) != (n, D):
+            raise nat.NativeError(f"{name} has shape {tuple(t.shape)}, expected {(n, D)}")
+    check_augment(augment, m, "adjoint64_aug")
+    gmres64_opts(augment, stall, augment, "adjoint64_aug")
+    w = PackedWeights64(state_dict)
+    ae = lambda k: state_dict["autoencoder." + k]
+    enc = [ae(f"encoder.mlp.mlp.{i}.{p}") for i, p in ((0, "weight"), (0, "bias"), (2, "weight"), (2, "bias"))]
+    plan = plan_for(batch)
+    h0 = mlp2_64(batch.x, *enc)
+    fmap = FixedPointMap64(plan, w, h0, batch.prb_data, batch.edge_attr, getattr(batch, "unit_normal_vector", None))
+    sv = None
+    try:
+        sv = DeviceGmres64Aug(fmap, m, augment)
+        return sv.solve_adjoint(h_star, grad, eps, max_products, stall=stall)
     finally:
         if sv is not None:
             sv.close()
