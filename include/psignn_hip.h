@@ -658,6 +658,45 @@ int psignn_gmres_solve_adjoint_lin_batch(int n, psignn_gmres_t** solvers, const 
                                          int n_layers, const float* const* d_grads, double eps, int max_products, int poll_every,
                                          float* const* d_works, float* const* d_results, psignn_gmres_adjoint_info_t* h_infos,
                                          double* const* h_rel_trace, double* const* h_abs_trace, void* stream);
+/* Augmented restarts (LGMRES; Baker, Jessup, Manteuffel 2005) and a settable stall ratio for the restarted fp32 adjoint solve,
+ * opt-in; the method is the one psignn_gmres64_solve_adjoint_opts below runs in float64 (stated in the header of
+ * csrc/krylov_f64.hip), here with fp32 vectors.  A solve keeps the `augment` newest corrections dy / |dy| of its cycles in a ring and,
+ * of the steps a cycle may take, spends the last ka = min(stored, augment, left - 1) on them: one product J^T zhat each, w = J^T zhat -
+ * zhat, orthogonalised against the basis like a Krylov vector.  The ring is cleared at the start of every solve.  stall: the solve
+ * ends at the head of a cycle c > 0 when !(rel <= stall * prev_rel); 0.5 is the rule of psignn_gmres_solve_adjoint, 1.0 stops only
+ * when a cycle does not lower rel at all.  {0, 0.5} launches the kernels of the entry points without options, with their arguments,
+ * and gives their bits.  The lockstep solve above takes no options.
+ * replaces: nothing of the reference; options of the solve that stands for dirichlet/psignn/model.py:210-223. */
+typedef struct {
+  int32_t augment; /* corrections kept, 0 .. the handle's augment */
+  double stall;    /* in (0, 1] */
+} psignn_gmres_opts_t;
+/* psignn_gmres_adjoint_info_t (unchanged) plus the augmentation steps of the solve (model.py:210-223 reports none of this). */
+typedef struct {
+  int32_t products, cycles, stop_reason, n_reorth;
+  double lowest, lowest_abs;
+  int32_t n_aug;
+} psignn_gmres_info_t;
+/* psignn_gmres_create with a caller-owned ring of (augment + 1) rows of ld floats beside the basis, 0 <= augment <= min(m_max - 1, 8)
+ * (one slot more than a cycle reads, so that the cycle's correction is written while the kept ones are read).  shard_elems = 0: sized
+ * for itself; otherwise psignn_gmres_create_for_batch's rule.  augment = 0 with a NULL ring is psignn_gmres_create / _create_for_batch;
+ * d_ring is NULL exactly when augment is 0.
+ * replaces: nothing kept between solves at dirichlet/psignn/model.py:210-223. */
+int psignn_gmres_create_aug(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis, int augment, float* d_ring,
+                            int64_t shard_elems);
+/* psignn_gmres_solve_adjoint with options: opts->augment above the handle's, or stall outside (0, 1] or NaN, is PSIGNN_EINVAL before
+ * any launch.  Traces, poll_every, determinism, d_work and d_result as there.
+ * replaces: the solve of dirichlet/psignn/model.py:210-223 (autograd.grad(new_H, H, y) per step there), by another method. */
+int psignn_gmres_solve_adjoint_opts(psignn_gmres_t* s, const psignn_plan_t* plan, const float* d_weights, int n_layers,
+                                    const float* d_h_star, const float* d_prb, const float* d_normals, const float* d_grad, double eps,
+                                    int max_products, int poll_every, const psignn_gmres_opts_t* opts, float* d_work, float* d_result,
+                                    psignn_gmres_info_t* h_info, double* h_rel_trace, double* h_abs_trace, void* stream);
+/* psignn_gmres_solve_adjoint_lin with the same options, refused in the same way.
+ * replaces: the solve of dirichlet/psignn/model.py:210-223 with the Jacobian at H* linearised once, by another method. */
+int psignn_gmres_solve_adjoint_lin_opts(psignn_gmres_t* s, const psignn_lin_t* lin, const float* d_weights, int n_layers,
+                                        const float* d_grad, double eps, int max_products, int poll_every,
+                                        const psignn_gmres_opts_t* opts, float* d_work, float* d_result, psignn_gmres_info_t* h_info,
+                                        double* h_rel_trace, double* h_abs_trace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Reference solve of the discrete Poisson system A u = y on the device: Jacobi-preconditioned conjugate gradient in float64 on the

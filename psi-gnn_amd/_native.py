@@ -70,6 +70,15 @@ class Gmres64Info(C.Structure):
                 ("lowest", C.c_double), ("lowest_abs", C.c_double), ("n_aug", C.c_int32)]
 
 
+class GmresOpts(C.Structure):   # psignn_gmres_opts_t
+    _fields_ = [("augment", C.c_int32), ("stall", C.c_double)]
+
+
+class GmresInfo(C.Structure):   # psignn_gmres_info_t
+    _fields_ = [("products", C.c_int32), ("cycles", C.c_int32), ("stop_reason", C.c_int32), ("n_reorth", C.c_int32),
+                ("lowest", C.c_double), ("lowest_abs", C.c_double), ("n_aug", C.c_int32)]
+
+
 class Newton64Opts(C.Structure):
     _fields_ = [("eps", C.c_double), ("sigma0", C.c_double), ("eta", C.c_double), ("growth", C.c_double), ("reject_floor", C.c_double),
                 ("sigma_off", C.c_double), ("threshold", C.c_int32), ("max_products", C.c_int32), ("max_rejects", C.c_int32),
@@ -220,6 +229,11 @@ SIGNATURES = {
     "psignn_gmres_solve_adjoint_lin": (_INT, [_P, _P, _P, _INT, _P, C.c_double, _INT, _INT, _P, _P,
                                               C.POINTER(GmresAdjointInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_gmres_create_for_batch": (_INT, [C.POINTER(_P), _I64, _I64, _INT, _P, _I64]),
+    "psignn_gmres_create_aug": (_INT, [C.POINTER(_P), _I64, _I64, _INT, _P, _INT, _P, _I64]),
+    "psignn_gmres_solve_adjoint_opts": (_INT, [_P, _P, _P, _INT, _P, _P, _P, _P, C.c_double, _INT, _INT, C.POINTER(GmresOpts), _P, _P,
+                                               C.POINTER(GmresInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
+    "psignn_gmres_solve_adjoint_lin_opts": (_INT, [_P, _P, _P, _INT, _P, C.c_double, _INT, _INT, C.POINTER(GmresOpts), _P, _P,
+                                                   C.POINTER(GmresInfo), C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "psignn_gmres_adjoint_batchable": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P)]),
     "psignn_gmres_solve_adjoint_lin_batch": (_INT, [_INT, C.POINTER(_P), C.POINTER(_P), _P, _INT, C.POINTER(_P), C.c_double, _INT, _INT,
                                                     C.POINTER(_P), C.POINTER(_P), C.POINTER(GmresAdjointInfo),

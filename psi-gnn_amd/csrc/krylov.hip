@@ -20,6 +20,7 @@
 #include "vec_helpers.h"
 #include "internal.h"
 #include "solver_shapes.h"
+#include "gmres_dense.h"
 #include <algorithm>
 #include <stddef.h>
 #include <vector>
@@ -57,6 +58,9 @@ struct psignn_gmres {
   struct AdjState* h_ast = nullptr;
   double *a_rel = nullptr, *a_abs = nullptr;
   int a_cap = 0;             // entries of each trace
+  // augmented restarts of the adjoint solve (psignn_gmres_create_aug)
+  int augment = 0;           // corrections a solve on this handle may keep
+  float* Z = nullptr;        // caller-owned ring of corrections: (augment + 1, ld); NULL when augment = 0
 };
 
 // Solve-level state of the restarted adjoint solve (one per handle, device memory; GmresState above is re-armed every cycle)
@@ -71,6 +75,13 @@ struct AdjState {
   int32_t pad;
   double prev_rel, lowest, lowest_abs;
   double rnorm;         // |r| of this cycle (row 0 is divided by it)
+  // augmented restarts (cleared by k_lg_init, written by k_lg_check / k_lg_norm; a solve without options touches none of them)
+  int32_t nk, ka;       // this cycle's plan: Krylov steps, augmentation steps (nk + ka = steps_left)
+  int32_t stored;       // corrections in the ring
+  int32_t head;         // the ring slot that is due
+  int32_t n_aug;        // augmentation steps of this solve
+  int32_t dy_ok;        // the last cycle's correction went into the ring (its slot still holds dy, not dy / |dy|)
+  double dyn;           // |dy| of the last cycle
 };
 
 // (every kernel of the restarted adjoint solve keeps its code in a *_body function: the single-handle kernel and its batched form,
@@ -474,6 +485,21 @@ extern "C" int psignn_gmres_create_for_batch(psignn_gmres_t** out, int64_t n_ele
   return gmres_create(out, n_elems, ld, m_max, d_basis, shard_elems);
 }
 
+// A handle whose adjoint solves may keep up to `augment` corrections (psignn_gmres_solve_adjoint_opts): the ring is the caller's, like
+// the basis, (augment + 1) rows of ld floats.  shard_elems = 0: sized for itself; otherwise psignn_gmres_create_for_batch's rule.
+extern "C" int psignn_gmres_create_aug(psignn_gmres_t** out, int64_t n_elems, int64_t ld, int m_max, float* d_basis, int augment,
+                                       float* d_ring, int64_t shard_elems) {
+  if (out) *out = nullptr;
+  ARG_CHECK(augment >= 0 && augment <= 8 && augment <= m_max - 1, "augment out of range (0 .. min(m_max - 1, 8))");
+  ARG_CHECK((augment == 0) == (d_ring == nullptr), "d_ring holds (augment + 1) rows of ld floats; NULL exactly when augment is 0");
+  ARG_CHECK(shard_elems == 0 || shard_elems >= n_elems, "shard_elems is 0 or the sum of the shard's vector lengths: at least n_elems");
+  const int rc = gmres_create(out, n_elems, ld, m_max, d_basis, shard_elems ? shard_elems : n_elems);
+  if (rc) return rc;
+  (*out)->augment = augment;
+  (*out)->Z = d_ring;
+  return PSIGNN_OK;
+}
+
 // Device bytes the handle allocated itself (not the caller's basis): the dot partials follow the handle's blocks, hence its vector width
 extern "C" size_t psignn_gmres_bytes(const psignn_gmres_t* s) { return s ? s->bytes : 0; }
 
@@ -632,9 +658,13 @@ __global__ __launch_bounds__(TB) void k_ag_begin(int64_t M, const AdjState* __re
 }
 
 // One block: the stop tests of the solve and the re-arming of the cycle
+// AUG, a solve with kept corrections or another stall ratio (k_lg_check): the ratio is `stall`, the last cycle's augmentation steps
+// are counted and the cycle's plan is written.  The solve without options (AUG false) compiles to what it always was.
+template <bool AUG>
 __device__ __forceinline__ void ag_check_body(AdjState* as, GmresState* st, const float* __restrict__ part, int nblk,
                                               double* __restrict__ g, double* __restrict__ rel_trace,
-                                              double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
+                                              double* __restrict__ abs_trace, int cap, double eps, int max_products, int m,
+                                              double stall, int augment) {
   __shared__ double sh[TB];
   if (as->done) return;
   const double sr = block_sum_partials(part, nblk, sh);
@@ -660,7 +690,7 @@ __device__ __forceinline__ void ag_check_body(AdjState* as, GmresState* st, cons
   const int left = min(m, max_products - products - 1);
   int done = 1, stop = 0;
   if (rel < eps || nr == 0.0) stop = 1;   // (a zero right-hand side: y = 0 is the answer)
-  else if (c > 0 && !(rel <= 0.5 * as->prev_rel)) stop = 2;   // (a NaN stops here too)
+  else if (c > 0 && !(rel <= (AUG ? stall : 0.5) * as->prev_rel)) stop = 2;   // (a NaN stops here too)
   else if (left <= 0) stop = 0;
   else done = 0;
   as->prev_rel = rel;
@@ -669,6 +699,12 @@ __device__ __forceinline__ void ag_check_body(AdjState* as, GmresState* st, cons
   as->steps_left = done ? 0 : left;
   as->rnorm = nr;
   st->done = done;
+  if (AUG && c > 0 && st->k > as->nk) as->n_aug += st->k - as->nk;
+  if (AUG && !done) {
+    const int ka = lgm_plan_ka(as->stored, augment, left);
+    as->ka = ka;
+    as->nk = left - ka;
+  }
   if (!done) {
     st->k = 0; st->breakdown = 0; st->reorth = 1;
     st->beta = nf;          // k_gm_finish stops the cycle at |residual| <= eta * beta with eta = eps / 2
@@ -679,7 +715,13 @@ __device__ __forceinline__ void ag_check_body(AdjState* as, GmresState* st, cons
 __global__ __launch_bounds__(TB) void k_ag_check(AdjState* as, GmresState* st, const float* __restrict__ part, int nblk,
                                                  double* __restrict__ g, double* __restrict__ rel_trace,
                                                  double* __restrict__ abs_trace, int cap, double eps, int max_products, int m) {
-  ag_check_body(as, st, part, nblk, g, rel_trace, abs_trace, cap, eps, max_products, m);
+  ag_check_body<false>(as, st, part, nblk, g, rel_trace, abs_trace, cap, eps, max_products, m, 0.5, 0);
+}
+__global__ __launch_bounds__(TB) void k_lg_check(AdjState* as, GmresState* st, const float* __restrict__ part, int nblk,
+                                                 double* __restrict__ g, double* __restrict__ rel_trace,
+                                                 double* __restrict__ abs_trace, int cap, double eps, int max_products, int m,
+                                                 double stall, int augment) {
+  ag_check_body<true>(as, st, part, nblk, g, rel_trace, abs_trace, cap, eps, max_products, m, stall, augment);
 }
 
 template <int VEC>
@@ -696,6 +738,103 @@ template <int VEC>
 __global__ __launch_bounds__(TB) void k_ag_keep(int64_t M, const AdjState* __restrict__ as, const float* __restrict__ y,
                                                 float* __restrict__ ybest) {
   ag_keep_body<VEC>(M, as, y, ybest);
+}
+
+// ------------------------------------------------------------------------------------------
+// Augmented restarts (LGMRES; Baker, Jessup, Manteuffel 2005) and the stall ratio of the restarted adjoint solve, opt-in through
+// psignn_gmres_solve_adjoint_opts / _lin_opts.  The method is the one stated in the header of krylov_f64.hip, with fp32 vectors;
+// tests/lgmres_ref.py restates it.  In short:
+//   ring     : (the handle's augment) + 1 rows of ld floats beside the basis, caller-owned; cleared at the start of every solve
+//              (k_lg_init: stored = 0).  At the end of a cycle dy = sum_j z_j s_j, y -= dy; dy / |dy| becomes the newest entry when
+//              |dy| is positive and finite.  The slot that is due is never a source of the cycle that writes it.
+//   plan     : k_lg_check writes ka = min(stored, augment, left - 1) and nk = left - ka (gmres_dense.h: lgm_plan_*) into AdjState.
+//   aug step : j >= nk.  The product J^T zhat goes into basis row j + 1, k_lg_shift forms w -= zhat (zhat is no basis vector: the
+//              shift cannot sit on the Hessenberg's diagonal), then gm_step_launch with shift 0.
+//   end      : k_lg_combine reads min(k, nk) basis rows and k - min(k, nk) ring rows, writes y, the raw dy into the slot that is due
+//              and the block partials of |dy|^2; k_lg_norm (one block) turns them into |dy|, the stored flag and the new head;
+//              k_gm_scale divides the slot by |dy| once the next check has re-armed the flag it is gated by.
+//   stop     : at the head of cycle c > 0 the solve ends when !(rel <= stall * prev_rel).
+// No atomics, every scalar on the device; the host reads AdjState after a check, as it always has.  {augment 0, stall 0.5} launches
+// exactly the kernels of the solve without options.
+// ------------------------------------------------------------------------------------------
+__global__ void k_lg_init(AdjState* as) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    as->nk = 0; as->ka = 0; as->stored = 0; as->head = 0; as->n_aug = 0; as->dy_ok = 0; as->dyn = 0.0;
+  }
+}
+
+// w -= zhat in place, the head of an augmentation step: two reads, one write
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_lg_shift(int64_t M, const GmresState* __restrict__ st, const float* __restrict__ zhat,
+                                                 float* __restrict__ w) {
+  if (st->done) return;
+  int64_t e0 = elem0<VEC>();
+  if (e0 >= M) return;
+  float x[VEC], z[VEC];
+  ldv<VEC>(w, e0, M, x);
+  ldv<VEC>(zhat, e0, M, z);
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) x[i] -= z[i];
+  stv<VEC>(w, e0, M, x);
+}
+
+// The end of an augmented cycle (not gated: the cycle's flag is up): dy = sum_{i < min(k, nk)} coef_i v_i + sum_{nk <= i < k} coef_i
+// zhat_(i - nk), the basis rows first, each list in ascending order; y -= dy; dy -> the ring slot that is due; block partials of
+// |dy|^2 in part[0 .. nblk).  Z is read and written in distinct rows: the ring has one slot more than a cycle reads.
+template <int VEC>
+__global__ __launch_bounds__(TB) void k_lg_combine(int64_t M, int64_t ld, const GmresState* __restrict__ st,
+                                                   const AdjState* __restrict__ as, const float* __restrict__ V, float* Z, int nslots,
+                                                   const float* __restrict__ coef, float* __restrict__ y, float* __restrict__ part,
+                                                   int nblk) {
+  int64_t e0 = elem0<VEC>();
+  const int k = st->k, nk = as->nk, head = as->head;
+  const int kb = min(k, nk);
+  float s = 0.f, zero = 0.f;
+  if (e0 < M) {
+    float acc[VEC];
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) acc[q] = 0.f;
+    for (int i = 0; i < kb; ++i) {
+      const float c = coef[i];
+      float v[VEC];
+      ldv<VEC>(V + (int64_t)i * ld, e0, M, v);
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) acc[q] = fmaf(c, v[q], acc[q]);
+    }
+    for (int i = nk; i < k; ++i) {
+      const float c = coef[i];
+      float v[VEC];
+      ldv<VEC>(Z + (int64_t)lgm_slot_newest(head, nslots, i - nk) * ld, e0, M, v);
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) acc[q] = fmaf(c, v[q], acc[q]);
+    }
+    float b[VEC];
+    ldv<VEC>(y, e0, M, b);
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) {
+      b[q] -= acc[q];
+      s = fmaf(acc[q], acc[q], s);
+    }
+    stv<VEC>(y, e0, M, b);
+    stv<VEC>(Z + (int64_t)lgm_slot_due(head) * ld, e0, M, acc);
+  }
+  block_pair_store(s, zero, part, nblk);
+}
+
+// One block: n = |dy|; when n > 0 and finite the slot that was due becomes the newest entry (it holds dy until the next head of a
+// cycle divides it by n) and the `augment` newest are kept.
+__global__ __launch_bounds__(TB) void k_lg_norm(AdjState* as, const float* __restrict__ part, int nblk, int nslots, int augment) {
+  __shared__ double sh[TB];
+  const double s2 = block_sum_partials(part, nblk, sh);
+  if (threadIdx.x != 0) return;
+  const double n = (double)(float)sqrt(s2);
+  const int ok = n > 0.0 && n < (double)INFINITY;   // (a NaN is neither)
+  as->dyn = n;
+  as->dy_ok = ok;
+  if (ok) {
+    as->head = lgm_push(as->head, nslots);
+    as->stored = lgm_stored_after_push(as->stored, augment);
+  }
 }
 
 using ws::AdjWork;   // work = [ operator scratch | y | J^T y | y_best | grad_p | h*_p | prb_p | normals_p | layer states ]
@@ -762,23 +901,39 @@ static int adjoint_gmres_read_out(psignn_gmres* s, const psignn_plan* res_plan, 
 
 // vjp(w, out): out = J_f(h*)^T w in the solve's numbering.  grad, y, fy, ybest: that numbering too.  res_plan: the plan whose order the
 // solve runs in (the result goes back to the caller's numbering), or NULL.
+// o: {0, 0.5} is the solve without options; anything else keeps corrections in the handle's ring and / or tests the stall ratio
+// (the k_lg_* kernels above).  h_n_aug (may be NULL): the augmentation steps of the solve.
+static const psignn_gmres_opts_t GM_PLAIN = {0, 0.5};
+static int adjoint_opts_check(const char* who, const psignn_gmres* s, const psignn_gmres_opts_t* o) {
+  ARG_CHECK_AS(who, s && o, "NULL argument");
+  ARG_CHECK_AS(who, o->augment >= 0 && o->augment <= s->augment, "augment out of range (0 .. the handle's augment)");
+  ARG_CHECK_AS(who, o->stall > 0.0 && o->stall <= 1.0, "stall must be in (0, 1]");   // (a NaN is not)
+  return PSIGNN_OK;
+}
 template <class F>
 static int adjoint_gmres_loop(psignn_gmres* s, const float* grad, double eps, int max_products, int poll_every, F&& vjp, const AdjWork& w,
                               const psignn_plan* res_plan, float* d_result, psignn_gmres_adjoint_info_t* info, double* h_rel,
-                              double* h_abs, hipStream_t st) {
+                              double* h_abs, hipStream_t st, const psignn_gmres_opts_t& o = GM_PLAIN, int32_t* h_n_aug = nullptr) {
   if (poll_every <= 0) poll_every = 8;
   int rc = adj_prepare(s, max_products);
   if (rc) return rc;
   const unsigned g = (unsigned)s->nblk;
   const int64_t vb = s->M * 4;
+  const int aug = o.augment, nslots = s->augment + 1;
+  const bool plain = aug == 0 && o.stall == 0.5;   // the launches of the solve without options
   k_gm_init<<<4, TB, 0, st>>>(s->st, s->g, s->res_hist, s->m);
   k_ag_init<<<1, 64, 0, st>>>(s->ast);
+  if (!plain) k_lg_init<<<1, 64, 0, st>>>(s->ast);
   for (int cycle = 0;; ++cycle) {
     if (cycle > 0 && (rc = vjp(w.y, w.fy))) return rc;
     PROF_BYTES(cycle ? 4 * vb : 3 * vb);
     VLAUNCH("k_ag_begin", st, s->vec, k_ag_begin, (g, TB, 0, st), s->M, s->ast, w.y, w.fy, grad, s->V, s->part, s->nblk, cycle == 0);
-    LAUNCH("k_ag_check", st, (k_ag_check<<<1, TB, 0, st>>>(s->ast, s->st, s->part, s->nblk, s->g, s->a_rel, s->a_abs, s->a_cap, eps,
-                                                          max_products, s->m)));
+    if (plain)
+      LAUNCH("k_ag_check", st, (k_ag_check<<<1, TB, 0, st>>>(s->ast, s->st, s->part, s->nblk, s->g, s->a_rel, s->a_abs, s->a_cap, eps,
+                                                            max_products, s->m)));
+    else
+      LAUNCH("k_lg_check", st, (k_lg_check<<<1, TB, 0, st>>>(s->ast, s->st, s->part, s->nblk, s->g, s->a_rel, s->a_abs, s->a_cap, eps,
+                                                            max_products, s->m, o.stall, aug)));
     PROF_BYTES(2 * vb);
     VLAUNCH("k_ag_keep", st, s->vec, k_ag_keep, (g, TB, 0, st), s->M, s->ast, w.y, w.ybest);
     VLAUNCH("k_gm_scale", st, s->vec, k_gm_scale, (g, TB, 0, st), s->M, s->V, s->V, &s->ast->rnorm, s->st, 1);
@@ -786,9 +941,27 @@ static int adjoint_gmres_loop(psignn_gmres* s, const float* grad, double eps, in
     HIP_TRY(hipStreamSynchronize(st));
     if (s->h_ast->done) break;
     const int steps = s->h_ast->steps_left;
+    // the cycle's plan and the ring as the check left them (no kept corrections: all Krylov steps)
+    const int nk = aug ? s->h_ast->nk : steps, head = aug ? s->h_ast->head : 0;
+    if (steps < 1 || steps > s->m || nk < 1 || nk > steps || steps - nk > aug || head < 0 || head >= nslots) {
+      psignn_set_error("gmres adjoint: internal: plan of %d Krylov steps out of %d (restart length %d), %d kept, ring head %d of %d", nk,
+                       steps, s->m, aug, head, nslots);
+      return PSIGNN_EHIP;
+    }
+    if (aug && cycle > 0 && s->h_ast->dy_ok) {   // zhat = dy / |dy|: the newest slot still holds the last cycle's dy
+      float* zn = s->Z + (size_t)lgm_slot_newest(head, nslots, 0) * s->ld;
+      PROF_BYTES(2 * vb);
+      VLAUNCH("k_gm_scale", st, s->vec, k_gm_scale, (g, TB, 0, st), s->M, zn, zn, &s->ast->dyn, s->st, 1);
+    }
     for (int j = 0; j < steps; ++j) {
-      if ((rc = vjp(s->V + (size_t)j * s->ld, s->V + (size_t)(j + 1) * s->ld))) return rc;
-      gm_step_launch(s, j, 1.0, 0.5 * eps, &s->ast->steps_left, st);
+      float* wj = s->V + (size_t)(j + 1) * s->ld;
+      const float* src = j < nk ? s->V + (size_t)j * s->ld : s->Z + (size_t)lgm_slot_newest(head, nslots, j - nk) * s->ld;
+      if ((rc = vjp(src, wj))) return rc;
+      if (j >= nk) {
+        PROF_BYTES(3 * vb);
+        VLAUNCH("k_lg_shift", st, s->vec, k_lg_shift, (g, TB, 0, st), s->M, s->st, src, wj);
+      }
+      gm_step_launch(s, j, j < nk ? 1.0 : 0.0, 0.5 * eps, &s->ast->steps_left, st);
       if ((j + 1) % poll_every == 0 && j + 1 < steps) {
         HIP_TRY(hipMemcpyAsync(s->h_st, s->st, sizeof(GmresState), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -796,42 +969,99 @@ static int adjoint_gmres_loop(psignn_gmres* s, const float* grad, double eps, in
       }
     }
     LAUNCH("k_gm_backsolve", st, (k_gm_backsolve<<<1, 64, 0, st>>>(s->st, 0, s->m, s->H, s->g, s->y, s->coef)));
-    VLAUNCH("k_gm_combine", st, s->vec, k_gm_combine, (g, TB, 0, st), s->M, s->ld, s->st, 0, s->V, s->coef, w.y, -1.f, w.y);
+    if (!aug) {
+      VLAUNCH("k_gm_combine", st, s->vec, k_gm_combine, (g, TB, 0, st), s->M, s->ld, s->st, 0, s->V, s->coef, w.y, -1.f, w.y);
+    } else {
+      PROF_BYTES(((int64_t)steps + 3) * vb);
+      VLAUNCH("k_lg_combine", st, s->vec, k_lg_combine, (g, TB, 0, st), s->M, s->ld, s->st, s->ast, s->V, s->Z, nslots, s->coef, w.y,
+              s->part, s->nblk);
+      LAUNCH("k_lg_norm", st, (k_lg_norm<<<1, TB, 0, st>>>(s->ast, s->part, s->nblk, nslots, aug)));
+    }
   }
+  if (h_n_aug) *h_n_aug = plain ? 0 : s->h_ast->n_aug;
   return adjoint_gmres_read_out(s, res_plan, w.ybest, d_result, info, h_rel, h_abs, st);
 }
 
-extern "C" int psignn_gmres_solve_adjoint(psignn_gmres_t* s, const psignn_plan_t* p, const float* W, int nl, const float* h_star,
-                                          const float* prb, const float* nrm, const float* grad, double eps, int max_products,
-                                          int poll_every, float* d_work, float* d_result, psignn_gmres_adjoint_info_t* info,
-                                          double* h_rel, double* h_abs, void* stream) {
-  ARG_CHECK(s && p && W && h_star && prb && grad && d_work, "NULL argument");
-  ARG_CHECK(s->M == p->N * D, "the GMRES handle was made for another vector length than the plan's N * d");
-  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
-  ARG_CHECK(!p->mixed || nrm, "mixed plan needs unit normals");
-  ARG_CHECK(max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
+static int adjoint_direct(const char* who, psignn_gmres_t* s, const psignn_plan_t* p, const float* W, int nl, const float* h_star,
+                          const float* prb, const float* nrm, const float* grad, double eps, int max_products, int poll_every,
+                          const psignn_gmres_opts_t& o, float* d_work, float* d_result, psignn_gmres_adjoint_info_t* info,
+                          int32_t* h_n_aug, double* h_rel, double* h_abs, void* stream) {
+  ARG_CHECK_AS(who, s && p && W && h_star && prb && grad && d_work, "NULL argument");
+  ARG_CHECK_AS(who, s->M == p->N * D, "the GMRES handle was made for another vector length than the plan's N * d");
+  ARG_CHECK_AS(who, nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK_AS(who, !p->mixed || nrm, "mixed plan needs unit normals");
+  ARG_CHECK_AS(who, max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
   hipStream_t st = (hipStream_t)stream;
   const AdjWork w = adj_work(p, nl, d_work);
   AdjointOp op;   // tiled plans: the whole solve in plan order; otherwise the caller's numbering
   int rc = op.setup(p, W, nl, h_star, prb, nrm, grad, ws::Adapter{w.fwork, w.hs_p, w.grad_p, nullptr, w.prbp, w.nrmp}, w.fwork, w.lwork, st);
   if (rc) return rc;
-  return adjoint_gmres_loop(s, op.grad, eps, max_products, poll_every, op, w, op.tiled ? p : nullptr, d_result, info, h_rel, h_abs, st);
+  return adjoint_gmres_loop(s, op.grad, eps, max_products, poll_every, op, w, op.tiled ? p : nullptr, d_result, info, h_rel, h_abs, st, o,
+                            h_n_aug);
+}
+extern "C" int psignn_gmres_solve_adjoint(psignn_gmres_t* s, const psignn_plan_t* p, const float* W, int nl, const float* h_star,
+                                          const float* prb, const float* nrm, const float* grad, double eps, int max_products,
+                                          int poll_every, float* d_work, float* d_result, psignn_gmres_adjoint_info_t* info,
+                                          double* h_rel, double* h_abs, void* stream) {
+  return adjoint_direct(__func__, s, p, W, nl, h_star, prb, nrm, grad, eps, max_products, poll_every, GM_PLAIN, d_work, d_result, info,
+                        nullptr, h_rel, h_abs, stream);
+}
+// The read-out of a solve with options: psignn_gmres_adjoint_info_t's fields plus n_aug
+static void gm_opts_info(const psignn_gmres_adjoint_info_t& i, int32_t n_aug, psignn_gmres_info_t* o) {
+  o->products = i.products;
+  o->cycles = i.cycles;
+  o->stop_reason = i.stop_reason;
+  o->n_reorth = i.n_reorth;
+  o->lowest = i.lowest;
+  o->lowest_abs = i.lowest_abs;
+  o->n_aug = n_aug;
+}
+extern "C" int psignn_gmres_solve_adjoint_opts(psignn_gmres_t* s, const psignn_plan_t* p, const float* W, int nl, const float* h_star,
+                                               const float* prb, const float* nrm, const float* grad, double eps, int max_products,
+                                               int poll_every, const psignn_gmres_opts_t* opts, float* d_work, float* d_result,
+                                               psignn_gmres_info_t* info, double* h_rel, double* h_abs, void* stream) {
+  int rc = adjoint_opts_check(__func__, s, opts);   // (before any launch)
+  if (rc) return rc;
+  psignn_gmres_adjoint_info_t i{};
+  int32_t n_aug = 0;
+  rc = adjoint_direct(__func__, s, p, W, nl, h_star, prb, nrm, grad, eps, max_products, poll_every, *opts, d_work, d_result, &i, &n_aug,
+                      h_rel, h_abs, stream);
+  if (rc == PSIGNN_OK && info) gm_opts_info(i, n_aug, info);
+  return rc;
 }
 
-extern "C" int psignn_gmres_solve_adjoint_lin(psignn_gmres_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad,
-                                              double eps, int max_products, int poll_every, float* d_work, float* d_result,
-                                              psignn_gmres_adjoint_info_t* info, double* h_rel, double* h_abs, void* stream) {
-  ARG_CHECK(s && lin && W && grad && d_work, "NULL argument");
+static int adjoint_lin(const char* who, psignn_gmres_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad, double eps,
+                       int max_products, int poll_every, const psignn_gmres_opts_t& o, float* d_work, float* d_result,
+                       psignn_gmres_adjoint_info_t* info, int32_t* h_n_aug, double* h_rel, double* h_abs, void* stream) {
+  ARG_CHECK_AS(who, s && lin && W && grad && d_work, "NULL argument");
   const psignn_plan* p = psignn_lin_plan(lin);
-  ARG_CHECK(p && s->M == p->N * D, "the GMRES handle was made for another vector length than the linearisation's plan");
-  ARG_CHECK(nl >= 1 && nl <= 64, "n_layers out of range");
-  ARG_CHECK(max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
+  ARG_CHECK_AS(who, p && s->M == p->N * D, "the GMRES handle was made for another vector length than the linearisation's plan");
+  ARG_CHECK_AS(who, nl >= 1 && nl <= 64, "n_layers out of range");
+  ARG_CHECK_AS(who, max_products >= 1 && eps >= 0.0, "max_products >= 1, eps >= 0");
   hipStream_t st = (hipStream_t)stream;
   const AdjWork w = adj_work(p, nl, d_work);
   int rc;
   if ((rc = psignn_plan_permute(p, grad, D, w.grad_p, 1, st))) return rc;
   auto vjp = [&](const float* y, float* out) { return psignn_lin_vjp(lin, W, nl, y, out, w.fwork, st); };
-  return adjoint_gmres_loop(s, w.grad_p, eps, max_products, poll_every, vjp, w, p, d_result, info, h_rel, h_abs, st);
+  return adjoint_gmres_loop(s, w.grad_p, eps, max_products, poll_every, vjp, w, p, d_result, info, h_rel, h_abs, st, o, h_n_aug);
+}
+extern "C" int psignn_gmres_solve_adjoint_lin(psignn_gmres_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad,
+                                              double eps, int max_products, int poll_every, float* d_work, float* d_result,
+                                              psignn_gmres_adjoint_info_t* info, double* h_rel, double* h_abs, void* stream) {
+  return adjoint_lin(__func__, s, lin, W, nl, grad, eps, max_products, poll_every, GM_PLAIN, d_work, d_result, info, nullptr, h_rel, h_abs,
+                     stream);
+}
+extern "C" int psignn_gmres_solve_adjoint_lin_opts(psignn_gmres_t* s, const psignn_lin_t* lin, const float* W, int nl, const float* grad,
+                                                   double eps, int max_products, int poll_every, const psignn_gmres_opts_t* opts,
+                                                   float* d_work, float* d_result, psignn_gmres_info_t* info, double* h_rel,
+                                                   double* h_abs, void* stream) {
+  int rc = adjoint_opts_check(__func__, s, opts);   // (before any launch)
+  if (rc) return rc;
+  psignn_gmres_adjoint_info_t i{};
+  int32_t n_aug = 0;
+  rc = adjoint_lin(__func__, s, lin, W, nl, grad, eps, max_products, poll_every, *opts, d_work, d_result, &i, &n_aug, h_rel, h_abs, stream);
+  if (rc == PSIGNN_OK && info) gm_opts_info(i, n_aug, info);
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -865,7 +1095,7 @@ __global__ __launch_bounds__(TB) void k_ag_check_batch(const GmresBatchDesc* __r
     if (threadIdx.x == 0) d.ast->improved = 0;
     return;
   }
-  ag_check_body(d.ast, d.st, d.part, d.nblk, d.g, d.rel_trace, d.abs_trace, d.cap, eps, max_products, d.m);
+  ag_check_body<false>(d.ast, d.st, d.part, d.nblk, d.g, d.rel_trace, d.abs_trace, d.cap, eps, max_products, d.m, 0.5, 0);
 }
 template <int VEC>
 __global__ __launch_bounds__(TB) void k_ag_keep_batch(const GmresBatchDesc* __restrict__ descs) {

@@ -993,6 +993,23 @@ def check_bw_gmres_lockstep(value, bw_solver):
     return value
 
 
+def check_bw_gmres_aug(augment, stall, bw_solver, m):
+    """The ``bw_gmres_augment`` / ``bw_gmres_stall`` config values as ``(int, float)`` (None: the default, 0 / 0.5): corrections the
+    GMRES adjoint solve keeps between restart cycles, an int in 0..min(``m`` - 1, 8) with ``m`` = ``bw_gmres_m``, and its stall ratio,
+    a float in (0, 1] (``DeviceGmresAug.solve_adjoint``).  Both need ``bw_solver = "gmres"``: NativeError naming the keys otherwise.
+    A host check: nothing is allocated."""
+    if bw_solver != "gmres":
+        raise nat.NativeError(f'bw_gmres_augment / bw_gmres_stall need bw_solver = "gmres" (bw_solver is {bw_solver!r})')
+    a = 0 if augment is None else augment
+    if isinstance(a, bool) or not isinstance(a, int) or not 0 <= a <= min(int(m) - 1, AUGMENT_MAX):
+        raise nat.NativeError(f"bw_gmres_augment must be an int in 0..min(bw_gmres_m - 1, {AUGMENT_MAX}) = "
+                              f"{min(int(m) - 1, AUGMENT_MAX)}, got {augment!r}")
+    st = 0.5 if stall is None else stall
+    if isinstance(st, bool) or not isinstance(st, (int, float)) or not 0.0 < float(st) <= 1.0:   # (a NaN is not)
+        raise nat.NativeError(f"bw_gmres_stall must be a float in (0, 1], got {stall!r}")
+    return a, float(st)
+
+
 def check_lin_neumann(value):
     """``"direct"`` / ``"stored"`` as given; ValueError for anything else (a host check: nothing is allocated)."""
     if not isinstance(value, str) or value not in LIN_NEUMANN:
@@ -1718,6 +1735,68 @@ class DeviceGmres:
         return list(h)
 
 
+class DeviceGmresAug(DeviceGmres):
+    """``DeviceGmres`` whose adjoint solves take augmented restarts (LGMRES) and a settable stall ratio (``psignn_gmres_create_aug``,
+    ``psignn_gmres_solve_adjoint_opts`` / ``_lin_opts``; the method: the header of csrc/krylov_f64.hip, here with fp32 vectors).  The
+    ring of ``augment + 1`` rows beside the basis is a torch tensor, like the basis; a solve keeps the ``augment`` newest corrections
+    of its cycles and searches them in the last steps of the next cycle.  ``stall``: the solve ends on a cycle with ``not rel <=
+    stall * prev_rel``; 0.5 is ``DeviceGmres``'s rule, 1.0 stops only when a cycle does not lower ``rel``.  ``augment=0, stall=0.5``
+    launches the kernels of ``DeviceGmres`` and gives its bits.  A class of its own because the signatures of ``DeviceGmres`` are
+    pinned.  The lockstep solve (``gmres_solve_adjoint_batch``) takes no options."""
+
+    def __init__(self, n_elems, device, m_max, augment=0, shard_elems=None):
+        self.augment = check_augment(augment, m_max, "DeviceGmresAug")
+        self.M, self.m, self.device = int(n_elems), int(m_max), device
+        self.shard_elems = None if shard_elems is None else int(shard_elems)
+        if self.shard_elems is not None and self.shard_elems < self.M:
+            raise nat.NativeError(f"DeviceGmresAug: shard_elems is the summed length of the shard, at least n_elems = {self.M}, "
+                                  f"got {shard_elems}")
+        self.ld = (self.M + 63) // 64 * 64
+        self.V = torch.empty((self.m + 1, self.ld), dtype=torch.float32, device=device)
+        self.Z = torch.zeros((self.augment + 1, self.ld), dtype=torch.float32, device=device) if self.augment else None
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            nat.check(nat.lib().psignn_gmres_create_aug(C.byref(h), self.M, self.ld, self.m, nat.ptr(self.V), self.augment,
+                                                        nat.ptr(self.Z), self.shard_elems or 0), "psignn_gmres_create_aug")
+        self.handle = h
+        self._fin = weakref.finalize(self, nat.lib().psignn_gmres_destroy, h)
+
+    @property
+    def nbytes(self):
+        """``DeviceGmres.nbytes`` plus the ring."""
+        return DeviceGmres.nbytes.fget(self) + (self.Z.numel() * 4 if self.Z is not None else 0)
+
+    def solve_adjoint(self, fmap, h_star, grad, eps, max_products, lin=None, poll_every=8, augment=None, stall=0.5):
+        """``DeviceGmres.solve_adjoint`` with ``augment`` (None: the handle's) and ``stall``.  The dict gains ``n_aug`` (the
+        augmentation steps of the solve) and ``augment``."""
+        opts = gmres64_opts(augment, stall, self.augment, "DeviceGmresAug.solve_adjoint", nat.GmresOpts)
+        nat.require_default_width(getattr(fmap, "width", D), "solve_adjoint")
+        plan, nl = fmap.plan, fmap.weights.n_layers
+        if plan.N * D != self.M:
+            raise nat.NativeError(f"DeviceGmresAug of {self.M} elements was handed a map of {plan.N * D}")
+        hs, gr = _f32c(h_star), _f32c(grad)
+        result = torch.empty_like(gr)
+        info = nat.GmresInfo()
+        cap = int(max_products) // 2 + 3
+        rel, abs_ = (C.c_double * cap)(), (C.c_double * cap)()
+        lib = nat.lib()
+        with torch.cuda.device(self.device):
+            self._workspace(plan, nl)
+            if lin is not None:
+                nat.check(lib.psignn_gmres_solve_adjoint_lin_opts(
+                    self.handle, lin.handle, nat.ptr(fmap.weights.flat), nl, nat.ptr(gr), float(eps), int(max_products),
+                    int(poll_every), C.byref(opts), nat.ptr(self._work), nat.ptr(result), C.byref(info), rel, abs_, self._sp()),
+                    "psignn_gmres_solve_adjoint_lin_opts")
+            else:
+                nat.check(lib.psignn_gmres_solve_adjoint_opts(
+                    self.handle, plan.handle, nat.ptr(fmap.weights.flat), nl, nat.ptr(hs), nat.ptr(fmap.prb), nat.ptr(fmap.nrm),
+                    nat.ptr(gr), float(eps), int(max_products), int(poll_every), C.byref(opts), nat.ptr(self._work), nat.ptr(result),
+                    C.byref(info), rel, abs_, self._sp()), "psignn_gmres_solve_adjoint_opts")
+        out = self._result(info, rel, abs_, result)
+        out["n_aug"], out["augment"] = int(info.n_aug), int(opts.augment)
+        return out
+
+
 def gmres_adjoint_batchable(solvers, lins) -> bool:
     """Whether ``gmres_solve_adjoint_batch`` takes these ``DeviceGmres`` handles and linearisations together
     (``psignn_gmres_adjoint_batchable``): one vector width and one restart length, every ``lins[i]`` built and of a form the batched
@@ -2291,16 +2370,17 @@ class DeviceGmres64:
 AUGMENT_MAX = 8   # psignn_gmres64_create_aug
 
 
-def gmres64_opts(augment, stall, handle_augment, who):
+def gmres64_opts(augment, stall, handle_augment, who, struct=None):
     """The checked ``psignn_gmres64_opts_t`` of one solve: ``augment`` (None: the handle's) in ``0 .. handle_augment``, ``stall`` in
-    ``(0, 1]``.  Raises ``NativeError`` before any native call."""
+    ``(0, 1]``.  Raises ``NativeError`` before any native call.  ``struct``: another structure of the same two fields
+    (``nat.GmresOpts`` of the fp32 solver)."""
     a = int(handle_augment if augment is None else augment)
     if not 0 <= a <= int(handle_augment):
         raise nat.NativeError(f"{who}: augment must be in 0 .. {int(handle_augment)} (the handle's), got {augment}")
     st = float(stall)
     if not 0.0 < st <= 1.0:   # (a NaN is not)
         raise nat.NativeError(f"{who}: stall must be in (0, 1], got {stall}")
-    return nat.Gmres64Opts(a, st)
+    return (nat.Gmres64Opts if struct is None else struct)(a, st)
 
 
 def check_augment(augment, m, who):

@@ -30,6 +30,12 @@ Drop-in for ``tests/model_psignn.py`` (``ModelPSIGNN``, ``ModelPSIGNNIterative``
   otherwise): the replicas of a list call take the lockstep route with the GMRES adjoint solve -- forward solves through
   ``engine.broyden_solve_batch``, the R adjoint systems through ``engine.gmres_solve_adjoint_batch`` -- where
   ``DeepEquilibrium.lockstep_applies`` says yes; without it replicas with ``bw_solver = "gmres"`` are solved one after the other.
+  Two optional keys ``"bw_gmres_augment"`` (int in 0..min(``bw_gmres_m`` - 1, 8), default 0) and ``"bw_gmres_stall"`` (float in
+  (0, 1], default 0.5), both needing ``bw_solver = "gmres"`` (``NativeError`` naming the keys otherwise): the GMRES adjoint solve keeps
+  that many corrections between restart cycles (LGMRES) and ends on a cycle with ``not rel <= stall * prev_rel``
+  (``engine.DeviceGmresAug.solve_adjoint``); with both at their defaults the objects, launches and bits are those without the keys.
+  With a non-default value ``last_backward`` carries ``n_aug``, and the replicas of a list call are solved one after the other whatever
+  ``bw_gmres_lockstep`` says (``DeepEquilibrium.lockstep_applies`` says no: the lockstep GMRES takes no options).
   An optional key ``"fp_lockstep"`` (bool, default False; True needs ``solver`` = ``utilities.solver.anderson`` or
   ``forward_iteration``, ``NativeError`` naming both keys otherwise): the forward solves of a shard -- ``batch.solve_shard_batched``,
   the replicas of a list call -- run in one lockstep Anderson / Picard solve (``utilities.solver.anderson_batch`` /
@@ -442,13 +448,16 @@ class DeepEquilibrium(nn.Module):
 
     def lockstep_applies(self, fmaps):
         """Whether R replicas go through the batched solvers: a host-side decision on the bound maps, before anything is
-        allocated.  No: a solver other than ``utilities.solver.broyden``, ``bw_solver = "gmres"`` without ``bw_gmres_lockstep``, an
+        allocated.  No: a solver other than ``utilities.solver.broyden``, ``bw_solver = "gmres"`` without ``bw_gmres_lockstep`` or with
+        a non-default ``bw_gmres_augment`` / ``bw_gmres_stall``, an
         untiled plan, ``n_layers > 1``, a bf16 pair history, both families in one call, a mixed plan without
         ``lin_neumann = "stored"``.  (Solvers of one call share one size class by construction: all are sized for the whole shard.)"""
         if self.config_deq["solver"] is not _solver.broyden or self.history_dtype() != torch.float32:
             return False
         if self.config_deq.get("bw_solver") is not None and not self.config_deq.get("bw_gmres_lockstep"):
             return False   # the GMRES adjoint solve takes its lockstep form only with the key (decided before the maps are looked at)
+        if self._bw_gmres_opts() is not None:
+            return False   # kept corrections / another stall ratio: the lockstep GMRES takes no options
         if any(not f.plan.tiled or f.weights.n_layers != 1 or not f.can_linearize() for f in fmaps):
             return False
         if any(bool(f.plan.mixed) != bool(fmaps[0].plan.mixed) for f in fmaps):
@@ -550,12 +559,19 @@ class DeepEquilibrium(nn.Module):
             return linearize
         return bool(self.config_deq.get("bw_linearize", False)) if linearize is None else bool(linearize)
 
+    def _bw_gmres_opts(self):
+        """``(augment, stall)`` of the GMRES adjoint solve when ``bw_gmres_augment`` / ``bw_gmres_stall`` hold a non-default value,
+        else None (the solve without options)."""
+        a, st = int(self.config_deq.get("bw_gmres_augment", 0)), float(self.config_deq.get("bw_gmres_stall", 0.5))
+        return None if a == 0 and st == 0.5 else (a, st)
+
     def implicit_backward(self, H_star, H_init, batch, grad):
         """Solve y = J_f(H*)^T y + grad with the configured solver (the reference's backward hook, model.py:210-223):
         returns the solver dict; ``out["result"]`` is the gradient w.r.t. the fixed point's input.  With ``bw_linearize``
         the map is the transposed product of one linearisation of f at H* (where ``fmap.can_linearize()``).  With
         ``bw_solver = "gmres"`` the system is solved by restarted GMRES instead (``engine.DeviceGmres.solve_adjoint``, restart
-        length ``bw_gmres_m``): ``bw_tol`` is its tolerance, ``bw_thres`` its budget of transposed products."""
+        length ``bw_gmres_m``): ``bw_tol`` is its tolerance, ``bw_thres`` its budget of transposed products.  With a non-default
+        ``bw_gmres_augment`` / ``bw_gmres_stall`` the solve is ``engine.DeviceGmresAug.solve_adjoint`` and the dict carries ``n_aug``."""
         nat.require_default_width(self.f.latent_dim, "implicit_backward")
         fmap = self.f.bind(H_init, batch)
         g = grad.contiguous()
@@ -563,6 +579,19 @@ class DeepEquilibrium(nn.Module):
         if self.config_deq.get("bw_solver") == "gmres":   # opt-in: the linear system by restarted GMRES, whatever config["solver"] is
             # handle and basis ((m + 1) * N * d floats) are kept between calls on the same plan, like the Broyden adjoint solver's state
             m = int(self.config_deq.get("bw_gmres_m", 50))
+            opts = self._bw_gmres_opts()
+            if opts is not None:   # kept corrections and / or another stall ratio: a handle with a ring, keyed by its size too
+                key = (fmap.plan, m, opts[0], "aug")
+                old = getattr(self, "_bw_gmres_key", None)
+                if old is None or len(old) != 4 or old[0] is not key[0] or old[1:] != key[1:]:
+                    if getattr(self, "_bw_gmres", None) is not None:
+                        self._bw_gmres.close()
+                    self._bw_gmres = engine.DeviceGmresAug(fmap.plan.N * engine.D, fmap.plan.device, m, augment=opts[0])
+                    self._bw_gmres_key = key
+                out = self._bw_gmres.solve_adjoint(fmap, H_star, g, self.config_deq["bw_tol"], self.config_deq["bw_thres"], lin=lin,
+                                                   augment=opts[0], stall=opts[1])
+                out.update(eps=self.config_deq["bw_tol"], threshold=self.config_deq["bw_thres"])
+                return out
             key = (fmap.plan, m)
             old = getattr(self, "_bw_gmres_key", None)
             if old is None or len(old) != 2 or old[0] is not key[0] or old[1] != m:
@@ -641,7 +670,7 @@ class DeepEquilibrium(nn.Module):
         return from_p(ev), val.abs()
 
 
-for _name in ("history_dtype", "_linearization", "_linearize_default", "implicit_backward"):   # (implicit_backward: both bw_solver routes)
+for _name in ("history_dtype", "_linearization", "_linearize_default", "_bw_gmres_opts", "implicit_backward"):   # (implicit_backward: both bw_solver routes)
     setattr(_ReplicaSlot, _name, getattr(DeepEquilibrium, _name))
 del _name
 
@@ -676,6 +705,13 @@ class _Base(nn.Module):
         if "bw_gmres_lockstep" in self.config:   # optional: replicas with bw_solver = "gmres" solve their adjoint systems in lockstep
             self.config_deq["bw_gmres_lockstep"] = engine.check_bw_gmres_lockstep(self.config["bw_gmres_lockstep"],
                                                                                  self.config.get("bw_solver"))   # (NativeError otherwise)
+        if "bw_gmres_augment" in self.config or "bw_gmres_stall" in self.config:   # optional: LGMRES restarts / the stall ratio of the GMRES adjoint solve
+            a, st = engine.check_bw_gmres_aug(self.config.get("bw_gmres_augment"), self.config.get("bw_gmres_stall"),
+                                              self.config.get("bw_solver"), self.config_deq.get("bw_gmres_m"))   # (NativeError otherwise)
+            if "bw_gmres_augment" in self.config:
+                self.config_deq["bw_gmres_augment"] = a
+            if "bw_gmres_stall" in self.config:
+                self.config_deq["bw_gmres_stall"] = st
         if "fp_lockstep" in self.config:   # optional: shards solved by anderson / forward_iteration run in lockstep
             self.config_deq["fp_lockstep"] = engine.check_fp_lockstep(self.config["fp_lockstep"], self.config["solver"],
                                                                      (_solver.anderson, _solver.forward_iteration))   # (NativeError otherwise)
